@@ -22,16 +22,30 @@ resident in HBM.  One process per GPU; ranks work on independent reference
 views (weak scaling, no data-path collective).
 
     python bench.py --gpus N --steps K --warmup W [--repeats R] [--config 1|5]
+                    [--dump-outputs DIR] [--full]
 
 With N > 1 and no torch.distributed environment the script re-executes itself
 under `python -m torch.distributed.run` with N ranks on 127.0.0.1.  After W
 warm-up steps the K-step region (barrier + device synchronisation on both
-sides, time = max over ranks) is measured R times; `value` / `ms_per_step` are
-the MEDIAN repeat, min and max are in "timing".
+sides, time = max over ranks) is measured R times (default 1, so that K is the
+number of timed steps); `value` / `ms_per_step` are the MEDIAN repeat, min and
+max are in "timing".
+
+A plain run does only what the headline needs: set-up, warm-up, the timed
+steps, the outputs (--dump-outputs) and the result line.  --full adds what the
+benchmark measures or checks besides: the replay checked against the
+optimize() it was recorded from, the roofline (its own profiled pass and the
+peak microbenchmarks), the secondary workloads, the CPU baseline, the RCCL
+round and checks and, with N > 1, whole views per second over the GPUs.
+
+--dump-outputs DIR writes what the timed path computed in its last step, as a
+caller of that path receives it, to DIR/<name>.npy (float32 / float64, at most
+64 MB in all; rank 0's view): per replayed batch the nodes after its Newton
+loop and its final active set, and the loop statistics of every batch.
 
 --workload newton_steps is the headline of rounds 1-5 (the scale-2 loop of the
 same view replayed from a perturbed start surface; a step = one Newton step):
-now `secondary.scale2_replay` of the default run.
+now `secondary.scale2_replay` of a --full run.
 
 --config 5 (BASELINE.json configs[4]): every rank holds --views-per-rank
 reference views (64 over 8 GPUs), shading-aware (-S): per view the
@@ -152,6 +166,7 @@ class LoopReplay:
             L["patches"] = geom[2] * geom[3]
         self.stats = _capi.LoopStats()
         self.check = _capi.check
+        self.last_pass = []
 
     def run_loop(self, L):
         C = self.C
@@ -162,12 +177,35 @@ class LoopReplay:
         return s.newton_steps, s.active_patch_steps, s.linear_iterations
 
     def run_pass(self):
-        """-> (active patch-steps, CG iterations, Newton steps) of one pass."""
+        """-> (active patch-steps, CG iterations, Newton steps) of one pass;
+        the statistics of every loop stay in last_pass."""
         ps = its = ns = 0
+        last = []
         for L in self.loops:
             n, p, i = self.run_loop(L)
             ns += n; ps += p; its += i
+            last.append((n, i, p, self.stats.final_active_nodes, self.stats.nan_break))
+        self.last_pass = last
         return ps, its, ns
+
+    def outputs(self):
+        """What the last pass left, as smvs_gn_run_loop's caller receives it:
+        per batch the nodes (f, dx, dy, dxy) and the final active set, and per
+        batch (newton_steps, linear_iterations, active_patch_steps,
+        final_active_nodes, nan_break)."""
+        C = self.C
+        out = {"loop_stats": np.array(self.last_pass, dtype=np.float64)}
+        for b, L in enumerate(self.loops):
+            nodes = np.zeros((L["nodes"], 4))
+            self.check(self.lib.smvs_get_nodes(L["handle"], nodes.ctypes.data_as(
+                C.POINTER(C.c_double))))
+            active = np.zeros(L["nodes"], dtype=np.uint8)
+            n_active = C.c_int(0)
+            self.check(self.lib.smvs_get_active(L["handle"], active.ctypes.data_as(
+                C.POINTER(C.c_uint8)), C.byref(n_active)))
+            out["batch%02d_scale%d_nodes" % (b, L["scale"])] = nodes
+            out["batch%02d_scale%d_active" % (b, L["scale"])] = active.astype(np.float32)
+        return out
 
     def verify(self):
         """The replay is the optimize() it was recorded from: per batch the
@@ -209,6 +247,27 @@ class LoopReplay:
         for L in self.loops:
             self.lib.smvs_ctx_destroy(L["handle"])
         self.loops = []
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float64 kept, anything
+    else as float32.  Should they exceed 64 MB in all, each array is cut to the
+    same fixed, seeded sample of its rows (the sample depends on the shapes
+    alone, so two builds of the project are compared row for row)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64
+                                      else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, DUMP_LIMIT_BYTES / max(total, 1))
+    for name, a in sorted(arrays.items()):
+        if frac < 1.0 and a.ndim > 0 and a.shape[0] > 1:
+            k = max(1, int(a.shape[0] * frac))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def patch_flops_table():
@@ -888,6 +947,15 @@ def optimize_workload(args):
         aps += sum(e["active_patch_steps"] for e in r["log"])
         loop_s += sum(e["loop_seconds"] for e in r["log"])
     wall = time.perf_counter() - t0
+    if args.dump_outputs:
+        arrays = dict(depth=r["depth"], normals=r["normals"],
+                      batch_log=np.array([[e["scale"], e["iter"], e["newton_steps"],
+                                           e["valid_patches"], e["cg_iterations"],
+                                           e["active_patch_steps"]] for e in r["log"]],
+                                         dtype=np.float64))
+        if r["lighting"] is not None:
+            arrays["lighting"] = r["lighting"]
+        dump_outputs(args.dump_outputs, arrays)
     print(json.dumps({
         "metric": "Gauss-Newton iters/sec x active patches over all Newton loops of optimize(), "
                   "1920x1080 ref view, 8 neighbours",
@@ -908,7 +976,7 @@ def scale2_replay(args):
     """`--workload newton_steps` in a child process: the headline of rounds
     1-5 (scale-2 Newton steps from a perturbed start surface)."""
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "newton_steps",
-           "--steps", "20", "--warmup", "5", "--repeats", "30", "--no-cpu-baseline",
+           "--steps", "20", "--warmup", "5", "--repeats", "30", "--full", "--no-cpu-baseline",
            "--no-secondary", "--no-peaks"]
     if args.small:
         cmd.append("--small")
@@ -945,8 +1013,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=100,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="how often the K-step region is measured (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the replay check, the roofline and peaks, the "
+                         "secondary workloads, the CPU baseline, the RCCL round and checks and "
+                         "(N > 1) whole views over the GPUs; the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the timed path computed in its last step to "
+                         "DIR/<name>.npy (rank 0)")
     ap.add_argument("--config", type=int, default=1, choices=(1, 5),
                     help="1: BASELINE configs[1] (headline); 5: configs[4], views sharded "
                          "over the GPUs, shading-aware")
@@ -972,7 +1047,7 @@ def main():
                          "replayed from their recorded start states (a step = one pass over "
                          "them); newton_steps: the scale-2 loop replayed from a perturbed start "
                          "surface (a step = one Newton step; the headline of rounds 1-5, "
-                         "secondary.scale2_replay of the default run); optimize: --steps whole "
+                         "secondary.scale2_replay of a --full run); optimize: --steps whole "
                          "optimize() calls timed by the C++ loop timers (secondary.optimize)")
     ap.add_argument("--views-worker", action="store_true",
                     help="internal: one process of the multi-GPU views workload")
@@ -1044,7 +1119,8 @@ def main():
         # optimize()'s batch log
         w, h = (480, 270) if args.small else (W, H)
         replay = LoopReplay(scene_inputs(rank, args.small), device=local_rank)
-        replay.verify()
+        if args.full:
+            replay.verify()
         replay_log = list(replay.log)
         surf = None
     else:
@@ -1151,11 +1227,21 @@ def main():
     repeats.sort(key=lambda r: r[0])
     value, secs, units, cg_total = repeats[len(repeats) // 2]
 
+    if rank == 0 and args.dump_outputs:
+        if replay is not None:
+            arrays = replay.outputs()
+        else:
+            arrays = {}
+            for v, c in enumerate(ctxs):
+                arrays["view%d_nodes" % v] = c.get_nodes()
+                arrays["view%d_active" % v] = c.get_active()[0]
+        dump_outputs(args.dump_outputs, arrays)
+
     roof = None
-    if rank == 0 and replay is not None:
+    if rank == 0 and args.full and replay is not None:
         roof = loops_roofline(replay, args.steps, 1e3 * secs / args.steps,
                               with_peaks=not args.no_peaks)
-    elif rank == 0:
+    elif rank == 0 and args.full:
         lighting = fit_lighting([ctx])[0] if args.config == 5 else None
         if args.config == 5:
             ctx.set_nodes(surf["nodes"])
@@ -1165,7 +1251,7 @@ def main():
     # --shared-lighting: what one RCCL round of the lighting normal equations
     # costs (2,176 bytes all-reduced in place on the device buffers)
     rccl_round = None
-    if native is not None:
+    if native is not None and args.full:
         try:
             ctx.light_accumulate_dev()
             barrier()
@@ -1190,7 +1276,8 @@ def main():
     rccl_proof = None
     proof_hung = False
     # (not in the one-GPU rehearsal over gloo: RCCL refuses ranks that share a device)
-    if world > 1 and backend == "nccl" and os.environ.get("SMVS_BENCH_NO_RCCL_PROOF", "") == "":
+    if args.full and world > 1 and backend == "nccl" \
+            and os.environ.get("SMVS_BENCH_NO_RCCL_PROOF", "") == "":
         import threading
         box = {}
 
@@ -1262,7 +1349,7 @@ def main():
     # of the run); the CPU baseline forks one oracle process per view, so it
     # runs afterwards in a child process that never loads the HIP runtime.
     secondary = cpu = None
-    if world > 1 or args.config == 5:
+    if args.full and (world > 1 or args.config == 5):
         secondary = {}
         if rccl_round is not None:
             secondary["rccl_lighting_round"] = rccl_round
@@ -1278,7 +1365,7 @@ def main():
         secondary["scaling_note"] = ("the headline scales by construction (independent "
                                      "views, no data-path collective); views_per_s is the "
                                      "whole per-view task whose host side can fail to scale")
-    if world == 1 and args.config == 1:
+    if args.full and world == 1 and args.config == 1:
         if not args.no_secondary:
             try:
                 secondary = secondary_workloads(args)
@@ -1314,7 +1401,7 @@ def main():
                            len(replay_log), ns,
                            sum(e["active_patch_steps"] for e in replay_log)))
             config_extra = dict(batches_per_step=len(replay_log), newton_steps_per_step=ns,
-                                replay_verified_against_optimize_log=True)
+                                replay_verified_against_optimize_log=args.full)
         else:
             workload = ("configs[1]: %dx%d synthetic textured sphere, 1 ref + %d neighbours, "
                         "-o2 (scale 2, %d patches), basic photometric optimizer, %s"

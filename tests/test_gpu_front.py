@@ -733,7 +733,7 @@ def test_bench_two_ranks_on_the_logical_devices_of_one_gpu(hip, tmp_path):
     env = dict(os.environ, SMVS_DEVICE_MAP="0,0", SMVS_BENCH_DIST_BACKEND="gloo",
                SMVS_LOCK_DIR=str(tmp_path))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--small", "--steps",
-           "4", "--warmup", "1", "--repeats", "2", "--views-per-rank", "3"]
+           "4", "--warmup", "1", "--repeats", "2", "--views-per-rank", "3", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=root, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.strip().startswith("{")][-1])
@@ -856,7 +856,7 @@ def test_bench_contract_small(hip):
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--small", "--steps", "3",
-           "--warmup", "1", "--repeats", "2", "--no-cpu-baseline", "--no-peaks"]
+           "--warmup", "1", "--repeats", "2", "--full", "--no-cpu-baseline", "--no-peaks"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -901,6 +901,43 @@ def test_bench_contract_small(hip):
     assert "optimize" in line["config"]["workload"]
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(hip, tmp_path):
+    """A plain bench.py run (no --full): set-up, warm-up, exactly --steps timed
+    steps, nothing measured or checked besides, and with --dump-outputs what the
+    last timed pass computed -- per replayed batch the nodes and the active set,
+    and the loop statistics, whose units are the headline's."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--small", "--steps", "3",
+           "--warmup", "1", "--dump-outputs", str(out_dir)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, res.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["timing"]["repeats"] == 1
+    assert out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["secondary"] is None
+    cfg = out["config"]
+    files = sorted(os.listdir(str(out_dir)))
+    nodes = [f for f in files if f.endswith("_nodes.npy")]
+    active = [f for f in files if f.endswith("_active.npy")]
+    assert len(nodes) == len(active) == cfg["batches_per_step"]
+    arrays = {f: np.load(str(out_dir / f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    stats = arrays["loop_stats.npy"]
+    assert stats.shape == (cfg["batches_per_step"], 5)
+    assert stats[:, 0].sum() == cfg["newton_steps_per_step"]
+    units = stats[:, 2].sum()
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - units) < 1e-6 * units
+    for f in nodes:
+        a = arrays[f]
+        assert a.ndim == 2 and a.shape[1] == 4 and np.isfinite(a).all()
+        assert arrays[f.replace("_nodes", "_active")].shape == (a.shape[0],)
+
+
 def test_bench_contract_value_optimize_and_traffic_source(hip):
     """The honesty fields: `value_optimize` (the same region timed in place by
     the C++ loop timers) at the top level beside the headline, the committed
@@ -909,7 +946,7 @@ def test_bench_contract_value_optimize_and_traffic_source(hip):
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--small", "--steps", "3",
-           "--warmup", "1", "--repeats", "2"]
+           "--warmup", "1", "--repeats", "2", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.strip()][-1])
@@ -936,8 +973,8 @@ def test_bench_newton_steps_workload_is_still_there(hip):
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--small", "--workload", "newton_steps",
-           "--steps", "3", "--warmup", "1", "--repeats", "2", "--no-cpu-baseline", "--no-peaks",
-           "--no-secondary"]
+           "--steps", "3", "--warmup", "1", "--repeats", "2", "--full", "--no-cpu-baseline",
+           "--no-peaks", "--no-secondary"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.strip()][-1])
@@ -957,7 +994,7 @@ def test_bench_config5_runs_whole_views_in_child_processes(hip):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--small", "--config", "5",
            "--views-per-rank", "2", "--shared-lighting", "--steps", "4", "--warmup", "1",
-           "--repeats", "2", "--no-peaks", "--no-cpu-baseline"]
+           "--repeats", "2", "--full", "--no-peaks", "--no-cpu-baseline"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -1061,7 +1098,7 @@ def test_bench_two_gpus_reports_whole_views(hip):
         pytest.skip("needs 2 GPUs (the driver's multi-GPU node)")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--small", "--steps",
-           "4", "--warmup", "1", "--repeats", "2", "--views-per-rank", "3"]
+           "4", "--warmup", "1", "--repeats", "2", "--views-per-rank", "3", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.strip().startswith("{")][-1])

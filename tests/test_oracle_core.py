@@ -2,8 +2,9 @@
 
 * the known-answer values of tests/gtest_bicubic_patch.cc and
   tests/gtest_matrix_vector.cc (tests/golden/reference_known_answers.json);
-* the reference's own ldl_inverse compiled from /root/reference
-  (oracle/_ref/libref_ldl.so), bit for bit;
+* the reference's own ldl_inverse, bit for bit: its outputs stored in
+  tests/golden/reference_ldl_inverse.npz (and oracle/_ref/libref_ldl.so where
+  the reference tree was there to build it);
 * the finite-difference identities the reference's gtest files assert for
   Correspondence, surface_derivative, spherical_harmonics and the bicubic
   basis table (tests/gtest_correspondence.cc, gtest_surface_deriv.cc,
@@ -17,6 +18,7 @@ import pytest
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden",
                       "reference_known_answers.json")
+REF_LDL = os.path.join(os.path.dirname(__file__), "golden", "reference_ldl_inverse.npz")
 KIND = {"f": 0, "dx": 1, "dy": 2, "dxy": 3, "dxx": 4, "dyy": 5}
 
 
@@ -52,21 +54,19 @@ def test_ldl_known_answer(oracle, known):
 
 
 def test_ldl_matches_reference_build_bitwise(oracle):
-    if oracle.ref_ldl() is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    rng = np.random.default_rng(1)
-    for n in (2, 3, 4, 7, 16):
-        for _ in range(20):
-            B = rng.normal(size=(n, n))
-            A = B @ B.T + 0.1 * np.eye(n)
-            mine = oracle.ldl_inverse(A)
-            ref = oracle.ref_ldl_inverse(A)
-            assert np.array_equal(mine, ref)
-    # zero pivot: both leave the input untouched (ldl_decomposition.h:60-61)
-    Z = np.zeros((4, 4))
-    assert np.array_equal(oracle.ldl_inverse(Z), oracle.ref_ldl_inverse(Z))
-    S = np.array([[1.0, 1, 0, 0], [1, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]])
-    assert np.array_equal(oracle.ldl_inverse(S), oracle.ref_ldl_inverse(S))
+    """Against the outputs of the reference's own ldl_inverse, stored in
+    tests/golden/reference_ldl_inverse.npz (100 SPD matrices of sizes 2 .. 16;
+    a zero and a singular 4 x 4, which both leave untouched,
+    ldl_decomposition.h:60-61); where oracle/_ref was built, also against the
+    live reference build."""
+    ref = np.load(REF_LDL)
+    for key in sorted(k for k in ref.files if k.startswith("A_")):
+        want = ref["inverse_" + key[2:]]
+        for A, W in zip(ref[key], want):
+            assert np.array_equal(oracle.ldl_inverse(A), W), key
+            if oracle.ref_ldl() is not None:
+                assert np.array_equal(oracle.ref_ldl_inverse(A), W), key
+    assert sum(len(ref[k]) for k in ref.files if k.startswith("A_")) == 102
 
 
 def test_vec_dot_known_answer(oracle, known):

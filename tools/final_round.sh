@@ -12,10 +12,10 @@ tail -3 gpurun_out/${R}_collect.log
 cp gpurun_out/prof_${R}/summary/traffic_${R}.json profiles/ 2>/dev/null
 # the batch logs of the whole-optimize() parity tests, device / oracle, one table
 cat gpurun_out/units_*.txt > gpurun_out/${R}_parity_units.txt 2>/dev/null
-timeout 900 python bench.py > gpurun_out/${R}_bench_default.json 2> gpurun_out/${R}_bench_default.err
+timeout 900 python bench.py --full --repeats 100 > profiles/${R}_bench_default.json
 python - <<PY
 import json
-d = json.load(open("gpurun_out/${R}_bench_default.json"))
+d = json.load(open("profiles/${R}_bench_default.json"))
 print("bench", d["value"], d["ms_per_step"], d["roofline"]["kernel"], d["roofline"]["frac"], d["cpu_baseline"]["value"])
 print({k: v for k, v in d["secondary"]["views_per_s"]["per_gpu"].items()} if "views_per_s" in d.get("secondary", {}) else d.get("secondary"))
 PY
