@@ -523,6 +523,60 @@ typedef struct {
 
 int smvs_cut_depth_maps(int device, smvs_mesh_view *views, int n_views);
 
+/* The point cloud of MeshGenerator::generate_mesh, mesh_generator.cc:160-299
+ * (the default path of smvsrecon, app/smvsrecon.cc:278-343): per view
+ * DepthTriangulator::full_triangulation (mve::geom::depthmap_triangulate),
+ * depthmap_mesh_confidences(m, 4), the scale value (:252-262) and the normal
+ * lookup (:264-276), merged in view-list order; optionally clipped to an AABB
+ * (smvsrecon.cc:306-319).  The semantics pinned for the MVE pieces are the
+ * [MVE-unverified] table of DESIGN.md section 9.
+ *   depth / normals : as smvs_mesh_view, but read only
+ *   image           : width*height*channels bytes (the colour embedding at
+ *                     the depth map's size; 1 channel = grey)
+ *   cut_depth       : optional out (may be NULL): the map that was
+ *                     triangulated -- the "smvs-cut" embedding (:222-226)
+ *                     when cutting, else the input depth */
+typedef struct {
+    int width, height;
+    float flen;
+    float rot[9], trans[3];
+    const float *depth;
+    const float *normals;
+    const uint8_t *image;
+    int channels;
+    float *cut_depth;
+} smvs_point_view;
+
+typedef struct {
+    int cut_surfaces;     /* MeshGenerator::Options::cut_surfaces (--no-cut: 0) */
+    int use_aabb;         /* --aabb: delete vertices outside [aabb_min, aabb_max] */
+    float aabb_min[3], aabb_max[3];
+    float dd_factor;      /* depthmap_triangulate's discontinuity factor, 5 */
+    int want_faces;       /* keep the triangles for smvs_points_download (tests);
+                             not available together with use_aabb */
+} smvs_points_options;
+
+typedef struct smvs_points smvs_points;
+
+/* generate_mesh :160-299 with the cut of smvs_cut_depth_maps, on the device,
+ * all views at once; options NULL = the reference's defaults (cut, no AABB,
+ * dd_factor 5, no faces).  -> a handle holding the points on the host and
+ * their number. */
+int smvs_points_generate(int device, const smvs_point_view *views, int n_views,
+    const smvs_points_options *options, smvs_points **handle,
+    int64_t *n_points);
+/* Number of points and of triangles (0 unless want_faces) of a handle. */
+int smvs_points_info(const smvs_points *handle, int64_t *n_points,
+    int64_t *n_faces);
+/* The point attributes (mve::TriangleMesh vertices, vertex normals, colours,
+ * confidences and values as save_ply_mesh writes them); any pointer may be
+ * NULL.  xyz / normals: n_points*3 floats; rgb: n_points*3 bytes (the image's
+ * bytes: ci / 255 stored as uchar); confidence / value: n_points floats;
+ * faces: n_faces*3 vertex ids (depthmap_triangulate's face list, merged). */
+int smvs_points_download(const smvs_points *handle, float *xyz, float *normals,
+    uint8_t *rgb, float *confidence, float *value, uint32_t *faces);
+int smvs_points_release(smvs_points *handle);
+
 /* The context-free entry points above (smvs_sgm_run, smvs_sgm_depth_for_view,
  * smvs_bilateral_upsample, smvs_cut_depth_maps) draw their device buffers,
  * stream and pinned staging memory from a per-device pool of workspaces that

@@ -176,6 +176,32 @@ int smvs_host_reconstruct_scene(const char *scene_dir,
     int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
     int *n_skipped, double *seconds, int *input_scale_used);
 
+/* smvsrecon's generate_mesh (app/smvsrecon.cc:278-343, MeshGenerator::
+ * generate_mesh, lib/mesh_generator.cc:160-299) on a reconstructed scene: the
+ * point cloud of the views' <dm_name> / <dm_name>N / <input> embeddings (cut
+ * on the device, smvs_points_generate), smvs-cut.mvei per view when cutting,
+ * the AABB clip, <scene>/smvs-{B,S}<input_scale>.ply.  create_triangle_mesh
+ * (--mesh) and simplify (--simplify) are refused.  view_ids may be NULL
+ * (every view).  ply_path (may be NULL) receives the file name. */
+typedef struct {
+    const char *image_embedding;    /* "undistorted" */
+    int input_scale;                /* the scale the scene was reconstructed at */
+    int use_shading;                /* names smvs-S / smvs-B */
+    int cut_surface;                /* 0: --no-cut */
+    int create_triangle_mesh;       /* --mesh: refused */
+    int simplify;                   /* --simplify: refused */
+    int use_aabb;
+    float aabb_min[3], aabb_max[3];
+    int device;
+} smvs_host_point_cloud_settings;
+int smvs_host_generate_point_cloud(const char *scene_dir,
+    const smvs_host_point_cloud_settings *settings, const int *view_ids,
+    int n_view_ids, char *ply_path, int ply_path_capacity, int64_t *n_points);
+/* save_ply_points: the PLY writer of the point cloud from SoA buffers
+ * (xyz, normals n*3 floats; rgb n*3 bytes; confidence, value n floats). */
+int smvs_host_save_ply_points(const char *path, const float *xyz, const float *normals,
+    const uint8_t *rgb, const float *confidence, const float *value, int64_t n);
+
 /* Byte-image containers of a view directory (csrc/host/png_io.cc,
  * scene_io.cc): load `path` (.png or .mvei, u8) -> width, height, channels and,
  * if pixels != NULL with room for capacity bytes, the interleaved data;

@@ -1,0 +1,77 @@
+// smvs::MeshGenerator's point-cloud path (reference: lib/mesh_generator.h,
+// lib/mesh_generator.cc:160-299) and smvsrecon's generate_mesh
+// (app/smvsrecon.cc:278-343) on top of smvs_points_generate.  The cut, the
+// triangulation and every per-vertex value run on the device; the host loads
+// the embeddings, writes smvs-cut per view and streams the PLY file.
+#pragma once
+
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "scene_io.h"
+
+namespace smvs_amd {
+
+// mve::TriangleMesh reduced to what the point export fills (SoA as the C ABI
+// hands it back); colours as the bytes save_ply_mesh writes
+struct PointCloud
+{
+    typedef std::shared_ptr<PointCloud> Ptr;
+    std::vector<float> xyz, normals, confidences, values;
+    std::vector<uint8_t> colors;
+    std::size_t size(void) const { return confidences.size(); }
+};
+
+class MeshGenerator
+{
+public:
+    struct Options
+    {
+        std::size_t num_threads = 0;        // (the device does the work)
+        bool cut_surfaces = true;
+        bool simplify = false;              // refused: serial approximate_triangulation
+        bool create_triangle_mesh = false;  // refused: WIP in the reference
+        int device = 0;
+        float dd_factor = 5.0f;
+        bool use_aabb = false;              // smvsrecon --aabb (:306-319)
+        float aabb_min[3] = { 0, 0, 0 }, aabb_max[3] = { 0, 0, 0 };
+    };
+
+    explicit MeshGenerator(Options const& opts);
+    // views lacking depth (dm_name), normals (dm_name + "N") or the image are
+    // skipped (:165-180); writes smvs-cut.mvei per view when cutting (:222-226)
+    PointCloud::Ptr generate_mesh(std::vector<SceneView> const& views,
+        std::string const& image_name, std::string const& dm_name);
+
+private:
+    Options opts;
+};
+
+// mve::geom::save_ply_mesh with vertex normals, values and confidences
+// (binary little endian; x y z nx ny nz red green blue confidence value;
+// an empty face element), streamed from the SoA buffers
+void save_ply_points(std::string const& path, PointCloud const& points);
+
+// AppSettings of smvsrecon's generate_mesh
+struct PointCloudSettings
+{
+    std::vector<int> view_ids;          // empty: every view of the scene
+    std::string image_embedding = "undistorted";
+    int input_scale = 0;                // names the embeddings and the file
+    bool use_shading = false;
+    bool cut_surface = true;            // --no-cut
+    bool create_triangle_mesh = false;  // --mesh: refused
+    bool simplify = false;              // --simplify: refused
+    bool use_aabb = false;
+    float aabb_min[3] = { 0, 0, 0 }, aabb_max[3] = { 0, 0, 0 };
+    int device = 0;
+};
+
+// app/smvsrecon.cc:278-343: generate_mesh over the scene's views, AABB clip,
+// <scene>/smvs-{B,S}<input_scale>.ply; -> the file written
+std::string generate_scene_point_cloud(std::string const& scene_path,
+    PointCloudSettings const& settings, std::size_t* n_points = nullptr);
+
+} // namespace smvs_amd

@@ -485,3 +485,84 @@ def cut_depth_maps(cams, depths, normals, device=0):
         arr[i].normals = _p(nm[i], _fp)
     check(lib.smvs_cut_depth_maps(device, arr, n))
     return d, nm
+
+
+class PointView(C.Structure):
+    """smvs_point_view of include/smvs_hip.h."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("flen", C.c_float),
+                ("rot", C.c_float * 9), ("trans", C.c_float * 3),
+                ("depth", _fp), ("normals", _fp), ("image", _u8p),
+                ("channels", C.c_int), ("cut_depth", _fp)]
+
+
+class PointsOptions(C.Structure):
+    """smvs_points_options of include/smvs_hip.h."""
+    _fields_ = [("cut_surfaces", C.c_int), ("use_aabb", C.c_int),
+                ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3),
+                ("dd_factor", C.c_float), ("want_faces", C.c_int)]
+
+
+def generate_points(cams, depths, normals, images, cut=True, aabb=None, faces=False,
+                    dd_factor=5.0, cut_maps=False, device=0):
+    """MeshGenerator::generate_mesh's point cloud over all views on the device
+    (smvs_points_generate).  cams: objects with .flen, .R, .t; depths[i] (h, w)
+    ray-length depth; normals[i] (h, w, 3) camera space; images[i] (h, w) or
+    (h, w, c) uint8 at the depth map's size.  aabb: None or (min3, max3).
+    Returns a dict of numpy arrays: xyz, normals (n, 3) float32, rgb (n, 3)
+    uint8, confidence, value (n,) float32, faces (m, 3) uint32 when asked
+    for, cut_depth (the triangulated maps) when cut_maps."""
+    lib = _capi.load()
+    n = len(cams)
+    if not (len(depths) == len(normals) == len(images) == n):
+        raise ValueError("cams, depths, normals and images differ in length")
+    d = [_f32(x) for x in depths]
+    nm = [_f32(x) for x in normals]
+    im = [np.ascontiguousarray(x, dtype=np.uint8) for x in images]
+    cuts = [np.zeros_like(x) for x in d] if cut_maps else None
+    arr = (PointView * max(n, 1))()
+    for i in range(n):
+        h, w = d[i].shape
+        if nm[i].shape != (h, w, 3) or im[i].shape[:2] != (h, w):
+            raise ValueError("view %d: normals / image do not match the depth map" % i)
+        arr[i].height, arr[i].width = h, w
+        arr[i].flen = float(cams[i].flen)
+        for k, x in enumerate(np.asarray(cams[i].R, dtype=np.float32).reshape(9)):
+            arr[i].rot[k] = float(x)
+        for k, x in enumerate(np.asarray(cams[i].t, dtype=np.float32).reshape(3)):
+            arr[i].trans[k] = float(x)
+        arr[i].depth = _p(d[i], _fp)
+        arr[i].normals = _p(nm[i], _fp)
+        arr[i].image = _p(im[i], _u8p)
+        arr[i].channels = 1 if im[i].ndim == 2 else im[i].shape[2]
+        arr[i].cut_depth = _p(cuts[i], _fp) if cut_maps else None
+    opt = PointsOptions()
+    opt.cut_surfaces = int(bool(cut))
+    opt.use_aabb = int(aabb is not None)
+    if aabb is not None:
+        for k in range(3):
+            opt.aabb_min[k] = float(aabb[0][k])
+            opt.aabb_max[k] = float(aabb[1][k])
+    opt.dd_factor = float(dd_factor)
+    opt.want_faces = int(bool(faces))
+    handle = C.c_void_p()
+    n_points = C.c_int64()
+    check(lib.smvs_points_generate(device, arr if n else None, n, C.byref(opt),
+                                   C.byref(handle), C.byref(n_points)))
+    try:
+        n_faces = C.c_int64()
+        check(lib.smvs_points_info(handle, None, C.byref(n_faces)))
+        k = n_points.value
+        out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
+               "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
+               "value": np.zeros(k, np.float32)}
+        fc = np.zeros((n_faces.value, 3), np.uint32) if faces else None
+        check(lib.smvs_points_download(handle, _p(out["xyz"], _fp), _p(out["normals"], _fp),
+                                       _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
+                                       _p(out["value"], _fp), _p(fc, _u32p)))
+    finally:
+        lib.smvs_points_release(handle)
+    if faces:
+        out["faces"] = fc
+    if cut_maps:
+        out["cut_depth"] = cuts
+    return out

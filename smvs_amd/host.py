@@ -564,3 +564,66 @@ def last_embeddings():
         if lib.smvs_host_embedding(name.encode(), a.ctypes.data_as(_fp), C.c_longlong(n), whc) == 0:
             out[name] = a.reshape(whc[1], whc[0], whc[2]).squeeze()
     return out
+
+
+class PointCloudSettings(C.Structure):
+    _fields_ = [("image_embedding", C.c_char_p), ("input_scale", C.c_int),
+                ("use_shading", C.c_int), ("cut_surface", C.c_int),
+                ("create_triangle_mesh", C.c_int), ("simplify", C.c_int),
+                ("use_aabb", C.c_int), ("aabb_min", C.c_float * 3),
+                ("aabb_max", C.c_float * 3), ("device", C.c_int)]
+
+
+def generate_point_cloud(scene_dir, view_ids=None, image_embedding="undistorted",
+                         input_scale=0, use_shading=False, cut=True, aabb=None,
+                         mesh=False, simplify=False, device=0):
+    """smvsrecon's generate_mesh (app/smvsrecon.cc:278-343) on a reconstructed
+    scene through smvs_amd::generate_scene_point_cloud: the point cloud of the
+    views' smvs-{B,S}<input_scale> embeddings, written as
+    <scene>/smvs-{B,S}<input_scale>.ply (and smvs-cut.mvei per view when
+    cutting).  aabb: None or (min3, max3).  mesh / simplify (--mesh,
+    --simplify) are refused.  Returns (ply path, number of points)."""
+    lib = load()
+    st = PointCloudSettings()
+    st.image_embedding = image_embedding.encode()
+    st.input_scale = int(input_scale)
+    st.use_shading = int(bool(use_shading))
+    st.cut_surface = int(bool(cut))
+    st.create_triangle_mesh = int(bool(mesh))
+    st.simplify = int(bool(simplify))
+    st.use_aabb = int(aabb is not None)
+    if aabb is not None:
+        for k in range(3):
+            st.aabb_min[k] = float(aabb[0][k])
+            st.aabb_max[k] = float(aabb[1][k])
+    st.device = int(device)
+    ids = None if view_ids is None else np.asarray(view_ids, dtype=np.int32)
+    path = C.create_string_buffer(4096)
+    n = C.c_int64(0)
+    rc = lib.smvs_host_generate_point_cloud(
+        scene_dir.encode(), C.byref(st), ids.ctypes.data_as(_i32p) if ids is not None else None,
+        C.c_int(0 if ids is None else ids.size), path, C.c_int(len(path)), C.byref(n))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    return path.value.decode(), n.value
+
+
+def save_ply_points(path, xyz, normals, rgb, confidence, value):
+    """The host's PLY writer of the point cloud (save_ply_points)."""
+    lib = load()
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    normals = np.ascontiguousarray(normals, np.float32)
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    confidence = np.ascontiguousarray(confidence, np.float32)
+    value = np.ascontiguousarray(value, np.float32)
+    n = confidence.size
+    if xyz.shape != (n, 3) or normals.shape != (n, 3) or rgb.shape != (n, 3) \
+            or value.size != n:
+        raise ValueError("save_ply_points: attribute shapes differ")
+    fp = C.POINTER(C.c_float)
+    rc = lib.smvs_host_save_ply_points(
+        path.encode(), xyz.ctypes.data_as(fp), normals.ctypes.data_as(fp),
+        rgb.ctypes.data_as(C.POINTER(C.c_uint8)), confidence.ctypes.data_as(fp),
+        value.ctypes.data_as(fp), C.c_int64(n))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
