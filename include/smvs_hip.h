@@ -565,7 +565,8 @@ typedef struct smvs_points smvs_points;
 int smvs_points_generate(int device, const smvs_point_view *views, int n_views,
     const smvs_points_options *options, smvs_points **handle,
     int64_t *n_points);
-/* Number of points and of triangles (0 unless want_faces) of a handle. */
+/* Number of points and of triangles (0 unless want_faces; a mesh handle's
+ * faces) of a handle. */
 int smvs_points_info(const smvs_points *handle, int64_t *n_points,
     int64_t *n_faces);
 /* The point attributes (mve::TriangleMesh vertices, vertex normals, colours,
@@ -576,6 +577,29 @@ int smvs_points_info(const smvs_points *handle, int64_t *n_points,
 int smvs_points_download(const smvs_points *handle, float *xyz, float *normals,
     uint8_t *rgb, float *confidence, float *value, uint32_t *faces);
 int smvs_points_release(smvs_points *handle);
+
+/* smvsrecon --mesh without --simplify (app/smvsrecon.cc:306-324): per view
+ * the triangulation and confidences of smvs_points_generate, merged with
+ * mve::geom::mesh_merge in view-list order (mesh_generator.cc:279-282; face
+ * ids offset by the vertices before them), optionally clipped with
+ * delete_vertices_fix_faces (the faces that lose a corner go, the rest keep
+ * their order; vertices no face uses any more are kept), then
+ * recalc_normals' angle-weighted vertex normals.  The semantics pinned for
+ * the MVE pieces are rows M1-M6 of DESIGN.md section 9.5.  options NULL =
+ * the reference's defaults (cut, no AABB, dd_factor 5).  The handle is read
+ * with smvs_points_info / smvs_points_download and freed with
+ * smvs_points_release; it has no values (a non-NULL value pointer is an
+ * argument error) and always the faces. */
+typedef struct {
+    int cut_surfaces;     /* MeshGenerator::Options::cut_surfaces (--no-cut: 0) */
+    int use_aabb;         /* --aabb: delete vertices outside [aabb_min, aabb_max] */
+    float aabb_min[3], aabb_max[3];
+    float dd_factor;      /* depthmap_triangulate's discontinuity factor, 5 */
+} smvs_mesh_options;
+
+int smvs_mesh_generate(int device, const smvs_point_view *views, int n_views,
+    const smvs_mesh_options *options, smvs_points **handle,
+    int64_t *n_vertices, int64_t *n_faces);
 
 /* The context-free entry points above (smvs_sgm_run, smvs_sgm_depth_for_view,
  * smvs_bilateral_upsample, smvs_cut_depth_maps) draw their device buffers,

@@ -5,7 +5,8 @@ this package is the thin host-side handle used by tests and bench.py.
 """
 from . import _capi  # noqa: F401
 from .device import (ViewContext, device_count, sgm_run, bilateral_upsample,  # noqa: F401
-                     sgm_depth_for_view, cut_depth_maps, generate_points)
+                     sgm_depth_for_view, cut_depth_maps, generate_points,
+                     generate_mesh)
 
 __all__ = ["ViewContext", "device_count", "sgm_run", "bilateral_upsample",
-           "sgm_depth_for_view", "cut_depth_maps", "generate_points"]
+           "sgm_depth_for_view", "cut_depth_maps", "generate_points", "generate_mesh"]

@@ -982,6 +982,42 @@ smvs_host_block_multiply(int num_nodes, int node_stride, const double *blocks9,
     }
 }
 
+namespace {
+
+PointCloudSettings
+point_cloud_settings(const smvs_host_point_cloud_settings *o, const int *view_ids,
+    int n_view_ids)
+{
+    PointCloudSettings conf;
+    if (o->image_embedding != nullptr)
+        conf.image_embedding = o->image_embedding;
+    conf.input_scale = o->input_scale;
+    conf.use_shading = o->use_shading != 0;
+    conf.cut_surface = o->cut_surface != 0;
+    conf.create_triangle_mesh = o->create_triangle_mesh != 0;
+    conf.simplify = o->simplify != 0;
+    conf.use_aabb = o->use_aabb != 0;
+    std::copy(o->aabb_min, o->aabb_min + 3, conf.aabb_min);
+    std::copy(o->aabb_max, o->aabb_max + 3, conf.aabb_max);
+    conf.device = o->device;
+    if (view_ids != nullptr)
+        conf.view_ids.assign(view_ids, view_ids + n_view_ids);
+    return conf;
+}
+
+void
+copy_path(std::string const& path, char *ply_path, int ply_path_capacity)
+{
+    if (ply_path != nullptr && ply_path_capacity > 0) {
+        std::size_t const k = std::min<std::size_t>(path.size(),
+            (std::size_t)ply_path_capacity - 1);
+        std::memcpy(ply_path, path.data(), k);
+        ply_path[k] = 0;
+    }
+}
+
+} // namespace
+
 extern "C" int
 smvs_host_generate_point_cloud(const char *scene_dir,
     const smvs_host_point_cloud_settings *o, const int *view_ids, int n_view_ids,
@@ -990,30 +1026,36 @@ smvs_host_generate_point_cloud(const char *scene_dir,
     try {
         if (scene_dir == nullptr || o == nullptr || (view_ids == nullptr && n_view_ids > 0))
             throw std::invalid_argument("smvs_host_generate_point_cloud: bad argument");
-        PointCloudSettings conf;
-        if (o->image_embedding != nullptr)
-            conf.image_embedding = o->image_embedding;
-        conf.input_scale = o->input_scale;
-        conf.use_shading = o->use_shading != 0;
-        conf.cut_surface = o->cut_surface != 0;
-        conf.create_triangle_mesh = o->create_triangle_mesh != 0;
-        conf.simplify = o->simplify != 0;
-        conf.use_aabb = o->use_aabb != 0;
-        std::copy(o->aabb_min, o->aabb_min + 3, conf.aabb_min);
-        std::copy(o->aabb_max, o->aabb_max + 3, conf.aabb_max);
-        conf.device = o->device;
-        if (view_ids != nullptr)
-            conf.view_ids.assign(view_ids, view_ids + n_view_ids);
+        PointCloudSettings const conf = point_cloud_settings(o, view_ids, n_view_ids);
         std::size_t n = 0;
         std::string const path = generate_scene_point_cloud(scene_dir, conf, &n);
-        if (ply_path != nullptr && ply_path_capacity > 0) {
-            std::size_t const k = std::min<std::size_t>(path.size(),
-                (std::size_t)ply_path_capacity - 1);
-            std::memcpy(ply_path, path.data(), k);
-            ply_path[k] = 0;
-        }
+        copy_path(path, ply_path, ply_path_capacity);
         if (n_points != nullptr)
             *n_points = (int64_t)n;
+        return 0;
+    } catch (std::exception const& e) {
+        g_host_error = e.what();
+        return -1;
+    }
+}
+
+extern "C" int
+smvs_host_generate_mesh(const char *scene_dir,
+    const smvs_host_point_cloud_settings *o, const int *view_ids, int n_view_ids,
+    char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces)
+{
+    try {
+        if (scene_dir == nullptr || o == nullptr || (view_ids == nullptr && n_view_ids > 0))
+            throw std::invalid_argument("smvs_host_generate_mesh: bad argument");
+        PointCloudSettings conf = point_cloud_settings(o, view_ids, n_view_ids);
+        conf.create_triangle_mesh = true;
+        std::size_t nv = 0, nf = 0;
+        std::string const path = generate_scene_mesh(scene_dir, conf, &nv, &nf);
+        copy_path(path, ply_path, ply_path_capacity);
+        if (n_vertices != nullptr)
+            *n_vertices = (int64_t)nv;
+        if (n_faces != nullptr)
+            *n_faces = (int64_t)nf;
         return 0;
     } catch (std::exception const& e) {
         g_host_error = e.what();
@@ -1037,6 +1079,31 @@ smvs_host_save_ply_points(const char *path, const float *xyz, const float *norma
         pc.confidences.assign(confidence, confidence + k);
         pc.values.assign(value, value + k);
         save_ply_points(path, pc);
+        return 0;
+    } catch (std::exception const& e) {
+        g_host_error = e.what();
+        return -1;
+    }
+}
+
+extern "C" int
+smvs_host_save_ply_mesh(const char *path, const float *xyz, const float *normals,
+    const uint8_t *rgb, const float *confidence, int64_t n, const uint32_t *faces,
+    int64_t m)
+{
+    try {
+        if (path == nullptr || n < 0 || m < 0 || (n > 0 && (xyz == nullptr
+                || normals == nullptr || rgb == nullptr || confidence == nullptr))
+            || (m > 0 && faces == nullptr))
+            throw std::invalid_argument("smvs_host_save_ply_mesh: bad argument");
+        TriangleMesh mesh;
+        std::size_t const k = (std::size_t)n;
+        mesh.xyz.assign(xyz, xyz + 3 * k);
+        mesh.normals.assign(normals, normals + 3 * k);
+        mesh.colors.assign(rgb, rgb + 3 * k);
+        mesh.confidences.assign(confidence, confidence + k);
+        mesh.faces.assign(faces, faces + 3 * (std::size_t)m);
+        save_ply_mesh(path, mesh);
         return 0;
     } catch (std::exception const& e) {
         g_host_error = e.what();

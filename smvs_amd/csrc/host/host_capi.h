@@ -181,7 +181,7 @@ int smvs_host_reconstruct_scene(const char *scene_dir,
  * point cloud of the views' <dm_name> / <dm_name>N / <input> embeddings (cut
  * on the device, smvs_points_generate), smvs-cut.mvei per view when cutting,
  * the AABB clip, <scene>/smvs-{B,S}<input_scale>.ply.  create_triangle_mesh
- * (--mesh) and simplify (--simplify) are refused.  view_ids may be NULL
+ * (--mesh: smvs_host_generate_mesh) and simplify (--simplify) are refused.  view_ids may be NULL
  * (every view).  ply_path (may be NULL) receives the file name. */
 typedef struct {
     const char *image_embedding;    /* "undistorted" */
@@ -201,6 +201,22 @@ int smvs_host_generate_point_cloud(const char *scene_dir,
  * (xyz, normals n*3 floats; rgb n*3 bytes; confidence, value n floats). */
 int smvs_host_save_ply_points(const char *path, const float *xyz, const float *normals,
     const uint8_t *rgb, const float *confidence, const float *value, int64_t n);
+/* smvsrecon --mesh (app/smvsrecon.cc:278-343 with create_triangle_mesh):
+ * the triangle mesh of the same views (smvs_mesh_generate: merged, AABB
+ * clip with delete_vertices_fix_faces, recalc_normals), smvs-cut.mvei per
+ * view when cutting, <scene>/smvs-m-{B,S}<input_scale>.ply.  The settings are
+ * the point cloud's (create_triangle_mesh is implied and ignored); simplify
+ * (--simplify) is refused. */
+int smvs_host_generate_mesh(const char *scene_dir,
+    const smvs_host_point_cloud_settings *settings, const int *view_ids,
+    int n_view_ids, char *ply_path, int ply_path_capacity, int64_t *n_vertices,
+    int64_t *n_faces);
+/* save_ply_mesh: the PLY writer of the triangle mesh from SoA
+ * buffers (xyz, normals n*3 floats; rgb n*3 bytes; confidence n floats;
+ * faces m*3 vertex ids < n). */
+int smvs_host_save_ply_mesh(const char *path, const float *xyz, const float *normals,
+    const uint8_t *rgb, const float *confidence, int64_t n, const uint32_t *faces,
+    int64_t m);
 
 /* Byte-image containers of a view directory (csrc/host/png_io.cc,
  * scene_io.cc): load `path` (.png or .mvei, u8) -> width, height, channels and,

@@ -1,6 +1,7 @@
 #include "mesh_generator.h"
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -22,59 +23,85 @@ void check_status(int rc, char const* what)
 
 MeshGenerator::MeshGenerator(Options const& o) : opts(o)
 {
-    if (opts.create_triangle_mesh)
-        throw std::invalid_argument("MeshGenerator: the triangle mesh "
-            "(create_triangle_mesh, --mesh) is not supported");
     if (opts.simplify)
         throw std::invalid_argument("MeshGenerator: the simplified "
             "triangulation (--simplify) is not supported");
+}
+
+struct MeshGenerator::Inputs
+{
+    std::vector<SceneView const*> views;
+    std::vector<FloatImage::Ptr> depth, normals, cut;
+    std::vector<ByteImage::Ptr> color;
+    std::vector<smvs_point_view> pv;
+};
+
+void
+MeshGenerator::load_views(std::vector<SceneView> const& inputviews,
+    std::string const& image_name, std::string const& dm_name, Inputs& in) const
+{
+    std::string const nm_name = dm_name + "N";
+    for (SceneView const& v : inputviews) {
+        if (!v.present || !v.has_image(dm_name) || !v.has_image(nm_name)
+            || !v.has_image(image_name))
+            continue;
+        in.views.push_back(&v);
+    }
+    std::size_t const n = in.views.size();
+    in.depth.resize(n);
+    in.normals.resize(n);
+    in.color.resize(n);
+    in.cut.resize(n);
+    in.pv.resize(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        SceneView const& v = *in.views[i];
+        in.depth[i] = load_mvei_float(v.image_path(dm_name));
+        in.normals[i] = load_mvei_float(v.image_path(nm_name));
+        in.color[i] = v.load_byte_image(image_name);
+        int const w = in.depth[i]->width(), h = in.depth[i]->height();
+        if (in.depth[i]->channels() != 1 || in.normals[i]->width() != w
+            || in.normals[i]->height() != h || in.normals[i]->channels() != 3)
+            throw std::invalid_argument("view " + std::to_string(v.id)
+                + ": depth / normal maps do not match");
+        // (depthmap_triangulate: "Color image dimension mismatch")
+        if (in.color[i]->width() != w || in.color[i]->height() != h)
+            throw std::invalid_argument("view " + std::to_string(v.id)
+                + ": colour image dimension mismatch");
+        in.cut[i] = FloatImage::create(w, h, 1);
+        smvs_point_view& p = in.pv[i];
+        p.width = w;
+        p.height = h;
+        p.flen = v.camera.flen;
+        std::copy(v.camera.rot, v.camera.rot + 9, p.rot);
+        std::copy(v.camera.trans, v.camera.trans + 3, p.trans);
+        p.depth = in.depth[i]->begin();
+        p.normals = in.normals[i]->begin();
+        p.image = in.color[i]->begin();
+        p.channels = in.color[i]->channels();
+        p.cut_depth = opts.cut_surfaces ? in.cut[i]->begin() : nullptr;
+    }
+}
+
+void
+MeshGenerator::save_cut_maps(Inputs const& in) const
+{
+    if (opts.cut_surfaces)
+        for (std::size_t i = 0; i < in.views.size(); ++i)
+            save_mvei(in.views[i]->image_path("smvs-cut"),
+                FloatImage::ConstPtr(in.cut[i]));
 }
 
 PointCloud::Ptr
 MeshGenerator::generate_mesh(std::vector<SceneView> const& inputviews,
     std::string const& image_name, std::string const& dm_name)
 {
-    std::string const nm_name = dm_name + "N";
-    std::vector<SceneView const*> views;
-    for (SceneView const& v : inputviews) {
-        if (!v.present || !v.has_image(dm_name) || !v.has_image(nm_name)
-            || !v.has_image(image_name))
-            continue;
-        views.push_back(&v);
-    }
-    std::vector<FloatImage::Ptr> depth(views.size()), normals(views.size());
-    std::vector<ByteImage::Ptr> color(views.size());
-    std::vector<FloatImage::Ptr> cut(views.size());
-    std::vector<smvs_point_view> pv(views.size());
-    for (std::size_t i = 0; i < views.size(); ++i) {
-        SceneView const& v = *views[i];
-        depth[i] = load_mvei_float(v.image_path(dm_name));
-        normals[i] = load_mvei_float(v.image_path(nm_name));
-        color[i] = v.load_byte_image(image_name);
-        int const w = depth[i]->width(), h = depth[i]->height();
-        if (depth[i]->channels() != 1 || normals[i]->width() != w
-            || normals[i]->height() != h || normals[i]->channels() != 3)
-            throw std::invalid_argument("view " + std::to_string(v.id)
-                + ": depth / normal maps do not match");
-        // (depthmap_triangulate: "Color image dimension mismatch")
-        if (color[i]->width() != w || color[i]->height() != h)
-            throw std::invalid_argument("view " + std::to_string(v.id)
-                + ": colour image dimension mismatch");
-        cut[i] = FloatImage::create(w, h, 1);
-        smvs_point_view& p = pv[i];
-        p.width = w;
-        p.height = h;
-        p.flen = v.camera.flen;
-        std::copy(v.camera.rot, v.camera.rot + 9, p.rot);
-        std::copy(v.camera.trans, v.camera.trans + 3, p.trans);
-        p.depth = depth[i]->begin();
-        p.normals = normals[i]->begin();
-        p.image = color[i]->begin();
-        p.channels = color[i]->channels();
-        p.cut_depth = opts.cut_surfaces ? cut[i]->begin() : nullptr;
-    }
+    if (opts.create_triangle_mesh)
+        throw std::invalid_argument("MeshGenerator::generate_mesh: the triangle "
+            "mesh (create_triangle_mesh, --mesh) comes from generate_triangle_mesh");
+    Inputs in;
+    load_views(inputviews, image_name, dm_name, in);
     PointCloud::Ptr pset(new PointCloud);
-    if (views.empty())
+    if (in.views.empty())
         return pset;
     smvs_points_options po;
     po.cut_surfaces = opts.cut_surfaces ? 1 : 0;
@@ -85,7 +112,7 @@ MeshGenerator::generate_mesh(std::vector<SceneView> const& inputviews,
     po.want_faces = 0;
     smvs_points* handle = nullptr;
     int64_t n = 0;
-    check_status(smvs_points_generate(opts.device, pv.data(), (int)pv.size(), &po,
+    check_status(smvs_points_generate(opts.device, in.pv.data(), (int)in.pv.size(), &po,
         &handle, &n), "smvs_points_generate");
     pset->xyz.resize(3 * (std::size_t)n);
     pset->normals.resize(3 * (std::size_t)n);
@@ -96,10 +123,40 @@ MeshGenerator::generate_mesh(std::vector<SceneView> const& inputviews,
         pset->colors.data(), pset->confidences.data(), pset->values.data(), nullptr);
     smvs_points_release(handle);
     check_status(rc, "smvs_points_download");
-    if (opts.cut_surfaces)
-        for (std::size_t i = 0; i < views.size(); ++i)
-            save_mvei(views[i]->image_path("smvs-cut"), FloatImage::ConstPtr(cut[i]));
+    save_cut_maps(in);
     return pset;
+}
+
+TriangleMesh::Ptr
+MeshGenerator::generate_triangle_mesh(std::vector<SceneView> const& inputviews,
+    std::string const& image_name, std::string const& dm_name)
+{
+    Inputs in;
+    load_views(inputviews, image_name, dm_name, in);
+    TriangleMesh::Ptr mesh(new TriangleMesh);
+    if (in.views.empty())
+        return mesh;
+    smvs_mesh_options mo;
+    mo.cut_surfaces = opts.cut_surfaces ? 1 : 0;
+    mo.use_aabb = opts.use_aabb ? 1 : 0;
+    std::copy(opts.aabb_min, opts.aabb_min + 3, mo.aabb_min);
+    std::copy(opts.aabb_max, opts.aabb_max + 3, mo.aabb_max);
+    mo.dd_factor = opts.dd_factor;
+    smvs_points* handle = nullptr;
+    int64_t nv = 0, nf = 0;
+    check_status(smvs_mesh_generate(opts.device, in.pv.data(), (int)in.pv.size(), &mo,
+        &handle, &nv, &nf), "smvs_mesh_generate");
+    mesh->xyz.resize(3 * (std::size_t)nv);
+    mesh->normals.resize(3 * (std::size_t)nv);
+    mesh->colors.resize(3 * (std::size_t)nv);
+    mesh->confidences.resize((std::size_t)nv);
+    mesh->faces.resize(3 * (std::size_t)nf);
+    int const rc = smvs_points_download(handle, mesh->xyz.data(), mesh->normals.data(),
+        mesh->colors.data(), mesh->confidences.data(), nullptr, mesh->faces.data());
+    smvs_points_release(handle);
+    check_status(rc, "smvs_points_download");
+    save_cut_maps(in);
+    return mesh;
 }
 
 void
@@ -144,6 +201,119 @@ save_ply_points(std::string const& path, PointCloud const& points)
         throw std::runtime_error("save_ply_points: write failed: " + path);
 }
 
+void
+save_ply_mesh(std::string const& path, TriangleMesh const& mesh)
+{
+    std::size_t const n = mesh.size(), m = mesh.num_faces();
+    if (mesh.xyz.size() != 3 * n || mesh.normals.size() != 3 * n
+        || mesh.colors.size() != 3 * n || mesh.faces.size() != 3 * m)
+        throw std::invalid_argument("save_ply_mesh: attribute sizes differ");
+    if (n > (std::size_t)INT32_MAX)
+        throw std::invalid_argument("save_ply_mesh: vertex ids exceed int32");
+    for (uint32_t id : mesh.faces)
+        if (id >= n)
+            throw std::invalid_argument("save_ply_mesh: face references no vertex");
+    std::ofstream out(path.c_str(), std::ios::binary);
+    if (!out)
+        throw std::runtime_error("save_ply_mesh: cannot open " + path);
+    out << "ply\n"
+        << "format binary_little_endian 1.0\n"
+        << "comment Export generated by smvs_amd\n"
+        << "element vertex " << n << "\n"
+        << "property float x\nproperty float y\nproperty float z\n"
+        << "property float nx\nproperty float ny\nproperty float nz\n"
+        << "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+        << "property float confidence\n"
+        << "element face " << m << "\n"
+        << "property list uchar int vertex_indices\n"
+        << "end_header\n";
+    // 31 bytes per vertex, 13 per face, in chunks (the hosts are little endian)
+    std::size_t const chunk = 1 << 16;
+    std::vector<char> buf(chunk * 31);
+    for (std::size_t at = 0; at < n; at += chunk) {
+        std::size_t const k = std::min(chunk, n - at);
+        char* p = buf.data();
+        for (std::size_t i = at; i < at + k; ++i) {
+            std::memcpy(p, &mesh.xyz[3 * i], 12);
+            std::memcpy(p + 12, &mesh.normals[3 * i], 12);
+            std::memcpy(p + 24, &mesh.colors[3 * i], 3);
+            std::memcpy(p + 27, &mesh.confidences[i], 4);
+            p += 31;
+        }
+        out.write(buf.data(), (std::streamsize)(k * 31));
+    }
+    for (std::size_t at = 0; at < m; at += chunk) {
+        std::size_t const k = std::min(chunk, m - at);
+        char* p = buf.data();
+        for (std::size_t i = at; i < at + k; ++i) {
+            *p = 3;
+            std::memcpy(p + 1, &mesh.faces[3 * i], 12);
+            p += 13;
+        }
+        out.write(buf.data(), (std::streamsize)(k * 13));
+    }
+    if (!out)
+        throw std::runtime_error("save_ply_mesh: write failed: " + path);
+}
+
+namespace {
+
+// the scene's views of the settings and the embedding names smvsrecon's main
+// hands over (:502-515)
+struct SceneInputs
+{
+    Scene::Ptr scene;
+    std::vector<SceneView> views;
+    std::string input_name, dm_name;
+};
+
+SceneInputs
+scene_inputs(std::string const& scene_path, PointCloudSettings const& conf)
+{
+    SceneInputs s;
+    s.scene = Scene::create(scene_path);
+    std::vector<SceneView>& all = s.scene->get_views();
+    if (conf.view_ids.empty())
+        s.views = all;
+    else
+        for (int id : conf.view_ids) {
+            if (id < 0 || id >= (int)all.size())
+                throw std::invalid_argument("no view " + std::to_string(id));
+            s.views.push_back(all[(std::size_t)id]);
+        }
+    s.input_name = conf.input_scale > 0
+        ? "undist-L" + std::to_string(conf.input_scale) : conf.image_embedding;
+    s.dm_name = std::string(conf.use_shading ? "smvs-S" : "smvs-B")
+        + std::to_string(conf.input_scale);
+    return s;
+}
+
+MeshGenerator::Options
+generator_options(PointCloudSettings const& conf)
+{
+    MeshGenerator::Options mo;
+    mo.cut_surfaces = conf.cut_surface;
+    mo.device = conf.device;
+    mo.use_aabb = conf.use_aabb;
+    std::copy(conf.aabb_min, conf.aabb_min + 3, mo.aabb_min);
+    std::copy(conf.aabb_max, conf.aabb_max + 3, mo.aabb_max);
+    return mo;
+}
+
+// :326-335
+std::string
+output_name(Scene const& scene, PointCloudSettings const& conf, bool mesh)
+{
+    std::string meshname = "smvs-";
+    if (mesh)
+        meshname += "m-";
+    meshname += conf.use_shading ? "S" : "B";
+    meshname += std::to_string(conf.input_scale) + ".ply";
+    return scene.get_path() + "/" + meshname;
+}
+
+} // namespace
+
 std::string
 generate_scene_point_cloud(std::string const& scene_path,
     PointCloudSettings const& conf, std::size_t* n_points)
@@ -152,40 +322,34 @@ generate_scene_point_cloud(std::string const& scene_path,
         throw std::invalid_argument("--mesh (create_triangle_mesh) is not supported");
     if (conf.simplify)
         throw std::invalid_argument("--simplify is not supported");
-    Scene::Ptr scene = Scene::create(scene_path);
-    std::vector<SceneView>& all = scene->get_views();
-    std::vector<SceneView> recon_views;
-    if (conf.view_ids.empty())
-        recon_views = all;
-    else
-        for (int id : conf.view_ids) {
-            if (id < 0 || id >= (int)all.size())
-                throw std::invalid_argument("no view " + std::to_string(id));
-            recon_views.push_back(all[(std::size_t)id]);
-        }
-    // the names smvsrecon's main hands over (:502-515)
-    std::string const input_name = conf.input_scale > 0
-        ? "undist-L" + std::to_string(conf.input_scale) : conf.image_embedding;
-    std::string const dm_name = std::string(conf.use_shading ? "smvs-S" : "smvs-B")
-        + std::to_string(conf.input_scale);
-
-    MeshGenerator::Options mo;
-    mo.cut_surfaces = conf.cut_surface;
-    mo.device = conf.device;
-    mo.use_aabb = conf.use_aabb;
-    std::copy(conf.aabb_min, conf.aabb_min + 3, mo.aabb_min);
-    std::copy(conf.aabb_max, conf.aabb_max + 3, mo.aabb_max);
-    MeshGenerator meshgen(mo);
-    PointCloud::Ptr points = meshgen.generate_mesh(recon_views, input_name, dm_name);
-
-    // :326-335
-    std::string meshname = "smvs-";
-    meshname += conf.use_shading ? "S" : "B";
-    meshname += std::to_string(conf.input_scale) + ".ply";
-    meshname = scene->get_path() + "/" + meshname;
+    SceneInputs const in = scene_inputs(scene_path, conf);
+    MeshGenerator meshgen(generator_options(conf));
+    PointCloud::Ptr points = meshgen.generate_mesh(in.views, in.input_name, in.dm_name);
+    std::string const meshname = output_name(*in.scene, conf, false);
     save_ply_points(meshname, *points);
     if (n_points != nullptr)
         *n_points = points->size();
+    return meshname;
+}
+
+std::string
+generate_scene_mesh(std::string const& scene_path, PointCloudSettings const& conf,
+    std::size_t* n_vertices, std::size_t* n_faces)
+{
+    if (conf.simplify)
+        throw std::invalid_argument("--simplify is not supported");
+    SceneInputs const in = scene_inputs(scene_path, conf);
+    MeshGenerator::Options mo = generator_options(conf);
+    mo.create_triangle_mesh = true;
+    MeshGenerator meshgen(mo);
+    TriangleMesh::Ptr mesh = meshgen.generate_triangle_mesh(in.views, in.input_name,
+        in.dm_name);
+    std::string const meshname = output_name(*in.scene, conf, true);
+    save_ply_mesh(meshname, *mesh);
+    if (n_vertices != nullptr)
+        *n_vertices = mesh->size();
+    if (n_faces != nullptr)
+        *n_faces = mesh->num_faces();
     return meshname;
 }
 

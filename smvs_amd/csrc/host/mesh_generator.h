@@ -1,8 +1,9 @@
-// smvs::MeshGenerator's point-cloud path (reference: lib/mesh_generator.h,
-// lib/mesh_generator.cc:160-299) and smvsrecon's generate_mesh
-// (app/smvsrecon.cc:278-343) on top of smvs_points_generate.  The cut, the
-// triangulation and every per-vertex value run on the device; the host loads
-// the embeddings, writes smvs-cut per view and streams the PLY file.
+// smvs::MeshGenerator's point-cloud and triangle-mesh paths (reference:
+// lib/mesh_generator.h, lib/mesh_generator.cc:160-299) and smvsrecon's
+// generate_mesh (app/smvsrecon.cc:278-343) on top of smvs_points_generate and
+// smvs_mesh_generate.  The cut, the triangulation and every per-vertex value
+// run on the device; the host loads the embeddings, writes smvs-cut per view
+// and streams the PLY file.
 #pragma once
 
 #include <cstdint>
@@ -24,6 +25,19 @@ struct PointCloud
     std::size_t size(void) const { return confidences.size(); }
 };
 
+// mve::TriangleMesh as smvsrecon --mesh saves it:
+// the point cloud's SoA without values, plus the face list (3 vertex ids per
+// face); normals are recalc_normals' vertex normals
+struct TriangleMesh
+{
+    typedef std::shared_ptr<TriangleMesh> Ptr;
+    std::vector<float> xyz, normals, confidences;
+    std::vector<uint8_t> colors;
+    std::vector<uint32_t> faces;
+    std::size_t size(void) const { return confidences.size(); }
+    std::size_t num_faces(void) const { return faces.size() / 3; }
+};
+
 class MeshGenerator
 {
 public:
@@ -32,7 +46,8 @@ public:
         std::size_t num_threads = 0;        // (the device does the work)
         bool cut_surfaces = true;
         bool simplify = false;              // refused: serial approximate_triangulation
-        bool create_triangle_mesh = false;  // refused: WIP in the reference
+        bool create_triangle_mesh = false;  // generate_mesh refuses it: use
+                                            // generate_triangle_mesh
         int device = 0;
         float dd_factor = 5.0f;
         bool use_aabb = false;              // smvsrecon --aabb (:306-319)
@@ -44,8 +59,19 @@ public:
     // skipped (:165-180); writes smvs-cut.mvei per view when cutting (:222-226)
     PointCloud::Ptr generate_mesh(std::vector<SceneView> const& views,
         std::string const& image_name, std::string const& dm_name);
+    // the create_triangle_mesh path (:279-282) with smvsrecon's AABB clip and
+    // recalc_normals (app/smvsrecon.cc:306-324), on smvs_mesh_generate; views
+    // and smvs-cut as generate_mesh
+    TriangleMesh::Ptr generate_triangle_mesh(std::vector<SceneView> const& views,
+        std::string const& image_name, std::string const& dm_name);
 
 private:
+    struct Inputs;
+    // loads the usable views' maps and images into the device's view records
+    void load_views(std::vector<SceneView> const& inputviews,
+        std::string const& image_name, std::string const& dm_name, Inputs& in) const;
+    void save_cut_maps(Inputs const& in) const;
+
     Options opts;
 };
 
@@ -53,6 +79,11 @@ private:
 // (binary little endian; x y z nx ny nz red green blue confidence value;
 // an empty face element), streamed from the SoA buffers
 void save_ply_points(std::string const& path, PointCloud const& points);
+
+// mve::geom::save_ply_mesh of the triangle mesh with smvsrecon's options
+// (DESIGN.md M6): x y z nx ny nz red green blue confidence, no value, and
+// `element face` as `uchar 3` + three int32 per face; streamed
+void save_ply_mesh(std::string const& path, TriangleMesh const& mesh);
 
 // AppSettings of smvsrecon's generate_mesh
 struct PointCloudSettings
@@ -62,7 +93,8 @@ struct PointCloudSettings
     int input_scale = 0;                // names the embeddings and the file
     bool use_shading = false;
     bool cut_surface = true;            // --no-cut
-    bool create_triangle_mesh = false;  // --mesh: refused
+    bool create_triangle_mesh = false;  // --mesh: generate_scene_mesh; refused
+                                        // by generate_scene_point_cloud
     bool simplify = false;              // --simplify: refused
     bool use_aabb = false;
     float aabb_min[3] = { 0, 0, 0 }, aabb_max[3] = { 0, 0, 0 };
@@ -73,5 +105,11 @@ struct PointCloudSettings
 // <scene>/smvs-{B,S}<input_scale>.ply; -> the file written
 std::string generate_scene_point_cloud(std::string const& scene_path,
     PointCloudSettings const& settings, std::size_t* n_points = nullptr);
+
+// the same with --mesh: the triangle mesh, <scene>/smvs-m-{B,S}<input_scale>.ply;
+// -> the file written
+std::string generate_scene_mesh(std::string const& scene_path,
+    PointCloudSettings const& settings, std::size_t* n_vertices = nullptr,
+    std::size_t* n_faces = nullptr);
 
 } // namespace smvs_amd

@@ -16,6 +16,7 @@
 // assumptions listed in tests/golden/README.md [MVE-unverified].
 #include "common.h"
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -350,6 +351,11 @@ smvs_cut_depth_maps(int device, smvs_mesh_view *views, int n_views)
 //   ring   3 relaxations of the distance to the nearest border vertex
 //   emit   position, colour, normal, confidence, scale value (and faces)
 //   clip   keep flags, scan, order-preserving compaction (AABB only)
+// The triangle mesh (smvs_mesh_generate) runs the same
+// passes up to emit (without normal and scale value), then
+//   normals  recalc_normals as a per-vertex gather over the incident faces
+//   clip     as above, plus kept faces per block, their scan and a scatter
+//            that renumbers the faces' vertices (AABB only)
 // ===========================================================================
 namespace smvs_hip {
 
@@ -720,6 +726,9 @@ points_ring_kernel(const PointViewDev *__restrict__ pv, PointBufs B, int src)
     B.dist[src ^ 1][p] = (uint8_t)d;
 }
 
+// MESH: the triangle mesh's vertices (M1 of DESIGN.md section 9.5): position,
+// colour and confidence only; its normals come from mesh_normals_kernel
+template <bool MESH>
 __global__ void __launch_bounds__(256)
 points_emit_kernel(const MeshViewDev *__restrict__ views,
     const PointViewDev *__restrict__ pv, PointBufs B, int dist_buf)
@@ -762,6 +771,10 @@ points_emit_kernel(const MeshViewDev *__restrict__ views,
     B.rgb[3 * id + 0] = g;
     B.rgb[3 * id + 1] = P.channels >= 3 ? px[1] : g;
     B.rgb[3 * id + 2] = P.channels >= 3 ? px[2] : g;
+    int const d = B.dist[dist_buf][p];
+    B.conf[id] = d >= 4 ? 1.0f : (float)d / 4.0f;
+    if constexpr (MESH)
+        return;
     // ViewProjection::get_proj, (int) truncation, lookup in the world-space
     // normal map; 0 where the reference leaves the value unset
     float const u = dot3(V.KR + 0, pos) - V.t[0];
@@ -776,8 +789,6 @@ points_emit_kernel(const MeshViewDev *__restrict__ views,
     }
     for (int r = 0; r < 3; ++r)
         B.nrm[3 * id + r] = n[r];
-    int const d = B.dist[dist_buf][p];
-    B.conf[id] = d >= 4 ? 1.0f : (float)d / 4.0f;
     // mvscale: 2 * mean distance to the one-ring, in MeshInfo's order
     int const cnt = m & 15;
     uint32_t const list = B.nbr[p];
@@ -930,33 +941,208 @@ points_compact_kernel(size_t n, float3 lo, float3 hi,
         dst.rgb[3 * j + r] = src.rgb[3 * i + r];
     }
     dst.conf[j] = src.conf[i];
-    dst.val[j] = src.val[i];
+    if (dst.val != nullptr)   // (the triangle mesh has no values)
+        dst.val[j] = src.val[i];
+}
+
+// ------------------------------------------------------------- triangle mesh
+// smvsrecon --mesh: the faces survive the AABB clip
+// (delete_vertices_fix_faces, M2) and every vertex gets recalc_normals' angle
+// weighted normal (M3-M5).  A vertex belongs to one pixel and its faces lie in
+// that pixel's four incident blocks, whose face ids grow in the order
+// (x-1,y-1), (x,y-1), (x-1,y), (x,y), tri[0] before tri[1] (the topo pass's
+// walk): gathering them in that order adds the same terms in the same order as
+// the reference's scatter over the face list.  No atomics.
+struct MeshClip {
+    int on;
+    float3 lo, hi;
+};
+
+// the global pixel of corner cc of block (bx, by) of a view starting at off
+__device__ __forceinline__ size_t
+corner_pixel(size_t off, int w, int bx, int by, int cc)
+{
+    return off + (size_t)(by + (cc >> 1)) * w + bx + (cc & 1);
+}
+
+// the vertex ids of triangle t of block (bx, by) and whether the clip keeps
+// the face (M2 (a): every corner kept)
+__device__ __forceinline__ bool
+tri_vertices(const PointViewDev &P, const PointBufs &B, MeshClip clip, int bx, int by,
+    int t, uint32_t *ids)
+{
+    bool keep = true;
+    for (int k = 0; k < 3; ++k) {
+        ids[k] = B.vid[corner_pixel(P.off, P.w, bx, by, tri_corner(t, k))];
+        if (clip.on && outside_aabb(B.xyz + 3 * (size_t)ids[k], clip.lo, clip.hi))
+            keep = false;
+    }
+    return keep;
+}
+
+// M3 / M4 for face (a, b, c) = q[0..2]: the unit face normal and the angle at
+// corner k; -> false for a face of zero area (it adds nothing)
+__device__ __forceinline__ bool
+face_term(const float (*q)[3], int k, float *fn, float *weight)
+{
+#pragma clang fp contract(off)
+    float ab[3], bc[3], ca[3], nca[3];
+    for (int r = 0; r < 3; ++r) {
+        ab[r] = q[1][r] - q[0][r];
+        bc[r] = q[2][r] - q[1][r];
+        ca[r] = q[0][r] - q[2][r];
+        nca[r] = -ca[r];
+    }
+    fn[0] = ab[1] * nca[2] - ab[2] * nca[1];
+    fn[1] = ab[2] * nca[0] - ab[0] * nca[2];
+    fn[2] = ab[0] * nca[1] - ab[1] * nca[0];
+    float const fnl = sqrtf(dot3(fn, fn));
+    if (fnl == 0.0f)
+        return false;
+    for (int r = 0; r < 3; ++r)
+        fn[r] = fn[r] / fnl;
+    float const lab = sqrtf(dot3(ab, ab)), lbc = sqrtf(dot3(bc, bc)),
+        lca = sqrtf(dot3(ca, ca));
+    float cosine;
+    if (k == 0) {
+        cosine = dot3(ab, nca) / (lab * lca);
+    } else if (k == 1) {
+        float const nab[3] = { -ab[0], -ab[1], -ab[2] };
+        cosine = dot3(nab, bc) / (lab * lbc);
+    } else {
+        float const nbc[3] = { -bc[0], -bc[1], -bc[2] };
+        cosine = dot3(ca, nbc) / (lca * lbc);
+    }
+    cosine = cosine < -1.0f ? -1.0f : (cosine > 1.0f ? 1.0f : cosine);
+    *weight = acosf(cosine);
+    return true;
+}
+
+// recalc_normals as a gather: the vertex of pixel p sums fn * w over its kept
+// faces in face-id order, then normalises (M5); written to its pre-clip slot
+__global__ void __launch_bounds__(256)
+mesh_normals_kernel(const PointViewDev *__restrict__ pv, PointBufs B, MeshClip clip)
+{
+#pragma clang fp contract(off)
+    int v, x, y;
+    size_t p;
+    if (!point_thread(pv, v, x, y, p))
+        return;
+    if (!(B.meta[p] >> 5 & 1))
+        return;
+    PointViewDev const &P = pv[v];
+    float vn[3] = { 0.0f, 0.0f, 0.0f };
+    for (int b = 0; b < 4; ++b) {
+        int const bx = x - 1 + (b & 1), by = y - 1 + (b >> 1);
+        if (bx < 0 || by < 0)
+            continue;
+        int const c = B.code[P.off + (size_t)by * P.w + bx];
+        int const me = 3 - b;   // the pixel's corner in that block
+        for (int j = 0; j < 2; ++j) {
+            int const t = (c >> (3 * j)) & 7;
+            if (!(tri_mask(t) >> me & 1))
+                continue;
+            uint32_t ids[3];
+            if (!tri_vertices(P, B, clip, bx, by, t, ids))
+                continue;
+            float q[3][3];
+            int k_me = 0;
+            for (int k = 0; k < 3; ++k) {
+                for (int r = 0; r < 3; ++r)
+                    q[k][r] = B.xyz[3 * (size_t)ids[k] + r];
+                if (tri_corner(t, k) == me)
+                    k_me = k;
+            }
+            float fn[3], weight;
+            if (!face_term(q, k_me, fn, &weight))
+                continue;
+            for (int r = 0; r < 3; ++r)
+                vn[r] += fn[r] * weight;
+        }
+    }
+    float const vnl = sqrtf(dot3(vn, vn));
+    if (vnl > 0.0f)
+        for (int r = 0; r < 3; ++r)
+            vn[r] = vn[r] / vnl;
+    size_t const id = B.vid[p];
+    for (int r = 0; r < 3; ++r)
+        B.nrm[3 * id + r] = vn[r];
+}
+
+// per block: the number of its faces the clip keeps (their order is the
+// blocks' order, so an exclusive scan of these gives the new face ids)
+__global__ void __launch_bounds__(256)
+mesh_face_count_kernel(const PointViewDev *__restrict__ pv, PointBufs B, MeshClip clip,
+    unsigned long long *__restrict__ count)
+{
+    int v, x, y;
+    size_t p;
+    if (!point_thread(pv, v, x, y, p))
+        return;
+    int const c = B.code[p];
+    int n = 0;
+    for (int j = 0; j < 2; ++j) {
+        int const t = (c >> (3 * j)) & 7;
+        uint32_t ids[3];
+        if (t != 0 && tri_vertices(pv[v], B, clip, x, y, t, ids))
+            ++n;
+    }
+    count[p] = (unsigned long long)n;
+}
+
+// M2 (b): the kept faces at their scanned position, vertex ids through the
+// exclusive scan of the vertex keep flags (vmap)
+__global__ void __launch_bounds__(256)
+mesh_face_scatter_kernel(const PointViewDev *__restrict__ pv, PointBufs B, MeshClip clip,
+    const unsigned long long *__restrict__ at, const unsigned long long *__restrict__ vmap,
+    uint32_t *__restrict__ faces)
+{
+    int v, x, y;
+    size_t p;
+    if (!point_thread(pv, v, x, y, p))
+        return;
+    int const c = B.code[p];
+    size_t f = (size_t)at[p];
+    for (int j = 0; j < 2; ++j) {
+        int const t = (c >> (3 * j)) & 7;
+        uint32_t ids[3];
+        if (t == 0 || !tri_vertices(pv[v], B, clip, x, y, t, ids))
+            continue;
+        for (int k = 0; k < 3; ++k)
+            faces[3 * f + k] = (uint32_t)vmap[ids[k]];
+        ++f;
+    }
 }
 
 } // namespace smvs_hip
 
 struct smvs_points {
+    bool mesh = false;   // smvs_mesh_generate: no values, faces always
     int64_t n_points = 0, n_faces = 0;
     std::vector<float> xyz, nrm, conf, val;
     std::vector<uint8_t> rgb;
     std::vector<uint32_t> faces;
 };
 
-extern "C" int
-smvs_points_generate(int device, const smvs_point_view *views, int n_views,
-    const smvs_points_options *options, smvs_points **handle, int64_t *n_points)
+namespace {
+
+// what smvs_points_generate and smvs_mesh_generate ask of export_views
+struct ExportOptions {
+    bool cut, use_aabb, want_faces, mesh;
+    float aabb_min[3], aabb_max[3];
+    float dd_factor;
+};
+
+int
+export_views(int device, const smvs_point_view *views, int n_views,
+    ExportOptions const &opt, smvs_points **handle, int64_t *n_points)
 {
     SMVS_REQUIRE(handle != nullptr, "no handle pointer");
     *handle = nullptr;
     SMVS_REQUIRE(views != nullptr && n_views >= 1, "no views");
     SMVS_REQUIRE(n_views <= 4096, "too many views");
-    smvs_points_options opt = { 1, 0, { 0, 0, 0 }, { 0, 0, 0 }, 5.0f, 0 };
-    if (options != nullptr)
-        opt = *options;
     SMVS_REQUIRE(opt.dd_factor >= 0.0f && std::isfinite(opt.dd_factor),
         "dd_factor must be finite and >= 0");
-    SMVS_REQUIRE(!(opt.want_faces && opt.use_aabb),
-        "the face list is not kept together with the AABB clip");
     size_t total_pix = 0, max_pix = 0;
     for (int i = 0; i < n_views; ++i) {
         smvs_point_view const &in = views[i];
@@ -969,6 +1155,7 @@ smvs_points_generate(int device, const smvs_point_view *views, int n_views,
     }
     // vertex ids are 32-bit and the faces (<= 2 per pixel) as well
     SMVS_REQUIRE(total_pix < ((size_t)1 << 31), "too many pixels");
+    bool const faces_out = opt.want_faces || opt.mesh;
 
     WorkspaceLease lease(device);
     if (lease.w == nullptr)
@@ -1004,9 +1191,13 @@ smvs_points_generate(int device, const smvs_point_view *views, int n_views,
         out_at[k][1] = carve(12 * N);
         out_at[k][2] = carve(3 * N);
         out_at[k][3] = carve(4 * N);
-        out_at[k][4] = carve(4 * N);
+        out_at[k][4] = opt.mesh ? 0 : carve(4 * N);
     }
-    size_t const faces_at = opt.want_faces ? carve(4 * 3 * 2 * N) : 0;
+    size_t const faces_at = faces_out ? carve(4 * 3 * 2 * N) : 0;
+    // the clipped mesh: kept faces per block and their scan
+    bool const clip_faces = opt.mesh && opt.use_aabb;
+    size_t const fscan_at = clip_faces ? carve(8 * N) : 0;
+    size_t const ftiles_at = clip_faces ? carve(8 * (n_tiles + 1)) : 0;
     char *slab = nullptr;
     int rc;
     if ((rc = ws.ensure(0, total, &slab)) != SMVS_OK)
@@ -1031,7 +1222,7 @@ smvs_points_generate(int device, const smvs_point_view *views, int n_views,
         P.channels = in.channels;
         P.off = off;
         // generate_mesh triangulates the cut maps, or the depth maps (:211-213)
-        P.dm = opt.cut_surfaces ? V.cut : V.depth_ray;
+        P.dm = opt.cut ? V.cut : V.depth_ray;
         P.image = reinterpret_cast<uint8_t *>(slab + offsets[5 * i + 4]);
         off += npix;
         if ((rc = ws.upload(V.depth_ray, in.depth, sizeof(float) * npix))
@@ -1045,7 +1236,7 @@ smvs_points_generate(int device, const smvs_point_view *views, int n_views,
     if ((rc = ws.upload(d_table, table.data(), sizeof(MeshViewDev) * n_views))
         || (rc = ws.upload(d_ptable, ptable.data(), sizeof(PointViewDev) * n_views)))
         return rc;
-    if ((rc = launch_prepare_and_cut(stream, d_table, table, opt.cut_surfaces != 0)))
+    if ((rc = launch_prepare_and_cut(stream, d_table, table, opt.cut)))
         return rc;
 
     PointBufs B;
@@ -1062,11 +1253,17 @@ smvs_points_generate(int device, const smvs_point_view *views, int n_views,
         b.nrm = reinterpret_cast<float *>(slab + out_at[k][1]);
         b.rgb = reinterpret_cast<uint8_t *>(slab + out_at[k][2]);
         b.conf = reinterpret_cast<float *>(slab + out_at[k][3]);
-        b.val = reinterpret_cast<float *>(slab + out_at[k][4]);
+        b.val = opt.mesh ? nullptr : reinterpret_cast<float *>(slab + out_at[k][4]);
     };
     outputs(B, 0);
-    B.faces = opt.want_faces ? reinterpret_cast<uint32_t *>(slab + faces_at) : nullptr;
+    uint32_t *const faces = faces_out ? reinterpret_cast<uint32_t *>(slab + faces_at) : nullptr;
+    // with the clip the mesh's faces are written by the scatter below
+    B.faces = clip_faces ? nullptr : faces;
     B.dd_factor = opt.dd_factor;
+    MeshClip clip;
+    clip.on = opt.use_aabb ? 1 : 0;
+    clip.lo = make_float3(opt.aabb_min[0], opt.aabb_min[1], opt.aabb_min[2]);
+    clip.hi = make_float3(opt.aabb_max[0], opt.aabb_max[1], opt.aabb_max[2]);
 
     dim3 const grid((unsigned)((max_pix + 255) / 256), (unsigned)n_views);
     hipLaunchKernelGGL(points_code_kernel, grid, dim3(256), 0, stream, d_table, d_ptable, B);
@@ -1078,27 +1275,49 @@ smvs_points_generate(int device, const smvs_point_view *views, int n_views,
     hipLaunchKernelGGL(points_topo_kernel, grid, dim3(256), 0, stream, d_ptable, B);
     for (int r = 0; r < 3; ++r)
         hipLaunchKernelGGL(points_ring_kernel, grid, dim3(256), 0, stream, d_ptable, B, r & 1);
-    hipLaunchKernelGGL(points_emit_kernel, grid, dim3(256), 0, stream, d_table, d_ptable, B, 1);
+    if (opt.mesh) {
+        hipLaunchKernelGGL(points_emit_kernel<true>, grid, dim3(256), 0, stream, d_table,
+            d_ptable, B, 1);
+        hipLaunchKernelGGL(mesh_normals_kernel, grid, dim3(256), 0, stream, d_ptable, B,
+            clip);
+    } else
+        hipLaunchKernelGGL(points_emit_kernel<false>, grid, dim3(256), 0, stream, d_table,
+            d_ptable, B, 1);
     SMVS_HIP_CHECK(hipGetLastError());
     unsigned long long sums = 0;
     if ((rc = ws.download(&sums, B.tiles + n_tiles, sizeof(sums))))
         return rc;
     size_t n_vert = (size_t)(sums & 0xffffffffull);
-    size_t const n_face = (size_t)(sums >> 32);
+    size_t n_face = (size_t)(sums >> 32);
     PointBufs O = B;
     if (opt.use_aabb && n_vert > 0) {
-        float3 const lo = make_float3(opt.aabb_min[0], opt.aabb_min[1], opt.aabb_min[2]);
-        float3 const hi = make_float3(opt.aabb_max[0], opt.aabb_max[1], opt.aabb_max[2]);
         unsigned const blocks = (unsigned)((n_vert + 255) / 256);
         hipLaunchKernelGGL(points_keep_kernel, dim3(blocks), dim3(256), 0, stream,
-            B.xyz, n_vert, lo, hi, B.scan);
+            B.xyz, n_vert, clip.lo, clip.hi, B.scan);
         SMVS_HIP_CHECK(hipGetLastError());
         if ((rc = exclusive_scan(stream, B.scan, n_vert, B.tiles)))
             return rc;
         outputs(O, 1);
         hipLaunchKernelGGL(points_compact_kernel, dim3(blocks), dim3(256), 0, stream,
-            n_vert, lo, hi, B.scan, B, O);
+            n_vert, clip.lo, clip.hi, B.scan, B, O);
         SMVS_HIP_CHECK(hipGetLastError());
+        if (clip_faces) {
+            unsigned long long *const fscan =
+                reinterpret_cast<unsigned long long *>(slab + fscan_at);
+            unsigned long long *const ftiles =
+                reinterpret_cast<unsigned long long *>(slab + ftiles_at);
+            hipLaunchKernelGGL(mesh_face_count_kernel, grid, dim3(256), 0, stream,
+                d_ptable, B, clip, fscan);
+            SMVS_HIP_CHECK(hipGetLastError());
+            if ((rc = exclusive_scan(stream, fscan, N, ftiles)))
+                return rc;
+            hipLaunchKernelGGL(mesh_face_scatter_kernel, grid, dim3(256), 0, stream,
+                d_ptable, B, clip, fscan, B.scan, faces);
+            SMVS_HIP_CHECK(hipGetLastError());
+            if ((rc = ws.download(&sums, ftiles + n_tiles, sizeof(sums))))
+                return rc;
+            n_face = (size_t)sums;
+        }
         if ((rc = ws.download(&sums, B.tiles + (n_vert + SCAN_TILE - 1) / SCAN_TILE,
                 sizeof(sums))))
             return rc;
@@ -1110,20 +1329,21 @@ smvs_points_generate(int device, const smvs_point_view *views, int n_views,
                     sizeof(float) * table[i].w * table[i].h)))
             return rc;
     smvs_points *h = new smvs_points;
+    h->mesh = opt.mesh;
     h->n_points = (int64_t)n_vert;
-    h->n_faces = opt.want_faces ? (int64_t)n_face : 0;
+    h->n_faces = faces_out ? (int64_t)n_face : 0;
     h->xyz.resize(3 * n_vert);
     h->nrm.resize(3 * n_vert);
     h->rgb.resize(3 * n_vert);
     h->conf.resize(n_vert);
-    h->val.resize(n_vert);
+    h->val.resize(opt.mesh ? 0 : n_vert);
     h->faces.resize(3 * (size_t)h->n_faces);
     if ((rc = ws.download(h->xyz.data(), O.xyz, 12 * n_vert))
         || (rc = ws.download(h->nrm.data(), O.nrm, 12 * n_vert))
         || (rc = ws.download(h->rgb.data(), O.rgb, 3 * n_vert))
         || (rc = ws.download(h->conf.data(), O.conf, 4 * n_vert))
-        || (rc = ws.download(h->val.data(), O.val, 4 * n_vert))
-        || (rc = ws.download(h->faces.data(), B.faces, 12 * (size_t)h->n_faces))) {
+        || (rc = ws.download(h->val.data(), O.val, 4 * h->val.size()))
+        || (rc = ws.download(h->faces.data(), faces, 12 * (size_t)h->n_faces))) {
         delete h;
         return rc;
     }
@@ -1131,6 +1351,52 @@ smvs_points_generate(int device, const smvs_point_view *views, int n_views,
     if (n_points != nullptr)
         *n_points = h->n_points;
     return SMVS_OK;
+}
+
+} // namespace
+
+extern "C" int
+smvs_points_generate(int device, const smvs_point_view *views, int n_views,
+    const smvs_points_options *options, smvs_points **handle, int64_t *n_points)
+{
+    SMVS_REQUIRE(handle != nullptr, "no handle pointer");
+    *handle = nullptr;
+    smvs_points_options opt = { 1, 0, { 0, 0, 0 }, { 0, 0, 0 }, 5.0f, 0 };
+    if (options != nullptr)
+        opt = *options;
+    SMVS_REQUIRE(!(opt.want_faces && opt.use_aabb),
+        "the face list is not kept together with the AABB clip");
+    ExportOptions e;
+    e.cut = opt.cut_surfaces != 0;
+    e.use_aabb = opt.use_aabb != 0;
+    e.want_faces = opt.want_faces != 0;
+    e.mesh = false;
+    std::copy(opt.aabb_min, opt.aabb_min + 3, e.aabb_min);
+    std::copy(opt.aabb_max, opt.aabb_max + 3, e.aabb_max);
+    e.dd_factor = opt.dd_factor;
+    return export_views(device, views, n_views, e, handle, n_points);
+}
+
+extern "C" int
+smvs_mesh_generate(int device, const smvs_point_view *views, int n_views,
+    const smvs_mesh_options *options, smvs_points **handle, int64_t *n_vertices,
+    int64_t *n_faces)
+{
+    smvs_mesh_options opt = { 1, 0, { 0, 0, 0 }, { 0, 0, 0 }, 5.0f };
+    if (options != nullptr)
+        opt = *options;
+    ExportOptions e;
+    e.cut = opt.cut_surfaces != 0;
+    e.use_aabb = opt.use_aabb != 0;
+    e.want_faces = true;
+    e.mesh = true;
+    std::copy(opt.aabb_min, opt.aabb_min + 3, e.aabb_min);
+    std::copy(opt.aabb_max, opt.aabb_max + 3, e.aabb_max);
+    e.dd_factor = opt.dd_factor;
+    int const rc = export_views(device, views, n_views, e, handle, n_vertices);
+    if (rc == SMVS_OK && n_faces != nullptr)
+        *n_faces = (*handle)->n_faces;
+    return rc;
 }
 
 extern "C" int
@@ -1149,6 +1415,8 @@ smvs_points_download(const smvs_points *handle, float *xyz, float *normals,
     uint8_t *rgb, float *confidence, float *value, uint32_t *faces)
 {
     SMVS_REQUIRE(handle != nullptr, "no handle");
+    SMVS_REQUIRE(!(handle->mesh && value != nullptr),
+        "a triangle mesh has no values");
     auto copy = [](void *dst, auto const &src) {
         if (dst != nullptr && !src.empty())
             memcpy(dst, src.data(), src.size() * sizeof(src[0]));

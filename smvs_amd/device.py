@@ -502,16 +502,9 @@ class PointsOptions(C.Structure):
                 ("dd_factor", C.c_float), ("want_faces", C.c_int)]
 
 
-def generate_points(cams, depths, normals, images, cut=True, aabb=None, faces=False,
-                    dd_factor=5.0, cut_maps=False, device=0):
-    """MeshGenerator::generate_mesh's point cloud over all views on the device
-    (smvs_points_generate).  cams: objects with .flen, .R, .t; depths[i] (h, w)
-    ray-length depth; normals[i] (h, w, 3) camera space; images[i] (h, w) or
-    (h, w, c) uint8 at the depth map's size.  aabb: None or (min3, max3).
-    Returns a dict of numpy arrays: xyz, normals (n, 3) float32, rgb (n, 3)
-    uint8, confidence, value (n,) float32, faces (m, 3) uint32 when asked
-    for, cut_depth (the triangulated maps) when cut_maps."""
-    lib = _capi.load()
+def _point_views(cams, depths, normals, images, cut_maps):
+    """smvs_point_view records of the views (and the arrays they point to,
+    which have to outlive the call)."""
     n = len(cams)
     if not (len(depths) == len(normals) == len(images) == n):
         raise ValueError("cams, depths, normals and images differ in length")
@@ -535,6 +528,21 @@ def generate_points(cams, depths, normals, images, cut=True, aabb=None, faces=Fa
         arr[i].image = _p(im[i], _u8p)
         arr[i].channels = 1 if im[i].ndim == 2 else im[i].shape[2]
         arr[i].cut_depth = _p(cuts[i], _fp) if cut_maps else None
+    return arr, cuts, (d, nm, im)
+
+
+def generate_points(cams, depths, normals, images, cut=True, aabb=None, faces=False,
+                    dd_factor=5.0, cut_maps=False, device=0):
+    """MeshGenerator::generate_mesh's point cloud over all views on the device
+    (smvs_points_generate).  cams: objects with .flen, .R, .t; depths[i] (h, w)
+    ray-length depth; normals[i] (h, w, 3) camera space; images[i] (h, w) or
+    (h, w, c) uint8 at the depth map's size.  aabb: None or (min3, max3).
+    Returns a dict of numpy arrays: xyz, normals (n, 3) float32, rgb (n, 3)
+    uint8, confidence, value (n,) float32, faces (m, 3) uint32 when asked
+    for, cut_depth (the triangulated maps) when cut_maps."""
+    lib = _capi.load()
+    n = len(cams)
+    arr, cuts, _keep = _point_views(cams, depths, normals, images, cut_maps)
     opt = PointsOptions()
     opt.cut_surfaces = int(bool(cut))
     opt.use_aabb = int(aabb is not None)
@@ -563,6 +571,52 @@ def generate_points(cams, depths, normals, images, cut=True, aabb=None, faces=Fa
         lib.smvs_points_release(handle)
     if faces:
         out["faces"] = fc
+    if cut_maps:
+        out["cut_depth"] = cuts
+    return out
+
+
+class MeshOptions(C.Structure):
+    """smvs_mesh_options of include/smvs_hip.h."""
+    _fields_ = [("cut_surfaces", C.c_int), ("use_aabb", C.c_int),
+                ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3),
+                ("dd_factor", C.c_float)]
+
+
+def generate_mesh(cams, depths, normals, images, cut=True, aabb=None, dd_factor=5.0,
+                  cut_maps=False, device=0):
+    """smvsrecon --mesh's triangle mesh over all views on the device
+    (smvs_mesh_generate): merged in view-list order, clipped to aabb (None or
+    (min3, max3)) with delete_vertices_fix_faces, vertex normals of
+    recalc_normals.  Inputs as generate_points.
+    Returns a dict of numpy arrays: xyz, normals (n, 3) float32, rgb (n, 3)
+    uint8, confidence (n,) float32, faces (m, 3) uint32, and cut_depth (the
+    triangulated maps) when cut_maps."""
+    lib = _capi.load()
+    n = len(cams)
+    arr, cuts, _keep = _point_views(cams, depths, normals, images, cut_maps)
+    opt = MeshOptions()
+    opt.cut_surfaces = int(bool(cut))
+    opt.use_aabb = int(aabb is not None)
+    if aabb is not None:
+        for k in range(3):
+            opt.aabb_min[k] = float(aabb[0][k])
+            opt.aabb_max[k] = float(aabb[1][k])
+    opt.dd_factor = float(dd_factor)
+    handle = C.c_void_p()
+    n_vertices, n_faces = C.c_int64(), C.c_int64()
+    check(lib.smvs_mesh_generate(device, arr if n else None, n, C.byref(opt),
+                                 C.byref(handle), C.byref(n_vertices), C.byref(n_faces)))
+    try:
+        k = n_vertices.value
+        out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
+               "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
+               "faces": np.zeros((n_faces.value, 3), np.uint32)}
+        check(lib.smvs_points_download(handle, _p(out["xyz"], _fp), _p(out["normals"], _fp),
+                                       _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
+                                       None, _p(out["faces"], _u32p)))
+    finally:
+        lib.smvs_points_release(handle)
     if cut_maps:
         out["cut_depth"] = cuts
     return out

@@ -574,16 +574,8 @@ class PointCloudSettings(C.Structure):
                 ("aabb_max", C.c_float * 3), ("device", C.c_int)]
 
 
-def generate_point_cloud(scene_dir, view_ids=None, image_embedding="undistorted",
-                         input_scale=0, use_shading=False, cut=True, aabb=None,
-                         mesh=False, simplify=False, device=0):
-    """smvsrecon's generate_mesh (app/smvsrecon.cc:278-343) on a reconstructed
-    scene through smvs_amd::generate_scene_point_cloud: the point cloud of the
-    views' smvs-{B,S}<input_scale> embeddings, written as
-    <scene>/smvs-{B,S}<input_scale>.ply (and smvs-cut.mvei per view when
-    cutting).  aabb: None or (min3, max3).  mesh / simplify (--mesh,
-    --simplify) are refused.  Returns (ply path, number of points)."""
-    lib = load()
+def _point_cloud_settings(image_embedding, input_scale, use_shading, cut, aabb, mesh,
+                          simplify, device):
     st = PointCloudSettings()
     st.image_embedding = image_embedding.encode()
     st.input_scale = int(input_scale)
@@ -597,6 +589,22 @@ def generate_point_cloud(scene_dir, view_ids=None, image_embedding="undistorted"
             st.aabb_min[k] = float(aabb[0][k])
             st.aabb_max[k] = float(aabb[1][k])
     st.device = int(device)
+    return st
+
+
+def generate_point_cloud(scene_dir, view_ids=None, image_embedding="undistorted",
+                         input_scale=0, use_shading=False, cut=True, aabb=None,
+                         mesh=False, simplify=False, device=0):
+    """smvsrecon's generate_mesh (app/smvsrecon.cc:278-343) on a reconstructed
+    scene through smvs_amd::generate_scene_point_cloud: the point cloud of the
+    views' smvs-{B,S}<input_scale> embeddings, written as
+    <scene>/smvs-{B,S}<input_scale>.ply (and smvs-cut.mvei per view when
+    cutting).  aabb: None or (min3, max3).  mesh / simplify (--mesh,
+    --simplify) are refused (the mesh: generate_mesh).  Returns (ply path,
+    number of points)."""
+    lib = load()
+    st = _point_cloud_settings(image_embedding, input_scale, use_shading, cut, aabb, mesh,
+                               simplify, device)
     ids = None if view_ids is None else np.asarray(view_ids, dtype=np.int32)
     path = C.create_string_buffer(4096)
     n = C.c_int64(0)
@@ -606,6 +614,29 @@ def generate_point_cloud(scene_dir, view_ids=None, image_embedding="undistorted"
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
     return path.value.decode(), n.value
+
+
+def generate_mesh(scene_dir, view_ids=None, image_embedding="undistorted", input_scale=0,
+                  use_shading=False, cut=True, aabb=None, simplify=False, device=0):
+    """smvsrecon --mesh on a reconstructed scene through
+    smvs_amd::generate_scene_mesh: the triangle mesh of the views'
+    smvs-{B,S}<input_scale> embeddings, written as
+    <scene>/smvs-m-{B,S}<input_scale>.ply (and smvs-cut.mvei per view when
+    cutting).  aabb: None or (min3, max3); simplify (--simplify) is refused.
+    Returns (ply path, number of vertices, number of faces)."""
+    lib = load()
+    st = _point_cloud_settings(image_embedding, input_scale, use_shading, cut, aabb, True,
+                               simplify, device)
+    ids = None if view_ids is None else np.asarray(view_ids, dtype=np.int32)
+    path = C.create_string_buffer(4096)
+    nv, nf = C.c_int64(0), C.c_int64(0)
+    rc = lib.smvs_host_generate_mesh(
+        scene_dir.encode(), C.byref(st), ids.ctypes.data_as(_i32p) if ids is not None else None,
+        C.c_int(0 if ids is None else ids.size), path, C.c_int(len(path)), C.byref(nv),
+        C.byref(nf))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    return path.value.decode(), nv.value, nf.value
 
 
 def save_ply_points(path, xyz, normals, rgb, confidence, value):
@@ -625,5 +656,25 @@ def save_ply_points(path, xyz, normals, rgb, confidence, value):
         path.encode(), xyz.ctypes.data_as(fp), normals.ctypes.data_as(fp),
         rgb.ctypes.data_as(C.POINTER(C.c_uint8)), confidence.ctypes.data_as(fp),
         value.ctypes.data_as(fp), C.c_int64(n))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+
+
+def save_ply_mesh(path, xyz, normals, rgb, confidence, faces):
+    """The host's PLY writer of the triangle mesh (save_ply_mesh)."""
+    lib = load()
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    normals = np.ascontiguousarray(normals, np.float32)
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    confidence = np.ascontiguousarray(confidence, np.float32)
+    faces = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    n = confidence.size
+    if xyz.shape != (n, 3) or normals.shape != (n, 3) or rgb.shape != (n, 3):
+        raise ValueError("save_ply_mesh: attribute shapes differ")
+    fp = C.POINTER(C.c_float)
+    rc = lib.smvs_host_save_ply_mesh(
+        path.encode(), xyz.ctypes.data_as(fp), normals.ctypes.data_as(fp),
+        rgb.ctypes.data_as(C.POINTER(C.c_uint8)), confidence.ctypes.data_as(fp),
+        C.c_int64(n), faces.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_int64(len(faces)))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
