@@ -601,6 +601,53 @@ int smvs_mesh_generate(int device, const smvs_point_view *views, int n_views,
     const smvs_mesh_options *options, smvs_points **handle,
     int64_t *n_vertices, int64_t *n_faces);
 
+/* smvsrecon --simplify (MeshGenerator::Options::simplify, mesh_generator.cc:
+ * 238-243): per view DepthTriangulator::approximate_triangulation
+ * (depth_triangulator.cc:27-172) -- Garland and Heckbert's greedy insertion
+ * into an incremental Delaunay triangulation (delaunay_2d.cc, quad_edge.h) --
+ * instead of the full triangulation, then the confidences, scale values,
+ * normal lookup and merge of smvs_points_generate / smvs_mesh_generate on the
+ * irregular meshes.  Rows S1-S13 of DESIGN.md section 9.7 pin the semantics.
+ * One persistent workgroup per view runs the insertion loop.
+ *   create_triangle_mesh  0: the point cloud (values, looked-up normals; the
+ *                            faces too unless use_aabb), 1: the mesh of
+ *                            --mesh --simplify (recalc_normals, no values)
+ *   max_vertices          -1: pixels / 40; the number of loop ITERATIONS (S1)
+ *   max_error             -1.0: (max depth - mean depth) * 1e-3 (S2)
+ * options NULL = the reference's defaults (cut, no AABB, point cloud, -1, -1).
+ * Refused as argument errors: image size != depth size is the caller's to
+ * keep (one width / height per view), width or height < 2 or > 4096,
+ * non-finite or negative depths.  A view whose loop hits a safety cap (the
+ * walks over the subdivision are bounded) ends the call with SMVS_ERR_STATE. */
+typedef struct {
+    int cut_surfaces;     /* MeshGenerator::Options::cut_surfaces (--no-cut: 0) */
+    int use_aabb;         /* --aabb: delete vertices outside [aabb_min, aabb_max] */
+    float aabb_min[3], aabb_max[3];
+    int create_triangle_mesh;
+    int max_vertices;
+    double max_error;
+} smvs_simplify_options;
+
+int smvs_simplified_generate(int device, const smvs_point_view *views, int n_views,
+    const smvs_simplify_options *options, smvs_points **handle,
+    int64_t *n_vertices, int64_t *n_faces);
+
+/* The greedy triangulation of ONE depth map in pixel space, before any
+ * clean-up (S1-S8), so that a divergence from the restatement can be located
+ * at the insertion where it happens.  Outputs (any may be NULL):
+ *   iterations       loop iterations run (S1: no-op insertions count)
+ *   vertices         n_vertices * 3 doubles (x, y, z), the four corners first;
+ *                    room for min(budget, pixels) + 5 vertices
+ *   triangles        n_triangles * 3 vertex ids per triangle id (S4's order);
+ *                    room for twice as many triangles as vertices
+ *   num_zero_depths  per triangle
+ *   clocks4          100 MHz ticks the workgroup spent in selection, the
+ *                    Delaunay lane, the rescans, and in total */
+int smvs_simplify_triangulate(int device, const float *depth, int width, int height,
+    int max_vertices, double max_error, int64_t *iterations, int64_t *n_vertices,
+    double *vertices, int64_t *n_triangles, uint32_t *triangles,
+    int32_t *num_zero_depths, uint64_t *clocks4);
+
 /* The context-free entry points above (smvs_sgm_run, smvs_sgm_depth_for_view,
  * smvs_bilateral_upsample, smvs_cut_depth_maps) draw their device buffers,
  * stream and pinned staging memory from a per-device pool of workspaces that

@@ -181,7 +181,8 @@ int smvs_host_reconstruct_scene(const char *scene_dir,
  * point cloud of the views' <dm_name> / <dm_name>N / <input> embeddings (cut
  * on the device, smvs_points_generate), smvs-cut.mvei per view when cutting,
  * the AABB clip, <scene>/smvs-{B,S}<input_scale>.ply.  create_triangle_mesh
- * (--mesh: smvs_host_generate_mesh) and simplify (--simplify) are refused.  view_ids may be NULL
+ * (--mesh: smvs_host_generate_mesh) and simplify (--simplify:
+ * smvs_host_generate_simplified) are refused.  view_ids may be NULL
  * (every view).  ply_path (may be NULL) receives the file name. */
 typedef struct {
     const char *image_embedding;    /* "undistorted" */
@@ -189,7 +190,7 @@ typedef struct {
     int use_shading;                /* names smvs-S / smvs-B */
     int cut_surface;                /* 0: --no-cut */
     int create_triangle_mesh;       /* --mesh: refused */
-    int simplify;                   /* --simplify: refused */
+    int simplify;                   /* --simplify: refused (smvs_host_generate_simplified) */
     int use_aabb;
     float aabb_min[3], aabb_max[3];
     int device;
@@ -206,8 +207,18 @@ int smvs_host_save_ply_points(const char *path, const float *xyz, const float *n
  * clip with delete_vertices_fix_faces, recalc_normals), smvs-cut.mvei per
  * view when cutting, <scene>/smvs-m-{B,S}<input_scale>.ply.  The settings are
  * the point cloud's (create_triangle_mesh is implied and ignored); simplify
- * (--simplify) is refused. */
+ * (--simplify) is refused: smvs_host_generate_simplified. */
 int smvs_host_generate_mesh(const char *scene_dir,
+    const smvs_host_point_cloud_settings *settings, const int *view_ids,
+    int n_view_ids, char *ply_path, int ply_path_capacity, int64_t *n_vertices,
+    int64_t *n_faces);
+/* smvsrecon --simplify (and --mesh --simplify with create_triangle_mesh):
+ * approximate_triangulation per view on the device (smvs_simplified_generate,
+ * DESIGN.md section 9.7), smvs-cut.mvei per view when cutting, the reference's
+ * file names: <scene>/smvs-{B,S}<input_scale>.ply, with the mesh
+ * smvs-m-{B,S}<input_scale>.ply.  The settings are the point cloud's; simplify
+ * is implied and ignored.  *n_faces is 0 for the point cloud. */
+int smvs_host_generate_simplified(const char *scene_dir,
     const smvs_host_point_cloud_settings *settings, const int *view_ids,
     int n_view_ids, char *ply_path, int ply_path_capacity, int64_t *n_vertices,
     int64_t *n_faces);

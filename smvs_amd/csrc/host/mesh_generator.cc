@@ -160,6 +160,53 @@ MeshGenerator::generate_triangle_mesh(std::vector<SceneView> const& inputviews,
 }
 
 void
+MeshGenerator::generate_simplified(std::vector<SceneView> const& inputviews,
+    std::string const& image_name, std::string const& dm_name, bool create_triangle_mesh,
+    PointCloud* points, TriangleMesh* mesh, int max_vertices, double max_error)
+{
+    if ((create_triangle_mesh ? (void*)mesh : (void*)points) == nullptr)
+        throw std::invalid_argument("MeshGenerator::generate_simplified: no output");
+    Inputs in;
+    load_views(inputviews, image_name, dm_name, in);
+    if (in.views.empty())
+        return;
+    smvs_simplify_options so;
+    so.cut_surfaces = opts.cut_surfaces ? 1 : 0;
+    so.use_aabb = opts.use_aabb ? 1 : 0;
+    std::copy(opts.aabb_min, opts.aabb_min + 3, so.aabb_min);
+    std::copy(opts.aabb_max, opts.aabb_max + 3, so.aabb_max);
+    so.create_triangle_mesh = create_triangle_mesh ? 1 : 0;
+    so.max_vertices = max_vertices;
+    so.max_error = max_error;
+    smvs_points* handle = nullptr;
+    int64_t nv = 0, nf = 0;
+    check_status(smvs_simplified_generate(opts.device, in.pv.data(), (int)in.pv.size(), &so,
+        &handle, &nv, &nf), "smvs_simplified_generate");
+    std::size_t const n = (std::size_t)nv;
+    int rc;
+    if (create_triangle_mesh) {
+        mesh->xyz.resize(3 * n);
+        mesh->normals.resize(3 * n);
+        mesh->colors.resize(3 * n);
+        mesh->confidences.resize(n);
+        mesh->faces.resize(3 * (std::size_t)nf);
+        rc = smvs_points_download(handle, mesh->xyz.data(), mesh->normals.data(),
+            mesh->colors.data(), mesh->confidences.data(), nullptr, mesh->faces.data());
+    } else {
+        points->xyz.resize(3 * n);
+        points->normals.resize(3 * n);
+        points->colors.resize(3 * n);
+        points->confidences.resize(n);
+        points->values.resize(n);
+        rc = smvs_points_download(handle, points->xyz.data(), points->normals.data(),
+            points->colors.data(), points->confidences.data(), points->values.data(), nullptr);
+    }
+    smvs_points_release(handle);
+    check_status(rc, "smvs_points_download");
+    save_cut_maps(in);
+}
+
+void
 save_ply_points(std::string const& path, PointCloud const& points)
 {
     std::size_t const n = points.size();
@@ -350,6 +397,34 @@ generate_scene_mesh(std::string const& scene_path, PointCloudSettings const& con
         *n_vertices = mesh->size();
     if (n_faces != nullptr)
         *n_faces = mesh->num_faces();
+    return meshname;
+}
+
+std::string
+generate_scene_simplified(std::string const& scene_path, PointCloudSettings const& conf,
+    std::size_t* n_vertices, std::size_t* n_faces)
+{
+    SceneInputs const in = scene_inputs(scene_path, conf);
+    MeshGenerator meshgen(generator_options(conf));
+    std::string const meshname = output_name(*in.scene, conf, conf.create_triangle_mesh);
+    std::size_t nv = 0, nf = 0;
+    if (conf.create_triangle_mesh) {
+        TriangleMesh mesh;
+        meshgen.generate_simplified(in.views, in.input_name, in.dm_name, true, nullptr, &mesh);
+        save_ply_mesh(meshname, mesh);
+        nv = mesh.size();
+        nf = mesh.num_faces();
+    } else {
+        PointCloud points;
+        meshgen.generate_simplified(in.views, in.input_name, in.dm_name, false, &points,
+            nullptr);
+        save_ply_points(meshname, points);
+        nv = points.size();
+    }
+    if (n_vertices != nullptr)
+        *n_vertices = nv;
+    if (n_faces != nullptr)
+        *n_faces = nf;
     return meshname;
 }
 

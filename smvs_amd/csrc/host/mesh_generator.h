@@ -1,7 +1,8 @@
 // smvs::MeshGenerator's point-cloud and triangle-mesh paths (reference:
 // lib/mesh_generator.h, lib/mesh_generator.cc:160-299) and smvsrecon's
 // generate_mesh (app/smvsrecon.cc:278-343) on top of smvs_points_generate and
-// smvs_mesh_generate.  The cut, the triangulation and every per-vertex value
+// smvs_mesh_generate, and the simplified triangulation (--simplify) on top of
+// smvs_simplified_generate.  The cut, the triangulation and every per-vertex value
 // run on the device; the host loads the embeddings, writes smvs-cut per view
 // and streams the PLY file.
 #pragma once
@@ -45,7 +46,7 @@ public:
     {
         std::size_t num_threads = 0;        // (the device does the work)
         bool cut_surfaces = true;
-        bool simplify = false;              // refused: serial approximate_triangulation
+        bool simplify = false;              // refused here: generate_simplified is the entry
         bool create_triangle_mesh = false;  // generate_mesh refuses it: use
                                             // generate_triangle_mesh
         int device = 0;
@@ -64,6 +65,16 @@ public:
     // and smvs-cut as generate_mesh
     TriangleMesh::Ptr generate_triangle_mesh(std::vector<SceneView> const& views,
         std::string const& image_name, std::string const& dm_name);
+
+    // Options::simplify (approximate_triangulation per view, DESIGN.md section
+    // 9.7) on smvs_simplified_generate: the point cloud (points != nullptr) or,
+    // with create_triangle_mesh, the mesh of --mesh --simplify (mesh !=
+    // nullptr); views and smvs-cut as generate_mesh.  max_vertices / max_error:
+    // -1 = approximate_triangulation's defaults
+    void generate_simplified(std::vector<SceneView> const& views,
+        std::string const& image_name, std::string const& dm_name,
+        bool create_triangle_mesh, PointCloud* points, TriangleMesh* mesh,
+        int max_vertices = -1, double max_error = -1.0);
 
 private:
     struct Inputs;
@@ -95,7 +106,8 @@ struct PointCloudSettings
     bool cut_surface = true;            // --no-cut
     bool create_triangle_mesh = false;  // --mesh: generate_scene_mesh; refused
                                         // by generate_scene_point_cloud
-    bool simplify = false;              // --simplify: refused
+    bool simplify = false;              // --simplify: generate_scene_simplified;
+                                        // refused by the two entries above
     bool use_aabb = false;
     float aabb_min[3] = { 0, 0, 0 }, aabb_max[3] = { 0, 0, 0 };
     int device = 0;
@@ -109,6 +121,14 @@ std::string generate_scene_point_cloud(std::string const& scene_path,
 // the same with --mesh: the triangle mesh, <scene>/smvs-m-{B,S}<input_scale>.ply;
 // -> the file written
 std::string generate_scene_mesh(std::string const& scene_path,
+    PointCloudSettings const& settings, std::size_t* n_vertices = nullptr,
+    std::size_t* n_faces = nullptr);
+
+// the same with --simplify (and --mesh when settings.create_triangle_mesh):
+// the file names are the reference's, smvs-{B,S}<scale>.ply or
+// smvs-m-{B,S}<scale>.ply (--simplify has no name of its own); -> the file
+// written.  settings.simplify is implied.
+std::string generate_scene_simplified(std::string const& scene_path,
     PointCloudSettings const& settings, std::size_t* n_vertices = nullptr,
     std::size_t* n_faces = nullptr);
 

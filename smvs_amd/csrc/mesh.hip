@@ -15,64 +15,13 @@
 // fill_cam_to_world, fill_camera_pos, depthmap_convert_conventions) follow the
 // assumptions listed in tests/golden/README.md [MVE-unverified].
 #include "common.h"
+#include "mesh_shared.h"
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 namespace smvs_hip {
-
-struct MeshViewDev {
-    int w, h;
-    float invproj[9];   // CameraInfo::fill_inverse_calibration
-    float KR[9];        // ViewProjection::KR = K * R
-    float t[3];         // ViewProjection::t = KR * camera position
-    float rot[9];       // world -> camera rotation
-    float c2w_t[3];     // translation column of the cam-to-world matrix
-    float *depth_z;     // depthmaps[i] after depthmap_convert_conventions(false)
-    float *depth_ray;   // cutmaps_j[i]: the input ray-length depth
-    float *cut;         // cutmaps[i]
-    float *normals;     // world space after the preparation pass
-};
-
-__device__ __forceinline__ float
-dot3(const float *a, const float *b)
-{
-#pragma clang fp contract(off)
-    float s = 0.0f;
-    s += a[0] * b[0];
-    s += a[1] * b[1];
-    s += a[2] * b[2];
-    return s;
-}
-
-// mve::geom::pixel_3dpos followed by Matrix4f::mult(pos, 1) with the
-// cam-to-world matrix (mesh_generator.cc:80-82, 120-123)
-__device__ __forceinline__ void
-world_point(MeshViewDev const &V, int x, int y, float depth, float *pos)
-{
-#pragma clang fp contract(off)
-    float const px = (float)x + 0.5f, py = (float)y + 0.5f;
-    float v[3];
-    for (int r = 0; r < 3; ++r) {
-        float s = 0.0f;
-        s += V.invproj[3 * r] * px;
-        s += V.invproj[3 * r + 1] * py;
-        s += V.invproj[3 * r + 2] * 1.0f;
-        v[r] = s;
-    }
-    float const len = sqrtf(dot3(v, v));
-    float pc[3];
-    for (int r = 0; r < 3; ++r)
-        pc[r] = v[r] / len * depth;
-    for (int r = 0; r < 3; ++r) {
-        float s = 0.0f;
-        s += V.rot[r] * pc[0];
-        s += V.rot[3 + r] * pc[1];
-        s += V.rot[6 + r] * pc[2];
-        pos[r] = s + V.c2w_t[r] * 1.0f;
-    }
-}
 
 // ViewProjection::get_surface_power, mesh_generator.cc:321-342
 __device__ __forceinline__ float
@@ -210,7 +159,7 @@ mat3_mul_f(const float *A, const float *B, float *C)
 // CameraInfo::fill_calibration / fill_inverse_calibration (ppoint = 0.5,
 // paspect = 1) at the depth map's size, ViewProjection's KR and t, and the
 // cam-to-world transform of one view
-static void
+void
 fill_view_camera(int width, int height, float flen, const float *rot,
     const float *trans, MeshViewDev &V)
 {
@@ -244,7 +193,7 @@ fill_view_camera(int width, int height, float flen, const float *rot,
 
 // generate_mesh :197-215 for all views: normals to world space, then the cut
 // when asked for and there is more than one view (:211)
-static int
+int
 launch_prepare_and_cut(hipStream_t stream, const MeshViewDev *d_table,
     std::vector<MeshViewDev> const &table, bool cut)
 {
@@ -810,7 +759,6 @@ points_emit_kernel(const MeshViewDev *__restrict__ views,
 // ------------------------------------------------------------ exclusive scan
 // of n 64-bit values in place: 4096 per tile (256 threads x 16), a tile pass,
 // one workgroup over the tile sums, a second tile pass; order fixed, no atomics
-constexpr int SCAN_ITEMS = 16, SCAN_TILE = 256 * SCAN_ITEMS;
 
 __device__ __forceinline__ unsigned long long
 block_exclusive_scan(unsigned long long v, unsigned long long *total)
@@ -892,7 +840,7 @@ scan_apply_kernel(unsigned long long *a, size_t n,
     }
 }
 
-static int
+int
 exclusive_scan(hipStream_t stream, unsigned long long *a, size_t n,
     unsigned long long *tiles)
 {
@@ -907,14 +855,6 @@ exclusive_scan(hipStream_t stream, unsigned long long *a, size_t n,
 }
 
 // ------------------------------------------------------------------ AABB clip
-// smvsrecon.cc:310-315: any coordinate below the minimum or above the maximum
-__device__ __forceinline__ bool
-outside_aabb(const float *q, float3 lo, float3 hi)
-{
-    return q[0] < lo.x || q[0] > hi.x || q[1] < lo.y || q[1] > hi.y
-        || q[2] < lo.z || q[2] > hi.z;
-}
-
 __global__ void __launch_bounds__(256)
 points_keep_kernel(const float *__restrict__ xyz, size_t n, float3 lo, float3 hi,
     unsigned long long *__restrict__ keep)
@@ -978,44 +918,6 @@ tri_vertices(const PointViewDev &P, const PointBufs &B, MeshClip clip, int bx, i
             keep = false;
     }
     return keep;
-}
-
-// M3 / M4 for face (a, b, c) = q[0..2]: the unit face normal and the angle at
-// corner k; -> false for a face of zero area (it adds nothing)
-__device__ __forceinline__ bool
-face_term(const float (*q)[3], int k, float *fn, float *weight)
-{
-#pragma clang fp contract(off)
-    float ab[3], bc[3], ca[3], nca[3];
-    for (int r = 0; r < 3; ++r) {
-        ab[r] = q[1][r] - q[0][r];
-        bc[r] = q[2][r] - q[1][r];
-        ca[r] = q[0][r] - q[2][r];
-        nca[r] = -ca[r];
-    }
-    fn[0] = ab[1] * nca[2] - ab[2] * nca[1];
-    fn[1] = ab[2] * nca[0] - ab[0] * nca[2];
-    fn[2] = ab[0] * nca[1] - ab[1] * nca[0];
-    float const fnl = sqrtf(dot3(fn, fn));
-    if (fnl == 0.0f)
-        return false;
-    for (int r = 0; r < 3; ++r)
-        fn[r] = fn[r] / fnl;
-    float const lab = sqrtf(dot3(ab, ab)), lbc = sqrtf(dot3(bc, bc)),
-        lca = sqrtf(dot3(ca, ca));
-    float cosine;
-    if (k == 0) {
-        cosine = dot3(ab, nca) / (lab * lca);
-    } else if (k == 1) {
-        float const nab[3] = { -ab[0], -ab[1], -ab[2] };
-        cosine = dot3(nab, bc) / (lab * lbc);
-    } else {
-        float const nbc[3] = { -bc[0], -bc[1], -bc[2] };
-        cosine = dot3(ca, nbc) / (lca * lbc);
-    }
-    cosine = cosine < -1.0f ? -1.0f : (cosine > 1.0f ? 1.0f : cosine);
-    *weight = acosf(cosine);
-    return true;
 }
 
 // recalc_normals as a gather: the vertex of pixel p sums fn * w over its kept
@@ -1115,14 +1017,6 @@ mesh_face_scatter_kernel(const PointViewDev *__restrict__ pv, PointBufs B, MeshC
 }
 
 } // namespace smvs_hip
-
-struct smvs_points {
-    bool mesh = false;   // smvs_mesh_generate: no values, faces always
-    int64_t n_points = 0, n_faces = 0;
-    std::vector<float> xyz, nrm, conf, val;
-    std::vector<uint8_t> rgb;
-    std::vector<uint32_t> faces;
-};
 
 namespace {
 

@@ -620,3 +620,88 @@ def generate_mesh(cams, depths, normals, images, cut=True, aabb=None, dd_factor=
     if cut_maps:
         out["cut_depth"] = cuts
     return out
+
+
+class SimplifyOptions(C.Structure):
+    """smvs_simplify_options of include/smvs_hip.h."""
+    _fields_ = [("cut_surfaces", C.c_int), ("use_aabb", C.c_int),
+                ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3),
+                ("create_triangle_mesh", C.c_int), ("max_vertices", C.c_int),
+                ("max_error", C.c_double)]
+
+
+def generate_simplified(cams, depths, normals, images, mesh=False, cut=True, aabb=None,
+                        max_vertices=-1, max_error=-1.0, cut_maps=False, device=0):
+    """smvsrecon --simplify over all views on the device
+    (smvs_simplified_generate): every view's greedy
+    Delaunay triangulation, merged in view-list order.  mesh=False: the point
+    cloud (xyz, normals, rgb, confidence, value, and faces unless aabb);
+    mesh=True: the mesh of --mesh --simplify (recalc_normals' normals, faces,
+    no value).  max_vertices / max_error: -1 = the reference's defaults.
+    Inputs as generate_points; cut_depth (the triangulated maps) when cut_maps."""
+    lib = _capi.load()
+    n = len(cams)
+    arr, cuts, _keep = _point_views(cams, depths, normals, images, cut_maps)
+    opt = SimplifyOptions()
+    opt.cut_surfaces = int(bool(cut))
+    opt.use_aabb = int(aabb is not None)
+    if aabb is not None:
+        for k in range(3):
+            opt.aabb_min[k] = float(aabb[0][k])
+            opt.aabb_max[k] = float(aabb[1][k])
+    opt.create_triangle_mesh = int(bool(mesh))
+    opt.max_vertices = int(max_vertices)
+    opt.max_error = float(max_error)
+    handle = C.c_void_p()
+    n_vertices, n_faces = C.c_int64(), C.c_int64()
+    check(lib.smvs_simplified_generate(device, arr if n else None, n, C.byref(opt),
+                                       C.byref(handle), C.byref(n_vertices),
+                                       C.byref(n_faces)))
+    try:
+        k = n_vertices.value
+        out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
+               "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32)}
+        if not mesh:
+            out["value"] = np.zeros(k, np.float32)
+        with_faces = mesh or aabb is None
+        fc = np.zeros((n_faces.value, 3), np.uint32) if with_faces else None
+        check(lib.smvs_points_download(handle, _p(out["xyz"], _fp), _p(out["normals"], _fp),
+                                       _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
+                                       _p(out.get("value"), _fp), _p(fc, _u32p)))
+    finally:
+        lib.smvs_points_release(handle)
+    if with_faces:
+        out["faces"] = fc
+    if cut_maps:
+        out["cut_depth"] = cuts
+    return out
+
+
+def simplify_triangulate(depth, max_vertices=-1, max_error=-1.0, device=0, clocks=False):
+    """The greedy triangulation of one depth map in pixel space, before any
+    clean-up (smvs_simplify_triangulate, rows S1-S8).  Returns a dict:
+    iterations, vertices (n, 3) float64 (the four corners first), triangles
+    (t, 3) uint32 per triangle id, num_zero_depths (t,) int32, and with clocks=True (the stamped
+    diagnostic build of the kernel) clocks (4,) uint64: 100 MHz ticks in
+    selection, Delaunay lane, rescans, total."""
+    lib = _capi.load()
+    d = _f32(depth)
+    if d.ndim != 2:
+        raise ValueError("depth must be (h, w)")
+    h, w = d.shape
+    budget = (w * h) // 40 if max_vertices < 0 else int(max_vertices)
+    cap = min(max(budget, 0), w * h) + 5
+    verts = np.zeros((cap, 3), np.float64)
+    tris = np.zeros((2 * cap, 3), np.uint32)
+    nzero = np.zeros(2 * cap, np.int32)
+    ticks = np.zeros(4, np.uint64)
+    it, nv, nt = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib.smvs_simplify_triangulate(device, _p(d, _fp), w, h, int(max_vertices),
+                                        C.c_double(max_error), C.byref(it), C.byref(nv),
+                                        _p(verts, _dp), C.byref(nt), _p(tris, _u32p),
+                                        _p(nzero, _i32p),
+                                        _p(ticks if clocks else None,
+                                           C.POINTER(C.c_uint64))))
+    return {"iterations": it.value, "vertices": verts[:nv.value],
+            "triangles": tris[:nt.value], "num_zero_depths": nzero[:nt.value],
+            "clocks": ticks if clocks else None}

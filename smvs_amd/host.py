@@ -639,6 +639,30 @@ def generate_mesh(scene_dir, view_ids=None, image_embedding="undistorted", input
     return path.value.decode(), nv.value, nf.value
 
 
+def generate_simplified(scene_dir, mesh=False, view_ids=None, image_embedding="undistorted",
+                        input_scale=0, use_shading=False, cut=True, aabb=None, device=0):
+    """smvsrecon --simplify (mesh=True: --mesh --simplify) on a reconstructed
+    scene through smvs_amd::generate_scene_simplified: every view's greedy
+    Delaunay triangulation, written under the
+    reference's names <scene>/smvs-{B,S}<input_scale>.ply or, with the mesh,
+    smvs-m-{B,S}<input_scale>.ply (and smvs-cut.mvei per view when cutting).
+    Returns (ply path, number of vertices, number of faces; 0 faces for the
+    point cloud)."""
+    lib = load()
+    st = _point_cloud_settings(image_embedding, input_scale, use_shading, cut, aabb, mesh,
+                               True, device)
+    ids = None if view_ids is None else np.asarray(view_ids, dtype=np.int32)
+    path = C.create_string_buffer(4096)
+    nv, nf = C.c_int64(0), C.c_int64(0)
+    rc = lib.smvs_host_generate_simplified(
+        scene_dir.encode(), C.byref(st), ids.ctypes.data_as(_i32p) if ids is not None else None,
+        C.c_int(0 if ids is None else ids.size), path, C.c_int(len(path)), C.byref(nv),
+        C.byref(nf))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    return path.value.decode(), nv.value, nf.value
+
+
 def save_ply_points(path, xyz, normals, rgb, confidence, value):
     """The host's PLY writer of the point cloud (save_ply_points)."""
     lib = load()
