@@ -355,6 +355,43 @@ int smvs_sgm_depth_for_view_raw(int device, const uint8_t *main_img, int w, int 
     int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
     uint16_t penalty2, float *depth);
 
+/* Which of the reference's two path aggregations the three entries above
+ * reproduce.  The reference selects it at build time (SMVS_ENABLE_SSE,
+ * lib/defines.h):
+ *   SMVS_SGM_P2_CONSTANT  the SSE build, sgm_stereo.cc:361-406: constant
+ *                         penalty2 (what the entries without `_mode` run);
+ *   SMVS_SGM_P2_ADAPTIVE  the build without SSE, sgm_stereo.cc:310-346: per
+ *                         (pixel, predecessor on the path)
+ *                         penalty2' = max(penalty1 * 3 / 2, penalty2 / (|I - I'| + 1))
+ *                         in int, I = the u8 main image at SGM scale; and, as
+ *                         that build does (:626-654), the two bottom corners
+ *                         start their upward diagonal with 2 C.
+ * Mode 0 gives the bytes of the entry without `_mode`.  An unknown mode -- and
+ * penalties for which a wrap of the u16 volumes cannot be excluded,
+ * 8 * (255 + max(penalty2, penalty1 * 3 / 2)) + 4 * 255 >= 65536 -- is
+ * SMVS_ERR_INVALID before any device call.  penalty2 < penalty1 is accepted in
+ * the adaptive mode (penalty2' >= penalty1 always) and refused in mode 0. */
+typedef enum { SMVS_SGM_P2_CONSTANT = 0, SMVS_SGM_P2_ADAPTIVE = 1 } smvs_sgm_p2_mode;
+
+/* smvs_sgm_run with the aggregation of sgm_stereo.cc:310-346 selectable */
+int smvs_sgm_run_mode(int device, const uint8_t *main_img, int w, int h,
+    const uint8_t *neighbor_img, int nw, int nh, const float *M,
+    const float *t, float min_depth, float max_depth, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth,
+    int32_t *argmin, uint16_t *cost, uint16_t *sgm);
+/* smvs_sgm_depth_for_view with the aggregation of sgm_stereo.cc:310-346
+ * selectable (all four runs of a view use the mode, each with its own main
+ * image: the neighbour's in the neighbour -> main runs) */
+int smvs_sgm_depth_for_view_mode(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth);
+/* smvs_sgm_depth_for_view_raw with the aggregation of sgm_stereo.cc:310-346
+ * selectable (the image of the penalty is the desaturated, halved one) */
+int smvs_sgm_depth_for_view_raw_mode(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, int p2_mode, float *depth);
+
 /* DepthOptimizer::depthmap_bilateral_filter, depth_optimizer.cc:957-1004 */
 int smvs_bilateral_upsample(int device, const float *dm, int dm_w, int dm_h,
     const float *ci, int w, int h, int channels, float sigma,

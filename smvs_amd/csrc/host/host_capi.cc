@@ -211,6 +211,16 @@ smvs_host_sgm_depth(const smvs_host_view *main_in, const smvs_host_view *subs_in
     float min_depth, float max_depth, int device, float *depth_out, int *out_w,
     int *out_h)
 {
+    return smvs_host_sgm_depth_mode(main_in, subs_in, n_subs, bundle_in, sgm_scale,
+        min_depth, max_depth, device, 0, depth_out, out_w, out_h);
+}
+
+extern "C" int
+smvs_host_sgm_depth_mode(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, int sgm_scale,
+    float min_depth, float max_depth, int device, int adaptive_penalty2,
+    float *depth_out, int *out_w, int *out_h)
+{
     try {
         StereoView::Ptr main_view = make_view(*main_in, false);
         std::vector<StereoView::Ptr> subs;
@@ -223,6 +233,7 @@ smvs_host_sgm_depth(const smvs_host_view *main_in, const smvs_host_view *subs_in
         opts.min_depth = min_depth;
         opts.max_depth = max_depth;
         opts.device = device;
+        opts.adaptive_penalty2 = adaptive_penalty2 != 0;
         FloatImage::Ptr d = reconstruct_sgm_depth_for_view(opts, main_view, subs,
             bundle);
         if (out_w != nullptr)
@@ -788,6 +799,17 @@ smvs_host_reconstruct_scene(const char *scene_dir,
     int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
     int *n_skipped, double *seconds, int *input_scale_used)
 {
+    return smvs_host_reconstruct_scene_mode(scene_dir, o, 0, view_ids, n_view_ids,
+        reconstructed_out, max_reconstructed, n_reconstructed, n_skipped, seconds,
+        input_scale_used);
+}
+
+extern "C" int
+smvs_host_reconstruct_scene_mode(const char *scene_dir,
+    const smvs_host_recon_settings *o, int sgm_adaptive_penalty2, const int *view_ids,
+    int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
+    int *n_skipped, double *seconds, int *input_scale_used)
+{
     try {
         if (scene_dir == nullptr || o == nullptr)
             throw std::invalid_argument("smvs_host_reconstruct_scene: bad argument");
@@ -804,6 +826,7 @@ smvs_host_reconstruct_scene(const char *scene_dir,
         conf.sgm_min = o->sgm_min;
         conf.sgm_max = o->sgm_max;
         conf.sgm_scale = o->sgm_scale;
+        conf.sgm_adaptive_penalty2 = sgm_adaptive_penalty2 != 0;
         conf.num_neighbors = (std::size_t)o->num_neighbors;
         conf.min_neighbors = (std::size_t)o->min_neighbors;
         conf.first_device = o->first_device;

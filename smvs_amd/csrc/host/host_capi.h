@@ -97,6 +97,13 @@ int smvs_host_sgm_depth(const smvs_host_view *main_view,
     const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
     int sgm_scale, float min_depth, float max_depth, int device,
     float *depth_out, int *out_w, int *out_h);
+/* The same with SGMStereo::Options::adaptive_penalty2 (not in the reference's
+ * Options: != 0 reproduces its build without SSE, lib/sgm_stereo.cc:310-346;
+ * 0 is smvs_host_sgm_depth). */
+int smvs_host_sgm_depth_mode(const smvs_host_view *main_view,
+    const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
+    int sgm_scale, float min_depth, float max_depth, int device,
+    int adaptive_penalty2, float *depth_out, int *out_w, int *out_h);
 
 /* smvs::Surface on its own (lib/surface.cc): Surface::create (from the bundle
  * when init_depth is NULL, else from the W x H depth map) followed by a
@@ -175,6 +182,14 @@ int smvs_host_reconstruct_scene(const char *scene_dir,
     const smvs_host_recon_settings *settings, const int *view_ids, int n_view_ids,
     int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
     int *n_skipped, double *seconds, int *input_scale_used);
+/* The same with ReconSettings::sgm_adaptive_penalty2 (the settings struct keeps
+ * its layout for existing callers, so the switch is an argument: != 0 runs the
+ * SGM front end of every view as the reference's build without SSE does,
+ * lib/sgm_stereo.cc:310-346; 0 is smvs_host_reconstruct_scene). */
+int smvs_host_reconstruct_scene_mode(const char *scene_dir,
+    const smvs_host_recon_settings *settings, int sgm_adaptive_penalty2,
+    const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
+    int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used);
 
 /* smvsrecon's generate_mesh (app/smvsrecon.cc:278-343, MeshGenerator::
  * generate_mesh, lib/mesh_generator.cc:160-299) on a reconstructed scene: the

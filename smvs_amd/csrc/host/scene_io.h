@@ -88,6 +88,9 @@ struct ReconSettings
     bool force_recon = false, force_sgm = false, full_optimization = false;
     float sgm_min = 0.0f, sgm_max = 0.0f;
     int sgm_scale = 1;
+    // not in the reference's AppSettings: SGMStereo::Options::adaptive_penalty2
+    // (the reference's build without SSE, lib/sgm_stereo.cc:310-346)
+    bool sgm_adaptive_penalty2 = false;
     std::size_t num_neighbors = 6, min_neighbors = 3;
     int first_device = 0, num_devices = 1, views_in_flight = 2;
 };

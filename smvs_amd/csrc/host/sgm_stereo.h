@@ -22,6 +22,11 @@ public:
         uint16_t penalty1 = 6;
         uint16_t penalty2 = 96;
         int device = 0;      // HIP device (not in the reference)
+        // not in the reference's Options: selects which of its two builds is
+        // reproduced -- false: the SSE build (constant penalty2,
+        // lib/sgm_stereo.cc:361-406), true: the build without SSE
+        // (penalty2 adapted to the intensity step, lib/sgm_stereo.cc:310-346)
+        bool adaptive_penalty2 = false;
     };
 
     SGMStereo(Options const& opts, StereoView::Ptr main,

@@ -4,7 +4,9 @@
 // Replaces SGMStereo::run_sgm (reference: lib/sgm_stereo.cc:98-124):
 // census_filter (:126-148), warped_neighbors_for_depth (:150-190),
 // create_cost_volume (:192-244), aggregate_sgm_costs (:429-667, the SSE
-// branch with constant penalty2, :361-406), depth_from_sgm_volume (:274-306);
+// branch with constant penalty2, :361-406; on request the branch without SSE,
+// fill_path_cost :310-346 with its seeds :626-654 -- SMVS_SGM_P2_ADAPTIVE, the
+// ADAPT kernels below), depth_from_sgm_volume (:274-306);
 // and DepthOptimizer::depthmap_bilateral_filter (lib/depth_optimizer.cc:957-1004).
 //
 // Integer path: results are bit-exact with the reference semantics.  The
@@ -408,7 +410,19 @@ struct PathArgs {
     int last;          // 1: last path, fuse the winner-takes-all
     uint8_t *delta;    // all-paths kernel, DELTA form: eight [h][w][D] u8 volumes
     size_t vol;        // bytes of one of them
+    const uint8_t *img; // ADAPT kernels: the main image at SGM scale, [h][w]
 };
+
+// The reference's build without SSE (sgm_stereo.cc:310-346) adapts penalty2 to
+// the intensity step between a pixel and its predecessor on the path:
+// max(P1 * 3 / 2, P2 / (|I - I'| + 1)) in int.  It is the same for every plane
+// of the pixel, i.e. uniform over the lanes that hold a line.
+__device__ __forceinline__ uint32_t
+adapted_penalty2(uint32_t p1, uint32_t p2, uint32_t i_here, uint32_t i_before)
+{
+    uint32_t const diff = (i_here > i_before ? i_here - i_before : i_before - i_here) + 1u;
+    return max(p1 * 3u / 2u, p2 / diff);
+}
 
 // Wave-wide unsigned minimum with DPP row operations (VALU latency instead of
 // the LDS crossbar of ds_bpermute): prefix-min inside each row of 16 lanes,
@@ -454,6 +468,14 @@ lane_next(uint32_t v, uint32_t fill)
 // 589-612): the first pixel of a line copies C and adds it to S; for a
 // diagonal path the corner pixel that lies on both the entry row and the
 // entry column is added twice.
+//
+// ADAPT (the build without SSE): penalty2 per step from the image
+// (adapted_penalty2, an exact integer division: this kernel serves the odd
+// plane counts and is bound by its scalar accesses), and the corner of an
+// UPWARD diagonal sweep starts its line with 2 C, not C (:626-654 seed the path
+// volumes with `+=`, row loop and column loop both).  No sum wraps inside
+// check_sgm_options' range, so the masks below change nothing there.
+template <bool ADAPT>
 __global__ void __launch_bounds__(64)
 sgm_path_kernel(PathArgs A)
 {
@@ -498,12 +520,19 @@ sgm_path_kernel(PathArgs A)
     bool const ok0 = d0 < D, ok1 = d1 < D;
     uint32_t const BIG = 0xFFFFu;
     uint32_t prev0 = BIG, prev1 = BIG;
+    uint32_t i_before = 0;
 
     for (int s = 0; s < len; ++s, x += A.dx, y += A.dy) {
         size_t const base = ((size_t)y * w + x) * D;
         uint32_t c0 = ok0 ? A.cost[base + d0] : 0u;
         uint32_t c1 = ok1 ? A.cost[base + d1] : 0u;
         uint32_t l0, l1;
+        uint32_t p2 = A.p2;
+        if (ADAPT) {
+            uint32_t const i_here = A.img[(size_t)y * w + x];
+            p2 = adapted_penalty2(A.p1, A.p2, i_here, i_before);
+            i_before = i_here;
+        }
         if (s == 0) {
             l0 = c0;
             l1 = c1;
@@ -513,7 +542,7 @@ sgm_path_kernel(PathArgs A)
             uint32_t const right = (uint32_t)__shfl_down((int)prev0, 1);
             bool const has_left = lane > 0;
             bool const has_right = lane < 63 && d1 + 1 < D;
-            uint32_t const far = (mn + A.p2) & 0xFFFFu;
+            uint32_t const far = (mn + p2) & 0xFFFFu;
             // u16 wrapping arithmetic of the SSE code (_mm_add_epi16)
             uint32_t u0 = prev0;
             u0 = min(u0, has_left ? ((left + A.p1) & 0xFFFFu) : BIG);
@@ -530,6 +559,10 @@ sgm_path_kernel(PathArgs A)
         if (s == 0 && extra_seed) {
             add0 = (2 * c0) & 0xFFFFu;
             add1 = (2 * c1) & 0xFFFFu;
+            if (ADAPT && A.dy < 0) {
+                l0 = add0;
+                l1 = add1;
+            }
         }
         if (ok0) {
             uint32_t const old = A.first ? 0u : A.sgm[base + d0];
@@ -636,10 +669,29 @@ max_dpp0(uint32_t v)
 }
 
 // FULL: 128 planes, every lane of a half wave has four (no idle lanes to reset)
-template <int K, bool FULL>
+//
+// ADAPT: the build without SSE (sgm_stereo.cc:310-346, adapted_penalty2 above).
+// penalty2' depends on |I - I'| in [0, 255] only, so the wave builds the 256
+// packed values {p2', p2'} once in LDS (1 KiB, four exact integer divisions
+// per lane) and a step is one broadcast ds_read_b32 indexed by the difference
+// of two image bytes -- both known as soon as the bytes are loaded, which
+// happens with the cost words of the chunk AHEAD, so neither the load nor the
+// LDS read sits on the dependent chain of the recurrence.  (An exact division
+// per step would add ~25 VALU instructions to a step of ~40.)  The image byte
+// is one address per half wave: a broadcast load.
+// Range of the DELTA bytes in this mode: a step stores u - min L' with
+// min L' <= u <= min L' + p2' (u is a minimum of terms >= min L', one of them
+// min L' + p2'), and p2' <= max(P2, P1 * 3 / 2) <= 255 by delta_form(); the
+// first cell of a line stores 0, or C <= 255 at a doubly seeded corner.  The
+// corner of an UPWARD diagonal sweep starts its line with L = 2 C <= 510
+// (:626-654 seed the path volumes with `+=`), which changes pa / pb only: the
+// byte it stores is the same C.  All 16-bit lanes stay below 2^15: L <= 510,
+// BIG2 + P1 < 2^16.
+template <int K, bool FULL, bool ADAPT = false>
 __global__ void __launch_bounds__(64)
 sgm_paths2_kernel(PathArgs A)
 {
+    __shared__ uint32_t p2_table[ADAPT ? 256 : 1];
     int const w = A.w, h = A.h, D = A.D;
     int const ndiag = w + h - 1;
     // block -> (direction, pair of lines); the long horizontal lines first
@@ -661,6 +713,16 @@ sgm_paths2_kernel(PathArgs A)
 
     int const lane = threadIdx.x;
     int const half = lane >> 5, hl = lane & 31;
+    if (ADAPT) {
+        // entry d: |I - I'| = d (one wave per block: the barrier is a wait on LDS)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            uint32_t const d = (uint32_t)(lane + 64 * j);
+            uint32_t const p = max(A.p1 * 3u / 2u, A.p2 / (d + 1u));
+            p2_table[d] = p | (p << 16);
+        }
+        __syncthreads();
+    }
     int x0 = 0, y0 = 0, len = 0, extra_seed = 0;
     bool const has_line = path_line(A, 2 * b + half, &x0, &y0, &len, &extra_seed);
     if (!has_line)
@@ -679,6 +741,11 @@ sgm_paths2_kernel(PathArgs A)
     uint32_t const BIG2 = 0x7FFF7FFFu;
     uint32_t const p1p1 = (uint32_t)A.p1 | ((uint32_t)A.p1 << 16);
     uint32_t const p2p2 = (uint32_t)A.p2 | ((uint32_t)A.p2 << 16);
+    // ADAPT: the image bytes of the line, one per step
+    size_t const io0 = has_line ? (size_t)y0 * w + x0 : 0;
+    ptrdiff_t const istep = (ptrdiff_t)A.dy * w + A.dx;
+    const uint8_t *__restrict__ iin = ADAPT ? A.img + io0 : nullptr;
+    uint32_t i_before = 0;
     // v_perm_b32 selectors of the two neighbour vectors that reach into the
     // adjacent lanes -- {plane 3 of the lane before, own plane 0} and {own plane
     // 3, plane 0 of the lane after} -- per lane: at the ends of a line (where
@@ -697,11 +764,19 @@ sgm_paths2_kernel(PathArgs A)
         if (ok) {
             pa = ca;
             pb = cb;
+            if (ADAPT && extra_seed && A.dy < 0) {
+                pa = pk_add(ca, ca);
+                pb = pk_add(cb, cb);
+            }
             *e32 = extra_seed ? c : 0u;
         }
+        if (ADAPT)
+            i_before = *iin;
     }
     cin += step;
     e32 += step;
+    if (ADAPT)
+        iin += istep;
     // the remaining steps of the two lines as scalars: every "is this step
     // inside my line" below is then a lane mask built by scalar instructions
     int const rest0 = max(__builtin_amdgcn_readlane(len, 0) - 1, 0);
@@ -712,6 +787,7 @@ sgm_paths2_kernel(PathArgs A)
     };
 
     uint32_t c_cur[K], c_next[K], outv[K];
+    uint32_t far_cur[K], far_next[K];   // ADAPT: {p2', p2'} of the steps
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         c_cur[k] = 0;
@@ -719,6 +795,22 @@ sgm_paths2_kernel(PathArgs A)
             c_cur[k] = cin[(ptrdiff_t)k * step];
     }
     cin += (ptrdiff_t)K * step;
+    if (ADAPT) {
+        uint32_t iv[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            iv[k] = 0;
+            if (inside(k))
+                iv[k] = iin[(ptrdiff_t)k * istep];
+        }
+        iin += (ptrdiff_t)K * istep;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            uint32_t const d = iv[k] > i_before ? iv[k] - i_before : i_before - iv[k];
+            far_cur[k] = p2_table[d];
+            i_before = iv[k];
+        }
+    }
     // one chunk of K steps; FAST: this chunk and the next lie inside both lines
     // (no predicates on the loads and stores)
     auto const chunk = [&](auto fast_tag, int base) {
@@ -728,6 +820,15 @@ sgm_paths2_kernel(PathArgs A)
             c_next[k] = 0;
             if (FAST || inside(base + K + k))
                 c_next[k] = cin[(ptrdiff_t)k * step];
+        }
+        uint32_t iv[K];
+        if (ADAPT) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                iv[k] = 0;
+                if (FAST || inside(base + K + k))
+                    iv[k] = iin[(ptrdiff_t)k * istep];
+            }
         }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -749,7 +850,7 @@ sgm_paths2_kernel(PathArgs A)
                 uint32_t const mm_lower = m_lower | (m_lower << 16);
                 uint32_t const mm_upper = m_upper | (m_upper << 16);
                 uint32_t const mnmn = upper ? mm_upper : mm_lower;
-                uint32_t const far = pk_add(mnmn, p2p2);
+                uint32_t const far = pk_add(mnmn, ADAPT ? far_cur[k] : p2p2);
                 // neighbouring planes: {3 of the lane before, 0}, {1, 2}, {3, 0 of the lane after}
                 // (wave_shr:1 / wave_shl:1; the lanes without a source are ends of
                 // a line, whose selectors do not look at what arrives)
@@ -770,6 +871,17 @@ sgm_paths2_kernel(PathArgs A)
                 outv[k] = __builtin_amdgcn_perm(eb, ea, 0x06040200u);
                 if (!FULL && !ok)
                     pa = pb = BIG2;
+            }
+        }
+        if (ADAPT) {
+            // the penalties of the chunk ahead (a step past the end of a line
+            // reads image byte 0: an entry of the table like any other, and what
+            // that step computes is never stored)
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                uint32_t const d = iv[k] > i_before ? iv[k] - i_before : i_before - iv[k];
+                far_next[k] = p2_table[d];
+                i_before = iv[k];
             }
         }
         if (FULL && FAST) {
@@ -793,6 +905,12 @@ sgm_paths2_kernel(PathArgs A)
 #pragma unroll
         for (int k = 0; k < K; ++k)
             c_cur[k] = c_next[k];
+        if (ADAPT) {
+            iin += (ptrdiff_t)K * istep;
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                far_cur[k] = far_next[k];
+        }
     }
 }
 
@@ -814,7 +932,17 @@ sgm_paths2_kernel(PathArgs A)
 // direction: no atomics, no zero fill) and sgm_sum_wta_kernel forms
 // S = 8 C + the eight bytes on the fly: 16 + 9 bytes per cost cell instead of
 // 8 x (1 + 4) + 2 with the read-modify-writes of the u16 volume.
-template <int K, bool DELTA>
+//
+// ADAPT (the build without SSE): penalty2 per step from the image byte of the
+// step and of the step before (adapted_penalty2: an exact integer division on
+// values that are uniform over the wave and known a chunk ahead of the
+// recurrence; this kernel serves penalty2 > 255 too, which a byte-indexed
+// table of packed u16 pairs would serve as well, but the division is off the
+// dependent chain here and keeps the fall-back free of LDS).  The corner of an
+// upward diagonal sweep starts with L = 2 C (:626-654).  DELTA bytes: as in
+// sgm_paths2_kernel, u - min L' <= p2' <= 255.  Without DELTA a path adds at
+// most max(510, 255 + p2') to a u16 of S (check_sgm_options).
+template <int K, bool DELTA, bool ADAPT = false>
 __global__ void __launch_bounds__(64)
 sgm_all_paths_kernel(PathArgs A)
 {
@@ -865,15 +993,27 @@ sgm_all_paths_kernel(PathArgs A)
     // bits, so no sum below needs a mask
     uint32_t const BIG = 0x7FFFu;
     uint32_t prev0 = BIG, prev1 = BIG;
+    // ADAPT: the image bytes of the line, one per step
+    ptrdiff_t const istep = (ptrdiff_t)A.dy * w + A.dx;
+    const uint8_t *__restrict__ iin = ADAPT ? A.img + ((size_t)y0 * w + x0) : nullptr;
+    uint32_t i_before = 0;
 
     uint32_t c_cur[K], c_next[K], addv[K];
+    uint32_t p2_cur[K], p2_next[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         c_cur[k] = 0;
         if (k < len)
             c_cur[k] = cin[(ptrdiff_t)k * step];
+        if (ADAPT) {
+            uint32_t const i_here = k < len ? iin[(ptrdiff_t)k * istep] : 0u;
+            p2_cur[k] = adapted_penalty2(A.p1, A.p2, i_here, i_before);
+            i_before = i_here;
+        }
     }
     cin += (ptrdiff_t)K * step;
+    if (ADAPT)
+        iin += (ptrdiff_t)K * istep;
     for (int base = 0; base < len; base += K) {
         int const n = min(K, len - base);
 #pragma unroll
@@ -881,8 +1021,15 @@ sgm_all_paths_kernel(PathArgs A)
             c_next[k] = 0;
             if (base + K + k < len)
                 c_next[k] = cin[(ptrdiff_t)k * step];
+            if (ADAPT) {
+                uint32_t const i_here = base + K + k < len ? iin[(ptrdiff_t)k * istep] : 0u;
+                p2_next[k] = adapted_penalty2(A.p1, A.p2, i_here, i_before);
+                i_before = i_here;
+            }
         }
         cin += (ptrdiff_t)K * step;
+        if (ADAPT)
+            iin += (ptrdiff_t)K * istep;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             addv[k] = 0;
@@ -897,12 +1044,16 @@ sgm_all_paths_kernel(PathArgs A)
                     e1 = extra_seed ? c1 : 0u;
                     prev0 = c0;
                     prev1 = c1;
+                    if (ADAPT && extra_seed && A.dy < 0) {
+                        prev0 = 2u * c0;
+                        prev1 = 2u * c1;
+                    }
                 } else {
                     // :310-346: L = C + min(L'(d), L'(d -+ 1) + P1, min L' + P2) - min L'
                     uint32_t const mn = wave_min_u32(min(prev0, prev1));
                     uint32_t const left = lane_prev(prev1, BIG);
                     uint32_t const right = lane_next(prev0, BIG);
-                    uint32_t const far = mn + A.p2;
+                    uint32_t const far = mn + (ADAPT ? p2_cur[k] : A.p2);
                     uint32_t const u0 = min(min(prev0, left + A.p1), min(prev1 + A.p1, far));
                     uint32_t const u1 = min(min(prev1, prev0 + A.p1), min(right + A.p1, far));
                     e0 = u0 - mn;
@@ -934,6 +1085,11 @@ sgm_all_paths_kernel(PathArgs A)
 #pragma unroll
         for (int k = 0; k < K; ++k)
             c_cur[k] = c_next[k];
+        if (ADAPT) {
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                p2_cur[k] = p2_next[k];
+        }
     }
 }
 
@@ -1500,6 +1656,14 @@ struct SgmWorkspace {
     {
         return (num_steps % 4) == 0 && penalty2 <= 255u;
     }
+    // the largest penalty2 a step can use: the option itself, or in the adaptive
+    // mode max(P2 / diff, P1 * 3 / 2) <= max(P2, P1 * 3 / 2)
+    static unsigned largest_penalty2(unsigned penalty1, unsigned penalty2, int p2_mode)
+    {
+        unsigned const floor_value = penalty1 * 3u / 2u;
+        return p2_mode == SMVS_SGM_P2_ADAPTIVE && floor_value > penalty2 ? floor_value
+                                                                        : penalty2;
+    }
     int ensure(size_t npix, int num_steps, unsigned penalty2)
     {
         size_t const vol = npix * (size_t)num_steps;
@@ -1519,22 +1683,52 @@ struct SgmWorkspace {
     }
 };
 
+// The penalties alone (no device involved: the *_mode entries call this before
+// anything else).
 static int
-check_sgm_options(int num_steps, float min_depth, float max_depth,
-    unsigned penalty1, unsigned penalty2)
+check_sgm_penalties(unsigned penalty1, unsigned penalty2, int p2_mode)
 {
-    SMVS_REQUIRE(num_steps >= 2 && num_steps <= 128,
-        "num_steps must be in [2, 128]");
-    SMVS_REQUIRE(min_depth > 0.f && max_depth > min_depth, "bad depth range");
-    SMVS_REQUIRE(penalty2 >= penalty1, "penalty2 must not be below penalty1");
+    SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
+        "unknown penalty2 mode");
     // The all-paths kernel adds the eight path costs into S with u32 atomics
     // on packed u16 pairs: exact only while no 16-bit lane can carry into its
     // neighbour, i.e. while S stays below 2^16.  Per path L <= 255 + P2 (Q20),
     // border pixels add C up to 4 times more (Q19).  The reference wraps every
     // u16 lane on its own (_mm_add_epi16), which this bound never reaches.
-    SMVS_REQUIRE(8u * (255u + penalty2) + 4u * 255u < 65536u,
+    //
+    // SMVS_SGM_P2_ADAPTIVE (the build without SSE, sgm_stereo.cc:310-346), the
+    // same bound re-derived: a step uses p2' = max(P1 * 3 / 2, P2 / diff), so
+    // p2' <= Pmax = max(P2, P1 * 3 / 2).  A line starts with L = C <= 255, or
+    // with 2 C <= 510 at the corner of an upward diagonal sweep (:626-654 seed
+    // the path volumes with `+=`); a step gives L = C + u - min L' with
+    // min L' <= u <= min L' + p2', hence L <= 255 + Pmax behind the start
+    // whatever the start held.  What a line adds to S at its start is its seed
+    // (C, twice at a corner) -- the same "up to 4 C more" (Q19) -- so
+    // S <= 8 (255 + Pmax) + 4 * 255.  Inside the bound no sum of the
+    // reference's literal loop wraps either (L' + p2' <= max(510, 255 + Pmax)
+    // + Pmax), so its uint16_t narrowing never acts.
+    // penalty2 < penalty1 is ACCEPTED in this mode: p2' >= P1 * 3 / 2 >= P1 at
+    // every step, which is all the recurrence (and its closed form) needs; the
+    // constant mode keeps refusing it.
+    if (p2_mode == SMVS_SGM_P2_CONSTANT)
+        SMVS_REQUIRE(penalty2 >= penalty1, "penalty2 must not be below penalty1");
+    unsigned const pmax = SgmWorkspace::largest_penalty2(penalty1, penalty2, p2_mode);
+    SMVS_REQUIRE(penalty1 <= 0xFFFFu && penalty2 <= 0xFFFFu
+            && 8u * (255u + pmax) + 4u * 255u < 65536u,
         "penalty2 too large for the u16 aggregation volume");
     return SMVS_OK;
+}
+
+static int
+check_sgm_options(int num_steps, float min_depth, float max_depth,
+    unsigned penalty1, unsigned penalty2, int p2_mode = SMVS_SGM_P2_CONSTANT)
+{
+    SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
+        "unknown penalty2 mode");
+    SMVS_REQUIRE(num_steps >= 2 && num_steps <= 128,
+        "num_steps must be in [2, 128]");
+    SMVS_REQUIRE(min_depth > 0.f && max_depth > min_depth, "bad depth range");
+    return check_sgm_penalties(penalty1, penalty2, p2_mode);
 }
 
 // SGMStereo::run_sgm (sgm_stereo.cc:98-124) on device images; the depth map
@@ -1543,17 +1737,20 @@ static int
 sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     int w, int h, const uint8_t *d_nbr, int nw, int nh, const float *M,
     const float *t, float min_depth, float max_depth, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, float *d_depth)
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *d_depth)
 {
     int rc = check_sgm_options(num_steps, min_depth, max_depth, penalty1,
-        penalty2);
+        penalty2, p2_mode);
     if (rc != SMVS_OK)
         return rc;
     SMVS_REQUIRE(B.runs < SgmWorkspace::MAX_RUNS, "too many runs on one workspace");
     hipStream_t const stream = B.ws->stream;
     size_t const npix = (size_t)w * h;
     size_t const vol = npix * num_steps;
-    if ((rc = B.ensure(npix, num_steps, penalty2)) != SMVS_OK)
+    bool const adapt = p2_mode == SMVS_SGM_P2_ADAPTIVE;
+    // (what decides the form of the volumes: the largest penalty2 of a step)
+    unsigned const pmax = SgmWorkspace::largest_penalty2(penalty1, penalty2, p2_mode);
+    if ((rc = B.ensure(npix, num_steps, pmax)) != SMVS_OK)
         return rc;
     // sgm_stereo.cc:195-203: inverse-depth planes by repeated float addition
     float depths[128];
@@ -1634,7 +1831,8 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     P.last = 0;
     P.delta = B.delta;
     P.vol = vol;
-    bool const df = SgmWorkspace::delta_form(num_steps, penalty2);
+    P.img = d_main;
+    bool const df = SgmWorkspace::delta_form(num_steps, pmax);
     // (SMVS_SGM_PATHS=wave: a wave per line, two planes per lane -- rounds 3-5)
     static bool const wave_per_line = [] {
         const char *e = std::getenv("SMVS_SGM_PATHS");
@@ -1646,7 +1844,11 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
         int const nd = w + h - 1;
         int const pairs = 2 * ((h + 1) / 2) + 2 * ((w + 1) / 2) + 4 * ((nd + 1) / 2);
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_PATHS);
-        if (num_steps == 128)
+        if (adapt && num_steps == 128)
+            hipLaunchKernelGGL((sgm_paths2_kernel<8, true, true>), dim3(pairs), dim3(64), 0, stream, P);
+        else if (adapt)
+            hipLaunchKernelGGL((sgm_paths2_kernel<8, false, true>), dim3(pairs), dim3(64), 0, stream, P);
+        else if (num_steps == 128)
             hipLaunchKernelGGL((sgm_paths2_kernel<8, true>), dim3(pairs), dim3(64), 0, stream, P);
         else
             hipLaunchKernelGGL((sgm_paths2_kernel<8, false>), dim3(pairs), dim3(64), 0, stream, P);
@@ -1655,16 +1857,24 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
         P.first = 0;
         int const lines = 2 * h + 2 * w + 4 * (w + h - 1);
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_PATHS);
-        hipLaunchKernelGGL((sgm_all_paths_kernel<16, true>), dim3(lines), dim3(64), 0,
-            stream, P);
+        if (adapt)
+            hipLaunchKernelGGL((sgm_all_paths_kernel<16, true, true>), dim3(lines), dim3(64),
+                0, stream, P);
+        else
+            hipLaunchKernelGGL((sgm_all_paths_kernel<16, true>), dim3(lines), dim3(64), 0,
+                stream, P);
     } else if ((num_steps % 2) == 0) {
         SMVS_HIP_CHECK(hipMemsetAsync(B.sgm, 0, sizeof(uint16_t) * vol, stream));
         P.dx = P.dy = 0;
         P.first = 0;
         int const lines = 2 * h + 2 * w + 4 * (w + h - 1);
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_PATHS);
-        hipLaunchKernelGGL((sgm_all_paths_kernel<16, false>), dim3(lines), dim3(64), 0,
-            stream, P);
+        if (adapt)
+            hipLaunchKernelGGL((sgm_all_paths_kernel<16, false, true>), dim3(lines), dim3(64),
+                0, stream, P);
+        else
+            hipLaunchKernelGGL((sgm_all_paths_kernel<16, false>), dim3(lines), dim3(64), 0,
+                stream, P);
     } else {
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_PATHS);
         // odd plane counts: one launch per direction, scalar accesses
@@ -1673,8 +1883,12 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
             P.dy = dirs[k][1];
             P.first = k == 0 ? 1 : 0;
             int const lines = P.dy == 0 ? h : (P.dx == 0 ? w : w + h - 1);
-            hipLaunchKernelGGL(sgm_path_kernel, dim3(lines), dim3(64), 0, stream,
-                P);
+            if (adapt)
+                hipLaunchKernelGGL(sgm_path_kernel<true>, dim3(lines), dim3(64), 0, stream,
+                    P);
+            else
+                hipLaunchKernelGGL(sgm_path_kernel<false>, dim3(lines), dim3(64), 0, stream,
+                    P);
         }
     }
     SMVS_HIP_CHECK(hipGetLastError());
@@ -1699,17 +1913,17 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
 
 using namespace smvs_hip;
 
-extern "C" int
-smvs_sgm_run(int device, const uint8_t *main_img, int w, int h,
+static int
+sgm_run_impl(int device, const uint8_t *main_img, int w, int h,
     const uint8_t *neighbor_img, int nw, int nh, const float *M,
     const float *t, float min_depth, float max_depth, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, float *depth, int32_t *argmin,
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth, int32_t *argmin,
     uint16_t *cost, uint16_t *sgm)
 {
     SMVS_REQUIRE(main_img && neighbor_img && M && t, "null argument");
     SMVS_REQUIRE(w > 10 && h > 8 && nw > 1 && nh > 1, "image too small");
     int rc = check_sgm_options(num_steps, min_depth, max_depth, penalty1,
-        penalty2);
+        penalty2, p2_mode);
     if (rc != SMVS_OK)
         return rc;
     WorkspaceLease lease(device);
@@ -1730,7 +1944,7 @@ smvs_sgm_run(int device, const uint8_t *main_img, int w, int h,
         || (rc = ws.upload(d_nbr, neighbor_img, nnpix)))
         return rc;
     if ((rc = sgm_run_device(B, d_main, w, h, d_nbr, nw, nh, M, t, min_depth,
-            max_depth, num_steps, penalty1, penalty2, d_depth)) != SMVS_OK)
+            max_depth, num_steps, penalty1, penalty2, p2_mode, d_depth)) != SMVS_OK)
         return rc;
     if (depth != nullptr
         && (rc = ws.download(depth, d_depth, sizeof(float) * npix)) != SMVS_OK)
@@ -1753,6 +1967,30 @@ smvs_sgm_run(int device, const uint8_t *main_img, int w, int h,
     }
     SMVS_HIP_CHECK(hipStreamSynchronize(ws.stream));
     return SMVS_OK;
+}
+
+extern "C" int
+smvs_sgm_run(int device, const uint8_t *main_img, int w, int h,
+    const uint8_t *neighbor_img, int nw, int nh, const float *M,
+    const float *t, float min_depth, float max_depth, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, float *depth, int32_t *argmin,
+    uint16_t *cost, uint16_t *sgm)
+{
+    return sgm_run_impl(device, main_img, w, h, neighbor_img, nw, nh, M, t, min_depth,
+        max_depth, num_steps, penalty1, penalty2, SMVS_SGM_P2_CONSTANT, depth, argmin,
+        cost, sgm);
+}
+
+// sgm_stereo.cc:310-346 with p2_mode = SMVS_SGM_P2_ADAPTIVE
+extern "C" int
+smvs_sgm_run_mode(int device, const uint8_t *main_img, int w, int h,
+    const uint8_t *neighbor_img, int nw, int nh, const float *M,
+    const float *t, float min_depth, float max_depth, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth, int32_t *argmin,
+    uint16_t *cost, uint16_t *sgm)
+{
+    return sgm_run_impl(device, main_img, w, h, neighbor_img, nw, nh, M, t, min_depth,
+        max_depth, num_steps, penalty1, penalty2, p2_mode, depth, argmin, cost, sgm);
 }
 
 // StereoView::get_byte_image (desaturate<uint8_t>, stereo_view.cc:86-95
@@ -1847,8 +2085,15 @@ static int
 sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
     int main_channels, const smvs_sgm_neighbor *neighbors,
     const int *neighbor_channels, int n_neighbors, int halvings, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, float *depth)
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth)
 {
+    SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
+        "unknown penalty2 mode");
+    if (p2_mode != SMVS_SGM_P2_CONSTANT) {
+        int const prc = check_sgm_penalties(penalty1, penalty2, p2_mode);
+        if (prc != SMVS_OK)
+            return prc;
+    }
     SMVS_REQUIRE(main_img && neighbors && depth, "null argument");
     SMVS_REQUIRE(n_neighbors >= 1 && n_neighbors <= 2,
         "one or two neighbours (app/smvsrecon.cc:360-365)");
@@ -1889,7 +2134,8 @@ sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
             return rc;
     }
     if ((rc = ws.ensure(WS_BWD, max_nnpix, &d_bwd))
-        || (rc = B.ensure(npix > max_nnpix ? npix : max_nnpix, num_steps, penalty2)))
+        || (rc = B.ensure(npix > max_nnpix ? npix : max_nnpix, num_steps,
+                SgmWorkspace::largest_penalty2(penalty1, penalty2, p2_mode))))
         return rc;
     for (int k = 0; k < n_neighbors; ++k) {
         smvs_sgm_neighbor const &N = neighbors[k];
@@ -1897,11 +2143,11 @@ sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
         // then neighbour -> main with the neighbour's own depth range
         if ((rc = sgm_run_device(B, d_main, mw, mh, d_nbr[k], nw[k], nh[k],
                 N.M_fwd, N.t_fwd, N.range_main[0], N.range_main[1], num_steps,
-                penalty1, penalty2, d_fwd[k])) != SMVS_OK)
+                penalty1, penalty2, p2_mode, d_fwd[k])) != SMVS_OK)
             return rc;
         if ((rc = sgm_run_device(B, d_nbr[k], nw[k], nh[k], d_main, mw, mh,
                 N.M_bwd, N.t_bwd, N.range_neighbor[0], N.range_neighbor[1],
-                num_steps, penalty1, penalty2, d_bwd)) != SMVS_OK)
+                num_steps, penalty1, penalty2, p2_mode, d_bwd)) != SMVS_OK)
             return rc;
         LrArgs L;
         L.d_main = d_fwd[k];
@@ -1937,7 +2183,17 @@ smvs_sgm_depth_for_view(int device, const uint8_t *main_img, int w, int h,
     uint16_t penalty1, uint16_t penalty2, float *depth)
 {
     return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
-        n_neighbors, 0, num_steps, penalty1, penalty2, depth);
+        n_neighbors, 0, num_steps, penalty1, penalty2, SMVS_SGM_P2_CONSTANT, depth);
+}
+
+// sgm_stereo.cc:310-346 with p2_mode = SMVS_SGM_P2_ADAPTIVE
+extern "C" int
+smvs_sgm_depth_for_view_mode(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth)
+{
+    return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
+        n_neighbors, 0, num_steps, penalty1, penalty2, p2_mode, depth);
 }
 
 extern "C" int
@@ -1946,13 +2202,28 @@ smvs_sgm_depth_for_view_raw(int device, const uint8_t *main_img, int w, int h,
     int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
     uint16_t penalty2, float *depth)
 {
+    return smvs_sgm_depth_for_view_raw_mode(device, main_img, w, h, channels, neighbors,
+        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2,
+        SMVS_SGM_P2_CONSTANT, depth);
+}
+
+// sgm_stereo.cc:310-346 with p2_mode = SMVS_SGM_P2_ADAPTIVE
+extern "C" int
+smvs_sgm_depth_for_view_raw_mode(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, int p2_mode, float *depth)
+{
+    SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
+        "unknown penalty2 mode");
     SMVS_REQUIRE(channels == 1 || channels == 3, "1 or 3 channels");
     SMVS_REQUIRE(neighbor_channels != nullptr, "null argument");
     for (int k = 0; k < n_neighbors && k < 2; ++k)
         SMVS_REQUIRE(neighbor_channels[k] == 1 || neighbor_channels[k] == 3,
             "1 or 3 channels");
     return sgm_depth_for_view_impl(device, main_img, w, h, channels, neighbors,
-        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, depth);
+        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, p2_mode,
+        depth);
 }
 
 extern "C" int

@@ -394,8 +394,14 @@ class ViewContext:
         return {k: (ms[i], cnt[i]) for i, k in enumerate(_capi.K_NAMES)}
 
 
+P2_CONSTANT, P2_ADAPTIVE = 0, 1   # smvs_sgm_p2_mode of include/smvs_hip.h
+
+
 def sgm_run(main_img, neighbor_img, M, t, min_depth, max_depth, num_steps=128,
-            p1=6, p2=96, device=0, want_volumes=False):
+            p1=6, p2=96, device=0, want_volumes=False, adaptive_p2=False):
+    """SGMStereo::run_sgm on the device.  adaptive_p2: the path aggregation of
+    the reference's build without SSE (lib/sgm_stereo.cc:310-346, penalty2
+    adapted to the intensity step); off by default."""
     lib = _capi.load()
     main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
     neighbor_img = np.ascontiguousarray(neighbor_img, dtype=np.uint8)
@@ -405,11 +411,11 @@ def sgm_run(main_img, neighbor_img, M, t, min_depth, max_depth, num_steps=128,
     argmin = np.zeros((h, w), dtype=np.int32)
     cost = np.zeros((h, w, num_steps), dtype=np.uint16) if want_volumes else None
     sgm = np.zeros((h, w, num_steps), dtype=np.uint16) if want_volumes else None
-    check(lib.smvs_sgm_run(device, _p(main_img, _u8p), w, h,
+    check(lib.smvs_sgm_run_mode(device, _p(main_img, _u8p), w, h,
           _p(neighbor_img, _u8p), nw, nh, _p(M, _fp), _p(t, _fp),
           C.c_float(min_depth), C.c_float(max_depth), num_steps,
-          C.c_uint16(p1), C.c_uint16(p2), _p(depth, _fp), _p(argmin, _i32p),
-          _p(cost, _u16p), _p(sgm, _u16p)))
+          C.c_uint16(p1), C.c_uint16(p2), C.c_int(P2_ADAPTIVE if adaptive_p2 else P2_CONSTANT),
+          _p(depth, _fp), _p(argmin, _i32p), _p(cost, _u16p), _p(sgm, _u16p)))
     return dict(depth=depth, argmin=argmin, cost=cost, sgm=sgm)
 
 
@@ -433,13 +439,21 @@ class SgmNeighbor(C.Structure):
                 ("range_main", C.c_float * 2), ("range_neighbor", C.c_float * 2)]
 
 
-def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0):
+def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0,
+                       adaptive_p2=False, halvings=None):
     """reconstruct_sgm_depth_for_view on the device.  neighbors: list of dicts
     {image, M_fwd, t_fwd, M_bwd, t_bwd, range_main, range_neighbor} (SGM-scale
-    u8 images, float reprojections)."""
+    u8 images, float reprojections).  adaptive_p2: as for sgm_run.
+    halvings (an int): the images are full-resolution u8 embeddings of one or
+    three channels, desaturated and halved that often on the device
+    (smvs_sgm_depth_for_view_raw_mode); the map has the SGM-scale size."""
     lib = _capi.load()
+    mode = C.c_int(P2_ADAPTIVE if adaptive_p2 else P2_CONSTANT)
     main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
-    h, w = main_img.shape
+    h, w = main_img.shape[:2]
+    if halvings is not None:
+        return _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device,
+                                       mode, int(halvings))
     keep = []
     arr = (SgmNeighbor * len(neighbors))()
     for k, nb in enumerate(neighbors):
@@ -453,8 +467,40 @@ def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0
             for i in range(n):
                 getattr(arr[k], name)[i] = float(v[i])
     depth = np.zeros((h, w), dtype=np.float32)
-    check(lib.smvs_sgm_depth_for_view(device, _p(main_img, _u8p), w, h, arr,
-          len(neighbors), num_steps, C.c_uint16(p1), C.c_uint16(p2), _p(depth, _fp)))
+    check(lib.smvs_sgm_depth_for_view_mode(device, _p(main_img, _u8p), w, h, arr,
+          len(neighbors), num_steps, C.c_uint16(p1), C.c_uint16(p2), mode, _p(depth, _fp)))
+    return depth
+
+
+def _sgm_neighbors(neighbors, keep):
+    arr = (SgmNeighbor * len(neighbors))()
+    for k, nb in enumerate(neighbors):
+        img = np.ascontiguousarray(nb["image"], dtype=np.uint8)
+        keep.append(img)
+        arr[k].image = _p(img, _u8p)
+        arr[k].height, arr[k].width = img.shape[:2]
+        for name, n in (("M_fwd", 9), ("t_fwd", 3), ("M_bwd", 9), ("t_bwd", 3),
+                        ("range_main", 2), ("range_neighbor", 2)):
+            v = _f32(nb[name]).reshape(n)
+            for i in range(n):
+                getattr(arr[k], name)[i] = float(v[i])
+    return arr
+
+
+def _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device, mode,
+                            halvings):
+    keep = []
+    arr = _sgm_neighbors(neighbors, keep)
+    h, w = main_img.shape[:2]
+    channels = 1 if main_img.ndim == 2 else main_img.shape[2]
+    nch = (C.c_int * len(neighbors))(*[1 if k.ndim == 2 else k.shape[2] for k in keep])
+    ow, oh = w, h
+    for _ in range(halvings):
+        ow, oh = (ow + 1) // 2, (oh + 1) // 2
+    depth = np.zeros((oh, ow), dtype=np.float32)
+    check(lib.smvs_sgm_depth_for_view_raw_mode(device, _p(main_img, _u8p), w, h, channels,
+          arr, nch, len(neighbors), halvings, num_steps, C.c_uint16(p1), C.c_uint16(p2),
+          mode, _p(depth, _fp)))
     return depth
 
 

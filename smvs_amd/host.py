@@ -227,14 +227,17 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       regularization=1.0, output_scale=2, use_shading=False, use_sgm=True,
                       force_recon=False, force_sgm=False, sgm_range=(0.0, 0.0), sgm_scale=1,
                       num_neighbors=6, min_neighbors=3, first_device=0, num_devices=1,
-                      views_in_flight=2, input_scale=-1, max_pixels=1700000, details=False):
+                      views_in_flight=2, input_scale=-1, max_pixels=1700000, details=False,
+                      sgm_adaptive_penalty2=False):
     """smvsrecon's scene-level run (app/smvsrecon.cc:400-745) through
     smvs_amd::reconstruct_scene: returns (reconstructed ids, skipped, seconds)
     [, input scale used if `details`].  input_scale < 0 (the default, as
     app/smvsrecon.cc:44): smvsrecon's automatic choice from max_pixels
     (:477-500); 0: full resolution; > 0: the views are read from the
     embedding undist-L<input_scale>, created with rescale_half_size_gaussian
-    where missing (:621-650), and the outputs are named smvs-B<input_scale>."""
+    where missing (:621-650), and the outputs are named smvs-B<input_scale>.
+    sgm_adaptive_penalty2: the SGM front end as the reference's build without
+    SSE runs it (lib/sgm_stereo.cc:310-346); off by default."""
     lib = load()
     st = ReconSettings(image_embedding.encode(), regularization, output_scale,
                        1 if use_shading else 0, 1 if use_sgm else 0,
@@ -248,7 +251,8 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                              C.byref(cap), None, None, None, None, None, None, None)
     out = np.zeros(max(cap.value, 1), np.int32)
     n = C.c_int(0); sk = C.c_int(0); secs = C.c_double(0.0); used = C.c_int(0)
-    rc = lib.smvs_host_reconstruct_scene(scene_dir.encode(), C.byref(st),
+    rc = lib.smvs_host_reconstruct_scene_mode(scene_dir.encode(), C.byref(st),
+        C.c_int(1 if sgm_adaptive_penalty2 else 0),
         ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), out.ctypes.data_as(_i32p),
         C.c_int(out.size), C.byref(n), C.byref(sk), C.byref(secs), C.byref(used))
@@ -339,7 +343,11 @@ def view_queue_selftest(n_tasks, num_devices, views_in_flight, throwing_task=-1)
     return dev, wrk
 
 
-def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0):
+def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
+              adaptive_penalty2=False):
+    """reconstruct_sgm_depth_for_view through the host mirror.
+    adaptive_penalty2: SGMStereo::Options::adaptive_penalty2 (the reference's
+    build without SSE, lib/sgm_stereo.cc:310-346); off by default."""
     lib = load()
     keep = []
     main, subs, n_subs, b = _marshal(inputs, keep)
@@ -348,9 +356,9 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0):
         w, h = (w + 1) // 2, (h + 1) // 2
     out = np.zeros((h, w), dtype=np.float32)
     ow = C.c_int(0); oh = C.c_int(0)
-    rc = lib.smvs_host_sgm_depth(C.byref(main), subs, n_subs, C.byref(b),
+    rc = lib.smvs_host_sgm_depth_mode(C.byref(main), subs, n_subs, C.byref(b),
         sgm_scale, C.c_float(min_depth), C.c_float(max_depth), device,
-        out.ctypes.data_as(_fp), C.byref(ow), C.byref(oh))
+        C.c_int(1 if adaptive_penalty2 else 0), out.ctypes.data_as(_fp), C.byref(ow), C.byref(oh))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
     assert (ow.value, oh.value) == (w, h)
