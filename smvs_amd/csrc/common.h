@@ -73,11 +73,11 @@ enum {
                      // the steps enqueued behind it change nothing
     I_SURF_VALID,    // valid patches of the device surface (surface.hip)
     I_SURF_CHANGED,  // patches filled / deleted by the last grid operation
-    I_TOPO_PASS0 = 16,   // cut_boundaries passes enqueued ahead: {deleted, candidates} of
-                         // pass k at I_TOPO_PASS0 + 2 k (topology.hip), TOPO_AHEAD passes
+    I_TOPO_PASS0 = 16,   // cut_boundaries: {deleted, candidates} of a pass, two word pairs
+                         // that the passes of the three-launch form alternate between
+                         // (topology.hip); the words up to I_NUM are not used
     I_NUM = 24
 };
-constexpr int TOPO_AHEAD = 4;
 
 struct SubPlanes {
     int width = 0, height = 0;
@@ -191,8 +191,7 @@ struct smvs_ctx {
     hipEvent_t image_ready[SMVS_MAX_SUBS + 1] = { nullptr };
     uint8_t *upload_stage[SMVS_MAX_SUBS + 1] = { nullptr };
     size_t upload_stage_cap[SMVS_MAX_SUBS + 1] = { 0 };
-    uint32_t image_pending = 0;     // bit v: on its way (staged or being converted), not yet waited for
-    uint32_t image_direct = 0;      // bit v: converted by the upload itself (no staging buffer)
+    uint32_t image_pending = 0;     // bit v: on its way into upload_stage[v], not yet waited for
     uint32_t upload_stage_busy = 0; // bit v: a conversion from upload_stage[v] may be in flight
     // resident PCG (cg_resident.hip)
     double *res_work = nullptr;     // partial sums + barrier words
@@ -247,8 +246,6 @@ struct smvs_ctx {
     size_t topo_mse_arrived_cap = 0;
     double *topo_pix = nullptr;       // [H][W][3]: surface depth, d/dx, d/dy per pixel
     size_t topo_pix_cap = 0;
-    uint8_t *topo_pair_alive = nullptr;   // [P][n_subs]: verdict of the visibility test's
-    size_t topo_pair_cap = 0;             // geometric half (topo_visibility_kernel<1>)
 
     // grid surgery on the device (surface.hip)
     float *surf_depth = nullptr;       // [H][W] Surface::depth (surface.cc:46-50): the

@@ -221,7 +221,6 @@ ctx_reset_for_reuse(smvs_ctx *ctx)
 {
     ctx->image_ok = ctx->planes_ok = 0;
     ctx->image_pending = 0;
-    ctx->image_direct = 0;
     ctx->upload_stage_busy = 0;   // (the caller has synchronised the stream)
     ctx->sgm_pin_busy = false;
     ctx->sgm_resident = false;
@@ -437,8 +436,6 @@ ctx_free(smvs_ctx *ctx)
         (void)hipFree(ctx->topo_mse_arrived);
     if (ctx->topo_pix)
         (void)hipFree(ctx->topo_pix);
-    if (ctx->topo_pair_alive)
-        (void)hipFree(ctx->topo_pair_alive);
     if (ctx->blur_tmp[0])
         (void)hipFree(ctx->blur_tmp[0]);
     if (ctx->blur_tmp[1])

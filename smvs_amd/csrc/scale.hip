@@ -17,16 +17,6 @@
 
 namespace smvs_hip {
 
-__global__ void __launch_bounds__(256)
-byte_to_float_kernel(const uint8_t *__restrict__ in, float *__restrict__ out,
-    size_t n)
-{
-#pragma clang fp contract(off)
-    size_t const i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        out[i] = (float)in[i] / 255.0f;
-}
-
 // Sixteen bytes per thread (one 16-byte load, four 16-byte stores) out of the
 // context's own staging buffers (device allocations: 256-byte aligned) instead
 // of a byte per thread: 24 k workgroups of four-byte stores were 16 us
@@ -61,34 +51,6 @@ byte_to_float_blocks(size_t n)
     return (unsigned)std::max<size_t>(1, (threads + 255) / 256);
 }
 
-// The same conversion out of the caller's page-locked memory (the bytes cross
-// the bus as the kernel reads them) with a SMALL grid that strides over the
-// image, sixteen bytes per thread and step: enough requests in flight for the
-// bus, and the rest of the chip stays free for the context's own kernels
-// (SMVS_UPLOAD_STREAM=kernel, smvs_ctx_upload_image_async).
-constexpr int UPLOAD_BLOCKS = 64;
-
-__global__ void __launch_bounds__(256)
-host_bytes_to_float_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, size_t n)
-{
-#pragma clang fp contract(off)
-    size_t const threads = (size_t)gridDim.x * blockDim.x;
-    size_t const t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    size_t const chunks = n / 16;
-    for (size_t c = t; c < chunks; c += threads) {
-        uint4 const v = reinterpret_cast<const uint4 *>(in)[c];
-        uint32_t const w[4] = { v.x, v.y, v.z, v.w };
-        float4 *dst = reinterpret_cast<float4 *>(out + c * 16);
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            dst[q] = make_float4((float)(w[q] & 0xFFu) / 255.0f,
-                (float)((w[q] >> 8) & 0xFFu) / 255.0f, (float)((w[q] >> 16) & 0xFFu) / 255.0f,
-                (float)(w[q] >> 24) / 255.0f);
-    }
-    for (size_t i = chunks * 16 + t; i < n; i += threads)
-        out[i] = (float)in[i] / 255.0f;
-}
-
 // The Gaussian taps of one scale, handed to the kernels by value: the tap
 // index is uniform across a wave, so the weights come out of the kernel
 // arguments with scalar loads.  wsum is Accum<float>'s weight total: the
@@ -115,8 +77,7 @@ constexpr int BLUR_X_LDS_FROM = 12;   // half width from which blur_x_kernel sta
 // ROWS (round 6, the per-thread-loads form only): image rows per workgroup.  With
 // one row a 1920 x 1080 x 3 image was 24,840 workgroups of one output per
 // thread; the rows of a thread are independent, so their loads are all in flight
-// together and a launch is a quarter of the workgroups (SMVS_BLUR_X_ROWS=1: one
-// row, A/B).
+// together and a launch is a quarter of the workgroups.
 constexpr int BLUR_X_ROWS = 4;
 
 template <int C, int KS, int ROWS>
@@ -275,18 +236,8 @@ launch_blur_x(hipStream_t stream, const float *in, float *tmp, int w, int h, int
     BlurTaps const &taps)
 {
     unsigned const bx = (unsigned)((w * c + 255) / 256);
-    constexpr bool staged = KS >= BLUR_X_LDS_FROM;
-    const char *env = std::getenv("SMVS_BLUR_X_ROWS");
-    if (staged || (env != nullptr && env[0] == '1')) {
-        if (c == 1)
-            hipLaunchKernelGGL((blur_x_kernel<1, KS, 1>), dim3(bx, (unsigned)h), dim3(256), 0,
-                stream, in, tmp, w, h, taps);
-        else
-            hipLaunchKernelGGL((blur_x_kernel<3, KS, 1>), dim3(bx, (unsigned)h), dim3(256), 0,
-                stream, in, tmp, w, h, taps);
-        return;
-    }
-    constexpr int ROWS = staged ? 1 : BLUR_X_ROWS;
+    // (the LDS form takes one row)
+    constexpr int ROWS = KS >= BLUR_X_LDS_FROM ? 1 : BLUR_X_ROWS;
     dim3 const grid(bx, (unsigned)((h + ROWS - 1) / ROWS));
     if (c == 1)
         hipLaunchKernelGGL((blur_x_kernel<1, KS, ROWS>), grid, dim3(256), 0, stream, in, tmp,
@@ -310,15 +261,9 @@ launch_blur_ks(hipStream_t stream, const float *in, float *tmp, float *out, int 
     // on different XCDs and the kernel fetched 8 x its input (225 MB at KS = 23,
     // profiles/r6_hbm_traffic.txt).  A row of the grid padded to a multiple of 8
     // keeps a column of blocks on ONE XCD (the padding blocks leave at once).
-    // SMVS_BLUR_XCD=0: unpadded (A/B).
-    static bool const pad = [] {
-        const char *e = std::getenv("SMVS_BLUR_XCD");
-        return !(e != nullptr && e[0] == '0');
-    }();
-    unsigned const by = pad ? (bx + 7u) & ~7u : bx;
     hipLaunchKernelGGL(blur_y_kernel<KS>,
-        dim3(by, (unsigned)((h + BLUR_ROWS - 1) / BLUR_ROWS)), dim3(256), 0, stream, tmp,
-        out, w * c, h, taps);
+        dim3((bx + 7u) & ~7u, (unsigned)((h + BLUR_ROWS - 1) / BLUR_ROWS)), dim3(256), 0,
+        stream, tmp, out, w * c, h, taps);
 }
 
 static void
@@ -445,11 +390,11 @@ gradients_kernel(const float *__restrict__ img, int w, int h, int c,
 // kernels (A/B).
 // nine rows per tile: 960 tiles at 1920 x 1080, which the chip holds at once (four
 // workgroups of 33 KB per CU); with eight rows the 1,080 tiles ran as a full round
-// and a tail (2.39 against 2.34 ms per view, SMVS_FUSE_ROWS=8)
-constexpr int FUSE_ROWS_DEFAULT = 9;
+// and a tail (2.39 against 2.34 ms per view)
+constexpr int FUSE_ROWS = 9;
 constexpr int FUSE_COLS = 254;          // + the two halo columns = 256 pixels = the workgroup
 
-template <int C, int KS, int FUSE_ROWS>
+template <int C, int KS>
 __global__ void __launch_bounds__(256)
 blur_y_gradients_kernel(const float *__restrict__ in, int w, int h, BlurTaps taps,
     FitMatrix fit, float2 *__restrict__ grad, float4 *__restrict__ hess)
@@ -583,39 +528,28 @@ quadratic_fit_matrix(void)
     return f;
 }
 
-// blur_x + the fused y pass / luminance / fit (the half widths of the scales
-// 0 .. 5 only: any other takes the separate kernels).  false: not launched.
-template <int KS, int ROWS>
+// blur_x + the fused y pass / luminance / fit at half width KS
+template <int KS>
 static bool
-launch_blur_gradients_rows(hipStream_t stream, const float *in, float *tmp, int w, int h,
+launch_blur_gradients_ks(hipStream_t stream, const float *in, float *tmp, int w, int h,
     int c, BlurTaps const &taps, FitMatrix const &fit, float2 *grad, float4 *hess)
 {
     launch_blur_x<KS>(stream, in, tmp, w, h, c, taps);
     // (a grid row is a multiple of 8 workgroups: a column of tiles, whose tap rows
     // overlap, stays on ONE XCD and its L2 -- launch_blur_ks)
     dim3 const grid((((unsigned)w + FUSE_COLS - 1) / FUSE_COLS + 7u) & ~7u,
-        ((unsigned)h + ROWS - 1) / ROWS);
+        ((unsigned)h + FUSE_ROWS - 1) / FUSE_ROWS);
     if (c == 1)
-        hipLaunchKernelGGL((blur_y_gradients_kernel<1, KS, ROWS>), grid, dim3(256), 0, stream,
+        hipLaunchKernelGGL((blur_y_gradients_kernel<1, KS>), grid, dim3(256), 0, stream,
             tmp, w, h, taps, fit, grad, hess);
     else
-        hipLaunchKernelGGL((blur_y_gradients_kernel<3, KS, ROWS>), grid, dim3(256), 0, stream,
+        hipLaunchKernelGGL((blur_y_gradients_kernel<3, KS>), grid, dim3(256), 0, stream,
             tmp, w, h, taps, fit, grad, hess);
     return true;
 }
 
-template <int KS>
-static bool
-launch_blur_gradients_ks(hipStream_t stream, const float *in, float *tmp, int w, int h,
-    int c, BlurTaps const &taps, FitMatrix const &fit, float2 *grad, float4 *hess)
-{
-    const char *e = std::getenv("SMVS_FUSE_ROWS");
-    if (e != nullptr && std::atoi(e) == 8)
-        return launch_blur_gradients_rows<KS, 8>(stream, in, tmp, w, h, c, taps, fit, grad, hess);
-    return launch_blur_gradients_rows<KS, FUSE_ROWS_DEFAULT>(stream, in, tmp, w, h, c, taps, fit,
-        grad, hess);
-}
-
+// ... for the half widths of the scales 0 .. 5 only: any other takes the
+// separate kernels.  false: not launched.
 static bool
 launch_blur_gradients(hipStream_t stream, const float *in, float *tmp, int w, int h, int c,
     BlurTaps const &taps, FitMatrix const &fit, float2 *grad, float4 *hess)
@@ -726,82 +660,18 @@ smvs_ctx_upload_image_async(smvs_ctx *ctx, int view, int width, int height,
         vi.h = height;
         vi.c = channels;
     }
-    bool const had_image = ((ctx->image_ok >> v) & 1u) != 0u;
     ctx->image_ok &= ~(1u << v);
     ctx->image_pending &= ~(1u << v);
-    ctx->image_direct &= ~(1u << v);
-    // SMVS_UPLOAD_STREAM=same: the copies on the context's own stream (A/B)
-    static bool const same_stream = [] {
-        const char *e = std::getenv("SMVS_UPLOAD_STREAM");
-        return e != nullptr && e[0] == 's';
-    }();
-    auto const ensure_stage = [&]() -> int {
-        if (ctx->upload_stage_cap[v] < n) {
-            ctx->upload_stage_cap[v] = 0;
-            int const arc = device_alloc(&ctx->upload_stage[v], n);
-            if (arc != SMVS_OK)
-                return arc;
-            ctx->upload_stage_cap[v] = n;
-        }
-        return SMVS_OK;
-    };
-    if (same_stream) {
-        if ((rc = ensure_stage()) != SMVS_OK)
-            return rc;
-        SMVS_HIP_CHECK(hipMemcpyAsync(ctx->upload_stage[v], bytes, n, hipMemcpyHostToDevice,
-            ctx->stream));
-        hipLaunchKernelGGL(byte_to_float16_kernel, dim3(byte_to_float_blocks(n)),
-            dim3(256), 0, ctx->stream, ctx->upload_stage[v], vi.data, n);
-        SMVS_HIP_CHECK(hipGetLastError());
-        ctx->image_ok |= 1u << v;
-        return SMVS_OK;
-    }
-    // SMVS_UPLOAD_STREAM=kernel (round 6, measured and left off): the images
-    // converted straight out of the caller's page-locked memory by small-grid
-    // kernels (the bytes cross the bus as the kernel reads them) -- the main image
-    // on the context's stream, the others on the copy stream with their events --
-    // instead of DMAs into staging buffers + a conversion each.  A warm optimize()
-    // with SGM 16.2-16.4 against 15.9-16.1 ms, 69-70 against 70-72 views/s with
-    // eight views in flight: the DMA engines cost the compute queues nothing.
-    static bool const by_dma = [] {
-        const char *e = std::getenv("SMVS_UPLOAD_STREAM");
-        return !(e != nullptr && e[0] == 'k');
-    }();
-    auto const convert_from_host = [&](hipStream_t stream) {
-        if ((reinterpret_cast<uintptr_t>(bytes) & 15u) == 0u)
-            hipLaunchKernelGGL(host_bytes_to_float_kernel, dim3(UPLOAD_BLOCKS), dim3(256), 0,
-                stream, bytes, vi.data, n);
-        else
-            hipLaunchKernelGGL(byte_to_float_kernel, dim3((unsigned)((n + 255) / 256)),
-                dim3(256), 0, stream, bytes, vi.data, n);
-    };
-    if (v == 0 && !by_dma) {
-        convert_from_host(ctx->stream);
-        SMVS_HIP_CHECK(hipGetLastError());
-        ctx->image_ok |= 1u << v;
-        return SMVS_OK;
-    }
     if (ctx->copy_stream == nullptr)
         SMVS_HIP_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     if (ctx->image_ready[v] == nullptr)
         SMVS_HIP_CHECK(hipEventCreateWithFlags(&ctx->image_ready[v], hipEventDisableTiming));
-    if (!by_dma) {
-        // (an image this view had before may still be read by kernels of the
-        // context's stream: the new one is then written behind them)
-        if (had_image) {
-            SMVS_HIP_CHECK(hipEventRecord(ctx->image_ready[v], ctx->stream));
-            SMVS_HIP_CHECK(hipStreamWaitEvent(ctx->copy_stream, ctx->image_ready[v], 0));
-        }
-        convert_from_host(ctx->copy_stream);
-        SMVS_HIP_CHECK(hipGetLastError());
-        SMVS_HIP_CHECK(hipEventRecord(ctx->image_ready[v], ctx->copy_stream));
-        ctx->image_pending |= 1u << v;
-        ctx->image_direct |= 1u << v;
-        ctx->image_ok |= 1u << v;   // (every consumer waits for what it reads)
-        return SMVS_OK;
+    if (ctx->upload_stage_cap[v] < n) {
+        ctx->upload_stage_cap[v] = 0;
+        if ((rc = device_alloc(&ctx->upload_stage[v], n)) != SMVS_OK)
+            return rc;
+        ctx->upload_stage_cap[v] = n;
     }
-    if ((rc = ensure_stage()) != SMVS_OK)
-        return rc;
     // (a conversion still reading this staging buffer: only a second upload
     // of the same view before the first was read -- the copy then waits for the
     // context's stream; the common case has nothing to wait for and must not be
@@ -829,10 +699,6 @@ smvs_hip::ctx_materialise_images(smvs_ctx *ctx, uint32_t views)
         size_t const n = (size_t)vi.w * vi.h * vi.c;
         SMVS_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->image_ready[v], 0));
         ctx->image_pending &= ~(1u << v);
-        if ((ctx->image_direct >> v) & 1u) {
-            ctx->image_direct &= ~(1u << v);     // (converted by the upload itself)
-            continue;
-        }
         hipLaunchKernelGGL(byte_to_float16_kernel, dim3(byte_to_float_blocks(n)),
             dim3(256), 0, ctx->stream, ctx->upload_stage[v], vi.data, n);
         SMVS_HIP_CHECK(hipGetLastError());

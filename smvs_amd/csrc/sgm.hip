@@ -220,7 +220,7 @@ for_each_index(F &f, std::integer_sequence<int, I...>)
 __global__ void __launch_bounds__(256)
 cost_packed_kernel(const uint8_t *__restrict__ warped,
     const unsigned long long *__restrict__ main_census, int w, int h, int D,
-    uint8_t *__restrict__ cost, int xcd_bands)
+    uint8_t *__restrict__ cost)
 {
     constexpr int TW = CP_W + 8;
     __shared__ uint8_t tile[(CP_H + 6) * TW * CP_D];
@@ -231,7 +231,7 @@ cost_packed_kernel(const uint8_t *__restrict__ warped,
     // time: 178 MB read per launch for a 66 MB volume (profiles/r6_sgm_counters.txt).
     // The launch is padded to eight bands of equal length.
     unsigned const band = gridDim.x >> 3;
-    unsigned const tile_id = xcd_bands ? (blockIdx.x & 7u) * band + (blockIdx.x >> 3) : blockIdx.x;
+    unsigned const tile_id = (blockIdx.x & 7u) * band + (blockIdx.x >> 3);
     if (tile_id >= (unsigned)(tiles_x * ((h + CP_H - 1) / CP_H)))
         return;
     int const x0 = (int)(tile_id % (unsigned)tiles_x) * CP_W;
@@ -1793,21 +1793,12 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     {
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_COST);
         int const tiles = ((w + CT_W - 1) / CT_W) * ((h + CT_H - 1) / CT_H);
-        // (SMVS_SGM_COST=tiled: the one-plane-per-lane kernel for every plane count)
-        static bool const force_tiled = [] {
-            const char *e = std::getenv("SMVS_SGM_COST");
-            return e != nullptr && e[0] == 't';
-        }();
-        // (SMVS_SGM_XCD=0: tiles in plain order, rounds 1-5; A/B)
-        static bool const bands = [] {
-            const char *e = std::getenv("SMVS_SGM_XCD");
-            return !(e != nullptr && e[0] == '0');
-        }();
-        if ((num_steps & 3) == 0 && !force_tiled)
+        // (the packed kernel stages four planes per load; any other plane count
+        // takes the one-plane-per-lane kernel)
+        if ((num_steps & 3) == 0)
             hipLaunchKernelGGL(cost_packed_kernel,
-                dim3(bands ? ((tiles + 7) / 8) * 8 : tiles, (num_steps + CP_D - 1) / CP_D),
-                dim3(256), 0, stream, B.warped, B.census, w, h, num_steps, B.cost,
-                bands ? 1 : 0);
+                dim3(((tiles + 7) / 8) * 8, (num_steps + CP_D - 1) / CP_D),
+                dim3(256), 0, stream, B.warped, B.census, w, h, num_steps, B.cost);
         else
             hipLaunchKernelGGL(cost_tiled_kernel,
                 dim3(tiles, (num_steps + CT_D - 1) / CT_D), dim3(256), 0, stream,

@@ -181,14 +181,6 @@ struct TopoArgs {
     int exact_divisions;
     // SMVS_NCC_PAIRS=0: the NCC samples of a lane one after the other
     int ncc_pairs;
-    // the two halves of the visibility test as launches of their own
-    // (topo_visibility_kernel<1> / <2>): what the geometric half decided per
-    // (patch, neighbour), [num_patches][n_subs]
-    uint8_t *pair_alive;
-    // cut_boundaries passes enqueued ahead of their predecessor's count: a pass
-    // whose predecessor deleted at most 10 patches does nothing
-    // (`while (deleted > 10)`, depth_optimizer.cc:186-190)
-    const int *pass_gate;
     // topo_visibility_kernel: lanes per (patch, neighbour) and the stash slots
     // per thread its launch reserves (vis_launch_shape)
     int vis_group, ncc_stash_slots;
@@ -618,18 +610,6 @@ topo_pixel_surface_kernel(TopoArgs A)
 // on the host (A.vis_group), the NCC's warped colours beyond the kept ones in an
 // LDS stash, a sample's depth and template entry from LDS, the neighbour
 // wave-uniform (blockIdx.y): 9.1 -> 5.8 ms per --no-sgm view, masks unchanged.
-//
-// PART 0: the whole test in one launch (the default).  SMVS_VIS_SPLIT=1
-// (round 6, an experiment that did not pay: 3 % slower) runs the two halves
-// as launches of their own with the NCC on, PART 1 = the pass over the patch's pixels (borders,
-// z-buffer, warp anisotropy) leaving its verdict per (patch, neighbour) in
-// `pair_alive`, PART 2 = ncc_for_patch for the pairs that are still alive:
-// the same statements in the same order (one body, `if constexpr`), so the
-// masks are those of PART 0 bit for bit -- but each half is compiled for its
-// own registers: the waves of the fused kernel waited for memory half of
-// their life at three per SIMD (profiles/r5_visibility_counters.txt), and the
-// NCC half without the Jacobian's live range fits more of them.
-template <int PART>
 __global__ void __launch_bounds__(256, 2)
 topo_visibility_kernel(TopoArgs A)
 {
@@ -656,10 +636,9 @@ topo_visibility_kernel(TopoArgs A)
     int const g_log2 = 31 - __clz(G);           // G = 1 << g_log2
     int const gl = threadIdx.x & (G - 1);     // lane inside the group
     int const dstride = ps * ps + 4;
-    // (PART 2 does not walk the pixels)
-    bool const depth_in_lds = PART != 2 && A.lds_depth_doubles > 0;
+    bool const depth_in_lds = A.lds_depth_doubles > 0;
     double *const my_depths = lds_depth + (threadIdx.x >> g_log2) * dstride;
-    if (PART != 1 && A.lds_tpl_n > 0) {
+    if (A.lds_tpl_n > 0) {
         const NccSample *src = A.ncc + A.ncc_off[31];
         for (int i = threadIdx.x; i < A.lds_tpl_n; i += 256) {
             NccSample const e = src[i];
@@ -682,8 +661,6 @@ topo_visibility_kernel(TopoArgs A)
     // of the vector arithmetic instead of 30 vector registers of every lane.
     int const s = (int)blockIdx.y;
     int const p = (int)(((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) >> g_log2);
-    // (index of the pair: < num_patches * n_subs, 32 bits)
-    unsigned const gid = (unsigned)p * (unsigned)A.n_subs + (unsigned)s;
     bool alive = p < A.num_patches && A.patch_valid[p];
     int const pc = alive ? p : 0;
     int const px = A.start_x + (pc % A.npx) * ps;
@@ -736,7 +713,7 @@ topo_visibility_kernel(TopoArgs A)
         worst = worst < ratio ? ratio : worst;
         return true;
     };
-    if (PART != 2 && alive) {
+    if (alive) {
         if (depth_in_lds) {
             int const n00 = (pc / A.npx) * A.stride + pc % A.npx;
             for (int c = gl; c < 4; c += G)
@@ -763,23 +740,13 @@ topo_visibility_kernel(TopoArgs A)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if constexpr (PART != 2) {
-        visible = group_all(visible, G, lane, red);
-        worst = vis_group_max(worst, G, red);
-        alive = alive && visible && !(worst > 8.0);
-    } else {
-        // (the verdict of the geometric half: the whole group reads one byte)
-        alive = alive && A.pair_alive[gid] != 0;   // (alive implies gid in range)
-    }
-    if constexpr (PART == 1) {
-        if (gl == 0 && p < A.num_patches)
-            A.pair_alive[gid] = alive ? 1 : 0;
-        return;
-    }
+    visible = group_all(visible, G, lane, red);
+    worst = vis_group_max(worst, G, red);
+    alive = alive && visible && !(worst > 8.0);
 
     // ncc_for_patch
     double ncc = 1.0;
-    if (PART != 1 && A.use_ncc) {
+    if (A.use_ncc) {
         int const flags = smvs_topo::ncc_flags(px, py, ps, mv.w, mv.h);
         const NccSample *tpl = A.ncc + A.ncc_off[flags];
         int const n = A.ncc_off[flags + 1] - A.ncc_off[flags];
@@ -1105,10 +1072,6 @@ topo_visibility_kernel(TopoArgs A)
 __global__ void __launch_bounds__(256)
 topo_mse_candidates_kernel(TopoArgs A)
 {
-    // (a pass enqueued ahead whose predecessor ended the loop: every thread of
-    // the launch reads the same word)
-    if (A.pass_gate != nullptr && *A.pass_gate <= 10)
-        return;
     int const p = blockIdx.x * blockDim.x + threadIdx.x;
     bool const in_range = p < A.num_patches;
     bool const valid = in_range && A.patch_valid[p];
@@ -1150,10 +1113,6 @@ topo_mse_kernel(TopoArgs A)
 {
 #pragma clang fp contract(off)
     __shared__ double red[4];
-    // (a pass enqueued ahead whose predecessor ended the loop: every thread of
-    // the launch reads the same word)
-    if (A.pass_gate != nullptr && *A.pass_gate <= 10)
-        return;
     int const ps = A.ps;
     int const G = group_size(ps, MSE_WORKGROUP_FROM);
     int const gl = threadIdx.x & (G - 1);
@@ -1288,10 +1247,6 @@ topo_border_nodes_kernel(TopoArgs A)
         *A.deleted = 0;
         *A.mse_count = 0;
     }
-    // (a pass enqueued ahead whose predecessor ended the loop: every thread of
-    // the launch reads the same word)
-    if (A.pass_gate != nullptr && *A.pass_gate <= 10)
-        return;
     int const n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= A.num_nodes)
         return;
@@ -1314,10 +1269,6 @@ __global__ void __launch_bounds__(256)
 topo_cut_patches_kernel(TopoArgs A)
 {
 #pragma clang fp contract(off)
-    // (a pass enqueued ahead whose predecessor ended the loop: every thread of
-    // the launch reads the same word)
-    if (A.pass_gate != nullptr && *A.pass_gate <= 10)
-        return;
     int const p = blockIdx.x * blockDim.x + threadIdx.x;
     bool remove = false;
     if (p < A.num_patches && A.patch_valid_rw[p]) {
@@ -1368,10 +1319,6 @@ topo_cut_patches_kernel(TopoArgs A)
 __global__ void __launch_bounds__(256)
 topo_cut_nodes_kernel(TopoArgs A)
 {
-    // (a pass enqueued ahead whose predecessor ended the loop: every thread of
-    // the launch reads the same word)
-    if (A.pass_gate != nullptr && *A.pass_gate <= 10)
-        return;
     int const n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= A.num_nodes || !A.node_valid_rw[n])
         return;
@@ -1589,8 +1536,6 @@ fill_args(smvs_ctx *ctx, TopoArgs *A, const char *who)
         const char *window = std::getenv("SMVS_ZBUF_WINDOW");
         A->zbuf5 = window != nullptr && std::atoi(window) == 3 ? 0 : 1;
     }
-    A->pair_alive = nullptr;
-    A->pass_gate = nullptr;
 
     A->ncc = ctx->topo_ncc;
     for (int i = 0; i < 33; ++i)
@@ -1783,46 +1728,19 @@ smvs_topology_subviews(smvs_ctx *ctx, const float *sgm_depth, int use_ncc,
         // (three workgroups per CU -- what the kernel's registers allow -- leave
         // each 53 KB of the 160)
         size_t const budget = 52 * 1024;
-        static bool const no_lds = [] {
-            const char *e = std::getenv("SMVS_NCC_LDS");
-            return e != nullptr && e[0] == '0';
-        }();
         size_t const depth_doubles = (size_t)(256 / group) * ((size_t)ctx->patchsize * ctx->patchsize + 4);
         size_t const tpl_n = (size_t)(ctx->topo_ncc_off[32] - ctx->topo_ncc_off[31]);
-        if (!no_lds && group <= 256 && stash_bytes + depth_doubles * 8 <= budget) {
+        if (group <= 256 && stash_bytes + depth_doubles * 8 <= budget) {
             A.lds_depth_doubles = (int)depth_doubles;
             stash_bytes += depth_doubles * 8;
         }
-        if (!no_lds && stash_bytes + tpl_n * 8 <= budget) {
+        if (stash_bytes + tpl_n * 8 <= budget) {
             A.lds_tpl_n = (int)tpl_n;
             stash_bytes += tpl_n * 8;
         }
     }
-    // SMVS_VIS_SPLIT=1: the two halves as launches of their own.  Measured
-    // (profiles/r6_visibility_split.txt): 165 + 461 us against 606 us fused --
-    // the NCC half keeps its 159 VGPRs, and the fused kernel overlaps the two
-    // halves' waits; the default stays fused.
-    static bool const split = [] {
-        const char *e = std::getenv("SMVS_VIS_SPLIT");
-        return e != nullptr && e[0] == '1';
-    }();
-    if (use_ncc && split) {
-        size_t const pairs = (size_t)ctx->num_patches * ctx->n_subs;
-        if (pairs > ctx->topo_pair_cap) {
-            ctx->topo_pair_cap = 0;
-            if ((rc = device_alloc(&ctx->topo_pair_alive, pairs)) != SMVS_OK)
-                return rc;
-            ctx->topo_pair_cap = pairs;
-        }
-        A.pair_alive = ctx->topo_pair_alive;
-        hipLaunchKernelGGL(topo_visibility_kernel<1>,
-            dim3((unsigned)((items + 255) / 256), (unsigned)ctx->n_subs), dim3(256), 0, ctx->stream, A);
-        hipLaunchKernelGGL(topo_visibility_kernel<2>,
-            dim3((unsigned)((items + 255) / 256), (unsigned)ctx->n_subs), dim3(256), stash_bytes, ctx->stream, A);
-    } else {
-        hipLaunchKernelGGL(topo_visibility_kernel<0>,
-            dim3((unsigned)((items + 255) / 256), (unsigned)ctx->n_subs), dim3(256), stash_bytes, ctx->stream, A);
-    }
+    hipLaunchKernelGGL(topo_visibility_kernel,
+        dim3((unsigned)((items + 255) / 256), (unsigned)ctx->n_subs), dim3(256), stash_bytes, ctx->stream, A);
     SMVS_HIP_CHECK(hipGetLastError());
     if (patch_vis_out == nullptr)
         return SMVS_OK;   // (the masks stay on the device: surface.hip)
@@ -1869,13 +1787,8 @@ prepare_patch_mse(smvs_ctx *ctx, TopoArgs *A, const char *who)
         ctx->topo_mse_list_cap = (size_t)ctx->num_patches;
     }
     // patch sizes 32 and up: the kernel works in chunks of 256 pixels
-    // (SMVS_MSE_CHUNKS=0: a workgroup per patch, as before round 6)
-    static bool const no_chunks = [] {
-        const char *e = std::getenv("SMVS_MSE_CHUNKS");
-        return e != nullptr && e[0] == '0';
-    }();
     int const pp = ctx->patchsize * ctx->patchsize;
-    int const chunks = !no_chunks && group_size(ctx->patchsize, MSE_WORKGROUP_FROM) == 256
+    int const chunks = group_size(ctx->patchsize, MSE_WORKGROUP_FROM) == 256
         && pp > 256 ? pp / 256 : 1;
     if (chunks > 1) {
         size_t const parts = (size_t)ctx->num_patches * chunks * 2;
@@ -1979,24 +1892,11 @@ smvs_topology_cut_boundaries(smvs_ctx *ctx, const float *inv_calibration9,
     int deleted = 11;
     bool const trace = std::getenv("SMVS_TOPO_TRACE") != nullptr;
     // `while (deleted > 10) deleted = cut_boundaries();` (depth_optimizer.cc:
-    // 186-190, 323-337).  The passes CAN be enqueued ahead, SMVS_TOPO_AHEAD=2..4
-    // at a time: pass k + 1 is gated on pass k's count on the device (its
-    // kernels leave at once when that count is <= 10) and the host reads the
-    // counts of the whole chunk with one synchronisation.  Measured in round 6
-    // (profiles/r6_cut_passes_ahead.txt): four ahead is SLOWER, a warm optimize()
-    // 18.5 -> 19.4 ms with SGM and 30.9 -> 34.0 ms without -- most calls end
-    // after their first pass (24 passes in ~20 calls per view), and the 118
-    // launches that then do nothing cost more than the round trips they save.
-    // The default is one pass per synchronisation, as in round 5.
-    static int const ahead = [] {
-        const char *e = std::getenv("SMVS_TOPO_AHEAD");
-        int const v = e != nullptr ? std::atoi(e) : 1;
-        return v < 1 ? 1 : (v > TOPO_AHEAD ? TOPO_AHEAD : v);
-    }();
+    // 186-190, 323-337): one pass per synchronisation.
     // (read per call: a test runs both forms in one process)
     const char *fused_env = std::getenv("SMVS_CUT_FUSED");
     bool const fused_passes = !(fused_env != nullptr && fused_env[0] == '0');
-    if (fused_passes && ahead == 1) {
+    if (fused_passes) {
         // three launches per pass (topo_border_candidates_kernel); the pass's
         // counters alternate between the word pairs 0 and 1, each cleared by the
         // last kernel of the pass before
@@ -2012,7 +1912,6 @@ smvs_topology_cut_boundaries(smvs_ctx *ctx, const float *inv_calibration9,
             TopoArgs P = A;
             P.deleted = words + 2 * slot;
             P.mse_count = words + 2 * slot + 1;
-            P.pass_gate = nullptr;
             hipLaunchKernelGGL(topo_border_candidates_kernel, dim3(cover), dim3(256), 0,
                 ctx->stream, P);
             int const mrc = launch_patch_mse_listed(ctx, P);
@@ -2038,36 +1937,27 @@ smvs_topology_cut_boundaries(smvs_ctx *ctx, const float *inv_calibration9,
         // (the counters of a pass are cleared by its first kernel; the word pairs
         // are then no longer what the three-launch form expects to find)
         ctx->topo_slots_clean = false;
-        for (int k = 0; k < ahead; ++k) {
-            TopoArgs P = A;
-            P.deleted = ctx->status + I_TOPO_PASS0 + 2 * k;
-            P.mse_count = ctx->status + I_TOPO_PASS0 + 2 * k + 1;
-            P.pass_gate = k == 0 ? nullptr : ctx->status + I_TOPO_PASS0 + 2 * (k - 1);
-            hipLaunchKernelGGL(topo_border_nodes_kernel,
-                dim3((unsigned)((ctx->num_nodes + 255) / 256)), dim3(256), 0,
-                ctx->stream, P);
-            int const mrc = launch_patch_mse(ctx, P, true);
-            if (mrc != SMVS_OK)
-                return mrc;
-            hipLaunchKernelGGL(topo_cut_patches_kernel,
-                dim3((unsigned)((ctx->num_patches + 255) / 256)), dim3(256), 0,
-                ctx->stream, P);
-            hipLaunchKernelGGL(topo_cut_nodes_kernel,
-                dim3((unsigned)((ctx->num_nodes + 255) / 256)), dim3(256), 0,
-                ctx->stream, P);
-        }
+        TopoArgs P = A;
+        P.deleted = ctx->status + I_TOPO_PASS0;
+        P.mse_count = ctx->status + I_TOPO_PASS0 + 1;
+        hipLaunchKernelGGL(topo_border_nodes_kernel,
+            dim3((unsigned)((ctx->num_nodes + 255) / 256)), dim3(256), 0, ctx->stream, P);
+        int const mrc = launch_patch_mse(ctx, P, true);
+        if (mrc != SMVS_OK)
+            return mrc;
+        hipLaunchKernelGGL(topo_cut_patches_kernel,
+            dim3((unsigned)((ctx->num_patches + 255) / 256)), dim3(256), 0, ctx->stream, P);
+        hipLaunchKernelGGL(topo_cut_nodes_kernel,
+            dim3((unsigned)((ctx->num_nodes + 255) / 256)), dim3(256), 0, ctx->stream, P);
         SMVS_HIP_CHECK(hipGetLastError());
         SMVS_HIP_CHECK(hipMemcpyAsync(ctx->status_host + I_TOPO_PASS0,
-            ctx->status + I_TOPO_PASS0, 2 * TOPO_AHEAD * sizeof(int), hipMemcpyDeviceToHost,
-            ctx->stream));
+            ctx->status + I_TOPO_PASS0, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         SMVS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        for (int k = 0; k < ahead && deleted > 10; ++k) {
-            deleted = ctx->status_host[I_TOPO_PASS0 + 2 * k];
-            total += deleted;
-            if (trace)
-                std::fprintf(stderr, "[smvs topo] cut pass: %d of %d patches evaluated, %d deleted\n",
-                    ctx->status_host[I_TOPO_PASS0 + 2 * k + 1], ctx->num_patches, deleted);
-        }
+        deleted = ctx->status_host[I_TOPO_PASS0];
+        total += deleted;
+        if (trace)
+            std::fprintf(stderr, "[smvs topo] cut pass: %d of %d patches evaluated, %d deleted\n",
+                ctx->status_host[I_TOPO_PASS0 + 1], ctx->num_patches, deleted);
     }
     if (patch_valid_out != nullptr)
         SMVS_HIP_CHECK(hipMemcpyAsync(patch_valid_out, ctx->patch_valid,
