@@ -8,6 +8,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libsmvs_hip.so")
 SOURCES = ["ctx.hip", "gn_construct.hip", "cg.hip", "cg_resident.hip", "update.hip", "sgm.hip",
            "scale.hip", "topology.hip", "mesh.hip", "simplify.hip", "pool.hip", "surface.hip"]
+# HIP-free units of the library: the host compiler builds them
+HOST_CC_SOURCES = ["tile_budget.cc"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-Wall", "-Wno-unused-function"]
 
@@ -16,8 +18,10 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + ["common.h", "mesh_shared.h", os.path.join("host", "topo_math.h"),
-                                                      os.path.join("host", "surface_math.h")]]
+    # every header and source of csrc/ and the two host/ headers the device code includes
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
+    deps += [os.path.join(CSRC, s) for s in HOST_CC_SOURCES + [os.path.join("host", "topo_math.h"),
+                                                             os.path.join("host", "surface_math.h")]]
     deps.append(os.path.join(HERE, "..", "include", "smvs_hip.h"))
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -101,9 +105,18 @@ def _build_hip(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd))
         procs.append((cmd, subprocess.Popen(cmd)))
+    cxx = os.environ.get("CXX", "g++")
+    for s in HOST_CC_SOURCES:
+        obj = os.path.join(CSRC, s.replace(".cc", ".o"))
+        objs.append(obj)
+        cmd = [cxx, "-std=c++17", "-O3", "-fPIC", "-Wall", "-pthread", "-c",
+               os.path.join(CSRC, s), "-o", obj]
+        if verbose:
+            print(" ".join(cmd))
+        procs.append((cmd, subprocess.Popen(cmd)))
     for cmd, p in procs:
         if p.wait() != 0:
-            raise RuntimeError("hipcc failed: " + " ".join(cmd))
+            raise RuntimeError("compiler failed: " + " ".join(cmd))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs \
         + ["-Wl,-rpath,/opt/rocm/lib"]
     if verbose:

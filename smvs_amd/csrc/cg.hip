@@ -45,17 +45,6 @@ quad_bcast(double v)
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-struct CgState {
-    double rr;       // z.r (r_dot_r of the reference)
-    double q0;
-    double tol;
-    double gnorm;
-    int iter;        // iteration this state belongs to
-    int done;
-    int info;
-    int pad;
-};
-
 struct CgArgs {
     const double *H9;
     const double *Pinv;
@@ -76,23 +65,20 @@ struct CgArgs {
     double fixed_tolerance;  // < 0: 0.01 * ||g||
 };
 
-// Progress words in pinned host memory (the host paces its launches on them
-// instead of synchronising): [0] = tag | k once A_k has settled the solver
-// state, [1] = tag | 1 once the solve is finished, [2] = info, [3] = the
-// iteration count.  The tag (solve id << 16) keeps late writes of an earlier
-// solve's trailing no-op launches from being mistaken for this solve's.
+// Publishes the progress words (common.h, PROGRESS_*): the solve's result once
+// it is finished, then that A_k has settled the solver state.
 __device__ __forceinline__ void
 publish_progress(CgArgs const &A, int done, int info, int iter)
 {
     if (done) {
-        __hip_atomic_store(A.progress + 2, info, __ATOMIC_RELAXED,
+        __hip_atomic_store(A.progress + PROGRESS_INFO, info, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.progress + 3, iter, __ATOMIC_RELAXED,
+        __hip_atomic_store(A.progress + PROGRESS_ITERS, iter, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.progress + 1, A.solve_tag | 1, __ATOMIC_RELEASE,
+        __hip_atomic_store(A.progress + PROGRESS_DONE, progress_done_word(A.solve_tag), __ATOMIC_RELEASE,
             __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    __hip_atomic_store(A.progress + 0, A.solve_tag | A.k, __ATOMIC_RELEASE,
+    __hip_atomic_store(A.progress + PROGRESS_SEEN, A.solve_tag | A.k, __ATOMIC_RELEASE,
         __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -780,10 +766,10 @@ cg_solve_launch(smvs_ctx *ctx, int max_iterations, double error_tolerance,
     auto const t_start = std::chrono::steady_clock::now();
     long spins = 0;
     for (;;) {
-        int const done_word = __atomic_load_n(&progress[1], __ATOMIC_ACQUIRE);
-        if (done_word == (A.solve_tag | 1))
+        int const done_word = __atomic_load_n(&progress[PROGRESS_DONE], __ATOMIC_ACQUIRE);
+        if (done_word == progress_done_word(A.solve_tag))
             break;
-        int const seen_word = __atomic_load_n(&progress[0], __ATOMIC_ACQUIRE);
+        int const seen_word = __atomic_load_n(&progress[PROGRESS_SEEN], __ATOMIC_ACQUIRE);
         int const seen = (seen_word & ~0xFFFF) == A.solve_tag
             ? (seen_word & 0xFFFF) : 0;
         if (k <= max_iterations && k <= seen + AHEAD) {
@@ -804,8 +790,8 @@ cg_solve_launch(smvs_ctx *ctx, int max_iterations, double error_tolerance,
         if (k > max_iterations && seen >= max_iterations) {
             // A_max settles the state as done (the done word is published
             // before the progress word); reaching this means it did not
-            if (__atomic_load_n(&progress[1], __ATOMIC_ACQUIRE)
-                == (A.solve_tag | 1))
+            if (__atomic_load_n(&progress[PROGRESS_DONE], __ATOMIC_ACQUIRE)
+                == progress_done_word(A.solve_tag))
                 break;
             set_error("cg_solve_launch: solver did not report completion");
             return SMVS_ERR_STATE;
@@ -818,9 +804,9 @@ cg_solve_launch(smvs_ctx *ctx, int max_iterations, double error_tolerance,
             if (q != hipSuccess && q != hipErrorNotReady)
                 SMVS_HIP_CHECK(q);
             if (q == hipSuccess
-                && __atomic_load_n(&progress[1], __ATOMIC_ACQUIRE)
-                    != (A.solve_tag | 1)
-                && __atomic_load_n(&progress[0], __ATOMIC_ACQUIRE)
+                && __atomic_load_n(&progress[PROGRESS_DONE], __ATOMIC_ACQUIRE)
+                    != progress_done_word(A.solve_tag)
+                && __atomic_load_n(&progress[PROGRESS_SEEN], __ATOMIC_ACQUIRE)
                     == seen_word) {
                 // the stream is idle, nothing is in flight and the solver
                 // has not finished: the launches above were lost
@@ -837,8 +823,8 @@ cg_solve_launch(smvs_ctx *ctx, int max_iterations, double error_tolerance,
         }
     }
     SMVS_HIP_CHECK(hipGetLastError());
-    int const iters = progress[3];
-    int const solve_info = progress[2];
+    int const iters = progress[PROGRESS_ITERS];
+    int const solve_info = progress[PROGRESS_INFO];
     ctx->last_cg_iterations = iters;
     if (num_iterations != nullptr)
         *num_iterations = iters;

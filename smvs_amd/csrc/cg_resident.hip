@@ -40,67 +40,20 @@
 // barrier kernel holds CUs, fewer CUs than tiles) the barrier times out, the
 // solve reports failure and the caller falls back to the streaming kernels.
 #include "common.h"
-
-#include <fcntl.h>
-#include <sys/file.h>
-#include <unistd.h>
+#include "cg_resident_plan.h"
+#include "cg_exchange.h"
 
 #include <algorithm>
-#include <atomic>
-#include <cerrno>
 #include <chrono>
 #include <cmath>
-#include <mutex>
 #include <string>
-#include <thread>
 
 namespace smvs_hip {
 
-constexpr int RES_THREADS = 512;
-constexpr int RES_WAVES = RES_THREADS / 64;
-constexpr int RES_MAX_BLOCKS = 256;
-
 typedef double double4_r __attribute__((ext_vector_type(4)));
 
-struct ResState {           // mirrors CgState of cg.hip
-    double rr, q0, tol, gnorm;
-    int iter, done, info, pad;
-};
-
-// Exchange area (zeroed before every launch).  A double travels as two
-// 8-byte granules {tag = epoch, 32 data bits}: the data is its own flag
-// (cdna_hip_programming.md Guideline 16, form R2), so one sweep over the
-// granules of all workgroups is barrier and all-reduce at once.
-constexpr int RES_KINDS = 8;                 // doubles per all-reduce, at most
-constexpr int RES_GROUP = 16;                                  // workgroups per first-level group
-constexpr int RES_MAX_GROUPS = RES_MAX_BLOCKS / RES_GROUP;
-constexpr int RES_REPLICAS = 16;                               // copies of the group sums
-struct ResExchange {
-    // flat all-reduce (two-exchange solver): every workgroup sweeps all of these
-    unsigned long long gran[2][2 * RES_KINDS][RES_MAX_BLOCKS];   // [parity][..][wg]
-    // tree all-reduce (one-exchange solver): a double is the pair {lo, hi} of
-    // adjacent granules; the first workgroup of a group of RES_GROUP sums its
-    // group's partial sums into lvl2, every workgroup sums the groups
-    unsigned long long lvl1[2][RES_MAX_BLOCKS][RES_KINDS][2];    // [parity][wg][kind]
-    // (RES_REPLICAS copies of the group sums, 2 KB apart: all 256 workgroups
-    // polling the same sixteen cache lines made those lines' memory channel the
-    // clock of the second hop -- a poll round there took as long as the channel
-    // needed for 4,096 line reads, and a group's store queued behind them)
-    unsigned long long lvl2[2][RES_REPLICAS][RES_MAX_GROUPS][RES_KINDS][2];   // [parity][copy][group][kind]
-    unsigned timeout;
-    // compacted solve: solve tag | 1 (the tile has an active node) or | 2 (it has
-    // none: its workgroup has left), written once per solve by every workgroup
-    unsigned live[RES_MAX_BLOCKS];
-};
-
-// Who takes part in an exchange (the compacted solve, see the kernel): the
-// first LIVE workgroup of a group sums the group, members and groups without an
-// active node are not waited for -- their sums are exactly +0.0, so leaving
-// them out of the tree changes no bit of any total.
-struct LiveSet {
-    bool leads;         // this workgroup sums its group (wave-uniform)
-    unsigned bits;      // lane (kind, j): bit 0 member j of its group is live, bit 1 group j is
-};
+constexpr int RES_PIPELINED = 1;      // launch-ahead Newton loop (update.hip)
+constexpr int RES_TEST_GIVE_UP = 2;   // report a failure (test hook)
 
 struct ResArgs {
     const double *H9;        // [5][N][16]
@@ -111,9 +64,9 @@ struct ResArgs {
                              // granules; one-exchange solver: [2][N][4][2] q of the rim
                              // nodes as tagged pairs, double-buffered by iteration parity
     ResExchange *ex;
-    ResState *state;         // [2] (state[0] is written at the end)
+    CgState *state;          // [2] (state[0] is written at the end)
     int *status;
-    int *progress;           // pinned host words, see cg.hip
+    int *progress;           // pinned host words (common.h, PROGRESS_*)
     int solve_tag;
     int num_nodes, stride, rows;
     int tw, th, tiles_x, num_tiles;
@@ -121,8 +74,7 @@ struct ResArgs {
     double q_tolerance, fixed_tolerance;
     long long *trace;        // debug: 100 MHz wall-clock stamps (or nullptr)
     int trace_wg;            // ... of this workgroup's iterations (SMVS_CG_TRACE_WG)
-    int pipelined;           // bit 0: launch-ahead Newton loop (update.hip), bit 1:
-                             // report a failure (test hook)
+    int pipelined;           // RES_PIPELINED | RES_TEST_GIVE_UP
     // fused assembly (the Newton loop): per-patch systems instead of H / g / P
     const double *Hp;        // the packed per-patch systems, 36 quads per patch ...
     const double *gp;        // ... and gradients, 4 quads per patch, laid out as
@@ -140,320 +92,11 @@ struct ResArgs {
     int compact;             // leave out what has no active node (SMVS_CG_COMPACT, default 1)
 };
 
-// GaussNewtonStep::construct's scatter (gauss_newton_step.cc:88-142) in gather
-// form for ONE node, as gn_assemble_kernel does it with four lanes: the <= 4
-// incident patches in ascending patch id, local node order 0 (ix, iy),
-// 1 (ix+1, iy), 2 (ix, iy+1), 3 (ix+1, iy+1); only stored slots (other node
-// >= this node), blocks towards inactive nodes omitted (Q6).
-struct NodeSystem {
-    double hd[10];      // diagonal block, upper triangle (Q4)
-    double hu[4][16];   // slots 5..8
-    double g[4];
-};
+} // namespace smvs_hip
 
-// `count` consecutive quads of patch p's record from element `e0` (a multiple
-// of 4) on, or -- unconditionally, so that the loads of a thread stay
-// independent of its flags -- the same number of loads from the block of zeros.
-struct QuadSource {
-    const double4_r *base;
-    unsigned step;
-    __device__ __forceinline__ double4_r operator[](int i) const { return base[(size_t)i * step]; }
-};
-__device__ __forceinline__ QuadSource
-patch_quads(ResArgs const &A, int p, int e0, bool use)
-{
-    const double4_r *Hq = reinterpret_cast<const double4_r *>(A.Hp);
-    QuadSource q;
-    q.base = use ? Hq + ((size_t)(e0 >> 2) * A.layout.hq + (size_t)p * A.layout.hp)
-        : reinterpret_cast<const double4_r *>(A.zeros);
-    q.step = use ? A.layout.hq : 0u;
-    return q;
-}
-__device__ __forceinline__ double4_r
-patch_gradient(ResArgs const &A, int p, int ln, bool use)
-{
-    const double4_r *gq = reinterpret_cast<const double4_r *>(A.gp);
-    return *(use ? gq + ((size_t)ln * A.layout.gq + (size_t)p * A.layout.gp)
-        : reinterpret_cast<const double4_r *>(A.zeros));
-}
+#include "cg_resident_assemble.h"
 
-// The loads below are unconditional: a block that does not contribute (patch
-// outside the grid / invalid, other node inactive) is read from a block of
-// zeros instead, so that all flag loads, then all block loads, are
-// independent and in flight together -- with a branch per block every one of
-// them cost a full memory latency, ~25 in a row at 2 waves per SIMD.  Adding
-// +0.0 in place of an omitted term leaves every sum bit-identical (the sums
-// start at +0.0 and can never be -0.0).
-__device__ __forceinline__ void
-assemble_node(ResArgs const &A, int ix, int iy, bool on, NodeSystem &S)
-{
-#pragma unroll
-    for (int i = 0; i < 10; ++i)
-        S.hd[i] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            S.hu[k][i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        S.g[i] = 0.0;
-    if (!on)
-        return;
-    int const n = iy * A.stride + ix;
-    int const rows = A.npy + 1;
-    // flags of the 3 x 3 nodes around (ix, iy) and of the four incident patches
-    bool act[3][3], pv[4];
-#pragma unroll
-    for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) {
-            int const jx = ix + dx, jy = iy + dy;
-            bool const inside = jx >= 0 && jx < A.stride && jy >= 0 && jy < rows;
-            uint8_t const f = A.active[inside ? jy * A.stride + jx : n];
-            act[dy + 1][dx + 1] = inside && f != 0;
-        }
-    int pidx[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        int const pxq = ix - (1 - (q & 1));
-        int const pyq = iy - (1 - (q >> 1));
-        bool const inside = pxq >= 0 && pxq < A.npx && pyq >= 0 && pyq < A.npy;
-        pidx[q] = inside ? pyq * A.npx + pxq : 0;
-        uint8_t const f = A.patch_valid[pidx[q]];
-        pv[q] = inside && f != 0;
-    }
-    if (!act[1][1])
-        return;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        int const ln = 3 - q;   // local index of the node in that patch
-#pragma unroll
-        for (int lm = 0; lm < 4; ++lm) {
-            if (lm < ln)
-                continue;
-            // the other node, relative to this one
-            int const dx = (lm & 1) - (ln & 1), dy = (lm >> 1) - (ln >> 1);
-            bool const use = pv[q] && act[dy + 1][dx + 1];
-            if (lm == ln) {
-                QuadSource const tri = patch_quads(A, pidx[q], patch_diag_offset(ln), use);
-                double4_r const b0 = tri[0], b1 = tri[1], b2 = tri[2];
-                S.hd[0] += b0.x; S.hd[1] += b0.y; S.hd[2] += b0.z; S.hd[3] += b0.w;
-                S.hd[4] += b1.x; S.hd[5] += b1.y; S.hd[6] += b1.z;
-                S.hd[7] += b1.w; S.hd[8] += b2.x;
-                S.hd[9] += b2.y;
-            } else {
-                QuadSource const blk = patch_quads(A, pidx[q], patch_upper_offset(ln, lm), use);
-                double4_r const b0 = blk[0], b1 = blk[1], b2 = blk[2], b3 = blk[3];
-                int const k = (dy + 1) * 3 + dx + 1 - 5;
-                S.hu[k][0] += b0.x; S.hu[k][1] += b0.y; S.hu[k][2] += b0.z; S.hu[k][3] += b0.w;
-                S.hu[k][4] += b1.x; S.hu[k][5] += b1.y; S.hu[k][6] += b1.z; S.hu[k][7] += b1.w;
-                S.hu[k][8] += b2.x; S.hu[k][9] += b2.y; S.hu[k][10] += b2.z; S.hu[k][11] += b2.w;
-                S.hu[k][12] += b3.x; S.hu[k][13] += b3.y; S.hu[k][14] += b3.z; S.hu[k][15] += b3.w;
-            }
-        }
-        double4_r const gv = patch_gradient(A, pidx[q], ln, pv[q]);
-        S.g[0] += gv.x; S.g[1] += gv.y; S.g[2] += gv.z; S.g[3] += gv.w;
-    }
-}
-
-// The diagonal block (upper triangle) and the gradient of node (ix, iy) alone,
-// with assemble_node's sums in assemble_node's order: what the one-exchange
-// solver needs of a HALO node to form that node's z = P r itself.
-__device__ __forceinline__ void
-assemble_diagonal(ResArgs const &A, int ix, int iy, double (&hd)[10], double (&g)[4])
-{
-#pragma unroll
-    for (int i = 0; i < 10; ++i)
-        hd[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        g[i] = 0.0;
-    int const n = iy * A.stride + ix;
-    uint8_t const fself = A.active[n];
-    int pidx[4];
-    bool pv[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        int const pxq = ix - (1 - (q & 1));
-        int const pyq = iy - (1 - (q >> 1));
-        bool const inside = pxq >= 0 && pxq < A.npx && pyq >= 0 && pyq < A.npy;
-        pidx[q] = inside ? pyq * A.npx + pxq : 0;
-        uint8_t const f = A.patch_valid[pidx[q]];
-        pv[q] = inside && f != 0;
-    }
-    if (fself == 0)
-        return;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        int const ln = 3 - q;   // local index of the node in that patch
-        QuadSource const tri = patch_quads(A, pidx[q], patch_diag_offset(ln), pv[q]);
-        double4_r const b0 = tri[0], b1 = tri[1], b2 = tri[2];
-        hd[0] += b0.x; hd[1] += b0.y; hd[2] += b0.z; hd[3] += b0.w;
-        hd[4] += b1.x; hd[5] += b1.y; hd[6] += b1.z;
-        hd[7] += b1.w; hd[8] += b2.x;
-        hd[9] += b2.y;
-        double4_r const gv = patch_gradient(A, pidx[q], ln, pv[q]);
-        g[0] += gv.x; g[1] += gv.y; g[2] += gv.z; g[3] += gv.w;
-    }
-}
-
-// The four upper blocks (slots 5..8) of node (ix, iy) alone, with
-// assemble_node's sums in assemble_node's order.
-__device__ __forceinline__ void
-assemble_upper(ResArgs const &A, int ix, int iy, bool on, double (&hu)[4][16])
-{
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            hu[k][i] = 0.0;
-    if (!on)
-        return;
-    int const n = iy * A.stride + ix;
-    int const rows = A.npy + 1;
-    bool act[2][3], pv[4];   // nodes (dx, dy) with dy in {0, 1}: the upper slots' ends
-#pragma unroll
-    for (int dy = 0; dy <= 1; ++dy)
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) {
-            int const jx = ix + dx, jy = iy + dy;
-            bool const inside = jx >= 0 && jx < A.stride && jy >= 0 && jy < rows;
-            uint8_t const f = A.active[inside ? jy * A.stride + jx : n];
-            act[dy][dx + 1] = inside && f != 0;
-        }
-    int pidx[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        int const pxq = ix - (1 - (q & 1));
-        int const pyq = iy - (1 - (q >> 1));
-        bool const inside = pxq >= 0 && pxq < A.npx && pyq >= 0 && pyq < A.npy;
-        pidx[q] = inside ? pyq * A.npx + pxq : 0;
-        uint8_t const f = A.patch_valid[pidx[q]];
-        pv[q] = inside && f != 0;
-    }
-    if (!act[0][1])
-        return;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        int const ln = 3 - q;   // local index of the node in that patch
-#pragma unroll
-        for (int lm = 0; lm < 4; ++lm) {
-            if (lm <= ln)
-                continue;
-            int const dx = (lm & 1) - (ln & 1), dy = (lm >> 1) - (ln >> 1);
-            bool const use = pv[q] && act[dy][dx + 1];
-            QuadSource const blk = patch_quads(A, pidx[q], patch_upper_offset(ln, lm), use);
-            double4_r const b0 = blk[0], b1 = blk[1], b2 = blk[2], b3 = blk[3];
-            int const k = (dy + 1) * 3 + dx + 1 - 5;
-            hu[k][0] += b0.x; hu[k][1] += b0.y; hu[k][2] += b0.z; hu[k][3] += b0.w;
-            hu[k][4] += b1.x; hu[k][5] += b1.y; hu[k][6] += b1.z; hu[k][7] += b1.w;
-            hu[k][8] += b2.x; hu[k][9] += b2.y; hu[k][10] += b2.z; hu[k][11] += b2.w;
-            hu[k][12] += b3.x; hu[k][13] += b3.y; hu[k][14] += b3.z; hu[k][15] += b3.w;
-        }
-    }
-}
-
-// One stored block of another node: row node (mx, my), its upper slot 5..8
-// (a compile-time constant at every call: the loops fold to the <= 2 patches
-// that hold both nodes).
-__device__ __forceinline__ void
-assemble_block(ResArgs const &A, int mx, int my, int slot, double *out16)
-{
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-        out16[i] = 0.0;
-    int const mrow = my * A.stride + mx;
-    bool const act_row = A.active[mrow] != 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        int const ln = 3 - q;
-#pragma unroll
-        for (int lm = 0; lm < 4; ++lm) {
-            if (lm <= ln)
-                continue;
-            int const dx = (lm & 1) - (ln & 1), dy = (lm >> 1) - (ln >> 1);
-            if ((dy + 1) * 3 + dx + 1 != slot)
-                continue;
-            int const pxq = mx - (1 - (q & 1));
-            int const pyq = my - (1 - (q >> 1));
-            bool const inside = pxq >= 0 && pxq < A.npx && pyq >= 0 && pyq < A.npy;
-            int const p = inside ? pyq * A.npx + pxq : 0;
-            int const m = inside
-                ? pyq * A.stride + pxq + (lm & 1) + (lm >> 1) * A.stride : mrow;
-            uint8_t const fp = A.patch_valid[p];
-            uint8_t const fm = A.active[m];
-            bool const use = act_row && inside && fp != 0 && fm != 0;
-            QuadSource const blk = patch_quads(A, p, patch_upper_offset(ln, lm), use);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                double4_r const v = blk[i];
-                out16[4 * i + 0] += v.x; out16[4 * i + 1] += v.y;
-                out16[4 * i + 2] += v.z; out16[4 * i + 3] += v.w;
-            }
-        }
-    }
-}
-
-// A rim block for the tile's LDS: the stored block of row node (mx, my)
-// towards its neighbour of LOWER slot s seen from the tile node (i.e. the row
-// node's upper slot 8 - s), s chosen at run time so that one thread per rim
-// block can do the work.  The <= 2 patches holding both nodes, in ascending
-// patch id as in assemble_block:
-//   s = 0 (slot 8): q 3 (ln 0, lm 3)
-//   s = 1 (slot 7): q 2 (ln 1, lm 3), q 3 (ln 0, lm 2)
-//   s = 2 (slot 6): q 2 (ln 1, lm 2)
-//   s = 3 (slot 5): q 1 (ln 2, lm 3), q 3 (ln 0, lm 1)
-// Flags in one batch, the two blocks in one batch (a missing contribution is
-// read from the block of zeros).
-__device__ __forceinline__ void
-assemble_rim_block(ResArgs const &A, int mx, int my, int s, double *dst16)
-{
-    int const q[2] = { s == 0 ? 3 : (s == 3 ? 1 : 2), 3 };
-    int const ln[2] = { s == 0 ? 0 : (s == 3 ? 2 : 1), 0 };
-    int const lm[2] = { s == 2 ? 2 : 3, s == 1 ? 2 : 1 };
-    bool const two = s == 1 || s == 3;
-    int const mrow = my * A.stride + mx;
-    uint8_t const frow = A.active[mrow];
-    QuadSource src[2];
-    uint8_t fp[2], fm[2];
-    bool inside[2];
-    int p[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        int const pxq = mx - (1 - (q[e] & 1));
-        int const pyq = my - (1 - (q[e] >> 1));
-        inside[e] = (e == 0 || two) && pxq >= 0 && pxq < A.npx && pyq >= 0
-            && pyq < A.npy;
-        p[e] = inside[e] ? pyq * A.npx + pxq : 0;
-        int const m = inside[e]
-            ? pyq * A.stride + pxq + (lm[e] & 1) + (lm[e] >> 1) * A.stride : mrow;
-        fp[e] = A.patch_valid[p[e]];
-        fm[e] = A.active[m];
-    }
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        bool const use = frow != 0 && inside[e] && fp[e] != 0 && fm[e] != 0;
-        // (ln, lm depend on s at run time here: the offset is computed, not folded)
-        src[e] = patch_quads(A, p[e], patch_upper_offset(ln[e], lm[e]), use);
-    }
-    double4_r v0[4], v1[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v0[i] = src[0][i];
-        v1[i] = src[1][i];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        // (0 + first) + second, as assemble_block
-        double4_r r;
-        r.x = (0.0 + v0[i].x) + v1[i].x;
-        r.y = (0.0 + v0[i].y) + v1[i].y;
-        r.z = (0.0 + v0[i].z) + v1[i].z;
-        r.w = (0.0 + v0[i].w) + v1[i].w;
-        reinterpret_cast<double4_r *>(dst16)[i] = r;
-    }
-}
+namespace smvs_hip {
 
 constexpr int TRACE_ITERS = 12, TRACE_POINTS = 12;
 // after the iteration rows: four prologue stamps of every workgroup
@@ -467,618 +110,36 @@ constexpr int TRACE_SKEW_ITER = 5;
 constexpr int TRACE_WAVE_BASE = TRACE_SKEW_BASE + 4 * RES_MAX_BLOCKS;
 constexpr int TRACE_TOTAL = TRACE_WAVE_BASE + 8 * 8;
 
-__device__ __forceinline__ void
-st_agent(double *p, double v)
+// What tools/cg_trace.py reads: the stamps of one solve, appended to `path`.
+static void
+dump_trace(const char *path, const long long *tr, int num_nodes, int num_tiles,
+    int iterations, int exchanges)
 {
-    __hip_atomic_store(reinterpret_cast<unsigned long long *>(p),
-        (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
-        __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() is also a
-// release fence at workgroup scope: s_waitcnt vmcnt(0) in front of the
-// s_barrier, so every wave that had published rim values sat at the next
-// barrier until the fabric had acknowledged its write-through stores -- 2 to
-// 2.8 us in EVERY iteration of the one-exchange solver (cg_trace.py, "sweep
-// wave starts"; profiles/r4_cg_barrier.txt).  Nothing in this kernel passes
-// data between the threads of a workgroup through global memory: what
-// crosses workgroups carries its own tag, everything else is LDS.
-__device__ __forceinline__ void
-lds_barrier(void)
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// A double that crosses workgroups travels as two 8-byte granules {tag, 32
-// data bits} (Guideline 16, form R2): the reader polls until both tags carry
-// the value it expects, no release / drain on the writer's side.
-__device__ __forceinline__ void
-st_granules(unsigned long long *g, unsigned tag, double v)
-{
-    unsigned long long const bits = (unsigned long long)__double_as_longlong(v);
-    __hip_atomic_store(g, ((unsigned long long)tag << 32) | (bits & 0xFFFFFFFFull),
-        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(g + 1, ((unsigned long long)tag << 32) | (bits >> 32),
-        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ double
-ld_agent(const double *p)
-{
-    unsigned long long const v = __hip_atomic_load(
-        reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED,
-        __HIP_MEMORY_SCOPE_AGENT);
-    return __longlong_as_double((long long)v);
-}
-
-// Cross-lane sums without the LDS pipe.  __shfl_xor of a double is two
-// ds_bpermute_b32, and the CU has ONE LDS unit for its eight waves: the eight
-// butterflies of an exchange (8 kinds x 6 steps x 2 words x 8 waves = 768
-// bpermutes) kept it busy for ~2.5 us per iteration -- the largest single item
-// of an iteration, found with the per-wave stamps of tools/cg_trace.py
-// (profiles/r4_cg_waves.txt).  gfx950 has what is needed on the VALU:
-// v_permlane32_swap / v_permlane16_swap exchange halves / rows between two
-// registers, DPP row rotations cover the 16 lanes of a row.
-typedef unsigned int uint2_r __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ double
-join_words(unsigned lo, unsigned hi)
-{
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// HALF = 32: on return the lower 32 lanes hold x[l] + x[l + 32], the upper 32
-// lanes y[l - 32] + y[l] -- one step of a reduce-scatter over two kinds (with
-// y = x: a butterfly step).  HALF = 16: the same between the even and the odd
-// rows of 16 lanes.  Every pair is summed as (lower lane) + (upper lane).
-template <int HALF>
-__device__ __forceinline__ double
-swap_add(double x, double y)
-{
-    unsigned long long const xb = (unsigned long long)__double_as_longlong(x);
-    unsigned long long const yb = (unsigned long long)__double_as_longlong(y);
-    uint2_r lo, hi;
-    if constexpr (HALF == 32) {
-        lo = __builtin_amdgcn_permlane32_swap((unsigned)xb, (unsigned)yb, false, false);
-        hi = __builtin_amdgcn_permlane32_swap((unsigned)(xb >> 32), (unsigned)(yb >> 32),
-            false, false);
-    } else {
-        lo = __builtin_amdgcn_permlane16_swap((unsigned)xb, (unsigned)yb, false, false);
-        hi = __builtin_amdgcn_permlane16_swap((unsigned)(xb >> 32), (unsigned)(yb >> 32),
-            false, false);
+    FILE *f = std::fopen(path, "a");
+    if (f == nullptr)
+        return;
+    std::fprintf(f, "solve nodes=%d tiles=%d its=%d exchanges=%d\n",
+        num_nodes, num_tiles, iterations, exchanges);
+    for (int k = 0; k <= TRACE_ITERS; ++k) {
+        for (int q = 0; q < TRACE_POINTS; ++q)
+            std::fprintf(f, "%lld ", tr[(size_t)k * TRACE_POINTS + q]);
+        std::fprintf(f, "\n");
     }
-    // .x: [x of the lower half | y of the lower half], .y: [x of the upper half |
-    // y of the upper half]
-    return join_words(lo.x, hi.x) + join_words(lo.y, hi.y);
-}
-
-template <int ROR>
-__device__ __forceinline__ double
-row_rotated(double v)
-{
-    unsigned long long const b = (unsigned long long)__double_as_longlong(v);
-    int const lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)b, 0x120 + ROR, 0xf, 0xf,
-        false);
-    int const hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), 0x120 + ROR, 0xf,
-        0xf, false);
-    return join_words((unsigned)lo, (unsigned)hi);
-}
-
-// Sum over the 16 lanes of a row, every lane gets it (bit-identical in all of
-// them: after the rotation by 8 the values have period 8, so the two lanes of
-// every later pair add the same two numbers).
-__device__ __forceinline__ double
-row_sum(double v)
-{
-    v += row_rotated<8>(v);
-    v += row_rotated<4>(v);
-    v += row_rotated<2>(v);
-    v += row_rotated<1>(v);
-    return v;
-}
-
-// First half of a workgroup sum of K per-thread values: the per-wave sums go
-// to red[K][RES_WAVES]; after the barrier inside, the sum of kind k is
-// red[k][0] + ... + red[k][RES_WAVES - 1] in that order (block_total).  The
-// wave sums are a reduce-scatter: across the halves of the wave a lane keeps
-// half of its kinds, across the rows of a half a quarter; what is left (two
-// kinds of eight) is summed over the row.  Fixed order, the same in every wave
-// and workgroup.
-template <int K>
-__device__ __forceinline__ void
-wave_partials(double const (&v)[K], double *red /*[K][RES_WAVES]*/)
-{
-    constexpr int P = K <= 1 ? 1 : K <= 2 ? 2 : K <= 4 ? 4 : 8;   // kinds, padded
-    static_assert(K <= 8, "block_partials: at most eight kinds");
-    int const lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double a[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-        a[i] = i < K ? v[i] : 0.0;
-    // halves of the wave
-    constexpr int N1 = P > 1 ? P / 2 : 1;
-#pragma unroll
-    for (int i = 0; i < N1; ++i)
-        a[i] = swap_add<32>(a[i], P > 1 ? a[i + N1] : a[i]);
-    // rows of a half
-    constexpr int N2 = N1 > 1 ? N1 / 2 : 1;
-#pragma unroll
-    for (int i = 0; i < N2; ++i)
-        a[i] = swap_add<16>(a[i], N1 > 1 ? a[i + N2] : a[i]);
-#pragma unroll
-    for (int i = 0; i < N2; ++i)
-        a[i] = row_sum(a[i]);
-    // which kinds this lane's row holds: bit 5 of the lane chose among the
-    // halves of a[0 .. P), bit 4 among the halves of what was left
-    int const b5 = lane >> 5, b4 = (lane >> 4) & 1;
-    int const first = (P > 1 ? b5 * N1 : 0) + (N1 > 1 ? b4 * N2 : 0);
-    if ((lane & 15) == 0 && (P > 1 || b5 == 0) && (N1 > 1 || b4 == 0)) {
-#pragma unroll
-        for (int i = 0; i < N2; ++i)
-            if (first + i < K)
-                red[(first + i) * RES_WAVES + wave] = a[i];
+    for (int b = 0; b < num_tiles; ++b)
+        std::fprintf(f, "block %d %lld %lld %lld %lld\n", b,
+            tr[TRACE_BLOCK_BASE + 4 * b], tr[TRACE_BLOCK_BASE + 4 * b + 1],
+            tr[TRACE_BLOCK_BASE + 4 * b + 2], tr[TRACE_BLOCK_BASE + 4 * b + 3]);
+    for (int w = 0; w < 8; ++w) {
+        std::fprintf(f, "wave %d", w);
+        for (int q = 0; q < 8; ++q)
+            std::fprintf(f, " %lld", tr[TRACE_WAVE_BASE + 8 * w + q]);
+        std::fprintf(f, "\n");
     }
-}
-
-template <int K>
-__device__ __forceinline__ void
-block_partials(double const (&v)[K], double *red /*[K][RES_WAVES]*/)
-{
-    wave_partials<K>(v, red);
-    lds_barrier();
-    // (no second barrier: the partials are next written by the following
-    // block_partials, and every thread passes the caller's barrier behind the
-    // sweep first)
-}
-
-// The same without the workgroup barrier: every wave raises its own tag behind
-// its partial sums (LDS serves a wave's requests in order), and only the waves
-// that need the workgroup's sums wait for the eight tags -- the others go on
-// to their stores and polls.  The slots are safe to reuse: whoever reads them
-// does so before the barrier at the end of the exchange, and they are written
-// again only behind it.
-struct PartialTags {
-    volatile unsigned *tag;     // [RES_WAVES]
-    __device__ __forceinline__ void raise(unsigned t) const
-    {
-        if ((threadIdx.x & 63) == 0) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            tag[threadIdx.x >> 6] = t;
-        }
-    }
-    // wave-uniform; false after a bounded wait
-    __device__ __forceinline__ bool wait(unsigned t) const
-    {
-        for (unsigned spins = 0; !__all(tag[threadIdx.x & (RES_WAVES - 1)] == t); ++spins) {
-            if (spins > (1u << 22))
-                return false;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        return true;
-    }
-};
-
-__device__ __forceinline__ double
-block_total(const double *red, int k)
-{
-    double s = 0.0;
-#pragma unroll
-    for (int wv = 0; wv < RES_WAVES; ++wv)
-        s += red[k * RES_WAVES + wv];
-    return s;
-}
-
-struct NoIdleWork {
-    __device__ __forceinline__ void operator()() const {}
-};
-
-// All-reduce of K doubles over the workgroups of the grid, and the grid-wide
-// synchronisation point of the phase: every workgroup publishes its K sums as
-// tagged granules; K waves of every workgroup (kind k each, waves FIRST ..
-// FIRST + K - 1) sweep the granules of all workgroups until every tag carries
-// this epoch, then all sum them in the same fixed order.  The slots are
-// double-buffered by epoch parity: a workgroup can publish epoch e + 2 only
-// after everybody published e + 1, i.e. after everybody finished reading e.
-// The waves that do not sweep run `idle` meanwhile (the halo of the
-// one-exchange solver).  Returns false after a bounded wait (a workgroup is
-// not resident / gave up).
-template <int K, int FIRST, typename Idle>
-__device__ __forceinline__ bool
-grid_allreduce(ResExchange *ex, unsigned solve_tag, unsigned epoch, int nblocks,
-    double (&v)[K], double *red, int *lds_flag, Idle idle)
-{
-    static_assert(K <= RES_KINDS && FIRST + K <= RES_WAVES, "sweeping waves");
-    // tags carry the solve id: granules of earlier solves never match, so the
-    // exchange area needs no clearing between solves
-    unsigned const tag = solve_tag | epoch;
-    double *res = red + RES_KINDS * RES_WAVES;   // [K] results, behind the partial sums
-    block_partials<K>(v, red);
-    if (nblocks == 1) {
-        // a grid of one tile (the coarse scales, the tiny systems of the fuzz
-        // sweep): nothing to exchange -- the workgroup's sums are the totals,
-        // no granule leaves the CU (6 us per iteration on a loaded chip)
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            v[k] = block_total(red, k);
-        lds_barrier();   // (the partial sums are free for the next reduction)
-        return true;
-    }
-    // (nothing to drain: everything that crosses workgroups is a granule, the
-    // vectors of the solve live in registers and LDS)
-    unsigned const par = epoch & 1u;
-    if (threadIdx.x < 2 * K) {
-        // (only the publishing threads need the workgroup's sums)
-        int const k = threadIdx.x >> 1, half = threadIdx.x & 1;
-        unsigned long long const bits = (unsigned long long)__double_as_longlong(
-            block_total(red, k));
-        unsigned const word = half ? (unsigned)(bits >> 32) : (unsigned)bits;
-        __hip_atomic_store(&ex->gran[par][threadIdx.x][blockIdx.x],
-            ((unsigned long long)tag << 32) | word, __ATOMIC_RELAXED,
-            __HIP_MEMORY_SCOPE_AGENT);
-    }
-    int const wave = (int)(threadIdx.x >> 6) - FIRST;
-    if (wave >= 0 && wave < K) {
-        int const lane = threadIdx.x & 63;
-        constexpr int PER_LANE = RES_MAX_BLOCKS / 64;
-        unsigned lo[PER_LANE], hi[PER_LANE];
-        bool ok = true;
-        for (unsigned spins = 0;; ++spins) {
-            bool all = true;
-#pragma unroll
-            for (int j = 0; j < PER_LANE; ++j) {
-                int const blk = lane + 64 * j;
-                unsigned long long g0 = (unsigned long long)tag << 32, g1 = g0;
-                if (blk < nblocks) {
-                    g0 = __hip_atomic_load(&ex->gran[par][2 * wave][blk],
-                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    g1 = __hip_atomic_load(&ex->gran[par][2 * wave + 1][blk],
-                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                lo[j] = (unsigned)g0;
-                hi[j] = (unsigned)g1;
-                all &= (unsigned)(g0 >> 32) == tag && (unsigned)(g1 >> 32) == tag;
-            }
-            if (__all(all))
-                break;
-            if (spins > (1u << 18)
-                || ((spins & 255u) == 255u
-                    && __hip_atomic_load(&ex->timeout, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                __hip_atomic_store(&ex->timeout, 1u, __ATOMIC_RELAXED,
-                    __HIP_MEMORY_SCOPE_AGENT);
-                ok = false;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        // fixed order: workgroups lane, lane + 64, ... per lane, then the tree
-        double sum = 0.0;
-#pragma unroll
-        for (int j = 0; j < PER_LANE; ++j) {
-            unsigned long long const bits = ((unsigned long long)hi[j] << 32) | lo[j];
-            sum += (lane + 64 * j) < nblocks
-                ? __longlong_as_double((long long)bits) : 0.0;
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-            sum += __shfl_xor(sum, off);
-        if (lane == 0) {
-            res[wave] = sum;
-            // (a halo wait that gave up raises the same flag)
-            if (wave == 0 && __hip_atomic_load(&ex->timeout, __ATOMIC_RELAXED,
-                    __HIP_MEMORY_SCOPE_AGENT) != 0u)
-                ok = false;
-            lds_flag[wave] = ok ? 1 : 0;
-        }
-    } else {
-        idle();
-    }
-    lds_barrier();
-    // The results live apart from the partial sums, so two workgroup barriers
-    // per all-reduce are enough (one inside block_partials, this one): results and
-    // flags are next written behind the next all-reduce's first barrier, which
-    // every thread reaches only after it has read these.
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        v[k] = res[k];
-        ok = ok && lds_flag[k] != 0;
-    }
-    return ok;
-}
-
-// A double as ONE 16-byte write-through store / ONE 16-byte L1-bypassing load
-// of its two adjacent granules {data lo, tag}, {data hi, tag}.  Both halves
-// carry the tag, so nothing depends on the 16 bytes arriving together; what
-// the wide access buys is half the number of fabric transactions of the
-// exchange (an 8-byte sc1 store is one fabric write per lane:
-// MI355X_MICROARCH.md, "stores of each flavour").
-typedef unsigned int uint4_r __attribute__((ext_vector_type(4)));
-constexpr int AUX_SC1 = 16;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t
-pair_buffer(void *base, size_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void
-st_pair16(__amdgpu_buffer_rsrc_t buf, unsigned byte_offset, unsigned tag, double v)
-{
-    unsigned long long const bits = (unsigned long long)__double_as_longlong(v);
-    uint4_r const w = { (unsigned)bits, tag, (unsigned)(bits >> 32), tag };
-    __builtin_amdgcn_raw_buffer_store_b128(w, buf, (int)byte_offset, 0, AUX_SC1);
-}
-
-__device__ __forceinline__ bool
-ld_pair16(__amdgpu_buffer_rsrc_t buf, unsigned byte_offset, unsigned tag, double *v)
-{
-    uint4_r const w = __builtin_amdgcn_raw_buffer_load_b128(buf, (int)byte_offset, 0,
-        AUX_SC1);
-    *v = __longlong_as_double((long long)(((unsigned long long)w.z << 32) | w.x));
-    return w.y == tag && w.w == tag;
-}
-
-// The four doubles of one node's exchanged vector (64 bytes): four 16-byte
-// loads per poll until all carry `want`; false after a bounded wait.
-__device__ __forceinline__ void
-nap(int units)
-{
-    for (int i = 0; i < units; ++i)
-        __builtin_amdgcn_s_sleep(8);
-}
-
-__device__ __forceinline__ bool
-poll_node_pairs(__amdgpu_buffer_rsrc_t buf, unsigned byte_offset, unsigned want,
-    ResExchange *ex, double (&out)[4], int gap = 0)
-{
-    for (unsigned spins = 0;; ++spins) {
-        bool ok = true;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            ok &= ld_pair16(buf, byte_offset + (unsigned)q * 16u, want, &out[q]);
-        if (ok)
-            return true;
-        if (spins > (1u << 18)
-            || ((spins & 255u) == 255u
-                && __hip_atomic_load(&ex->timeout, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            __hip_atomic_store(&ex->timeout, 1u, __ATOMIC_RELAXED,
-                __HIP_MEMORY_SCOPE_AGENT);
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        nap(gap);
-        asm volatile("" ::: "memory");   // (the loads are re-issued every round)
-    }
-}
-
-// One double as a pair of adjacent tagged granules: every lane of the wave
-// polls its own pair (one 16-byte load) until all lanes see their tag
-// (inactive lanes take no part and get 0).  Wave-uniform result: false after a
-// bounded wait.
-__device__ __forceinline__ bool
-poll_pairs(__amdgpu_buffer_rsrc_t buf, unsigned byte_offset, bool active, unsigned tag,
-    ResExchange *ex, double *value, int gap = 0, unsigned *rounds = nullptr)
-{
-    double got = 0.0;
-    bool mine_ok = !active;
-    bool good = true;
-    for (unsigned spins = 0;; ++spins) {
-        if (!mine_ok)
-            mine_ok = ld_pair16(buf, byte_offset, tag, &got);
-        if (__all(mine_ok))
-            break;
-        if (rounds != nullptr)
-            *rounds += 1;
-        if (spins > (1u << 18)
-            || ((spins & 255u) == 255u
-                && __hip_atomic_load(&ex->timeout, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            __hip_atomic_store(&ex->timeout, 1u, __ATOMIC_RELAXED,
-                __HIP_MEMORY_SCOPE_AGENT);
-            good = false;
-            break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        nap(gap);
-        asm volatile("" ::: "memory");
-    }
-    *value = active ? got : 0.0;
-    if (rounds != nullptr)
-        *rounds += 1;
-    return good;
-}
-
-// Sum over the 16 / 32 lanes of an aligned segment, fixed order, every lane gets it.
-__device__ __forceinline__ double
-segment16_sum(double v)
-{
-    return row_sum(v);
-}
-
-__device__ __forceinline__ double
-segment32_sum(double v)
-{
-    return row_sum(swap_add<16>(v, v));
-}
-
-// Who publishes the sums of an exchange.  On gfx9 loads and stores share ONE
-// counter (vmcnt): a wave that has issued a write-through store cannot see the
-// result of a later load before the fabric has acknowledged that store.  The
-// sweeping waves live on their polls, so the workgroup's sums -- and, in a
-// group's first workgroup, the group's sums, which the sweeping waves hand
-// over through LDS -- are stored by the last wave, which never waits for a
-// load.  (The rim's q is published by the owners of the nodes: one wave
-// issuing all ~380 write-through stores of a tile was measured and is far
-// slower, the issue rate of such stores is what counts there.)
-// (the wave of the middle rows of a tile: the fewest rim nodes, so the fewest
-// write-through stores of its own in front of the sums)
-constexpr int RES_SUM_WAVE = 5;
-
-// LDS mailbox between the sweeping waves and the publishing wave of a group's
-// first workgroup: value first, then the tag (LDS serves a wave's requests in
-// order), read in the opposite order.
-struct GroupMailbox {
-    volatile double *value;     // [RES_KINDS]
-    volatile unsigned *tag;     // [RES_KINDS]
-    __device__ __forceinline__ void put(int kind, unsigned t, double v) const
-    {
-        value[kind] = v;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        tag[kind] = t;
-    }
-    // (one lane per kind) false after a bounded wait
-    __device__ __forceinline__ bool take(int kind, unsigned t, double *v) const
-    {
-        for (unsigned spins = 0; tag[kind] != t; ++spins) {
-            if (spins > (1u << 22))
-                return false;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        *v = value[kind];
-        return true;
-    }
-};
-
-__device__ __forceinline__ GroupMailbox
-group_mailbox(double *red)
-{
-    double *base = red + RES_KINDS * RES_WAVES + RES_KINDS + (RES_KINDS + 1) / 2;
-    return { base, reinterpret_cast<volatile unsigned *>(base + RES_KINDS) };
-}
-
-__device__ __forceinline__ PartialTags
-partial_tags(double *red)
-{
-    double *base = red + RES_KINDS * RES_WAVES + RES_KINDS + (RES_KINDS + 1) / 2
-        + RES_KINDS + (RES_KINDS + 1) / 2;
-    return { reinterpret_cast<volatile unsigned *>(base) };
-}
-
-// All-reduce of K doubles over the workgroups in two levels.  The flat sweep
-// above makes every workgroup read every workgroup's K sums: 256 x 256 x K
-// granule pairs per exchange, all aimed at the same few KB -- measured, its
-// time grows with K (4.4 us for one sum, 6.2 for three, 12 for seven).  Here
-// the first workgroup of every group of RES_GROUP sums its group (16 x K
-// pairs), publishes the group's sums, and every workgroup sums the <= 16
-// groups: 2 x 16 x K pairs per workgroup and exchange instead of 256 x K, two
-// hops instead of one.  Lane (kind, j) of the sweeping waves 1 .. (K + 3) / 4
-// handles member / group j of one kind; the other waves run `others(wave)`.
-// Same guarantees as the flat form: fixed summation order (a tree over the
-// members of a group, then a tree over the groups), bit-identical results in
-// every workgroup, slots double-buffered by epoch parity, bounded waits.
-template <int K, typename Others, typename Mark>
-__device__ __forceinline__ bool
-grid_allreduce_tree(ResExchange *ex, unsigned solve_tag, unsigned epoch, int nblocks,
-    LiveSet const live, double (&v)[K], double *red, int *lds_flag, Others others, Mark mark,
-    int wait_member = 6, int wait_poll = 0)
-{
-    constexpr int SWEEPERS = (K + 3) / 4;
-    static_assert(K <= RES_KINDS && 1 + SWEEPERS <= RES_SUM_WAVE, "sweeping waves");
-    unsigned const tag = solve_tag | epoch;
-    double *res = red + RES_KINDS * RES_WAVES;
-    GroupMailbox const box = group_mailbox(red);
-    PartialTags const partials = partial_tags(red);
-    wave_partials<K>(v, red);
-    partials.raise(tag);
-    mark(20, -1);
-    unsigned const par = epoch & 1u;
-    int const b = (int)blockIdx.x;
-    __amdgpu_buffer_rsrc_t const xbuf = pair_buffer(ex, sizeof(ResExchange));
-    auto lvl1_at = [&](int wg, int kind) {
-        return (unsigned)(offsetof(ResExchange, lvl1)
-            + ((((size_t)par * RES_MAX_BLOCKS + (size_t)wg) * RES_KINDS + (size_t)kind) * 16));
-    };
-    auto lvl2_at = [&](int copy, int group, int kind) {
-        return (unsigned)(offsetof(ResExchange, lvl2)
-            + (((((size_t)par * RES_REPLICAS + (size_t)copy) * RES_MAX_GROUPS + (size_t)group)
-                   * RES_KINDS + (size_t)kind) * 16));
-    };
-    int const ngroups = (nblocks + RES_GROUP - 1) / RES_GROUP;
-    bool const leads = live.leads;
-    bool const member_live = (live.bits & 1u) != 0u, group_live = (live.bits & 2u) != 0u;
-    int const wave = (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (wave == RES_SUM_WAVE) {
-        bool handed = partials.wait(tag);
-        mark(21, -1);
-        if (nblocks > 1 && lane < K)
-            st_pair16(xbuf, lvl1_at(b, lane), tag, block_total(red, lane));
-        if (leads) {
-            // lane (copy, kind): eight copies per store instruction
-            static_assert(K == 8, "eight kinds per copy");
-            double part = 0.0;
-            handed = box.take(lane & 7, tag, &part) && handed;
-#pragma unroll
-            for (int c = lane >> 3; c < RES_REPLICAS; c += 8)
-                st_pair16(xbuf, lvl2_at(c, b / RES_GROUP, lane & 7), tag, part);
-        }
-        if (!__all(handed) && lane == 0)
-            __hip_atomic_store(&ex->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        others(wave);
-    } else if (wave >= 1 && wave <= SWEEPERS) {
-        int const kind = 4 * (wave - 1) + (lane >> 4), j = lane & 15;
-        bool const kind_ok = kind < K;
-        bool ok = true, ok2 = true;
-        double total;
-        unsigned rounds1 = 0, rounds2 = 0;
-        mark(8, -1);
-        if (nblocks == 1) {
-            // a grid of one tile (the coarse scales): nothing to exchange
-            ok = partials.wait(tag);
-            total = kind_ok ? block_total(red, kind) : 0.0;
-        } else if (ngroups == 1) {
-            // a single group: every workgroup sums its <= 16 members itself,
-            // one hop instead of two
-            ok = poll_pairs(xbuf, lvl1_at(j < nblocks ? j : 0, kind_ok ? kind : 0),
-                kind_ok && j < nblocks && member_live, tag, ex, &total, wait_poll);
-            total = segment16_sum(total);
-        } else {
-            if (leads) {
-                // this workgroup sums its group
-                int const member = b - b % RES_GROUP + j;
-                double part;
-                ok = poll_pairs(xbuf, lvl1_at(member < nblocks ? member : b,
-                        kind_ok ? kind : 0), kind_ok && member < nblocks && member_live, tag,
-                    ex, &part, wait_poll, &rounds1);
-                part = segment16_sum(part);
-                mark(5, -1);
-                if (kind_ok && j == 0)
-                    box.put(kind, tag, part);
-            } else {
-                // the group sums cannot be there yet (they are a hop behind)
-                nap(wait_member);
-            }
-            mark(9, -1);
-            ok2 = poll_pairs(xbuf, lvl2_at(b % RES_REPLICAS, j < ngroups ? j : 0,
-                    kind_ok ? kind : 0),
-                kind_ok && j < ngroups && group_live, tag, ex, &total, wait_poll, &rounds2);
-            total = segment16_sum(total);
-        }
-        mark(6, -1);
-        mark(10, (long long)(rounds1 * 1000u + rounds2));
-        if (kind_ok && j == 0)
-            res[kind] = total;
-        if (lane == 0) {
-            bool flag_ok = ok && ok2;
-            // (a wait of another wave that gave up raises the same flag)
-            if (wave == 1 && __hip_atomic_load(&ex->timeout, __ATOMIC_RELAXED,
-                    __HIP_MEMORY_SCOPE_AGENT) != 0u)
-                flag_ok = false;
-            lds_flag[wave - 1] = flag_ok ? 1 : 0;
-        }
-    } else {
-        others(wave);
-    }
-    lds_barrier();
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        v[k] = res[k];
-#pragma unroll
-    for (int w = 0; w < SWEEPERS; ++w)
-        ok = ok && lds_flag[w] != 0;
-    return ok;
+    for (int b = 0; b < num_tiles; ++b)
+        std::fprintf(f, "skew %d %lld %lld %lld %lld\n", b,
+            tr[TRACE_SKEW_BASE + 4 * b], tr[TRACE_SKEW_BASE + 4 * b + 1],
+            tr[TRACE_SKEW_BASE + 4 * b + 2], tr[TRACE_SKEW_BASE + 4 * b + 3]);
+    std::fclose(f);
 }
 
 // Position of a thread in its tile and the addressing that follows from it.
@@ -1809,7 +870,7 @@ cg_resident_kernel(ResArgs A)
     bool alive = true;
     int reporter = 0;       // the workgroup that writes the result (compacted: the first live one)
     bool report_all = false;
-    ResState st;
+    CgState st;
     if constexpr (!ONE) {
         // zero the direction tile (out-of-grid halo stays zero for the whole solve)
         for (int i = tid; i < LH * LW * 4; i += RES_THREADS)
@@ -2224,7 +1285,7 @@ cg_resident_kernel(ResArgs A)
         // (a halo wait of any workgroup that gave up raised the exchange's flag)
         bool const late_timeout = __hip_atomic_load(&A.ex->timeout, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_AGENT) != 0u;
-        int const failed = alive && !late_timeout && !(A.pipelined & 2) ? 0 : 1;   // (bit 1: test hook)
+        int const failed = alive && !late_timeout && !(A.pipelined & RES_TEST_GIVE_UP) ? 0 : 1;
         if (!st.done && !failed) {
             // max_iterations <= 1 never reaches here (handled by the host)
             st.done = 1;
@@ -2235,80 +1296,24 @@ cg_resident_kernel(ResArgs A)
         A.status[I_ITER] = st.iter;
         if (failed && A.pipelined)
             A.status[I_STEP_ABORT] = ABORT_SOLVER;   // the enqueued steps do nothing
-        __hip_atomic_store(A.progress + 2, st.info, __ATOMIC_RELAXED,
+        __hip_atomic_store(A.progress + PROGRESS_INFO, st.info, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.progress + 3, st.iter, __ATOMIC_RELAXED,
+        __hip_atomic_store(A.progress + PROGRESS_ITERS, st.iter, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.progress + 4, failed, __ATOMIC_RELAXED,
+        __hip_atomic_store(A.progress + PROGRESS_GAVE_UP, failed, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.progress + 1, A.solve_tag | 1, __ATOMIC_RELEASE,
+        __hip_atomic_store(A.progress + PROGRESS_DONE, progress_done_word(A.solve_tag), __ATOMIC_RELEASE,
             __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
-static size_t
+size_t
 resident_lds_bytes(int tw, int th, bool one)
 {
     return resident_lds_layout(tw, th, one).total * sizeof(double);
 }
 
-// Tile shape: tw * th <= 512 nodes, at most max_tiles tiles, fits the LDS of
-// the solver variant, smallest rim.
-static bool
-choose_tiling(int stride, int rows, int max_tiles, bool one, int *tw_out, int *th_out)
-{
-    long best = -1;
-    for (int tw = 4; tw <= 128 && tw <= RES_THREADS; ++tw) {
-        int const th = RES_THREADS / tw;
-        if (th < 2)
-            continue;
-        for (int t2 = th; t2 >= 2 && t2 >= th - 8; --t2) {
-            long const tiles = (long)((stride + tw - 1) / tw)
-                * ((rows + t2 - 1) / t2);
-            if (tiles > max_tiles)
-                continue;
-            // (long thin tiles have a long rim: the one-exchange solver keeps
-            // r, P and q of the halo in LDS)
-            if (resident_lds_bytes(tw, t2, one) > (size_t)160 * 1024)
-                continue;
-            // prefer few idle threads, then a short rim
-            long const waste = tiles * (long)(tw * t2) - (long)stride * rows;
-            long const score = waste * 4 + tiles * (tw + t2);
-            if (best < 0 || score < best) {
-                best = score;
-                *tw_out = tw;
-                *th_out = t2;
-            }
-        }
-    }
-    return best >= 0;
-}
-
-// Which of the two resident solvers a context runs (smvs_ctx_set_solver), and
-// on which tiles.  The one-exchange recurrence exists to save a grid-wide
-// exchange per iteration; on a grid of ONE tile nothing is exchanged, so AUTO
-// runs the reference's operation order there (conjugate_gradient.h:121-198:
-// d.Ad, then r.r, z.r, x.(b + r) of the updated vectors summed directly) --
-// the tiny ill-conditioned systems of the fuzz sweep live on such grids.
-// SMVS_REF_ORDER_TILES=n widens that to grids of <= n tiles (measurements).
-struct ResidentPlan {
-    int tw, th;
-    bool one;
-    int blocks;     // workgroups of the launch = tiles, row-major
-};
-
-static void
-finish_plan(const smvs_ctx *ctx, int max_tiles, ResidentPlan *plan)
-{
-    int const stride = ctx->node_stride, rows = ctx->num_nodes / stride;
-    int const tiles_x = (stride + plan->tw - 1) / plan->tw;
-    int const tiles_y = (rows + plan->th - 1) / plan->th;
-    plan->blocks = tiles_x * tiles_y;
-}
-
-static bool
-compute_resident_plan(const smvs_ctx *ctx, ResidentPlan *plan);
-
+// The plan (cg_resident_plan.h) of the context's grid.
 // (once per grid: a Newton step asks for the plan, a loop three more times)
 static bool
 resident_plan(const smvs_ctx *ctx, ResidentPlan *plan)
@@ -2316,8 +1321,15 @@ resident_plan(const smvs_ctx *ctx, ResidentPlan *plan)
     smvs_ctx::ResidentPlanMemo &m = ctx->res_plan;
     if (m.stride != ctx->node_stride || m.nodes != ctx->num_nodes
         || m.solver_mode != (int)ctx->solver_mode || m.cus != ctx->resident_cus) {
+        static int const ref_order_tiles = [] {
+            const char *e = std::getenv("SMVS_REF_ORDER_TILES");
+            int const n = e != nullptr ? std::atoi(e) : 1;
+            return n < 0 ? 0 : n;
+        }();
         ResidentPlan p = {};
-        m.ok = compute_resident_plan(ctx, &p);
+        m.ok = compute_resident_plan(ctx->node_stride, ctx->num_nodes / ctx->node_stride,
+            std::min(ctx->resident_cus, RES_MAX_BLOCKS), ctx->solver_mode,
+            ref_order_tiles, &p);
         m.stride = ctx->node_stride;
         m.nodes = ctx->num_nodes;
         m.solver_mode = (int)ctx->solver_mode;
@@ -2328,39 +1340,17 @@ resident_plan(const smvs_ctx *ctx, ResidentPlan *plan)
     return m.ok;
 }
 
-static bool
-compute_resident_plan(const smvs_ctx *ctx, ResidentPlan *plan)
+// the context's device has that many CUs (0: HIP error)
+static int
+resident_cus(smvs_ctx *ctx)
 {
-    int const stride = ctx->node_stride;
-    int const rows = ctx->num_nodes / stride;
-    int const max_tiles = ctx->resident_cus < RES_MAX_BLOCKS
-        ? ctx->resident_cus : RES_MAX_BLOCKS;
-    static int const ref_order_tiles = [] {
-        const char *e = std::getenv("SMVS_REF_ORDER_TILES");
-        int const n = e != nullptr ? std::atoi(e) : 1;
-        return n < 0 ? 0 : n;
-    }();
-    int tw = 0, th = 0;
-    bool const have_ref = choose_tiling(stride, rows, max_tiles, false, &tw, &th);
-    if (have_ref) {
-        long const tiles = (long)((stride + tw - 1) / tw) * ((rows + th - 1) / th);
-        if (ctx->solver_mode == SMVS_SOLVER_RESIDENT_REF || tiles <= ref_order_tiles) {
-            plan->tw = tw;
-            plan->th = th;
-            plan->one = false;
-            finish_plan(ctx, max_tiles, plan);
-            return true;
-        }
-    } else if (ctx->solver_mode == SMVS_SOLVER_RESIDENT_REF) {
-        return false;
+    if (ctx->resident_cus == 0) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, physical_device(ctx->device)) != hipSuccess)
+            return 0;
+        ctx->resident_cus = prop.multiProcessorCount;
     }
-    if (!choose_tiling(stride, rows, max_tiles, true, &tw, &th))
-        return false;
-    plan->tw = tw;
-    plan->th = th;
-    plan->one = true;
-    finish_plan(ctx, max_tiles, plan);
-    return true;
+    return ctx->resident_cus;
 }
 
 // Does the resident solver take this system?  (grid fits the chip's CUs and
@@ -2381,12 +1371,8 @@ cg_resident_applies(smvs_ctx *ctx, int max_iterations)
     }();
     if (env_off)
         return false;
-    if (ctx->resident_cus == 0) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, physical_device(ctx->device)) != hipSuccess)
-            return false;
-        ctx->resident_cus = prop.multiProcessorCount;
-    }
+    if (resident_cus(ctx) == 0)
+        return false;
     ResidentPlan plan;
     if (!resident_plan(ctx, &plan))
         return false;
@@ -2397,167 +1383,34 @@ cg_resident_applies(smvs_ctx *ctx, int max_iterations)
 
 static DeviceTileBudget g_resident_budget[16];
 
-void
-DeviceTileBudget::bind(int device)
-{
-    // (caller holds the mutex)
-    if (bound)
-        return;
-    bound = true;
-    hipDeviceProp_t prop;
-    capacity = RES_MAX_BLOCKS;
-    // (`device` is the PHYSICAL device here: logical devices mapped onto one
-    // GPU share its CUs, cg_resident_budget)
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess
-        && prop.multiProcessorCount < capacity)
-        capacity = prop.multiProcessorCount;
-    // the same GPU may have different indices in different processes
-    // (HIP_VISIBLE_DEVICES): name the file after the PCI bus id
-    char bus[64] = "";
-    if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus), device) != hipSuccess)
-        std::snprintf(bus, sizeof(bus), "index%d", device);
-    for (char *c = bus; *c != 0; ++c)
-        if (*c == ':' || *c == '/')
-            *c = '_';
-    // SMVS_LOCK_DIR, else the user's runtime directory, else /tmp.  The file
-    // is never followed through a symlink; when another user created it
-    // (O_RDWR refused) a read-only descriptor serves flock() just as well.
-    const char *dir = std::getenv("SMVS_LOCK_DIR");
-    if (dir == nullptr || dir[0] == 0)
-        dir = std::getenv("XDG_RUNTIME_DIR");
-    if (dir == nullptr || dir[0] == 0)
-        dir = "/tmp";
-    std::string const path = std::string(dir) + "/smvs_hip_barrier_" + bus + ".lock";
-    fd = ::open(path.c_str(), O_CREAT | O_RDWR | O_CLOEXEC | O_NOFOLLOW, 0666);
-    if (fd < 0)
-        fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC | O_NOFOLLOW);
-    if (fd < 0)
-        std::fprintf(stderr, "[smvs_hip] no lock file %s (%s): the resident solver is "
-            "serialised inside this process only; a second process on the same GPU may "
-            "push it into the streaming kernels\n", path.c_str(), std::strerror(errno));
-}
-
-// The advisory file lock that makes PROCESSES sharing a GPU take turns with
-// their barrier kernels.  Taken by the head of this process's line WITHOUT the
-// budget's mutex held (it may sleep for as long as another process's loops
-// run); kept while loops of this process follow each other, but for at most
-// FILE_HOLD at a stretch: after that the next acquirer lets the loops in flight
-// drain, returns the lock -- a process waiting on it gets its turn -- and takes
-// it again (a drain every 100 ms costs the single process ~1 %).  A lock somebody holds for 20 s is not one of ours (or is stuck):
-// go on without it for a while -- the worst case is a resident solve that times
-// out into the streaming kernels, not a hang.
-static constexpr auto FILE_HOLD = std::chrono::milliseconds(100);
-static constexpr auto FILE_GIVE_UP = std::chrono::seconds(20);
-static constexpr auto FILE_RETRY_AFTER = std::chrono::seconds(60);
-
-bool
-DeviceTileBudget::take_file_lock(void)
-{
-    // (no mutex held: the caller is the only thread of this process in here)
-    auto const t0 = std::chrono::steady_clock::now();
-    for (long spin = 0;; ++spin) {
-        if (::flock(fd, LOCK_EX | LOCK_NB) == 0)
-            return true;
-        if (errno != EWOULDBLOCK && errno != EINTR)
-            return false;
-        if (std::chrono::steady_clock::now() - t0 > FILE_GIVE_UP) {
-            static std::atomic<bool> warned{false};
-            if (!warned.exchange(true))
-                std::fprintf(stderr, "[smvs_hip] barrier lock file busy for 20 s: "
-                    "continuing without it\n");
-            return false;
-        }
-        if (spin < 64)
-            std::this_thread::yield();
-        else
-            std::this_thread::sleep_for(std::chrono::microseconds(50));
-    }
-}
-
-void
-DeviceTileBudget::unlock_file(void)
-{
-    if (fd >= 0 && file_locked)
-        (void)::flock(fd, LOCK_UN);
-    file_locked = false;
-}
-
-void
-DeviceTileBudget::acquire(int device, int tiles)
-{
-    std::unique_lock<std::mutex> guard(mutex);
-    bind(device);
-    if (tiles > capacity)
-        tiles = capacity;
-    unsigned long long const ticket = next_ticket++;
-    // in arrival order; the head of the line waits for its tiles, the others
-    // wait for the head
-    turn.wait(guard, [&] { return serving == ticket && used + tiles <= capacity; });
-    auto const now = std::chrono::steady_clock::now();
-    bool handed_back = false;
-    if (fd >= 0 && now >= no_file_until) {
-        if (file_locked && now - file_since > FILE_HOLD) {
-            // this process has had the GPU's barrier kernels to itself long
-            // enough: let its loops in flight end (nobody passes the head of the
-            // line meanwhile) and hand the lock back before taking it again
-            turn.wait(guard, [&] { return holders == 0; });
-            unlock_file();
-            handed_back = true;
-        }
-        if (!file_locked) {
-            guard.unlock();
-            // (flock is not FIFO and a waiting process polls every 50 us: taking
-            // the lock again at once would win it back nearly every time, and
-            // the waiter would starve into its 20 s give-up.  Four of its poll
-            // periods are its turn.)
-            if (handed_back)
-                std::this_thread::sleep_for(std::chrono::microseconds(200));
-            bool const got = take_file_lock();
-            guard.lock();
-            file_locked = got;
-            file_since = std::chrono::steady_clock::now();
-            if (!got)
-                no_file_until = file_since + FILE_RETRY_AFTER;
-        }
-    }
-    used += tiles;
-    serving += 1;
-    holders += 1;
-    guard.unlock();
-    turn.notify_all();   // (the next in line may fit beside this one)
-}
-
-void
-DeviceTileBudget::release(int tiles)
-{
-    {
-        std::lock_guard<std::mutex> guard(mutex);
-        if (tiles > capacity)
-            tiles = capacity;
-        used -= tiles;
-        if (--holders == 0)
-            unlock_file();      // (non-blocking)
-    }
-    turn.notify_all();
-}
-
+// The tile budget (tile_budget.h) of the GPU behind a logical device: logical
+// devices mapped onto one GPU share its CUs.
 DeviceTileBudget &
 cg_resident_budget(int device)
 {
-    return g_resident_budget[physical_device(device) & 15];
+    int const physical = physical_device(device);
+    DeviceTileBudget &budget = g_resident_budget[physical & 15];
+    if (!budget.is_bound()) {
+        hipDeviceProp_t prop;
+        int capacity = RES_MAX_BLOCKS;
+        if (hipGetDeviceProperties(&prop, physical) == hipSuccess
+            && prop.multiProcessorCount < capacity)
+            capacity = prop.multiProcessorCount;
+        // the same GPU may have different indices in different processes
+        // (HIP_VISIBLE_DEVICES): name the file after the PCI bus id
+        char bus[64] = "";
+        if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus), physical) != hipSuccess)
+            std::snprintf(bus, sizeof(bus), "index%d", physical);
+        budget.bind(capacity, bus);
+    }
+    return budget;
 }
 
 int
 cg_resident_tiles(smvs_ctx *ctx)
 {
     ResidentPlan plan;
-    if (ctx->resident_cus == 0) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, physical_device(ctx->device)) != hipSuccess)
-            return 0;
-        ctx->resident_cus = prop.multiProcessorCount;
-    }
-    if (!resident_plan(ctx, &plan))
+    if (resident_cus(ctx) == 0 || !resident_plan(ctx, &plan))
         return 0;
     return plan.blocks;
 }
@@ -2625,7 +1478,7 @@ resident_enqueue(smvs_ctx *ctx, int max_iterations, double error_tolerance,
     A.b = ctx->b;
     A.zg = reinterpret_cast<unsigned long long *>(ctx->res_zx);
     A.ex = reinterpret_cast<ResExchange *>(ctx->res_work);
-    A.state = reinterpret_cast<ResState *>(ctx->cg_state);
+    A.state = reinterpret_cast<CgState *>(ctx->cg_state);
     A.status = ctx->status;
     A.progress = ctx->cg_progress;
     ctx->cg_solve_id = (ctx->cg_solve_id + 1) & 0x7FFF;
@@ -2694,7 +1547,7 @@ resident_enqueue(smvs_ctx *ctx, int max_iterations, double error_tolerance,
         }();
         A.trace_wg = wg;
     }
-    A.pipelined = pipelined ? (test_give_up ? 3 : 1) : 0;
+    A.pipelined = pipelined ? RES_PIPELINED | (test_give_up ? RES_TEST_GIVE_UP : 0) : 0;
     *solve_tag_out = A.solve_tag;
     *num_tiles_out = num_tiles;
     {
@@ -2758,7 +1611,7 @@ cg_resident_solve(smvs_ctx *ctx, int max_iterations, double error_tolerance,
         SMVS_HIP_CHECK(hipMemsetAsync(trace_dev, 0, trace_n * sizeof(long long),
             ctx->stream));
     }
-    ScopedTileBudget guard(ctx->device, cg_resident_tiles(ctx));
+    ScopedTileBudget guard(cg_resident_budget(ctx->device), cg_resident_tiles(ctx));
     int solve_tag = 0, num_tiles = 0;
     int const rc = resident_enqueue(ctx, max_iterations, error_tolerance,
         q_tolerance, fused, false, trace_dev, &solve_tag, &num_tiles);
@@ -2768,15 +1621,16 @@ cg_resident_solve(smvs_ctx *ctx, int max_iterations, double error_tolerance,
     volatile int *progress = ctx->cg_progress;
     auto const t_start = std::chrono::steady_clock::now();
     long spins = 0;
-    while (__atomic_load_n(&progress[1], __ATOMIC_ACQUIRE) != (solve_tag | 1)) {
+    while (__atomic_load_n(&progress[PROGRESS_DONE], __ATOMIC_ACQUIRE)
+        != progress_done_word(solve_tag)) {
         __builtin_ia32_pause();
         if ((++spins & 0xFFFF) == 0) {
             hipError_t const q = hipStreamQuery(ctx->stream);
             if (q != hipSuccess && q != hipErrorNotReady)
                 SMVS_HIP_CHECK(q);
             if (q == hipSuccess
-                && __atomic_load_n(&progress[1], __ATOMIC_ACQUIRE)
-                    != (solve_tag | 1)) {
+                && __atomic_load_n(&progress[PROGRESS_DONE], __ATOMIC_ACQUIRE)
+                    != progress_done_word(solve_tag)) {
                 set_error("cg_resident_solve: kernel ended without a result");
                 return SMVS_ERR_STATE;
             }
@@ -2793,41 +1647,19 @@ cg_resident_solve(smvs_ctx *ctx, int max_iterations, double error_tolerance,
         SMVS_HIP_CHECK(hipMemcpy(tr.data(), trace_dev, trace_n * sizeof(long long),
             hipMemcpyDeviceToHost));
         (void)hipFree(trace_dev);
-        if (FILE *f = std::fopen(trace_path, "a")) {
-            std::fprintf(f, "solve nodes=%d tiles=%d its=%d exchanges=%d\n",
-                ctx->num_nodes, num_tiles, progress[3],
-                [&] { ResidentPlan p; return resident_plan(ctx, &p) && p.one; }() ? 1 : 2);
-            for (int k = 0; k <= TRACE_ITERS; ++k) {
-                for (int q = 0; q < TRACE_POINTS; ++q)
-                    std::fprintf(f, "%lld ", tr[(size_t)k * TRACE_POINTS + q]);
-                std::fprintf(f, "\n");
-            }
-            for (int b = 0; b < num_tiles; ++b)
-                std::fprintf(f, "block %d %lld %lld %lld %lld\n", b,
-                    tr[TRACE_BLOCK_BASE + 4 * b], tr[TRACE_BLOCK_BASE + 4 * b + 1],
-                    tr[TRACE_BLOCK_BASE + 4 * b + 2], tr[TRACE_BLOCK_BASE + 4 * b + 3]);
-            for (int w = 0; w < 8; ++w) {
-                std::fprintf(f, "wave %d", w);
-                for (int q = 0; q < 8; ++q)
-                    std::fprintf(f, " %lld", tr[TRACE_WAVE_BASE + 8 * w + q]);
-                std::fprintf(f, "\n");
-            }
-            for (int b = 0; b < num_tiles; ++b)
-                std::fprintf(f, "skew %d %lld %lld %lld %lld\n", b,
-                    tr[TRACE_SKEW_BASE + 4 * b], tr[TRACE_SKEW_BASE + 4 * b + 1],
-                    tr[TRACE_SKEW_BASE + 4 * b + 2], tr[TRACE_SKEW_BASE + 4 * b + 3]);
-            std::fclose(f);
-        }
+        ResidentPlan plan;
+        dump_trace(trace_path, tr.data(), ctx->num_nodes, num_tiles,
+            progress[PROGRESS_ITERS], resident_plan(ctx, &plan) && plan.one ? 1 : 2);
     }
     // (every workgroup has passed its last barrier when the result appears:
     // the kernel is draining and cannot block a barrier kernel started now)
-    if (progress[4] != 0)
+    if (progress[PROGRESS_GAVE_UP] != 0)
         return cg_resident_gave_up(ctx);
-    ctx->last_cg_iterations = progress[3];
+    ctx->last_cg_iterations = progress[PROGRESS_ITERS];
     if (num_iterations != nullptr)
-        *num_iterations = progress[3];
+        *num_iterations = progress[PROGRESS_ITERS];
     if (info != nullptr)
-        *info = progress[2];
+        *info = progress[PROGRESS_INFO];
     *ran = true;
     return SMVS_OK;
 }

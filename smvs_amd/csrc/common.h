@@ -5,16 +5,14 @@
 #include "host/topo_math.h"
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdarg>
 #include <cstdint>
-#include <condition_variable>
-#include <mutex>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "../../include/smvs_hip.h"
+#include "tile_budget.h"
 
 namespace smvs_hip {
 
@@ -77,6 +75,53 @@ enum {
                          // that the passes of the three-launch form alternate between
                          // (topology.hip); the words up to I_NUM are not used
     I_NUM = 24
+};
+
+// State of a PCG solve on the device (ctx->cg_state, [2]): the streaming
+// kernels (cg.hip) double-buffer it by iteration parity, the resident solver
+// (cg_resident.hip) leaves its result in [0].
+struct CgState {
+    double rr;       // z.r (r_dot_r of the reference)
+    double q0;
+    double tol;
+    double gnorm;
+    int iter;        // iteration this state belongs to
+    int done;
+    int info;
+    int pad;
+};
+
+// Progress words of a PCG solve in pinned host memory (ctx->cg_progress): the
+// host paces its launches on them, or spins on them, instead of synchronising.
+// The tag (solve id << 16) keeps late writes of an earlier solve's trailing
+// no-op launches from being mistaken for this solve's.
+enum {
+    PROGRESS_SEEN = 0,   // tag | k once launch A_k of cg.hip has settled the solver state
+    PROGRESS_DONE,       // progress_done_word(tag) once the solve is finished; before
+                         // it, in this order:
+    PROGRESS_INFO,       // smvs_cg_info
+    PROGRESS_ITERS,      // the iteration count
+    PROGRESS_GAVE_UP     // resident solver: its workgroups were not all resident
+};
+__host__ __device__ __forceinline__ constexpr int
+progress_done_word(int solve_tag)
+{
+    return solve_tag | 1;
+}
+
+// Result words of a Newton step in its pinned slot (ctx->step_words,
+// STEP_SLOT_INTS ints), published by finish_step_kernel (update.hip).
+enum {
+    STEP_SEQ = 0,          // the sequence tag, stored last
+    STEP_NUM_ACTIVE,       // active nodes
+    STEP_NAN,              // delta[0] was NaN: nothing was updated
+    STEP_ACTIVE_PATCHES,   // active patches of the step
+    STEP_NEXT_LIVE,        // length of the next live-patch list
+    STEP_GATE,             // 0 ran / 1 skipped (the loop had ended) / 1 + ABORT_*
+                           // (the step was abandoned)
+    STEP_CG_ITERS,         // CG iterations
+    STEP_LOOP_ENDS,        // the loop ends after this step
+    STEP_SCALARS           // two doubles: sum of shifts, number of terms
 };
 
 struct SubPlanes {
@@ -152,7 +197,7 @@ struct smvs_ctx {
     double *x = nullptr, *r = nullptr, *z = nullptr, *Ad = nullptr,
         *d = nullptr, *d2 = nullptr, *b = nullptr;
     double *partials = nullptr;     // [2][8][512] per-block reduction partials of cg.hip (high, low words)
-    void *cg_state = nullptr;       // CgState[2] (cg.hip)
+    void *cg_state = nullptr;       // CgState[2]
     int last_cg_iterations = 0;     // sizes the first chunk of the next solve
     bool cg_use_active = false;     // system built by gn_construct: skip inactive nodes
     double *scalars = nullptr;      // [S_NUM]
@@ -531,53 +576,11 @@ int cg_resident_solve(smvs_ctx *ctx, int max_iterations, double error_tolerance,
     double q_tolerance, int *num_iterations, int *info, bool *ran,
     bool fused = false);
 bool cg_resident_applies(smvs_ctx *ctx, int max_iterations);
-// Barrier kernels (the resident PCG: every workgroup of a launch must be
-// co-resident, one per CU) share a device by a TILE BUDGET: a Newton loop
-// (update.hip holds its share for the whole loop, patch kernels included) or a
-// single solve acquires as many tiles as its grid has workgroups and waits
-// while the tiles in use plus its own exceed the device's CUs.  A full-size
-// solve (256 tiles at 1920x1080, scale 2) therefore still runs alone, but the
-// loops of the coarse scales -- 1, 4, 16, 64 tiles -- of several views in
-// flight run side by side instead of taking turns (round 3's exclusive lock).
-// Requests are served in arrival order, so a large request is not starved by
-// a stream of small ones.  Across PROCESSES that share the GPU the budget
-// cannot be shared; there an advisory lock on a file named after the device's
-// PCI bus id still makes the processes take turns: two such kernels of two
-// processes started together could each hold half of the CUs and wait for the
-// other half for ever.  The file lock is taken without the mutex held, kept
-// while loops of this process follow each other, and handed back after 100 ms at
-// the latest so that a process waiting for it gets its turn (cg_resident.hip).
-class DeviceTileBudget {
-public:
-    void acquire(int device, int tiles);
-    void release(int tiles);
-private:
-    void bind(int device);      // capacity, lock file: once
-    bool take_file_lock(void);
-    void unlock_file(void);
-    std::mutex mutex;
-    std::condition_variable turn;
-    int capacity = 0, used = 0, holders = 0;
-    unsigned long long next_ticket = 0, serving = 0;
-    int fd = -1;
-    bool bound = false, file_locked = false;
-    std::chrono::steady_clock::time_point file_since{}, no_file_until{};
-};
+// the tile budget (tile_budget.h) of the GPU behind a logical device
 DeviceTileBudget &cg_resident_budget(int device);
 // workgroups (= tiles = CUs) the resident solver launches for this context's
 // grid; 0 when it does not apply
 int cg_resident_tiles(smvs_ctx *ctx);
-struct ScopedTileBudget {
-    DeviceTileBudget &budget;
-    int tiles;
-    ScopedTileBudget(int device, int tiles_) : budget(cg_resident_budget(device)), tiles(tiles_)
-    {
-        budget.acquire(physical_device(device), tiles);
-    }
-    ~ScopedTileBudget() { budget.release(tiles); }
-    ScopedTileBudget(ScopedTileBudget const &) = delete;
-    ScopedTileBudget &operator=(ScopedTileBudget const &) = delete;
-};
 int cg_resident_enqueue(smvs_ctx *ctx, int max_iterations, double q_tolerance,
     bool test_give_up = false);
 int cg_resident_gave_up(smvs_ctx *ctx);   // a resident solve failed: what runs from now on

@@ -301,12 +301,7 @@ struct FinishArgs {
                                    // [1] = workgroups arrived)
     int wide;              // surfaces of 2^24 nodes and more: two atomics per workgroup
     const double *scalars;
-    int *host_words;       // pinned slot (STEP_SLOT_INTS ints): [0] sequence tag,
-                           // [1] active nodes, [2] NaN, [3] active patches of the
-                           // step, [4] next list length, [5] 0 ran / 1 skipped (the
-                           // loop had ended) / 1 + ABORT_* (the step was abandoned),
-                           // [6] CG iterations, [7] the loop ends after this step,
-                           // [8..11] two doubles: sum of shifts, number of terms
+    int *host_words;       // pinned slot of the step (common.h, STEP_*)
     int npx, npy, stride, num_nodes;
     int full_optimization;
     int seq;
@@ -331,9 +326,9 @@ finish_step_kernel(FinishArgs A)
         int const gate = A.status[I_STOP] != 0 ? 1 : (abort != 0 ? 1 + abort : 0);
         if (gate != 0) {
             if (blockIdx.x == 0 && threadIdx.x == 0) {
-                __hip_atomic_store(A.host_words + 5, gate, __ATOMIC_RELAXED,
+                __hip_atomic_store(A.host_words + STEP_GATE, gate, __ATOMIC_RELAXED,
                     __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(A.host_words + 0, A.seq, __ATOMIC_RELEASE,
+                __hip_atomic_store(A.host_words + STEP_SEQ, A.seq, __ATOMIC_RELEASE,
                     __HIP_MEMORY_SCOPE_SYSTEM);
             }
             return;
@@ -455,13 +450,13 @@ finish_step_kernel(FinishArgs A)
         A.status[I_NAN] = skip ? 1 : 0;
         A.status[I_NUM_ACTIVE] = num_active;
         A.status[I_LIVE_PATCHES] = next_live;
-        __hip_atomic_store(A.host_words + 1, num_active, __ATOMIC_RELAXED,
+        __hip_atomic_store(A.host_words + STEP_NUM_ACTIVE, num_active, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.host_words + 2, skip ? 1 : 0, __ATOMIC_RELAXED,
+        __hip_atomic_store(A.host_words + STEP_NAN, skip ? 1 : 0, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.host_words + 3, active_patches,
+        __hip_atomic_store(A.host_words + STEP_ACTIVE_PATCHES, active_patches,
             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.host_words + 4, next_live, __ATOMIC_RELAXED,
+        __hip_atomic_store(A.host_words + STEP_NEXT_LIVE, next_live, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_SYSTEM);
         double const sum_diff = pre_sum_diff;
         double const count_diff = pre_count_diff;
@@ -474,16 +469,16 @@ finish_step_kernel(FinishArgs A)
             stop = stop || !(num_active > initial / 20);
         if (A.check_stop || begin)
             A.status[I_STOP] = stop ? 1 : 0;
-        __hip_atomic_store(A.host_words + 5, 0, __ATOMIC_RELAXED,
+        __hip_atomic_store(A.host_words + STEP_GATE, 0, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.host_words + 6, begin ? 0 : pre_iter, __ATOMIC_RELAXED,
+        __hip_atomic_store(A.host_words + STEP_CG_ITERS, begin ? 0 : pre_iter, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.host_words + 7, stop ? 1 : 0, __ATOMIC_RELAXED,
+        __hip_atomic_store(A.host_words + STEP_LOOP_ENDS, stop ? 1 : 0, __ATOMIC_RELAXED,
             __HIP_MEMORY_SCOPE_SYSTEM);
-        double *host_scalars = reinterpret_cast<double *>(A.host_words + 8);
+        double *host_scalars = reinterpret_cast<double *>(A.host_words + STEP_SCALARS);
         host_scalars[0] = sum_diff;
         host_scalars[1] = count_diff;
-        __hip_atomic_store(A.host_words + 0, A.seq, __ATOMIC_RELEASE,
+        __hip_atomic_store(A.host_words + STEP_SEQ, A.seq, __ATOMIC_RELEASE,
             __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
@@ -880,14 +875,14 @@ wait_step_words(smvs_ctx *ctx, int seq, const int **slot_out)
     const int *words = ctx->step_words + (seq & (STEP_SLOTS - 1)) * STEP_SLOT_INTS;
     auto const t_start = std::chrono::steady_clock::now();
     long spins = 0;
-    while (__atomic_load_n(&words[0], __ATOMIC_ACQUIRE) != seq) {
+    while (__atomic_load_n(&words[STEP_SEQ], __ATOMIC_ACQUIRE) != seq) {
         __builtin_ia32_pause();
         if ((++spins & 0xFFFF) == 0) {
             hipError_t const q = hipStreamQuery(ctx->stream);
             if (q != hipSuccess && q != hipErrorNotReady)
                 SMVS_HIP_CHECK(q);
             if (q == hipSuccess
-                && __atomic_load_n(&words[0], __ATOMIC_ACQUIRE) != seq) {
+                && __atomic_load_n(&words[STEP_SEQ], __ATOMIC_ACQUIRE) != seq) {
                 set_error("smvs_gn_run_loop: the step ended without "
                     "publishing its result");
                 return SMVS_ERR_STATE;
@@ -912,8 +907,8 @@ read_loop_begin(smvs_ctx *ctx, LoopState &L)
     int const rc = wait_step_words(ctx, L.begin_seq, &words);
     if (rc != SMVS_OK)
         return rc;
-    L.num_initial = L.num_active = words[1];
-    L.known_live = words[4];
+    L.num_initial = L.num_active = words[STEP_NUM_ACTIVE];
+    L.known_live = words[STEP_NEXT_LIVE];
     L.begin_seq = 0;
     return SMVS_OK;
 }
@@ -925,9 +920,9 @@ account_step(const smvs_gn_loop_params *prm, smvs_gn_loop_stats *stats,
 {
     L.newton_step += 1;
     stats->linear_iterations += cg_iterations;
-    stats->active_patch_steps += words[3];
-    L.known_live = words[4];
-    if (words[2] != 0) {
+    stats->active_patch_steps += words[STEP_ACTIVE_PATCHES];
+    L.known_live = words[STEP_NEXT_LIVE];
+    if (words[STEP_NAN] != 0) {
         stats->nan_break = 1;
         L.ended = true;
         return;
@@ -936,12 +931,12 @@ account_step(const smvs_gn_loop_params *prm, smvs_gn_loop_stats *stats,
         // depth_optimizer.cc:277-288: sum_diff / size; with no reprojection
         // term at all this is 0 / 0 = NaN, the comparison is false and the
         // loop goes on to its step limit like the reference
-        const double *sc = reinterpret_cast<const double *>(words + 8);
+        const double *sc = reinterpret_cast<const double *>(words + STEP_SCALARS);
         if (sc[0] / sc[1] < prm->full_opt_threshold)
             L.ended = true;
         return;
     }
-    L.num_active = words[1];
+    L.num_active = words[STEP_NUM_ACTIVE];
 }
 
 static int
@@ -1021,10 +1016,10 @@ static int
 run_steps_pipelined(smvs_ctx *ctx, const smvs_gn_loop_params *prm,
     smvs_gn_loop_stats *stats, LoopState &L)
 {
-    // the loop's share of the device's CUs (common.h, DeviceTileBudget): the
+    // the loop's share of the device's CUs (tile_budget.h): the
     // barrier kernels running side by side never ask for more workgroups than
     // the device can keep resident together
-    ScopedTileBudget guard(ctx->device, cg_resident_tiles(ctx));
+    ScopedTileBudget guard(cg_resident_budget(ctx->device), cg_resident_tiles(ctx));
     static_assert(I_STEP_ABORT == I_STOP + 1, "cleared together");
     int const test_mode = loop_test_mode();
     int rc;
@@ -1125,9 +1120,9 @@ run_steps_pipelined(smvs_ctx *ctx, const smvs_gn_loop_params *prm,
             return fail(rc);
         seqs[0] = seqs[1];
         in_flight -= 1;
-        if (words[5] == 1 + ABORT_SOLVER || words[5] == 1 + ABORT_GRID) {
+        if (words[STEP_GATE] == 1 + ABORT_SOLVER || words[STEP_GATE] == 1 + ABORT_GRID) {
             // this step and the one behind it did nothing
-            bool const solver = words[5] == 1 + ABORT_SOLVER;
+            bool const solver = words[STEP_GATE] == 1 + ABORT_SOLVER;
             if ((rc = drain()) != SMVS_OK)
                 return fail(rc);
             SMVS_HIP_CHECK(hipMemsetAsync(ctx->status + I_STOP, 0,
@@ -1144,19 +1139,19 @@ run_steps_pipelined(smvs_ctx *ctx, const smvs_gn_loop_params *prm,
                 return fail(rc);
             continue;
         }
-        if (words[5] != 0) {
+        if (words[STEP_GATE] != 0) {
             set_error("smvs_gn_run_loop: a step was skipped before the loop ended");
             return fail(SMVS_ERR_STATE);
         }
-        ctx->last_cg_iterations = words[6];
-        account_step(prm, stats, L, words, words[6]);
+        ctx->last_cg_iterations = words[STEP_CG_ITERS];
+        account_step(prm, stats, L, words, words[STEP_CG_ITERS]);
         if (prm->full_optimization) {
-            const double *sc = reinterpret_cast<const double *>(words + 8);
+            const double *sc = reinterpret_cast<const double *>(words + STEP_SCALARS);
             last_update = sc[0] / sc[1];
         }
         if (!L.ended && !(L.num_active > L.num_initial / 20))
             L.ended = true;
-        if (L.ended != (words[7] != 0)) {
+        if (L.ended != (words[STEP_LOOP_ENDS] != 0)) {
             set_error("smvs_gn_run_loop: host and device disagree on the end "
                 "of the loop");
             return fail(SMVS_ERR_STATE);
