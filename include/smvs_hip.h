@@ -685,6 +685,20 @@ int smvs_simplify_triangulate(int device, const float *depth, int width, int hei
     double *vertices, int64_t *n_triangles, uint32_t *triangles,
     int32_t *num_zero_depths, uint64_t *clocks4);
 
+/* smvsrecon's input scaling (app/smvsrecon.cc:634-647): `halvings` chained
+ * mve::image::rescale_half_size_gaussian<uint8_t> (sigma^2 = 0.75,
+ * [MVE-unverified] M29) of one interleaved u8 image on the device, bit-identical
+ * with the host mirror's function (host/scene_io.cc); the intermediate levels
+ * stay on the device.  out receives the last level, ((w + 1) / 2 per halving) x
+ * ((h + 1) / 2 ...) x channels bytes, *out_width / *out_height its size.
+ * Argument errors (SMVS_ERR_INVALID, before any device call): a null pointer,
+ * halvings < 1, channels outside 1..4, a level whose input is narrower or lower
+ * than 2 pixels ("image too small", as the host function), out_capacity below
+ * the last level's bytes. */
+int smvs_rescale_half_gaussian(int device, const uint8_t *pixels, int width, int height,
+    int channels, int halvings, uint8_t *out, size_t out_capacity, int *out_width,
+    int *out_height);
+
 /* The context-free entry points above (smvs_sgm_run, smvs_sgm_depth_for_view,
  * smvs_bilateral_upsample, smvs_cut_depth_maps) draw their device buffers,
  * stream and pinned staging memory from a per-device pool of workspaces that

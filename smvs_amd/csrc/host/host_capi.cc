@@ -810,9 +810,24 @@ smvs_host_reconstruct_scene_mode(const char *scene_dir,
     int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
     int *n_skipped, double *seconds, int *input_scale_used)
 {
+    return smvs_host_reconstruct_scene_flags(scene_dir, o,
+        sgm_adaptive_penalty2 != 0 ? SMVS_HOST_SCENE_ADAPTIVE_PENALTY2 : 0u, view_ids,
+        n_view_ids, reconstructed_out, max_reconstructed, n_reconstructed, n_skipped,
+        seconds, input_scale_used);
+}
+
+extern "C" int
+smvs_host_reconstruct_scene_flags(const char *scene_dir,
+    const smvs_host_recon_settings *o, unsigned flags, const int *view_ids,
+    int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
+    int *n_skipped, double *seconds, int *input_scale_used)
+{
     try {
         if (scene_dir == nullptr || o == nullptr)
             throw std::invalid_argument("smvs_host_reconstruct_scene: bad argument");
+        if ((flags & ~(unsigned)(SMVS_HOST_SCENE_ADAPTIVE_PENALTY2
+                | SMVS_HOST_SCENE_DEVICE_INPUT_SCALING)) != 0u)
+            throw std::invalid_argument("smvs_host_reconstruct_scene_flags: unknown flag");
         ReconSettings conf;
         if (o->image_embedding != nullptr)
             conf.image_embedding = o->image_embedding;
@@ -826,7 +841,8 @@ smvs_host_reconstruct_scene_mode(const char *scene_dir,
         conf.sgm_min = o->sgm_min;
         conf.sgm_max = o->sgm_max;
         conf.sgm_scale = o->sgm_scale;
-        conf.sgm_adaptive_penalty2 = sgm_adaptive_penalty2 != 0;
+        conf.sgm_adaptive_penalty2 = (flags & SMVS_HOST_SCENE_ADAPTIVE_PENALTY2) != 0u;
+        conf.device_input_scaling = (flags & SMVS_HOST_SCENE_DEVICE_INPUT_SCALING) != 0u;
         conf.num_neighbors = (std::size_t)o->num_neighbors;
         conf.min_neighbors = (std::size_t)o->min_neighbors;
         conf.first_device = o->first_device;
@@ -975,6 +991,34 @@ smvs_host_rescale_half_size_gaussian(const uint8_t *pixels, int width, int heigh
         ByteImage::Ptr half = rescale_half_size_gaussian(img);
         std::memcpy(out, half->begin(),
             (std::size_t)half->width() * half->height() * half->channels());
+        return 0;
+    } catch (std::exception const& e) {
+        g_host_error = e.what();
+        return -1;
+    }
+}
+
+extern "C" int
+smvs_host_rescale_half_size_gaussian_device(const uint8_t *pixels, int width, int height,
+    int channels, int halvings, int device, uint8_t *out, size_t out_capacity,
+    int *out_width, int *out_height)
+{
+    try {
+        if (pixels == nullptr || out == nullptr || out_width == nullptr
+            || out_height == nullptr || width < 1 || height < 1 || channels < 1)
+            throw std::invalid_argument(
+                "smvs_host_rescale_half_size_gaussian_device: bad argument");
+        ByteImage::Ptr img = ByteImage::create_for_overwrite(width, height, channels);
+        std::memcpy(img->begin(), pixels, (std::size_t)width * height * channels);
+        ByteImage::Ptr scaled = rescale_half_size_gaussian_device(img, halvings, device);
+        std::size_t const n = (std::size_t)scaled->width() * scaled->height()
+            * scaled->channels();
+        if (out_capacity < n)
+            throw std::invalid_argument(
+                "smvs_host_rescale_half_size_gaussian_device: buffer too small");
+        std::memcpy(out, scaled->begin(), n);
+        *out_width = scaled->width();
+        *out_height = scaled->height();
         return 0;
     } catch (std::exception const& e) {
         g_host_error = e.what();

@@ -191,6 +191,20 @@ int smvs_host_reconstruct_scene_mode(const char *scene_dir,
     const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
     int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used);
 
+/* The same with a word of switches the settings struct does not hold (it keeps
+ * its layout for existing callers).  Bit 0: ReconSettings::sgm_adaptive_penalty2
+ * (smvs_host_reconstruct_scene_mode's argument); bit 1: ReconSettings::
+ * device_input_scaling -- the input scaling of app/smvsrecon.cc:621-650 runs on
+ * the device (smvs_rescale_half_gaussian), one ViewQueue task per view; the
+ * undist-L<s> images are the host path's, bit for bit.  An unknown bit is an
+ * argument error.  smvs_host_reconstruct_scene and ..._mode forward to this. */
+#define SMVS_HOST_SCENE_ADAPTIVE_PENALTY2 1
+#define SMVS_HOST_SCENE_DEVICE_INPUT_SCALING 2
+int smvs_host_reconstruct_scene_flags(const char *scene_dir,
+    const smvs_host_recon_settings *settings, unsigned flags, const int *view_ids,
+    int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
+    int *n_skipped, double *seconds, int *input_scale_used);
+
 /* smvsrecon's generate_mesh (app/smvsrecon.cc:278-343, MeshGenerator::
  * generate_mesh, lib/mesh_generator.cc:160-299) on a reconstructed scene: the
  * point cloud of the views' <dm_name> / <dm_name>N / <input> embeddings (cut
@@ -255,6 +269,13 @@ int smvs_host_save_png(const char *path, const uint8_t *pixels, int width, int h
     int channels);
 int smvs_host_rescale_half_size_gaussian(const uint8_t *pixels, int width, int height,
     int channels, uint8_t *out);
+/* `halvings` of them chained on device `device` (smvs_rescale_half_gaussian,
+ * app/smvsrecon.cc:634-647), bit-identical with the host function applied
+ * `halvings` times; out has room for out_capacity bytes, *out_width /
+ * *out_height receive the last level's size. */
+int smvs_host_rescale_half_size_gaussian_device(const uint8_t *pixels, int width,
+    int height, int channels, int halvings, int device, uint8_t *out,
+    size_t out_capacity, int *out_width, int *out_height);
 
 /* MVE scene I/O without a device: parses the scene (views/<x>.mve/meta.ini,
  * synth_0.out) -> number of list entries, and per entry (caller-sized arrays of

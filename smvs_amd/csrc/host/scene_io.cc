@@ -19,6 +19,7 @@
 #include "sgm_stereo.h"
 #include "stereo_view.h"
 #include "view_queue.h"
+#include "../../../include/smvs_hip.h"
 
 namespace smvs_amd {
 
@@ -283,6 +284,33 @@ rescale_half_size_gaussian(ByteImage::ConstPtr img)
     return out;
 }
 
+ByteImage::Ptr
+rescale_half_size_gaussian_device(ByteImage::ConstPtr img, int halvings, int device)
+{
+    if (img == nullptr)
+        throw std::invalid_argument("rescale_half_size_gaussian_device: no image");
+    int w = img->width(), h = img->height();
+    int const c = img->channels();
+    // the last level's size, to allocate it (the entry checks the levels itself)
+    for (int s = 0; s < halvings && w >= 2 && h >= 2; ++s) {
+        w = (w + 1) >> 1;
+        h = (h + 1) >> 1;
+    }
+    ByteImage::Ptr out = ByteImage::create_for_overwrite(std::max(w, 1), std::max(h, 1),
+        std::max(c, 1));
+    int ow = 0, oh = 0;
+    int const rc = smvs_rescale_half_gaussian(device, img->begin(), img->width(),
+        img->height(), c, halvings, out->begin(),
+        (std::size_t)out->width() * out->height() * out->channels(), &ow, &oh);
+    if (rc == SMVS_ERR_INVALID)
+        throw std::invalid_argument(smvs_last_error());
+    if (rc != SMVS_OK)
+        throw std::runtime_error(smvs_last_error());
+    if (ow != out->width() || oh != out->height())
+        throw std::runtime_error("rescale_half_size_gaussian_device: unexpected size");
+    return out;
+}
+
 Scene::Ptr
 Scene::create(std::string const& path)
 {
@@ -472,17 +500,42 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                 needed[n] = 1;
         }
         std::vector<std::future<void>> resize_tasks;
-        for (std::size_t i = 0; i < views.size(); ++i) {
-            SceneView const& view = views[i];
-            if (!needed[i] || !view.present || !view.has_image(conf.image_embedding)
-                || view.has_image(input_name))
-                continue;
-            resize_tasks.push_back(std::async(std::launch::async, [&view, &conf, &input_name] {
-                ByteImage::Ptr scaled = view.load_byte_image(conf.image_embedding);
-                for (int s = 0; s < conf.input_scale; ++s)
-                    scaled = rescale_half_size_gaussian(scaled);
-                save_png_u8(view.directory + "/" + input_name + ".png", scaled);
-            }));
+        if (conf.device_input_scaling) {
+            // the same tasks on the device: a bounded number of host threads,
+            // spread over the devices like the per-view tasks below
+            ViewQueue queue(conf.num_devices, conf.views_in_flight);
+            for (std::size_t i = 0; i < views.size(); ++i) {
+                SceneView const& view = views[i];
+                if (!needed[i] || !view.present || !view.has_image(conf.image_embedding)
+                    || view.has_image(input_name))
+                    continue;
+                resize_tasks.push_back(queue.add_task(
+                    [&view, &conf, &input_name](ViewQueue::Slot const& slot) {
+                        ByteImage::Ptr scaled = view.load_byte_image(conf.image_embedding);
+                        if (scaled->channels() >= 1 && scaled->channels() <= 4)
+                            scaled = rescale_half_size_gaussian_device(scaled,
+                                conf.input_scale, conf.first_device + slot.device);
+                        else   // a channel count the device entry refuses
+                            for (int s = 0; s < conf.input_scale; ++s)
+                                scaled = rescale_half_size_gaussian(scaled);
+                        save_png_u8(view.directory + "/" + input_name + ".png", scaled);
+                    }));
+            }
+            queue.wait_idle();
+        } else {
+            for (std::size_t i = 0; i < views.size(); ++i) {
+                SceneView const& view = views[i];
+                if (!needed[i] || !view.present || !view.has_image(conf.image_embedding)
+                    || view.has_image(input_name))
+                    continue;
+                resize_tasks.push_back(std::async(std::launch::async,
+                    [&view, &conf, &input_name] {
+                        ByteImage::Ptr scaled = view.load_byte_image(conf.image_embedding);
+                        for (int s = 0; s < conf.input_scale; ++s)
+                            scaled = rescale_half_size_gaussian(scaled);
+                        save_png_u8(view.directory + "/" + input_name + ".png", scaled);
+                    }));
+            }
         }
         for (auto& t : resize_tasks)
             t.get();

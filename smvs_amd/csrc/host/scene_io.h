@@ -54,6 +54,12 @@ struct SceneView
 // smvsrecon pre-scales its input embedding with (app/smvsrecon.cc:634-647)
 // [MVE-unverified, tests/golden/README.md M29]
 ByteImage::Ptr rescale_half_size_gaussian(ByteImage::ConstPtr image);
+// `halvings` of them chained on device `device` (smvs_rescale_half_gaussian),
+// bit-identical with the host function applied `halvings` times; throws
+// std::invalid_argument for what the device entry refuses (more than four
+// channels, a level too small), std::runtime_error for a device error
+ByteImage::Ptr rescale_half_size_gaussian_device(ByteImage::ConstPtr image,
+    int halvings, int device);
 
 class Scene
 {
@@ -91,6 +97,9 @@ struct ReconSettings
     // not in the reference's AppSettings: SGMStereo::Options::adaptive_penalty2
     // (the reference's build without SSE, lib/sgm_stereo.cc:310-346)
     bool sgm_adaptive_penalty2 = false;
+    // not in the reference's AppSettings: the input scaling of :621-650 on the
+    // device (rescale_half_size_gaussian_device), one ViewQueue task per view
+    bool device_input_scaling = false;
     std::size_t num_neighbors = 6, min_neighbors = 3;
     int first_device = 0, num_devices = 1, views_in_flight = 2;
 };

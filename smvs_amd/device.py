@@ -431,6 +431,28 @@ def bilateral_upsample(dm, ci, sigma=5.0, kernel_size=5, device=0):
     return out
 
 
+def rescale_half_gaussian(image, halvings=1, device=0):
+    """smvs_rescale_half_gaussian: `halvings` chained rescale_half_size_gaussian
+    of a u8 image (h, w) or (h, w, c), c = 1..4, on the device
+    (app/smvsrecon.cc:634-647); bit-identical with the host mirror's function."""
+    lib = _capi.load()
+    a = np.ascontiguousarray(image, dtype=np.uint8)
+    squeeze = a.ndim == 2
+    if squeeze:
+        a = a[:, :, None]
+    h, w, c = a.shape
+    ow, oh = w, h
+    for _ in range(max(halvings, 0)):
+        ow, oh = (ow + 1) // 2, (oh + 1) // 2
+    out = np.zeros((oh, ow, c), np.uint8)
+    gw, gh = C.c_int(0), C.c_int(0)
+    check(lib.smvs_rescale_half_gaussian(C.c_int(device), _p(a, _u8p), C.c_int(w),
+          C.c_int(h), C.c_int(c), C.c_int(halvings), _p(out, _u8p),
+          C.c_size_t(out.size), C.byref(gw), C.byref(gh)))
+    assert (gw.value, gh.value) == (ow, oh)
+    return out[:, :, 0] if squeeze else out
+
+
 class SgmNeighbor(C.Structure):
     """smvs_sgm_neighbor of include/smvs_hip.h."""
     _fields_ = [("image", _u8p), ("width", C.c_int), ("height", C.c_int),

@@ -228,7 +228,7 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       force_recon=False, force_sgm=False, sgm_range=(0.0, 0.0), sgm_scale=1,
                       num_neighbors=6, min_neighbors=3, first_device=0, num_devices=1,
                       views_in_flight=2, input_scale=-1, max_pixels=1700000, details=False,
-                      sgm_adaptive_penalty2=False):
+                      sgm_adaptive_penalty2=False, device_input_scaling=False):
     """smvsrecon's scene-level run (app/smvsrecon.cc:400-745) through
     smvs_amd::reconstruct_scene: returns (reconstructed ids, skipped, seconds)
     [, input scale used if `details`].  input_scale < 0 (the default, as
@@ -237,7 +237,10 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     embedding undist-L<input_scale>, created with rescale_half_size_gaussian
     where missing (:621-650), and the outputs are named smvs-B<input_scale>.
     sgm_adaptive_penalty2: the SGM front end as the reference's build without
-    SSE runs it (lib/sgm_stereo.cc:310-346); off by default."""
+    SSE runs it (lib/sgm_stereo.cc:310-346); off by default.
+    device_input_scaling: the undist-L<input_scale> images are made on the
+    device (smvs_rescale_half_gaussian, one ViewQueue task per view) instead of
+    by the host loop, with the same bytes; off by default."""
     lib = load()
     st = ReconSettings(image_embedding.encode(), regularization, output_scale,
                        1 if use_shading else 0, 1 if use_sgm else 0,
@@ -251,8 +254,8 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                              C.byref(cap), None, None, None, None, None, None, None)
     out = np.zeros(max(cap.value, 1), np.int32)
     n = C.c_int(0); sk = C.c_int(0); secs = C.c_double(0.0); used = C.c_int(0)
-    rc = lib.smvs_host_reconstruct_scene_mode(scene_dir.encode(), C.byref(st),
-        C.c_int(1 if sgm_adaptive_penalty2 else 0),
+    rc = lib.smvs_host_reconstruct_scene_flags(scene_dir.encode(), C.byref(st),
+        C.c_uint((1 if sgm_adaptive_penalty2 else 0) | (2 if device_input_scaling else 0)),
         ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), out.ctypes.data_as(_i32p),
         C.c_int(out.size), C.byref(n), C.byref(sk), C.byref(secs), C.byref(used))
@@ -289,20 +292,41 @@ def save_png(path, array):
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
 
 
-def rescale_half_size_gaussian(array):
-    """mve::image::rescale_half_size_gaussian<uint8_t> of the host mirror."""
+def rescale_half_size_gaussian(array, halvings=1, device=None):
+    """mve::image::rescale_half_size_gaussian<uint8_t> of the host mirror,
+    `halvings` times.  device=None: the host loop; device=k: the whole chain on
+    device k (rescale_half_size_gaussian_device), the same bytes."""
     lib = load()
     a = np.ascontiguousarray(array, dtype=np.uint8)
     squeeze = a.ndim == 2
     if squeeze:
         a = a[:, :, None]
-    h, w, c = a.shape
-    out = np.zeros(((h + 1) // 2, (w + 1) // 2, c), np.uint8)
-    rc = lib.smvs_host_rescale_half_size_gaussian(a.ctypes.data_as(_u8p), C.c_int(w),
-                                                  C.c_int(h), C.c_int(c),
-                                                  out.ctypes.data_as(_u8p))
-    if rc != 0:
-        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    if device is None:
+        if halvings < 1:
+            raise ValueError("rescale_half_size_gaussian: halvings < 1")
+        for _ in range(halvings):
+            h, w, c = a.shape
+            out = np.zeros(((h + 1) // 2, (w + 1) // 2, c), np.uint8)
+            rc = lib.smvs_host_rescale_half_size_gaussian(a.ctypes.data_as(_u8p), C.c_int(w),
+                                                          C.c_int(h), C.c_int(c),
+                                                          out.ctypes.data_as(_u8p))
+            if rc != 0:
+                raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+            a = out
+    else:
+        h, w, c = a.shape
+        ow, oh = w, h
+        for _ in range(max(halvings, 0)):
+            ow, oh = (ow + 1) // 2, (oh + 1) // 2
+        out = np.zeros((oh, ow, c), np.uint8)
+        gw, gh = C.c_int(0), C.c_int(0)
+        rc = lib.smvs_host_rescale_half_size_gaussian_device(
+            a.ctypes.data_as(_u8p), C.c_int(w), C.c_int(h), C.c_int(c), C.c_int(halvings),
+            C.c_int(device), out.ctypes.data_as(_u8p), C.c_size_t(out.size), C.byref(gw),
+            C.byref(gh))
+        if rc != 0:
+            raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+        assert (gw.value, gh.value) == (ow, oh)
     return out[:, :, 0] if squeeze else out
 
 
