@@ -272,7 +272,7 @@ struct smvs_ctx {
     bool sgm_resident = false;   // topo_sgm holds smvs_ctx_sgm_init_depth's result
     float *sgm_lowres = nullptr; // its input, SGM resolution
     size_t sgm_lowres_cap = 0;
-    float *bil_lut = nullptr;    // compressed colour-weight table of the bilateral filter (sgm.hip)
+    float *bil_lut = nullptr;    // compressed colour-weight table of the bilateral filter (bilateral.hip)
     float *bil_tri = nullptr;    // ... and the triangle of all byte pairs (round 6)
     int topo_slot = 0;           // cut_boundaries: the word pair of the next pass (topology.hip)
     bool topo_slots_clean = false;   // ... and whether both pairs are zero on the stream

@@ -1,13 +1,13 @@
-// Census / plane-sweep cost volume, 8-path SGM aggregation, WTA and the joint
-// bilateral upsample on gfx950.
+// Census / plane-sweep cost volume, 8-path SGM aggregation and WTA on gfx950:
+// one run_sgm, as smvs_sgm_run[_mode] and as sgm_run_device for a view's front
+// end (sgm_view.hip); and the counters of the front end's kernel timer.
 //
 // Replaces SGMStereo::run_sgm (reference: lib/sgm_stereo.cc:98-124):
 // census_filter (:126-148), warped_neighbors_for_depth (:150-190),
 // create_cost_volume (:192-244), aggregate_sgm_costs (:429-667, the SSE
 // branch with constant penalty2, :361-406; on request the branch without SSE,
 // fill_path_cost :310-346 with its seeds :626-654 -- SMVS_SGM_P2_ADAPTIVE, the
-// ADAPT kernels below), depth_from_sgm_volume (:274-306);
-// and DepthOptimizer::depthmap_bilateral_filter (lib/depth_optimizer.cc:957-1004).
+// ADAPT kernels below), depth_from_sgm_volume (:274-306).
 //
 // Integer path: results are bit-exact with the reference semantics.  The
 // float warp is evaluated in the reference's operation order with FMA
@@ -22,15 +22,13 @@
 // atomics on packed u16 pairs (integer adds commute: bit-exact); odd plane
 // counts take one launch per direction.  Each path reads C once and
 // read-modify-writes S once.
-#include "common.h"
-#include <type_traits>
+#include "dpp.h"
+#include "sgm_internal.h"
 
-#include <utility>
-
+#include <cstdlib>
 #include <mutex>
-
-#include <cmath>
-#include <vector>
+#include <type_traits>
+#include <utility>
 
 namespace smvs_hip {
 
@@ -424,41 +422,6 @@ adapted_penalty2(uint32_t p1, uint32_t p2, uint32_t i_here, uint32_t i_before)
     return max(p1 * 3u / 2u, p2 / diff);
 }
 
-// Wave-wide unsigned minimum with DPP row operations (VALU latency instead of
-// the LDS crossbar of ds_bpermute): prefix-min inside each row of 16 lanes,
-// row_bcast:15 / row_bcast:31 to combine the rows, total in lane 63.
-__device__ __forceinline__ uint32_t
-wave_min_u32(uint32_t v)
-{
-    uint32_t const ident = 0xFFFFFFFFu;
-#define SMVS_DPP(x, ctrl, rmask)                                             \
-    (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)(x), ctrl, rmask, \
-        0xf, false)
-    v = min(v, SMVS_DPP(v, 0x111, 0xf));   // row_shr:1
-    v = min(v, SMVS_DPP(v, 0x112, 0xf));   // row_shr:2
-    v = min(v, SMVS_DPP(v, 0x114, 0xf));   // row_shr:4
-    v = min(v, SMVS_DPP(v, 0x118, 0xf));   // row_shr:8
-    v = min(v, SMVS_DPP(v, 0x142, 0xa));   // row_bcast:15 -> rows 1, 3
-    v = min(v, SMVS_DPP(v, 0x143, 0xc));   // row_bcast:31 -> rows 2, 3
-#undef SMVS_DPP
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-// value of the previous / next lane (wave_shr:1 / wave_shl:1); lanes without
-// a source get `fill`
-__device__ __forceinline__ uint32_t
-lane_prev(uint32_t v, uint32_t fill)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xf,
-        0xf, false);
-}
-
-__device__ __forceinline__ uint32_t
-lane_next(uint32_t v, uint32_t fill)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x130, 0xf,
-        0xf, false);
-}
 
 // One wavefront per line.  Lines: for a horizontal path the rows, for a
 // vertical path the columns, for a diagonal path all diagonals that start on
@@ -657,16 +620,6 @@ pk_min(uint32_t a, uint32_t b)
         __builtin_bit_cast(u16x2_r, a), __builtin_bit_cast(u16x2_r, b)));
 }
 
-// max over a DPP pattern with bound_ctrl: a lane without a source reads 0, the
-// identity of an unsigned maximum -- one v_max_u32_dpp, nothing to move into
-// the destination first (the minimum below is taken as the maximum of the
-// complements)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t
-max_dpp0(uint32_t v)
-{
-    return max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, true));
-}
 
 // FULL: 128 planes, every lane of a half wave has four (no idle lanes to reset)
 //
@@ -693,23 +646,20 @@ sgm_paths2_kernel(PathArgs A)
 {
     __shared__ uint32_t p2_table[ADAPT ? 256 : 1];
     int const w = A.w, h = A.h, D = A.D;
-    int const ndiag = w + h - 1;
-    // block -> (direction, pair of lines); the long horizontal lines first
-    int const counts[8] = { h, h, w, ndiag, ndiag, w, ndiag, ndiag };
+    // block -> (direction, pair of lines), the grid being sgm_grid_line_pairs();
+    // the long horizontal lines first
     int b = blockIdx.x;
     int dir = 0;
     for (; dir < 8; ++dir) {
-        int const pairs_of_dir = (counts[dir] + 1) >> 1;
+        int const pairs_of_dir = (sgm_dir_lines(dir, w, h) + 1) >> 1;
         if (b < pairs_of_dir)
             break;
         b -= pairs_of_dir;
     }
     if (dir > 7)
         return;
-    int const dirs[8][2] = { { 1, 0 }, { -1, 0 }, { 0, 1 }, { 1, 1 }, { -1, 1 },
-        { 0, -1 }, { 1, -1 }, { -1, -1 } };
-    A.dx = dirs[dir][0];
-    A.dy = dirs[dir][1];
+    A.dx = SGM_DIRS[dir][0];
+    A.dy = SGM_DIRS[dir][1];
 
     int const lane = threadIdx.x;
     int const half = lane >> 5, hl = lane & 31;
@@ -840,11 +790,11 @@ sgm_paths2_kernel(PathArgs A)
                 // the minimum over the line: per lane, then over its half wave
                 uint32_t m = pk_min(pa, pb);
                 m = ~min(m & 0xFFFFu, m >> 16);
-                m = max_dpp0<0x111, 0xf>(m);   // row_shr:1
-                m = max_dpp0<0x112, 0xf>(m);   // row_shr:2
-                m = max_dpp0<0x114, 0xf>(m);   // row_shr:4
-                m = max_dpp0<0x118, 0xf>(m);   // row_shr:8
-                m = max_dpp0<0x142, 0xa>(m);   // row_bcast:15 -> rows 1, 3
+                m = max_dpp0<DPP_ROW_SHR1, DPP_ROWS_ALL>(m);
+                m = max_dpp0<DPP_ROW_SHR2, DPP_ROWS_ALL>(m);
+                m = max_dpp0<DPP_ROW_SHR4, DPP_ROWS_ALL>(m);
+                m = max_dpp0<DPP_ROW_SHR8, DPP_ROWS_ALL>(m);
+                m = max_dpp0<DPP_ROW_BCAST15, DPP_ROWS_1_3>(m);
                 uint32_t const m_lower = ~(uint32_t)__builtin_amdgcn_readlane((int)m, 31);
                 uint32_t const m_upper = ~(uint32_t)__builtin_amdgcn_readlane((int)m, 63);
                 uint32_t const mm_lower = m_lower | (m_lower << 16);
@@ -854,10 +804,8 @@ sgm_paths2_kernel(PathArgs A)
                 // neighbouring planes: {3 of the lane before, 0}, {1, 2}, {3, 0 of the lane after}
                 // (wave_shr:1 / wave_shl:1; the lanes without a source are ends of
                 // a line, whose selectors do not look at what arrives)
-                uint32_t const pb_prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pb, 0x138,
-                    0xf, 0xf, true);
-                uint32_t const pa_next = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pa, 0x130,
-                    0xf, 0xf, true);
+                uint32_t const pb_prev = dpp_u32<DPP_WAVE_SHR1, DPP_ROWS_ALL, true>(0u, pb);
+                uint32_t const pa_next = dpp_u32<DPP_WAVE_SHL1, DPP_ROWS_ALL, true>(0u, pa);
                 uint32_t const below_a = __builtin_amdgcn_perm(pa, pb_prev, sel_below);
                 uint32_t const mid = __builtin_amdgcn_alignbit(pb, pa, 16);
                 uint32_t const above_b = __builtin_amdgcn_perm(pa_next, pb, sel_above);
@@ -946,32 +894,34 @@ template <int K, bool DELTA, bool ADAPT = false>
 __global__ void __launch_bounds__(64)
 sgm_all_paths_kernel(PathArgs A)
 {
-    // block -> (direction, line); the long horizontal lines come first
+    // block -> (direction, line), the grid being sgm_grid_lines(); the long
+    // horizontal lines come first.  (The two horizontal directions by a
+    // division, the rest by a walk: sgm_paths2_kernel's single walk over all
+    // eight compiles to other instructions here, so this decode keeps its form
+    // and takes only its counts from sgm_dir_lines().)
     int const w = A.w, h = A.h, D = A.D;
-    int const ndiag = w + h - 1;
+    int const rows = sgm_dir_lines(0, w, h);   // == sgm_dir_lines(1, w, h)
     int b = blockIdx.x;
     int dir;
-    if (b < 2 * h) {
-        dir = b / h;              // 0: ->, 1: <-
-        b -= dir * h;
+    if (b < 2 * rows) {
+        dir = b / rows;           // 0: ->, 1: <-
+        b -= dir * rows;
     } else {
-        b -= 2 * h;
+        b -= 2 * rows;
         // remaining six: (0,1) (1,1) (-1,1) (0,-1) (1,-1) (-1,-1)
-        int const counts[6] = { w, ndiag, ndiag, w, ndiag, ndiag };
         dir = 2;
-        for (int k = 0; k < 6; ++k) {
-            if (b < counts[k])
+        for (int k = 2; k < 8; ++k) {
+            int const lines_of_dir = sgm_dir_lines(k, w, h);
+            if (b < lines_of_dir)
                 break;
-            b -= counts[k];
+            b -= lines_of_dir;
             dir += 1;
         }
         if (dir > 7)
             return;
     }
-    int const dirs[8][2] = { { 1, 0 }, { -1, 0 }, { 0, 1 }, { 1, 1 }, { -1, 1 },
-        { 0, -1 }, { 1, -1 }, { -1, -1 } };
-    A.dx = dirs[dir][0];
-    A.dy = dirs[dir][1];
+    A.dx = SGM_DIRS[dir][0];
+    A.dy = SGM_DIRS[dir][1];
 
     int const lane = threadIdx.x;
     int x0, y0, len, extra_seed;
@@ -1093,6 +1043,22 @@ sgm_all_paths_kernel(PathArgs A)
     }
 }
 
+// The end of both WTA kernels (sgm_stereo.cc:300-303): the winning plane is the
+// low byte of the (value, plane) key; no depth for the two nearest planes and
+// for dark pixels.
+__device__ __forceinline__ void
+wta_store(uint32_t key, size_t p, const uint8_t *__restrict__ main_img,
+    const float *__restrict__ depths, float *__restrict__ depth,
+    int32_t *__restrict__ argmin)
+{
+    int const min_index = (int)(key & 0xFFu);
+    if (argmin != nullptr)
+        argmin[p] = min_index;
+    if (depth != nullptr)
+        depth[p] = (min_index < 2 || main_img[p] < 25) ? 0.0f
+            : depths[min_index];
+}
+
 // WTA with 16 lanes per pixel (sgm_stereo.cc:274-306): lane sub reads planes
 // sub, sub + 16, ...; the first minimum wins through the (value, plane) key.
 __global__ void __launch_bounds__(256)
@@ -1106,23 +1072,9 @@ wta_rows_kernel(const uint16_t *__restrict__ sgm,
     if (p < npix)
         for (int d = sub; d < D; d += 16)
             key = min(key, (uint32_t)sgm[p * D + d] * 256u + (uint32_t)d);
-    uint32_t const ident = 0xFFFFFFFFu;
-#define SMVS_DPP(x, ctrl)                                                     \
-    (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)(x), ctrl, 0xf,   \
-        0xf, false)
-    key = min(key, SMVS_DPP(key, 0x111));
-    key = min(key, SMVS_DPP(key, 0x112));
-    key = min(key, SMVS_DPP(key, 0x114));
-    key = min(key, SMVS_DPP(key, 0x118));
-#undef SMVS_DPP
-    if (sub == 15 && p < npix) {
-        int const min_index = (int)(key & 0xFFu);
-        if (argmin != nullptr)
-            argmin[p] = min_index;
-        if (depth != nullptr)
-            depth[p] = (min_index < 2 || main_img[p] < 25) ? 0.0f
-                : depths[min_index];
-    }
+    key = row_prefix_min_u32(key);
+    if (sub == 15 && p < npix)
+        wta_store(key, p, main_img, depths, depth, argmin);
 }
 
 // S = 8 C + the eight path bytes of the DELTA form, and the winner-takes-all of
@@ -1163,26 +1115,12 @@ sgm_sum_wta_kernel(const uint8_t *__restrict__ cost, const uint8_t *__restrict__
     }
     // minimum over the 32 lanes of the pixel: inside the rows of 16 by DPP
     // shifts, then across the two rows
-    uint32_t const ident = 0xFFFFFFFFu;
-#define SMVS_DPP(x, ctrl)                                                     \
-    (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)(x), ctrl, 0xf,   \
-        0xf, false)
-    key = min(key, SMVS_DPP(key, 0x111));
-    key = min(key, SMVS_DPP(key, 0x112));
-    key = min(key, SMVS_DPP(key, 0x114));
-    key = min(key, SMVS_DPP(key, 0x118));
-#undef SMVS_DPP
+    key = row_prefix_min_u32(key);
     // lanes 15 and 31 of the pixel hold the row minima
     uint32_t const other = (uint32_t)__shfl_xor((int)key, 16);
     key = min(key, other);
-    if (sub == 31 && p < npix) {
-        int const min_index = (int)(key & 0xFFu);
-        if (argmin != nullptr)
-            argmin[p] = min_index;
-        if (depth != nullptr)
-            depth[p] = (min_index < 2 || main_img[p] < 25) ? 0.0f
-                : depths[min_index];
-    }
+    if (sub == 31 && p < npix)
+        wta_store(key, p, main_img, depths, depth, argmin);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1194,498 +1132,39 @@ widen_u8_kernel(const uint8_t *__restrict__ src, uint16_t *__restrict__ dst,
         dst[i] = src[i];
 }
 
-// depth_optimizer.cc:957-1004
-struct BilateralArgs {
-    const float *dm;
-    const float *ci;
-    float *out;
-    int dm_w, dm_h, w, h, channels, kernel_size;
-    float sigma;
-};
+// The counters of the optional per-kernel event timer (SgmProfile,
+// sgm_internal.h; smvs_sgm_profile below): one copy for the whole library, the
+// launches of sgm_view.hip and bilateral.hip report here too.
+std::mutex g_sgm_prof_mutex;
+bool g_sgm_prof_on = false;
+double g_sgm_prof_ms[SMVS_SGM_K_COUNT] = { 0 };
+long long g_sgm_prof_launches[SMVS_SGM_K_COUNT] = { 0 };
 
-__device__ __forceinline__ float
-exp_rounded(float x)
+SgmProfile::SgmProfile()
 {
-    return (float)exp((double)x);
+    std::lock_guard<std::mutex> guard(g_sgm_prof_mutex);
+    on = g_sgm_prof_on;
 }
 
-__global__ void __launch_bounds__(256)
-bilateral_kernel(BilateralArgs A)
+SgmProfile::~SgmProfile()
 {
-#pragma clang fp contract(off)
-    int const x = blockIdx.x * blockDim.x + threadIdx.x;
-    int const y = blockIdx.y;
-    if (x >= A.w)
+    if (pending.empty())
         return;
-    float const scale_x = (float)A.dm_w / (float)A.w;
-    float const scale_y = (float)A.dm_h / (float)A.h;
-    float acc_v = 0.0f, acc_w = 0.0f;
-    for (int ky = -A.kernel_size; ky <= A.kernel_size; ++ky)
-        for (int kx = -A.kernel_size; kx <= A.kernel_size; ++kx) {
-            int const ci_x = min(max(x + kx, 0), A.w - 1);
-            int const ci_y = min(max(y + ky, 0), A.h - 1);
-            float fx = scale_x * (float)ci_x, fy = scale_y * (float)ci_y;
-            fx = fminf(fmaxf(fx, 0.f), (float)A.dm_w - 1.f);
-            fy = fminf(fmaxf(fy, 0.f), (float)A.dm_h - 1.f);
-            int const dm_x = (int)fx, dm_y = (int)fy;
-            float const dv = A.dm[(size_t)dm_y * A.dm_w + dm_x];
-            if (dv == 0.0f)
-                continue;
-            // math::gaussian / gaussian_2d are std::exp on floats: the host's
-            // expf is correctly rounded (glibc), the device's float expf is
-            // not, so the exponential is taken in double and rounded once.
-            // The initial surface then matches the CPU path bit for bit.
-            float weight = 1.0f;
-            weight *= exp_rounded(-((float)kx * (float)kx
-                / (2.0f * A.sigma * A.sigma)
-                + (float)ky * (float)ky / (2.0f * A.sigma * A.sigma)));
-            for (int c = 0; c < A.channels; ++c) {
-                float const diff =
-                    A.ci[((size_t)ci_y * A.w + ci_x) * A.channels + c]
-                    - A.ci[((size_t)y * A.w + x) * A.channels + c];
-                weight *= exp_rounded(-(diff * diff) / (2.0f * 0.1f * 0.1f));
-            }
-            acc_v += dv * weight;
-            acc_w += weight;
+    std::lock_guard<std::mutex> guard(g_sgm_prof_mutex);
+    for (auto &p : pending) {
+        float ms = 0.f;
+        if (hipEventSynchronize(p.b) == hipSuccess
+            && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
+            g_sgm_prof_ms[p.cls] += ms;
+            g_sgm_prof_launches[p.cls] += 1;
         }
-    A.out[(size_t)y * A.w + x] = acc_w > 0 ? acc_v / acc_w : 0.0f;
-}
-
-// The same filter when the guidance image is a byte image divided by 255 (the
-// main image a context holds): the colour weight of a tap is a function of the
-// two bytes only.  The HOST evaluates the reference's own float expression
-// with expf for all 256 x 256 pairs (math::gaussian is std::exp on floats, and
-// glibc's expf is not correctly rounded in ~0.3 % of its arguments, so only the
-// host's own values give the CPU path's weights bit for bit) and compresses
-// them for LDS: the weight depends on the pair almost only through the
-// difference d = tap - centre -- the float rounding of the two quotients
-// leaves at most four distinct values per d -- so the table is 511 x 4 floats
-// plus a 2-bit selector per pair: 24 KB.  No exponential on the device; the
-// spatial weights of the (2 k + 1)^2 taps are kernel arguments.
-constexpr int BIL_MAX_K = 7;
-constexpr int BIL_VALS = 2048;            // 511 differences x 4 candidates (floats)
-constexpr int BIL_SEL = 65536 / 16;       // 2-bit selectors, 16 per word
-constexpr int BIL_TABLE_WORDS = BIL_VALS + BIL_SEL;
-struct BilateralSpatial { float w[(2 * BIL_MAX_K + 1) * (2 * BIL_MAX_K + 1)]; };
-
-// f = (float)b / 255.0f is inverted exactly by rounding f * 255
-__global__ void __launch_bounds__(256)
-float_to_byte_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, size_t n)
-{
-#pragma clang fp contract(off)
-    size_t const i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        out[i] = (uint8_t)(in[i] * 255.0f + 0.5f);
-}
-
-template <int C>
-__global__ void __launch_bounds__(256)
-bilateral_table_kernel(BilateralArgs A, const uint8_t *__restrict__ ci8,
-    const uint32_t *__restrict__ table, BilateralSpatial S)
-{
-#pragma clang fp contract(off)
-    __shared__ uint32_t lds[BIL_TABLE_WORDS];
-    for (int i = threadIdx.x; i < BIL_TABLE_WORDS; i += 256)
-        lds[i] = table[i];
-    __syncthreads();
-    const float *vals = reinterpret_cast<const float *>(lds);
-    const uint32_t *sel = lds + BIL_VALS;
-    int const x = blockIdx.x * blockDim.x + threadIdx.x;
-    int const y = blockIdx.y;
-    if (x >= A.w)
-        return;
-    float const scale_x = (float)A.dm_w / (float)A.w;
-    float const scale_y = (float)A.dm_h / (float)A.h;
-    int const ks = A.kernel_size, kw = 2 * ks + 1;
-    unsigned centre[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-        centre[c] = ci8[((size_t)y * A.w + x) * C + c];
-    float acc_v = 0.0f, acc_w = 0.0f;
-    for (int ky = -ks; ky <= ks; ++ky) {
-        int const ci_y = min(max(y + ky, 0), A.h - 1);
-        float fy = scale_y * (float)ci_y;
-        fy = fminf(fmaxf(fy, 0.f), (float)A.dm_h - 1.f);
-        const float *dm_row = A.dm + (size_t)(int)fy * A.dm_w;
-        const uint8_t *ci_row = ci8 + (size_t)ci_y * A.w * C;
-        for (int kx = -ks; kx <= ks; ++kx) {
-            int const ci_x = min(max(x + kx, 0), A.w - 1);
-            float fx = scale_x * (float)ci_x;
-            fx = fminf(fmaxf(fx, 0.f), (float)A.dm_w - 1.f);
-            float const dv = dm_row[(int)fx];
-            if (dv == 0.0f)
-                continue;
-            float weight = 1.0f;
-            weight *= S.w[(ky + ks) * kw + (kx + ks)];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                unsigned const b = ci_row[ci_x * C + c];
-                unsigned const pair = (centre[c] << 8) | b;
-                unsigned const which = (sel[pair >> 4] >> ((pair & 15u) * 2u)) & 3u;
-                weight *= vals[((b + 255u - centre[c]) << 2) | which];
-            }
-            acc_v += dv * weight;
-            acc_w += weight;
-        }
-    }
-    A.out[(size_t)y * A.w + x] = acc_w > 0 ? acc_v / acc_w : 0.0f;
-}
-
-// The compressed colour-weight table, or nullptr when some difference has
-// more than four distinct weights (another libm: the exponentials are then
-// taken on the device as in bilateral_kernel).
-static const uint32_t *
-bilateral_colour_table(void)
-{
-#pragma clang fp contract(off)
-    static std::vector<uint32_t> table;
-    static bool usable = false;
-    static std::once_flag once;
-    std::call_once(once, []() {
-        std::vector<uint32_t> t(BIL_TABLE_WORDS, 0u);
-        int count[511] = { 0 };
-        bool ok = true;
-        for (int a = 0; a < 256 && ok; ++a)
-            for (int b = 0; b < 256; ++b) {
-                // gaussian(tap - centre, 0.1) as the reference evaluates it on floats
-                float const diff = (float)b / 255.0f - (float)a / 255.0f;
-                float const wgt = expf(-(diff * diff) / (2.0f * 0.1f * 0.1f));
-                uint32_t bits;
-                memcpy(&bits, &wgt, sizeof(bits));
-                int const d = b + 255 - a;
-                int k = 0;
-                while (k < count[d] && t[(size_t)d * 4 + k] != bits)
-                    k += 1;
-                if (k == count[d]) {
-                    if (k == 4) {
-                        ok = false;
-                        break;
-                    }
-                    t[(size_t)d * 4 + k] = bits;
-                    count[d] += 1;
-                }
-                unsigned const pair = ((unsigned)a << 8) | (unsigned)b;
-                t[BIL_VALS + (pair >> 4)] |= (uint32_t)k << ((pair & 15u) * 2u);
-            }
-        usable = ok;
-        table.swap(t);
-    });
-    return usable ? table.data() : nullptr;
-}
-
-// Round 6: the same weights as ONE lookup per tap and channel.  The colour
-// weight of a pair of bytes is symmetric to the bit -- (float)b / 255 - (float)a
-// / 255 changes its sign exactly when the bytes change places, and the weight
-// squares it -- so the table of all pairs is a triangle of 256 x 257 / 2 floats
-// = 131,584 bytes: it fits the CU's 160 KB of LDS whole.  A persistent grid of
-// one workgroup of 1,024 lanes per CU loads it once and walks over the image;
-// per tap and channel: minimum, maximum, the triangle's index, one LDS read (the
-// compressed table above: two dependent LDS reads and twelve vector
-// instructions, and the kernel was bound by both).  Half width BIL_TRI_K (the
-// reference's default, depth_optimizer.h:70-72) with the window's columns
-// unrolled -- the clamped column of the guidance image and the column of the
-// depth map a tap reads are formed once per pixel, not once per tap.  Same taps,
-// same order, same products: the filtered map is array_equal with the oracle's
-// (tests/test_gpu_front.py).  SMVS_BILATERAL=compressed: the kernel above.
-constexpr int BIL_TRI_K = 5;
-constexpr int BIL_TRI_FLOATS = 256 * 257 / 2;
-constexpr int BIL_TRI_THREADS = 1024;
-
-template <int C>
-__global__ void __launch_bounds__(BIL_TRI_THREADS)
-bilateral_triangle_kernel(BilateralArgs A, const uint8_t *__restrict__ ci8,
-    const float *__restrict__ triangle, BilateralSpatial S)
-{
-#pragma clang fp contract(off)
-    extern __shared__ float tri[];
-    for (int i = threadIdx.x; i < BIL_TRI_FLOATS; i += BIL_TRI_THREADS)
-        tri[i] = triangle[i];
-    __syncthreads();
-    constexpr int KS = BIL_TRI_K, KW = 2 * KS + 1;
-    float const scale_x = (float)A.dm_w / (float)A.w;
-    float const scale_y = (float)A.dm_h / (float)A.h;
-    long long const npix = (long long)A.w * A.h;
-    for (long long pix = (long long)blockIdx.x * BIL_TRI_THREADS + threadIdx.x; pix < npix;
-        pix += (long long)gridDim.x * BIL_TRI_THREADS) {
-        int const y = (int)(pix / A.w), x = (int)(pix - (long long)y * A.w);
-        unsigned centre[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-            centre[c] = ci8[(size_t)pix * C + c];
-        // the columns of the window: byte offset in a row of the guidance image,
-        // column of the depth map
-        int col_ci[KW], col_dm[KW];
-#pragma unroll
-        for (int k = 0; k < KW; ++k) {
-            int const ci_x = min(max(x + k - KS, 0), A.w - 1);
-            float fx = scale_x * (float)ci_x;
-            fx = fminf(fmaxf(fx, 0.f), (float)A.dm_w - 1.f);
-            col_ci[k] = ci_x * C;
-            col_dm[k] = (int)fx;
-        }
-        float acc_v = 0.0f, acc_w = 0.0f;
-#pragma unroll 1
-        for (int ky = -KS; ky <= KS; ++ky) {
-            int const ci_y = min(max(y + ky, 0), A.h - 1);
-            float fy = scale_y * (float)ci_y;
-            fy = fminf(fmaxf(fy, 0.f), (float)A.dm_h - 1.f);
-            const float *dm_row = A.dm + (size_t)(int)fy * A.dm_w;
-            const uint8_t *ci_row = ci8 + (size_t)ci_y * A.w * C;
-            const float *sw = S.w + (ky + KS) * KW;
-            // every load of a window row is issued before the first is used, the
-            // bytes of a tap without depth included (a tap was: depth -> branch ->
-            // bytes -> table, three round trips in a row, eleven times per row)
-            float dv[KW];
-            unsigned bytes[KW][C];
-#pragma unroll
-            for (int k = 0; k < KW; ++k) {
-                dv[k] = dm_row[col_dm[k]];
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-                    bytes[k][c] = ci_row[col_ci[k] + c];
-            }
-#pragma unroll
-            for (int k = 0; k < KW; ++k) {
-                float weight = 1.0f;
-                weight *= sw[k];
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    unsigned const b = bytes[k][c];
-                    unsigned const lo = min(b, centre[c]), hi = max(b, centre[c]);
-                    // byte offset 4 (hi (hi + 1) / 2 + lo) = (2 hi) hi + 2 hi + 4 lo:
-                    // a shift, a 24-bit multiply-add, a shift-add
-                    unsigned const h2 = hi << 1;
-                    unsigned t;
-                    asm("v_mad_u32_u24 %0, %1, %2, %1" : "=v"(t) : "v"(h2), "v"(hi));
-                    weight *= *reinterpret_cast<const float *>(
-                        reinterpret_cast<const char *>(tri) + (t + (lo << 2)));
-                }
-                // a tap without depth is skipped by the reference: it adds +0 to
-                // both sums here, which leaves them as they are to the bit (the
-                // sums start at +0 and the weights are positive: never -0)
-                acc_v += dv[k] * weight;
-                acc_w += dv[k] == 0.0f ? 0.0f : weight;
-            }
-        }
-        A.out[pix] = acc_w > 0 ? acc_v / acc_w : 0.0f;
+        (void)hipEventDestroy(p.a);
+        (void)hipEventDestroy(p.b);
     }
 }
 
-// The triangle of colour weights (index hi (hi + 1) / 2 + lo), or nullptr when
-// some pair is not symmetric to the bit (it always is, see above; checked
-// because the bits are the host libm's).
-static const float *
-bilateral_colour_triangle(void)
-{
-#pragma clang fp contract(off)
-    static std::vector<float> table;
-    static bool usable = false;
-    static std::once_flag once;
-    std::call_once(once, []() {
-        std::vector<float> t((size_t)BIL_TRI_FLOATS, 0.0f);
-        bool ok = true;
-        for (int a = 0; a < 256 && ok; ++a)
-            for (int b = 0; b < 256; ++b) {
-                // gaussian(tap - centre, 0.1) as the reference evaluates it on floats
-                float const diff = (float)b / 255.0f - (float)a / 255.0f;
-                float const wgt = expf(-(diff * diff) / (2.0f * 0.1f * 0.1f));
-                int const lo = a < b ? a : b, hi = a < b ? b : a;
-                size_t const at = (size_t)hi * (size_t)(hi + 1) / 2 + (size_t)lo;
-                if (a <= b) {
-                    t[at] = wgt;
-                } else {
-                    // (a > b: the mirrored pair has been stored)
-                    if (std::memcmp(&t[at], &wgt, sizeof(float)) != 0) {
-                        ok = false;
-                        break;
-                    }
-                }
-            }
-        usable = ok;
-        table.swap(t);
-    });
-    return usable ? table.data() : nullptr;
-}
-
-// ------------------------------------------------------- L/R check + merge
-// SGMStereo::reconstruct, sgm_stereo.cc:64-91: the main view's depth is kept
-// where its correspondence in the neighbour (integer pixel coordinates, no
-// +0.5; Correspondence in double from the float M, t) lies inside the 3 %
-// border and the neighbour's own depth agrees within a factor 0.8; truncating
-// lookup.  Operation order of correspondence.cc:20-51, contraction off.
-struct LrArgs {
-    float *d_main;
-    const float *d_neig;
-    int w, h, nw, nh, cut;
-    double M[9], t[3];
-};
-
-__global__ void __launch_bounds__(256)
-sgm_lr_check_kernel(LrArgs A)
-{
-#pragma clang fp contract(off)
-    int const x = blockIdx.x * blockDim.x + threadIdx.x;
-    int const y = blockIdx.y;
-    if (x >= A.w)
-        return;
-    size_t const o = (size_t)y * A.w + x;
-    float const dm = A.d_main[o];
-    if (dm == 0.0f)
-        return;
-    double const u = (double)x, v = (double)y, wd = (double)dm;
-    double const p = A.M[0] * u + A.M[1] * v + A.M[2];
-    double const q = A.M[3] * u + A.M[4] * v + A.M[5];
-    double const r = A.M[6] * u + A.M[7] * v + A.M[8];
-    double const a = wd * p + A.t[0];
-    double const b = wd * q + A.t[1];
-    double const d = wd * r + A.t[2];
-    double const cx = a / d, cy = b / d;
-    if (cx < (double)A.cut || cx >= (double)(A.nw - A.cut)
-        || cy < (double)A.cut || cy >= (double)(A.nh - A.cut)) {
-        A.d_main[o] = 0.0f;
-        return;
-    }
-    float const cdepth = (float)d;
-    float const ndepth = A.d_neig[(size_t)(int)cy * A.nw + (size_t)(int)cx];
-    float const ratio = fminf(cdepth, ndepth) / fmaxf(cdepth, ndepth);
-    if (ndepth == 0.0f || (double)ratio < 0.8)
-        A.d_main[o] = 0.0f;
-}
-
-// app/smvsrecon.cc:366-377: average where both maps are valid
-__global__ void __launch_bounds__(256)
-sgm_merge_kernel(float *__restrict__ d1, const float *__restrict__ d2, size_t n)
-{
-#pragma clang fp contract(off)
-    size_t const i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    float const b = d2[i];
-    if (b == 0.0f)
-        return;
-    float const a = d1[i];
-    d1[i] = a == 0.0f ? b : (a + b) * 0.5f;
-}
-
-// Optional per-kernel timing of the front end (smvs_sgm_profile): HIP events
-// on the workspace's stream around every launch of a call, read back when the
-// call has synchronised.  Off by default: no events, no overhead.
-static std::mutex g_sgm_prof_mutex;
-static bool g_sgm_prof_on = false;
-static double g_sgm_prof_ms[SMVS_SGM_K_COUNT] = { 0 };
-static long long g_sgm_prof_launches[SMVS_SGM_K_COUNT] = { 0 };
-
-struct SgmProfile {
-    struct Pending { int cls; hipEvent_t a, b; };
-    std::vector<Pending> pending;
-    bool on;
-    SgmProfile()
-    {
-        std::lock_guard<std::mutex> guard(g_sgm_prof_mutex);
-        on = g_sgm_prof_on;
-    }
-    // (called when the stream is idle)
-    ~SgmProfile()
-    {
-        if (pending.empty())
-            return;
-        std::lock_guard<std::mutex> guard(g_sgm_prof_mutex);
-        for (auto &p : pending) {
-            float ms = 0.f;
-            if (hipEventSynchronize(p.b) == hipSuccess
-                && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-                g_sgm_prof_ms[p.cls] += ms;
-                g_sgm_prof_launches[p.cls] += 1;
-            }
-            (void)hipEventDestroy(p.a);
-            (void)hipEventDestroy(p.b);
-        }
-    }
-};
-
-struct SgmKernelTimer {
-    SgmProfile *prof;
-    hipStream_t stream;
-    int cls;
-    hipEvent_t a = nullptr, b = nullptr;
-    SgmKernelTimer(SgmProfile *p, hipStream_t s, int c) : prof(p), stream(s), cls(c)
-    {
-        if (prof == nullptr || !prof->on)
-            return;
-        (void)hipEventCreate(&a);
-        (void)hipEventCreate(&b);
-        (void)hipEventRecord(a, stream);
-    }
-    ~SgmKernelTimer()
-    {
-        if (a == nullptr)
-            return;
-        (void)hipEventRecord(b, stream);
-        prof->pending.push_back({ cls, a, b });
-    }
-};
-
-// Slots of a pooled workspace (pool.hip) used by this file.
-enum {
-    WS_DEPTHS = 0, WS_CENSUS, WS_WARPED, WS_COST, WS_SGM, WS_ARGMIN,   // one run_sgm
-    WS_MAIN, WS_NBR0, WS_NBR1, WS_FWD0, WS_FWD1, WS_BWD, WS_COST16,   // a view's front end
-    WS_RAW, WS_RAW0, WS_RAW1,                                         // raw u8 images + scratch
-    WS_BIL_DM, WS_BIL_CI, WS_BIL_OUT,                                 // bilateral upsample
-    WS_DELTA                                                          // eight path-byte volumes
-};
-
-// Work buffers of one run_sgm inside a pooled workspace; reused by the runs of
-// a view (the runs are ordered on the workspace's stream).  Every run has its
-// own depth table.
-struct SgmWorkspace {
-    static constexpr int MAX_RUNS = 4;
-    Workspace *ws;
-    SgmProfile *prof = nullptr;
-    float *depths = nullptr;
-    unsigned long long *census = nullptr;
-    uint8_t *warped = nullptr, *cost = nullptr;
-    uint16_t *sgm = nullptr;     // S: only when the caller wants it or the DELTA form does not apply
-    uint8_t *delta = nullptr;    // the eight path-byte volumes of the DELTA form
-    int32_t *argmin = nullptr;
-    int runs = 0;
-    bool want_sgm = false;       // smvs_sgm_run hands the S volume to its caller
-    explicit SgmWorkspace(Workspace *w) : ws(w) {}
-    // penalty2 <= 255: L - C fits a byte; planes in fours: the u32 accesses of
-    // sgm_sum_wta_kernel
-    static bool delta_form(int num_steps, unsigned penalty2)
-    {
-        return (num_steps % 4) == 0 && penalty2 <= 255u;
-    }
-    // the largest penalty2 a step can use: the option itself, or in the adaptive
-    // mode max(P2 / diff, P1 * 3 / 2) <= max(P2, P1 * 3 / 2)
-    static unsigned largest_penalty2(unsigned penalty1, unsigned penalty2, int p2_mode)
-    {
-        unsigned const floor_value = penalty1 * 3u / 2u;
-        return p2_mode == SMVS_SGM_P2_ADAPTIVE && floor_value > penalty2 ? floor_value
-                                                                        : penalty2;
-    }
-    int ensure(size_t npix, int num_steps, unsigned penalty2)
-    {
-        size_t const vol = npix * (size_t)num_steps;
-        bool const df = delta_form(num_steps, penalty2);
-        int rc;
-        if ((rc = ws->ensure(WS_DEPTHS, (size_t)128 * MAX_RUNS, &depths))
-            || (rc = ws->ensure(WS_CENSUS, npix, &census))
-            || (rc = ws->ensure(WS_WARPED, vol, &warped))
-            || (rc = ws->ensure(WS_COST, vol, &cost))
-            || (rc = ws->ensure(WS_ARGMIN, npix, &argmin)))
-            return rc;
-        if (df && (rc = ws->ensure(WS_DELTA, 8 * vol, &delta)))
-            return rc;
-        if ((!df || want_sgm) && (rc = ws->ensure(WS_SGM, vol, &sgm)))
-            return rc;
-        return SMVS_OK;
-    }
-};
-
-// The penalties alone (no device involved: the *_mode entries call this before
-// anything else).
-static int
+// (declared in sgm_internal.h)
+int
 check_sgm_penalties(unsigned penalty1, unsigned penalty2, int p2_mode)
 {
     SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
@@ -1731,9 +1210,8 @@ check_sgm_options(int num_steps, float min_depth, float max_depth,
     return check_sgm_penalties(penalty1, penalty2, p2_mode);
 }
 
-// SGMStereo::run_sgm (sgm_stereo.cc:98-124) on device images; the depth map
-// (and optionally argmin) stay on the device.  Asynchronous on `stream`.
-static int
+// (declared in sgm_internal.h)
+int
 sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     int w, int h, const uint8_t *d_nbr, int nw, int nh, const float *M,
     const float *t, float min_depth, float max_depth, int num_steps,
@@ -1807,10 +1285,6 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     }
     SMVS_HIP_CHECK(hipGetLastError());
 
-    // the eight paths in the reference's order: ->, <-, then the three
-    // top-to-bottom paths, then the three bottom-to-top paths
-    static const int dirs[8][2] = { { 1, 0 }, { -1, 0 }, { 0, 1 }, { 1, 1 },
-        { -1, 1 }, { 0, -1 }, { 1, -1 }, { -1, -1 } };
     PathArgs P;
     P.cost = B.cost;
     P.sgm = B.sgm;
@@ -1832,8 +1306,7 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     if (df && (num_steps & 3) == 0 && num_steps <= 128 && !wave_per_line) {
         P.dx = P.dy = 0;
         P.first = 0;
-        int const nd = w + h - 1;
-        int const pairs = 2 * ((h + 1) / 2) + 2 * ((w + 1) / 2) + 4 * ((nd + 1) / 2);
+        int const pairs = sgm_grid_line_pairs(w, h);
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_PATHS);
         if (adapt && num_steps == 128)
             hipLaunchKernelGGL((sgm_paths2_kernel<8, true, true>), dim3(pairs), dim3(64), 0, stream, P);
@@ -1846,7 +1319,7 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     } else if (df) {
         P.dx = P.dy = 0;
         P.first = 0;
-        int const lines = 2 * h + 2 * w + 4 * (w + h - 1);
+        int const lines = sgm_grid_lines(w, h);
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_PATHS);
         if (adapt)
             hipLaunchKernelGGL((sgm_all_paths_kernel<16, true, true>), dim3(lines), dim3(64),
@@ -1858,7 +1331,7 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
         SMVS_HIP_CHECK(hipMemsetAsync(B.sgm, 0, sizeof(uint16_t) * vol, stream));
         P.dx = P.dy = 0;
         P.first = 0;
-        int const lines = 2 * h + 2 * w + 4 * (w + h - 1);
+        int const lines = sgm_grid_lines(w, h);
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_PATHS);
         if (adapt)
             hipLaunchKernelGGL((sgm_all_paths_kernel<16, false, true>), dim3(lines), dim3(64),
@@ -1870,10 +1343,10 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_PATHS);
         // odd plane counts: one launch per direction, scalar accesses
         for (int k = 0; k < 8; ++k) {
-            P.dx = dirs[k][0];
-            P.dy = dirs[k][1];
+            P.dx = SGM_DIRS[k][0];
+            P.dy = SGM_DIRS[k][1];
             P.first = k == 0 ? 1 : 0;
-            int const lines = P.dy == 0 ? h : (P.dx == 0 ? w : w + h - 1);
+            int const lines = sgm_dir_lines(k, w, h);
             if (adapt)
                 hipLaunchKernelGGL(sgm_path_kernel<true>, dim3(lines), dim3(64), 0, stream,
                     P);
@@ -1982,769 +1455,6 @@ smvs_sgm_run_mode(int device, const uint8_t *main_img, int w, int h,
 {
     return sgm_run_impl(device, main_img, w, h, neighbor_img, nw, nh, M, t, min_depth,
         max_depth, num_steps, penalty1, penalty2, p2_mode, depth, argmin, cost, sgm);
-}
-
-// StereoView::get_byte_image (desaturate<uint8_t>, stereo_view.cc:86-95
-// [MVE-unverified]: 0.21 r + 0.72 g + 0.07 b + 0.5, truncated) on the device
-__global__ void __launch_bounds__(256)
-sgm_desaturate_kernel(const uint8_t *__restrict__ in, size_t npix, int channels,
-    uint8_t *__restrict__ out)
-{
-#pragma clang fp contract(off)
-    size_t const p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= npix)
-        return;
-    if (channels < 3) {
-        out[p] = in[p * channels];
-        return;
-    }
-    float const v = (float)in[p * channels] * 0.21f + (float)in[p * channels + 1] * 0.72f
-        + (float)in[p * channels + 2] * 0.07f + 0.5f;
-    out[p] = (uint8_t)v;
-}
-
-// mve::image::rescale_half_size<uint8_t> (sgm_stereo.cc:31-39 [MVE-unverified]):
-// mean of the 2 x 2 block (odd sizes repeat the last row / column), + 0.5, truncated
-__global__ void __launch_bounds__(256)
-sgm_half_size_kernel(const uint8_t *__restrict__ in, int w, int h,
-    uint8_t *__restrict__ out)
-{
-#pragma clang fp contract(off)
-    int const ow = (w + 1) >> 1, oh = (h + 1) >> 1;
-    int const x = blockIdx.x * blockDim.x + threadIdx.x;
-    int const y = blockIdx.y;
-    if (x >= ow || y >= oh)
-        return;
-    int const x0 = 2 * x, x1 = min(2 * x + 1, w - 1);
-    int const y0 = 2 * y, y1 = min(2 * y + 1, h - 1);
-    float const v = (float)in[(size_t)y0 * w + x0] * 0.25f
-        + (float)in[(size_t)y0 * w + x1] * 0.25f
-        + (float)in[(size_t)y1 * w + x0] * 0.25f
-        + (float)in[(size_t)y1 * w + x1] * 0.25f;
-    out[(size_t)y * ow + x] = (uint8_t)(v + 0.5f);
-}
-
-// mve::image::rescale_half_size_gaussian<uint8_t>(img, sigma2 = 0.75f)
-// [MVE-unverified M29], the input scaling of app/smvsrecon.cc:634-647, with the
-// bits of the host mirror's loop (host/scene_io.cc, rescale_half_size_gaussian):
-// interleaved u8 [h][w][C] -> ((w + 1) / 2, (h + 1) / 2, C); output (x, y) reads
-// the rows max(0, 2y - 1), 2y, min(h - 1, 2y + 1), min(h - 1, 2y + 2) and the
-// columns by the same rule.
-//
-// What makes the result the host's, bit for bit:
-//   weights       w1, w2, w3 are kernel arguments: the host's std::exp values,
-//                 never expf on the device;
-//   weight sum    clamping changes which byte a tap reads, not which weight it
-//                 adds, so the sum of the sixteen weights is the same at every
-//                 position: formed once on the host in the loop's order (wsum);
-//   contraction   off: every product is rounded before it is added;
-//   order         v = 0, then += (float)byte * weight over the rows and inside
-//                 a row over the columns, one chain of sixteen float adds;
-//   division      __fdiv_rn: the correctly rounded IEEE quotient (v_div_scale /
-//                 v_div_fmas / v_div_fixup), whatever the translation unit's
-//                 fast-math or -fhip-fp32-correctly-rounded-divide-sqrt setting;
-//   rounding      half away from zero as the host writes it (floor(q + 0.5) for
-//                 q > 0, else ceil(q - 0.5)), then the cast to u8.
-//
-// A workgroup makes an output tile of TX x RHG_TY pixels, TX * C <= 256 bytes
-// wide.  Its input -- 2 TX + 2 columns by 2 RHG_TY + 2 rows, the tile times two
-// plus the apron of one pixel before and two behind -- is staged in LDS with
-// aligned dword loads along the interleaved rows, so that a byte comes from HBM
-// once (1 / 64 + 1 / 16 more for the aprons, which the L2 serves).  A row of the
-// image starts at any byte, so row r of the tile is stored from the aligned
-// dword below its first byte and read back with that row's shift (0..3).  The
-// taps are LDS byte reads; neighbouring lanes make neighbouring output dwords,
-// 8 input bytes apart: lanes l and l + 16 of a half wave meet on a bank (2-way).
-// Each thread makes one aligned dword of an output row and stores it whole; the
-// dwords a tile shares with its neighbour or with the next row (the first and
-// the last of a row segment) are stored byte by byte.
-constexpr int RHG_TY = 16;
-constexpr int RHG_PITCH_DW = 132;   // (2 * 64 + 2) * 4 bytes + 3 of shift, in dwords
-template <int C> struct RhgTile { static constexpr int TX = C == 1 ? 256 : C == 2 ? 128 : 64; };
-
-struct RhgArgs {
-    const uint8_t *in;     // 4-byte aligned, readable up to the dword that holds the last byte
-    uint8_t *out;          // 4-byte aligned
-    int w, h, ow, oh;
-    float w1, w2, w3, wsum;
-};
-
-template <int C>
-__global__ void __launch_bounds__(256)
-rescale_half_gaussian_u8_kernel(RhgArgs A)
-{
-#pragma clang fp contract(off)
-    constexpr int TX = RhgTile<C>::TX;
-    constexpr int OUT_DW = TX * C / 4 + 1;   // dwords a row segment of the tile can touch
-    __shared__ uint32_t tile[(2 * RHG_TY + 2) * RHG_PITCH_DW];
-    int const tid = threadIdx.x;
-    int const tx0 = blockIdx.x * TX, ty0 = blockIdx.y * RHG_TY;
-    int const tx1 = min(tx0 + TX, A.ow), ty1 = min(ty0 + RHG_TY, A.oh);   // exclusive
-    // staged input pixels [xin0, xin1] x [yin0, yin1]
-    int const xin0 = max(0, 2 * tx0 - 1), xin1 = min(A.w - 1, 2 * tx1);
-    int const yin0 = max(0, 2 * ty0 - 1), yin1 = min(A.h - 1, 2 * ty1);
-    int const nrows = yin1 - yin0 + 1;
-    int const nbytes = (xin1 - xin0 + 1) * C;          // <= (2 TX + 2) C <= 520
-    size_t const rowbytes = (size_t)A.w * C;
-    size_t const in_dwords = (rowbytes * (size_t)A.h + 3) >> 2;
-    const uint32_t *in32 = reinterpret_cast<const uint32_t *>(A.in);
-    for (int idx = tid; idx < nrows * RHG_PITCH_DW; idx += 256) {
-        int const r = idx / RHG_PITCH_DW, d = idx - r * RHG_PITCH_DW;
-        size_t const first = (size_t)(yin0 + r) * rowbytes + (size_t)xin0 * C;
-        size_t const dw = (first >> 2) + (size_t)d;
-        // (the dwords that hold bytes of this row of the tile, inside the buffer)
-        if (dw <= ((first + (size_t)nbytes - 1) >> 2) && dw < in_dwords)
-            tile[idx] = in32[dw];
-    }
-    __syncthreads();
-    const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
-    int const shift_mul = (int)(rowbytes & 3), shift_add = (xin0 * C) & 3;
-    size_t const orow = (size_t)A.ow * C;
-    float const wk[4] = { A.w2, A.w1, A.w1, A.w2 };   // rows 1, 2; rows 0, 3 below
-    float const we[4] = { A.w3, A.w2, A.w2, A.w3 };
-    for (int idx = tid; idx < (ty1 - ty0) * OUT_DW; idx += 256) {
-        int const yy = idx / OUT_DW, q = idx - yy * OUT_DW;
-        int const y = ty0 + yy;
-        size_t const row0 = (size_t)y * orow;
-        size_t const gs = row0 + (size_t)tx0 * C, ge = row0 + (size_t)tx1 * C;
-        size_t const g0 = ((gs >> 2) + (size_t)q) << 2;
-        if (g0 >= ge)
-            continue;
-        // LDS byte offsets of the four input rows
-        int rowoff[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int const yi = min(A.h - 1, max(0, 2 * y - 1 + r));
-            rowoff[r] = (yi - yin0) * (RHG_PITCH_DW * 4)
-                + ((((yi & 3) * shift_mul) + shift_add) & 3);
-        }
-        uint32_t packed = 0;
-        bool all = true;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            size_t const g = g0 + (size_t)b;
-            bool const valid = g >= gs && g < ge;
-            all = all && valid;
-            if (!valid)
-                continue;
-            int const j = (int)(g - row0);
-            int const x = j / C, ch = j - x * C;
-            int coloff[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                coloff[k] = (min(A.w - 1, max(0, 2 * x - 1 + k)) - xin0) * C + ch;
-            float v = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    v += (float)tb[rowoff[r] + coloff[k]]
-                        * ((r == 0 || r == 3) ? we[k] : wk[k]);
-            float const quot = __fdiv_rn(v, A.wsum);
-            uint8_t const byte = (uint8_t)(quot > 0.0f ? floorf(quot + 0.5f)
-                                                       : ceilf(quot - 0.5f));
-            packed |= (uint32_t)byte << (8 * b);
-        }
-        if (all) {
-            *reinterpret_cast<uint32_t *>(A.out + g0) = packed;
-        } else {
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-                if (g0 + (size_t)b >= gs && g0 + (size_t)b < ge)
-                    A.out[g0 + (size_t)b] = (uint8_t)(packed >> (8 * b));
-        }
-    }
-}
-
-// The levels an image of w x h goes through in `halvings` steps; false when a
-// level's input is narrower or lower than 2 (the host function's "image too
-// small").  *ow / *oh: the last level's size.
-static bool
-rescale_half_gaussian_sizes(int w, int h, int halvings, int *ow, int *oh)
-{
-    for (int i = 0; i < halvings; ++i) {
-        if (w < 2 || h < 2)
-            return false;
-        w = (w + 1) >> 1;
-        h = (h + 1) >> 1;
-    }
-    *ow = w;
-    *oh = h;
-    return true;
-}
-
-// app/smvsrecon.cc:634-647: `halvings` chained rescale_half_size_gaussian of one
-// image; the levels ping-pong between two slots of the workspace
-extern "C" int
-smvs_rescale_half_gaussian(int device, const uint8_t *pixels, int width, int height,
-    int channels, int halvings, uint8_t *out, size_t out_capacity, int *out_width,
-    int *out_height)
-{
-    SMVS_REQUIRE(pixels && out && out_width && out_height, "null argument");
-    SMVS_REQUIRE(halvings >= 1 && halvings <= 30, "halvings must be in [1, 30]");
-    SMVS_REQUIRE(channels >= 1 && channels <= 4, "1 to 4 channels");
-    SMVS_REQUIRE(width <= (1 << 20) && height <= (1 << 20)
-        && (width < 1 || height < 1
-            || (size_t)width * (size_t)height * (size_t)channels <= ((size_t)1 << 31)),
-        "image too large");
-    int fw = 0, fh = 0;
-    SMVS_REQUIRE(rescale_half_gaussian_sizes(width, height, halvings, &fw, &fh),
-        "image too small");
-    size_t const out_bytes = (size_t)fw * fh * channels;
-    SMVS_REQUIRE(out_capacity >= out_bytes, "output buffer too small");
-    // the host's weights and their sum in the host loop's order (scene_io.cc)
-    float const sigma2 = 0.75f;
-    float const w1 = std::exp(-0.5f / (2.0f * sigma2));
-    float const w2 = std::exp(-2.5f / (2.0f * sigma2));
-    float const w3 = std::exp(-4.5f / (2.0f * sigma2));
-    float const wrow[4][4] = { { w3, w2, w2, w3 }, { w2, w1, w1, w2 },
-        { w2, w1, w1, w2 }, { w3, w2, w2, w3 } };
-    float wsum = 0.0f;
-    {
-#pragma clang fp contract(off)
-        for (int r = 0; r < 4; ++r)
-            for (int k = 0; k < 4; ++k)
-                wsum += wrow[r][k];
-    }
-    WorkspaceLease lease(device);
-    if (lease.w == nullptr)
-        return SMVS_ERR_HIP;
-    Workspace &ws = *lease.w;
-    int rc;
-    size_t const in_bytes = (size_t)width * height * channels;
-    size_t const half_bytes = (size_t)((width + 1) >> 1) * ((height + 1) >> 1) * channels;
-    uint8_t *cur = nullptr, *other = nullptr;
-    // (whole dwords: the kernel loads the dword that holds a level's last byte)
-    if ((rc = ws.ensure(WS_RAW, (in_bytes + 3) & ~(size_t)3, &cur))
-        || (rc = ws.ensure(WS_RAW0, (half_bytes + 3) & ~(size_t)3, &other))
-        || (rc = ws.upload(cur, pixels, in_bytes)))
-        return rc;
-    int cw = width, ch = height;
-    for (int i = 0; i < halvings; ++i) {
-        RhgArgs A;
-        A.in = cur;
-        A.out = other;
-        A.w = cw;
-        A.h = ch;
-        A.ow = (cw + 1) >> 1;
-        A.oh = (ch + 1) >> 1;
-        A.w1 = w1;
-        A.w2 = w2;
-        A.w3 = w3;
-        A.wsum = wsum;
-        unsigned const gy = (unsigned)((A.oh + RHG_TY - 1) / RHG_TY);
-        switch (channels) {
-        case 1:
-            hipLaunchKernelGGL(rescale_half_gaussian_u8_kernel<1>,
-                dim3((unsigned)((A.ow + RhgTile<1>::TX - 1) / RhgTile<1>::TX), gy), dim3(256),
-                0, ws.stream, A);
-            break;
-        case 2:
-            hipLaunchKernelGGL(rescale_half_gaussian_u8_kernel<2>,
-                dim3((unsigned)((A.ow + RhgTile<2>::TX - 1) / RhgTile<2>::TX), gy), dim3(256),
-                0, ws.stream, A);
-            break;
-        case 3:
-            hipLaunchKernelGGL(rescale_half_gaussian_u8_kernel<3>,
-                dim3((unsigned)((A.ow + RhgTile<3>::TX - 1) / RhgTile<3>::TX), gy), dim3(256),
-                0, ws.stream, A);
-            break;
-        default:
-            hipLaunchKernelGGL(rescale_half_gaussian_u8_kernel<4>,
-                dim3((unsigned)((A.ow + RhgTile<4>::TX - 1) / RhgTile<4>::TX), gy), dim3(256),
-                0, ws.stream, A);
-            break;
-        }
-        SMVS_HIP_CHECK(hipGetLastError());
-        uint8_t *t = cur; cur = other; other = t;
-        cw = A.ow;
-        ch = A.oh;
-    }
-    if ((rc = ws.download(out, cur, out_bytes)) != SMVS_OK)
-        return rc;
-    *out_width = cw;
-    *out_height = ch;
-    return SMVS_OK;
-}
-
-// One view's SGM input image on the device: upload (raw: interleaved u8 of
-// `channels`; otherwise already at SGM scale, one channel), desaturate and
-// `halvings` half-size steps.  *out (slot `slot_out`) receives the image,
-// *ow / *oh its size.
-static int
-sgm_prepare_image(Workspace &ws, const uint8_t *host, int w, int h, int channels,
-    int halvings, int slot_out, int slot_tmp, uint8_t **out, int *ow, int *oh)
-{
-    int rc;
-    size_t const npix = (size_t)w * h;
-    uint8_t *a = nullptr, *b = nullptr;
-    if (channels == 1 && halvings == 0) {
-        if ((rc = ws.ensure(slot_out, npix, &a)) || (rc = ws.upload(a, host, npix)))
-            return rc;
-        *out = a;
-        *ow = w;
-        *oh = h;
-        return SMVS_OK;
-    }
-    // raw bytes into the scratch slot, results ping-pong between the two
-    if ((rc = ws.ensure(slot_tmp, npix * (size_t)channels + npix, &b))
-        || (rc = ws.ensure(slot_out, npix, &a))
-        || (rc = ws.upload(b, host, npix * (size_t)channels)))
-        return rc;
-    uint8_t *grey = b + npix * (size_t)channels;   // behind the raw bytes
-    hipLaunchKernelGGL(sgm_desaturate_kernel, dim3((unsigned)((npix + 255) / 256)),
-        dim3(256), 0, ws.stream, b, npix, channels, halvings % 2 == 0 ? a : grey);
-    uint8_t *cur = halvings % 2 == 0 ? a : grey;
-    uint8_t *other = halvings % 2 == 0 ? grey : a;
-    int cw = w, ch = h;
-    for (int i = 0; i < halvings; ++i) {
-        int const nw = (cw + 1) >> 1, nh = (ch + 1) >> 1;
-        hipLaunchKernelGGL(sgm_half_size_kernel, dim3((nw + 255) / 256, nh), dim3(256), 0,
-            ws.stream, cur, cw, ch, other);
-        uint8_t *t = cur; cur = other; other = t;
-        cw = nw;
-        ch = nh;
-    }
-    SMVS_HIP_CHECK(hipGetLastError());
-    // (an even number of swaps ends in `a` when it started there, an odd one
-    // when it started in `grey`: cur == a by construction)
-    *out = cur;
-    *ow = cw;
-    *oh = ch;
-    return SMVS_OK;
-}
-
-// reconstruct_sgm_depth_for_view on prepared device images
-static int
-sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
-    int main_channels, const smvs_sgm_neighbor *neighbors,
-    const int *neighbor_channels, int n_neighbors, int halvings, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth)
-{
-    SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
-        "unknown penalty2 mode");
-    if (p2_mode != SMVS_SGM_P2_CONSTANT) {
-        int const prc = check_sgm_penalties(penalty1, penalty2, p2_mode);
-        if (prc != SMVS_OK)
-            return prc;
-    }
-    SMVS_REQUIRE(main_img && neighbors && depth, "null argument");
-    SMVS_REQUIRE(n_neighbors >= 1 && n_neighbors <= 2,
-        "one or two neighbours (app/smvsrecon.cc:360-365)");
-    SMVS_REQUIRE(halvings >= 0 && halvings <= 8, "halvings out of range");
-    SMVS_REQUIRE((w >> halvings) > 10 && (h >> halvings) > 8, "image too small");
-    for (int k = 0; k < n_neighbors; ++k)
-        SMVS_REQUIRE(neighbors[k].image && (neighbors[k].width >> halvings) > 10
-            && (neighbors[k].height >> halvings) > 8, "bad neighbour image");
-    int rc;
-    WorkspaceLease lease(device);
-    if (lease.w == nullptr)
-        return SMVS_ERR_HIP;
-    Workspace &ws = *lease.w;
-    hipStream_t const stream = ws.stream;
-    SgmProfile prof;
-    SgmWorkspace B(&ws);
-    B.prof = &prof;
-    // the SGM-scale images (every buffer before the first SGM launch: growing
-    // one waits for the stream)
-    uint8_t *d_main = nullptr, *d_nbr[2] = { nullptr, nullptr };
-    int mw = 0, mh = 0, nw[2] = { 0, 0 }, nh[2] = { 0, 0 };
-    if ((rc = sgm_prepare_image(ws, main_img, w, h, main_channels, halvings, WS_MAIN,
-             WS_RAW, &d_main, &mw, &mh)) != SMVS_OK)
-        return rc;
-    for (int k = 0; k < n_neighbors; ++k)
-        if ((rc = sgm_prepare_image(ws, neighbors[k].image, neighbors[k].width,
-                 neighbors[k].height, neighbor_channels != nullptr ? neighbor_channels[k] : 1,
-                 halvings, k == 0 ? WS_NBR0 : WS_NBR1, k == 0 ? WS_RAW0 : WS_RAW1,
-                 &d_nbr[k], &nw[k], &nh[k])) != SMVS_OK)
-            return rc;
-    size_t const npix = (size_t)mw * mh;
-    float *d_fwd[2] = { nullptr, nullptr }, *d_bwd = nullptr;
-    size_t max_nnpix = 0;
-    for (int k = 0; k < n_neighbors; ++k) {
-        size_t const nnpix = (size_t)nw[k] * nh[k];
-        max_nnpix = nnpix > max_nnpix ? nnpix : max_nnpix;
-        if ((rc = ws.ensure(k == 0 ? WS_FWD0 : WS_FWD1, npix, &d_fwd[k])))
-            return rc;
-    }
-    if ((rc = ws.ensure(WS_BWD, max_nnpix, &d_bwd))
-        || (rc = B.ensure(npix > max_nnpix ? npix : max_nnpix, num_steps,
-                SgmWorkspace::largest_penalty2(penalty1, penalty2, p2_mode))))
-        return rc;
-    for (int k = 0; k < n_neighbors; ++k) {
-        smvs_sgm_neighbor const &N = neighbors[k];
-        // SGMStereo::reconstruct, sgm_stereo.cc:46-62: main -> neighbour,
-        // then neighbour -> main with the neighbour's own depth range
-        if ((rc = sgm_run_device(B, d_main, mw, mh, d_nbr[k], nw[k], nh[k],
-                N.M_fwd, N.t_fwd, N.range_main[0], N.range_main[1], num_steps,
-                penalty1, penalty2, p2_mode, d_fwd[k])) != SMVS_OK)
-            return rc;
-        if ((rc = sgm_run_device(B, d_nbr[k], nw[k], nh[k], d_main, mw, mh,
-                N.M_bwd, N.t_bwd, N.range_neighbor[0], N.range_neighbor[1],
-                num_steps, penalty1, penalty2, p2_mode, d_bwd)) != SMVS_OK)
-            return rc;
-        LrArgs L;
-        L.d_main = d_fwd[k];
-        L.d_neig = d_bwd;
-        L.w = mw;
-        L.h = mh;
-        L.nw = nw[k];
-        L.nh = nh[k];
-        L.cut = (int)(0.03 * (double)(nw[k] > nh[k] ? nw[k] : nh[k]));
-        for (int i = 0; i < 9; ++i)
-            L.M[i] = (double)N.M_fwd[i];
-        for (int i = 0; i < 3; ++i)
-            L.t[i] = (double)N.t_fwd[i];
-        {
-            SgmKernelTimer timer(&prof, stream, SMVS_SGM_K_LR_CHECK);
-            hipLaunchKernelGGL(sgm_lr_check_kernel, dim3((mw + 255) / 256, mh),
-                dim3(256), 0, stream, L);
-        }
-        SMVS_HIP_CHECK(hipGetLastError());
-    }
-    if (n_neighbors > 1) {
-        SgmKernelTimer timer(&prof, stream, SMVS_SGM_K_MERGE);
-        hipLaunchKernelGGL(sgm_merge_kernel, dim3((unsigned)((npix + 255) / 256)),
-            dim3(256), 0, stream, d_fwd[0], d_fwd[1], npix);
-        SMVS_HIP_CHECK(hipGetLastError());
-    }
-    return ws.download(depth, d_fwd[0], sizeof(float) * npix);
-}
-
-extern "C" int
-smvs_sgm_depth_for_view(int device, const uint8_t *main_img, int w, int h,
-    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, float *depth)
-{
-    return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
-        n_neighbors, 0, num_steps, penalty1, penalty2, SMVS_SGM_P2_CONSTANT, depth);
-}
-
-// sgm_stereo.cc:310-346 with p2_mode = SMVS_SGM_P2_ADAPTIVE
-extern "C" int
-smvs_sgm_depth_for_view_mode(int device, const uint8_t *main_img, int w, int h,
-    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth)
-{
-    return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
-        n_neighbors, 0, num_steps, penalty1, penalty2, p2_mode, depth);
-}
-
-extern "C" int
-smvs_sgm_depth_for_view_raw(int device, const uint8_t *main_img, int w, int h,
-    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
-    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
-    uint16_t penalty2, float *depth)
-{
-    return smvs_sgm_depth_for_view_raw_mode(device, main_img, w, h, channels, neighbors,
-        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2,
-        SMVS_SGM_P2_CONSTANT, depth);
-}
-
-// sgm_stereo.cc:310-346 with p2_mode = SMVS_SGM_P2_ADAPTIVE
-extern "C" int
-smvs_sgm_depth_for_view_raw_mode(int device, const uint8_t *main_img, int w, int h,
-    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
-    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
-    uint16_t penalty2, int p2_mode, float *depth)
-{
-    SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
-        "unknown penalty2 mode");
-    SMVS_REQUIRE(channels == 1 || channels == 3, "1 or 3 channels");
-    SMVS_REQUIRE(neighbor_channels != nullptr, "null argument");
-    for (int k = 0; k < n_neighbors && k < 2; ++k)
-        SMVS_REQUIRE(neighbor_channels[k] == 1 || neighbor_channels[k] == 3,
-            "1 or 3 channels");
-    return sgm_depth_for_view_impl(device, main_img, w, h, channels, neighbors,
-        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, p2_mode,
-        depth);
-}
-
-extern "C" int
-smvs_bilateral_upsample(int device, const float *dm, int dm_w, int dm_h,
-    const float *ci, int w, int h, int channels, float sigma, int kernel_size,
-    float *out)
-{
-    SMVS_REQUIRE(dm && ci && out, "null argument");
-    SMVS_REQUIRE(dm_w > 0 && dm_h > 0 && w > 0 && h > 0 && channels > 0
-        && kernel_size >= 0 && sigma > 0.f, "bad argument");
-    WorkspaceLease lease(device);
-    if (lease.w == nullptr)
-        return SMVS_ERR_HIP;
-    Workspace &ws = *lease.w;
-    float *d_dm = nullptr, *d_ci = nullptr, *d_out = nullptr;
-    int rc;
-    size_t const n = (size_t)w * h;
-    if ((rc = ws.ensure(WS_BIL_DM, (size_t)dm_w * dm_h, &d_dm))
-        || (rc = ws.ensure(WS_BIL_CI, n * channels, &d_ci))
-        || (rc = ws.ensure(WS_BIL_OUT, n, &d_out))
-        || (rc = ws.upload(d_dm, dm, sizeof(float) * dm_w * dm_h))
-        || (rc = ws.upload(d_ci, ci, sizeof(float) * n * channels)))
-        return rc;
-    BilateralArgs A;
-    A.dm = d_dm;
-    A.ci = d_ci;
-    A.out = d_out;
-    A.dm_w = dm_w;
-    A.dm_h = dm_h;
-    A.w = w;
-    A.h = h;
-    A.channels = channels;
-    A.kernel_size = kernel_size;
-    A.sigma = sigma;
-    SgmProfile prof;
-    {
-        SgmKernelTimer timer(&prof, ws.stream, SMVS_SGM_K_BILATERAL);
-        hipLaunchKernelGGL(bilateral_kernel, dim3((w + 255) / 256, h), dim3(256), 0,
-            ws.stream, A);
-    }
-    SMVS_HIP_CHECK(hipGetLastError());
-    return ws.download(out, d_out, sizeof(float) * n);
-}
-
-// The same filter for a view whose context already holds the main image
-// (smvs_ctx_upload_image): guided by that image, and the full-size result
-// stays on the device as the depth map the visibility tests of
-// smvs_topology_subviews compare with (lib/depth_optimizer.cc:35-51 hands the
-// filtered map to both).  Saves the upload of the float image (25 MB at
-// 1920 x 1080 x 3) and of the result, once per topology pass.
-// The low-resolution SGM map from page-locked host memory (read over the bus)
-// to the device.  from_mve: the map is the view's "smvs-sgm" embedding as
-// StereoView::write_depth_to_view stored it (MVE's ray-length convention) and is
-// turned into z-depth on the way -- mve::image::depthmap_convert_conventions
-// with the float operations of host/stereo_view.cc (StereoView::get_sgm_depth,
-// stereo_view.h:121-135), so the same bits as the host conversion.
-struct SgmMapUpload {
-    const float *src;
-    float *dst;
-    int w, h;
-    int from_mve;
-    float invproj[9];
-};
-
-__global__ void __launch_bounds__(256)
-sgm_map_upload_kernel(SgmMapUpload A)
-{
-#pragma clang fp contract(off)
-    size_t const i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)A.w * A.h)
-        return;
-    float d = A.src[i];
-    if (A.from_mve != 0) {
-        int const y = (int)(i / (size_t)A.w), x = (int)(i - (size_t)y * A.w);
-        float const px = (float)x + 0.5f, py = (float)y + 0.5f;
-        float v[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            v[r] = A.invproj[3 * r] * px + A.invproj[3 * r + 1] * py + A.invproj[3 * r + 2];
-        float const len = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        // `double len = px.norm(); dm *= 1.0 / len` [MVE-unverified, M10]
-        double const len_d = (double)len;
-        // (from_mve == 2: the map is still the z-depth the SGM front end produced;
-        // the view would store it as ray length first -- write_depth_to_view,
-        // `dm *= len` -- and the reference reads it back through that embedding)
-        if (A.from_mve == 2)
-            d = (float)((double)d * len_d);
-        d = (float)((double)d * (1.0 / len_d));
-    }
-    A.dst[i] = d;
-}
-
-static int
-sgm_init_depth(smvs_ctx *ctx, const float *dm, int dm_w, int dm_h, const float *inv_calibration9,
-    int dm_is_z_depth, float sigma, int kernel_size, float *out);
-
-extern "C" int
-smvs_ctx_sgm_init_depth(smvs_ctx *ctx, const float *dm, int dm_w, int dm_h,
-    float sigma, int kernel_size, float *out)
-{
-    return sgm_init_depth(ctx, dm, dm_w, dm_h, nullptr, 0, sigma, kernel_size, out);
-}
-
-extern "C" int
-smvs_ctx_sgm_init_depth_mve(smvs_ctx *ctx, const float *dm, int dm_w, int dm_h,
-    const float *inv_calibration9, int dm_is_z_depth, float sigma, int kernel_size, float *out)
-{
-    SMVS_REQUIRE(dm == nullptr || inv_calibration9 != nullptr, "null argument");
-    return sgm_init_depth(ctx, dm, dm_w, dm_h, inv_calibration9, dm_is_z_depth != 0 ? 1 : 0, sigma,
-        kernel_size, out);
-}
-
-static int
-sgm_init_depth(smvs_ctx *ctx, const float *dm, int dm_w, int dm_h, const float *inv_calibration9,
-    int dm_is_z_depth, float sigma, int kernel_size, float *out)
-{
-    SMVS_REQUIRE(ctx != nullptr, "null argument");
-    if (dm == nullptr) {   // forget the resident map
-        ctx->sgm_resident = false;
-        return SMVS_OK;
-    }
-    SMVS_REQUIRE(dm_w > 0 && dm_h > 0 && kernel_size >= 0 && sigma > 0.f,
-        "bad argument");
-    if ((ctx->image_ok & 1u) == 0u) {
-        set_error("smvs_ctx_sgm_init_depth: no main image (smvs_ctx_upload_image)");
-        return SMVS_ERR_STATE;
-    }
-    if (ctx->images[0].w != ctx->width || ctx->images[0].h != ctx->height) {
-        set_error("smvs_ctx_sgm_init_depth: main image size differs from the context");
-        return SMVS_ERR_INVALID;
-    }
-    SMVS_HIP_CHECK(set_device(ctx->device));
-    int rc;
-    // (the guide image may still be on its way: smvs_ctx_upload_image_async)
-    if ((rc = ctx_materialise_images(ctx, 1u)) != SMVS_OK)
-        return rc;
-    size_t const n = (size_t)ctx->width * ctx->height;
-    size_t const n_low = (size_t)dm_w * dm_h;
-    if (ctx->sgm_lowres_cap < n_low) {
-        if ((rc = device_alloc(&ctx->sgm_lowres, n_low)) != SMVS_OK)
-            return rc;
-        ctx->sgm_lowres_cap = n_low;
-    }
-    if (ctx->topo_sgm_cap < n) {
-        if ((rc = device_alloc(&ctx->topo_sgm, n)) != SMVS_OK)
-            return rc;
-        ctx->topo_sgm_cap = n;
-    }
-    ctx->sgm_resident = false;
-    {
-        // The map goes to the device through a kernel that reads page-locked
-        // memory over the bus, not as a DMA: at this moment the nine images of the
-        // view are on their way (smvs_ctx_upload_image_async) and a tenth transfer
-        // queues behind them, with the host waiting for it before it can launch
-        // the filter (round 6, profiles/r6_upload_overlap.txt).
-        if (ctx->sgm_pin_busy) {
-            SMVS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            ctx->sgm_pin_busy = false;
-        }
-        if (ctx->sgm_pin_cap < n_low) {
-            if (ctx->sgm_pin != nullptr)
-                (void)hipHostFree(ctx->sgm_pin);
-            ctx->sgm_pin = nullptr;
-            ctx->sgm_pin_cap = 0;
-            SMVS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ctx->sgm_pin),
-                sizeof(float) * n_low, hipHostMallocDefault));
-            ctx->sgm_pin_cap = n_low;
-        }
-        std::memcpy(ctx->sgm_pin, dm, sizeof(float) * n_low);
-        SgmMapUpload U;
-        U.src = ctx->sgm_pin;
-        U.dst = ctx->sgm_lowres;
-        U.w = dm_w;
-        U.h = dm_h;
-        U.from_mve = inv_calibration9 != nullptr ? (dm_is_z_depth ? 2 : 1) : 0;
-        for (int i = 0; i < 9; ++i)
-            U.invproj[i] = inv_calibration9 != nullptr ? inv_calibration9[i] : 0.0f;
-        hipLaunchKernelGGL(sgm_map_upload_kernel, dim3((unsigned)((n_low + 255) / 256)),
-            dim3(256), 0, ctx->stream, U);
-        SMVS_HIP_CHECK(hipGetLastError());
-        ctx->sgm_pin_busy = true;
-    }
-    BilateralArgs A;
-    A.dm = ctx->sgm_lowres;
-    A.ci = ctx->images[0].data;
-    A.out = ctx->topo_sgm;
-    A.dm_w = dm_w;
-    A.dm_h = dm_h;
-    A.w = ctx->width;
-    A.h = ctx->height;
-    A.channels = ctx->images[0].c;
-    A.kernel_size = kernel_size;
-    A.sigma = sigma;
-    SgmProfile prof;
-    const uint32_t *host_table = nullptr;
-    if (kernel_size <= BIL_MAX_K && (A.channels == 1 || A.channels == 3))
-        host_table = bilateral_colour_table();
-    bool const tabled = host_table != nullptr;
-    // the triangle of all pairs in LDS (round 6), unless SMVS_BILATERAL=compressed
-    const float *host_triangle = nullptr;
-    if (tabled && kernel_size == BIL_TRI_K) {
-        const char *form = std::getenv("SMVS_BILATERAL");
-        if (!(form != nullptr && std::strcmp(form, "compressed") == 0))
-            host_triangle = bilateral_colour_triangle();
-    }
-    BilateralSpatial S = {};
-    size_t const n_img = n * (size_t)A.channels;
-    if (tabled) {
-#pragma clang fp contract(off)
-        if (host_triangle != nullptr) {
-            if (ctx->bil_tri == nullptr) {
-                if ((rc = device_alloc(&ctx->bil_tri, BIL_TRI_FLOATS)) != SMVS_OK
-                    || (rc = ctx_upload(ctx, ctx->bil_tri, host_triangle,
-                            BIL_TRI_FLOATS * sizeof(float))) != SMVS_OK) {
-                    (void)device_alloc(&ctx->bil_tri, 0);
-                    return rc;
-                }
-            }
-        } else if (ctx->bil_lut == nullptr) {
-            if ((rc = device_alloc(&ctx->bil_lut, BIL_TABLE_WORDS)) != SMVS_OK
-                || (rc = ctx_upload(ctx, ctx->bil_lut, host_table,
-                        BIL_TABLE_WORDS * sizeof(uint32_t))) != SMVS_OK)
-                return rc;
-        }
-        // (the byte staging buffer of the image uploads is free between them)
-        if (ctx->byte_stage_cap < n_img) {
-            if ((rc = device_alloc(&ctx->byte_stage, n_img)) != SMVS_OK) {
-                ctx->byte_stage_cap = 0;
-                return rc;
-            }
-            ctx->byte_stage_cap = n_img;
-        }
-        // math::gaussian_2d as bilateral_kernel evaluates it, with the host's expf
-        int const kw = 2 * kernel_size + 1;
-        for (int ky = -kernel_size; ky <= kernel_size; ++ky)
-            for (int kx = -kernel_size; kx <= kernel_size; ++kx)
-                S.w[(ky + kernel_size) * kw + (kx + kernel_size)]
-                    = expf(-((float)kx * (float)kx / (2.0f * sigma * sigma)
-                        + (float)ky * (float)ky / (2.0f * sigma * sigma)));
-    }
-    {
-        SgmKernelTimer timer(&prof, ctx->stream, SMVS_SGM_K_BILATERAL);
-        dim3 const grid((ctx->width + 255) / 256, ctx->height);
-        if (tabled) {
-            hipLaunchKernelGGL(float_to_byte_kernel, dim3((unsigned)((n_img + 255) / 256)),
-                dim3(256), 0, ctx->stream, ctx->images[0].data, ctx->byte_stage, n_img);
-            const uint32_t *table = reinterpret_cast<const uint32_t *>(ctx->bil_lut);
-            if (host_triangle != nullptr) {
-                // one workgroup per CU, the table in its LDS for the whole image
-                size_t const lds = BIL_TRI_FLOATS * sizeof(float);
-                const void *k = A.channels == 3
-                    ? reinterpret_cast<const void *>(&bilateral_triangle_kernel<3>)
-                    : reinterpret_cast<const void *>(&bilateral_triangle_kernel<1>);
-                if ((rc = allow_dynamic_lds(ctx->device, k, lds)) != SMVS_OK)
-                    return rc;
-                int cus = 0;
-                if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
-                        physical_device(ctx->device)) != hipSuccess || cus <= 0)
-                    cus = 256;
-                unsigned const blocks = (unsigned)std::min<size_t>((size_t)cus,
-                    (n + BIL_TRI_THREADS - 1) / BIL_TRI_THREADS);
-                if (A.channels == 3)
-                    hipLaunchKernelGGL(bilateral_triangle_kernel<3>, dim3(blocks),
-                        dim3(BIL_TRI_THREADS), lds, ctx->stream, A, ctx->byte_stage, ctx->bil_tri, S);
-                else
-                    hipLaunchKernelGGL(bilateral_triangle_kernel<1>, dim3(blocks),
-                        dim3(BIL_TRI_THREADS), lds, ctx->stream, A, ctx->byte_stage, ctx->bil_tri, S);
-            } else if (A.channels == 3)
-                hipLaunchKernelGGL(bilateral_table_kernel<3>, grid, dim3(256), 0, ctx->stream,
-                    A, ctx->byte_stage, table, S);
-            else
-                hipLaunchKernelGGL(bilateral_table_kernel<1>, grid, dim3(256), 0, ctx->stream,
-                    A, ctx->byte_stage, table, S);
-        } else {
-            hipLaunchKernelGGL(bilateral_kernel, grid, dim3(256), 0, ctx->stream, A);
-        }
-    }
-    SMVS_HIP_CHECK(hipGetLastError());
-    // (no wait when the caller does not want the filtered map back: whatever
-    // reads it next runs behind the filter on the context's stream)
-    if (out != nullptr) {
-        if ((rc = ctx_download(ctx, out, ctx->topo_sgm, sizeof(float) * n)) != SMVS_OK)
-            return rc;
-        ctx->sgm_pin_busy = false;
-    }
-    ctx->sgm_resident = true;
-    return SMVS_OK;
 }
 
 extern "C" int

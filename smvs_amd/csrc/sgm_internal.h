@@ -1,0 +1,173 @@
+// What the translation units of the SGM front end share: sgm.hip (run_sgm),
+// sgm_view.hip (a view's front end), image_prep.hip (a view's input image),
+// bilateral.hip (the joint bilateral upsample).
+#pragma once
+
+#include "common.h"
+
+#include <vector>
+
+namespace smvs_hip {
+
+// Optional per-kernel timing of the front end (smvs_sgm_profile): HIP events
+// on the workspace's stream around every launch of a call, read back when the
+// call has synchronised.  Off by default: no events, no overhead.  (The
+// counters and the two members that touch them: sgm.hip.)
+struct SgmProfile {
+    struct Pending { int cls; hipEvent_t a, b; };
+    std::vector<Pending> pending;
+    bool on;
+    SgmProfile();
+    // (called when the stream is idle)
+    ~SgmProfile();
+};
+
+struct SgmKernelTimer {
+    SgmProfile *prof;
+    hipStream_t stream;
+    int cls;
+    hipEvent_t a = nullptr, b = nullptr;
+    SgmKernelTimer(SgmProfile *p, hipStream_t s, int c) : prof(p), stream(s), cls(c)
+    {
+        if (prof == nullptr || !prof->on)
+            return;
+        (void)hipEventCreate(&a);
+        (void)hipEventCreate(&b);
+        (void)hipEventRecord(a, stream);
+    }
+    ~SgmKernelTimer()
+    {
+        if (a == nullptr)
+            return;
+        (void)hipEventRecord(b, stream);
+        prof->pending.push_back({ cls, a, b });
+    }
+};
+
+// Slots of a pooled workspace (pool.hip) used by the front end.
+enum {
+    WS_DEPTHS = 0, WS_CENSUS, WS_WARPED, WS_COST, WS_SGM, WS_ARGMIN,   // one run_sgm
+    WS_MAIN, WS_NBR0, WS_NBR1, WS_FWD0, WS_FWD1, WS_BWD, WS_COST16,   // a view's front end
+    WS_RAW, WS_RAW0, WS_RAW1,                                         // raw u8 images + scratch
+    WS_BIL_DM, WS_BIL_CI, WS_BIL_OUT,                                 // bilateral upsample
+    WS_DELTA                                                          // eight path-byte volumes
+};
+static_assert(WS_DELTA < Workspace::SLOTS, "the last slot must exist in a Workspace");
+
+// Work buffers of one run_sgm inside a pooled workspace; reused by the runs of
+// a view (the runs are ordered on the workspace's stream).  Every run has its
+// own depth table.
+struct SgmWorkspace {
+    static constexpr int MAX_RUNS = 4;
+    Workspace *ws;
+    SgmProfile *prof = nullptr;
+    float *depths = nullptr;
+    unsigned long long *census = nullptr;
+    uint8_t *warped = nullptr, *cost = nullptr;
+    uint16_t *sgm = nullptr;     // S: only when the caller wants it or the DELTA form does not apply
+    uint8_t *delta = nullptr;    // the eight path-byte volumes of the DELTA form
+    int32_t *argmin = nullptr;
+    int runs = 0;
+    bool want_sgm = false;       // smvs_sgm_run hands the S volume to its caller
+    explicit SgmWorkspace(Workspace *w) : ws(w) {}
+    // penalty2 <= 255: L - C fits a byte; planes in fours: the u32 accesses of
+    // sgm_sum_wta_kernel
+    static bool delta_form(int num_steps, unsigned penalty2)
+    {
+        return (num_steps % 4) == 0 && penalty2 <= 255u;
+    }
+    // the largest penalty2 a step can use: the option itself, or in the adaptive
+    // mode max(P2 / diff, P1 * 3 / 2) <= max(P2, P1 * 3 / 2)
+    static unsigned largest_penalty2(unsigned penalty1, unsigned penalty2, int p2_mode)
+    {
+        unsigned const floor_value = penalty1 * 3u / 2u;
+        return p2_mode == SMVS_SGM_P2_ADAPTIVE && floor_value > penalty2 ? floor_value
+                                                                        : penalty2;
+    }
+    int ensure(size_t npix, int num_steps, unsigned penalty2)
+    {
+        size_t const vol = npix * (size_t)num_steps;
+        bool const df = delta_form(num_steps, penalty2);
+        int rc;
+        if ((rc = ws->ensure(WS_DEPTHS, (size_t)128 * MAX_RUNS, &depths))
+            || (rc = ws->ensure(WS_CENSUS, npix, &census))
+            || (rc = ws->ensure(WS_WARPED, vol, &warped))
+            || (rc = ws->ensure(WS_COST, vol, &cost))
+            || (rc = ws->ensure(WS_ARGMIN, npix, &argmin)))
+            return rc;
+        if (df && (rc = ws->ensure(WS_DELTA, 8 * vol, &delta)))
+            return rc;
+        if ((!df || want_sgm) && (rc = ws->ensure(WS_SGM, vol, &sgm)))
+            return rc;
+        return SMVS_OK;
+    }
+};
+
+// The penalties alone (no device involved: the *_mode entries call this before
+// anything else).
+int check_sgm_penalties(unsigned penalty1, unsigned penalty2, int p2_mode);
+
+// SGMStereo::run_sgm (sgm_stereo.cc:98-124) on device images; the depth map
+// (and optionally argmin) stay on the device.  Asynchronous on the workspace's
+// stream.  (sgm.hip)
+int sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
+    int w, int h, const uint8_t *d_nbr, int nw, int nh, const float *M,
+    const float *t, float min_depth, float max_depth, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *d_depth);
+
+// One view's SGM input image on the device: upload (raw: interleaved u8 of
+// `channels`; otherwise already at SGM scale, one channel), desaturate and
+// `halvings` half-size steps.  *out (slot `slot_out`) receives the image,
+// *ow / *oh its size.  (image_prep.hip)
+int sgm_prepare_image(Workspace &ws, const uint8_t *host, int w, int h, int channels,
+    int halvings, int slot_out, int slot_tmp, uint8_t **out, int *ow, int *oh);
+
+// The eight path directions (dx, dy) in the reference's order: ->, <-, then
+// the three top-to-bottom paths, then the three bottom-to-top paths.  The host
+// launches in this order, the all-direction kernels decode blockIdx.x in it.
+constexpr int SGM_DIRS[8][2] = { { 1, 0 }, { -1, 0 }, { 0, 1 }, { 1, 1 }, { -1, 1 },
+    { 0, -1 }, { 1, -1 }, { -1, -1 } };
+
+// Lines of direction k in a w x h image: the rows of a horizontal path, the
+// columns of a vertical one, every diagonal that starts on the entry row or
+// the entry column of a diagonal one.
+__host__ __device__ __forceinline__ constexpr int
+sgm_dir_lines(int k, int w, int h)
+{
+    return SGM_DIRS[k][1] == 0 ? h : (SGM_DIRS[k][0] == 0 ? w : w + h - 1);
+}
+
+// Grid of the all-direction kernels: a block per line (sgm_all_paths_kernel),
+// or per pair of adjacent lines of one direction (sgm_paths2_kernel).  The
+// kernels find (direction, line) by walking the same counts.
+__host__ __device__ __forceinline__ constexpr int
+sgm_grid_lines(int w, int h)
+{
+    int n = 0;
+    for (int k = 0; k < 8; ++k)
+        n += sgm_dir_lines(k, w, h);
+    return n;
+}
+__host__ __device__ __forceinline__ constexpr int
+sgm_grid_line_pairs(int w, int h)
+{
+    int n = 0;
+    for (int k = 0; k < 8; ++k)
+        n += (sgm_dir_lines(k, w, h) + 1) / 2;
+    return n;
+}
+// the sums written out; odd and even w and h at the smallest image
+// smvs_sgm_run accepts, and an ordinary one
+constexpr bool
+sgm_grids_agree(int w, int h)
+{
+    int const d = w + h - 1;
+    return sgm_grid_lines(w, h) == h + h + w + d + d + w + d + d
+        && sgm_grid_line_pairs(w, h) == 2 * ((h + 1) / 2 + (w + 1) / 2) + 4 * ((d + 1) / 2);
+}
+static_assert(sgm_grids_agree(11, 9) && sgm_grids_agree(12, 9) && sgm_grids_agree(11, 10)
+        && sgm_grids_agree(64, 48), "grid size and per-direction line counts disagree");
+// (sgm_all_paths_kernel finds the two horizontal directions by one division)
+static_assert(sgm_dir_lines(0, 64, 48) == sgm_dir_lines(1, 64, 48), "directions 0, 1: rows");
+
+} // namespace smvs_hip

@@ -231,7 +231,7 @@ def test_path_cost_minus_cost_fits_a_byte():
 
 
 def test_bilateral_colour_weight_depends_on_the_pair_almost_only_through_the_difference():
-    """csrc/sgm.hip compresses the 256 x 256 colour weights
+    """csrc/bilateral.hip compresses the 256 x 256 colour weights
     expf(-(b/255 - a/255)^2 / (2 * 0.1^2)) (float arithmetic, the host's expf)
     to 511 differences x <= 4 candidates + a 2-bit selector; with another libm
     the device falls back to exponentials, this test says which one applies here."""
