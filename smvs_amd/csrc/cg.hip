@@ -21,6 +21,7 @@
 // paces its launches on progress words the kernels publish in pinned host
 // memory (cg_solve_launch).
 #include "common.h"
+#include "dpp.h"
 
 #include <chrono>
 #include <cmath>
@@ -33,16 +34,12 @@ constexpr int CG_MAX_BLOCKS = 512;
 
 typedef double double4_v __attribute__((ext_vector_type(4)));
 
-// broadcast lane (CTRL & 3) of every quad to the quad (DPP quad_perm)
-template <int CTRL>
+// broadcast lane K of every quad to the quad (DPP quad_perm)
+template <int K>
 __device__ __forceinline__ double
 quad_bcast(double v)
 {
-    long long const bits = __double_as_longlong(v);
-    int lo = (int)(bits & 0xFFFFFFFFll), hi = (int)(bits >> 32);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+    return dpp_f64<dpp_quad_bcast(K), true>(v);
 }
 
 struct CgArgs {
@@ -638,10 +635,10 @@ cg_update_kernel(CgArgs A, int nb)
         // z = P r needs the node's whole residual: the four row-lanes of a
         // node are neighbours in the wave.
         double rn[4];
-        rn[0] = quad_bcast<0x00>(ri);
-        rn[1] = quad_bcast<0x55>(ri);
-        rn[2] = quad_bcast<0xAA>(ri);
-        rn[3] = quad_bcast<0xFF>(ri);
+        rn[0] = quad_bcast<0>(ri);
+        rn[1] = quad_bcast<1>(ri);
+        rn[2] = quad_bcast<2>(ri);
+        rn[3] = quad_bcast<3>(ri);
         if (in_range) {
             A.x[gid] = xi;
             A.r[gid] = ri;

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "cg_resident_plan.h"
+#include "dpp.h"
 
 namespace smvs_hip {
 
@@ -97,13 +98,7 @@ ld_agent(const double *p)
 // (profiles/r4_cg_waves.txt).  gfx950 has what is needed on the VALU:
 // v_permlane32_swap / v_permlane16_swap exchange halves / rows between two
 // registers, DPP row rotations cover the 16 lanes of a row.
-typedef unsigned int uint2_r __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ double
-join_words(unsigned lo, unsigned hi)
-{
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
+// (the moves themselves: dpp.h)
 
 // HALF = 32: on return the lower 32 lanes hold x[l] + x[l + 32], the upper 32
 // lanes y[l - 32] + y[l] -- one step of a reduce-scatter over two kinds (with
@@ -113,33 +108,16 @@ template <int HALF>
 __device__ __forceinline__ double
 swap_add(double x, double y)
 {
-    unsigned long long const xb = (unsigned long long)__double_as_longlong(x);
-    unsigned long long const yb = (unsigned long long)__double_as_longlong(y);
-    uint2_r lo, hi;
-    if constexpr (HALF == 32) {
-        lo = __builtin_amdgcn_permlane32_swap((unsigned)xb, (unsigned)yb, false, false);
-        hi = __builtin_amdgcn_permlane32_swap((unsigned)(xb >> 32), (unsigned)(yb >> 32),
-            false, false);
-    } else {
-        lo = __builtin_amdgcn_permlane16_swap((unsigned)xb, (unsigned)yb, false, false);
-        hi = __builtin_amdgcn_permlane16_swap((unsigned)(xb >> 32), (unsigned)(yb >> 32),
-            false, false);
-    }
-    // .x: [x of the lower half | y of the lower half], .y: [x of the upper half |
-    // y of the upper half]
-    return join_words(lo.x, hi.x) + join_words(lo.y, hi.y);
+    double lower, upper;
+    permlane_swap_f64<HALF>(x, y, lower, upper);
+    return lower + upper;
 }
 
 template <int ROR>
 __device__ __forceinline__ double
 row_rotated(double v)
 {
-    unsigned long long const b = (unsigned long long)__double_as_longlong(v);
-    int const lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)b, 0x120 + ROR, 0xf, 0xf,
-        false);
-    int const hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), 0x120 + ROR, 0xf,
-        0xf, false);
-    return join_words((unsigned)lo, (unsigned)hi);
+    return dpp_f64<dpp_row_ror(ROR)>(v);
 }
 
 // Sum over the 16 lanes of a row, every lane gets it (bit-identical in all of

@@ -63,7 +63,7 @@ enum {
     I_ACTIVE_PATCHES,
     I_TOPO_DELETED,  // patches deleted by one cut_boundaries pass
     I_TOPO_CANDIDATES,   // (behind I_TOPO_DELETED: one memset clears both) patches
-                         // the mse kernel evaluates (topology.hip)
+                         // the mse kernel evaluates (topo_mse.hip)
     I_LIVE_PATCHES,  // entries of the compacted live-patch list
     I_NUM_INITIAL,   // active nodes at the start of the Newton loop (finish_step_kernel, begin)
     I_STOP,          // pipelined Newton loop: the loop has ended, enqueued steps do nothing
@@ -73,7 +73,7 @@ enum {
     I_SURF_CHANGED,  // patches filled / deleted by the last grid operation
     I_TOPO_PASS0 = 16,   // cut_boundaries: {deleted, candidates} of a pass, two word pairs
                          // that the passes of the three-launch form alternate between
-                         // (topology.hip); the words up to I_NUM are not used
+                         // (topo_cut.hip); the words up to I_NUM are not used
     I_NUM = 24
 };
 
@@ -274,7 +274,7 @@ struct smvs_ctx {
     size_t sgm_lowres_cap = 0;
     float *bil_lut = nullptr;    // compressed colour-weight table of the bilateral filter (bilateral.hip)
     float *bil_tri = nullptr;    // ... and the triangle of all byte pairs (round 6)
-    int topo_slot = 0;           // cut_boundaries: the word pair of the next pass (topology.hip)
+    int topo_slot = 0;           // cut_boundaries: the word pair of the next pass (topo_cut.hip)
     bool topo_slots_clean = false;   // ... and whether both pairs are zero on the stream
     smvs_topo::NccSample *topo_ncc = nullptr;
     int topo_ncc_off[33] = { 0 };
@@ -283,9 +283,9 @@ struct smvs_ctx {
     size_t topo_mse_cap = 0;
     uint8_t *topo_border = nullptr;   // nodes with > 1 missing neighbour (cut_boundaries)
     size_t topo_border_cap = 0;
-    int *topo_mse_list = nullptr;     // patches whose error is evaluated (topology.hip)
+    int *topo_mse_list = nullptr;     // patches whose error is evaluated (topo_mse.hip)
     size_t topo_mse_list_cap = 0;
-    double *topo_mse_parts = nullptr;  // partial sums of the chunked patch MSE (topology.hip)
+    double *topo_mse_parts = nullptr;  // partial sums of the chunked patch MSE (topo_mse.hip)
     size_t topo_mse_parts_cap = 0;
     int *topo_mse_arrived = nullptr;   // ... and its arrival counters (zero between launches)
     size_t topo_mse_arrived_cap = 0;
@@ -378,6 +378,23 @@ int device_alloc(T **ptr, size_t count)
     if (count == 0)
         return SMVS_OK;
     return device_malloc(reinterpret_cast<void **>(ptr), count * sizeof(T));
+}
+
+// A buffer that only grows: room for `count` items of `each` elements, *cap
+// the items there is room for.
+// (device_alloc frees the old buffer first: the capacity goes to zero with
+// it, so that a failed allocation is tried again by the next call instead of
+// leaving a null pointer behind a capacity that says it is there)
+template <typename T>
+int device_grow(T **ptr, size_t *cap, size_t count, size_t each = 1)
+{
+    if (count <= *cap)
+        return SMVS_OK;
+    *cap = 0;
+    int const rc = device_alloc(ptr, count * each);
+    if (rc == SMVS_OK)
+        *cap = count;
+    return rc;
 }
 
 // A reusable device workspace of the context-free entry points (pool.hip): a

@@ -839,7 +839,7 @@ def test_cut_boundaries_in_three_launches_and_in_five(hip, oracle, monkeypatch, 
 def test_topology_shared_reciprocals_give_the_bits_of_the_divisions(hip, oracle, monkeypatch,
                                                                    size, n_subs, scale):
     """The visibility and MSE kernels take the ten quotients of a warp from one
-    refined reciprocal of d and one of d * d (csrc/topology.hip, SharedDivisor):
+    refined reciprocal of d and one of d * d (csrc/topo_divide.h, SharedDivisor):
     the instruction sequence of the division without its scaling steps.  With
     SMVS_TOPO_DIVIDE=exact every quotient is the division itself -- masks and
     errors must be the same bits (and the oracle's, the tests above).  So must
@@ -886,7 +886,7 @@ def test_topology_shared_reciprocals_give_the_bits_of_the_divisions(hip, oracle,
 def test_visibility_masks_do_not_depend_on_the_lanes_per_pair(hip, oracle, monkeypatch, size,
                                                               n_subs, scale):
     """Round 6 chose the lanes per (patch, neighbour) of the visibility kernel by
-    patch size (csrc/topology.hip, SMVS_VIS_GROUP_<ps>): one lane, a row of
+    patch size (csrc/topo_visibility.hip, SMVS_VIS_GROUP_<ps>): one lane, a row of
     sixteen, a whole wave and the whole workgroup must give the oracle's masks --
     the group size changes who sums what (DPP rows, permlane swaps, LDS across
     waves), which samples go to the LDS stash and how many groups share a
