@@ -140,6 +140,21 @@ int smvs_ctx_download_planes(smvs_ctx *ctx, int view, float *grad2,
 /* shading image + gradients alone (scale independent, stereo_view.cc:64-84) */
 int smvs_ctx_upload_shading(smvs_ctx *ctx, const float *shading1,
     const float *shading_grad2);
+/* The same planes made on the device from the main view's uploaded image:
+ * StereoView::initialize_linear (lib/stereo_view.cc:64-84) -- the inverse sRGB
+ * curve per element, the luminance (0.21, 0.72, 0.07) and rows x and y of the
+ * 3x3 quadratic fit of the unblurred image -- in place of the host's loops and
+ * smvs_ctx_upload_shading, bit for bit.  gamma_lut256: the curve at the 256
+ * values (float)k / 255.0f an image element can take, evaluated by the caller
+ * with the host's own expression (the device evaluates no powf); NULL: no
+ * gamma correction.  Needs the main image (smvs_ctx_upload_image[_async] with
+ * view = -1; SMVS_ERR_INVALID without one); an upload still on its way is
+ * converted first.  Only enqueues on the context's stream.
+ * smvs_ctx_download_shading hands the planes back, whichever entry made them
+ * (either pointer may be NULL; SMVS_ERR_STATE when there are none). */
+int smvs_ctx_prepare_shading(smvs_ctx *ctx, const float *gamma_lut256);
+int smvs_ctx_download_shading(smvs_ctx *ctx, float *shading1,
+    float *shading_grad2);
 
 /* Surface state (surface.h:106-120) as flat arrays.
  *   nodes[(npx+1)*(npy+1)][4] = f, dx, dy, dxy (patch units);

@@ -249,7 +249,7 @@ static int ctx_free(smvs_ctx *ctx);
 extern "C" int
 smvs_ctx_create(int device, int width, int height, int n_subs, smvs_ctx **out)
 {
-    if (out != nullptr && width > 4 && height > 4 && n_subs >= 1
+    if (out != nullptr && width > 2 && height > 2 && n_subs >= 1
         && n_subs <= SMVS_MAX_SUBS) {
         std::lock_guard<std::mutex> guard(g_ctx_pool_mutex);
         for (size_t i = 0; i < g_ctx_pool.size(); ++i) {
@@ -263,7 +263,8 @@ smvs_ctx_create(int device, int width, int height, int n_subs, smvs_ctx **out)
         }
     }
     SMVS_REQUIRE(out != nullptr, "out must not be null");
-    SMVS_REQUIRE(width > 4 && height > 4, "image too small");
+    // (the smallest image smvs_ctx_upload_image takes: one interior pixel)
+    SMVS_REQUIRE(width > 2 && height > 2, "image too small");
     SMVS_REQUIRE(n_subs >= 1 && n_subs <= SMVS_MAX_SUBS,
         "n_subs must be in [1, SMVS_MAX_SUBS]");
     int const count = logical_device_count();

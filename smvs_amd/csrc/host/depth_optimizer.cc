@@ -359,7 +359,19 @@ DepthOptimizer::upload_images(void)
             check(smvs_ctx_upload_image_async(ctx, (int)j, sb->width(), sb->height(),
                 sb->channels(), sb->begin()), "smvs_ctx_upload_image_async");
         }
-        if (opts.use_shading)
+        if (opts.use_shading && opts.device_shading_prep) {
+            // (the view's lazy host planes are never formed; the curve's table
+            // is the host expression at the 256 values an element can take)
+            if (!main_view->wants_linear())
+                throw std::invalid_argument("use_shading needs a main view created "
+                    "with initialize_linear");
+            float lut[256];
+            if (main_view->gamma_correction())
+                imgtools::gamma_inv_srgb_lut(lut);
+            check(smvs_ctx_prepare_shading(ctx,
+                main_view->gamma_correction() ? lut : nullptr),
+                "smvs_ctx_prepare_shading");
+        } else if (opts.use_shading)
             check(smvs_ctx_upload_shading(ctx,
                 main_view->get_shading_image()->begin(),
                 main_view->get_shading_gradients()->begin()),

@@ -47,6 +47,11 @@ public:
         std::string output_name = "smvs";
         int device = 0;  // HIP device (not in the reference)
         int solver = 0;  // smvs_solver_mode of include/smvs_hip.h (not in the reference)
+        // not in the reference: with use_shading, the main view's shading planes
+        // (StereoView::initialize_linear, lib/stereo_view.cc:64-84) are made on the
+        // device from the uploaded image (smvs_ctx_prepare_shading) instead of
+        // on the host and uploaded; the same bits
+        bool device_shading_prep = false;
     };
 
     struct IterationLog

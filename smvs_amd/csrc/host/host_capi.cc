@@ -79,7 +79,19 @@ smvs_host_optimize(const smvs_host_view *main_in, const smvs_host_view *subs_in,
     int sgm_w, int sgm_h, float *sgm_roundtrip, const smvs_host_options *o,
     float *depth_out, float *normals_out, smvs_host_log *log)
 {
+    return smvs_host_optimize_flags(main_in, subs_in, n_subs, bundle_in, sgm_depth, sgm_w,
+        sgm_h, sgm_roundtrip, o, 0u, depth_out, normals_out, log);
+}
+
+extern "C" int
+smvs_host_optimize_flags(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, const float *sgm_depth,
+    int sgm_w, int sgm_h, float *sgm_roundtrip, const smvs_host_options *o,
+    unsigned flags, float *depth_out, float *normals_out, smvs_host_log *log)
+{
     try {
+        if ((flags & ~(unsigned)SMVS_HOST_OPTIMIZE_DEVICE_SHADING_PREP) != 0u)
+            throw std::invalid_argument("smvs_host_optimize_flags: unknown flag");
         // (the previous call's embeddings go back to the page-locked pool BEFORE
         // this call asks it for its maps: kept until the next call's end, the 33 MB
         // of a 1920 x 1080 depth + normal pair were allocated afresh every time --
@@ -110,6 +122,7 @@ smvs_host_optimize(const smvs_host_view *main_in, const smvs_host_view *subs_in,
         opts.full_optimization = o->full_optimization != 0;
         opts.device = o->device;
         opts.solver = o->solver;
+        opts.device_shading_prep = (flags & SMVS_HOST_OPTIMIZE_DEVICE_SHADING_PREP) != 0u;
         // (the test harness sets Options::debug_lvl through the environment:
         // smvs_host_options is mirrored field for field by smvs_amd/host.py)
         if (const char *lvl = std::getenv("SMVS_DEBUG_LVL"))
@@ -131,6 +144,41 @@ smvs_host_optimize(const smvs_host_view *main_in, const smvs_host_view *subs_in,
         g_host_error = e.what();
         return -1;
     }
+}
+
+extern "C" int
+smvs_host_shading_planes(const uint8_t *bytes, int width, int height, int channels,
+    int gamma, float *shading_out, float *grad_out)
+{
+    try {
+        if (bytes == nullptr || width < 1 || height < 1 || channels < 1)
+            throw std::invalid_argument("smvs_host_shading_planes: bad argument");
+        ByteImage::Ptr img = ByteImage::create_for_overwrite(width, height, channels);
+        std::memcpy(img->begin(), bytes, (size_t)width * height * channels);
+        StereoView::Ptr view = StereoView::create(0, img, CameraInfo(), true, gamma != 0);
+        size_t const npix = (size_t)width * height;
+        if (shading_out != nullptr)
+            std::memcpy(shading_out, view->get_shading_image()->begin(),
+                sizeof(float) * npix);
+        if (grad_out != nullptr)
+            std::memcpy(grad_out, view->get_shading_gradients()->begin(),
+                sizeof(float) * 2 * npix);
+        return 0;
+    } catch (std::exception const& e) {
+        g_host_error = e.what();
+        return -1;
+    }
+}
+
+extern "C" int
+smvs_host_gamma_inv_srgb_lut(float *out256)
+{
+    if (out256 == nullptr) {
+        g_host_error = "smvs_host_gamma_inv_srgb_lut: bad argument";
+        return -1;
+    }
+    imgtools::gamma_inv_srgb_lut(out256);
+    return 0;
 }
 
 extern "C" int
@@ -826,7 +874,8 @@ smvs_host_reconstruct_scene_flags(const char *scene_dir,
         if (scene_dir == nullptr || o == nullptr)
             throw std::invalid_argument("smvs_host_reconstruct_scene: bad argument");
         if ((flags & ~(unsigned)(SMVS_HOST_SCENE_ADAPTIVE_PENALTY2
-                | SMVS_HOST_SCENE_DEVICE_INPUT_SCALING)) != 0u)
+                | SMVS_HOST_SCENE_DEVICE_INPUT_SCALING
+                | SMVS_HOST_SCENE_DEVICE_SHADING_PREP | SMVS_HOST_SCENE_GAMMA_SRGB)) != 0u)
             throw std::invalid_argument("smvs_host_reconstruct_scene_flags: unknown flag");
         ReconSettings conf;
         if (o->image_embedding != nullptr)
@@ -843,6 +892,8 @@ smvs_host_reconstruct_scene_flags(const char *scene_dir,
         conf.sgm_scale = o->sgm_scale;
         conf.sgm_adaptive_penalty2 = (flags & SMVS_HOST_SCENE_ADAPTIVE_PENALTY2) != 0u;
         conf.device_input_scaling = (flags & SMVS_HOST_SCENE_DEVICE_INPUT_SCALING) != 0u;
+        conf.device_shading_prep = (flags & SMVS_HOST_SCENE_DEVICE_SHADING_PREP) != 0u;
+        conf.gamma_correction = (flags & SMVS_HOST_SCENE_GAMMA_SRGB) != 0u;
         conf.num_neighbors = (std::size_t)o->num_neighbors;
         conf.min_neighbors = (std::size_t)o->min_neighbors;
         conf.first_device = o->first_device;

@@ -65,6 +65,28 @@ int smvs_host_optimize(const smvs_host_view *main_view,
     const float *sgm_depth, int sgm_w, int sgm_h, float *sgm_depth_roundtrip,
     const smvs_host_options *opts, float *depth_out, float *normals_out,
     smvs_host_log *log);
+/* The same with a word of switches smvs_host_options does not hold (it keeps
+ * its layout for existing callers).  Bit 0: DepthOptimizer::Options::
+ * device_shading_prep -- with use_shading, the main view's shading planes
+ * (StereoView::initialize_linear, lib/stereo_view.cc:64-84) are made on the
+ * device (smvs_ctx_prepare_shading) instead of on the host; the results are
+ * the host path's, bit for bit.  An unknown bit is an argument error, raised
+ * before anything else is looked at.  smvs_host_optimize forwards with 0. */
+#define SMVS_HOST_OPTIMIZE_DEVICE_SHADING_PREP 1
+int smvs_host_optimize_flags(const smvs_host_view *main_view,
+    const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
+    const float *sgm_depth, int sgm_w, int sgm_h, float *sgm_depth_roundtrip,
+    const smvs_host_options *opts, unsigned flags, float *depth_out,
+    float *normals_out, smvs_host_log *log);
+
+/* The host's StereoView::initialize_linear (lib/stereo_view.cc:64-84) of a view
+ * built from `bytes` (width x height x channels, interleaved): shading_out
+ * (width x height floats) and grad_out (x 2), either may be NULL.
+ * smvs_host_gamma_inv_srgb_lut: imgtools::gamma_inv_srgb_lut, the table
+ * DepthOptimizer hands to smvs_ctx_prepare_shading.  Neither needs a device. */
+int smvs_host_shading_planes(const uint8_t *bytes, int width, int height,
+    int channels, int gamma, float *shading_out, float *grad_out);
+int smvs_host_gamma_inv_srgb_lut(float *out256);
 
 /* The embeddings the last smvs_host_optimize of this thread left in its main
  * view (write_depth_to_view / write_image_to_view: the result "smvs" / "smvsN",
@@ -196,10 +218,17 @@ int smvs_host_reconstruct_scene_mode(const char *scene_dir,
  * (smvs_host_reconstruct_scene_mode's argument); bit 1: ReconSettings::
  * device_input_scaling -- the input scaling of app/smvsrecon.cc:621-650 runs on
  * the device (smvs_rescale_half_gaussian), one ViewQueue task per view; the
- * undist-L<s> images are the host path's, bit for bit.  An unknown bit is an
- * argument error.  smvs_host_reconstruct_scene and ..._mode forward to this. */
+ * undist-L<s> images are the host path's, bit for bit; bit 3: ReconSettings::
+ * device_shading_prep -- with use_shading, every view's shading planes
+ * (lib/stereo_view.cc:64-84) are made on the device (smvs_ctx_prepare_shading),
+ * the embeddings are the host path's, bit for bit; bit 4: ReconSettings::
+ * gamma_correction (app/smvsrecon.cc:52, 669), which the struct has no field
+ * for.  An unknown bit is an argument error.  smvs_host_reconstruct_scene and ..._mode forward to this. */
 #define SMVS_HOST_SCENE_ADAPTIVE_PENALTY2 1
 #define SMVS_HOST_SCENE_DEVICE_INPUT_SCALING 2
+/* (value 4 is not assigned: it stays the argument error callers have met so far) */
+#define SMVS_HOST_SCENE_DEVICE_SHADING_PREP 8   /* ReconSettings::device_shading_prep */
+#define SMVS_HOST_SCENE_GAMMA_SRGB 16           /* ReconSettings::gamma_correction (--gamma-srgb) */
 int smvs_host_reconstruct_scene_flags(const char *scene_dir,
     const smvs_host_recon_settings *settings, unsigned flags, const int *view_ids,
     int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,

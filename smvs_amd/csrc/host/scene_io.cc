@@ -593,6 +593,7 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                 do_opts.num_iterations = 5;
                 do_opts.min_scale = conf.output_scale;
                 do_opts.use_shading = conf.use_shading;
+                do_opts.device_shading_prep = conf.device_shading_prep;
                 do_opts.output_name = report.output_name;
                 do_opts.use_sgm = conf.use_sgm;
                 do_opts.full_optimization = conf.full_optimization;

@@ -100,6 +100,9 @@ struct ReconSettings
     // not in the reference's AppSettings: the input scaling of :621-650 on the
     // device (rescale_half_size_gaussian_device), one ViewQueue task per view
     bool device_input_scaling = false;
+    // not in the reference's AppSettings: DepthOptimizer::Options::
+    // device_shading_prep (with use_shading only)
+    bool device_shading_prep = false;
     std::size_t num_neighbors = 6, min_neighbors = 3;
     int first_device = 0, num_devices = 1, views_in_flight = 2;
 };

@@ -169,8 +169,9 @@ StereoView::create(int view_id, ByteImage::ConstPtr bytes,
     sv->view_id = view_id;
     sv->camera = camera;
     sv->bytes = bytes;
-    if (initialize_linear)
-        sv->initialize_linear(gamma_correction);
+    // (computed on first use: get_shading_image() and its siblings)
+    sv->linear_wanted = initialize_linear;
+    sv->linear_gamma = initialize_linear && gamma_correction;
     return sv;
 }
 
@@ -212,24 +213,48 @@ StereoView::set_scale_planes(FloatImage::Ptr gradients, FloatImage::Ptr hessian)
 }
 
 void
-StereoView::initialize_linear(bool gamma_correction)
+StereoView::initialize_linear(void) const
 {
     // lib/stereo_view.cc:64-84
     this->linear_image = this->get_image()->duplicate();
-    if (gamma_correction) {
+    if (linear_gamma) {
         int64_t const n = (int64_t)linear_image->get_pixel_amount()
             * linear_image->channels();
-        for (int64_t i = 0; i < n; ++i) {
-            float const v = linear_image->at(i);
-            linear_image->at(i) = v <= 0.04045f ? v / 12.92f
-                : std::pow((v + 0.055f) / 1.055f, 2.4f);
-        }
+        for (int64_t i = 0; i < n; ++i)
+            linear_image->at(i) = imgtools::gamma_inv_srgb(linear_image->at(i));
     }
     this->shading = this->linear_image->channels() > 1
         ? imgtools::desaturate(this->linear_image) : this->linear_image;
     this->shading_grad = FloatImage::create(shading->width(),
         shading->height(), 2);
     imgtools::gradients_and_hessian(this->shading, this->shading_grad, nullptr);
+}
+
+FloatImage::ConstPtr
+StereoView::get_shading_image(void) const
+{
+    if (!linear_wanted)
+        return nullptr;
+    std::call_once(linear_once, [this]() { this->initialize_linear(); });
+    return shading;
+}
+
+FloatImage::ConstPtr
+StereoView::get_shading_gradients(void) const
+{
+    if (!linear_wanted)
+        return nullptr;
+    std::call_once(linear_once, [this]() { this->initialize_linear(); });
+    return shading_grad;
+}
+
+FloatImage::ConstPtr
+StereoView::get_linear_image(void) const
+{
+    if (!linear_wanted)
+        return nullptr;
+    std::call_once(linear_once, [this]() { this->initialize_linear(); });
+    return linear_image;
 }
 
 float

@@ -4,6 +4,7 @@
 // and camera; named embeddings written by the optimizer are kept in a map.
 #pragma once
 
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <string>
@@ -42,9 +43,15 @@ public:
     FloatImage::ConstPtr get_scaleimage(void) const { return scaleimage; }
     FloatImage::ConstPtr get_image_gradients(void) const { return image_grad; }
     FloatImage::ConstPtr get_image_hessian(void) const { return image_hessian; }
-    FloatImage::ConstPtr get_shading_image(void) const { return shading; }
-    FloatImage::ConstPtr get_shading_gradients(void) const { return shading_grad; }
-    FloatImage::ConstPtr get_linear_image(void) const { return linear_image; }
+    // The linear image and the shading planes (lib/stereo_view.cc:64-84) of a
+    // view created with initialize_linear are computed on first use, like
+    // get_image(): DepthOptimizer::Options::device_shading_prep makes the planes
+    // on the device and never asks for them.  Null without initialize_linear.
+    FloatImage::ConstPtr get_shading_image(void) const;
+    FloatImage::ConstPtr get_shading_gradients(void) const;
+    FloatImage::ConstPtr get_linear_image(void) const;
+    bool wants_linear(void) const { return linear_wanted; }
+    bool gamma_correction(void) const { return linear_gamma; }
 
     // "smvs-sgm" embedding: stored in MVE convention (ray length); the getter
     // converts to z-depth (lib/stereo_view.h:121-130)
@@ -67,7 +74,7 @@ public:
 
 private:
     StereoView(void) = default;
-    void initialize_linear(bool gamma_correction);
+    void initialize_linear(void) const;
 
 private:
     int view_id = 0;
@@ -76,7 +83,10 @@ private:
     mutable FloatImage::ConstPtr image;   // lazily converted, see get_image()
     mutable std::once_flag image_once;
     FloatImage::Ptr scaleimage, image_grad, image_hessian;
-    FloatImage::Ptr linear_image, shading, shading_grad;
+    bool linear_wanted = false, linear_gamma = false;
+    // lazily computed, see get_shading_image()
+    mutable FloatImage::Ptr linear_image, shading, shading_grad;
+    mutable std::once_flag linear_once;
     mutable std::map<std::string, FloatImage::Ptr> embeddings;
     // z-depth maps of write_depth_to_view_deferred not yet converted and stored
     mutable std::map<std::string, FloatImage::Ptr> deferred_depth;
@@ -85,6 +95,21 @@ private:
 
 // image helpers shared with SGMStereo / DepthOptimizer
 namespace imgtools {
+// The inverse sRGB curve of lib/stereo_view.cc:69-77: the ONE expression both
+// initialize_linear's loop and the table below evaluate.
+inline float
+gamma_inv_srgb(float v)
+{
+    return v <= 0.04045f ? v / 12.92f : std::pow((v + 0.055f) / 1.055f, 2.4f);
+}
+// ... at the 256 values (float)k / 255.0f an image element can take
+// (smvs_ctx_prepare_shading's table)
+inline void
+gamma_inv_srgb_lut(float out[256])
+{
+    for (int k = 0; k < 256; ++k)
+        out[k] = gamma_inv_srgb((float)k / 255.0f);
+}
 FloatImage::Ptr blur_gaussian(FloatImage::ConstPtr in, float sigma);
 FloatImage::Ptr desaturate(FloatImage::ConstPtr in);
 ByteImage::Ptr desaturate(ByteImage::ConstPtr in);

@@ -10,6 +10,7 @@
 // MVE's blur_gaussian / desaturate semantics are recalled [MVE-unverified].
 #include "common.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 #include <cmath>
@@ -372,6 +373,88 @@ gradients_kernel(const float *__restrict__ img, int w, int h, int c,
         grad[p] = g;
         if (hess != nullptr)
             hess[p] = hs;
+    }
+}
+
+// The main view's shading planes (StereoView::initialize_linear,
+// stereo_view.cc:64-84): the inverse sRGB curve per element (GAMMA), the
+// luminance, and rows x and y of the quadratic fit of the UNBLURRED image --
+// gradients_kernel's tiling, window and fit, with the shading value written out
+// as a plane of its own.  The image's floats are (float)byte / 255.0f, 256
+// distinct values, so the curve is a table of 256 floats that the HOST fills
+// with its own expression (imgtools::gamma_inv_srgb_lut): the byte comes back
+// as (int)(v * 255.0f + 0.5f) and the kernel evaluates no transcendental.  The
+// table arrives by value in the kernel arguments; the lookup index differs per
+// lane, so the first 256 threads stage it in LDS.
+struct GammaLut { float v[256]; };
+
+template <int C, bool GAMMA>
+__global__ void __launch_bounds__(256)
+shading_prepare_kernel(const float *__restrict__ img, int w, int h, GammaLut lut,
+    FitMatrix fit, float *__restrict__ shading, float2 *__restrict__ grad)
+{
+#pragma clang fp contract(off)
+    __shared__ float lum[GRAD_ROWS + 2][256 + 2];
+    __shared__ float tab[GAMMA ? 256 : 1];
+    int const x0 = blockIdx.x * blockDim.x;
+    int const t = threadIdx.x;
+    int const y0 = blockIdx.y * GRAD_ROWS;
+    // (padding workgroups of the row, see the launch: the whole workgroup leaves)
+    if (x0 >= w)
+        return;
+    if constexpr (GAMMA) {
+        tab[t] = lut.v[t];
+        __syncthreads();
+    }
+    for (int col = t; col < 256 + 2; col += 256) {
+        int const gx = min(max(x0 + col - 1, 0), w - 1);
+#pragma unroll
+        for (int row = 0; row < GRAD_ROWS + 2; ++row) {
+            int const gy = min(max(y0 + row - 1, 0), h - 1);
+            const float *px = img + ((size_t)gy * w + gx) * C;
+            float l[C];
+#pragma unroll
+            for (int ch = 0; ch < C; ++ch) {
+                float const v = px[ch];
+                if constexpr (GAMMA) {
+                    // (the byte the float came from; the bound only keeps a
+                    // value no byte gives inside the table)
+                    int const k = (int)(v * 255.0f + 0.5f);
+                    l[ch] = tab[min(max(k, 0), 255)];
+                } else {
+                    l[ch] = v;
+                }
+            }
+            if constexpr (C >= 3)
+                lum[row][col] = l[0] * 0.21f + l[1] * 0.72f + l[2] * 0.07f;
+            else
+                lum[row][col] = l[0];
+        }
+    }
+    __syncthreads();
+    int const x = x0 + t;
+    if (x >= w)
+        return;
+#pragma unroll 1
+    for (int r = 0; r < GRAD_ROWS; ++r) {
+        int const y = y0 + r;
+        if (y >= h)
+            break;
+        size_t const p = (size_t)y * w + x;
+        float2 g = make_float2(0.f, 0.f);
+        float4 hs;
+        // (the clamped halo values only ever sit in the windows of the rim,
+        // whose gradients are zero)
+        if (x >= 1 && x < w - 1 && y >= 1 && y < h - 1) {
+            double v[9];
+            int k = 0;
+            for (int a = -1; a < 2; ++a)
+                for (int b = -1; b < 2; ++b)
+                    v[k++] = lum[r + b + 1][t + 1 + a];
+            quadratic_fit(fit, v, false, &g, &hs);
+        }
+        shading[p] = lum[r + 1][t + 1];
+        grad[p] = g;
     }
 }
 
@@ -875,5 +958,79 @@ smvs_ctx_upload_shading(smvs_ctx *ctx, const float *shading1,
         npix * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
     SMVS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     ctx->has_shading = true;
+    return SMVS_OK;
+}
+
+// StereoView::initialize_linear (lib/stereo_view.cc:64-84) of the main view on
+// the device, in place of the host's planes and smvs_ctx_upload_shading.
+extern "C" int
+smvs_ctx_prepare_shading(smvs_ctx *ctx, const float *gamma_lut256)
+{
+    SMVS_REQUIRE(ctx != nullptr, "null context");
+    SMVS_REQUIRE((ctx->image_ok & 1u) != 0u, "the main view has no image");
+    smvs_ctx::ViewImage const &vi = ctx->images[0];
+    SMVS_REQUIRE(vi.data != nullptr && vi.w == ctx->width && vi.h == ctx->height
+        && (vi.c == 1 || vi.c == 3), "bad main image");
+    SMVS_HIP_CHECK(set_device(ctx->device));
+    int rc;
+    // (an image still on its way is converted first, on the same stream)
+    if ((rc = ctx_materialise_images(ctx, 1u)) != SMVS_OK)
+        return rc;
+    size_t const npix = (size_t)ctx->width * ctx->height;
+    if (ctx->main_shading == nullptr) {
+        if ((rc = device_alloc(&ctx->main_shading, npix)) != SMVS_OK)
+            return rc;
+        if ((rc = device_alloc(&ctx->main_shading_grad, npix)) != SMVS_OK)
+            return rc;
+    }
+    GammaLut lut = {};
+    bool const gamma = gamma_lut256 != nullptr;
+    if (gamma)
+        std::copy(gamma_lut256, gamma_lut256 + 256, lut.v);
+    FitMatrix const fit = quadratic_fit_matrix();
+    // (gradients_kernel's grid: a row of it is a multiple of 8 workgroups)
+    dim3 const grid((((unsigned)vi.w + 255u) / 256u + 7u) & ~7u,
+        ((unsigned)vi.h + GRAD_ROWS - 1) / GRAD_ROWS);
+    {
+        ScopedKernelTimer timer(ctx, SMVS_K_MISC);
+        if (vi.c == 1 && gamma)
+            hipLaunchKernelGGL((shading_prepare_kernel<1, true>), grid, dim3(256), 0,
+                ctx->stream, vi.data, vi.w, vi.h, lut, fit, ctx->main_shading,
+                ctx->main_shading_grad);
+        else if (vi.c == 1)
+            hipLaunchKernelGGL((shading_prepare_kernel<1, false>), grid, dim3(256), 0,
+                ctx->stream, vi.data, vi.w, vi.h, lut, fit, ctx->main_shading,
+                ctx->main_shading_grad);
+        else if (gamma)
+            hipLaunchKernelGGL((shading_prepare_kernel<3, true>), grid, dim3(256), 0,
+                ctx->stream, vi.data, vi.w, vi.h, lut, fit, ctx->main_shading,
+                ctx->main_shading_grad);
+        else
+            hipLaunchKernelGGL((shading_prepare_kernel<3, false>), grid, dim3(256), 0,
+                ctx->stream, vi.data, vi.w, vi.h, lut, fit, ctx->main_shading,
+                ctx->main_shading_grad);
+    }
+    SMVS_HIP_CHECK(hipGetLastError());
+    ctx->has_shading = true;
+    return SMVS_OK;
+}
+
+extern "C" int
+smvs_ctx_download_shading(smvs_ctx *ctx, float *shading1, float *shading_grad2)
+{
+    SMVS_REQUIRE(ctx != nullptr, "null context");
+    if (!ctx->has_shading) {
+        set_error("smvs_ctx_download_shading: the context has no shading planes");
+        return SMVS_ERR_STATE;
+    }
+    SMVS_HIP_CHECK(set_device(ctx->device));
+    size_t const npix = (size_t)ctx->width * ctx->height;
+    if (shading1 != nullptr)
+        SMVS_HIP_CHECK(hipMemcpyAsync(shading1, ctx->main_shading, npix * sizeof(float),
+            hipMemcpyDeviceToHost, ctx->stream));
+    if (shading_grad2 != nullptr)
+        SMVS_HIP_CHECK(hipMemcpyAsync(shading_grad2, ctx->main_shading_grad,
+            npix * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
+    SMVS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return SMVS_OK;
 }

@@ -152,6 +152,32 @@ class ViewContext:
                                                 _p(hess, _fp)))
         return grad, hess
 
+    def prepare_shading(self, gamma_lut=None):
+        """smvs_ctx_prepare_shading: the main view's shading planes from its
+        uploaded image; gamma_lut = host.gamma_inv_srgb_lut() for --gamma-srgb.
+        Only enqueues."""
+        lut = None
+        if gamma_lut is not None:
+            lut = _f32(gamma_lut).reshape(-1)
+            if lut.size != 256:
+                raise ValueError("prepare_shading: the table has 256 entries")
+        check(self.lib.smvs_ctx_prepare_shading(self.handle, _p(lut, _fp)))
+
+    def download_shading(self):
+        """(shading (h, w), shading gradients (h, w, 2)) of the context."""
+        shading = np.zeros((self.height, self.width), np.float32)
+        grad = np.zeros((self.height, self.width, 2), np.float32)
+        check(self.lib.smvs_ctx_download_shading(self.handle, _p(shading, _fp),
+                                                 _p(grad, _fp)))
+        return shading, grad
+
+    def upload_shading(self, shading, shading_grad):
+        """smvs_ctx_upload_shading: planes computed elsewhere."""
+        sh = _f32(shading); shg = _f32(shading_grad)
+        assert sh.shape == (self.height, self.width)
+        assert shg.shape == (self.height, self.width, 2)
+        check(self.lib.smvs_ctx_upload_shading(self.handle, _p(sh, _fp), _p(shg, _fp)))
+
     def set_surface(self, surf):
         nodes = _f64(surf["nodes"]).reshape(-1, 4)
         nv = np.ascontiguousarray(surf["node_valid"], dtype=np.uint8)

@@ -93,10 +93,13 @@ def _marshal(inputs, keep):
 def optimize(inputs, regularization=0.01, light_reg=0.0, num_iterations=5,
              min_scale=2, use_shading=False, sgm_depth=None,
              full_optimization=False, device=0, solver="auto", want_maps=True,
-             gamma_correction=False):
+             gamma_correction=False, device_shading_prep=False):
     """want_maps=False: optimize() only -- the depth / normal maps the reference
     reads back with get_depth() / get_normals() afterwards are not fetched (the
-    embeddings optimize() itself writes are; tools/optimize_timeline.py)."""
+    embeddings optimize() itself writes are; tools/optimize_timeline.py).
+    device_shading_prep (with use_shading): the main view's shading planes are
+    made on the device (smvs_ctx_prepare_shading) instead of by the host's
+    StereoView::initialize_linear, with the same bits; off by default."""
     lib = load()
     keep = []
     main, subs, n_subs, b = _marshal(inputs, keep)
@@ -115,9 +118,10 @@ def optimize(inputs, regularization=0.01, light_reg=0.0, num_iterations=5,
         sd = np.ascontiguousarray(sgm_depth, dtype=np.float32)
         sh, sw = sd.shape
         rt = np.zeros_like(sd)
-    rc = lib.smvs_host_optimize(C.byref(main), subs, n_subs, C.byref(b),
+    rc = lib.smvs_host_optimize_flags(C.byref(main), subs, n_subs, C.byref(b),
         sd.ctypes.data_as(_fp) if sd is not None else None, sw, sh,
         rt.ctypes.data_as(_fp) if rt is not None else None, C.byref(o),
+        C.c_uint(1 if device_shading_prep else 0),
         depth.ctypes.data_as(_fp) if want_maps else None,
         normals.ctypes.data_as(_fp) if want_maps else None, C.byref(log))
     if rc != 0:
@@ -228,7 +232,8 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       force_recon=False, force_sgm=False, sgm_range=(0.0, 0.0), sgm_scale=1,
                       num_neighbors=6, min_neighbors=3, first_device=0, num_devices=1,
                       views_in_flight=2, input_scale=-1, max_pixels=1700000, details=False,
-                      sgm_adaptive_penalty2=False, device_input_scaling=False):
+                      sgm_adaptive_penalty2=False, device_input_scaling=False,
+                      device_shading_prep=False, gamma_correction=False):
     """smvsrecon's scene-level run (app/smvsrecon.cc:400-745) through
     smvs_amd::reconstruct_scene: returns (reconstructed ids, skipped, seconds)
     [, input scale used if `details`].  input_scale < 0 (the default, as
@@ -240,7 +245,12 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     SSE runs it (lib/sgm_stereo.cc:310-346); off by default.
     device_input_scaling: the undist-L<input_scale> images are made on the
     device (smvs_rescale_half_gaussian, one ViewQueue task per view) instead of
-    by the host loop, with the same bytes; off by default."""
+    by the host loop, with the same bytes; off by default.
+    device_shading_prep (with use_shading): every view's shading planes are made
+    on the device (smvs_ctx_prepare_shading) instead of by the host's
+    StereoView::initialize_linear, with the same bits; off by default.
+    gamma_correction: smvsrecon's --gamma-srgb (app/smvsrecon.cc:52, 669), with
+    use_shading only."""
     lib = load()
     st = ReconSettings(image_embedding.encode(), regularization, output_scale,
                        1 if use_shading else 0, 1 if use_sgm else 0,
@@ -255,7 +265,8 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     out = np.zeros(max(cap.value, 1), np.int32)
     n = C.c_int(0); sk = C.c_int(0); secs = C.c_double(0.0); used = C.c_int(0)
     rc = lib.smvs_host_reconstruct_scene_flags(scene_dir.encode(), C.byref(st),
-        C.c_uint((1 if sgm_adaptive_penalty2 else 0) | (2 if device_input_scaling else 0)),
+        C.c_uint((1 if sgm_adaptive_penalty2 else 0) | (2 if device_input_scaling else 0)
+                 | (8 if device_shading_prep else 0) | (16 if gamma_correction else 0)),
         ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), out.ctypes.data_as(_i32p),
         C.c_int(out.size), C.byref(n), C.byref(sk), C.byref(secs), C.byref(used))
@@ -279,6 +290,37 @@ def load_byte_image(path):
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
     return out if c > 1 else out.reshape(h, w)
+
+
+def shading_planes(img, gamma=False):
+    """The host's StereoView::initialize_linear (lib/stereo_view.cc:64-84) of a
+    view with the u8 image `img` (h, w) or (h, w, c): (shading (h, w), shading
+    gradients (h, w, 2)).  Needs no device."""
+    lib = load()
+    a = np.ascontiguousarray(img, dtype=np.uint8)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    h, w, c = a.shape
+    shading = np.zeros((h, w), np.float32)
+    grad = np.zeros((h, w, 2), np.float32)
+    rc = lib.smvs_host_shading_planes(a.ctypes.data_as(_u8p), C.c_int(w), C.c_int(h),
+                                      C.c_int(c), C.c_int(1 if gamma else 0),
+                                      shading.ctypes.data_as(_fp), grad.ctypes.data_as(_fp))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    return shading, grad
+
+
+def gamma_inv_srgb_lut():
+    """imgtools::gamma_inv_srgb_lut: the inverse sRGB curve of
+    initialize_linear at the 256 values np.float32(k) / 255 an image element
+    can take -- the table smvs_ctx_prepare_shading looks up."""
+    lib = load()
+    lut = np.zeros(256, np.float32)
+    rc = lib.smvs_host_gamma_inv_srgb_lut(lut.ctypes.data_as(_fp))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    return lut
 
 
 def save_png(path, array):
