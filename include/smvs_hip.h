@@ -323,7 +323,16 @@ int smvs_light_upload(smvs_ctx *ctx, const double *A256, const double *b16);
  * (sgm_stereo.cc:154-160).  Outputs (any may be NULL):
  *   depth[w*h]  (sgm_stereo.cc:274-306),
  *   argmin[w*h] winning plane index,
- *   cost[w*h*num_steps], sgm[w*h*num_steps] u16 volumes (parity tests). */
+ *   cost[w*h*num_steps], sgm[w*h*num_steps] u16 volumes (parity tests).
+ * Plane counts: num_steps is 2 .. 128, or a multiple of 8 from 136 to 256;
+ * any other count is SMVS_ERR_INVALID before any device call.  Why 8:
+ * SGMStereo::Options::num_steps is a free integer, but the reference's default
+ * build (SMVS_ENABLE_SSE, lib/defines.h:21) aggregates in groups of eight
+ * planes (sgm_stereo.cc:355-356, 377, 399, 416) and is only defined for
+ * multiples of eight; the counts up to 128 stay as they were.  Why 256: the
+ * winner-takes-all key keeps the plane index in one byte.  The bytes above
+ * 128 planes are the reference's, as below; a 960 x 540 x 256 run holds
+ * 133 MB of warped and of cost bytes each and 1.06 GB of path bytes. */
 int smvs_sgm_run(int device, const uint8_t *main_img, int w, int h,
     const uint8_t *neighbor_img, int nw, int nh, const float *M,
     const float *t, float min_depth, float max_depth, int num_steps,
@@ -353,6 +362,10 @@ typedef struct {
     float range_neighbor[2];
 } smvs_sgm_neighbor;
 
+/* num_steps: the plane counts of smvs_sgm_run (2 .. 128, or a multiple of 8
+ * from 136 to 256: the reference's default build is defined for multiples of
+ * eight only), used by all four runs of the view; any other count is
+ * SMVS_ERR_INVALID before any device call. */
 int smvs_sgm_depth_for_view(int device, const uint8_t *main_img, int w, int h,
     const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
     uint16_t penalty1, uint16_t penalty2, float *depth);
@@ -364,7 +377,7 @@ int smvs_sgm_depth_for_view(int device, const uint8_t *main_img, int w, int h,
  * mve::image::rescale_half_size run on the device.  w, h and the neighbours'
  * width / height are the full-resolution sizes; the reprojections, the depth
  * ranges and the output map refer to the SGM-scale sizes ((s + 1) >> 1 per
- * halving). */
+ * halving).  num_steps: as for smvs_sgm_depth_for_view. */
 int smvs_sgm_depth_for_view_raw(int device, const uint8_t *main_img, int w, int h,
     int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
     int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
@@ -385,7 +398,8 @@ int smvs_sgm_depth_for_view_raw(int device, const uint8_t *main_img, int w, int 
  * penalties for which a wrap of the u16 volumes cannot be excluded,
  * 8 * (255 + max(penalty2, penalty1 * 3 / 2)) + 4 * 255 >= 65536 -- is
  * SMVS_ERR_INVALID before any device call.  penalty2 < penalty1 is accepted in
- * the adaptive mode (penalty2' >= penalty1 always) and refused in mode 0. */
+ * the adaptive mode (penalty2' >= penalty1 always) and refused in mode 0.
+ * The plane counts are those of smvs_sgm_run in both modes. */
 typedef enum { SMVS_SGM_P2_CONSTANT = 0, SMVS_SGM_P2_ADAPTIVE = 1 } smvs_sgm_p2_mode;
 
 /* smvs_sgm_run with the aggregation of sgm_stereo.cc:310-346 selectable */

@@ -94,6 +94,22 @@ max_dpp0(uint32_t v)
     return max(v, dpp_u32<CTRL, ROW_MASK, true>(0u, v));
 }
 
+// Wave-wide unsigned maximum on max_dpp0, the same in every lane: the prefix
+// maximum of the rows, row_bcast:15 / row_bcast:31 to combine the four rows,
+// the total read from lane 63 (sgm_paths_wide_kernel's minimum over a line of
+// 64 lanes, as the maximum of the complements)
+__device__ __forceinline__ uint32_t
+wave_max_dpp0(uint32_t v)
+{
+    v = max_dpp0<DPP_ROW_SHR1, DPP_ROWS_ALL>(v);
+    v = max_dpp0<DPP_ROW_SHR2, DPP_ROWS_ALL>(v);
+    v = max_dpp0<DPP_ROW_SHR4, DPP_ROWS_ALL>(v);
+    v = max_dpp0<DPP_ROW_SHR8, DPP_ROWS_ALL>(v);
+    v = max_dpp0<DPP_ROW_BCAST15, DPP_ROWS_1_3>(v);
+    v = max_dpp0<DPP_ROW_BCAST31, DPP_ROWS_2_3>(v);
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
 // ---- doubles: the two words of the value moved separately ----
 __device__ __forceinline__ double
 join_words(unsigned lo, unsigned hi)

@@ -269,7 +269,20 @@ smvs_host_sgm_depth_mode(const smvs_host_view *main_in, const smvs_host_view *su
     float min_depth, float max_depth, int device, int adaptive_penalty2,
     float *depth_out, int *out_w, int *out_h)
 {
+    return smvs_host_sgm_depth_steps(main_in, subs_in, n_subs, bundle_in, sgm_scale,
+        min_depth, max_depth, device, adaptive_penalty2, 128, depth_out, out_w, out_h);
+}
+
+extern "C" int
+smvs_host_sgm_depth_steps(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, int sgm_scale,
+    float min_depth, float max_depth, int device, int adaptive_penalty2,
+    int num_steps, float *depth_out, int *out_w, int *out_h)
+{
     try {
+        if (!SGMStereo::Options::valid_num_steps(num_steps))
+            throw std::invalid_argument("smvs_host_sgm_depth_steps: num_steps must be "
+                "in [2, 128] or a multiple of 8 in [136, 256]");
         StereoView::Ptr main_view = make_view(*main_in, false);
         std::vector<StereoView::Ptr> subs;
         for (int j = 0; j < n_subs; ++j)
@@ -277,7 +290,7 @@ smvs_host_sgm_depth_mode(const smvs_host_view *main_in, const smvs_host_view *su
         Bundle::Ptr bundle = make_bundle(bundle_in);
         SGMStereo::Options opts;
         opts.scale = sgm_scale;
-        opts.num_steps = 128;
+        opts.num_steps = num_steps;
         opts.min_depth = min_depth;
         opts.max_depth = max_depth;
         opts.device = device;
@@ -870,7 +883,21 @@ smvs_host_reconstruct_scene_flags(const char *scene_dir,
     int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
     int *n_skipped, double *seconds, int *input_scale_used)
 {
+    return smvs_host_reconstruct_scene_steps(scene_dir, o, flags, 128, view_ids,
+        n_view_ids, reconstructed_out, max_reconstructed, n_reconstructed, n_skipped,
+        seconds, input_scale_used);
+}
+
+extern "C" int
+smvs_host_reconstruct_scene_steps(const char *scene_dir,
+    const smvs_host_recon_settings *o, unsigned flags, int sgm_num_steps,
+    const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
+    int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used)
+{
     try {
+        if (!SGMStereo::Options::valid_num_steps(sgm_num_steps))
+            throw std::invalid_argument("smvs_host_reconstruct_scene_steps: sgm_num_steps "
+                "must be in [2, 128] or a multiple of 8 in [136, 256]");
         if (scene_dir == nullptr || o == nullptr)
             throw std::invalid_argument("smvs_host_reconstruct_scene: bad argument");
         if ((flags & ~(unsigned)(SMVS_HOST_SCENE_ADAPTIVE_PENALTY2
@@ -891,6 +918,7 @@ smvs_host_reconstruct_scene_flags(const char *scene_dir,
         conf.sgm_max = o->sgm_max;
         conf.sgm_scale = o->sgm_scale;
         conf.sgm_adaptive_penalty2 = (flags & SMVS_HOST_SCENE_ADAPTIVE_PENALTY2) != 0u;
+        conf.sgm_num_steps = sgm_num_steps;
         conf.device_input_scaling = (flags & SMVS_HOST_SCENE_DEVICE_INPUT_SCALING) != 0u;
         conf.device_shading_prep = (flags & SMVS_HOST_SCENE_DEVICE_SHADING_PREP) != 0u;
         conf.gamma_correction = (flags & SMVS_HOST_SCENE_GAMMA_SRGB) != 0u;

@@ -126,6 +126,14 @@ int smvs_host_sgm_depth_mode(const smvs_host_view *main_view,
     const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
     int sgm_scale, float min_depth, float max_depth, int device,
     int adaptive_penalty2, float *depth_out, int *out_w, int *out_h);
+/* The same with SGMStereo::Options::num_steps, the number of inverse-depth
+ * planes: 2 .. 128, or a multiple of 8 from 136 to 256 (include/smvs_hip.h,
+ * "plane counts"); any other count is an argument error before anything runs.
+ * smvs_host_sgm_depth and ..._mode forward to this with 128. */
+int smvs_host_sgm_depth_steps(const smvs_host_view *main_view,
+    const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
+    int sgm_scale, float min_depth, float max_depth, int device,
+    int adaptive_penalty2, int num_steps, float *depth_out, int *out_w, int *out_h);
 
 /* smvs::Surface on its own (lib/surface.cc): Surface::create (from the bundle
  * when init_depth is NULL, else from the W x H depth map) followed by a
@@ -233,6 +241,15 @@ int smvs_host_reconstruct_scene_flags(const char *scene_dir,
     const smvs_host_recon_settings *settings, unsigned flags, const int *view_ids,
     int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
     int *n_skipped, double *seconds, int *input_scale_used);
+/* The same with ReconSettings::sgm_num_steps, the inverse-depth planes of every
+ * view's SGM front end (the settings struct keeps its layout): 2 .. 128, or a
+ * multiple of 8 from 136 to 256; any other count is an argument error before
+ * the scene is read.  smvs_host_reconstruct_scene_flags forwards to this with
+ * 128. */
+int smvs_host_reconstruct_scene_steps(const char *scene_dir,
+    const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
+    const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
+    int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used);
 
 /* smvsrecon's generate_mesh (app/smvsrecon.cc:278-343, MeshGenerator::
  * generate_mesh, lib/mesh_generator.cc:160-299) on a reconstructed scene: the

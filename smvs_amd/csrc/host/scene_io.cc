@@ -398,6 +398,10 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
 {
     typedef std::chrono::steady_clock Clock;
     ReconSettings conf = conf_in;
+    // (before the scene is read and any task starts)
+    if (!SGMStereo::Options::valid_num_steps(conf.sgm_num_steps))
+        throw std::invalid_argument("sgm_num_steps must be in [2, 128] or a multiple "
+            "of 8 in [136, 256]");
     Scene::Ptr scene = Scene::create(scene_path);
     std::vector<SceneView>& views = scene->get_views();
 
@@ -574,7 +578,7 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                     if (conf.force_sgm || !have) {
                         SGMStereo::Options sgm_opts;
                         sgm_opts.scale = conf.sgm_scale;
-                        sgm_opts.num_steps = 128;
+                        sgm_opts.num_steps = conf.sgm_num_steps;
                         sgm_opts.min_depth = conf.sgm_min;
                         sgm_opts.max_depth = conf.sgm_max;
                         sgm_opts.device = device;

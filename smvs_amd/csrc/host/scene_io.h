@@ -97,6 +97,10 @@ struct ReconSettings
     // not in the reference's AppSettings: SGMStereo::Options::adaptive_penalty2
     // (the reference's build without SSE, lib/sgm_stereo.cc:310-346)
     bool sgm_adaptive_penalty2 = false;
+    // not in the reference's AppSettings (app/smvsrecon.cc:693-709 leaves
+    // SGMStereo::Options::num_steps at its default): the inverse-depth planes of
+    // the SGM front end, 2 .. 128 or a multiple of 8 from 136 to 256
+    int sgm_num_steps = 128;
     // not in the reference's AppSettings: the input scaling of :621-650 on the
     // device (rescale_half_size_gaussian_device), one ViewQueue task per view
     bool device_input_scaling = false;

@@ -16,6 +16,9 @@ public:
     {
         int debug_lvl = 0;
         int scale = 1;
+        // a free integer in the reference; the device takes 2 .. 128 and the
+        // multiples of 8 from 136 to 256 (valid_num_steps, include/smvs_hip.h
+        // "plane counts") and refuses the rest as an argument error
         int num_steps = 128;
         float min_depth = 0.0f;
         float max_depth = 0.0f;
@@ -27,6 +30,12 @@ public:
         // lib/sgm_stereo.cc:361-406), true: the build without SSE
         // (penalty2 adapted to the intensity step, lib/sgm_stereo.cc:310-346)
         bool adaptive_penalty2 = false;
+
+        // the plane counts smvs_sgm_run / smvs_sgm_depth_for_view accept
+        static bool valid_num_steps(int n)
+        {
+            return (n >= 2 && n <= 128) || (n > 128 && n <= 256 && n % 8 == 0);
+        }
     };
 
     SGMStereo(Options const& opts, StereoView::Ptr main,

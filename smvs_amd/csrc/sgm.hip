@@ -21,7 +21,8 @@
 // even plane count all eight directions run in ONE launch and add into S with
 // atomics on packed u16 pairs (integer adds commute: bit-exact); odd plane
 // counts take one launch per direction.  Each path reads C once and
-// read-modify-writes S once.
+// read-modify-writes S once.  Plane counts above 128 (multiples of 8 up to
+// SGM_MAX_PLANES): sgm_paths_wide_kernel, four planes per lane.
 #include "dpp.h"
 #include "sgm_internal.h"
 
@@ -1043,6 +1044,268 @@ sgm_all_paths_kernel(PathArgs A)
     }
 }
 
+// ---- one line per wavefront, four planes per lane, packed 16-bit arithmetic:
+// the plane counts above 128 (multiples of four up to SGM_MAX_PLANES = 256;
+// check_sgm_plane_count admits the multiples of eight) ----
+// sgm_paths2_kernel's step on a whole wave: lane l holds planes 4 l .. 4 l + 3 as
+// two u16 pairs, 64 lanes cover up to 256 planes, the cost words of the chunk
+// ahead are loaded before the recurrence of the current chunk starts.  What
+// differs from the half-wave kernel is what crosses lanes:
+//   * the neighbouring planes come from lane -+ 1 of the WAVE (wave_shr:1 /
+//     wave_shl:1 cross the rows and the 32-lane boundary); only lane 0 and, in
+//     FULL, lane 63 have no source;
+//   * the minimum of a line runs over 64 lanes (wave_max_dpp0 of the
+//     complements: four row shifts, row_bcast:15, row_bcast:31, one readlane).
+// A step's instructions serve ONE line here, not two.
+//
+// FULL: 256 planes, every lane has four (no idle lanes to reset).
+// ADAPT: penalty2' from the 256-entry LDS table of packed {p2', p2'}, read for
+// the chunk ahead (sgm_paths2_kernel's comment).
+// DELTA (largest penalty2 <= 255): L - C as one byte per cell into the
+// direction's own volume, plain stores.  Without DELTA the lane adds its two
+// u16 pairs {L, L} into S with two u32 atomics (sgm_all_paths_kernel's
+// argument: no 16-bit half of S carries, check_sgm_penalties).
+//
+// Same integers as sgm_all_paths_kernel, hence the same bytes.  Range, with
+// Pmax = the largest penalty2 of a step (<= 255 with DELTA, <= 7808 without, by
+// check_sgm_penalties): a line starts with L = C <= 255, or 2 C <= 510 at the
+// doubly seeded corner of an upward diagonal in ADAPT; a step gives
+// L = C + u - min L' with min L' <= u <= min L' + p2', so L <= 255 + Pmax
+// behind the start and every sum of a step is <= max(510, 255 + Pmax) + Pmax
+// < 2^15.  The sentinel BIG2 = 0x7FFF per half is above every L, and
+// BIG2 + P1 <= 0x7FFF + 7808 < 2^16 (P1 <= Pmax in both modes).  The DELTA
+// form marks a missing neighbour plane at the ends of the line with 0xFF00 out
+// of the byte permute: 0xFF00 + P1 <= 0xFFFF since P1 <= 255 there; without
+// DELTA the lane without a source keeps BIG2 as the DPP move's old value.
+// Bytes stored with DELTA: u - min L' <= p2' <= 255; C at a doubly seeded corner.
+template <int K, bool FULL, bool ADAPT, bool DELTA>
+__global__ void __launch_bounds__(64)
+sgm_paths_wide_kernel(PathArgs A)
+{
+    __shared__ uint32_t p2_table[ADAPT ? 256 : 1];
+    int const w = A.w, h = A.h, D = A.D;
+    // block -> (direction, line), the grid being sgm_grid_lines(); the long
+    // horizontal lines first
+    int b = blockIdx.x;
+    int dir = 0;
+    for (; dir < 8; ++dir) {
+        int const lines_of_dir = sgm_dir_lines(dir, w, h);
+        if (b < lines_of_dir)
+            break;
+        b -= lines_of_dir;
+    }
+    if (dir > 7)
+        return;
+    A.dx = SGM_DIRS[dir][0];
+    A.dy = SGM_DIRS[dir][1];
+
+    int const lane = threadIdx.x;
+    if (ADAPT) {
+        // entry d: |I - I'| = d (one wave per block: the barrier is a wait on LDS)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            uint32_t const d = (uint32_t)(lane + 64 * j);
+            uint32_t const p = max(A.p1 * 3u / 2u, A.p2 / (d + 1u));
+            p2_table[d] = p | (p << 16);
+        }
+        __syncthreads();
+    }
+    int x0 = 0, y0 = 0, len = 0, extra_seed = 0;
+    if (!path_line(A, b, &x0, &y0, &len, &extra_seed))
+        return;
+    bool const ok = FULL || 4 * lane < D;
+    int const li = ok ? lane : 0;
+    // the line as running pointers, four planes (bytes) per lane
+    size_t const o0 = (((size_t)y0 * w + x0) * D >> 2) + li;
+    ptrdiff_t const step = ((ptrdiff_t)A.dy * w + A.dx) * D / 4;
+    const uint32_t *__restrict__ cin = reinterpret_cast<const uint32_t *>(A.cost) + o0;
+    uint32_t *__restrict__ e32
+        = reinterpret_cast<uint32_t *>(A.delta + (DELTA ? (size_t)dir * A.vol : 0)) + o0;
+    // without DELTA: the lane's two u16 pairs of S
+    uint32_t *__restrict__ s32 = reinterpret_cast<uint32_t *>(A.sgm) + 2 * o0;
+    uint32_t const BIG2 = 0x7FFF7FFFu;
+    uint32_t const p1p1 = (uint32_t)A.p1 | ((uint32_t)A.p1 << 16);
+    uint32_t const p2p2 = (uint32_t)A.p2 | ((uint32_t)A.p2 << 16);
+    // ADAPT: the image bytes of the line, one per step
+    ptrdiff_t const istep = (ptrdiff_t)A.dy * w + A.dx;
+    const uint8_t *__restrict__ iin = ADAPT ? A.img + ((size_t)y0 * w + x0) : nullptr;
+    uint32_t i_before = 0;
+    // DELTA: v_perm_b32 selectors of the two neighbour vectors that reach into
+    // the adjacent lanes -- {plane 3 of the lane before, own plane 0} and {own
+    // plane 3, plane 0 of the lane after}; lane 0 and lane 63 have no such lane
+    // and take the bytes 0x00, 0xff instead, i.e. 0xff00: no such plane.  (An
+    // idle lane after the last one of the line holds BIG2: no selector needed.)
+    uint32_t const sel_below = DELTA && lane == 0 ? 0x05040d0cu : 0x05040302u;   // perm(pa, pb_prev)
+    uint32_t const sel_above = DELTA && lane == 63 ? 0x0d0c0302u : 0x05040302u;  // perm(pa_next, pb)
+
+    // ---- the first cell of the line: L = C (sgm_stereo.cc:457-464; a corner
+    // that is seeded from its row and from its column adds C twice) ----
+    uint32_t pa = BIG2, pb = BIG2;     // planes {4 l, 4 l + 1}, {4 l + 2, 4 l + 3}
+    {
+        uint32_t const c = *cin;
+        uint32_t const ca = __builtin_amdgcn_perm(0u, c, 0x0c010c00u);
+        uint32_t const cb = __builtin_amdgcn_perm(0u, c, 0x0c030c02u);
+        if (ok) {
+            pa = ca;
+            pb = cb;
+            if (ADAPT && extra_seed && A.dy < 0) {
+                pa = pk_add(ca, ca);
+                pb = pk_add(cb, cb);
+            }
+            if (DELTA) {
+                *e32 = extra_seed ? c : 0u;
+            } else {
+                (void)__hip_atomic_fetch_add(s32, extra_seed ? pk_add(ca, ca) : ca,
+                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                (void)__hip_atomic_fetch_add(s32 + 1, extra_seed ? pk_add(cb, cb) : cb,
+                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        if (ADAPT)
+            i_before = *iin;
+    }
+    cin += step;
+    e32 += step;
+    s32 += 2 * step;
+    if (ADAPT)
+        iin += istep;
+    // the remaining steps of the line, a scalar
+    int const rest = max(__builtin_amdgcn_readfirstlane(len) - 1, 0);
+
+    uint32_t c_cur[K], c_next[K], outa[K], outb[K];
+    uint32_t far_cur[K], far_next[K];   // ADAPT: {p2', p2'} of the steps
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        c_cur[k] = 0;
+        if (k < rest)
+            c_cur[k] = cin[(ptrdiff_t)k * step];
+    }
+    cin += (ptrdiff_t)K * step;
+    if (ADAPT) {
+        uint32_t iv[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            iv[k] = 0;
+            if (k < rest)
+                iv[k] = iin[(ptrdiff_t)k * istep];
+        }
+        iin += (ptrdiff_t)K * istep;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            uint32_t const d = iv[k] > i_before ? iv[k] - i_before : i_before - iv[k];
+            far_cur[k] = p2_table[d];
+            i_before = iv[k];
+        }
+    }
+    // one chunk of K steps; FAST: this chunk and the next lie inside the line
+    // (no predicates on the loads and stores)
+    auto const chunk = [&](auto fast_tag, int base) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            c_next[k] = 0;
+            if (FAST || base + K + k < rest)
+                c_next[k] = cin[(ptrdiff_t)k * step];
+        }
+        uint32_t iv[K];
+        if (ADAPT) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                iv[k] = 0;
+                if (FAST || base + K + k < rest)
+                    iv[k] = iin[(ptrdiff_t)k * istep];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            outa[k] = outb[k] = 0;
+            if (FAST || base + k < rest) {
+                // the four cost bytes as two u16 pairs
+                uint32_t const ca = __builtin_amdgcn_perm(0u, c_cur[k], 0x0c010c00u);
+                uint32_t const cb = __builtin_amdgcn_perm(0u, c_cur[k], 0x0c030c02u);
+                // the minimum over the line: per lane, then over the wave
+                uint32_t m = pk_min(pa, pb);
+                m = wave_max_dpp0(~min(m & 0xFFFFu, m >> 16));
+                uint32_t const mn = ~m;
+                uint32_t const mnmn = mn | (mn << 16);
+                uint32_t const far = pk_add(mnmn, ADAPT ? far_cur[k] : p2p2);
+                // neighbouring planes: {3 of the lane before, 0}, {1, 2}, {3, 0 of the lane after}
+                uint32_t pb_prev, pa_next;
+                if (DELTA) {
+                    // (a lane without a source reads 0; its selector does not
+                    // look at what arrives)
+                    pb_prev = dpp_u32<DPP_WAVE_SHR1, DPP_ROWS_ALL, true>(0u, pb);
+                    pa_next = dpp_u32<DPP_WAVE_SHL1, DPP_ROWS_ALL, true>(0u, pa);
+                } else {
+                    pb_prev = lane_prev(pb, BIG2);
+                    pa_next = lane_next(pa, BIG2);
+                }
+                uint32_t const below_a = __builtin_amdgcn_perm(pa, pb_prev, sel_below);
+                uint32_t const mid = __builtin_amdgcn_alignbit(pb, pa, 16);
+                uint32_t const above_b = __builtin_amdgcn_perm(pa_next, pb, sel_above);
+                uint32_t const mid1 = pk_add(mid, p1p1);
+                // :310-346: L = C + min(L'(d), L'(d -+ 1) + P1, min L' + P2) - min L'
+                uint32_t const ua = pk_min(pk_min(pa, pk_add(below_a, p1p1)), pk_min(mid1, far));
+                uint32_t const ub = pk_min(pk_min(pb, mid1), pk_min(pk_add(above_b, p1p1), far));
+                uint32_t const ea = pk_sub(ua, mnmn), eb = pk_sub(ub, mnmn);
+                pa = pk_add(ca, ea);
+                pb = pk_add(cb, eb);
+                if (DELTA) {
+                    outa[k] = __builtin_amdgcn_perm(eb, ea, 0x06040200u);
+                } else {
+                    outa[k] = pa;
+                    outb[k] = pb;
+                }
+                if (!FULL && !ok)
+                    pa = pb = BIG2;
+            }
+        }
+        if (ADAPT) {
+            // the penalties of the chunk ahead (a step past the end of the line
+            // reads image byte 0: an entry of the table like any other, and what
+            // that step computes is never stored)
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                uint32_t const d = iv[k] > i_before ? iv[k] - i_before : i_before - iv[k];
+                far_next[k] = p2_table[d];
+                i_before = iv[k];
+            }
+        }
+        if (FULL || ok) {
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                if (FAST || base + k < rest) {
+                    if (DELTA) {
+                        e32[(ptrdiff_t)k * step] = outa[k];
+                    } else {
+                        (void)__hip_atomic_fetch_add(&s32[2 * (ptrdiff_t)k * step], outa[k],
+                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        (void)__hip_atomic_fetch_add(&s32[2 * (ptrdiff_t)k * step + 1], outb[k],
+                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+        }
+    };
+    for (int base = 0; base < rest; base += K) {
+        if (base + 2 * K <= rest)
+            chunk(std::true_type(), base);
+        else
+            chunk(std::false_type(), base);
+        cin += (ptrdiff_t)K * step;
+        e32 += (ptrdiff_t)K * step;
+        s32 += 2 * (ptrdiff_t)K * step;
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            c_cur[k] = c_next[k];
+        if (ADAPT) {
+            iin += (ptrdiff_t)K * istep;
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                far_cur[k] = far_next[k];
+        }
+    }
+}
+
 // The end of both WTA kernels (sgm_stereo.cc:300-303): the winning plane is the
 // low byte of the (value, plane) key; no depth for the two nearest planes and
 // for dark pixels.
@@ -1123,6 +1386,48 @@ sgm_sum_wta_kernel(const uint8_t *__restrict__ cost, const uint8_t *__restrict__
         wta_store(key, p, main_img, depths, depth, argmin);
 }
 
+// The same with 64 lanes per pixel, for the plane counts above 128: a wavefront
+// is one pixel, so the minimum over the four rows of 16 lanes is the wave's
+// (row_prefix_min_u32, then row_bcast:15 / row_bcast:31 -- wave_min_u32).  The
+// plane index uses the key's whole low byte at 256 planes; S < 2^16 keeps
+// value * 256 + plane inside 32 bits.
+__global__ void __launch_bounds__(256)
+sgm_sum_wta_wide_kernel(const uint8_t *__restrict__ cost, const uint8_t *__restrict__ delta,
+    size_t vol, const uint8_t *__restrict__ main_img, const float *__restrict__ depths,
+    size_t npix, int D, float *__restrict__ depth, int32_t *__restrict__ argmin,
+    uint16_t *__restrict__ sgm_out)
+{
+    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    int const sub = threadIdx.x & 63;
+    int const d0 = 4 * sub;
+    uint32_t key = 0xFFFFFFFFu;
+    if (p < npix && d0 < D) {
+        size_t const o = p * (size_t)D + d0;   // D % 4 == 0: aligned u32
+        uint32_t const c = *reinterpret_cast<const uint32_t *>(cost + o);
+        uint32_t e[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            e[k] = *reinterpret_cast<const uint32_t *>(delta + (size_t)k * vol + o);
+        uint32_t sv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            uint32_t sum = 8u * ((c >> (8 * j)) & 0xFFu);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                sum += (e[k] >> (8 * j)) & 0xFFu;
+            sv[j] = sum & 0xFFFFu;
+            key = min(key, sv[j] * 256u + (uint32_t)(d0 + j));
+        }
+        if (sgm_out != nullptr) {
+            uint2 const packed = make_uint2(sv[0] | (sv[1] << 16), sv[2] | (sv[3] << 16));
+            *reinterpret_cast<uint2 *>(sgm_out + o) = packed;
+        }
+    }
+    key = wave_min_u32(key);
+    if (sub == 63 && p < npix)
+        wta_store(key, p, main_img, depths, depth, argmin);
+}
+
 __global__ void __launch_bounds__(256)
 widen_u8_kernel(const uint8_t *__restrict__ src, uint16_t *__restrict__ dst,
     size_t n)
@@ -1198,14 +1503,24 @@ check_sgm_penalties(unsigned penalty1, unsigned penalty2, int p2_mode)
     return SMVS_OK;
 }
 
+// (declared in sgm_internal.h)
+int
+check_sgm_plane_count(int num_steps)
+{
+    SMVS_REQUIRE(sgm_plane_count_ok(num_steps),
+        "num_steps must be in [2, 128] or a multiple of 8 in [136, 256]");
+    return SMVS_OK;
+}
+
 static int
 check_sgm_options(int num_steps, float min_depth, float max_depth,
     unsigned penalty1, unsigned penalty2, int p2_mode = SMVS_SGM_P2_CONSTANT)
 {
     SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
         "unknown penalty2 mode");
-    SMVS_REQUIRE(num_steps >= 2 && num_steps <= 128,
-        "num_steps must be in [2, 128]");
+    int const rc = check_sgm_plane_count(num_steps);
+    if (rc != SMVS_OK)
+        return rc;
     SMVS_REQUIRE(min_depth > 0.f && max_depth > min_depth, "bad depth range");
     return check_sgm_penalties(penalty1, penalty2, p2_mode);
 }
@@ -1231,7 +1546,7 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     if ((rc = B.ensure(npix, num_steps, pmax)) != SMVS_OK)
         return rc;
     // sgm_stereo.cc:195-203: inverse-depth planes by repeated float addition
-    float depths[128];
+    float depths[SGM_MAX_PLANES];
     {
 #pragma clang fp contract(off)
         float inv_depth = 1.0f / max_depth;
@@ -1241,7 +1556,7 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
             inv_depth += increment;
         }
     }
-    float *d_depths = B.depths + 128 * B.runs;
+    float *d_depths = B.depths + SGM_MAX_PLANES * B.runs;
     B.runs += 1;
     if ((rc = B.ws->upload(d_depths, depths, sizeof(float) * num_steps)) != SMVS_OK)
         return rc;
@@ -1303,7 +1618,35 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
         const char *e = std::getenv("SMVS_SGM_PATHS");
         return e != nullptr && e[0] == 'w';
     }();
-    if (df && (num_steps & 3) == 0 && num_steps <= 128 && !wave_per_line) {
+    if (num_steps > 128) {
+        // a line per wave, four planes per lane (multiples of 8 up to
+        // SGM_MAX_PLANES: check_sgm_plane_count); S zeroed for the atomics
+        if (!df)
+            SMVS_HIP_CHECK(hipMemsetAsync(B.sgm, 0, sizeof(uint16_t) * vol, stream));
+        P.dx = P.dy = 0;
+        P.first = 0;
+        int const lines = sgm_grid_lines(w, h);
+        bool const full = num_steps == SGM_MAX_PLANES;
+        SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_PATHS);
+        auto const launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(lines), dim3(64), 0, stream, P);
+        };
+        if (df) {
+            if (adapt)
+                full ? launch(sgm_paths_wide_kernel<8, true, true, true>)
+                     : launch(sgm_paths_wide_kernel<8, false, true, true>);
+            else
+                full ? launch(sgm_paths_wide_kernel<8, true, false, true>)
+                     : launch(sgm_paths_wide_kernel<8, false, false, true>);
+        } else {
+            if (adapt)
+                full ? launch(sgm_paths_wide_kernel<8, true, true, false>)
+                     : launch(sgm_paths_wide_kernel<8, false, true, false>);
+            else
+                full ? launch(sgm_paths_wide_kernel<8, true, false, false>)
+                     : launch(sgm_paths_wide_kernel<8, false, false, false>);
+        }
+    } else if (df && (num_steps & 3) == 0 && num_steps <= 128 && !wave_per_line) {
         P.dx = P.dy = 0;
         P.first = 0;
         int const pairs = sgm_grid_line_pairs(w, h);
@@ -1358,7 +1701,12 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     SMVS_HIP_CHECK(hipGetLastError());
     {
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_WTA);
-        if (df)
+        if (df && num_steps > 128)
+            hipLaunchKernelGGL(sgm_sum_wta_wide_kernel,
+                dim3((unsigned)((npix * 64 + 255) / 256)), dim3(256), 0, stream,
+                B.cost, B.delta, vol, d_main, d_depths, npix, num_steps, d_depth,
+                B.argmin, B.want_sgm ? B.sgm : nullptr);
+        else if (df)
             hipLaunchKernelGGL(sgm_sum_wta_kernel,
                 dim3((unsigned)((npix * 32 + 255) / 256)), dim3(256), 0, stream,
                 B.cost, B.delta, vol, d_main, d_depths, npix, num_steps, d_depth,

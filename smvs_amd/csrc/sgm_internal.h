@@ -54,6 +54,26 @@ enum {
 };
 static_assert(WS_DELTA < Workspace::SLOTS, "the last slot must exist in a Workspace");
 
+// The largest plane count of a run: the key of the WTA kernels is
+// value * 256 + plane (one byte for the plane), and 64 lanes x 4 planes is one
+// wavefront per line in sgm_paths_wide_kernel.
+constexpr int SGM_MAX_PLANES = 256;
+
+// The plane counts a run takes: 2 .. 128 (any), and the multiples of 8 from 136
+// to SGM_MAX_PLANES.  Why 8: SGMStereo::Options::num_steps is a free integer,
+// but the reference's default build (SMVS_ENABLE_SSE) aggregates in groups of
+// eight planes (lib/sgm_stereo.cc:355-356, 377, 399, 416) and is only defined
+// for multiples of eight; the counts up to 128 keep what they always took.
+__host__ __device__ __forceinline__ constexpr bool
+sgm_plane_count_ok(int num_steps)
+{
+    return (num_steps >= 2 && num_steps <= 128)
+        || (num_steps > 128 && num_steps <= SGM_MAX_PLANES && (num_steps % 8) == 0);
+}
+static_assert(sgm_plane_count_ok(2) && sgm_plane_count_ok(127) && sgm_plane_count_ok(136)
+        && sgm_plane_count_ok(256) && !sgm_plane_count_ok(1) && !sgm_plane_count_ok(129)
+        && !sgm_plane_count_ok(132) && !sgm_plane_count_ok(264), "the plane-count rule");
+
 // Work buffers of one run_sgm inside a pooled workspace; reused by the runs of
 // a view (the runs are ordered on the workspace's stream).  Every run has its
 // own depth table.
@@ -89,7 +109,7 @@ struct SgmWorkspace {
         size_t const vol = npix * (size_t)num_steps;
         bool const df = delta_form(num_steps, penalty2);
         int rc;
-        if ((rc = ws->ensure(WS_DEPTHS, (size_t)128 * MAX_RUNS, &depths))
+        if ((rc = ws->ensure(WS_DEPTHS, (size_t)SGM_MAX_PLANES * MAX_RUNS, &depths))
             || (rc = ws->ensure(WS_CENSUS, npix, &census))
             || (rc = ws->ensure(WS_WARPED, vol, &warped))
             || (rc = ws->ensure(WS_COST, vol, &cost))
@@ -106,6 +126,9 @@ struct SgmWorkspace {
 // The penalties alone (no device involved: the *_mode entries call this before
 // anything else).
 int check_sgm_penalties(unsigned penalty1, unsigned penalty2, int p2_mode);
+// The plane count alone (sgm_plane_count_ok; no device involved: every entry
+// calls this before its first device call).
+int check_sgm_plane_count(int num_steps);
 
 // SGMStereo::run_sgm (sgm_stereo.cc:98-124) on device images; the depth map
 // (and optionally argmin) stay on the device.  Asynchronous on the workspace's
@@ -137,8 +160,8 @@ sgm_dir_lines(int k, int w, int h)
     return SGM_DIRS[k][1] == 0 ? h : (SGM_DIRS[k][0] == 0 ? w : w + h - 1);
 }
 
-// Grid of the all-direction kernels: a block per line (sgm_all_paths_kernel),
-// or per pair of adjacent lines of one direction (sgm_paths2_kernel).  The
+// Grid of the all-direction kernels: a block per line (sgm_all_paths_kernel,
+// sgm_paths_wide_kernel), or per pair of adjacent lines of one direction (sgm_paths2_kernel).  The
 // kernels find (direction, line) by walking the same counts.
 __host__ __device__ __forceinline__ constexpr int
 sgm_grid_lines(int w, int h)

@@ -85,6 +85,10 @@ sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
         if (prc != SMVS_OK)
             return prc;
     }
+    // (before the first device call, as the penalties: sgm_run_device checks
+    // both again)
+    if (int const src = check_sgm_plane_count(num_steps); src != SMVS_OK)
+        return src;
     SMVS_REQUIRE(main_img && neighbors && depth, "null argument");
     SMVS_REQUIRE(n_neighbors >= 1 && n_neighbors <= 2,
         "one or two neighbours (app/smvsrecon.cc:360-365)");

@@ -233,7 +233,7 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       num_neighbors=6, min_neighbors=3, first_device=0, num_devices=1,
                       views_in_flight=2, input_scale=-1, max_pixels=1700000, details=False,
                       sgm_adaptive_penalty2=False, device_input_scaling=False,
-                      device_shading_prep=False, gamma_correction=False):
+                      device_shading_prep=False, gamma_correction=False, sgm_num_steps=128):
     """smvsrecon's scene-level run (app/smvsrecon.cc:400-745) through
     smvs_amd::reconstruct_scene: returns (reconstructed ids, skipped, seconds)
     [, input scale used if `details`].  input_scale < 0 (the default, as
@@ -250,7 +250,10 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     on the device (smvs_ctx_prepare_shading) instead of by the host's
     StereoView::initialize_linear, with the same bits; off by default.
     gamma_correction: smvsrecon's --gamma-srgb (app/smvsrecon.cc:52, 669), with
-    use_shading only."""
+    use_shading only.
+    sgm_num_steps: the inverse-depth planes of the SGM front end
+    (SGMStereo::Options::num_steps): 2 .. 128, or a multiple of 8 from 136 to
+    256; smvsrecon runs 128."""
     lib = load()
     st = ReconSettings(image_embedding.encode(), regularization, output_scale,
                        1 if use_shading else 0, 1 if use_sgm else 0,
@@ -264,9 +267,10 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                              C.byref(cap), None, None, None, None, None, None, None)
     out = np.zeros(max(cap.value, 1), np.int32)
     n = C.c_int(0); sk = C.c_int(0); secs = C.c_double(0.0); used = C.c_int(0)
-    rc = lib.smvs_host_reconstruct_scene_flags(scene_dir.encode(), C.byref(st),
+    rc = lib.smvs_host_reconstruct_scene_steps(scene_dir.encode(), C.byref(st),
         C.c_uint((1 if sgm_adaptive_penalty2 else 0) | (2 if device_input_scaling else 0)
                  | (8 if device_shading_prep else 0) | (16 if gamma_correction else 0)),
+        C.c_int(sgm_num_steps),
         ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), out.ctypes.data_as(_i32p),
         C.c_int(out.size), C.byref(n), C.byref(sk), C.byref(secs), C.byref(used))
@@ -410,10 +414,12 @@ def view_queue_selftest(n_tasks, num_devices, views_in_flight, throwing_task=-1)
 
 
 def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
-              adaptive_penalty2=False):
+              adaptive_penalty2=False, num_steps=128):
     """reconstruct_sgm_depth_for_view through the host mirror.
     adaptive_penalty2: SGMStereo::Options::adaptive_penalty2 (the reference's
-    build without SSE, lib/sgm_stereo.cc:310-346); off by default."""
+    build without SSE, lib/sgm_stereo.cc:310-346); off by default.
+    num_steps: SGMStereo::Options::num_steps, the inverse-depth planes: 2 .. 128,
+    or a multiple of 8 from 136 to 256."""
     lib = load()
     keep = []
     main, subs, n_subs, b = _marshal(inputs, keep)
@@ -422,9 +428,9 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
         w, h = (w + 1) // 2, (h + 1) // 2
     out = np.zeros((h, w), dtype=np.float32)
     ow = C.c_int(0); oh = C.c_int(0)
-    rc = lib.smvs_host_sgm_depth_mode(C.byref(main), subs, n_subs, C.byref(b),
+    rc = lib.smvs_host_sgm_depth_steps(C.byref(main), subs, n_subs, C.byref(b),
         sgm_scale, C.c_float(min_depth), C.c_float(max_depth), device,
-        C.c_int(1 if adaptive_penalty2 else 0), out.ctypes.data_as(_fp), C.byref(ow), C.byref(oh))
+        C.c_int(1 if adaptive_penalty2 else 0), C.c_int(num_steps), out.ctypes.data_as(_fp), C.byref(ow), C.byref(oh))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
     assert (ow.value, oh.value) == (w, h)
