@@ -62,22 +62,106 @@ struct ReactivateArgs {
     int check_stop;
 };
 
-// One thread per (patch, full-resolution pixel): project with the old and
-// the updated nodes into every visible neighbour (pixel coordinates WITHOUT
-// the +0.5 convention, depth_optimizer.cc:669-672).
-// (Round 6 also measured a variant that stages the 32 doubles of a workgroup's
-// <= 64 patches in LDS instead of loading them per pixel thread: 23.5 / 27.9 us
-// against 26.4 us on three boxes, nothing outside the box-to-box spread.  Not
-// kept.)
+// The sixteen x-direction FMAs of eval_patch's value: they depend only on the
+// pixel's column, so a thread that owns several rows of one column forms them
+// once.  Same operations in the same order as eval_patch (explicit FMAs): the
+// bits of the value are the same.
+__device__ __forceinline__ void
+eval_patch_column(const double *tab, int ci, double const theta[16], double g[4])
+{
+    const double *X = tab + (size_t)ci * 12;
+#pragma unroll
+    for (int ey = 0; ey < 4; ++ey) {
+        double g0 = 0.0;
+#pragma unroll
+        for (int ex = 0; ex < 4; ++ex) {
+            int const a = ex & 1, ix = ex >> 1, b = ey & 1, iy = ey >> 1;
+            g0 = __builtin_fma(theta[4 * (2 * b + a) + ix + 2 * iy], X[ex * 3 + 0], g0);
+        }
+        g[ey] = g0;
+    }
+}
+
+// ... and the four y-direction FMAs that finish the value at row cj
+__device__ __forceinline__ double
+eval_patch_row(const double *tab, int cj, double const g[4])
+{
+    const double *Y = tab + (size_t)cj * 12;
+    double v = 0.0;
+#pragma unroll
+    for (int ey = 0; ey < 4; ++ey)
+        v = __builtin_fma(g[ey], Y[ey * 3 + 0], v);
+    return v;
+}
+
+// One pixel (u, v) against one neighbour: did its reprojection move by more
+// than the threshold (th2 = threshold^2); FULL: the shift itself is added to
+// *sum.
+//   (w0 p + t0)/(w0 r + t2) - (w1 p + t0)/(w1 r + t2)
+//     = (w0 - w1)(p t2 - r t0) / ((w0 r + t2)(w1 r + t2)):
+// no cancellation; the numerators are affine in the pixel
+// (depth_optimizer.cc:669-672, 277-303).
+// The comparison decides an active set, so the roundings are part of the
+// result: the source fixes which product fuses with which sum (contraction
+// off, the FMAs written out) instead of leaving it to the compiler, whose
+// choice follows the shape of the surrounding code -- with several pixels of
+// one column per thread M[6] * u has several uses and would no longer be the
+// product that fuses.  These are the fusions of the one-pixel kernel of
+// rounds 1-6 as compiled (read from its instruction sequence):
+//   r = fma(M6, u, M7 v) + M8, likewise nx and ny; den = fma(w0, r, t2) *
+//   fma(w1, r, t2); nx^2 + ny^2 = fma(nx, nx, ny ny).
+template <bool FULL>
+__device__ __forceinline__ bool
+pixel_moved(const double *M, const double *t, const double *sh, double u, double v,
+    double w0, double w1, double dw, double th2, double *sum)
+{
+#pragma clang fp contract(off)
+    double const r = __builtin_fma(M[6], u, M[7] * v) + M[8];
+    double const nx = __builtin_fma(sh[0], u, sh[1] * v) + sh[2];
+    double const ny = __builtin_fma(sh[3], u, sh[4] * v) + sh[5];
+    double const den = __builtin_fma(w0, r, t[2]) * __builtin_fma(w1, r, t[2]);
+    double const num2 = (dw * dw) * __builtin_fma(nx, nx, ny * ny);
+    if (FULL) {
+        // the mean shift needs the quotient itself
+        double inv = __builtin_amdgcn_rcp(den);
+        inv = __builtin_fma(__builtin_fma(-den, inv, 1.0), inv, inv);
+        inv = __builtin_fma(__builtin_fma(-den, inv, 1.0), inv, inv);
+        double const d2 = num2 * inv * inv;
+        *sum += sqrt(d2);
+        return d2 > th2;
+    }
+    // shift^2 > threshold^2 without the division
+    return num2 > th2 * (den * den);
+}
+
+// One thread per (patch, column ci, K consecutive rows) of the
+// full-resolution pixels: project with the old and the updated nodes into
+// every visible neighbour (pixel coordinates WITHOUT the +0.5 convention,
+// depth_optimizer.cc:669-672).  A patch has ps^2 / K threads; K <= ps.
+// What the K pixels of a thread share is done once: the patch record (32
+// doubles, 16 vector loads), the x-direction sums of the bicubic
+// (eval_patch_column) and the walk over the neighbours with its scalar loads
+// of the camera words.  Inside the walk the K pixel tests do not depend on
+// one another, but as compiled they run one after the other through the same
+// registers: the saving is the shared loads, x-direction FMAs and scalar work
+// and the four times fewer waves, not an overlap of the K tests.
 // FULL: DepthOptimizer::Options::full_optimization (the mean shift instead of
 // the active set, depth_optimizer.cc:277-288).  A template argument since round
 // 6: as a run-time flag the compiler evaluated BOTH variants of the test for
 // every neighbour and selected (38 FP64 instructions per neighbour where the
 // active-set test needs 20).
-template <bool FULL>
+// Without FULL the result (the flags) does not depend on K: every pixel's test
+// has the bits of the one-pixel kernel.  With FULL a thread adds its K pixels'
+// shifts before the wave and workgroup sums, so the association of the mean's
+// sum changes with K in the last bits -- as it already does from run to run:
+// the workgroups' sums meet in atomics, and the mean is only compared with
+// the 0.01 threshold.
+template <bool FULL, int K>
 __global__ void __launch_bounds__(256)
 reactivate_kernel(ReactivateArgs A)
 {
+    static_assert(K == 1 || K == 2 || K == 4, "rows per thread");
+    constexpr int LOG2K = K == 4 ? 2 : K == 2 ? 1 : 0;
     long long const gid0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     // (the wave-uniform words every thread needs first, asked for together: as
     // three tests in a row they were three scalar round trips before a wave's
@@ -93,8 +177,11 @@ reactivate_kernel(ReactivateArgs A)
     // it was known (live_count < 0)
     int const live_count = A.live_list == nullptr ? A.num_patches
         : (A.live_count >= 0 ? A.live_count : live_on_device);
-    if (((long long)live_count << (2 * A.ps_log2))
-        > (long long)gridDim.x * blockDim.x) {
+    // threads of a patch: ps^2 / K (the patch size is a power of two: shifts
+    // instead of 64-bit divisions, which cost more than the arithmetic of a
+    // pixel)
+    int const tshift = 2 * A.ps_log2 - LOG2K;
+    if (((long long)live_count << tshift) > (long long)gridDim.x * blockDim.x) {
         // (cannot happen behind a patch kernel of the same step, which is
         // sized for the same length and would have abandoned the step)
         if (gid0 == 0)
@@ -104,24 +191,12 @@ reactivate_kernel(ReactivateArgs A)
     // NaN guard of the reference on delta[0] (depth_optimizer.cc:267)
     if (isnan(x0))
         return;
-    // (the patch size is a power of two: shifts instead of 64-bit divisions,
-    // which cost more than the arithmetic of a pixel)
-    // (measured: one thread per 16-pixel chunk, loading the nodes once per
-    // chunk, is slower -- 40 instead of 25 us: too few waves to hide the
-    // latency of its serial pixels)
-    int const slot = (int)(gid0 >> (2 * A.ps_log2));
-    int const pid = (int)(gid0 & (long long)((1 << (2 * A.ps_log2)) - 1));
+    int const slot = (int)(gid0 >> tshift);
+    int const tid = (int)(gid0 & (long long)((1 << tshift) - 1));
     // Round 6: ONE level of dependent loads behind the list entry (before: list
     // entry -> validity -> active flags -> nodes and deltas -> visibility mask):
     // everything that depends only on the patch id is asked for at once, whether
     // or not the patch turns out to need evaluation.
-    // (What the kernel's 24 us are -- measured, profiles/r6_reactivate_counters.txt:
-    // a wave lives 11,600 cycles at eight per SIMD, issuing 16 % of them, waiting
-    // for memory 45 %, stalled at issue 39 % (109 FP64 instructions per wave at
-    // four cycles each, eight waves taking turns).  Round 6 halved its vector
-    // instructions (the template argument), flattened this chain and cut its
-    // stores to one lane per patch, each for nothing measurable: the three
-    // effects overlap, and what remains is ~27 waves per SIMD x 4.8 us / 8.)
     int patch = -1;
     if (slot < live_count)
         patch = A.live_list != nullptr ? A.live_list[slot] : slot;
@@ -147,43 +222,31 @@ reactivate_kernel(ReactivateArgs A)
     double sum = 0.0, cnt = 0.0;
     bool moved = false;
     if (in_range && valid && act != 0) {
-        {
-            double const th2 = A.threshold * A.threshold;
-            int const ci = pid & (A.ps - 1), cj = pid >> A.ps_log2;
-            double w0, dw, dum0, dum1;
-            eval_patch(A.hermite_tab, ci, cj, th0, &w0, &dum0, &dum1);
-            eval_patch(A.hermite_tab, ci, cj, thd, &dw, &dum0, &dum1);
-            double const w1 = w0 + dw;
-            double const u = (double)(A.start_x + ix * A.ps + ci);
-            double const v = (double)(A.start_y + iy * A.ps + cj);
-            for (int j = 0; j < A.n_subs; ++j) {
-                if (!((vis >> j) & 1u))
-                    continue;
-                const double *M = A.cams->M[j];
-                const double *t = A.cams->t[j];
-                const double *sh = A.cams->shift[j];
-                // (w0 p + t0)/(w0 r + t2) - (w1 p + t0)/(w1 r + t2)
-                //   = (w0 - w1)(p t2 - r t0) / ((w0 r + t2)(w1 r + t2)):
-                // no cancellation; the numerators are affine in the pixel
-                // (depth_optimizer.cc:669-672, 277-303)
-                double const r = M[6] * u + M[7] * v + M[8];
-                double const nx = sh[0] * u + sh[1] * v + sh[2];
-                double const ny = sh[3] * u + sh[4] * v + sh[5];
-                double const den = (w0 * r + t[2]) * (w1 * r + t[2]);
-                double const num2 = dw * dw * (nx * nx + ny * ny);
+        double const th2 = A.threshold * A.threshold;
+        int const ci = tid & (A.ps - 1), cj0 = (tid >> A.ps_log2) << LOG2K;
+        double g0[4], gd[4];
+        eval_patch_column(A.hermite_tab, ci, th0, g0);
+        eval_patch_column(A.hermite_tab, ci, thd, gd);
+        double w0[K], w1[K], dw[K], v[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            w0[k] = eval_patch_row(A.hermite_tab, cj0 + k, g0);
+            dw[k] = eval_patch_row(A.hermite_tab, cj0 + k, gd);
+            w1[k] = w0[k] + dw[k];
+            v[k] = (double)(A.start_y + iy * A.ps + cj0 + k);
+        }
+        double const u = (double)(A.start_x + ix * A.ps + ci);
+        for (int j = 0; j < A.n_subs; ++j) {
+            if (!((vis >> j) & 1u))
+                continue;
+            const double *M = A.cams->M[j];
+            const double *t = A.cams->t[j];
+            const double *sh = A.cams->shift[j];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
                 cnt += 1.0;
-                if (FULL) {
-                    // the mean shift needs the quotient itself
-                    double inv = __builtin_amdgcn_rcp(den);
-                    inv = __builtin_fma(__builtin_fma(-den, inv, 1.0), inv, inv);
-                    inv = __builtin_fma(__builtin_fma(-den, inv, 1.0), inv, inv);
-                    double const d2 = num2 * inv * inv;
-                    sum += sqrt(d2);
-                    moved |= d2 > th2;
-                } else {
-                    // shift^2 > threshold^2 without the division
-                    moved |= num2 > th2 * (den * den);
-                }
+                moved |= pixel_moved<FULL>(M, t, sh, u, v[k], w0[k], w1[k], dw[k],
+                    th2, &sum);
             }
         }
     }
@@ -191,10 +254,10 @@ reactivate_kernel(ReactivateArgs A)
         // One lane per patch and wave raises the four flags (rounds 1-5: every
         // pixel that moved wrote them -- in a first step nearly all of 2 M
         // threads, four byte stores each to 128 k distinct bytes).  The lanes of
-        // a patch are an aligned group of min(64, ps^2): they share the patch and
-        // its node ids.
+        // a patch are an aligned group of min(64, ps^2 / K): they share the patch
+        // and its node ids.
         int const lane = (int)(threadIdx.x & 63u);
-        int const group = 2 * A.ps_log2 >= 6 ? 64 : 1 << (2 * A.ps_log2);
+        int const group = tshift >= 6 ? 64 : 1 << tshift;
         unsigned long long const votes = __ballot(moved);
         unsigned long long const mine = group >= 64 ? ~0ull
             : ((1ull << group) - 1ull) << (lane & ~(group - 1));
@@ -232,6 +295,38 @@ reactivate_kernel(ReactivateArgs A)
         atomicAdd(&A.scalars[S_SUMDIFF], s);
         atomicAdd(&A.scalars[S_COUNT_DIFF], c);
     }
+}
+
+// Pixels per thread of reactivate_kernel at patch size 2^ps_log2: four at every
+// scale, never more than the patch has rows.  Measured per launch on MI355X
+// (1920 x 1080, 8 neighbours, the Newton loops of one optimize(), scales 2 / 3 /
+// 4 / 5 / 6; profiles/reactivate_after.txt):
+//   one pixel per thread (rounds 1-6)   33 / 31 / 30 / 23 / 17 us
+//   one, this kernel with K = 1         36 / 33 / 32 / 24 / 19 us
+//   two                                 24 / 23 / 22 / 17 / 13 us
+//   four                                22 / 21 / 19 / 15.5 / 12.5 us
+// and sixteen (one thread per 4 x 4 chunk, round 6) 40 us where one took 25:
+// too few waves to hide the latency of its serial pixels.  With one pixel per
+// thread a wave lived 11,300 cycles and issued during 16 % of them
+// (profiles/reactivate_before.txt); staging the patch records of a workgroup in
+// LDS changed nothing then (round 6) and was not tried again.  Not tried on top
+// of four pixels: wave-uniform loads of the patch record where a whole wave
+// shares a patch, the neighbours' camera words staged once per workgroup.
+// SMVS_REACTIVATE_PIXELS=1|2|4 (read once) forces one value for every scale:
+// tests/test_gpu_reactivate_pixels.py runs each, and it is the A/B switch of
+// the table above.
+static int
+reactivate_pixels(int ps_log2)
+{
+    static int const forced = [] {
+        const char *e = std::getenv("SMVS_REACTIVATE_PIXELS");
+        int const k = e != nullptr ? std::atoi(e) : 0;
+        return k == 1 || k == 2 || k == 4 ? k : 0;
+    }();
+    int k = forced != 0 ? forced : 4;
+    while (k > (1 << ps_log2))
+        k >>= 1;
+    return k;
 }
 
 // delta[0] NaN guard (depth_optimizer.cc:267-268) and reset of the next set
@@ -582,15 +677,19 @@ reactivate_launch(smvs_ctx *ctx, double threshold, int full_optimization,
     A.live_list = known_live >= 0 ? ctx->live_list : nullptr;
     A.live_count = pipe != nullptr ? -1 : known_live;   // -1: read on the device
     A.check_stop = pipe != nullptr ? 1 : 0;
+    // ps^2 / K threads per patch of the list (or of the surface)
+    int const K = reactivate_pixels(ctx->scale);
     long long const items = (long long)(known_live >= 0 ? known_live
-        : ctx->num_patches) * ctx->patchsize * ctx->patchsize;
+        : ctx->num_patches) * ctx->patchsize * ctx->patchsize / K;
     {
         ScopedKernelTimer timer(ctx, SMVS_K_REACTIVATE);
         dim3 const grid((unsigned)((items + 255) / 256 > 0 ? (items + 255) / 256 : 1));
-        if (full_optimization)
-            hipLaunchKernelGGL(reactivate_kernel<true>, grid, dim3(256), 0, ctx->stream, A);
-        else
-            hipLaunchKernelGGL(reactivate_kernel<false>, grid, dim3(256), 0, ctx->stream, A);
+        void (*kernel)(ReactivateArgs) = full_optimization
+            ? (K == 4 ? reactivate_kernel<true, 4> : K == 2 ? reactivate_kernel<true, 2>
+                : reactivate_kernel<true, 1>)
+            : (K == 4 ? reactivate_kernel<false, 4> : K == 2 ? reactivate_kernel<false, 2>
+                : reactivate_kernel<false, 1>);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, A);
     }
     SMVS_HIP_CHECK(hipGetLastError());
     if (publish_seq != 0) {
