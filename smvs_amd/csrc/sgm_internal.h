@@ -1,9 +1,11 @@
-// What the translation units of the SGM front end share: sgm.hip (run_sgm),
-// sgm_view.hip (a view's front end), image_prep.hip (a view's input image),
-// bilateral.hip (the joint bilateral upsample).
+// What the translation units of the SGM front end share: sgm.hip (run_sgm:
+// census, warp, cost, WTA), sgm_paths.hip (its path aggregation), sgm_view.hip
+// (a view's front end), image_prep.hip (a view's input image), bilateral.hip
+// (the joint bilateral upsample).
 #pragma once
 
 #include "common.h"
+#include "sgm_path_plan.h"
 
 #include <vector>
 
@@ -90,12 +92,6 @@ struct SgmWorkspace {
     int runs = 0;
     bool want_sgm = false;       // smvs_sgm_run hands the S volume to its caller
     explicit SgmWorkspace(Workspace *w) : ws(w) {}
-    // penalty2 <= 255: L - C fits a byte; planes in fours: the u32 accesses of
-    // sgm_sum_wta_kernel
-    static bool delta_form(int num_steps, unsigned penalty2)
-    {
-        return (num_steps % 4) == 0 && penalty2 <= 255u;
-    }
     // the largest penalty2 a step can use: the option itself, or in the adaptive
     // mode max(P2 / diff, P1 * 3 / 2) <= max(P2, P1 * 3 / 2)
     static unsigned largest_penalty2(unsigned penalty1, unsigned penalty2, int p2_mode)
@@ -104,10 +100,9 @@ struct SgmWorkspace {
         return p2_mode == SMVS_SGM_P2_ADAPTIVE && floor_value > penalty2 ? floor_value
                                                                         : penalty2;
     }
-    int ensure(size_t npix, int num_steps, unsigned penalty2)
+    int ensure(size_t npix, int num_steps, SgmPathPlan const &plan)
     {
         size_t const vol = npix * (size_t)num_steps;
-        bool const df = delta_form(num_steps, penalty2);
         int rc;
         if ((rc = ws->ensure(WS_DEPTHS, (size_t)SGM_MAX_PLANES * MAX_RUNS, &depths))
             || (rc = ws->ensure(WS_CENSUS, npix, &census))
@@ -115,9 +110,9 @@ struct SgmWorkspace {
             || (rc = ws->ensure(WS_COST, vol, &cost))
             || (rc = ws->ensure(WS_ARGMIN, npix, &argmin)))
             return rc;
-        if (df && (rc = ws->ensure(WS_DELTA, 8 * vol, &delta)))
+        if (plan.delta && (rc = ws->ensure(WS_DELTA, 8 * vol, &delta)))
             return rc;
-        if ((!df || want_sgm) && (rc = ws->ensure(WS_SGM, vol, &sgm)))
+        if (plan.needs_s(want_sgm) && (rc = ws->ensure(WS_SGM, vol, &sgm)))
             return rc;
         return SMVS_OK;
     }
@@ -129,6 +124,19 @@ int check_sgm_penalties(unsigned penalty1, unsigned penalty2, int p2_mode);
 // The plane count alone (sgm_plane_count_ok; no device involved: every entry
 // calls this before its first device call).
 int check_sgm_plane_count(int num_steps);
+
+// The plan of a run (sgm_path_plan.h) with this process's SMVS_SGM_PATHS: `wave`
+// asks for a wave per line, two planes per lane, up to 128 planes.
+// (sgm_paths.hip)
+SgmPathPlan sgm_path_plan_here(int num_steps, unsigned largest_p2);
+
+// aggregate_sgm_costs (sgm_stereo.cc:429-667) on B.cost: what lies between the
+// cost kernels and the WTA kernels of a run -- S zeroed where the plan asks
+// for it, the launches of the plan's form under a timer of class
+// SMVS_SGM_K_PATHS, hipGetLastError.  The path bytes go to B.delta or the sums
+// to B.sgm, as plan.delta says.  (sgm_paths.hip)
+int sgm_launch_paths(SgmWorkspace &B, SgmPathPlan const &plan, const uint8_t *d_main,
+    int w, int h, int num_steps, unsigned p1, unsigned p2, int p2_mode);
 
 // SGMStereo::run_sgm (sgm_stereo.cc:98-124) on device images; the depth map
 // (and optionally argmin) stay on the device.  Asynchronous on the workspace's

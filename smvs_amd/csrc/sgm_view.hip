@@ -130,7 +130,8 @@ sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
     }
     if ((rc = ws.ensure(WS_BWD, max_nnpix, &d_bwd))
         || (rc = B.ensure(npix > max_nnpix ? npix : max_nnpix, num_steps,
-                SgmWorkspace::largest_penalty2(penalty1, penalty2, p2_mode))))
+                sgm_path_plan_here(num_steps,
+                    SgmWorkspace::largest_penalty2(penalty1, penalty2, p2_mode)))))
         return rc;
     for (int k = 0; k < n_neighbors; ++k) {
         smvs_sgm_neighbor const &N = neighbors[k];

@@ -248,7 +248,11 @@ def _sgm_pair(w, h, seed):
                                           (80, 56, 64, 10, 255),     # the largest penalty the byte form takes
                                           (80, 56, 64, 10, 300),     # above it: u16 volume, atomics
                                           (72, 48, 62, 6, 96),       # even, not a multiple of 4: atomics
-                                          (150, 41, 20, 3, 40)])
+                                          (150, 41, 20, 3, 40),
+                                          # one launch per direction on a portrait image (more entry-column
+                                          # diagonals than entry-row ones), and on the smallest image the
+                                          # entry takes; odd plane count, idle lanes
+                                          (12, 30, 5, 6, 96), (11, 9, 5, 6, 96)])
 def test_sgm_bit_exact(hip, oracle, w, h, D, p1, p2):
     """cost volume, aggregated volume, argmin and depth map are bit-exact
     with the oracle (sgm_stereo.cc:98-306), ragged sizes and odd plane counts

@@ -71,6 +71,9 @@ CASES = [
     (48, 32, 64, 40, 20),     # penalty2 < penalty1: penalty2' = 60 everywhere
     (80, 56, 64, 170, 255),   # the largest penalties of the byte form
     (48, 32, 64, 171, 255),   # P1 * 3 / 2 = 256: one past it
+    (12, 30, 5, 6, 96),       # one launch per direction on a portrait image: more
+                              # entry-column diagonals than entry-row ones
+    (11, 9, 5, 6, 96),        # ... and on the smallest image the entry takes
 ]
 
 
