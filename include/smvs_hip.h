@@ -421,6 +421,53 @@ int smvs_sgm_depth_for_view_raw_mode(int device, const uint8_t *main_img, int w,
     int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
     uint16_t penalty2, int p2_mode, float *depth);
 
+/* Which depth the winner-takes-all step of a run stores.  Not in the reference:
+ * depth_from_sgm_volume (sgm_stereo.cc:274-306) returns the depth of the
+ * winning plane, so a map holds at most num_steps - 2 distinct values.
+ *   SMVS_SGM_WINNER_PLANE     that (what every entry above runs);
+ *   SMVS_SGM_WINNER_SUBPLANE  the parabola through the aggregated cost S of the
+ *                             winner i (the first minimum, as before) and of
+ *                             its two neighbours refines it.  All in float, in
+ *                             this order, no contraction, IEEE division:
+ *     inv[0] = 1.0f / max_depth, inc = (1.0f / min_depth - inv[0]) / (num_steps - 1),
+ *     inv[k + 1] = inv[k] + inc          (sgm_stereo.cc:197-203: the planes'
+ *                                         depths are 1.0f / inv[k])
+ *     a = S[i - 1], b = S[i], c = S[i + 1] as int, den = a - 2 b + c   (>= 0)
+ *     off = 0 if i == num_steps - 1 or den == 0,
+ *           else (float)(a - c) / (float)(2 * den)                    (|off| <= 0.5)
+ *     n = i + 1 if off > 0, else i - 1
+ *     depth = 1.0f / (inv[i] + fabsf(off) * (inv[n] - inv[i]))
+ *                             With off == 0 that is the plane's depth to the
+ *                             bit.  argmin stays i, and the rule of
+ *                             sgm_stereo.cc:300-303 (no depth for i < 2 and
+ *                             for main_img < 25) is unchanged, as are the
+ *                             left/right check and the merge behind it.
+ * p2_mode: smvs_sgm_p2_mode, as in the `_mode` entries.  A NULL options
+ * pointer or an unknown winner is SMVS_ERR_INVALID before any device call, as
+ * are an unknown p2_mode, the plane counts and the penalties; { p2_mode,
+ * SMVS_SGM_WINNER_PLANE } gives the bytes of the `_mode` entry. */
+typedef enum { SMVS_SGM_WINNER_PLANE = 0, SMVS_SGM_WINNER_SUBPLANE = 1 } smvs_sgm_winner;
+typedef struct { int p2_mode; int winner; } smvs_sgm_options;
+
+/* smvs_sgm_run_mode with the winner of sgm_stereo.cc:274-306 selectable */
+int smvs_sgm_run_opts(int device, const uint8_t *main_img, int w, int h,
+    const uint8_t *neighbor_img, int nw, int nh, const float *M,
+    const float *t, float min_depth, float max_depth, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_options *opts, float *depth,
+    int32_t *argmin, uint16_t *cost, uint16_t *sgm);
+/* smvs_sgm_depth_for_view_mode with the winner of sgm_stereo.cc:274-306
+ * selectable (all four runs of a view, sgm_stereo.cc:46-62, use it; the check
+ * of :64-91 and the merge of app/smvsrecon.cc:366-377 see the refined maps) */
+int smvs_sgm_depth_for_view_opts(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_options *opts, float *depth);
+/* smvs_sgm_depth_for_view_raw_mode with the winner of sgm_stereo.cc:274-306
+ * selectable */
+int smvs_sgm_depth_for_view_raw_opts(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_options *opts, float *depth);
+
 /* DepthOptimizer::depthmap_bilateral_filter, depth_optimizer.cc:957-1004 */
 int smvs_bilateral_upsample(int device, const float *dm, int dm_w, int dm_h,
     const float *ci, int w, int h, int channels, float sigma,

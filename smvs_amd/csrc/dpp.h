@@ -30,6 +30,8 @@ constexpr int DPP_ROW_HALF_MIRROR = 0x141;   // row_half_mirror: lane 7 - l of t
 constexpr int dpp_quad_bcast(int k) { return k * 0x55; }
 // row_ror:n: lane (l + n) mod 16 of the same row, n = 1 .. 15
 constexpr int dpp_row_ror(int n) { return 0x120 + n; }
+// row_newbcast:n (gfx90a and later): lane n of every row to the whole row
+constexpr int dpp_row_newbcast(int n) { return 0x150 + n; }
 // row_mask: the rows of 16 lanes that are written
 constexpr int DPP_ROWS_ALL = 0xf;
 constexpr int DPP_ROWS_1_3 = 0xa;

@@ -279,6 +279,33 @@ smvs_host_sgm_depth_steps(const smvs_host_view *main_in, const smvs_host_view *s
     float min_depth, float max_depth, int device, int adaptive_penalty2,
     int num_steps, float *depth_out, int *out_w, int *out_h)
 {
+    return smvs_host_sgm_depth_subplane(main_in, subs_in, n_subs, bundle_in, sgm_scale,
+        min_depth, max_depth, device, adaptive_penalty2, num_steps, 0, depth_out, out_w,
+        out_h);
+}
+
+extern "C" int
+smvs_host_sgm_default_switches(int *out4)
+{
+    if (out4 == nullptr) {
+        g_host_error = "smvs_host_sgm_default_switches: bad argument";
+        return -1;
+    }
+    SGMStereo::Options const opts;
+    ReconSettings const conf;
+    out4[0] = opts.adaptive_penalty2 ? 1 : 0;
+    out4[1] = opts.subplane ? 1 : 0;
+    out4[2] = conf.sgm_adaptive_penalty2 ? 1 : 0;
+    out4[3] = conf.sgm_subplane ? 1 : 0;
+    return 0;
+}
+
+extern "C" int
+smvs_host_sgm_depth_subplane(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, int sgm_scale,
+    float min_depth, float max_depth, int device, int adaptive_penalty2,
+    int num_steps, int subplane, float *depth_out, int *out_w, int *out_h)
+{
     try {
         if (!SGMStereo::Options::valid_num_steps(num_steps))
             throw std::invalid_argument("smvs_host_sgm_depth_steps: num_steps must be "
@@ -295,6 +322,7 @@ smvs_host_sgm_depth_steps(const smvs_host_view *main_in, const smvs_host_view *s
         opts.max_depth = max_depth;
         opts.device = device;
         opts.adaptive_penalty2 = adaptive_penalty2 != 0;
+        opts.subplane = subplane != 0;
         FloatImage::Ptr d = reconstruct_sgm_depth_for_view(opts, main_view, subs,
             bundle);
         if (out_w != nullptr)
@@ -894,6 +922,18 @@ smvs_host_reconstruct_scene_steps(const char *scene_dir,
     const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
     int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used)
 {
+    return smvs_host_reconstruct_scene_subplane(scene_dir, o, flags, sgm_num_steps, 0,
+        view_ids, n_view_ids, reconstructed_out, max_reconstructed, n_reconstructed,
+        n_skipped, seconds, input_scale_used);
+}
+
+extern "C" int
+smvs_host_reconstruct_scene_subplane(const char *scene_dir,
+    const smvs_host_recon_settings *o, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, const int *view_ids, int n_view_ids, int *reconstructed_out,
+    int max_reconstructed, int *n_reconstructed, int *n_skipped, double *seconds,
+    int *input_scale_used)
+{
     try {
         if (!SGMStereo::Options::valid_num_steps(sgm_num_steps))
             throw std::invalid_argument("smvs_host_reconstruct_scene_steps: sgm_num_steps "
@@ -919,6 +959,7 @@ smvs_host_reconstruct_scene_steps(const char *scene_dir,
         conf.sgm_scale = o->sgm_scale;
         conf.sgm_adaptive_penalty2 = (flags & SMVS_HOST_SCENE_ADAPTIVE_PENALTY2) != 0u;
         conf.sgm_num_steps = sgm_num_steps;
+        conf.sgm_subplane = sgm_subplane != 0;
         conf.device_input_scaling = (flags & SMVS_HOST_SCENE_DEVICE_INPUT_SCALING) != 0u;
         conf.device_shading_prep = (flags & SMVS_HOST_SCENE_DEVICE_SHADING_PREP) != 0u;
         conf.gamma_correction = (flags & SMVS_HOST_SCENE_GAMMA_SRGB) != 0u;

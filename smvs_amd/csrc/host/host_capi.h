@@ -134,6 +134,20 @@ int smvs_host_sgm_depth_steps(const smvs_host_view *main_view,
     const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
     int sgm_scale, float min_depth, float max_depth, int device,
     int adaptive_penalty2, int num_steps, float *depth_out, int *out_w, int *out_h);
+/* The same with SGMStereo::Options::subplane (not in the reference's Options:
+ * != 0 refines every run's winning plane with the parabola through its
+ * aggregated cost and its two neighbours', SMVS_SGM_WINNER_SUBPLANE of
+ * include/smvs_hip.h; 0 is smvs_host_sgm_depth_steps, which forwards to this). */
+int smvs_host_sgm_depth_subplane(const smvs_host_view *main_view,
+    const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
+    int sgm_scale, float min_depth, float max_depth, int device,
+    int adaptive_penalty2, int num_steps, int subplane, float *depth_out, int *out_w,
+    int *out_h);
+/* The switches of the SGM front end that the reference does not have, as a
+ * default-constructed SGMStereo::Options and ReconSettings hold them (no
+ * device involved): out4 = { Options::adaptive_penalty2, Options::subplane,
+ * ReconSettings::sgm_adaptive_penalty2, ReconSettings::sgm_subplane }. */
+int smvs_host_sgm_default_switches(int *out4);
 
 /* smvs::Surface on its own (lib/surface.cc): Surface::create (from the bundle
  * when init_depth is NULL, else from the W x H depth map) followed by a
@@ -250,6 +264,17 @@ int smvs_host_reconstruct_scene_steps(const char *scene_dir,
     const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
     const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
     int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used);
+/* The same with ReconSettings::sgm_subplane (an argument: the settings struct
+ * keeps its layout and the flags word its known bits): != 0 runs every view's
+ * SGM front end with SGMStereo::Options::subplane.  An smvs-sgm embedding of
+ * the right size is reused as before (app/smvsrecon.cc:702-708), so a scene
+ * that already has one needs force_sgm as well.
+ * smvs_host_reconstruct_scene_steps forwards to this with 0. */
+int smvs_host_reconstruct_scene_subplane(const char *scene_dir,
+    const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, const int *view_ids, int n_view_ids, int *reconstructed_out,
+    int max_reconstructed, int *n_reconstructed, int *n_skipped, double *seconds,
+    int *input_scale_used);
 
 /* smvsrecon's generate_mesh (app/smvsrecon.cc:278-343, MeshGenerator::
  * generate_mesh, lib/mesh_generator.cc:160-299) on a reconstructed scene: the

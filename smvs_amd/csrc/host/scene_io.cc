@@ -583,6 +583,7 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                         sgm_opts.max_depth = conf.sgm_max;
                         sgm_opts.device = device;
                         sgm_opts.adaptive_penalty2 = conf.sgm_adaptive_penalty2;
+                        sgm_opts.subplane = conf.sgm_subplane;
                         (void)reconstruct_sgm_depth_for_view(sgm_opts, main_view,
                             stereo_views, bundle);
                         save_mvei(view.image_path("smvs-sgm"),

@@ -101,6 +101,11 @@ struct ReconSettings
     // SGMStereo::Options::num_steps at its default): the inverse-depth planes of
     // the SGM front end, 2 .. 128 or a multiple of 8 from 136 to 256
     int sgm_num_steps = 128;
+    // not in the reference's AppSettings: SGMStereo::Options::subplane (the
+    // smvs-sgm map refined between the planes).  An smvs-sgm embedding of the
+    // right size is reused as before (app/smvsrecon.cc:702-708): switching this
+    // on for a scene that has one needs force_sgm
+    bool sgm_subplane = false;
     // not in the reference's AppSettings: the input scaling of :621-650 on the
     // device (rescale_half_size_gaussian_device), one ViewQueue task per view
     bool device_input_scaling = false;

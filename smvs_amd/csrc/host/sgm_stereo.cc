@@ -9,6 +9,20 @@
 
 namespace smvs_amd {
 
+namespace {
+
+// the two switches the reference's Options do not have, as the device takes them
+smvs_sgm_options
+device_options(SGMStereo::Options const& o)
+{
+    smvs_sgm_options d;
+    d.p2_mode = o.adaptive_penalty2 ? SMVS_SGM_P2_ADAPTIVE : SMVS_SGM_P2_CONSTANT;
+    d.winner = o.subplane ? SMVS_SGM_WINNER_SUBPLANE : SMVS_SGM_WINNER_PLANE;
+    return d;
+}
+
+} // namespace
+
 SGMStereo::SGMStereo(Options const& opts, StereoView::Ptr main,
     StereoView::Ptr neighbor)
     : opts(opts), main(main), neighbor(neighbor)
@@ -32,14 +46,14 @@ SGMStereo::run_sgm(float min_depth, float max_depth)
         (float)neighbor_image->width(), (float)neighbor_image->height(), M, t);
     FloatImage::Ptr depth = FloatImage::create(main_image->width(),
         main_image->height(), 1);
-    int const rc = smvs_sgm_run_mode(opts.device, main_image->begin(),
+    smvs_sgm_options const dev_opts = device_options(opts);
+    int const rc = smvs_sgm_run_opts(opts.device, main_image->begin(),
         main_image->width(), main_image->height(), neighbor_image->begin(),
         neighbor_image->width(), neighbor_image->height(), M, t, min_depth,
-        max_depth, opts.num_steps, opts.penalty1, opts.penalty2,
-        opts.adaptive_penalty2 ? SMVS_SGM_P2_ADAPTIVE : SMVS_SGM_P2_CONSTANT,
+        max_depth, opts.num_steps, opts.penalty1, opts.penalty2, &dev_opts,
         depth->begin(), nullptr, nullptr, nullptr);
     if (rc != SMVS_OK)
-        throw std::runtime_error(std::string("smvs_sgm_run_mode: ")
+        throw std::runtime_error(std::string("smvs_sgm_run_opts: ")
             + smvs_last_error());
     return depth;
 }
@@ -145,13 +159,13 @@ run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
     sgm_scale_size(o.scale, &w, &h);
     FloatImage::Ptr depth = FloatImage::create_for_overwrite(w, h, 1);
     // desaturate + half-size on the device, then 4 x run_sgm, L/R check, merge
-    int const rc = smvs_sgm_depth_for_view_raw_mode(o.device, main_bytes->begin(),
+    smvs_sgm_options const dev_opts = device_options(o);
+    int const rc = smvs_sgm_depth_for_view_raw_opts(o.device, main_bytes->begin(),
         main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
         channels.data(), (int)dev.size(), o.scale, o.num_steps, o.penalty1, o.penalty2,
-        o.adaptive_penalty2 ? SMVS_SGM_P2_ADAPTIVE : SMVS_SGM_P2_CONSTANT,
-        depth->begin());
+        &dev_opts, depth->begin());
     if (rc != SMVS_OK)
-        throw std::runtime_error(std::string("smvs_sgm_depth_for_view_raw_mode: ")
+        throw std::runtime_error(std::string("smvs_sgm_depth_for_view_raw_opts: ")
             + smvs_last_error());
     return depth;
 }

@@ -30,6 +30,11 @@ public:
         // lib/sgm_stereo.cc:361-406), true: the build without SSE
         // (penalty2 adapted to the intensity step, lib/sgm_stereo.cc:310-346)
         bool adaptive_penalty2 = false;
+        // not in the reference's Options (depth_from_sgm_volume,
+        // lib/sgm_stereo.cc:274-306, returns the winning plane's depth): true
+        // refines the winner with the parabola through its aggregated cost and
+        // its two neighbours' (SMVS_SGM_WINNER_SUBPLANE, include/smvs_hip.h)
+        bool subplane = false;
 
         // the plane counts smvs_sgm_run / smvs_sgm_depth_for_view accept
         static bool valid_num_steps(int n)

@@ -402,6 +402,42 @@ wta_store(uint32_t key, size_t p, const uint8_t *__restrict__ main_img,
             : depths[min_index];
 }
 
+// The sub-plane winner (SMVS_SGM_WINNER_SUBPLANE; extends sgm_stereo.cc:300-303,
+// not in the reference): the parabola through the winner's S = b and its two
+// neighbours a, c moves the inverse depth towards the neighbouring plane on
+// the lower side, by at most half a plane.  inv[k] is the inverse depth of
+// plane k as sgm_stereo.cc:197-203 accumulates it (depths[k] == 1 / inv[k]), so
+// an offset of 0 gives depths[i] to the bit.  The caller has excluded i < 2.
+// float in the written order, contraction off, IEEE division.
+__device__ __forceinline__ float
+subplane_depth(int i, int a, int b, int c, const float *__restrict__ inv, int D)
+{
+#pragma clang fp contract(off)
+    int const den = a - 2 * b + c;   // >= 0: b is the minimum
+    float off = 0.0f;
+    if (i != D - 1 && den != 0)
+        off = (float)(a - c) / (float)(2 * den);   // in [-0.5, 0.5]
+    int const n = off > 0.0f ? i + 1 : i - 1;
+    float const base = inv[i];
+    float const step = fabsf(off) * (inv[n] - base);
+    return 1.0f / (base + step);
+}
+
+// wta_store for the sub-plane winner: argmin and the validity rule are
+// wta_store's; a and c are only looked at for a valid winner (c not at all in
+// the last plane).
+__device__ __forceinline__ void
+wta_store_subplane(int min_index, int a, int b, int c, size_t p,
+    const uint8_t *__restrict__ main_img, const float *__restrict__ inv, int D,
+    float *__restrict__ depth, int32_t *__restrict__ argmin)
+{
+    if (argmin != nullptr)
+        argmin[p] = min_index;
+    if (depth != nullptr)
+        depth[p] = (min_index < 2 || main_img[p] < 25) ? 0.0f
+            : subplane_depth(min_index, a, b, c, inv, D);
+}
+
 // WTA with 16 lanes per pixel (sgm_stereo.cc:274-306): lane sub reads planes
 // sub, sub + 16, ...; the first minimum wins through the (value, plane) key.
 __global__ void __launch_bounds__(256)
@@ -418,6 +454,29 @@ wta_rows_kernel(const uint16_t *__restrict__ sgm,
     key = row_prefix_min_u32(key);
     if (sub == 15 && p < npix)
         wta_store(key, p, main_img, depths, depth, argmin);
+}
+
+// wta_rows_kernel with the sub-plane winner: S is in memory, lane 15 reads the
+// winner's two neighbours from it.
+__global__ void __launch_bounds__(256)
+wta_rows_subplane_kernel(const uint16_t *__restrict__ sgm,
+    const uint8_t *__restrict__ main_img, const float *__restrict__ inv,
+    size_t npix, int D, float *__restrict__ depth, int32_t *__restrict__ argmin)
+{
+    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    int const sub = threadIdx.x & 15;
+    uint32_t key = 0xFFFFFFFFu;
+    if (p < npix)
+        for (int d = sub; d < D; d += 16)
+            key = min(key, (uint32_t)sgm[p * D + d] * 256u + (uint32_t)d);
+    key = row_prefix_min_u32(key);
+    if (sub == 15 && p < npix) {
+        int const i = (int)(key & 0xFFu);
+        const uint16_t *s = sgm + p * D;
+        int const a = i >= 1 ? (int)s[i - 1] : 0;
+        int const c = i + 1 < D ? (int)s[i + 1] : 0;
+        wta_store_subplane(i, a, (int)(key >> 8), c, p, main_img, inv, D, depth, argmin);
+    }
 }
 
 // S = 8 C + the eight path bytes of the DELTA form, and the winner-takes-all of
@@ -508,6 +567,89 @@ sgm_sum_wta_wide_kernel(const uint8_t *__restrict__ cost, const uint8_t *__restr
         wta_store(key, p, main_img, depths, depth, argmin);
 }
 
+// The two kernels above with the sub-plane winner (wta_store_subplane; `inv`:
+// the planes' inverse depths), LANES = 32 or 64 lanes per pixel.  S of the
+// winner's neighbours is in registers -- of the same lane, or for plane
+// 4 sub - 1 / 4 sub + 4 of the previous / next lane of the wave (wave_shr:1 /
+// wave_shl:1: every 16th plane crosses a row of 16 lanes).  The winner's key
+// goes to every lane of the pixel and the lane that holds the winning plane
+// stores.  Everything up to the minimum is the text of the kernels above, which
+// keep their instruction streams this way.
+template <int LANES>
+__device__ __forceinline__ void
+sum_wta_subplane(const uint8_t *__restrict__ cost, const uint8_t *__restrict__ delta,
+    size_t vol, const uint8_t *__restrict__ main_img, const float *__restrict__ inv,
+    size_t npix, int D, float *__restrict__ depth, int32_t *__restrict__ argmin,
+    uint16_t *__restrict__ sgm_out)
+{
+    static_assert(LANES == 32 || LANES == 64, "half a wavefront or a whole one per pixel");
+    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / LANES;
+    int const sub = threadIdx.x & (LANES - 1);
+    int const d0 = 4 * sub;
+    uint32_t key = 0xFFFFFFFFu;
+    uint32_t sv[4] = { 0u, 0u, 0u, 0u };
+    if (p < npix && d0 < D) {
+        size_t const o = p * (size_t)D + d0;   // D % 4 == 0: aligned u32
+        uint32_t const c = *reinterpret_cast<const uint32_t *>(cost + o);
+        uint32_t e[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            e[k] = *reinterpret_cast<const uint32_t *>(delta + (size_t)k * vol + o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            uint32_t sum = 8u * ((c >> (8 * j)) & 0xFFu);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                sum += (e[k] >> (8 * j)) & 0xFFu;
+            sv[j] = sum & 0xFFFFu;
+            key = min(key, sv[j] * 256u + (uint32_t)(d0 + j));
+        }
+        if (sgm_out != nullptr) {
+            uint2 const packed = make_uint2(sv[0] | (sv[1] << 16), sv[2] | (sv[3] << 16));
+            *reinterpret_cast<uint2 *>(sgm_out + o) = packed;
+        }
+    }
+    // (every lane of the wave takes part in the moves from here on)
+    uint32_t const left = lane_prev(sv[3], 0u);    // S of plane d0 - 1
+    uint32_t const right = lane_next(sv[0], 0u);   // S of plane d0 + 4
+    if constexpr (LANES == 32) {
+        key = row_prefix_min_u32(key);
+        uint32_t const other = (uint32_t)__shfl_xor((int)key, 16);
+        key = min(key, other);
+        // lanes 15 and 31 of the pixel both hold its minimum: to their rows
+        key = dpp_u32<dpp_row_newbcast(15)>(key, key);
+    } else {
+        key = wave_min_u32(key);
+    }
+    int const i = (int)(key & 0xFFu);
+    // (a pixel past the end has the key of all ones: plane 255, no lane of 32)
+    if ((i >> 2) == sub && p < npix) {
+        int const j = i & 3;
+        uint32_t const a = j == 0 ? left : (j == 1 ? sv[0] : (j == 2 ? sv[1] : sv[2]));
+        uint32_t const c = j == 0 ? sv[1] : (j == 1 ? sv[2] : (j == 2 ? sv[3] : right));
+        wta_store_subplane(i, (int)a, (int)(key >> 8), (int)c, p, main_img, inv, D, depth,
+            argmin);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+sgm_sum_wta_subplane_kernel(const uint8_t *__restrict__ cost,
+    const uint8_t *__restrict__ delta, size_t vol, const uint8_t *__restrict__ main_img,
+    const float *__restrict__ inv, size_t npix, int D, float *__restrict__ depth,
+    int32_t *__restrict__ argmin, uint16_t *__restrict__ sgm_out)
+{
+    sum_wta_subplane<32>(cost, delta, vol, main_img, inv, npix, D, depth, argmin, sgm_out);
+}
+
+__global__ void __launch_bounds__(256)
+sgm_sum_wta_wide_subplane_kernel(const uint8_t *__restrict__ cost,
+    const uint8_t *__restrict__ delta, size_t vol, const uint8_t *__restrict__ main_img,
+    const float *__restrict__ inv, size_t npix, int D, float *__restrict__ depth,
+    int32_t *__restrict__ argmin, uint16_t *__restrict__ sgm_out)
+{
+    sum_wta_subplane<64>(cost, delta, vol, main_img, inv, npix, D, depth, argmin, sgm_out);
+}
+
 __global__ void __launch_bounds__(256)
 widen_u8_kernel(const uint8_t *__restrict__ src, uint16_t *__restrict__ dst,
     size_t n)
@@ -592,6 +734,16 @@ check_sgm_plane_count(int num_steps)
     return SMVS_OK;
 }
 
+// (declared in sgm_internal.h)
+int
+check_sgm_winner(const smvs_sgm_options *opts)
+{
+    SMVS_REQUIRE(opts != nullptr, "null options (winner, p2_mode)");
+    SMVS_REQUIRE(opts->winner == SMVS_SGM_WINNER_PLANE
+            || opts->winner == SMVS_SGM_WINNER_SUBPLANE, "unknown winner");
+    return SMVS_OK;
+}
+
 static int
 check_sgm_options(int num_steps, float min_depth, float max_depth,
     unsigned penalty1, unsigned penalty2, int p2_mode = SMVS_SGM_P2_CONSTANT)
@@ -608,12 +760,15 @@ int
 sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     int w, int h, const uint8_t *d_nbr, int nw, int nh, const float *M,
     const float *t, float min_depth, float max_depth, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *d_depth)
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *d_depth)
 {
     int rc = check_sgm_options(num_steps, min_depth, max_depth, penalty1,
         penalty2, p2_mode);
     if (rc != SMVS_OK)
         return rc;
+    SMVS_REQUIRE(winner == SMVS_SGM_WINNER_PLANE || winner == SMVS_SGM_WINNER_SUBPLANE,
+        "unknown winner");
+    bool const subplane = winner == SMVS_SGM_WINNER_SUBPLANE;
     SMVS_REQUIRE(B.runs < SgmWorkspace::MAX_RUNS, "too many runs on one workspace");
     hipStream_t const stream = B.ws->stream;
     size_t const npix = (size_t)w * h;
@@ -623,20 +778,26 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
         SgmWorkspace::largest_penalty2(penalty1, penalty2, p2_mode));
     if ((rc = B.ensure(npix, num_steps, plan)) != SMVS_OK)
         return rc;
-    // sgm_stereo.cc:195-203: inverse-depth planes by repeated float addition
-    float depths[SGM_MAX_PLANES];
+    // sgm_stereo.cc:195-203: inverse-depth planes by repeated float addition;
+    // behind the depths the inverse depths themselves, which only the sub-plane
+    // winner reads
+    float depths[2 * SGM_MAX_PLANES];
+    float *const inv = depths + SGM_MAX_PLANES;
     {
 #pragma clang fp contract(off)
         float inv_depth = 1.0f / max_depth;
         float const increment = (1.0f / min_depth - inv_depth) / (num_steps - 1);
         for (int i = 0; i < num_steps; ++i) {
             depths[i] = 1.0f / inv_depth;
+            inv[i] = inv_depth;
             inv_depth += increment;
         }
     }
-    float *d_depths = B.depths + SGM_MAX_PLANES * B.runs;
+    float *d_depths = B.depths + 2 * SGM_MAX_PLANES * B.runs;
+    float *d_inv = d_depths + SGM_MAX_PLANES;
     B.runs += 1;
-    if ((rc = B.ws->upload(d_depths, depths, sizeof(float) * num_steps)) != SMVS_OK)
+    if ((rc = B.ws->upload(d_depths, depths,
+             sizeof(float) * (subplane ? SGM_MAX_PLANES + num_steps : num_steps))) != SMVS_OK)
         return rc;
 
     {
@@ -683,20 +844,24 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
         return rc;
     {
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_WTA);
+        // (the sub-plane forms take the inverse depths where the others take the
+        // depths; grids and every other argument are the same)
+        const float *const table = subplane ? d_inv : d_depths;
         if (plan.wta == SGM_WTA_SUM_WIDE)
-            hipLaunchKernelGGL(sgm_sum_wta_wide_kernel,
+            hipLaunchKernelGGL(subplane ? sgm_sum_wta_wide_subplane_kernel
+                                        : sgm_sum_wta_wide_kernel,
                 dim3((unsigned)((npix * 64 + 255) / 256)), dim3(256), 0, stream,
-                B.cost, B.delta, vol, d_main, d_depths, npix, num_steps, d_depth,
+                B.cost, B.delta, vol, d_main, table, npix, num_steps, d_depth,
                 B.argmin, B.want_sgm ? B.sgm : nullptr);
         else if (plan.wta == SGM_WTA_SUM)
-            hipLaunchKernelGGL(sgm_sum_wta_kernel,
+            hipLaunchKernelGGL(subplane ? sgm_sum_wta_subplane_kernel : sgm_sum_wta_kernel,
                 dim3((unsigned)((npix * 32 + 255) / 256)), dim3(256), 0, stream,
-                B.cost, B.delta, vol, d_main, d_depths, npix, num_steps, d_depth,
+                B.cost, B.delta, vol, d_main, table, npix, num_steps, d_depth,
                 B.argmin, B.want_sgm ? B.sgm : nullptr);
         else
-            hipLaunchKernelGGL(wta_rows_kernel,
+            hipLaunchKernelGGL(subplane ? wta_rows_subplane_kernel : wta_rows_kernel,
                 dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, stream,
-                B.sgm, d_main, d_depths, npix, num_steps, d_depth,
+                B.sgm, d_main, table, npix, num_steps, d_depth,
                 B.argmin);
     }
     SMVS_HIP_CHECK(hipGetLastError());
@@ -711,8 +876,8 @@ static int
 sgm_run_impl(int device, const uint8_t *main_img, int w, int h,
     const uint8_t *neighbor_img, int nw, int nh, const float *M,
     const float *t, float min_depth, float max_depth, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth, int32_t *argmin,
-    uint16_t *cost, uint16_t *sgm)
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *depth,
+    int32_t *argmin, uint16_t *cost, uint16_t *sgm)
 {
     SMVS_REQUIRE(main_img && neighbor_img && M && t, "null argument");
     SMVS_REQUIRE(w > 10 && h > 8 && nw > 1 && nh > 1, "image too small");
@@ -738,7 +903,7 @@ sgm_run_impl(int device, const uint8_t *main_img, int w, int h,
         || (rc = ws.upload(d_nbr, neighbor_img, nnpix)))
         return rc;
     if ((rc = sgm_run_device(B, d_main, w, h, d_nbr, nw, nh, M, t, min_depth,
-            max_depth, num_steps, penalty1, penalty2, p2_mode, d_depth)) != SMVS_OK)
+            max_depth, num_steps, penalty1, penalty2, p2_mode, winner, d_depth)) != SMVS_OK)
         return rc;
     if (depth != nullptr
         && (rc = ws.download(depth, d_depth, sizeof(float) * npix)) != SMVS_OK)
@@ -771,8 +936,8 @@ smvs_sgm_run(int device, const uint8_t *main_img, int w, int h,
     uint16_t *cost, uint16_t *sgm)
 {
     return sgm_run_impl(device, main_img, w, h, neighbor_img, nw, nh, M, t, min_depth,
-        max_depth, num_steps, penalty1, penalty2, SMVS_SGM_P2_CONSTANT, depth, argmin,
-        cost, sgm);
+        max_depth, num_steps, penalty1, penalty2, SMVS_SGM_P2_CONSTANT,
+        SMVS_SGM_WINNER_PLANE, depth, argmin, cost, sgm);
 }
 
 // sgm_stereo.cc:310-346 with p2_mode = SMVS_SGM_P2_ADAPTIVE
@@ -784,7 +949,23 @@ smvs_sgm_run_mode(int device, const uint8_t *main_img, int w, int h,
     uint16_t *cost, uint16_t *sgm)
 {
     return sgm_run_impl(device, main_img, w, h, neighbor_img, nw, nh, M, t, min_depth,
-        max_depth, num_steps, penalty1, penalty2, p2_mode, depth, argmin, cost, sgm);
+        max_depth, num_steps, penalty1, penalty2, p2_mode, SMVS_SGM_WINNER_PLANE, depth,
+        argmin, cost, sgm);
+}
+
+// sgm_stereo.cc:274-306 with opts->winner = SMVS_SGM_WINNER_SUBPLANE
+extern "C" int
+smvs_sgm_run_opts(int device, const uint8_t *main_img, int w, int h,
+    const uint8_t *neighbor_img, int nw, int nh, const float *M,
+    const float *t, float min_depth, float max_depth, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_options *opts, float *depth,
+    int32_t *argmin, uint16_t *cost, uint16_t *sgm)
+{
+    if (int const rc = check_sgm_winner(opts); rc != SMVS_OK)
+        return rc;
+    return sgm_run_impl(device, main_img, w, h, neighbor_img, nw, nh, M, t, min_depth,
+        max_depth, num_steps, penalty1, penalty2, opts->p2_mode, opts->winner, depth,
+        argmin, cost, sgm);
 }
 
 extern "C" int

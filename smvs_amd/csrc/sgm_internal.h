@@ -78,7 +78,8 @@ static_assert(sgm_plane_count_ok(2) && sgm_plane_count_ok(127) && sgm_plane_coun
 
 // Work buffers of one run_sgm inside a pooled workspace; reused by the runs of
 // a view (the runs are ordered on the workspace's stream).  Every run has its
-// own depth table.
+// own depth table: SGM_MAX_PLANES depths, then as many inverse depths (the
+// sub-plane winner's).
 struct SgmWorkspace {
     static constexpr int MAX_RUNS = 4;
     Workspace *ws;
@@ -104,7 +105,7 @@ struct SgmWorkspace {
     {
         size_t const vol = npix * (size_t)num_steps;
         int rc;
-        if ((rc = ws->ensure(WS_DEPTHS, (size_t)SGM_MAX_PLANES * MAX_RUNS, &depths))
+        if ((rc = ws->ensure(WS_DEPTHS, (size_t)2 * SGM_MAX_PLANES * MAX_RUNS, &depths))
             || (rc = ws->ensure(WS_CENSUS, npix, &census))
             || (rc = ws->ensure(WS_WARPED, vol, &warped))
             || (rc = ws->ensure(WS_COST, vol, &cost))
@@ -124,6 +125,10 @@ int check_sgm_penalties(unsigned penalty1, unsigned penalty2, int p2_mode);
 // The plane count alone (sgm_plane_count_ok; no device involved: every entry
 // calls this before its first device call).
 int check_sgm_plane_count(int num_steps);
+// The options of the *_opts entries: non-NULL, a known winner (no device
+// involved: the entries call this first; p2_mode goes through
+// check_sgm_penalties as in the *_mode entries).
+int check_sgm_winner(const smvs_sgm_options *opts);
 
 // The plan of a run (sgm_path_plan.h) with this process's SMVS_SGM_PATHS: `wave`
 // asks for a wave per line, two planes per lane, up to 128 planes.
@@ -139,12 +144,12 @@ int sgm_launch_paths(SgmWorkspace &B, SgmPathPlan const &plan, const uint8_t *d_
     int w, int h, int num_steps, unsigned p1, unsigned p2, int p2_mode);
 
 // SGMStereo::run_sgm (sgm_stereo.cc:98-124) on device images; the depth map
-// (and optionally argmin) stay on the device.  Asynchronous on the workspace's
-// stream.  (sgm.hip)
+// (and optionally argmin) stay on the device.  winner: smvs_sgm_winner.
+// Asynchronous on the workspace's stream.  (sgm.hip)
 int sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     int w, int h, const uint8_t *d_nbr, int nw, int nh, const float *M,
     const float *t, float min_depth, float max_depth, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *d_depth);
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *d_depth);
 
 // One view's SGM input image on the device: upload (raw: interleaved u8 of
 // `channels`; otherwise already at SGM scale, one channel), desaturate and

@@ -76,7 +76,7 @@ static int
 sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
     int main_channels, const smvs_sgm_neighbor *neighbors,
     const int *neighbor_channels, int n_neighbors, int halvings, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth)
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *depth)
 {
     SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
         "unknown penalty2 mode");
@@ -139,11 +139,11 @@ sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
         // then neighbour -> main with the neighbour's own depth range
         if ((rc = sgm_run_device(B, d_main, mw, mh, d_nbr[k], nw[k], nh[k],
                 N.M_fwd, N.t_fwd, N.range_main[0], N.range_main[1], num_steps,
-                penalty1, penalty2, p2_mode, d_fwd[k])) != SMVS_OK)
+                penalty1, penalty2, p2_mode, winner, d_fwd[k])) != SMVS_OK)
             return rc;
         if ((rc = sgm_run_device(B, d_nbr[k], nw[k], nh[k], d_main, mw, mh,
                 N.M_bwd, N.t_bwd, N.range_neighbor[0], N.range_neighbor[1],
-                num_steps, penalty1, penalty2, p2_mode, d_bwd)) != SMVS_OK)
+                num_steps, penalty1, penalty2, p2_mode, winner, d_bwd)) != SMVS_OK)
             return rc;
         LrArgs L;
         L.d_main = d_fwd[k];
@@ -179,7 +179,8 @@ smvs_sgm_depth_for_view(int device, const uint8_t *main_img, int w, int h,
     uint16_t penalty1, uint16_t penalty2, float *depth)
 {
     return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
-        n_neighbors, 0, num_steps, penalty1, penalty2, SMVS_SGM_P2_CONSTANT, depth);
+        n_neighbors, 0, num_steps, penalty1, penalty2, SMVS_SGM_P2_CONSTANT,
+        SMVS_SGM_WINNER_PLANE, depth);
 }
 
 // sgm_stereo.cc:310-346 with p2_mode = SMVS_SGM_P2_ADAPTIVE
@@ -189,7 +190,21 @@ smvs_sgm_depth_for_view_mode(int device, const uint8_t *main_img, int w, int h,
     uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth)
 {
     return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
-        n_neighbors, 0, num_steps, penalty1, penalty2, p2_mode, depth);
+        n_neighbors, 0, num_steps, penalty1, penalty2, p2_mode, SMVS_SGM_WINNER_PLANE,
+        depth);
+}
+
+// sgm_stereo.cc:274-306 with opts->winner = SMVS_SGM_WINNER_SUBPLANE in all four
+// runs of the view
+extern "C" int
+smvs_sgm_depth_for_view_opts(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_options *opts, float *depth)
+{
+    if (int const rc = check_sgm_winner(opts); rc != SMVS_OK)
+        return rc;
+    return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
+        n_neighbors, 0, num_steps, penalty1, penalty2, opts->p2_mode, opts->winner, depth);
 }
 
 extern "C" int
@@ -210,6 +225,23 @@ smvs_sgm_depth_for_view_raw_mode(int device, const uint8_t *main_img, int w, int
     int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
     uint16_t penalty2, int p2_mode, float *depth)
 {
+    smvs_sgm_options const opts = { p2_mode, SMVS_SGM_WINNER_PLANE };
+    return smvs_sgm_depth_for_view_raw_opts(device, main_img, w, h, channels, neighbors,
+        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, &opts,
+        depth);
+}
+
+// sgm_stereo.cc:274-306 with opts->winner = SMVS_SGM_WINNER_SUBPLANE in all four
+// runs of the view
+extern "C" int
+smvs_sgm_depth_for_view_raw_opts(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_options *opts, float *depth)
+{
+    if (int const rc = check_sgm_winner(opts); rc != SMVS_OK)
+        return rc;
+    int const p2_mode = opts->p2_mode;
     SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
         "unknown penalty2 mode");
     SMVS_REQUIRE(channels == 1 || channels == 3, "1 or 3 channels");
@@ -219,6 +251,6 @@ smvs_sgm_depth_for_view_raw_mode(int device, const uint8_t *main_img, int w, int
             "1 or 3 channels");
     return sgm_depth_for_view_impl(device, main_img, w, h, channels, neighbors,
         neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, p2_mode,
-        depth);
+        opts->winner, depth);
 }
 

@@ -421,13 +421,28 @@ class ViewContext:
 
 
 P2_CONSTANT, P2_ADAPTIVE = 0, 1   # smvs_sgm_p2_mode of include/smvs_hip.h
+WINNER_PLANE, WINNER_SUBPLANE = 0, 1   # smvs_sgm_winner
+
+
+class SgmOptions(C.Structure):
+    """smvs_sgm_options of include/smvs_hip.h."""
+    _fields_ = [("p2_mode", C.c_int), ("winner", C.c_int)]
+
+
+def _sgm_options(adaptive_p2, subplane):
+    return SgmOptions(P2_ADAPTIVE if adaptive_p2 else P2_CONSTANT,
+                      WINNER_SUBPLANE if subplane else WINNER_PLANE)
 
 
 def sgm_run(main_img, neighbor_img, M, t, min_depth, max_depth, num_steps=128,
-            p1=6, p2=96, device=0, want_volumes=False, adaptive_p2=False):
+            p1=6, p2=96, device=0, want_volumes=False, adaptive_p2=False, subplane=False):
     """SGMStereo::run_sgm on the device.  adaptive_p2: the path aggregation of
     the reference's build without SSE (lib/sgm_stereo.cc:310-346, penalty2
-    adapted to the intensity step); off by default."""
+    adapted to the intensity step); off by default.
+    subplane: the depth of the winning plane refined by the parabola through
+    its aggregated cost and its two neighbours' (SMVS_SGM_WINNER_SUBPLANE of
+    include/smvs_hip.h, not in the reference); argmin and the volumes are the
+    same; off by default."""
     lib = _capi.load()
     main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
     neighbor_img = np.ascontiguousarray(neighbor_img, dtype=np.uint8)
@@ -437,10 +452,11 @@ def sgm_run(main_img, neighbor_img, M, t, min_depth, max_depth, num_steps=128,
     argmin = np.zeros((h, w), dtype=np.int32)
     cost = np.zeros((h, w, num_steps), dtype=np.uint16) if want_volumes else None
     sgm = np.zeros((h, w, num_steps), dtype=np.uint16) if want_volumes else None
-    check(lib.smvs_sgm_run_mode(device, _p(main_img, _u8p), w, h,
+    opts = _sgm_options(adaptive_p2, subplane)
+    check(lib.smvs_sgm_run_opts(device, _p(main_img, _u8p), w, h,
           _p(neighbor_img, _u8p), nw, nh, _p(M, _fp), _p(t, _fp),
           C.c_float(min_depth), C.c_float(max_depth), num_steps,
-          C.c_uint16(p1), C.c_uint16(p2), C.c_int(P2_ADAPTIVE if adaptive_p2 else P2_CONSTANT),
+          C.c_uint16(p1), C.c_uint16(p2), C.byref(opts),
           _p(depth, _fp), _p(argmin, _i32p), _p(cost, _u16p), _p(sgm, _u16p)))
     return dict(depth=depth, argmin=argmin, cost=cost, sgm=sgm)
 
@@ -488,20 +504,21 @@ class SgmNeighbor(C.Structure):
 
 
 def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0,
-                       adaptive_p2=False, halvings=None):
+                       adaptive_p2=False, halvings=None, subplane=False):
     """reconstruct_sgm_depth_for_view on the device.  neighbors: list of dicts
     {image, M_fwd, t_fwd, M_bwd, t_bwd, range_main, range_neighbor} (SGM-scale
-    u8 images, float reprojections).  adaptive_p2: as for sgm_run.
+    u8 images, float reprojections).  adaptive_p2, subplane: as for sgm_run
+    (all four runs of the view).
     halvings (an int): the images are full-resolution u8 embeddings of one or
     three channels, desaturated and halved that often on the device
-    (smvs_sgm_depth_for_view_raw_mode); the map has the SGM-scale size."""
+    (smvs_sgm_depth_for_view_raw_opts); the map has the SGM-scale size."""
     lib = _capi.load()
-    mode = C.c_int(P2_ADAPTIVE if adaptive_p2 else P2_CONSTANT)
+    opts = _sgm_options(adaptive_p2, subplane)
     main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
     h, w = main_img.shape[:2]
     if halvings is not None:
         return _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device,
-                                       mode, int(halvings))
+                                       opts, int(halvings))
     keep = []
     arr = (SgmNeighbor * len(neighbors))()
     for k, nb in enumerate(neighbors):
@@ -515,8 +532,9 @@ def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0
             for i in range(n):
                 getattr(arr[k], name)[i] = float(v[i])
     depth = np.zeros((h, w), dtype=np.float32)
-    check(lib.smvs_sgm_depth_for_view_mode(device, _p(main_img, _u8p), w, h, arr,
-          len(neighbors), num_steps, C.c_uint16(p1), C.c_uint16(p2), mode, _p(depth, _fp)))
+    check(lib.smvs_sgm_depth_for_view_opts(device, _p(main_img, _u8p), w, h, arr,
+          len(neighbors), num_steps, C.c_uint16(p1), C.c_uint16(p2), C.byref(opts),
+          _p(depth, _fp)))
     return depth
 
 
@@ -535,7 +553,7 @@ def _sgm_neighbors(neighbors, keep):
     return arr
 
 
-def _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device, mode,
+def _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device, opts,
                             halvings):
     keep = []
     arr = _sgm_neighbors(neighbors, keep)
@@ -546,9 +564,9 @@ def _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device,
     for _ in range(halvings):
         ow, oh = (ow + 1) // 2, (oh + 1) // 2
     depth = np.zeros((oh, ow), dtype=np.float32)
-    check(lib.smvs_sgm_depth_for_view_raw_mode(device, _p(main_img, _u8p), w, h, channels,
+    check(lib.smvs_sgm_depth_for_view_raw_opts(device, _p(main_img, _u8p), w, h, channels,
           arr, nch, len(neighbors), halvings, num_steps, C.c_uint16(p1), C.c_uint16(p2),
-          mode, _p(depth, _fp)))
+          C.byref(opts), _p(depth, _fp)))
     return depth
 
 

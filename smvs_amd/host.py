@@ -233,7 +233,8 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       num_neighbors=6, min_neighbors=3, first_device=0, num_devices=1,
                       views_in_flight=2, input_scale=-1, max_pixels=1700000, details=False,
                       sgm_adaptive_penalty2=False, device_input_scaling=False,
-                      device_shading_prep=False, gamma_correction=False, sgm_num_steps=128):
+                      device_shading_prep=False, gamma_correction=False, sgm_num_steps=128,
+                      sgm_subplane=False):
     """smvsrecon's scene-level run (app/smvsrecon.cc:400-745) through
     smvs_amd::reconstruct_scene: returns (reconstructed ids, skipped, seconds)
     [, input scale used if `details`].  input_scale < 0 (the default, as
@@ -253,7 +254,12 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     use_shading only.
     sgm_num_steps: the inverse-depth planes of the SGM front end
     (SGMStereo::Options::num_steps): 2 .. 128, or a multiple of 8 from 136 to
-    256; smvsrecon runs 128."""
+    256; smvsrecon runs 128.
+    sgm_subplane: ReconSettings::sgm_subplane -- the smvs-sgm map of every view
+    refined between the planes (SGMStereo::Options::subplane); off by default.
+    An smvs-sgm embedding of the right size is reused as before
+    (app/smvsrecon.cc:702-708): switching the mode on for a scene that has been
+    reconstructed already needs force_sgm as well."""
     lib = load()
     st = ReconSettings(image_embedding.encode(), regularization, output_scale,
                        1 if use_shading else 0, 1 if use_sgm else 0,
@@ -267,10 +273,10 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                              C.byref(cap), None, None, None, None, None, None, None)
     out = np.zeros(max(cap.value, 1), np.int32)
     n = C.c_int(0); sk = C.c_int(0); secs = C.c_double(0.0); used = C.c_int(0)
-    rc = lib.smvs_host_reconstruct_scene_steps(scene_dir.encode(), C.byref(st),
+    rc = lib.smvs_host_reconstruct_scene_subplane(scene_dir.encode(), C.byref(st),
         C.c_uint((1 if sgm_adaptive_penalty2 else 0) | (2 if device_input_scaling else 0)
                  | (8 if device_shading_prep else 0) | (16 if gamma_correction else 0)),
-        C.c_int(sgm_num_steps),
+        C.c_int(sgm_num_steps), C.c_int(1 if sgm_subplane else 0),
         ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), out.ctypes.data_as(_i32p),
         C.c_int(out.size), C.byref(n), C.byref(sk), C.byref(secs), C.byref(used))
@@ -414,12 +420,15 @@ def view_queue_selftest(n_tasks, num_devices, views_in_flight, throwing_task=-1)
 
 
 def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
-              adaptive_penalty2=False, num_steps=128):
+              adaptive_penalty2=False, num_steps=128, subplane=False):
     """reconstruct_sgm_depth_for_view through the host mirror.
     adaptive_penalty2: SGMStereo::Options::adaptive_penalty2 (the reference's
     build without SSE, lib/sgm_stereo.cc:310-346); off by default.
     num_steps: SGMStereo::Options::num_steps, the inverse-depth planes: 2 .. 128,
-    or a multiple of 8 from 136 to 256."""
+    or a multiple of 8 from 136 to 256.
+    subplane: SGMStereo::Options::subplane (the winning plane's depth refined by
+    the parabola through its aggregated cost and its two neighbours'; not in
+    the reference); off by default."""
     lib = load()
     keep = []
     main, subs, n_subs, b = _marshal(inputs, keep)
@@ -428,9 +437,10 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
         w, h = (w + 1) // 2, (h + 1) // 2
     out = np.zeros((h, w), dtype=np.float32)
     ow = C.c_int(0); oh = C.c_int(0)
-    rc = lib.smvs_host_sgm_depth_steps(C.byref(main), subs, n_subs, C.byref(b),
+    rc = lib.smvs_host_sgm_depth_subplane(C.byref(main), subs, n_subs, C.byref(b),
         sgm_scale, C.c_float(min_depth), C.c_float(max_depth), device,
-        C.c_int(1 if adaptive_penalty2 else 0), C.c_int(num_steps), out.ctypes.data_as(_fp), C.byref(ow), C.byref(oh))
+        C.c_int(1 if adaptive_penalty2 else 0), C.c_int(num_steps),
+        C.c_int(1 if subplane else 0), out.ctypes.data_as(_fp), C.byref(ow), C.byref(oh))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
     assert (ow.value, oh.value) == (w, h)

@@ -2,7 +2,9 @@
 """Times smvs_sgm_run on the 960x540x128 workload of BASELINE.json configs[2]
 (profiling helper; use under rocprofv3 for per-kernel numbers).
 --adaptive-p2: the adaptive-penalty aggregation (SMVS_SGM_P2_ADAPTIVE, the
-reference's build without SSE) instead of the constant one; --repeat N: N timed
+reference's build without SSE) instead of the constant one; --subplane: the
+sub-plane winner (SMVS_SGM_WINNER_SUBPLANE) instead of the plane's depth, and
+the distinct depth values of the map; --repeat N: N timed
 calls instead of 3; --num-steps N: N inverse-depth planes instead of 128
 (2 .. 128, or a multiple of 8 from 136 to 256); --p2 N: penalty2 instead of 96
 (above 255: the u16 volume with atomics); --kernels: after one warm-up call,
@@ -34,9 +36,13 @@ repeat = _arg("--repeat", 3)
 D = _arg("--num-steps", 128)
 p2 = _arg("--p2", 96)
 kernels = "--kernels" in sys.argv
+subplane = "--subplane" in sys.argv
 kw = dict(adaptive_p2=True) if adaptive else {}
 if adaptive:
     print("penalty2 adapted to the intensity step (SMVS_SGM_P2_ADAPTIVE)")
+if subplane:
+    kw["subplane"] = True
+    print("sub-plane winner (SMVS_SGM_WINNER_SUBPLANE)")
 
 
 def run():
@@ -53,6 +59,8 @@ for i in range(repeat):
     out = run()
     dt = time.perf_counter() - t0
     print("sgm_run %dx%dx%d: %.1f ms (incl. H2D/D2H), valid %.2f" % (hw, hh, D, 1e3 * dt, (out["depth"] > 0).mean()))
+if subplane:
+    print("distinct depth values: %d" % np.unique(out["depth"][out["depth"] > 0]).size)
 if kernels:
     ms = (C.c_double * 8)()
     cnt = (C.c_longlong * 8)()
