@@ -49,10 +49,16 @@ bilateral_kernel(BilateralArgs A)
             float const dv = A.dm[(size_t)dm_y * A.dm_w + dm_x];
             if (dv == 0.0f)
                 continue;
-            // math::gaussian / gaussian_2d are std::exp on floats: the host's
-            // expf is correctly rounded (glibc), the device's float expf is
-            // not, so the exponential is taken in double and rounded once.
-            // The initial surface then matches the CPU path bit for bit.
+            // math::gaussian / gaussian_2d are std::exp on floats.  The
+            // exponential is taken in double and rounded once: the correctly
+            // rounded value, which the device's float expf does not give --
+            // and which the host's (glibc) expf misses by an ulp in ~0.3 % of
+            // its arguments (see bilateral_table_kernel).  So this path is
+            // NOT the CPU path bit for bit: on the cases of
+            // tests/test_gpu_bilateral.py the filtered map differs from it in
+            // 8 of 394,616 pixels, by at most two ulps
+            // (profiles/bilateral_forms_parity.txt; the tests allow 1e-5 of
+            // the largest depth).  The forms with the host's tables are.
             float weight = 1.0f;
             weight *= exp_rounded(-((float)kx * (float)kx
                 / (2.0f * A.sigma * A.sigma)
