@@ -468,6 +468,89 @@ int smvs_sgm_depth_for_view_raw_opts(int device, const uint8_t *main_img, int w,
     int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
     uint16_t penalty2, const smvs_sgm_options *opts, float *depth);
 
+/* How the checked maps of a view's neighbours become one map.  The reference
+ * (app/smvsrecon.cc:360-377) looks at the first two neighbours only and
+ * averages them where both have a depth:
+ *   SMVS_SGM_MERGE_REFERENCE  that: one or two neighbours, the bytes of the
+ *                             `_opts` entries (min_agree and agree_ratio are
+ *                             not read);
+ *   SMVS_SGM_MERGE_CONSENSUS  not in the reference: n = 1 .. SMVS_MAX_SUBS
+ *                             neighbours, 2 n runs, and per pixel the largest
+ *                             group of maps that agree with one of them.
+ * Definition of the consensus.  Per pixel, c[0 .. n-1] are the left/right-
+ * checked forward depths of the n neighbours in neighbour order (the check is
+ * sgm_stereo.cc:64-91, unchanged; 0 means no depth).  All arithmetic in float,
+ * in this order, no contraction, IEEE division:
+ *     best = 0, best_count = 0
+ *     for k = 0 .. n-1 with c[k] != 0:
+ *         count = number of j in 0 .. n-1 with c[j] != 0 and
+ *                 (j == k  or  fminf(c[j], c[k]) / fmaxf(c[j], c[k]) >= agree_ratio)
+ *         if count > best_count: best_count = count, best = k
+ *                                       (strict: ties keep the lowest k)
+ *     if best_count == 0 or best_count < min_agree: out = 0
+ *     else: s = 0.0f
+ *           for j ascending over the supporters of c[best] (the set counted
+ *               above): s = s + c[j]
+ *           out = s / (float)best_count
+ * The supporters are taken around one candidate (a star), not as a transitive
+ * closure: with a ~ b ~ c and a !~ c, b's star holds all three and a's two.
+ * support[pixel] = best_count as u8 (also where out = 0 because of min_agree).
+ * Two consequences hold to the bit: n = 2, agree_ratio = 0, min_agree = 1 gives
+ * the reference merge's bytes ((a + b) / 2.0f == (a + b) * 0.5f), and n = 1,
+ * min_agree = 1 gives the checked map itself.
+ * Accepted: n in 1 .. SMVS_MAX_SUBS, agree_ratio in [0, 1], min_agree in
+ * 1 .. SMVS_MAX_SUBS; anything else (a NaN ratio, a NULL options pointer, an
+ * unknown merge or winner, three neighbours with the reference's merge) is
+ * SMVS_ERR_INVALID before any device call.
+ * agree_ratio = 0.95 and min_agree = 2 are what the host mirror and the Python
+ * layer default to.  They are defaults of a user option, not tuned values: at
+ * 128 planes over a 3 .. 12 range adjacent planes differ by 0.6 % at the near
+ * end and by 2.4 % at the far end, so 0.95 admits about two planes at the far
+ * end (the left/right check uses 0.8).  Nobody has measured their effect on
+ * real scenes. */
+typedef enum { SMVS_SGM_MERGE_REFERENCE = 0, SMVS_SGM_MERGE_CONSENSUS = 1 } smvs_sgm_merge;
+typedef struct {
+    int p2_mode;        /* smvs_sgm_p2_mode */
+    int winner;         /* smvs_sgm_winner */
+    int merge;          /* smvs_sgm_merge */
+    int min_agree;
+    float agree_ratio;
+} smvs_sgm_view_options;
+
+/* smvs_sgm_depth_for_view_opts / _raw_opts with the merge selectable.  With
+ * the consensus the neighbour images are prepared one at a time, the n forward
+ * and n backward maps stay on the device, and one kernel does the n left/right
+ * checks and the merge per pixel.  Optional outputs of the consensus (NULL:
+ * not wanted; with the reference's merge they must be NULL):
+ *   checked[n * w * h]  the n checked forward maps, neighbour-major,
+ *   support[w * h]      best_count.
+ * (w, h of the outputs: the SGM-scale size, as for depth.) */
+int smvs_sgm_depth_for_view_merge(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_view_options *opts,
+    float *depth, float *checked, uint8_t *support);
+int smvs_sgm_depth_for_view_raw_merge(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_view_options *opts, float *depth, float *checked,
+    uint8_t *support);
+
+/* The check-and-merge kernel alone, on maps of the caller (as smvs_sgm_run
+ * exposes one run): fwd[n * w * h] are the n unchecked forward maps of the main
+ * view, neighbors[k] holds neighbour k's own backward map bwd[width * height]
+ * and the float reprojection main -> neighbour of the check.  opts: merge must
+ * be SMVS_SGM_MERGE_CONSENSUS (p2_mode and winner are not read).  Outputs, any
+ * may be NULL: merged[w * h], checked[n * w * h], support[w * h].  A
+ * correspondence that is not a number fails the check. */
+typedef struct {
+    const float *bwd;
+    int width, height;
+    float M_fwd[9], t_fwd[3];
+} smvs_sgm_check_neighbor;
+int smvs_sgm_check_merge(int device, const float *fwd, int w, int h,
+    const smvs_sgm_check_neighbor *neighbors, int n_neighbors,
+    const smvs_sgm_view_options *opts, float *merged, float *checked, uint8_t *support);
+
 /* DepthOptimizer::depthmap_bilateral_filter, depth_optimizer.cc:957-1004 */
 int smvs_bilateral_upsample(int device, const float *dm, int dm_w, int dm_h,
     const float *ci, int w, int h, int channels, float sigma,
@@ -813,7 +896,8 @@ enum {
     SMVS_SGM_K_PATHS,        /* 8-path aggregation (K14) */
     SMVS_SGM_K_WTA,          /* argmin + depth (K15) */
     SMVS_SGM_K_LR_CHECK,     /* left / right consistency (K16) */
-    SMVS_SGM_K_MERGE,        /* two-neighbour merge (K16) */
+    SMVS_SGM_K_MERGE,        /* two-neighbour merge (K16); with SMVS_SGM_MERGE_CONSENSUS the one
+                              * check-and-merge kernel (then no SMVS_SGM_K_LR_CHECK launches) */
     SMVS_SGM_K_BILATERAL,    /* joint bilateral upsample (K17) */
     SMVS_SGM_K_COUNT
 };

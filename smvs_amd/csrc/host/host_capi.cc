@@ -306,7 +306,45 @@ smvs_host_sgm_depth_subplane(const smvs_host_view *main_in, const smvs_host_view
     float min_depth, float max_depth, int device, int adaptive_penalty2,
     int num_steps, int subplane, float *depth_out, int *out_w, int *out_h)
 {
+    return smvs_host_sgm_depth_merge(main_in, subs_in, n_subs, bundle_in, sgm_scale,
+        min_depth, max_depth, device, adaptive_penalty2, num_steps, subplane, 2, 0, 0.95f,
+        2, depth_out, out_w, out_h);
+}
+
+extern "C" int
+smvs_host_sgm_merge_defaults(int *ints8, float *ratios2)
+{
+    if (ints8 == nullptr || ratios2 == nullptr) {
+        g_host_error = "smvs_host_sgm_merge_defaults: bad argument";
+        return -1;
+    }
+    SGMStereo::Options const opts;
+    ReconSettings const conf;
+    ints8[0] = opts.num_neighbors;
+    ints8[1] = opts.consensus ? 1 : 0;
+    ints8[2] = opts.min_agree;
+    ints8[3] = 0;
+    ints8[4] = conf.sgm_neighbors;
+    ints8[5] = conf.sgm_consensus ? 1 : 0;
+    ints8[6] = conf.sgm_min_agree;
+    ints8[7] = 0;
+    ratios2[0] = opts.agree_ratio;
+    ratios2[1] = conf.sgm_agree_ratio;
+    return 0;
+}
+
+extern "C" int
+smvs_host_sgm_depth_merge(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, int sgm_scale,
+    float min_depth, float max_depth, int device, int adaptive_penalty2,
+    int num_steps, int subplane, int num_neighbors, int consensus, float agree_ratio,
+    int min_agree, float *depth_out, int *out_w, int *out_h)
+{
     try {
+        // (before the views are copied: an argument error needs no image)
+        if (consensus == 0 && num_neighbors > 2)
+            throw std::invalid_argument("smvs_host_sgm_depth_merge: more than two "
+                "neighbours need the consensus merge");
         if (!SGMStereo::Options::valid_num_steps(num_steps))
             throw std::invalid_argument("smvs_host_sgm_depth_steps: num_steps must be "
                 "in [2, 128] or a multiple of 8 in [136, 256]");
@@ -323,6 +361,10 @@ smvs_host_sgm_depth_subplane(const smvs_host_view *main_in, const smvs_host_view
         opts.device = device;
         opts.adaptive_penalty2 = adaptive_penalty2 != 0;
         opts.subplane = subplane != 0;
+        opts.num_neighbors = num_neighbors;
+        opts.consensus = consensus != 0;
+        opts.agree_ratio = agree_ratio;
+        opts.min_agree = min_agree;
         FloatImage::Ptr d = reconstruct_sgm_depth_for_view(opts, main_view, subs,
             bundle);
         if (out_w != nullptr)
@@ -934,7 +976,28 @@ smvs_host_reconstruct_scene_subplane(const char *scene_dir,
     int max_reconstructed, int *n_reconstructed, int *n_skipped, double *seconds,
     int *input_scale_used)
 {
+    return smvs_host_reconstruct_scene_merge(scene_dir, o, flags, sgm_num_steps,
+        sgm_subplane, 2, 0, 0.95f, 2, view_ids, n_view_ids, reconstructed_out,
+        max_reconstructed, n_reconstructed, n_skipped, seconds, input_scale_used);
+}
+
+extern "C" int
+smvs_host_reconstruct_scene_merge(const char *scene_dir,
+    const smvs_host_recon_settings *o, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const int *view_ids, int n_view_ids, int *reconstructed_out,
+    int max_reconstructed, int *n_reconstructed, int *n_skipped, double *seconds,
+    int *input_scale_used)
+{
     try {
+        if (sgm_neighbors < 1 || sgm_neighbors > SMVS_MAX_SUBS
+            || (sgm_consensus == 0 && sgm_neighbors > 2))
+            throw std::invalid_argument("smvs_host_reconstruct_scene_merge: sgm_neighbors "
+                "must be 1 or 2, or up to 16 with sgm_consensus");
+        if (sgm_consensus != 0 && (!(sgm_agree_ratio >= 0.0f && sgm_agree_ratio <= 1.0f)
+                || sgm_min_agree < 1 || sgm_min_agree > SMVS_MAX_SUBS))
+            throw std::invalid_argument("smvs_host_reconstruct_scene_merge: sgm_agree_ratio "
+                "must be in [0, 1] and sgm_min_agree in [1, 16]");
         if (!SGMStereo::Options::valid_num_steps(sgm_num_steps))
             throw std::invalid_argument("smvs_host_reconstruct_scene_steps: sgm_num_steps "
                 "must be in [2, 128] or a multiple of 8 in [136, 256]");
@@ -960,6 +1023,10 @@ smvs_host_reconstruct_scene_subplane(const char *scene_dir,
         conf.sgm_adaptive_penalty2 = (flags & SMVS_HOST_SCENE_ADAPTIVE_PENALTY2) != 0u;
         conf.sgm_num_steps = sgm_num_steps;
         conf.sgm_subplane = sgm_subplane != 0;
+        conf.sgm_neighbors = sgm_neighbors;
+        conf.sgm_consensus = sgm_consensus != 0;
+        conf.sgm_agree_ratio = sgm_agree_ratio;
+        conf.sgm_min_agree = sgm_min_agree;
         conf.device_input_scaling = (flags & SMVS_HOST_SCENE_DEVICE_INPUT_SCALING) != 0u;
         conf.device_shading_prep = (flags & SMVS_HOST_SCENE_DEVICE_SHADING_PREP) != 0u;
         conf.gamma_correction = (flags & SMVS_HOST_SCENE_GAMMA_SRGB) != 0u;

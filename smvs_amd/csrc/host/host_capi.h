@@ -143,6 +143,25 @@ int smvs_host_sgm_depth_subplane(const smvs_host_view *main_view,
     int sgm_scale, float min_depth, float max_depth, int device,
     int adaptive_penalty2, int num_steps, int subplane, float *depth_out, int *out_w,
     int *out_h);
+/* The same with SGMStereo::Options::num_neighbors / consensus / agree_ratio /
+ * min_agree (not in the reference, which merges the first two neighbours): the
+ * first min(n_subs, num_neighbors) neighbours, merged by consensus
+ * (SMVS_SGM_MERGE_CONSENSUS of include/smvs_hip.h) when consensus != 0.
+ * num_neighbors > 2 with consensus == 0 is an argument error, never a silent
+ * truncation.  smvs_host_sgm_depth_subplane forwards to this with
+ * (2, 0, 0.95f, 2), which takes the path and gives the bytes it always did. */
+int smvs_host_sgm_depth_merge(const smvs_host_view *main_view,
+    const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
+    int sgm_scale, float min_depth, float max_depth, int device,
+    int adaptive_penalty2, int num_steps, int subplane, int num_neighbors,
+    int consensus, float agree_ratio, int min_agree, float *depth_out, int *out_w,
+    int *out_h);
+/* The merge options as a default-constructed SGMStereo::Options and
+ * ReconSettings hold them (no device involved): ints4 = { Options::
+ * num_neighbors, consensus, min_agree, 0 }, then the same of ReconSettings::
+ * sgm_neighbors, sgm_consensus, sgm_min_agree in ints4[4 .. 7]; ratios2 =
+ * { Options::agree_ratio, ReconSettings::sgm_agree_ratio }. */
+int smvs_host_sgm_merge_defaults(int *ints8, float *ratios2);
 /* The switches of the SGM front end that the reference does not have, as a
  * default-constructed SGMStereo::Options and ReconSettings hold them (no
  * device involved): out4 = { Options::adaptive_penalty2, Options::subplane,
@@ -273,6 +292,19 @@ int smvs_host_reconstruct_scene_steps(const char *scene_dir,
 int smvs_host_reconstruct_scene_subplane(const char *scene_dir,
     const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
     int sgm_subplane, const int *view_ids, int n_view_ids, int *reconstructed_out,
+    int max_reconstructed, int *n_reconstructed, int *n_skipped, double *seconds,
+    int *input_scale_used);
+/* The same with ReconSettings::sgm_neighbors / sgm_consensus / sgm_agree_ratio /
+ * sgm_min_agree (arguments: the settings struct keeps its layout): every view's
+ * smvs-sgm map from its first sgm_neighbors neighbours (capped by the
+ * neighbours the view has), merged by consensus when sgm_consensus != 0;
+ * sgm_neighbors > 2 without it is an argument error.  The reuse rule is that of
+ * sgm_subplane: a scene that already has smvs-sgm embeddings needs force_sgm.
+ * smvs_host_reconstruct_scene_subplane forwards to this with (2, 0, 0.95f, 2). */
+int smvs_host_reconstruct_scene_merge(const char *scene_dir,
+    const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const int *view_ids, int n_view_ids, int *reconstructed_out,
     int max_reconstructed, int *n_reconstructed, int *n_skipped, double *seconds,
     int *input_scale_used);
 

@@ -584,6 +584,10 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                         sgm_opts.device = device;
                         sgm_opts.adaptive_penalty2 = conf.sgm_adaptive_penalty2;
                         sgm_opts.subplane = conf.sgm_subplane;
+                        sgm_opts.num_neighbors = conf.sgm_neighbors;
+                        sgm_opts.consensus = conf.sgm_consensus;
+                        sgm_opts.agree_ratio = conf.sgm_agree_ratio;
+                        sgm_opts.min_agree = conf.sgm_min_agree;
                         (void)reconstruct_sgm_depth_for_view(sgm_opts, main_view,
                             stereo_views, bundle);
                         save_mvei(view.image_path("smvs-sgm"),

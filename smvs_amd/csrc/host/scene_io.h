@@ -106,6 +106,18 @@ struct ReconSettings
     // right size is reused as before (app/smvsrecon.cc:702-708): switching this
     // on for a scene that has one needs force_sgm
     bool sgm_subplane = false;
+    // not in the reference's AppSettings: SGMStereo::Options::num_neighbors /
+    // consensus / agree_ratio / min_agree -- the smvs-sgm map of a view from its
+    // first sgm_neighbors neighbours (capped by the neighbours the view has),
+    // merged by consensus; more than two need sgm_consensus.  0.95 and 2 are
+    // defaults of a user option, not tuned values, and their effect on real
+    // scenes has not been measured.  As for sgm_subplane, an smvs-sgm embedding
+    // of the right size is reused: switching this on for a scene that has one
+    // needs force_sgm
+    int sgm_neighbors = 2;
+    bool sgm_consensus = false;
+    float sgm_agree_ratio = 0.95f;
+    int sgm_min_agree = 2;
     // not in the reference's AppSettings: the input scaling of :621-650 on the
     // device (rescale_half_size_gaussian_device), one ViewQueue task per view
     bool device_input_scaling = false;

@@ -158,6 +158,21 @@ run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
     int w = main_bytes->width(), h = main_bytes->height();
     sgm_scale_size(o.scale, &w, &h);
     FloatImage::Ptr depth = FloatImage::create_for_overwrite(w, h, 1);
+    if (o.consensus) {
+        // the same over n neighbours: 2 n x run_sgm, then the n checks and the
+        // consensus in one kernel
+        smvs_sgm_options const base = device_options(o);
+        smvs_sgm_view_options const view_opts = { base.p2_mode, base.winner,
+            SMVS_SGM_MERGE_CONSENSUS, o.min_agree, o.agree_ratio };
+        int const rc = smvs_sgm_depth_for_view_raw_merge(o.device, main_bytes->begin(),
+            main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
+            channels.data(), (int)dev.size(), o.scale, o.num_steps, o.penalty1,
+            o.penalty2, &view_opts, depth->begin(), nullptr, nullptr);
+        if (rc != SMVS_OK)
+            throw std::runtime_error(std::string("smvs_sgm_depth_for_view_raw_merge: ")
+                + smvs_last_error());
+        return depth;
+    }
     // desaturate + half-size on the device, then 4 x run_sgm, L/R check, merge
     smvs_sgm_options const dev_opts = device_options(o);
     int const rc = smvs_sgm_depth_for_view_raw_opts(o.device, main_bytes->begin(),
@@ -189,10 +204,19 @@ reconstruct_sgm_depth_for_view(SGMStereo::Options opts,
     Bundle::ConstPtr bundle)
 {
     // app/smvsrecon.cc:346-384: SGMStereo::reconstruct against the first two
-    // neighbours and the merge of the two checked maps, in one device call
+    // neighbours and the merge of the two checked maps, in one device call;
+    // with opts.consensus against the first opts.num_neighbors
     if (neighbors.empty())
         throw std::invalid_argument("reconstruct_sgm_depth_for_view: no neighbour");
-    std::vector<PairInputs> pairs(std::min<std::size_t>(neighbors.size(), 2));
+    if (opts.num_neighbors < 1 || opts.num_neighbors > SMVS_MAX_SUBS)
+        throw std::invalid_argument("reconstruct_sgm_depth_for_view: num_neighbors "
+            "must be in [1, " + std::to_string(SMVS_MAX_SUBS) + "]");
+    if (!opts.consensus && opts.num_neighbors > 2)
+        throw std::invalid_argument("reconstruct_sgm_depth_for_view: the reference's "
+            "merge takes one or two neighbours (app/smvsrecon.cc:360-365); more need "
+            "Options::consensus");
+    std::vector<PairInputs> pairs(std::min<std::size_t>(neighbors.size(),
+        (std::size_t)opts.num_neighbors));
     for (std::size_t k = 0; k < pairs.size(); ++k)
         prepare_pair(opts, main_view, neighbors[k], bundle, &pairs[k]);
     FloatImage::Ptr d1 = run_pairs(opts, main_view, pairs);

@@ -1,6 +1,6 @@
 // Host mirror of smvs::SGMStereo (reference: lib/sgm_stereo.h:21-88).  The
 // cost volumes, the 8-path aggregation, the WTA, the left/right check and the
-// two-neighbour merge run on the device (smvs_sgm_depth_for_view); the host
+// merge run on the device (smvs_sgm_depth_for_view_raw_opts / _raw_merge); the host
 // keeps the depth range from the bundle and the image half-sizing.
 #pragma once
 
@@ -35,6 +35,21 @@ public:
         // refines the winner with the parabola through its aggregated cost and
         // its two neighbours' (SMVS_SGM_WINNER_SUBPLANE, include/smvs_hip.h)
         bool subplane = false;
+        // not in the reference, whose reconstruct_sgm_depth_for_view looks at
+        // the first two neighbours only (app/smvsrecon.cc:360-377):
+        // reconstruct_sgm_depth_for_view uses the first min(neighbors.size(),
+        // num_neighbors) neighbours.  More than two need `consensus`
+        // (SMVS_SGM_MERGE_CONSENSUS, include/smvs_hip.h: per pixel the mean of
+        // the largest group of checked depths whose ratio to one of them is at
+        // least agree_ratio; no depth with fewer than min_agree of them).
+        // 0.95 and 2 are defaults of a user option, not tuned values: at 128
+        // planes over a 3 .. 12 range 0.95 admits about two planes at the far
+        // end (the left/right check uses 0.8), and nobody has measured their
+        // effect on real scenes.
+        int num_neighbors = 2;
+        bool consensus = false;
+        float agree_ratio = 0.95f;
+        int min_agree = 2;
 
         // the plane counts smvs_sgm_run / smvs_sgm_depth_for_view accept
         static bool valid_num_steps(int n)
@@ -63,7 +78,10 @@ private:
     ByteImage::ConstPtr neighbor_image;
 };
 
-// app/smvsrecon.cc:346-384: SGM against the first two neighbours, averaged
+// app/smvsrecon.cc:346-384: SGM against the first two neighbours, averaged;
+// with Options::consensus against the first Options::num_neighbors, merged by
+// consensus.  More than two neighbours without `consensus` is
+// std::invalid_argument (never a silent truncation).
 FloatImage::Ptr reconstruct_sgm_depth_for_view(SGMStereo::Options opts,
     StereoView::Ptr main_view, std::vector<StereoView::Ptr> const& neighbors,
     Bundle::ConstPtr bundle = nullptr);

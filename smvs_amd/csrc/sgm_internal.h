@@ -52,9 +52,10 @@ enum {
     WS_MAIN, WS_NBR0, WS_NBR1, WS_FWD0, WS_FWD1, WS_BWD, WS_COST16,   // a view's front end
     WS_RAW, WS_RAW0, WS_RAW1,                                         // raw u8 images + scratch
     WS_BIL_DM, WS_BIL_CI, WS_BIL_OUT,                                 // bilateral upsample
-    WS_DELTA                                                          // eight path-byte volumes
+    WS_DELTA,                                                         // eight path-byte volumes
+    WS_FWDN, WS_BWDN, WS_SUPPORT                                      // consensus merge: n + n maps, support
 };
-static_assert(WS_DELTA < Workspace::SLOTS, "the last slot must exist in a Workspace");
+static_assert(WS_SUPPORT < Workspace::SLOTS, "the last slot must exist in a Workspace");
 
 // The largest plane count of a run: the key of the WTA kernels is
 // value * 256 + plane (one byte for the plane), and 64 lanes x 4 planes is one
@@ -79,9 +80,10 @@ static_assert(sgm_plane_count_ok(2) && sgm_plane_count_ok(127) && sgm_plane_coun
 // Work buffers of one run_sgm inside a pooled workspace; reused by the runs of
 // a view (the runs are ordered on the workspace's stream).  Every run has its
 // own depth table: SGM_MAX_PLANES depths, then as many inverse depths (the
-// sub-plane winner's).
+// sub-plane winner's).  MAX_RUNS: two runs per neighbour of the consensus front
+// end (64 KB of tables).
 struct SgmWorkspace {
-    static constexpr int MAX_RUNS = 4;
+    static constexpr int MAX_RUNS = 2 * SMVS_MAX_SUBS;
     Workspace *ws;
     SgmProfile *prof = nullptr;
     float *depths = nullptr;
@@ -129,6 +131,12 @@ int check_sgm_plane_count(int num_steps);
 // involved: the entries call this first; p2_mode goes through
 // check_sgm_penalties as in the *_mode entries).
 int check_sgm_winner(const smvs_sgm_options *opts);
+// The options of the *_merge entries and the neighbour count they go with:
+// non-NULL, a known winner and merge, one or two neighbours for the reference's
+// merge, 1 .. SMVS_MAX_SUBS neighbours, agree_ratio in [0, 1] (a NaN is none)
+// and min_agree in 1 .. SMVS_MAX_SUBS for the consensus (no device involved:
+// the entries call this first).  (sgm_view.hip)
+int check_sgm_view_options(const smvs_sgm_view_options *opts, int n_neighbors);
 
 // The plan of a run (sgm_path_plan.h) with this process's SMVS_SGM_PATHS: `wave`
 // asks for a wave per line, two planes per lane, up to 128 planes.

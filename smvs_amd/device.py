@@ -434,6 +434,29 @@ def _sgm_options(adaptive_p2, subplane):
                       WINNER_SUBPLANE if subplane else WINNER_PLANE)
 
 
+MERGE_REFERENCE, MERGE_CONSENSUS = 0, 1   # smvs_sgm_merge
+MAX_SUBS = 16                             # SMVS_MAX_SUBS
+
+
+class SgmViewOptions(C.Structure):
+    """smvs_sgm_view_options of include/smvs_hip.h."""
+    _fields_ = [("p2_mode", C.c_int), ("winner", C.c_int), ("merge", C.c_int),
+                ("min_agree", C.c_int), ("agree_ratio", C.c_float)]
+
+
+class SgmCheckNeighbor(C.Structure):
+    """smvs_sgm_check_neighbor of include/smvs_hip.h."""
+    _fields_ = [("bwd", _fp), ("width", C.c_int), ("height", C.c_int),
+                ("M_fwd", C.c_float * 9), ("t_fwd", C.c_float * 3)]
+
+
+def _sgm_view_options(adaptive_p2, subplane, consensus, agree_ratio, min_agree):
+    return SgmViewOptions(P2_ADAPTIVE if adaptive_p2 else P2_CONSTANT,
+                          WINNER_SUBPLANE if subplane else WINNER_PLANE,
+                          MERGE_CONSENSUS if consensus else MERGE_REFERENCE,
+                          int(min_agree), float(agree_ratio))
+
+
 def sgm_run(main_img, neighbor_img, M, t, min_depth, max_depth, num_steps=128,
             p1=6, p2=96, device=0, want_volumes=False, adaptive_p2=False, subplane=False):
     """SGMStereo::run_sgm on the device.  adaptive_p2: the path aggregation of
@@ -504,18 +527,36 @@ class SgmNeighbor(C.Structure):
 
 
 def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0,
-                       adaptive_p2=False, halvings=None, subplane=False):
+                       adaptive_p2=False, halvings=None, subplane=False,
+                       consensus=False, agree_ratio=0.95, min_agree=2, want_checked=False):
     """reconstruct_sgm_depth_for_view on the device.  neighbors: list of dicts
     {image, M_fwd, t_fwd, M_bwd, t_bwd, range_main, range_neighbor} (SGM-scale
     u8 images, float reprojections).  adaptive_p2, subplane: as for sgm_run
     (all four runs of the view).
     halvings (an int): the images are full-resolution u8 embeddings of one or
     three channels, desaturated and halved that often on the device
-    (smvs_sgm_depth_for_view_raw_opts); the map has the SGM-scale size."""
+    (smvs_sgm_depth_for_view_raw_opts); the map has the SGM-scale size.
+    consensus: SMVS_SGM_MERGE_CONSENSUS of include/smvs_hip.h (not in the
+    reference, which merges the first two neighbours): 1 .. 16 neighbours, per
+    pixel the mean of the largest group of checked depths whose ratio to one of
+    them is at least agree_ratio, or 0 with fewer than min_agree of them; off by
+    default.  0.95 and 2 are defaults of a user option, not tuned values (0.95
+    admits about two of 128 planes at the far end of a 3 .. 12 range; the
+    left/right check uses 0.8); nobody has measured their effect on real scenes.
+    want_checked (with consensus): returns a dict {depth, checked (n, h, w),
+    support (h, w) u8} instead of the depth map."""
     lib = _capi.load()
     opts = _sgm_options(adaptive_p2, subplane)
     main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
     h, w = main_img.shape[:2]
+    if consensus or want_checked:
+        if not consensus:
+            raise ValueError("want_checked: the checked maps and the support are "
+                             "outputs of the consensus merge")
+        return _sgm_depth_for_view_merge(
+            lib, main_img, neighbors, num_steps, p1, p2, device,
+            _sgm_view_options(adaptive_p2, subplane, True, agree_ratio, min_agree),
+            None if halvings is None else int(halvings), want_checked)
     if halvings is not None:
         return _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device,
                                        opts, int(halvings))
@@ -568,6 +609,67 @@ def _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device,
           arr, nch, len(neighbors), halvings, num_steps, C.c_uint16(p1), C.c_uint16(p2),
           C.byref(opts), _p(depth, _fp)))
     return depth
+
+
+def _sgm_depth_for_view_merge(lib, main_img, neighbors, num_steps, p1, p2, device, vopts,
+                              halvings, want_checked):
+    """smvs_sgm_depth_for_view_merge (halvings None) / _raw_merge."""
+    keep = []
+    arr = _sgm_neighbors(neighbors, keep)
+    n = len(neighbors)
+    h, w = main_img.shape[:2]
+    oh, ow = h, w
+    for _ in range(halvings or 0):
+        ow, oh = (ow + 1) // 2, (oh + 1) // 2
+    depth = np.zeros((oh, ow), dtype=np.float32)
+    checked = np.zeros((n, oh, ow), dtype=np.float32) if want_checked else None
+    support = np.zeros((oh, ow), dtype=np.uint8) if want_checked else None
+    if halvings is None:
+        if main_img.ndim != 2 or any(k.ndim != 2 for k in keep):
+            raise ValueError("one-channel images at SGM scale (or pass halvings)")
+        check(lib.smvs_sgm_depth_for_view_merge(device, _p(main_img, _u8p), w, h, arr, n,
+              num_steps, C.c_uint16(p1), C.c_uint16(p2), C.byref(vopts), _p(depth, _fp),
+              _p(checked, _fp), _p(support, _u8p)))
+    else:
+        channels = 1 if main_img.ndim == 2 else main_img.shape[2]
+        nch = (C.c_int * n)(*[1 if k.ndim == 2 else k.shape[2] for k in keep])
+        check(lib.smvs_sgm_depth_for_view_raw_merge(device, _p(main_img, _u8p), w, h,
+              channels, arr, nch, n, halvings, num_steps, C.c_uint16(p1), C.c_uint16(p2),
+              C.byref(vopts), _p(depth, _fp), _p(checked, _fp), _p(support, _u8p)))
+    if want_checked:
+        return dict(depth=depth, checked=checked, support=support)
+    return depth
+
+
+def sgm_check_merge(fwd, neighbors, agree_ratio=0.95, min_agree=2, device=0):
+    """smvs_sgm_check_merge: the kernel of the consensus front end alone, on
+    maps of the caller.  fwd (n, h, w): the unchecked forward maps of the main
+    view; neighbors: n dicts {bwd (nh, nw), M_fwd, t_fwd} (the neighbour's own
+    backward map, the float reprojection main -> neighbour of the check).
+    Returns dict(merged (h, w), checked (n, h, w), support (h, w) u8)."""
+    lib = _capi.load()
+    fwd = _f32(fwd)
+    if fwd.ndim != 3 or fwd.shape[0] != len(neighbors):
+        raise ValueError("fwd: (n, h, w) with one map per neighbour")
+    n, h, w = fwd.shape
+    keep = []
+    arr = (SgmCheckNeighbor * max(n, 1))()
+    for k, nb in enumerate(neighbors):
+        b = _f32(nb["bwd"])
+        keep.append(b)
+        arr[k].bwd = _p(b, _fp)
+        arr[k].height, arr[k].width = b.shape
+        for name, cnt in (("M_fwd", 9), ("t_fwd", 3)):
+            v = _f32(nb[name]).reshape(cnt)
+            for i in range(cnt):
+                getattr(arr[k], name)[i] = float(v[i])
+    vopts = _sgm_view_options(False, False, True, agree_ratio, min_agree)
+    merged = np.zeros((h, w), dtype=np.float32)
+    checked = np.zeros((n, h, w), dtype=np.float32)
+    support = np.zeros((h, w), dtype=np.uint8)
+    check(lib.smvs_sgm_check_merge(device, _p(fwd, _fp), w, h, arr, n, C.byref(vopts),
+          _p(merged, _fp), _p(checked, _fp), _p(support, _u8p)))
+    return dict(merged=merged, checked=checked, support=support)
 
 
 class MeshView(C.Structure):

@@ -234,7 +234,8 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       views_in_flight=2, input_scale=-1, max_pixels=1700000, details=False,
                       sgm_adaptive_penalty2=False, device_input_scaling=False,
                       device_shading_prep=False, gamma_correction=False, sgm_num_steps=128,
-                      sgm_subplane=False):
+                      sgm_subplane=False, sgm_neighbors=2, sgm_consensus=False,
+                      sgm_agree_ratio=0.95, sgm_min_agree=2):
     """smvsrecon's scene-level run (app/smvsrecon.cc:400-745) through
     smvs_amd::reconstruct_scene: returns (reconstructed ids, skipped, seconds)
     [, input scale used if `details`].  input_scale < 0 (the default, as
@@ -259,7 +260,15 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     refined between the planes (SGMStereo::Options::subplane); off by default.
     An smvs-sgm embedding of the right size is reused as before
     (app/smvsrecon.cc:702-708): switching the mode on for a scene that has been
-    reconstructed already needs force_sgm as well."""
+    reconstructed already needs force_sgm as well.
+    sgm_neighbors, sgm_consensus, sgm_agree_ratio, sgm_min_agree:
+    ReconSettings::sgm_neighbors / ... -- the smvs-sgm map of every view from its
+    first sgm_neighbors neighbours (capped by the neighbours the view has, which
+    num_neighbors bounds), merged by consensus (SGMStereo::Options::consensus,
+    SMVS_SGM_MERGE_CONSENSUS of include/smvs_hip.h); more than two neighbours
+    without sgm_consensus is an error.  Off by default; 0.95 and 2 are defaults of
+    a user option, not tuned values, and nobody has measured their effect on real
+    scenes.  The reuse rule is that of sgm_subplane (force_sgm)."""
     lib = load()
     st = ReconSettings(image_embedding.encode(), regularization, output_scale,
                        1 if use_shading else 0, 1 if use_sgm else 0,
@@ -273,10 +282,12 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                              C.byref(cap), None, None, None, None, None, None, None)
     out = np.zeros(max(cap.value, 1), np.int32)
     n = C.c_int(0); sk = C.c_int(0); secs = C.c_double(0.0); used = C.c_int(0)
-    rc = lib.smvs_host_reconstruct_scene_subplane(scene_dir.encode(), C.byref(st),
+    rc = lib.smvs_host_reconstruct_scene_merge(scene_dir.encode(), C.byref(st),
         C.c_uint((1 if sgm_adaptive_penalty2 else 0) | (2 if device_input_scaling else 0)
                  | (8 if device_shading_prep else 0) | (16 if gamma_correction else 0)),
         C.c_int(sgm_num_steps), C.c_int(1 if sgm_subplane else 0),
+        C.c_int(sgm_neighbors), C.c_int(1 if sgm_consensus else 0),
+        C.c_float(sgm_agree_ratio), C.c_int(sgm_min_agree),
         ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), out.ctypes.data_as(_i32p),
         C.c_int(out.size), C.byref(n), C.byref(sk), C.byref(secs), C.byref(used))
@@ -420,7 +431,8 @@ def view_queue_selftest(n_tasks, num_devices, views_in_flight, throwing_task=-1)
 
 
 def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
-              adaptive_penalty2=False, num_steps=128, subplane=False):
+              adaptive_penalty2=False, num_steps=128, subplane=False, neighbors=2,
+              consensus=False, agree_ratio=0.95, min_agree=2):
     """reconstruct_sgm_depth_for_view through the host mirror.
     adaptive_penalty2: SGMStereo::Options::adaptive_penalty2 (the reference's
     build without SSE, lib/sgm_stereo.cc:310-346); off by default.
@@ -428,7 +440,16 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
     or a multiple of 8 from 136 to 256.
     subplane: SGMStereo::Options::subplane (the winning plane's depth refined by
     the parabola through its aggregated cost and its two neighbours'; not in
-    the reference); off by default."""
+    the reference); off by default.
+    neighbors, consensus, agree_ratio, min_agree: SGMStereo::Options::
+    num_neighbors / consensus / agree_ratio / min_agree -- the first `neighbors`
+    neighbours of the inputs, merged by consensus (SMVS_SGM_MERGE_CONSENSUS of
+    include/smvs_hip.h: per pixel the mean of the largest group of checked
+    depths whose ratio to one of them is at least agree_ratio, none with fewer
+    than min_agree).  More than two neighbours without consensus raise; off by
+    default.  0.95 and 2 are defaults of a user option, not tuned values (0.95
+    admits about two of 128 planes at the far end of a 3 .. 12 range; the
+    left/right check uses 0.8); nobody has measured their effect on real scenes."""
     lib = load()
     keep = []
     main, subs, n_subs, b = _marshal(inputs, keep)
@@ -437,10 +458,12 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
         w, h = (w + 1) // 2, (h + 1) // 2
     out = np.zeros((h, w), dtype=np.float32)
     ow = C.c_int(0); oh = C.c_int(0)
-    rc = lib.smvs_host_sgm_depth_subplane(C.byref(main), subs, n_subs, C.byref(b),
+    rc = lib.smvs_host_sgm_depth_merge(C.byref(main), subs, n_subs, C.byref(b),
         sgm_scale, C.c_float(min_depth), C.c_float(max_depth), device,
         C.c_int(1 if adaptive_penalty2 else 0), C.c_int(num_steps),
-        C.c_int(1 if subplane else 0), out.ctypes.data_as(_fp), C.byref(ow), C.byref(oh))
+        C.c_int(1 if subplane else 0), C.c_int(neighbors), C.c_int(1 if consensus else 0),
+        C.c_float(agree_ratio), C.c_int(min_agree), out.ctypes.data_as(_fp), C.byref(ow),
+        C.byref(oh))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
     assert (ow.value, oh.value) == (w, h)

@@ -9,7 +9,13 @@ calls instead of 3; --num-steps N: N inverse-depth planes instead of 128
 (2 .. 128, or a multiple of 8 from 136 to 256); --p2 N: penalty2 instead of 96
 (above 255: the u16 volume with atomics); --kernels: after one warm-up call,
 the per-kernel event times of the timed calls (smvs_sgm_profile) and the path
-kernel's share of the HBM peak from its algorithmic bytes."""
+kernel's share of the HBM peak from its algorithmic bytes.
+--neighbors N [--consensus]: instead of one run, a view's whole front end
+(smvs_sgm_depth_for_view_opts, or ..._merge with SMVS_SGM_MERGE_CONSENSUS at
+agree_ratio 0.95, min_agree 2) over N ring neighbours at the same size: the
+time per view and, from smvs_sgm_profile, the left/right-check and merge
+kernels (with --consensus the one fused kernel, reported as merge) with the
+bytes they move.  Without --consensus N is 1 or 2, the reference's merge."""
 import ctypes as C
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -43,6 +49,62 @@ if adaptive:
 if subplane:
     kw["subplane"] = True
     print("sub-plane winner (SMVS_SGM_WINNER_SUBPLANE)")
+
+if "--neighbors" in sys.argv:
+    n = _arg("--neighbors", 2)
+    consensus = "--consensus" in sys.argv
+    main, subs = synth.ring_cameras(w, h, n)
+    small = [im[::2, ::2].copy() for im in [synth.render(scene, c) for c in [main] + subs]]
+    cams = [synth.Camera(c.R, c.t, c.flen, hw, hh) for c in [main] + subs]
+    nbs = []
+    for k in range(1, n + 1):
+        Mf, tf = synth.reprojection(cams[0], cams[k])
+        Mb, tb = synth.reprojection(cams[k], cams[0])
+        nbs.append(dict(image=small[k], M_fwd=Mf, t_fwd=tf, M_bwd=Mb, t_bwd=tb,
+                        range_main=[2.0, 10.0], range_neighbor=[2.0, 10.0]))
+    if consensus:
+        kw["consensus"] = True
+    print("front end of a view, %d neighbours, %s" % (n, "consensus merge (0.95, 2)" if consensus
+                                                      else "the reference's merge"))
+
+    def view():
+        return smvs_amd.sgm_depth_for_view(small[0], nbs, D, 6, p2, **kw)
+
+    lib = _capi.load()
+    view()   # warm-up: workspace growth, first-launch costs
+    times = []
+    for i in range(repeat):
+        t0 = time.perf_counter()
+        out = view()
+        times.append(time.perf_counter() - t0)
+        print("front end %dx%dx%d x %d neighbours: %.2f ms per view (incl. H2D/D2H), valid %.3f"
+              % (hw, hh, D, n, 1e3 * times[-1], (out > 0).mean()))
+    print("front end: best %.2f ms per view" % (1e3 * min(times)))
+    # (the events of the per-kernel timer serialise the launches: a call of its own)
+    lib.smvs_sgm_profile(1, None, None)
+    for i in range(repeat):
+        view()
+    ms = (C.c_double * 8)()
+    cnt = (C.c_longlong * 8)()
+    lib.smvs_sgm_profile(0, ms, cnt)
+    names = ["census", "warp", "cost", "paths", "wta", "lr_check", "merge"]
+    for i, name in enumerate(names):
+        if cnt[i]:
+            print("kernel %-8s %9.1f us per launch, %9.1f us per view (%d launches per view)"
+                  % (name, 1e3 * ms[i] / cnt[i], 1e3 * ms[i] / repeat, cnt[i] // repeat))
+    npix = hw * hh
+    if consensus:
+        # n forward maps read, n scattered lookups, the merged map written
+        nbytes = 4 * npix * (2 * n + 1)
+        us = 1e3 * ms[6] / max(cnt[6], 1)
+        print("check + merge (one kernel): %.1f us per view, %.1f MB, %.2f TB/s"
+              % (1e3 * ms[6] / repeat, nbytes / 1e6, nbytes / us / 1e6))
+    else:
+        # per check a map read and written back where rejected, a lookup; the
+        # merge reads two maps and writes one
+        print("check + merge (%d launches): %.1f us per view"
+              % ((cnt[5] + cnt[6]) // repeat, 1e3 * (ms[5] + ms[6]) / repeat))
+    sys.exit(0)
 
 
 def run():
