@@ -20,7 +20,7 @@
 // blocks read bank (k-1)&1.  The host never synchronises inside a solve: it
 // paces its launches on progress words the kernels publish in pinned host
 // memory (cg_solve_launch).
-#include "common.h"
+#include "newton_step.h"
 #include "dpp.h"
 
 #include <chrono>

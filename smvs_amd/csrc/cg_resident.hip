@@ -39,7 +39,7 @@
 // Every spin is bounded: if the workgroups are not all resident (another
 // barrier kernel holds CUs, fewer CUs than tiles) the barrier times out, the
 // solve reports failure and the caller falls back to the streaming kernels.
-#include "common.h"
+#include "newton_step.h"
 #include "cg_resident_plan.h"
 #include "cg_exchange.h"
 
@@ -52,7 +52,7 @@ namespace smvs_hip {
 
 typedef double double4_r __attribute__((ext_vector_type(4)));
 
-constexpr int RES_PIPELINED = 1;      // launch-ahead Newton loop (update.hip)
+constexpr int RES_PIPELINED = 1;      // launch-ahead Newton loop (newton_loop.hip)
 constexpr int RES_TEST_GIVE_UP = 2;   // report a failure (test hook)
 
 struct ResArgs {

@@ -67,7 +67,7 @@ enum {
     I_LIVE_PATCHES,  // entries of the compacted live-patch list
     I_NUM_INITIAL,   // active nodes at the start of the Newton loop (finish_step_kernel, begin)
     I_STOP,          // pipelined Newton loop: the loop has ended, enqueued steps do nothing
-    I_STEP_ABORT,    // pipelined Newton loop: this step was abandoned (ABORT_*); it and
+    I_STEP_ABORT,    // pipelined Newton loop: this step was abandoned (ABORT_*, newton_step.h); it and
                      // the steps enqueued behind it change nothing
     I_SURF_VALID,    // valid patches of the device surface (surface.hip)
     I_SURF_CHANGED,  // patches filled / deleted by the last grid operation
@@ -109,21 +109,6 @@ progress_done_word(int solve_tag)
     return solve_tag | 1;
 }
 
-// Result words of a Newton step in its pinned slot (ctx->step_words,
-// STEP_SLOT_INTS ints), published by finish_step_kernel (update.hip).
-enum {
-    STEP_SEQ = 0,          // the sequence tag, stored last
-    STEP_NUM_ACTIVE,       // active nodes
-    STEP_NAN,              // delta[0] was NaN: nothing was updated
-    STEP_ACTIVE_PATCHES,   // active patches of the step
-    STEP_NEXT_LIVE,        // length of the next live-patch list
-    STEP_GATE,             // 0 ran / 1 skipped (the loop had ended) / 1 + ABORT_*
-                           // (the step was abandoned)
-    STEP_CG_ITERS,         // CG iterations
-    STEP_LOOP_ENDS,        // the loop ends after this step
-    STEP_SCALARS           // two doubles: sum of shifts, number of terms
-};
-
 struct SubPlanes {
     int width = 0, height = 0;
     float2 *grad = nullptr;   // [h][w]  (I_x, I_y)
@@ -135,7 +120,7 @@ struct DeviceCameras {
     double t[SMVS_MAX_SUBS][3];
     // p t2 - r t0 and q t2 - r t1 as affine functions of the pixel (u, v, 1),
     // with (p, q, r) = M (u, v, 1): the numerators of the reprojection shift
-    // (update.hip, reactivate_kernel)
+    // (reactivate.hip, reactivate_kernel)
     double shift[SMVS_MAX_SUBS][6];
 };
 
@@ -205,7 +190,7 @@ struct smvs_ctx {
     int *status_host = nullptr;     // pinned
     int *cg_progress = nullptr;     // pinned, written by the CG kernels (cg.hip)
     int *step_words = nullptr;      // pinned ring of STEP_SLOTS result slots, written by
-                                    // finish_step_kernel (update.hip)
+                                    // finish_step_kernel (newton_step.h)
     unsigned long long *step_counter = nullptr;   // device, its packed counters
     double *zero_block = nullptr;   // 16 doubles of +0.0 (cg_resident.hip)
     int last_loop_steps = 1 << 30;  // Newton steps of the previous smvs_gn_run_loop (launch-ahead heuristic)
@@ -255,7 +240,7 @@ struct smvs_ctx {
     int solver_mode = 0;            // smvs_solver_mode (smvs_ctx_set_solver)
     float *map_scratch = nullptr;   // depth / normal map output, W*H*3 (or *4) floats
     size_t map_scratch_floats = 0;
-    double *light_partial = nullptr;  // per-block lighting sums (update.hip)
+    double *light_partial = nullptr;  // per-block lighting sums (surface_maps.hip)
 
     // scale space on the device (scale.hip): float images of the views
     struct ViewImage { int w = 0, h = 0, c = 0; float *data = nullptr; };
@@ -552,55 +537,5 @@ ldl_inverse4(double A[16])
             for (int c2 = 0; c2 < 4; ++c2)
                 A[c1 * 4 + c2] += L[r * 4 + c2] * L[r * 4 + c1] * D[r];
 }
-
-// reasons in status[I_STEP_ABORT]; finish_step_kernel reports 1 + reason
-constexpr int ABORT_SOLVER = 1;   // the resident solver gave up (workgroups not co-resident)
-constexpr int ABORT_GRID = 2;     // a launch was sized for a shorter live list
-constexpr int STEP_SLOTS = 4;        // steps whose result words can coexist
-constexpr int STEP_SLOT_INTS = 16;   // one 64-byte line per slot
-
-// Launch-ahead mode of the Newton loop: the launches of a step are sized and
-// enqueued before the previous step's result is known; the kernels read the
-// list length and the loop's stop word on the device.
-struct StepPipeline {
-    int seq;             // sequence tag finish_step_kernel publishes (never 0)
-    int grid_live;       // list length the launches are sized for
-    double full_opt_threshold;
-};
-
-// internal entry points used by the fused loop
-// known_live: entries of the live-patch list the previous reactivate_launch
-// of the same Newton loop built (its count read back by the host), or -1 to
-// build the list here.
-// skip_assembly: leave the per-patch systems unassembled (the resident solver
-// gathers them itself, cg_resident_solve(..., fused = true)).
-int gn_construct_launch(smvs_ctx *ctx, double reg, double light_reg,
-    bool use_lighting, int known_live = -1, bool skip_assembly = false,
-    bool check_stop = false);
-int gn_assemble_launch(smvs_ctx *ctx);
-int live_patch_list_launch(smvs_ctx *ctx);
-int cg_solve_launch(smvs_ctx *ctx, int max_iterations, double error_tolerance,
-    double q_tolerance, int *num_iterations, int *info);
-// known_live >= 0: walk the live list (its length as read back by the host);
-// publish_seq != 0: the Newton loop's fused end of step (finish_step_kernel
-// publishes the result words tagged with this sequence number).
-int reactivate_launch(smvs_ctx *ctx, double threshold, int full_optimization,
-    bool build_live_list = false, int known_live = -1, int publish_seq = 0,
-    const StepPipeline *pipe = nullptr);
-// fused: assemble H, g, P from the per-patch systems inside the kernel (the
-// caller has NOT run the assembly kernel); *ran = false means nothing was done.
-int cg_resident_solve(smvs_ctx *ctx, int max_iterations, double error_tolerance,
-    double q_tolerance, int *num_iterations, int *info, bool *ran,
-    bool fused = false);
-bool cg_resident_applies(smvs_ctx *ctx, int max_iterations);
-// the tile budget (tile_budget.h) of the GPU behind a logical device
-DeviceTileBudget &cg_resident_budget(int device);
-// workgroups (= tiles = CUs) the resident solver launches for this context's
-// grid; 0 when it does not apply
-int cg_resident_tiles(smvs_ctx *ctx);
-int cg_resident_enqueue(smvs_ctx *ctx, int max_iterations, double q_tolerance,
-    bool test_give_up = false);
-int cg_resident_gave_up(smvs_ctx *ctx);   // a resident solve failed: what runs from now on
-
 
 } // namespace smvs_hip

@@ -1,5 +1,5 @@
 // Context management, plane / surface uploads, profiling.
-#include "common.h"
+#include "newton_step.h"
 
 #include <cstdlib>
 

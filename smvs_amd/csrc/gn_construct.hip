@@ -22,7 +22,7 @@
 // independent 4 x 4 node blocks each) cover the ten node blocks (bi <= bj) of
 // the symmetric 16 x 16 patch system; a 16x16x4 would compute all sixteen.
 // One wavefront owns 64 sampled pixels = 4 patches at the fine scales.
-#include "common.h"
+#include "newton_step.h"
 
 namespace smvs_hip {
 
@@ -734,7 +734,7 @@ gn_patch_kernel(PatchKernelArgs A)
 
     int const lane = WAVES == 1 ? (int)threadIdx.x : (int)(threadIdx.x & 63);
     // a pipelined Newton loop enqueues steps before it knows whether the loop
-    // goes on (update.hip): once it has ended they do nothing
+    // goes on (newton_loop.hip): once it has ended they do nothing
     if (A.check_stop && (A.status[I_STOP] | A.status[I_STEP_ABORT]) != 0)
         return;
     // Work = the compacted list of live patches (a patch with an active node,

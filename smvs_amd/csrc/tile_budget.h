@@ -1,6 +1,6 @@
 // Barrier kernels (the resident PCG: every workgroup of a launch must be
 // co-resident, one per CU) share a device by a TILE BUDGET: a Newton loop
-// (update.hip holds its share for the whole loop, patch kernels included) or a
+// (newton_loop.hip holds its share for the whole loop, patch kernels included) or a
 // single solve acquires as many tiles as its grid has workgroups and waits
 // while the tiles in use plus its own exceed the device's CUs.  A full-size
 // solve (256 tiles at 1920x1080, scale 2) therefore still runs alone, but the

@@ -191,6 +191,44 @@ def test_maps_in_one_pass_pinned_buffers_and_mve_convention(hip, oracle):
     ctx.close()
 
 
+def test_map_scratch_is_shared_in_any_call_order(hip, oracle):
+    """The map getters and smvs_light_accumulate write through one scratch
+    buffer of the context, W*H*3 floats or W*H*4 (smvs_get_maps).  The same five
+    calls on two identical contexts, forward (the scratch starts at W*H*3 and
+    grows) and backward (it starts at W*H*4): every map and both lighting
+    systems bit for bit -- light_accumulate_kernel's per-block sums are added
+    in a fixed order by light_finalize_kernel."""
+    w, h = 256, 192
+    prob, ctx_a, _ = _setup(hip, oracle, w, h, 2, 2, shading=True)
+    ctx_b = hip.ViewContext(w, h, 2)
+    ctx_b.set_views(prob["views"])
+    ctx_b.set_surface(prob["surf"])
+    inv = _inverse_calibration(prob["main"].flen, w, h)
+    calls = [lambda c: ("depth", c.depth_map()),
+             lambda c: ("maps", c.maps(inv)),
+             lambda c: ("normals", c.normal_map()),
+             lambda c: ("light", c.light_accumulate()),
+             lambda c: ("maps", c.maps(inv))]
+    got = {"depth": [], "maps": [], "normals": [], "light": []}
+    for ctx, order in ((ctx_a, calls), (ctx_b, calls[::-1])):
+        for call in order:
+            kind, out = call(ctx)
+            got[kind].append(out)
+        ctx.close()
+    assert [len(v) for v in got.values()] == [2, 4, 2, 2]
+    d0, n0 = got["depth"][0], got["normals"][0]
+    assert np.count_nonzero(d0) > 0.5 * d0.size and np.count_nonzero(n0) > 0.5 * n0.size
+    assert np.array_equal(got["depth"][1], d0)
+    for n in [got["normals"][1]] + [m[1] for m in got["maps"]]:
+        assert np.array_equal(n, n0)
+    for m in got["maps"][1:]:
+        assert np.array_equal(m[0], got["maps"][0][0])
+    assert not np.array_equal(got["maps"][0][0], d0)     # MVE's convention
+    (A0, b0), (A1, b1) = got["light"]
+    assert np.array_equal(A0, A1) and np.array_equal(b0, b1)
+    assert np.all(np.diag(A0) > 0)
+
+
 def test_light_fit_matches_oracle(hip, oracle):
     """LightOptimizer accumulation (light_optimizer.cc:32-49)."""
     prob, ctx, orc = _setup(hip, oracle, 256, 192, 2, 2, shading=True)

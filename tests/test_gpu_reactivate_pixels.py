@@ -1,5 +1,5 @@
 """Re-activation with several pixels per thread (reactivate_kernel<FULL, K>,
-csrc/update.hip) against the CPU oracle, through the C ABI
+csrc/reactivate.hip) against the CPU oracle, through the C ABI
 (smvs_update_and_reactivate, smvs_get_active), on the smallest surfaces at which
 the mapping of threads to pixels can go wrong:
 
@@ -398,7 +398,7 @@ def test_every_pixels_per_thread_gives_the_same_active_set(forced, cases, scale,
 @pytest.mark.parametrize("scale", LOOP_SCALES)
 def test_every_pixels_per_thread_runs_the_same_newton_loop(forced, loop_cases, scale, solver,
                                                            full):
-    """The live-list path of reactivate_launch under every value of the switch:
+    """The live-list path (step_end_launch) under every value of the switch:
     the same loop bit for bit, and the oracle's."""
     ref = loop_cases[scale]["ref"][full]
     tag = "loop_%d_%s_%d_" % (scale, solver, full)
