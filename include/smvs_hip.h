@@ -551,6 +551,80 @@ int smvs_sgm_check_merge(int device, const float *fwd, int w, int h,
     const smvs_sgm_check_neighbor *neighbors, int n_neighbors,
     const smvs_sgm_view_options *opts, float *merged, float *checked, uint8_t *support);
 
+/* Multi-neighbour plane sweep.  Not in the reference, and not a value of
+ * smvs_sgm_merge: instead of 2 n runs and a merge of n depth maps, ONE cost
+ * volume of the main view from all n neighbours, aggregated once, one winner.
+ * All n forward runs of a view share its pixel grid, its census and its depth
+ * planes (the main view's depth range does not depend on the neighbour,
+ * sgm_stereo.cc:50-57), so per view the work is n x (warp + cost), one fold,
+ * one path aggregation, one WTA.  Integers only.
+ *
+ * Definition.  c[k][p][d] is the cost byte of neighbour k, k = 0 .. n-1 in
+ * neighbour order, at pixel p and plane d: the byte create_cost_volume
+ * (sgm_stereo.cc:192-244) gives for the pair (main, neighbour k) over the main
+ * view's planes.  A byte of 255 is no cost; any other byte is a cost.
+ * Fold, per (p, d), in int:
+ *     m = number of k with c[k] != 255
+ *     if m < min_views:            C = 255
+ *     else: k_eff = (best_k == 0) ? m : min(best_k, m)
+ *           S = sum of the k_eff smallest c[k] != 255   (a multiset: ties need no order)
+ *           C = (2 * S + k_eff) / (2 * k_eff)           (integer division: mean, half up)
+ * Two consequences hold to the byte: n = 1 with min_views = 1 gives c[0], and
+ * j copies of one neighbour give that neighbour's volume for any best_k.  The
+ * intermediates fit 16 bits (2 * 254 * 16 + 16 < 65536).
+ * Run.  aggregate_sgm_costs and depth_from_sgm_volume run on C exactly as on the
+ * volume of a pair, for either p2_mode and either winner; the rule of
+ * sgm_stereo.cc:300-303 (no depth for a winner index below 2 or a main-image
+ * byte below 25), the depth table and the bound on the penalties are unchanged.
+ * There is no neighbour-side run and no left/right check.
+ * Support, per pixel with winner plane i:
+ *     support = number of k with c[k][p][i] <= support_cost      (u8)
+ * If min_support > 0 and support < min_support, depth is 0; argmin stays i.
+ * Accepted: n in 1 .. SMVS_MAX_SUBS, min_views in 1 .. n, best_k in
+ * 0 .. SMVS_MAX_SUBS, support_cost in 0 .. 254, min_support in 0 .. n,
+ * 0 < min_depth < max_depth, the plane counts and penalties of
+ * smvs_sgm_run_opts; anything else (a NULL options pointer, an unknown p2_mode
+ * or winner) is SMVS_ERR_INVALID before any device call.
+ * min_views = min(2, n), best_k = (n + 1) / 2, support_cost = 20 and
+ * min_support = min(2, n) are what the host mirror and the Python layer default
+ * to: defaults of a user option, untuned; nobody has measured them on real
+ * scenes.
+ * Memory: the n volumes of w * h * num_steps bytes are all held until the
+ * support kernel has run (a slot of the pooled workspace, next to the volumes
+ * of one run): 66 MB each at 960 x 540 x 128, and 2.1 GB for n = 16 at
+ * 960 x 540 x 256. */
+typedef struct {
+    int p2_mode;        /* smvs_sgm_p2_mode */
+    int winner;         /* smvs_sgm_winner */
+    int min_views;
+    int best_k;
+    int support_cost;
+    int min_support;
+} smvs_sgm_sweep_options;
+
+/* The sweep for one view, images at SGM scale (u8, one channel).  Of
+ * neighbors[k] only image, width, height, M_fwd and t_fwd are read; range[2] =
+ * { min_depth, max_depth } of the main view.  A neighbour image may be as small
+ * as 2 x 2 (it is never a main view).  Outputs, any may be NULL: depth[w * h],
+ * argmin[w * h], support[w * h], cost[w * h * num_steps] (u16: the folded
+ * volume C), sgm[w * h * num_steps] (u16, as smvs_sgm_run gives it). */
+int smvs_sgm_sweep_for_view(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, const float *range, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_sweep_options *opts, float *depth,
+    int32_t *argmin, uint8_t *support, uint16_t *cost, uint16_t *sgm);
+/* The same on the views' full-resolution u8 embeddings, desaturated and halved
+ * on the device as in smvs_sgm_depth_for_view_raw (sizes, reprojections and
+ * outputs as there).  Outputs, either may be NULL: depth, support. */
+int smvs_sgm_sweep_for_view_raw(int device, const uint8_t *main_img, int w, int h, int channels,
+    const smvs_sgm_neighbor *neighbors, const int *neighbor_channels, int n_neighbors,
+    int halvings, const float *range, int num_steps, uint16_t penalty1, uint16_t penalty2,
+    const smvs_sgm_sweep_options *opts, float *depth, uint8_t *support);
+/* The fold kernel alone, on bytes of the caller (as smvs_sgm_check_merge exposes
+ * the consensus kernel): costs[n_neighbors * len], neighbour-major, out[len];
+ * len in 1 .. 2^32.  min_views and best_k as above. */
+int smvs_sgm_fold_costs(int device, const uint8_t *costs, int n_neighbors, size_t len,
+    int min_views, int best_k, uint8_t *out);
+
 /* DepthOptimizer::depthmap_bilateral_filter, depth_optimizer.cc:957-1004 */
 int smvs_bilateral_upsample(int device, const float *dm, int dm_w, int dm_h,
     const float *ci, int w, int h, int channels, float sigma,
@@ -895,9 +969,11 @@ enum {
     SMVS_SGM_K_COST,         /* census of the warped planes + Hamming cost (K11, K13) */
     SMVS_SGM_K_PATHS,        /* 8-path aggregation (K14) */
     SMVS_SGM_K_WTA,          /* argmin + depth (K15) */
-    SMVS_SGM_K_LR_CHECK,     /* left / right consistency (K16) */
+    SMVS_SGM_K_LR_CHECK,     /* left / right consistency (K16); in the plane sweep the one
+                              * support kernel (it has no left / right check) */
     SMVS_SGM_K_MERGE,        /* two-neighbour merge (K16); with SMVS_SGM_MERGE_CONSENSUS the one
-                              * check-and-merge kernel (then no SMVS_SGM_K_LR_CHECK launches) */
+                              * check-and-merge kernel (then no SMVS_SGM_K_LR_CHECK launches);
+                              * in the plane sweep the one fold of the n cost volumes */
     SMVS_SGM_K_BILATERAL,    /* joint bilateral upsample (K17) */
     SMVS_SGM_K_COUNT
 };

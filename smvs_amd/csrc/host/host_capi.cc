@@ -340,11 +340,50 @@ smvs_host_sgm_depth_merge(const smvs_host_view *main_in, const smvs_host_view *s
     int num_steps, int subplane, int num_neighbors, int consensus, float agree_ratio,
     int min_agree, float *depth_out, int *out_w, int *out_h)
 {
+    return smvs_host_sgm_depth_sweep(main_in, subs_in, n_subs, bundle_in, sgm_scale,
+        min_depth, max_depth, device, adaptive_penalty2, num_steps, subplane, num_neighbors,
+        consensus, agree_ratio, min_agree, nullptr, depth_out, out_w, out_h);
+}
+
+extern "C" int
+smvs_host_sgm_sweep_defaults(int *ints10)
+{
+    if (ints10 == nullptr) {
+        g_host_error = "smvs_host_sgm_sweep_defaults: bad argument";
+        return -1;
+    }
+    SGMStereo::Options const opts;
+    ReconSettings const conf;
+    ints10[0] = opts.sweep ? 1 : 0;
+    ints10[1] = opts.sweep_min_views;
+    ints10[2] = opts.sweep_best_k;
+    ints10[3] = opts.sweep_support_cost;
+    ints10[4] = opts.sweep_min_support;
+    ints10[5] = conf.sgm_sweep ? 1 : 0;
+    ints10[6] = conf.sgm_sweep_min_views;
+    ints10[7] = conf.sgm_sweep_best_k;
+    ints10[8] = conf.sgm_sweep_support_cost;
+    ints10[9] = conf.sgm_sweep_min_support;
+    return 0;
+}
+
+extern "C" int
+smvs_host_sgm_depth_sweep(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, int sgm_scale,
+    float min_depth, float max_depth, int device, int adaptive_penalty2,
+    int num_steps, int subplane, int num_neighbors, int consensus, float agree_ratio,
+    int min_agree, const smvs_host_sgm_sweep *sweep, float *depth_out, int *out_w,
+    int *out_h)
+{
     try {
         // (before the views are copied: an argument error needs no image)
-        if (consensus == 0 && num_neighbors > 2)
+        bool const sweep_on = sweep != nullptr && sweep->sweep != 0;
+        if (sweep_on && consensus != 0)
+            throw std::invalid_argument("smvs_host_sgm_depth_sweep: sweep and consensus "
+                "exclude each other");
+        if (consensus == 0 && !sweep_on && num_neighbors > 2)
             throw std::invalid_argument("smvs_host_sgm_depth_merge: more than two "
-                "neighbours need the consensus merge");
+                "neighbours need the consensus merge or the sweep");
         if (!SGMStereo::Options::valid_num_steps(num_steps))
             throw std::invalid_argument("smvs_host_sgm_depth_steps: num_steps must be "
                 "in [2, 128] or a multiple of 8 in [136, 256]");
@@ -365,6 +404,13 @@ smvs_host_sgm_depth_merge(const smvs_host_view *main_in, const smvs_host_view *s
         opts.consensus = consensus != 0;
         opts.agree_ratio = agree_ratio;
         opts.min_agree = min_agree;
+        if (sweep_on) {
+            opts.sweep = true;
+            opts.sweep_min_views = sweep->min_views;
+            opts.sweep_best_k = sweep->best_k;
+            opts.sweep_support_cost = sweep->support_cost;
+            opts.sweep_min_support = sweep->min_support;
+        }
         FloatImage::Ptr d = reconstruct_sgm_depth_for_view(opts, main_view, subs,
             bundle);
         if (out_w != nullptr)
@@ -989,11 +1035,37 @@ smvs_host_reconstruct_scene_merge(const char *scene_dir,
     int max_reconstructed, int *n_reconstructed, int *n_skipped, double *seconds,
     int *input_scale_used)
 {
+    return smvs_host_reconstruct_scene_sweep(scene_dir, o, flags, sgm_num_steps,
+        sgm_subplane, sgm_neighbors, sgm_consensus, sgm_agree_ratio, sgm_min_agree, nullptr,
+        view_ids, n_view_ids, reconstructed_out, max_reconstructed, n_reconstructed,
+        n_skipped, seconds, input_scale_used);
+}
+
+extern "C" int
+smvs_host_reconstruct_scene_sweep(const char *scene_dir,
+    const smvs_host_recon_settings *o, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const int *view_ids,
+    int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
+    int *n_skipped, double *seconds, int *input_scale_used)
+{
     try {
+        bool const sweep_on = sweep != nullptr && sweep->sweep != 0;
+        if (sweep_on && sgm_consensus != 0)
+            throw std::invalid_argument("smvs_host_reconstruct_scene_sweep: sgm_sweep and "
+                "sgm_consensus exclude each other");
         if (sgm_neighbors < 1 || sgm_neighbors > SMVS_MAX_SUBS
-            || (sgm_consensus == 0 && sgm_neighbors > 2))
+            || (sgm_consensus == 0 && !sweep_on && sgm_neighbors > 2))
             throw std::invalid_argument("smvs_host_reconstruct_scene_merge: sgm_neighbors "
-                "must be 1 or 2, or up to 16 with sgm_consensus");
+                "must be 1 or 2, or up to 16 with sgm_consensus or sgm_sweep");
+        if (sweep_on && (sweep->min_views < -1 || sweep->min_views == 0
+                || sweep->min_views > SMVS_MAX_SUBS || sweep->best_k < -1
+                || sweep->best_k > SMVS_MAX_SUBS || sweep->support_cost < 0
+                || sweep->support_cost > 254 || sweep->min_support < -1
+                || sweep->min_support > SMVS_MAX_SUBS))
+            throw std::invalid_argument("smvs_host_reconstruct_scene_sweep: sgm_sweep_min_views "
+                "must be -1 or in [1, 16], sgm_sweep_best_k and sgm_sweep_min_support -1 or in "
+                "[0, 16], sgm_sweep_support_cost in [0, 254]");
         if (sgm_consensus != 0 && (!(sgm_agree_ratio >= 0.0f && sgm_agree_ratio <= 1.0f)
                 || sgm_min_agree < 1 || sgm_min_agree > SMVS_MAX_SUBS))
             throw std::invalid_argument("smvs_host_reconstruct_scene_merge: sgm_agree_ratio "
@@ -1027,6 +1099,13 @@ smvs_host_reconstruct_scene_merge(const char *scene_dir,
         conf.sgm_consensus = sgm_consensus != 0;
         conf.sgm_agree_ratio = sgm_agree_ratio;
         conf.sgm_min_agree = sgm_min_agree;
+        if (sweep_on) {
+            conf.sgm_sweep = true;
+            conf.sgm_sweep_min_views = sweep->min_views;
+            conf.sgm_sweep_best_k = sweep->best_k;
+            conf.sgm_sweep_support_cost = sweep->support_cost;
+            conf.sgm_sweep_min_support = sweep->min_support;
+        }
         conf.device_input_scaling = (flags & SMVS_HOST_SCENE_DEVICE_INPUT_SCALING) != 0u;
         conf.device_shading_prep = (flags & SMVS_HOST_SCENE_DEVICE_SHADING_PREP) != 0u;
         conf.gamma_correction = (flags & SMVS_HOST_SCENE_GAMMA_SRGB) != 0u;

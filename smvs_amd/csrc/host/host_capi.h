@@ -162,6 +162,29 @@ int smvs_host_sgm_depth_merge(const smvs_host_view *main_view,
  * sgm_neighbors, sgm_consensus, sgm_min_agree in ints4[4 .. 7]; ratios2 =
  * { Options::agree_ratio, ReconSettings::sgm_agree_ratio }. */
 int smvs_host_sgm_merge_defaults(int *ints8, float *ratios2);
+/* SGMStereo::Options::sweep / sweep_min_views / sweep_best_k /
+ * sweep_support_cost / sweep_min_support (the multi-neighbour plane sweep of
+ * include/smvs_hip.h; not in the reference); -1 in min_views, best_k and
+ * min_support: the default at n neighbours (min(2, n), (n + 1) / 2, min(2, n)). */
+typedef struct {
+    int sweep;
+    int min_views, best_k, support_cost, min_support;
+} smvs_host_sgm_sweep;
+/* smvs_host_sgm_depth_merge with the plane sweep selectable: with sweep->sweep
+ * != 0 the map of the sweep over the first min(n_subs, num_neighbors)
+ * neighbours (any count up to SMVS_MAX_SUBS).  sweep together with consensus is
+ * an argument error.  sweep == NULL: off; smvs_host_sgm_depth_merge forwards to
+ * this with NULL. */
+int smvs_host_sgm_depth_sweep(const smvs_host_view *main_view,
+    const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
+    int sgm_scale, float min_depth, float max_depth, int device,
+    int adaptive_penalty2, int num_steps, int subplane, int num_neighbors,
+    int consensus, float agree_ratio, int min_agree, const smvs_host_sgm_sweep *sweep,
+    float *depth_out, int *out_w, int *out_h);
+/* The sweep options as a default-constructed SGMStereo::Options (ints10[0 .. 4])
+ * and ReconSettings (ints10[5 .. 9]) hold them, in the order of
+ * smvs_host_sgm_sweep (no device involved). */
+int smvs_host_sgm_sweep_defaults(int *ints10);
 /* The switches of the SGM front end that the reference does not have, as a
  * default-constructed SGMStereo::Options and ReconSettings hold them (no
  * device involved): out4 = { Options::adaptive_penalty2, Options::subplane,
@@ -307,6 +330,17 @@ int smvs_host_reconstruct_scene_merge(const char *scene_dir,
     int sgm_min_agree, const int *view_ids, int n_view_ids, int *reconstructed_out,
     int max_reconstructed, int *n_reconstructed, int *n_skipped, double *seconds,
     int *input_scale_used);
+/* The same with ReconSettings::sgm_sweep and its four values: every view's
+ * smvs-sgm map by the plane sweep over its first sgm_neighbors neighbours.
+ * sweep together with sgm_consensus is an argument error; sweep == NULL: off
+ * (smvs_host_reconstruct_scene_merge forwards to this with NULL).  The reuse
+ * rule is that of sgm_subplane (force_sgm). */
+int smvs_host_reconstruct_scene_sweep(const char *scene_dir,
+    const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const int *view_ids,
+    int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
+    int *n_skipped, double *seconds, int *input_scale_used);
 
 /* smvsrecon's generate_mesh (app/smvsrecon.cc:278-343, MeshGenerator::
  * generate_mesh, lib/mesh_generator.cc:160-299) on a reconstructed scene: the

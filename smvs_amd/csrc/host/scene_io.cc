@@ -588,6 +588,11 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                         sgm_opts.consensus = conf.sgm_consensus;
                         sgm_opts.agree_ratio = conf.sgm_agree_ratio;
                         sgm_opts.min_agree = conf.sgm_min_agree;
+                        sgm_opts.sweep = conf.sgm_sweep;
+                        sgm_opts.sweep_min_views = conf.sgm_sweep_min_views;
+                        sgm_opts.sweep_best_k = conf.sgm_sweep_best_k;
+                        sgm_opts.sweep_support_cost = conf.sgm_sweep_support_cost;
+                        sgm_opts.sweep_min_support = conf.sgm_sweep_min_support;
                         (void)reconstruct_sgm_depth_for_view(sgm_opts, main_view,
                             stereo_views, bundle);
                         save_mvei(view.image_path("smvs-sgm"),

@@ -118,6 +118,16 @@ struct ReconSettings
     bool sgm_consensus = false;
     float sgm_agree_ratio = 0.95f;
     int sgm_min_agree = 2;
+    // SGMStereo::Options::sweep / sweep_min_views / sweep_best_k /
+    // sweep_support_cost / sweep_min_support -- the smvs-sgm map of a view by the
+    // plane sweep over its first sgm_neighbors neighbours (not together with
+    // sgm_consensus); -1: the default at n neighbours.  Untuned defaults of a
+    // user option; the reuse rule is that of sgm_subplane (force_sgm).
+    bool sgm_sweep = false;
+    int sgm_sweep_min_views = -1;
+    int sgm_sweep_best_k = -1;
+    int sgm_sweep_support_cost = 20;
+    int sgm_sweep_min_support = -1;
     // not in the reference's AppSettings: the input scaling of :621-650 on the
     // device (rescale_half_size_gaussian_device), one ViewQueue task per view
     bool device_input_scaling = false;

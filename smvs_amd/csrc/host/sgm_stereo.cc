@@ -158,6 +158,24 @@ run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
     int w = main_bytes->width(), h = main_bytes->height();
     sgm_scale_size(o.scale, &w, &h);
     FloatImage::Ptr depth = FloatImage::create_for_overwrite(w, h, 1);
+    if (o.sweep) {
+        // n x (warp + cost) over the main view's planes, one fold, one
+        // aggregation, one winner, the support test
+        int const n = (int)dev.size();
+        smvs_sgm_options const base = device_options(o);
+        smvs_sgm_sweep_options const sweep_opts = { base.p2_mode, base.winner,
+            o.sweep_min_views < 0 ? std::min(2, n) : o.sweep_min_views,
+            o.sweep_best_k < 0 ? (n + 1) / 2 : o.sweep_best_k, o.sweep_support_cost,
+            o.sweep_min_support < 0 ? std::min(2, n) : o.sweep_min_support };
+        int const rc = smvs_sgm_sweep_for_view_raw(o.device, main_bytes->begin(),
+            main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
+            channels.data(), n, o.scale, dev[0].range_main, o.num_steps, o.penalty1,
+            o.penalty2, &sweep_opts, depth->begin(), nullptr);
+        if (rc != SMVS_OK)
+            throw std::runtime_error(std::string("smvs_sgm_sweep_for_view_raw: ")
+                + smvs_last_error());
+        return depth;
+    }
     if (o.consensus) {
         // the same over n neighbours: 2 n x run_sgm, then the n checks and the
         // consensus in one kernel
@@ -205,16 +223,19 @@ reconstruct_sgm_depth_for_view(SGMStereo::Options opts,
 {
     // app/smvsrecon.cc:346-384: SGMStereo::reconstruct against the first two
     // neighbours and the merge of the two checked maps, in one device call;
-    // with opts.consensus against the first opts.num_neighbors
+    // with opts.consensus or opts.sweep against the first opts.num_neighbors
     if (neighbors.empty())
         throw std::invalid_argument("reconstruct_sgm_depth_for_view: no neighbour");
     if (opts.num_neighbors < 1 || opts.num_neighbors > SMVS_MAX_SUBS)
         throw std::invalid_argument("reconstruct_sgm_depth_for_view: num_neighbors "
             "must be in [1, " + std::to_string(SMVS_MAX_SUBS) + "]");
-    if (!opts.consensus && opts.num_neighbors > 2)
+    if (opts.sweep && opts.consensus)
+        throw std::invalid_argument("reconstruct_sgm_depth_for_view: Options::sweep and "
+            "Options::consensus exclude each other");
+    if (!opts.consensus && !opts.sweep && opts.num_neighbors > 2)
         throw std::invalid_argument("reconstruct_sgm_depth_for_view: the reference's "
             "merge takes one or two neighbours (app/smvsrecon.cc:360-365); more need "
-            "Options::consensus");
+            "Options::consensus or Options::sweep");
     std::vector<PairInputs> pairs(std::min<std::size_t>(neighbors.size(),
         (std::size_t)opts.num_neighbors));
     for (std::size_t k = 0; k < pairs.size(); ++k)

@@ -1,6 +1,7 @@
 // Host mirror of smvs::SGMStereo (reference: lib/sgm_stereo.h:21-88).  The
 // cost volumes, the 8-path aggregation, the WTA, the left/right check and the
-// merge run on the device (smvs_sgm_depth_for_view_raw_opts / _raw_merge); the host
+// merge run on the device (smvs_sgm_depth_for_view_raw_opts / _raw_merge, or
+// smvs_sgm_sweep_for_view_raw); the host
 // keeps the depth range from the bundle and the image half-sizing.
 #pragma once
 
@@ -50,6 +51,23 @@ public:
         bool consensus = false;
         float agree_ratio = 0.95f;
         int min_agree = 2;
+        // not in the reference either: the multi-neighbour plane sweep of
+        // include/smvs_hip.h (smvs_sgm_sweep_for_view_raw) over the first
+        // min(neighbors.size(), num_neighbors) neighbours instead of the runs,
+        // the checks and the merge: one cost volume of the main view from all
+        // of them (per cell the rounded mean of the sweep_best_k smallest cost
+        // bytes, none with fewer than sweep_min_views), one aggregation, one
+        // winner, no depth where fewer than sweep_min_support neighbours have
+        // a cost of at most sweep_support_cost at the winner plane.  Not
+        // together with `consensus`.  -1 stands for the default at n
+        // neighbours: min_views = min(2, n), best_k = (n + 1) / 2, min_support =
+        // min(2, n).  These and 20 are defaults of a user option, untuned:
+        // nobody has measured them on real scenes.
+        bool sweep = false;
+        int sweep_min_views = -1;
+        int sweep_best_k = -1;
+        int sweep_support_cost = 20;
+        int sweep_min_support = -1;
 
         // the plane counts smvs_sgm_run / smvs_sgm_depth_for_view accept
         static bool valid_num_steps(int n)
@@ -80,8 +98,9 @@ private:
 
 // app/smvsrecon.cc:346-384: SGM against the first two neighbours, averaged;
 // with Options::consensus against the first Options::num_neighbors, merged by
-// consensus.  More than two neighbours without `consensus` is
-// std::invalid_argument (never a silent truncation).
+// consensus; with Options::sweep the plane sweep over them.  More than two
+// neighbours with neither, and both together, are std::invalid_argument (never
+// a silent truncation).
 FloatImage::Ptr reconstruct_sgm_depth_for_view(SGMStereo::Options opts,
     StereoView::Ptr main_view, std::vector<StereoView::Ptr> const& neighbors,
     Bundle::ConstPtr bundle = nullptr);

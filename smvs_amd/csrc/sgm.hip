@@ -757,10 +757,8 @@ check_sgm_options(int num_steps, float min_depth, float max_depth,
 
 // (declared in sgm_internal.h)
 int
-sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
-    int w, int h, const uint8_t *d_nbr, int nw, int nh, const float *M,
-    const float *t, float min_depth, float max_depth, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *d_depth)
+sgm_run_plan(SgmWorkspace &B, int w, int h, float min_depth, float max_depth, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, SgmRun *R)
 {
     int rc = check_sgm_options(num_steps, min_depth, max_depth, penalty1,
         penalty2, p2_mode);
@@ -768,15 +766,13 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
         return rc;
     SMVS_REQUIRE(winner == SMVS_SGM_WINNER_PLANE || winner == SMVS_SGM_WINNER_SUBPLANE,
         "unknown winner");
-    bool const subplane = winner == SMVS_SGM_WINNER_SUBPLANE;
+    R->subplane = winner == SMVS_SGM_WINNER_SUBPLANE;
     SMVS_REQUIRE(B.runs < SgmWorkspace::MAX_RUNS, "too many runs on one workspace");
-    hipStream_t const stream = B.ws->stream;
     size_t const npix = (size_t)w * h;
-    size_t const vol = npix * num_steps;
     // (what decides the form of the volumes: the largest penalty2 of a step)
-    SgmPathPlan const plan = sgm_path_plan_here(num_steps,
+    R->plan = sgm_path_plan_here(num_steps,
         SgmWorkspace::largest_penalty2(penalty1, penalty2, p2_mode));
-    if ((rc = B.ensure(npix, num_steps, plan)) != SMVS_OK)
+    if ((rc = B.ensure(npix, num_steps, R->plan)) != SMVS_OK)
         return rc;
     // sgm_stereo.cc:195-203: inverse-depth planes by repeated float addition;
     // behind the depths the inverse depths themselves, which only the sub-plane
@@ -794,24 +790,35 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
         }
     }
     float *d_depths = B.depths + 2 * SGM_MAX_PLANES * B.runs;
-    float *d_inv = d_depths + SGM_MAX_PLANES;
+    R->d_depths = d_depths;
+    R->d_inv = d_depths + SGM_MAX_PLANES;
     B.runs += 1;
-    if ((rc = B.ws->upload(d_depths, depths,
-             sizeof(float) * (subplane ? SGM_MAX_PLANES + num_steps : num_steps))) != SMVS_OK)
-        return rc;
+    return B.ws->upload(d_depths, depths,
+        sizeof(float) * (R->subplane ? SGM_MAX_PLANES + num_steps : num_steps));
+}
 
-    {
-        SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_CENSUS);
-        hipLaunchKernelGGL(census_main_kernel, dim3((w + 255) / 256, h), dim3(256),
-            0, stream, d_main, w, h, B.census);
-    }
+// (declared in sgm_internal.h)
+void
+sgm_launch_census(SgmWorkspace &B, const uint8_t *d_main, int w, int h)
+{
+    SgmKernelTimer timer(B.prof, B.ws->stream, SMVS_SGM_K_CENSUS);
+    hipLaunchKernelGGL(census_main_kernel, dim3((w + 255) / 256, h), dim3(256),
+        0, B.ws->stream, d_main, w, h, B.census);
+}
+
+// (declared in sgm_internal.h)
+int
+sgm_launch_warp_cost(SgmWorkspace &B, SgmRun const &R, int w, int h, const uint8_t *d_nbr,
+    int nw, int nh, const float *M, const float *t, int num_steps, uint8_t *d_cost)
+{
+    hipStream_t const stream = B.ws->stream;
     WarpArgs W;
     W.neighbor = d_nbr;
     W.nw = nw;
     W.nh = nh;
     memcpy(W.M, M, sizeof(float) * 9);
     memcpy(W.t, t, sizeof(float) * 3);
-    W.depths = d_depths;
+    W.depths = R.d_depths;
     W.D = num_steps;
     W.w = w;
     W.h = h;
@@ -830,15 +837,28 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
         if ((num_steps & 3) == 0)
             hipLaunchKernelGGL(cost_packed_kernel,
                 dim3(((tiles + 7) / 8) * 8, (num_steps + CP_D - 1) / CP_D),
-                dim3(256), 0, stream, B.warped, B.census, w, h, num_steps, B.cost);
+                dim3(256), 0, stream, B.warped, B.census, w, h, num_steps, d_cost);
         else
             hipLaunchKernelGGL(cost_tiled_kernel,
                 dim3(tiles, (num_steps + CT_D - 1) / CT_D), dim3(256), 0, stream,
                 B.warped, B.census, w, h,
-                num_steps, B.cost);
+                num_steps, d_cost);
     }
     SMVS_HIP_CHECK(hipGetLastError());
+    return SMVS_OK;
+}
 
+// (declared in sgm_internal.h)
+int
+sgm_run_tail(SgmWorkspace &B, SgmRun const &R, const uint8_t *d_main, int w, int h,
+    int num_steps, uint16_t penalty1, uint16_t penalty2, int p2_mode, float *d_depth)
+{
+    hipStream_t const stream = B.ws->stream;
+    size_t const npix = (size_t)w * h;
+    size_t const vol = npix * num_steps;
+    SgmPathPlan const &plan = R.plan;
+    bool const subplane = R.subplane;
+    int rc;
     if ((rc = sgm_launch_paths(B, plan, d_main, w, h, num_steps, penalty1, penalty2,
             p2_mode)) != SMVS_OK)
         return rc;
@@ -846,7 +866,7 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
         SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_WTA);
         // (the sub-plane forms take the inverse depths where the others take the
         // depths; grids and every other argument are the same)
-        const float *const table = subplane ? d_inv : d_depths;
+        const float *const table = subplane ? R.d_inv : R.d_depths;
         if (plan.wta == SGM_WTA_SUM_WIDE)
             hipLaunchKernelGGL(subplane ? sgm_sum_wta_wide_subplane_kernel
                                         : sgm_sum_wta_wide_kernel,
@@ -866,6 +886,39 @@ sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
     }
     SMVS_HIP_CHECK(hipGetLastError());
     return SMVS_OK;
+}
+
+// (declared in sgm_internal.h)
+int
+sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
+    int w, int h, const uint8_t *d_nbr, int nw, int nh, const float *M,
+    const float *t, float min_depth, float max_depth, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *d_depth)
+{
+    SgmRun R;
+    int rc = sgm_run_plan(B, w, h, min_depth, max_depth, num_steps, penalty1, penalty2,
+        p2_mode, winner, &R);
+    if (rc != SMVS_OK)
+        return rc;
+    sgm_launch_census(B, d_main, w, h);
+    if ((rc = sgm_launch_warp_cost(B, R, w, h, d_nbr, nw, nh, M, t, num_steps, B.cost))
+        != SMVS_OK)
+        return rc;
+    return sgm_run_tail(B, R, d_main, w, h, num_steps, penalty1, penalty2, p2_mode, d_depth);
+}
+
+// (declared in sgm_internal.h)
+int
+sgm_download_cost16(Workspace &ws, const uint8_t *d_cost, size_t vol, uint16_t *cost)
+{
+    int rc;
+    uint16_t *d_cost16 = nullptr;
+    if ((rc = ws.ensure(WS_COST16, vol, &d_cost16)))
+        return rc;
+    hipLaunchKernelGGL(widen_u8_kernel, dim3((unsigned)((vol + 255) / 256)),
+        dim3(256), 0, ws.stream, d_cost, d_cost16, vol);
+    SMVS_HIP_CHECK(hipGetLastError());
+    return ws.download(cost, d_cost16, sizeof(uint16_t) * vol);
 }
 
 } // namespace smvs_hip
@@ -914,16 +967,8 @@ sgm_run_impl(int device, const uint8_t *main_img, int w, int h,
     if (sgm != nullptr
         && (rc = ws.download(sgm, B.sgm, sizeof(uint16_t) * vol)) != SMVS_OK)
         return rc;
-    if (cost != nullptr) {
-        uint16_t *d_cost16 = nullptr;
-        if ((rc = ws.ensure(WS_COST16, vol, &d_cost16)))
-            return rc;
-        hipLaunchKernelGGL(widen_u8_kernel, dim3((unsigned)((vol + 255) / 256)),
-            dim3(256), 0, ws.stream, B.cost, d_cost16, vol);
-        SMVS_HIP_CHECK(hipGetLastError());
-        if ((rc = ws.download(cost, d_cost16, sizeof(uint16_t) * vol)) != SMVS_OK)
-            return rc;
-    }
+    if (cost != nullptr && (rc = sgm_download_cost16(ws, B.cost, vol, cost)) != SMVS_OK)
+        return rc;
     SMVS_HIP_CHECK(hipStreamSynchronize(ws.stream));
     return SMVS_OK;
 }

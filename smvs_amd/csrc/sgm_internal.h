@@ -1,7 +1,8 @@
 // What the translation units of the SGM front end share: sgm.hip (run_sgm:
 // census, warp, cost, WTA), sgm_paths.hip (its path aggregation), sgm_view.hip
-// (a view's front end), image_prep.hip (a view's input image), bilateral.hip
-// (the joint bilateral upsample).
+// (a view's front end), sgm_sweep.hip (the opt-in plane sweep over n
+// neighbours), image_prep.hip (a view's input image), bilateral.hip (the joint
+// bilateral upsample).
 #pragma once
 
 #include "common.h"
@@ -53,9 +54,10 @@ enum {
     WS_RAW, WS_RAW0, WS_RAW1,                                         // raw u8 images + scratch
     WS_BIL_DM, WS_BIL_CI, WS_BIL_OUT,                                 // bilateral upsample
     WS_DELTA,                                                         // eight path-byte volumes
-    WS_FWDN, WS_BWDN, WS_SUPPORT                                      // consensus merge: n + n maps, support
+    WS_FWDN, WS_BWDN, WS_SUPPORT,                                     // consensus merge: n + n maps, support
+    WS_SWEEP                                                          // plane sweep: n cost volumes
 };
-static_assert(WS_SUPPORT < Workspace::SLOTS, "the last slot must exist in a Workspace");
+static_assert(WS_SWEEP < Workspace::SLOTS, "the last slot must exist in a Workspace");
 
 // The largest plane count of a run: the key of the WTA kernels is
 // value * 256 + plane (one byte for the plane), and 64 lanes x 4 planes is one
@@ -150,6 +152,31 @@ SgmPathPlan sgm_path_plan_here(int num_steps, unsigned largest_p2);
 // to B.sgm, as plan.delta says.  (sgm_paths.hip)
 int sgm_launch_paths(SgmWorkspace &B, SgmPathPlan const &plan, const uint8_t *d_main,
     int w, int h, int num_steps, unsigned p1, unsigned p2, int p2_mode);
+
+// The stages of a run, which sgm_run_device and the plane sweep of
+// sgm_sweep.hip share.  (sgm.hip)
+struct SgmRun {
+    SgmPathPlan plan;
+    const float *d_depths = nullptr, *d_inv = nullptr;   // this run's tables in B.depths
+    bool subplane = false;
+};
+// The checks of a run, its plan, B's buffers for w x h x num_steps and the run's
+// depth table (sgm_stereo.cc:195-203) uploaded.
+int sgm_run_plan(SgmWorkspace &B, int w, int h, float min_depth, float max_depth,
+    int num_steps, uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, SgmRun *R);
+// census_filter of the main image into B.census
+void sgm_launch_census(SgmWorkspace &B, const uint8_t *d_main, int w, int h);
+// warped_neighbors_for_depth and create_cost_volume for one neighbour: through
+// B.warped into d_cost (B.cost, or a volume of the sweep); hipGetLastError
+int sgm_launch_warp_cost(SgmWorkspace &B, SgmRun const &R, int w, int h,
+    const uint8_t *d_nbr, int nw, int nh, const float *M, const float *t, int num_steps,
+    uint8_t *d_cost);
+// sgm_launch_paths on B.cost and the WTA kernel of the plan: d_depth, B.argmin
+// (and B.sgm with B.want_sgm)
+int sgm_run_tail(SgmWorkspace &B, SgmRun const &R, const uint8_t *d_main, int w, int h,
+    int num_steps, uint16_t penalty1, uint16_t penalty2, int p2_mode, float *d_depth);
+// a u8 cost volume on the device, widened to u16, to the host (slot WS_COST16)
+int sgm_download_cost16(Workspace &ws, const uint8_t *d_cost, size_t vol, uint16_t *cost);
 
 // SGMStereo::run_sgm (sgm_stereo.cc:98-124) on device images; the depth map
 // (and optionally argmin) stay on the device.  winner: smvs_sgm_winner.

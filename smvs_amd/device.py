@@ -672,6 +672,97 @@ def sgm_check_merge(fwd, neighbors, agree_ratio=0.95, min_agree=2, device=0):
     return dict(merged=merged, checked=checked, support=support)
 
 
+class SgmSweepOptions(C.Structure):
+    """smvs_sgm_sweep_options of include/smvs_hip.h."""
+    _fields_ = [("p2_mode", C.c_int), ("winner", C.c_int), ("min_views", C.c_int),
+                ("best_k", C.c_int), ("support_cost", C.c_int), ("min_support", C.c_int)]
+
+
+def sgm_sweep_defaults(n):
+    """(min_views, best_k, support_cost, min_support) for n neighbours: defaults
+    of a user option, untuned; nobody has measured them on real scenes."""
+    return min(2, n), (n + 1) // 2, 20, min(2, n)
+
+
+def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2=96, device=0,
+                       adaptive_p2=False, subplane=False, halvings=None, min_views=None,
+                       best_k=None, support_cost=20, min_support=None, want_volumes=False):
+    """The multi-neighbour plane sweep of include/smvs_hip.h (not in the
+    reference; opt-in): one cost volume of the main view from all n = 1 .. 16
+    neighbours -- per cell the rounded mean of the best_k smallest of the
+    neighbours' cost bytes (0: of all), no cost with fewer than min_views of them
+    -- aggregated once, one winner; support = the neighbours whose own cost at
+    the winner plane is at most support_cost, and no depth below min_support of
+    them.  No neighbour-side runs and no left/right check.
+    neighbors: dicts of which image, M_fwd and t_fwd are read; depth_range:
+    (min, max) of the main view.  halvings (an int): full-resolution embeddings
+    of one or three channels, as for sgm_depth_for_view.  adaptive_p2, subplane:
+    as for sgm_run.  min_views, best_k, min_support: None is min(2, n),
+    (n + 1) // 2 and min(2, n); with support_cost = 20 these are defaults of a
+    user option, untuned, and nobody has measured them on real scenes.
+    Returns dict(depth, argmin, support[, cost, sgm]); with halvings dict(depth,
+    support)."""
+    lib = _capi.load()
+    n = len(neighbors)
+    d_views, d_k, _, d_support = sgm_sweep_defaults(n)
+    opts = SgmSweepOptions(P2_ADAPTIVE if adaptive_p2 else P2_CONSTANT,
+                           WINNER_SUBPLANE if subplane else WINNER_PLANE,
+                           d_views if min_views is None else int(min_views),
+                           d_k if best_k is None else int(best_k), int(support_cost),
+                           d_support if min_support is None else int(min_support))
+    main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
+    keep = []
+    full = [dict(M_bwd=np.zeros(9), t_bwd=np.zeros(3), range_main=depth_range,
+                 range_neighbor=depth_range, **{k: nb[k] for k in ("image", "M_fwd", "t_fwd")})
+            for nb in neighbors]
+    arr = _sgm_neighbors(full, keep) if n else None
+    rng = (C.c_float * 2)(float(depth_range[0]), float(depth_range[1]))
+    h, w = main_img.shape[:2]
+    if halvings is not None:
+        if want_volumes:
+            raise ValueError("want_volumes: the volumes are outputs of the SGM-scale entry")
+        channels = 1 if main_img.ndim == 2 else main_img.shape[2]
+        nch = (C.c_int * max(n, 1))(*[1 if k.ndim == 2 else k.shape[2] for k in keep])
+        ow, oh = w, h
+        for _ in range(int(halvings)):
+            ow, oh = (ow + 1) // 2, (oh + 1) // 2
+        depth = np.zeros((oh, ow), dtype=np.float32)
+        support = np.zeros((oh, ow), dtype=np.uint8)
+        check(lib.smvs_sgm_sweep_for_view_raw(device, _p(main_img, _u8p), w, h, channels, arr,
+              nch, n, int(halvings), rng, num_steps, C.c_uint16(p1), C.c_uint16(p2),
+              C.byref(opts), _p(depth, _fp), _p(support, _u8p)))
+        return dict(depth=depth, support=support)
+    if main_img.ndim != 2 or any(k.ndim != 2 for k in keep):
+        raise ValueError("one-channel images at SGM scale (or pass halvings)")
+    depth = np.zeros((h, w), dtype=np.float32)
+    argmin = np.zeros((h, w), dtype=np.int32)
+    support = np.zeros((h, w), dtype=np.uint8)
+    cost = np.zeros((h, w, num_steps), dtype=np.uint16) if want_volumes else None
+    sgm = np.zeros((h, w, num_steps), dtype=np.uint16) if want_volumes else None
+    check(lib.smvs_sgm_sweep_for_view(device, _p(main_img, _u8p), w, h, arr, n, rng, num_steps,
+          C.c_uint16(p1), C.c_uint16(p2), C.byref(opts), _p(depth, _fp), _p(argmin, _i32p),
+          _p(support, _u8p), _p(cost, _u16p), _p(sgm, _u16p)))
+    out = dict(depth=depth, argmin=argmin, support=support)
+    if want_volumes:
+        out.update(cost=cost, sgm=sgm)
+    return out
+
+
+def sgm_fold_costs(costs, min_views=1, best_k=0, device=0):
+    """smvs_sgm_fold_costs: the fold kernel of the plane sweep alone.  costs
+    (n, ...) u8, one array of cost bytes per neighbour (255: no cost); returns the
+    folded bytes in the shape of one of them."""
+    lib = _capi.load()
+    costs = np.ascontiguousarray(costs, dtype=np.uint8)
+    if costs.ndim < 2:
+        raise ValueError("costs: (n, ...) with one array per neighbour")
+    n = costs.shape[0]
+    out = np.zeros(costs.shape[1:], dtype=np.uint8)
+    check(lib.smvs_sgm_fold_costs(device, _p(costs, _u8p), n, C.c_size_t(out.size),
+          int(min_views), int(best_k), _p(out, _u8p)))
+    return out
+
+
 class MeshView(C.Structure):
     """smvs_mesh_view of include/smvs_hip.h."""
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("flen", C.c_float),

@@ -227,6 +227,12 @@ class ReconSettings(C.Structure):
                 ("input_scale", C.c_int), ("max_pixels", C.c_int)]
 
 
+class SgmSweep(C.Structure):
+    """smvs_host_sgm_sweep of csrc/host/host_capi.h."""
+    _fields_ = [("sweep", C.c_int), ("min_views", C.c_int), ("best_k", C.c_int),
+                ("support_cost", C.c_int), ("min_support", C.c_int)]
+
+
 def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       regularization=1.0, output_scale=2, use_shading=False, use_sgm=True,
                       force_recon=False, force_sgm=False, sgm_range=(0.0, 0.0), sgm_scale=1,
@@ -235,7 +241,9 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       sgm_adaptive_penalty2=False, device_input_scaling=False,
                       device_shading_prep=False, gamma_correction=False, sgm_num_steps=128,
                       sgm_subplane=False, sgm_neighbors=2, sgm_consensus=False,
-                      sgm_agree_ratio=0.95, sgm_min_agree=2):
+                      sgm_agree_ratio=0.95, sgm_min_agree=2, sgm_sweep=False,
+                      sgm_sweep_min_views=-1, sgm_sweep_best_k=-1, sgm_sweep_support_cost=20,
+                      sgm_sweep_min_support=-1):
     """smvsrecon's scene-level run (app/smvsrecon.cc:400-745) through
     smvs_amd::reconstruct_scene: returns (reconstructed ids, skipped, seconds)
     [, input scale used if `details`].  input_scale < 0 (the default, as
@@ -268,8 +276,19 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     SMVS_SGM_MERGE_CONSENSUS of include/smvs_hip.h); more than two neighbours
     without sgm_consensus is an error.  Off by default; 0.95 and 2 are defaults of
     a user option, not tuned values, and nobody has measured their effect on real
-    scenes.  The reuse rule is that of sgm_subplane (force_sgm)."""
+    scenes.  The reuse rule is that of sgm_subplane (force_sgm).
+    sgm_sweep and its four values: ReconSettings::sgm_sweep / ... -- the smvs-sgm
+    map of every view by the multi-neighbour plane sweep of include/smvs_hip.h
+    over its first sgm_neighbors neighbours (one cost volume from all of them,
+    one aggregation, one winner, a support test; no left/right check) instead of
+    the runs and the merge; not together with sgm_consensus.  -1: the default at
+    n neighbours (min_views min(2, n), best_k (n + 1) // 2, min_support
+    min(2, n)).  Off by default; these and 20 are defaults of a user option,
+    untuned, and nobody has measured them on real scenes.  The reuse rule is that
+    of sgm_subplane (force_sgm)."""
     lib = load()
+    sweep = SgmSweep(1 if sgm_sweep else 0, sgm_sweep_min_views, sgm_sweep_best_k,
+                     sgm_sweep_support_cost, sgm_sweep_min_support)
     st = ReconSettings(image_embedding.encode(), regularization, output_scale,
                        1 if use_shading else 0, 1 if use_sgm else 0,
                        1 if force_recon else 0, 1 if force_sgm else 0, 0,
@@ -282,12 +301,12 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                              C.byref(cap), None, None, None, None, None, None, None)
     out = np.zeros(max(cap.value, 1), np.int32)
     n = C.c_int(0); sk = C.c_int(0); secs = C.c_double(0.0); used = C.c_int(0)
-    rc = lib.smvs_host_reconstruct_scene_merge(scene_dir.encode(), C.byref(st),
+    rc = lib.smvs_host_reconstruct_scene_sweep(scene_dir.encode(), C.byref(st),
         C.c_uint((1 if sgm_adaptive_penalty2 else 0) | (2 if device_input_scaling else 0)
                  | (8 if device_shading_prep else 0) | (16 if gamma_correction else 0)),
         C.c_int(sgm_num_steps), C.c_int(1 if sgm_subplane else 0),
         C.c_int(sgm_neighbors), C.c_int(1 if sgm_consensus else 0),
-        C.c_float(sgm_agree_ratio), C.c_int(sgm_min_agree),
+        C.c_float(sgm_agree_ratio), C.c_int(sgm_min_agree), C.byref(sweep),
         ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), out.ctypes.data_as(_i32p),
         C.c_int(out.size), C.byref(n), C.byref(sk), C.byref(secs), C.byref(used))
@@ -432,7 +451,9 @@ def view_queue_selftest(n_tasks, num_devices, views_in_flight, throwing_task=-1)
 
 def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
               adaptive_penalty2=False, num_steps=128, subplane=False, neighbors=2,
-              consensus=False, agree_ratio=0.95, min_agree=2):
+              consensus=False, agree_ratio=0.95, min_agree=2, sweep=False,
+              sweep_min_views=-1, sweep_best_k=-1, sweep_support_cost=20,
+              sweep_min_support=-1):
     """reconstruct_sgm_depth_for_view through the host mirror.
     adaptive_penalty2: SGMStereo::Options::adaptive_penalty2 (the reference's
     build without SSE, lib/sgm_stereo.cc:310-346); off by default.
@@ -449,20 +470,29 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
     than min_agree).  More than two neighbours without consensus raise; off by
     default.  0.95 and 2 are defaults of a user option, not tuned values (0.95
     admits about two of 128 planes at the far end of a 3 .. 12 range; the
-    left/right check uses 0.8); nobody has measured their effect on real scenes."""
+    left/right check uses 0.8); nobody has measured their effect on real scenes.
+    sweep and its four values: SGMStereo::Options::sweep / ... -- the
+    multi-neighbour plane sweep of include/smvs_hip.h over the first `neighbors`
+    neighbours instead of the runs and the merge; raises together with
+    consensus.  -1: the default at n neighbours (min_views min(2, n), best_k
+    (n + 1) // 2, min_support min(2, n)); untuned defaults of a user option,
+    nobody has measured them on real scenes.  Off by default."""
     lib = load()
     keep = []
+    sw = SgmSweep(1 if sweep else 0, sweep_min_views, sweep_best_k, sweep_support_cost,
+                  sweep_min_support)
     main, subs, n_subs, b = _marshal(inputs, keep)
     w, h = main.width, main.height
     for _ in range(sgm_scale):
         w, h = (w + 1) // 2, (h + 1) // 2
     out = np.zeros((h, w), dtype=np.float32)
     ow = C.c_int(0); oh = C.c_int(0)
-    rc = lib.smvs_host_sgm_depth_merge(C.byref(main), subs, n_subs, C.byref(b),
+    rc = lib.smvs_host_sgm_depth_sweep(C.byref(main), subs, n_subs, C.byref(b),
         sgm_scale, C.c_float(min_depth), C.c_float(max_depth), device,
         C.c_int(1 if adaptive_penalty2 else 0), C.c_int(num_steps),
         C.c_int(1 if subplane else 0), C.c_int(neighbors), C.c_int(1 if consensus else 0),
-        C.c_float(agree_ratio), C.c_int(min_agree), out.ctypes.data_as(_fp), C.byref(ow),
+        C.c_float(agree_ratio), C.c_int(min_agree), C.byref(sw), out.ctypes.data_as(_fp),
+        C.byref(ow),
         C.byref(oh))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())

@@ -15,8 +15,13 @@ kernel's share of the HBM peak from its algorithmic bytes.
 agree_ratio 0.95, min_agree 2) over N ring neighbours at the same size: the
 time per view and, from smvs_sgm_profile, the left/right-check and merge
 kernels (with --consensus the one fused kernel, reported as merge) with the
-bytes they move.  Without --consensus N is 1 or 2, the reference's merge."""
+bytes they move.  Without --consensus N is 1 or 2, the reference's merge.
+--neighbors N --sweep: the multi-neighbour plane sweep (smvs_sgm_sweep_for_view
+at the defaults for N neighbours) instead: the time per view, the fold kernel
+(reported as merge) with its (N + 1) volume bytes against the HBM read peak of
+profiles/r2_peaks.json, and the support kernel (reported as lr_check)."""
 import ctypes as C
+import json
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -53,6 +58,9 @@ if subplane:
 if "--neighbors" in sys.argv:
     n = _arg("--neighbors", 2)
     consensus = "--consensus" in sys.argv
+    sweep = "--sweep" in sys.argv
+    if sweep and consensus:
+        sys.exit("--sweep and --consensus exclude each other")
     main, subs = synth.ring_cameras(w, h, n)
     small = [im[::2, ::2].copy() for im in [synth.render(scene, c) for c in [main] + subs]]
     cams = [synth.Camera(c.R, c.t, c.flen, hw, hh) for c in [main] + subs]
@@ -64,10 +72,14 @@ if "--neighbors" in sys.argv:
                         range_main=[2.0, 10.0], range_neighbor=[2.0, 10.0]))
     if consensus:
         kw["consensus"] = True
-    print("front end of a view, %d neighbours, %s" % (n, "consensus merge (0.95, 2)" if consensus
-                                                      else "the reference's merge"))
+    print("front end of a view, %d neighbours, %s" % (
+        n, "plane sweep (min_views %d, best_k %d, support_cost %d, min_support %d)"
+        % smvs_amd.device.sgm_sweep_defaults(n) if sweep
+        else "consensus merge (0.95, 2)" if consensus else "the reference's merge"))
 
     def view():
+        if sweep:
+            return smvs_amd.sgm_sweep_for_view(small[0], nbs, (2.0, 10.0), D, 6, p2, **kw)["depth"]
         return smvs_amd.sgm_depth_for_view(small[0], nbs, D, 6, p2, **kw)
 
     lib = _capi.load()
@@ -93,7 +105,18 @@ if "--neighbors" in sys.argv:
             print("kernel %-8s %9.1f us per launch, %9.1f us per view (%d launches per view)"
                   % (name, 1e3 * ms[i] / cnt[i], 1e3 * ms[i] / repeat, cnt[i] // repeat))
     npix = hw * hh
-    if consensus:
+    if sweep:
+        # n volumes read, the folded one written
+        nbytes = (n + 1) * npix * D
+        us = 1e3 * ms[6] / max(cnt[6], 1)
+        with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                               "profiles", "r2_peaks.json")) as f:
+            peak = json.load(f)["hbm_read_GBps"] / 1e3
+        print("fold (one kernel): %.1f us per view, %.1f MB, %.2f TB/s, %.2f of the %.2f TB/s "
+              "HBM read peak" % (us, nbytes / 1e6, nbytes / us / 1e6, nbytes / us / 1e6 / peak,
+                                 peak))
+        print("support (one kernel): %.1f us per view" % (1e3 * ms[5] / max(cnt[5], 1)))
+    elif consensus:
         # n forward maps read, n scattered lookups, the merged map written
         nbytes = 4 * npix * (2 * n + 1)
         us = 1e3 * ms[6] / max(cnt[6], 1)
