@@ -625,6 +625,94 @@ int smvs_sgm_sweep_for_view_raw(int device, const uint8_t *main_img, int w, int 
 int smvs_sgm_fold_costs(int device, const uint8_t *costs, int n_neighbors, size_t len,
     int min_views, int best_k, uint8_t *out);
 
+/* Two single-run rejections for the front end above.  Not in the reference;
+ * both off by default, and with both off every entry below gives the bytes and
+ * the launches of the entry it extends.
+ *
+ * Uniqueness test.  Integers only.  Per pixel of a run, after the winner i has
+ * been found (the first minimum, unchanged), with S the aggregated u16 sums,
+ * b = S[i] and D = num_steps:
+ *     competitors = { d in 0 .. D-1 : |d - i| > uniqueness_window }
+ *     if competitors is empty:  the pixel passes;  runner_up = 65535
+ *     else  r = min over competitors of S[d];      runner_up = r
+ *           rejected  iff  r * (100 - uniqueness) < b * 100     (int, 32 bits)
+ * A rejected pixel gets depth 0; argmin stays i; the rule of
+ * sgm_stereo.cc:300-303 is unchanged, and the sub-plane winner computes what it
+ * computed for a pixel that passes.  The comparison is strict: a competitor
+ * exactly at the bound passes.  The test is part of the WTA step of EVERY run
+ * of an entry, the neighbour-side runs of a view included.  uniqueness = 0
+ * rejects nothing and launches the WTA kernels of the entries above.
+ * uniqueness in 0 .. 99 (a percentage), uniqueness_window in 1 .. 256 (planes).
+ * The window is an option because the usual fixed +-1 assumes planes a pixel
+ * apart: at 128 planes over depths 3 .. 12 adjacent planes are less than a
+ * pixel apart and window 1 rejects half of a synthetic pair's valid pixels,
+ * window 16 a twentieth.  The defaults of the layers above (0, 1) are defaults
+ * of a user option, untuned; nobody has measured them on real scenes.
+ *
+ * Speckle removal.  On a depth map of w x h floats:
+ *     a pixel is valid iff depth > 0.0f (a NaN is not);
+ *     two valid 4-neighbours (x +- 1 or y +- 1) a, b are linked iff
+ *         fminf(a, b) / fmaxf(a, b) >= speckle_ratio   (IEEE division, no
+ *         contraction: the idiom of the consensus);
+ *     components are the transitive closure of the links (unlike the
+ *         consensus's star, a ~ b ~ c puts a and c together);
+ *     size[p] = the number of pixels of p's component as u32, 0 for a pixel
+ *         that is not valid;
+ *     out[p] = 0 where 0 < size[p] < speckle_size, else the input's bits.
+ * The partition is a fact of the input, so the result is defined to the bit.
+ * speckle_size 0 and 1 remove nothing (off: no launch); speckle_ratio in
+ * [0, 1].  The filter runs on the final map of a view, before the download:
+ * after the reference merge, after the consensus merge (checked and support
+ * stay those of the merge), after the sweep's support test.  Its launches are
+ * timed in class SMVS_SGM_K_MERGE of smvs_sgm_profile.
+ *
+ * SMVS_ERR_INVALID before any device call: a NULL filter pointer, uniqueness
+ * outside 0 .. 99, a window outside 1 .. 256, a negative speckle_size, a ratio
+ * outside [0, 1] or NaN, speckle_size > 1 on the run entry, a runner_up output
+ * with uniqueness = 0. */
+typedef struct {
+    int uniqueness;
+    int uniqueness_window;
+    int speckle_size;
+    float speckle_ratio;
+} smvs_sgm_filter_options;
+
+/* smvs_sgm_run_opts with the uniqueness test; extra optional output
+ * runner_up[w * h] (u16).  The speckle fields must be off. */
+int smvs_sgm_run_filtered(int device, const uint8_t *main_img, int w, int h,
+    const uint8_t *neighbor_img, int nw, int nh, const float *M,
+    const float *t, float min_depth, float max_depth, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint16_t *cost,
+    uint16_t *sgm, uint16_t *runner_up);
+/* smvs_sgm_depth_for_view_merge / _raw_merge with the filters */
+int smvs_sgm_depth_for_view_filtered(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_view_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support);
+int smvs_sgm_depth_for_view_raw_filtered(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_view_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support);
+/* smvs_sgm_sweep_for_view / _raw with the filters; extra optional output of the
+ * first: runner_up[w * h] (u16) */
+int smvs_sgm_sweep_for_view_filtered(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, const float *range, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_sweep_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint8_t *support,
+    uint16_t *cost, uint16_t *sgm, uint16_t *runner_up);
+int smvs_sgm_sweep_for_view_raw_filtered(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_sweep_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, uint8_t *support);
+/* The speckle kernels alone, on a map of the caller: depth[w * h], out[w * h]
+ * (may be depth itself), size[w * h] (may be NULL); w * h < 2^31.  The kernels
+ * run for every speckle_size (0 and 1 give the input's bits and the sizes). */
+int smvs_sgm_filter_speckles(int device, const float *depth, int w, int h, int speckle_size,
+    float speckle_ratio, float *out, uint32_t *size);
+
 /* DepthOptimizer::depthmap_bilateral_filter, depth_optimizer.cc:957-1004 */
 int smvs_bilateral_upsample(int device, const float *dm, int dm_w, int dm_h,
     const float *ci, int w, int h, int channels, float sigma,

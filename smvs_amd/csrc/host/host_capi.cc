@@ -375,7 +375,57 @@ smvs_host_sgm_depth_sweep(const smvs_host_view *main_in, const smvs_host_view *s
     int min_agree, const smvs_host_sgm_sweep *sweep, float *depth_out, int *out_w,
     int *out_h)
 {
+    return smvs_host_sgm_depth_filtered(main_in, subs_in, n_subs, bundle_in, sgm_scale,
+        min_depth, max_depth, device, adaptive_penalty2, num_steps, subplane, num_neighbors,
+        consensus, agree_ratio, min_agree, sweep, nullptr, depth_out, out_w, out_h);
+}
+
+extern "C" int
+smvs_host_sgm_filter_defaults(int *ints6, float *ratios2)
+{
+    if (ints6 == nullptr || ratios2 == nullptr) {
+        g_host_error = "smvs_host_sgm_filter_defaults: bad argument";
+        return -1;
+    }
+    SGMStereo::Options const opts;
+    ReconSettings const conf;
+    ints6[0] = opts.uniqueness;
+    ints6[1] = opts.uniqueness_window;
+    ints6[2] = opts.speckle_size;
+    ints6[3] = conf.sgm_uniqueness;
+    ints6[4] = conf.sgm_uniqueness_window;
+    ints6[5] = conf.sgm_speckle_size;
+    ratios2[0] = opts.speckle_ratio;
+    ratios2[1] = conf.sgm_speckle_ratio;
+    return 0;
+}
+
+namespace {
+// the accepted set of include/smvs_hip.h (a NaN ratio fails the comparisons)
+void
+check_host_sgm_filter(const smvs_host_sgm_filter *f, char const* who)
+{
+    if (f == nullptr)
+        return;
+    if (f->uniqueness < 0 || f->uniqueness > 99 || f->uniqueness_window < 1
+        || f->uniqueness_window > 256 || f->speckle_size < 0
+        || !(f->speckle_ratio >= 0.0f && f->speckle_ratio <= 1.0f))
+        throw std::invalid_argument(std::string(who) + ": sgm_uniqueness must be in [0, 99], "
+            "sgm_uniqueness_window in [1, 256], sgm_speckle_size not negative and "
+            "sgm_speckle_ratio in [0, 1]");
+}
+}
+
+extern "C" int
+smvs_host_sgm_depth_filtered(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, int sgm_scale,
+    float min_depth, float max_depth, int device, int adaptive_penalty2,
+    int num_steps, int subplane, int num_neighbors, int consensus, float agree_ratio,
+    int min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    float *depth_out, int *out_w, int *out_h)
+{
     try {
+        check_host_sgm_filter(filter, "smvs_host_sgm_depth_filtered");
         // (before the views are copied: an argument error needs no image)
         bool const sweep_on = sweep != nullptr && sweep->sweep != 0;
         if (sweep_on && consensus != 0)
@@ -410,6 +460,12 @@ smvs_host_sgm_depth_sweep(const smvs_host_view *main_in, const smvs_host_view *s
             opts.sweep_best_k = sweep->best_k;
             opts.sweep_support_cost = sweep->support_cost;
             opts.sweep_min_support = sweep->min_support;
+        }
+        if (filter != nullptr) {
+            opts.uniqueness = filter->uniqueness;
+            opts.uniqueness_window = filter->uniqueness_window;
+            opts.speckle_size = filter->speckle_size;
+            opts.speckle_ratio = filter->speckle_ratio;
         }
         FloatImage::Ptr d = reconstruct_sgm_depth_for_view(opts, main_view, subs,
             bundle);
@@ -1049,7 +1105,22 @@ smvs_host_reconstruct_scene_sweep(const char *scene_dir,
     int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
     int *n_skipped, double *seconds, int *input_scale_used)
 {
+    return smvs_host_reconstruct_scene_filtered(scene_dir, o, flags, sgm_num_steps,
+        sgm_subplane, sgm_neighbors, sgm_consensus, sgm_agree_ratio, sgm_min_agree, sweep,
+        nullptr, view_ids, n_view_ids, reconstructed_out, max_reconstructed, n_reconstructed,
+        n_skipped, seconds, input_scale_used);
+}
+
+extern "C" int
+smvs_host_reconstruct_scene_filtered(const char *scene_dir,
+    const smvs_host_recon_settings *o, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
+    int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used)
+{
     try {
+        check_host_sgm_filter(filter, "smvs_host_reconstruct_scene_filtered");
         bool const sweep_on = sweep != nullptr && sweep->sweep != 0;
         if (sweep_on && sgm_consensus != 0)
             throw std::invalid_argument("smvs_host_reconstruct_scene_sweep: sgm_sweep and "
@@ -1105,6 +1176,12 @@ smvs_host_reconstruct_scene_sweep(const char *scene_dir,
             conf.sgm_sweep_best_k = sweep->best_k;
             conf.sgm_sweep_support_cost = sweep->support_cost;
             conf.sgm_sweep_min_support = sweep->min_support;
+        }
+        if (filter != nullptr) {
+            conf.sgm_uniqueness = filter->uniqueness;
+            conf.sgm_uniqueness_window = filter->uniqueness_window;
+            conf.sgm_speckle_size = filter->speckle_size;
+            conf.sgm_speckle_ratio = filter->speckle_ratio;
         }
         conf.device_input_scaling = (flags & SMVS_HOST_SCENE_DEVICE_INPUT_SCALING) != 0u;
         conf.device_shading_prep = (flags & SMVS_HOST_SCENE_DEVICE_SHADING_PREP) != 0u;

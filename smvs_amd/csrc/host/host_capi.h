@@ -185,6 +185,28 @@ int smvs_host_sgm_depth_sweep(const smvs_host_view *main_view,
  * and ReconSettings (ints10[5 .. 9]) hold them, in the order of
  * smvs_host_sgm_sweep (no device involved). */
 int smvs_host_sgm_sweep_defaults(int *ints10);
+/* SGMStereo::Options::uniqueness / uniqueness_window / speckle_size /
+ * speckle_ratio (the two filters of include/smvs_hip.h, "Two single-run
+ * rejections"; not in the reference). */
+typedef struct {
+    int uniqueness, uniqueness_window, speckle_size;
+    float speckle_ratio;
+} smvs_host_sgm_filter;
+/* smvs_host_sgm_depth_sweep with the filters, for any of the three front ends:
+ * uniqueness outside 0 .. 99, a window outside 1 .. 256, a negative
+ * speckle_size and a ratio outside [0, 1] are argument errors before anything
+ * runs.  filter == NULL: off; smvs_host_sgm_depth_sweep forwards to this with
+ * NULL. */
+int smvs_host_sgm_depth_filtered(const smvs_host_view *main_view,
+    const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
+    int sgm_scale, float min_depth, float max_depth, int device,
+    int adaptive_penalty2, int num_steps, int subplane, int num_neighbors,
+    int consensus, float agree_ratio, int min_agree, const smvs_host_sgm_sweep *sweep,
+    const smvs_host_sgm_filter *filter, float *depth_out, int *out_w, int *out_h);
+/* The filter options as a default-constructed SGMStereo::Options (ints6[0 .. 2],
+ * ratios2[0]) and ReconSettings (ints6[3 .. 5], ratios2[1]) hold them, in the
+ * order of smvs_host_sgm_filter (no device involved). */
+int smvs_host_sgm_filter_defaults(int *ints6, float *ratios2);
 /* The switches of the SGM front end that the reference does not have, as a
  * default-constructed SGMStereo::Options and ReconSettings hold them (no
  * device involved): out4 = { Options::adaptive_penalty2, Options::subplane,
@@ -341,6 +363,19 @@ int smvs_host_reconstruct_scene_sweep(const char *scene_dir,
     int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const int *view_ids,
     int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
     int *n_skipped, double *seconds, int *input_scale_used);
+
+/* The same with ReconSettings::sgm_uniqueness / sgm_uniqueness_window /
+ * sgm_speckle_size / sgm_speckle_ratio: the two filters in every view's SGM
+ * front end (arguments: the settings struct keeps its layout).  A value outside
+ * the accepted set is an argument error before the scene is read; filter ==
+ * NULL: off (smvs_host_reconstruct_scene_sweep forwards to this with NULL).  The
+ * reuse rule is that of sgm_subplane (force_sgm). */
+int smvs_host_reconstruct_scene_filtered(const char *scene_dir,
+    const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
+    int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used);
 
 /* smvsrecon's generate_mesh (app/smvsrecon.cc:278-343, MeshGenerator::
  * generate_mesh, lib/mesh_generator.cc:160-299) on a reconstructed scene: the

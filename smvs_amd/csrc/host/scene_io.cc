@@ -593,6 +593,10 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                         sgm_opts.sweep_best_k = conf.sgm_sweep_best_k;
                         sgm_opts.sweep_support_cost = conf.sgm_sweep_support_cost;
                         sgm_opts.sweep_min_support = conf.sgm_sweep_min_support;
+                        sgm_opts.uniqueness = conf.sgm_uniqueness;
+                        sgm_opts.uniqueness_window = conf.sgm_uniqueness_window;
+                        sgm_opts.speckle_size = conf.sgm_speckle_size;
+                        sgm_opts.speckle_ratio = conf.sgm_speckle_ratio;
                         (void)reconstruct_sgm_depth_for_view(sgm_opts, main_view,
                             stereo_views, bundle);
                         save_mvei(view.image_path("smvs-sgm"),

@@ -128,6 +128,15 @@ struct ReconSettings
     int sgm_sweep_best_k = -1;
     int sgm_sweep_support_cost = 20;
     int sgm_sweep_min_support = -1;
+    // SGMStereo::Options::uniqueness / uniqueness_window / speckle_size /
+    // speckle_ratio -- the two filters of include/smvs_hip.h ("Two single-run
+    // rejections") in every view's SGM front end, whichever of the three it is.
+    // Off by default; untuned defaults of a user option; the reuse rule is that
+    // of sgm_subplane (force_sgm).
+    int sgm_uniqueness = 0;
+    int sgm_uniqueness_window = 1;
+    int sgm_speckle_size = 0;
+    float sgm_speckle_ratio = 0.95f;
     // not in the reference's AppSettings: the input scaling of :621-650 on the
     // device (rescale_half_size_gaussian_device), one ViewQueue task per view
     bool device_input_scaling = false;

@@ -158,6 +158,10 @@ run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
     int w = main_bytes->width(), h = main_bytes->height();
     sgm_scale_size(o.scale, &w, &h);
     FloatImage::Ptr depth = FloatImage::create_for_overwrite(w, h, 1);
+    // (the defaults call the entries without the filters)
+    bool const filtered = !o.filters_default();
+    smvs_sgm_filter_options const filter = { o.uniqueness, o.uniqueness_window,
+        o.speckle_size, o.speckle_ratio };
     if (o.sweep) {
         // n x (warp + cost) over the main view's planes, one fold, one
         // aggregation, one winner, the support test
@@ -167,6 +171,16 @@ run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
             o.sweep_min_views < 0 ? std::min(2, n) : o.sweep_min_views,
             o.sweep_best_k < 0 ? (n + 1) / 2 : o.sweep_best_k, o.sweep_support_cost,
             o.sweep_min_support < 0 ? std::min(2, n) : o.sweep_min_support };
+        if (filtered) {
+            int const frc = smvs_sgm_sweep_for_view_raw_filtered(o.device, main_bytes->begin(),
+                main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
+                channels.data(), n, o.scale, dev[0].range_main, o.num_steps, o.penalty1,
+                o.penalty2, &sweep_opts, &filter, depth->begin(), nullptr);
+            if (frc != SMVS_OK)
+                throw std::runtime_error(std::string("smvs_sgm_sweep_for_view_raw_filtered: ")
+                    + smvs_last_error());
+            return depth;
+        }
         int const rc = smvs_sgm_sweep_for_view_raw(o.device, main_bytes->begin(),
             main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
             channels.data(), n, o.scale, dev[0].range_main, o.num_steps, o.penalty1,
@@ -176,12 +190,24 @@ run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
                 + smvs_last_error());
         return depth;
     }
-    if (o.consensus) {
+    if (o.consensus || filtered) {
         // the same over n neighbours: 2 n x run_sgm, then the n checks and the
-        // consensus in one kernel
+        // consensus in one kernel; with the filters either merge goes through
+        // the one entry that takes them
         smvs_sgm_options const base = device_options(o);
         smvs_sgm_view_options const view_opts = { base.p2_mode, base.winner,
-            SMVS_SGM_MERGE_CONSENSUS, o.min_agree, o.agree_ratio };
+            o.consensus ? SMVS_SGM_MERGE_CONSENSUS : SMVS_SGM_MERGE_REFERENCE, o.min_agree,
+            o.agree_ratio };
+        if (filtered) {
+            int const frc = smvs_sgm_depth_for_view_raw_filtered(o.device, main_bytes->begin(),
+                main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
+                channels.data(), (int)dev.size(), o.scale, o.num_steps, o.penalty1,
+                o.penalty2, &view_opts, &filter, depth->begin(), nullptr, nullptr);
+            if (frc != SMVS_OK)
+                throw std::runtime_error(std::string("smvs_sgm_depth_for_view_raw_filtered: ")
+                    + smvs_last_error());
+            return depth;
+        }
         int const rc = smvs_sgm_depth_for_view_raw_merge(o.device, main_bytes->begin(),
             main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
             channels.data(), (int)dev.size(), o.scale, o.num_steps, o.penalty1,

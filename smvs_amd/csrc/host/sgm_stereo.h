@@ -68,6 +68,26 @@ public:
         int sweep_best_k = -1;
         int sweep_support_cost = 20;
         int sweep_min_support = -1;
+        // not in the reference either: the two filters of include/smvs_hip.h
+        // ("Two single-run rejections") for any of the three front ends above.
+        // uniqueness (0 .. 99, a percentage; 0 is off): in the WTA step of every
+        // run no depth where a plane more than uniqueness_window (1 .. 256)
+        // planes from the winner has a sum r with
+        // r * (100 - uniqueness) < S[winner] * 100.  speckle_size (0 and 1 are
+        // off): connected components of the final map (4-neighbours whose
+        // min / max is at least speckle_ratio) with fewer pixels are removed.
+        // (0, 1, 0, 0.95) are defaults of a user option, untuned: nobody has
+        // measured them on real scenes.
+        int uniqueness = 0;
+        int uniqueness_window = 1;
+        int speckle_size = 0;
+        float speckle_ratio = 0.95f;
+        // whether the entries without the filters are called
+        bool filters_default() const
+        {
+            return uniqueness == 0 && uniqueness_window == 1 && speckle_size == 0
+                && speckle_ratio == 0.95f;
+        }
 
         // the plane counts smvs_sgm_run / smvs_sgm_depth_for_view accept
         static bool valid_num_steps(int n)

@@ -650,6 +650,162 @@ sgm_sum_wta_wide_subplane_kernel(const uint8_t *__restrict__ cost,
     sum_wta_subplane<64>(cost, delta, vol, main_img, inv, npix, D, depth, argmin, sgm_out);
 }
 
+// ------------------------------------------------------- uniqueness test
+// The WTA kernels above with the uniqueness test of include/smvs_hip.h (not in
+// the reference): r, the smallest S among the planes more than `window` away
+// from the winner i, and no depth where r * (100 - uniqueness) < S[i] * 100.
+// New kernels: the six above know nothing of it.
+
+// Whether no plane of 0 .. D - 1 is more than `window` away from i.
+__device__ __forceinline__ bool
+no_competitor(int i, int window, int D)
+{
+    return i - window <= 0 && i + window >= D - 1;
+}
+
+// wta_store / wta_store_subplane with the test: r is the minimum over the
+// competitors (any value without one); table: the depths, or the inverse depths
+// for the sub-plane winner.  a and c as in wta_store_subplane.
+template <bool SUBPLANE>
+__device__ __forceinline__ void
+wta_store_unique(int i, int a, int b, int c, uint32_t r, int window, int uniqueness, size_t p,
+    const uint8_t *__restrict__ main_img, const float *__restrict__ table, int D,
+    float *__restrict__ depth, int32_t *__restrict__ argmin, uint16_t *__restrict__ runner_up)
+{
+    bool const none = no_competitor(i, window, D);
+    if (runner_up != nullptr)
+        runner_up[p] = (uint16_t)(none ? 65535u : r);
+    if (argmin != nullptr)
+        argmin[p] = i;
+    if (depth != nullptr) {
+        // (r <= 65535 and b <= 65535: 32 bits)
+        bool const rejected = !none && r * (uint32_t)(100 - uniqueness) < (uint32_t)b * 100u;
+        float v = 0.0f;
+        if (!(i < 2 || main_img[p] < 25 || rejected)) {
+            if constexpr (SUBPLANE)
+                v = subplane_depth(i, a, b, c, table, D);
+            else
+                v = table[i];
+        }
+        depth[p] = v;
+    }
+}
+
+// wta_rows_kernel / wta_rows_subplane_kernel with the test: S is in memory; the
+// winner goes to the 16 lanes of the pixel, each takes the minimum of its planes
+// outside the window (a second read of S, from the cache), a second prefix
+// minimum brings r to lane 15.
+template <bool SUBPLANE>
+__global__ void __launch_bounds__(256)
+wta_rows_unique_kernel(const uint16_t *__restrict__ sgm,
+    const uint8_t *__restrict__ main_img, const float *__restrict__ table,
+    size_t npix, int D, int window, int uniqueness, float *__restrict__ depth,
+    int32_t *__restrict__ argmin, uint16_t *__restrict__ runner_up)
+{
+    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    int const sub = threadIdx.x & 15;
+    uint32_t key = 0xFFFFFFFFu;
+    if (p < npix)
+        for (int d = sub; d < D; d += 16)
+            key = min(key, (uint32_t)sgm[p * D + d] * 256u + (uint32_t)d);
+    key = row_prefix_min_u32(key);
+    key = dpp_u32<dpp_row_newbcast(15)>(key, key);
+    int const i = (int)(key & 0xFFu);
+    uint32_t r = 0xFFFFFFFFu;
+    if (p < npix)
+        for (int d = sub; d < D; d += 16)
+            if (d < i - window || d > i + window)
+                r = min(r, (uint32_t)sgm[p * D + d]);
+    r = row_prefix_min_u32(r);
+    if (sub == 15 && p < npix) {
+        const uint16_t *s = sgm + p * D;
+        int const a = SUBPLANE && i >= 1 ? (int)s[i - 1] : 0;
+        int const c = SUBPLANE && i + 1 < D ? (int)s[i + 1] : 0;
+        wta_store_unique<SUBPLANE>(i, a, (int)(key >> 8), c, r, window, uniqueness, p, main_img,
+            table, D, depth, argmin, runner_up);
+    }
+}
+
+// sgm_sum_wta*_kernel with the test, LANES = 32 or 64 lanes per pixel: S is
+// formed in registers as in sum_wta_subplane, every lane learns the winner,
+// takes the minimum of its own four sums outside the window, and a second
+// cross-lane minimum gives r to every lane; the lane that holds the winning
+// plane stores.
+template <int LANES, bool SUBPLANE>
+__global__ void __launch_bounds__(256)
+sgm_sum_wta_unique_kernel(const uint8_t *__restrict__ cost, const uint8_t *__restrict__ delta,
+    size_t vol, const uint8_t *__restrict__ main_img, const float *__restrict__ table,
+    size_t npix, int D, int window, int uniqueness, float *__restrict__ depth,
+    int32_t *__restrict__ argmin, uint16_t *__restrict__ runner_up,
+    uint16_t *__restrict__ sgm_out)
+{
+    static_assert(LANES == 32 || LANES == 64, "half a wavefront or a whole one per pixel");
+    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / LANES;
+    int const sub = threadIdx.x & (LANES - 1);
+    int const d0 = 4 * sub;
+    bool const mine = p < npix && d0 < D;
+    uint32_t key = 0xFFFFFFFFu;
+    uint32_t sv[4] = { 0u, 0u, 0u, 0u };
+    if (mine) {
+        size_t const o = p * (size_t)D + d0;   // D % 4 == 0: aligned u32
+        uint32_t const c = *reinterpret_cast<const uint32_t *>(cost + o);
+        uint32_t e[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            e[k] = *reinterpret_cast<const uint32_t *>(delta + (size_t)k * vol + o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            uint32_t sum = 8u * ((c >> (8 * j)) & 0xFFu);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                sum += (e[k] >> (8 * j)) & 0xFFu;
+            sv[j] = sum & 0xFFFFu;
+            key = min(key, sv[j] * 256u + (uint32_t)(d0 + j));
+        }
+        if (sgm_out != nullptr) {
+            uint2 const packed = make_uint2(sv[0] | (sv[1] << 16), sv[2] | (sv[3] << 16));
+            *reinterpret_cast<uint2 *>(sgm_out + o) = packed;
+        }
+    }
+    // (every lane of the wave takes part in the moves from here on)
+    uint32_t const left = lane_prev(sv[3], 0u);    // S of plane d0 - 1
+    uint32_t const right = lane_next(sv[0], 0u);   // S of plane d0 + 4
+    if constexpr (LANES == 32) {
+        key = row_prefix_min_u32(key);
+        uint32_t const other = (uint32_t)__shfl_xor((int)key, 16);
+        key = min(key, other);
+        key = dpp_u32<dpp_row_newbcast(15)>(key, key);
+    } else {
+        key = wave_min_u32(key);
+    }
+    int const i = (int)(key & 0xFFu);
+    uint32_t r = 0xFFFFFFFFu;
+    if (mine) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int const d = d0 + j;
+            if (d < i - window || d > i + window)
+                r = min(r, sv[j]);
+        }
+    }
+    if constexpr (LANES == 32) {
+        r = row_prefix_min_u32(r);
+        uint32_t const other = (uint32_t)__shfl_xor((int)r, 16);
+        r = min(r, other);
+        r = dpp_u32<dpp_row_newbcast(15)>(r, r);
+    } else {
+        r = wave_min_u32(r);
+    }
+    // (a pixel past the end has the key of all ones: plane 255, no lane of 32)
+    if ((i >> 2) == sub && p < npix) {
+        int const j = i & 3;
+        uint32_t const a = j == 0 ? left : (j == 1 ? sv[0] : (j == 2 ? sv[1] : sv[2]));
+        uint32_t const c = j == 0 ? sv[1] : (j == 1 ? sv[2] : (j == 2 ? sv[3] : right));
+        wta_store_unique<SUBPLANE>(i, (int)a, (int)(key >> 8), (int)c, r, window, uniqueness, p,
+            main_img, table, D, depth, argmin, runner_up);
+    }
+}
+
 __global__ void __launch_bounds__(256)
 widen_u8_kernel(const uint8_t *__restrict__ src, uint16_t *__restrict__ dst,
     size_t n)
@@ -741,6 +897,25 @@ check_sgm_winner(const smvs_sgm_options *opts)
     SMVS_REQUIRE(opts != nullptr, "null options (winner, p2_mode)");
     SMVS_REQUIRE(opts->winner == SMVS_SGM_WINNER_PLANE
             || opts->winner == SMVS_SGM_WINNER_SUBPLANE, "unknown winner");
+    return SMVS_OK;
+}
+
+// (declared in sgm_internal.h)
+int
+check_sgm_filter(const smvs_sgm_filter_options *filter, bool run_entry)
+{
+    SMVS_REQUIRE(filter != nullptr,
+        "null filter options (uniqueness, uniqueness_window, speckle_size, speckle_ratio)");
+    SMVS_REQUIRE(filter->uniqueness >= 0 && filter->uniqueness <= 99,
+        "uniqueness must be in [0, 99]");
+    SMVS_REQUIRE(filter->uniqueness_window >= 1 && filter->uniqueness_window <= SGM_MAX_PLANES,
+        "uniqueness_window must be in [1, 256]");
+    if (int const rc = check_sgm_speckle(filter->speckle_size, filter->speckle_ratio);
+        rc != SMVS_OK)
+        return rc;
+    if (run_entry)
+        SMVS_REQUIRE(filter->speckle_size <= 1,
+            "the speckle filter works on a view's final map, not on a run");
     return SMVS_OK;
 }
 
@@ -867,7 +1042,29 @@ sgm_run_tail(SgmWorkspace &B, SgmRun const &R, const uint8_t *d_main, int w, int
         // (the sub-plane forms take the inverse depths where the others take the
         // depths; grids and every other argument are the same)
         const float *const table = subplane ? R.d_inv : R.d_depths;
-        if (plan.wta == SGM_WTA_SUM_WIDE)
+        if (B.uniqueness != 0) {
+            // the same three forms and grids with the uniqueness test
+            int const window = B.uniqueness_window, uniq = B.uniqueness;
+            uint16_t *const s_out = B.want_sgm ? B.sgm : nullptr;
+            if (plan.wta == SGM_WTA_SUM_WIDE)
+                hipLaunchKernelGGL((subplane ? sgm_sum_wta_unique_kernel<64, true>
+                                             : sgm_sum_wta_unique_kernel<64, false>),
+                    dim3((unsigned)((npix * 64 + 255) / 256)), dim3(256), 0, stream,
+                    B.cost, B.delta, vol, d_main, table, npix, num_steps, window, uniq, d_depth,
+                    B.argmin, B.runner_up, s_out);
+            else if (plan.wta == SGM_WTA_SUM)
+                hipLaunchKernelGGL((subplane ? sgm_sum_wta_unique_kernel<32, true>
+                                             : sgm_sum_wta_unique_kernel<32, false>),
+                    dim3((unsigned)((npix * 32 + 255) / 256)), dim3(256), 0, stream,
+                    B.cost, B.delta, vol, d_main, table, npix, num_steps, window, uniq, d_depth,
+                    B.argmin, B.runner_up, s_out);
+            else
+                hipLaunchKernelGGL(subplane ? wta_rows_unique_kernel<true>
+                                            : wta_rows_unique_kernel<false>,
+                    dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, stream,
+                    B.sgm, d_main, table, npix, num_steps, window, uniq, d_depth, B.argmin,
+                    B.runner_up);
+        } else if (plan.wta == SGM_WTA_SUM_WIDE)
             hipLaunchKernelGGL(subplane ? sgm_sum_wta_wide_subplane_kernel
                                         : sgm_sum_wta_wide_kernel,
                 dim3((unsigned)((npix * 64 + 255) / 256)), dim3(256), 0, stream,
@@ -930,7 +1127,8 @@ sgm_run_impl(int device, const uint8_t *main_img, int w, int h,
     const uint8_t *neighbor_img, int nw, int nh, const float *M,
     const float *t, float min_depth, float max_depth, int num_steps,
     uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *depth,
-    int32_t *argmin, uint16_t *cost, uint16_t *sgm)
+    int32_t *argmin, uint16_t *cost, uint16_t *sgm,
+    const smvs_sgm_filter_options *filter = nullptr, uint16_t *runner_up = nullptr)
 {
     SMVS_REQUIRE(main_img && neighbor_img && M && t, "null argument");
     SMVS_REQUIRE(w > 10 && h > 8 && nw > 1 && nh > 1, "image too small");
@@ -948,6 +1146,12 @@ sgm_run_impl(int device, const uint8_t *main_img, int w, int h,
     SgmWorkspace B(&ws);
     B.prof = &prof;
     B.want_sgm = sgm != nullptr;
+    if (filter != nullptr) {
+        B.uniqueness = filter->uniqueness;
+        B.uniqueness_window = filter->uniqueness_window;
+    }
+    if (runner_up != nullptr && (rc = ws.ensure(WS_RUNNER_UP, npix, &B.runner_up)))
+        return rc;
     uint8_t *d_main = nullptr, *d_nbr = nullptr;
     float *d_depth = nullptr;
     if ((rc = ws.ensure(WS_MAIN, npix, &d_main)) || (rc = ws.ensure(WS_NBR0, nnpix, &d_nbr))
@@ -963,6 +1167,9 @@ sgm_run_impl(int device, const uint8_t *main_img, int w, int h,
         return rc;
     if (argmin != nullptr
         && (rc = ws.download(argmin, B.argmin, sizeof(int32_t) * npix)) != SMVS_OK)
+        return rc;
+    if (runner_up != nullptr
+        && (rc = ws.download(runner_up, B.runner_up, sizeof(uint16_t) * npix)) != SMVS_OK)
         return rc;
     if (sgm != nullptr
         && (rc = ws.download(sgm, B.sgm, sizeof(uint16_t) * vol)) != SMVS_OK)
@@ -1011,6 +1218,26 @@ smvs_sgm_run_opts(int device, const uint8_t *main_img, int w, int h,
     return sgm_run_impl(device, main_img, w, h, neighbor_img, nw, nh, M, t, min_depth,
         max_depth, num_steps, penalty1, penalty2, opts->p2_mode, opts->winner, depth,
         argmin, cost, sgm);
+}
+
+// smvs_sgm_run_opts with the uniqueness test in the WTA step
+extern "C" int
+smvs_sgm_run_filtered(int device, const uint8_t *main_img, int w, int h,
+    const uint8_t *neighbor_img, int nw, int nh, const float *M,
+    const float *t, float min_depth, float max_depth, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint16_t *cost,
+    uint16_t *sgm, uint16_t *runner_up)
+{
+    int rc;
+    if ((rc = check_sgm_winner(opts)) != SMVS_OK
+        || (rc = check_sgm_filter(filter, true)) != SMVS_OK)
+        return rc;
+    SMVS_REQUIRE(runner_up == nullptr || filter->uniqueness != 0,
+        "runner_up is an output of the uniqueness test (uniqueness > 0)");
+    return sgm_run_impl(device, main_img, w, h, neighbor_img, nw, nh, M, t, min_depth,
+        max_depth, num_steps, penalty1, penalty2, opts->p2_mode, opts->winner, depth,
+        argmin, cost, sgm, filter, runner_up);
 }
 
 extern "C" int

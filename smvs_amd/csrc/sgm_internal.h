@@ -1,7 +1,7 @@
 // What the translation units of the SGM front end share: sgm.hip (run_sgm:
 // census, warp, cost, WTA), sgm_paths.hip (its path aggregation), sgm_view.hip
 // (a view's front end), sgm_sweep.hip (the opt-in plane sweep over n
-// neighbours), image_prep.hip (a view's input image), bilateral.hip (the joint
+// neighbours), sgm_speckle.hip (the opt-in speckle removal), image_prep.hip (a view's input image), bilateral.hip (the joint
 // bilateral upsample).
 #pragma once
 
@@ -55,9 +55,10 @@ enum {
     WS_BIL_DM, WS_BIL_CI, WS_BIL_OUT,                                 // bilateral upsample
     WS_DELTA,                                                         // eight path-byte volumes
     WS_FWDN, WS_BWDN, WS_SUPPORT,                                     // consensus merge: n + n maps, support
-    WS_SWEEP                                                          // plane sweep: n cost volumes
+    WS_SWEEP,                                                         // plane sweep: n cost volumes
+    WS_SPECKLE, WS_RUNNER_UP                                          // filters: labels + counts, runner-up map
 };
-static_assert(WS_SWEEP < Workspace::SLOTS, "the last slot must exist in a Workspace");
+static_assert(WS_RUNNER_UP < Workspace::SLOTS, "the last slot must exist in a Workspace");
 
 // The largest plane count of a run: the key of the WTA kernels is
 // value * 256 + plane (one byte for the plane), and 64 lanes x 4 planes is one
@@ -82,7 +83,9 @@ static_assert(sgm_plane_count_ok(2) && sgm_plane_count_ok(127) && sgm_plane_coun
 // Work buffers of one run_sgm inside a pooled workspace; reused by the runs of
 // a view (the runs are ordered on the workspace's stream).  Every run has its
 // own depth table: SGM_MAX_PLANES depths, then as many inverse depths (the
-// sub-plane winner's).  MAX_RUNS: two runs per neighbour of the consensus front
+// sub-plane winner's).  The uniqueness test of a call (include/smvs_hip.h,
+// "uniqueness test") is the workspace's, since every run of a view makes it:
+// uniqueness == 0 launches the WTA kernels that know nothing of it.  MAX_RUNS: two runs per neighbour of the consensus front
 // end (64 KB of tables).
 struct SgmWorkspace {
     static constexpr int MAX_RUNS = 2 * SMVS_MAX_SUBS;
@@ -96,6 +99,8 @@ struct SgmWorkspace {
     int32_t *argmin = nullptr;
     int runs = 0;
     bool want_sgm = false;       // smvs_sgm_run hands the S volume to its caller
+    int uniqueness = 0, uniqueness_window = 1;
+    uint16_t *runner_up = nullptr;   // optional output of the uniqueness WTA kernels
     explicit SgmWorkspace(Workspace *w) : ws(w) {}
     // the largest penalty2 a step can use: the option itself, or in the adaptive
     // mode max(P2 / diff, P1 * 3 / 2) <= max(P2, P1 * 3 / 2)
@@ -139,6 +144,28 @@ int check_sgm_winner(const smvs_sgm_options *opts);
 // and min_agree in 1 .. SMVS_MAX_SUBS for the consensus (no device involved:
 // the entries call this first).  (sgm_view.hip)
 int check_sgm_view_options(const smvs_sgm_view_options *opts, int n_neighbors);
+// The filter options of the *_filtered entries: non-NULL, uniqueness in 0 .. 99,
+// the window in 1 .. 256, speckle_size >= 0, speckle_ratio in [0, 1] (a NaN is
+// none); run_entry: the speckle fields must be off (no device involved: the
+// entries call this first).  (sgm.hip)
+int check_sgm_filter(const smvs_sgm_filter_options *filter, bool run_entry);
+// Whether the speckle filter of the options runs at all (sizes 0 and 1 remove
+// nothing).
+inline bool
+sgm_speckle_on(const smvs_sgm_filter_options *filter)
+{
+    return filter != nullptr && filter->speckle_size > 1;
+}
+// speckle_size and speckle_ratio alone.  (sgm_speckle.hip)
+int check_sgm_speckle(int speckle_size, float speckle_ratio);
+// The two words per pixel the speckle kernels work in (slot WS_SPECKLE).
+int sgm_speckle_ensure(Workspace &ws, size_t npix, uint32_t **d_words);
+// Speckle removal of d_depth[w * h] into d_out (may be d_depth) on the
+// workspace's stream, four launches under timers of class SMVS_SGM_K_MERGE (three
+// for a map of one tile); want_size: the component sizes are left in
+// d_words[0 .. w * h).  hipGetLastError.  (sgm_speckle.hip)
+int sgm_launch_speckle(Workspace &ws, SgmProfile *prof, const float *d_depth, int w, int h,
+    int speckle_size, float speckle_ratio, uint32_t *d_words, float *d_out, bool want_size);
 
 // The plan of a run (sgm_path_plan.h) with this process's SMVS_SGM_PATHS: `wave`
 // asks for a wave per line, two planes per lane, up to 128 planes.

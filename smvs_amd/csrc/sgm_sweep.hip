@@ -278,7 +278,8 @@ sgm_sweep_impl(int device, const uint8_t *main_img, int w, int h, int main_chann
     const smvs_sgm_neighbor *neighbors, const int *neighbor_channels, int n_neighbors,
     int halvings, const float *range, int num_steps, uint16_t penalty1, uint16_t penalty2,
     const smvs_sgm_sweep_options *opts, float *depth, int32_t *argmin, uint8_t *support,
-    uint16_t *cost, uint16_t *sgm)
+    uint16_t *cost, uint16_t *sgm, const smvs_sgm_filter_options *filter = nullptr,
+    uint16_t *runner_up = nullptr)
 {
     int rc;
     if ((rc = check_sgm_sweep_options(opts, n_neighbors)) != SMVS_OK
@@ -313,6 +314,10 @@ sgm_sweep_impl(int device, const uint8_t *main_img, int w, int h, int main_chann
     SgmWorkspace B(&ws);
     B.prof = &prof;
     B.want_sgm = sgm != nullptr;
+    if (filter != nullptr) {
+        B.uniqueness = filter->uniqueness;
+        B.uniqueness_window = filter->uniqueness_window;
+    }
     uint8_t *d_main = nullptr, *d_nbr = nullptr, *d_tmp = nullptr;
     int mw = 0, mh = 0;
     if ((rc = sgm_prepare_image(ws, main_img, w, h, main_channels, halvings, WS_MAIN,
@@ -326,6 +331,10 @@ sgm_sweep_impl(int device, const uint8_t *main_img, int w, int h, int main_chann
     float *d_depth = nullptr;
     uint8_t *d_support = nullptr, *d_vols = nullptr;
     SgmRun R;
+    uint32_t *d_speckle = nullptr;
+    if ((sgm_speckle_on(filter) && (rc = sgm_speckle_ensure(ws, npix, &d_speckle)))
+        || (runner_up != nullptr && (rc = ws.ensure(WS_RUNNER_UP, npix, &B.runner_up))))
+        return rc;
     if ((rc = ws.ensure(WS_NBR0, max_rawpix, &d_nbr))
         || (max_tmp != 0 && (rc = ws.ensure(WS_RAW0, max_tmp, &d_tmp)))
         || (rc = ws.ensure(WS_FWD0, npix, &d_depth))
@@ -357,7 +366,15 @@ sgm_sweep_impl(int device, const uint8_t *main_img, int w, int h, int main_chann
             opts->support_cost, opts->min_support, d_support, d_depth);
     }
     SMVS_HIP_CHECK(hipGetLastError());
+    // (after the support test: the components are those of the map that leaves)
+    if (sgm_speckle_on(filter)
+        && (rc = sgm_launch_speckle(ws, &prof, d_depth, mw, mh, filter->speckle_size,
+                filter->speckle_ratio, d_speckle, d_depth, false)) != SMVS_OK)
+        return rc;
     if (depth != nullptr && (rc = ws.download(depth, d_depth, sizeof(float) * npix)) != SMVS_OK)
+        return rc;
+    if (runner_up != nullptr
+        && (rc = ws.download(runner_up, B.runner_up, sizeof(uint16_t) * npix)) != SMVS_OK)
         return rc;
     if (argmin != nullptr
         && (rc = ws.download(argmin, B.argmin, sizeof(int32_t) * npix)) != SMVS_OK)
@@ -398,6 +415,46 @@ smvs_sgm_sweep_for_view_raw(int device, const uint8_t *main_img, int w, int h, i
     return sgm_sweep_impl(device, main_img, w, h, channels, neighbors, neighbor_channels,
         n_neighbors, halvings, range, num_steps, penalty1, penalty2, opts, depth, nullptr,
         support, nullptr, nullptr);
+}
+
+// smvs_sgm_sweep_for_view with the uniqueness test in its one WTA step and the
+// speckle filter behind the support test
+extern "C" int
+smvs_sgm_sweep_for_view_filtered(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, const float *range, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_sweep_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint8_t *support,
+    uint16_t *cost, uint16_t *sgm, uint16_t *runner_up)
+{
+    if (int const rc = check_sgm_filter(filter, false); rc != SMVS_OK)
+        return rc;
+    SMVS_REQUIRE(runner_up == nullptr || filter->uniqueness != 0,
+        "runner_up is an output of the uniqueness test (uniqueness > 0)");
+    return sgm_sweep_impl(device, main_img, w, h, 1, neighbors, nullptr, n_neighbors, 0, range,
+        num_steps, penalty1, penalty2, opts, depth, argmin, support, cost, sgm, filter,
+        runner_up);
+}
+
+// smvs_sgm_sweep_for_view_raw with the filters
+extern "C" int
+smvs_sgm_sweep_for_view_raw_filtered(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_sweep_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, uint8_t *support)
+{
+    int rc;
+    if ((rc = check_sgm_filter(filter, false)) != SMVS_OK
+        || (rc = check_sgm_sweep_options(opts, n_neighbors)) != SMVS_OK)
+        return rc;
+    SMVS_REQUIRE(channels == 1 || channels == 3, "1 or 3 channels");
+    SMVS_REQUIRE(neighbor_channels != nullptr, "null argument");
+    for (int k = 0; k < n_neighbors; ++k)
+        SMVS_REQUIRE(neighbor_channels[k] == 1 || neighbor_channels[k] == 3,
+            "1 or 3 channels");
+    return sgm_sweep_impl(device, main_img, w, h, channels, neighbors, neighbor_channels,
+        n_neighbors, halvings, range, num_steps, penalty1, penalty2, opts, depth, nullptr,
+        support, nullptr, nullptr, filter, nullptr);
 }
 
 // the fold kernel alone, on the caller's bytes

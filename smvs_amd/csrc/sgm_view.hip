@@ -256,7 +256,8 @@ static int
 sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
     int main_channels, const smvs_sgm_neighbor *neighbors,
     const int *neighbor_channels, int n_neighbors, int halvings, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *depth)
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *depth,
+    const smvs_sgm_filter_options *filter = nullptr)
 {
     SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
         "unknown penalty2 mode");
@@ -286,6 +287,10 @@ sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
     SgmProfile prof;
     SgmWorkspace B(&ws);
     B.prof = &prof;
+    if (filter != nullptr) {
+        B.uniqueness = filter->uniqueness;
+        B.uniqueness_window = filter->uniqueness_window;
+    }
     // the SGM-scale images (every buffer before the first SGM launch: growing
     // one waits for the stream)
     uint8_t *d_main = nullptr, *d_nbr[2] = { nullptr, nullptr };
@@ -301,6 +306,9 @@ sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
             return rc;
     size_t const npix = (size_t)mw * mh;
     float *d_fwd[2] = { nullptr, nullptr }, *d_bwd = nullptr;
+    uint32_t *d_speckle = nullptr;
+    if (sgm_speckle_on(filter) && (rc = sgm_speckle_ensure(ws, npix, &d_speckle)))
+        return rc;
     size_t max_nnpix = 0;
     for (int k = 0; k < n_neighbors; ++k) {
         size_t const nnpix = (size_t)nw[k] * nh[k];
@@ -350,6 +358,10 @@ sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
             dim3(256), 0, stream, d_fwd[0], d_fwd[1], npix);
         SMVS_HIP_CHECK(hipGetLastError());
     }
+    if (sgm_speckle_on(filter)
+        && (rc = sgm_launch_speckle(ws, &prof, d_fwd[0], mw, mh, filter->speckle_size,
+                filter->speckle_ratio, d_speckle, d_fwd[0], false)) != SMVS_OK)
+        return rc;
     return ws.download(depth, d_fwd[0], sizeof(float) * npix);
 }
 
@@ -442,7 +454,8 @@ static int
 sgm_depth_for_view_consensus(int device, const uint8_t *main_img, int w, int h,
     int main_channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
     int n_neighbors, int halvings, int num_steps, uint16_t penalty1, uint16_t penalty2,
-    const smvs_sgm_view_options *opts, float *depth, float *checked, uint8_t *support)
+    const smvs_sgm_view_options *opts, float *depth, float *checked, uint8_t *support,
+    const smvs_sgm_filter_options *filter = nullptr)
 {
     int const p2_mode = opts->p2_mode, winner = opts->winner;
     int rc;
@@ -484,6 +497,10 @@ sgm_depth_for_view_consensus(int device, const uint8_t *main_img, int w, int h,
     SgmProfile prof;
     SgmWorkspace B(&ws);
     B.prof = &prof;
+    if (filter != nullptr) {
+        B.uniqueness = filter->uniqueness;
+        B.uniqueness_window = filter->uniqueness_window;
+    }
     uint8_t *d_main = nullptr, *d_nbr = nullptr, *d_tmp = nullptr;
     int mw = 0, mh = 0;
     if ((rc = sgm_prepare_image(ws, main_img, w, h, main_channels, halvings, WS_MAIN,
@@ -495,6 +512,9 @@ sgm_depth_for_view_consensus(int device, const uint8_t *main_img, int w, int h,
     // the maps, the volumes
     float *d_fwd = nullptr, *d_bwd = nullptr, *d_merged = nullptr;
     uint8_t *d_support = nullptr;
+    uint32_t *d_speckle = nullptr;
+    if (sgm_speckle_on(filter) && (rc = sgm_speckle_ensure(ws, npix, &d_speckle)))
+        return rc;
     if ((rc = ws.ensure(WS_NBR0, max_rawpix, &d_nbr))
         || (max_tmp != 0 && (rc = ws.ensure(WS_RAW0, max_tmp, &d_tmp)))
         || (rc = ws.ensure(WS_FWDN, npix * (size_t)n_neighbors, &d_fwd))
@@ -537,6 +557,12 @@ sgm_depth_for_view_consensus(int device, const uint8_t *main_img, int w, int h,
     A.agree_ratio = opts->agree_ratio;
     if ((rc = launch_check_merge(A, n_neighbors, &prof, stream)) != SMVS_OK)
         return rc;
+    // (checked and support are those of the merge: the speckle filter sees the
+    // merged map only)
+    if (sgm_speckle_on(filter)
+        && (rc = sgm_launch_speckle(ws, &prof, d_merged, mw, mh, filter->speckle_size,
+                filter->speckle_ratio, d_speckle, d_merged, false)) != SMVS_OK)
+        return rc;
     if (checked != nullptr
         && (rc = ws.download(checked, d_fwd, sizeof(float) * npix * (size_t)n_neighbors)))
         return rc;
@@ -545,11 +571,12 @@ sgm_depth_for_view_consensus(int device, const uint8_t *main_img, int w, int h,
     return ws.download(depth, d_merged, sizeof(float) * npix);
 }
 
-extern "C" int
-smvs_sgm_depth_for_view_merge(int device, const uint8_t *main_img, int w, int h,
+// (filter: null in the entries without the filters)
+static int
+sgm_depth_for_view_merge_impl(int device, const uint8_t *main_img, int w, int h,
     const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
     uint16_t penalty1, uint16_t penalty2, const smvs_sgm_view_options *opts,
-    float *depth, float *checked, uint8_t *support)
+    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support)
 {
     if (int const rc = check_sgm_view_options(opts, n_neighbors); rc != SMVS_OK)
         return rc;
@@ -558,18 +585,42 @@ smvs_sgm_depth_for_view_merge(int device, const uint8_t *main_img, int w, int h,
             "checked and support are outputs of the consensus merge");
         return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
             n_neighbors, 0, num_steps, penalty1, penalty2, opts->p2_mode, opts->winner,
-            depth);
+            depth, filter);
     }
     return sgm_depth_for_view_consensus(device, main_img, w, h, 1, neighbors, nullptr,
-        n_neighbors, 0, num_steps, penalty1, penalty2, opts, depth, checked, support);
+        n_neighbors, 0, num_steps, penalty1, penalty2, opts, depth, checked, support, filter);
 }
 
 extern "C" int
-smvs_sgm_depth_for_view_raw_merge(int device, const uint8_t *main_img, int w, int h,
+smvs_sgm_depth_for_view_merge(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_view_options *opts,
+    float *depth, float *checked, uint8_t *support)
+{
+    return sgm_depth_for_view_merge_impl(device, main_img, w, h, neighbors, n_neighbors,
+        num_steps, penalty1, penalty2, opts, nullptr, depth, checked, support);
+}
+
+// smvs_sgm_depth_for_view_merge with the uniqueness test in every run of the
+// view and the speckle filter on the merged map
+extern "C" int
+smvs_sgm_depth_for_view_filtered(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_view_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support)
+{
+    if (int const rc = check_sgm_filter(filter, false); rc != SMVS_OK)
+        return rc;
+    return sgm_depth_for_view_merge_impl(device, main_img, w, h, neighbors, n_neighbors,
+        num_steps, penalty1, penalty2, opts, filter, depth, checked, support);
+}
+
+static int
+sgm_depth_for_view_raw_merge_impl(int device, const uint8_t *main_img, int w, int h,
     int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
     int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
-    uint16_t penalty2, const smvs_sgm_view_options *opts, float *depth, float *checked,
-    uint8_t *support)
+    uint16_t penalty2, const smvs_sgm_view_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support)
 {
     if (int const rc = check_sgm_view_options(opts, n_neighbors); rc != SMVS_OK)
         return rc;
@@ -585,11 +636,38 @@ smvs_sgm_depth_for_view_raw_merge(int device, const uint8_t *main_img, int w, in
             "checked and support are outputs of the consensus merge");
         return sgm_depth_for_view_impl(device, main_img, w, h, channels, neighbors,
             neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2,
-            opts->p2_mode, opts->winner, depth);
+            opts->p2_mode, opts->winner, depth, filter);
     }
     return sgm_depth_for_view_consensus(device, main_img, w, h, channels, neighbors,
         neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, opts, depth,
-        checked, support);
+        checked, support, filter);
+}
+
+extern "C" int
+smvs_sgm_depth_for_view_raw_merge(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_view_options *opts, float *depth, float *checked,
+    uint8_t *support)
+{
+    return sgm_depth_for_view_raw_merge_impl(device, main_img, w, h, channels, neighbors,
+        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, opts, nullptr,
+        depth, checked, support);
+}
+
+// smvs_sgm_depth_for_view_raw_merge with the filters
+extern "C" int
+smvs_sgm_depth_for_view_raw_filtered(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_view_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support)
+{
+    if (int const rc = check_sgm_filter(filter, false); rc != SMVS_OK)
+        return rc;
+    return sgm_depth_for_view_raw_merge_impl(device, main_img, w, h, channels, neighbors,
+        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, opts, filter,
+        depth, checked, support);
 }
 
 // the fused kernel alone, on the caller's maps

@@ -457,15 +457,62 @@ def _sgm_view_options(adaptive_p2, subplane, consensus, agree_ratio, min_agree):
                           int(min_agree), float(agree_ratio))
 
 
+class SgmFilterOptions(C.Structure):
+    """smvs_sgm_filter_options of include/smvs_hip.h."""
+    _fields_ = [("uniqueness", C.c_int), ("uniqueness_window", C.c_int),
+                ("speckle_size", C.c_int), ("speckle_ratio", C.c_float)]
+
+
+# (uniqueness, uniqueness_window, speckle_size, speckle_ratio) of the Python
+# fronts: both filters off.  Defaults of a user option, untuned; nobody has
+# measured them on real scenes.
+SGM_FILTER_DEFAULTS = (0, 1, 0, 0.95)
+
+
+def _sgm_filter(uniqueness, uniqueness_window, speckle_size, speckle_ratio):
+    """The filter options, or None where they are the defaults (the entries
+    without the filters are called then)."""
+    if (uniqueness, uniqueness_window, speckle_size, speckle_ratio) == SGM_FILTER_DEFAULTS:
+        return None
+    return SgmFilterOptions(int(uniqueness), int(uniqueness_window), int(speckle_size),
+                            float(speckle_ratio))
+
+
+def sgm_filter_speckles(depth, speckle_size, speckle_ratio=0.95, device=0):
+    """smvs_sgm_filter_speckles: the speckle kernels of include/smvs_hip.h alone
+    (not in the reference).  depth (h, w) float; pixels > 0 are valid, two valid
+    4-neighbours are linked where min / max >= speckle_ratio, and every
+    component with fewer than speckle_size pixels is set to 0.  Returns
+    (out (h, w) f32, size (h, w) u32: the pixel count of each pixel's component,
+    0 for a pixel that is not valid)."""
+    lib = _capi.load()
+    depth = _f32(depth)
+    if depth.ndim != 2:
+        raise ValueError("depth: (h, w)")
+    h, w = depth.shape
+    out = np.zeros((h, w), dtype=np.float32)
+    size = np.zeros((h, w), dtype=np.uint32)
+    check(lib.smvs_sgm_filter_speckles(device, _p(depth, _fp), w, h, int(speckle_size),
+          C.c_float(speckle_ratio), _p(out, _fp), _p(size, C.POINTER(C.c_uint32))))
+    return out, size
+
+
 def sgm_run(main_img, neighbor_img, M, t, min_depth, max_depth, num_steps=128,
-            p1=6, p2=96, device=0, want_volumes=False, adaptive_p2=False, subplane=False):
+            p1=6, p2=96, device=0, want_volumes=False, adaptive_p2=False, subplane=False,
+            uniqueness=0, uniqueness_window=1):
     """SGMStereo::run_sgm on the device.  adaptive_p2: the path aggregation of
     the reference's build without SSE (lib/sgm_stereo.cc:310-346, penalty2
     adapted to the intensity step); off by default.
     subplane: the depth of the winning plane refined by the parabola through
     its aggregated cost and its two neighbours' (SMVS_SGM_WINNER_SUBPLANE of
     include/smvs_hip.h, not in the reference); argmin and the volumes are the
-    same; off by default."""
+    same; off by default.
+    uniqueness (0 .. 99, a percentage; 0 is off), uniqueness_window (1 .. 256
+    planes): the uniqueness test of include/smvs_hip.h (not in the reference): no
+    depth where a plane more than the window away from the winner has a sum r
+    with r * (100 - uniqueness) < S[winner] * 100.  With uniqueness > 0 and
+    want_volumes the dict also holds runner_up (h, w) u16.  (0, 1) are defaults
+    of a user option, untuned."""
     lib = _capi.load()
     main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
     neighbor_img = np.ascontiguousarray(neighbor_img, dtype=np.uint8)
@@ -476,6 +523,20 @@ def sgm_run(main_img, neighbor_img, M, t, min_depth, max_depth, num_steps=128,
     cost = np.zeros((h, w, num_steps), dtype=np.uint16) if want_volumes else None
     sgm = np.zeros((h, w, num_steps), dtype=np.uint16) if want_volumes else None
     opts = _sgm_options(adaptive_p2, subplane)
+    filt = _sgm_filter(uniqueness, uniqueness_window, *SGM_FILTER_DEFAULTS[2:])
+    if filt is not None:
+        runner = np.zeros((h, w), dtype=np.uint16) \
+            if want_volumes and filt.uniqueness != 0 else None
+        check(lib.smvs_sgm_run_filtered(device, _p(main_img, _u8p), w, h,
+              _p(neighbor_img, _u8p), nw, nh, _p(M, _fp), _p(t, _fp),
+              C.c_float(min_depth), C.c_float(max_depth), num_steps,
+              C.c_uint16(p1), C.c_uint16(p2), C.byref(opts), C.byref(filt),
+              _p(depth, _fp), _p(argmin, _i32p), _p(cost, _u16p), _p(sgm, _u16p),
+              _p(runner, _u16p)))
+        out = dict(depth=depth, argmin=argmin, cost=cost, sgm=sgm)
+        if runner is not None:
+            out["runner_up"] = runner
+        return out
     check(lib.smvs_sgm_run_opts(device, _p(main_img, _u8p), w, h,
           _p(neighbor_img, _u8p), nw, nh, _p(M, _fp), _p(t, _fp),
           C.c_float(min_depth), C.c_float(max_depth), num_steps,
@@ -528,7 +589,8 @@ class SgmNeighbor(C.Structure):
 
 def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0,
                        adaptive_p2=False, halvings=None, subplane=False,
-                       consensus=False, agree_ratio=0.95, min_agree=2, want_checked=False):
+                       consensus=False, agree_ratio=0.95, min_agree=2, want_checked=False,
+                       uniqueness=0, uniqueness_window=1, speckle_size=0, speckle_ratio=0.95):
     """reconstruct_sgm_depth_for_view on the device.  neighbors: list of dicts
     {image, M_fwd, t_fwd, M_bwd, t_bwd, range_main, range_neighbor} (SGM-scale
     u8 images, float reprojections).  adaptive_p2, subplane: as for sgm_run
@@ -544,19 +606,26 @@ def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0
     admits about two of 128 planes at the far end of a 3 .. 12 range; the
     left/right check uses 0.8); nobody has measured their effect on real scenes.
     want_checked (with consensus): returns a dict {depth, checked (n, h, w),
-    support (h, w) u8} instead of the depth map."""
+    support (h, w) u8} instead of the depth map.
+    uniqueness, uniqueness_window: the uniqueness test of sgm_run in every run of
+    the view.  speckle_size, speckle_ratio: the speckle removal of
+    sgm_filter_speckles on the merged map (sizes 0 and 1 are off).  Both are
+    filters of include/smvs_hip.h, not in the reference and off by default;
+    (0, 1, 0, 0.95) are defaults of a user option, untuned, and nobody has
+    measured them on real scenes."""
     lib = _capi.load()
     opts = _sgm_options(adaptive_p2, subplane)
     main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
     h, w = main_img.shape[:2]
-    if consensus or want_checked:
-        if not consensus:
+    filt = _sgm_filter(uniqueness, uniqueness_window, speckle_size, speckle_ratio)
+    if consensus or want_checked or filt is not None:
+        if want_checked and not consensus:
             raise ValueError("want_checked: the checked maps and the support are "
                              "outputs of the consensus merge")
         return _sgm_depth_for_view_merge(
             lib, main_img, neighbors, num_steps, p1, p2, device,
-            _sgm_view_options(adaptive_p2, subplane, True, agree_ratio, min_agree),
-            None if halvings is None else int(halvings), want_checked)
+            _sgm_view_options(adaptive_p2, subplane, consensus, agree_ratio, min_agree),
+            None if halvings is None else int(halvings), want_checked, filt)
     if halvings is not None:
         return _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device,
                                        opts, int(halvings))
@@ -612,8 +681,9 @@ def _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device,
 
 
 def _sgm_depth_for_view_merge(lib, main_img, neighbors, num_steps, p1, p2, device, vopts,
-                              halvings, want_checked):
-    """smvs_sgm_depth_for_view_merge (halvings None) / _raw_merge."""
+                              halvings, want_checked, filt=None):
+    """smvs_sgm_depth_for_view_merge (halvings None) / _raw_merge; with filt
+    (SgmFilterOptions) smvs_sgm_depth_for_view_filtered / _raw_filtered."""
     keep = []
     arr = _sgm_neighbors(neighbors, keep)
     n = len(neighbors)
@@ -627,15 +697,26 @@ def _sgm_depth_for_view_merge(lib, main_img, neighbors, num_steps, p1, p2, devic
     if halvings is None:
         if main_img.ndim != 2 or any(k.ndim != 2 for k in keep):
             raise ValueError("one-channel images at SGM scale (or pass halvings)")
-        check(lib.smvs_sgm_depth_for_view_merge(device, _p(main_img, _u8p), w, h, arr, n,
-              num_steps, C.c_uint16(p1), C.c_uint16(p2), C.byref(vopts), _p(depth, _fp),
-              _p(checked, _fp), _p(support, _u8p)))
+        if filt is not None:
+            check(lib.smvs_sgm_depth_for_view_filtered(device, _p(main_img, _u8p), w, h, arr,
+                  n, num_steps, C.c_uint16(p1), C.c_uint16(p2), C.byref(vopts),
+                  C.byref(filt), _p(depth, _fp), _p(checked, _fp), _p(support, _u8p)))
+        else:
+            check(lib.smvs_sgm_depth_for_view_merge(device, _p(main_img, _u8p), w, h, arr, n,
+                  num_steps, C.c_uint16(p1), C.c_uint16(p2), C.byref(vopts), _p(depth, _fp),
+                  _p(checked, _fp), _p(support, _u8p)))
     else:
         channels = 1 if main_img.ndim == 2 else main_img.shape[2]
         nch = (C.c_int * n)(*[1 if k.ndim == 2 else k.shape[2] for k in keep])
-        check(lib.smvs_sgm_depth_for_view_raw_merge(device, _p(main_img, _u8p), w, h,
-              channels, arr, nch, n, halvings, num_steps, C.c_uint16(p1), C.c_uint16(p2),
-              C.byref(vopts), _p(depth, _fp), _p(checked, _fp), _p(support, _u8p)))
+        if filt is not None:
+            check(lib.smvs_sgm_depth_for_view_raw_filtered(device, _p(main_img, _u8p), w, h,
+                  channels, arr, nch, n, halvings, num_steps, C.c_uint16(p1),
+                  C.c_uint16(p2), C.byref(vopts), C.byref(filt), _p(depth, _fp),
+                  _p(checked, _fp), _p(support, _u8p)))
+        else:
+            check(lib.smvs_sgm_depth_for_view_raw_merge(device, _p(main_img, _u8p), w, h,
+                  channels, arr, nch, n, halvings, num_steps, C.c_uint16(p1), C.c_uint16(p2),
+                  C.byref(vopts), _p(depth, _fp), _p(checked, _fp), _p(support, _u8p)))
     if want_checked:
         return dict(depth=depth, checked=checked, support=support)
     return depth
@@ -686,7 +767,8 @@ def sgm_sweep_defaults(n):
 
 def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2=96, device=0,
                        adaptive_p2=False, subplane=False, halvings=None, min_views=None,
-                       best_k=None, support_cost=20, min_support=None, want_volumes=False):
+                       best_k=None, support_cost=20, min_support=None, want_volumes=False,
+                       uniqueness=0, uniqueness_window=1, speckle_size=0, speckle_ratio=0.95):
     """The multi-neighbour plane sweep of include/smvs_hip.h (not in the
     reference; opt-in): one cost volume of the main view from all n = 1 .. 16
     neighbours -- per cell the rounded mean of the best_k smallest of the
@@ -700,10 +782,14 @@ def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2
     as for sgm_run.  min_views, best_k, min_support: None is min(2, n),
     (n + 1) // 2 and min(2, n); with support_cost = 20 these are defaults of a
     user option, untuned, and nobody has measured them on real scenes.
-    Returns dict(depth, argmin, support[, cost, sgm]); with halvings dict(depth,
-    support)."""
+    uniqueness, uniqueness_window, speckle_size, speckle_ratio: the two filters of
+    sgm_depth_for_view -- the uniqueness test in the sweep's one WTA step, the
+    speckle removal behind the support test; off by default, defaults untuned.
+    Returns dict(depth, argmin, support[, cost, sgm][, runner_up: with
+    want_volumes and uniqueness > 0]); with halvings dict(depth, support)."""
     lib = _capi.load()
     n = len(neighbors)
+    filt = _sgm_filter(uniqueness, uniqueness_window, speckle_size, speckle_ratio)
     d_views, d_k, _, d_support = sgm_sweep_defaults(n)
     opts = SgmSweepOptions(P2_ADAPTIVE if adaptive_p2 else P2_CONSTANT,
                            WINNER_SUBPLANE if subplane else WINNER_PLANE,
@@ -728,9 +814,15 @@ def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2
             ow, oh = (ow + 1) // 2, (oh + 1) // 2
         depth = np.zeros((oh, ow), dtype=np.float32)
         support = np.zeros((oh, ow), dtype=np.uint8)
-        check(lib.smvs_sgm_sweep_for_view_raw(device, _p(main_img, _u8p), w, h, channels, arr,
-              nch, n, int(halvings), rng, num_steps, C.c_uint16(p1), C.c_uint16(p2),
-              C.byref(opts), _p(depth, _fp), _p(support, _u8p)))
+        if filt is not None:
+            check(lib.smvs_sgm_sweep_for_view_raw_filtered(device, _p(main_img, _u8p), w, h,
+                  channels, arr, nch, n, int(halvings), rng, num_steps, C.c_uint16(p1),
+                  C.c_uint16(p2), C.byref(opts), C.byref(filt), _p(depth, _fp),
+                  _p(support, _u8p)))
+        else:
+            check(lib.smvs_sgm_sweep_for_view_raw(device, _p(main_img, _u8p), w, h, channels,
+                  arr, nch, n, int(halvings), rng, num_steps, C.c_uint16(p1), C.c_uint16(p2),
+                  C.byref(opts), _p(depth, _fp), _p(support, _u8p)))
         return dict(depth=depth, support=support)
     if main_img.ndim != 2 or any(k.ndim != 2 for k in keep):
         raise ValueError("one-channel images at SGM scale (or pass halvings)")
@@ -739,10 +831,21 @@ def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2
     support = np.zeros((h, w), dtype=np.uint8)
     cost = np.zeros((h, w, num_steps), dtype=np.uint16) if want_volumes else None
     sgm = np.zeros((h, w, num_steps), dtype=np.uint16) if want_volumes else None
-    check(lib.smvs_sgm_sweep_for_view(device, _p(main_img, _u8p), w, h, arr, n, rng, num_steps,
-          C.c_uint16(p1), C.c_uint16(p2), C.byref(opts), _p(depth, _fp), _p(argmin, _i32p),
-          _p(support, _u8p), _p(cost, _u16p), _p(sgm, _u16p)))
+    runner = None
+    if filt is not None:
+        if want_volumes and filt.uniqueness != 0:
+            runner = np.zeros((h, w), dtype=np.uint16)
+        check(lib.smvs_sgm_sweep_for_view_filtered(device, _p(main_img, _u8p), w, h, arr, n,
+              rng, num_steps, C.c_uint16(p1), C.c_uint16(p2), C.byref(opts), C.byref(filt),
+              _p(depth, _fp), _p(argmin, _i32p), _p(support, _u8p), _p(cost, _u16p),
+              _p(sgm, _u16p), _p(runner, _u16p)))
+    else:
+        check(lib.smvs_sgm_sweep_for_view(device, _p(main_img, _u8p), w, h, arr, n, rng,
+              num_steps, C.c_uint16(p1), C.c_uint16(p2), C.byref(opts), _p(depth, _fp),
+              _p(argmin, _i32p), _p(support, _u8p), _p(cost, _u16p), _p(sgm, _u16p)))
     out = dict(depth=depth, argmin=argmin, support=support)
+    if runner is not None:
+        out["runner_up"] = runner
     if want_volumes:
         out.update(cost=cost, sgm=sgm)
     return out

@@ -233,6 +233,15 @@ class SgmSweep(C.Structure):
                 ("support_cost", C.c_int), ("min_support", C.c_int)]
 
 
+class SgmFilter(C.Structure):
+    """smvs_host_sgm_filter of csrc/host/host_capi.h: ReconSettings::
+    sgm_uniqueness / sgm_uniqueness_window / sgm_speckle_size / sgm_speckle_ratio
+    (SGMStereo::Options::uniqueness / ...), passed next to the settings struct,
+    which keeps its layout."""
+    _fields_ = [("uniqueness", C.c_int), ("uniqueness_window", C.c_int),
+                ("speckle_size", C.c_int), ("speckle_ratio", C.c_float)]
+
+
 def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       regularization=1.0, output_scale=2, use_shading=False, use_sgm=True,
                       force_recon=False, force_sgm=False, sgm_range=(0.0, 0.0), sgm_scale=1,
@@ -243,7 +252,8 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       sgm_subplane=False, sgm_neighbors=2, sgm_consensus=False,
                       sgm_agree_ratio=0.95, sgm_min_agree=2, sgm_sweep=False,
                       sgm_sweep_min_views=-1, sgm_sweep_best_k=-1, sgm_sweep_support_cost=20,
-                      sgm_sweep_min_support=-1):
+                      sgm_sweep_min_support=-1, sgm_uniqueness=0, sgm_uniqueness_window=1,
+                      sgm_speckle_size=0, sgm_speckle_ratio=0.95):
     """smvsrecon's scene-level run (app/smvsrecon.cc:400-745) through
     smvs_amd::reconstruct_scene: returns (reconstructed ids, skipped, seconds)
     [, input scale used if `details`].  input_scale < 0 (the default, as
@@ -285,8 +295,19 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     n neighbours (min_views min(2, n), best_k (n + 1) // 2, min_support
     min(2, n)).  Off by default; these and 20 are defaults of a user option,
     untuned, and nobody has measured them on real scenes.  The reuse rule is that
+    of sgm_subplane (force_sgm).
+    sgm_uniqueness, sgm_uniqueness_window, sgm_speckle_size, sgm_speckle_ratio:
+    ReconSettings::sgm_uniqueness / ... -- the two filters of include/smvs_hip.h
+    in every view's SGM front end, whichever of the three it is: the uniqueness
+    test (0 .. 99, a percentage; 0 is off) over planes more than the window
+    (1 .. 256) from the winner in every run, and the removal of connected
+    components of fewer than sgm_speckle_size pixels (0 and 1 are off) from the
+    final map.  Off by default; (0, 1, 0, 0.95) are defaults of a user option,
+    untuned, and nobody has measured them on real scenes.  The reuse rule is that
     of sgm_subplane (force_sgm)."""
     lib = load()
+    filt = SgmFilter(int(sgm_uniqueness), int(sgm_uniqueness_window), int(sgm_speckle_size),
+                     float(sgm_speckle_ratio))
     sweep = SgmSweep(1 if sgm_sweep else 0, sgm_sweep_min_views, sgm_sweep_best_k,
                      sgm_sweep_support_cost, sgm_sweep_min_support)
     st = ReconSettings(image_embedding.encode(), regularization, output_scale,
@@ -301,12 +322,12 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                              C.byref(cap), None, None, None, None, None, None, None)
     out = np.zeros(max(cap.value, 1), np.int32)
     n = C.c_int(0); sk = C.c_int(0); secs = C.c_double(0.0); used = C.c_int(0)
-    rc = lib.smvs_host_reconstruct_scene_sweep(scene_dir.encode(), C.byref(st),
+    rc = lib.smvs_host_reconstruct_scene_filtered(scene_dir.encode(), C.byref(st),
         C.c_uint((1 if sgm_adaptive_penalty2 else 0) | (2 if device_input_scaling else 0)
                  | (8 if device_shading_prep else 0) | (16 if gamma_correction else 0)),
         C.c_int(sgm_num_steps), C.c_int(1 if sgm_subplane else 0),
         C.c_int(sgm_neighbors), C.c_int(1 if sgm_consensus else 0),
-        C.c_float(sgm_agree_ratio), C.c_int(sgm_min_agree), C.byref(sweep),
+        C.c_float(sgm_agree_ratio), C.c_int(sgm_min_agree), C.byref(sweep), C.byref(filt),
         ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), out.ctypes.data_as(_i32p),
         C.c_int(out.size), C.byref(n), C.byref(sk), C.byref(secs), C.byref(used))
@@ -453,7 +474,8 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
               adaptive_penalty2=False, num_steps=128, subplane=False, neighbors=2,
               consensus=False, agree_ratio=0.95, min_agree=2, sweep=False,
               sweep_min_views=-1, sweep_best_k=-1, sweep_support_cost=20,
-              sweep_min_support=-1):
+              sweep_min_support=-1, uniqueness=0, uniqueness_window=1, speckle_size=0,
+              speckle_ratio=0.95):
     """reconstruct_sgm_depth_for_view through the host mirror.
     adaptive_penalty2: SGMStereo::Options::adaptive_penalty2 (the reference's
     build without SSE, lib/sgm_stereo.cc:310-346); off by default.
@@ -476,9 +498,16 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
     neighbours instead of the runs and the merge; raises together with
     consensus.  -1: the default at n neighbours (min_views min(2, n), best_k
     (n + 1) // 2, min_support min(2, n)); untuned defaults of a user option,
-    nobody has measured them on real scenes.  Off by default."""
+    nobody has measured them on real scenes.  Off by default.
+    uniqueness, uniqueness_window, speckle_size, speckle_ratio:
+    SGMStereo::Options::uniqueness / ... -- the two filters of include/smvs_hip.h
+    for any of the three front ends (the uniqueness test in every run, the
+    speckle removal on the final map); off by default, (0, 1, 0, 0.95) are
+    untuned defaults of a user option."""
     lib = load()
     keep = []
+    filt = SgmFilter(int(uniqueness), int(uniqueness_window), int(speckle_size),
+                     float(speckle_ratio))
     sw = SgmSweep(1 if sweep else 0, sweep_min_views, sweep_best_k, sweep_support_cost,
                   sweep_min_support)
     main, subs, n_subs, b = _marshal(inputs, keep)
@@ -487,12 +516,12 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
         w, h = (w + 1) // 2, (h + 1) // 2
     out = np.zeros((h, w), dtype=np.float32)
     ow = C.c_int(0); oh = C.c_int(0)
-    rc = lib.smvs_host_sgm_depth_sweep(C.byref(main), subs, n_subs, C.byref(b),
+    rc = lib.smvs_host_sgm_depth_filtered(C.byref(main), subs, n_subs, C.byref(b),
         sgm_scale, C.c_float(min_depth), C.c_float(max_depth), device,
         C.c_int(1 if adaptive_penalty2 else 0), C.c_int(num_steps),
         C.c_int(1 if subplane else 0), C.c_int(neighbors), C.c_int(1 if consensus else 0),
-        C.c_float(agree_ratio), C.c_int(min_agree), C.byref(sw), out.ctypes.data_as(_fp),
-        C.byref(ow),
+        C.c_float(agree_ratio), C.c_int(min_agree), C.byref(sw), C.byref(filt),
+        out.ctypes.data_as(_fp), C.byref(ow),
         C.byref(oh))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())

@@ -19,7 +19,13 @@ bytes they move.  Without --consensus N is 1 or 2, the reference's merge.
 --neighbors N --sweep: the multi-neighbour plane sweep (smvs_sgm_sweep_for_view
 at the defaults for N neighbours) instead: the time per view, the fold kernel
 (reported as merge) with its (N + 1) volume bytes against the HBM read peak of
-profiles/r2_peaks.json, and the support kernel (reported as lr_check)."""
+profiles/r2_peaks.json, and the support kernel (reported as lr_check).
+--uniqueness U [--uniqueness-window W]: the uniqueness test of include/smvs_hip.h
+in the WTA step of every run (U in 1 .. 99; W planes, 1 without the flag);
+--speckle N [--speckle-ratio R] (with --neighbors): the speckle removal on the
+view's final map (components below N pixels; R 0.95 without the flag), its
+launches counted as merge, and the same launches alone on that map
+(smvs_sgm_filter_speckles) so that their time stands by itself."""
 import ctypes as C
 import json
 import os, sys, time
@@ -29,8 +35,8 @@ import smvs_amd
 from smvs_amd import synth, _capi
 
 
-def _arg(name, default):
-    return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+def _arg(name, default, kind=int):
+    return kind(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
 
 
 w, h = (1920, 1080) if "--small" not in sys.argv else (480, 270)
@@ -54,6 +60,12 @@ if adaptive:
 if subplane:
     kw["subplane"] = True
     print("sub-plane winner (SMVS_SGM_WINNER_SUBPLANE)")
+uniqueness = _arg("--uniqueness", 0)
+speckle = _arg("--speckle", 0)
+speckle_ratio = _arg("--speckle-ratio", 0.95, float)
+if uniqueness:
+    kw.update(uniqueness=uniqueness, uniqueness_window=_arg("--uniqueness-window", 1))
+    print("uniqueness test: %d %%, window %d" % (uniqueness, kw["uniqueness_window"]))
 
 if "--neighbors" in sys.argv:
     n = _arg("--neighbors", 2)
@@ -72,6 +84,10 @@ if "--neighbors" in sys.argv:
                         range_main=[2.0, 10.0], range_neighbor=[2.0, 10.0]))
     if consensus:
         kw["consensus"] = True
+    if speckle:
+        kw.update(speckle_size=speckle, speckle_ratio=speckle_ratio)
+        print("speckle removal: components below %d pixels, ratio %g (its launches count as "
+              "merge)" % (speckle, speckle_ratio))
     print("front end of a view, %d neighbours, %s" % (
         n, "plane sweep (min_views %d, best_k %d, support_cost %d, min_support %d)"
         % smvs_amd.device.sgm_sweep_defaults(n) if sweep
@@ -105,7 +121,29 @@ if "--neighbors" in sys.argv:
             print("kernel %-8s %9.1f us per launch, %9.1f us per view (%d launches per view)"
                   % (name, 1e3 * ms[i] / cnt[i], 1e3 * ms[i] / repeat, cnt[i] // repeat))
     npix = hw * hh
-    if sweep:
+    if speckle:
+        # the same launches alone, on the map as it is in front of the filter
+        plain = {k: v for k, v in kw.items() if not k.startswith("speckle")}
+        if sweep:
+            before = smvs_amd.sgm_sweep_for_view(small[0], nbs, (2.0, 10.0), D, 6, p2,
+                                                 **plain)["depth"]
+        else:
+            before = smvs_amd.sgm_depth_for_view(small[0], nbs, D, 6, p2, **plain)
+        smvs_amd.sgm_filter_speckles(before, speckle, speckle_ratio)
+        lib.smvs_sgm_profile(1, None, None)
+        for i in range(repeat):
+            after, size = smvs_amd.sgm_filter_speckles(before, speckle, speckle_ratio)
+        sms = (C.c_double * 8)()
+        scnt = (C.c_longlong * 8)()
+        lib.smvs_sgm_profile(0, sms, scnt)
+        print("speckle removal alone (%d launches): %.1f us per map; %d of %d valid pixels "
+              "removed, largest component %d" % (scnt[6] // repeat, 1e3 * sms[6] / repeat,
+                                                 int(((before > 0) & (after == 0)).sum()),
+                                                 int((before > 0).sum()), int(size.max())))
+    if speckle:
+        print("merge class: %d launches per view, the speckle launches among them: %.1f us per "
+              "view" % (cnt[6] // repeat, 1e3 * ms[6] / repeat))
+    elif sweep:
         # n volumes read, the folded one written
         nbytes = (n + 1) * npix * D
         us = 1e3 * ms[6] / max(cnt[6], 1)
@@ -115,7 +153,10 @@ if "--neighbors" in sys.argv:
         print("fold (one kernel): %.1f us per view, %.1f MB, %.2f TB/s, %.2f of the %.2f TB/s "
               "HBM read peak" % (us, nbytes / 1e6, nbytes / us / 1e6, nbytes / us / 1e6 / peak,
                                  peak))
+    if sweep:
         print("support (one kernel): %.1f us per view" % (1e3 * ms[5] / max(cnt[5], 1)))
+    elif speckle:
+        pass
     elif consensus:
         # n forward maps read, n scattered lookups, the merged map written
         nbytes = 4 * npix * (2 * n + 1)

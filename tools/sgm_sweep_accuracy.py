@@ -7,9 +7,16 @@ the consensus merge at n = 4 and 6 (0.95, 2) and the plane sweep at n = 2, 4
 and 6 (defaults for n), without and with the support test: the coverage (share
 of pixels with a depth) and, among those, the share whose depth lies within one
 plane of the true depth (both taken to the nearest plane in inverse depth; the
-truth is the mean of the four full-resolution pixels).
+truth is the mean of the four full-resolution pixels).  Behind those rows, for
+the sweep with the support test at n = 4 and 6: the same with the two filters of
+include/smvs_hip.h (the uniqueness test at 10 %, window 1, in front of the
+support test; the speckle removal at ratio 0.95, size 200, behind it), each alone
+and both, with the number of pixels whose depth is more than one plane off.
 
-    python tools/sgm_sweep_accuracy.py > profiles/sgm_sweep_synth_accuracy.txt
+    python tools/sgm_sweep_accuracy.py > profiles/sgm_filters_synth_accuracy.txt
+
+(profiles/sgm_sweep_synth_accuracy.txt holds the rows above the filters', from
+before there were filters.)
 
 Two synthetic scenes say nothing about real data."""
 import os
@@ -20,13 +27,16 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 
+import sgm_filter_ref as filter_ref
 import sgm_merge_ref as merge_ref
 import sgm_sweep_compose as compose
+import sgm_sweep_ref as sweep_ref
 from oracle import pyoracle as oracle
 from smvs_amd import host, synth
 
 D = 64
 N = 6
+UNIQUENESS, WINDOW, SPECKLE_SIZE, SPECKLE_RATIO = 10, 1, 200, 0.95
 
 
 def checked_maps(inputs, n):
@@ -53,6 +63,7 @@ def main():
     print("# (192 x 128), %d planes; CPU oracle + restatements (tools/sgm_sweep_accuracy.py)" % D)
     print("# coverage: pixels with a depth; within: of those, depth within one plane of the truth")
     print("# Synthetic: two rendered scenes say nothing about real data.")
+    filtered = []     # the rows of the filters, printed behind the others
     for kind in ("sphere", "plane"):
         inputs = synth.pipeline_inputs(kind, 384, 256, N, flen=1.2)
         truth = inputs["truth"].astype(np.float64)
@@ -65,11 +76,15 @@ def main():
             return np.abs(inv[None, None, :] - 1.0 / depth[:, :, None]).argmin(axis=2)
         true_plane = plane(truth)
 
-        def row(name, depth):
+        def row(name, depth, keep=None):
             valid = depth != 0
             near = np.abs(plane(np.where(valid, depth, 1.0).astype(np.float64)) - true_plane) <= 1
-            print("%-7s %-46s coverage %5.1f %%  within %5.1f %%"
-                  % (kind, name, 100.0 * valid.mean(), 100.0 * near[valid].mean()))
+            text = ("%-7s %-46s coverage %5.1f %%  within %5.1f %%"
+                    % (kind, name, 100.0 * valid.mean(), 100.0 * near[valid].mean()))
+            if keep is None:
+                print(text)
+            else:
+                keep.append(text + "  wrong %5d" % int((valid & ~near).sum()))
         print("# %s: depth range %.3f .. %.3f" % (kind, rng[0], rng[1]))
         stack = checked_maps(inputs, N)
         row("reference merge, n = 2", merge_ref.reference_merge(stack[0], stack[1]))
@@ -86,6 +101,25 @@ def main():
                 got["unchecked"])
             row("sweep n = %d, support (cost <= %d, >= %d)" % (n, support_cost, min_support),
                 got["depth"])
+            if n == 2:
+                continue
+            rejected = filter_ref.uniqueness(got["sgm"], got["argmin"], UNIQUENESS, WINDOW)[0]
+            unique = sweep_ref.apply_support(
+                filter_ref.apply_uniqueness(got["unchecked"], rejected), got["support"],
+                min_support)
+            row("sweep n = %d, support" % n, got["depth"], filtered)
+            row("sweep n = %d, support, uniqueness" % n, unique, filtered)
+            row("sweep n = %d, support, speckle" % n,
+                filter_ref.filter_speckles(got["depth"], SPECKLE_SIZE, SPECKLE_RATIO)[0],
+                filtered)
+            row("sweep n = %d, support, uniqueness, speckle" % n,
+                filter_ref.filter_speckles(unique, SPECKLE_SIZE, SPECKLE_RATIO)[0], filtered)
+    print("# the sweep with the filters: uniqueness %d %%, window %d; speckle ratio %g, size %d;"
+          % (UNIQUENESS, WINDOW, SPECKLE_RATIO, SPECKLE_SIZE))
+    print("# wrong: pixels with a depth more than one plane off.  Synthetic, as above: this says")
+    print("# nothing about real data.")
+    for text in filtered:
+        print(text)
 
 
 if __name__ == "__main__":
