@@ -1,12 +1,13 @@
-// Census / plane-sweep cost volume and WTA on gfx950 around the 8-path SGM
-// aggregation of sgm_paths.hip: one run_sgm, as smvs_sgm_run[_mode] and as
+// Census and plane-sweep cost volume on gfx950 in front of the 8-path SGM
+// aggregation of sgm_paths.hip and the winner-takes-all of sgm_wta.hip: one
+// run_sgm, as smvs_sgm_run[_mode] and as
 // sgm_run_device for a view's front end (sgm_view.hip); and the counters of the
 // front end's kernel timer.
 //
 // Replaces SGMStereo::run_sgm (reference: lib/sgm_stereo.cc:98-124):
 // census_filter (:126-148), warped_neighbors_for_depth (:150-190),
 // create_cost_volume (:192-244), aggregate_sgm_costs (:429-667,
-// sgm_launch_paths), depth_from_sgm_volume (:274-306).
+// sgm_launch_paths), depth_from_sgm_volume (:274-306, sgm_launch_wta).
 //
 // Integer path: results are bit-exact with the reference semantics.  The
 // float warp is evaluated in the reference's operation order with FMA
@@ -386,426 +387,6 @@ cost_tiled_kernel(const uint8_t *__restrict__ warped,
     }
 }
 
-// The end of both WTA kernels (sgm_stereo.cc:300-303): the winning plane is the
-// low byte of the (value, plane) key; no depth for the two nearest planes and
-// for dark pixels.
-__device__ __forceinline__ void
-wta_store(uint32_t key, size_t p, const uint8_t *__restrict__ main_img,
-    const float *__restrict__ depths, float *__restrict__ depth,
-    int32_t *__restrict__ argmin)
-{
-    int const min_index = (int)(key & 0xFFu);
-    if (argmin != nullptr)
-        argmin[p] = min_index;
-    if (depth != nullptr)
-        depth[p] = (min_index < 2 || main_img[p] < 25) ? 0.0f
-            : depths[min_index];
-}
-
-// The sub-plane winner (SMVS_SGM_WINNER_SUBPLANE; extends sgm_stereo.cc:300-303,
-// not in the reference): the parabola through the winner's S = b and its two
-// neighbours a, c moves the inverse depth towards the neighbouring plane on
-// the lower side, by at most half a plane.  inv[k] is the inverse depth of
-// plane k as sgm_stereo.cc:197-203 accumulates it (depths[k] == 1 / inv[k]), so
-// an offset of 0 gives depths[i] to the bit.  The caller has excluded i < 2.
-// float in the written order, contraction off, IEEE division.
-__device__ __forceinline__ float
-subplane_depth(int i, int a, int b, int c, const float *__restrict__ inv, int D)
-{
-#pragma clang fp contract(off)
-    int const den = a - 2 * b + c;   // >= 0: b is the minimum
-    float off = 0.0f;
-    if (i != D - 1 && den != 0)
-        off = (float)(a - c) / (float)(2 * den);   // in [-0.5, 0.5]
-    int const n = off > 0.0f ? i + 1 : i - 1;
-    float const base = inv[i];
-    float const step = fabsf(off) * (inv[n] - base);
-    return 1.0f / (base + step);
-}
-
-// wta_store for the sub-plane winner: argmin and the validity rule are
-// wta_store's; a and c are only looked at for a valid winner (c not at all in
-// the last plane).
-__device__ __forceinline__ void
-wta_store_subplane(int min_index, int a, int b, int c, size_t p,
-    const uint8_t *__restrict__ main_img, const float *__restrict__ inv, int D,
-    float *__restrict__ depth, int32_t *__restrict__ argmin)
-{
-    if (argmin != nullptr)
-        argmin[p] = min_index;
-    if (depth != nullptr)
-        depth[p] = (min_index < 2 || main_img[p] < 25) ? 0.0f
-            : subplane_depth(min_index, a, b, c, inv, D);
-}
-
-// WTA with 16 lanes per pixel (sgm_stereo.cc:274-306): lane sub reads planes
-// sub, sub + 16, ...; the first minimum wins through the (value, plane) key.
-__global__ void __launch_bounds__(256)
-wta_rows_kernel(const uint16_t *__restrict__ sgm,
-    const uint8_t *__restrict__ main_img, const float *__restrict__ depths,
-    size_t npix, int D, float *__restrict__ depth, int32_t *__restrict__ argmin)
-{
-    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
-    int const sub = threadIdx.x & 15;
-    uint32_t key = 0xFFFFFFFFu;
-    if (p < npix)
-        for (int d = sub; d < D; d += 16)
-            key = min(key, (uint32_t)sgm[p * D + d] * 256u + (uint32_t)d);
-    key = row_prefix_min_u32(key);
-    if (sub == 15 && p < npix)
-        wta_store(key, p, main_img, depths, depth, argmin);
-}
-
-// wta_rows_kernel with the sub-plane winner: S is in memory, lane 15 reads the
-// winner's two neighbours from it.
-__global__ void __launch_bounds__(256)
-wta_rows_subplane_kernel(const uint16_t *__restrict__ sgm,
-    const uint8_t *__restrict__ main_img, const float *__restrict__ inv,
-    size_t npix, int D, float *__restrict__ depth, int32_t *__restrict__ argmin)
-{
-    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
-    int const sub = threadIdx.x & 15;
-    uint32_t key = 0xFFFFFFFFu;
-    if (p < npix)
-        for (int d = sub; d < D; d += 16)
-            key = min(key, (uint32_t)sgm[p * D + d] * 256u + (uint32_t)d);
-    key = row_prefix_min_u32(key);
-    if (sub == 15 && p < npix) {
-        int const i = (int)(key & 0xFFu);
-        const uint16_t *s = sgm + p * D;
-        int const a = i >= 1 ? (int)s[i - 1] : 0;
-        int const c = i + 1 < D ? (int)s[i + 1] : 0;
-        wta_store_subplane(i, a, (int)(key >> 8), c, p, main_img, inv, D, depth, argmin);
-    }
-}
-
-// S = 8 C + the eight path bytes of the DELTA form, and the winner-takes-all of
-// wta_rows_kernel on it, 32 lanes per pixel with four planes each (one u32
-// per volume and lane).  S itself is only written when the caller wants the
-// volume (smvs_sgm_run's `sgm` output).
-__global__ void __launch_bounds__(256)
-sgm_sum_wta_kernel(const uint8_t *__restrict__ cost, const uint8_t *__restrict__ delta,
-    size_t vol, const uint8_t *__restrict__ main_img, const float *__restrict__ depths,
-    size_t npix, int D, float *__restrict__ depth, int32_t *__restrict__ argmin,
-    uint16_t *__restrict__ sgm_out)
-{
-    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 5;
-    int const sub = threadIdx.x & 31;
-    int const d0 = 4 * sub;
-    uint32_t key = 0xFFFFFFFFu;
-    if (p < npix && d0 < D) {
-        size_t const o = p * (size_t)D + d0;   // D % 4 == 0: aligned u32
-        uint32_t const c = *reinterpret_cast<const uint32_t *>(cost + o);
-        uint32_t e[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            e[k] = *reinterpret_cast<const uint32_t *>(delta + (size_t)k * vol + o);
-        uint32_t sv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint32_t sum = 8u * ((c >> (8 * j)) & 0xFFu);
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                sum += (e[k] >> (8 * j)) & 0xFFu;
-            sv[j] = sum & 0xFFFFu;
-            key = min(key, sv[j] * 256u + (uint32_t)(d0 + j));
-        }
-        if (sgm_out != nullptr) {
-            uint2 const packed = make_uint2(sv[0] | (sv[1] << 16), sv[2] | (sv[3] << 16));
-            *reinterpret_cast<uint2 *>(sgm_out + o) = packed;
-        }
-    }
-    // minimum over the 32 lanes of the pixel: inside the rows of 16 by DPP
-    // shifts, then across the two rows
-    key = row_prefix_min_u32(key);
-    // lanes 15 and 31 of the pixel hold the row minima
-    uint32_t const other = (uint32_t)__shfl_xor((int)key, 16);
-    key = min(key, other);
-    if (sub == 31 && p < npix)
-        wta_store(key, p, main_img, depths, depth, argmin);
-}
-
-// The same with 64 lanes per pixel, for the plane counts above 128: a wavefront
-// is one pixel, so the minimum over the four rows of 16 lanes is the wave's
-// (row_prefix_min_u32, then row_bcast:15 / row_bcast:31 -- wave_min_u32).  The
-// plane index uses the key's whole low byte at 256 planes; S < 2^16 keeps
-// value * 256 + plane inside 32 bits.
-__global__ void __launch_bounds__(256)
-sgm_sum_wta_wide_kernel(const uint8_t *__restrict__ cost, const uint8_t *__restrict__ delta,
-    size_t vol, const uint8_t *__restrict__ main_img, const float *__restrict__ depths,
-    size_t npix, int D, float *__restrict__ depth, int32_t *__restrict__ argmin,
-    uint16_t *__restrict__ sgm_out)
-{
-    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    int const sub = threadIdx.x & 63;
-    int const d0 = 4 * sub;
-    uint32_t key = 0xFFFFFFFFu;
-    if (p < npix && d0 < D) {
-        size_t const o = p * (size_t)D + d0;   // D % 4 == 0: aligned u32
-        uint32_t const c = *reinterpret_cast<const uint32_t *>(cost + o);
-        uint32_t e[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            e[k] = *reinterpret_cast<const uint32_t *>(delta + (size_t)k * vol + o);
-        uint32_t sv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint32_t sum = 8u * ((c >> (8 * j)) & 0xFFu);
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                sum += (e[k] >> (8 * j)) & 0xFFu;
-            sv[j] = sum & 0xFFFFu;
-            key = min(key, sv[j] * 256u + (uint32_t)(d0 + j));
-        }
-        if (sgm_out != nullptr) {
-            uint2 const packed = make_uint2(sv[0] | (sv[1] << 16), sv[2] | (sv[3] << 16));
-            *reinterpret_cast<uint2 *>(sgm_out + o) = packed;
-        }
-    }
-    key = wave_min_u32(key);
-    if (sub == 63 && p < npix)
-        wta_store(key, p, main_img, depths, depth, argmin);
-}
-
-// The two kernels above with the sub-plane winner (wta_store_subplane; `inv`:
-// the planes' inverse depths), LANES = 32 or 64 lanes per pixel.  S of the
-// winner's neighbours is in registers -- of the same lane, or for plane
-// 4 sub - 1 / 4 sub + 4 of the previous / next lane of the wave (wave_shr:1 /
-// wave_shl:1: every 16th plane crosses a row of 16 lanes).  The winner's key
-// goes to every lane of the pixel and the lane that holds the winning plane
-// stores.  Everything up to the minimum is the text of the kernels above, which
-// keep their instruction streams this way.
-template <int LANES>
-__device__ __forceinline__ void
-sum_wta_subplane(const uint8_t *__restrict__ cost, const uint8_t *__restrict__ delta,
-    size_t vol, const uint8_t *__restrict__ main_img, const float *__restrict__ inv,
-    size_t npix, int D, float *__restrict__ depth, int32_t *__restrict__ argmin,
-    uint16_t *__restrict__ sgm_out)
-{
-    static_assert(LANES == 32 || LANES == 64, "half a wavefront or a whole one per pixel");
-    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / LANES;
-    int const sub = threadIdx.x & (LANES - 1);
-    int const d0 = 4 * sub;
-    uint32_t key = 0xFFFFFFFFu;
-    uint32_t sv[4] = { 0u, 0u, 0u, 0u };
-    if (p < npix && d0 < D) {
-        size_t const o = p * (size_t)D + d0;   // D % 4 == 0: aligned u32
-        uint32_t const c = *reinterpret_cast<const uint32_t *>(cost + o);
-        uint32_t e[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            e[k] = *reinterpret_cast<const uint32_t *>(delta + (size_t)k * vol + o);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint32_t sum = 8u * ((c >> (8 * j)) & 0xFFu);
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                sum += (e[k] >> (8 * j)) & 0xFFu;
-            sv[j] = sum & 0xFFFFu;
-            key = min(key, sv[j] * 256u + (uint32_t)(d0 + j));
-        }
-        if (sgm_out != nullptr) {
-            uint2 const packed = make_uint2(sv[0] | (sv[1] << 16), sv[2] | (sv[3] << 16));
-            *reinterpret_cast<uint2 *>(sgm_out + o) = packed;
-        }
-    }
-    // (every lane of the wave takes part in the moves from here on)
-    uint32_t const left = lane_prev(sv[3], 0u);    // S of plane d0 - 1
-    uint32_t const right = lane_next(sv[0], 0u);   // S of plane d0 + 4
-    if constexpr (LANES == 32) {
-        key = row_prefix_min_u32(key);
-        uint32_t const other = (uint32_t)__shfl_xor((int)key, 16);
-        key = min(key, other);
-        // lanes 15 and 31 of the pixel both hold its minimum: to their rows
-        key = dpp_u32<dpp_row_newbcast(15)>(key, key);
-    } else {
-        key = wave_min_u32(key);
-    }
-    int const i = (int)(key & 0xFFu);
-    // (a pixel past the end has the key of all ones: plane 255, no lane of 32)
-    if ((i >> 2) == sub && p < npix) {
-        int const j = i & 3;
-        uint32_t const a = j == 0 ? left : (j == 1 ? sv[0] : (j == 2 ? sv[1] : sv[2]));
-        uint32_t const c = j == 0 ? sv[1] : (j == 1 ? sv[2] : (j == 2 ? sv[3] : right));
-        wta_store_subplane(i, (int)a, (int)(key >> 8), (int)c, p, main_img, inv, D, depth,
-            argmin);
-    }
-}
-
-__global__ void __launch_bounds__(256)
-sgm_sum_wta_subplane_kernel(const uint8_t *__restrict__ cost,
-    const uint8_t *__restrict__ delta, size_t vol, const uint8_t *__restrict__ main_img,
-    const float *__restrict__ inv, size_t npix, int D, float *__restrict__ depth,
-    int32_t *__restrict__ argmin, uint16_t *__restrict__ sgm_out)
-{
-    sum_wta_subplane<32>(cost, delta, vol, main_img, inv, npix, D, depth, argmin, sgm_out);
-}
-
-__global__ void __launch_bounds__(256)
-sgm_sum_wta_wide_subplane_kernel(const uint8_t *__restrict__ cost,
-    const uint8_t *__restrict__ delta, size_t vol, const uint8_t *__restrict__ main_img,
-    const float *__restrict__ inv, size_t npix, int D, float *__restrict__ depth,
-    int32_t *__restrict__ argmin, uint16_t *__restrict__ sgm_out)
-{
-    sum_wta_subplane<64>(cost, delta, vol, main_img, inv, npix, D, depth, argmin, sgm_out);
-}
-
-// ------------------------------------------------------- uniqueness test
-// The WTA kernels above with the uniqueness test of include/smvs_hip.h (not in
-// the reference): r, the smallest S among the planes more than `window` away
-// from the winner i, and no depth where r * (100 - uniqueness) < S[i] * 100.
-// New kernels: the six above know nothing of it.
-
-// Whether no plane of 0 .. D - 1 is more than `window` away from i.
-__device__ __forceinline__ bool
-no_competitor(int i, int window, int D)
-{
-    return i - window <= 0 && i + window >= D - 1;
-}
-
-// wta_store / wta_store_subplane with the test: r is the minimum over the
-// competitors (any value without one); table: the depths, or the inverse depths
-// for the sub-plane winner.  a and c as in wta_store_subplane.
-template <bool SUBPLANE>
-__device__ __forceinline__ void
-wta_store_unique(int i, int a, int b, int c, uint32_t r, int window, int uniqueness, size_t p,
-    const uint8_t *__restrict__ main_img, const float *__restrict__ table, int D,
-    float *__restrict__ depth, int32_t *__restrict__ argmin, uint16_t *__restrict__ runner_up)
-{
-    bool const none = no_competitor(i, window, D);
-    if (runner_up != nullptr)
-        runner_up[p] = (uint16_t)(none ? 65535u : r);
-    if (argmin != nullptr)
-        argmin[p] = i;
-    if (depth != nullptr) {
-        // (r <= 65535 and b <= 65535: 32 bits)
-        bool const rejected = !none && r * (uint32_t)(100 - uniqueness) < (uint32_t)b * 100u;
-        float v = 0.0f;
-        if (!(i < 2 || main_img[p] < 25 || rejected)) {
-            if constexpr (SUBPLANE)
-                v = subplane_depth(i, a, b, c, table, D);
-            else
-                v = table[i];
-        }
-        depth[p] = v;
-    }
-}
-
-// wta_rows_kernel / wta_rows_subplane_kernel with the test: S is in memory; the
-// winner goes to the 16 lanes of the pixel, each takes the minimum of its planes
-// outside the window (a second read of S, from the cache), a second prefix
-// minimum brings r to lane 15.
-template <bool SUBPLANE>
-__global__ void __launch_bounds__(256)
-wta_rows_unique_kernel(const uint16_t *__restrict__ sgm,
-    const uint8_t *__restrict__ main_img, const float *__restrict__ table,
-    size_t npix, int D, int window, int uniqueness, float *__restrict__ depth,
-    int32_t *__restrict__ argmin, uint16_t *__restrict__ runner_up)
-{
-    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
-    int const sub = threadIdx.x & 15;
-    uint32_t key = 0xFFFFFFFFu;
-    if (p < npix)
-        for (int d = sub; d < D; d += 16)
-            key = min(key, (uint32_t)sgm[p * D + d] * 256u + (uint32_t)d);
-    key = row_prefix_min_u32(key);
-    key = dpp_u32<dpp_row_newbcast(15)>(key, key);
-    int const i = (int)(key & 0xFFu);
-    uint32_t r = 0xFFFFFFFFu;
-    if (p < npix)
-        for (int d = sub; d < D; d += 16)
-            if (d < i - window || d > i + window)
-                r = min(r, (uint32_t)sgm[p * D + d]);
-    r = row_prefix_min_u32(r);
-    if (sub == 15 && p < npix) {
-        const uint16_t *s = sgm + p * D;
-        int const a = SUBPLANE && i >= 1 ? (int)s[i - 1] : 0;
-        int const c = SUBPLANE && i + 1 < D ? (int)s[i + 1] : 0;
-        wta_store_unique<SUBPLANE>(i, a, (int)(key >> 8), c, r, window, uniqueness, p, main_img,
-            table, D, depth, argmin, runner_up);
-    }
-}
-
-// sgm_sum_wta*_kernel with the test, LANES = 32 or 64 lanes per pixel: S is
-// formed in registers as in sum_wta_subplane, every lane learns the winner,
-// takes the minimum of its own four sums outside the window, and a second
-// cross-lane minimum gives r to every lane; the lane that holds the winning
-// plane stores.
-template <int LANES, bool SUBPLANE>
-__global__ void __launch_bounds__(256)
-sgm_sum_wta_unique_kernel(const uint8_t *__restrict__ cost, const uint8_t *__restrict__ delta,
-    size_t vol, const uint8_t *__restrict__ main_img, const float *__restrict__ table,
-    size_t npix, int D, int window, int uniqueness, float *__restrict__ depth,
-    int32_t *__restrict__ argmin, uint16_t *__restrict__ runner_up,
-    uint16_t *__restrict__ sgm_out)
-{
-    static_assert(LANES == 32 || LANES == 64, "half a wavefront or a whole one per pixel");
-    size_t const p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / LANES;
-    int const sub = threadIdx.x & (LANES - 1);
-    int const d0 = 4 * sub;
-    bool const mine = p < npix && d0 < D;
-    uint32_t key = 0xFFFFFFFFu;
-    uint32_t sv[4] = { 0u, 0u, 0u, 0u };
-    if (mine) {
-        size_t const o = p * (size_t)D + d0;   // D % 4 == 0: aligned u32
-        uint32_t const c = *reinterpret_cast<const uint32_t *>(cost + o);
-        uint32_t e[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            e[k] = *reinterpret_cast<const uint32_t *>(delta + (size_t)k * vol + o);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint32_t sum = 8u * ((c >> (8 * j)) & 0xFFu);
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                sum += (e[k] >> (8 * j)) & 0xFFu;
-            sv[j] = sum & 0xFFFFu;
-            key = min(key, sv[j] * 256u + (uint32_t)(d0 + j));
-        }
-        if (sgm_out != nullptr) {
-            uint2 const packed = make_uint2(sv[0] | (sv[1] << 16), sv[2] | (sv[3] << 16));
-            *reinterpret_cast<uint2 *>(sgm_out + o) = packed;
-        }
-    }
-    // (every lane of the wave takes part in the moves from here on)
-    uint32_t const left = lane_prev(sv[3], 0u);    // S of plane d0 - 1
-    uint32_t const right = lane_next(sv[0], 0u);   // S of plane d0 + 4
-    if constexpr (LANES == 32) {
-        key = row_prefix_min_u32(key);
-        uint32_t const other = (uint32_t)__shfl_xor((int)key, 16);
-        key = min(key, other);
-        key = dpp_u32<dpp_row_newbcast(15)>(key, key);
-    } else {
-        key = wave_min_u32(key);
-    }
-    int const i = (int)(key & 0xFFu);
-    uint32_t r = 0xFFFFFFFFu;
-    if (mine) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            int const d = d0 + j;
-            if (d < i - window || d > i + window)
-                r = min(r, sv[j]);
-        }
-    }
-    if constexpr (LANES == 32) {
-        r = row_prefix_min_u32(r);
-        uint32_t const other = (uint32_t)__shfl_xor((int)r, 16);
-        r = min(r, other);
-        r = dpp_u32<dpp_row_newbcast(15)>(r, r);
-    } else {
-        r = wave_min_u32(r);
-    }
-    // (a pixel past the end has the key of all ones: plane 255, no lane of 32)
-    if ((i >> 2) == sub && p < npix) {
-        int const j = i & 3;
-        uint32_t const a = j == 0 ? left : (j == 1 ? sv[0] : (j == 2 ? sv[1] : sv[2]));
-        uint32_t const c = j == 0 ? sv[1] : (j == 1 ? sv[2] : (j == 2 ? sv[3] : right));
-        wta_store_unique<SUBPLANE>(i, (int)a, (int)(key >> 8), (int)c, r, window, uniqueness, p,
-            main_img, table, D, depth, argmin, runner_up);
-    }
-}
-
 __global__ void __launch_bounds__(256)
 widen_u8_kernel(const uint8_t *__restrict__ src, uint16_t *__restrict__ dst,
     size_t n)
@@ -932,21 +513,22 @@ check_sgm_options(int num_steps, float min_depth, float max_depth,
 
 // (declared in sgm_internal.h)
 int
-sgm_run_plan(SgmWorkspace &B, int w, int h, float min_depth, float max_depth, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, SgmRun *R)
+sgm_run_plan(SgmWorkspace &B, int w, int h, float min_depth, float max_depth,
+    SgmRunParams const &P, SgmRun *R)
 {
-    int rc = check_sgm_options(num_steps, min_depth, max_depth, penalty1,
-        penalty2, p2_mode);
+    int const num_steps = P.num_steps;
+    int rc = check_sgm_options(num_steps, min_depth, max_depth, P.penalty1, P.penalty2,
+        P.p2_mode);
     if (rc != SMVS_OK)
         return rc;
-    SMVS_REQUIRE(winner == SMVS_SGM_WINNER_PLANE || winner == SMVS_SGM_WINNER_SUBPLANE,
+    SMVS_REQUIRE(P.winner == SMVS_SGM_WINNER_PLANE || P.winner == SMVS_SGM_WINNER_SUBPLANE,
         "unknown winner");
-    R->subplane = winner == SMVS_SGM_WINNER_SUBPLANE;
+    R->subplane = P.winner == SMVS_SGM_WINNER_SUBPLANE;
     SMVS_REQUIRE(B.runs < SgmWorkspace::MAX_RUNS, "too many runs on one workspace");
     size_t const npix = (size_t)w * h;
     // (what decides the form of the volumes: the largest penalty2 of a step)
     R->plan = sgm_path_plan_here(num_steps,
-        SgmWorkspace::largest_penalty2(penalty1, penalty2, p2_mode));
+        SgmWorkspace::largest_penalty2(P.penalty1, P.penalty2, P.p2_mode));
     if ((rc = B.ensure(npix, num_steps, R->plan)) != SMVS_OK)
         return rc;
     // sgm_stereo.cc:195-203: inverse-depth planes by repeated float addition;
@@ -1026,82 +608,29 @@ sgm_launch_warp_cost(SgmWorkspace &B, SgmRun const &R, int w, int h, const uint8
 // (declared in sgm_internal.h)
 int
 sgm_run_tail(SgmWorkspace &B, SgmRun const &R, const uint8_t *d_main, int w, int h,
-    int num_steps, uint16_t penalty1, uint16_t penalty2, int p2_mode, float *d_depth)
+    SgmRunParams const &P, float *d_depth)
 {
-    hipStream_t const stream = B.ws->stream;
-    size_t const npix = (size_t)w * h;
-    size_t const vol = npix * num_steps;
-    SgmPathPlan const &plan = R.plan;
-    bool const subplane = R.subplane;
-    int rc;
-    if ((rc = sgm_launch_paths(B, plan, d_main, w, h, num_steps, penalty1, penalty2,
-            p2_mode)) != SMVS_OK)
+    if (int const rc = sgm_launch_paths(B, R.plan, d_main, w, h, P); rc != SMVS_OK)
         return rc;
-    {
-        SgmKernelTimer timer(B.prof, stream, SMVS_SGM_K_WTA);
-        // (the sub-plane forms take the inverse depths where the others take the
-        // depths; grids and every other argument are the same)
-        const float *const table = subplane ? R.d_inv : R.d_depths;
-        if (B.uniqueness != 0) {
-            // the same three forms and grids with the uniqueness test
-            int const window = B.uniqueness_window, uniq = B.uniqueness;
-            uint16_t *const s_out = B.want_sgm ? B.sgm : nullptr;
-            if (plan.wta == SGM_WTA_SUM_WIDE)
-                hipLaunchKernelGGL((subplane ? sgm_sum_wta_unique_kernel<64, true>
-                                             : sgm_sum_wta_unique_kernel<64, false>),
-                    dim3((unsigned)((npix * 64 + 255) / 256)), dim3(256), 0, stream,
-                    B.cost, B.delta, vol, d_main, table, npix, num_steps, window, uniq, d_depth,
-                    B.argmin, B.runner_up, s_out);
-            else if (plan.wta == SGM_WTA_SUM)
-                hipLaunchKernelGGL((subplane ? sgm_sum_wta_unique_kernel<32, true>
-                                             : sgm_sum_wta_unique_kernel<32, false>),
-                    dim3((unsigned)((npix * 32 + 255) / 256)), dim3(256), 0, stream,
-                    B.cost, B.delta, vol, d_main, table, npix, num_steps, window, uniq, d_depth,
-                    B.argmin, B.runner_up, s_out);
-            else
-                hipLaunchKernelGGL(subplane ? wta_rows_unique_kernel<true>
-                                            : wta_rows_unique_kernel<false>,
-                    dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, stream,
-                    B.sgm, d_main, table, npix, num_steps, window, uniq, d_depth, B.argmin,
-                    B.runner_up);
-        } else if (plan.wta == SGM_WTA_SUM_WIDE)
-            hipLaunchKernelGGL(subplane ? sgm_sum_wta_wide_subplane_kernel
-                                        : sgm_sum_wta_wide_kernel,
-                dim3((unsigned)((npix * 64 + 255) / 256)), dim3(256), 0, stream,
-                B.cost, B.delta, vol, d_main, table, npix, num_steps, d_depth,
-                B.argmin, B.want_sgm ? B.sgm : nullptr);
-        else if (plan.wta == SGM_WTA_SUM)
-            hipLaunchKernelGGL(subplane ? sgm_sum_wta_subplane_kernel : sgm_sum_wta_kernel,
-                dim3((unsigned)((npix * 32 + 255) / 256)), dim3(256), 0, stream,
-                B.cost, B.delta, vol, d_main, table, npix, num_steps, d_depth,
-                B.argmin, B.want_sgm ? B.sgm : nullptr);
-        else
-            hipLaunchKernelGGL(subplane ? wta_rows_subplane_kernel : wta_rows_kernel,
-                dim3((unsigned)((npix * 16 + 255) / 256)), dim3(256), 0, stream,
-                B.sgm, d_main, table, npix, num_steps, d_depth,
-                B.argmin);
-    }
-    SMVS_HIP_CHECK(hipGetLastError());
-    return SMVS_OK;
+    // (ends with hipGetLastError)
+    return sgm_launch_wta(B, R, d_main, (size_t)w * h, P.num_steps, d_depth);
 }
 
 // (declared in sgm_internal.h)
 int
-sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
-    int w, int h, const uint8_t *d_nbr, int nw, int nh, const float *M,
-    const float *t, float min_depth, float max_depth, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *d_depth)
+sgm_run_device(SgmWorkspace &B, const uint8_t *d_main, int w, int h, const uint8_t *d_nbr,
+    int nw, int nh, const float *M, const float *t, float min_depth, float max_depth,
+    SgmRunParams const &P, float *d_depth)
 {
     SgmRun R;
-    int rc = sgm_run_plan(B, w, h, min_depth, max_depth, num_steps, penalty1, penalty2,
-        p2_mode, winner, &R);
+    int rc = sgm_run_plan(B, w, h, min_depth, max_depth, P, &R);
     if (rc != SMVS_OK)
         return rc;
     sgm_launch_census(B, d_main, w, h);
-    if ((rc = sgm_launch_warp_cost(B, R, w, h, d_nbr, nw, nh, M, t, num_steps, B.cost))
+    if ((rc = sgm_launch_warp_cost(B, R, w, h, d_nbr, nw, nh, M, t, P.num_steps, B.cost))
         != SMVS_OK)
         return rc;
-    return sgm_run_tail(B, R, d_main, w, h, num_steps, penalty1, penalty2, p2_mode, d_depth);
+    return sgm_run_tail(B, R, d_main, w, h, P, d_depth);
 }
 
 // (declared in sgm_internal.h)
@@ -1146,10 +675,7 @@ sgm_run_impl(int device, const uint8_t *main_img, int w, int h,
     SgmWorkspace B(&ws);
     B.prof = &prof;
     B.want_sgm = sgm != nullptr;
-    if (filter != nullptr) {
-        B.uniqueness = filter->uniqueness;
-        B.uniqueness_window = filter->uniqueness_window;
-    }
+    B.set_filter(filter);
     if (runner_up != nullptr && (rc = ws.ensure(WS_RUNNER_UP, npix, &B.runner_up)))
         return rc;
     uint8_t *d_main = nullptr, *d_nbr = nullptr;
@@ -1159,8 +685,9 @@ sgm_run_impl(int device, const uint8_t *main_img, int w, int h,
         || (rc = ws.upload(d_main, main_img, npix))
         || (rc = ws.upload(d_nbr, neighbor_img, nnpix)))
         return rc;
-    if ((rc = sgm_run_device(B, d_main, w, h, d_nbr, nw, nh, M, t, min_depth,
-            max_depth, num_steps, penalty1, penalty2, p2_mode, winner, d_depth)) != SMVS_OK)
+    SgmRunParams const P = { num_steps, penalty1, penalty2, p2_mode, winner };
+    if ((rc = sgm_run_device(B, d_main, w, h, d_nbr, nw, nh, M, t, min_depth, max_depth, P,
+            d_depth)) != SMVS_OK)
         return rc;
     if (depth != nullptr
         && (rc = ws.download(depth, d_depth, sizeof(float) * npix)) != SMVS_OK)

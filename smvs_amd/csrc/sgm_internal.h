@@ -1,7 +1,8 @@
 // What the translation units of the SGM front end share: sgm.hip (run_sgm:
-// census, warp, cost, WTA), sgm_paths.hip (its path aggregation), sgm_view.hip
-// (a view's front end), sgm_sweep.hip (the opt-in plane sweep over n
-// neighbours), sgm_speckle.hip (the opt-in speckle removal), image_prep.hip (a view's input image), bilateral.hip (the joint
+// census, warp, cost), sgm_paths.hip (its path aggregation), sgm_wta.hip (its
+// winner-takes-all), sgm_view.hip (a view's front end), sgm_sweep.hip (the
+// opt-in plane sweep over n neighbours), sgm_speckle.hip (the opt-in speckle
+// removal), image_prep.hip (a view's input image), bilateral.hip (the joint
 // bilateral upsample).
 #pragma once
 
@@ -85,8 +86,8 @@ static_assert(sgm_plane_count_ok(2) && sgm_plane_count_ok(127) && sgm_plane_coun
 // own depth table: SGM_MAX_PLANES depths, then as many inverse depths (the
 // sub-plane winner's).  The uniqueness test of a call (include/smvs_hip.h,
 // "uniqueness test") is the workspace's, since every run of a view makes it:
-// uniqueness == 0 launches the WTA kernels that know nothing of it.  MAX_RUNS: two runs per neighbour of the consensus front
-// end (64 KB of tables).
+// uniqueness == 0 launches the WTA kernels without it.  MAX_RUNS: two runs per
+// neighbour of the consensus front end (64 KB of tables).
 struct SgmWorkspace {
     static constexpr int MAX_RUNS = 2 * SMVS_MAX_SUBS;
     Workspace *ws;
@@ -102,6 +103,12 @@ struct SgmWorkspace {
     int uniqueness = 0, uniqueness_window = 1;
     uint16_t *runner_up = nullptr;   // optional output of the uniqueness WTA kernels
     explicit SgmWorkspace(Workspace *w) : ws(w) {}
+    // the uniqueness test of a *_filtered entry's options; null: off
+    void set_filter(const smvs_sgm_filter_options *filter)
+    {
+        uniqueness = filter != nullptr ? filter->uniqueness : 0;
+        uniqueness_window = filter != nullptr ? filter->uniqueness_window : 1;
+    }
     // the largest penalty2 a step can use: the option itself, or in the adaptive
     // mode max(P2 / diff, P1 * 3 / 2) <= max(P2, P1 * 3 / 2)
     static unsigned largest_penalty2(unsigned penalty1, unsigned penalty2, int p2_mode)
@@ -167,6 +174,15 @@ int sgm_speckle_ensure(Workspace &ws, size_t npix, uint32_t **d_words);
 int sgm_launch_speckle(Workspace &ws, SgmProfile *prof, const float *d_depth, int w, int h,
     int speckle_size, float speckle_ratio, uint32_t *d_words, float *d_out, bool want_size);
 
+// What a run is asked for besides its images and depth range: the options of
+// SGMStereo (num_steps, the penalties), smvs_sgm_p2_mode and smvs_sgm_winner.
+// Each entry fills one and every stage of the run reads it.
+struct SgmRunParams {
+    int num_steps;
+    uint16_t penalty1, penalty2;
+    int p2_mode, winner;
+};
+
 // The plan of a run (sgm_path_plan.h) with this process's SMVS_SGM_PATHS: `wave`
 // asks for a wave per line, two planes per lane, up to 128 planes.
 // (sgm_paths.hip)
@@ -178,7 +194,7 @@ SgmPathPlan sgm_path_plan_here(int num_steps, unsigned largest_p2);
 // SMVS_SGM_K_PATHS, hipGetLastError.  The path bytes go to B.delta or the sums
 // to B.sgm, as plan.delta says.  (sgm_paths.hip)
 int sgm_launch_paths(SgmWorkspace &B, SgmPathPlan const &plan, const uint8_t *d_main,
-    int w, int h, int num_steps, unsigned p1, unsigned p2, int p2_mode);
+    int w, int h, SgmRunParams const &P);
 
 // The stages of a run, which sgm_run_device and the plane sweep of
 // sgm_sweep.hip share.  (sgm.hip)
@@ -190,7 +206,7 @@ struct SgmRun {
 // The checks of a run, its plan, B's buffers for w x h x num_steps and the run's
 // depth table (sgm_stereo.cc:195-203) uploaded.
 int sgm_run_plan(SgmWorkspace &B, int w, int h, float min_depth, float max_depth,
-    int num_steps, uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, SgmRun *R);
+    SgmRunParams const &P, SgmRun *R);
 // census_filter of the main image into B.census
 void sgm_launch_census(SgmWorkspace &B, const uint8_t *d_main, int w, int h);
 // warped_neighbors_for_depth and create_cost_volume for one neighbour: through
@@ -198,20 +214,24 @@ void sgm_launch_census(SgmWorkspace &B, const uint8_t *d_main, int w, int h);
 int sgm_launch_warp_cost(SgmWorkspace &B, SgmRun const &R, int w, int h,
     const uint8_t *d_nbr, int nw, int nh, const float *M, const float *t, int num_steps,
     uint8_t *d_cost);
-// sgm_launch_paths on B.cost and the WTA kernel of the plan: d_depth, B.argmin
-// (and B.sgm with B.want_sgm)
+// depth_from_sgm_volume (sgm_stereo.cc:274-306) behind sgm_launch_paths: the
+// WTA kernel of (R.plan.wta, R.subplane, B.uniqueness != 0) under a timer of
+// class SMVS_SGM_K_WTA, hipGetLastError.  d_depth, B.argmin (B.sgm with
+// B.want_sgm, B.runner_up where set).  (sgm_wta.hip)
+int sgm_launch_wta(SgmWorkspace &B, SgmRun const &R, const uint8_t *d_main, size_t npix,
+    int num_steps, float *d_depth);
+// sgm_launch_paths on B.cost, then sgm_launch_wta
 int sgm_run_tail(SgmWorkspace &B, SgmRun const &R, const uint8_t *d_main, int w, int h,
-    int num_steps, uint16_t penalty1, uint16_t penalty2, int p2_mode, float *d_depth);
+    SgmRunParams const &P, float *d_depth);
 // a u8 cost volume on the device, widened to u16, to the host (slot WS_COST16)
 int sgm_download_cost16(Workspace &ws, const uint8_t *d_cost, size_t vol, uint16_t *cost);
 
 // SGMStereo::run_sgm (sgm_stereo.cc:98-124) on device images; the depth map
-// (and optionally argmin) stay on the device.  winner: smvs_sgm_winner.
-// Asynchronous on the workspace's stream.  (sgm.hip)
-int sgm_run_device(SgmWorkspace &B, const uint8_t *d_main,
-    int w, int h, const uint8_t *d_nbr, int nw, int nh, const float *M,
-    const float *t, float min_depth, float max_depth, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *d_depth);
+// (and optionally argmin) stay on the device.  Asynchronous on the workspace's
+// stream.  (sgm.hip)
+int sgm_run_device(SgmWorkspace &B, const uint8_t *d_main, int w, int h, const uint8_t *d_nbr,
+    int nw, int nh, const float *M, const float *t, float min_depth, float max_depth,
+    SgmRunParams const &P, float *d_depth);
 
 // One view's SGM input image on the device: upload (raw: interleaved u8 of
 // `channels`; otherwise already at SGM scale, one channel), desaturate and

@@ -1,5 +1,5 @@
 // Which form of the SGM path aggregation (sgm_paths.hip) a run takes, what it
-// needs of the workspace and which WTA kernel (sgm.hip) follows.  Host
+// needs of the workspace and which WTA kernel (sgm_wta.hip) follows.  Host
 // arithmetic only: no HIP, no smvs_ctx.  The rule exists here and nowhere else.
 #pragma once
 

@@ -939,20 +939,20 @@ static_assert(SGM_MAX_PLANES == 256, "sgm_path_plan's `full` of the wide form");
 // (declared in sgm_internal.h)
 int
 sgm_launch_paths(SgmWorkspace &B, SgmPathPlan const &plan, const uint8_t *d_main,
-    int w, int h, int num_steps, unsigned p1, unsigned p2, int p2_mode)
+    int w, int h, SgmRunParams const &R)
 {
     hipStream_t const stream = B.ws->stream;
-    size_t const vol = (size_t)w * h * num_steps;
-    bool const adapt = p2_mode == SMVS_SGM_P2_ADAPTIVE;
+    size_t const vol = (size_t)w * h * R.num_steps;
+    bool const adapt = R.p2_mode == SMVS_SGM_P2_ADAPTIVE;
     PathArgs P;
     P.cost = B.cost;
     P.sgm = B.sgm;
     P.w = w;
     P.h = h;
-    P.D = num_steps;
+    P.D = R.num_steps;
     P.dx = P.dy = 0;
-    P.p1 = p1;
-    P.p2 = p2;
+    P.p1 = R.penalty1;
+    P.p2 = R.penalty2;
     P.first = 0;
     P.last = 0;
     P.delta = B.delta;

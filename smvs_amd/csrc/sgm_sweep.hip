@@ -3,7 +3,7 @@
 // definition): the cost volumes of the main view against n neighbours over the
 // main view's planes, folded into one volume, one path aggregation, one winner,
 // and the support of the winner among the neighbours.  The census, warp, cost,
-// path and WTA kernels are those of a run (sgm.hip, sgm_paths.hip); the fold and
+// path and WTA kernels are those of a run (sgm.hip, sgm_paths.hip, sgm_wta.hip); the fold and
 // the support kernel are here.
 #include "sgm_internal.h"
 
@@ -314,10 +314,7 @@ sgm_sweep_impl(int device, const uint8_t *main_img, int w, int h, int main_chann
     SgmWorkspace B(&ws);
     B.prof = &prof;
     B.want_sgm = sgm != nullptr;
-    if (filter != nullptr) {
-        B.uniqueness = filter->uniqueness;
-        B.uniqueness_window = filter->uniqueness_window;
-    }
+    B.set_filter(filter);
     uint8_t *d_main = nullptr, *d_nbr = nullptr, *d_tmp = nullptr;
     int mw = 0, mh = 0;
     if ((rc = sgm_prepare_image(ws, main_img, w, h, main_channels, halvings, WS_MAIN,
@@ -331,6 +328,7 @@ sgm_sweep_impl(int device, const uint8_t *main_img, int w, int h, int main_chann
     float *d_depth = nullptr;
     uint8_t *d_support = nullptr, *d_vols = nullptr;
     SgmRun R;
+    SgmRunParams const P = { num_steps, penalty1, penalty2, opts->p2_mode, opts->winner };
     uint32_t *d_speckle = nullptr;
     if ((sgm_speckle_on(filter) && (rc = sgm_speckle_ensure(ws, npix, &d_speckle)))
         || (runner_up != nullptr && (rc = ws.ensure(WS_RUNNER_UP, npix, &B.runner_up))))
@@ -340,8 +338,7 @@ sgm_sweep_impl(int device, const uint8_t *main_img, int w, int h, int main_chann
         || (rc = ws.ensure(WS_FWD0, npix, &d_depth))
         || (rc = ws.ensure(WS_SUPPORT, npix, &d_support))
         || (rc = ws.ensure(WS_SWEEP, stride * (size_t)n_neighbors, &d_vols))
-        || (rc = sgm_run_plan(B, mw, mh, range[0], range[1], num_steps, penalty1, penalty2,
-                opts->p2_mode, opts->winner, &R)))
+        || (rc = sgm_run_plan(B, mw, mh, range[0], range[1], P, &R)))
         return rc;
     sgm_launch_census(B, d_main, mw, mh);
     for (int k = 0; k < n_neighbors; ++k) {
@@ -356,8 +353,7 @@ sgm_sweep_impl(int device, const uint8_t *main_img, int w, int h, int main_chann
     }
     if ((rc = launch_fold(d_vols, stride, vol, B.cost, n_neighbors, opts->best_k,
              opts->min_views, &prof, stream)) != SMVS_OK
-        || (rc = sgm_run_tail(B, R, d_main, mw, mh, num_steps, penalty1, penalty2,
-                opts->p2_mode, d_depth)) != SMVS_OK)
+        || (rc = sgm_run_tail(B, R, d_main, mw, mh, P, d_depth)) != SMVS_OK)
         return rc;
     {
         SgmKernelTimer timer(&prof, stream, SMVS_SGM_K_LR_CHECK);

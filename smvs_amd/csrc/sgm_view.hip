@@ -279,6 +279,7 @@ sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
         SMVS_REQUIRE(neighbors[k].image && (neighbors[k].width >> halvings) > 10
             && (neighbors[k].height >> halvings) > 8, "bad neighbour image");
     int rc;
+    SgmRunParams const P = { num_steps, penalty1, penalty2, p2_mode, winner };
     WorkspaceLease lease(device);
     if (lease.w == nullptr)
         return SMVS_ERR_HIP;
@@ -287,10 +288,7 @@ sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
     SgmProfile prof;
     SgmWorkspace B(&ws);
     B.prof = &prof;
-    if (filter != nullptr) {
-        B.uniqueness = filter->uniqueness;
-        B.uniqueness_window = filter->uniqueness_window;
-    }
+    B.set_filter(filter);
     // the SGM-scale images (every buffer before the first SGM launch: growing
     // one waits for the stream)
     uint8_t *d_main = nullptr, *d_nbr[2] = { nullptr, nullptr };
@@ -326,12 +324,11 @@ sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
         // SGMStereo::reconstruct, sgm_stereo.cc:46-62: main -> neighbour,
         // then neighbour -> main with the neighbour's own depth range
         if ((rc = sgm_run_device(B, d_main, mw, mh, d_nbr[k], nw[k], nh[k],
-                N.M_fwd, N.t_fwd, N.range_main[0], N.range_main[1], num_steps,
-                penalty1, penalty2, p2_mode, winner, d_fwd[k])) != SMVS_OK)
+                N.M_fwd, N.t_fwd, N.range_main[0], N.range_main[1], P, d_fwd[k])) != SMVS_OK)
             return rc;
         if ((rc = sgm_run_device(B, d_nbr[k], nw[k], nh[k], d_main, mw, mh,
-                N.M_bwd, N.t_bwd, N.range_neighbor[0], N.range_neighbor[1],
-                num_steps, penalty1, penalty2, p2_mode, winner, d_bwd)) != SMVS_OK)
+                N.M_bwd, N.t_bwd, N.range_neighbor[0], N.range_neighbor[1], P, d_bwd))
+            != SMVS_OK)
             return rc;
         LrArgs L;
         L.d_main = d_fwd[k];
@@ -457,7 +454,8 @@ sgm_depth_for_view_consensus(int device, const uint8_t *main_img, int w, int h,
     const smvs_sgm_view_options *opts, float *depth, float *checked, uint8_t *support,
     const smvs_sgm_filter_options *filter = nullptr)
 {
-    int const p2_mode = opts->p2_mode, winner = opts->winner;
+    int const p2_mode = opts->p2_mode;
+    SgmRunParams const P = { num_steps, penalty1, penalty2, p2_mode, opts->winner };
     int rc;
     if ((rc = check_sgm_penalties(penalty1, penalty2, p2_mode)) != SMVS_OK
         || (rc = check_sgm_plane_count(num_steps)) != SMVS_OK)
@@ -497,10 +495,7 @@ sgm_depth_for_view_consensus(int device, const uint8_t *main_img, int w, int h,
     SgmProfile prof;
     SgmWorkspace B(&ws);
     B.prof = &prof;
-    if (filter != nullptr) {
-        B.uniqueness = filter->uniqueness;
-        B.uniqueness_window = filter->uniqueness_window;
-    }
+    B.set_filter(filter);
     uint8_t *d_main = nullptr, *d_nbr = nullptr, *d_tmp = nullptr;
     int mw = 0, mh = 0;
     if ((rc = sgm_prepare_image(ws, main_img, w, h, main_channels, halvings, WS_MAIN,
@@ -536,12 +531,10 @@ sgm_depth_for_view_consensus(int device, const uint8_t *main_img, int w, int h,
         SMVS_REQUIRE(pw == nw[k] && ph == nh[k], "SGM-scale size of a neighbour");
         // SGMStereo::reconstruct, sgm_stereo.cc:46-62, as in the reference's merge
         if ((rc = sgm_run_device(B, d_main, mw, mh, d_nbr, pw, ph, N.M_fwd, N.t_fwd,
-                N.range_main[0], N.range_main[1], num_steps, penalty1, penalty2, p2_mode,
-                winner, d_fwd + npix * (size_t)k)) != SMVS_OK)
+                N.range_main[0], N.range_main[1], P, d_fwd + npix * (size_t)k)) != SMVS_OK)
             return rc;
         if ((rc = sgm_run_device(B, d_nbr, pw, ph, d_main, mw, mh, N.M_bwd, N.t_bwd,
-                N.range_neighbor[0], N.range_neighbor[1], num_steps, penalty1, penalty2,
-                p2_mode, winner, d_bwd + bwd_at[k])) != SMVS_OK)
+                N.range_neighbor[0], N.range_neighbor[1], P, d_bwd + bwd_at[k])) != SMVS_OK)
             return rc;
         fill_check_neighbor(&A.nb[k], d_bwd + bwd_at[k], pw, ph, N.M_fwd, N.t_fwd);
     }

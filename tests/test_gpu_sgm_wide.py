@@ -1,6 +1,6 @@
 """GPU parity of the SGM plane counts above 128 ("plane
-counts": the multiples of 8 from 136 to 256, sgm_paths_wide_kernel and
-sgm_sum_wta_wide_kernel) against the oracle's pieces -- cost volume, the
+counts": the multiples of 8 from 136 to 256, sgm_paths_wide_kernel of
+sgm_paths.hip and sgm_sum_wta_wide_kernel of sgm_wta.hip) against the oracle's pieces -- cost volume, the
 literal aggregation loop, the WTA -- and, for the adaptive-penalty mode, the
 serial restatement tests/sgm_adaptive_reference.cc in its literal form.  The
 path is integer: every comparison is array_equal."""

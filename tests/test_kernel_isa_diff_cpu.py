@@ -3,7 +3,10 @@ pure function over assembly text, tested here on small hand-written snippets in
 the compiler's layout (no compiler needed).  What may differ between two equal
 kernels: the numbering of the basic-block labels (.LBB<function>_<block>),
 comments, and -- outside the kernels -- the file name and the __hip_cuid_ symbol.
-Anything else, an opcode or a register, is a difference."""
+Anything else, an opcode or a register, is a difference.  Among the differences
+the tool sets one kind apart, `permuted`: equal resources, equally many lines,
+and the same lines once their order and the order of a line's operands do not
+count (the cases at the end)."""
 import importlib.util
 import os
 
@@ -159,3 +162,72 @@ def test_report_counts_missing_and_different_kernels(isa, monkeypatch, capsys):
     fewer = {k: v for k, v in moved.items() if k == KERNEL}
     assert isa.report(parent, fewer) == 1
     assert "only in the parent" in capsys.readouterr().out
+
+
+# ---- the third verdict: `permuted` (equal resources, equally many lines, the
+# same lines once the order of the lines and of a line's operands does not count)
+FMA = "v_fma_f64 v[2:3], v[2:3], v[4:5], v[2:3]"
+LOAD = "global_load_dwordx2 v[2:3], v1, s[0:1]"
+WAIT = "s_waitcnt vmcnt(0)"
+
+
+def verdict_after(isa, edit, **kw):
+    text = unit("a.hip", "11", 0, 0, "x")
+    a = isa.kernels_of(text)
+    b = isa.kernels_of(edit(unit("a.hip", "11", 0, 0, "x", **kw)))
+    return isa.verdict_of(a[KERNEL], b[KERNEL]), isa.permuted_kernel(a[KERNEL], b[KERNEL])
+
+
+def test_an_unchanged_kernel_is_same_not_permuted_by_name(isa):
+    assert verdict_after(isa, lambda t: t) == ("same", True)
+
+
+def test_two_operands_swapped_is_permuted(isa):
+    swapped = "v_fma_f64 v[2:3], v[4:5], v[2:3], v[2:3]"
+    assert verdict_after(isa, lambda t: t.replace(FMA, swapped)) == ("permuted", True)
+
+
+def test_two_lines_swapped_is_permuted(isa):
+    def swap(t):
+        assert t.count(LOAD + "\n\t" + WAIT) == 1
+        return t.replace(LOAD + "\n\t" + WAIT, WAIT + "\n\t" + LOAD)
+    assert verdict_after(isa, swap) == ("permuted", True)
+
+
+@pytest.mark.parametrize("old, new", [
+    (FMA, "v_fma_f64 v[2:3], v[2:3], v[6:7], v[2:3]"),   # one operand changed
+    (LOAD, "global_load_dwordx2 v[2:3], v1, s[0:1] offset:8"),   # a modifier added
+    (FMA, "v_mul_f64 v[2:3], v[2:3], v[4:5]"),   # another opcode
+    (WAIT, WAIT + "\n\ts_nop 0"),                # one line added
+    (WAIT + "\n", ""),                           # one line removed
+])
+def test_a_changed_added_or_removed_line_is_different(isa, old, new):
+    def edit(t):
+        assert t.count(old) == 1
+        return t.replace(old, new)
+    assert verdict_after(isa, edit) == ("DIFFERENT", False)
+
+
+def test_changed_resources_are_not_permuted(isa):
+    verdict, permuted = verdict_after(isa, lambda t: t, vgprs=8)
+    assert not permuted
+    assert verdict == "DIFFERENT (resources differ)"
+    # ... even where the stream itself is only reordered
+    a = isa.kernels_of(unit("a.hip", "11", 0, 0, "x"))[KERNEL]
+    b = (dict(a[0], sgpr=a[0]["sgpr"] + 2), list(reversed(a[1])))
+    assert not isa.permuted_kernel(a, b)
+    assert isa.permuted_kernel(a, (a[0], list(reversed(a[1]))))
+
+
+def test_report_counts_permuted_kernels_apart(isa, monkeypatch, capsys):
+    monkeypatch.setattr(isa, "demangle", lambda names: {n: "void smvs_hip::" + n + "(double*)" for n in names})
+    parent = isa.collect([("a", unit("a.hip", "1", 0, 0, "x"))])
+    text = unit("b.hip", "2", 0, 0, "x")
+    swapped = isa.collect([("b", text.replace(FMA, "v_fma_f64 v[2:3], v[4:5], v[2:3], v[2:3]"))])
+    assert isa.report(parent, swapped) == 0
+    out = capsys.readouterr().out
+    assert out.count("| permuted") == 1 and out.count("| same") == 1
+    assert "0 of 2 kernels differ or are missing on one side, 1 are permuted" in out
+    changed = isa.collect([("b", text.replace(FMA, "v_mul_f64 v[2:3], v[2:3], v[4:5]"))])
+    assert isa.report(parent, changed) == 1
+    assert "| DIFFERENT" in capsys.readouterr().out

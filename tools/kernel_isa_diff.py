@@ -17,9 +17,13 @@ FLAGS plus --cuda-device-only -S.  From the assembly, per kernel:
     outside every kernel and are not looked at.
 
 Kernels are matched by name across files (a kernel may move between sources).
-Prints the table of profiles/split_*_kernel_resources.txt and exits non-zero if
-the kernel sets differ, or any kernel's resources or stream differ.  Nothing
-here looks for a particular instruction: streams are only compared.
+Prints the table of profiles/split_*_kernel_resources.txt with a verdict per
+kernel: `same` (equal streams), `permuted` (equal resources, equally many
+lines, and the same lines once the order of the lines and of the operands
+inside a line does not count: what one more level of inlining does to an add's
+operands), or `DIFFERENT`.  Exits non-zero if the kernel sets differ, or any
+kernel's resources differ or its stream is DIFFERENT.  Nothing here looks for a
+particular instruction: streams are only compared.
 
 A tree is a checkout: `git worktree add ../parent HEAD~1`, or an export of a
 commit (`git archive`).
@@ -126,6 +130,29 @@ def same_kernel(a, b):
     return a[0] == b[0], a[1] == b[1]
 
 
+def line_key(line):
+    """A normalised line -> (mnemonic, sorted operand tokens): what is left of a
+    line when the order of its operands does not count."""
+    head, _, rest = line.partition(" ")
+    return head, tuple(sorted(t.strip() for t in rest.split(",") if t.strip()))
+
+
+def permuted_kernel(a, b):
+    """(resources, stream) pairs of kernels_of() -> whether b is a's stream
+    reordered: equal resources, equally many lines, and the same multiset of
+    lines once each is reduced to line_key().  (An equal stream is one.)"""
+    return a[0] == b[0] and len(a[1]) == len(b[1]) \
+        and sorted(map(line_key, a[1])) == sorted(map(line_key, b[1]))
+
+
+def verdict_of(a, b):
+    """-> "same", "permuted" or "DIFFERENT" for the two kernels' streams, with
+    " (resources differ)" behind it where they do"""
+    same_res, same_stream = same_kernel(a, b)
+    verdict = "same" if same_stream else ("permuted" if permuted_kernel(a, b) else "DIFFERENT")
+    return verdict if same_res else verdict + " (resources differ)"
+
+
 def load_build(tree):
     path = os.path.join(tree, "smvs_amd", "build.py")
     spec = importlib.util.spec_from_file_location("_isa_diff_build_%x" % abs(hash(path)), path)
@@ -205,24 +232,23 @@ def report(parent, branch, out=None):
     head = "%7s%6s%6s%6s%8s%6s" % ("VGPR", "AGPR", "SGPR", "LDS", "scratch", "occ")
     print("kernels: parent %d, branch %d\n" % (len(parent), len(branch)), file=out)
     print("%-*s %-*s |%s |%s | instructions" % (wf, "file", wk, "kernel", head, head), file=out)
-    bad = 0
+    bad = permuted = 0
     for k in order:
         cols = []
         for side in (parent, branch):
             cols.append("%7d%6d%6d%6d%8d%6d" % tuple(side[k][1][r] for r in RESOURCES)
                         if k in side else " " * len(head))
         if k in parent and k in branch:
-            same_res, same_stream = same_kernel(parent[k][1:], branch[k][1:])
-            verdict = "same" if same_stream else "DIFFERENT"
-            if not same_res:
-                verdict += " (resources differ)"
-            bad += 0 if same_res and same_stream else 1
+            verdict = verdict_of(parent[k][1:], branch[k][1:])
+            permuted += verdict == "permuted"
+            bad += verdict not in ("same", "permuted")
         else:
             verdict = "only in the " + ("parent" if k in parent else "branch")
             bad += 1
         print("%-*s %-*s |%s |%s | %s" % (wf, (branch.get(k) or parent[k])[0], wk, shown[k],
                                              cols[0], cols[1], verdict), file=out)
-    print("\n%d of %d kernels differ or are missing on one side" % (bad, len(order)), file=out)
+    print("\n%d of %d kernels differ or are missing on one side, %d are permuted"
+          % (bad, len(order), permuted), file=out)
     return bad
 
 
