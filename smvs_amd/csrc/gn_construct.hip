@@ -699,6 +699,119 @@ pixel_system(PatchKernelArgs const &A, const double *tabs /*LDS [spr][12]*/,
 }
 
 // ---------------------------------------------------------------------------
+// Phases 2 and 3 of the wave-per-chunk form, gn_patch_kernel<1, 4, false>.
+// Called behind the barrier that follows the stores of (M6, v6): chunk c's
+// pixel systems are in lds + c * scratch_rows * 64.  The patch system is four
+// serial chains over (chunk, tt, qq, row a) -- the accumulators of the three
+// MFMA block families and the gradient sum -- and none reads another, so each
+// wave walks ALL chunks in chunk order for ONE chain: waves 0, 1, 2 form T and
+// issue their family's MFMA, wave 3 sums the gradient.  Every chain sees the
+// operands of the one-wave form in its order (same bits), no wave waits for
+// another, and each stores what it holds.
+// ---------------------------------------------------------------------------
+template <int WAVES>
+__device__ __forceinline__ void
+patch_family_chain(PatchKernelArgs const &A, const double *lds, int scratch_rows,
+    const double *tabs, int wave, int lane, int slot_base, int live_count)
+{
+    static_assert(WAVES == 4, "three block families and the gradient: four chains");
+    // (wave-uniform: the branches on it are scalar)
+    int const role = __builtin_amdgcn_readfirstlane(wave);
+    int const kg = lane >> 4, col = lane & 15;
+    int ex0, ey0;
+    col_functions(col, &ex0, &ey0);
+    // the six D6 entries of sample `si` for the column with functions (ex, ey)
+    auto d6 = [&](int si, int ex, int ey, double D[6]) {
+        si = min(si, A.P - 1);
+        int const sy = si / A.spr, sx = si - sy * A.spr;
+        const double *X = tabs + sx * 12 + ex * 3;
+        const double *Y = tabs + sy * 12 + ey * 3;
+        double const x0 = X[0], x1 = X[1], x2 = X[2];
+        double const y0 = Y[0], y1 = Y[1], y2 = Y[2];
+        D[0] = x0 * y0; D[1] = x1 * y0; D[2] = x0 * y1;
+        D[3] = x1 * y1; D[4] = x2 * y0; D[5] = x0 * y2;
+    };
+
+    // (the role is decided outside the loops: the four slots of a sample row
+    // are one block of straight-line code for the scheduler)
+    double fam = 0.0, gsum = 0.0;
+    if (role == WAVES - 1) {
+#pragma unroll 1
+        for (int c = 0; c < WAVES; ++c) {
+            const double *Mc = lds + (size_t)c * scratch_rows * 64;
+#pragma unroll 1
+            for (int tt = 0; tt < 4; ++tt) {
+#pragma unroll
+                for (int qq = 0; qq < 4; ++qq) {
+                    int const pl = 4 * (4 * qq + tt) + kg;  // pixel slot in the chunk
+                    double D0[6];
+                    d6(c * 64 + pl, ex0, ey0, D0);
+#pragma unroll
+                    for (int a = 0; a < 6; ++a)
+                        gsum = __builtin_fma(Mc[(21 + a) * 64 + pl], D0[a], gsum);
+                }
+            }
+        }
+    } else {
+        // the A operand: D6 of the column rotated left by 4 * role within the 16
+        int exv, eyv;
+        col_functions((col - 4 * role) & 15, &exv, &eyv);
+#pragma unroll 1
+        for (int c = 0; c < WAVES; ++c) {
+            const double *Mc = lds + (size_t)c * scratch_rows * 64;
+#pragma unroll 1
+            for (int tt = 0; tt < 4; ++tt) {
+#pragma unroll
+                for (int qq = 0; qq < 4; ++qq) {
+                    int const pl = 4 * (4 * qq + tt) + kg;
+                    double D0[6], Dv[6];
+                    d6(c * 64 + pl, ex0, ey0, D0);
+                    d6(c * 64 + pl, exv, eyv, Dv);
+                    double Mx[21];
+#pragma unroll
+                    for (int i = 0; i < 21; ++i)
+                        Mx[i] = Mc[i * 64 + pl];
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) {
+                        double T = 0.0;
+#pragma unroll
+                        for (int b = 0; b < 6; ++b)
+                            T = __builtin_fma(Mx[sym6(a, b)], D0[b], T);
+                        fam = __builtin_amdgcn_mfma_f64_4x4x4f64(Dv[a], T, fam, 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+
+    // ---- phase 3: every wave stores what it holds ----
+    if (slot_base >= live_count)
+        return;
+    int const patch = A.live_list[slot_base];
+    // (the packed record and the lane layout: phase 3 of gn_patch_kernel)
+    auto at = [&](int e) { return patch_h_at(A.layout, (size_t)patch, e); };
+    int const bs = col >> 2, jc = col & 3;
+    if (role == 0) {
+        if (kg <= jc)
+            A.Hp[at(patch_diag_offset(bs) + upper_block(kg, jc))] = fam;
+    } else if (role == 1) {
+        if (bs >= 1)
+            A.Hp[at(patch_upper_offset(bs - 1, bs) + kg * 4 + jc)] = fam;
+        else   // block (3, 0): the transpose of the stored block (0, 3)
+            A.Hp[at(patch_upper_offset(0, 3) + jc * 4 + kg)] = fam;
+    } else if (role == 2) {
+        if (bs >= 2)
+            A.Hp[at(patch_upper_offset(bs - 2, bs) + kg * 4 + jc)] = fam;
+    } else {
+        double gv = gsum;
+        gv += __shfl_xor(gv, 16);
+        gv += __shfl_xor(gv, 32);
+        if (lane < 16)
+            A.gp[patch_g_at(A.layout, (size_t)patch, lane)] = gv;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // The patch kernel: one wavefront per block -- or, WAVES > 1, one wavefront per
 // CHUNK of a patch.
 //   PPW patches per wave (4 when a patch has <= 16 sampled pixels, else 1),
@@ -708,10 +821,13 @@ pixel_system(PatchKernelArgs const &A, const double *tabs /*LDS [spr][12]*/,
 //   coarse step has a few hundred patches: 375 waves on 1,024 SIMDs, each
 //   running four dependent chains of ~20 us (projection -> taps -> IRLS, eight
 //   neighbours in a row).  With WAVES = 4 every chunk has its own wave (its own
-//   LDS scratch) for phase 1; phase 2 -- the accumulation on the matrix cores,
-//   a few microseconds per chunk -- is taken in turns in chunk order with the
-//   accumulators handed on through LDS, so the patch system is bit-identical
-//   with the one-wave form; the last wave stores it.
+//   LDS scratch) for phase 1.  Phase 2 -- the accumulation on the matrix cores
+//   -- is four serial chains (three MFMA block families, the gradient sum):
+//   each wave walks one of them through the four chunks in chunk order
+//   (patch_family_chain), so the patch system is bit-identical with the
+//   one-wave form, and stores what it holds.  (Round 5 took phase 2 in turns,
+//   one wave per chunk with the accumulators handed on through LDS: three of
+//   four waves waiting.)
 // ---------------------------------------------------------------------------
 //   ONE_CHUNK (PPW == 1, WAVES == 1): the patch has at most 64 samples (scales 4
 //   and 5): no loop over chunks, so the accumulators are only live in phase 2
@@ -730,7 +846,6 @@ gn_patch_kernel(PatchKernelArgs A)
     int const scratch_rows = max(27, 5 * (A.n_subs - 1));
     double *Msh = lds + (size_t)wave * scratch_rows * 64;
     double *tabs = lds + (size_t)WAVES * scratch_rows * 64;  // [spr][12] sampled coordinates
-    double *hand = tabs + A.spr * 12;     // WAVES > 1: [4][64] accumulators from wave to wave
 
     int const lane = WAVES == 1 ? (int)threadIdx.x : (int)(threadIdx.x & 63);
     // a pipelined Newton loop enqueues steps before it knows whether the loop
@@ -840,29 +955,21 @@ gn_patch_kernel(PatchKernelArgs A)
                 Msh[(21 + i) * 64 + lane] = v6[i];
         }
         __syncthreads();
-        // WAVES > 1: the waves take turns at phase 2 in chunk order and hand the
-        // accumulators on through LDS, so that the matrix-core accumulation runs
-        // through the chunks exactly as in one wave -- the patch system has the
-        // same bits (a reordered sum moved three of 121,524 patches of a
-        // 1920 x 1080 optimize() across a validity decision five scales later).
-        // Phase 1, the long dependent chain, is what runs side by side.
-#pragma unroll 1
-        for (int turn = 0; turn < WAVES; ++turn) {
-        if (WAVES > 1 && wave != turn) {
-            __syncthreads();
-            continue;
+        if constexpr (WAVES > 1) {
+            // Every chunk's (M6, v6) is in LDS.  The accumulation must run
+            // through the chunks exactly as in one wave (a reordered sum moved
+            // three of 121,524 patches of a 1920 x 1080 optimize() across a
+            // validity decision five scales later) -- per accumulator: each
+            // wave walks all chunks for one of the four chains, and stores it.
+            patch_family_chain<WAVES>(A, lds, scratch_rows, tabs, wave, lane, slot_base, live_count);
+            return;
         }
-        if (WAVES == 1 ? c == c_first : turn == 0) {
+        if (c == c_first) {
 #pragma unroll
             for (int q = 0; q < PPW; ++q) {
                 acc[q][0] = acc[q][1] = acc[q][2] = 0.0;
                 gacc[q] = 0.0;
             }
-        } else if (WAVES > 1) {
-            acc[0][0] = hand[0 * 64 + lane];
-            acc[0][1] = hand[1 * 64 + lane];
-            acc[0][2] = hand[2 * 64 + lane];
-            gacc[0] = hand[3 * 64 + lane];
         }
         // ---- phase 2: H += sum_pix D6^T (M6 D6) on the matrix cores ----
         // With PPW == 4 and 4 x 4 samples per patch, pixel slot
@@ -931,21 +1038,7 @@ gn_patch_kernel(PatchKernelArgs A)
                 gacc[q] = gsum;
             }
         }
-        if (WAVES > 1) {
-            if (turn + 1 < WAVES) {
-                hand[0 * 64 + lane] = acc[0][0];
-                hand[1 * 64 + lane] = acc[0][1];
-                hand[2 * 64 + lane] = acc[0][2];
-                hand[3 * 64 + lane] = gacc[0];
-            }
-            __syncthreads();
-        }
-        }   // turns
     }
-
-    // (the wave of the last chunk holds the patch system)
-    if (WAVES > 1 && wave != WAVES - 1)
-        return;
 
     // ---- phase 3: store the per-patch systems ----
 #pragma unroll
@@ -1258,7 +1351,7 @@ gn_construct_launch(smvs_ctx *ctx, double reg, double light_reg,
             return e != nullptr && e[0] == '0';
         }();
         int const chunks = four ? 1 : (A.P + 63) / 64;
-        size_t const lds4 = (size_t)(4 * scratch_rows * 64 + A.spr * 12 + 4 * 64) * sizeof(double);
+        size_t const lds4 = (size_t)(4 * scratch_rows * 64 + A.spr * 12) * sizeof(double);
         if (four)
             hipLaunchKernelGGL((gn_patch_kernel<4, 1, false>), dim3(blocks), dim3(64), lds,
                 ctx->stream, A);
