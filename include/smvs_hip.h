@@ -707,6 +707,34 @@ int smvs_sgm_sweep_for_view_raw_filtered(int device, const uint8_t *main_img, in
     int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
     uint16_t penalty2, const smvs_sgm_sweep_options *opts,
     const smvs_sgm_filter_options *filter, float *depth, uint8_t *support);
+/* The 14 view and sweep entries above are three front ends behind one call
+ * record (csrc/sgm_internal.h, SgmViewCall): an entry fixes the fields it does
+ * not take and hands on the rest.  "SGM scale": channels = 1 for the main image
+ * and every neighbour, halvings = 0.  "constant, plane": p2_mode =
+ * SMVS_SGM_P2_CONSTANT, winner = SMVS_SGM_WINNER_PLANE.  "off": both filters off
+ * (uniqueness = 0, speckle_size = 0), no runner_up.
+ *
+ *   entry                                 front                 fixes
+ *   smvs_sgm_depth_for_view               reference merge       SGM scale; constant, plane; off
+ *   smvs_sgm_depth_for_view_mode          reference merge       SGM scale; plane; off
+ *   smvs_sgm_depth_for_view_opts          reference merge       SGM scale; off
+ *   smvs_sgm_depth_for_view_raw           reference merge       constant, plane; off
+ *   smvs_sgm_depth_for_view_raw_mode      reference merge       plane; off
+ *   smvs_sgm_depth_for_view_raw_opts      reference merge       off
+ *   smvs_sgm_depth_for_view_merge         opts->merge: either   SGM scale; off
+ *   smvs_sgm_depth_for_view_filtered      opts->merge: either   SGM scale
+ *   smvs_sgm_depth_for_view_raw_merge     opts->merge: either   off
+ *   smvs_sgm_depth_for_view_raw_filtered  opts->merge: either   nothing
+ *   smvs_sgm_sweep_for_view               plane sweep           SGM scale; off
+ *   smvs_sgm_sweep_for_view_filtered      plane sweep           SGM scale
+ *   smvs_sgm_sweep_for_view_raw           plane sweep           off; no argmin, cost, sgm
+ *   smvs_sgm_sweep_for_view_raw_filtered  plane sweep           no argmin, cost, sgm, runner_up
+ *
+ * The reference merge has the depth map as its only output (checked and support
+ * must be NULL); the consensus adds checked and support; the sweep's outputs
+ * are all optional.  All 14 make their argument checks in one order, before
+ * any device call (csrc/sgm_view.hip, check_sgm_view_call). */
+
 /* The speckle kernels alone, on a map of the caller: depth[w * h], out[w * h]
  * (may be depth itself), size[w * h] (may be NULL); w * h < 2^31.  The kernels
  * run for every speckle_size (0 and 1 give the input's bits and the sizes). */

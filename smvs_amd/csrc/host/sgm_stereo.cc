@@ -21,6 +21,15 @@ device_options(SGMStereo::Options const& o)
     return d;
 }
 
+// a device entry's answer: its error under the name of the entry called
+void
+require_ok(int rc, char const* entry)
+{
+    if (rc != SMVS_OK)
+        throw std::runtime_error(std::string(entry) + ": " + smvs_last_error());
+}
+#define SGM_DEVICE_CALL(entry, ...) require_ok(entry(__VA_ARGS__), #entry)
+
 } // namespace
 
 SGMStereo::SGMStereo(Options const& opts, StereoView::Ptr main,
@@ -47,14 +56,11 @@ SGMStereo::run_sgm(float min_depth, float max_depth)
     FloatImage::Ptr depth = FloatImage::create(main_image->width(),
         main_image->height(), 1);
     smvs_sgm_options const dev_opts = device_options(opts);
-    int const rc = smvs_sgm_run_opts(opts.device, main_image->begin(),
+    SGM_DEVICE_CALL(smvs_sgm_run_opts, opts.device, main_image->begin(),
         main_image->width(), main_image->height(), neighbor_image->begin(),
         neighbor_image->width(), neighbor_image->height(), M, t, min_depth,
         max_depth, opts.num_steps, opts.penalty1, opts.penalty2, &dev_opts,
         depth->begin(), nullptr, nullptr, nullptr);
-    if (rc != SMVS_OK)
-        throw std::runtime_error(std::string("smvs_sgm_run_opts: ")
-            + smvs_last_error());
     return depth;
 }
 
@@ -155,77 +161,50 @@ run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
         channels.push_back(p.channels);
     }
     ByteImage::ConstPtr main_bytes = main_view->get_raw_bytes();
-    int w = main_bytes->width(), h = main_bytes->height();
+    uint8_t const* const pixels = main_bytes->begin();
+    int const fw = main_bytes->width(), fh = main_bytes->height();
+    int const fc = main_bytes->channels(), n = (int)dev.size();
+    int w = fw, h = fh;
     sgm_scale_size(o.scale, &w, &h);
     FloatImage::Ptr depth = FloatImage::create_for_overwrite(w, h, 1);
-    // (the defaults call the entries without the filters)
-    bool const filtered = !o.filters_default();
+    // the option structs of every front; which entry is called: the sweep, the
+    // consensus, the filters (their defaults call the entries without them)
+    smvs_sgm_options const base = device_options(o);
+    smvs_sgm_view_options const view_opts = { base.p2_mode, base.winner,
+        o.consensus ? SMVS_SGM_MERGE_CONSENSUS : SMVS_SGM_MERGE_REFERENCE, o.min_agree,
+        o.agree_ratio };
+    smvs_sgm_sweep_options const sweep_opts = { base.p2_mode, base.winner,
+        o.sweep_min_views < 0 ? std::min(2, n) : o.sweep_min_views,
+        o.sweep_best_k < 0 ? (n + 1) / 2 : o.sweep_best_k, o.sweep_support_cost,
+        o.sweep_min_support < 0 ? std::min(2, n) : o.sweep_min_support };
     smvs_sgm_filter_options const filter = { o.uniqueness, o.uniqueness_window,
         o.speckle_size, o.speckle_ratio };
-    if (o.sweep) {
+    bool const filtered = !o.filters_default();
+    if (o.sweep && filtered)
         // n x (warp + cost) over the main view's planes, one fold, one
         // aggregation, one winner, the support test
-        int const n = (int)dev.size();
-        smvs_sgm_options const base = device_options(o);
-        smvs_sgm_sweep_options const sweep_opts = { base.p2_mode, base.winner,
-            o.sweep_min_views < 0 ? std::min(2, n) : o.sweep_min_views,
-            o.sweep_best_k < 0 ? (n + 1) / 2 : o.sweep_best_k, o.sweep_support_cost,
-            o.sweep_min_support < 0 ? std::min(2, n) : o.sweep_min_support };
-        if (filtered) {
-            int const frc = smvs_sgm_sweep_for_view_raw_filtered(o.device, main_bytes->begin(),
-                main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
-                channels.data(), n, o.scale, dev[0].range_main, o.num_steps, o.penalty1,
-                o.penalty2, &sweep_opts, &filter, depth->begin(), nullptr);
-            if (frc != SMVS_OK)
-                throw std::runtime_error(std::string("smvs_sgm_sweep_for_view_raw_filtered: ")
-                    + smvs_last_error());
-            return depth;
-        }
-        int const rc = smvs_sgm_sweep_for_view_raw(o.device, main_bytes->begin(),
-            main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
-            channels.data(), n, o.scale, dev[0].range_main, o.num_steps, o.penalty1,
-            o.penalty2, &sweep_opts, depth->begin(), nullptr);
-        if (rc != SMVS_OK)
-            throw std::runtime_error(std::string("smvs_sgm_sweep_for_view_raw: ")
-                + smvs_last_error());
-        return depth;
-    }
-    if (o.consensus || filtered) {
-        // the same over n neighbours: 2 n x run_sgm, then the n checks and the
-        // consensus in one kernel; with the filters either merge goes through
-        // the one entry that takes them
-        smvs_sgm_options const base = device_options(o);
-        smvs_sgm_view_options const view_opts = { base.p2_mode, base.winner,
-            o.consensus ? SMVS_SGM_MERGE_CONSENSUS : SMVS_SGM_MERGE_REFERENCE, o.min_agree,
-            o.agree_ratio };
-        if (filtered) {
-            int const frc = smvs_sgm_depth_for_view_raw_filtered(o.device, main_bytes->begin(),
-                main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
-                channels.data(), (int)dev.size(), o.scale, o.num_steps, o.penalty1,
-                o.penalty2, &view_opts, &filter, depth->begin(), nullptr, nullptr);
-            if (frc != SMVS_OK)
-                throw std::runtime_error(std::string("smvs_sgm_depth_for_view_raw_filtered: ")
-                    + smvs_last_error());
-            return depth;
-        }
-        int const rc = smvs_sgm_depth_for_view_raw_merge(o.device, main_bytes->begin(),
-            main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
-            channels.data(), (int)dev.size(), o.scale, o.num_steps, o.penalty1,
-            o.penalty2, &view_opts, depth->begin(), nullptr, nullptr);
-        if (rc != SMVS_OK)
-            throw std::runtime_error(std::string("smvs_sgm_depth_for_view_raw_merge: ")
-                + smvs_last_error());
-        return depth;
-    }
-    // desaturate + half-size on the device, then 4 x run_sgm, L/R check, merge
-    smvs_sgm_options const dev_opts = device_options(o);
-    int const rc = smvs_sgm_depth_for_view_raw_opts(o.device, main_bytes->begin(),
-        main_bytes->width(), main_bytes->height(), main_bytes->channels(), dev.data(),
-        channels.data(), (int)dev.size(), o.scale, o.num_steps, o.penalty1, o.penalty2,
-        &dev_opts, depth->begin());
-    if (rc != SMVS_OK)
-        throw std::runtime_error(std::string("smvs_sgm_depth_for_view_raw_opts: ")
-            + smvs_last_error());
+        SGM_DEVICE_CALL(smvs_sgm_sweep_for_view_raw_filtered, o.device, pixels, fw, fh, fc,
+            dev.data(), channels.data(), n, o.scale, dev[0].range_main, o.num_steps, o.penalty1,
+            o.penalty2, &sweep_opts, &filter, depth->begin(), nullptr);
+    else if (o.sweep)
+        SGM_DEVICE_CALL(smvs_sgm_sweep_for_view_raw, o.device, pixels, fw, fh, fc, dev.data(),
+            channels.data(), n, o.scale, dev[0].range_main, o.num_steps, o.penalty1, o.penalty2,
+            &sweep_opts, depth->begin(), nullptr);
+    else if (filtered)
+        // with the filters either merge goes through the one entry that takes them
+        SGM_DEVICE_CALL(smvs_sgm_depth_for_view_raw_filtered, o.device, pixels, fw, fh, fc,
+            dev.data(), channels.data(), n, o.scale, o.num_steps, o.penalty1, o.penalty2,
+            &view_opts, &filter, depth->begin(), nullptr, nullptr);
+    else if (o.consensus)
+        // 2 n x run_sgm, then the n checks and the consensus in one kernel
+        SGM_DEVICE_CALL(smvs_sgm_depth_for_view_raw_merge, o.device, pixels, fw, fh, fc,
+            dev.data(), channels.data(), n, o.scale, o.num_steps, o.penalty1, o.penalty2,
+            &view_opts, depth->begin(), nullptr, nullptr);
+    else
+        // desaturate + half-size on the device, then 4 x run_sgm, L/R check, merge
+        SGM_DEVICE_CALL(smvs_sgm_depth_for_view_raw_opts, o.device, pixels, fw, fh, fc,
+            dev.data(), channels.data(), n, o.scale, o.num_steps, o.penalty1, o.penalty2, &base,
+            depth->begin());
     return depth;
 }
 

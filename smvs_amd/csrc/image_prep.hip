@@ -285,24 +285,41 @@ smvs_rescale_half_gaussian(int device, const uint8_t *pixels, int width, int hei
 }
 
 // (declared in sgm_internal.h)
+smvs_hip::SgmPreparedSize
+smvs_hip::sgm_prepared_size(int w, int h, int channels, int halvings)
+{
+    size_t const npix = (size_t)w * h;
+    // raw bytes and the grey image behind them; neither for an image that is
+    // one channel at SGM scale already
+    SgmPreparedSize Z = { w, h, npix,
+        channels == 1 && halvings == 0 ? 0 : npix * (size_t)channels + npix };
+    for (int i = 0; i < halvings; ++i) {
+        Z.w = (Z.w + 1) >> 1;
+        Z.h = (Z.h + 1) >> 1;
+    }
+    return Z;
+}
+
+// (declared in sgm_internal.h)
 int
 smvs_hip::sgm_prepare_image(Workspace &ws, const uint8_t *host, int w, int h, int channels,
     int halvings, int slot_out, int slot_tmp, uint8_t **out, int *ow, int *oh)
 {
     int rc;
+    SgmPreparedSize const Z = sgm_prepared_size(w, h, channels, halvings);
     size_t const npix = (size_t)w * h;
     uint8_t *a = nullptr, *b = nullptr;
-    if (channels == 1 && halvings == 0) {
-        if ((rc = ws.ensure(slot_out, npix, &a)) || (rc = ws.upload(a, host, npix)))
+    *ow = Z.w;
+    *oh = Z.h;
+    if (Z.tmp == 0) {
+        if ((rc = ws.ensure(slot_out, Z.out, &a)) || (rc = ws.upload(a, host, npix)))
             return rc;
         *out = a;
-        *ow = w;
-        *oh = h;
         return SMVS_OK;
     }
     // raw bytes into the scratch slot, results ping-pong between the two
-    if ((rc = ws.ensure(slot_tmp, npix * (size_t)channels + npix, &b))
-        || (rc = ws.ensure(slot_out, npix, &a))
+    if ((rc = ws.ensure(slot_tmp, Z.tmp, &b))
+        || (rc = ws.ensure(slot_out, Z.out, &a))
         || (rc = ws.upload(b, host, npix * (size_t)channels)))
         return rc;
     uint8_t *grey = b + npix * (size_t)channels;   // behind the raw bytes
@@ -323,7 +340,5 @@ smvs_hip::sgm_prepare_image(Workspace &ws, const uint8_t *host, int w, int h, in
     // (an even number of swaps ends in `a` when it started there, an odd one
     // when it started in `grey`: cur == a by construction)
     *out = cur;
-    *ow = cw;
-    *oh = ch;
     return SMVS_OK;
 }

@@ -135,26 +135,23 @@ struct SgmWorkspace {
     }
 };
 
-// The penalties alone (no device involved: the *_mode entries call this before
-// anything else).
+// The small checks, none of which involves a device; check_sgm_view_call and
+// the entries outside it (the runs, smvs_sgm_check_merge, smvs_sgm_fold_costs,
+// smvs_sgm_filter_speckles) are made of them.
+// p2_mode and the penalties:
 int check_sgm_penalties(unsigned penalty1, unsigned penalty2, int p2_mode);
-// The plane count alone (sgm_plane_count_ok; no device involved: every entry
-// calls this before its first device call).
+// sgm_plane_count_ok:
 int check_sgm_plane_count(int num_steps);
-// The options of the *_opts entries: non-NULL, a known winner (no device
-// involved: the entries call this first; p2_mode goes through
-// check_sgm_penalties as in the *_mode entries).
+// smvs_sgm_options: non-NULL, a known winner
 int check_sgm_winner(const smvs_sgm_options *opts);
-// The options of the *_merge entries and the neighbour count they go with:
-// non-NULL, a known winner and merge, one or two neighbours for the reference's
-// merge, 1 .. SMVS_MAX_SUBS neighbours, agree_ratio in [0, 1] (a NaN is none)
-// and min_agree in 1 .. SMVS_MAX_SUBS for the consensus (no device involved:
-// the entries call this first).  (sgm_view.hip)
+// smvs_sgm_view_options and the neighbour count: non-NULL, a known winner and
+// merge, one or two neighbours for the reference's merge; for the consensus
+// 1 .. SMVS_MAX_SUBS neighbours, agree_ratio in [0, 1] (a NaN is none) and
+// min_agree in 1 .. SMVS_MAX_SUBS.  (sgm_view.hip)
 int check_sgm_view_options(const smvs_sgm_view_options *opts, int n_neighbors);
-// The filter options of the *_filtered entries: non-NULL, uniqueness in 0 .. 99,
-// the window in 1 .. 256, speckle_size >= 0, speckle_ratio in [0, 1] (a NaN is
-// none); run_entry: the speckle fields must be off (no device involved: the
-// entries call this first).  (sgm.hip)
+// smvs_sgm_filter_options: non-NULL, uniqueness in 0 .. 99, the window in
+// 1 .. 256, speckle_size >= 0, speckle_ratio in [0, 1] (a NaN is none);
+// run_entry: the speckle fields must be off.  (sgm.hip)
 int check_sgm_filter(const smvs_sgm_filter_options *filter, bool run_entry);
 // Whether the speckle filter of the options runs at all (sizes 0 and 1 remove
 // nothing).
@@ -239,6 +236,81 @@ int sgm_run_device(SgmWorkspace &B, const uint8_t *d_main, int w, int h, const u
 // *ow / *oh its size.  (image_prep.hip)
 int sgm_prepare_image(Workspace &ws, const uint8_t *host, int w, int h, int channels,
     int halvings, int slot_out, int slot_tmp, uint8_t **out, int *ow, int *oh);
+// What sgm_prepare_image makes of w x h x channels in `halvings` steps: the
+// SGM-scale size ((s + 1) >> 1 per halving) and the bytes it asks of its two
+// slots (tmp 0: the slot is not touched).  A front that sends several images
+// through one pair of slots sizes them with this.  (image_prep.hip)
+struct SgmPreparedSize {
+    int w, h;
+    size_t out, tmp;
+};
+SgmPreparedSize sgm_prepared_size(int w, int h, int channels, int halvings);
+
+// ------------------------------------------------- a view entry's call record
+// What one of the 14 smvs_sgm_depth_for_view* / smvs_sgm_sweep_for_view*
+// entries is asked for (include/smvs_hip.h: which entry fixes which field).
+// The entries at SGM scale are the raw ones with channels = 1, SGM_ONE_CHANNEL
+// and halvings = 0; the entries without filters those with SGM_FILTERS_OFF.
+struct SgmViewCall {
+    int device;
+    const uint8_t *main_img;
+    int w, h, channels;
+    const smvs_sgm_neighbor *neighbors;
+    const int *neighbor_channels;
+    int n_neighbors, halvings;
+    SgmRunParams P;
+    bool sweep;                     // the front: the sweep, or that of view_opts.merge
+    smvs_sgm_view_options view_opts;    // (p2_mode and winner of both: as in P)
+    smvs_sgm_sweep_options sweep_opts;
+    const float *range;             // the sweep's depth range
+    const smvs_sgm_filter_options *filter;
+    const char *null_options;       // the entry's options pointer was null: the refusal
+    float *depth, *checked;         // outputs; null: not asked for
+    uint8_t *support;
+    int32_t *argmin;
+    uint16_t *cost, *sgm, *runner_up;
+};
+constexpr int SGM_ONE_CHANNEL[SMVS_MAX_SUBS] = { 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1 };
+static_assert(SMVS_MAX_SUBS == 16, "SGM_ONE_CHANNEL: one entry per neighbour");
+// (what SgmWorkspace::set_filter and sgm_speckle_on make of it: nothing runs)
+constexpr smvs_sgm_filter_options SGM_FILTERS_OFF = { 0, 1, 0, 0.95f };
+
+// Every refusal of a view entry, before its first device call, in the one
+// order written above it.  (sgm_view.hip)
+int check_sgm_view_call(SgmViewCall const &C);
+// smvs_sgm_sweep_options and the neighbour count, as the checks above.  (sgm_sweep.hip)
+int check_sgm_sweep_options(const smvs_sgm_sweep_options *opts, int n_neighbors);
+
+// What the three fronts share of one call: the leased workspace, the timers,
+// the run buffers, the main image at SGM scale, the speckle words.  (sgm_view.hip)
+struct SgmViewSession {
+    SgmViewCall const &C;
+    WorkspaceLease lease;
+    SgmProfile prof;                // (destroyed before the lease: the stream is idle then)
+    SgmWorkspace B;
+    uint8_t *d_main = nullptr;
+    int mw = 0, mh = 0;
+    size_t npix = 0;
+    uint32_t *d_speckle = nullptr;
+    explicit SgmViewSession(SgmViewCall const &call) : C(call), lease(call.device), B(lease.w) {}
+    Workspace &ws() { return *lease.w; }
+    // the call's filter and want_sgm, the main image prepared (WS_MAIN, WS_RAW),
+    // the speckle words when the filter asks
+    int open();
+    // neighbour k prepared into the two slots
+    int neighbor(int k, int slot_out, int slot_tmp, uint8_t **d_nbr, int *nw, int *nh);
+    // B's buffers for runs on images of up to largest_pix pixels
+    int ensure_runs(size_t largest_pix);
+    // SGMStereo::reconstruct, sgm_stereo.cc:46-62: main -> neighbour k, then
+    // neighbour k -> main with the neighbour's own depth range
+    int run_pair(int k, const uint8_t *d_nbr, int nw, int nh, float *d_fwd, float *d_bwd);
+    // the speckle filter on d_map when on, then the outputs the call asks for
+    int finish(float *d_map, const float *d_checked, const uint8_t *d_support);
+};
+// check, session, front: what every view entry does with its record
+int sgm_run_view_call(SgmViewCall const &C);
+// the sweep front of an open session (sgm_sweep.hip)
+int sgm_front_sweep(SgmViewSession &S, SgmViewCall const &C);
 
 // The eight path directions (dx, dy) in the reference's order: ->, <-, then
 // the three top-to-bottom paths, then the three bottom-to-top paths.  The host

@@ -241,13 +241,14 @@ sgm_support_kernel(const uint8_t *__restrict__ costs, size_t stride, int n,
         depth[p] = 0.0f;
 }
 
-// The options of the sweep entries and the neighbour count they go with (no
-// device involved: the entries call this first).
-static int
+static const char SGM_NULL_SWEEP_OPTIONS[]
+    = "null options (p2_mode, winner, min_views, best_k, support_cost, min_support)";
+
+// (declared in sgm_internal.h)
+int
 check_sgm_sweep_options(const smvs_sgm_sweep_options *opts, int n_neighbors)
 {
-    SMVS_REQUIRE(opts != nullptr,
-        "null options (p2_mode, winner, min_views, best_k, support_cost, min_support)");
+    SMVS_REQUIRE(opts != nullptr, SGM_NULL_SWEEP_OPTIONS);
     SMVS_REQUIRE(opts->p2_mode == SMVS_SGM_P2_CONSTANT
             || opts->p2_mode == SMVS_SGM_P2_ADAPTIVE, "unknown penalty2 mode");
     SMVS_REQUIRE(opts->winner == SMVS_SGM_WINNER_PLANE
@@ -265,124 +266,105 @@ check_sgm_sweep_options(const smvs_sgm_sweep_options *opts, int n_neighbors)
     return SMVS_OK;
 }
 
-} // namespace smvs_hip
-
-using namespace smvs_hip;
-
-// The sweep on prepared device images: main census once; per neighbour its
-// image (one at a time through the slots of neighbour 0, as the consensus front
-// end), warp and cost into volume k; fold into the run's cost buffer; paths;
-// WTA; support.
-static int
-sgm_sweep_impl(int device, const uint8_t *main_img, int w, int h, int main_channels,
-    const smvs_sgm_neighbor *neighbors, const int *neighbor_channels, int n_neighbors,
-    int halvings, const float *range, int num_steps, uint16_t penalty1, uint16_t penalty2,
-    const smvs_sgm_sweep_options *opts, float *depth, int32_t *argmin, uint8_t *support,
-    uint16_t *cost, uint16_t *sgm, const smvs_sgm_filter_options *filter = nullptr,
-    uint16_t *runner_up = nullptr)
+// (declared in sgm_internal.h)  The sweep front: main census once; per
+// neighbour its image (one at a time through the slots of neighbour 0, as the
+// consensus front), warp and cost into volume k; fold into the run's cost
+// buffer; paths; WTA; support.
+int
+sgm_front_sweep(SgmViewSession &S, SgmViewCall const &C)
 {
     int rc;
-    if ((rc = check_sgm_sweep_options(opts, n_neighbors)) != SMVS_OK
-        || (rc = check_sgm_plane_count(num_steps)) != SMVS_OK
-        || (rc = check_sgm_penalties(penalty1, penalty2, opts->p2_mode)) != SMVS_OK)
-        return rc;
-    SMVS_REQUIRE(range != nullptr, "null argument (range)");
-    // (a NaN fails the comparisons)
-    SMVS_REQUIRE(range[0] > 0.f && range[1] > range[0],
-        "bad depth range: 0 < min_depth < max_depth");
-    SMVS_REQUIRE(main_img && neighbors, "null argument");
-    SMVS_REQUIRE(halvings >= 0 && halvings <= 8, "halvings out of range");
-    SMVS_REQUIRE((w >> halvings) > 10 && (h >> halvings) > 8, "image too small");
-    size_t max_rawpix = 0, max_tmp = 0;
-    for (int k = 0; k < n_neighbors; ++k) {
-        smvs_sgm_neighbor const &N = neighbors[k];
-        SMVS_REQUIRE(N.image && (N.width >> halvings) > 1 && (N.height >> halvings) > 1,
-            "bad neighbour image");
-        int const ch = neighbor_channels != nullptr ? neighbor_channels[k] : 1;
-        // (what sgm_prepare_image asks of its two slots)
-        size_t const rawpix = (size_t)N.width * N.height;
-        size_t const tmp = ch == 1 && halvings == 0 ? 0 : rawpix * (size_t)(ch + 1);
-        max_rawpix = rawpix > max_rawpix ? rawpix : max_rawpix;
-        max_tmp = tmp > max_tmp ? tmp : max_tmp;
-    }
-    WorkspaceLease lease(device);
-    if (lease.w == nullptr)
-        return SMVS_ERR_HIP;
-    Workspace &ws = *lease.w;
-    hipStream_t const stream = ws.stream;
-    SgmProfile prof;
-    SgmWorkspace B(&ws);
-    B.prof = &prof;
-    B.want_sgm = sgm != nullptr;
-    B.set_filter(filter);
-    uint8_t *d_main = nullptr, *d_nbr = nullptr, *d_tmp = nullptr;
-    int mw = 0, mh = 0;
-    if ((rc = sgm_prepare_image(ws, main_img, w, h, main_channels, halvings, WS_MAIN,
-             WS_RAW, &d_main, &mw, &mh)) != SMVS_OK)
-        return rc;
-    size_t const npix = (size_t)mw * mh;
+    Workspace &ws = S.ws();
+    SgmWorkspace &B = S.B;
+    int const n = C.n_neighbors, mw = S.mw, mh = S.mh, num_steps = C.P.num_steps;
+    size_t const npix = S.npix;
     size_t const vol = npix * (size_t)num_steps;
     size_t const stride = fold_stride(vol);
+    size_t max_out = 0, max_tmp = 0;
+    for (int k = 0; k < n; ++k) {
+        SgmPreparedSize const Z = sgm_prepared_size(C.neighbors[k].width, C.neighbors[k].height,
+            C.neighbor_channels[k], C.halvings);
+        max_out = Z.out > max_out ? Z.out : max_out;
+        max_tmp = Z.tmp > max_tmp ? Z.tmp : max_tmp;
+    }
     // every buffer at its largest size before the first SGM launch (growing one
     // waits for the stream)
     float *d_depth = nullptr;
-    uint8_t *d_support = nullptr, *d_vols = nullptr;
+    uint8_t *d_nbr = nullptr, *d_tmp = nullptr, *d_support = nullptr, *d_vols = nullptr;
     SgmRun R;
-    SgmRunParams const P = { num_steps, penalty1, penalty2, opts->p2_mode, opts->winner };
-    uint32_t *d_speckle = nullptr;
-    if ((sgm_speckle_on(filter) && (rc = sgm_speckle_ensure(ws, npix, &d_speckle)))
-        || (runner_up != nullptr && (rc = ws.ensure(WS_RUNNER_UP, npix, &B.runner_up))))
-        return rc;
-    if ((rc = ws.ensure(WS_NBR0, max_rawpix, &d_nbr))
+    if ((C.runner_up != nullptr && (rc = ws.ensure(WS_RUNNER_UP, npix, &B.runner_up)))
+        || (rc = ws.ensure(WS_NBR0, max_out, &d_nbr))
         || (max_tmp != 0 && (rc = ws.ensure(WS_RAW0, max_tmp, &d_tmp)))
         || (rc = ws.ensure(WS_FWD0, npix, &d_depth))
         || (rc = ws.ensure(WS_SUPPORT, npix, &d_support))
-        || (rc = ws.ensure(WS_SWEEP, stride * (size_t)n_neighbors, &d_vols))
-        || (rc = sgm_run_plan(B, mw, mh, range[0], range[1], P, &R)))
+        || (rc = ws.ensure(WS_SWEEP, stride * (size_t)n, &d_vols))
+        || (rc = sgm_run_plan(B, mw, mh, C.range[0], C.range[1], C.P, &R)))
         return rc;
-    sgm_launch_census(B, d_main, mw, mh);
-    for (int k = 0; k < n_neighbors; ++k) {
-        smvs_sgm_neighbor const &N = neighbors[k];
+    sgm_launch_census(B, S.d_main, mw, mh);
+    for (int k = 0; k < n; ++k) {
+        smvs_sgm_neighbor const &N = C.neighbors[k];
         int pw = 0, ph = 0;
-        if ((rc = sgm_prepare_image(ws, N.image, N.width, N.height,
-                 neighbor_channels != nullptr ? neighbor_channels[k] : 1, halvings, WS_NBR0,
-                 WS_RAW0, &d_nbr, &pw, &ph)) != SMVS_OK
+        if ((rc = S.neighbor(k, WS_NBR0, WS_RAW0, &d_nbr, &pw, &ph)) != SMVS_OK
             || (rc = sgm_launch_warp_cost(B, R, mw, mh, d_nbr, pw, ph, N.M_fwd, N.t_fwd,
                     num_steps, d_vols + stride * (size_t)k)) != SMVS_OK)
             return rc;
     }
-    if ((rc = launch_fold(d_vols, stride, vol, B.cost, n_neighbors, opts->best_k,
-             opts->min_views, &prof, stream)) != SMVS_OK
-        || (rc = sgm_run_tail(B, R, d_main, mw, mh, P, d_depth)) != SMVS_OK)
+    if ((rc = launch_fold(d_vols, stride, vol, B.cost, n, C.sweep_opts.best_k,
+             C.sweep_opts.min_views, &S.prof, ws.stream)) != SMVS_OK
+        || (rc = sgm_run_tail(B, R, S.d_main, mw, mh, C.P, d_depth)) != SMVS_OK)
         return rc;
     {
-        SgmKernelTimer timer(&prof, stream, SMVS_SGM_K_LR_CHECK);
+        SgmKernelTimer timer(&S.prof, ws.stream, SMVS_SGM_K_LR_CHECK);
         hipLaunchKernelGGL(sgm_support_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256),
-            0, stream, d_vols, stride, n_neighbors, B.argmin, npix, num_steps,
-            opts->support_cost, opts->min_support, d_support, d_depth);
+            0, ws.stream, d_vols, stride, n, B.argmin, npix, num_steps,
+            C.sweep_opts.support_cost, C.sweep_opts.min_support, d_support, d_depth);
     }
     SMVS_HIP_CHECK(hipGetLastError());
-    // (after the support test: the components are those of the map that leaves)
-    if (sgm_speckle_on(filter)
-        && (rc = sgm_launch_speckle(ws, &prof, d_depth, mw, mh, filter->speckle_size,
-                filter->speckle_ratio, d_speckle, d_depth, false)) != SMVS_OK)
-        return rc;
-    if (depth != nullptr && (rc = ws.download(depth, d_depth, sizeof(float) * npix)) != SMVS_OK)
-        return rc;
-    if (runner_up != nullptr
-        && (rc = ws.download(runner_up, B.runner_up, sizeof(uint16_t) * npix)) != SMVS_OK)
-        return rc;
-    if (argmin != nullptr
-        && (rc = ws.download(argmin, B.argmin, sizeof(int32_t) * npix)) != SMVS_OK)
-        return rc;
-    if (support != nullptr && (rc = ws.download(support, d_support, npix)) != SMVS_OK)
-        return rc;
-    if (sgm != nullptr && (rc = ws.download(sgm, B.sgm, sizeof(uint16_t) * vol)) != SMVS_OK)
-        return rc;
-    if (cost != nullptr && (rc = sgm_download_cost16(ws, B.cost, vol, cost)) != SMVS_OK)
-        return rc;
-    SMVS_HIP_CHECK(hipStreamSynchronize(stream));
-    return SMVS_OK;
+    return S.finish(d_depth, nullptr, d_support);
+}
+
+} // namespace smvs_hip
+
+using namespace smvs_hip;
+
+// The two entries with the filters fill a record each (the one at SGM scale
+// has the volumes among its outputs, the raw one has not); the two without
+// them are those with both filters off.
+extern "C" int
+smvs_sgm_sweep_for_view_filtered(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, const float *range, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_sweep_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint8_t *support,
+    uint16_t *cost, uint16_t *sgm, uint16_t *runner_up)
+{
+    smvs_sgm_sweep_options const o = opts != nullptr ? *opts : smvs_sgm_sweep_options{};
+    SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h, .channels = 1,
+        .neighbors = neighbors, .neighbor_channels = SGM_ONE_CHANNEL,
+        .n_neighbors = n_neighbors, .halvings = 0,
+        .P = { num_steps, penalty1, penalty2, o.p2_mode, o.winner }, .sweep = true,
+        .sweep_opts = o, .range = range, .filter = filter,
+        .null_options = opts != nullptr ? nullptr : SGM_NULL_SWEEP_OPTIONS,
+        .depth = depth, .support = support, .argmin = argmin, .cost = cost, .sgm = sgm,
+        .runner_up = runner_up };
+    return sgm_run_view_call(C);
+}
+
+extern "C" int
+smvs_sgm_sweep_for_view_raw_filtered(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_sweep_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, uint8_t *support)
+{
+    smvs_sgm_sweep_options const o = opts != nullptr ? *opts : smvs_sgm_sweep_options{};
+    SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h,
+        .channels = channels, .neighbors = neighbors, .neighbor_channels = neighbor_channels,
+        .n_neighbors = n_neighbors, .halvings = halvings,
+        .P = { num_steps, penalty1, penalty2, o.p2_mode, o.winner }, .sweep = true,
+        .sweep_opts = o, .range = range, .filter = filter,
+        .null_options = opts != nullptr ? nullptr : SGM_NULL_SWEEP_OPTIONS,
+        .depth = depth, .support = support };
+    return sgm_run_view_call(C);
 }
 
 extern "C" int
@@ -391,8 +373,9 @@ smvs_sgm_sweep_for_view(int device, const uint8_t *main_img, int w, int h,
     uint16_t penalty1, uint16_t penalty2, const smvs_sgm_sweep_options *opts, float *depth,
     int32_t *argmin, uint8_t *support, uint16_t *cost, uint16_t *sgm)
 {
-    return sgm_sweep_impl(device, main_img, w, h, 1, neighbors, nullptr, n_neighbors, 0, range,
-        num_steps, penalty1, penalty2, opts, depth, argmin, support, cost, sgm);
+    return smvs_sgm_sweep_for_view_filtered(device, main_img, w, h, neighbors, n_neighbors,
+        range, num_steps, penalty1, penalty2, opts, &SGM_FILTERS_OFF, depth, argmin, support,
+        cost, sgm, nullptr);
 }
 
 extern "C" int
@@ -401,56 +384,9 @@ smvs_sgm_sweep_for_view_raw(int device, const uint8_t *main_img, int w, int h, i
     int halvings, const float *range, int num_steps, uint16_t penalty1, uint16_t penalty2,
     const smvs_sgm_sweep_options *opts, float *depth, uint8_t *support)
 {
-    if (int const rc = check_sgm_sweep_options(opts, n_neighbors); rc != SMVS_OK)
-        return rc;
-    SMVS_REQUIRE(channels == 1 || channels == 3, "1 or 3 channels");
-    SMVS_REQUIRE(neighbor_channels != nullptr, "null argument");
-    for (int k = 0; k < n_neighbors; ++k)
-        SMVS_REQUIRE(neighbor_channels[k] == 1 || neighbor_channels[k] == 3,
-            "1 or 3 channels");
-    return sgm_sweep_impl(device, main_img, w, h, channels, neighbors, neighbor_channels,
-        n_neighbors, halvings, range, num_steps, penalty1, penalty2, opts, depth, nullptr,
-        support, nullptr, nullptr);
-}
-
-// smvs_sgm_sweep_for_view with the uniqueness test in its one WTA step and the
-// speckle filter behind the support test
-extern "C" int
-smvs_sgm_sweep_for_view_filtered(int device, const uint8_t *main_img, int w, int h,
-    const smvs_sgm_neighbor *neighbors, int n_neighbors, const float *range, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_sweep_options *opts,
-    const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint8_t *support,
-    uint16_t *cost, uint16_t *sgm, uint16_t *runner_up)
-{
-    if (int const rc = check_sgm_filter(filter, false); rc != SMVS_OK)
-        return rc;
-    SMVS_REQUIRE(runner_up == nullptr || filter->uniqueness != 0,
-        "runner_up is an output of the uniqueness test (uniqueness > 0)");
-    return sgm_sweep_impl(device, main_img, w, h, 1, neighbors, nullptr, n_neighbors, 0, range,
-        num_steps, penalty1, penalty2, opts, depth, argmin, support, cost, sgm, filter,
-        runner_up);
-}
-
-// smvs_sgm_sweep_for_view_raw with the filters
-extern "C" int
-smvs_sgm_sweep_for_view_raw_filtered(int device, const uint8_t *main_img, int w, int h,
-    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
-    int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
-    uint16_t penalty2, const smvs_sgm_sweep_options *opts,
-    const smvs_sgm_filter_options *filter, float *depth, uint8_t *support)
-{
-    int rc;
-    if ((rc = check_sgm_filter(filter, false)) != SMVS_OK
-        || (rc = check_sgm_sweep_options(opts, n_neighbors)) != SMVS_OK)
-        return rc;
-    SMVS_REQUIRE(channels == 1 || channels == 3, "1 or 3 channels");
-    SMVS_REQUIRE(neighbor_channels != nullptr, "null argument");
-    for (int k = 0; k < n_neighbors; ++k)
-        SMVS_REQUIRE(neighbor_channels[k] == 1 || neighbor_channels[k] == 3,
-            "1 or 3 channels");
-    return sgm_sweep_impl(device, main_img, w, h, channels, neighbors, neighbor_channels,
-        n_neighbors, halvings, range, num_steps, penalty1, penalty2, opts, depth, nullptr,
-        support, nullptr, nullptr, filter, nullptr);
+    return smvs_sgm_sweep_for_view_raw_filtered(device, main_img, w, h, channels, neighbors,
+        neighbor_channels, n_neighbors, halvings, range, num_steps, penalty1, penalty2, opts,
+        &SGM_FILTERS_OFF, depth, support);
 }
 
 // the fold kernel alone, on the caller's bytes

@@ -208,19 +208,58 @@ launch_check_merge(CheckMergeArgs const &A, int n, SgmProfile *prof, hipStream_t
     return SMVS_OK;
 }
 
-static void
-fill_check_neighbor(CheckNeighbor *C, const float *d_bwd, int nw, int nh, const float *M,
-    const float *t)
+// The 3 % border of the left/right check in a neighbour of nw x nh
+// (sgm_stereo.cc:70-71), and the float reprojection of an entry widened to the
+// doubles both check kernels compute in.
+static int
+lr_cut(int nw, int nh)
 {
-    C->bwd = d_bwd;
-    C->nw = nw;
-    C->nh = nh;
-    C->cut = (int)(0.03 * (double)(nw > nh ? nw : nh));
-    C->pad = 0;
+    return (int)(0.03 * (double)(nw > nh ? nw : nh));
+}
+
+static void
+widen_reprojection(double *M, double *t, const float *M_fwd, const float *t_fwd)
+{
     for (int i = 0; i < 9; ++i)
-        C->M[i] = (double)M[i];
+        M[i] = (double)M_fwd[i];
     for (int i = 0; i < 3; ++i)
-        C->t[i] = (double)t[i];
+        t[i] = (double)t_fwd[i];
+}
+
+static LrArgs
+fill_lr_args(float *d_fwd, const float *d_bwd, int w, int h, int nw, int nh, const float *M_fwd,
+    const float *t_fwd)
+{
+    LrArgs L = { d_fwd, d_bwd, w, h, nw, nh, lr_cut(nw, nh), {}, {} };
+    widen_reprojection(L.M, L.t, M_fwd, t_fwd);
+    return L;
+}
+
+static void
+fill_check_neighbor(CheckNeighbor *C, const float *d_bwd, int nw, int nh, const float *M_fwd,
+    const float *t_fwd)
+{
+    *C = { d_bwd, nw, nh, lr_cut(nw, nh), 0, {}, {} };
+    widen_reprojection(C->M, C->t, M_fwd, t_fwd);
+}
+
+// The fused kernel's arguments behind nb[0 .. n), which the caller has filled:
+// the unused neighbours are copies of nb[0], the checked maps go where the
+// forward maps are (a thread reads and writes its own pixel).
+static void
+fill_check_merge(CheckMergeArgs *A, int n, float *d_fwd, float *d_merged, bool want_checked,
+    uint8_t *d_support, int w, int h, int min_agree, float agree_ratio)
+{
+    for (int k = n; k < SMVS_MAX_SUBS; ++k)
+        A->nb[k] = A->nb[0];
+    A->fwd = d_fwd;
+    A->merged = d_merged;
+    A->checked = want_checked ? d_fwd : nullptr;
+    A->support = d_support;
+    A->w = w;
+    A->h = h;
+    A->min_agree = min_agree;
+    A->agree_ratio = agree_ratio;
 }
 
 // (declared in sgm_internal.h)
@@ -247,140 +286,298 @@ check_sgm_view_options(const smvs_sgm_view_options *opts, int n_neighbors)
     return SMVS_OK;
 }
 
-} // namespace smvs_hip
-
-using namespace smvs_hip;
-
-// reconstruct_sgm_depth_for_view on prepared device images
-static int
-sgm_depth_for_view_impl(int device, const uint8_t *main_img, int w, int h,
-    int main_channels, const smvs_sgm_neighbor *neighbors,
-    const int *neighbor_channels, int n_neighbors, int halvings, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, int winner, float *depth,
-    const smvs_sgm_filter_options *filter = nullptr)
+// (declared in sgm_internal.h)  The one order of the checks, for all 14 entries.
+// No check involves a device, and a later one may rely on an earlier one (the
+// neighbour arrays are read once the count is known to fit them).
+//   1. the entry's options pointer            2. the filter options
+//   3. p2_mode, winner, merge
+//   4. the neighbour count: 1 .. 2 for the reference's merge, 1 .. SMVS_MAX_SUBS
+//      for the consensus and the sweep
+//   5. the front's options: agree_ratio, min_agree; min_views, best_k,
+//      support_cost, min_support
+//   6. the plane count                        7. the penalties, in both modes
+//   8. the sweep's depth range
+//   9. null pointers: the images, depth (optional in the sweep), neighbor_channels
+//  10. the channels of the main image, then of each neighbour
+//  11. halvings
+//  12. the main image's size at SGM scale, then each neighbour's: above 10 x 8
+//      where the neighbour gets a run of its own, above 1 x 1 in the sweep
+//  13. outputs the options exclude: checked and support with the reference's
+//      merge, runner_up without the uniqueness test
+int
+check_sgm_view_call(SgmViewCall const &C)
 {
-    SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
-        "unknown penalty2 mode");
-    if (p2_mode != SMVS_SGM_P2_CONSTANT) {
-        int const prc = check_sgm_penalties(penalty1, penalty2, p2_mode);
-        if (prc != SMVS_OK)
-            return prc;
-    }
-    // (before the first device call, as the penalties: sgm_run_device checks
-    // both again)
-    if (int const src = check_sgm_plane_count(num_steps); src != SMVS_OK)
-        return src;
-    SMVS_REQUIRE(main_img && neighbors && depth, "null argument");
-    SMVS_REQUIRE(n_neighbors >= 1 && n_neighbors <= 2,
-        "one or two neighbours (app/smvsrecon.cc:360-365)");
-    SMVS_REQUIRE(halvings >= 0 && halvings <= 8, "halvings out of range");
-    SMVS_REQUIRE((w >> halvings) > 10 && (h >> halvings) > 8, "image too small");
-    for (int k = 0; k < n_neighbors; ++k)
-        SMVS_REQUIRE(neighbors[k].image && (neighbors[k].width >> halvings) > 10
-            && (neighbors[k].height >> halvings) > 8, "bad neighbour image");
     int rc;
-    SgmRunParams const P = { num_steps, penalty1, penalty2, p2_mode, winner };
-    WorkspaceLease lease(device);
+    SMVS_REQUIRE(C.null_options == nullptr, C.null_options);
+    if ((rc = check_sgm_filter(C.filter, false)) != SMVS_OK)
+        return rc;
+    SMVS_REQUIRE(C.P.p2_mode == SMVS_SGM_P2_CONSTANT || C.P.p2_mode == SMVS_SGM_P2_ADAPTIVE,
+        "unknown penalty2 mode");
+    rc = C.sweep ? check_sgm_sweep_options(&C.sweep_opts, C.n_neighbors)
+                 : check_sgm_view_options(&C.view_opts, C.n_neighbors);
+    if (rc != SMVS_OK || (rc = check_sgm_plane_count(C.P.num_steps)) != SMVS_OK
+        || (rc = check_sgm_penalties(C.P.penalty1, C.P.penalty2, C.P.p2_mode)) != SMVS_OK)
+        return rc;
+    if (C.sweep) {
+        SMVS_REQUIRE(C.range != nullptr, "null argument (range)");
+        // (a NaN fails the comparisons)
+        SMVS_REQUIRE(C.range[0] > 0.f && C.range[1] > C.range[0],
+            "bad depth range: 0 < min_depth < max_depth");
+    }
+    SMVS_REQUIRE(C.main_img && C.neighbors && (C.sweep || C.depth) && C.neighbor_channels,
+        "null argument");
+    SMVS_REQUIRE(C.channels == 1 || C.channels == 3, "1 or 3 channels");
+    for (int k = 0; k < C.n_neighbors; ++k)
+        SMVS_REQUIRE(C.neighbor_channels[k] == 1 || C.neighbor_channels[k] == 3,
+            "1 or 3 channels");
+    SMVS_REQUIRE(C.halvings >= 0 && C.halvings <= 8, "halvings out of range");
+    SMVS_REQUIRE((C.w >> C.halvings) > 10 && (C.h >> C.halvings) > 8, "image too small");
+    int const least_w = C.sweep ? 1 : 10, least_h = C.sweep ? 1 : 8;
+    for (int k = 0; k < C.n_neighbors; ++k)
+        SMVS_REQUIRE(C.neighbors[k].image && (C.neighbors[k].width >> C.halvings) > least_w
+                && (C.neighbors[k].height >> C.halvings) > least_h, "bad neighbour image");
+    if (!C.sweep && C.view_opts.merge == SMVS_SGM_MERGE_REFERENCE)
+        SMVS_REQUIRE(C.checked == nullptr && C.support == nullptr,
+            "checked and support are outputs of the consensus merge");
+    SMVS_REQUIRE(C.runner_up == nullptr || C.filter->uniqueness != 0,
+        "runner_up is an output of the uniqueness test (uniqueness > 0)");
+    return SMVS_OK;
+}
+
+// ------------------------------------------------------------ the session
+int
+SgmViewSession::open()
+{
     if (lease.w == nullptr)
         return SMVS_ERR_HIP;
-    Workspace &ws = *lease.w;
-    hipStream_t const stream = ws.stream;
-    SgmProfile prof;
-    SgmWorkspace B(&ws);
     B.prof = &prof;
-    B.set_filter(filter);
-    // the SGM-scale images (every buffer before the first SGM launch: growing
-    // one waits for the stream)
-    uint8_t *d_main = nullptr, *d_nbr[2] = { nullptr, nullptr };
-    int mw = 0, mh = 0, nw[2] = { 0, 0 }, nh[2] = { 0, 0 };
-    if ((rc = sgm_prepare_image(ws, main_img, w, h, main_channels, halvings, WS_MAIN,
+    B.want_sgm = C.sgm != nullptr;
+    B.set_filter(C.filter);
+    int rc;
+    if ((rc = sgm_prepare_image(ws(), C.main_img, C.w, C.h, C.channels, C.halvings, WS_MAIN,
              WS_RAW, &d_main, &mw, &mh)) != SMVS_OK)
         return rc;
-    for (int k = 0; k < n_neighbors; ++k)
-        if ((rc = sgm_prepare_image(ws, neighbors[k].image, neighbors[k].width,
-                 neighbors[k].height, neighbor_channels != nullptr ? neighbor_channels[k] : 1,
-                 halvings, k == 0 ? WS_NBR0 : WS_NBR1, k == 0 ? WS_RAW0 : WS_RAW1,
+    npix = (size_t)mw * mh;
+    return sgm_speckle_on(C.filter) ? sgm_speckle_ensure(ws(), npix, &d_speckle) : SMVS_OK;
+}
+
+int
+SgmViewSession::neighbor(int k, int slot_out, int slot_tmp, uint8_t **d_nbr, int *nw, int *nh)
+{
+    smvs_sgm_neighbor const &N = C.neighbors[k];
+    return sgm_prepare_image(ws(), N.image, N.width, N.height, C.neighbor_channels[k],
+        C.halvings, slot_out, slot_tmp, d_nbr, nw, nh);
+}
+
+int
+SgmViewSession::ensure_runs(size_t largest_pix)
+{
+    return B.ensure(largest_pix, C.P.num_steps, sgm_path_plan_here(C.P.num_steps,
+        SgmWorkspace::largest_penalty2(C.P.penalty1, C.P.penalty2, C.P.p2_mode)));
+}
+
+int
+SgmViewSession::run_pair(int k, const uint8_t *d_nbr, int nw, int nh, float *d_fwd, float *d_bwd)
+{
+    smvs_sgm_neighbor const &N = C.neighbors[k];
+    int const rc = sgm_run_device(B, d_main, mw, mh, d_nbr, nw, nh, N.M_fwd, N.t_fwd,
+        N.range_main[0], N.range_main[1], C.P, d_fwd);
+    return rc != SMVS_OK ? rc : sgm_run_device(B, d_nbr, nw, nh, d_main, mw, mh, N.M_bwd,
+        N.t_bwd, N.range_neighbor[0], N.range_neighbor[1], C.P, d_bwd);
+}
+
+int
+SgmViewSession::finish(float *d_map, const float *d_checked, const uint8_t *d_support)
+{
+    int rc;
+    Workspace &w = ws();
+    // (behind the merge or the support test: the components are those of the
+    // map that leaves; checked and support are those of the unfiltered map)
+    if (sgm_speckle_on(C.filter)
+        && (rc = sgm_launch_speckle(w, &prof, d_map, mw, mh, C.filter->speckle_size,
+                C.filter->speckle_ratio, d_speckle, d_map, false)) != SMVS_OK)
+        return rc;
+    auto get = [&w](void *host, const void *dev, size_t bytes) {
+        return host != nullptr ? w.download(host, dev, bytes) : (int)SMVS_OK;
+    };
+    // the consensus's own outputs, then the map (every download waits for the
+    // stream: nothing is left to synchronise)
+    if (!C.sweep)
+        return (rc = get(C.checked, d_checked, sizeof(float) * npix * (size_t)C.n_neighbors))
+                || (rc = get(C.support, d_support, npix))
+            ? rc : get(C.depth, d_map, sizeof(float) * npix);
+    size_t const vol = npix * (size_t)C.P.num_steps;
+    if ((rc = get(C.depth, d_map, sizeof(float) * npix))
+        || (rc = get(C.runner_up, B.runner_up, sizeof(uint16_t) * npix))
+        || (rc = get(C.argmin, B.argmin, sizeof(int32_t) * npix))
+        || (rc = get(C.support, d_support, npix))
+        || (rc = get(C.sgm, B.sgm, sizeof(uint16_t) * vol))
+        || (C.cost != nullptr && (rc = sgm_download_cost16(w, B.cost, vol, C.cost))))
+        return rc;
+    SMVS_HIP_CHECK(hipStreamSynchronize(w.stream));
+    return SMVS_OK;
+}
+
+// -------------------------------------------------------------- the fronts
+// reconstruct_sgm_depth_for_view: both neighbour images prepared before the
+// first run (every buffer before the first SGM launch: growing one waits for
+// the stream); per neighbour the two runs and the left/right check; the merge.
+static int
+sgm_front_reference(SgmViewSession &S, SgmViewCall const &C)
+{
+    int rc;
+    Workspace &ws = S.ws();
+    int const n = C.n_neighbors, mw = S.mw, mh = S.mh;
+    size_t const npix = S.npix;
+    uint8_t *d_nbr[2] = { nullptr, nullptr };
+    int nw[2] = { 0, 0 }, nh[2] = { 0, 0 };
+    for (int k = 0; k < n; ++k)
+        if ((rc = S.neighbor(k, k == 0 ? WS_NBR0 : WS_NBR1, k == 0 ? WS_RAW0 : WS_RAW1,
                  &d_nbr[k], &nw[k], &nh[k])) != SMVS_OK)
             return rc;
-    size_t const npix = (size_t)mw * mh;
     float *d_fwd[2] = { nullptr, nullptr }, *d_bwd = nullptr;
-    uint32_t *d_speckle = nullptr;
-    if (sgm_speckle_on(filter) && (rc = sgm_speckle_ensure(ws, npix, &d_speckle)))
-        return rc;
     size_t max_nnpix = 0;
-    for (int k = 0; k < n_neighbors; ++k) {
+    for (int k = 0; k < n; ++k) {
         size_t const nnpix = (size_t)nw[k] * nh[k];
         max_nnpix = nnpix > max_nnpix ? nnpix : max_nnpix;
         if ((rc = ws.ensure(k == 0 ? WS_FWD0 : WS_FWD1, npix, &d_fwd[k])))
             return rc;
     }
     if ((rc = ws.ensure(WS_BWD, max_nnpix, &d_bwd))
-        || (rc = B.ensure(npix > max_nnpix ? npix : max_nnpix, num_steps,
-                sgm_path_plan_here(num_steps,
-                    SgmWorkspace::largest_penalty2(penalty1, penalty2, p2_mode)))))
+        || (rc = S.ensure_runs(npix > max_nnpix ? npix : max_nnpix)))
         return rc;
-    for (int k = 0; k < n_neighbors; ++k) {
-        smvs_sgm_neighbor const &N = neighbors[k];
-        // SGMStereo::reconstruct, sgm_stereo.cc:46-62: main -> neighbour,
-        // then neighbour -> main with the neighbour's own depth range
-        if ((rc = sgm_run_device(B, d_main, mw, mh, d_nbr[k], nw[k], nh[k],
-                N.M_fwd, N.t_fwd, N.range_main[0], N.range_main[1], P, d_fwd[k])) != SMVS_OK)
+    for (int k = 0; k < n; ++k) {
+        if ((rc = S.run_pair(k, d_nbr[k], nw[k], nh[k], d_fwd[k], d_bwd)) != SMVS_OK)
             return rc;
-        if ((rc = sgm_run_device(B, d_nbr[k], nw[k], nh[k], d_main, mw, mh,
-                N.M_bwd, N.t_bwd, N.range_neighbor[0], N.range_neighbor[1], P, d_bwd))
-            != SMVS_OK)
-            return rc;
-        LrArgs L;
-        L.d_main = d_fwd[k];
-        L.d_neig = d_bwd;
-        L.w = mw;
-        L.h = mh;
-        L.nw = nw[k];
-        L.nh = nh[k];
-        L.cut = (int)(0.03 * (double)(nw[k] > nh[k] ? nw[k] : nh[k]));
-        for (int i = 0; i < 9; ++i)
-            L.M[i] = (double)N.M_fwd[i];
-        for (int i = 0; i < 3; ++i)
-            L.t[i] = (double)N.t_fwd[i];
+        LrArgs const L = fill_lr_args(d_fwd[k], d_bwd, mw, mh, nw[k], nh[k],
+            C.neighbors[k].M_fwd, C.neighbors[k].t_fwd);
         {
-            SgmKernelTimer timer(&prof, stream, SMVS_SGM_K_LR_CHECK);
+            SgmKernelTimer timer(&S.prof, ws.stream, SMVS_SGM_K_LR_CHECK);
             hipLaunchKernelGGL(sgm_lr_check_kernel, dim3((mw + 255) / 256, mh),
-                dim3(256), 0, stream, L);
+                dim3(256), 0, ws.stream, L);
         }
         SMVS_HIP_CHECK(hipGetLastError());
     }
-    if (n_neighbors > 1) {
-        SgmKernelTimer timer(&prof, stream, SMVS_SGM_K_MERGE);
+    if (n > 1) {
+        SgmKernelTimer timer(&S.prof, ws.stream, SMVS_SGM_K_MERGE);
         hipLaunchKernelGGL(sgm_merge_kernel, dim3((unsigned)((npix + 255) / 256)),
-            dim3(256), 0, stream, d_fwd[0], d_fwd[1], npix);
+            dim3(256), 0, ws.stream, d_fwd[0], d_fwd[1], npix);
         SMVS_HIP_CHECK(hipGetLastError());
     }
-    if (sgm_speckle_on(filter)
-        && (rc = sgm_launch_speckle(ws, &prof, d_fwd[0], mw, mh, filter->speckle_size,
-                filter->speckle_ratio, d_speckle, d_fwd[0], false)) != SMVS_OK)
+    return S.finish(d_fwd[0], nullptr, nullptr);
+}
+
+// SMVS_SGM_MERGE_CONSENSUS: 2 n runs, the neighbour images one at a time
+// through the slots of neighbour 0, the n forward and n backward maps kept,
+// then the fused kernel.
+static int
+sgm_front_consensus(SgmViewSession &S, SgmViewCall const &C)
+{
+    int rc;
+    Workspace &ws = S.ws();
+    int const n = C.n_neighbors, mw = S.mw, mh = S.mh;
+    size_t const npix = S.npix;
+    size_t bwd_at[SMVS_MAX_SUBS + 1] = { 0 };
+    size_t max_nnpix = 0, max_out = 0, max_tmp = 0;
+    for (int k = 0; k < n; ++k) {
+        SgmPreparedSize const Z = sgm_prepared_size(C.neighbors[k].width, C.neighbors[k].height,
+            C.neighbor_channels[k], C.halvings);
+        size_t const nnpix = (size_t)Z.w * Z.h;
+        max_out = Z.out > max_out ? Z.out : max_out;
+        max_tmp = Z.tmp > max_tmp ? Z.tmp : max_tmp;
+        max_nnpix = nnpix > max_nnpix ? nnpix : max_nnpix;
+        bwd_at[k + 1] = bwd_at[k] + nnpix;
+    }
+    // every buffer at its largest size before the first SGM launch (growing one
+    // waits for the stream): the neighbours' slots, the maps, the volumes
+    uint8_t *d_nbr = nullptr, *d_tmp = nullptr, *d_support = nullptr;
+    float *d_fwd = nullptr, *d_bwd = nullptr, *d_merged = nullptr;
+    if ((rc = ws.ensure(WS_NBR0, max_out, &d_nbr))
+        || (max_tmp != 0 && (rc = ws.ensure(WS_RAW0, max_tmp, &d_tmp)))
+        || (rc = ws.ensure(WS_FWDN, npix * (size_t)n, &d_fwd))
+        || (rc = ws.ensure(WS_BWDN, bwd_at[n], &d_bwd))
+        || (rc = ws.ensure(WS_FWD0, npix, &d_merged))
+        || (rc = ws.ensure(WS_SUPPORT, npix, &d_support))
+        || (rc = S.ensure_runs(npix > max_nnpix ? npix : max_nnpix)))
         return rc;
-    return ws.download(depth, d_fwd[0], sizeof(float) * npix);
+    CheckMergeArgs A;
+    for (int k = 0; k < n; ++k) {
+        int pw = 0, ph = 0;
+        if ((rc = S.neighbor(k, WS_NBR0, WS_RAW0, &d_nbr, &pw, &ph)) != SMVS_OK
+            || (rc = S.run_pair(k, d_nbr, pw, ph, d_fwd + npix * (size_t)k, d_bwd + bwd_at[k]))
+                != SMVS_OK)
+            return rc;
+        fill_check_neighbor(&A.nb[k], d_bwd + bwd_at[k], pw, ph, C.neighbors[k].M_fwd,
+            C.neighbors[k].t_fwd);
+    }
+    fill_check_merge(&A, n, d_fwd, d_merged, C.checked != nullptr,
+        C.support != nullptr ? d_support : nullptr, mw, mh, C.view_opts.min_agree,
+        C.view_opts.agree_ratio);
+    if ((rc = launch_check_merge(A, n, &S.prof, ws.stream)) != SMVS_OK)
+        return rc;
+    return S.finish(d_merged, d_fwd, d_support);
+}
+
+// (declared in sgm_internal.h)
+int
+sgm_run_view_call(SgmViewCall const &C)
+{
+    int rc;
+    if ((rc = check_sgm_view_call(C)) != SMVS_OK)
+        return rc;
+    SgmViewSession S(C);
+    if ((rc = S.open()) != SMVS_OK)
+        return rc;
+    if (C.sweep)
+        return sgm_front_sweep(S, C);
+    return C.view_opts.merge == SMVS_SGM_MERGE_CONSENSUS ? sgm_front_consensus(S, C)
+                                               : sgm_front_reference(S, C);
+}
+
+} // namespace smvs_hip
+
+using namespace smvs_hip;
+
+// ------------------------------------------------------------- the entries
+// Two entries fill a record: the one that takes smvs_sgm_options and the one
+// that takes smvs_sgm_view_options with the filters, both on raw images.  The
+// others are one of the two with the fields they do not take set to what they
+// mean: the reference's constant penalty2 and plane winner, one channel at SGM
+// scale, both filters off.
+extern "C" int
+smvs_sgm_depth_for_view_raw_opts(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_options *opts, float *depth)
+{
+    smvs_sgm_options const o = opts != nullptr ? *opts : smvs_sgm_options{};
+    SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h,
+        .channels = channels, .neighbors = neighbors, .neighbor_channels = neighbor_channels,
+        .n_neighbors = n_neighbors, .halvings = halvings,
+        .P = { num_steps, penalty1, penalty2, o.p2_mode, o.winner },
+        .view_opts = { o.p2_mode, o.winner, SMVS_SGM_MERGE_REFERENCE, 0, 0.0f },
+        .filter = &SGM_FILTERS_OFF,
+        .null_options = opts != nullptr ? nullptr : "null options (winner, p2_mode)",
+        .depth = depth };
+    return sgm_run_view_call(C);
 }
 
 extern "C" int
-smvs_sgm_depth_for_view(int device, const uint8_t *main_img, int w, int h,
-    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, float *depth)
+smvs_sgm_depth_for_view_raw_filtered(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_view_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support)
 {
-    return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
-        n_neighbors, 0, num_steps, penalty1, penalty2, SMVS_SGM_P2_CONSTANT,
-        SMVS_SGM_WINNER_PLANE, depth);
-}
-
-// sgm_stereo.cc:310-346 with p2_mode = SMVS_SGM_P2_ADAPTIVE
-extern "C" int
-smvs_sgm_depth_for_view_mode(int device, const uint8_t *main_img, int w, int h,
-    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth)
-{
-    return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
-        n_neighbors, 0, num_steps, penalty1, penalty2, p2_mode, SMVS_SGM_WINNER_PLANE,
-        depth);
+    smvs_sgm_view_options const o = opts != nullptr ? *opts : smvs_sgm_view_options{};
+    SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h,
+        .channels = channels, .neighbors = neighbors, .neighbor_channels = neighbor_channels,
+        .n_neighbors = n_neighbors, .halvings = halvings,
+        .P = { num_steps, penalty1, penalty2, o.p2_mode, o.winner }, .view_opts = o,
+        .filter = filter,
+        .null_options = opts != nullptr ? nullptr : "null options (p2_mode, winner, merge)",
+        .depth = depth, .checked = checked, .support = support };
+    return sgm_run_view_call(C);
 }
 
 // sgm_stereo.cc:274-306 with opts->winner = SMVS_SGM_WINNER_SUBPLANE in all four
@@ -390,21 +587,28 @@ smvs_sgm_depth_for_view_opts(int device, const uint8_t *main_img, int w, int h,
     const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
     uint16_t penalty1, uint16_t penalty2, const smvs_sgm_options *opts, float *depth)
 {
-    if (int const rc = check_sgm_winner(opts); rc != SMVS_OK)
-        return rc;
-    return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
-        n_neighbors, 0, num_steps, penalty1, penalty2, opts->p2_mode, opts->winner, depth);
+    return smvs_sgm_depth_for_view_raw_opts(device, main_img, w, h, 1, neighbors,
+        SGM_ONE_CHANNEL, n_neighbors, 0, num_steps, penalty1, penalty2, opts, depth);
+}
+
+// sgm_stereo.cc:310-346 with p2_mode = SMVS_SGM_P2_ADAPTIVE
+extern "C" int
+smvs_sgm_depth_for_view_mode(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, int p2_mode, float *depth)
+{
+    smvs_sgm_options const opts = { p2_mode, SMVS_SGM_WINNER_PLANE };
+    return smvs_sgm_depth_for_view_opts(device, main_img, w, h, neighbors, n_neighbors,
+        num_steps, penalty1, penalty2, &opts, depth);
 }
 
 extern "C" int
-smvs_sgm_depth_for_view_raw(int device, const uint8_t *main_img, int w, int h,
-    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
-    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
-    uint16_t penalty2, float *depth)
+smvs_sgm_depth_for_view(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, float *depth)
 {
-    return smvs_sgm_depth_for_view_raw_mode(device, main_img, w, h, channels, neighbors,
-        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2,
-        SMVS_SGM_P2_CONSTANT, depth);
+    return smvs_sgm_depth_for_view_mode(device, main_img, w, h, neighbors, n_neighbors,
+        num_steps, penalty1, penalty2, SMVS_SGM_P2_CONSTANT, depth);
 }
 
 // sgm_stereo.cc:310-346 with p2_mode = SMVS_SGM_P2_ADAPTIVE
@@ -420,178 +624,27 @@ smvs_sgm_depth_for_view_raw_mode(int device, const uint8_t *main_img, int w, int
         depth);
 }
 
-// sgm_stereo.cc:274-306 with opts->winner = SMVS_SGM_WINNER_SUBPLANE in all four
-// runs of the view
 extern "C" int
-smvs_sgm_depth_for_view_raw_opts(int device, const uint8_t *main_img, int w, int h,
+smvs_sgm_depth_for_view_raw(int device, const uint8_t *main_img, int w, int h,
     int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
     int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
-    uint16_t penalty2, const smvs_sgm_options *opts, float *depth)
+    uint16_t penalty2, float *depth)
 {
-    if (int const rc = check_sgm_winner(opts); rc != SMVS_OK)
-        return rc;
-    int const p2_mode = opts->p2_mode;
-    SMVS_REQUIRE(p2_mode == SMVS_SGM_P2_CONSTANT || p2_mode == SMVS_SGM_P2_ADAPTIVE,
-        "unknown penalty2 mode");
-    SMVS_REQUIRE(channels == 1 || channels == 3, "1 or 3 channels");
-    SMVS_REQUIRE(neighbor_channels != nullptr, "null argument");
-    for (int k = 0; k < n_neighbors && k < 2; ++k)
-        SMVS_REQUIRE(neighbor_channels[k] == 1 || neighbor_channels[k] == 3,
-            "1 or 3 channels");
-    return sgm_depth_for_view_impl(device, main_img, w, h, channels, neighbors,
-        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, p2_mode,
-        opts->winner, depth);
-}
-
-
-// The front end with SMVS_SGM_MERGE_CONSENSUS: 2 n runs, the neighbour images
-// one at a time through the slots of neighbour 0, the n forward and n backward
-// maps kept, then the fused kernel.
-static int
-sgm_depth_for_view_consensus(int device, const uint8_t *main_img, int w, int h,
-    int main_channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
-    int n_neighbors, int halvings, int num_steps, uint16_t penalty1, uint16_t penalty2,
-    const smvs_sgm_view_options *opts, float *depth, float *checked, uint8_t *support,
-    const smvs_sgm_filter_options *filter = nullptr)
-{
-    int const p2_mode = opts->p2_mode;
-    SgmRunParams const P = { num_steps, penalty1, penalty2, p2_mode, opts->winner };
-    int rc;
-    if ((rc = check_sgm_penalties(penalty1, penalty2, p2_mode)) != SMVS_OK
-        || (rc = check_sgm_plane_count(num_steps)) != SMVS_OK)
-        return rc;
-    SMVS_REQUIRE(main_img && neighbors && depth, "null argument");
-    SMVS_REQUIRE(halvings >= 0 && halvings <= 8, "halvings out of range");
-    SMVS_REQUIRE((w >> halvings) > 10 && (h >> halvings) > 8, "image too small");
-    // the SGM-scale sizes ((s + 1) >> 1 per halving, as sgm_prepare_image)
-    int nw[SMVS_MAX_SUBS], nh[SMVS_MAX_SUBS];
-    size_t bwd_at[SMVS_MAX_SUBS + 1] = { 0 };
-    size_t max_nnpix = 0, max_rawpix = 0, max_tmp = 0;
-    for (int k = 0; k < n_neighbors; ++k) {
-        smvs_sgm_neighbor const &N = neighbors[k];
-        SMVS_REQUIRE(N.image && (N.width >> halvings) > 10 && (N.height >> halvings) > 8,
-            "bad neighbour image");
-        int const ch = neighbor_channels != nullptr ? neighbor_channels[k] : 1;
-        // (what sgm_prepare_image asks of its two slots)
-        size_t const rawpix = (size_t)N.width * N.height;
-        size_t const tmp = ch == 1 && halvings == 0 ? 0 : rawpix * (size_t)(ch + 1);
-        max_rawpix = rawpix > max_rawpix ? rawpix : max_rawpix;
-        max_tmp = tmp > max_tmp ? tmp : max_tmp;
-        nw[k] = N.width;
-        nh[k] = N.height;
-        for (int i = 0; i < halvings; ++i) {
-            nw[k] = (nw[k] + 1) >> 1;
-            nh[k] = (nh[k] + 1) >> 1;
-        }
-        size_t const nnpix = (size_t)nw[k] * nh[k];
-        max_nnpix = nnpix > max_nnpix ? nnpix : max_nnpix;
-        bwd_at[k + 1] = bwd_at[k] + nnpix;
-    }
-    WorkspaceLease lease(device);
-    if (lease.w == nullptr)
-        return SMVS_ERR_HIP;
-    Workspace &ws = *lease.w;
-    hipStream_t const stream = ws.stream;
-    SgmProfile prof;
-    SgmWorkspace B(&ws);
-    B.prof = &prof;
-    B.set_filter(filter);
-    uint8_t *d_main = nullptr, *d_nbr = nullptr, *d_tmp = nullptr;
-    int mw = 0, mh = 0;
-    if ((rc = sgm_prepare_image(ws, main_img, w, h, main_channels, halvings, WS_MAIN,
-             WS_RAW, &d_main, &mw, &mh)) != SMVS_OK)
-        return rc;
-    size_t const npix = (size_t)mw * mh;
-    // every buffer at its largest size before the first SGM launch (growing one
-    // waits for the stream): the two slots all neighbour images pass through,
-    // the maps, the volumes
-    float *d_fwd = nullptr, *d_bwd = nullptr, *d_merged = nullptr;
-    uint8_t *d_support = nullptr;
-    uint32_t *d_speckle = nullptr;
-    if (sgm_speckle_on(filter) && (rc = sgm_speckle_ensure(ws, npix, &d_speckle)))
-        return rc;
-    if ((rc = ws.ensure(WS_NBR0, max_rawpix, &d_nbr))
-        || (max_tmp != 0 && (rc = ws.ensure(WS_RAW0, max_tmp, &d_tmp)))
-        || (rc = ws.ensure(WS_FWDN, npix * (size_t)n_neighbors, &d_fwd))
-        || (rc = ws.ensure(WS_BWDN, bwd_at[n_neighbors], &d_bwd))
-        || (rc = ws.ensure(WS_FWD0, npix, &d_merged))
-        || (rc = ws.ensure(WS_SUPPORT, npix, &d_support))
-        || (rc = B.ensure(npix > max_nnpix ? npix : max_nnpix, num_steps,
-                sgm_path_plan_here(num_steps,
-                    SgmWorkspace::largest_penalty2(penalty1, penalty2, p2_mode)))))
-        return rc;
-    CheckMergeArgs A;
-    for (int k = 0; k < n_neighbors; ++k) {
-        smvs_sgm_neighbor const &N = neighbors[k];
-        int pw = 0, ph = 0;
-        if ((rc = sgm_prepare_image(ws, N.image, N.width, N.height,
-                 neighbor_channels != nullptr ? neighbor_channels[k] : 1, halvings, WS_NBR0,
-                 WS_RAW0, &d_nbr, &pw, &ph)) != SMVS_OK)
-            return rc;
-        SMVS_REQUIRE(pw == nw[k] && ph == nh[k], "SGM-scale size of a neighbour");
-        // SGMStereo::reconstruct, sgm_stereo.cc:46-62, as in the reference's merge
-        if ((rc = sgm_run_device(B, d_main, mw, mh, d_nbr, pw, ph, N.M_fwd, N.t_fwd,
-                N.range_main[0], N.range_main[1], P, d_fwd + npix * (size_t)k)) != SMVS_OK)
-            return rc;
-        if ((rc = sgm_run_device(B, d_nbr, pw, ph, d_main, mw, mh, N.M_bwd, N.t_bwd,
-                N.range_neighbor[0], N.range_neighbor[1], P, d_bwd + bwd_at[k])) != SMVS_OK)
-            return rc;
-        fill_check_neighbor(&A.nb[k], d_bwd + bwd_at[k], pw, ph, N.M_fwd, N.t_fwd);
-    }
-    for (int k = n_neighbors; k < SMVS_MAX_SUBS; ++k)
-        A.nb[k] = A.nb[0];
-    A.fwd = d_fwd;
-    A.merged = d_merged;
-    A.checked = checked != nullptr ? d_fwd : nullptr;      // in place
-    A.support = support != nullptr ? d_support : nullptr;
-    A.w = mw;
-    A.h = mh;
-    A.min_agree = opts->min_agree;
-    A.agree_ratio = opts->agree_ratio;
-    if ((rc = launch_check_merge(A, n_neighbors, &prof, stream)) != SMVS_OK)
-        return rc;
-    // (checked and support are those of the merge: the speckle filter sees the
-    // merged map only)
-    if (sgm_speckle_on(filter)
-        && (rc = sgm_launch_speckle(ws, &prof, d_merged, mw, mh, filter->speckle_size,
-                filter->speckle_ratio, d_speckle, d_merged, false)) != SMVS_OK)
-        return rc;
-    if (checked != nullptr
-        && (rc = ws.download(checked, d_fwd, sizeof(float) * npix * (size_t)n_neighbors)))
-        return rc;
-    if (support != nullptr && (rc = ws.download(support, d_support, npix)))
-        return rc;
-    return ws.download(depth, d_merged, sizeof(float) * npix);
-}
-
-// (filter: null in the entries without the filters)
-static int
-sgm_depth_for_view_merge_impl(int device, const uint8_t *main_img, int w, int h,
-    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_view_options *opts,
-    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support)
-{
-    if (int const rc = check_sgm_view_options(opts, n_neighbors); rc != SMVS_OK)
-        return rc;
-    if (opts->merge == SMVS_SGM_MERGE_REFERENCE) {
-        SMVS_REQUIRE(checked == nullptr && support == nullptr,
-            "checked and support are outputs of the consensus merge");
-        return sgm_depth_for_view_impl(device, main_img, w, h, 1, neighbors, nullptr,
-            n_neighbors, 0, num_steps, penalty1, penalty2, opts->p2_mode, opts->winner,
-            depth, filter);
-    }
-    return sgm_depth_for_view_consensus(device, main_img, w, h, 1, neighbors, nullptr,
-        n_neighbors, 0, num_steps, penalty1, penalty2, opts, depth, checked, support, filter);
+    return smvs_sgm_depth_for_view_raw_mode(device, main_img, w, h, channels, neighbors,
+        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2,
+        SMVS_SGM_P2_CONSTANT, depth);
 }
 
 extern "C" int
-smvs_sgm_depth_for_view_merge(int device, const uint8_t *main_img, int w, int h,
-    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
-    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_view_options *opts,
-    float *depth, float *checked, uint8_t *support)
+smvs_sgm_depth_for_view_raw_merge(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_view_options *opts, float *depth, float *checked,
+    uint8_t *support)
 {
-    return sgm_depth_for_view_merge_impl(device, main_img, w, h, neighbors, n_neighbors,
-        num_steps, penalty1, penalty2, opts, nullptr, depth, checked, support);
+    return smvs_sgm_depth_for_view_raw_filtered(device, main_img, w, h, channels, neighbors,
+        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, opts,
+        &SGM_FILTERS_OFF, depth, checked, support);
 }
 
 // smvs_sgm_depth_for_view_merge with the uniqueness test in every run of the
@@ -602,65 +655,19 @@ smvs_sgm_depth_for_view_filtered(int device, const uint8_t *main_img, int w, int
     uint16_t penalty1, uint16_t penalty2, const smvs_sgm_view_options *opts,
     const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support)
 {
-    if (int const rc = check_sgm_filter(filter, false); rc != SMVS_OK)
-        return rc;
-    return sgm_depth_for_view_merge_impl(device, main_img, w, h, neighbors, n_neighbors,
-        num_steps, penalty1, penalty2, opts, filter, depth, checked, support);
-}
-
-static int
-sgm_depth_for_view_raw_merge_impl(int device, const uint8_t *main_img, int w, int h,
-    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
-    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
-    uint16_t penalty2, const smvs_sgm_view_options *opts,
-    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support)
-{
-    if (int const rc = check_sgm_view_options(opts, n_neighbors); rc != SMVS_OK)
-        return rc;
-    SMVS_REQUIRE(opts->p2_mode == SMVS_SGM_P2_CONSTANT
-            || opts->p2_mode == SMVS_SGM_P2_ADAPTIVE, "unknown penalty2 mode");
-    SMVS_REQUIRE(channels == 1 || channels == 3, "1 or 3 channels");
-    SMVS_REQUIRE(neighbor_channels != nullptr, "null argument");
-    for (int k = 0; k < n_neighbors; ++k)
-        SMVS_REQUIRE(neighbor_channels[k] == 1 || neighbor_channels[k] == 3,
-            "1 or 3 channels");
-    if (opts->merge == SMVS_SGM_MERGE_REFERENCE) {
-        SMVS_REQUIRE(checked == nullptr && support == nullptr,
-            "checked and support are outputs of the consensus merge");
-        return sgm_depth_for_view_impl(device, main_img, w, h, channels, neighbors,
-            neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2,
-            opts->p2_mode, opts->winner, depth, filter);
-    }
-    return sgm_depth_for_view_consensus(device, main_img, w, h, channels, neighbors,
-        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, opts, depth,
-        checked, support, filter);
+    return smvs_sgm_depth_for_view_raw_filtered(device, main_img, w, h, 1, neighbors,
+        SGM_ONE_CHANNEL, n_neighbors, 0, num_steps, penalty1, penalty2, opts, filter, depth,
+        checked, support);
 }
 
 extern "C" int
-smvs_sgm_depth_for_view_raw_merge(int device, const uint8_t *main_img, int w, int h,
-    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
-    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
-    uint16_t penalty2, const smvs_sgm_view_options *opts, float *depth, float *checked,
-    uint8_t *support)
+smvs_sgm_depth_for_view_merge(int device, const uint8_t *main_img, int w, int h,
+    const smvs_sgm_neighbor *neighbors, int n_neighbors, int num_steps,
+    uint16_t penalty1, uint16_t penalty2, const smvs_sgm_view_options *opts,
+    float *depth, float *checked, uint8_t *support)
 {
-    return sgm_depth_for_view_raw_merge_impl(device, main_img, w, h, channels, neighbors,
-        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, opts, nullptr,
-        depth, checked, support);
-}
-
-// smvs_sgm_depth_for_view_raw_merge with the filters
-extern "C" int
-smvs_sgm_depth_for_view_raw_filtered(int device, const uint8_t *main_img, int w, int h,
-    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
-    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
-    uint16_t penalty2, const smvs_sgm_view_options *opts,
-    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support)
-{
-    if (int const rc = check_sgm_filter(filter, false); rc != SMVS_OK)
-        return rc;
-    return sgm_depth_for_view_raw_merge_impl(device, main_img, w, h, channels, neighbors,
-        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, opts, filter,
-        depth, checked, support);
+    return smvs_sgm_depth_for_view_filtered(device, main_img, w, h, neighbors, n_neighbors,
+        num_steps, penalty1, penalty2, opts, &SGM_FILTERS_OFF, depth, checked, support);
 }
 
 // the fused kernel alone, on the caller's maps
@@ -708,16 +715,8 @@ smvs_sgm_check_merge(int device, const float *fwd, int w, int h,
             return rc;
         fill_check_neighbor(&A.nb[k], d_bwd + bwd_at[k], N.width, N.height, N.M_fwd, N.t_fwd);
     }
-    for (int k = n_neighbors; k < SMVS_MAX_SUBS; ++k)
-        A.nb[k] = A.nb[0];
-    A.fwd = d_fwd;
-    A.merged = d_merged;
-    A.checked = checked != nullptr ? d_fwd : nullptr;      // in place
-    A.support = d_support;
-    A.w = w;
-    A.h = h;
-    A.min_agree = o.min_agree;
-    A.agree_ratio = o.agree_ratio;
+    fill_check_merge(&A, n_neighbors, d_fwd, d_merged, checked != nullptr, d_support, w, h,
+        o.min_agree, o.agree_ratio);
     if ((rc = launch_check_merge(A, n_neighbors, &prof, ws.stream)) != SMVS_OK)
         return rc;
     if (checked != nullptr

@@ -557,6 +557,14 @@ def bilateral_upsample(dm, ci, sigma=5.0, kernel_size=5, device=0):
     return out
 
 
+def _halved(w, h, halvings):
+    """(w, h) after `halvings` half-size steps, (s + 1) // 2 each: the size of
+    the device's output for a raw image."""
+    for _ in range(max(int(halvings or 0), 0)):
+        w, h = (w + 1) // 2, (h + 1) // 2
+    return w, h
+
+
 def rescale_half_gaussian(image, halvings=1, device=0):
     """smvs_rescale_half_gaussian: `halvings` chained rescale_half_size_gaussian
     of a u8 image (h, w) or (h, w, c), c = 1..4, on the device
@@ -567,9 +575,7 @@ def rescale_half_gaussian(image, halvings=1, device=0):
     if squeeze:
         a = a[:, :, None]
     h, w, c = a.shape
-    ow, oh = w, h
-    for _ in range(max(halvings, 0)):
-        ow, oh = (ow + 1) // 2, (oh + 1) // 2
+    ow, oh = _halved(w, h, halvings)
     out = np.zeros((oh, ow, c), np.uint8)
     gw, gh = C.c_int(0), C.c_int(0)
     check(lib.smvs_rescale_half_gaussian(C.c_int(device), _p(a, _u8p), C.c_int(w),
@@ -614,9 +620,7 @@ def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0
     (0, 1, 0, 0.95) are defaults of a user option, untuned, and nobody has
     measured them on real scenes."""
     lib = _capi.load()
-    opts = _sgm_options(adaptive_p2, subplane)
     main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
-    h, w = main_img.shape[:2]
     filt = _sgm_filter(uniqueness, uniqueness_window, speckle_size, speckle_ratio)
     if consensus or want_checked or filt is not None:
         if want_checked and not consensus:
@@ -626,26 +630,9 @@ def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0
             lib, main_img, neighbors, num_steps, p1, p2, device,
             _sgm_view_options(adaptive_p2, subplane, consensus, agree_ratio, min_agree),
             None if halvings is None else int(halvings), want_checked, filt)
-    if halvings is not None:
-        return _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device,
-                                       opts, int(halvings))
-    keep = []
-    arr = (SgmNeighbor * len(neighbors))()
-    for k, nb in enumerate(neighbors):
-        img = np.ascontiguousarray(nb["image"], dtype=np.uint8)
-        keep.append(img)
-        arr[k].image = _p(img, _u8p)
-        arr[k].height, arr[k].width = img.shape
-        for name, n in (("M_fwd", 9), ("t_fwd", 3), ("M_bwd", 9), ("t_bwd", 3),
-                        ("range_main", 2), ("range_neighbor", 2)):
-            v = _f32(nb[name]).reshape(n)
-            for i in range(n):
-                getattr(arr[k], name)[i] = float(v[i])
-    depth = np.zeros((h, w), dtype=np.float32)
-    check(lib.smvs_sgm_depth_for_view_opts(device, _p(main_img, _u8p), w, h, arr,
-          len(neighbors), num_steps, C.c_uint16(p1), C.c_uint16(p2), C.byref(opts),
-          _p(depth, _fp)))
-    return depth
+    return _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device,
+                                   _sgm_options(adaptive_p2, subplane),
+                                   None if halvings is None else int(halvings))
 
 
 def _sgm_neighbors(neighbors, keep):
@@ -665,15 +652,21 @@ def _sgm_neighbors(neighbors, keep):
 
 def _sgm_depth_for_view_raw(lib, main_img, neighbors, num_steps, p1, p2, device, opts,
                             halvings):
+    """smvs_sgm_depth_for_view_opts (halvings None) / _raw_opts."""
     keep = []
     arr = _sgm_neighbors(neighbors, keep)
     h, w = main_img.shape[:2]
+    ow, oh = _halved(w, h, halvings)
+    depth = np.zeros((oh, ow), dtype=np.float32)
+    if halvings is None:
+        if main_img.ndim != 2 or any(k.ndim != 2 for k in keep):
+            raise ValueError("one-channel images at SGM scale (or pass halvings)")
+        check(lib.smvs_sgm_depth_for_view_opts(device, _p(main_img, _u8p), w, h, arr,
+              len(neighbors), num_steps, C.c_uint16(p1), C.c_uint16(p2), C.byref(opts),
+              _p(depth, _fp)))
+        return depth
     channels = 1 if main_img.ndim == 2 else main_img.shape[2]
     nch = (C.c_int * len(neighbors))(*[1 if k.ndim == 2 else k.shape[2] for k in keep])
-    ow, oh = w, h
-    for _ in range(halvings):
-        ow, oh = (ow + 1) // 2, (oh + 1) // 2
-    depth = np.zeros((oh, ow), dtype=np.float32)
     check(lib.smvs_sgm_depth_for_view_raw_opts(device, _p(main_img, _u8p), w, h, channels,
           arr, nch, len(neighbors), halvings, num_steps, C.c_uint16(p1), C.c_uint16(p2),
           C.byref(opts), _p(depth, _fp)))
@@ -688,9 +681,7 @@ def _sgm_depth_for_view_merge(lib, main_img, neighbors, num_steps, p1, p2, devic
     arr = _sgm_neighbors(neighbors, keep)
     n = len(neighbors)
     h, w = main_img.shape[:2]
-    oh, ow = h, w
-    for _ in range(halvings or 0):
-        ow, oh = (ow + 1) // 2, (oh + 1) // 2
+    ow, oh = _halved(w, h, halvings)
     depth = np.zeros((oh, ow), dtype=np.float32)
     checked = np.zeros((n, oh, ow), dtype=np.float32) if want_checked else None
     support = np.zeros((oh, ow), dtype=np.uint8) if want_checked else None
@@ -809,9 +800,7 @@ def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2
             raise ValueError("want_volumes: the volumes are outputs of the SGM-scale entry")
         channels = 1 if main_img.ndim == 2 else main_img.shape[2]
         nch = (C.c_int * max(n, 1))(*[1 if k.ndim == 2 else k.shape[2] for k in keep])
-        ow, oh = w, h
-        for _ in range(int(halvings)):
-            ow, oh = (ow + 1) // 2, (oh + 1) // 2
+        ow, oh = _halved(w, h, halvings)
         depth = np.zeros((oh, ow), dtype=np.float32)
         support = np.zeros((oh, ow), dtype=np.uint8)
         if filt is not None:
