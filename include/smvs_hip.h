@@ -707,12 +707,14 @@ int smvs_sgm_sweep_for_view_raw_filtered(int device, const uint8_t *main_img, in
     int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
     uint16_t penalty2, const smvs_sgm_sweep_options *opts,
     const smvs_sgm_filter_options *filter, float *depth, uint8_t *support);
-/* The 14 view and sweep entries above are three front ends behind one call
- * record (csrc/sgm_internal.h, SgmViewCall): an entry fixes the fields it does
- * not take and hands on the rest.  "SGM scale": channels = 1 for the main image
+/* The 16 view and sweep entries (14 above, the two with the photo test below)
+ * are three front ends behind one call record (csrc/sgm_internal.h,
+ * SgmViewCall): an entry fixes the fields it does not take and hands on the
+ * rest.  "SGM scale": channels = 1 for the main image
  * and every neighbour, halvings = 0.  "constant, plane": p2_mode =
  * SMVS_SGM_P2_CONSTANT, winner = SMVS_SGM_WINNER_PLANE.  "off": both filters off
- * (uniqueness = 0, speckle_size = 0), no runner_up.
+ * (uniqueness = 0, speckle_size = 0), no runner_up.  Every entry but the last two
+ * also fixes the photo test: off (radius 0), no witness, no confidence, no views.
  *
  *   entry                                 front                 fixes
  *   smvs_sgm_depth_for_view               reference merge       SGM scale; constant, plane; off
@@ -729,11 +731,109 @@ int smvs_sgm_sweep_for_view_raw_filtered(int device, const uint8_t *main_img, in
  *   smvs_sgm_sweep_for_view_filtered      plane sweep           SGM scale
  *   smvs_sgm_sweep_for_view_raw           plane sweep           off; no argmin, cost, sgm
  *   smvs_sgm_sweep_for_view_raw_filtered  plane sweep           no argmin, cost, sgm, runner_up
+ *   smvs_sgm_depth_for_view_raw_photo     opts->merge: either   nothing
+ *   smvs_sgm_sweep_for_view_raw_photo     plane sweep           nothing
  *
  * The reference merge has the depth map as its only output (checked and support
  * must be NULL); the consensus adds checked and support; the sweep's outputs
- * are all optional.  All 14 make their argument checks in one order, before
+ * are all optional.  All 16 make their argument checks in one order, before
  * any device call (csrc/sgm_view.hip, check_sgm_view_call). */
+
+/* Multi-view photo-consistency test.  Not in the reference; opt-in, off by
+ * default (radius 0), and with it off the two entries below give the bytes and
+ * the launches of the `_filtered` entries.  A depth of the view's final map is
+ * kept only where the main image around the pixel, warped at that depth, agrees
+ * with the best few of n witness images; the same kernel gives a per-pixel
+ * confidence.  The definition is normative (tests/sgm_photo_ref.py restates it).
+ *
+ * Inputs: the main image I (u8, w x h, one channel, at SGM scale); a depth map a
+ * of w x h floats in the depth convention of the SGM planes (what every front
+ * end produces); n witnesses (1 <= n <= 16), each a u8 image of nw x nh and the
+ * float reprojection M[9], t[3] main -> witness; radius r in 1 .. 3
+ * (N = (2 r + 1)^2), best_k (0: all), min_views, min_score.
+ *
+ * A pixel is valid iff a > 0.0f (a NaN is not: the speckle filter's rule).  A
+ * pixel that is not valid keeps its bits and gets confidence -1.0f and views 0.
+ *
+ * For a valid pixel (x, y) and a witness k, j = -r .. r (outer), i = -r .. r
+ * (inner):
+ *     xc = clamp(x + i, 0, w - 1), yc = clamp(y + j, 0, h - 1), A = I[yc][xc];
+ *     (B, inside) = the sample of warped_neighbors_for_depth
+ *         (sgm_stereo.cc:163-188) for main pixel (xc, yc) at THE CENTRE PIXEL'S
+ *         depth a(x, y), evaluated as the warp kernel of the runs evaluates it:
+ *         float, contraction off, px = 0.5f + xc, py = 0.5f + yc, the three-term
+ *         sums from 0.0f, p = (M (px, py, 1)) * a + t, two IEEE divisions by
+ *         p2, - 0.5f, the u8 linear_at with + 0.5f.  One difference: inside is
+ *         stated positively,
+ *             inside = !(p2 < 0) && p0 >= 0 && p1 >= 0 && p0 <= nw - 1
+ *                      && p1 <= nh - 1,
+ *         so a coordinate that is not a number is outside; for every other input
+ *         this is the reference's test;
+ *     integer sums: SA += A, SB += B, SAB += A B, SAA += A A, SBB += B B (all
+ *         below 2^31 for r <= 3).
+ * Witness k is defined iff all N samples were inside.  Then
+ *     cov = N SAB - SA SB,  va = N SAA - SA^2,  vb = N SBB - SB^2,
+ *     score_k = 0.0 if va == 0 || vb == 0 (a flat window is no evidence), else
+ *     score_k = (double)(cov |cov|) / (double)(va vb):
+ * both products are exact integers below 2^53, the score is one IEEE double
+ * division: the signed squared correlation in [-1, 1].  (Not the NCC itself, on
+ * purpose: no square root, so nothing but correctly rounded + - x / decides a
+ * bit.)
+ * Per pixel, with c the number of defined witnesses and
+ * k' = min(best_k ? best_k : n, c):
+ *     confidence = -1.0f if c < max(min_views, 1), else
+ *         (float)((s_1 + s_2 + ... + s_k') / (double)k'), the defined scores in
+ *         descending order, added in that order in double;
+ *     out = 0.0f where confidence < min_score (a float comparison: a pixel
+ *         exactly at the bound is kept), else the input's bits;
+ *     views = c as u8.
+ * min_score = -1 drops nothing (confidence only).
+ *
+ * In the two view entries `neighbors` (and neighbor_channels) hold
+ * n_neighbors + n_witness entries, at most 16: the first n_neighbors go through
+ * the front exactly as in the `_filtered` entry, ALL of them are witnesses (of a
+ * witness behind n_neighbors only image, width, height, M_fwd and t_fwd are
+ * read).  Every image is uploaded and prepared once per call.  The test runs on
+ * the final map of the view, before the speckle removal; checked and support
+ * stay those of the unfiltered map.  One launch, timed in class
+ * SMVS_SGM_K_MERGE of smvs_sgm_profile.  The defaults of the layers above
+ * (radius 0, best_k 2, min_views 2, min_score 0.49) are defaults of a user
+ * option, untuned; nobody has measured them on real scenes.
+ *
+ * SMVS_ERR_INVALID before any device call, behind the checks of the `_filtered`
+ * entry and in this order: a NULL photo pointer; radius outside 0 .. 3; best_k
+ * or min_views outside 0 .. n_neighbors + n_witness; min_score outside [-1, 1]
+ * or NaN; n_witness < 0 or more than 16 entries in all; with radius 0 a
+ * witness, a confidence or a views output (an error, never silently ignored);
+ * a witness without an image, with a size below 1 x 1 at SGM scale or with a
+ * channel count other than 1 or 3. */
+typedef struct { int radius; int best_k; int min_views; float min_score; } smvs_sgm_photo_options;
+
+/* smvs_sgm_depth_for_view_raw_filtered with the test; extra optional outputs
+ * confidence[w * h] (f32) and views[w * h] (u8) at SGM scale. */
+int smvs_sgm_depth_for_view_raw_photo(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_view_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support,
+    int n_witness, const smvs_sgm_photo_options *photo, float *confidence, uint8_t *views);
+/* smvs_sgm_sweep_for_view_filtered on raw images (every optional output of it)
+ * with the test */
+int smvs_sgm_sweep_for_view_raw_photo(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_sweep_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint8_t *support,
+    uint16_t *cost, uint16_t *sgm, uint16_t *runner_up, int n_witness,
+    const smvs_sgm_photo_options *photo, float *confidence, uint8_t *views);
+/* The kernel alone, on a map and SGM-scale images of the caller: main_img
+ * [w * h], depth[w * h], out[w * h] (may be depth itself), confidence[w * h] and
+ * views[w * h] (either may be NULL); of a witness only image, width, height,
+ * M_fwd and t_fwd are read.  No minimum size; w * h < 2^31 for every image.
+ * radius in 1 .. 3, n in 1 .. 16, the other options as above. */
+int smvs_sgm_photo_check(int device, const uint8_t *main_img, int w, int h, const float *depth,
+    const smvs_sgm_neighbor *witnesses, int n, const smvs_sgm_photo_options *opts, float *out,
+    float *confidence, uint8_t *views);
 
 /* The speckle kernels alone, on a map of the caller: depth[w * h], out[w * h]
  * (may be depth itself), size[w * h] (may be NULL); w * h < 2^31.  The kernels

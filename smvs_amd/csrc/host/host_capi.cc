@@ -416,6 +416,46 @@ check_host_sgm_filter(const smvs_host_sgm_filter *f, char const* who)
 }
 }
 
+namespace {
+// the accepted set of include/smvs_hip.h as far as it does not depend on the
+// witnesses there are (a NaN score fails the comparisons)
+void
+check_host_sgm_photo(const smvs_host_sgm_photo *p, char const* who)
+{
+    if (p == nullptr)
+        return;
+    if (p->radius < 0 || p->radius > 3 || p->best_k < 0 || p->best_k > SMVS_MAX_SUBS
+        || p->min_views < 0 || p->min_views > SMVS_MAX_SUBS
+        || !(p->min_score >= -1.0f && p->min_score <= 1.0f) || p->witnesses < -1
+        || p->witnesses > SMVS_MAX_SUBS)
+        throw std::invalid_argument(std::string(who) + ": sgm_photo_radius must be in [0, 3], "
+            "sgm_photo_best_k and sgm_photo_min_views in [0, 16], sgm_photo_min_score in "
+            "[-1, 1] and sgm_photo_witnesses -1 or in [0, 16]");
+}
+}
+
+extern "C" int
+smvs_host_sgm_photo_defaults(int *ints8, float *scores2)
+{
+    if (ints8 == nullptr || scores2 == nullptr) {
+        g_host_error = "smvs_host_sgm_photo_defaults: bad argument";
+        return -1;
+    }
+    SGMStereo::Options const opts;
+    ReconSettings const conf;
+    ints8[0] = opts.photo_radius;
+    ints8[1] = opts.photo_best_k;
+    ints8[2] = opts.photo_min_views;
+    ints8[3] = opts.photo_witnesses;
+    ints8[4] = conf.sgm_photo_radius;
+    ints8[5] = conf.sgm_photo_best_k;
+    ints8[6] = conf.sgm_photo_min_views;
+    ints8[7] = conf.sgm_photo_witnesses;
+    scores2[0] = opts.photo_min_score;
+    scores2[1] = conf.sgm_photo_min_score;
+    return 0;
+}
+
 extern "C" int
 smvs_host_sgm_depth_filtered(const smvs_host_view *main_in, const smvs_host_view *subs_in,
     int n_subs, const smvs_host_bundle *bundle_in, int sgm_scale,
@@ -424,8 +464,23 @@ smvs_host_sgm_depth_filtered(const smvs_host_view *main_in, const smvs_host_view
     int min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
     float *depth_out, int *out_w, int *out_h)
 {
+    return smvs_host_sgm_depth_photo(main_in, subs_in, n_subs, bundle_in, sgm_scale, min_depth,
+        max_depth, device, adaptive_penalty2, num_steps, subplane, num_neighbors, consensus,
+        agree_ratio, min_agree, sweep, filter, nullptr, depth_out, nullptr, out_w, out_h);
+}
+
+extern "C" int
+smvs_host_sgm_depth_photo(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, int sgm_scale,
+    float min_depth, float max_depth, int device, int adaptive_penalty2,
+    int num_steps, int subplane, int num_neighbors, int consensus, float agree_ratio,
+    int min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const smvs_host_sgm_photo *photo, float *depth_out, float *confidence_out, int *out_w,
+    int *out_h)
+{
     try {
         check_host_sgm_filter(filter, "smvs_host_sgm_depth_filtered");
+        check_host_sgm_photo(photo, "smvs_host_sgm_depth_photo");
         // (before the views are copied: an argument error needs no image)
         bool const sweep_on = sweep != nullptr && sweep->sweep != 0;
         if (sweep_on && consensus != 0)
@@ -467,8 +522,19 @@ smvs_host_sgm_depth_filtered(const smvs_host_view *main_in, const smvs_host_view
             opts.speckle_size = filter->speckle_size;
             opts.speckle_ratio = filter->speckle_ratio;
         }
+        if (photo != nullptr) {
+            opts.photo_radius = photo->radius;
+            opts.photo_best_k = photo->best_k;
+            opts.photo_min_views = photo->min_views;
+            opts.photo_min_score = photo->min_score;
+            opts.photo_witnesses = photo->witnesses;
+        }
         FloatImage::Ptr d = reconstruct_sgm_depth_for_view(opts, main_view, subs,
             bundle);
+        if (confidence_out != nullptr && main_view->has_embedding("smvs-sgm-confidence")) {
+            FloatImage::Ptr c = main_view->get_embedding("smvs-sgm-confidence");
+            std::memcpy(confidence_out, c->begin(), sizeof(float) * c->get_pixel_amount());
+        }
         if (out_w != nullptr)
             *out_w = d->width();
         if (out_h != nullptr)
@@ -1119,8 +1185,24 @@ smvs_host_reconstruct_scene_filtered(const char *scene_dir,
     const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
     int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used)
 {
+    return smvs_host_reconstruct_scene_photo(scene_dir, o, flags, sgm_num_steps, sgm_subplane,
+        sgm_neighbors, sgm_consensus, sgm_agree_ratio, sgm_min_agree, sweep, filter, nullptr,
+        view_ids, n_view_ids, reconstructed_out, max_reconstructed, n_reconstructed, n_skipped,
+        seconds, input_scale_used);
+}
+
+extern "C" int
+smvs_host_reconstruct_scene_photo(const char *scene_dir,
+    const smvs_host_recon_settings *o, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const smvs_host_sgm_photo *photo, const int *view_ids, int n_view_ids,
+    int *reconstructed_out, int max_reconstructed, int *n_reconstructed, int *n_skipped,
+    double *seconds, int *input_scale_used)
+{
     try {
         check_host_sgm_filter(filter, "smvs_host_reconstruct_scene_filtered");
+        check_host_sgm_photo(photo, "smvs_host_reconstruct_scene_photo");
         bool const sweep_on = sweep != nullptr && sweep->sweep != 0;
         if (sweep_on && sgm_consensus != 0)
             throw std::invalid_argument("smvs_host_reconstruct_scene_sweep: sgm_sweep and "
@@ -1182,6 +1264,13 @@ smvs_host_reconstruct_scene_filtered(const char *scene_dir,
             conf.sgm_uniqueness_window = filter->uniqueness_window;
             conf.sgm_speckle_size = filter->speckle_size;
             conf.sgm_speckle_ratio = filter->speckle_ratio;
+        }
+        if (photo != nullptr) {
+            conf.sgm_photo_radius = photo->radius;
+            conf.sgm_photo_best_k = photo->best_k;
+            conf.sgm_photo_min_views = photo->min_views;
+            conf.sgm_photo_min_score = photo->min_score;
+            conf.sgm_photo_witnesses = photo->witnesses;
         }
         conf.device_input_scaling = (flags & SMVS_HOST_SCENE_DEVICE_INPUT_SCALING) != 0u;
         conf.device_shading_prep = (flags & SMVS_HOST_SCENE_DEVICE_SHADING_PREP) != 0u;

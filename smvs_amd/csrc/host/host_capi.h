@@ -203,6 +203,34 @@ int smvs_host_sgm_depth_filtered(const smvs_host_view *main_view,
     int adaptive_penalty2, int num_steps, int subplane, int num_neighbors,
     int consensus, float agree_ratio, int min_agree, const smvs_host_sgm_sweep *sweep,
     const smvs_host_sgm_filter *filter, float *depth_out, int *out_w, int *out_h);
+/* SGMStereo::Options::photo_radius / photo_best_k / photo_min_views /
+ * photo_min_score / photo_witnesses (the multi-view photo-consistency test of
+ * include/smvs_hip.h; not in the reference). */
+typedef struct {
+    int radius, best_k, min_views;
+    float min_score;
+    int witnesses;
+} smvs_host_sgm_photo;
+/* smvs_host_sgm_depth_filtered with the photo-consistency test, for any of the
+ * three front ends: its witnesses are the first `witnesses` of subs (-1: all, 16
+ * at the most; never fewer than the front end uses).  radius outside 0 .. 3,
+ * best_k or min_views outside 0 .. 16, min_score outside [-1, 1] or NaN and
+ * witnesses outside -1 .. 16 are argument errors before anything runs; the
+ * device refuses a best_k or min_views above the witnesses there are.
+ * confidence_out (may be NULL): the confidence map, written with the test on.
+ * photo == NULL or radius 0: off; smvs_host_sgm_depth_filtered forwards to this
+ * with NULL. */
+int smvs_host_sgm_depth_photo(const smvs_host_view *main_view,
+    const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
+    int sgm_scale, float min_depth, float max_depth, int device,
+    int adaptive_penalty2, int num_steps, int subplane, int num_neighbors,
+    int consensus, float agree_ratio, int min_agree, const smvs_host_sgm_sweep *sweep,
+    const smvs_host_sgm_filter *filter, const smvs_host_sgm_photo *photo, float *depth_out,
+    float *confidence_out, int *out_w, int *out_h);
+/* The photo options as a default-constructed SGMStereo::Options (ints8[0 .. 3],
+ * scores2[0]) and ReconSettings (ints8[4 .. 7], scores2[1]) hold them: radius,
+ * best_k, min_views, witnesses; min_score (no device involved). */
+int smvs_host_sgm_photo_defaults(int *ints8, float *scores2);
 /* The filter options as a default-constructed SGMStereo::Options (ints6[0 .. 2],
  * ratios2[0]) and ReconSettings (ints6[3 .. 5], ratios2[1]) hold them, in the
  * order of smvs_host_sgm_filter (no device involved). */
@@ -376,6 +404,21 @@ int smvs_host_reconstruct_scene_filtered(const char *scene_dir,
     int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
     const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
     int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used);
+
+/* The same with ReconSettings::sgm_photo_radius / sgm_photo_best_k /
+ * sgm_photo_min_views / sgm_photo_min_score / sgm_photo_witnesses: the
+ * photo-consistency test behind every view's SGM front end, the confidence saved
+ * as smvs-sgm-confidence.  A value outside the accepted set is an argument error
+ * before the scene is read; photo == NULL: off
+ * (smvs_host_reconstruct_scene_filtered forwards to this with NULL).  The reuse
+ * rule is that of sgm_subplane (force_sgm). */
+int smvs_host_reconstruct_scene_photo(const char *scene_dir,
+    const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const smvs_host_sgm_photo *photo, const int *view_ids, int n_view_ids,
+    int *reconstructed_out, int max_reconstructed, int *n_reconstructed, int *n_skipped,
+    double *seconds, int *input_scale_used);
 
 /* smvsrecon's generate_mesh (app/smvsrecon.cc:278-343, MeshGenerator::
  * generate_mesh, lib/mesh_generator.cc:160-299) on a reconstructed scene: the

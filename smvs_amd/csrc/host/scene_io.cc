@@ -597,10 +597,18 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                         sgm_opts.uniqueness_window = conf.sgm_uniqueness_window;
                         sgm_opts.speckle_size = conf.sgm_speckle_size;
                         sgm_opts.speckle_ratio = conf.sgm_speckle_ratio;
+                        sgm_opts.photo_radius = conf.sgm_photo_radius;
+                        sgm_opts.photo_best_k = conf.sgm_photo_best_k;
+                        sgm_opts.photo_min_views = conf.sgm_photo_min_views;
+                        sgm_opts.photo_min_score = conf.sgm_photo_min_score;
+                        sgm_opts.photo_witnesses = conf.sgm_photo_witnesses;
                         (void)reconstruct_sgm_depth_for_view(sgm_opts, main_view,
                             stereo_views, bundle);
                         save_mvei(view.image_path("smvs-sgm"),
                             main_view->get_embedding("smvs-sgm"));
+                        if (main_view->has_embedding("smvs-sgm-confidence"))
+                            save_mvei(view.image_path("smvs-sgm-confidence"),
+                                main_view->get_embedding("smvs-sgm-confidence"));
                     } else {
                         main_view->write_image_to_view(
                             load_mvei_float(view.image_path("smvs-sgm")), "smvs-sgm");

@@ -137,6 +137,18 @@ struct ReconSettings
     int sgm_uniqueness_window = 1;
     int sgm_speckle_size = 0;
     float sgm_speckle_ratio = 0.95f;
+    // SGMStereo::Options::photo_radius / photo_best_k / photo_min_views /
+    // photo_min_score / photo_witnesses -- the multi-view photo-consistency test
+    // of include/smvs_hip.h behind every view's SGM front end, whichever of the
+    // three it is, with the view's neighbours as witnesses (-1: all num_neighbors
+    // of them); the confidence is saved as smvs-sgm-confidence next to smvs-sgm.
+    // Off by default (radius 0); untuned defaults of a user option; the reuse
+    // rule is that of sgm_subplane (force_sgm).
+    int sgm_photo_radius = 0;
+    int sgm_photo_best_k = 2;
+    int sgm_photo_min_views = 2;
+    float sgm_photo_min_score = 0.49f;
+    int sgm_photo_witnesses = -1;
     // not in the reference's AppSettings: the input scaling of :621-650 on the
     // device (rescale_half_size_gaussian_device), one ViewQueue task per view
     bool device_input_scaling = false;

@@ -150,9 +150,12 @@ prepare_pair(SGMStereo::Options const& o, StereoView::Ptr main_view,
     }
 }
 
+// pairs: the n_front neighbours of the front end, then the further witnesses
+// of the photo-consistency test (none with the test off); *confidence: its map
+// when it is on
 FloatImage::Ptr
 run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
-    std::vector<PairInputs> const& pairs)
+    std::vector<PairInputs> const& pairs, int n_front, FloatImage::Ptr* confidence)
 {
     std::vector<smvs_sgm_neighbor> dev;
     std::vector<int> channels;
@@ -163,7 +166,8 @@ run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
     ByteImage::ConstPtr main_bytes = main_view->get_raw_bytes();
     uint8_t const* const pixels = main_bytes->begin();
     int const fw = main_bytes->width(), fh = main_bytes->height();
-    int const fc = main_bytes->channels(), n = (int)dev.size();
+    int const fc = main_bytes->channels(), n = n_front;
+    int const n_witness = (int)dev.size() - n_front;
     int w = fw, h = fh;
     sgm_scale_size(o.scale, &w, &h);
     FloatImage::Ptr depth = FloatImage::create_for_overwrite(w, h, 1);
@@ -180,7 +184,22 @@ run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
     smvs_sgm_filter_options const filter = { o.uniqueness, o.uniqueness_window,
         o.speckle_size, o.speckle_ratio };
     bool const filtered = !o.filters_default();
-    if (o.sweep && filtered)
+    smvs_sgm_photo_options const photo = { o.photo_radius, o.photo_best_k, o.photo_min_views,
+        o.photo_min_score };
+    if (o.photo_radius != 0) {
+        // the test behind whichever front: the entries that take every option
+        *confidence = FloatImage::create_for_overwrite(w, h, 1);
+        if (o.sweep)
+            SGM_DEVICE_CALL(smvs_sgm_sweep_for_view_raw_photo, o.device, pixels, fw, fh, fc,
+                dev.data(), channels.data(), n, o.scale, dev[0].range_main, o.num_steps,
+                o.penalty1, o.penalty2, &sweep_opts, &filter, depth->begin(), nullptr, nullptr,
+                nullptr, nullptr, nullptr, n_witness, &photo, (*confidence)->begin(), nullptr);
+        else
+            SGM_DEVICE_CALL(smvs_sgm_depth_for_view_raw_photo, o.device, pixels, fw, fh, fc,
+                dev.data(), channels.data(), n, o.scale, o.num_steps, o.penalty1, o.penalty2,
+                &view_opts, &filter, depth->begin(), nullptr, nullptr, n_witness, &photo,
+                (*confidence)->begin(), nullptr);
+    } else if (o.sweep && filtered)
         // n x (warp + cost) over the main view's planes, one fold, one
         // aggregation, one winner, the support test
         SGM_DEVICE_CALL(smvs_sgm_sweep_for_view_raw_filtered, o.device, pixels, fw, fh, fc,
@@ -218,7 +237,9 @@ SGMStereo::reconstruct(Options sgm_opts, StereoView::Ptr main_view,
     // consistency check on the device
     std::vector<PairInputs> pairs(1);
     prepare_pair(sgm_opts, main_view, neighbor, bundle, &pairs[0]);
-    return run_pairs(sgm_opts, main_view, pairs);
+    sgm_opts.photo_radius = 0;      // (a pair has no further witness)
+    FloatImage::Ptr confidence;
+    return run_pairs(sgm_opts, main_view, pairs, 1, &confidence);
 }
 
 FloatImage::Ptr
@@ -241,11 +262,24 @@ reconstruct_sgm_depth_for_view(SGMStereo::Options opts,
         throw std::invalid_argument("reconstruct_sgm_depth_for_view: the reference's "
             "merge takes one or two neighbours (app/smvsrecon.cc:360-365); more need "
             "Options::consensus or Options::sweep");
-    std::vector<PairInputs> pairs(std::min<std::size_t>(neighbors.size(),
-        (std::size_t)opts.num_neighbors));
+    std::size_t const n_front = std::min<std::size_t>(neighbors.size(),
+        (std::size_t)opts.num_neighbors);
+    // with the photo-consistency test: the first photo_witnesses neighbours (all
+    // of them at -1, SMVS_MAX_SUBS at the most, the front's own at the least)
+    std::size_t n_all = n_front;
+    if (opts.photo_radius != 0) {
+        std::size_t const asked = opts.photo_witnesses < 0 ? neighbors.size()
+            : (std::size_t)opts.photo_witnesses;
+        n_all = std::max(n_front, std::min<std::size_t>(std::min(asked, neighbors.size()),
+            (std::size_t)SMVS_MAX_SUBS));
+    }
+    std::vector<PairInputs> pairs(n_all);
     for (std::size_t k = 0; k < pairs.size(); ++k)
         prepare_pair(opts, main_view, neighbors[k], bundle, &pairs[k]);
-    FloatImage::Ptr d1 = run_pairs(opts, main_view, pairs);
+    FloatImage::Ptr confidence;
+    FloatImage::Ptr d1 = run_pairs(opts, main_view, pairs, (int)n_front, &confidence);
+    if (confidence != nullptr)
+        main_view->write_image_to_view(confidence, "smvs-sgm-confidence");
     // (app/smvsrecon.cc:383: write_depth_to_view -- the conversion of the stored
     // copy to MVE's convention waits until the embedding is read; the optimizer
     // of this view takes the map as it is and converts on the device)

@@ -1,7 +1,8 @@
 // Host mirror of smvs::SGMStereo (reference: lib/sgm_stereo.h:21-88).  The
 // cost volumes, the 8-path aggregation, the WTA, the left/right check and the
 // merge run on the device (smvs_sgm_depth_for_view_raw_opts / _raw_merge, or
-// smvs_sgm_sweep_for_view_raw); the host
+// smvs_sgm_sweep_for_view_raw, or with the photo-consistency test the two
+// `_raw_photo` entries); the host
 // keeps the depth range from the bundle and the image half-sizing.
 #pragma once
 
@@ -88,6 +89,26 @@ public:
             return uniqueness == 0 && uniqueness_window == 1 && speckle_size == 0
                 && speckle_ratio == 0.95f;
         }
+
+        // not in the reference either: the multi-view photo-consistency test of
+        // include/smvs_hip.h for any of the three front ends above, on the final
+        // map of the view and before the speckle removal.  photo_radius (1 .. 3;
+        // 0 is off): per pixel and witness the (2 r + 1)^2 window of the main
+        // image against its warp into the witness at the pixel's own depth; the
+        // confidence is the mean of the photo_best_k largest scores (0: of all),
+        // none with fewer than photo_min_views of them, and a depth whose
+        // confidence is below photo_min_score is removed (-1 removes nothing).
+        // photo_witnesses: how many of the neighbours
+        // reconstruct_sgm_depth_for_view is given are witnesses (never fewer
+        // than the front end uses); -1: all of them, up to 16.  With the test on
+        // the confidence is written as the smvs-sgm-confidence embedding.
+        // (0, 2, 2, 0.49, -1) are defaults of a user option, untuned: nobody has
+        // measured them on real scenes.
+        int photo_radius = 0;
+        int photo_best_k = 2;
+        int photo_min_views = 2;
+        float photo_min_score = 0.49f;
+        int photo_witnesses = -1;
 
         // the plane counts smvs_sgm_run / smvs_sgm_depth_for_view accept
         static bool valid_num_steps(int n)

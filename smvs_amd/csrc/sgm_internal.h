@@ -2,8 +2,9 @@
 // census, warp, cost), sgm_paths.hip (its path aggregation), sgm_wta.hip (its
 // winner-takes-all), sgm_view.hip (a view's front end), sgm_sweep.hip (the
 // opt-in plane sweep over n neighbours), sgm_speckle.hip (the opt-in speckle
-// removal), image_prep.hip (a view's input image), bilateral.hip (the joint
-// bilateral upsample).
+// removal), sgm_photo.hip (the opt-in multi-view photo-consistency test),
+// image_prep.hip (a view's input image), bilateral.hip (the joint bilateral
+// upsample).
 #pragma once
 
 #include "common.h"
@@ -57,9 +58,10 @@ enum {
     WS_DELTA,                                                         // eight path-byte volumes
     WS_FWDN, WS_BWDN, WS_SUPPORT,                                     // consensus merge: n + n maps, support
     WS_SWEEP,                                                         // plane sweep: n cost volumes
-    WS_SPECKLE, WS_RUNNER_UP                                          // filters: labels + counts, runner-up map
+    WS_SPECKLE, WS_RUNNER_UP,                                         // filters: labels + counts, runner-up map
+    WS_PHOTO, WS_PHOTO_OUT                                            // photo test: witness images; confidence + views
 };
-static_assert(WS_RUNNER_UP < Workspace::SLOTS, "the last slot must exist in a Workspace");
+static_assert(WS_PHOTO_OUT < Workspace::SLOTS, "the last slot must exist in a Workspace");
 
 // The largest plane count of a run: the key of the WTA kernels is
 // value * 256 + plane (one byte for the plane), and 64 lanes x 4 planes is one
@@ -171,6 +173,31 @@ int sgm_speckle_ensure(Workspace &ws, size_t npix, uint32_t **d_words);
 int sgm_launch_speckle(Workspace &ws, SgmProfile *prof, const float *d_depth, int w, int h,
     int speckle_size, float speckle_ratio, uint32_t *d_words, float *d_out, bool want_size);
 
+// The photo-consistency test of include/smvs_hip.h ("Multi-view
+// photo-consistency test"): radius 0 is off.
+inline bool
+sgm_photo_on(const smvs_sgm_photo_options *photo)
+{
+    return photo != nullptr && photo->radius > 0;
+}
+// smvs_sgm_photo_options for n witnesses in all: radius in 0 .. 3, best_k and
+// min_views in 0 .. n, min_score in [-1, 1] (a NaN is none).  (sgm_photo.hip)
+int check_sgm_photo(const smvs_sgm_photo_options *photo, int n);
+// One witness of the test on the device: its SGM-scale image and the float
+// reprojection main -> witness.
+struct SgmPhotoWitness {
+    const uint8_t *image;
+    int nw, nh;
+    float M[9], t[3];
+};
+// The test of d_depth[w * h] against n witnesses (1 .. SMVS_MAX_SUBS) into d_out
+// (may be d_depth), d_confidence and d_views (either may be null) on the
+// workspace's stream: one launch under a timer of class SMVS_SGM_K_MERGE.
+// hipGetLastError.  (sgm_photo.hip)
+int sgm_launch_photo(Workspace &ws, SgmProfile *prof, const uint8_t *d_main, int w, int h,
+    const float *d_depth, const SgmPhotoWitness *witnesses, int n,
+    smvs_sgm_photo_options const &opts, float *d_out, float *d_confidence, uint8_t *d_views);
+
 // What a run is asked for besides its images and depth range: the options of
 // SGMStereo (num_steps, the penalties), smvs_sgm_p2_mode and smvs_sgm_winner.
 // Each entry fills one and every stage of the run reads it.
@@ -247,10 +274,13 @@ struct SgmPreparedSize {
 SgmPreparedSize sgm_prepared_size(int w, int h, int channels, int halvings);
 
 // ------------------------------------------------- a view entry's call record
-// What one of the 14 smvs_sgm_depth_for_view* / smvs_sgm_sweep_for_view*
+// What one of the 16 smvs_sgm_depth_for_view* / smvs_sgm_sweep_for_view*
 // entries is asked for (include/smvs_hip.h: which entry fixes which field).
 // The entries at SGM scale are the raw ones with channels = 1, SGM_ONE_CHANNEL
-// and halvings = 0; the entries without filters those with SGM_FILTERS_OFF.
+// and halvings = 0; the entries without filters those with SGM_FILTERS_OFF; the
+// 14 without the photo test those with SGM_PHOTO_OFF and no further witness.
+// neighbors and neighbor_channels hold n_neighbors + n_witness entries: the
+// first n_neighbors go through the front, all of them are witnesses of the test.
 struct SgmViewCall {
     int device;
     const uint8_t *main_img;
@@ -269,11 +299,18 @@ struct SgmViewCall {
     uint8_t *support;
     int32_t *argmin;
     uint16_t *cost, *sgm, *runner_up;
+    int n_witness;                  // the photo test: entries of `neighbors` behind n_neighbors
+    const smvs_sgm_photo_options *photo;
+    float *confidence;              // its outputs; null: not asked for
+    uint8_t *views;
 };
 constexpr int SGM_ONE_CHANNEL[SMVS_MAX_SUBS] = { 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1 };
 static_assert(SMVS_MAX_SUBS == 16, "SGM_ONE_CHANNEL: one entry per neighbour");
 // (what SgmWorkspace::set_filter and sgm_speckle_on make of it: nothing runs)
 constexpr smvs_sgm_filter_options SGM_FILTERS_OFF = { 0, 1, 0, 0.95f };
+// (what sgm_photo_on makes of it: no launch; best_k and min_views pass the check
+// for every neighbour count)
+constexpr smvs_sgm_photo_options SGM_PHOTO_OFF = { 0, 0, 0, 0.49f };
 
 // Every refusal of a view entry, before its first device call, in the one
 // order written above it.  (sgm_view.hip)
@@ -282,7 +319,8 @@ int check_sgm_view_call(SgmViewCall const &C);
 int check_sgm_sweep_options(const smvs_sgm_sweep_options *opts, int n_neighbors);
 
 // What the three fronts share of one call: the leased workspace, the timers,
-// the run buffers, the main image at SGM scale, the speckle words.  (sgm_view.hip)
+// the run buffers, the main image at SGM scale, the speckle words, the
+// witnesses of the photo test.  (sgm_view.hip)
 struct SgmViewSession {
     SgmViewCall const &C;
     WorkspaceLease lease;
@@ -292,19 +330,28 @@ struct SgmViewSession {
     int mw = 0, mh = 0;
     size_t npix = 0;
     uint32_t *d_speckle = nullptr;
+    // the photo test: every witness image at SGM scale in one slot (WS_PHOTO),
+    // confidence and views behind each other in another (WS_PHOTO_OUT)
+    SgmPhotoWitness witness[SMVS_MAX_SUBS];
+    uint8_t *d_witness = nullptr, *d_views = nullptr;
+    size_t witness_at[SMVS_MAX_SUBS + 1] = { 0 };
+    float *d_confidence = nullptr;
     explicit SgmViewSession(SgmViewCall const &call) : C(call), lease(call.device), B(lease.w) {}
     Workspace &ws() { return *lease.w; }
     // the call's filter and want_sgm, the main image prepared (WS_MAIN, WS_RAW),
-    // the speckle words when the filter asks
+    // the speckle words when the filter asks; with the photo test its two slots
+    // and the witnesses behind the front's neighbours, prepared and kept
     int open();
-    // neighbour k prepared into the two slots
+    // neighbour k prepared into the two slots (and kept as witness k of the
+    // photo test)
     int neighbor(int k, int slot_out, int slot_tmp, uint8_t **d_nbr, int *nw, int *nh);
     // B's buffers for runs on images of up to largest_pix pixels
     int ensure_runs(size_t largest_pix);
     // SGMStereo::reconstruct, sgm_stereo.cc:46-62: main -> neighbour k, then
     // neighbour k -> main with the neighbour's own depth range
     int run_pair(int k, const uint8_t *d_nbr, int nw, int nh, float *d_fwd, float *d_bwd);
-    // the speckle filter on d_map when on, then the outputs the call asks for
+    // the photo test on d_map when on, the speckle filter on d_map when on, then
+    // the outputs the call asks for
     int finish(float *d_map, const float *d_checked, const uint8_t *d_support);
 };
 // check, session, front: what every view entry does with its record

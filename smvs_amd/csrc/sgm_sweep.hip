@@ -327,9 +327,32 @@ sgm_front_sweep(SgmViewSession &S, SgmViewCall const &C)
 
 using namespace smvs_hip;
 
-// The two entries with the filters fill a record each (the one at SGM scale
-// has the volumes among its outputs, the raw one has not); the two without
-// them are those with both filters off.
+// One entry fills the record: raw images, the filters, the photo test, every
+// output.  The two with the filters are that one with the photo test off (the
+// one at SGM scale has the volumes among its outputs, the raw one has not); the
+// two without the filters are those with both filters off.
+extern "C" int
+smvs_sgm_sweep_for_view_raw_photo(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_sweep_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint8_t *support,
+    uint16_t *cost, uint16_t *sgm, uint16_t *runner_up, int n_witness,
+    const smvs_sgm_photo_options *photo, float *confidence, uint8_t *views)
+{
+    smvs_sgm_sweep_options const o = opts != nullptr ? *opts : smvs_sgm_sweep_options{};
+    SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h,
+        .channels = channels, .neighbors = neighbors, .neighbor_channels = neighbor_channels,
+        .n_neighbors = n_neighbors, .halvings = halvings,
+        .P = { num_steps, penalty1, penalty2, o.p2_mode, o.winner }, .sweep = true,
+        .sweep_opts = o, .range = range, .filter = filter,
+        .null_options = opts != nullptr ? nullptr : SGM_NULL_SWEEP_OPTIONS,
+        .depth = depth, .support = support, .argmin = argmin, .cost = cost, .sgm = sgm,
+        .runner_up = runner_up, .n_witness = n_witness, .photo = photo,
+        .confidence = confidence, .views = views };
+    return sgm_run_view_call(C);
+}
+
 extern "C" int
 smvs_sgm_sweep_for_view_filtered(int device, const uint8_t *main_img, int w, int h,
     const smvs_sgm_neighbor *neighbors, int n_neighbors, const float *range, int num_steps,
@@ -337,16 +360,9 @@ smvs_sgm_sweep_for_view_filtered(int device, const uint8_t *main_img, int w, int
     const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint8_t *support,
     uint16_t *cost, uint16_t *sgm, uint16_t *runner_up)
 {
-    smvs_sgm_sweep_options const o = opts != nullptr ? *opts : smvs_sgm_sweep_options{};
-    SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h, .channels = 1,
-        .neighbors = neighbors, .neighbor_channels = SGM_ONE_CHANNEL,
-        .n_neighbors = n_neighbors, .halvings = 0,
-        .P = { num_steps, penalty1, penalty2, o.p2_mode, o.winner }, .sweep = true,
-        .sweep_opts = o, .range = range, .filter = filter,
-        .null_options = opts != nullptr ? nullptr : SGM_NULL_SWEEP_OPTIONS,
-        .depth = depth, .support = support, .argmin = argmin, .cost = cost, .sgm = sgm,
-        .runner_up = runner_up };
-    return sgm_run_view_call(C);
+    return smvs_sgm_sweep_for_view_raw_photo(device, main_img, w, h, 1, neighbors,
+        SGM_ONE_CHANNEL, n_neighbors, 0, range, num_steps, penalty1, penalty2, opts, filter,
+        depth, argmin, support, cost, sgm, runner_up, 0, &SGM_PHOTO_OFF, nullptr, nullptr);
 }
 
 extern "C" int
@@ -356,15 +372,10 @@ smvs_sgm_sweep_for_view_raw_filtered(int device, const uint8_t *main_img, int w,
     uint16_t penalty2, const smvs_sgm_sweep_options *opts,
     const smvs_sgm_filter_options *filter, float *depth, uint8_t *support)
 {
-    smvs_sgm_sweep_options const o = opts != nullptr ? *opts : smvs_sgm_sweep_options{};
-    SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h,
-        .channels = channels, .neighbors = neighbors, .neighbor_channels = neighbor_channels,
-        .n_neighbors = n_neighbors, .halvings = halvings,
-        .P = { num_steps, penalty1, penalty2, o.p2_mode, o.winner }, .sweep = true,
-        .sweep_opts = o, .range = range, .filter = filter,
-        .null_options = opts != nullptr ? nullptr : SGM_NULL_SWEEP_OPTIONS,
-        .depth = depth, .support = support };
-    return sgm_run_view_call(C);
+    return smvs_sgm_sweep_for_view_raw_photo(device, main_img, w, h, channels, neighbors,
+        neighbor_channels, n_neighbors, halvings, range, num_steps, penalty1, penalty2, opts,
+        filter, depth, nullptr, support, nullptr, nullptr, nullptr, 0, &SGM_PHOTO_OFF, nullptr,
+        nullptr);
 }
 
 extern "C" int

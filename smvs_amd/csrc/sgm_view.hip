@@ -286,7 +286,7 @@ check_sgm_view_options(const smvs_sgm_view_options *opts, int n_neighbors)
     return SMVS_OK;
 }
 
-// (declared in sgm_internal.h)  The one order of the checks, for all 14 entries.
+// (declared in sgm_internal.h)  The one order of the checks, for all 16 entries.
 // No check involves a device, and a later one may rely on an earlier one (the
 // neighbour arrays are read once the count is known to fit them).
 //   1. the entry's options pointer            2. the filter options
@@ -304,6 +304,9 @@ check_sgm_view_options(const smvs_sgm_view_options *opts, int n_neighbors)
 //      where the neighbour gets a run of its own, above 1 x 1 in the sweep
 //  13. outputs the options exclude: checked and support with the reference's
 //      merge, runner_up without the uniqueness test
+//  14. the photo test: the options pointer; radius, best_k, min_views, min_score;
+//      the witness count; with radius 0 no witness, confidence or views; each
+//      witness behind the front's neighbours: its image, size and channels
 int
 check_sgm_view_call(SgmViewCall const &C)
 {
@@ -341,6 +344,20 @@ check_sgm_view_call(SgmViewCall const &C)
             "checked and support are outputs of the consensus merge");
     SMVS_REQUIRE(C.runner_up == nullptr || C.filter->uniqueness != 0,
         "runner_up is an output of the uniqueness test (uniqueness > 0)");
+    int const n_all = C.n_neighbors + C.n_witness;
+    if ((rc = check_sgm_photo(C.photo, n_all)) != SMVS_OK)
+        return rc;
+    SMVS_REQUIRE(C.n_witness >= 0 && n_all <= SMVS_MAX_SUBS,
+        "n_witness must not be negative, n_neighbors + n_witness at most SMVS_MAX_SUBS");
+    if (!sgm_photo_on(C.photo))
+        SMVS_REQUIRE(C.n_witness == 0 && C.confidence == nullptr && C.views == nullptr,
+            "witnesses, confidence and views belong to the photo test (photo radius > 0)");
+    for (int k = C.n_neighbors; k < n_all; ++k) {
+        SMVS_REQUIRE(C.neighbors[k].image && (C.neighbors[k].width >> C.halvings) >= 1
+                && (C.neighbors[k].height >> C.halvings) >= 1, "bad witness image");
+        SMVS_REQUIRE(C.neighbor_channels[k] == 1 || C.neighbor_channels[k] == 3,
+            "1 or 3 channels (witness)");
+    }
     return SMVS_OK;
 }
 
@@ -358,15 +375,53 @@ SgmViewSession::open()
              WS_RAW, &d_main, &mw, &mh)) != SMVS_OK)
         return rc;
     npix = (size_t)mw * mh;
-    return sgm_speckle_on(C.filter) ? sgm_speckle_ensure(ws(), npix, &d_speckle) : SMVS_OK;
+    if (sgm_speckle_on(C.filter) && (rc = sgm_speckle_ensure(ws(), npix, &d_speckle)) != SMVS_OK)
+        return rc;
+    if (!sgm_photo_on(C.photo))
+        return SMVS_OK;
+    // the photo test's slots at their final size, then the witnesses the front
+    // does not prepare, through the slots of neighbour 0: all before the
+    // front's first SGM launch
+    int const n_all = C.n_neighbors + C.n_witness;
+    for (int k = 0; k < n_all; ++k) {
+        SgmPreparedSize const Z = sgm_prepared_size(C.neighbors[k].width, C.neighbors[k].height,
+            C.neighbor_channels[k], C.halvings);
+        witness_at[k + 1] = witness_at[k] + (((size_t)Z.w * Z.h + 15) & ~(size_t)15);
+    }
+    if ((rc = ws().ensure(WS_PHOTO, witness_at[n_all], &d_witness))
+        || (rc = ws().ensure(WS_PHOTO_OUT, npix * (sizeof(float) + 1), &d_confidence)))
+        return rc;
+    d_views = reinterpret_cast<uint8_t *>(d_confidence + npix);
+    for (int k = C.n_neighbors; k < n_all; ++k) {
+        uint8_t *d_img = nullptr;
+        int pw = 0, ph = 0;
+        if ((rc = neighbor(k, WS_NBR0, WS_RAW0, &d_img, &pw, &ph)) != SMVS_OK)
+            return rc;
+    }
+    return SMVS_OK;
 }
 
 int
 SgmViewSession::neighbor(int k, int slot_out, int slot_tmp, uint8_t **d_nbr, int *nw, int *nh)
 {
     smvs_sgm_neighbor const &N = C.neighbors[k];
-    return sgm_prepare_image(ws(), N.image, N.width, N.height, C.neighbor_channels[k],
+    int const rc = sgm_prepare_image(ws(), N.image, N.width, N.height, C.neighbor_channels[k],
         C.halvings, slot_out, slot_tmp, d_nbr, nw, nh);
+    if (rc != SMVS_OK || !sgm_photo_on(C.photo))
+        return rc;
+    // kept for the photo test (the slot may hold the next neighbour by then)
+    SgmPhotoWitness &W = witness[k];
+    uint8_t *const kept = d_witness + witness_at[k];
+    SMVS_HIP_CHECK(hipMemcpyAsync(kept, *d_nbr, (size_t)*nw * *nh, hipMemcpyDeviceToDevice,
+        ws().stream));
+    W.image = kept;
+    W.nw = *nw;
+    W.nh = *nh;
+    for (int i = 0; i < 9; ++i)
+        W.M[i] = N.M_fwd[i];
+    for (int i = 0; i < 3; ++i)
+        W.t[i] = N.t_fwd[i];
+    return SMVS_OK;
 }
 
 int
@@ -391,8 +446,16 @@ SgmViewSession::finish(float *d_map, const float *d_checked, const uint8_t *d_su
 {
     int rc;
     Workspace &w = ws();
-    // (behind the merge or the support test: the components are those of the
-    // map that leaves; checked and support are those of the unfiltered map)
+    // (behind the merge or the support test, the photo test first: the components
+    // are those of the map that leaves; checked and support are those of the
+    // unfiltered map)
+    bool const photo = sgm_photo_on(C.photo);
+    if (photo
+        && (rc = sgm_launch_photo(w, &prof, d_main, mw, mh, d_map, witness,
+                C.n_neighbors + C.n_witness, *C.photo, d_map,
+                C.confidence != nullptr ? d_confidence : nullptr,
+                C.views != nullptr ? d_views : nullptr)) != SMVS_OK)
+        return rc;
     if (sgm_speckle_on(C.filter)
         && (rc = sgm_launch_speckle(w, &prof, d_map, mw, mh, C.filter->speckle_size,
                 C.filter->speckle_ratio, d_speckle, d_map, false)) != SMVS_OK)
@@ -400,6 +463,9 @@ SgmViewSession::finish(float *d_map, const float *d_checked, const uint8_t *d_su
     auto get = [&w](void *host, const void *dev, size_t bytes) {
         return host != nullptr ? w.download(host, dev, bytes) : (int)SMVS_OK;
     };
+    if (photo && ((rc = get(C.confidence, d_confidence, sizeof(float) * npix))
+            || (rc = get(C.views, d_views, npix))))
+        return rc;
     // the consensus's own outputs, then the map (every download waits for the
     // stream: nothing is left to synchronise)
     if (!C.sweep)
@@ -540,10 +606,10 @@ using namespace smvs_hip;
 
 // ------------------------------------------------------------- the entries
 // Two entries fill a record: the one that takes smvs_sgm_options and the one
-// that takes smvs_sgm_view_options with the filters, both on raw images.  The
-// others are one of the two with the fields they do not take set to what they
-// mean: the reference's constant penalty2 and plane winner, one channel at SGM
-// scale, both filters off.
+// that takes smvs_sgm_view_options with the filters and the photo test, both on
+// raw images.  The others are one of the two with the fields they do not take
+// set to what they mean: the reference's constant penalty2 and plane winner, one
+// channel at SGM scale, both filters off, the photo test off.
 extern "C" int
 smvs_sgm_depth_for_view_raw_opts(int device, const uint8_t *main_img, int w, int h,
     int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
@@ -558,7 +624,27 @@ smvs_sgm_depth_for_view_raw_opts(int device, const uint8_t *main_img, int w, int
         .view_opts = { o.p2_mode, o.winner, SMVS_SGM_MERGE_REFERENCE, 0, 0.0f },
         .filter = &SGM_FILTERS_OFF,
         .null_options = opts != nullptr ? nullptr : "null options (winner, p2_mode)",
-        .depth = depth };
+        .depth = depth, .photo = &SGM_PHOTO_OFF };
+    return sgm_run_view_call(C);
+}
+
+extern "C" int
+smvs_sgm_depth_for_view_raw_photo(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_view_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support,
+    int n_witness, const smvs_sgm_photo_options *photo, float *confidence, uint8_t *views)
+{
+    smvs_sgm_view_options const o = opts != nullptr ? *opts : smvs_sgm_view_options{};
+    SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h,
+        .channels = channels, .neighbors = neighbors, .neighbor_channels = neighbor_channels,
+        .n_neighbors = n_neighbors, .halvings = halvings,
+        .P = { num_steps, penalty1, penalty2, o.p2_mode, o.winner }, .view_opts = o,
+        .filter = filter,
+        .null_options = opts != nullptr ? nullptr : "null options (p2_mode, winner, merge)",
+        .depth = depth, .checked = checked, .support = support, .n_witness = n_witness,
+        .photo = photo, .confidence = confidence, .views = views };
     return sgm_run_view_call(C);
 }
 
@@ -569,15 +655,9 @@ smvs_sgm_depth_for_view_raw_filtered(int device, const uint8_t *main_img, int w,
     uint16_t penalty2, const smvs_sgm_view_options *opts,
     const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support)
 {
-    smvs_sgm_view_options const o = opts != nullptr ? *opts : smvs_sgm_view_options{};
-    SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h,
-        .channels = channels, .neighbors = neighbors, .neighbor_channels = neighbor_channels,
-        .n_neighbors = n_neighbors, .halvings = halvings,
-        .P = { num_steps, penalty1, penalty2, o.p2_mode, o.winner }, .view_opts = o,
-        .filter = filter,
-        .null_options = opts != nullptr ? nullptr : "null options (p2_mode, winner, merge)",
-        .depth = depth, .checked = checked, .support = support };
-    return sgm_run_view_call(C);
+    return smvs_sgm_depth_for_view_raw_photo(device, main_img, w, h, channels, neighbors,
+        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, opts, filter,
+        depth, checked, support, 0, &SGM_PHOTO_OFF, nullptr, nullptr);
 }
 
 // sgm_stereo.cc:274-306 with opts->winner = SMVS_SGM_WINNER_SUBPLANE in all four

@@ -478,6 +478,67 @@ def _sgm_filter(uniqueness, uniqueness_window, speckle_size, speckle_ratio):
                             float(speckle_ratio))
 
 
+class SgmPhotoOptions(C.Structure):
+    """smvs_sgm_photo_options of include/smvs_hip.h."""
+    _fields_ = [("radius", C.c_int), ("best_k", C.c_int), ("min_views", C.c_int),
+                ("min_score", C.c_float)]
+
+
+# (photo_radius, photo_best_k, photo_min_views, photo_min_score) of the Python
+# fronts: the photo-consistency test off.  Defaults of a user option, untuned;
+# nobody has measured them on real scenes.
+SGM_PHOTO_DEFAULTS = (0, 2, 2, 0.49)
+
+
+def _sgm_photo(radius, best_k, min_views, min_score, witnesses):
+    """The photo options, or None where they are the defaults and there is no
+    witness (the entries without the test are called then)."""
+    if (radius, best_k, min_views, min_score) == SGM_PHOTO_DEFAULTS and not witnesses:
+        return None
+    return SgmPhotoOptions(int(radius), int(best_k), int(min_views), float(min_score))
+
+
+def _sgm_witnesses(neighbors, witnesses):
+    """The front's neighbours followed by the further witnesses of the photo test
+    as full neighbour dicts (of a witness only image, M_fwd and t_fwd are read)."""
+    return list(neighbors) + [
+        dict(M_bwd=np.zeros(9), t_bwd=np.zeros(3), range_main=(0, 0), range_neighbor=(0, 0),
+             **{k: nb[k] for k in ("image", "M_fwd", "t_fwd")}) for nb in witnesses or ()]
+
+
+def sgm_photo_check(main_img, depth, witnesses, radius=2, best_k=2, min_views=2, min_score=0.49,
+                    device=0):
+    """smvs_sgm_photo_check: the multi-view photo-consistency test of
+    include/smvs_hip.h alone (not in the reference), on a map of the caller.
+    main_img (h, w) u8 at SGM scale; depth (h, w) float in the depth convention of
+    the SGM planes; witnesses: 1 .. 16 dicts {image (nh, nw) u8, M_fwd, t_fwd} (the
+    float reprojection main -> witness).  Per valid pixel (depth > 0) and witness
+    the (2 radius + 1)^2 window of the main image against its warp into the
+    witness at the pixel's own depth: the signed squared correlation, where every
+    sample lies inside the witness.  confidence = the mean of the best_k largest
+    scores (0: of all), -1 with fewer than max(min_views, 1) of them; no depth
+    where confidence < min_score (-1 drops nothing).  Returns (out (h, w) f32,
+    confidence (h, w) f32, views (h, w) u8: the witnesses with a score).  The
+    defaults are defaults of a user option, untuned."""
+    lib = _capi.load()
+    main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
+    depth = _f32(depth)
+    if main_img.ndim != 2 or depth.shape != main_img.shape:
+        raise ValueError("main_img and depth: (h, w)")
+    h, w = depth.shape
+    keep = []
+    arr = _sgm_neighbors(_sgm_witnesses([], witnesses), keep) if len(witnesses) else None
+    if any(k.ndim != 2 for k in keep):
+        raise ValueError("witness images: (nh, nw), one channel at SGM scale")
+    opts = SgmPhotoOptions(int(radius), int(best_k), int(min_views), float(min_score))
+    out = np.zeros((h, w), dtype=np.float32)
+    conf = np.zeros((h, w), dtype=np.float32)
+    views = np.zeros((h, w), dtype=np.uint8)
+    check(lib.smvs_sgm_photo_check(device, _p(main_img, _u8p), w, h, _p(depth, _fp), arr,
+          len(witnesses), C.byref(opts), _p(out, _fp), _p(conf, _fp), _p(views, _u8p)))
+    return out, conf, views
+
+
 def sgm_filter_speckles(depth, speckle_size, speckle_ratio=0.95, device=0):
     """smvs_sgm_filter_speckles: the speckle kernels of include/smvs_hip.h alone
     (not in the reference).  depth (h, w) float; pixels > 0 are valid, two valid
@@ -596,7 +657,9 @@ class SgmNeighbor(C.Structure):
 def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0,
                        adaptive_p2=False, halvings=None, subplane=False,
                        consensus=False, agree_ratio=0.95, min_agree=2, want_checked=False,
-                       uniqueness=0, uniqueness_window=1, speckle_size=0, speckle_ratio=0.95):
+                       uniqueness=0, uniqueness_window=1, speckle_size=0, speckle_ratio=0.95,
+                       photo_radius=0, photo_best_k=2, photo_min_views=2, photo_min_score=0.49,
+                       witnesses=None):
     """reconstruct_sgm_depth_for_view on the device.  neighbors: list of dicts
     {image, M_fwd, t_fwd, M_bwd, t_bwd, range_main, range_neighbor} (SGM-scale
     u8 images, float reprojections).  adaptive_p2, subplane: as for sgm_run
@@ -618,10 +681,28 @@ def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0
     sgm_filter_speckles on the merged map (sizes 0 and 1 are off).  Both are
     filters of include/smvs_hip.h, not in the reference and off by default;
     (0, 1, 0, 0.95) are defaults of a user option, untuned, and nobody has
-    measured them on real scenes."""
+    measured them on real scenes.
+    photo_radius (1 .. 3; 0 is off), photo_best_k, photo_min_views,
+    photo_min_score, witnesses: the photo-consistency test of sgm_photo_check on
+    the view's final map, before the speckle removal.  Its witnesses are the
+    neighbours followed by `witnesses` (dicts {image, M_fwd, t_fwd}, images as the
+    neighbours'; at most 16 in all).  Returns a dict {depth, confidence, views}
+    (and checked, support with want_checked).  Off by default; witnesses or a
+    changed option with photo_radius = 0 is an error.  (0, 2, 2, 0.49) are
+    defaults of a user option, untuned."""
     lib = _capi.load()
     main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
     filt = _sgm_filter(uniqueness, uniqueness_window, speckle_size, speckle_ratio)
+    photo = _sgm_photo(photo_radius, photo_best_k, photo_min_views, photo_min_score, witnesses)
+    if photo is not None:
+        if want_checked and not consensus:
+            raise ValueError("want_checked: the checked maps and the support are "
+                             "outputs of the consensus merge")
+        return _sgm_depth_for_view_photo(
+            lib, main_img, neighbors, witnesses, num_steps, p1, p2, device,
+            _sgm_view_options(adaptive_p2, subplane, consensus, agree_ratio, min_agree),
+            halvings, want_checked,
+            filt if filt is not None else SgmFilterOptions(*SGM_FILTER_DEFAULTS), photo)
     if consensus or want_checked or filt is not None:
         if want_checked and not consensus:
             raise ValueError("want_checked: the checked maps and the support are "
@@ -713,6 +794,43 @@ def _sgm_depth_for_view_merge(lib, main_img, neighbors, num_steps, p1, p2, devic
     return depth
 
 
+def _raw_images(main_img, keep, halvings):
+    """(channels, neighbour channel array, halvings) for a raw entry; halvings
+    None: one-channel images at SGM scale, as (1, ones, 0)."""
+    if halvings is None and (main_img.ndim != 2 or any(k.ndim != 2 for k in keep)):
+        raise ValueError("one-channel images at SGM scale (or pass halvings)")
+    channels = 1 if main_img.ndim == 2 else main_img.shape[2]
+    nch = (C.c_int * max(len(keep), 1))(*[1 if k.ndim == 2 else k.shape[2] for k in keep])
+    return channels, nch, 0 if halvings is None else int(halvings)
+
+
+def _sgm_depth_for_view_photo(lib, main_img, neighbors, witnesses, num_steps, p1, p2, device,
+                              vopts, halvings, want_checked, filt, photo):
+    """smvs_sgm_depth_for_view_raw_photo."""
+    keep = []
+    every = _sgm_witnesses(neighbors, witnesses)
+    arr = _sgm_neighbors(every, keep) if every else None
+    n = len(neighbors)
+    channels, nch, halvings = _raw_images(main_img, keep, halvings)
+    h, w = main_img.shape[:2]
+    ow, oh = _halved(w, h, halvings)
+    depth = np.zeros((oh, ow), dtype=np.float32)
+    checked = np.zeros((n, oh, ow), dtype=np.float32) if want_checked else None
+    support = np.zeros((oh, ow), dtype=np.uint8) if want_checked else None
+    on = photo.radius != 0
+    conf = np.zeros((oh, ow), dtype=np.float32) if on else None
+    views = np.zeros((oh, ow), dtype=np.uint8) if on else None
+    check(lib.smvs_sgm_depth_for_view_raw_photo(
+        device, _p(main_img, _u8p), w, h, channels, arr, nch, n, halvings, num_steps,
+        C.c_uint16(p1), C.c_uint16(p2), C.byref(vopts), C.byref(filt), _p(depth, _fp),
+        _p(checked, _fp), _p(support, _u8p), len(every) - n, C.byref(photo), _p(conf, _fp),
+        _p(views, _u8p)))
+    out = dict(depth=depth, confidence=conf, views=views)
+    if want_checked:
+        out.update(checked=checked, support=support)
+    return out
+
+
 def sgm_check_merge(fwd, neighbors, agree_ratio=0.95, min_agree=2, device=0):
     """smvs_sgm_check_merge: the kernel of the consensus front end alone, on
     maps of the caller.  fwd (n, h, w): the unchecked forward maps of the main
@@ -759,7 +877,9 @@ def sgm_sweep_defaults(n):
 def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2=96, device=0,
                        adaptive_p2=False, subplane=False, halvings=None, min_views=None,
                        best_k=None, support_cost=20, min_support=None, want_volumes=False,
-                       uniqueness=0, uniqueness_window=1, speckle_size=0, speckle_ratio=0.95):
+                       uniqueness=0, uniqueness_window=1, speckle_size=0, speckle_ratio=0.95,
+                       photo_radius=0, photo_best_k=2, photo_min_views=2, photo_min_score=0.49,
+                       witnesses=None):
     """The multi-neighbour plane sweep of include/smvs_hip.h (not in the
     reference; opt-in): one cost volume of the main view from all n = 1 .. 16
     neighbours -- per cell the rounded mean of the best_k smallest of the
@@ -776,11 +896,16 @@ def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2
     uniqueness, uniqueness_window, speckle_size, speckle_ratio: the two filters of
     sgm_depth_for_view -- the uniqueness test in the sweep's one WTA step, the
     speckle removal behind the support test; off by default, defaults untuned.
+    photo_radius, photo_best_k, photo_min_views, photo_min_score, witnesses: the
+    photo-consistency test of sgm_depth_for_view behind the support test (the
+    sweep's neighbours followed by `witnesses`); the dict then also holds
+    confidence and views.  Off by default, defaults untuned.
     Returns dict(depth, argmin, support[, cost, sgm][, runner_up: with
     want_volumes and uniqueness > 0]); with halvings dict(depth, support)."""
     lib = _capi.load()
     n = len(neighbors)
     filt = _sgm_filter(uniqueness, uniqueness_window, speckle_size, speckle_ratio)
+    photo = _sgm_photo(photo_radius, photo_best_k, photo_min_views, photo_min_score, witnesses)
     d_views, d_k, _, d_support = sgm_sweep_defaults(n)
     opts = SgmSweepOptions(P2_ADAPTIVE if adaptive_p2 else P2_CONSTANT,
                            WINNER_SUBPLANE if subplane else WINNER_PLANE,
@@ -792,9 +917,41 @@ def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2
     full = [dict(M_bwd=np.zeros(9), t_bwd=np.zeros(3), range_main=depth_range,
                  range_neighbor=depth_range, **{k: nb[k] for k in ("image", "M_fwd", "t_fwd")})
             for nb in neighbors]
-    arr = _sgm_neighbors(full, keep) if n else None
+    if photo is not None:
+        full = _sgm_witnesses(full, witnesses)
+    arr = _sgm_neighbors(full, keep) if full else None
     rng = (C.c_float * 2)(float(depth_range[0]), float(depth_range[1]))
     h, w = main_img.shape[:2]
+    if photo is not None:
+        # smvs_sgm_sweep_for_view_raw_photo: every output at either scale
+        if halvings is not None and want_volumes:
+            raise ValueError("want_volumes: the volumes are outputs of the SGM-scale entry")
+        channels, nch, hv = _raw_images(main_img, keep, halvings)
+        ow, oh = _halved(w, h, hv)
+        filt = filt if filt is not None else SgmFilterOptions(*SGM_FILTER_DEFAULTS)
+        depth = np.zeros((oh, ow), dtype=np.float32)
+        support = np.zeros((oh, ow), dtype=np.uint8)
+        argmin = np.zeros((oh, ow), dtype=np.int32) if halvings is None else None
+        cost = np.zeros((oh, ow, num_steps), dtype=np.uint16) if want_volumes else None
+        sgm = np.zeros((oh, ow, num_steps), dtype=np.uint16) if want_volumes else None
+        runner = np.zeros((oh, ow), dtype=np.uint16) \
+            if want_volumes and filt.uniqueness != 0 else None
+        on = photo.radius != 0
+        conf = np.zeros((oh, ow), dtype=np.float32) if on else None
+        views = np.zeros((oh, ow), dtype=np.uint8) if on else None
+        check(lib.smvs_sgm_sweep_for_view_raw_photo(
+            device, _p(main_img, _u8p), w, h, channels, arr, nch, n, hv, rng, num_steps,
+            C.c_uint16(p1), C.c_uint16(p2), C.byref(opts), C.byref(filt), _p(depth, _fp),
+            _p(argmin, _i32p), _p(support, _u8p), _p(cost, _u16p), _p(sgm, _u16p),
+            _p(runner, _u16p), len(full) - n, C.byref(photo), _p(conf, _fp), _p(views, _u8p)))
+        out = dict(depth=depth, support=support, confidence=conf, views=views)
+        if halvings is None:
+            out["argmin"] = argmin
+        if runner is not None:
+            out["runner_up"] = runner
+        if want_volumes:
+            out.update(cost=cost, sgm=sgm)
+        return out
     if halvings is not None:
         if want_volumes:
             raise ValueError("want_volumes: the volumes are outputs of the SGM-scale entry")

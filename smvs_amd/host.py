@@ -242,6 +242,15 @@ class SgmFilter(C.Structure):
                 ("speckle_size", C.c_int), ("speckle_ratio", C.c_float)]
 
 
+class SgmPhoto(C.Structure):
+    """smvs_host_sgm_photo of csrc/host/host_capi.h: ReconSettings::
+    sgm_photo_radius / sgm_photo_best_k / sgm_photo_min_views / sgm_photo_min_score /
+    sgm_photo_witnesses (SGMStereo::Options::photo_radius / ...), passed next to
+    the settings struct, which keeps its layout."""
+    _fields_ = [("radius", C.c_int), ("best_k", C.c_int), ("min_views", C.c_int),
+                ("min_score", C.c_float), ("witnesses", C.c_int)]
+
+
 def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       regularization=1.0, output_scale=2, use_shading=False, use_sgm=True,
                       force_recon=False, force_sgm=False, sgm_range=(0.0, 0.0), sgm_scale=1,
@@ -253,7 +262,9 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       sgm_agree_ratio=0.95, sgm_min_agree=2, sgm_sweep=False,
                       sgm_sweep_min_views=-1, sgm_sweep_best_k=-1, sgm_sweep_support_cost=20,
                       sgm_sweep_min_support=-1, sgm_uniqueness=0, sgm_uniqueness_window=1,
-                      sgm_speckle_size=0, sgm_speckle_ratio=0.95):
+                      sgm_speckle_size=0, sgm_speckle_ratio=0.95, sgm_photo_radius=0,
+                      sgm_photo_best_k=2, sgm_photo_min_views=2, sgm_photo_min_score=0.49,
+                      sgm_photo_witnesses=-1):
     """smvsrecon's scene-level run (app/smvsrecon.cc:400-745) through
     smvs_amd::reconstruct_scene: returns (reconstructed ids, skipped, seconds)
     [, input scale used if `details`].  input_scale < 0 (the default, as
@@ -304,10 +315,22 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     components of fewer than sgm_speckle_size pixels (0 and 1 are off) from the
     final map.  Off by default; (0, 1, 0, 0.95) are defaults of a user option,
     untuned, and nobody has measured them on real scenes.  The reuse rule is that
-    of sgm_subplane (force_sgm)."""
+    of sgm_subplane (force_sgm).
+    sgm_photo_radius, sgm_photo_best_k, sgm_photo_min_views, sgm_photo_min_score,
+    sgm_photo_witnesses: ReconSettings::sgm_photo_radius / ... -- the multi-view
+    photo-consistency test of include/smvs_hip.h behind every view's SGM front
+    end, whichever of the three it is, before the speckle removal: radius 1 .. 3
+    (0 is off), the view's first sgm_photo_witnesses neighbours as witnesses (-1:
+    all num_neighbors of them), the mean of the best_k largest scores, none with
+    fewer than min_views, no depth below min_score.  The confidence is saved as
+    smvs-sgm-confidence next to smvs-sgm.  Off by default; (0, 2, 2, 0.49, -1) are
+    defaults of a user option, untuned, and nobody has measured them on real
+    scenes.  The reuse rule is that of sgm_subplane (force_sgm)."""
     lib = load()
     filt = SgmFilter(int(sgm_uniqueness), int(sgm_uniqueness_window), int(sgm_speckle_size),
                      float(sgm_speckle_ratio))
+    photo = SgmPhoto(int(sgm_photo_radius), int(sgm_photo_best_k), int(sgm_photo_min_views),
+                     float(sgm_photo_min_score), int(sgm_photo_witnesses))
     sweep = SgmSweep(1 if sgm_sweep else 0, sgm_sweep_min_views, sgm_sweep_best_k,
                      sgm_sweep_support_cost, sgm_sweep_min_support)
     st = ReconSettings(image_embedding.encode(), regularization, output_scale,
@@ -322,13 +345,13 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                              C.byref(cap), None, None, None, None, None, None, None)
     out = np.zeros(max(cap.value, 1), np.int32)
     n = C.c_int(0); sk = C.c_int(0); secs = C.c_double(0.0); used = C.c_int(0)
-    rc = lib.smvs_host_reconstruct_scene_filtered(scene_dir.encode(), C.byref(st),
+    rc = lib.smvs_host_reconstruct_scene_photo(scene_dir.encode(), C.byref(st),
         C.c_uint((1 if sgm_adaptive_penalty2 else 0) | (2 if device_input_scaling else 0)
                  | (8 if device_shading_prep else 0) | (16 if gamma_correction else 0)),
         C.c_int(sgm_num_steps), C.c_int(1 if sgm_subplane else 0),
         C.c_int(sgm_neighbors), C.c_int(1 if sgm_consensus else 0),
         C.c_float(sgm_agree_ratio), C.c_int(sgm_min_agree), C.byref(sweep), C.byref(filt),
-        ids.ctypes.data_as(_i32p) if ids is not None else None,
+        C.byref(photo), ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), out.ctypes.data_as(_i32p),
         C.c_int(out.size), C.byref(n), C.byref(sk), C.byref(secs), C.byref(used))
     if rc != 0:
@@ -475,7 +498,8 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
               consensus=False, agree_ratio=0.95, min_agree=2, sweep=False,
               sweep_min_views=-1, sweep_best_k=-1, sweep_support_cost=20,
               sweep_min_support=-1, uniqueness=0, uniqueness_window=1, speckle_size=0,
-              speckle_ratio=0.95):
+              speckle_ratio=0.95, photo_radius=0, photo_best_k=2, photo_min_views=2,
+              photo_min_score=0.49, photo_witnesses=-1):
     """reconstruct_sgm_depth_for_view through the host mirror.
     adaptive_penalty2: SGMStereo::Options::adaptive_penalty2 (the reference's
     build without SSE, lib/sgm_stereo.cc:310-346); off by default.
@@ -503,9 +527,19 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
     SGMStereo::Options::uniqueness / ... -- the two filters of include/smvs_hip.h
     for any of the three front ends (the uniqueness test in every run, the
     speckle removal on the final map); off by default, (0, 1, 0, 0.95) are
-    untuned defaults of a user option."""
+    untuned defaults of a user option.
+    photo_radius, photo_best_k, photo_min_views, photo_min_score, photo_witnesses:
+    SGMStereo::Options::photo_radius / ... -- the multi-view photo-consistency
+    test of include/smvs_hip.h on the final map of any of the three front ends,
+    before the speckle removal, with the first photo_witnesses neighbours of the
+    inputs as witnesses (-1: all of them, 16 at the most).  With photo_radius
+    > 0 returns (depth, confidence), the confidence being what the mirror writes
+    as the smvs-sgm-confidence embedding.  Off by default; (0, 2, 2, 0.49, -1)
+    are untuned defaults of a user option."""
     lib = load()
     keep = []
+    photo = SgmPhoto(int(photo_radius), int(photo_best_k), int(photo_min_views),
+                     float(photo_min_score), int(photo_witnesses))
     filt = SgmFilter(int(uniqueness), int(uniqueness_window), int(speckle_size),
                      float(speckle_ratio))
     sw = SgmSweep(1 if sweep else 0, sweep_min_views, sweep_best_k, sweep_support_cost,
@@ -515,18 +549,19 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
     for _ in range(sgm_scale):
         w, h = (w + 1) // 2, (h + 1) // 2
     out = np.zeros((h, w), dtype=np.float32)
+    conf = np.zeros((h, w), dtype=np.float32) if photo.radius != 0 else None
     ow = C.c_int(0); oh = C.c_int(0)
-    rc = lib.smvs_host_sgm_depth_filtered(C.byref(main), subs, n_subs, C.byref(b),
+    rc = lib.smvs_host_sgm_depth_photo(C.byref(main), subs, n_subs, C.byref(b),
         sgm_scale, C.c_float(min_depth), C.c_float(max_depth), device,
         C.c_int(1 if adaptive_penalty2 else 0), C.c_int(num_steps),
         C.c_int(1 if subplane else 0), C.c_int(neighbors), C.c_int(1 if consensus else 0),
         C.c_float(agree_ratio), C.c_int(min_agree), C.byref(sw), C.byref(filt),
-        out.ctypes.data_as(_fp), C.byref(ow),
-        C.byref(oh))
+        C.byref(photo), out.ctypes.data_as(_fp),
+        conf.ctypes.data_as(_fp) if conf is not None else None, C.byref(ow), C.byref(oh))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
     assert (ow.value, oh.value) == (w, h)
-    return out
+    return out if conf is None else (out, conf)
 
 
 def select_neighbors(scene, view, num_neighbors=6, use_bundle=True):

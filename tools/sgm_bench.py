@@ -25,7 +25,14 @@ in the WTA step of every run (U in 1 .. 99; W planes, 1 without the flag);
 --speckle N [--speckle-ratio R] (with --neighbors): the speckle removal on the
 view's final map (components below N pixels; R 0.95 without the flag), its
 launches counted as merge, and the same launches alone on that map
-(smvs_sgm_filter_speckles) so that their time stands by itself."""
+(smvs_sgm_filter_speckles) so that their time stands by itself.
+--photo R [--photo-best-k K] [--photo-min-views V] [--photo-min-score S]
+[--witnesses N] (with --neighbors): the multi-view photo-consistency test of
+include/smvs_hip.h on the view's final map (window radius R in 1 .. 3; K 2, V 2,
+S 0.49 without the flags) with N ring views as witnesses, the front end's
+neighbours first (N = --neighbors without the flag); its one launch counted as
+merge, and the same launch alone on the map in front of it (smvs_sgm_photo_check)
+with the bytes it moves, so that its time stands by itself."""
 import ctypes as C
 import json
 import os, sys, time
@@ -67,17 +74,20 @@ if uniqueness:
     kw.update(uniqueness=uniqueness, uniqueness_window=_arg("--uniqueness-window", 1))
     print("uniqueness test: %d %%, window %d" % (uniqueness, kw["uniqueness_window"]))
 
+photo = _arg("--photo", 0)
+
 if "--neighbors" in sys.argv:
     n = _arg("--neighbors", 2)
     consensus = "--consensus" in sys.argv
     sweep = "--sweep" in sys.argv
     if sweep and consensus:
         sys.exit("--sweep and --consensus exclude each other")
-    main, subs = synth.ring_cameras(w, h, n)
+    n_all = max(n, _arg("--witnesses", n)) if photo else n
+    main, subs = synth.ring_cameras(w, h, n_all)
     small = [im[::2, ::2].copy() for im in [synth.render(scene, c) for c in [main] + subs]]
     cams = [synth.Camera(c.R, c.t, c.flen, hw, hh) for c in [main] + subs]
     nbs = []
-    for k in range(1, n + 1):
+    for k in range(1, n_all + 1):
         Mf, tf = synth.reprojection(cams[0], cams[k])
         Mb, tb = synth.reprojection(cams[k], cams[0])
         nbs.append(dict(image=small[k], M_fwd=Mf, t_fwd=tf, M_bwd=Mb, t_bwd=tb,
@@ -88,6 +98,16 @@ if "--neighbors" in sys.argv:
         kw.update(speckle_size=speckle, speckle_ratio=speckle_ratio)
         print("speckle removal: components below %d pixels, ratio %g (its launches count as "
               "merge)" % (speckle, speckle_ratio))
+    nbs, further = nbs[:n], nbs[n:]
+    if photo:
+        photo_kw = dict(photo_radius=photo, photo_best_k=_arg("--photo-best-k", 2),
+                        photo_min_views=_arg("--photo-min-views", 2),
+                        photo_min_score=_arg("--photo-min-score", 0.49, float))
+        kw.update(photo_kw, witnesses=further)
+        print("photo-consistency test: radius %d, best %d, at least %d views, score >= %g, %d "
+              "witnesses (its launch counts as merge)"
+              % (photo, photo_kw["photo_best_k"], photo_kw["photo_min_views"],
+                 photo_kw["photo_min_score"], n_all))
     print("front end of a view, %d neighbours, %s" % (
         n, "plane sweep (min_views %d, best_k %d, support_cost %d, min_support %d)"
         % smvs_amd.device.sgm_sweep_defaults(n) if sweep
@@ -96,7 +116,8 @@ if "--neighbors" in sys.argv:
     def view():
         if sweep:
             return smvs_amd.sgm_sweep_for_view(small[0], nbs, (2.0, 10.0), D, 6, p2, **kw)["depth"]
-        return smvs_amd.sgm_depth_for_view(small[0], nbs, D, 6, p2, **kw)
+        out = smvs_amd.sgm_depth_for_view(small[0], nbs, D, 6, p2, **kw)
+        return out["depth"] if isinstance(out, dict) else out
 
     lib = _capi.load()
     view()   # warm-up: workspace growth, first-launch costs
@@ -121,7 +142,35 @@ if "--neighbors" in sys.argv:
             print("kernel %-8s %9.1f us per launch, %9.1f us per view (%d launches per view)"
                   % (name, 1e3 * ms[i] / cnt[i], 1e3 * ms[i] / repeat, cnt[i] // repeat))
     npix = hw * hh
-    if speckle:
+    if photo:
+        # the same launch alone, on the map as it is in front of the test
+        plain = {k: v for k, v in kw.items()
+                 if not k.startswith(("photo", "speckle")) and k != "witnesses"}
+        if sweep:
+            before = smvs_amd.sgm_sweep_for_view(small[0], nbs, (2.0, 10.0), D, 6, p2,
+                                                 **plain)["depth"]
+        else:
+            before = smvs_amd.sgm_depth_for_view(small[0], nbs, D, 6, p2, **plain)
+        alone = (photo, photo_kw["photo_best_k"], photo_kw["photo_min_views"],
+                 photo_kw["photo_min_score"])
+        smvs_amd.sgm_photo_check(small[0], before, nbs + further, *alone)
+        lib.smvs_sgm_profile(1, None, None)
+        for i in range(repeat):
+            after, conf, views = smvs_amd.sgm_photo_check(small[0], before, nbs + further, *alone)
+        pms = (C.c_double * 8)()
+        pcnt = (C.c_longlong * 8)()
+        lib.smvs_sgm_profile(0, pms, pcnt)
+        # read: the main image, the map, the witnesses' images (gathered);
+        # written: the map, the confidence, the views
+        nbytes = npix * (1 + 4 + n_all + 4 + 4 + 1)
+        samples = int((before > 0).sum()) * n_all * (2 * photo + 1) ** 2
+        us = 1e3 * pms[6] / repeat
+        print("photo test alone (%d launch): %.1f us per map, %.1f MB, %.3f TB/s; at most %.1f M "
+              "samples; %d of %d valid pixels removed, views up to %d"
+              % (pcnt[6] // repeat, us, nbytes / 1e6, nbytes / us / 1e6, samples / 1e6,
+                 int(((before > 0) & (after == 0)).sum()), int((before > 0).sum()),
+                 int(views.max())))
+    if speckle and not photo:
         # the same launches alone, on the map as it is in front of the filter
         plain = {k: v for k, v in kw.items() if not k.startswith("speckle")}
         if sweep:
@@ -140,7 +189,11 @@ if "--neighbors" in sys.argv:
               "removed, largest component %d" % (scnt[6] // repeat, 1e3 * sms[6] / repeat,
                                                  int(((before > 0) & (after == 0)).sum()),
                                                  int((before > 0).sum()), int(size.max())))
-    if speckle:
+    if photo:
+        print("merge class: %d launches per view, the photo test%s among them: %.1f us per view"
+              % (cnt[6] // repeat, " and the speckle launches" if speckle else "",
+                 1e3 * ms[6] / repeat))
+    elif speckle:
         print("merge class: %d launches per view, the speckle launches among them: %.1f us per "
               "view" % (cnt[6] // repeat, 1e3 * ms[6] / repeat))
     elif sweep:
@@ -155,7 +208,7 @@ if "--neighbors" in sys.argv:
                                  peak))
     if sweep:
         print("support (one kernel): %.1f us per view" % (1e3 * ms[5] / max(cnt[5], 1)))
-    elif speckle:
+    elif speckle or photo:
         pass
     elif consensus:
         # n forward maps read, n scattered lookups, the merged map written
