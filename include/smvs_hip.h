@@ -707,14 +707,16 @@ int smvs_sgm_sweep_for_view_raw_filtered(int device, const uint8_t *main_img, in
     int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
     uint16_t penalty2, const smvs_sgm_sweep_options *opts,
     const smvs_sgm_filter_options *filter, float *depth, uint8_t *support);
-/* The 16 view and sweep entries (14 above, the two with the photo test below)
- * are three front ends behind one call record (csrc/sgm_internal.h,
+/* The 18 view and sweep entries (14 above, the two with the photo test and the
+ * two with the refinement sweeps below) are three front ends behind one call record (csrc/sgm_internal.h,
  * SgmViewCall): an entry fixes the fields it does not take and hands on the
  * rest.  "SGM scale": channels = 1 for the main image
  * and every neighbour, halvings = 0.  "constant, plane": p2_mode =
  * SMVS_SGM_P2_CONSTANT, winner = SMVS_SGM_WINNER_PLANE.  "off": both filters off
  * (uniqueness = 0, speckle_size = 0), no runner_up.  Every entry but the last two
  * also fixes the photo test: off (radius 0), no witness, no confidence, no views.
+ * Every entry but the two `_refine` ones fixes the refinement sweeps: off
+ * (sweeps 0), no slant.
  *
  *   entry                                 front                 fixes
  *   smvs_sgm_depth_for_view               reference merge       SGM scale; constant, plane; off
@@ -733,10 +735,12 @@ int smvs_sgm_sweep_for_view_raw_filtered(int device, const uint8_t *main_img, in
  *   smvs_sgm_sweep_for_view_raw_filtered  plane sweep           no argmin, cost, sgm, runner_up
  *   smvs_sgm_depth_for_view_raw_photo     opts->merge: either   nothing
  *   smvs_sgm_sweep_for_view_raw_photo     plane sweep           nothing
+ *   smvs_sgm_depth_for_view_raw_refine    opts->merge: either   nothing
+ *   smvs_sgm_sweep_for_view_raw_refine    plane sweep           nothing
  *
  * The reference merge has the depth map as its only output (checked and support
  * must be NULL); the consensus adds checked and support; the sweep's outputs
- * are all optional.  All 16 make their argument checks in one order, before
+ * are all optional.  All 18 make their argument checks in one order, before
  * any device call (csrc/sgm_view.hip, check_sgm_view_call). */
 
 /* Multi-view photo-consistency test.  Not in the reference; opt-in, off by
@@ -834,6 +838,118 @@ int smvs_sgm_sweep_for_view_raw_photo(int device, const uint8_t *main_img, int w
 int smvs_sgm_photo_check(int device, const uint8_t *main_img, int w, int h, const float *depth,
     const smvs_sgm_neighbor *witnesses, int n, const smvs_sgm_photo_options *opts, float *out,
     float *confidence, uint8_t *views);
+
+/* Multi-view plane refinement sweeps.  Not in the reference; opt-in, off by
+ * default (sweeps 0), and with them off the two `_refine` entries below give the
+ * bytes and the launches of the `_photo` entries.  The photo test's confidence
+ * becomes an objective: every pixel holds a small plane hypothesis (a depth and
+ * two slants), and red-black sweeps let it adopt a 4-neighbour's extrapolated
+ * plane, or a deterministic perturbation of its own, whenever that raises its
+ * confidence.  The definition is normative (tests/sgm_refine_ref.py restates
+ * it); it extends the block above and uses its vocabulary.
+ *
+ * Inputs: those of the photo test (I, a, n witnesses, smvs_sgm_photo_options
+ * with radius 1 .. 3) and smvs_sgm_refine_options: sweeps in 0 .. 8 (0: off),
+ * samples in 0 .. 8, depth_step and slant_step finite in [0, 1], seed, fill 0 or 1.
+ *
+ * Hypothesis.  A pixel has none, or (a, gx, gy), three floats with a > 0.  The
+ * depth of window sample (i, j), i, j = -r .. r, is
+ *     d = a + gx * (float)i;  d = d + gy * (float)j;
+ * two rounded products and two rounded sums in this order, contraction off.
+ * Linear in depth, not in inverse depth, on purpose: with gx = gy = 0 every
+ * sample depth is a's bits.
+ *
+ * Confidence of a hypothesis at (x, y): the photo test's confidence with "the
+ * centre pixel's depth" replaced by d(i, j) per sample.  A sample with !(d > 0)
+ * counts as outside (the witness is then not defined).  The integer sums, the
+ * score, the mean of the best k' in descending order in double, the cast to
+ * float, -1.0f with fewer than max(min_views, 1) defined witnesses and views = c
+ * are unchanged.
+ *
+ * Start.  A pixel valid in the input (a > 0.0f) has (a, 0, 0) with that
+ * hypothesis's confidence and views: exactly the photo test's.  Every other pixel
+ * has no hypothesis, confidence -1.0f and views 0.
+ *
+ * Sweep t = 0 .. sweeps - 1, half-sweep c = 0, 1.  Active are the pixels with
+ * ((x + y) & 1) == c; with fill = 0 only those valid in the input.  An active
+ * pixel considers the candidates below in this order; a candidate replaces the
+ * pixel's hypothesis, confidence and views iff its confidence, as a float, is
+ * strictly greater than the current one (a tie keeps the earlier; a pixel without
+ * a hypothesis holds -1.0f).
+ *   1. The left (x - 1), right (x + 1), up (y - 1) and down (y + 1) neighbour, if
+ *      it is inside the image and has a hypothesis (a', gx', gy').  The slants
+ *      are taken over; the depth is extrapolated by one float addition:
+ *          left a' + gx',  right a' - gx',  up a' + gy',  down a' - gy';
+ *      skipped if !(depth > 0).  The four neighbours have the other colour and do
+ *      not change in this half-sweep, so working in place is race-free and the
+ *      result does not depend on the launch geometry.
+ *   2. m = 0 .. samples - 1, only if the pixel has a hypothesis (a, gx, gy) by
+ *      then, each from the pixel's hypothesis AT THAT MOMENT, all in uint32:
+ *          mix(v): v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b;
+ *                  v ^= v >> 16;
+ *          h0  = mix(seed ^ mix((uint32)(y * w + x) ^ mix((uint32)(t * 16 + m))));
+ *          h_j = mix(h0 + j * 0x9e3779b9), j = 1, 2, 3;
+ *          u_j = (float)((int32)(h_j >> 8) - 8388608) * 2^-23   (exact, [-1, 1));
+ *          s = 2^-t (exact);
+ *          e = a * depth_step;  e = e * s;  a" = a + e * u_1;
+ *          g = a * slant_step;  g = g * s;  gx" = gx + g * u_2;  gy" = gy + g * u_3;
+ *      every product and sum rounded, contraction off; skipped if !(a" > 0).
+ *
+ * End.  A pixel with a hypothesis: out = 0.0f where confidence < min_score (the
+ * photo test's float comparison), else out = a; slant = (gx, gy); confidence and
+ * views those of the final hypothesis (a dropped pixel keeps all three).  A pixel
+ * without a hypothesis keeps its input bits (NaN and negatives included),
+ * confidence -1.0f, views 0, slant (0, 0).
+ *
+ * Consequences: sweeps = 0 gives the photo test's three outputs to the byte and
+ * zero slants; a pixel valid in the input never ends with a lower confidence
+ * than the photo test gives it; fill = 0 never gives a depth to a pixel that had
+ * none.
+ *
+ * In the two view entries the refinement takes the photo test's place: on the
+ * view's final map, before the speckle removal; checked and support stay those
+ * of the unfiltered map.  1 + 2 sweeps + 1 launches, timed in class
+ * SMVS_SGM_K_MERGE of smvs_sgm_profile.  The defaults of the layers above (sweeps
+ * 0, samples 2, depth_step 0.02, slant_step 0.01, seed 1, fill 1; at 128 planes
+ * over 3 .. 12 two planes are about 2 % apart at the far end) are defaults of a
+ * user option, untuned; nobody has measured them on real scenes.
+ *
+ * SMVS_ERR_INVALID before any device call, behind the checks of the `_photo`
+ * entry and in this order: a NULL refine pointer; sweeps or samples outside
+ * 0 .. 8; depth_step or slant_step outside [0, 1] or NaN; fill other than 0 or 1;
+ * sweeps > 0 with photo radius 0; a slant output with sweeps 0 (errors, never
+ * silently ignored). */
+typedef struct {
+    int sweeps; int samples; float depth_step; float slant_step; uint32_t seed; int fill;
+} smvs_sgm_refine_options;
+
+/* smvs_sgm_depth_for_view_raw_photo with the sweeps; extra optional output
+ * slant[h][w][2] (f32, gx then gy) at SGM scale. */
+int smvs_sgm_depth_for_view_raw_refine(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_view_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support,
+    int n_witness, const smvs_sgm_photo_options *photo, float *confidence, uint8_t *views,
+    const smvs_sgm_refine_options *refine, float *slant);
+/* smvs_sgm_sweep_for_view_raw_photo with the sweeps */
+int smvs_sgm_sweep_for_view_raw_refine(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_sweep_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint8_t *support,
+    uint16_t *cost, uint16_t *sgm, uint16_t *runner_up, int n_witness,
+    const smvs_sgm_photo_options *photo, float *confidence, uint8_t *views,
+    const smvs_sgm_refine_options *refine, float *slant);
+/* The kernels alone, on a map and SGM-scale images of the caller, as
+ * smvs_sgm_photo_check: out[w * h] (may be depth itself), slant[w * h * 2],
+ * confidence[w * h] and views[w * h] (each of the three may be NULL).  No minimum
+ * size; radius in 1 .. 3, n in 1 .. 16; sweeps = 0 is accepted (the start and the
+ * end alone: the photo test's outputs and zero slants). */
+int smvs_sgm_plane_refine(int device, const uint8_t *main_img, int w, int h, const float *depth,
+    const smvs_sgm_neighbor *witnesses, int n, const smvs_sgm_photo_options *photo,
+    const smvs_sgm_refine_options *refine, float *out, float *slant, float *confidence,
+    uint8_t *views);
 
 /* The speckle kernels alone, on a map of the caller: depth[w * h], out[w * h]
  * (may be depth itself), size[w * h] (may be NULL); w * h < 2^31.  The kernels

@@ -8,7 +8,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libsmvs_hip.so")
 SOURCES = ["ctx.hip", "gn_construct.hip", "cg.hip", "cg_resident.hip", "reactivate.hip", "newton_loop.hip",
            "surface_maps.hip", "sgm.hip",
-           "sgm_paths.hip", "sgm_wta.hip", "sgm_view.hip", "sgm_sweep.hip", "sgm_speckle.hip", "sgm_photo.hip", "image_prep.hip", "bilateral.hip",
+           "sgm_paths.hip", "sgm_wta.hip", "sgm_view.hip", "sgm_sweep.hip", "sgm_speckle.hip", "sgm_photo.hip", "sgm_refine.hip", "image_prep.hip", "bilateral.hip",
            "scale.hip", "topology.hip", "topo_zbuffer.hip", "topo_visibility.hip", "topo_mse.hip",
            "topo_cut.hip", "mesh.hip", "simplify.hip", "pool.hip", "surface.hip"]
 # HIP-free units of the library: the host compiler builds them

@@ -385,7 +385,7 @@ int device_grow(T **ptr, size_t *cap, size_t count, size_t each = 1)
 // A reusable device workspace of the context-free entry points (pool.hip): a
 // stream, named device buffers that only grow, pinned staging memory.
 struct Workspace {
-    enum { SLOTS = 28 };
+    enum { SLOTS = 29 };
     struct Buf { void *p = nullptr; size_t cap = 0; };
     int device = 0;
     hipStream_t stream = nullptr;

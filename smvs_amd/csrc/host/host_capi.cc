@@ -434,6 +434,60 @@ check_host_sgm_photo(const smvs_host_sgm_photo *p, char const* who)
 }
 }
 
+namespace {
+// the accepted set of include/smvs_hip.h (a NaN step fails the comparisons);
+// sweeps without the photo test: the device refuses them
+void
+check_host_sgm_refine(const smvs_host_sgm_refine *r, char const* who)
+{
+    if (r == nullptr)
+        return;
+    if (r->sweeps < 0 || r->sweeps > 8 || r->samples < 0 || r->samples > 8
+        || !(r->depth_step >= 0.0f && r->depth_step <= 1.0f)
+        || !(r->slant_step >= 0.0f && r->slant_step <= 1.0f) || (r->fill != 0 && r->fill != 1))
+        throw std::invalid_argument(std::string(who) + ": sgm_refine_sweeps and "
+            "sgm_refine_samples must be in [0, 8], sgm_refine_depth_step and "
+            "sgm_refine_slant_step in [0, 1] and sgm_refine_fill 0 or 1");
+}
+
+void
+set_refine(SGMStereo::Options* opts, const smvs_host_sgm_refine *r)
+{
+    if (r == nullptr)
+        return;
+    opts->refine_sweeps = r->sweeps;
+    opts->refine_samples = r->samples;
+    opts->refine_depth_step = r->depth_step;
+    opts->refine_slant_step = r->slant_step;
+    opts->refine_seed = r->seed;
+    opts->refine_fill = r->fill;
+}
+}
+
+extern "C" int
+smvs_host_sgm_refine_defaults(int *ints8, float *steps4)
+{
+    if (ints8 == nullptr || steps4 == nullptr) {
+        g_host_error = "smvs_host_sgm_refine_defaults: bad argument";
+        return -1;
+    }
+    SGMStereo::Options const opts;
+    ReconSettings const conf;
+    ints8[0] = opts.refine_sweeps;
+    ints8[1] = opts.refine_samples;
+    ints8[2] = (int)opts.refine_seed;
+    ints8[3] = opts.refine_fill;
+    ints8[4] = conf.sgm_refine_sweeps;
+    ints8[5] = conf.sgm_refine_samples;
+    ints8[6] = (int)conf.sgm_refine_seed;
+    ints8[7] = conf.sgm_refine_fill;
+    steps4[0] = opts.refine_depth_step;
+    steps4[1] = opts.refine_slant_step;
+    steps4[2] = conf.sgm_refine_depth_step;
+    steps4[3] = conf.sgm_refine_slant_step;
+    return 0;
+}
+
 extern "C" int
 smvs_host_sgm_photo_defaults(int *ints8, float *scores2)
 {
@@ -478,9 +532,25 @@ smvs_host_sgm_depth_photo(const smvs_host_view *main_in, const smvs_host_view *s
     const smvs_host_sgm_photo *photo, float *depth_out, float *confidence_out, int *out_w,
     int *out_h)
 {
+    return smvs_host_sgm_depth_refine(main_in, subs_in, n_subs, bundle_in, sgm_scale, min_depth,
+        max_depth, device, adaptive_penalty2, num_steps, subplane, num_neighbors, consensus,
+        agree_ratio, min_agree, sweep, filter, photo, nullptr, depth_out, confidence_out, nullptr,
+        out_w, out_h);
+}
+
+extern "C" int
+smvs_host_sgm_depth_refine(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, int sgm_scale,
+    float min_depth, float max_depth, int device, int adaptive_penalty2,
+    int num_steps, int subplane, int num_neighbors, int consensus, float agree_ratio,
+    int min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const smvs_host_sgm_photo *photo, const smvs_host_sgm_refine *refine, float *depth_out,
+    float *confidence_out, float *slant_out, int *out_w, int *out_h)
+{
     try {
         check_host_sgm_filter(filter, "smvs_host_sgm_depth_filtered");
         check_host_sgm_photo(photo, "smvs_host_sgm_depth_photo");
+        check_host_sgm_refine(refine, "smvs_host_sgm_depth_refine");
         // (before the views are copied: an argument error needs no image)
         bool const sweep_on = sweep != nullptr && sweep->sweep != 0;
         if (sweep_on && consensus != 0)
@@ -529,8 +599,13 @@ smvs_host_sgm_depth_photo(const smvs_host_view *main_in, const smvs_host_view *s
             opts.photo_min_score = photo->min_score;
             opts.photo_witnesses = photo->witnesses;
         }
+        set_refine(&opts, refine);
         FloatImage::Ptr d = reconstruct_sgm_depth_for_view(opts, main_view, subs,
             bundle);
+        if (slant_out != nullptr && main_view->has_embedding("smvs-sgm-slant")) {
+            FloatImage::Ptr c = main_view->get_embedding("smvs-sgm-slant");
+            std::memcpy(slant_out, c->begin(), sizeof(float) * c->get_pixel_amount() * c->channels());
+        }
         if (confidence_out != nullptr && main_view->has_embedding("smvs-sgm-confidence")) {
             FloatImage::Ptr c = main_view->get_embedding("smvs-sgm-confidence");
             std::memcpy(confidence_out, c->begin(), sizeof(float) * c->get_pixel_amount());
@@ -1200,9 +1275,25 @@ smvs_host_reconstruct_scene_photo(const char *scene_dir,
     int *reconstructed_out, int max_reconstructed, int *n_reconstructed, int *n_skipped,
     double *seconds, int *input_scale_used)
 {
+    return smvs_host_reconstruct_scene_refine(scene_dir, o, flags, sgm_num_steps, sgm_subplane,
+        sgm_neighbors, sgm_consensus, sgm_agree_ratio, sgm_min_agree, sweep, filter, photo,
+        nullptr, view_ids, n_view_ids, reconstructed_out, max_reconstructed, n_reconstructed,
+        n_skipped, seconds, input_scale_used);
+}
+
+extern "C" int
+smvs_host_reconstruct_scene_refine(const char *scene_dir,
+    const smvs_host_recon_settings *o, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const smvs_host_sgm_photo *photo, const smvs_host_sgm_refine *refine, const int *view_ids,
+    int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
+    int *n_skipped, double *seconds, int *input_scale_used)
+{
     try {
         check_host_sgm_filter(filter, "smvs_host_reconstruct_scene_filtered");
         check_host_sgm_photo(photo, "smvs_host_reconstruct_scene_photo");
+        check_host_sgm_refine(refine, "smvs_host_reconstruct_scene_refine");
         bool const sweep_on = sweep != nullptr && sweep->sweep != 0;
         if (sweep_on && sgm_consensus != 0)
             throw std::invalid_argument("smvs_host_reconstruct_scene_sweep: sgm_sweep and "
@@ -1271,6 +1362,14 @@ smvs_host_reconstruct_scene_photo(const char *scene_dir,
             conf.sgm_photo_min_views = photo->min_views;
             conf.sgm_photo_min_score = photo->min_score;
             conf.sgm_photo_witnesses = photo->witnesses;
+        }
+        if (refine != nullptr) {
+            conf.sgm_refine_sweeps = refine->sweeps;
+            conf.sgm_refine_samples = refine->samples;
+            conf.sgm_refine_depth_step = refine->depth_step;
+            conf.sgm_refine_slant_step = refine->slant_step;
+            conf.sgm_refine_seed = refine->seed;
+            conf.sgm_refine_fill = refine->fill;
         }
         conf.device_input_scaling = (flags & SMVS_HOST_SCENE_DEVICE_INPUT_SCALING) != 0u;
         conf.device_shading_prep = (flags & SMVS_HOST_SCENE_DEVICE_SHADING_PREP) != 0u;

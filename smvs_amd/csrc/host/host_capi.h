@@ -227,6 +227,34 @@ int smvs_host_sgm_depth_photo(const smvs_host_view *main_view,
     int consensus, float agree_ratio, int min_agree, const smvs_host_sgm_sweep *sweep,
     const smvs_host_sgm_filter *filter, const smvs_host_sgm_photo *photo, float *depth_out,
     float *confidence_out, int *out_w, int *out_h);
+/* SGMStereo::Options::refine_sweeps / refine_samples / refine_depth_step /
+ * refine_slant_step / refine_seed / refine_fill (the multi-view plane refinement
+ * sweeps of include/smvs_hip.h; not in the reference). */
+typedef struct {
+    int sweeps, samples;
+    float depth_step, slant_step;
+    uint32_t seed;
+    int fill;
+} smvs_host_sgm_refine;
+/* smvs_host_sgm_depth_photo with the refinement sweeps in the photo test's place,
+ * for any of the three front ends.  sweeps or samples outside 0 .. 8, a step
+ * outside [0, 1] or NaN and fill other than 0 or 1 are argument errors before
+ * anything runs; the device refuses sweeps > 0 with the photo test off.
+ * slant_out (may be NULL): the slants [h][w][2], written with the sweeps on.
+ * refine == NULL or sweeps 0: off; smvs_host_sgm_depth_photo forwards to this
+ * with NULL. */
+int smvs_host_sgm_depth_refine(const smvs_host_view *main_view,
+    const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
+    int sgm_scale, float min_depth, float max_depth, int device,
+    int adaptive_penalty2, int num_steps, int subplane, int num_neighbors,
+    int consensus, float agree_ratio, int min_agree, const smvs_host_sgm_sweep *sweep,
+    const smvs_host_sgm_filter *filter, const smvs_host_sgm_photo *photo,
+    const smvs_host_sgm_refine *refine, float *depth_out, float *confidence_out,
+    float *slant_out, int *out_w, int *out_h);
+/* The refine options as a default-constructed SGMStereo::Options (ints8[0 .. 3],
+ * steps4[0 .. 1]) and ReconSettings (ints8[4 .. 7], steps4[2 .. 3]) hold them:
+ * sweeps, samples, seed, fill; depth_step, slant_step (no device involved). */
+int smvs_host_sgm_refine_defaults(int *ints8, float *steps4);
 /* The photo options as a default-constructed SGMStereo::Options (ints8[0 .. 3],
  * scores2[0]) and ReconSettings (ints8[4 .. 7], scores2[1]) hold them: radius,
  * best_k, min_views, witnesses; min_score (no device involved). */
@@ -419,6 +447,21 @@ int smvs_host_reconstruct_scene_photo(const char *scene_dir,
     const smvs_host_sgm_photo *photo, const int *view_ids, int n_view_ids,
     int *reconstructed_out, int max_reconstructed, int *n_reconstructed, int *n_skipped,
     double *seconds, int *input_scale_used);
+
+/* The same with ReconSettings::sgm_refine_sweeps / sgm_refine_samples /
+ * sgm_refine_depth_step / sgm_refine_slant_step / sgm_refine_seed /
+ * sgm_refine_fill: the plane refinement sweeps in the photo test's place, the
+ * slants saved as smvs-sgm-slant (two channels) next to smvs-sgm-confidence.  A
+ * value outside the accepted set is an argument error before the scene is read;
+ * refine == NULL: off (smvs_host_reconstruct_scene_photo forwards to this with
+ * NULL).  The reuse rule is that of sgm_subplane (force_sgm). */
+int smvs_host_reconstruct_scene_refine(const char *scene_dir,
+    const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const smvs_host_sgm_photo *photo, const smvs_host_sgm_refine *refine, const int *view_ids,
+    int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
+    int *n_skipped, double *seconds, int *input_scale_used);
 
 /* smvsrecon's generate_mesh (app/smvsrecon.cc:278-343, MeshGenerator::
  * generate_mesh, lib/mesh_generator.cc:160-299) on a reconstructed scene: the

@@ -602,6 +602,12 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                         sgm_opts.photo_min_views = conf.sgm_photo_min_views;
                         sgm_opts.photo_min_score = conf.sgm_photo_min_score;
                         sgm_opts.photo_witnesses = conf.sgm_photo_witnesses;
+                        sgm_opts.refine_sweeps = conf.sgm_refine_sweeps;
+                        sgm_opts.refine_samples = conf.sgm_refine_samples;
+                        sgm_opts.refine_depth_step = conf.sgm_refine_depth_step;
+                        sgm_opts.refine_slant_step = conf.sgm_refine_slant_step;
+                        sgm_opts.refine_seed = conf.sgm_refine_seed;
+                        sgm_opts.refine_fill = conf.sgm_refine_fill;
                         (void)reconstruct_sgm_depth_for_view(sgm_opts, main_view,
                             stereo_views, bundle);
                         save_mvei(view.image_path("smvs-sgm"),
@@ -609,6 +615,9 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                         if (main_view->has_embedding("smvs-sgm-confidence"))
                             save_mvei(view.image_path("smvs-sgm-confidence"),
                                 main_view->get_embedding("smvs-sgm-confidence"));
+                        if (main_view->has_embedding("smvs-sgm-slant"))
+                            save_mvei(view.image_path("smvs-sgm-slant"),
+                                main_view->get_embedding("smvs-sgm-slant"));
                     } else {
                         main_view->write_image_to_view(
                             load_mvei_float(view.image_path("smvs-sgm")), "smvs-sgm");

@@ -149,6 +149,19 @@ struct ReconSettings
     int sgm_photo_min_views = 2;
     float sgm_photo_min_score = 0.49f;
     int sgm_photo_witnesses = -1;
+    // SGMStereo::Options::refine_sweeps / refine_samples / refine_depth_step /
+    // refine_slant_step / refine_seed / refine_fill -- the multi-view plane
+    // refinement sweeps of include/smvs_hip.h in the photo test's place (they
+    // need sgm_photo_radius > 0); the slants are saved as smvs-sgm-slant (two
+    // channels) next to smvs-sgm-confidence, and the optimizer does not read
+    // them.  Off by default (sweeps 0); untuned defaults of a user option; the
+    // reuse rule is that of sgm_subplane (force_sgm).
+    int sgm_refine_sweeps = 0;
+    int sgm_refine_samples = 2;
+    float sgm_refine_depth_step = 0.02f;
+    float sgm_refine_slant_step = 0.01f;
+    uint32_t sgm_refine_seed = 1;
+    int sgm_refine_fill = 1;
     // not in the reference's AppSettings: the input scaling of :621-650 on the
     // device (rescale_half_size_gaussian_device), one ViewQueue task per view
     bool device_input_scaling = false;

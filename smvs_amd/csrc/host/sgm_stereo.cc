@@ -152,10 +152,11 @@ prepare_pair(SGMStereo::Options const& o, StereoView::Ptr main_view,
 
 // pairs: the n_front neighbours of the front end, then the further witnesses
 // of the photo-consistency test (none with the test off); *confidence: its map
-// when it is on
+// when it is on; *slant: the two slants of the refinement sweeps when they are on
 FloatImage::Ptr
 run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
-    std::vector<PairInputs> const& pairs, int n_front, FloatImage::Ptr* confidence)
+    std::vector<PairInputs> const& pairs, int n_front, FloatImage::Ptr* confidence,
+    FloatImage::Ptr* slant)
 {
     std::vector<smvs_sgm_neighbor> dev;
     std::vector<int> channels;
@@ -186,7 +187,28 @@ run_pairs(SGMStereo::Options const& o, StereoView::Ptr main_view,
     bool const filtered = !o.filters_default();
     smvs_sgm_photo_options const photo = { o.photo_radius, o.photo_best_k, o.photo_min_views,
         o.photo_min_score };
-    if (o.photo_radius != 0) {
+    smvs_sgm_refine_options const refine = { o.refine_sweeps, o.refine_samples,
+        o.refine_depth_step, o.refine_slant_step, o.refine_seed, o.refine_fill };
+    if (!o.refine_default()) {
+        // the sweeps in the test's place (sweeps 0: the test, or nothing); the
+        // device refuses sweeps without the test
+        if (o.photo_radius != 0)
+            *confidence = FloatImage::create_for_overwrite(w, h, 1);
+        if (o.refine_sweeps != 0)
+            *slant = FloatImage::create_for_overwrite(w, h, 2);
+        float* const conf = *confidence != nullptr ? (*confidence)->begin() : nullptr;
+        float* const sl = *slant != nullptr ? (*slant)->begin() : nullptr;
+        if (o.sweep)
+            SGM_DEVICE_CALL(smvs_sgm_sweep_for_view_raw_refine, o.device, pixels, fw, fh, fc,
+                dev.data(), channels.data(), n, o.scale, dev[0].range_main, o.num_steps,
+                o.penalty1, o.penalty2, &sweep_opts, &filter, depth->begin(), nullptr, nullptr,
+                nullptr, nullptr, nullptr, n_witness, &photo, conf, nullptr, &refine, sl);
+        else
+            SGM_DEVICE_CALL(smvs_sgm_depth_for_view_raw_refine, o.device, pixels, fw, fh, fc,
+                dev.data(), channels.data(), n, o.scale, o.num_steps, o.penalty1, o.penalty2,
+                &view_opts, &filter, depth->begin(), nullptr, nullptr, n_witness, &photo,
+                conf, nullptr, &refine, sl);
+    } else if (o.photo_radius != 0) {
         // the test behind whichever front: the entries that take every option
         *confidence = FloatImage::create_for_overwrite(w, h, 1);
         if (o.sweep)
@@ -238,8 +260,9 @@ SGMStereo::reconstruct(Options sgm_opts, StereoView::Ptr main_view,
     std::vector<PairInputs> pairs(1);
     prepare_pair(sgm_opts, main_view, neighbor, bundle, &pairs[0]);
     sgm_opts.photo_radius = 0;      // (a pair has no further witness)
-    FloatImage::Ptr confidence;
-    return run_pairs(sgm_opts, main_view, pairs, 1, &confidence);
+    sgm_opts.refine_sweeps = 0;
+    FloatImage::Ptr confidence, slant;
+    return run_pairs(sgm_opts, main_view, pairs, 1, &confidence, &slant);
 }
 
 FloatImage::Ptr
@@ -276,10 +299,12 @@ reconstruct_sgm_depth_for_view(SGMStereo::Options opts,
     std::vector<PairInputs> pairs(n_all);
     for (std::size_t k = 0; k < pairs.size(); ++k)
         prepare_pair(opts, main_view, neighbors[k], bundle, &pairs[k]);
-    FloatImage::Ptr confidence;
-    FloatImage::Ptr d1 = run_pairs(opts, main_view, pairs, (int)n_front, &confidence);
+    FloatImage::Ptr confidence, slant;
+    FloatImage::Ptr d1 = run_pairs(opts, main_view, pairs, (int)n_front, &confidence, &slant);
     if (confidence != nullptr)
         main_view->write_image_to_view(confidence, "smvs-sgm-confidence");
+    if (slant != nullptr)
+        main_view->write_image_to_view(slant, "smvs-sgm-slant");
     // (app/smvsrecon.cc:383: write_depth_to_view -- the conversion of the stored
     // copy to MVE's convention waits until the embedding is read; the optimizer
     // of this view takes the map as it is and converts on the device)

@@ -2,7 +2,8 @@
 // cost volumes, the 8-path aggregation, the WTA, the left/right check and the
 // merge run on the device (smvs_sgm_depth_for_view_raw_opts / _raw_merge, or
 // smvs_sgm_sweep_for_view_raw, or with the photo-consistency test the two
-// `_raw_photo` entries); the host
+// `_raw_photo` entries, with the refinement sweeps the two `_raw_refine`
+// entries); the host
 // keeps the depth range from the bundle and the image half-sizing.
 #pragma once
 
@@ -109,6 +110,30 @@ public:
         int photo_min_views = 2;
         float photo_min_score = 0.49f;
         int photo_witnesses = -1;
+
+        // not in the reference either: the multi-view plane refinement sweeps of
+        // include/smvs_hip.h in the photo test's place (they need photo_radius >
+        // 0).  refine_sweeps (1 .. 8; 0 is off) red-black sweeps in which a pixel
+        // adopts a 4-neighbour's extrapolated plane (depth and two slants) or one
+        // of refine_samples (0 .. 8) hashed perturbations of its own -- relative
+        // steps refine_depth_step and refine_slant_step, halved per sweep, from
+        // refine_seed -- whenever that raises the photo test's confidence;
+        // refine_fill = 1 lets a pixel without a depth adopt a neighbour's
+        // plane.  With the sweeps on the slants are written as the two-channel
+        // smvs-sgm-slant embedding; the optimizer does not read them.
+        // (0, 2, 0.02, 0.01, 1, 1) are defaults of a user option, untuned: nobody
+        // has measured them on real scenes.
+        int refine_sweeps = 0;
+        int refine_samples = 2;
+        float refine_depth_step = 0.02f;
+        float refine_slant_step = 0.01f;
+        uint32_t refine_seed = 1;
+        int refine_fill = 1;
+        bool refine_default() const
+        {
+            return refine_sweeps == 0 && refine_samples == 2 && refine_depth_step == 0.02f
+                && refine_slant_step == 0.01f && refine_seed == 1 && refine_fill == 1;
+        }
 
         // the plane counts smvs_sgm_run / smvs_sgm_depth_for_view accept
         static bool valid_num_steps(int n)

@@ -3,8 +3,8 @@
 // winner-takes-all), sgm_view.hip (a view's front end), sgm_sweep.hip (the
 // opt-in plane sweep over n neighbours), sgm_speckle.hip (the opt-in speckle
 // removal), sgm_photo.hip (the opt-in multi-view photo-consistency test),
-// image_prep.hip (a view's input image), bilateral.hip (the joint bilateral
-// upsample).
+// sgm_refine.hip (the opt-in multi-view plane refinement sweeps), image_prep.hip
+// (a view's input image), bilateral.hip (the joint bilateral upsample).
 #pragma once
 
 #include "common.h"
@@ -59,9 +59,10 @@ enum {
     WS_FWDN, WS_BWDN, WS_SUPPORT,                                     // consensus merge: n + n maps, support
     WS_SWEEP,                                                         // plane sweep: n cost volumes
     WS_SPECKLE, WS_RUNNER_UP,                                         // filters: labels + counts, runner-up map
-    WS_PHOTO, WS_PHOTO_OUT                                            // photo test: witness images; confidence + views
+    WS_PHOTO, WS_PHOTO_OUT,                                           // photo test: witness images; confidence + views
+    WS_REFINE                                                         // refinement: a, gx, gy; the slants
 };
-static_assert(WS_PHOTO_OUT < Workspace::SLOTS, "the last slot must exist in a Workspace");
+static_assert(WS_REFINE < Workspace::SLOTS, "the last slot must exist in a Workspace");
 
 // The largest plane count of a run: the key of the WTA kernels is
 // value * 256 + plane (one byte for the plane), and 64 lanes x 4 planes is one
@@ -198,6 +199,30 @@ int sgm_launch_photo(Workspace &ws, SgmProfile *prof, const uint8_t *d_main, int
     const float *d_depth, const SgmPhotoWitness *witnesses, int n,
     smvs_sgm_photo_options const &opts, float *d_out, float *d_confidence, uint8_t *d_views);
 
+// The plane refinement sweeps of include/smvs_hip.h ("Multi-view plane
+// refinement sweeps"): sweeps 0 is off.
+inline bool
+sgm_refine_on(const smvs_sgm_refine_options *refine)
+{
+    return refine != nullptr && refine->sweeps > 0;
+}
+// smvs_sgm_refine_options: non-NULL, sweeps and samples in 0 .. 8, depth_step and
+// slant_step in [0, 1] (a NaN is none), fill 0 or 1.  (sgm_refine.hip)
+int check_sgm_refine(const smvs_sgm_refine_options *refine);
+// Floats per pixel of slot WS_REFINE: the state planes a, gx, gy, then the slant
+// output [h][w][2].  (The state's confidence and views are the photo test's
+// outputs, slot WS_PHOTO_OUT.)
+constexpr size_t SGM_REFINE_PLANES = 5;
+// The refinement of d_depth[w * h] against n witnesses into d_out (may be
+// d_depth), d_slant (may be null), d_confidence and d_views (the state: neither
+// may be null) on the workspace's stream, with d_state[3 * w * h] to work in: a
+// start launch, 2 * sweeps half-sweep launches, an end launch, each under a timer
+// of class SMVS_SGM_K_MERGE.  hipGetLastError.  (sgm_refine.hip)
+int sgm_launch_refine(Workspace &ws, SgmProfile *prof, const uint8_t *d_main, int w, int h,
+    const float *d_depth, const SgmPhotoWitness *witnesses, int n,
+    smvs_sgm_photo_options const &photo, smvs_sgm_refine_options const &refine, float *d_state,
+    float *d_out, float *d_slant, float *d_confidence, uint8_t *d_views);
+
 // What a run is asked for besides its images and depth range: the options of
 // SGMStereo (num_steps, the penalties), smvs_sgm_p2_mode and smvs_sgm_winner.
 // Each entry fills one and every stage of the run reads it.
@@ -274,11 +299,12 @@ struct SgmPreparedSize {
 SgmPreparedSize sgm_prepared_size(int w, int h, int channels, int halvings);
 
 // ------------------------------------------------- a view entry's call record
-// What one of the 16 smvs_sgm_depth_for_view* / smvs_sgm_sweep_for_view*
+// What one of the 18 smvs_sgm_depth_for_view* / smvs_sgm_sweep_for_view*
 // entries is asked for (include/smvs_hip.h: which entry fixes which field).
 // The entries at SGM scale are the raw ones with channels = 1, SGM_ONE_CHANNEL
 // and halvings = 0; the entries without filters those with SGM_FILTERS_OFF; the
-// 14 without the photo test those with SGM_PHOTO_OFF and no further witness.
+// 14 without the photo test those with SGM_PHOTO_OFF and no further witness; the
+// 16 without the refinement those with SGM_REFINE_OFF and no slant.
 // neighbors and neighbor_channels hold n_neighbors + n_witness entries: the
 // first n_neighbors go through the front, all of them are witnesses of the test.
 struct SgmViewCall {
@@ -303,6 +329,8 @@ struct SgmViewCall {
     const smvs_sgm_photo_options *photo;
     float *confidence;              // its outputs; null: not asked for
     uint8_t *views;
+    const smvs_sgm_refine_options *refine;  // the refinement sweeps, in the photo test's place
+    float *slant;                   // their output [h][w][2]; null: not asked for
 };
 constexpr int SGM_ONE_CHANNEL[SMVS_MAX_SUBS] = { 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1 };
 static_assert(SMVS_MAX_SUBS == 16, "SGM_ONE_CHANNEL: one entry per neighbour");
@@ -311,6 +339,8 @@ constexpr smvs_sgm_filter_options SGM_FILTERS_OFF = { 0, 1, 0, 0.95f };
 // (what sgm_photo_on makes of it: no launch; best_k and min_views pass the check
 // for every neighbour count)
 constexpr smvs_sgm_photo_options SGM_PHOTO_OFF = { 0, 0, 0, 0.49f };
+// (what sgm_refine_on makes of it: the photo test's launch, or none)
+constexpr smvs_sgm_refine_options SGM_REFINE_OFF = { 0, 2, 0.02f, 0.01f, 1u, 1 };
 
 // Every refusal of a view entry, before its first device call, in the one
 // order written above it.  (sgm_view.hip)
@@ -336,6 +366,7 @@ struct SgmViewSession {
     uint8_t *d_witness = nullptr, *d_views = nullptr;
     size_t witness_at[SMVS_MAX_SUBS + 1] = { 0 };
     float *d_confidence = nullptr;
+    float *d_refine = nullptr;      // the refinement's planes (WS_REFINE), when it is on
     explicit SgmViewSession(SgmViewCall const &call) : C(call), lease(call.device), B(lease.w) {}
     Workspace &ws() { return *lease.w; }
     // the call's filter and want_sgm, the main image prepared (WS_MAIN, WS_RAW),
@@ -350,8 +381,9 @@ struct SgmViewSession {
     // SGMStereo::reconstruct, sgm_stereo.cc:46-62: main -> neighbour k, then
     // neighbour k -> main with the neighbour's own depth range
     int run_pair(int k, const uint8_t *d_nbr, int nw, int nh, float *d_fwd, float *d_bwd);
-    // the photo test on d_map when on, the speckle filter on d_map when on, then
-    // the outputs the call asks for
+    // the photo test on d_map when on (with the refinement sweeps on: those in its
+    // place), the speckle filter on d_map when on, then the outputs the call asks
+    // for
     int finish(float *d_map, const float *d_checked, const uint8_t *d_support);
 };
 // check, session, front: what every view entry does with its record

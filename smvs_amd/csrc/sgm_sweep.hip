@@ -327,18 +327,20 @@ sgm_front_sweep(SgmViewSession &S, SgmViewCall const &C)
 
 using namespace smvs_hip;
 
-// One entry fills the record: raw images, the filters, the photo test, every
-// output.  The two with the filters are that one with the photo test off (the
-// one at SGM scale has the volumes among its outputs, the raw one has not); the
-// two without the filters are those with both filters off.
+// One entry fills the record: raw images, the filters, the photo test, the
+// refinement sweeps, every output; the one with the photo test is that one with
+// the refinement off.  The two with the filters are that one with the photo test
+// off (the one at SGM scale has the volumes among its outputs, the raw one has
+// not); the two without the filters are those with both filters off.
 extern "C" int
-smvs_sgm_sweep_for_view_raw_photo(int device, const uint8_t *main_img, int w, int h,
+smvs_sgm_sweep_for_view_raw_refine(int device, const uint8_t *main_img, int w, int h,
     int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
     int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
     uint16_t penalty2, const smvs_sgm_sweep_options *opts,
     const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint8_t *support,
     uint16_t *cost, uint16_t *sgm, uint16_t *runner_up, int n_witness,
-    const smvs_sgm_photo_options *photo, float *confidence, uint8_t *views)
+    const smvs_sgm_photo_options *photo, float *confidence, uint8_t *views,
+    const smvs_sgm_refine_options *refine, float *slant)
 {
     smvs_sgm_sweep_options const o = opts != nullptr ? *opts : smvs_sgm_sweep_options{};
     SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h,
@@ -349,8 +351,23 @@ smvs_sgm_sweep_for_view_raw_photo(int device, const uint8_t *main_img, int w, in
         .null_options = opts != nullptr ? nullptr : SGM_NULL_SWEEP_OPTIONS,
         .depth = depth, .support = support, .argmin = argmin, .cost = cost, .sgm = sgm,
         .runner_up = runner_up, .n_witness = n_witness, .photo = photo,
-        .confidence = confidence, .views = views };
+        .confidence = confidence, .views = views, .refine = refine, .slant = slant };
     return sgm_run_view_call(C);
+}
+
+extern "C" int
+smvs_sgm_sweep_for_view_raw_photo(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, const float *range, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_sweep_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, int32_t *argmin, uint8_t *support,
+    uint16_t *cost, uint16_t *sgm, uint16_t *runner_up, int n_witness,
+    const smvs_sgm_photo_options *photo, float *confidence, uint8_t *views)
+{
+    return smvs_sgm_sweep_for_view_raw_refine(device, main_img, w, h, channels, neighbors,
+        neighbor_channels, n_neighbors, halvings, range, num_steps, penalty1, penalty2, opts,
+        filter, depth, argmin, support, cost, sgm, runner_up, n_witness, photo, confidence,
+        views, &SGM_REFINE_OFF, nullptr);
 }
 
 extern "C" int

@@ -286,7 +286,7 @@ check_sgm_view_options(const smvs_sgm_view_options *opts, int n_neighbors)
     return SMVS_OK;
 }
 
-// (declared in sgm_internal.h)  The one order of the checks, for all 16 entries.
+// (declared in sgm_internal.h)  The one order of the checks, for all 18 entries.
 // No check involves a device, and a later one may rely on an earlier one (the
 // neighbour arrays are read once the count is known to fit them).
 //   1. the entry's options pointer            2. the filter options
@@ -307,6 +307,9 @@ check_sgm_view_options(const smvs_sgm_view_options *opts, int n_neighbors)
 //  14. the photo test: the options pointer; radius, best_k, min_views, min_score;
 //      the witness count; with radius 0 no witness, confidence or views; each
 //      witness behind the front's neighbours: its image, size and channels
+//  15. the refinement sweeps: the options pointer; sweeps, samples; depth_step,
+//      slant_step; fill; sweeps > 0 with photo radius 0; a slant output with
+//      sweeps 0
 int
 check_sgm_view_call(SgmViewCall const &C)
 {
@@ -358,6 +361,12 @@ check_sgm_view_call(SgmViewCall const &C)
         SMVS_REQUIRE(C.neighbor_channels[k] == 1 || C.neighbor_channels[k] == 3,
             "1 or 3 channels (witness)");
     }
+    if ((rc = check_sgm_refine(C.refine)) != SMVS_OK)
+        return rc;
+    SMVS_REQUIRE(!sgm_refine_on(C.refine) || sgm_photo_on(C.photo),
+        "refine sweeps > 0 need the photo test's window and witnesses (photo radius > 0)");
+    SMVS_REQUIRE(C.slant == nullptr || sgm_refine_on(C.refine),
+        "slant is an output of the refinement sweeps (refine sweeps > 0)");
     return SMVS_OK;
 }
 
@@ -392,6 +401,9 @@ SgmViewSession::open()
         || (rc = ws().ensure(WS_PHOTO_OUT, npix * (sizeof(float) + 1), &d_confidence)))
         return rc;
     d_views = reinterpret_cast<uint8_t *>(d_confidence + npix);
+    if (sgm_refine_on(C.refine)
+        && (rc = ws().ensure(WS_REFINE, npix * SGM_REFINE_PLANES, &d_refine)))
+        return rc;
     for (int k = C.n_neighbors; k < n_all; ++k) {
         uint8_t *d_img = nullptr;
         int pw = 0, ph = 0;
@@ -449,8 +461,14 @@ SgmViewSession::finish(float *d_map, const float *d_checked, const uint8_t *d_su
     // (behind the merge or the support test, the photo test first: the components
     // are those of the map that leaves; checked and support are those of the
     // unfiltered map)
-    bool const photo = sgm_photo_on(C.photo);
-    if (photo
+    bool const photo = sgm_photo_on(C.photo), refine = sgm_refine_on(C.refine);
+    float *const d_slant = refine ? d_refine + 3 * npix : nullptr;
+    if (refine
+        && (rc = sgm_launch_refine(w, &prof, d_main, mw, mh, d_map, witness,
+                C.n_neighbors + C.n_witness, *C.photo, *C.refine, d_refine, d_map,
+                C.slant != nullptr ? d_slant : nullptr, d_confidence, d_views)) != SMVS_OK)
+        return rc;
+    if (photo && !refine
         && (rc = sgm_launch_photo(w, &prof, d_main, mw, mh, d_map, witness,
                 C.n_neighbors + C.n_witness, *C.photo, d_map,
                 C.confidence != nullptr ? d_confidence : nullptr,
@@ -464,7 +482,8 @@ SgmViewSession::finish(float *d_map, const float *d_checked, const uint8_t *d_su
         return host != nullptr ? w.download(host, dev, bytes) : (int)SMVS_OK;
     };
     if (photo && ((rc = get(C.confidence, d_confidence, sizeof(float) * npix))
-            || (rc = get(C.views, d_views, npix))))
+            || (rc = get(C.views, d_views, npix))
+            || (refine && (rc = get(C.slant, d_slant, 2 * sizeof(float) * npix)))))
         return rc;
     // the consensus's own outputs, then the map (every download waits for the
     // stream: nothing is left to synchronise)
@@ -606,10 +625,11 @@ using namespace smvs_hip;
 
 // ------------------------------------------------------------- the entries
 // Two entries fill a record: the one that takes smvs_sgm_options and the one
-// that takes smvs_sgm_view_options with the filters and the photo test, both on
-// raw images.  The others are one of the two with the fields they do not take
-// set to what they mean: the reference's constant penalty2 and plane winner, one
-// channel at SGM scale, both filters off, the photo test off.
+// that takes smvs_sgm_view_options with the filters, the photo test and the
+// refinement sweeps, both on raw images.  The others are one of the two with the
+// fields they do not take set to what they mean: the reference's constant
+// penalty2 and plane winner, one channel at SGM scale, both filters off, the
+// photo test off, the refinement off.
 extern "C" int
 smvs_sgm_depth_for_view_raw_opts(int device, const uint8_t *main_img, int w, int h,
     int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
@@ -624,7 +644,29 @@ smvs_sgm_depth_for_view_raw_opts(int device, const uint8_t *main_img, int w, int
         .view_opts = { o.p2_mode, o.winner, SMVS_SGM_MERGE_REFERENCE, 0, 0.0f },
         .filter = &SGM_FILTERS_OFF,
         .null_options = opts != nullptr ? nullptr : "null options (winner, p2_mode)",
-        .depth = depth, .photo = &SGM_PHOTO_OFF };
+        .depth = depth, .photo = &SGM_PHOTO_OFF, .refine = &SGM_REFINE_OFF };
+    return sgm_run_view_call(C);
+}
+
+extern "C" int
+smvs_sgm_depth_for_view_raw_refine(int device, const uint8_t *main_img, int w, int h,
+    int channels, const smvs_sgm_neighbor *neighbors, const int *neighbor_channels,
+    int n_neighbors, int halvings, int num_steps, uint16_t penalty1,
+    uint16_t penalty2, const smvs_sgm_view_options *opts,
+    const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support,
+    int n_witness, const smvs_sgm_photo_options *photo, float *confidence, uint8_t *views,
+    const smvs_sgm_refine_options *refine, float *slant)
+{
+    smvs_sgm_view_options const o = opts != nullptr ? *opts : smvs_sgm_view_options{};
+    SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h,
+        .channels = channels, .neighbors = neighbors, .neighbor_channels = neighbor_channels,
+        .n_neighbors = n_neighbors, .halvings = halvings,
+        .P = { num_steps, penalty1, penalty2, o.p2_mode, o.winner }, .view_opts = o,
+        .filter = filter,
+        .null_options = opts != nullptr ? nullptr : "null options (p2_mode, winner, merge)",
+        .depth = depth, .checked = checked, .support = support, .n_witness = n_witness,
+        .photo = photo, .confidence = confidence, .views = views, .refine = refine,
+        .slant = slant };
     return sgm_run_view_call(C);
 }
 
@@ -636,16 +678,9 @@ smvs_sgm_depth_for_view_raw_photo(int device, const uint8_t *main_img, int w, in
     const smvs_sgm_filter_options *filter, float *depth, float *checked, uint8_t *support,
     int n_witness, const smvs_sgm_photo_options *photo, float *confidence, uint8_t *views)
 {
-    smvs_sgm_view_options const o = opts != nullptr ? *opts : smvs_sgm_view_options{};
-    SgmViewCall const C = { .device = device, .main_img = main_img, .w = w, .h = h,
-        .channels = channels, .neighbors = neighbors, .neighbor_channels = neighbor_channels,
-        .n_neighbors = n_neighbors, .halvings = halvings,
-        .P = { num_steps, penalty1, penalty2, o.p2_mode, o.winner }, .view_opts = o,
-        .filter = filter,
-        .null_options = opts != nullptr ? nullptr : "null options (p2_mode, winner, merge)",
-        .depth = depth, .checked = checked, .support = support, .n_witness = n_witness,
-        .photo = photo, .confidence = confidence, .views = views };
-    return sgm_run_view_call(C);
+    return smvs_sgm_depth_for_view_raw_refine(device, main_img, w, h, channels, neighbors,
+        neighbor_channels, n_neighbors, halvings, num_steps, penalty1, penalty2, opts, filter,
+        depth, checked, support, n_witness, photo, confidence, views, &SGM_REFINE_OFF, nullptr);
 }
 
 extern "C" int

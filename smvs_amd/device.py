@@ -539,6 +539,65 @@ def sgm_photo_check(main_img, depth, witnesses, radius=2, best_k=2, min_views=2,
     return out, conf, views
 
 
+class SgmRefineOptions(C.Structure):
+    """smvs_sgm_refine_options of include/smvs_hip.h."""
+    _fields_ = [("sweeps", C.c_int), ("samples", C.c_int), ("depth_step", C.c_float),
+                ("slant_step", C.c_float), ("seed", C.c_uint32), ("fill", C.c_int)]
+
+
+# (refine_sweeps, refine_samples, refine_depth_step, refine_slant_step,
+# refine_seed, refine_fill) of the Python fronts: the plane refinement sweeps off.
+# Defaults of a user option, untuned; nobody has measured them on real scenes.
+SGM_REFINE_DEFAULTS = (0, 2, 0.02, 0.01, 1, 1)
+
+
+def _sgm_refine(sweeps, samples, depth_step, slant_step, seed, fill):
+    """The refine options, or None where they are the defaults (the entries
+    without the sweeps are called then)."""
+    if (sweeps, samples, depth_step, slant_step, seed, fill) == SGM_REFINE_DEFAULTS:
+        return None
+    return SgmRefineOptions(int(sweeps), int(samples), float(depth_step), float(slant_step),
+                            int(seed) & 0xFFFFFFFF, int(fill))
+
+
+def sgm_plane_refine(main_img, depth, witnesses, radius=2, best_k=2, min_views=2, min_score=0.49,
+                     sweeps=0, samples=2, depth_step=0.02, slant_step=0.01, seed=1, fill=1,
+                     device=0):
+    """smvs_sgm_plane_refine: the multi-view plane refinement sweeps of
+    include/smvs_hip.h alone (not in the reference), on a map of the caller.
+    main_img, depth, witnesses, radius, best_k, min_views, min_score: as for
+    sgm_photo_check, whose confidence is the objective.  Every pixel holds a plane
+    (depth, two slants); in each of `sweeps` red-black sweeps (0 .. 8) a pixel
+    adopts a 4-neighbour's extrapolated plane, or one of `samples` (0 .. 8) hashed
+    perturbations of its own (relative steps depth_step and slant_step, halved per
+    sweep; seed), whenever that raises its confidence; fill = 1 lets pixels
+    without a depth adopt a neighbour's plane.  sweeps = 0 gives sgm_photo_check's
+    outputs and zero slants.  Returns (out (h, w) f32, slant (h, w, 2) f32,
+    confidence (h, w) f32, views (h, w) u8).  The defaults are defaults of a user
+    option, untuned."""
+    lib = _capi.load()
+    main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
+    depth = _f32(depth)
+    if main_img.ndim != 2 or depth.shape != main_img.shape:
+        raise ValueError("main_img and depth: (h, w)")
+    h, w = depth.shape
+    keep = []
+    arr = _sgm_neighbors(_sgm_witnesses([], witnesses), keep) if len(witnesses) else None
+    if any(k.ndim != 2 for k in keep):
+        raise ValueError("witness images: (nh, nw), one channel at SGM scale")
+    photo = SgmPhotoOptions(int(radius), int(best_k), int(min_views), float(min_score))
+    refine = SgmRefineOptions(int(sweeps), int(samples), float(depth_step), float(slant_step),
+                              int(seed) & 0xFFFFFFFF, int(fill))
+    out = np.zeros((h, w), dtype=np.float32)
+    slant = np.zeros((h, w, 2), dtype=np.float32)
+    conf = np.zeros((h, w), dtype=np.float32)
+    views = np.zeros((h, w), dtype=np.uint8)
+    check(lib.smvs_sgm_plane_refine(device, _p(main_img, _u8p), w, h, _p(depth, _fp), arr,
+          len(witnesses), C.byref(photo), C.byref(refine), _p(out, _fp), _p(slant, _fp),
+          _p(conf, _fp), _p(views, _u8p)))
+    return out, slant, conf, views
+
+
 def sgm_filter_speckles(depth, speckle_size, speckle_ratio=0.95, device=0):
     """smvs_sgm_filter_speckles: the speckle kernels of include/smvs_hip.h alone
     (not in the reference).  depth (h, w) float; pixels > 0 are valid, two valid
@@ -659,7 +718,9 @@ def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0
                        consensus=False, agree_ratio=0.95, min_agree=2, want_checked=False,
                        uniqueness=0, uniqueness_window=1, speckle_size=0, speckle_ratio=0.95,
                        photo_radius=0, photo_best_k=2, photo_min_views=2, photo_min_score=0.49,
-                       witnesses=None):
+                       witnesses=None,
+                       refine_sweeps=0, refine_samples=2, refine_depth_step=0.02,
+                       refine_slant_step=0.01, refine_seed=1, refine_fill=1):
     """reconstruct_sgm_depth_for_view on the device.  neighbors: list of dicts
     {image, M_fwd, t_fwd, M_bwd, t_bwd, range_main, range_neighbor} (SGM-scale
     u8 images, float reprojections).  adaptive_p2, subplane: as for sgm_run
@@ -689,11 +750,22 @@ def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0
     neighbours'; at most 16 in all).  Returns a dict {depth, confidence, views}
     (and checked, support with want_checked).  Off by default; witnesses or a
     changed option with photo_radius = 0 is an error.  (0, 2, 2, 0.49) are
-    defaults of a user option, untuned."""
+    defaults of a user option, untuned.
+    refine_sweeps (1 .. 8; 0 is off), refine_samples, refine_depth_step,
+    refine_slant_step, refine_seed, refine_fill: the plane refinement sweeps of
+    sgm_plane_refine in the photo test's place (they need photo_radius > 0); the
+    dict then also holds slant (h, w, 2).  Off by default; a changed option with
+    refine_sweeps = 0 goes to the entry with the sweeps, which gives the photo
+    test's bytes.  (0, 2, 0.02, 0.01, 1, 1) are defaults of a user option,
+    untuned."""
     lib = _capi.load()
     main_img = np.ascontiguousarray(main_img, dtype=np.uint8)
     filt = _sgm_filter(uniqueness, uniqueness_window, speckle_size, speckle_ratio)
     photo = _sgm_photo(photo_radius, photo_best_k, photo_min_views, photo_min_score, witnesses)
+    refine = _sgm_refine(refine_sweeps, refine_samples, refine_depth_step, refine_slant_step,
+                         refine_seed, refine_fill)
+    if refine is not None and photo is None:
+        photo = SgmPhotoOptions(*SGM_PHOTO_DEFAULTS)
     if photo is not None:
         if want_checked and not consensus:
             raise ValueError("want_checked: the checked maps and the support are "
@@ -702,7 +774,8 @@ def sgm_depth_for_view(main_img, neighbors, num_steps=128, p1=6, p2=96, device=0
             lib, main_img, neighbors, witnesses, num_steps, p1, p2, device,
             _sgm_view_options(adaptive_p2, subplane, consensus, agree_ratio, min_agree),
             halvings, want_checked,
-            filt if filt is not None else SgmFilterOptions(*SGM_FILTER_DEFAULTS), photo)
+            filt if filt is not None else SgmFilterOptions(*SGM_FILTER_DEFAULTS), photo,
+            refine)
     if consensus or want_checked or filt is not None:
         if want_checked and not consensus:
             raise ValueError("want_checked: the checked maps and the support are "
@@ -805,8 +878,9 @@ def _raw_images(main_img, keep, halvings):
 
 
 def _sgm_depth_for_view_photo(lib, main_img, neighbors, witnesses, num_steps, p1, p2, device,
-                              vopts, halvings, want_checked, filt, photo):
-    """smvs_sgm_depth_for_view_raw_photo."""
+                              vopts, halvings, want_checked, filt, photo, refine=None):
+    """smvs_sgm_depth_for_view_raw_photo; with refine (SgmRefineOptions)
+    smvs_sgm_depth_for_view_raw_refine."""
     keep = []
     every = _sgm_witnesses(neighbors, witnesses)
     arr = _sgm_neighbors(every, keep) if every else None
@@ -820,12 +894,17 @@ def _sgm_depth_for_view_photo(lib, main_img, neighbors, witnesses, num_steps, p1
     on = photo.radius != 0
     conf = np.zeros((oh, ow), dtype=np.float32) if on else None
     views = np.zeros((oh, ow), dtype=np.uint8) if on else None
-    check(lib.smvs_sgm_depth_for_view_raw_photo(
-        device, _p(main_img, _u8p), w, h, channels, arr, nch, n, halvings, num_steps,
-        C.c_uint16(p1), C.c_uint16(p2), C.byref(vopts), C.byref(filt), _p(depth, _fp),
-        _p(checked, _fp), _p(support, _u8p), len(every) - n, C.byref(photo), _p(conf, _fp),
-        _p(views, _u8p)))
+    args = (device, _p(main_img, _u8p), w, h, channels, arr, nch, n, halvings, num_steps,
+            C.c_uint16(p1), C.c_uint16(p2), C.byref(vopts), C.byref(filt), _p(depth, _fp),
+            _p(checked, _fp), _p(support, _u8p), len(every) - n, C.byref(photo), _p(conf, _fp),
+            _p(views, _u8p))
     out = dict(depth=depth, confidence=conf, views=views)
+    if refine is not None:
+        slant = np.zeros((oh, ow, 2), dtype=np.float32) if refine.sweeps != 0 else None
+        check(lib.smvs_sgm_depth_for_view_raw_refine(*args, C.byref(refine), _p(slant, _fp)))
+        out["slant"] = slant
+    else:
+        check(lib.smvs_sgm_depth_for_view_raw_photo(*args))
     if want_checked:
         out.update(checked=checked, support=support)
     return out
@@ -879,7 +958,9 @@ def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2
                        best_k=None, support_cost=20, min_support=None, want_volumes=False,
                        uniqueness=0, uniqueness_window=1, speckle_size=0, speckle_ratio=0.95,
                        photo_radius=0, photo_best_k=2, photo_min_views=2, photo_min_score=0.49,
-                       witnesses=None):
+                       witnesses=None,
+                       refine_sweeps=0, refine_samples=2, refine_depth_step=0.02,
+                       refine_slant_step=0.01, refine_seed=1, refine_fill=1):
     """The multi-neighbour plane sweep of include/smvs_hip.h (not in the
     reference; opt-in): one cost volume of the main view from all n = 1 .. 16
     neighbours -- per cell the rounded mean of the best_k smallest of the
@@ -900,12 +981,20 @@ def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2
     photo-consistency test of sgm_depth_for_view behind the support test (the
     sweep's neighbours followed by `witnesses`); the dict then also holds
     confidence and views.  Off by default, defaults untuned.
+    refine_sweeps, refine_samples, refine_depth_step, refine_slant_step,
+    refine_seed, refine_fill: the plane refinement sweeps of sgm_depth_for_view in
+    the photo test's place; the dict then also holds slant.  Off by default,
+    defaults untuned.
     Returns dict(depth, argmin, support[, cost, sgm][, runner_up: with
     want_volumes and uniqueness > 0]); with halvings dict(depth, support)."""
     lib = _capi.load()
     n = len(neighbors)
     filt = _sgm_filter(uniqueness, uniqueness_window, speckle_size, speckle_ratio)
     photo = _sgm_photo(photo_radius, photo_best_k, photo_min_views, photo_min_score, witnesses)
+    refine = _sgm_refine(refine_sweeps, refine_samples, refine_depth_step, refine_slant_step,
+                         refine_seed, refine_fill)
+    if refine is not None and photo is None:
+        photo = SgmPhotoOptions(*SGM_PHOTO_DEFAULTS)
     d_views, d_k, _, d_support = sgm_sweep_defaults(n)
     opts = SgmSweepOptions(P2_ADAPTIVE if adaptive_p2 else P2_CONSTANT,
                            WINNER_SUBPLANE if subplane else WINNER_PLANE,
@@ -939,12 +1028,19 @@ def sgm_sweep_for_view(main_img, neighbors, depth_range, num_steps=128, p1=6, p2
         on = photo.radius != 0
         conf = np.zeros((oh, ow), dtype=np.float32) if on else None
         views = np.zeros((oh, ow), dtype=np.uint8) if on else None
-        check(lib.smvs_sgm_sweep_for_view_raw_photo(
-            device, _p(main_img, _u8p), w, h, channels, arr, nch, n, hv, rng, num_steps,
-            C.c_uint16(p1), C.c_uint16(p2), C.byref(opts), C.byref(filt), _p(depth, _fp),
-            _p(argmin, _i32p), _p(support, _u8p), _p(cost, _u16p), _p(sgm, _u16p),
-            _p(runner, _u16p), len(full) - n, C.byref(photo), _p(conf, _fp), _p(views, _u8p)))
+        args = (device, _p(main_img, _u8p), w, h, channels, arr, nch, n, hv, rng, num_steps,
+                C.c_uint16(p1), C.c_uint16(p2), C.byref(opts), C.byref(filt), _p(depth, _fp),
+                _p(argmin, _i32p), _p(support, _u8p), _p(cost, _u16p), _p(sgm, _u16p),
+                _p(runner, _u16p), len(full) - n, C.byref(photo), _p(conf, _fp),
+                _p(views, _u8p))
         out = dict(depth=depth, support=support, confidence=conf, views=views)
+        if refine is not None:
+            slant = np.zeros((oh, ow, 2), dtype=np.float32) if refine.sweeps != 0 else None
+            check(lib.smvs_sgm_sweep_for_view_raw_refine(*args, C.byref(refine),
+                                                         _p(slant, _fp)))
+            out["slant"] = slant
+        else:
+            check(lib.smvs_sgm_sweep_for_view_raw_photo(*args))
         if halvings is None:
             out["argmin"] = argmin
         if runner is not None:

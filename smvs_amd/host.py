@@ -251,6 +251,16 @@ class SgmPhoto(C.Structure):
                 ("min_score", C.c_float), ("witnesses", C.c_int)]
 
 
+class SgmRefine(C.Structure):
+    """smvs_host_sgm_refine of csrc/host/host_capi.h: ReconSettings::
+    sgm_refine_sweeps / sgm_refine_samples / sgm_refine_depth_step /
+    sgm_refine_slant_step / sgm_refine_seed / sgm_refine_fill (SGMStereo::Options::
+    refine_sweeps / ...), passed next to the settings struct, which keeps its
+    layout."""
+    _fields_ = [("sweeps", C.c_int), ("samples", C.c_int), ("depth_step", C.c_float),
+                ("slant_step", C.c_float), ("seed", C.c_uint32), ("fill", C.c_int)]
+
+
 def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       regularization=1.0, output_scale=2, use_shading=False, use_sgm=True,
                       force_recon=False, force_sgm=False, sgm_range=(0.0, 0.0), sgm_scale=1,
@@ -264,7 +274,9 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       sgm_sweep_min_support=-1, sgm_uniqueness=0, sgm_uniqueness_window=1,
                       sgm_speckle_size=0, sgm_speckle_ratio=0.95, sgm_photo_radius=0,
                       sgm_photo_best_k=2, sgm_photo_min_views=2, sgm_photo_min_score=0.49,
-                      sgm_photo_witnesses=-1):
+                      sgm_photo_witnesses=-1, sgm_refine_sweeps=0, sgm_refine_samples=2,
+                      sgm_refine_depth_step=0.02, sgm_refine_slant_step=0.01,
+                      sgm_refine_seed=1, sgm_refine_fill=1):
     """smvsrecon's scene-level run (app/smvsrecon.cc:400-745) through
     smvs_amd::reconstruct_scene: returns (reconstructed ids, skipped, seconds)
     [, input scale used if `details`].  input_scale < 0 (the default, as
@@ -325,12 +337,26 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     fewer than min_views, no depth below min_score.  The confidence is saved as
     smvs-sgm-confidence next to smvs-sgm.  Off by default; (0, 2, 2, 0.49, -1) are
     defaults of a user option, untuned, and nobody has measured them on real
-    scenes.  The reuse rule is that of sgm_subplane (force_sgm)."""
+    scenes.  The reuse rule is that of sgm_subplane (force_sgm).
+    sgm_refine_sweeps, sgm_refine_samples, sgm_refine_depth_step,
+    sgm_refine_slant_step, sgm_refine_seed, sgm_refine_fill: ReconSettings::
+    sgm_refine_sweeps / ... -- the multi-view plane refinement sweeps of
+    include/smvs_hip.h in the photo test's place (they need sgm_photo_radius > 0):
+    1 .. 8 red-black sweeps (0 is off) in which a pixel adopts a neighbour's plane
+    or one of `samples` perturbations of its own whenever that raises its
+    confidence.  The slants are saved as smvs-sgm-slant (two channels) next to
+    smvs-sgm-confidence; the optimizer does not read them.  Off by default;
+    (0, 2, 0.02, 0.01, 1, 1) are defaults of a user option, untuned, and nobody
+    has measured them on real scenes.  The reuse rule is that of sgm_subplane
+    (force_sgm)."""
     lib = load()
     filt = SgmFilter(int(sgm_uniqueness), int(sgm_uniqueness_window), int(sgm_speckle_size),
                      float(sgm_speckle_ratio))
     photo = SgmPhoto(int(sgm_photo_radius), int(sgm_photo_best_k), int(sgm_photo_min_views),
                      float(sgm_photo_min_score), int(sgm_photo_witnesses))
+    refine = SgmRefine(int(sgm_refine_sweeps), int(sgm_refine_samples),
+                       float(sgm_refine_depth_step), float(sgm_refine_slant_step),
+                       int(sgm_refine_seed) & 0xFFFFFFFF, int(sgm_refine_fill))
     sweep = SgmSweep(1 if sgm_sweep else 0, sgm_sweep_min_views, sgm_sweep_best_k,
                      sgm_sweep_support_cost, sgm_sweep_min_support)
     st = ReconSettings(image_embedding.encode(), regularization, output_scale,
@@ -345,13 +371,14 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                              C.byref(cap), None, None, None, None, None, None, None)
     out = np.zeros(max(cap.value, 1), np.int32)
     n = C.c_int(0); sk = C.c_int(0); secs = C.c_double(0.0); used = C.c_int(0)
-    rc = lib.smvs_host_reconstruct_scene_photo(scene_dir.encode(), C.byref(st),
+    rc = lib.smvs_host_reconstruct_scene_refine(scene_dir.encode(), C.byref(st),
         C.c_uint((1 if sgm_adaptive_penalty2 else 0) | (2 if device_input_scaling else 0)
                  | (8 if device_shading_prep else 0) | (16 if gamma_correction else 0)),
         C.c_int(sgm_num_steps), C.c_int(1 if sgm_subplane else 0),
         C.c_int(sgm_neighbors), C.c_int(1 if sgm_consensus else 0),
         C.c_float(sgm_agree_ratio), C.c_int(sgm_min_agree), C.byref(sweep), C.byref(filt),
-        C.byref(photo), ids.ctypes.data_as(_i32p) if ids is not None else None,
+        C.byref(photo), C.byref(refine),
+        ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), out.ctypes.data_as(_i32p),
         C.c_int(out.size), C.byref(n), C.byref(sk), C.byref(secs), C.byref(used))
     if rc != 0:
@@ -499,7 +526,8 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
               sweep_min_views=-1, sweep_best_k=-1, sweep_support_cost=20,
               sweep_min_support=-1, uniqueness=0, uniqueness_window=1, speckle_size=0,
               speckle_ratio=0.95, photo_radius=0, photo_best_k=2, photo_min_views=2,
-              photo_min_score=0.49, photo_witnesses=-1):
+              photo_min_score=0.49, photo_witnesses=-1, refine_sweeps=0, refine_samples=2,
+              refine_depth_step=0.02, refine_slant_step=0.01, refine_seed=1, refine_fill=1):
     """reconstruct_sgm_depth_for_view through the host mirror.
     adaptive_penalty2: SGMStereo::Options::adaptive_penalty2 (the reference's
     build without SSE, lib/sgm_stereo.cc:310-346); off by default.
@@ -535,9 +563,19 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
     inputs as witnesses (-1: all of them, 16 at the most).  With photo_radius
     > 0 returns (depth, confidence), the confidence being what the mirror writes
     as the smvs-sgm-confidence embedding.  Off by default; (0, 2, 2, 0.49, -1)
-    are untuned defaults of a user option."""
+    are untuned defaults of a user option.
+    refine_sweeps, refine_samples, refine_depth_step, refine_slant_step,
+    refine_seed, refine_fill: SGMStereo::Options::refine_sweeps / ... -- the
+    multi-view plane refinement sweeps of include/smvs_hip.h in the photo test's
+    place (they need photo_radius > 0).  With refine_sweeps > 0 returns (depth,
+    confidence, slant), the slant (h, w, 2) being what the mirror writes as the
+    smvs-sgm-slant embedding.  Off by default; (0, 2, 0.02, 0.01, 1, 1) are
+    untuned defaults of a user option."""
     lib = load()
     keep = []
+    refine = SgmRefine(int(refine_sweeps), int(refine_samples), float(refine_depth_step),
+                       float(refine_slant_step), int(refine_seed) & 0xFFFFFFFF,
+                       int(refine_fill))
     photo = SgmPhoto(int(photo_radius), int(photo_best_k), int(photo_min_views),
                      float(photo_min_score), int(photo_witnesses))
     filt = SgmFilter(int(uniqueness), int(uniqueness_window), int(speckle_size),
@@ -550,17 +588,21 @@ def sgm_depth(inputs, sgm_scale=1, min_depth=0.0, max_depth=0.0, device=0,
         w, h = (w + 1) // 2, (h + 1) // 2
     out = np.zeros((h, w), dtype=np.float32)
     conf = np.zeros((h, w), dtype=np.float32) if photo.radius != 0 else None
+    slant = np.zeros((h, w, 2), dtype=np.float32) if refine.sweeps != 0 else None
     ow = C.c_int(0); oh = C.c_int(0)
-    rc = lib.smvs_host_sgm_depth_photo(C.byref(main), subs, n_subs, C.byref(b),
+    rc = lib.smvs_host_sgm_depth_refine(C.byref(main), subs, n_subs, C.byref(b),
         sgm_scale, C.c_float(min_depth), C.c_float(max_depth), device,
         C.c_int(1 if adaptive_penalty2 else 0), C.c_int(num_steps),
         C.c_int(1 if subplane else 0), C.c_int(neighbors), C.c_int(1 if consensus else 0),
         C.c_float(agree_ratio), C.c_int(min_agree), C.byref(sw), C.byref(filt),
-        C.byref(photo), out.ctypes.data_as(_fp),
-        conf.ctypes.data_as(_fp) if conf is not None else None, C.byref(ow), C.byref(oh))
+        C.byref(photo), C.byref(refine), out.ctypes.data_as(_fp),
+        conf.ctypes.data_as(_fp) if conf is not None else None,
+        slant.ctypes.data_as(_fp) if slant is not None else None, C.byref(ow), C.byref(oh))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
     assert (ow.value, oh.value) == (w, h)
+    if slant is not None:
+        return out, conf, slant
     return out if conf is None else (out, conf)
 
 

@@ -32,7 +32,14 @@ include/smvs_hip.h on the view's final map (window radius R in 1 .. 3; K 2, V 2,
 S 0.49 without the flags) with N ring views as witnesses, the front end's
 neighbours first (N = --neighbors without the flag); its one launch counted as
 merge, and the same launch alone on the map in front of it (smvs_sgm_photo_check)
-with the bytes it moves, so that its time stands by itself."""
+with the bytes it moves, so that its time stands by itself.
+--refine SWEEPS [--refine-samples S] (with --photo): the multi-view plane
+refinement sweeps of include/smvs_hip.h in the photo test's place (SWEEPS in
+1 .. 8; S 2 without the flag; the other options at their defaults), their
+1 + 2 SWEEPS + 1 launches counted as merge; in the same session the view with
+the photo test alone, and the sweeps alone on the map in front of them
+(smvs_sgm_plane_refine) at SWEEPS and at 0 sweeps (the start and the end), so
+that the time of one half-sweep launch stands next to the photo kernel's."""
 import ctypes as C
 import json
 import os, sys, time
@@ -75,6 +82,9 @@ if uniqueness:
     print("uniqueness test: %d %%, window %d" % (uniqueness, kw["uniqueness_window"]))
 
 photo = _arg("--photo", 0)
+refine = _arg("--refine", 0)
+if refine and not photo:
+    sys.exit("--refine needs --photo (the sweeps use its window and witnesses)")
 
 if "--neighbors" in sys.argv:
     n = _arg("--neighbors", 2)
@@ -108,6 +118,11 @@ if "--neighbors" in sys.argv:
               "witnesses (its launch counts as merge)"
               % (photo, photo_kw["photo_best_k"], photo_kw["photo_min_views"],
                  photo_kw["photo_min_score"], n_all))
+    if refine:
+        refine_kw = dict(refine_sweeps=refine, refine_samples=_arg("--refine-samples", 2))
+        kw.update(refine_kw)
+        print("plane refinement: %d sweeps, %d samples, defaults otherwise (its launches count "
+              "as merge)" % (refine, refine_kw["refine_samples"]))
     print("front end of a view, %d neighbours, %s" % (
         n, "plane sweep (min_views %d, best_k %d, support_cost %d, min_support %d)"
         % smvs_amd.device.sgm_sweep_defaults(n) if sweep
@@ -129,6 +144,17 @@ if "--neighbors" in sys.argv:
         print("front end %dx%dx%d x %d neighbours: %.2f ms per view (incl. H2D/D2H), valid %.3f"
               % (hw, hh, D, n, 1e3 * times[-1], (out > 0).mean()))
     print("front end: best %.2f ms per view" % (1e3 * min(times)))
+    if refine:
+        # the same view with the photo test alone, in this session
+        with_sweeps, kw = kw, {k: v for k, v in kw.items() if not k.startswith("refine")}
+        view()
+        times = []
+        for i in range(repeat):
+            t0 = time.perf_counter()
+            view()
+            times.append(time.perf_counter() - t0)
+        print("front end with the photo test alone: best %.2f ms per view" % (1e3 * min(times)))
+        kw = with_sweeps
     # (the events of the per-kernel timer serialise the launches: a call of its own)
     lib.smvs_sgm_profile(1, None, None)
     for i in range(repeat):
@@ -145,7 +171,7 @@ if "--neighbors" in sys.argv:
     if photo:
         # the same launch alone, on the map as it is in front of the test
         plain = {k: v for k, v in kw.items()
-                 if not k.startswith(("photo", "speckle")) and k != "witnesses"}
+                 if not k.startswith(("photo", "speckle", "refine")) and k != "witnesses"}
         if sweep:
             before = smvs_amd.sgm_sweep_for_view(small[0], nbs, (2.0, 10.0), D, 6, p2,
                                                  **plain)["depth"]
@@ -170,6 +196,30 @@ if "--neighbors" in sys.argv:
               % (pcnt[6] // repeat, us, nbytes / 1e6, nbytes / us / 1e6, samples / 1e6,
                  int(((before > 0) & (after == 0)).sum()), int((before > 0).sum()),
                  int(views.max())))
+    if refine:
+        # the sweeps alone on the same map: all launches, and the start and the
+        # end alone (0 sweeps); the difference is the 2 x sweeps half-sweeps
+        def alone_us(sweeps):
+            args = dict(sweeps=sweeps, samples=refine_kw["refine_samples"])
+            smvs_amd.sgm_plane_refine(small[0], before, nbs + further, *alone, **args)
+            lib.smvs_sgm_profile(1, None, None)
+            for i in range(repeat):
+                got = smvs_amd.sgm_plane_refine(small[0], before, nbs + further, *alone, **args)
+            rms = (C.c_double * 8)()
+            rcnt = (C.c_longlong * 8)()
+            lib.smvs_sgm_profile(0, rms, rcnt)
+            return 1e3 * rms[6] / repeat, rcnt[6] // repeat, got
+        ends_us, ends_n, _ = alone_us(0)
+        all_us, all_n, (rout, rslant, rconf, rviews) = alone_us(refine)
+        valid = before > 0
+        print("refinement alone (%d launches): %.1f us per map; start + end (%d launches): %.1f "
+              "us; a half-sweep launch: %.1f us (the photo kernel: %.1f us); %d of %d valid "
+              "pixels changed depth, %d of %d holes filled, %d pixels without a depth after "
+              "(photo test alone: %d)"
+              % (all_n, all_us, ends_n, ends_us, (all_us - ends_us) / (2 * refine), us,
+                 int((valid & (rout != before) & (rout != 0)).sum()), int(valid.sum()),
+                 int((~valid & (rout > 0)).sum()), int((~valid).sum()),
+                 int((rout == 0).sum()), int((after == 0).sum())))
     if speckle and not photo:
         # the same launches alone, on the map as it is in front of the filter
         plain = {k: v for k, v in kw.items() if not k.startswith("speckle")}
@@ -190,8 +240,9 @@ if "--neighbors" in sys.argv:
                                                  int(((before > 0) & (after == 0)).sum()),
                                                  int((before > 0).sum()), int(size.max())))
     if photo:
-        print("merge class: %d launches per view, the photo test%s among them: %.1f us per view"
-              % (cnt[6] // repeat, " and the speckle launches" if speckle else "",
+        print("merge class: %d launches per view, the %s%s among them: %.1f us per view"
+              % (cnt[6] // repeat, "refinement's" if refine else "photo test",
+                 " and the speckle launches" if speckle else "",
                  1e3 * ms[6] / repeat))
     elif speckle:
         print("merge class: %d launches per view, the speckle launches among them: %.1f us per "
