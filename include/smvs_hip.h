@@ -1100,6 +1100,66 @@ int smvs_surface_info(smvs_ctx *ctx, smvs_surface_geometry *geometry,
 int smvs_surface_download(smvs_ctx *ctx, double *nodes, uint8_t *node_valid,
     uint8_t *patch_valid, uint32_t *patch_vis);
 
+/* Node slopes from the SGM plane hypotheses.  Not in the reference; opt-in, and
+ * without the three entries below every entry gives the bytes and the launches
+ * it gave before.  initialize_node_from_depth (surface.cc:667-760) sets a
+ * node's dx, dy, dxy from differences of the quadrant minima of its window: on
+ * a plane of slope b per pixel two quadrants ps/2 apart differ by b ps/2, while
+ * the bicubic patch (bicubic_patch.cc:20-86, Hermite on the unit square) needs
+ * dx = b ps -- half the slope, a dxy made of noise, a one-sided difference next
+ * to a hole.  The slants of the `_refine` entries above are the missing datum.
+ * The definition is normative (tests/surface_planes_ref.py restates it).
+ *
+ * Slant plane of a context.  Inputs: L, the resident SGM-scale z-depth map
+ * (dm_w x dm_h, what smvs_ctx_sgm_init_depth[_mve] left behind its upload
+ * kernel's conversion), and G = slant[dm_h][dm_w][2], z-depth per SGM pixel, gx
+ * then gy, as `_refine` writes it.  With the bilateral's factors
+ *     scale_x = (float)dm_w / (float)W;  scale_y = (float)dm_h / (float)H;
+ * the full-resolution pixel (x, y) reads the bilateral's centre tap
+ * (depth_optimizer.cc:981-984)
+ *     sx = (int)clamp(scale_x * (float)x, 0.f, (float)dm_w - 1.f);  sy likewise.
+ * If L(sx, sy) > 0.0f and both components of G(sx, sy) are finite,
+ *     P(x, y) = (G(sx, sy, 0) * scale_x, G(sx, sy, 1) * scale_y),
+ * one rounded float product each, contraction off; otherwise both components are
+ * the quiet NaN 0x7FC00000: "no slant".  P is W x H x 2 f32, z-depth per
+ * full-resolution pixel.
+ *
+ * Node from its window, with slants.  The window is the reference's: four
+ * quadrants of (ps/2)^2 pixels.  Its statistics -- the count of positive
+ * depths, the quadrant minima, the median -- are unchanged, and they alone
+ * decide whether the node exists and what f is.  In addition S is the set of
+ * window pixels inside the image with D > 0 and both components of P finite,
+ * cs = |S|.  With cs == 0 the node's dx, dy, dxy are the reference's.  With
+ * cs >= 1, mx is the element of 0-based rank cs / 2 of { P(p, 0) : p in S } in
+ * ascending key order (the rule f follows), my the same for component 1, taken
+ * independently, where
+ *     key(v) = bits ^ 0x80000000 if the sign bit is clear, else ~bits
+ * (so -0.0 < +0.0: the choice is a fact of the multiset, not of the traversal),
+ * and
+ *     dx = (double)mx * (double)ps;  dy = (double)my * (double)ps;  dxy = 0.0.
+ *
+ * Consequences: node_valid, patch_valid and every f are the bytes of the
+ * slant-free run; an all-NaN plane gives the slant-free nodes to the byte. */
+
+/* The slant plane P of the context from slant[dm_h][dm_w][2]; call it after
+ * smvs_ctx_sgm_init_depth[_mve].  SMVS_ERR_STATE without a resident map,
+ * SMVS_ERR_INVALID when dm_w x dm_h is not that map's size.  P stays in the
+ * context; out[W*H*2] (may be NULL) receives it.  slant == NULL forgets P, and
+ * so does every call of smvs_ctx_sgm_init_depth[_mve] (a new map invalidates
+ * it).  P is not part of smvs_ctx_clone_loop_state. */
+int smvs_ctx_sgm_init_slants(smvs_ctx *ctx, const float *slant, int dm_w, int dm_h,
+    float *out);
+/* smvs_surface_create with the rule above.  depth[W*H] and slant[W*H*2] (a
+ * plane P) are either both the caller's or both NULL; both NULL: the resident
+ * ones (SMVS_ERR_STATE if either is missing).  The surface keeps the plane as
+ * it keeps Surface::depth: the smvs_surface_fill_patches_from_depth calls that
+ * follow every subdivision use the same rule for the null nodes, until
+ * smvs_surface_create ends that.  Enqueue-only when no count is asked for. */
+int smvs_surface_create_planes(smvs_ctx *ctx, int scale, const float *depth,
+    const float *slant, int *num_valid_patches);
+/* The plane the surface holds, out[W*H*2] (SMVS_ERR_STATE without one). */
+int smvs_surface_slants(smvs_ctx *ctx, float *out);
+
 /* ------------------------------------------------------------------ */
 /* consumer of the depth / normal maps                */
 /* ------------------------------------------------------------------ */

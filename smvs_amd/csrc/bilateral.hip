@@ -452,6 +452,7 @@ sgm_init_depth(smvs_ctx *ctx, const float *dm, int dm_w, int dm_h, const float *
     SMVS_REQUIRE(ctx != nullptr, "null argument");
     if (dm == nullptr) {   // forget the resident map
         ctx->sgm_resident = false;
+        ctx->sgm_slant_ok = false;
         return SMVS_OK;
     }
     SMVS_REQUIRE(dm_w > 0 && dm_h > 0 && kernel_size >= 0 && sigma > 0.f,
@@ -482,6 +483,9 @@ sgm_init_depth(smvs_ctx *ctx, const float *dm, int dm_w, int dm_h, const float *
         ctx->topo_sgm_cap = n;
     }
     ctx->sgm_resident = false;
+    ctx->sgm_slant_ok = false;   // (a new map invalidates the slant plane)
+    ctx->sgm_lowres_w = dm_w;
+    ctx->sgm_lowres_h = dm_h;
     {
         // The map goes to the device through a kernel that reads page-locked
         // memory over the bus, not as a DMA: at this moment the nine images of the

@@ -257,6 +257,12 @@ struct smvs_ctx {
     bool sgm_resident = false;   // topo_sgm holds smvs_ctx_sgm_init_depth's result
     float *sgm_lowres = nullptr; // its input, SGM resolution
     size_t sgm_lowres_cap = 0;
+    int sgm_lowres_w = 0, sgm_lowres_h = 0;   // ... and its size
+    // the slant plane P of smvs_ctx_sgm_init_slants, [H][W][2] (surface_planes.hip);
+    // valid with the resident map only
+    float *sgm_slant = nullptr;
+    size_t sgm_slant_cap = 0;
+    bool sgm_slant_ok = false;
     float *bil_lut = nullptr;    // compressed colour-weight table of the bilateral filter (bilateral.hip)
     float *bil_tri = nullptr;    // ... and the triangle of all byte pairs (round 6)
     int topo_slot = 0;           // cut_boundaries: the word pair of the next pass (topo_cut.hip)
@@ -281,6 +287,9 @@ struct smvs_ctx {
     float *surf_depth = nullptr;       // [H][W] Surface::depth (surface.cc:46-50): the
     size_t surf_depth_cap = 0;         // initial depth the nodes are (re)filled from
     bool surf_depth_ok = false;
+    float *surf_slant = nullptr;       // [H][W][2] the slant plane the surface keeps next to
+    size_t surf_slant_cap = 0;         // it (smvs_surface_create_planes)
+    bool surf_slant_ok = false;
     double *surf_tmp = nullptr;        // scratch: the nodes before a subdivision,
     size_t surf_tmp_cap = 0;           // the proposals of expand (doubles)
     uint8_t *surf_tmp_bytes = nullptr; // scratch: validity before a subdivision, proposed flags
@@ -317,6 +326,10 @@ int pinned_pool_release(void);   // pool.hip -> buffers returned to the driver
 // Contents of the node / patch arrays are unspecified afterwards when the grid
 // grew.  Leaves has_surface untouched.
 int ctx_ensure_grid(smvs_ctx *ctx, int scale, int npx, int npy, int start_x, int start_y);
+// initialize_node_from_depth with the surface's slant plane for every null node
+// of the context's grid (surface_planes.hip; surface.hip's fill calls it while
+// ctx->surf_slant_ok): enqueues one launch, nothing for patch size 1.
+void launch_init_nodes_planes(smvs_ctx *ctx);
 // Images handed over by smvs_ctx_upload_image_async that have not been
 // converted yet: the wait for their DMA and the conversion are enqueued on the
 // context's stream (views: bit v = view v - 1 as in image_ok; every consumer of

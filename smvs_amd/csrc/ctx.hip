@@ -224,7 +224,9 @@ ctx_reset_for_reuse(smvs_ctx *ctx)
     ctx->upload_stage_busy = 0;   // (the caller has synchronised the stream)
     ctx->sgm_pin_busy = false;
     ctx->sgm_resident = false;
+    ctx->sgm_slant_ok = false;
     ctx->surf_depth_ok = false;
+    ctx->surf_slant_ok = false;
     ctx->has_cameras = ctx->has_surface = ctx->has_system = false;
     ctx->has_shading = false;
     ctx->update_prepared = false;
@@ -405,7 +407,8 @@ ctx_free(smvs_ctx *ctx)
         ctx->status, ctx->lightAb, ctx->stage, ctx->map_scratch,
         ctx->light_partial, ctx->res_work, ctx->res_zx, ctx->live_list,
         ctx->step_counter, ctx->nodes_saved, ctx->zero_block, ctx->byte_stage,
-        ctx->surf_depth, ctx->surf_tmp, ctx->surf_tmp_bytes, ctx->surf_bits };
+        ctx->surf_depth, ctx->surf_tmp, ctx->surf_tmp_bytes, ctx->surf_bits,
+        ctx->sgm_slant, ctx->surf_slant };
     for (void *p : bufs)
         if (p)
             (void)hipFree(p);

@@ -181,6 +181,21 @@ DepthOptimizer::DepthOptimizer(StereoView::Ptr main_view,
     // debugging aid: the grid surgery on the host Surface with an upload /
     // download per batch, as before round 4 (A/B against the device path)
     this->host_surgery = std::getenv("SMVS_HOST_SURGERY") != nullptr;
+    // (an option that cannot take effect is an error, before any device call)
+    if (opts.init_slants) {
+        if (!opts.use_sgm)
+            throw std::invalid_argument("DepthOptimizer: init_slants needs use_sgm");
+        FloatImage::Ptr sgm = main_view->get_deferred_depth("smvs-sgm");
+        if (sgm == nullptr && main_view->has_embedding("smvs-sgm"))
+            sgm = main_view->get_embedding("smvs-sgm");
+        FloatImage::Ptr slant;
+        if (main_view->has_embedding("smvs-sgm-slant"))
+            slant = main_view->get_embedding("smvs-sgm-slant");
+        if (sgm == nullptr || slant == nullptr || slant->channels() != 2
+            || slant->width() != sgm->width() || slant->height() != sgm->height())
+            throw std::invalid_argument("DepthOptimizer: init_slants needs an smvs-sgm-slant "
+                "embedding with two channels and the size of smvs-sgm");
+    }
     this->prepare_correspondences();
     check(smvs_ctx_create(opts.device, main_view->get_width(),
         main_view->get_height(), (int)sub_views.size(), &this->ctx),
@@ -277,8 +292,17 @@ DepthOptimizer::create_initial_surface(void)
                 filtered ? filtered->begin() : nullptr), "smvs_ctx_sgm_init_depth_mve");
             if (filtered)
                 main_view->write_depth_to_view(filtered, "smvs-sgm-filtered");
-            check(smvs_surface_create(ctx, init_scale, nullptr, nullptr, nullptr, 0,
-                &valid_patches), "smvs_surface_create");
+            if (opts.init_slants) {
+                // the slant plane from the embedding, tapped on the device next
+                // to the map it belongs to; the nodes read it where it lies
+                FloatImage::Ptr slant = main_view->get_embedding("smvs-sgm-slant");
+                check(smvs_ctx_sgm_init_slants(ctx, slant->begin(), slant->width(),
+                    slant->height(), nullptr), "smvs_ctx_sgm_init_slants");
+                check(smvs_surface_create_planes(ctx, init_scale, nullptr, nullptr,
+                    &valid_patches), "smvs_surface_create_planes");
+            } else
+                check(smvs_surface_create(ctx, init_scale, nullptr, nullptr, nullptr, 0,
+                    &valid_patches), "smvs_surface_create");
             this->surface_on_device();
             return;
         }
@@ -289,8 +313,12 @@ DepthOptimizer::create_initial_surface(void)
             main_view->get_height(), 1);
         check(smvs_ctx_sgm_init_depth(ctx, init->begin(), init->width(),
             init->height(), 5.0f, 5, full->begin()), "smvs_ctx_sgm_init_depth");
+        FloatImage::Ptr plane;
+        if (opts.init_slants)
+            plane = Surface::slant_plane(init, main_view->get_embedding("smvs-sgm-slant"),
+                main_view->get_width(), main_view->get_height());
         init = full;
-        this->surface = Surface::create(bundle, main_view, init_scale, init);
+        this->surface = Surface::create(bundle, main_view, init_scale, init, plane);
         this->sgm_depth = init;
     } else {
         if (bundle == nullptr)

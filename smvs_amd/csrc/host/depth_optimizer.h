@@ -52,6 +52,14 @@ public:
         // device from the uploaded image (smvs_ctx_prepare_shading) instead of
         // on the host and uploaded; the same bits
         bool device_shading_prep = false;
+        // not in the reference: with use_sgm, the initial surface's node slopes
+        // come from the view's "smvs-sgm-slant" embedding -- the plane
+        // hypotheses of the SGM front end's refinement sweeps -- instead of
+        // from differences of quadrant minima (include/smvs_hip.h, "Node
+        // slopes from the SGM plane hypotheses").  The embedding must have two
+        // channels and the size of "smvs-sgm"; without it, or with use_sgm
+        // off, the constructor throws std::invalid_argument.
+        bool init_slants = false;
     };
 
     struct IterationLog

@@ -89,9 +89,28 @@ smvs_host_optimize_flags(const smvs_host_view *main_in, const smvs_host_view *su
     int sgm_w, int sgm_h, float *sgm_roundtrip, const smvs_host_options *o,
     unsigned flags, float *depth_out, float *normals_out, smvs_host_log *log)
 {
+    // (this entry knows its one bit; the newer ones are smvs_host_optimize_planes')
+    if ((flags & ~(unsigned)SMVS_HOST_OPTIMIZE_DEVICE_SHADING_PREP) != 0u) {
+        g_host_error = "smvs_host_optimize_flags: unknown flag";
+        return -1;
+    }
+    return smvs_host_optimize_planes(main_in, subs_in, n_subs, bundle_in, sgm_depth, sgm_w,
+        sgm_h, sgm_roundtrip, nullptr, 0, 0, 0, o, flags, depth_out, normals_out, log);
+}
+
+extern "C" int
+smvs_host_optimize_planes(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, const float *sgm_depth,
+    int sgm_w, int sgm_h, float *sgm_roundtrip, const float *sgm_slant, int slant_w,
+    int slant_h, int slant_channels, const smvs_host_options *o,
+    unsigned flags, float *depth_out, float *normals_out, smvs_host_log *log)
+{
     try {
-        if ((flags & ~(unsigned)SMVS_HOST_OPTIMIZE_DEVICE_SHADING_PREP) != 0u)
-            throw std::invalid_argument("smvs_host_optimize_flags: unknown flag");
+        if ((flags & ~(unsigned)(SMVS_HOST_OPTIMIZE_DEVICE_SHADING_PREP
+                | SMVS_HOST_OPTIMIZE_INIT_SLANTS)) != 0u)
+            throw std::invalid_argument("smvs_host_optimize_planes: unknown flag");
+        if (sgm_slant != nullptr && (slant_w < 1 || slant_h < 1 || slant_channels < 1))
+            throw std::invalid_argument("smvs_host_optimize_planes: bad slant map");
         // (the previous call's embeddings go back to the page-locked pool BEFORE
         // this call asks it for its maps: kept until the next call's end, the 33 MB
         // of a 1920 x 1080 depth + normal pair were allocated afresh every time --
@@ -112,6 +131,13 @@ smvs_host_optimize_flags(const smvs_host_view *main_in, const smvs_host_view *su
                     sizeof(float) * sgm_w * sgm_h);
             }
         }
+        if (sgm_slant != nullptr) {
+            FloatImage::Ptr s = FloatImage::create_for_overwrite(slant_w, slant_h,
+                slant_channels);
+            std::memcpy(s->begin(), sgm_slant,
+                sizeof(float) * (size_t)slant_w * slant_h * slant_channels);
+            main_view->write_image_to_view(s, "smvs-sgm-slant");
+        }
         DepthOptimizer::Options opts;
         opts.regularization = o->regularization;
         opts.light_surf_regularization = o->light_surf_regularization;
@@ -123,6 +149,7 @@ smvs_host_optimize_flags(const smvs_host_view *main_in, const smvs_host_view *su
         opts.device = o->device;
         opts.solver = o->solver;
         opts.device_shading_prep = (flags & SMVS_HOST_OPTIMIZE_DEVICE_SHADING_PREP) != 0u;
+        opts.init_slants = (flags & SMVS_HOST_OPTIMIZE_INIT_SLANTS) != 0u;
         // (the test harness sets Options::debug_lvl through the environment:
         // smvs_host_options is mirrored field for field by smvs_amd/host.py)
         if (const char *lvl = std::getenv("SMVS_DEBUG_LVL"))
@@ -662,10 +689,65 @@ smvs_host_select_neighbors(const smvs_host_view *views_in, int n_views,
     }
 }
 
+static FloatImage::Ptr
+float_image_from(const float *data, int width, int height, int channels)
+{
+    FloatImage::Ptr img = FloatImage::create_for_overwrite(width, height, channels);
+    std::memcpy(img->begin(), data, sizeof(float) * (size_t)width * height * channels);
+    return img;
+}
+
+static int
+surface_script(const smvs_host_view *main_in,
+    const smvs_host_bundle *bundle_in, const float *init_depth, const float *init_slant,
+    int init_scale, const int *ops, int n_ops, int delete_every, int *info, double *nodes_out,
+    uint8_t *node_valid_out, uint8_t *patch_valid_out);
+
 extern "C" int
 smvs_host_surface_script(const smvs_host_view *main_in,
     const smvs_host_bundle *bundle_in, const float *init_depth, int init_scale,
     const int *ops, int n_ops, int delete_every, int *info, double *nodes_out,
+    uint8_t *node_valid_out, uint8_t *patch_valid_out)
+{
+    return surface_script(main_in, bundle_in, init_depth, nullptr, init_scale, ops, n_ops,
+        delete_every, info, nodes_out, node_valid_out, patch_valid_out);
+}
+
+extern "C" int
+smvs_host_surface_script_planes(const smvs_host_view *main_in, const float *init_depth,
+    const float *init_slant, int init_scale, const int *ops, int n_ops, int delete_every,
+    int *info, double *nodes_out, uint8_t *node_valid_out, uint8_t *patch_valid_out)
+{
+    if (init_depth == nullptr || init_slant == nullptr) {
+        g_host_error = "smvs_host_surface_script_planes: init_depth and init_slant are required";
+        return -1;
+    }
+    return surface_script(main_in, nullptr, init_depth, init_slant, init_scale, ops, n_ops,
+        delete_every, info, nodes_out, node_valid_out, patch_valid_out);
+}
+
+extern "C" int
+smvs_host_slant_plane(const float *lowres, const float *slants, int dm_w, int dm_h, int width,
+    int height, float *out)
+{
+    try {
+        if (lowres == nullptr || slants == nullptr || out == nullptr || dm_w < 1 || dm_h < 1
+            || width < 1 || height < 1)
+            throw std::invalid_argument("smvs_host_slant_plane: bad argument");
+        FloatImage::Ptr p = Surface::slant_plane(float_image_from(lowres, dm_w, dm_h, 1),
+            float_image_from(slants, dm_w, dm_h, 2), width, height);
+        std::memcpy(out, p->begin(), sizeof(float) * 2 * (size_t)width * height);
+        return 0;
+    } catch (std::exception const& e) {
+        g_host_error = e.what();
+        return -1;
+    }
+}
+
+static int
+surface_script(const smvs_host_view *main_in,
+    const smvs_host_bundle *bundle_in, const float *init_depth, const float *init_slant,
+    int init_scale, const int *ops, int n_ops, int delete_every, int *info, double *nodes_out,
     uint8_t *node_valid_out, uint8_t *patch_valid_out)
 {
     try {
@@ -681,7 +763,10 @@ smvs_host_surface_script(const smvs_host_view *main_in,
             std::memcpy(init->begin(), init_depth,
                 sizeof(float) * (size_t)main_in->width * main_in->height);
         }
-        Surface::Ptr surface = Surface::create(bundle, main_view, init_scale, init);
+        FloatImage::Ptr plane;
+        if (init_slant != nullptr)
+            plane = float_image_from(init_slant, main_in->width, main_in->height, 2);
+        Surface::Ptr surface = Surface::create(bundle, main_view, init_scale, init, plane);
         for (int k = 0; k < n_ops; ++k)
             switch (ops[k]) {
             case 1: surface->expand(); break;
@@ -716,10 +801,41 @@ smvs_host_surface_script(const smvs_host_view *main_in,
 }
 
 // The same script on the surface of a device context (csrc/surface.hip).
+static int
+surface_script_device(const smvs_host_view *main_in,
+    const smvs_host_bundle *bundle_in, const float *init_depth, const float *init_slant,
+    int init_scale, const int *ops, int n_ops, int delete_every, int device, int *info,
+    double *nodes_out, uint8_t *node_valid_out, uint8_t *patch_valid_out);
+
 extern "C" int
 smvs_host_surface_script_device(const smvs_host_view *main_in,
     const smvs_host_bundle *bundle_in, const float *init_depth, int init_scale,
     const int *ops, int n_ops, int delete_every, int device, int *info,
+    double *nodes_out, uint8_t *node_valid_out, uint8_t *patch_valid_out)
+{
+    return surface_script_device(main_in, bundle_in, init_depth, nullptr, init_scale, ops,
+        n_ops, delete_every, device, info, nodes_out, node_valid_out, patch_valid_out);
+}
+
+extern "C" int
+smvs_host_surface_script_planes_device(const smvs_host_view *main_in, const float *init_depth,
+    const float *init_slant, int init_scale, const int *ops, int n_ops, int delete_every,
+    int device, int *info, double *nodes_out, uint8_t *node_valid_out,
+    uint8_t *patch_valid_out)
+{
+    if (init_depth == nullptr || init_slant == nullptr) {
+        g_host_error = "smvs_host_surface_script_planes_device: init_depth and init_slant "
+            "are required";
+        return -1;
+    }
+    return surface_script_device(main_in, nullptr, init_depth, init_slant, init_scale, ops,
+        n_ops, delete_every, device, info, nodes_out, node_valid_out, patch_valid_out);
+}
+
+static int
+surface_script_device(const smvs_host_view *main_in,
+    const smvs_host_bundle *bundle_in, const float *init_depth, const float *init_slant,
+    int init_scale, const int *ops, int n_ops, int delete_every, int device, int *info,
     double *nodes_out, uint8_t *node_valid_out, uint8_t *patch_valid_out)
 {
     smvs_ctx *ctx = nullptr;
@@ -736,7 +852,10 @@ smvs_host_surface_script_device(const smvs_host_view *main_in,
         check(smvs_ctx_create(device, main_in->width, main_in->height, 1, &ctx),
             "smvs_ctx_create");
         int valid = 0;
-        if (init_depth != nullptr) {
+        if (init_slant != nullptr) {
+            check(smvs_surface_create_planes(ctx, init_scale, init_depth, init_slant, &valid),
+                "smvs_surface_create_planes");
+        } else if (init_depth != nullptr) {
             check(smvs_surface_create(ctx, init_scale, init_depth, nullptr, nullptr, 0,
                 &valid), "smvs_surface_create");
         } else {
@@ -849,10 +968,64 @@ smvs_host_sgm_image(const smvs_host_view *view_in, int halvings, uint8_t *out,
     }
 }
 
+static int
+surface_maps(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, const float *init_depth,
+    const float *init_slant, int init_scale, int device, float *depth_out, float *normals_out);
+
 extern "C" int
 smvs_host_surface_maps(const smvs_host_view *main_in, const smvs_host_view *subs_in,
     int n_subs, const smvs_host_bundle *bundle_in, const float *init_depth,
     int init_scale, int device, float *depth_out, float *normals_out)
+{
+    return surface_maps(main_in, subs_in, n_subs, bundle_in, init_depth, nullptr, init_scale,
+        device, depth_out, normals_out);
+}
+
+extern "C" int
+smvs_host_surface_maps_planes(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, const float *init_depth,
+    const float *init_slant, int init_scale, int device, float *depth_out, float *normals_out)
+{
+    if (init_depth == nullptr || init_slant == nullptr) {
+        g_host_error = "smvs_host_surface_maps_planes: init_depth and init_slant are required";
+        return -1;
+    }
+    return surface_maps(main_in, subs_in, n_subs, bundle_in, init_depth, init_slant, init_scale,
+        device, depth_out, normals_out);
+}
+
+extern "C" int
+smvs_host_surface_maps_host(const smvs_host_view *main_in, const float *init_depth,
+    const float *init_slant, int init_scale, float *depth_out, float *normals_out)
+{
+    try {
+        if (main_in == nullptr || init_depth == nullptr)
+            throw std::invalid_argument("smvs_host_surface_maps_host: bad argument");
+        StereoView::Ptr main_view = make_view(*main_in, false);
+        FloatImage::Ptr plane;
+        if (init_slant != nullptr)
+            plane = float_image_from(init_slant, main_in->width, main_in->height, 2);
+        Surface::Ptr surface = Surface::create(nullptr, main_view, init_scale,
+            float_image_from(init_depth, main_in->width, main_in->height, 1), plane);
+        size_t const npix = (size_t)main_in->width * main_in->height;
+        if (depth_out != nullptr)
+            std::memcpy(depth_out, surface->get_depth_map()->begin(), sizeof(float) * npix);
+        if (normals_out != nullptr)
+            std::memcpy(normals_out,
+                surface->get_normal_map(main_view->get_inverse_flen())->begin(),
+                sizeof(float) * 3 * npix);
+        return 0;
+    } catch (std::exception const& e) {
+        g_host_error = e.what();
+        return -1;
+    }
+}
+
+static int
+surface_maps(const smvs_host_view *main_in, const smvs_host_view *subs_in,
+    int n_subs, const smvs_host_bundle *bundle_in, const float *init_depth,
+    const float *init_slant, int init_scale, int device, float *depth_out, float *normals_out)
 {
     try {
         if (main_in == nullptr || subs_in == nullptr || n_subs < 1
@@ -869,7 +1042,10 @@ smvs_host_surface_maps(const smvs_host_view *main_in, const smvs_host_view *subs
             std::memcpy(init->begin(), init_depth,
                 sizeof(float) * (size_t)main_in->width * main_in->height);
         }
-        Surface::Ptr surface = Surface::create(bundle, main_view, init_scale, init);
+        FloatImage::Ptr plane;
+        if (init_slant != nullptr)
+            plane = float_image_from(init_slant, main_in->width, main_in->height, 2);
+        Surface::Ptr surface = Surface::create(bundle, main_view, init_scale, init, plane);
         DepthOptimizer::Options opts;
         opts.device = device;
         // lib/depth_optimizer.h:53-61: the surface constructor, then the
@@ -1281,8 +1457,52 @@ smvs_host_reconstruct_scene_photo(const char *scene_dir,
         n_skipped, seconds, input_scale_used);
 }
 
+static int
+reconstruct_scene_entry(unsigned known_flags, const char *scene_dir,
+    const smvs_host_recon_settings *o, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const smvs_host_sgm_photo *photo, const smvs_host_sgm_refine *refine, const int *view_ids,
+    int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
+    int *n_skipped, double *seconds, int *input_scale_used);
+
+// the flag bits of the entries up to smvs_host_reconstruct_scene_refine
+static unsigned const SCENE_FLAGS_REFINE = SMVS_HOST_SCENE_ADAPTIVE_PENALTY2
+    | SMVS_HOST_SCENE_DEVICE_INPUT_SCALING | SMVS_HOST_SCENE_DEVICE_SHADING_PREP
+    | SMVS_HOST_SCENE_GAMMA_SRGB;
+
 extern "C" int
 smvs_host_reconstruct_scene_refine(const char *scene_dir,
+    const smvs_host_recon_settings *o, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const smvs_host_sgm_photo *photo, const smvs_host_sgm_refine *refine, const int *view_ids,
+    int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
+    int *n_skipped, double *seconds, int *input_scale_used)
+{
+    return reconstruct_scene_entry(SCENE_FLAGS_REFINE, scene_dir, o, flags, sgm_num_steps,
+        sgm_subplane, sgm_neighbors, sgm_consensus, sgm_agree_ratio, sgm_min_agree, sweep,
+        filter, photo, refine, view_ids, n_view_ids, reconstructed_out, max_reconstructed,
+        n_reconstructed, n_skipped, seconds, input_scale_used);
+}
+
+extern "C" int
+smvs_host_reconstruct_scene_planes(const char *scene_dir,
+    const smvs_host_recon_settings *o, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const smvs_host_sgm_photo *photo, const smvs_host_sgm_refine *refine, const int *view_ids,
+    int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
+    int *n_skipped, double *seconds, int *input_scale_used)
+{
+    return reconstruct_scene_entry(SCENE_FLAGS_REFINE | SMVS_HOST_SCENE_INIT_SLANTS, scene_dir,
+        o, flags, sgm_num_steps, sgm_subplane, sgm_neighbors, sgm_consensus, sgm_agree_ratio,
+        sgm_min_agree, sweep, filter, photo, refine, view_ids, n_view_ids, reconstructed_out,
+        max_reconstructed, n_reconstructed, n_skipped, seconds, input_scale_used);
+}
+
+static int
+reconstruct_scene_entry(unsigned known_flags, const char *scene_dir,
     const smvs_host_recon_settings *o, unsigned flags, int sgm_num_steps,
     int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
     int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
@@ -1319,10 +1539,12 @@ smvs_host_reconstruct_scene_refine(const char *scene_dir,
                 "must be in [2, 128] or a multiple of 8 in [136, 256]");
         if (scene_dir == nullptr || o == nullptr)
             throw std::invalid_argument("smvs_host_reconstruct_scene: bad argument");
-        if ((flags & ~(unsigned)(SMVS_HOST_SCENE_ADAPTIVE_PENALTY2
-                | SMVS_HOST_SCENE_DEVICE_INPUT_SCALING
-                | SMVS_HOST_SCENE_DEVICE_SHADING_PREP | SMVS_HOST_SCENE_GAMMA_SRGB)) != 0u)
+        if ((flags & ~known_flags) != 0u)
             throw std::invalid_argument("smvs_host_reconstruct_scene_flags: unknown flag");
+        if ((flags & SMVS_HOST_SCENE_INIT_SLANTS) != 0u
+            && (refine == nullptr || refine->sweeps == 0))
+            throw std::invalid_argument("smvs_host_reconstruct_scene_refine: init_slants needs "
+                "sgm_refine_sweeps > 0");
         ReconSettings conf;
         if (o->image_embedding != nullptr)
             conf.image_embedding = o->image_embedding;
@@ -1374,6 +1596,7 @@ smvs_host_reconstruct_scene_refine(const char *scene_dir,
         conf.device_input_scaling = (flags & SMVS_HOST_SCENE_DEVICE_INPUT_SCALING) != 0u;
         conf.device_shading_prep = (flags & SMVS_HOST_SCENE_DEVICE_SHADING_PREP) != 0u;
         conf.gamma_correction = (flags & SMVS_HOST_SCENE_GAMMA_SRGB) != 0u;
+        conf.init_slants = (flags & SMVS_HOST_SCENE_INIT_SLANTS) != 0u;
         conf.num_neighbors = (std::size_t)o->num_neighbors;
         conf.min_neighbors = (std::size_t)o->min_neighbors;
         conf.first_device = o->first_device;

@@ -73,9 +73,24 @@ int smvs_host_optimize(const smvs_host_view *main_view,
  * the host path's, bit for bit.  An unknown bit is an argument error, raised
  * before anything else is looked at.  smvs_host_optimize forwards with 0. */
 #define SMVS_HOST_OPTIMIZE_DEVICE_SHADING_PREP 1
+/* Bit 1, known to smvs_host_optimize_planes only (to smvs_host_optimize_flags it
+ * stays the unknown bit it was): DepthOptimizer::Options::init_slants -- the
+ * initial surface's node slopes from the view's "smvs-sgm-slant" embedding.
+ * Without use_sgm, or without a two-channel embedding of the size of
+ * "smvs-sgm", an argument error before any device call. */
+#define SMVS_HOST_OPTIMIZE_INIT_SLANTS 2
 int smvs_host_optimize_flags(const smvs_host_view *main_view,
     const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
     const float *sgm_depth, int sgm_w, int sgm_h, float *sgm_depth_roundtrip,
+    const smvs_host_options *opts, unsigned flags, float *depth_out,
+    float *normals_out, smvs_host_log *log);
+/* The same with sgm_slant[slant_h][slant_w][slant_channels] (may be NULL: none)
+ * stored as the "smvs-sgm-slant" embedding, as the SGM front end's refinement
+ * sweeps would; smvs_host_optimize_flags forwards to this with NULL. */
+int smvs_host_optimize_planes(const smvs_host_view *main_view,
+    const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
+    const float *sgm_depth, int sgm_w, int sgm_h, float *sgm_depth_roundtrip,
+    const float *sgm_slant, int slant_w, int slant_h, int slant_channels,
     const smvs_host_options *opts, unsigned flags, float *depth_out,
     float *normals_out, smvs_host_log *log);
 
@@ -286,6 +301,23 @@ int smvs_host_surface_script_device(const smvs_host_view *main_view,
     const smvs_host_bundle *bundle, const float *init_depth, int init_scale,
     const int *ops, int n_ops, int delete_every, int device, int *info6,
     double *nodes_out, uint8_t *node_valid_out, uint8_t *patch_valid_out);
+/* The two with a slant plane: init_depth (W x H) and init_slant (W x H x 2, the
+ * plane P of include/smvs_hip.h, "Node slopes from the SGM plane hypotheses")
+ * are both required; Surface::create(..., init, slant) on the host,
+ * smvs_surface_create_planes on the device. */
+int smvs_host_surface_script_planes(const smvs_host_view *main_view,
+    const float *init_depth, const float *init_slant, int init_scale,
+    const int *ops, int n_ops, int delete_every, int *info, double *nodes_out,
+    uint8_t *node_valid_out, uint8_t *patch_valid_out);
+int smvs_host_surface_script_planes_device(const smvs_host_view *main_view,
+    const float *init_depth, const float *init_slant, int init_scale,
+    const int *ops, int n_ops, int delete_every, int device, int *info6,
+    double *nodes_out, uint8_t *node_valid_out, uint8_t *patch_valid_out);
+/* Surface::slant_plane, the tap rule of smvs_ctx_sgm_init_slants on the host (no
+ * device involved): lowres[dm_h][dm_w], slants[dm_h][dm_w][2] ->
+ * out[height][width][2]. */
+int smvs_host_slant_plane(const float *lowres, const float *slants, int dm_w, int dm_h,
+    int width, int height, float *out);
 
 /* The per-view tasks of smvsrecon (app/smvsrecon.cc:658-733) for n_jobs
  * reference views on a smvs_amd::ViewQueue: per job StereoView::create for the
@@ -371,6 +403,11 @@ int smvs_host_reconstruct_scene_mode(const char *scene_dir,
 /* (value 4 is not assigned: it stays the argument error callers have met so far) */
 #define SMVS_HOST_SCENE_DEVICE_SHADING_PREP 8   /* ReconSettings::device_shading_prep */
 #define SMVS_HOST_SCENE_GAMMA_SRGB 16           /* ReconSettings::gamma_correction (--gamma-srgb) */
+/* ReconSettings::init_slants: the initial surfaces' node slopes from the views'
+ * smvs-sgm-slant embeddings.  Known to smvs_host_reconstruct_scene_planes only
+ * (to the entries before it, it stays the unknown bit it was); an argument
+ * error before the scene is read unless the refinement sweeps are on. */
+#define SMVS_HOST_SCENE_INIT_SLANTS 32
 int smvs_host_reconstruct_scene_flags(const char *scene_dir,
     const smvs_host_recon_settings *settings, unsigned flags, const int *view_ids,
     int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
@@ -456,6 +493,17 @@ int smvs_host_reconstruct_scene_photo(const char *scene_dir,
  * refine == NULL: off (smvs_host_reconstruct_scene_photo forwards to this with
  * NULL).  The reuse rule is that of sgm_subplane (force_sgm). */
 int smvs_host_reconstruct_scene_refine(const char *scene_dir,
+    const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
+    int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
+    int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
+    const smvs_host_sgm_photo *photo, const smvs_host_sgm_refine *refine, const int *view_ids,
+    int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
+    int *n_skipped, double *seconds, int *input_scale_used);
+
+/* The same with SMVS_HOST_SCENE_INIT_SLANTS among the flags
+ * (ReconSettings::init_slants); smvs_host_reconstruct_scene_refine forwards
+ * here with its own set of bits. */
+int smvs_host_reconstruct_scene_planes(const char *scene_dir,
     const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
     int sgm_subplane, int sgm_neighbors, int sgm_consensus, float sgm_agree_ratio,
     int sgm_min_agree, const smvs_host_sgm_sweep *sweep, const smvs_host_sgm_filter *filter,
@@ -561,6 +609,16 @@ int smvs_host_surface_maps(const smvs_host_view *main_view,
     const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
     const float *init_depth, int init_scale, int device, float *depth_out,
     float *normals_out);
+/* The same for Surface::create(..., init_depth, init_slant): both required.
+ * smvs_host_surface_maps_host: Surface::get_depth_map / get_normal_map of the
+ * host mirror on their own, no device involved (init_slant may be NULL, either
+ * output may be NULL). */
+int smvs_host_surface_maps_host(const smvs_host_view *main_view, const float *init_depth,
+    const float *init_slant, int init_scale, float *depth_out, float *normals_out);
+int smvs_host_surface_maps_planes(const smvs_host_view *main_view,
+    const smvs_host_view *subs, int n_subs, const smvs_host_bundle *bundle,
+    const float *init_depth, const float *init_slant, int init_scale, int device,
+    float *depth_out, float *normals_out);
 
 /* Host-only pieces of the SGM front end, for CPU tests (no device involved):
  *   smvs_host_depth_range: SGMStereo::fill_depth_range_for_view

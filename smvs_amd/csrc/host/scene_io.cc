@@ -402,6 +402,9 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
     if (!SGMStereo::Options::valid_num_steps(conf.sgm_num_steps))
         throw std::invalid_argument("sgm_num_steps must be in [2, 128] or a multiple "
             "of 8 in [136, 256]");
+    if (conf.init_slants && conf.sgm_refine_sweeps == 0)
+        throw std::invalid_argument("init_slants needs sgm_refine_sweeps > 0: without the "
+            "refinement sweeps the SGM front end produces no slants");
     Scene::Ptr scene = Scene::create(scene_path);
     std::vector<SceneView>& views = scene->get_views();
 
@@ -621,6 +624,12 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                     } else {
                         main_view->write_image_to_view(
                             load_mvei_float(view.image_path("smvs-sgm")), "smvs-sgm");
+                        int swhct[4] = { 0, 0, 0, 0 };
+                        if (conf.init_slants
+                            && mvei_header(view.image_path("smvs-sgm-slant"), swhct))
+                            main_view->write_image_to_view(
+                                load_mvei_float(view.image_path("smvs-sgm-slant")),
+                                "smvs-sgm-slant");
                     }
                 }
                 DepthOptimizer::Options do_opts;                      // :711-720
@@ -629,6 +638,7 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                 do_opts.min_scale = conf.output_scale;
                 do_opts.use_shading = conf.use_shading;
                 do_opts.device_shading_prep = conf.device_shading_prep;
+                do_opts.init_slants = conf.init_slants;
                 do_opts.output_name = report.output_name;
                 do_opts.use_sgm = conf.use_sgm;
                 do_opts.full_optimization = conf.full_optimization;

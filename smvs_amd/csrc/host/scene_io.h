@@ -153,8 +153,8 @@ struct ReconSettings
     // refine_slant_step / refine_seed / refine_fill -- the multi-view plane
     // refinement sweeps of include/smvs_hip.h in the photo test's place (they
     // need sgm_photo_radius > 0); the slants are saved as smvs-sgm-slant (two
-    // channels) next to smvs-sgm-confidence, and the optimizer does not read
-    // them.  Off by default (sweeps 0); untuned defaults of a user option; the
+    // channels) next to smvs-sgm-confidence; the optimizer reads them with
+    // init_slants only.  Off by default (sweeps 0); untuned defaults of a user option; the
     // reuse rule is that of sgm_subplane (force_sgm).
     int sgm_refine_sweeps = 0;
     int sgm_refine_samples = 2;
@@ -168,6 +168,12 @@ struct ReconSettings
     // not in the reference's AppSettings: DepthOptimizer::Options::
     // device_shading_prep (with use_shading only)
     bool device_shading_prep = false;
+    // not in the reference's AppSettings: DepthOptimizer::Options::init_slants --
+    // the initial surface's node slopes from every view's smvs-sgm-slant
+    // embedding.  Needs sgm_refine_sweeps > 0 (an error otherwise, before the
+    // scene is read); a view whose smvs-sgm map is reused from disk needs its
+    // smvs-sgm-slant next to it.  Off by default.
+    bool init_slants = false;
     std::size_t num_neighbors = 6, min_neighbors = 3;
     int first_device = 0, num_devices = 1, views_in_flight = 2;
 };

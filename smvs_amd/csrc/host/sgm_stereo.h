@@ -120,7 +120,8 @@ public:
         // refine_seed -- whenever that raises the photo test's confidence;
         // refine_fill = 1 lets a pixel without a depth adopt a neighbour's
         // plane.  With the sweeps on the slants are written as the two-channel
-        // smvs-sgm-slant embedding; the optimizer does not read them.
+        // smvs-sgm-slant embedding; the optimizer reads them with
+        // DepthOptimizer::Options::init_slants only.
         // (0, 2, 0.02, 0.01, 1, 1) are defaults of a user option, untuned: nobody
         // has measured them on real scenes.
         int refine_sweeps = 0;

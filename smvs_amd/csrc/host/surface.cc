@@ -36,11 +36,16 @@ PatchEval::eval(double x, double y, int kx, int ky) const
 
 Surface::Ptr
 Surface::create(Bundle::ConstPtr bundle, StereoView::Ptr main_view, int scale,
-    FloatImage::ConstPtr init_depth)
+    FloatImage::ConstPtr init_depth, FloatImage::ConstPtr init_slant)
 {
     // lib/surface.cc:19-53
     Ptr s(new Surface());
     int const width = main_view->get_width(), height = main_view->get_height();
+    if (init_slant != nullptr && (init_depth == nullptr || init_slant->width() != width
+            || init_slant->height() != height || init_slant->channels() != 2))
+        throw std::invalid_argument("Surface::create: the slant plane needs an initial "
+            "depth map and two channels of the image's size");
+    s->slant = init_slant;
     s->pixel_width = width;
     s->pixel_height = height;
     // (the integer rules of :28-37, shared with the device: surface_math.h)
@@ -69,6 +74,24 @@ Surface::create(Bundle::ConstPtr bundle, StereoView::Ptr main_view, int scale,
     }
     s->fill_patches_from_depth();
     return s;
+}
+
+FloatImage::Ptr
+Surface::slant_plane(FloatImage::ConstPtr lowres, FloatImage::ConstPtr slants, int width,
+    int height)
+{
+    if (lowres == nullptr || slants == nullptr || slants->channels() != 2
+        || lowres->channels() != 1 || slants->width() != lowres->width()
+        || slants->height() != lowres->height() || width < 1 || height < 1)
+        throw std::invalid_argument("Surface::slant_plane: the slants need two channels "
+            "and the size of the SGM depth map");
+    FloatImage::Ptr out = FloatImage::create_for_overwrite(width, height, 2);
+    float* dst = out->begin();
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x)
+            smvs_surf::slant_tap(lowres->begin(), slants->begin(), lowres->width(),
+                lowres->height(), width, height, x, y, dst + 2 * ((size_t)y * width + x));
+    return out;
 }
 
 void
@@ -301,6 +324,9 @@ Surface::initialize_node_from_depth(int idx, int idy)
     // for all nodes instead of an allocation per node)
     std::vector<double>& all = window_depths;
     all.clear();
+    float const* smap = slant != nullptr ? slant->begin() : nullptr;
+    window_slants[0].clear();
+    window_slants[1].clear();
     double lowest[4] = { 0, 0, 0, 0 };
     int quadrants = 4;
     int const dw = depth->width(), dh = depth->height();
@@ -318,6 +344,13 @@ Surface::initialize_node_from_depth(int idx, int idy)
                 lowest[q] = any ? std::min(lowest[q], d) : d;
                 any = true;
                 all.push_back(d);
+                if (smap != nullptr) {
+                    float const* sp = smap + 2 * ((size_t)yy * dw + xx);
+                    if (smvs_surf::slant_finite(sp[0]) && smvs_surf::slant_finite(sp[1])) {
+                        window_slants[0].push_back(smvs_surf::slant_key(sp[0]));
+                        window_slants[1].push_back(smvs_surf::slant_key(sp[1]));
+                    }
+                }
             }
         }
         if (!any)
@@ -327,9 +360,17 @@ Surface::initialize_node_from_depth(int idx, int idy)
         return;
     std::nth_element(all.begin(), all.begin() + all.size() / 2, all.end());
     // (:703-758, shared with the device kernel)
+    // (the slants: the element of rank cs / 2 in key order, per component)
+    std::size_t const cs = window_slants[0].size();
+    float med[2] = { 0.f, 0.f };
+    for (int ch = 0; ch < 2 && cs > 0; ++ch) {
+        std::vector<uint32_t>& k = window_slants[ch];
+        std::nth_element(k.begin(), k.begin() + cs / 2, k.end());
+        med[ch] = smvs_surf::slant_from_key(k[cs / 2]);
+    }
     double node[4];
-    if (!smvs_surf::node_from_window(all[all.size() / 2], lowest, quadrants,
-            all.size(), node))
+    if (!smvs_surf::node_from_window_planes(all[all.size() / 2], lowest, quadrants,
+            all.size(), cs, med[0], med[1], patchsize, node))
         return;
     std::copy(node, node + 4, &nodes[4 * id]);
     node_valid[id] = 1;

@@ -37,8 +37,18 @@ public:
     typedef std::shared_ptr<Surface> Ptr;
 
     // lib/surface.h:36-37
+    // init_slant (with init_depth only): the slant plane P, two channels of
+    // the image's size -- the node slopes come from it (include/smvs_hip.h,
+    // "Node slopes from the SGM plane hypotheses"; not in the reference), and
+    // the surface keeps it next to its depth map for fill_patches_from_depth.
     static Ptr create(Bundle::ConstPtr bundle, StereoView::Ptr main_view,
-        int scale, FloatImage::ConstPtr init_depth = nullptr);
+        int scale, FloatImage::ConstPtr init_depth = nullptr,
+        FloatImage::ConstPtr init_slant = nullptr);
+    // The slant plane of a view (the tap rule of smvs_ctx_sgm_init_slants on the
+    // host): lowres = the SGM-scale z-depth map, slants = its two-channel
+    // slants -> width x height x 2.
+    static FloatImage::Ptr slant_plane(FloatImage::ConstPtr lowres,
+        FloatImage::ConstPtr slants, int width, int height);
 
     // A surface from its flat arrays (what smvs_surface_download returns): the
     // host view of a surface that lives in a device context.
@@ -107,6 +117,8 @@ private:
     int pixel_width = 0, pixel_height = 0;
     int scale = 0, patchsize = 0, npx = 0, npy = 0, start_x = 0, start_y = 0;
     FloatImage::Ptr depth;
+    FloatImage::ConstPtr slant;       // the slant plane, or null
+    std::vector<uint32_t> window_slants[2];   // scratch: the slant keys of a window
     std::vector<double> nodes;        // 4 per node
     std::vector<uint8_t> node_valid;
     std::vector<uint8_t> patch_valid;

@@ -270,6 +270,85 @@ depth_key(float d)
     return c.u;
 }
 
+// ------------------------------------- node initialisation with slant planes
+// Not in the reference; the normative text is in include/smvs_hip.h ("Node
+// slopes from the SGM plane hypotheses"), tests/surface_planes_ref.py restates
+// it.  The key of a float for the rank selection of the slants: an unsigned
+// order of all non-NaN floats with -0.0 < +0.0.
+SMVS_HD uint32_t
+slant_key(float v)
+{
+    union { float f; uint32_t u; } c;
+    c.f = v;
+    return (c.u & 0x80000000u) == 0u ? (c.u ^ 0x80000000u) : ~c.u;
+}
+
+SMVS_HD float
+slant_from_key(uint32_t key)
+{
+    union { float f; uint32_t u; } c;
+    c.u = (key & 0x80000000u) != 0u ? (key ^ 0x80000000u) : ~key;
+    return c.f;
+}
+
+// finite: the exponent field is not all ones
+SMVS_HD bool
+slant_finite(float v)
+{
+    union { float f; uint32_t u; } c;
+    c.f = v;
+    return (c.u & 0x7F800000u) != 0x7F800000u;
+}
+
+// The slant plane of a context at the full-resolution pixel (x, y): the
+// bilateral's centre tap (depth_optimizer.cc:981-984) into the SGM-scale
+// z-depth map L and the slants G[dm_h][dm_w][2]; out = the two components in
+// z-depth per full-resolution pixel, both the quiet NaN 0x7FC00000 where the
+// tap has no depth or no finite slant.
+SMVS_HD void
+slant_tap(float const* L, float const* G, int dm_w, int dm_h, int width, int height,
+    int x, int y, float* out)
+{
+    SMVS_NO_CONTRACT
+    float const scale_x = (float)dm_w / (float)width;
+    float const scale_y = (float)dm_h / (float)height;
+    float fx = scale_x * (float)x, fy = scale_y * (float)y;
+    float const hx = (float)dm_w - 1.f, hy = (float)dm_h - 1.f;
+    fx = fx < 0.f ? 0.f : (fx > hx ? hx : fx);
+    fy = fy < 0.f ? 0.f : (fy > hy ? hy : fy);
+    int const sx = (int)fx, sy = (int)fy;
+    std::size_t const tap = (std::size_t)sy * dm_w + sx;
+    float const gx = G[2 * tap], gy = G[2 * tap + 1];
+    union { float f; uint32_t u; } none;
+    none.u = 0x7FC00000u;
+    if (L[tap] > 0.0f && slant_finite(gx) && slant_finite(gy)) {
+        out[0] = gx * scale_x;
+        out[1] = gy * scale_y;
+    } else {
+        out[0] = none.f;
+        out[1] = none.f;
+    }
+}
+
+// node_from_window with the slants of the window: cs = the window pixels with
+// a depth and a finite slant, mx / my = the element of rank cs / 2 of their
+// first / second component in key order (ignored when cs == 0).  Existence
+// and f are node_from_window's.
+SMVS_HD bool
+node_from_window_planes(double median, double const* lowest, int quadrants,
+    std::size_t count, std::size_t cs, float mx, float my, int ps, double* node)
+{
+    SMVS_NO_CONTRACT
+    if (!node_from_window(median, lowest, quadrants, count, node))
+        return false;
+    if (cs >= 1) {
+        node[1] = (double)mx * (double)ps;
+        node[2] = (double)my * (double)ps;
+        node[3] = 0.0;
+    }
+    return true;
+}
+
 // ---------------------------------------------------- isolated patches
 // Surface::remove_isolated_patches, lib/surface.cc:887-927, deletes in place
 // while it walks the grid column by column, so a deletion changes the counts

@@ -542,7 +542,11 @@ static int
 launch_fill_from_depth(smvs_ctx *ctx, SurfArgs const &A)
 {
     int const ps = A.g.ps;
-    if (ps >= 2) {
+    if (ctx->surf_slant_ok) {
+        // the surface keeps a slant plane (smvs_surface_create_planes): the
+        // node slopes come from it, surface_planes.hip
+        launch_init_nodes_planes(ctx);
+    } else if (ps >= 2) {
         int const T = ps * ps;
         int const G = T < 64 ? T : 64;
         int glog = 0;
@@ -622,12 +626,16 @@ using namespace smvs_hip;
 
 static_assert(I_SURF_CHANGED == I_SURF_VALID + 1, "read_counts copies both words at once");
 
-extern "C" int
-smvs_surface_create(smvs_ctx *ctx, int scale, const float *depth,
+// Surface::create; planes: the slant plane the surface keeps
+// (smvs_surface_create_planes) -- PLANES_NONE ends it, PLANES_GIVEN uploads
+// slant[W*H*2], PLANES_RESIDENT copies smvs_ctx_sgm_init_slants' plane.
+enum { PLANES_NONE = 0, PLANES_GIVEN, PLANES_RESIDENT };
+
+static int
+surface_create(smvs_ctx *ctx, int scale, const float *depth,
     const int32_t *point_pixel, const float *point_depth, int n_points,
-    int *num_valid_patches)
+    int planes, const float *slant, int *num_valid_patches)
 {
-    SMVS_REQUIRE(ctx != nullptr, "null context");
     SMVS_REQUIRE(n_points >= 0 && (n_points == 0 || (point_pixel && point_depth)),
         "bad point list");
     SMVS_REQUIRE(scale >= 0 && scale <= 10, "scale out of range");
@@ -643,6 +651,7 @@ smvs_surface_create(smvs_ctx *ctx, int scale, const float *depth,
         ctx->surf_depth_cap = npix;
     }
     ctx->surf_depth_ok = false;
+    ctx->surf_slant_ok = false;   // (this entry ends smvs_surface_create_planes' rule)
     if (depth != nullptr) {
         // through the context's staging buffer, then the clamp of :74-79
         if ((rc = ctx_upload(ctx, ctx->surf_depth, depth, npix * sizeof(float))) != SMVS_OK)
@@ -678,6 +687,19 @@ smvs_surface_create(smvs_ctx *ctx, int scale, const float *depth,
     }
     SMVS_HIP_CHECK(hipGetLastError());
     ctx->surf_depth_ok = true;
+    if (planes != PLANES_NONE) {
+        if ((rc = device_grow(&ctx->surf_slant, &ctx->surf_slant_cap, npix * 2)) != SMVS_OK)
+            return rc;
+        if (planes == PLANES_GIVEN) {
+            if ((rc = ctx_upload(ctx, ctx->surf_slant, slant, npix * 2 * sizeof(float)))
+                    != SMVS_OK)
+                return rc;
+        } else {
+            SMVS_HIP_CHECK(hipMemcpyAsync(ctx->surf_slant, ctx->sgm_slant,
+                npix * 2 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        ctx->surf_slant_ok = true;
+    }
     if ((rc = ctx_ensure_grid(ctx, scale, g.npx, g.npy, g.start_x, g.start_y)) != SMVS_OK)
         return rc;
     SMVS_HIP_CHECK(hipMemsetAsync(ctx->node_valid, 0, (size_t)ctx->num_nodes, ctx->stream));
@@ -693,6 +715,49 @@ smvs_surface_create(smvs_ctx *ctx, int scale, const float *depth,
     ctx->has_surface = true;
     surface_changed(ctx);
     return read_counts(ctx, A, num_valid_patches, nullptr);
+}
+
+extern "C" int
+smvs_surface_create(smvs_ctx *ctx, int scale, const float *depth,
+    const int32_t *point_pixel, const float *point_depth, int n_points,
+    int *num_valid_patches)
+{
+    SMVS_REQUIRE(ctx != nullptr, "null context");
+    return surface_create(ctx, scale, depth, point_pixel, point_depth, n_points, PLANES_NONE,
+        nullptr, num_valid_patches);
+}
+
+extern "C" int
+smvs_surface_create_planes(smvs_ctx *ctx, int scale, const float *depth, const float *slant,
+    int *num_valid_patches)
+{
+    SMVS_REQUIRE(ctx != nullptr, "null context");
+    SMVS_REQUIRE((depth == nullptr) == (slant == nullptr),
+        "depth and slant are either both the caller's or both NULL");
+    if (depth == nullptr && !(ctx->sgm_resident && ctx->topo_sgm != nullptr
+            && ctx->sgm_slant_ok && ctx->sgm_slant != nullptr)) {
+        set_error("smvs_surface_create_planes: no depth map / slant plane given and not both "
+            "resident (smvs_ctx_sgm_init_depth, smvs_ctx_sgm_init_slants)");
+        return SMVS_ERR_STATE;
+    }
+    return surface_create(ctx, scale, depth, nullptr, nullptr, 0,
+        depth != nullptr ? PLANES_GIVEN : PLANES_RESIDENT, slant, num_valid_patches);
+}
+
+extern "C" int
+smvs_surface_slants(smvs_ctx *ctx, float *out)
+{
+    int rc = require_surface(ctx, "smvs_surface_slants");
+    if (rc != SMVS_OK)
+        return rc;
+    SMVS_REQUIRE(out != nullptr, "null argument");
+    if (!ctx->surf_slant_ok) {
+        set_error("smvs_surface_slants: the surface keeps no slant plane "
+            "(smvs_surface_create_planes)");
+        return SMVS_ERR_STATE;
+    }
+    return ctx_download(ctx, out, ctx->surf_slant,
+        (size_t)ctx->width * ctx->height * 2 * sizeof(float));
 }
 
 extern "C" int

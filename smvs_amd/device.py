@@ -141,6 +141,60 @@ class ViewContext:
               kernel_size, _p(out, _fp)))
         return out
 
+    def sgm_init_slants(self, slant, want_plane=True):
+        """smvs_ctx_sgm_init_slants: the slant plane of the context from the
+        SGM-scale slants (dm_h, dm_w, 2), after sgm_init_depth[_mve]; returns the
+        (H, W, 2) plane (None with want_plane=False).  slant None forgets it."""
+        if slant is None:
+            check(self.lib.smvs_ctx_sgm_init_slants(self.handle, None, 0, 0, None))
+            return None
+        s = _f32(slant)
+        if s.ndim != 3 or s.shape[2] != 2:
+            raise ValueError("slant must be (dm_h, dm_w, 2)")
+        out = np.zeros((self.height, self.width, 2), np.float32) if want_plane else None
+        check(self.lib.smvs_ctx_sgm_init_slants(self.handle, _p(s, _fp), s.shape[1],
+              s.shape[0], _p(out, _fp)))
+        return out
+
+    def create_surface(self, scale, depth=None, slant=None, planes=None):
+        """smvs_surface_create from depth (H, W), or from the resident filtered
+        SGM map with depth None; slant (H, W, 2) -- or planes=True with both
+        None: the resident ones -- makes it smvs_surface_create_planes.  Returns
+        the surface as surface_download() does, plus valid_patches."""
+        use_planes = slant is not None if planes is None else bool(planes)
+        d = None if depth is None else _f32(depth)
+        valid = C.c_int(0)
+        if use_planes:
+            s = None if slant is None else _f32(slant)
+            check(self.lib.smvs_surface_create_planes(self.handle, scale, _p(d, _fp),
+                  _p(s, _fp), C.byref(valid)))
+        else:
+            check(self.lib.smvs_surface_create(self.handle, scale, _p(d, _fp), None, None, 0,
+                  C.byref(valid)))
+        out = self.surface_download()
+        out["valid_patches"] = valid.value
+        return out
+
+    def surface_download(self):
+        """smvs_surface_info + smvs_surface_download: geometry and arrays."""
+        g = (C.c_int * 6)()
+        check(self.lib.smvs_surface_info(self.handle, C.cast(g, C.c_void_p), None))
+        scale, _, npx, npy, sx, sy = (int(x) for x in g)
+        self.num_nodes, self.num_patches = (npx + 1) * (npy + 1), npx * npy
+        nodes = np.zeros((self.num_nodes, 4))
+        nv = np.zeros(self.num_nodes, np.uint8)
+        pv = np.zeros(self.num_patches, np.uint8)
+        check(self.lib.smvs_surface_download(self.handle, _p(nodes, _dp), _p(nv, _u8p),
+              _p(pv, _u8p), None))
+        return dict(scale=scale, npx=npx, npy=npy, start_x=sx, start_y=sy, nodes=nodes,
+                    node_valid=nv, patch_valid=pv)
+
+    def surface_slants(self):
+        """smvs_surface_slants: the slant plane the surface keeps, (H, W, 2)."""
+        out = np.zeros((self.height, self.width, 2), np.float32)
+        check(self.lib.smvs_surface_slants(self.handle, _p(out, _fp)))
+        return out
+
     def set_scale(self, scale):
         check(self.lib.smvs_ctx_set_scale(self.handle, scale))
 

@@ -93,13 +93,19 @@ def _marshal(inputs, keep):
 def optimize(inputs, regularization=0.01, light_reg=0.0, num_iterations=5,
              min_scale=2, use_shading=False, sgm_depth=None,
              full_optimization=False, device=0, solver="auto", want_maps=True,
-             gamma_correction=False, device_shading_prep=False):
+             gamma_correction=False, device_shading_prep=False, sgm_slant=None,
+             init_slants=False):
     """want_maps=False: optimize() only -- the depth / normal maps the reference
     reads back with get_depth() / get_normals() afterwards are not fetched (the
     embeddings optimize() itself writes are; tools/optimize_timeline.py).
     device_shading_prep (with use_shading): the main view's shading planes are
     made on the device (smvs_ctx_prepare_shading) instead of by the host's
-    StereoView::initialize_linear, with the same bits; off by default."""
+    StereoView::initialize_linear, with the same bits; off by default.
+    sgm_slant (dm_h x dm_w x 2, z-depth per SGM pixel, as the SGM front end's
+    refinement sweeps give it) is stored as the view's smvs-sgm-slant embedding;
+    init_slants (DepthOptimizer::Options::init_slants): the initial surface's node
+    slopes come from it.  init_slants without sgm_depth, or without slants of two
+    channels and sgm_depth's size, is an error; off by default."""
     lib = load()
     keep = []
     main, subs, n_subs, b = _marshal(inputs, keep)
@@ -118,12 +124,29 @@ def optimize(inputs, regularization=0.01, light_reg=0.0, num_iterations=5,
         sd = np.ascontiguousarray(sgm_depth, dtype=np.float32)
         sh, sw = sd.shape
         rt = np.zeros_like(sd)
-    rc = lib.smvs_host_optimize_flags(C.byref(main), subs, n_subs, C.byref(b),
-        sd.ctypes.data_as(_fp) if sd is not None else None, sw, sh,
-        rt.ctypes.data_as(_fp) if rt is not None else None, C.byref(o),
-        C.c_uint(1 if device_shading_prep else 0),
-        depth.ctypes.data_as(_fp) if want_maps else None,
-        normals.ctypes.data_as(_fp) if want_maps else None, C.byref(log))
+    if sgm_slant is None and not init_slants:
+        rc = lib.smvs_host_optimize_flags(C.byref(main), subs, n_subs, C.byref(b),
+            sd.ctypes.data_as(_fp) if sd is not None else None, sw, sh,
+            rt.ctypes.data_as(_fp) if rt is not None else None, C.byref(o),
+            C.c_uint(1 if device_shading_prep else 0),
+            depth.ctypes.data_as(_fp) if want_maps else None,
+            normals.ctypes.data_as(_fp) if want_maps else None, C.byref(log))
+    else:
+        sl = None
+        slw = slh = slc = 0
+        if sgm_slant is not None:
+            sl = np.ascontiguousarray(sgm_slant, dtype=np.float32)
+            if sl.ndim == 2:
+                sl = sl[:, :, None]
+            slh, slw, slc = sl.shape
+        rc = lib.smvs_host_optimize_planes(C.byref(main), subs, n_subs, C.byref(b),
+            sd.ctypes.data_as(_fp) if sd is not None else None, sw, sh,
+            rt.ctypes.data_as(_fp) if rt is not None else None,
+            sl.ctypes.data_as(_fp) if sl is not None else None, C.c_int(slw), C.c_int(slh),
+            C.c_int(slc), C.byref(o),
+            C.c_uint((1 if device_shading_prep else 0) | (2 if init_slants else 0)),
+            depth.ctypes.data_as(_fp) if want_maps else None,
+            normals.ctypes.data_as(_fp) if want_maps else None, C.byref(log))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
     steps = [dict(scale=log.scale[i], iter=log.iter[i],
@@ -276,7 +299,7 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                       sgm_photo_best_k=2, sgm_photo_min_views=2, sgm_photo_min_score=0.49,
                       sgm_photo_witnesses=-1, sgm_refine_sweeps=0, sgm_refine_samples=2,
                       sgm_refine_depth_step=0.02, sgm_refine_slant_step=0.01,
-                      sgm_refine_seed=1, sgm_refine_fill=1):
+                      sgm_refine_seed=1, sgm_refine_fill=1, init_slants=False):
     """smvsrecon's scene-level run (app/smvsrecon.cc:400-745) through
     smvs_amd::reconstruct_scene: returns (reconstructed ids, skipped, seconds)
     [, input scale used if `details`].  input_scale < 0 (the default, as
@@ -345,10 +368,16 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     1 .. 8 red-black sweeps (0 is off) in which a pixel adopts a neighbour's plane
     or one of `samples` perturbations of its own whenever that raises its
     confidence.  The slants are saved as smvs-sgm-slant (two channels) next to
-    smvs-sgm-confidence; the optimizer does not read them.  Off by default;
-    (0, 2, 0.02, 0.01, 1, 1) are defaults of a user option, untuned, and nobody
-    has measured them on real scenes.  The reuse rule is that of sgm_subplane
-    (force_sgm)."""
+    smvs-sgm-confidence; the optimizer reads them with init_slants only.  Off by
+    default; (0, 2, 0.02, 0.01, 1, 1) are defaults of a user option, untuned, and
+    nobody has measured them on real scenes.  The reuse rule is that of
+    sgm_subplane (force_sgm).
+    init_slants: ReconSettings::init_slants -- every view's initial surface takes
+    its node slopes from the view's smvs-sgm-slant embedding (include/smvs_hip.h,
+    "Node slopes from the SGM plane hypotheses").  With sgm_refine_sweeps=0 it is
+    an error; off by default, and its effect on real scenes is not measured."""
+    if init_slants and int(sgm_refine_sweeps) == 0:
+        raise ValueError("init_slants needs sgm_refine_sweeps > 0")
     lib = load()
     filt = SgmFilter(int(sgm_uniqueness), int(sgm_uniqueness_window), int(sgm_speckle_size),
                      float(sgm_speckle_ratio))
@@ -371,9 +400,12 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
                              C.byref(cap), None, None, None, None, None, None, None)
     out = np.zeros(max(cap.value, 1), np.int32)
     n = C.c_int(0); sk = C.c_int(0); secs = C.c_double(0.0); used = C.c_int(0)
-    rc = lib.smvs_host_reconstruct_scene_refine(scene_dir.encode(), C.byref(st),
+    entry = lib.smvs_host_reconstruct_scene_planes if init_slants \
+        else lib.smvs_host_reconstruct_scene_refine
+    rc = entry(scene_dir.encode(), C.byref(st),
         C.c_uint((1 if sgm_adaptive_penalty2 else 0) | (2 if device_input_scaling else 0)
-                 | (8 if device_shading_prep else 0) | (16 if gamma_correction else 0)),
+                 | (8 if device_shading_prep else 0) | (16 if gamma_correction else 0)
+                 | (32 if init_slants else 0)),
         C.c_int(sgm_num_steps), C.c_int(1 if sgm_subplane else 0),
         C.c_int(sgm_neighbors), C.c_int(1 if sgm_consensus else 0),
         C.c_float(sgm_agree_ratio), C.c_int(sgm_min_agree), C.byref(sweep), C.byref(filt),
@@ -649,14 +681,35 @@ def select_neighbors(scene, view, num_neighbors=6, use_bundle=True):
     return [int(x) for x in out[:n_out.value]]
 
 
-def surface_script(inputs, init_scale, ops, init_depth=None, delete_every=3, device=None):
+def slant_plane(lowres, slants, width, height):
+    """Surface::slant_plane, the tap rule of smvs_ctx_sgm_init_slants on the host
+    (no device involved): the SGM-scale z-depth map and its (h, w, 2) slants ->
+    the (height, width, 2) plane."""
+    lib = load()
+    lo = np.ascontiguousarray(lowres, dtype=np.float32)
+    sl = np.ascontiguousarray(slants, dtype=np.float32)
+    if sl.shape != lo.shape + (2,):
+        raise ValueError("slants must be lowres.shape + (2,)")
+    out = np.zeros((height, width, 2), np.float32)
+    rc = lib.smvs_host_slant_plane(lo.ctypes.data_as(_fp), sl.ctypes.data_as(_fp),
+        C.c_int(lo.shape[1]), C.c_int(lo.shape[0]), C.c_int(width), C.c_int(height),
+        out.ctypes.data_as(_fp))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    return out
+
+
+def surface_script(inputs, init_scale, ops, init_depth=None, delete_every=3, device=None,
+                   init_slant=None):
     """smvs_amd::Surface on its own (csrc/host/surface.cc, mirror of
     lib/surface.cc): create + a script of operations (1 expand,
     2 subdivide_patches, 3 fill_patches_from_depth, 4 remove_isolated_patches,
     5 delete every delete_every-th valid patch + remove_nodes_without_patch).
     device=None: the host mirror, no device involved; device=k: the same
     script on the surface of a device context (csrc/surface.hip), result
-    downloaded (plus valid_patches as the last operation reported it)."""
+    downloaded (plus valid_patches as the last operation reported it).
+    init_slant (with init_depth): the (H, W, 2) slant plane the node slopes come
+    from (Surface::create(..., init, slant) / smvs_surface_create_planes)."""
     lib = load()
     keep = []
     main, _, _, bundle = _marshal(inputs, keep)
@@ -667,7 +720,21 @@ def surface_script(inputs, init_scale, ops, init_depth=None, delete_every=3, dev
     ops_a = np.asarray(list(ops) + [0], dtype=np.int32)
     depth = None if init_depth is None else np.ascontiguousarray(init_depth, dtype=np.float32)
     dptr = depth.ctypes.data_as(_fp) if depth is not None else None
-    if device is None:
+    if init_slant is not None:
+        if depth is None:
+            raise ValueError("init_slant needs init_depth")
+        plane = np.ascontiguousarray(init_slant, dtype=np.float32)
+        if plane.shape != (h, w, 2):
+            raise ValueError("init_slant must be (H, W, 2)")
+        tail = (info.ctypes.data_as(_i32p), nodes.ctypes.data_as(C.POINTER(C.c_double)),
+                nv.ctypes.data_as(_u8p), pv.ctypes.data_as(_u8p))
+        head = (C.byref(main), dptr, plane.ctypes.data_as(_fp), C.c_int(init_scale),
+                ops_a.ctypes.data_as(_i32p), C.c_int(len(ops)), C.c_int(delete_every))
+        if device is None:
+            rc = lib.smvs_host_surface_script_planes(*head, *tail)
+        else:
+            rc = lib.smvs_host_surface_script_planes_device(*head, C.c_int(device), *tail)
+    elif device is None:
         rc = lib.smvs_host_surface_script(C.byref(main), C.byref(bundle), dptr,
             C.c_int(init_scale), ops_a.ctypes.data_as(_i32p), C.c_int(len(ops)),
             C.c_int(delete_every), info.ctypes.data_as(_i32p),
@@ -691,9 +758,12 @@ def surface_script(inputs, init_scale, ops, init_depth=None, delete_every=3, dev
     return out
 
 
-def surface_maps(inputs, init_scale, init_depth=None, device=0):
+def surface_maps(inputs, init_scale, init_depth=None, device=0, init_slant=None):
     """DepthOptimizer(main, subs, surface, opts).get_depth() / get_normals()
-    without optimize() (lib/depth_optimizer.h:53-61)."""
+    without optimize() (lib/depth_optimizer.h:53-61).  init_slant (with
+    init_depth): the (H, W, 2) slant plane of Surface::create.  device=None (with
+    init_depth): the host mirror's Surface::get_depth_map / get_normal_map, no
+    device involved."""
     lib = load()
     keep = []
     main, subs, n_subs, b = _marshal(inputs, keep)
@@ -701,6 +771,25 @@ def surface_maps(inputs, init_scale, init_depth=None, device=0):
     depth = np.zeros((h, w), dtype=np.float32)
     normals = np.zeros((h, w, 3), dtype=np.float32)
     init = None if init_depth is None else np.ascontiguousarray(init_depth, dtype=np.float32)
+    if init_slant is not None or device is None:
+        if init is None:
+            raise ValueError("init_slant / device=None need init_depth")
+        plane = None
+        if init_slant is not None:
+            plane = np.ascontiguousarray(init_slant, dtype=np.float32)
+            if plane.shape != (h, w, 2):
+                raise ValueError("init_slant must be (H, W, 2)")
+        pptr = plane.ctypes.data_as(_fp) if plane is not None else None
+        if device is None:
+            rc = lib.smvs_host_surface_maps_host(C.byref(main), init.ctypes.data_as(_fp), pptr,
+                C.c_int(init_scale), depth.ctypes.data_as(_fp), normals.ctypes.data_as(_fp))
+        else:
+            rc = lib.smvs_host_surface_maps_planes(C.byref(main), subs, n_subs, C.byref(b),
+                init.ctypes.data_as(_fp), pptr, C.c_int(init_scale), C.c_int(device),
+                depth.ctypes.data_as(_fp), normals.ctypes.data_as(_fp))
+        if rc != 0:
+            raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+        return depth, normals
     rc = lib.smvs_host_surface_maps(C.byref(main), subs, n_subs, C.byref(b),
         init.ctypes.data_as(_fp) if init is not None else None, C.c_int(init_scale),
         C.c_int(device), depth.ctypes.data_as(_fp), normals.ctypes.data_as(_fp))
