@@ -655,6 +655,11 @@ class TopoView(C.Structure):
                 ("image", c_float_p), ("grad", c_float_p), ("flen", C.c_float)]
 
 
+class VisReport(C.Structure):
+    _fields_ = [("reason", c_i32_p), ("n", c_i32_p), ("ratio", c_double_p),
+                ("ncc", c_double_p), ("norm0", c_double_p), ("norm1", c_double_p)]
+
+
 class TopologyProblem:
     """Surface + float images + gradient planes for the orc_topology_* entry
     points.  images[0] / grads[0] belong to the main view."""
@@ -694,6 +699,31 @@ class TopologyProblem:
                                     self.n_subs, _p(self.M, c_double_p), _p(self.t, c_double_p),
                                     _p(sd, c_float_p), 1 if sd is not None else 0)
         return self.patch_vis.copy()
+
+    VIS_REASONS = ("not_valid", "border", "occluded", "anisotropy", "ncc_outside",
+                   "ncc_negative", "visible", "visible_nan")
+
+    def visibility_report(self, sgm_depth=None):
+        """subviews() with its decisions written down: arrays (patches,
+        neighbours) -- `reason` (index into VIS_REASONS), `ratio` (the largest
+        anisotropy ratio), `ncc`, `norm0`, `norm1`, `n` (ncc_for_patch's value,
+        norms and sample count); NaN / 0 where the pair never got that far.
+        `mask`: the visibility words rebuilt from the reasons alone.  Changes
+        the surface as subviews() does."""
+        sd = f32(sgm_depth) if sgm_depth is not None else None
+        shape = (self.patch_valid.size, self.n_subs)
+        rep = dict(reason=np.zeros(shape, np.int32), n=np.zeros(shape, np.int32))
+        for k in ("ratio", "ncc", "norm0", "norm1"):
+            rep[k] = np.zeros(shape, np.float64)
+        cr = VisReport(_p(rep["reason"], c_i32_p), _p(rep["n"], c_i32_p),
+                       *[_p(rep[k], c_double_p) for k in ("ratio", "ncc", "norm0", "norm1")])
+        lib().orc_topology_visibility_report(
+            C.byref(self.surf), C.byref(self.main), self.subs, self.n_subs,
+            _p(self.M, c_double_p), _p(self.t, c_double_p), _p(sd, c_float_p),
+            1 if sd is not None else 0, C.byref(cr))
+        bits = np.uint32(1) << np.arange(self.n_subs, dtype=np.uint32)
+        rep["mask"] = ((rep["reason"] >= 6) * bits).sum(axis=1).astype(np.uint32)
+        return rep
 
     def patch_mse(self):
         out = np.zeros(self.patch_valid.size)

@@ -705,6 +705,9 @@ typedef struct {
     int has_lighting;
     orc_opt_log *log;
     float flen, inv_flen;
+    /* orc_topology_visibility_report only (NULL otherwise): what
+     * create_subview_surfaces decided per (patch, neighbour), and by what */
+    const orc_vis_report *report;
 } OOpt;
 
 static void
@@ -790,9 +793,11 @@ opt_mse_for_patch(const OOpt *O, int patch_id)
     return error / counter;
 }
 
-/* depth_optimizer.cc:792-912 */
+/* depth_optimizer.cc:792-912.  detail (or NULL): { norm0, norm1, number of
+ * samples, 1 when a sample fell outside the neighbour }; the norms stay as the
+ * caller set them when the function returns before it has them. */
 static double
-opt_ncc_for_patch(const OOpt *O, int patch_id, int sub_id)
+opt_ncc_for_patch_detail(const OOpt *O, int patch_id, int sub_id, double *detail)
 {
     const OSurf *S = &O->surf;
     const OView *mv = O->main, *sv = &O->subs[sub_id];
@@ -883,9 +888,25 @@ opt_ncc_for_patch(const OOpt *O, int patch_id, int sub_id)
             result = 1;
         else
             result = orc_vec_dot(v0, v1, 3 * (size_t)n) / (norm0 * norm1);
+        if (detail)
+        {
+            detail[0] = norm0;
+            detail[1] = norm1;
+        }
+    }
+    if (detail)
+    {
+        detail[2] = n;
+        detail[3] = early;
     }
     free(pix); free(dep); free(v0); free(v1);
     return result;
+}
+
+static double
+opt_ncc_for_patch(const OOpt *O, int patch_id, int sub_id)
+{
+    return opt_ncc_for_patch_detail(O, patch_id, sub_id, NULL);
 }
 
 /* depth_optimizer.cc:433-604 */
@@ -980,6 +1001,10 @@ opt_create_subview_surfaces(OOpt *O)
             double const sw = O->subs[j].w, sh = O->subs[j].h;
             int const cw = O->subs[j].w + 1;
             int success = 1;
+            /* (the report's entry of this pair; nothing below reads it) */
+            size_t const r = (size_t)p * O->n_subs + j;
+            if (O->report)
+                O->report->reason[r] = ORC_VIS_OCCLUDED;
             for (int i = 0; i < n && success; i++)
             {
                 orc_corr C;
@@ -994,6 +1019,8 @@ opt_create_subview_surfaces(OOpt *O)
                     || proj[1] < cutoffset || proj[1] >= sh - cutoffset)
                 {
                     success = 0;
+                    if (O->report)
+                        O->report->reason[r] = ORC_VIS_BORDER;
                     break;
                 }
                 int const cx = (int)proj[0], cy = (int)proj[1];
@@ -1022,8 +1049,32 @@ opt_create_subview_surfaces(OOpt *O)
                 double const ratio = sigma0 / sigma1;
                 mx = mx > ratio ? mx : ratio;   /* std::max(max, ratio) */
             }
+            if (O->report)
+            {
+                O->report->ratio[r] = mx;
+                O->report->reason[r] = ORC_VIS_ANISOTROPY;
+            }
             if (mx > 8.0)
                 continue;
+            if (O->report)
+            {
+                /* the same two tests, with what they saw written down */
+                double ncc = NAN, detail[4] = { NAN, NAN, 0, 0 };
+                if (!O->opts->use_sgm)
+                    ncc = opt_ncc_for_patch_detail(O, p, j, detail);
+                O->report->ncc[r] = ncc;
+                O->report->norm0[r] = detail[0];
+                O->report->norm1[r] = detail[1];
+                O->report->n[r] = (int)detail[2];
+                O->report->reason[r] = detail[3] != 0 ? ORC_VIS_NCC_OUTSIDE
+                    : ncc < 0 ? ORC_VIS_NCC_NEGATIVE
+                    : ncc != ncc && !O->opts->use_sgm ? ORC_VIS_VISIBLE_NAN
+                    : ORC_VIS_VISIBLE;
+                if (!O->opts->use_sgm && ncc < 0)
+                    continue;
+                S->s.patch_vis[p] |= (1u << j);
+                continue;
+            }
             if (!O->opts->use_sgm && opt_ncc_for_patch(O, p, j) < 0)
                 continue;
             S->s.patch_vis[p] |= (1u << j);
@@ -1177,6 +1228,26 @@ orc_topology_subviews(orc_surface *s, const orc_topo_view *main_view,
     OOpt O; OView mainv; OView subv[32]; orc_opt_options opts;
     topo_setup(&O, &mainv, subv, &opts, s, main_view, subs, n_subs, Mi, ti,
         sgm_depth, use_sgm);
+    opt_create_subview_surfaces(&O);
+}
+
+void
+orc_topology_visibility_report(orc_surface *s, const orc_topo_view *main_view,
+    const orc_topo_view *subs, int n_subs, const double *Mi, const double *ti,
+    const float *sgm_depth, int use_sgm, const orc_vis_report *report)
+{
+    OOpt O; OView mainv; OView subv[32]; orc_opt_options opts;
+    topo_setup(&O, &mainv, subv, &opts, s, main_view, subs, n_subs, Mi, ti,
+        sgm_depth, use_sgm);
+    size_t const pairs = (size_t)s->npx * s->npy * n_subs;
+    for (size_t r = 0; r < pairs; ++r)
+    {
+        report->reason[r] = ORC_VIS_NOT_VALID;
+        report->n[r] = 0;
+        report->ratio[r] = report->ncc[r] = NAN;
+        report->norm0[r] = report->norm1[r] = NAN;
+    }
+    O.report = report;
     opt_create_subview_surfaces(&O);
 }
 

@@ -75,6 +75,32 @@ typedef struct {
 void orc_topology_subviews(orc_surface *s, const orc_topo_view *main_view,
     const orc_topo_view *subs, int n_subs, const double *Mi, const double *ti,
     const float *sgm_depth, int use_sgm);
+/* The same create_subview_surfaces with its decisions written down: per
+ * (patch, neighbour), index patch * n_subs + neighbour, the test that decided
+ * the pair and the numbers it looked at.  ratio: the largest anisotropy ratio
+ * (:556-572), NaN when the border / occlusion test ended the pair; ncc, norm0,
+ * norm1 (ncc_for_patch, :792-912): NaN, and n (its number of samples): 0,
+ * where the pair never got that far (the norms also when a sample fell
+ * outside the neighbour: ncc = -1).  The surface is modified as by
+ * orc_topology_subviews. */
+enum {
+    ORC_VIS_NOT_VALID = 0,      /* the patch is not valid */
+    ORC_VIS_BORDER = 1,         /* a pixel inside the neighbour's 3 % border */
+    ORC_VIS_OCCLUDED = 2,       /* a pixel behind the z-buffer */
+    ORC_VIS_ANISOTROPY = 3,     /* ratio > 8 */
+    ORC_VIS_NCC_OUTSIDE = 4,    /* an NCC sample outside [1, w - 2] x [1, h - 2] */
+    ORC_VIS_NCC_NEGATIVE = 5,   /* ncc < 0 */
+    ORC_VIS_VISIBLE = 6,
+    ORC_VIS_VISIBLE_NAN = 7     /* visible because a NaN ncc is not < 0 */
+};
+typedef struct {
+    int32_t *reason;
+    int32_t *n;
+    double *ratio, *ncc, *norm0, *norm1;
+} orc_vis_report;
+void orc_topology_visibility_report(orc_surface *s, const orc_topo_view *main_view,
+    const orc_topo_view *subs, int n_subs, const double *Mi, const double *ti,
+    const float *sgm_depth, int use_sgm, const orc_vis_report *report);
 /* mse_for_patch, :747-790, for every valid patch (-1 otherwise) */
 void orc_topology_patch_mse(orc_surface *s, const orc_topo_view *main_view,
     const orc_topo_view *subs, int n_subs, const double *Mi, const double *ti,

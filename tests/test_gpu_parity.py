@@ -885,11 +885,17 @@ def test_topology_shared_reciprocals_give_the_bits_of_the_divisions(hip, oracle,
     the instruction sequence of the division without its scaling steps.  With
     SMVS_TOPO_DIVIDE=exact every quotient is the division itself -- masks and
     errors must be the same bits (and the oracle's, the tests above).  So must
-    they be with the NCC samples of a lane taken one at a time instead of in
-    pairs and the neighbours of the MSE kernel one by one instead of four at
-    once: those only change when loads are issued.  And with the z-buffer as the
+    they be with the neighbours of the MSE kernel one by one instead of four at
+    once: that only changes when loads are issued.  And with the z-buffer as the
     reference keeps it (3 x 3 splats, nine lookups per pixel) instead of its
-    5 x 5 minimum filter and one lookup (round 6, topo_dilate5_kernel)."""
+    5 x 5 minimum filter and one lookup (round 6, topo_dilate5_kernel).
+    (SMVS_NCC_PAIRS=0 -- the NCC samples of a lane one at a time instead of in
+    pairs -- is set here too, but the views of this test are grey and the pairs
+    are the RGB path: on these inputs the switch selects nothing, and the NCC
+    of synth's renderings decides next to nothing anyway.  The leg that tests
+    it, and the other switches on masks the NCC did decide, is
+    test_gpu_visibility_decisions.py's
+    test_noise_masks_under_every_switch_of_the_kernel.)"""
     prob, surf, ctx, tp = _topology_setup(hip, oracle, size[0], size[1], n_subs, scale, 0.01)
     tp.subviews()
     surf2 = dict(surf)
