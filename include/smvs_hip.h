@@ -1324,6 +1324,52 @@ int smvs_rescale_half_gaussian(int device, const uint8_t *pixels, int width, int
     int channels, int halvings, uint8_t *out, size_t out_capacity, int *out_width,
     int *out_height);
 
+/* Undistortion: one interleaved u8 image of a camera with lens distortion, an
+ * off-centre principal point or non-square pixels, resampled on the device
+ * into the pinhole camera the rest of this library works with -- focal length
+ * out_focal pixels, principal point (out_width / 2, out_height / 2), square
+ * pixels (CameraInfo carries only flen).  The importer of COLMAP models
+ * (host/colmap_io.h) calls it per image; it has no counterpart in the
+ * reference.
+ *
+ * One form of the lens covers COLMAP's SIMPLE_PINHOLE (f, cx, cy), PINHOLE
+ * (fx, fy, cx, cy), SIMPLE_RADIAL (f, cx, cy, k), RADIAL (f, cx, cy, k1, k2)
+ * and OPENCV (fx, fy, cx, cy, k1, k2, p1, p2); parameters a model lacks are
+ * zero and their terms then vanish exactly.
+ *
+ * Per output pixel (x, y), everything in float, one rounding per operation,
+ * no contraction, in this order; inv = (float)(1.0 / (double)out_focal) is
+ * formed on the host:
+ *   u  = (((float)x + 0.5f) - 0.5f*(float)out_width ) * inv
+ *   v  = (((float)y + 0.5f) - 0.5f*(float)out_height) * inv
+ *   uu = u*u;  vv = v*v;  r2 = uu + vv;  uv = u*v
+ *   rad = 1.0f + r2*(k1 + k2*r2)
+ *   du = (2.0f*p1)*uv + p2*(r2 + 2.0f*uu)
+ *   dv = p1*(r2 + 2.0f*vv) + (2.0f*p2)*uv
+ *   sx = ((fx*(u*rad + du)) + cx) - 0.5f
+ *   sy = ((fy*(v*rad + dv)) + cy) - 0.5f
+ * The pixel is inside iff 0 <= sx <= width - 1 and 0 <= sy <= height - 1 (a NaN
+ * is outside).  Inside, each channel is Image<uint8_t>::linear_at
+ * ([MVE-unverified] M3): x0 = (int)sx, x1 = min(x0 + 1, width - 1), the same in
+ * y; w1 = sx - x0, w0 = 1 - w1, w3 = sy - y0, w2 = 1 - w3;
+ * v00*w0*w2 + v10*w1*w2 + v01*w0*w3 + v11*w1*w3 with the products and the sum
+ * left to right, then + 0.5f and truncated.  Outside, every channel is 0 and
+ * the pixel counts in *blank_pixels (may be NULL).  For a source f that is a
+ * power of two, a centred principal point and out_focal = f, out equals pixels
+ * byte for byte.
+ *
+ * Argument errors (SMVS_ERR_INVALID, before any device call; out untouched):
+ * a null pixels, lens or out, channels outside 1..4, any size below 1,
+ * out_focal not positive (or not finite), a non-finite lens value, an image of
+ * more than 2^31 bytes. */
+typedef struct {
+    float fx, fy, cx, cy, k1, k2, p1, p2;   /* source camera, pixels; COLMAP convention:
+                                               the centre of pixel (0,0) is (0.5,0.5) */
+} smvs_lens;
+int smvs_undistort_u8(int device, const uint8_t *pixels, int width, int height, int channels,
+    const smvs_lens *lens, float out_focal, int out_width, int out_height,
+    uint8_t *out, int64_t *blank_pixels /* may be NULL */);
+
 /* The context-free entry points above (smvs_sgm_run, smvs_sgm_depth_for_view,
  * smvs_bilateral_upsample, smvs_cut_depth_maps) draw their device buffers,
  * stream and pinned staging memory from a per-device pool of workspaces that

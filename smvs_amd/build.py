@@ -11,7 +11,7 @@ SOURCES = ["ctx.hip", "gn_construct.hip", "cg.hip", "cg_resident.hip", "reactiva
            "sgm_paths.hip", "sgm_wta.hip", "sgm_view.hip", "sgm_sweep.hip", "sgm_speckle.hip", "sgm_photo.hip", "sgm_refine.hip", "image_prep.hip", "bilateral.hip",
            "scale.hip", "topology.hip", "topo_zbuffer.hip", "topo_visibility.hip", "topo_mse.hip",
            "topo_cut.hip", "mesh.hip", "simplify.hip", "pool.hip", "surface.hip",
-           "surface_planes.hip"]
+           "surface_planes.hip", "undistort.hip"]
 # HIP-free units of the library: the host compiler builds them
 HOST_CC_SOURCES = ["tile_budget.cc"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
@@ -22,10 +22,11 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    # every header and source of csrc/ and the two host/ headers the device code includes
+    # every header and source of csrc/ and the three host/ headers the device code includes
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
     deps += [os.path.join(CSRC, s) for s in HOST_CC_SOURCES + [os.path.join("host", "topo_math.h"),
-                                                             os.path.join("host", "surface_math.h")]]
+                                                             os.path.join("host", "surface_math.h"),
+                                                             os.path.join("host", "undistort_math.h")]]
     deps.append(os.path.join(HERE, "..", "include", "smvs_hip.h"))
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -34,7 +35,8 @@ HOST_DIR = os.path.join(CSRC, "host")
 HOST_LIB = os.path.join(HOST_DIR, "libsmvs_host.so")
 HOST_SOURCES = ["camera.cc", "stereo_view.cc", "surface.cc", "sgm_stereo.cc",
                 "depth_optimizer.cc", "view_selection.cc", "view_queue.cc", "conjugate_gradient.cc",
-                "gauss_newton_step.cc", "scene_io.cc", "mesh_generator.cc", "png_io.cc", "jpeg_io.cc", "pinned_images.cc", "host_capi.cc"]
+                "gauss_newton_step.cc", "scene_io.cc", "mesh_generator.cc", "png_io.cc", "jpeg_io.cc", "pinned_images.cc",
+                "colmap_io.cc", "colmap_import.cc", "host_capi.cc"]
 
 
 def _host_stale():

@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../../include/smvs_hip.h"   /* smvs_lens */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -582,6 +584,49 @@ int smvs_host_rescale_half_size_gaussian(const uint8_t *pixels, int width, int h
 int smvs_host_rescale_half_size_gaussian_device(const uint8_t *pixels, int width,
     int height, int channels, int halvings, int device, uint8_t *out,
     size_t out_capacity, int *out_width, int *out_height);
+
+/* COLMAP models as MVE scenes (csrc/host/colmap_io.h; [COLMAP-unverified] C1-C9
+ * of tests/golden/COLMAP.md; no counterpart in the reference).
+ *
+ * smvs_host_undistort_u8: the undistortion resampling of include/smvs_hip.h;
+ * device = -1: the host form (csrc/host/undistort_math.h, the kernel's own
+ * arithmetic), device = k: smvs_undistort_u8 on device k; the same bytes and
+ * the same blank count.  What smvs_undistort_u8 refuses is refused here, with
+ * out untouched.
+ *
+ * smvs_host_read_colmap_model: cameras / images / points3D of model_dir (.bin
+ * if all three are there, else .txt), checked, as three sections in COLMAP's
+ * binary layout (C6-C8) one behind the other.  section_bytes3 receives their
+ * sizes; buffer may be NULL to ask for the sizes first.  *binary: which files
+ * were read.
+ *
+ * smvs_host_import_colmap: import_colmap.  container: 0 = png, 1 = mvei;
+ * device -1: the host form; threads 1..16.  The per-view arrays (any may be
+ * NULL) have room for max_views entries and receive the views written, in view
+ * order: the view id, COLMAP's IMAGE_ID, width / height / channels, flen and
+ * the number of blank pixels. */
+typedef struct {
+    int device;
+    float zoom;
+    int out_width, out_height;
+    int container;
+    int threads;
+    int overwrite;
+} smvs_host_import_settings;
+typedef struct {
+    int num_views, views_written;
+    int64_t points_kept, points_dropped, track_elements_kept, track_elements_dropped;
+    double seconds, decode_seconds, undistort_seconds, encode_seconds;
+} smvs_host_import_report;
+int smvs_host_undistort_u8(const uint8_t *pixels, int width, int height, int channels,
+    const smvs_lens *lens, float out_focal, int out_width, int out_height, int device,
+    uint8_t *out, int64_t *blank_pixels);
+int smvs_host_read_colmap_model(const char *model_dir, uint8_t *buffer, size_t capacity,
+    uint64_t *section_bytes3, int *binary);
+int smvs_host_import_colmap(const char *model_dir, const char *image_dir,
+    const char *scene_dir, const smvs_host_import_settings *settings, const int *view_ids,
+    int n_view_ids, smvs_host_import_report *report, int max_views, int *view_id,
+    uint32_t *image_id, int *whc3, float *flen, int64_t *blank_pixels);
 
 /* MVE scene I/O without a device: parses the scene (views/<x>.mve/meta.ini,
  * synth_0.out) -> number of list entries, and per entry (caller-sized arrays of

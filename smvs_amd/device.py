@@ -759,6 +759,48 @@ def rescale_half_gaussian(image, halvings=1, device=0):
     return out[:, :, 0] if squeeze else out
 
 
+class Lens(C.Structure):
+    """smvs_lens of include/smvs_hip.h: the source camera in pixels, COLMAP's
+    convention (the centre of pixel (0, 0) is (0.5, 0.5))."""
+    _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")]
+
+
+def make_lens(lens):
+    """A Lens from a Lens, a dict with fx, fy, cx, cy and optionally k1, k2, p1,
+    p2 (or f for fx = fy), or a sequence in the struct's order."""
+    if isinstance(lens, Lens):
+        return lens
+    if isinstance(lens, dict):
+        d = dict(lens)
+        if "f" in d:
+            d.setdefault("fx", d["f"]); d.setdefault("fy", d["f"])
+        return Lens(*[float(d.get(k, 0.0)) for k, _ in Lens._fields_])
+    v = [float(x) for x in lens]
+    return Lens(*(v + [0.0] * (8 - len(v))))
+
+
+def undistort(image, lens, out_focal, out_size=None, device=0, return_blank=False):
+    """smvs_undistort_u8: a u8 image (h, w) or (h, w, c), c = 1..4, of the camera
+    `lens` resampled on the device into the pinhole camera of focal length
+    out_focal pixels with a centred principal point; out_size = (width, height),
+    the input's by default.  return_blank: (image, number of blank pixels)."""
+    lib = _capi.load()
+    a = np.ascontiguousarray(image, dtype=np.uint8)
+    squeeze = a.ndim == 2
+    if squeeze:
+        a = a[:, :, None]
+    h, w, c = a.shape
+    ow, oh = (w, h) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    out = np.zeros((max(oh, 0), max(ow, 0), c), np.uint8)
+    blank = C.c_int64(0)
+    L = make_lens(lens)
+    check(lib.smvs_undistort_u8(C.c_int(device), _p(a, _u8p), C.c_int(w), C.c_int(h),
+          C.c_int(c), C.byref(L), C.c_float(out_focal), C.c_int(ow), C.c_int(oh),
+          _p(out, _u8p), C.byref(blank)))
+    out = out[:, :, 0] if squeeze else out
+    return (out, blank.value) if return_blank else out
+
+
 class SgmNeighbor(C.Structure):
     """smvs_sgm_neighbor of include/smvs_hip.h."""
     _fields_ = [("image", _u8p), ("width", C.c_int), ("height", C.c_int),

@@ -1040,3 +1040,162 @@ def save_ply_mesh(path, xyz, normals, rgb, confidence, faces):
         C.c_int64(n), faces.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_int64(len(faces)))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+
+
+# ------------------------------------------------------------------ COLMAP
+COLMAP_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4),
+                 3: ("RADIAL", 5), 4: ("OPENCV", 8)}
+
+
+class ImportSettings(C.Structure):
+    """smvs_host_import_settings of csrc/host/host_capi.h."""
+    _fields_ = [("device", C.c_int), ("zoom", C.c_float), ("out_width", C.c_int),
+                ("out_height", C.c_int), ("container", C.c_int), ("threads", C.c_int),
+                ("overwrite", C.c_int)]
+
+
+class ImportReport(C.Structure):
+    """smvs_host_import_report of csrc/host/host_capi.h."""
+    _fields_ = [("num_views", C.c_int), ("views_written", C.c_int),
+                ("points_kept", C.c_int64), ("points_dropped", C.c_int64),
+                ("track_elements_kept", C.c_int64), ("track_elements_dropped", C.c_int64),
+                ("seconds", C.c_double), ("decode_seconds", C.c_double),
+                ("undistort_seconds", C.c_double), ("encode_seconds", C.c_double)]
+
+
+def undistort(array, lens, out_focal, out_size=None, device=None, return_blank=False):
+    """The undistortion resampling of include/smvs_hip.h (smvs_undistort_u8) of a
+    u8 image (h, w) or (h, w, c): device=None is the host form
+    (csrc/host/undistort_math.h, the kernel's own arithmetic), device=k the
+    kernel on device k -- the same bytes.  lens: smvs_amd.device.make_lens;
+    out_size = (width, height), the input's by default.  return_blank: (image,
+    number of blank pixels)."""
+    from .device import make_lens
+    lib = load()
+    a = np.ascontiguousarray(array, dtype=np.uint8)
+    squeeze = a.ndim == 2
+    if squeeze:
+        a = a[:, :, None]
+    h, w, c = a.shape
+    ow, oh = (w, h) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    out = np.zeros((max(oh, 0), max(ow, 0), c), np.uint8)
+    blank = C.c_int64(0)
+    L = make_lens(lens)
+    rc = lib.smvs_host_undistort_u8(a.ctypes.data_as(_u8p), C.c_int(w), C.c_int(h), C.c_int(c),
+                                    C.byref(L), C.c_float(out_focal), C.c_int(ow), C.c_int(oh),
+                                    C.c_int(-1 if device is None else device),
+                                    out.ctypes.data_as(_u8p), C.byref(blank))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    out = out[:, :, 0] if squeeze else out
+    return (out, blank.value) if return_blank else out
+
+
+def _unpack_colmap(cams, imgs, pts):
+    """The three sections of smvs_host_read_colmap_model (COLMAP's binary
+    layout, tests/golden/COLMAP.md C6-C8) as dicts keyed by id."""
+    import struct
+    cameras, images, points = {}, {}, {}
+    (n,), at = struct.unpack_from("<Q", cams, 0), 8
+    for _ in range(n):
+        cid, model, w, h = struct.unpack_from("<IiQQ", cams, at)
+        at += 24
+        name, k = COLMAP_MODELS[model]
+        params = np.frombuffer(cams, "<f8", k, at).copy()
+        at += 8 * k
+        cameras[cid] = dict(model=name, width=w, height=h, params=params)
+    (n,), at = struct.unpack_from("<Q", imgs, 0), 8
+    for _ in range(n):
+        iid = struct.unpack_from("<I", imgs, at)[0]
+        q = np.frombuffer(imgs, "<f8", 4, at + 4).copy()
+        t = np.frombuffer(imgs, "<f8", 3, at + 36).copy()
+        cam = struct.unpack_from("<I", imgs, at + 60)[0]
+        at += 64
+        end = imgs.index(b"\0", at)
+        name = imgs[at:end].decode()
+        (m,), at = struct.unpack_from("<Q", imgs, end + 1), end + 9
+        rec = np.frombuffer(imgs, np.dtype([("x", "<f8"), ("y", "<f8"), ("id", "<u8")]), m, at)
+        at += 24 * m
+        xys = np.stack([rec["x"], rec["y"]], axis=1) if m else np.zeros((0, 2))
+        images[iid] = dict(q=q, t=t, camera_id=cam, name=name, xys=xys,
+                           point3D_ids=rec["id"].astype(np.int64))
+    (n,), at = struct.unpack_from("<Q", pts, 0), 8
+    for _ in range(n):
+        pid = struct.unpack_from("<Q", pts, at)[0]
+        xyz = np.frombuffer(pts, "<f8", 3, at + 8).copy()
+        rgb = np.frombuffer(pts, np.uint8, 3, at + 32).copy()
+        err, m = struct.unpack_from("<dQ", pts, at + 35)
+        at += 51
+        track = np.frombuffer(pts, "<u4", 2 * m, at).reshape(m, 2).copy()
+        at += 8 * m
+        points[pid] = dict(xyz=xyz, rgb=rgb, error=err, image_ids=track[:, 0],
+                           point2D_idxs=track[:, 1])
+    return cameras, images, points
+
+
+def read_colmap_model(model_dir):
+    """read_colmap_model of csrc/host/colmap_io.cc: cameras / images / points3D of
+    a COLMAP model (.bin if all three are there, else .txt), checked by the C++
+    reader.  -> dict(binary, cameras={id: dict(model, width, height, params)},
+    images={id: dict(q (w, x, y, z), t, camera_id, name, xys (m, 2), point3D_ids
+    (m,), -1 for none)}, points3D={id: dict(xyz, rgb, error, image_ids,
+    point2D_idxs)})."""
+    lib = load()
+    sizes = (C.c_uint64 * 3)()
+    binary = C.c_int(0)
+    rc = lib.smvs_host_read_colmap_model(model_dir.encode(), None, C.c_size_t(0), sizes,
+                                         C.byref(binary))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    buf = np.zeros(max(sum(sizes), 1), np.uint8)
+    rc = lib.smvs_host_read_colmap_model(model_dir.encode(), buf.ctypes.data_as(_u8p),
+                                         C.c_size_t(buf.size), sizes, C.byref(binary))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    raw = buf.tobytes()
+    a, b = sizes[0], sizes[0] + sizes[1]
+    cameras, images, points = _unpack_colmap(raw[:a], raw[a:b], raw[b:b + sizes[2]])
+    return dict(binary=bool(binary.value), cameras=cameras, images=images, points3D=points)
+
+
+def import_colmap(model_dir, image_dir, scene_dir, zoom=1.0, device=None, out_size=None,
+                  container="png", threads=4, view_ids=None, overwrite=False):
+    """import_colmap of csrc/host/colmap_io.h: a COLMAP model and its images as
+    the MVE scene `scene_dir` (views/view_%04d.mve/{meta.ini, undistorted.png},
+    synth_0.out), every image resampled into a pinhole camera with a centred
+    principal point and out_focal = zoom * fx -- by the host form (device=None)
+    or by smvs_undistort_u8 on device k, the same bytes.  The images sorted by
+    IMAGE_ID are the views 0 .. n - 1; view_ids restricts the views written.
+    threads: host workers decode -> undistort -> encode, 1..16.  Returns the
+    report as a dict; views[i]["blank_pixels"] counts the output pixels that see
+    nothing of the source image (raise zoom to lose them)."""
+    lib = load()
+    if container not in ("png", "mvei"):
+        raise ValueError("import_colmap: container must be 'png' or 'mvei'")
+    ow, oh = (0, 0) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    st = ImportSettings(-1 if device is None else int(device), float(zoom), ow, oh,
+                        0 if container == "png" else 1, int(threads), 1 if overwrite else 0)
+    model = read_colmap_model(model_dir)
+    names = {i: v["name"] for i, v in model["images"].items()}
+    cap = max(len(names), 1)
+    ids = None if view_ids is None else np.asarray(view_ids, dtype=np.int32)
+    rep = ImportReport()
+    vid = np.zeros(cap, np.int32); iid = np.zeros(cap, np.uint32)
+    whc = np.zeros((cap, 3), np.int32); flen = np.zeros(cap, np.float32)
+    blank = np.zeros(cap, np.int64)
+    rc = lib.smvs_host_import_colmap(
+        model_dir.encode(), image_dir.encode(), scene_dir.encode(), C.byref(st),
+        ids.ctypes.data_as(_i32p) if ids is not None else None,
+        C.c_int(0 if ids is None else ids.size), C.byref(rep), C.c_int(cap),
+        vid.ctypes.data_as(_i32p), iid.ctypes.data_as(C.POINTER(C.c_uint32)),
+        whc.ctypes.data_as(_i32p), flen.ctypes.data_as(_fp),
+        blank.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    views = [dict(view_id=int(vid[i]), image_id=int(iid[i]), name=names[int(iid[i])],
+                  width=int(whc[i, 0]), height=int(whc[i, 1]), channels=int(whc[i, 2]),
+                  flen=float(flen[i]), blank_pixels=int(blank[i]))
+             for i in range(min(rep.views_written, cap))]
+    out = {k: getattr(rep, k) for k, _ in ImportReport._fields_}
+    out["views"] = views
+    return out
