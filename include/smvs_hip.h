@@ -1263,6 +1263,96 @@ int smvs_mesh_generate(int device, const smvs_point_view *views, int n_views,
     const smvs_mesh_options *options, smvs_points **handle,
     int64_t *n_vertices, int64_t *n_faces);
 
+/* Volumetric fusion of the depth maps into ONE surface mesh (not in the
+ * reference, opt-in): a truncated signed distance field
+ * averaged over all views on a voxel grid, and a surface-nets mesh of its zero
+ * level.  This comment is the definition; tests/tsdf_ref.py restates it in
+ * numpy and the device agrees with it to the bit.  All arithmetic is float with
+ * FMA contraction off, one operation per operation written here; dot3,
+ * world_point and the projection are those of the mesh export.
+ *
+ * Inputs.  views as smvs_mesh_generate takes them (ray-length depth, camera
+ * space normals, 1- or 3-channel colour image, a size per view; cut_depth is
+ * not written).  The preparation is the mesh export's (z-depth depth_z and,
+ * with cut_surfaces and n_views > 1, the cut map cut).  A view's depth at pixel
+ * p is D(p) = depth_z[p] where cut[p] != 0, else 0.  normals may be NULL only
+ * when cut_surfaces == 0.
+ *   trunc <= 0      means 3.0f * voxel_size
+ *   min_weight <= 0 means 1
+ *
+ * Field.  Voxel (i, j, k), x fastest in every array, has the centre
+ * c[a] = origin[a] + ((float)idx[a] + 0.5f) * voxel_size.  For the views in
+ * list order:
+ *   1. proj = KR c - t (three dot3, as the cut computes them)
+ *   2. skip the view if proj[2] <= 0
+ *   3. u = proj[0] / proj[2], v = proj[1] / proj[2]; skip if u < 0 or v < 0
+ *   4. xj = (int)u, yj = (int)v; skip if xj >= width or yj >= height
+ *   5. skip if D(xj, yj) == 0
+ *   6. sdf = D - proj[2]; skip if sdf < -trunc
+ *   7. S += fminf(1.0f, sdf / trunc); W += 1 (uint32)
+ *   8. if sdf <= trunc: R, G, B (uint32) += the pixel's bytes (grey: all
+ *      three the one byte; 3 or 4 channels: bytes 0..2), C += 1
+ * F = S / (float)W where W >= min_weight, else NaN ("unknown").
+ *
+ * Vertices (surface nets).  Cell (i, j, k), 0 <= idx[a] <= dims[a] - 2, has
+ * the corners c = dx + 2 dy + 4 dz.  It is complete when no corner is NaN; a
+ * corner is inside when F < 0.0f; the cell is active when it is complete and
+ * its corners are not all on one side.  Edges, in this order: x (0,1) (2,3)
+ * (4,5) (6,7), y (0,2) (1,3) (4,6) (5,7), z (0,4) (1,5) (2,6) (3,7).  For each
+ * edge (a, b) with exactly one inside end: t = Fa / (Fa - Fb), the crossing is
+ * corner a's centre with t * voxel_size added along the edge's axis.
+ *   position    per coordinate the sum of the m crossings in edge order,
+ *               starting from 0.0f, divided by (float)m
+ *   normal      g[0] = the sum over the four x edges in order, starting from
+ *               0.0f, of (Fb - Fa), g[1], g[2] likewise over the y and z edges;
+ *               len = sqrtf(dot3(g, g)); g / len, or zero when len == 0.  It
+ *               points from inside to outside
+ *   colour      per channel, with Rs and Cs the sums of R and C over the 8
+ *               corners: (2 Rs + Cs) / (2 Cs) in integer division, 0 when Cs == 0
+ *   confidence  (float)(sum of W over the 8 corners) / (float)(8 n_views)
+ * Vertex ids are the rank of the active cell in the linear cell index.
+ *
+ * Faces.  For the grid points P in linear order and for each the axes
+ * a = 0, 1, 2 in turn: the edge from P to P + e_a, both ends known and exactly
+ * one inside.  With (a, b, c) cyclic the edge is shared by the cells at the
+ * (b, c) offsets (-1,-1) (0,-1) (0,0) (-1,0) from P: v0 .. v3.  The quad exists
+ * only when all four lie in the grid and are complete (they are then active).
+ * P inside: triangles (v0, v1, v2) (v0, v2, v3), else (v0, v2, v1)
+ * (v0, v3, v2).  Faces are counter-clockwise seen from outside (the side of
+ * F >= 0, the cameras' side), so the face normals agree with the vertex
+ * normals.  Where the field is unknown the mesh is open.
+ *
+ * Refused with SMVS_ERR_INVALID before any device call: n_views < 1 (or
+ * > 4096), a voxel_size that is not a positive finite number, a dim < 2 or
+ * > 1024, a volume of more than 2^27 voxels (28 bytes of device state per
+ * voxel: 3.5 GiB), a non-finite origin or trunc, cut_surfaces with a view's
+ * normals missing, a missing depth map or image.  No vertex is not an error:
+ * the handle then has 0 points and 0 faces.
+ *
+ * tsdf / weight (either may be NULL): the whole volume, dims[0] * dims[1] *
+ * dims[2] values, NaN = unknown.  The handle is a mesh handle (faces always,
+ * no values), read with smvs_points_info / smvs_points_download and freed with
+ * smvs_points_release. */
+typedef struct {
+    int cut_surfaces;
+    float origin[3];      /* the low corner of voxel (0, 0, 0) */
+    float voxel_size;
+    int dims[3];
+    float trunc;
+    int min_weight;
+} smvs_tsdf_options;
+
+int smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
+    const smvs_tsdf_options *options, float *tsdf, uint32_t *weight,
+    smvs_points **handle, int64_t *n_vertices, int64_t *n_faces);
+
+/* The componentwise minimum and maximum of world_point over the valid
+ * (non-zero) pixels of the maps smvs_tsdf_fuse would fuse: the cut maps with
+ * cut_surfaces and n_views > 1, else the depth maps (image and channels are not
+ * read).  lo[r] > hi[r] (+inf, -inf) means no valid pixel. */
+int smvs_tsdf_bounds(int device, const smvs_point_view *views, int n_views,
+    int cut_surfaces, float *lo, float *hi);
+
 /* smvsrecon --simplify (MeshGenerator::Options::simplify, mesh_generator.cc:
  * 238-243): per view DepthTriangulator::approximate_triangulation
  * (depth_triangulator.cc:27-172) -- Garland and Heckbert's greedy insertion

@@ -43,6 +43,13 @@ class LoopStats(C.Structure):
                 ("nan_break", C.c_int)]
 
 
+class TsdfOptions(C.Structure):
+    """smvs_tsdf_options of include/smvs_hip.h."""
+    _fields_ = [("cut_surfaces", C.c_int), ("origin", C.c_float * 3),
+                ("voxel_size", C.c_float), ("dims", C.c_int * 3),
+                ("trunc", C.c_float), ("min_weight", C.c_int)]
+
+
 K_NAMES = ["patch", "assemble", "cg_spmv", "cg_update", "cg_init",
            "reactivate", "misc", "cg_resident"]
 

@@ -559,6 +559,24 @@ int smvs_host_generate_simplified(const char *scene_dir,
     const smvs_host_point_cloud_settings *settings, const int *view_ids,
     int n_view_ids, char *ply_path, int ply_path_capacity, int64_t *n_vertices,
     int64_t *n_faces);
+/* Not in the reference: the views' depth maps fused into ONE surface mesh
+ * (smvs_tsdf_fuse), <scene>/smvs-fused-{B,S}
+ * <input_scale>.ply through save_ply_mesh; no smvs-cut is written.  The
+ * settings are the point cloud's (create_triangle_mesh and simplify are
+ * ignored); with use_aabb the box is [aabb_min, aabb_max], else
+ * smvs_tsdf_bounds padded by the truncation distance.  voxel_size <= 0: the
+ * box's longest side / resolution; trunc <= 0: 3 voxels; min_weight <= 0: 1.
+ * dims[a] = max(2, (int)ceilf((hi[a] - lo[a]) / voxel_size)). */
+typedef struct {
+    float voxel_size;
+    int resolution;
+    float trunc;
+    int min_weight;
+} smvs_host_fused_settings;
+int smvs_host_generate_fused(const char *scene_dir,
+    const smvs_host_point_cloud_settings *settings, const smvs_host_fused_settings *fused,
+    const int *view_ids, int n_view_ids, char *ply_path, int ply_path_capacity,
+    int64_t *n_vertices, int64_t *n_faces);
 /* save_ply_mesh: the PLY writer of the triangle mesh from SoA
  * buffers (xyz, normals n*3 floats; rgb n*3 bytes; confidence n floats;
  * faces m*3 vertex ids < n). */

@@ -1,6 +1,7 @@
 #include "mesh_generator.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -204,6 +205,77 @@ MeshGenerator::generate_simplified(std::vector<SceneView> const& inputviews,
     smvs_points_release(handle);
     check_status(rc, "smvs_points_download");
     save_cut_maps(in);
+}
+
+TriangleMesh::Ptr
+MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
+    std::string const& image_name, std::string const& dm_name, FusedOptions const& fused)
+{
+    Inputs in;
+    load_views(inputviews, image_name, dm_name, in);
+    TriangleMesh::Ptr mesh(new TriangleMesh);
+    if (in.views.empty())
+        return mesh;
+    if (fused.voxel_size <= 0.0f && fused.resolution < 8)
+        throw std::invalid_argument("generate_fused: resolution must be at least 8");
+    int const n = (int)in.pv.size();
+    float lo[3], hi[3];
+    if (opts.use_aabb) {
+        std::copy(opts.aabb_min, opts.aabb_min + 3, lo);
+        std::copy(opts.aabb_max, opts.aabb_max + 3, hi);
+    } else {
+        check_status(smvs_tsdf_bounds(opts.device, in.pv.data(), n,
+            opts.cut_surfaces ? 1 : 0, lo, hi), "smvs_tsdf_bounds");
+    }
+    for (int a = 0; a < 3; ++a)
+        if (!(lo[a] <= hi[a]))
+            throw std::invalid_argument(opts.use_aabb
+                ? "generate_fused: the box is empty"
+                : "generate_fused: the depth maps hold no valid pixel");
+    auto longest = [&]() {
+        return std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+    };
+    float voxel = fused.voxel_size;
+    if (!opts.use_aabb) {
+        // the bounds are padded by the truncation distance; where that is 3
+        // voxels of a voxel size that follows from the padded box:
+        // voxel = (side + 6 voxel) / resolution
+        float pad = fused.trunc;
+        if (pad <= 0.0f) {
+            if (voxel <= 0.0f)
+                voxel = longest() / (float)(fused.resolution - 6);
+            pad = 3.0f * voxel;
+        }
+        for (int a = 0; a < 3; ++a) {
+            lo[a] -= pad;
+            hi[a] += pad;
+        }
+    }
+    if (voxel <= 0.0f)
+        voxel = longest() / (float)fused.resolution;
+    smvs_tsdf_options to;
+    to.cut_surfaces = opts.cut_surfaces ? 1 : 0;
+    to.voxel_size = voxel;
+    to.trunc = fused.trunc;
+    to.min_weight = fused.min_weight;
+    for (int a = 0; a < 3; ++a) {
+        to.origin[a] = lo[a];
+        to.dims[a] = std::max(2, (int)std::ceil((hi[a] - lo[a]) / voxel));
+    }
+    smvs_points* handle = nullptr;
+    int64_t nv = 0, nf = 0;
+    check_status(smvs_tsdf_fuse(opts.device, in.pv.data(), n, &to, nullptr, nullptr, &handle,
+        &nv, &nf), "smvs_tsdf_fuse");
+    mesh->xyz.resize(3 * (std::size_t)nv);
+    mesh->normals.resize(3 * (std::size_t)nv);
+    mesh->colors.resize(3 * (std::size_t)nv);
+    mesh->confidences.resize((std::size_t)nv);
+    mesh->faces.resize(3 * (std::size_t)nf);
+    int const rc = smvs_points_download(handle, mesh->xyz.data(), mesh->normals.data(),
+        mesh->colors.data(), mesh->confidences.data(), nullptr, mesh->faces.data());
+    smvs_points_release(handle);
+    check_status(rc, "smvs_points_download");
+    return mesh;
 }
 
 void
@@ -425,6 +497,23 @@ generate_scene_simplified(std::string const& scene_path, PointCloudSettings cons
         *n_vertices = nv;
     if (n_faces != nullptr)
         *n_faces = nf;
+    return meshname;
+}
+
+std::string
+generate_scene_fused(std::string const& scene_path, PointCloudSettings const& conf,
+    MeshGenerator::FusedOptions const& fused, std::size_t* n_vertices, std::size_t* n_faces)
+{
+    SceneInputs const in = scene_inputs(scene_path, conf);
+    MeshGenerator meshgen(generator_options(conf));
+    TriangleMesh::Ptr mesh = meshgen.generate_fused(in.views, in.input_name, in.dm_name, fused);
+    std::string const meshname = in.scene->get_path() + "/smvs-fused-"
+        + (conf.use_shading ? "S" : "B") + std::to_string(conf.input_scale) + ".ply";
+    save_ply_mesh(meshname, *mesh);
+    if (n_vertices != nullptr)
+        *n_vertices = mesh->size();
+    if (n_faces != nullptr)
+        *n_faces = mesh->num_faces();
     return meshname;
 }
 

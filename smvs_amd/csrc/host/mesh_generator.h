@@ -76,6 +76,22 @@ public:
         bool create_triangle_mesh, PointCloud* points, TriangleMesh* mesh,
         int max_vertices = -1, double max_error = -1.0);
 
+    // Not in the reference: the views' depth maps fused into ONE surface mesh
+    // on smvs_tsdf_fuse.  The box is [aabb_min,
+    // aabb_max] with use_aabb, else smvs_tsdf_bounds padded by the truncation
+    // distance; dims[a] = max(2, (int)ceilf((hi[a] - lo[a]) / voxel_size)).
+    // No smvs-cut is written.
+    struct FusedOptions
+    {
+        float voxel_size = 0.0f;    // <= 0: the box's longest side / resolution
+        int resolution = 256;
+        float trunc = 0.0f;         // <= 0: 3 voxels
+        int min_weight = 0;         // <= 0: 1
+    };
+    TriangleMesh::Ptr generate_fused(std::vector<SceneView> const& views,
+        std::string const& image_name, std::string const& dm_name,
+        FusedOptions const& fused);
+
 private:
     struct Inputs;
     // loads the usable views' maps and images into the device's view records
@@ -131,5 +147,12 @@ std::string generate_scene_mesh(std::string const& scene_path,
 std::string generate_scene_simplified(std::string const& scene_path,
     PointCloudSettings const& settings, std::size_t* n_vertices = nullptr,
     std::size_t* n_faces = nullptr);
+
+// not in the reference: MeshGenerator::generate_fused over the scene's views,
+// <scene>/smvs-fused-{B,S}<input_scale>.ply through save_ply_mesh; the box is
+// the settings' AABB when use_aabb is set; -> the file written
+std::string generate_scene_fused(std::string const& scene_path,
+    PointCloudSettings const& settings, MeshGenerator::FusedOptions const& fused,
+    std::size_t* n_vertices = nullptr, std::size_t* n_faces = nullptr);
 
 } // namespace smvs_amd

@@ -1,4 +1,4 @@
-// Pieces of mesh.hip that simplify.hip uses as well: the per-view camera record
+// Pieces of mesh.hip that simplify.hip and tsdf.hip use as well: the per-view camera record
 // with the cut's prepare / cut launches, the 64-bit exclusive scan, the AABB
 // test, recalc_normals' face term and the result handle.
 #pragma once

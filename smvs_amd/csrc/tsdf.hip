@@ -1,0 +1,760 @@
+// Volumetric fusion of the depth maps into one surface mesh on gfx950
+// (not in the reference, opt-in).  The normative
+// definition is the comment of smvs_tsdf_fuse in include/smvs_hip.h, restated
+// in numpy by tests/tsdf_ref.py; every step below names the paragraph it
+// implements.
+//
+// The views are prepared exactly as the mesh export prepares them
+// (mesh_prepare_kernel, mesh_cut_kernel through launch_prepare_and_cut), then
+//   depth      per pixel: D = depth_z where the cut map is non-zero, else 0
+//   integrate  one lane per voxel walks the views in list order with the
+//              voxel's sums in registers; the volume is written once
+//   classify   per block of 256 grid points: active cells | quads << 32
+//   scan       mesh.hip's exclusive_scan over the blocks
+//   vertices   one surface-nets vertex per active cell, with its attributes,
+//              and the cell -> vertex id map
+//   faces      two triangles per quad through that map
+// Arithmetic: float, FMA contraction off, term by term as mesh.hip writes it.
+// No atomics: every order is an index order (vertex ids and face positions
+// come from the scan and a scan inside each block).
+#include "common.h"
+#include "mesh_shared.h"
+
+#include <cmath>
+#include <vector>
+
+namespace smvs_hip {
+
+struct TsdfGrid {
+    int nx, ny, nz;
+    float origin[3];
+    float voxel_size, trunc;
+    uint32_t min_weight;
+    int n_views;
+};
+
+struct TsdfImageDev {
+    const uint8_t *image;   // w * h * channels
+    int channels;
+};
+
+__device__ __forceinline__ bool
+tsdf_pixel(const MeshViewDev *views, int &v, int &x, int &y, size_t &p)
+{
+    v = blockIdx.y;
+    MeshViewDev const &V = views[v];
+    size_t const local = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (local >= (size_t)V.w * V.h)
+        return false;
+    x = (int)(local % V.w);
+    y = (int)(local / V.w);
+    p = local;
+    return true;
+}
+
+// Inputs: D(p) = depth_z[p] where cut[p] != 0, else 0 (in place in depth_z,
+// which nothing else reads after the cut)
+__global__ void __launch_bounds__(256)
+tsdf_depth_kernel(const MeshViewDev *__restrict__ views)
+{
+    int v, x, y;
+    size_t p;
+    if (!tsdf_pixel(views, v, x, y, p))
+        return;
+    if (views[v].cut[p] == 0.0f)
+        views[v].depth_z[p] = 0.0f;
+}
+
+// the centre of voxel (or grid point) idx along one axis
+__device__ __forceinline__ float
+tsdf_centre(TsdfGrid const &G, int axis, int idx)
+{
+#pragma clang fp contract(off)
+    return G.origin[axis] + ((float)idx + 0.5f) * G.voxel_size;
+}
+
+// Field, steps 1-8 and the division after the loop.  A block is a brick of
+// 8 x 8 x 4 voxels (a wave is one 8 x 8 slab of it), so that the 64 gathers of
+// a wave land in a small patch of each depth map.
+constexpr int TSDF_BX = 8, TSDF_BY = 8, TSDF_BZ = 4;
+
+__global__ void __launch_bounds__(256)
+tsdf_integrate_kernel(const MeshViewDev *__restrict__ views,
+    const TsdfImageDev *__restrict__ images, TsdfGrid G, float *__restrict__ tsdf,
+    uint32_t *__restrict__ weight, uint4 *__restrict__ colour)
+{
+#pragma clang fp contract(off)
+    int const bricks_x = (G.nx + TSDF_BX - 1) / TSDF_BX;
+    int const bricks_y = (G.ny + TSDF_BY - 1) / TSDF_BY;
+    int const brick = blockIdx.x;
+    int const i = (brick % bricks_x) * TSDF_BX + (threadIdx.x & 7);
+    int const j = (brick / bricks_x % bricks_y) * TSDF_BY + (threadIdx.x >> 3 & 7);
+    int const k = (brick / bricks_x / bricks_y) * TSDF_BZ + (threadIdx.x >> 6);
+    if (i >= G.nx || j >= G.ny || k >= G.nz)
+        return;
+    float const c[3] = { tsdf_centre(G, 0, i), tsdf_centre(G, 1, j), tsdf_centre(G, 2, k) };
+    float S = 0.0f;
+    uint32_t W = 0, R = 0, Gr = 0, B = 0, C = 0;
+    for (int v = 0; v < G.n_views; ++v) {
+        MeshViewDev const &V = views[v];
+        float proj[3];
+        proj[0] = dot3(V.KR + 0, c) - V.t[0];
+        proj[1] = dot3(V.KR + 3, c) - V.t[1];
+        proj[2] = dot3(V.KR + 6, c) - V.t[2];
+        if (proj[2] <= 0.0f)
+            continue;
+        float const u = proj[0] / proj[2];
+        float const w = proj[1] / proj[2];
+        if (u < 0.0f || w < 0.0f)
+            continue;
+        int const xj = (int)u;
+        int const yj = (int)w;
+        if (xj >= V.w || yj >= V.h)
+            continue;
+        size_t const pj = (size_t)yj * V.w + xj;
+        float const D = V.depth_z[pj];
+        if (D == 0.0f)
+            continue;
+        float const sdf = D - proj[2];
+        if (sdf < -G.trunc)
+            continue;
+        S += fminf(1.0f, sdf / G.trunc);
+        W += 1;
+        if (sdf <= G.trunc) {
+            int const ch = images[v].channels;
+            const uint8_t *px = images[v].image + pj * ch;
+            uint32_t const g = px[0];
+            R += g;
+            Gr += ch >= 3 ? px[1] : g;
+            B += ch >= 3 ? px[2] : g;
+            C += 1;
+        }
+    }
+    size_t const at = ((size_t)k * G.ny + j) * G.nx + i;
+    tsdf[at] = W >= G.min_weight ? S / (float)W : __builtin_nanf("");
+    weight[at] = W;
+    colour[at] = make_uint4(R, Gr, B, C);
+}
+
+// ----------------------------------------------------------------- extraction
+// Cells and grid points share the points' linear index (x fastest): cell
+// (i, j, k) is the one whose corner 0 is point (i, j, k).
+
+__device__ __forceinline__ bool
+tsdf_point(TsdfGrid const &G, size_t &lin, int &i, int &j, int &k)
+{
+    lin = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (lin >= (size_t)G.nx * G.ny * G.nz)
+        return false;
+    i = (int)(lin % G.nx);
+    j = (int)(lin / G.nx % G.ny);
+    k = (int)(lin / G.nx / G.ny);
+    return true;
+}
+
+__device__ __forceinline__ size_t
+tsdf_index(TsdfGrid const &G, int i, int j, int k)
+{
+    return ((size_t)k * G.ny + j) * G.nx + i;
+}
+
+// the cell's corners c = dx + 2 dy + 4 dz; -> complete (in the grid, no NaN)
+__device__ __forceinline__ bool
+tsdf_cell(const float *__restrict__ tsdf, TsdfGrid const &G, int i, int j, int k, float *f)
+{
+    if (i < 0 || j < 0 || k < 0 || i > G.nx - 2 || j > G.ny - 2 || k > G.nz - 2)
+        return false;
+    bool complete = true;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        f[c] = tsdf[tsdf_index(G, i + (c & 1), j + (c >> 1 & 1), k + (c >> 2))];
+        complete = complete && !(f[c] != f[c]);
+    }
+    return complete;
+}
+
+__device__ __forceinline__ bool
+tsdf_cell_active(const float *__restrict__ tsdf, TsdfGrid const &G, int i, int j, int k,
+    float *f)
+{
+    if (!tsdf_cell(tsdf, G, i, j, k, f))
+        return false;
+    int inside = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+        inside += f[c] < 0.0f;
+    return inside != 0 && inside != 8;
+}
+
+// the four cells around the edge from point (i, j, k) along axis a, as (b, c)
+// offsets with (a, b, c) cyclic: (-1,-1) (0,-1) (0,0) (-1,0)
+__device__ __forceinline__ void
+tsdf_quad_cell(int a, int q, int i, int j, int k, int *cell)
+{
+    int const ob = (q == 1 || q == 2) ? 0 : -1;
+    int const oc = (q == 2 || q == 3) ? 0 : -1;
+    int off[3] = { 0, 0, 0 };
+    off[(a + 1) % 3] = ob;
+    off[(a + 2) % 3] = oc;
+    cell[0] = i + off[0];
+    cell[1] = j + off[1];
+    cell[2] = k + off[2];
+}
+
+// Faces: bit a set when the edge along axis a has a quad; bit 3: P is inside
+__device__ __forceinline__ int
+tsdf_quads(const float *__restrict__ tsdf, TsdfGrid const &G, int i, int j, int k)
+{
+    int const n[3] = { G.nx, G.ny, G.nz };
+    int const p[3] = { i, j, k };
+    float const fa = tsdf[tsdf_index(G, i, j, k)];
+    if (fa != fa)
+        return 0;
+    int mask = fa < 0.0f ? 8 : 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (p[a] > n[a] - 2)
+            continue;
+        float const fb = tsdf[tsdf_index(G, i + (a == 0), j + (a == 1), k + (a == 2))];
+        if (fb != fb || (fa < 0.0f) == (fb < 0.0f))
+            continue;
+        bool all = true;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (!all)
+                break;
+            int cell[3];
+            float f[8];
+            tsdf_quad_cell(a, q, i, j, k, cell);
+            all = tsdf_cell(tsdf, G, cell[0], cell[1], cell[2], f);
+        }
+        if (all)
+            mask |= 1 << a;
+    }
+    return mask;
+}
+
+// exclusive scan of one 32-bit value per thread over the block of 256 and the
+// block's total; every thread of the block calls it
+__device__ __forceinline__ uint32_t
+tsdf_block_scan(uint32_t v, uint32_t *total)
+{
+    __shared__ uint32_t wsum[4];
+    int const lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        uint32_t const t = __shfl_up(inc, o, 64);
+        if (lane >= o)
+            inc += t;
+    }
+    if (lane == 63)
+        wsum[wave] = inc;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        pre += w < wave ? wsum[w] : 0u;
+        tot += wsum[w];
+    }
+    __syncthreads();
+    *total = tot;
+    return pre + inc - v;
+}
+
+// per thread: active cell (0 / 1) | quads (0..3) << 16, each where asked for
+template <bool CELLS, bool QUADS>
+__device__ __forceinline__ uint32_t
+tsdf_classify(const float *__restrict__ tsdf, TsdfGrid const &G, bool valid, int i, int j,
+    int k, float *f, bool *active, int *quads)
+{
+    *active = false;
+    *quads = 0;
+    if (!valid)
+        return 0;
+    if constexpr (CELLS)
+        *active = tsdf_cell_active(tsdf, G, i, j, k, f);
+    if constexpr (QUADS)
+        *quads = tsdf_quads(tsdf, G, i, j, k);
+    return (uint32_t)*active | (uint32_t)__popc(*quads & 7) << 16;
+}
+
+__global__ void __launch_bounds__(256)
+tsdf_classify_kernel(const float *__restrict__ tsdf, TsdfGrid G,
+    unsigned long long *__restrict__ counts)
+{
+    size_t lin;
+    int i = 0, j = 0, k = 0, quads;
+    bool active;
+    float f[8];
+    bool const valid = tsdf_point(G, lin, i, j, k);
+    uint32_t const mine = tsdf_classify<true, true>(tsdf, G, valid, i, j, k, f, &active, &quads);
+    uint32_t total;
+    (void)tsdf_block_scan(mine, &total);
+    if (threadIdx.x == 0)
+        counts[blockIdx.x] = (unsigned long long)(total & 0xffffu)
+            | (unsigned long long)(total >> 16) << 32;
+}
+
+struct TsdfOut {
+    float *xyz, *nrm, *conf;
+    uint8_t *rgb;
+    uint32_t *faces;
+};
+
+// Vertices: position, normal, colour, confidence of every active cell, at the
+// cell's rank; vid[cell] = that rank
+__global__ void __launch_bounds__(256)
+tsdf_vertex_kernel(const float *__restrict__ tsdf, const uint32_t *__restrict__ weight,
+    const uint4 *__restrict__ colour, TsdfGrid G,
+    const unsigned long long *__restrict__ counts, uint32_t *__restrict__ vid, TsdfOut O)
+{
+#pragma clang fp contract(off)
+    size_t lin;
+    int i = 0, j = 0, k = 0, quads;
+    bool active;
+    float f[8];
+    bool const valid = tsdf_point(G, lin, i, j, k);
+    uint32_t const mine = tsdf_classify<true, false>(tsdf, G, valid, i, j, k, f, &active, &quads);
+    uint32_t total;
+    uint32_t const before = tsdf_block_scan(mine, &total);
+    if (!active)
+        return;
+    size_t const id = (size_t)(uint32_t)counts[blockIdx.x] + (before & 0xffffu);
+    vid[lin] = (uint32_t)id;
+    // edges in the definition's order: x (0,1) (2,3) (4,5) (6,7), y (0,2) (1,3)
+    // (4,6) (5,7), z (0,4) (1,5) (2,6) (3,7)
+    int const cell[3] = { i, j, k };
+    float sum[3] = { 0.0f, 0.0f, 0.0f }, g[3] = { 0.0f, 0.0f, 0.0f };
+    int m = 0;
+#pragma unroll
+    for (int axis = 0; axis < 3; ++axis) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            // the two axes other than `axis`, lower first, carry e's bits
+            int const lo_axis = axis == 0 ? 1 : 0, hi_axis = axis == 2 ? 1 : 2;
+            int const a = (e & 1) << lo_axis | (e >> 1) << hi_axis;
+            int const b = a | 1 << axis;
+            g[axis] += f[b] - f[a];
+            if ((f[a] < 0.0f) == (f[b] < 0.0f))
+                continue;
+            float const t = f[a] / (f[a] - f[b]);
+            float q[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+                q[r] = tsdf_centre(G, r, cell[r] + (a >> r & 1));
+            q[axis] = q[axis] + t * G.voxel_size;
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+                sum[r] += q[r];
+            ++m;
+        }
+    }
+    for (int r = 0; r < 3; ++r)
+        O.xyz[3 * id + r] = sum[r] / (float)m;
+    float const len = sqrtf(dot3(g, g));
+    for (int r = 0; r < 3; ++r)
+        O.nrm[3 * id + r] = len == 0.0f ? 0.0f : g[r] / len;
+    uint32_t Rs = 0, Gs = 0, Bs = 0, Cs = 0, Ws = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        size_t const at = tsdf_index(G, i + (c & 1), j + (c >> 1 & 1), k + (c >> 2));
+        uint4 const col = colour[at];
+        Rs += col.x;
+        Gs += col.y;
+        Bs += col.z;
+        Cs += col.w;
+        Ws += weight[at];
+    }
+    O.rgb[3 * id + 0] = Cs == 0 ? 0 : (uint8_t)((2 * Rs + Cs) / (2 * Cs));
+    O.rgb[3 * id + 1] = Cs == 0 ? 0 : (uint8_t)((2 * Gs + Cs) / (2 * Cs));
+    O.rgb[3 * id + 2] = Cs == 0 ? 0 : (uint8_t)((2 * Bs + Cs) / (2 * Cs));
+    O.conf[id] = (float)Ws / (float)(8 * G.n_views);
+}
+
+// Faces: the quads of every grid point in linear order, axes 0, 1, 2 in turn,
+// two triangles each, counter-clockwise seen from outside
+__global__ void __launch_bounds__(256)
+tsdf_face_kernel(const float *__restrict__ tsdf, TsdfGrid G,
+    const unsigned long long *__restrict__ counts, const uint32_t *__restrict__ vid,
+    TsdfOut O)
+{
+    size_t lin;
+    int i = 0, j = 0, k = 0, quads;
+    bool active;
+    float f[8];
+    bool const valid = tsdf_point(G, lin, i, j, k);
+    uint32_t const mine = tsdf_classify<false, true>(tsdf, G, valid, i, j, k, f, &active, &quads);
+    uint32_t total;
+    uint32_t const before = tsdf_block_scan(mine, &total);
+    if ((quads & 7) == 0)
+        return;
+    size_t quad = (size_t)(counts[blockIdx.x] >> 32) + (before >> 16);
+    bool const inside = (quads & 8) != 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (!(quads >> a & 1))
+            continue;
+        uint32_t v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            int cell[3];
+            tsdf_quad_cell(a, q, i, j, k, cell);
+            v[q] = vid[tsdf_index(G, cell[0], cell[1], cell[2])];
+        }
+        uint32_t *out = O.faces + 6 * quad;
+        out[0] = v[0];
+        out[1] = inside ? v[1] : v[2];
+        out[2] = inside ? v[2] : v[1];
+        out[3] = v[0];
+        out[4] = inside ? v[2] : v[3];
+        out[5] = inside ? v[3] : v[2];
+        ++quad;
+    }
+}
+
+// --------------------------------------------------------------------- bounds
+// min and max of world_point over the valid pixels of the (cut) maps: per
+// block, then one block over the blocks' results.  Exact, so no order matters.
+__device__ __forceinline__ void
+tsdf_block_minmax(float *lo, float *hi, float *out)
+{
+    __shared__ float part[4][6];
+    int const lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo[r] = fminf(lo[r], __shfl_xor(lo[r], o, 64));
+            hi[r] = fmaxf(hi[r], __shfl_xor(hi[r], o, 64));
+        }
+    if (lane == 0)
+        for (int r = 0; r < 3; ++r) {
+            part[wave][r] = lo[r];
+            part[wave][3 + r] = hi[r];
+        }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        float v = part[0][threadIdx.x];
+        for (int w = 1; w < 4; ++w)
+            v = threadIdx.x < 3 ? fminf(v, part[w][threadIdx.x])
+                                : fmaxf(v, part[w][threadIdx.x]);
+        out[threadIdx.x] = v;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+tsdf_bounds_kernel(const MeshViewDev *__restrict__ views, float *__restrict__ partial)
+{
+    float const inf = __builtin_huge_valf();
+    float lo[3] = { inf, inf, inf }, hi[3] = { -inf, -inf, -inf };
+    int v, x, y;
+    size_t p;
+    if (tsdf_pixel(views, v, x, y, p)) {
+        float const d = views[v].cut[p];
+        if (d != 0.0f) {
+            float pos[3];
+            world_point(views[v], x, y, d, pos);
+            for (int r = 0; r < 3; ++r)
+                lo[r] = hi[r] = pos[r];
+        }
+    }
+    tsdf_block_minmax(lo, hi, partial + 6 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x));
+}
+
+__global__ void __launch_bounds__(256)
+tsdf_bounds_final_kernel(const float *__restrict__ partial, size_t n, float *__restrict__ out)
+{
+    float const inf = __builtin_huge_valf();
+    float lo[3] = { inf, inf, inf }, hi[3] = { -inf, -inf, -inf };
+    for (size_t b = threadIdx.x; b < n; b += 256)
+        for (int r = 0; r < 3; ++r) {
+            lo[r] = fminf(lo[r], partial[6 * b + r]);
+            hi[r] = fmaxf(hi[r], partial[6 * b + 3 + r]);
+        }
+    tsdf_block_minmax(lo, hi, out);
+}
+
+} // namespace smvs_hip
+
+using namespace smvs_hip;
+
+namespace {
+
+constexpr size_t TSDF_MAX_VOXELS = (size_t)1 << 27;
+
+struct Carver {
+    size_t total = 0;
+    size_t operator()(size_t bytes)
+    {
+        size_t const at = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return at;
+    }
+};
+
+// the views' maps and tables in the workspace slab, as the mesh export lays
+// them out; images only where the caller fuses
+struct ViewSlab {
+    std::vector<size_t> offsets;   // per view: depth_z, depth_ray, cut, normals, image
+    size_t table_at = 0, images_at = 0, max_pix = 0;
+    std::vector<MeshViewDev> table;
+    std::vector<TsdfImageDev> images;
+    MeshViewDev *d_table = nullptr;
+    TsdfImageDev *d_images = nullptr;
+};
+
+// argument checks shared by the two entries (before any device call)
+int
+check_views(const smvs_point_view *views, int n_views, int cut, bool want_images)
+{
+    SMVS_REQUIRE(views != nullptr && n_views >= 1, "no views");
+    SMVS_REQUIRE(n_views <= 4096, "too many views");
+    size_t total_pix = 0;
+    for (int i = 0; i < n_views; ++i) {
+        smvs_point_view const &in = views[i];
+        SMVS_REQUIRE(in.width > 0 && in.height > 0 && in.depth != nullptr
+            && in.flen > 0.0f, "bad view");
+        SMVS_REQUIRE(!want_images || (in.image != nullptr && in.channels >= 1
+            && in.channels <= 4), "bad view image");
+        SMVS_REQUIRE(!(cut && in.normals == nullptr),
+            "the cut needs the normal maps");
+        total_pix += (size_t)in.width * in.height;
+    }
+    SMVS_REQUIRE(total_pix < ((size_t)1 << 31), "too many pixels");
+    return SMVS_OK;
+}
+
+void
+carve_views(const smvs_point_view *views, int n_views, bool want_images, Carver &carve,
+    ViewSlab &s)
+{
+    s.offsets.resize((size_t)n_views * 5);
+    for (int i = 0; i < n_views; ++i) {
+        size_t const npix = (size_t)views[i].width * views[i].height;
+        s.max_pix = npix > s.max_pix ? npix : s.max_pix;
+        s.offsets[5 * i + 0] = carve(sizeof(float) * npix);       // depth_z
+        s.offsets[5 * i + 1] = carve(sizeof(float) * npix);       // depth_ray
+        s.offsets[5 * i + 2] = carve(sizeof(float) * npix);       // cut
+        s.offsets[5 * i + 3] = carve(sizeof(float) * 3 * npix);   // normals
+        s.offsets[5 * i + 4] = want_images ? carve(npix * views[i].channels) : 0;
+    }
+    s.table_at = carve(sizeof(MeshViewDev) * n_views);
+    s.images_at = carve(sizeof(TsdfImageDev) * n_views);
+}
+
+// uploads the views and runs the mesh path's preparation (and cut)
+int
+upload_and_prepare(Workspace &ws, char *slab, const smvs_point_view *views, int n_views,
+    bool cut, bool want_images, ViewSlab &s)
+{
+    int rc;
+    s.table.resize(n_views);
+    s.images.resize(n_views);
+    for (int i = 0; i < n_views; ++i) {
+        smvs_point_view const &in = views[i];
+        MeshViewDev &V = s.table[i];
+        fill_view_camera(in.width, in.height, in.flen, in.rot, in.trans, V);
+        size_t const npix = (size_t)in.width * in.height;
+        V.depth_z = reinterpret_cast<float *>(slab + s.offsets[5 * i + 0]);
+        V.depth_ray = reinterpret_cast<float *>(slab + s.offsets[5 * i + 1]);
+        V.cut = reinterpret_cast<float *>(slab + s.offsets[5 * i + 2]);
+        V.normals = reinterpret_cast<float *>(slab + s.offsets[5 * i + 3]);
+        if ((rc = ws.upload(V.depth_ray, in.depth, sizeof(float) * npix)))
+            return rc;
+        // without normals (cut off only) the preparation turns zeros
+        if (in.normals != nullptr) {
+            if ((rc = ws.upload(V.normals, in.normals, sizeof(float) * 3 * npix)))
+                return rc;
+        } else
+            SMVS_HIP_CHECK(hipMemsetAsync(V.normals, 0, sizeof(float) * 3 * npix,
+                ws.stream));
+        s.images[i].image = nullptr;
+        s.images[i].channels = in.channels;
+        if (want_images) {
+            uint8_t *img = reinterpret_cast<uint8_t *>(slab + s.offsets[5 * i + 4]);
+            s.images[i].image = img;
+            if ((rc = ws.upload(img, in.image, npix * in.channels)))
+                return rc;
+        }
+    }
+    s.d_table = reinterpret_cast<MeshViewDev *>(slab + s.table_at);
+    s.d_images = reinterpret_cast<TsdfImageDev *>(slab + s.images_at);
+    if ((rc = ws.upload(s.d_table, s.table.data(), sizeof(MeshViewDev) * n_views))
+        || (rc = ws.upload(s.d_images, s.images.data(), sizeof(TsdfImageDev) * n_views)))
+        return rc;
+    return launch_prepare_and_cut(ws.stream, s.d_table, s.table, cut);
+}
+
+} // namespace
+
+extern "C" int
+smvs_tsdf_bounds(int device, const smvs_point_view *views, int n_views, int cut_surfaces,
+    float *lo, float *hi)
+{
+    SMVS_REQUIRE(lo != nullptr && hi != nullptr, "no output");
+    int rc;
+    if ((rc = check_views(views, n_views, cut_surfaces, false)))
+        return rc;
+    WorkspaceLease lease(device);
+    if (lease.w == nullptr)
+        return SMVS_ERR_HIP;
+    Workspace &ws = *lease.w;
+    Carver carve;
+    ViewSlab s;
+    carve_views(views, n_views, false, carve, s);
+    unsigned const blocks = (unsigned)((s.max_pix + 255) / 256);
+    size_t const n_partial = (size_t)blocks * n_views;
+    size_t const partial_at = carve(sizeof(float) * 6 * n_partial);
+    size_t const result_at = carve(sizeof(float) * 6);
+    char *slab = nullptr;
+    if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
+        return rc;
+    if ((rc = upload_and_prepare(ws, slab, views, n_views, cut_surfaces != 0, false, s)))
+        return rc;
+    float *partial = reinterpret_cast<float *>(slab + partial_at);
+    float *result = reinterpret_cast<float *>(slab + result_at);
+    hipLaunchKernelGGL(tsdf_bounds_kernel, dim3(blocks, (unsigned)n_views), dim3(256), 0,
+        ws.stream, s.d_table, partial);
+    hipLaunchKernelGGL(tsdf_bounds_final_kernel, dim3(1), dim3(256), 0, ws.stream, partial,
+        n_partial, result);
+    SMVS_HIP_CHECK(hipGetLastError());
+    float out[6];
+    if ((rc = ws.download(out, result, sizeof(out))))
+        return rc;
+    for (int r = 0; r < 3; ++r) {
+        lo[r] = out[r];
+        hi[r] = out[3 + r];
+    }
+    return SMVS_OK;
+}
+
+extern "C" int
+smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
+    const smvs_tsdf_options *options, float *tsdf, uint32_t *weight, smvs_points **handle,
+    int64_t *n_vertices, int64_t *n_faces)
+{
+    SMVS_REQUIRE(handle != nullptr, "no handle pointer");
+    *handle = nullptr;
+    SMVS_REQUIRE(options != nullptr, "no options");
+    smvs_tsdf_options const &opt = *options;
+    int rc;
+    if ((rc = check_views(views, n_views, opt.cut_surfaces, true)))
+        return rc;
+    SMVS_REQUIRE(std::isfinite(opt.voxel_size) && opt.voxel_size > 0.0f,
+        "voxel_size must be positive and finite");
+    SMVS_REQUIRE(std::isfinite(opt.trunc), "trunc must be finite");
+    size_t n_vox = 1;
+    for (int r = 0; r < 3; ++r) {
+        SMVS_REQUIRE(opt.dims[r] >= 2 && opt.dims[r] <= 1024, "dims must be 2 .. 1024");
+        SMVS_REQUIRE(std::isfinite(opt.origin[r]), "origin must be finite");
+        n_vox *= (size_t)opt.dims[r];
+    }
+    SMVS_REQUIRE(n_vox <= TSDF_MAX_VOXELS, "the volume has more than 2^27 voxels");
+
+    TsdfGrid G;
+    G.nx = opt.dims[0];
+    G.ny = opt.dims[1];
+    G.nz = opt.dims[2];
+    for (int r = 0; r < 3; ++r)
+        G.origin[r] = opt.origin[r];
+    G.voxel_size = opt.voxel_size;
+    G.trunc = opt.trunc > 0.0f ? opt.trunc : 3.0f * opt.voxel_size;
+    G.min_weight = opt.min_weight > 0 ? (uint32_t)opt.min_weight : 1u;
+    G.n_views = n_views;
+
+    WorkspaceLease lease(device);
+    if (lease.w == nullptr)
+        return SMVS_ERR_HIP;
+    Workspace &ws = *lease.w;
+    Carver carve;
+    ViewSlab s;
+    carve_views(views, n_views, true, carve, s);
+    unsigned const point_blocks = (unsigned)((n_vox + 255) / 256);
+    size_t const scan_tiles = ((size_t)point_blocks + SCAN_TILE - 1) / SCAN_TILE;
+    size_t const tsdf_at = carve(4 * n_vox), weight_at = carve(4 * n_vox),
+        colour_at = carve(16 * n_vox), vid_at = carve(4 * n_vox),
+        counts_at = carve(8 * (size_t)point_blocks), tiles_at = carve(8 * (scan_tiles + 1));
+    char *slab = nullptr;
+    if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
+        return rc;
+    hipStream_t const stream = ws.stream;
+    if ((rc = upload_and_prepare(ws, slab, views, n_views, opt.cut_surfaces != 0, true, s)))
+        return rc;
+
+    float *d_tsdf = reinterpret_cast<float *>(slab + tsdf_at);
+    uint32_t *d_weight = reinterpret_cast<uint32_t *>(slab + weight_at);
+    uint4 *d_colour = reinterpret_cast<uint4 *>(slab + colour_at);
+    uint32_t *d_vid = reinterpret_cast<uint32_t *>(slab + vid_at);
+    unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(slab + counts_at);
+    unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(slab + tiles_at);
+
+    hipLaunchKernelGGL(tsdf_depth_kernel, dim3((unsigned)((s.max_pix + 255) / 256),
+        (unsigned)n_views), dim3(256), 0, stream, s.d_table);
+    unsigned const bricks = (unsigned)((G.nx + TSDF_BX - 1) / TSDF_BX)
+        * (unsigned)((G.ny + TSDF_BY - 1) / TSDF_BY)
+        * (unsigned)((G.nz + TSDF_BZ - 1) / TSDF_BZ);
+    hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(bricks), dim3(256), 0, stream, s.d_table,
+        s.d_images, G, d_tsdf, d_weight, d_colour);
+    hipLaunchKernelGGL(tsdf_classify_kernel, dim3(point_blocks), dim3(256), 0, stream, d_tsdf,
+        G, d_counts);
+    SMVS_HIP_CHECK(hipGetLastError());
+    if ((rc = exclusive_scan(stream, d_counts, point_blocks, d_tiles)))
+        return rc;
+    unsigned long long sums = 0;
+    if ((rc = ws.download(&sums, d_tiles + scan_tiles, sizeof(sums))))
+        return rc;
+    size_t const n_vert = (size_t)(sums & 0xffffffffull);
+    size_t const n_face = 2 * (size_t)(sums >> 32);
+
+    smvs_points *h = new smvs_points;
+    h->mesh = true;
+    h->n_points = (int64_t)n_vert;
+    h->n_faces = (int64_t)n_face;
+    h->xyz.resize(3 * n_vert);
+    h->nrm.resize(3 * n_vert);
+    h->rgb.resize(3 * n_vert);
+    h->conf.resize(n_vert);
+    h->faces.resize(3 * n_face);
+    auto fail = [&](int code) {
+        delete h;
+        return code;
+    };
+    if (n_vert > 0) {
+        Carver oc;
+        size_t const xyz_at = oc(12 * n_vert), nrm_at = oc(12 * n_vert), conf_at = oc(4 * n_vert),
+            rgb_at = oc(3 * n_vert), faces_at = oc(12 * n_face);
+        char *outs = nullptr;
+        if ((rc = ws.ensure(1, oc.total, &outs)) != SMVS_OK)
+            return fail(rc);
+        TsdfOut O;
+        O.xyz = reinterpret_cast<float *>(outs + xyz_at);
+        O.nrm = reinterpret_cast<float *>(outs + nrm_at);
+        O.conf = reinterpret_cast<float *>(outs + conf_at);
+        O.rgb = reinterpret_cast<uint8_t *>(outs + rgb_at);
+        O.faces = reinterpret_cast<uint32_t *>(outs + faces_at);
+        hipLaunchKernelGGL(tsdf_vertex_kernel, dim3(point_blocks), dim3(256), 0, stream,
+            d_tsdf, d_weight, d_colour, G, d_counts, d_vid, O);
+        hipLaunchKernelGGL(tsdf_face_kernel, dim3(point_blocks), dim3(256), 0, stream, d_tsdf,
+            G, d_counts, d_vid, O);
+        if (hipGetLastError() != hipSuccess) {
+            set_error("smvs_tsdf_fuse: extraction launch failed");
+            return fail(SMVS_ERR_HIP);
+        }
+        if ((rc = ws.download(h->xyz.data(), O.xyz, 12 * n_vert))
+            || (rc = ws.download(h->nrm.data(), O.nrm, 12 * n_vert))
+            || (rc = ws.download(h->rgb.data(), O.rgb, 3 * n_vert))
+            || (rc = ws.download(h->conf.data(), O.conf, 4 * n_vert))
+            || (rc = ws.download(h->faces.data(), O.faces, 12 * n_face)))
+            return fail(rc);
+    }
+    if ((tsdf != nullptr && (rc = ws.download(tsdf, d_tsdf, 4 * n_vox)))
+        || (weight != nullptr && (rc = ws.download(weight, d_weight, 4 * n_vox))))
+        return fail(rc);
+    *handle = h;
+    if (n_vertices != nullptr)
+        *n_vertices = h->n_points;
+    if (n_faces != nullptr)
+        *n_faces = h->n_faces;
+    return SMVS_OK;
+}

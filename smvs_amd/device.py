@@ -1368,6 +1368,83 @@ def generate_mesh(cams, depths, normals, images, cut=True, aabb=None, dd_factor=
     return out
 
 
+def _tsdf_views(cams, depths, normals, images):
+    """smvs_point_view records for the fusion: normals may be None (no cut),
+    images may be None (the bounds)"""
+    n = len(cams)
+    if normals is None:
+        normals = [np.zeros(np.shape(d) + (3,), np.float32) for d in depths]
+        no_normals = True
+    else:
+        no_normals = False
+    if images is None:
+        images = [np.zeros(np.shape(d), np.uint8) for d in depths]
+    arr, _, keep = _point_views(cams, depths, normals, images, False)
+    if no_normals:
+        for i in range(n):
+            arr[i].normals = None
+    return arr, keep
+
+
+def tsdf_bounds(cams, depths, normals, cut=True, device=0):
+    """smvs_tsdf_bounds: the box of the world points of the valid pixels of the
+    (cut) depth maps.  Inputs as generate_mesh; normals may be None when cut is
+    off.  Returns (lo, hi), float32 (3,) each; lo > hi when no pixel is valid."""
+    lib = _capi.load()
+    n = len(cams)
+    arr, _keep = _tsdf_views(cams, depths, normals, None)
+    lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    check(lib.smvs_tsdf_bounds(device, arr if n else None, n, int(bool(cut)), _p(lo, _fp),
+                               _p(hi, _fp)))
+    return lo, hi
+
+
+def fuse_tsdf(cams, depths, normals, images, origin, voxel_size, dims, trunc=0, min_weight=0,
+              cut=True, volume=False, device=0):
+    """smvs_tsdf_fuse: the depth maps fused into one surface mesh through a
+    truncated signed distance field on the voxel grid (origin, voxel_size,
+    dims = (nx, ny, nz)); the definition is in include/smvs_hip.h.  Inputs as
+    generate_mesh; normals may be None when cut is off.  trunc <= 0: 3 voxels;
+    min_weight <= 0: 1.  Returns the dict generate_mesh returns (xyz, normals,
+    rgb, confidence, faces) and, with volume, tsdf (nz, ny, nx) float32 with NaN
+    for unknown and weight (nz, ny, nx) uint32."""
+    lib = _capi.load()
+    n = len(cams)
+    arr, _keep = _tsdf_views(cams, depths, normals, images)
+    opt = _capi.TsdfOptions()
+    opt.cut_surfaces = int(bool(cut))
+    for k in range(3):
+        opt.origin[k] = float(origin[k])
+        opt.dims[k] = int(dims[k])
+    opt.voxel_size = float(voxel_size)
+    opt.trunc = float(trunc)
+    opt.min_weight = int(min_weight)
+    tsdf = weight = None
+    if volume:
+        shape = tuple(max(int(d), 0) for d in dims)[::-1]
+        tsdf = np.zeros(shape, np.float32)
+        weight = np.zeros(shape, np.uint32)
+    handle = C.c_void_p()
+    n_vertices, n_faces = C.c_int64(), C.c_int64()
+    check(lib.smvs_tsdf_fuse(device, arr if n else None, n, C.byref(opt), _p(tsdf, _fp),
+                             _p(weight, _u32p), C.byref(handle), C.byref(n_vertices),
+                             C.byref(n_faces)))
+    try:
+        k = n_vertices.value
+        out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
+               "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
+               "faces": np.zeros((n_faces.value, 3), np.uint32)}
+        check(lib.smvs_points_download(handle, _p(out["xyz"], _fp), _p(out["normals"], _fp),
+                                       _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
+                                       None, _p(out["faces"], _u32p)))
+    finally:
+        lib.smvs_points_release(handle)
+    if volume:
+        out["tsdf"] = tsdf
+        out["weight"] = weight
+    return out
+
+
 class SimplifyOptions(C.Structure):
     """smvs_simplify_options of include/smvs_hip.h."""
     _fields_ = [("cut_surfaces", C.c_int), ("use_aabb", C.c_int),

@@ -1001,6 +1001,40 @@ def generate_simplified(scene_dir, mesh=False, view_ids=None, image_embedding="u
     return path.value.decode(), nv.value, nf.value
 
 
+class FusedSettings(C.Structure):
+    _fields_ = [("voxel_size", C.c_float), ("resolution", C.c_int), ("trunc", C.c_float),
+                ("min_weight", C.c_int)]
+
+
+def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=0, min_weight=0,
+                   view_ids=None, image_embedding="undistorted", input_scale=0,
+                   use_shading=False, cut=True, device=0):
+    """Not in the reference: the views' smvs-{B,S}<input_scale> depth maps fused
+    into ONE surface mesh through a truncated signed distance field
+    (smvs_tsdf_fuse), written as
+    <scene>/smvs-fused-{B,S}<input_scale>.ply.  The box is aabb ((min3, max3)),
+    or the bounds of the (cut) depth maps' points padded by the truncation
+    distance; voxel_size None: the box's longest side / resolution; trunc 0: 3
+    voxels; min_weight 0: 1.  Returns (ply path, number of vertices, number of
+    faces)."""
+    lib = load()
+    st = _point_cloud_settings(image_embedding, input_scale, use_shading, cut, aabb, True,
+                               False, device)
+    fs = FusedSettings(0.0 if voxel_size is None else float(voxel_size), int(resolution),
+                       float(trunc), int(min_weight))
+    ids = None if view_ids is None else np.asarray(view_ids, dtype=np.int32)
+    path = C.create_string_buffer(4096)
+    nv, nf = C.c_int64(0), C.c_int64(0)
+    rc = lib.smvs_host_generate_fused(
+        scene_dir.encode(), C.byref(st), C.byref(fs),
+        ids.ctypes.data_as(_i32p) if ids is not None else None,
+        C.c_int(0 if ids is None else ids.size), path, C.c_int(len(path)), C.byref(nv),
+        C.byref(nf))
+    if rc != 0:
+        raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    return path.value.decode(), nv.value, nf.value
+
+
 def save_ply_points(path, xyz, normals, rgb, confidence, value):
     """The host's PLY writer of the point cloud (save_ply_points)."""
     lib = load()

@@ -1,0 +1,139 @@
+#!/usr/bin/env python3
+"""Times the volumetric fusion (smvs_tsdf_fuse) at 256^3 voxels with 16 views
+of 960 x 540 around the synthetic sphere's front, the cut on: the entry box to
+box (upload, preparation and cut, integration, extraction, download of the
+mesh), and the kernels alone -- from the kernel trace of a child process that
+runs the entry under rocprofv3 (--no-kernels skips it).  Prints one JSON line
+for the entry and one per kernel; the integration kernel's line carries the
+bytes it has to move (the volume written once, 24 bytes per voxel, and every
+depth map read once) over its time, and the fraction of the HBM copy rate
+tools/peaks.py measures on the same GPU (--no-peaks: left out).  The inputs are
+tools/points_bench.py's (the 16 views repeat the nine synthetic ones).
+
+    python tools/tsdf_bench.py [--dims N] [--views N] [--size W H] [--reps N]
+                               [--no-kernels] [--no-peaks]
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import numpy as np  # noqa: E402
+
+KERNELS = ["mesh_prepare_kernel", "mesh_cut_kernel", "tsdf_depth_kernel", "tsdf_integrate_kernel",
+           "tsdf_classify_kernel", "scan_tile_sums_kernel", "scan_tiles_kernel",
+           "scan_apply_kernel", "tsdf_vertex_kernel", "tsdf_face_kernel"]
+CHILD_REPS = 3
+BOX_LO, BOX_SIDE = (-1.3, -1.3, 2.7), 2.6
+
+
+def case(args):
+    from points_bench import inputs
+    cams, depths, normals, images = inputs(args.size[0], args.size[1], args.views)
+    return cams, depths, normals, images, BOX_LO, BOX_SIDE / args.dims, (args.dims,) * 3
+
+
+def child(args):
+    from smvs_amd import device
+    c = case(args)
+    for _ in range(CHILD_REPS):
+        device.fuse_tsdf(*c, cut=True)
+
+
+def kernel_times(args):
+    """-> {kernel: (launches per call, best total seconds per call)}"""
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "run",
+               "--", sys.executable, os.path.abspath(__file__), "--child", "--dims",
+               str(args.dims), "--views", str(args.views), "--size", str(args.size[0]),
+               str(args.size[1])]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+        if res.returncode != 0:
+            raise RuntimeError("rocprofv3 failed: " + res.stderr[-2000:])
+        files = glob.glob(os.path.join(tmp, "**", "*kernel_trace.csv"), recursive=True)
+        if not files:
+            raise RuntimeError("rocprofv3 left no kernel trace")
+        rows = {k: [] for k in KERNELS}
+        for fn in files:
+            with open(fn) as f:
+                for r in csv.DictReader(f):
+                    for k in KERNELS:
+                        if k in r["Kernel_Name"]:
+                            rows[k].append((int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
+    out = {}
+    for k, v in rows.items():
+        v.sort()
+        if not v or len(v) % CHILD_REPS:
+            raise RuntimeError("%d launches of %s in the trace of %d calls"
+                               % (len(v), k, CHILD_REPS))
+        per = len(v) // CHILD_REPS
+        out[k] = (per, min(sum(1e-9 * (e - s) for s, e in v[i * per:(i + 1) * per])
+                           for i in range(CHILD_REPS)))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dims", type=int, default=256)
+    ap.add_argument("--views", type=int, default=16)
+    ap.add_argument("--size", type=int, nargs=2, default=[960, 540])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--no-peaks", action="store_true")
+    args = ap.parse_args()
+    if args.child:
+        child(args)
+        return
+    import smvs_amd
+    from smvs_amd import device
+    if smvs_amd.device_count() < 1:
+        raise SystemExit("tsdf_bench needs a GPU")
+    c = case(args)
+    times = []
+    for _ in range(args.reps + 1):
+        t0 = time.perf_counter()
+        out = device.fuse_tsdf(*c, cut=True)
+        times.append(time.perf_counter() - t0)
+    n_vox = args.dims ** 3
+    pixels = args.size[0] * args.size[1] * args.views
+    print(json.dumps({"case": "entry", "dims": [args.dims] * 3, "views": args.views,
+                      "size": args.size, "cut": True, "vertices": len(out["xyz"]),
+                      "faces": len(out["faces"]), "fuse_ms_first": round(1e3 * times[0], 2),
+                      "fuse_ms_best": round(1e3 * min(times[1:]), 2)}), flush=True)
+    if args.no_kernels:
+        return
+    kt = kernel_times(args)
+    copy_peak = None
+    if not args.no_peaks:
+        import peaks
+        copy_peak = peaks.run()["hbm_copy_GBps"]
+    for k in KERNELS:
+        per, t = kt[k]
+        rec = {"case": "kernel", "kernel": k, "launches_per_call": per,
+               "ms_per_call_best": round(1e3 * t, 4)}
+        if k == "tsdf_integrate_kernel":
+            moved = 24 * n_vox + 4 * pixels
+            rec.update({"voxel_views": n_vox * args.views,
+                        "ns_per_1000_voxel_views": round(1e12 * t / (n_vox * args.views), 3),
+                        "bytes_moved_MB": round(1e-6 * moved, 1),
+                        "GBps": round(1e-9 * moved / t, 1)})
+            if copy_peak:
+                rec["hbm_copy_peak_GBps"] = round(copy_peak, 1)
+                rec["fraction_of_hbm_copy_peak"] = round(1e-9 * moved / t / copy_peak, 4)
+        print(json.dumps(rec), flush=True)
+    print(json.dumps({"case": "kernels_total",
+                      "ms_per_call_best": round(1e3 * sum(t for _, t in kt.values()), 3)}),
+          flush=True)
+
+
+if __name__ == "__main__":
+    main()
