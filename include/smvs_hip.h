@@ -1346,6 +1346,70 @@ int smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
     const smvs_tsdf_options *options, float *tsdf, uint32_t *weight,
     smvs_points **handle, int64_t *n_vertices, int64_t *n_faces);
 
+/* smvs_tsdf_fuse on a brick-sparse volume (opt-in): the
+ * same mesh, vertex for vertex and face for face to the bit, from a volume that
+ * exists only near the surface, so that grids of up to 4096 voxels per side
+ * fit.  tests/tsdf_sparse_ref.py restates this comment on top of tests/
+ * tsdf_ref.py.
+ *
+ * Grid, views, preparation, D, steps 1-8, F, vertices and faces are those of
+ * smvs_tsdf_fuse.
+ *   brick      8 x 8 x 4 voxels.  Brick (bi, bj, bk) holds the voxels
+ *              (8 bi .. 8 bi + 7, 8 bj .. 8 bj + 7, 4 bk .. 4 bk + 3) and has
+ *              the linear index (bk * by + bj) * bx + bi, with bx =
+ *              ceil(dims[0] / 8), by = ceil(dims[1] / 8), bz = ceil(dims[2] / 4).
+ *              Bricks at the high faces may be partial.
+ *   seed       a voxel whose C of step 8 is > 0 (some view puts it within the
+ *              truncation band); a seed brick holds a seed voxel
+ *   allocated  a brick that is a seed brick or has one among its up to 26
+ *              neighbours in the brick grid
+ * In allocated bricks F, W, R, G, B, C are smvs_tsdf_fuse's; elsewhere F is
+ * NaN and the sums are 0.  Every inside corner (F < 0) is a seed, and an active
+ * cell and the four cells of a quad lie within one voxel of an inside corner,
+ * hence in its brick or a neighbour of it: the cells, vertices and faces are
+ * exactly the dense ones.
+ *   order      vertex ids are the rank of the active cell by (linear brick
+ *              index of the cell's corner 0, then the voxel's index inside the
+ *              brick, x fastest over 8 x 8 x 4).  Faces follow the grid points
+ *              in that same order and for each point the axes 0, 1, 2, with
+ *              smvs_tsdf_fuse's rule for the two triangles.
+ * The order is the only difference to smvs_tsdf_fuse, whose order is the linear
+ * cell index over the whole grid.
+ *
+ * max_bricks <= 0 means 1 << 20 bricks; the state is 256 * 28 bytes per
+ * allocated brick (7 GiB at 1 << 20), which is stats->state_bytes.  More than
+ * 1 << 23 is refused (vertex ids are 32 bits).
+ *
+ * Refused with SMVS_ERR_INVALID before any device call: everything
+ * smvs_tsdf_fuse refuses but its size limits, which become: each dim 2 ..
+ * 4096, a brick grid of at most 2^28 bricks, and tsdf or weight asked for on a
+ * grid of more than 2^27 voxels.  SMVS_ERR_NOMEM, after the seed and dilation
+ * passes and before anything is allocated for the volume, when more than
+ * max_bricks bricks are allocated: stats and brick_state are filled, the error
+ * text names the count needed, there is no handle.
+ *
+ * brick_state (may be NULL): bx * by * bz bytes, 0 none, 1 allocated, 2 seed.
+ * tsdf / weight (either may be NULL): the whole grid as smvs_tsdf_fuse gives
+ * it, NaN / 0 where not allocated.  stats may be NULL.  The handle is a mesh
+ * handle as smvs_tsdf_fuse's; smvs_tsdf_vertex_cells gives per vertex the
+ * cell's linear index in the whole grid, (k * dims[1] + j) * dims[0] + i
+ * (n_vertices values), and is SMVS_ERR_INVALID on any other handle. */
+typedef struct {
+    int64_t max_bricks;
+} smvs_tsdf_sparse_options;
+
+typedef struct {
+    int64_t bricks, seed_bricks, allocated_bricks, state_bytes;
+} smvs_tsdf_sparse_stats;
+
+int smvs_tsdf_fuse_sparse(int device, const smvs_point_view *views, int n_views,
+    const smvs_tsdf_options *options, const smvs_tsdf_sparse_options *sparse,
+    uint8_t *brick_state, float *tsdf, uint32_t *weight,
+    smvs_tsdf_sparse_stats *stats, smvs_points **handle, int64_t *n_vertices,
+    int64_t *n_faces);
+
+int smvs_tsdf_vertex_cells(const smvs_points *handle, int64_t *cell);
+
 /* The componentwise minimum and maximum of world_point over the valid
  * (non-zero) pixels of the maps smvs_tsdf_fuse would fuse: the cut maps with
  * cut_surfaces and n_views > 1, else the depth maps (image and channels are not

@@ -50,6 +50,20 @@ class TsdfOptions(C.Structure):
                 ("trunc", C.c_float), ("min_weight", C.c_int)]
 
 
+class TsdfSparseOptions(C.Structure):
+    """smvs_tsdf_sparse_options of include/smvs_hip.h."""
+    _fields_ = [("max_bricks", C.c_int64)]
+
+
+class TsdfSparseStats(C.Structure):
+    """smvs_tsdf_sparse_stats of include/smvs_hip.h."""
+    _fields_ = [("bricks", C.c_int64), ("seed_bricks", C.c_int64),
+                ("allocated_bricks", C.c_int64), ("state_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 K_NAMES = ["patch", "assemble", "cg_spmv", "cg_update", "cg_init",
            "reactivate", "misc", "cg_resident"]
 

@@ -577,6 +577,22 @@ int smvs_host_generate_fused(const char *scene_dir,
     const smvs_host_point_cloud_settings *settings, const smvs_host_fused_settings *fused,
     const int *view_ids, int n_view_ids, char *ply_path, int ply_path_capacity,
     int64_t *n_vertices, int64_t *n_faces);
+/* smvs_host_generate_fused on the brick-sparse volume (smvs_tsdf_fuse_sparse,
+ * DESIGN.md section 9.9): the same file name, the same mesh with vertices and
+ * faces in the brick order.  resolution (and every dim) may go up to 4096;
+ * max_bricks <= 0: 1 << 20.  More bricks needed than max_bricks is an error
+ * whose text names the count. */
+typedef struct {
+    float voxel_size;
+    int resolution;
+    float trunc;
+    int min_weight;
+    int64_t max_bricks;
+} smvs_host_fused_sparse_settings;
+int smvs_host_generate_fused_sparse(const char *scene_dir,
+    const smvs_host_point_cloud_settings *settings,
+    const smvs_host_fused_sparse_settings *fused, const int *view_ids, int n_view_ids,
+    char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces);
 /* save_ply_mesh: the PLY writer of the triangle mesh from SoA
  * buffers (xyz, normals n*3 floats; rgb n*3 bytes; confidence n floats;
  * faces m*3 vertex ids < n). */

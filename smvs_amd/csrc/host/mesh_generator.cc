@@ -218,6 +218,10 @@ MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
         return mesh;
     if (fused.voxel_size <= 0.0f && fused.resolution < 8)
         throw std::invalid_argument("generate_fused: resolution must be at least 8");
+    if (fused.sparse && fused.voxel_size <= 0.0f && fused.resolution > 4096)
+        throw std::invalid_argument("generate_fused: resolution must be at most 4096");
+    if (!fused.sparse && fused.max_bricks > 0)
+        throw std::invalid_argument("generate_fused: max_bricks belongs to sparse");
     int const n = (int)in.pv.size();
     float lo[3], hi[3];
     if (opts.use_aabb) {
@@ -264,8 +268,14 @@ MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
     }
     smvs_points* handle = nullptr;
     int64_t nv = 0, nf = 0;
-    check_status(smvs_tsdf_fuse(opts.device, in.pv.data(), n, &to, nullptr, nullptr, &handle,
-        &nv, &nf), "smvs_tsdf_fuse");
+    if (fused.sparse) {
+        smvs_tsdf_sparse_options so;
+        so.max_bricks = fused.max_bricks;
+        check_status(smvs_tsdf_fuse_sparse(opts.device, in.pv.data(), n, &to, &so, nullptr,
+            nullptr, nullptr, nullptr, &handle, &nv, &nf), "smvs_tsdf_fuse_sparse");
+    } else
+        check_status(smvs_tsdf_fuse(opts.device, in.pv.data(), n, &to, nullptr, nullptr,
+            &handle, &nv, &nf), "smvs_tsdf_fuse");
     mesh->xyz.resize(3 * (std::size_t)nv);
     mesh->normals.resize(3 * (std::size_t)nv);
     mesh->colors.resize(3 * (std::size_t)nv);

@@ -80,13 +80,17 @@ public:
     // on smvs_tsdf_fuse.  The box is [aabb_min,
     // aabb_max] with use_aabb, else smvs_tsdf_bounds padded by the truncation
     // distance; dims[a] = max(2, (int)ceilf((hi[a] - lo[a]) / voxel_size)).
-    // No smvs-cut is written.
+    // No smvs-cut is written.  With sparse the volume is smvs_tsdf_fuse_sparse's
+    // (section 9.9): the same mesh in the brick order, and resolution (and
+    // every dim) may go up to 4096.
     struct FusedOptions
     {
         float voxel_size = 0.0f;    // <= 0: the box's longest side / resolution
         int resolution = 256;
         float trunc = 0.0f;         // <= 0: 3 voxels
         int min_weight = 0;         // <= 0: 1
+        bool sparse = false;
+        int64_t max_bricks = 0;     // sparse only; <= 0: 1 << 20
     };
     TriangleMesh::Ptr generate_fused(std::vector<SceneView> const& views,
         std::string const& image_name, std::string const& dm_name,

@@ -126,5 +126,7 @@ struct smvs_points {
     std::vector<float> xyz, nrm, conf, val;
     std::vector<uint8_t> rgb;
     std::vector<uint32_t> faces;
+    bool sparse = false;          // smvs_tsdf_fuse_sparse: cells per vertex
+    std::vector<int64_t> cells;
 };
 

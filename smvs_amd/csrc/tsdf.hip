@@ -17,26 +17,16 @@
 // Arithmetic: float, FMA contraction off, term by term as mesh.hip writes it.
 // No atomics: every order is an index order (vertex ids and face positions
 // come from the scan and a scan inside each block).
+// The per-element device functions live in tsdf_shared.h, which
+// tsdf_sparse.hip (the brick-sparse volume, section 9.9) uses as well.
 #include "common.h"
 #include "mesh_shared.h"
+#include "tsdf_shared.h"
 
 #include <cmath>
 #include <vector>
 
 namespace smvs_hip {
-
-struct TsdfGrid {
-    int nx, ny, nz;
-    float origin[3];
-    float voxel_size, trunc;
-    uint32_t min_weight;
-    int n_views;
-};
-
-struct TsdfImageDev {
-    const uint8_t *image;   // w * h * channels
-    int channels;
-};
 
 __device__ __forceinline__ bool
 tsdf_pixel(const MeshViewDev *views, int &v, int &x, int &y, size_t &p)
@@ -65,19 +55,8 @@ tsdf_depth_kernel(const MeshViewDev *__restrict__ views)
         views[v].depth_z[p] = 0.0f;
 }
 
-// the centre of voxel (or grid point) idx along one axis
-__device__ __forceinline__ float
-tsdf_centre(TsdfGrid const &G, int axis, int idx)
-{
-#pragma clang fp contract(off)
-    return G.origin[axis] + ((float)idx + 0.5f) * G.voxel_size;
-}
-
 // Field, steps 1-8 and the division after the loop.  A block is a brick of
-// 8 x 8 x 4 voxels (a wave is one 8 x 8 slab of it), so that the 64 gathers of
-// a wave land in a small patch of each depth map.
-constexpr int TSDF_BX = 8, TSDF_BY = 8, TSDF_BZ = 4;
-
+// 8 x 8 x 4 voxels (tsdf_shared.h).
 __global__ void __launch_bounds__(256)
 tsdf_integrate_kernel(const MeshViewDev *__restrict__ views,
     const TsdfImageDev *__restrict__ images, TsdfGrid G, float *__restrict__ tsdf,
@@ -97,27 +76,7 @@ tsdf_integrate_kernel(const MeshViewDev *__restrict__ views,
     uint32_t W = 0, R = 0, Gr = 0, B = 0, C = 0;
     for (int v = 0; v < G.n_views; ++v) {
         MeshViewDev const &V = views[v];
-        float proj[3];
-        proj[0] = dot3(V.KR + 0, c) - V.t[0];
-        proj[1] = dot3(V.KR + 3, c) - V.t[1];
-        proj[2] = dot3(V.KR + 6, c) - V.t[2];
-        if (proj[2] <= 0.0f)
-            continue;
-        float const u = proj[0] / proj[2];
-        float const w = proj[1] / proj[2];
-        if (u < 0.0f || w < 0.0f)
-            continue;
-        int const xj = (int)u;
-        int const yj = (int)w;
-        if (xj >= V.w || yj >= V.h)
-            continue;
-        size_t const pj = (size_t)yj * V.w + xj;
-        float const D = V.depth_z[pj];
-        if (D == 0.0f)
-            continue;
-        float const sdf = D - proj[2];
-        if (sdf < -G.trunc)
-            continue;
+        TSDF_STEPS_1_TO_6(V, c, G.trunc, continue);
         S += fminf(1.0f, sdf / G.trunc);
         W += 1;
         if (sdf <= G.trunc) {
@@ -152,133 +111,6 @@ tsdf_point(TsdfGrid const &G, size_t &lin, int &i, int &j, int &k)
     return true;
 }
 
-__device__ __forceinline__ size_t
-tsdf_index(TsdfGrid const &G, int i, int j, int k)
-{
-    return ((size_t)k * G.ny + j) * G.nx + i;
-}
-
-// the cell's corners c = dx + 2 dy + 4 dz; -> complete (in the grid, no NaN)
-__device__ __forceinline__ bool
-tsdf_cell(const float *__restrict__ tsdf, TsdfGrid const &G, int i, int j, int k, float *f)
-{
-    if (i < 0 || j < 0 || k < 0 || i > G.nx - 2 || j > G.ny - 2 || k > G.nz - 2)
-        return false;
-    bool complete = true;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        f[c] = tsdf[tsdf_index(G, i + (c & 1), j + (c >> 1 & 1), k + (c >> 2))];
-        complete = complete && !(f[c] != f[c]);
-    }
-    return complete;
-}
-
-__device__ __forceinline__ bool
-tsdf_cell_active(const float *__restrict__ tsdf, TsdfGrid const &G, int i, int j, int k,
-    float *f)
-{
-    if (!tsdf_cell(tsdf, G, i, j, k, f))
-        return false;
-    int inside = 0;
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-        inside += f[c] < 0.0f;
-    return inside != 0 && inside != 8;
-}
-
-// the four cells around the edge from point (i, j, k) along axis a, as (b, c)
-// offsets with (a, b, c) cyclic: (-1,-1) (0,-1) (0,0) (-1,0)
-__device__ __forceinline__ void
-tsdf_quad_cell(int a, int q, int i, int j, int k, int *cell)
-{
-    int const ob = (q == 1 || q == 2) ? 0 : -1;
-    int const oc = (q == 2 || q == 3) ? 0 : -1;
-    int off[3] = { 0, 0, 0 };
-    off[(a + 1) % 3] = ob;
-    off[(a + 2) % 3] = oc;
-    cell[0] = i + off[0];
-    cell[1] = j + off[1];
-    cell[2] = k + off[2];
-}
-
-// Faces: bit a set when the edge along axis a has a quad; bit 3: P is inside
-__device__ __forceinline__ int
-tsdf_quads(const float *__restrict__ tsdf, TsdfGrid const &G, int i, int j, int k)
-{
-    int const n[3] = { G.nx, G.ny, G.nz };
-    int const p[3] = { i, j, k };
-    float const fa = tsdf[tsdf_index(G, i, j, k)];
-    if (fa != fa)
-        return 0;
-    int mask = fa < 0.0f ? 8 : 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        if (p[a] > n[a] - 2)
-            continue;
-        float const fb = tsdf[tsdf_index(G, i + (a == 0), j + (a == 1), k + (a == 2))];
-        if (fb != fb || (fa < 0.0f) == (fb < 0.0f))
-            continue;
-        bool all = true;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (!all)
-                break;
-            int cell[3];
-            float f[8];
-            tsdf_quad_cell(a, q, i, j, k, cell);
-            all = tsdf_cell(tsdf, G, cell[0], cell[1], cell[2], f);
-        }
-        if (all)
-            mask |= 1 << a;
-    }
-    return mask;
-}
-
-// exclusive scan of one 32-bit value per thread over the block of 256 and the
-// block's total; every thread of the block calls it
-__device__ __forceinline__ uint32_t
-tsdf_block_scan(uint32_t v, uint32_t *total)
-{
-    __shared__ uint32_t wsum[4];
-    int const lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t const t = __shfl_up(inc, o, 64);
-        if (lane >= o)
-            inc += t;
-    }
-    if (lane == 63)
-        wsum[wave] = inc;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        pre += w < wave ? wsum[w] : 0u;
-        tot += wsum[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return pre + inc - v;
-}
-
-// per thread: active cell (0 / 1) | quads (0..3) << 16, each where asked for
-template <bool CELLS, bool QUADS>
-__device__ __forceinline__ uint32_t
-tsdf_classify(const float *__restrict__ tsdf, TsdfGrid const &G, bool valid, int i, int j,
-    int k, float *f, bool *active, int *quads)
-{
-    *active = false;
-    *quads = 0;
-    if (!valid)
-        return 0;
-    if constexpr (CELLS)
-        *active = tsdf_cell_active(tsdf, G, i, j, k, f);
-    if constexpr (QUADS)
-        *quads = tsdf_quads(tsdf, G, i, j, k);
-    return (uint32_t)*active | (uint32_t)__popc(*quads & 7) << 16;
-}
-
 __global__ void __launch_bounds__(256)
 tsdf_classify_kernel(const float *__restrict__ tsdf, TsdfGrid G,
     unsigned long long *__restrict__ counts)
@@ -295,12 +127,6 @@ tsdf_classify_kernel(const float *__restrict__ tsdf, TsdfGrid G,
         counts[blockIdx.x] = (unsigned long long)(total & 0xffffu)
             | (unsigned long long)(total >> 16) << 32;
 }
-
-struct TsdfOut {
-    float *xyz, *nrm, *conf;
-    uint8_t *rgb;
-    uint32_t *faces;
-};
 
 // Vertices: position, normal, colour, confidence of every active cell, at the
 // cell's rank; vid[cell] = that rank
@@ -322,39 +148,8 @@ tsdf_vertex_kernel(const float *__restrict__ tsdf, const uint32_t *__restrict__ 
         return;
     size_t const id = (size_t)(uint32_t)counts[blockIdx.x] + (before & 0xffffu);
     vid[lin] = (uint32_t)id;
-    // edges in the definition's order: x (0,1) (2,3) (4,5) (6,7), y (0,2) (1,3)
-    // (4,6) (5,7), z (0,4) (1,5) (2,6) (3,7)
     int const cell[3] = { i, j, k };
-    float sum[3] = { 0.0f, 0.0f, 0.0f }, g[3] = { 0.0f, 0.0f, 0.0f };
-    int m = 0;
-#pragma unroll
-    for (int axis = 0; axis < 3; ++axis) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            // the two axes other than `axis`, lower first, carry e's bits
-            int const lo_axis = axis == 0 ? 1 : 0, hi_axis = axis == 2 ? 1 : 2;
-            int const a = (e & 1) << lo_axis | (e >> 1) << hi_axis;
-            int const b = a | 1 << axis;
-            g[axis] += f[b] - f[a];
-            if ((f[a] < 0.0f) == (f[b] < 0.0f))
-                continue;
-            float const t = f[a] / (f[a] - f[b]);
-            float q[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-                q[r] = tsdf_centre(G, r, cell[r] + (a >> r & 1));
-            q[axis] = q[axis] + t * G.voxel_size;
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-                sum[r] += q[r];
-            ++m;
-        }
-    }
-    for (int r = 0; r < 3; ++r)
-        O.xyz[3 * id + r] = sum[r] / (float)m;
-    float const len = sqrtf(dot3(g, g));
-    for (int r = 0; r < 3; ++r)
-        O.nrm[3 * id + r] = len == 0.0f ? 0.0f : g[r] / len;
+    TSDF_VERTEX_GEOMETRY(G, cell, f, id, O);
     uint32_t Rs = 0, Gs = 0, Bs = 0, Cs = 0, Ws = 0;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -366,10 +161,7 @@ tsdf_vertex_kernel(const float *__restrict__ tsdf, const uint32_t *__restrict__ 
         Cs += col.w;
         Ws += weight[at];
     }
-    O.rgb[3 * id + 0] = Cs == 0 ? 0 : (uint8_t)((2 * Rs + Cs) / (2 * Cs));
-    O.rgb[3 * id + 1] = Cs == 0 ? 0 : (uint8_t)((2 * Gs + Cs) / (2 * Cs));
-    O.rgb[3 * id + 2] = Cs == 0 ? 0 : (uint8_t)((2 * Bs + Cs) / (2 * Cs));
-    O.conf[id] = (float)Ws / (float)(8 * G.n_views);
+    TSDF_VERTEX_ATTRIBUTES(G, Rs, Gs, Bs, Cs, Ws, id, O);
 }
 
 // Faces: the quads of every grid point in linear order, axes 0, 1, 2 in turn,
@@ -402,13 +194,7 @@ tsdf_face_kernel(const float *__restrict__ tsdf, TsdfGrid G,
             tsdf_quad_cell(a, q, i, j, k, cell);
             v[q] = vid[tsdf_index(G, cell[0], cell[1], cell[2])];
         }
-        uint32_t *out = O.faces + 6 * quad;
-        out[0] = v[0];
-        out[1] = inside ? v[1] : v[2];
-        out[2] = inside ? v[2] : v[1];
-        out[3] = v[0];
-        out[4] = inside ? v[2] : v[3];
-        out[5] = inside ? v[3] : v[2];
+        tsdf_quad_faces(v, inside, O.faces + 6 * quad);
         ++quad;
     }
 }
@@ -475,36 +261,10 @@ tsdf_bounds_final_kernel(const float *__restrict__ partial, size_t n, float *__r
     tsdf_block_minmax(lo, hi, out);
 }
 
-} // namespace smvs_hip
+// the host pieces tsdf_sparse.hip uses as well (declared in tsdf_shared.h)
+namespace tsdf_host {
 
-using namespace smvs_hip;
-
-namespace {
-
-constexpr size_t TSDF_MAX_VOXELS = (size_t)1 << 27;
-
-struct Carver {
-    size_t total = 0;
-    size_t operator()(size_t bytes)
-    {
-        size_t const at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    }
-};
-
-// the views' maps and tables in the workspace slab, as the mesh export lays
-// them out; images only where the caller fuses
-struct ViewSlab {
-    std::vector<size_t> offsets;   // per view: depth_z, depth_ray, cut, normals, image
-    size_t table_at = 0, images_at = 0, max_pix = 0;
-    std::vector<MeshViewDev> table;
-    std::vector<TsdfImageDev> images;
-    MeshViewDev *d_table = nullptr;
-    TsdfImageDev *d_images = nullptr;
-};
-
-// argument checks shared by the two entries (before any device call)
+// argument checks shared by the entries (before any device call)
 int
 check_views(const smvs_point_view *views, int n_views, int cut, bool want_images)
 {
@@ -586,6 +346,54 @@ upload_and_prepare(Workspace &ws, char *slab, const smvs_point_view *views, int 
     return launch_prepare_and_cut(ws.stream, s.d_table, s.table, cut);
 }
 
+int
+check_grid(const char *who, const smvs_tsdf_options &opt, int n_views, int max_dim,
+    TsdfGrid &G)
+{
+    auto refuse = [&](const char *msg) {
+        set_error("%s: %s", who, msg);
+        return SMVS_ERR_INVALID;
+    };
+    if (!(std::isfinite(opt.voxel_size) && opt.voxel_size > 0.0f))
+        return refuse("voxel_size must be positive and finite");
+    if (!std::isfinite(opt.trunc))
+        return refuse("trunc must be finite");
+    for (int r = 0; r < 3; ++r) {
+        if (!(opt.dims[r] >= 2 && opt.dims[r] <= max_dim))
+            return refuse(max_dim == 1024 ? "dims must be 2 .. 1024" : "dims must be 2 .. 4096");
+        if (!std::isfinite(opt.origin[r]))
+            return refuse("origin must be finite");
+    }
+    G.nx = opt.dims[0];
+    G.ny = opt.dims[1];
+    G.nz = opt.dims[2];
+    for (int r = 0; r < 3; ++r)
+        G.origin[r] = opt.origin[r];
+    G.voxel_size = opt.voxel_size;
+    G.trunc = opt.trunc > 0.0f ? opt.trunc : 3.0f * opt.voxel_size;
+    G.min_weight = opt.min_weight > 0 ? (uint32_t)opt.min_weight : 1u;
+    G.n_views = n_views;
+    return SMVS_OK;
+}
+
+void
+launch_depth(hipStream_t stream, ViewSlab const &s, int n_views)
+{
+    hipLaunchKernelGGL(tsdf_depth_kernel, dim3((unsigned)((s.max_pix + 255) / 256),
+        (unsigned)n_views), dim3(256), 0, stream, s.d_table);
+}
+
+} // namespace tsdf_host
+
+} // namespace smvs_hip
+
+using namespace smvs_hip;
+using namespace smvs_hip::tsdf_host;
+
+namespace {
+
+constexpr size_t TSDF_MAX_VOXELS = (size_t)1 << 27;
+
 } // namespace
 
 extern "C" int
@@ -641,27 +449,11 @@ smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
     int rc;
     if ((rc = check_views(views, n_views, opt.cut_surfaces, true)))
         return rc;
-    SMVS_REQUIRE(std::isfinite(opt.voxel_size) && opt.voxel_size > 0.0f,
-        "voxel_size must be positive and finite");
-    SMVS_REQUIRE(std::isfinite(opt.trunc), "trunc must be finite");
-    size_t n_vox = 1;
-    for (int r = 0; r < 3; ++r) {
-        SMVS_REQUIRE(opt.dims[r] >= 2 && opt.dims[r] <= 1024, "dims must be 2 .. 1024");
-        SMVS_REQUIRE(std::isfinite(opt.origin[r]), "origin must be finite");
-        n_vox *= (size_t)opt.dims[r];
-    }
-    SMVS_REQUIRE(n_vox <= TSDF_MAX_VOXELS, "the volume has more than 2^27 voxels");
-
     TsdfGrid G;
-    G.nx = opt.dims[0];
-    G.ny = opt.dims[1];
-    G.nz = opt.dims[2];
-    for (int r = 0; r < 3; ++r)
-        G.origin[r] = opt.origin[r];
-    G.voxel_size = opt.voxel_size;
-    G.trunc = opt.trunc > 0.0f ? opt.trunc : 3.0f * opt.voxel_size;
-    G.min_weight = opt.min_weight > 0 ? (uint32_t)opt.min_weight : 1u;
-    G.n_views = n_views;
+    if ((rc = check_grid("smvs_tsdf_fuse", opt, n_views, 1024, G)))
+        return rc;
+    size_t const n_vox = (size_t)G.nx * G.ny * G.nz;
+    SMVS_REQUIRE(n_vox <= TSDF_MAX_VOXELS, "the volume has more than 2^27 voxels");
 
     WorkspaceLease lease(device);
     if (lease.w == nullptr)
@@ -689,8 +481,7 @@ smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
     unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(slab + counts_at);
     unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(slab + tiles_at);
 
-    hipLaunchKernelGGL(tsdf_depth_kernel, dim3((unsigned)((s.max_pix + 255) / 256),
-        (unsigned)n_views), dim3(256), 0, stream, s.d_table);
+    launch_depth(stream, s, n_views);
     unsigned const bricks = (unsigned)((G.nx + TSDF_BX - 1) / TSDF_BX)
         * (unsigned)((G.ny + TSDF_BY - 1) / TSDF_BY)
         * (unsigned)((G.nz + TSDF_BZ - 1) / TSDF_BZ);

@@ -1,0 +1,321 @@
+// Pieces of the volumetric fusion that tsdf.hip (the dense volume) and
+// tsdf_sparse.hip (the brick-sparse volume) share: the grid record, the
+// per-element device functions of the definition in include/smvs_hip.h (voxel
+// centre, the projection steps 1-6, the cell / edge / quad rules, the block
+// scan, the vertex attribute arithmetic) and the host side's view upload.
+// The field functions take the field as (pointer, grid): tsdf.hip hands them
+// the volume, tsdf_sparse.hip a brick with its halo staged in LDS.
+#pragma once
+
+#include "common.h"
+#include "mesh_shared.h"
+
+#include <vector>
+
+namespace smvs_hip {
+
+struct TsdfGrid {
+    int nx, ny, nz;
+    float origin[3];
+    float voxel_size, trunc;
+    uint32_t min_weight;
+    int n_views;
+};
+
+struct TsdfImageDev {
+    const uint8_t *image;   // w * h * channels
+    int channels;
+};
+
+// A block is a brick of 8 x 8 x 4 voxels (a wave is one 8 x 8 slab of it), so
+// that the 64 gathers of a wave land in a small patch of each depth map.
+constexpr int TSDF_BX = 8, TSDF_BY = 8, TSDF_BZ = 4;
+
+// the centre of voxel (or grid point) idx along one axis
+__device__ __forceinline__ float
+tsdf_centre(TsdfGrid const &G, int axis, int idx)
+{
+#pragma clang fp contract(off)
+    return G.origin[axis] + ((float)idx + 0.5f) * G.voxel_size;
+}
+
+// Two pieces are macros, not functions: behind a function boundary the compiler
+// gives tsdf_integrate_kernel and tsdf_vertex_kernel other registers and another
+// schedule than they had with the text in their bodies (tools/
+// kernel_isa_diff.py; profiles/tsdf_sparse_kernel_resources.txt), and those
+// kernels keep the code they were measured with.  The text exists once.
+//
+// Field, steps 1-6 for the view V and the voxel centre c, inside a scope with
+// `#pragma clang fp contract(off)`: declares pj (the pixel) and sdf, or leaves
+// through SKIP (`continue`, `return false`)
+#define TSDF_STEPS_1_TO_6(V, c, trunc, SKIP)                                     \
+    float proj[3];                                                             \
+    proj[0] = dot3((V).KR + 0, c) - (V).t[0];                                  \
+    proj[1] = dot3((V).KR + 3, c) - (V).t[1];                                  \
+    proj[2] = dot3((V).KR + 6, c) - (V).t[2];                                  \
+    if (proj[2] <= 0.0f)                                                       \
+        SKIP;                                                                  \
+    float const u = proj[0] / proj[2];                                         \
+    float const w = proj[1] / proj[2];                                         \
+    if (u < 0.0f || w < 0.0f)                                                  \
+        SKIP;                                                                  \
+    int const xj = (int)u;                                                     \
+    int const yj = (int)w;                                                     \
+    if (xj >= (V).w || yj >= (V).h)                                            \
+        SKIP;                                                                  \
+    size_t const pj = (size_t)yj * (V).w + xj;                                 \
+    float const D = (V).depth_z[pj];                                           \
+    if (D == 0.0f)                                                             \
+        SKIP;                                                                  \
+    float const sdf = D - proj[2];                                             \
+    if (sdf < -(trunc))                                                        \
+        SKIP
+
+// steps 1-6 as a function: false where the view is skipped, else the pixel the
+// voxel centre falls into and its signed distance
+__device__ __forceinline__ bool
+tsdf_project(MeshViewDev const &V, const float *c, float trunc, size_t *pixel, float *sdf_out)
+{
+#pragma clang fp contract(off)
+    TSDF_STEPS_1_TO_6(V, c, trunc, return false);
+    *pixel = pj;
+    *sdf_out = sdf;
+    return true;
+}
+
+// ----------------------------------------------------------------- extraction
+// Cells and grid points share the points' linear index (x fastest): cell
+// (i, j, k) is the one whose corner 0 is point (i, j, k).
+
+__device__ __forceinline__ size_t
+tsdf_index(TsdfGrid const &G, int i, int j, int k)
+{
+    return ((size_t)k * G.ny + j) * G.nx + i;
+}
+
+// the cell's corners c = dx + 2 dy + 4 dz; -> complete (in the grid, no NaN)
+__device__ __forceinline__ bool
+tsdf_cell(const float *__restrict__ tsdf, TsdfGrid const &G, int i, int j, int k, float *f)
+{
+    if (i < 0 || j < 0 || k < 0 || i > G.nx - 2 || j > G.ny - 2 || k > G.nz - 2)
+        return false;
+    bool complete = true;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        f[c] = tsdf[tsdf_index(G, i + (c & 1), j + (c >> 1 & 1), k + (c >> 2))];
+        complete = complete && !(f[c] != f[c]);
+    }
+    return complete;
+}
+
+__device__ __forceinline__ bool
+tsdf_cell_active(const float *__restrict__ tsdf, TsdfGrid const &G, int i, int j, int k,
+    float *f)
+{
+    if (!tsdf_cell(tsdf, G, i, j, k, f))
+        return false;
+    int inside = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+        inside += f[c] < 0.0f;
+    return inside != 0 && inside != 8;
+}
+
+// the four cells around the edge from point (i, j, k) along axis a, as (b, c)
+// offsets with (a, b, c) cyclic: (-1,-1) (0,-1) (0,0) (-1,0)
+__device__ __forceinline__ void
+tsdf_quad_cell(int a, int q, int i, int j, int k, int *cell)
+{
+    int const ob = (q == 1 || q == 2) ? 0 : -1;
+    int const oc = (q == 2 || q == 3) ? 0 : -1;
+    int off[3] = { 0, 0, 0 };
+    off[(a + 1) % 3] = ob;
+    off[(a + 2) % 3] = oc;
+    cell[0] = i + off[0];
+    cell[1] = j + off[1];
+    cell[2] = k + off[2];
+}
+
+// Faces: bit a set when the edge along axis a has a quad; bit 3: P is inside
+__device__ __forceinline__ int
+tsdf_quads(const float *__restrict__ tsdf, TsdfGrid const &G, int i, int j, int k)
+{
+    int const n[3] = { G.nx, G.ny, G.nz };
+    int const p[3] = { i, j, k };
+    float const fa = tsdf[tsdf_index(G, i, j, k)];
+    if (fa != fa)
+        return 0;
+    int mask = fa < 0.0f ? 8 : 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (p[a] > n[a] - 2)
+            continue;
+        float const fb = tsdf[tsdf_index(G, i + (a == 0), j + (a == 1), k + (a == 2))];
+        if (fb != fb || (fa < 0.0f) == (fb < 0.0f))
+            continue;
+        bool all = true;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (!all)
+                break;
+            int cell[3];
+            float f[8];
+            tsdf_quad_cell(a, q, i, j, k, cell);
+            all = tsdf_cell(tsdf, G, cell[0], cell[1], cell[2], f);
+        }
+        if (all)
+            mask |= 1 << a;
+    }
+    return mask;
+}
+
+// exclusive scan of one 32-bit value per thread over the block of 256 and the
+// block's total; every thread of the block calls it
+__device__ __forceinline__ uint32_t
+tsdf_block_scan(uint32_t v, uint32_t *total)
+{
+    __shared__ uint32_t wsum[4];
+    int const lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        uint32_t const t = __shfl_up(inc, o, 64);
+        if (lane >= o)
+            inc += t;
+    }
+    if (lane == 63)
+        wsum[wave] = inc;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        pre += w < wave ? wsum[w] : 0u;
+        tot += wsum[w];
+    }
+    __syncthreads();
+    *total = tot;
+    return pre + inc - v;
+}
+
+// per thread: active cell (0 / 1) | quads (0..3) << 16, each where asked for
+template <bool CELLS, bool QUADS>
+__device__ __forceinline__ uint32_t
+tsdf_classify(const float *__restrict__ tsdf, TsdfGrid const &G, bool valid, int i, int j,
+    int k, float *f, bool *active, int *quads)
+{
+    *active = false;
+    *quads = 0;
+    if (!valid)
+        return 0;
+    if constexpr (CELLS)
+        *active = tsdf_cell_active(tsdf, G, i, j, k, f);
+    if constexpr (QUADS)
+        *quads = tsdf_quads(tsdf, G, i, j, k);
+    return (uint32_t)*active | (uint32_t)__popc(*quads & 7) << 16;
+}
+
+struct TsdfOut {
+    float *xyz, *nrm, *conf;
+    uint8_t *rgb;
+    uint32_t *faces;
+};
+
+// Vertices: position and normal of the active cell `cell` (int[3], indices in
+// the grid G) with the corner values f, written at rank id; inside a scope
+// with `#pragma clang fp contract(off)` (a macro: see above).  Edges in the
+// definition's order: x (0,1) (2,3) (4,5) (6,7), y (0,2) (1,3) (4,6) (5,7),
+// z (0,4) (1,5) (2,6) (3,7); the two axes other than `axis`, lower first,
+// carry e's bits.
+#define TSDF_VERTEX_GEOMETRY(G, cell, f, id, O)                                  \
+    float sum[3] = { 0.0f, 0.0f, 0.0f }, g[3] = { 0.0f, 0.0f, 0.0f };          \
+    int m = 0;                                                                 \
+    _Pragma("unroll")                                                          \
+    for (int axis = 0; axis < 3; ++axis) {                                     \
+        _Pragma("unroll")                                                      \
+        for (int e = 0; e < 4; ++e) {                                          \
+            int const lo_axis = axis == 0 ? 1 : 0, hi_axis = axis == 2 ? 1 : 2; \
+            int const a = (e & 1) << lo_axis | (e >> 1) << hi_axis;            \
+            int const b = a | 1 << axis;                                       \
+            g[axis] += f[b] - f[a];                                            \
+            if ((f[a] < 0.0f) == (f[b] < 0.0f))                                \
+                continue;                                                      \
+            float const t = f[a] / (f[a] - f[b]);                              \
+            float q[3];                                                        \
+            _Pragma("unroll")                                                  \
+            for (int r = 0; r < 3; ++r)                                        \
+                q[r] = tsdf_centre(G, r, cell[r] + (a >> r & 1));              \
+            q[axis] = q[axis] + t * (G).voxel_size;                            \
+            _Pragma("unroll")                                                  \
+            for (int r = 0; r < 3; ++r)                                        \
+                sum[r] += q[r];                                                \
+            ++m;                                                               \
+        }                                                                      \
+    }                                                                          \
+    for (int r = 0; r < 3; ++r)                                                \
+        (O).xyz[3 * (id) + r] = sum[r] / (float)m;                             \
+    float const len = sqrtf(dot3(g, g));                                       \
+    for (int r = 0; r < 3; ++r)                                                \
+        (O).nrm[3 * (id) + r] = len == 0.0f ? 0.0f : g[r] / len
+
+// Vertices: colour and confidence from the sums over the cell's 8 corners (a
+// macro: see above)
+#define TSDF_VERTEX_ATTRIBUTES(G, Rs, Gs, Bs, Cs, Ws, id, O)                     \
+    (O).rgb[3 * (id) + 0] = Cs == 0 ? 0 : (uint8_t)((2 * Rs + Cs) / (2 * Cs)); \
+    (O).rgb[3 * (id) + 1] = Cs == 0 ? 0 : (uint8_t)((2 * Gs + Cs) / (2 * Cs)); \
+    (O).rgb[3 * (id) + 2] = Cs == 0 ? 0 : (uint8_t)((2 * Bs + Cs) / (2 * Cs)); \
+    (O).conf[id] = (float)Ws / (float)(8 * (G).n_views)
+
+// Faces: the two triangles of a quad with the corners v0 .. v3
+__device__ __forceinline__ void
+tsdf_quad_faces(const uint32_t *v, bool inside, uint32_t *out)
+{
+    out[0] = v[0];
+    out[1] = inside ? v[1] : v[2];
+    out[2] = inside ? v[2] : v[1];
+    out[3] = v[0];
+    out[4] = inside ? v[2] : v[3];
+    out[5] = inside ? v[3] : v[2];
+}
+
+// ----------------------------------------------------------------------- host
+// tsdf.hip: the views' maps and tables in a workspace slab, as the mesh export
+// lays them out, uploaded and prepared (and cut)
+namespace tsdf_host {
+
+struct Carver {
+    size_t total = 0;
+    size_t operator()(size_t bytes)
+    {
+        size_t const at = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return at;
+    }
+};
+
+struct ViewSlab {
+    std::vector<size_t> offsets;   // per view: depth_z, depth_ray, cut, normals, image
+    size_t table_at = 0, images_at = 0, max_pix = 0;
+    std::vector<MeshViewDev> table;
+    std::vector<TsdfImageDev> images;
+    MeshViewDev *d_table = nullptr;
+    TsdfImageDev *d_images = nullptr;
+};
+
+// argument checks shared by the entries (before any device call)
+int check_views(const smvs_point_view *views, int n_views, int cut, bool want_images);
+// smvs_tsdf_options with each dim 2 .. max_dim (1024 or 4096); fills the grid record
+// (`who` heads the error text)
+int check_grid(const char *who, const smvs_tsdf_options &opt, int n_views, int max_dim,
+    TsdfGrid &G);
+// images only where the caller fuses
+void carve_views(const smvs_point_view *views, int n_views, bool want_images, Carver &carve,
+    ViewSlab &s);
+// uploads the views and runs the mesh path's preparation (and cut)
+int upload_and_prepare(Workspace &ws, char *slab, const smvs_point_view *views, int n_views,
+    bool cut, bool want_images, ViewSlab &s);
+// D(p) = depth_z[p] where cut[p] != 0, else 0, in place in depth_z
+void launch_depth(hipStream_t stream, ViewSlab const &s, int n_views);
+
+} // namespace tsdf_host
+
+} // namespace smvs_hip

@@ -1400,14 +1400,27 @@ def tsdf_bounds(cams, depths, normals, cut=True, device=0):
 
 
 def fuse_tsdf(cams, depths, normals, images, origin, voxel_size, dims, trunc=0, min_weight=0,
-              cut=True, volume=False, device=0):
+              cut=True, volume=False, device=0, sparse=False, max_bricks=0, brick_state=False):
     """smvs_tsdf_fuse: the depth maps fused into one surface mesh through a
     truncated signed distance field on the voxel grid (origin, voxel_size,
     dims = (nx, ny, nz)); the definition is in include/smvs_hip.h.  Inputs as
     generate_mesh; normals may be None when cut is off.  trunc <= 0: 3 voxels;
     min_weight <= 0: 1.  Returns the dict generate_mesh returns (xyz, normals,
     rgb, confidence, faces) and, with volume, tsdf (nz, ny, nx) float32 with NaN
-    for unknown and weight (nz, ny, nx) uint32."""
+    for unknown and weight (nz, ny, nx) uint32.
+
+    sparse: smvs_tsdf_fuse_sparse, the same mesh in the brick order from a
+    volume allocated in 8 x 8 x 4 bricks near the surface (dims up to 4096;
+    max_bricks <= 0: 1 << 20).  The dict gains cells (int64, per vertex the
+    cell's linear index in the grid), stats (bricks, seed_bricks,
+    allocated_bricks, state_bytes) and, with brick_state, brick_state
+    (bz, by, bx) uint8: 0 none, 1 allocated, 2 seed.  An SmvsError of status -4
+    (more than max_bricks needed) carries the stats as its `stats`."""
+    if sparse:
+        return _fuse_tsdf_sparse(cams, depths, normals, images, origin, voxel_size, dims, trunc,
+                                 min_weight, cut, volume, device, max_bricks, brick_state)
+    if max_bricks or brick_state:
+        raise ValueError("max_bricks and brick_state belong to sparse=True")
     lib = _capi.load()
     n = len(cams)
     arr, _keep = _tsdf_views(cams, depths, normals, images)
@@ -1442,6 +1455,63 @@ def fuse_tsdf(cams, depths, normals, images, origin, voxel_size, dims, trunc=0, 
     if volume:
         out["tsdf"] = tsdf
         out["weight"] = weight
+    return out
+
+
+def _fuse_tsdf_sparse(cams, depths, normals, images, origin, voxel_size, dims, trunc, min_weight,
+                      cut, volume, device, max_bricks, brick_state):
+    """fuse_tsdf(sparse=True)"""
+    lib = _capi.load()
+    n = len(cams)
+    arr, _keep = _tsdf_views(cams, depths, normals, images)
+    opt = _capi.TsdfOptions()
+    opt.cut_surfaces = int(bool(cut))
+    for k in range(3):
+        opt.origin[k] = float(origin[k])
+        opt.dims[k] = int(dims[k])
+    opt.voxel_size = float(voxel_size)
+    opt.trunc = float(trunc)
+    opt.min_weight = int(min_weight)
+    sopt = _capi.TsdfSparseOptions()
+    sopt.max_bricks = int(max_bricks)
+    stats = _capi.TsdfSparseStats()
+    shape = tuple(max(int(d), 0) for d in dims)[::-1]
+    tsdf = weight = state = None
+    if volume:
+        tsdf = np.zeros(shape, np.float32)
+        weight = np.zeros(shape, np.uint32)
+    if brick_state:
+        state = np.zeros((-(-shape[0] // 4), -(-shape[1] // 8), -(-shape[2] // 8)), np.uint8)
+    handle = C.c_void_p()
+    n_vertices, n_faces = C.c_int64(), C.c_int64()
+    rc = lib.smvs_tsdf_fuse_sparse(device, arr if n else None, n, C.byref(opt), C.byref(sopt),
+                                   _p(state, _u8p), _p(tsdf, _fp), _p(weight, _u32p),
+                                   C.byref(stats), C.byref(handle), C.byref(n_vertices),
+                                   C.byref(n_faces))
+    if rc != 0:
+        err = _capi.SmvsError(rc, lib.smvs_last_error().decode())
+        if rc == -4:
+            err.stats = stats.as_dict()
+        raise err
+    try:
+        k = n_vertices.value
+        out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
+               "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
+               "faces": np.zeros((n_faces.value, 3), np.uint32),
+               "cells": np.zeros(k, np.int64)}
+        check(lib.smvs_points_download(handle, _p(out["xyz"], _fp), _p(out["normals"], _fp),
+                                       _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
+                                       None, _p(out["faces"], _u32p)))
+        check(lib.smvs_tsdf_vertex_cells(handle, out["cells"].ctypes.data_as(
+            C.POINTER(C.c_int64))))
+    finally:
+        lib.smvs_points_release(handle)
+    out["stats"] = stats.as_dict()
+    if volume:
+        out["tsdf"] = tsdf
+        out["weight"] = weight
+    if brick_state:
+        out["brick_state"] = state
     return out
 
 

@@ -1006,9 +1006,14 @@ class FusedSettings(C.Structure):
                 ("min_weight", C.c_int)]
 
 
+class FusedSparseSettings(C.Structure):
+    _fields_ = [("voxel_size", C.c_float), ("resolution", C.c_int), ("trunc", C.c_float),
+                ("min_weight", C.c_int), ("max_bricks", C.c_int64)]
+
+
 def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=0, min_weight=0,
                    view_ids=None, image_embedding="undistorted", input_scale=0,
-                   use_shading=False, cut=True, device=0):
+                   use_shading=False, cut=True, device=0, sparse=False, max_bricks=0):
     """Not in the reference: the views' smvs-{B,S}<input_scale> depth maps fused
     into ONE surface mesh through a truncated signed distance field
     (smvs_tsdf_fuse), written as
@@ -1016,16 +1021,29 @@ def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=
     or the bounds of the (cut) depth maps' points padded by the truncation
     distance; voxel_size None: the box's longest side / resolution; trunc 0: 3
     voxels; min_weight 0: 1.  Returns (ply path, number of vertices, number of
-    faces)."""
+    faces).
+
+    sparse: the volume is allocated in 8 x 8 x 4 bricks near the surface
+    (smvs_tsdf_fuse_sparse, section 9.9): the same mesh with vertices and faces
+    in the brick order, under the same file name; resolution may go up to 4096;
+    max_bricks 0: 1 << 20 bricks."""
     lib = load()
     st = _point_cloud_settings(image_embedding, input_scale, use_shading, cut, aabb, True,
                                False, device)
-    fs = FusedSettings(0.0 if voxel_size is None else float(voxel_size), int(resolution),
-                       float(trunc), int(min_weight))
+    if sparse:
+        fs = FusedSparseSettings(0.0 if voxel_size is None else float(voxel_size),
+                                 int(resolution), float(trunc), int(min_weight), int(max_bricks))
+        entry = lib.smvs_host_generate_fused_sparse
+    else:
+        if max_bricks:
+            raise ValueError("max_bricks belongs to sparse=True")
+        fs = FusedSettings(0.0 if voxel_size is None else float(voxel_size), int(resolution),
+                           float(trunc), int(min_weight))
+        entry = lib.smvs_host_generate_fused
     ids = None if view_ids is None else np.asarray(view_ids, dtype=np.int32)
     path = C.create_string_buffer(4096)
     nv, nf = C.c_int64(0), C.c_int64(0)
-    rc = lib.smvs_host_generate_fused(
+    rc = entry(
         scene_dir.encode(), C.byref(st), C.byref(fs),
         ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), path, C.c_int(len(path)), C.byref(nv),

@@ -12,6 +12,14 @@ tools/points_bench.py's (the 16 views repeat the nine synthetic ones).
 
     python tools/tsdf_bench.py [--dims N] [--views N] [--size W H] [--reps N]
                                [--no-kernels] [--no-peaks]
+                               [--sparse [--resolution N] [--max-bricks N]]
+
+--sparse times smvs_tsdf_fuse_sparse (the brick-sparse volume, DESIGN.md section
+9.9) on the same case instead: --resolution N is --dims N and may go up to
+4096.  The entry's line carries the stats (bricks, seed and allocated bricks,
+state bytes, the dense volume's would-be bytes); the seed kernel's line its
+time per 1000 (voxel, view) pairs of the whole box, the integration kernel's
+its time per 1000 pairs of the allocated bricks.
 """
 import argparse
 import csv
@@ -31,6 +39,11 @@ import numpy as np  # noqa: E402
 KERNELS = ["mesh_prepare_kernel", "mesh_cut_kernel", "tsdf_depth_kernel", "tsdf_integrate_kernel",
            "tsdf_classify_kernel", "scan_tile_sums_kernel", "scan_tiles_kernel",
            "scan_apply_kernel", "tsdf_vertex_kernel", "tsdf_face_kernel"]
+SPARSE_KERNELS = ["mesh_prepare_kernel", "mesh_cut_kernel", "tsdf_depth_kernel",
+                  "tsdf_sparse_seed_kernel", "tsdf_sparse_dilate_kernel",
+                  "tsdf_sparse_table_kernel", "tsdf_sparse_integrate_kernel",
+                  "tsdf_sparse_classify_kernel", "scan_tile_sums_kernel", "scan_tiles_kernel",
+                  "scan_apply_kernel", "tsdf_sparse_vertex_kernel", "tsdf_sparse_face_kernel"]
 CHILD_REPS = 3
 BOX_LO, BOX_SIDE = (-1.3, -1.3, 2.7), 2.6
 
@@ -41,11 +54,15 @@ def case(args):
     return cams, depths, normals, images, BOX_LO, BOX_SIDE / args.dims, (args.dims,) * 3
 
 
+def sparse_args(args):
+    return {"sparse": True, "max_bricks": args.max_bricks} if args.sparse else {}
+
+
 def child(args):
     from smvs_amd import device
     c = case(args)
     for _ in range(CHILD_REPS):
-        device.fuse_tsdf(*c, cut=True)
+        device.fuse_tsdf(*c, cut=True, **sparse_args(args))
 
 
 def kernel_times(args):
@@ -55,17 +72,20 @@ def kernel_times(args):
                "--", sys.executable, os.path.abspath(__file__), "--child", "--dims",
                str(args.dims), "--views", str(args.views), "--size", str(args.size[0]),
                str(args.size[1])]
+        if args.sparse:
+            cmd += ["--sparse", "--max-bricks", str(args.max_bricks)]
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         if res.returncode != 0:
             raise RuntimeError("rocprofv3 failed: " + res.stderr[-2000:])
         files = glob.glob(os.path.join(tmp, "**", "*kernel_trace.csv"), recursive=True)
         if not files:
             raise RuntimeError("rocprofv3 left no kernel trace")
-        rows = {k: [] for k in KERNELS}
+        names = SPARSE_KERNELS if args.sparse else KERNELS
+        rows = {k: [] for k in names}
         for fn in files:
             with open(fn) as f:
                 for r in csv.DictReader(f):
-                    for k in KERNELS:
+                    for k in names:
                         if k in r["Kernel_Name"]:
                             rows[k].append((int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
     out = {}
@@ -80,6 +100,24 @@ def kernel_times(args):
     return out
 
 
+def sparse_kernel_lines(args, kt, stats, n_vox):
+    for k in SPARSE_KERNELS:
+        per, t = kt[k]
+        rec = {"case": "sparse_kernel", "kernel": k, "launches_per_call": per,
+               "ms_per_call_best": round(1e3 * t, 4)}
+        if k == "tsdf_sparse_seed_kernel":
+            rec.update({"voxel_views": n_vox * args.views,
+                        "ns_per_1000_voxel_views": round(1e12 * t / (n_vox * args.views), 4)})
+        if k == "tsdf_sparse_integrate_kernel" and stats["allocated_bricks"]:
+            pairs = 256 * stats["allocated_bricks"] * args.views
+            rec.update({"voxel_views": pairs,
+                        "ns_per_1000_voxel_views": round(1e12 * t / pairs, 3)})
+        print(json.dumps(rec), flush=True)
+    print(json.dumps({"case": "sparse_kernels_total",
+                      "ms_per_call_best": round(1e3 * sum(t for _, t in kt.values()), 3)}),
+          flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
@@ -89,7 +127,14 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--no-peaks", action="store_true")
+    ap.add_argument("--sparse", action="store_true", help="smvs_tsdf_fuse_sparse")
+    ap.add_argument("--resolution", type=int, help="with --sparse: --dims, up to 4096")
+    ap.add_argument("--max-bricks", type=int, default=0)
     args = ap.parse_args()
+    if args.resolution is not None:
+        if not args.sparse:
+            ap.error("--resolution belongs to --sparse")
+        args.dims = args.resolution
     if args.child:
         child(args)
         return
@@ -98,20 +143,30 @@ def main():
     if smvs_amd.device_count() < 1:
         raise SystemExit("tsdf_bench needs a GPU")
     c = case(args)
+    n_vox = args.dims ** 3
     times = []
     for _ in range(args.reps + 1):
         t0 = time.perf_counter()
-        out = device.fuse_tsdf(*c, cut=True)
+        out = device.fuse_tsdf(*c, cut=True, **sparse_args(args))
         times.append(time.perf_counter() - t0)
-    n_vox = args.dims ** 3
     pixels = args.size[0] * args.size[1] * args.views
-    print(json.dumps({"case": "entry", "dims": [args.dims] * 3, "views": args.views,
-                      "size": args.size, "cut": True, "vertices": len(out["xyz"]),
-                      "faces": len(out["faces"]), "fuse_ms_first": round(1e3 * times[0], 2),
-                      "fuse_ms_best": round(1e3 * min(times[1:]), 2)}), flush=True)
+    entry = {"case": "sparse_entry" if args.sparse else "entry", "dims": [args.dims] * 3,
+             "views": args.views, "size": args.size, "cut": True, "vertices": len(out["xyz"]),
+             "faces": len(out["faces"]), "fuse_ms_first": round(1e3 * times[0], 2),
+             "fuse_ms_best": round(1e3 * min(times[1:]), 2)}
+    if args.sparse:
+        st = out["stats"]
+        entry.update(st)
+        entry.update({"max_bricks": args.max_bricks or 1 << 20,
+                      "allocated_share": round(st["allocated_bricks"] / st["bricks"], 5),
+                      "dense_state_bytes": 28 * n_vox})
+    print(json.dumps(entry), flush=True)
     if args.no_kernels:
         return
     kt = kernel_times(args)
+    if args.sparse:
+        sparse_kernel_lines(args, kt, out["stats"], n_vox)
+        return
     copy_peak = None
     if not args.no_peaks:
         import peaks
