@@ -11,14 +11,21 @@ namespace smvs_hip {
 
 constexpr int RES_WAVES = RES_THREADS / 64;
 
-// Exchange area (zeroed before every launch).  A double travels as two
-// 8-byte granules {tag = epoch, 32 data bits}: the data is its own flag
-// (cdna_hip_programming.md Guideline 16, form R2), so one sweep over the
-// granules of all workgroups is barrier and all-reduce at once.
+// Exchange area.  Zeroed when it is allocated, when the 15-bit solve id starts
+// over and after a solve that gave up -- NOT before every launch: every tag
+// carries the solve id (solve_tag | epoch), so what earlier solves left behind
+// never matches.  A double travels as two 8-byte granules {tag, 32 data bits}:
+// the data is its own flag (cdna_hip_programming.md Guideline 16, form R2), so
+// one sweep over the granules of all workgroups is barrier and all-reduce at
+// once.
 constexpr int RES_KINDS = 8;                 // doubles per all-reduce, at most
 constexpr int RES_GROUP = 16;                                  // workgroups per first-level group
 constexpr int RES_MAX_GROUPS = RES_MAX_BLOCKS / RES_GROUP;
 constexpr int RES_REPLICAS = 16;                               // copies of the group sums
+constexpr int RES_DIRECT_GROUPS = 5;     // direct gather: groups per sweeping lane, at most
+// ... and up to how many groups a grid gathers directly by default (measured,
+// profiles/cg_direct_gather.txt)
+constexpr int RES_DIRECT_GROUPS_DEFAULT = 5;
 struct ResExchange {
     // flat all-reduce (two-exchange solver): every workgroup sweeps all of these
     unsigned long long gran[2][2 * RES_KINDS][RES_MAX_BLOCKS];   // [parity][..][wg]
@@ -43,7 +50,8 @@ struct ResExchange {
 // them out of the tree changes no bit of any total.
 struct LiveSet {
     bool leads;         // this workgroup sums its group (wave-uniform)
-    unsigned bits;      // lane (kind, j): bit 0 member j of its group is live, bit 1 group j is
+    unsigned bits;      // lane (kind, j): bit 0 member j of its group is live, bit 1 group j is,
+                        // bit 2 + g member j of group g < RES_DIRECT_GROUPS is (direct gather)
 };
 
 __device__ __forceinline__ void
@@ -446,6 +454,62 @@ poll_pairs(__amdgpu_buffer_rsrc_t buf, unsigned byte_offset, bool active, unsign
     return good;
 }
 
+// The direct gather's poll: lane (kind, j) waits for member j of each of G
+// groups, `stride` bytes apart (bit g of `active`: that member takes part),
+// with all its outstanding pairs in flight at once; a pair that has arrived is
+// not loaded again.  Members that take no part give 0.  Wave-uniform result:
+// false after a bounded wait.
+template <int G>
+__device__ __forceinline__ bool
+poll_group_pairs(__amdgpu_buffer_rsrc_t buf, unsigned byte_offset, unsigned stride,
+    unsigned active, unsigned tag, ResExchange *ex, double (&value)[G], int gap = 0,
+    unsigned *rounds = nullptr)
+{
+    // (the pairs stay in the registers they were loaded into: the kernel has
+    // none to spare)
+    uint4_r w[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+        w[g] = (uint4_r){ 0u, 0u, 0u, 0u };
+    unsigned pending = active;
+    bool good = true;
+    for (unsigned spins = 0;; ++spins) {
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+            if ((pending >> g) & 1u)
+                w[g] = __builtin_amdgcn_raw_buffer_load_b128(buf, (int)byte_offset,
+                    (int)((unsigned)g * stride), AUX_SC1);
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+            if (w[g].y == tag && w[g].w == tag)
+                pending &= ~(1u << g);
+        if (__all(pending == 0u))
+            break;
+        if (rounds != nullptr)
+            *rounds += 1;
+        if (spins > (1u << 18)
+            || ((spins & 255u) == 255u
+                && __hip_atomic_load(&ex->timeout, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
+            __hip_atomic_store(&ex->timeout, 1u, __ATOMIC_RELAXED,
+                __HIP_MEMORY_SCOPE_AGENT);
+            good = false;
+            break;
+        }
+        __builtin_amdgcn_s_sleep(1);
+        nap(gap);
+        asm volatile("" ::: "memory");
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+        value[g] = ((active >> g) & 1u)
+            ? __longlong_as_double((long long)(((unsigned long long)w[g].z << 32) | w[g].x))
+            : 0.0;
+    if (rounds != nullptr)
+        *rounds += 1;
+    return good;
+}
+
 // Sum over the 16 / 32 lanes of an aligned segment, fixed order, every lane gets it.
 __device__ __forceinline__ double
 segment16_sum(double v)
@@ -524,7 +588,29 @@ partial_tags(double *red)
 // Same guarantees as the flat form: fixed summation order (a tree over the
 // members of a group, then a tree over the groups), bit-identical results in
 // every workgroup, slots double-buffered by epoch parity, bounded waits.
-template <int K, typename Others, typename Mark>
+//
+// The direct gather (DIRECT: 1 < ngroups <= RES_DIRECT_GROUPS, the same in
+// every workgroup of a launch: the host chooses by nblocks alone).  The same
+// tree in ONE hop: nobody leads, nothing goes to lvl2 or through the mailbox;
+// lane (kind, j) of every workgroup polls member j of EVERY group, all pairs
+// in flight at once -- 75 x K pairs per workgroup at 75 tiles, no dependent
+// second hand-off across CUs (6.4 instead of 7.1 us per iteration there).  The totals keep the bits of the two-level form:
+// part_g = segment16_sum(members of group g) is what group g's leader computes,
+// on the same lane positions; every lane of the segment holds every part_g, lane
+// j keeps part_j (0.0 for j >= ngroups) and the segment runs segment16_sum
+// again: the tree over the groups on the lanes the second hop uses.  A group
+// that is wholly dead gives segment16_sum of zeros = +0.0 where the second hop
+// takes a literal 0.0 for the lane it does not poll: the same bits.
+// Slot reuse with every workgroup as reader of every lvl1 slot: a workgroup
+// publishes epoch e + 2 only after it has the totals of e + 1; those exist only
+// after every workgroup published e + 1; and every workgroup published e + 1
+// only after it had finished reading e (its sweepers' values are in res[]
+// behind the barrier that ends e).  So nobody still reads the slot of parity e
+// when e + 2 is written into it.
+// DIRECT is a compile-time choice (kernels of their own, see cg_resident.hip);
+// the host launches such a kernel only on grids of at most RES_DIRECT_GROUPS
+// groups.
+template <int K, bool DIRECT, typename Others, typename Mark>
 __device__ __forceinline__ bool
 grid_allreduce_tree(ResExchange *ex, unsigned solve_tag, unsigned epoch, int nblocks,
     LiveSet const live, double (&v)[K], double *red, int *lds_flag, Others others, Mark mark,
@@ -552,7 +638,7 @@ grid_allreduce_tree(ResExchange *ex, unsigned solve_tag, unsigned epoch, int nbl
                    * RES_KINDS + (size_t)kind) * 16));
     };
     int const ngroups = (nblocks + RES_GROUP - 1) / RES_GROUP;
-    bool const leads = live.leads;
+    bool const leads = !DIRECT && live.leads;
     bool const member_live = (live.bits & 1u) != 0u, group_live = (live.bits & 2u) != 0u;
     int const wave = (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (wave == RES_SUM_WAVE) {
@@ -588,6 +674,27 @@ grid_allreduce_tree(ResExchange *ex, unsigned solve_tag, unsigned epoch, int nbl
             // one hop instead of two
             ok = poll_pairs(xbuf, lvl1_at(j < nblocks ? j : 0, kind_ok ? kind : 0),
                 kind_ok && j < nblocks && member_live, tag, ex, &total, wait_poll);
+            total = segment16_sum(total);
+        } else if constexpr (DIRECT) {
+            // the direct gather: member j of every group, then both levels of
+            // the tree on this segment
+            unsigned active = 0u;
+#pragma unroll
+            for (int g = 0; g < RES_DIRECT_GROUPS; ++g)
+                if (kind_ok && RES_GROUP * g + j < nblocks && ((live.bits >> (2 + g)) & 1u))
+                    active |= 1u << g;
+            double part[RES_DIRECT_GROUPS];
+            ok = poll_group_pairs<RES_DIRECT_GROUPS>(xbuf, lvl1_at(j, kind_ok ? kind : 0),
+                (unsigned)(RES_GROUP * RES_KINDS * 16), active, tag, ex, part, wait_poll,
+                &rounds1);
+            mark(5, -1);
+            mark(9, -1);
+            total = 0.0;
+#pragma unroll
+            for (int g = 0; g < RES_DIRECT_GROUPS; ++g) {
+                double const sum_g = segment16_sum(part[g]);
+                total = j == g && g < ngroups ? sum_g : total;
+            }
             total = segment16_sum(total);
         } else {
             if (leads) {

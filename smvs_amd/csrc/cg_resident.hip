@@ -46,6 +46,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <string>
 
 namespace smvs_hip {
@@ -368,7 +369,16 @@ resident_lds_layout(int tw, int th, bool one)
 // BEFORE the all-reduce and collected by the wave that does not sweep, while
 // the sweep runs), so it forms the halo's z and d itself, bit-identical with
 // the owner's.
-template <bool FUSED, bool ONE, bool TRACE>
+//
+// DIRECT (one-exchange solver only): the all-reduce gathers in one hop, for
+// grids of 2 .. RES_DIRECT_GROUPS groups of RES_GROUP tiles (cg_exchange.h,
+// "the direct gather").  It is compiled into instantiations of its own,
+// which the host launches on such grids only (resident_enqueue): the pairs in flight per sweeping lane cost
+// registers in a kernel that has none to spare, and with both forms in one
+// kernel the register allocation of EVERY grid's iteration moved (three more
+// spill reloads in the loop, 0.5 - 0.8 us per iteration at 16, 75 and 256
+// tiles: profiles/cg_direct_gather.txt).
+template <bool FUSED, bool ONE, bool TRACE, bool DIRECT = false>
 __global__ void __launch_bounds__(RES_THREADS, 2)
 cg_resident_kernel(ResArgs A)
 {
@@ -1015,7 +1025,7 @@ cg_resident_kernel(ResArgs A)
         LiveSet live;
         int const ngroups_all = (nblocks + RES_GROUP - 1) / RES_GROUP;
         live.leads = ngroups_all > 1 && tile % RES_GROUP == 0;
-        live.bits = 3u;
+        live.bits = DIRECT ? 3u | (((1u << RES_DIRECT_GROUPS) - 1u) << 2) : 3u;
         if (compact) {
             // (a map that did not arrive: the solve is given up, and since nobody
             // knows who the first live tile is, every workgroup says so)
@@ -1032,6 +1042,13 @@ cg_resident_kernel(ResArgs A)
                 && (int)__builtin_ctz(mine16) == tile - member0;
             live.bits = (member0 + j < nblocks && tile_live(member0 + j) ? 1u : 0u)
                 | (j < ngroups_all && group_live(j) ? 2u : 0u);
+            // (the direct gather: member j of each group)
+            if constexpr (DIRECT) {
+#pragma unroll
+                for (int g = 0; g < RES_DIRECT_GROUPS; ++g)
+                    if (RES_GROUP * g + j < nblocks && tile_live(RES_GROUP * g + j))
+                        live.bits |= 4u << g;
+            }
             // the first live tile reports the result
             reporter = 0;
             for (int w = RES_MAX_BLOCKS / 64 - 1; w >= 0; --w)
@@ -1151,8 +1168,8 @@ cg_resident_kernel(ResArgs A)
                     skew(k, 3, 0);
                 }
             };
-            alive = grid_allreduce_tree<8>(A.ex, ztag, epoch++, nblocks, live, v8, red, flag,
-                other_waves, sweep_mark, A.wait_member, A.wait_poll);
+            alive = grid_allreduce_tree<8, DIRECT>(A.ex, ztag, epoch++, nblocks, live, v8, red,
+                flag, other_waves, sweep_mark, A.wait_member, A.wait_poll);
             if (!alive)
                 break;
             stamp(k, 3);
@@ -1459,7 +1476,9 @@ resident_enqueue(smvs_ctx *ctx, int max_iterations, double error_tolerance,
         ctx->res_zx_cap = zx_nodes;
     }
     {
-        const void *kernels[5] = {
+        const void *kernels[7] = {
+            reinterpret_cast<const void *>(cg_resident_kernel<false, true, false, true>),
+            reinterpret_cast<const void *>(cg_resident_kernel<true, true, false, true>),
             reinterpret_cast<const void *>(cg_resident_kernel<false, false, false>),
             reinterpret_cast<const void *>(cg_resident_kernel<true, false, false>),
             reinterpret_cast<const void *>(cg_resident_kernel<false, true, false>),
@@ -1539,6 +1558,24 @@ resident_enqueue(smvs_ctx *ctx, int max_iterations, double error_tolerance,
         }();
         A.compact = compact;
     }
+    // which form the all-reduce of the one-exchange solver takes, by the number
+    // of groups of RES_GROUP tiles alone: SMVS_CG_GATHER=tree (two levels
+    // whenever there is more than one group), direct (one hop up to
+    // RES_DIRECT_GROUPS groups) or the largest number of groups that gathers in
+    // one hop.  The totals have the same bits either way.
+    static int const direct_groups = [] {
+        const char *e = std::getenv("SMVS_CG_GATHER");
+        if (e == nullptr || e[0] == '\0')
+            return RES_DIRECT_GROUPS_DEFAULT;
+        if (std::strcmp(e, "tree") == 0)
+            return 0;
+        if (std::strcmp(e, "direct") == 0)
+            return RES_DIRECT_GROUPS;
+        return std::min(std::max(std::atoi(e), 0), RES_DIRECT_GROUPS);
+    }();
+    int const ngroups = (num_tiles + RES_GROUP - 1) / RES_GROUP;
+    // (the stamps of tools/cg_trace.py exist in the two-level kernels only)
+    bool const direct = one && trace_dev == nullptr && ngroups > 1 && ngroups <= direct_groups;
     A.trace = trace_dev;
     {
         static int const wg = [] {
@@ -1557,7 +1594,11 @@ resident_enqueue(smvs_ctx *ctx, int max_iterations, double error_tolerance,
                 ctx->stream, A);
         };
         // (stamps: the fused one-exchange kernel only, what tools/cg_trace.py runs)
-        if (fused && one && trace_dev != nullptr)
+        if (direct && fused)
+            launch(cg_resident_kernel<true, true, false, true>);
+        else if (direct)
+            launch(cg_resident_kernel<false, true, false, true>);
+        else if (fused && one && trace_dev != nullptr)
             launch(cg_resident_kernel<true, true, true>);
         else if (fused && one)
             launch(cg_resident_kernel<true, true, false>);
