@@ -110,10 +110,19 @@ mesh_cut_kernel(const MeshViewDev *__restrict__ views, int n_views, int i)
         proj[2] = dot3(N.KR + 6, pos) - N.t[2];
         if (proj[2] < 0)
             continue;
-        int const xj = (int)(proj[0] / proj[2]);
-        int const yj = (int)(proj[1] / proj[2]);
-        if (xj < 0 || xj >= N.w || yj < 0 || yj >= N.h)
+        // A point in view j's principal plane (proj[2] == 0, or NaN): the
+        // reference's quotient is infinite or NaN, its static_cast<int> gives
+        // INT_MIN on x86 and the pair is skipped.  A saturating conversion
+        // would turn NaN into column 0.
+        if (!(proj[2] > 0))
             continue;
+        // (int) truncates toward zero, so a quotient in (-1, 0) is column or
+        // row 0; the range is tested on the float, and only a finite quotient
+        // inside it is converted
+        float const qx = proj[0] / proj[2], qy = proj[1] / proj[2];
+        if (!(qx > -1.0f && qx < (float)N.w && qy > -1.0f && qy < (float)N.h))
+            continue;
+        int const xj = (int)qx, yj = (int)qy;
         size_t const pj = (size_t)yj * N.w + xj;
         float const dm_j = N.depth_z[pj];
         if (dm_j == 0.0f)
