@@ -1410,6 +1410,97 @@ int smvs_tsdf_fuse_sparse(int device, const smvs_point_view *views, int n_views,
 
 int smvs_tsdf_vertex_cells(const smvs_points *handle, int64_t *cell);
 
+/* smvs_tsdf_fuse_sparse with a brick cull in front of its seed pass (opt-in
+ * through cull != 0).  The cull decides nothing: a
+ * brick it drops provably holds no seed voxel, so brick_state, the stats, the
+ * volume and the mesh are smvs_tsdf_fuse_sparse's to the bit; only the number
+ * of bricks the exact seed test of step 8 runs on changes.  This comment is
+ * the definition of the candidates; tests/tsdf_cull_ref.py restates it.  All of
+ * it is double arithmetic, one operation per operation written here, no
+ * contraction, sums from left to right; only the pyramid is float, and min and
+ * max are exact.
+ *
+ * Pyramid, per view, of D (the prepared and cut z-depth of smvs_tsdf_fuse).
+ *   level 0    implicit: texel (x, y) = (lo, hi) = (D, D) where D < 0 or D > 0,
+ *              else (D is 0 or NaN: no such pixel passes steps 5-8)
+ *              (+inf, -inf).  It is read from D and not stored.
+ *   level l+1  ceil(w_l / 2) x ceil(h_l / 2) texels; texel (x, y) is the min of
+ *              lo and the max of hi over the level-l texels (2x .. 2x + 1,
+ *              2y .. 2y + 1) that exist.  The levels end at 1 x 1: a 1 x 1 map
+ *              has level 0 only.
+ *
+ * Box of brick (bi, bj, bk): per axis a, with i0 the brick's first voxel index
+ * and i1 its last clipped to dims[a] - 1, lo[a] = (double)c(i0), hi[a] =
+ * (double)c(i1), c the float voxel centre of smvs_tsdf_fuse.  Float rounding
+ * is monotone, so every voxel centre of the brick lies in the box.
+ *
+ * Per view, per row r of KR and t (widened to double):
+ *   a = 0, b = 0, mag = |t[r]|; for k = 0, 1, 2: p = KR[r][k] * lo[k],
+ *   q = KR[r][k] * hi[k], a = a + min(p, q), b = b + max(p, q),
+ *   mag = mag + |KR[r][k]| * max(|lo[k]|, |hi[k]|)
+ *   e = 2^-21 * mag + 2^-140
+ *   P_lo[r] = (a - t[r]) - e, P_hi[r] = (b - t[r]) + e
+ * The float proj[r] of step 1 of every voxel of the brick lies in [P_lo[r],
+ * P_hi[r]]: 2^-21 = 8 u bounds the five float roundings of dot3(...) - t and
+ * leaves 3 u for the double roundings here; 2^-140 covers three products that
+ * underflow.  If any of the six is not finite the view may seed the brick.
+ * Else, with zlo = P_lo[2], zhi = P_hi[2]:
+ *   zhi <= 0         the view cannot seed the brick (step 2).
+ *   zlo <= 0 < zhi   the pixel range is the whole image.
+ *   otherwise        per image axis (r = 0 with n = width, r = 1 with n =
+ *                    height): ulo = min(P_lo[r] / zlo, P_lo[r] / zhi), uhi =
+ *                    max(P_hi[r] / zlo, P_hi[r] / zhi), both clamped to
+ *                    [-4, n + 4]; first = floor(ulo) - 1, last = floor(uhi) + 1
+ *                    (the pixel of slack covers the float division of step 3);
+ *                    last < 0 or first > n - 1: the view cannot seed the
+ *                    brick; else first and last are clipped to 0 .. n - 1.
+ * The level is the smallest l with (x_last >> l) - (x_first >> l) <= 1 and the
+ * same in y; dlo and dhi are the min of lo and the max of hi over the texels
+ * (x_first >> l | x_last >> l, y_first >> l | y_last >> l) of that level.
+ * dlo > dhi (no valid pixel): the view cannot seed the brick.  Otherwise, with
+ * T = (double)trunc * (1 + 2^-22), the view may seed the brick exactly when
+ *   dhi >= max(zlo, 0) - T  and  dlo <= zhi + T.
+ * A brick is a candidate when some view may seed it.  DESIGN.md section 9.10
+ * proves seed brick => candidate, one inequality per step 1-6 and 8.
+ *
+ * cull == 0: exactly the launches of smvs_tsdf_fuse_sparse (which forwards
+ * here); tested_bricks == bricks and brick_candidate is all 1.  cull != 0: the
+ * pyramids (at most 8 w h / 3 bytes per view beside the maps), the cull, and
+ * the seed pass on the candidates alone; tested_bricks is their number.
+ * brick_candidate (may be NULL): bx * by * bz bytes, 1 where the exact seed
+ * test ran.  Everything else, the refusals and SMVS_ERR_NOMEM (which leaves
+ * stats and both brick arrays filled) are smvs_tsdf_fuse_sparse's. */
+typedef struct {
+    int64_t max_bricks;
+    int cull;
+} smvs_tsdf_sparse_opts;
+
+typedef struct {
+    int64_t bricks, seed_bricks, allocated_bricks, state_bytes, tested_bricks;
+} smvs_tsdf_sparse_opts_stats;
+
+int smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views,
+    const smvs_tsdf_options *options, const smvs_tsdf_sparse_opts *sparse,
+    uint8_t *brick_state, uint8_t *brick_candidate, float *tsdf, uint32_t *weight,
+    smvs_tsdf_sparse_opts_stats *stats, smvs_points **handle, int64_t *n_vertices,
+    int64_t *n_faces);
+
+/* The preparation, the pyramids and the cull of smvs_tsdf_fuse_sparse_opts
+ * alone: brick_candidate (bx * by * bz bytes) and their number (n_candidates
+ * may be NULL).  Refuses what smvs_tsdf_fuse_sparse refuses for the views and
+ * the grid, before any device call; images are not read and may be NULL. */
+int smvs_tsdf_brick_cull(int device, const smvs_point_view *views, int n_views,
+    const smvs_tsdf_options *options, uint8_t *brick_candidate, int64_t *n_candidates);
+
+/* One view's pyramid as smvs_tsdf_fuse_sparse_opts builds it (all views are
+ * prepared, and cut with cut_surfaces and n_views > 1): the levels >= 1, each
+ * row-major, concatenated from level 1 to the 1 x 1 level, lo and hi apart
+ * (either may be NULL; both NULL: only the counts, no device call).  n_texels
+ * and n_levels (may be NULL): the texels per array and the number of levels
+ * >= 1; a 1 x 1 view has none. */
+int smvs_tsdf_depth_pyramid(int device, const smvs_point_view *views, int n_views,
+    int cut_surfaces, int view, float *lo, float *hi, int64_t *n_texels, int *n_levels);
+
 /* The componentwise minimum and maximum of world_point over the valid
  * (non-zero) pixels of the maps smvs_tsdf_fuse would fuse: the cut maps with
  * cut_surfaces and n_views > 1, else the depth maps (image and channels are not

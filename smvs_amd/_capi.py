@@ -64,6 +64,19 @@ class TsdfSparseStats(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class TsdfSparseOpts(C.Structure):
+    """smvs_tsdf_sparse_opts of include/smvs_hip.h."""
+    _fields_ = [("max_bricks", C.c_int64), ("cull", C.c_int)]
+
+
+class TsdfSparseOptsStats(C.Structure):
+    """smvs_tsdf_sparse_opts_stats of include/smvs_hip.h."""
+    _fields_ = TsdfSparseStats._fields_ + [("tested_bricks", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 K_NAMES = ["patch", "assemble", "cg_spmv", "cg_update", "cg_init",
            "reactivate", "misc", "cg_resident"]
 

@@ -1972,6 +1972,39 @@ smvs_host_generate_fused_sparse(const char *scene_dir,
 }
 
 extern "C" int
+smvs_host_generate_fused_sparse_cull(const char *scene_dir,
+    const smvs_host_point_cloud_settings *o, const smvs_host_fused_sparse_cull_settings *f,
+    const int *view_ids, int n_view_ids, char *ply_path, int ply_path_capacity,
+    int64_t *n_vertices, int64_t *n_faces)
+{
+    try {
+        if (scene_dir == nullptr || o == nullptr || f == nullptr
+            || (view_ids == nullptr && n_view_ids > 0))
+            throw std::invalid_argument("smvs_host_generate_fused_sparse_cull: bad argument");
+        PointCloudSettings const conf = point_cloud_settings(o, view_ids, n_view_ids);
+        MeshGenerator::FusedOptions fo;
+        fo.voxel_size = f->voxel_size;
+        fo.resolution = f->resolution;
+        fo.trunc = f->trunc;
+        fo.min_weight = f->min_weight;
+        fo.sparse = true;
+        fo.max_bricks = f->max_bricks;
+        fo.cull = f->cull != 0;
+        std::size_t nv = 0, nf = 0;
+        std::string const path = generate_scene_fused(scene_dir, conf, fo, &nv, &nf);
+        copy_path(path, ply_path, ply_path_capacity);
+        if (n_vertices != nullptr)
+            *n_vertices = (int64_t)nv;
+        if (n_faces != nullptr)
+            *n_faces = (int64_t)nf;
+        return 0;
+    } catch (std::exception const& e) {
+        g_host_error = e.what();
+        return -1;
+    }
+}
+
+extern "C" int
 smvs_host_save_ply_points(const char *path, const float *xyz, const float *normals,
     const uint8_t *rgb, const float *confidence, const float *value, int64_t n)
 {

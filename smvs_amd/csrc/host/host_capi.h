@@ -593,6 +593,21 @@ int smvs_host_generate_fused_sparse(const char *scene_dir,
     const smvs_host_point_cloud_settings *settings,
     const smvs_host_fused_sparse_settings *fused, const int *view_ids, int n_view_ids,
     char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces);
+/* smvs_host_generate_fused_sparse through smvs_tsdf_fuse_sparse_opts (DESIGN.md
+ * section 9.10): with cull != 0 the brick cull against the views' depth min/max
+ * pyramids runs in front of the seed pass; the file is the same byte for byte. */
+typedef struct {
+    float voxel_size;
+    int resolution;
+    float trunc;
+    int min_weight;
+    int64_t max_bricks;
+    int cull;
+} smvs_host_fused_sparse_cull_settings;
+int smvs_host_generate_fused_sparse_cull(const char *scene_dir,
+    const smvs_host_point_cloud_settings *settings,
+    const smvs_host_fused_sparse_cull_settings *fused, const int *view_ids, int n_view_ids,
+    char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces);
 /* save_ply_mesh: the PLY writer of the triangle mesh from SoA
  * buffers (xyz, normals n*3 floats; rgb n*3 bytes; confidence n floats;
  * faces m*3 vertex ids < n). */

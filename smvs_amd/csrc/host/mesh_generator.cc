@@ -222,6 +222,8 @@ MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
         throw std::invalid_argument("generate_fused: resolution must be at most 4096");
     if (!fused.sparse && fused.max_bricks > 0)
         throw std::invalid_argument("generate_fused: max_bricks belongs to sparse");
+    if (!fused.sparse && fused.cull)
+        throw std::invalid_argument("generate_fused: cull belongs to sparse");
     int const n = (int)in.pv.size();
     float lo[3], hi[3];
     if (opts.use_aabb) {
@@ -268,7 +270,14 @@ MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
     }
     smvs_points* handle = nullptr;
     int64_t nv = 0, nf = 0;
-    if (fused.sparse) {
+    if (fused.sparse && fused.cull) {
+        smvs_tsdf_sparse_opts so;
+        so.max_bricks = fused.max_bricks;
+        so.cull = 1;
+        check_status(smvs_tsdf_fuse_sparse_opts(opts.device, in.pv.data(), n, &to, &so, nullptr,
+            nullptr, nullptr, nullptr, nullptr, &handle, &nv, &nf),
+            "smvs_tsdf_fuse_sparse_opts");
+    } else if (fused.sparse) {
         smvs_tsdf_sparse_options so;
         so.max_bricks = fused.max_bricks;
         check_status(smvs_tsdf_fuse_sparse(opts.device, in.pv.data(), n, &to, &so, nullptr,

@@ -91,6 +91,8 @@ public:
         int min_weight = 0;         // <= 0: 1
         bool sparse = false;
         int64_t max_bricks = 0;     // sparse only; <= 0: 1 << 20
+        bool cull = false;          // sparse only: the brick cull in front of the
+                                    // seed pass (section 9.10), the same mesh
     };
     TriangleMesh::Ptr generate_fused(std::vector<SceneView> const& views,
         std::string const& image_name, std::string const& dm_name,

@@ -1,5 +1,6 @@
-// Pieces of the volumetric fusion that tsdf.hip (the dense volume) and
-// tsdf_sparse.hip (the brick-sparse volume) share: the grid record, the
+// Pieces of the volumetric fusion that tsdf.hip (the dense volume),
+// tsdf_sparse.hip (the brick-sparse volume) and tsdf_cull.hip (the brick cull
+// in front of its seed pass) share: the grid record, the brick grid, the
 // per-element device functions of the definition in include/smvs_hip.h (voxel
 // centre, the projection steps 1-6, the cell / edge / quad rules, the block
 // scan, the vertex attribute arithmetic) and the host side's view upload.
@@ -82,6 +83,75 @@ tsdf_project(MeshViewDev const &V, const float *c, float trunc, size_t *pixel, f
     *sdf_out = sdf;
     return true;
 }
+
+// ---------------------------------------------------------------- brick grid
+// tsdf_sparse.hip and tsdf_cull.hip: the bricks of the whole grid
+struct TsdfBricks {
+    int bx, by, bz;
+    unsigned n;      // bx * by * bz <= 2^28
+};
+
+// (a launch's x extent in threads is 32 bits: a block per brick goes over x and y)
+constexpr unsigned SEED_GRID_X = 65536;
+
+struct BrickVoxel {
+    int i, j, k;       // the voxel in the grid
+    bool in_grid;
+};
+
+__device__ __forceinline__ BrickVoxel
+brick_voxel(TsdfGrid const &G, TsdfBricks const &B, unsigned brick)
+{
+    BrickVoxel v;
+    v.i = (int)(brick % B.bx) * TSDF_BX + (int)(threadIdx.x & 7);
+    v.j = (int)(brick / B.bx % B.by) * TSDF_BY + (int)(threadIdx.x >> 3 & 7);
+    v.k = (int)(brick / B.bx / B.by) * TSDF_BZ + (int)(threadIdx.x >> 6);
+    v.in_grid = v.i < G.nx && v.j < G.ny && v.k < G.nz;
+    return v;
+}
+
+// The exact seed test of one brick by its block of 256 (a macro: see above;
+// tsdf_sparse_seed_kernel keeps its code): seed[brick] = 2 where a voxel of
+// the brick has C > 0, else 0.  Inside a scope with
+// `#pragma clang fp contract(off)`; every thread of the block runs it.
+#define TSDF_SEED_BRICK(views, G, B, brick, seed)                                \
+    __shared__ uint32_t found;                                                 \
+    if (threadIdx.x == 0)                                                      \
+        found = 0;                                                             \
+    __syncthreads();                                                           \
+    BrickVoxel const p = brick_voxel(G, B, brick);                             \
+    float const c[3] = { tsdf_centre(G, 0, p.i), tsdf_centre(G, 1, p.j),       \
+        tsdf_centre(G, 2, p.k) };                                              \
+    for (int v = 0; v < (G).n_views; ++v) {                                    \
+        /* another wave's hit ends this wave too */                            \
+        if (__builtin_amdgcn_readfirstlane(*(volatile uint32_t *)&found) != 0) \
+            break;                                                             \
+        bool hit = false;                                                      \
+        if (p.in_grid) {                                                       \
+            size_t pj;                                                         \
+            float sdf;                                                         \
+            hit = tsdf_project((views)[v], c, (G).trunc, &pj, &sdf) && sdf <= (G).trunc; \
+        }                                                                      \
+        if (__ballot(hit) != 0) {                                              \
+            if ((threadIdx.x & 63) == 0)                                       \
+                *(volatile uint32_t *)&found = 1;                              \
+            break;                                                             \
+        }                                                                      \
+    }                                                                          \
+    __syncthreads();                                                           \
+    if (threadIdx.x == 0)                                                      \
+        (seed)[brick] = found != 0 ? 2 : 0
+
+// ------------------------------------------------------------ cull (9.10)
+// One view's min/max pyramid of D, levels 1 .. levels (level 0 is depth_z
+// itself): texel (x, y) of level l is texels[off[l] + y * w_l + x] = (lo, hi),
+// w_l = ceil(w / 2^l); (+inf, -inf) where no pixel below it is valid
+constexpr int TSDF_PYRAMID_MAX_LEVELS = 31;
+struct TsdfPyramidDev {
+    float2 *texels;
+    int levels;
+    uint32_t off[TSDF_PYRAMID_MAX_LEVELS + 1];
+};
 
 // ----------------------------------------------------------------- extraction
 // Cells and grid points share the points' linear index (x fastest): cell
@@ -315,6 +385,32 @@ int upload_and_prepare(Workspace &ws, char *slab, const smvs_point_view *views, 
     bool cut, bool want_images, ViewSlab &s);
 // D(p) = depth_z[p] where cut[p] != 0, else 0, in place in depth_z
 void launch_depth(hipStream_t stream, ViewSlab const &s, int n_views);
+
+// tsdf_cull.hip: the views' pyramids in the same slab and the passes over them
+struct PyramidSlab {
+    std::vector<size_t> at;              // per view: its texels
+    std::vector<TsdfPyramidDev> table;
+    size_t table_at = 0, bytes = 0;      // bytes: all views' texels
+    unsigned max_tiles = 0;
+    TsdfPyramidDev *d_table = nullptr;
+};
+// levels and the texels of levels >= 1 of a w x h map; off (may be null): the
+// TsdfPyramidDev offsets
+size_t pyramid_texels(int w, int h, int *levels, uint32_t *off);
+void carve_pyramids(const smvs_point_view *views, int n_views, Carver &carve, PyramidSlab &p);
+// after launch_depth: uploads the table and builds every view's levels
+int launch_pyramids(Workspace &ws, char *slab, ViewSlab const &s, int n_views, PyramidSlab &p);
+// candidate[brick] = 0 / 1 and counts[block of 256 bricks] = its candidates
+void launch_cull(hipStream_t stream, ViewSlab const &s, PyramidSlab const &p, TsdfGrid const &G,
+    TsdfBricks const &B, uint8_t *candidate, unsigned long long *counts);
+// counts scanned: list[rank] = brick for the candidates in brick order
+void launch_candidate_list(hipStream_t stream, const uint8_t *candidate, TsdfBricks const &B,
+    const unsigned long long *counts, uint32_t *list);
+// the exact seed test on the n bricks of the list; the other bytes are not written
+void launch_seed_list(hipStream_t stream, ViewSlab const &s, TsdfGrid const &G,
+    TsdfBricks const &B, const uint32_t *list, size_t n, uint8_t *seed);
+// the entry behind smvs_tsdf_fuse_sparse and smvs_tsdf_fuse_sparse_opts (tsdf_sparse.hip)
+TsdfBricks brick_grid(TsdfGrid const &G, size_t *n_bricks);
 
 } // namespace tsdf_host
 

@@ -5,7 +5,8 @@
 // the 8 x 8 x 4 bricks that hold a voxel within the truncation band of some view
 // or touch a brick that does.
 //   seed       one block per brick of the whole grid runs steps 1-6 and the
-//              test of step 8 until the first hit: one byte per brick
+//              test of step 8 until the first hit: one byte per brick (with
+//              the cull of tsdf_cull.hip, section 9.10: per candidate brick)
 //   dilate     per brick the OR over its 27 neighbours; counts per 256 bricks
 //   scan       mesh.hip's exclusive_scan over those counts
 //   table      brick -> slot (or -1) and slot -> brick, in linear brick order
@@ -26,32 +27,10 @@
 
 namespace smvs_hip {
 
-struct TsdfBricks {
-    int bx, by, bz;
-    unsigned n;      // bx * by * bz <= 2^28
-};
-
 // the halo of a brick as a grid of its own: the shared cell and quad rules
 // read it as they read the dense volume
 constexpr int HALO_X = TSDF_BX + 2, HALO_Y = TSDF_BY + 2, HALO_Z = TSDF_BZ + 2;
 constexpr int HALO_N = HALO_X * HALO_Y * HALO_Z;
-constexpr unsigned SEED_GRID_X = 65536;
-
-struct BrickVoxel {
-    int i, j, k;       // the voxel in the grid
-    bool in_grid;
-};
-
-__device__ __forceinline__ BrickVoxel
-brick_voxel(TsdfGrid const &G, TsdfBricks const &B, unsigned brick)
-{
-    BrickVoxel v;
-    v.i = (int)(brick % B.bx) * TSDF_BX + (int)(threadIdx.x & 7);
-    v.j = (int)(brick / B.bx % B.by) * TSDF_BY + (int)(threadIdx.x >> 3 & 7);
-    v.k = (int)(brick / B.bx / B.by) * TSDF_BZ + (int)(threadIdx.x >> 6);
-    v.in_grid = v.i < G.nx && v.j < G.ny && v.k < G.nz;
-    return v;
-}
 
 // where voxel (i, j, k) of the grid lives in the slot-major state; false where
 // its brick is not allocated
@@ -76,34 +55,10 @@ tsdf_sparse_seed_kernel(const MeshViewDev *__restrict__ views, TsdfGrid G, TsdfB
     uint8_t *__restrict__ seed)
 {
 #pragma clang fp contract(off)
-    __shared__ uint32_t found;
     unsigned const brick = blockIdx.y * SEED_GRID_X + blockIdx.x;
     if (brick >= B.n)
         return;
-    if (threadIdx.x == 0)
-        found = 0;
-    __syncthreads();
-    BrickVoxel const p = brick_voxel(G, B, brick);
-    float const c[3] = { tsdf_centre(G, 0, p.i), tsdf_centre(G, 1, p.j), tsdf_centre(G, 2, p.k) };
-    for (int v = 0; v < G.n_views; ++v) {
-        // another wave's hit ends this wave too
-        if (__builtin_amdgcn_readfirstlane(*(volatile uint32_t *)&found) != 0)
-            break;
-        bool hit = false;
-        if (p.in_grid) {
-            size_t pj;
-            float sdf;
-            hit = tsdf_project(views[v], c, G.trunc, &pj, &sdf) && sdf <= G.trunc;
-        }
-        if (__ballot(hit) != 0) {
-            if ((threadIdx.x & 63) == 0)
-                *(volatile uint32_t *)&found = 1;
-            break;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        seed[brick] = found != 0 ? 2 : 0;
+    TSDF_SEED_BRICK(views, G, B, brick, seed);
 }
 
 // Dilate and count: state = 2 seed, 1 a neighbour of a seed, 0 neither;
@@ -358,11 +313,46 @@ constexpr int64_t STATE_BYTES_PER_BRICK = 256 * 28;
 
 } // namespace
 
+TsdfBricks
+smvs_hip::tsdf_host::brick_grid(TsdfGrid const &G, size_t *n_bricks)
+{
+    TsdfBricks B;
+    B.bx = (G.nx + TSDF_BX - 1) / TSDF_BX;
+    B.by = (G.ny + TSDF_BY - 1) / TSDF_BY;
+    B.bz = (G.nz + TSDF_BZ - 1) / TSDF_BZ;
+    *n_bricks = (size_t)B.bx * B.by * B.bz;
+    B.n = (unsigned)*n_bricks;      // the entries refuse more than 2^28
+    return B;
+}
+
 extern "C" int
 smvs_tsdf_fuse_sparse(int device, const smvs_point_view *views, int n_views,
     const smvs_tsdf_options *options, const smvs_tsdf_sparse_options *sparse,
     uint8_t *brick_state, float *tsdf, uint32_t *weight, smvs_tsdf_sparse_stats *stats,
     smvs_points **handle, int64_t *n_vertices, int64_t *n_faces)
+{
+    smvs_tsdf_sparse_opts o;
+    o.max_bricks = sparse != nullptr ? sparse->max_bricks : 0;
+    o.cull = 0;
+    smvs_tsdf_sparse_opts_stats st = {};
+    int const rc = smvs_tsdf_fuse_sparse_opts(device, views, n_views, options, &o, brick_state,
+        nullptr, tsdf, weight, stats != nullptr ? &st : nullptr, handle, n_vertices, n_faces);
+    // (the stats are filled from the seed and dilation passes on, with SMVS_ERR_NOMEM too)
+    if (stats != nullptr && st.bricks != 0) {
+        stats->bricks = st.bricks;
+        stats->seed_bricks = st.seed_bricks;
+        stats->allocated_bricks = st.allocated_bricks;
+        stats->state_bytes = st.state_bytes;
+    }
+    return rc;
+}
+
+extern "C" int
+smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views,
+    const smvs_tsdf_options *options, const smvs_tsdf_sparse_opts *sparse,
+    uint8_t *brick_state, uint8_t *brick_candidate, float *tsdf, uint32_t *weight,
+    smvs_tsdf_sparse_opts_stats *stats, smvs_points **handle, int64_t *n_vertices,
+    int64_t *n_faces)
 {
     SMVS_REQUIRE(handle != nullptr, "no handle pointer");
     *handle = nullptr;
@@ -374,13 +364,9 @@ smvs_tsdf_fuse_sparse(int device, const smvs_point_view *views, int n_views,
     TsdfGrid G;
     if ((rc = check_grid("smvs_tsdf_fuse_sparse", opt, n_views, 4096, G)))
         return rc;
-    TsdfBricks B;
-    B.bx = (G.nx + TSDF_BX - 1) / TSDF_BX;
-    B.by = (G.ny + TSDF_BY - 1) / TSDF_BY;
-    B.bz = (G.nz + TSDF_BZ - 1) / TSDF_BZ;
-    size_t const n_bricks = (size_t)B.bx * B.by * B.bz;
+    size_t n_bricks;
+    TsdfBricks const B = brick_grid(G, &n_bricks);
     SMVS_REQUIRE(n_bricks <= MAX_BRICKS_GRID, "the brick grid has more than 2^28 bricks");
-    B.n = (unsigned)n_bricks;
     size_t const n_vox = (size_t)G.nx * G.ny * G.nz;
     SMVS_REQUIRE((tsdf == nullptr && weight == nullptr) || n_vox <= DENSE_MAX_VOXELS,
         "tsdf / weight are given only for grids of at most 2^27 voxels");
@@ -388,6 +374,7 @@ smvs_tsdf_fuse_sparse(int device, const smvs_point_view *views, int n_views,
     if (max_bricks <= 0)
         max_bricks = DEFAULT_MAX_BRICKS;
     SMVS_REQUIRE(max_bricks <= MAX_MAX_BRICKS, "max_bricks must be at most 2^23");
+    bool const cull = sparse != nullptr && sparse->cull != 0;
 
     WorkspaceLease lease(device);
     if (lease.w == nullptr)
@@ -395,12 +382,18 @@ smvs_tsdf_fuse_sparse(int device, const smvs_point_view *views, int n_views,
     Workspace &ws = *lease.w;
     Carver carve;
     ViewSlab s;
+    PyramidSlab pyr;
     carve_views(views, n_views, true, carve, s);
     unsigned const brick_blocks = (unsigned)((n_bricks + 255) / 256);
     size_t const brick_tiles = ((size_t)brick_blocks + SCAN_TILE - 1) / SCAN_TILE;
     size_t const seed_at = carve(n_bricks), state_at = carve(n_bricks),
         table_at = carve(4 * n_bricks), bcounts_at = carve(8 * (size_t)brick_blocks),
         btiles_at = carve(8 * (brick_tiles + 1));
+    size_t cand_at = 0;
+    if (cull) {
+        carve_pyramids(views, n_views, carve, pyr);
+        cand_at = carve(n_bricks);
+    }
     char *slab = nullptr;
     if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
         return rc;
@@ -414,11 +407,37 @@ smvs_tsdf_fuse_sparse(int device, const smvs_point_view *views, int n_views,
     unsigned long long *d_btiles = reinterpret_cast<unsigned long long *>(slab + btiles_at);
 
     launch_depth(stream, s, n_views);
-    // (a launch's x extent in threads is 32 bits: the bricks go over x and y)
-    unsigned const seed_x = n_bricks < SEED_GRID_X ? (unsigned)n_bricks : SEED_GRID_X;
-    unsigned const seed_y = (unsigned)((n_bricks + SEED_GRID_X - 1) / SEED_GRID_X);
-    hipLaunchKernelGGL(tsdf_sparse_seed_kernel, dim3(seed_x, seed_y), dim3(256), 0, stream,
-        s.d_table, G, B, d_seed);
+    size_t n_tested = n_bricks;
+    if (cull) {
+        // the candidates (section 9.10), their list in the table's place, and
+        // the exact test on the list alone; the counts are the dilation's, not
+        // yet in use
+        uint8_t *d_cand = reinterpret_cast<uint8_t *>(slab + cand_at);
+        uint32_t *d_cand_list = reinterpret_cast<uint32_t *>(d_table);
+        if ((rc = launch_pyramids(ws, slab, s, n_views, pyr)))
+            return rc;
+        launch_cull(stream, s, pyr, G, B, d_cand, d_bcounts);
+        SMVS_HIP_CHECK(hipGetLastError());
+        if ((rc = exclusive_scan(stream, d_bcounts, brick_blocks, d_btiles)))
+            return rc;
+        unsigned long long total = 0;
+        if ((rc = ws.download(&total, d_btiles + brick_tiles, sizeof(total))))
+            return rc;
+        n_tested = (size_t)total;
+        if (brick_candidate != nullptr && (rc = ws.download(brick_candidate, d_cand, n_bricks)))
+            return rc;
+        SMVS_HIP_CHECK(hipMemsetAsync(d_seed, 0, n_bricks, stream));
+        launch_candidate_list(stream, d_cand, B, d_bcounts, d_cand_list);
+        launch_seed_list(stream, s, G, B, d_cand_list, n_tested, d_seed);
+    } else {
+        if (brick_candidate != nullptr)
+            std::memset(brick_candidate, 1, n_bricks);
+        // (a launch's x extent in threads is 32 bits: the bricks go over x and y)
+        unsigned const seed_x = n_bricks < SEED_GRID_X ? (unsigned)n_bricks : SEED_GRID_X;
+        unsigned const seed_y = (unsigned)((n_bricks + SEED_GRID_X - 1) / SEED_GRID_X);
+        hipLaunchKernelGGL(tsdf_sparse_seed_kernel, dim3(seed_x, seed_y), dim3(256), 0, stream,
+            s.d_table, G, B, d_seed);
+    }
     hipLaunchKernelGGL(tsdf_sparse_dilate_kernel, dim3(brick_blocks), dim3(256), 0, stream,
         d_seed, B, d_state, d_bcounts);
     SMVS_HIP_CHECK(hipGetLastError());
@@ -433,6 +452,7 @@ smvs_tsdf_fuse_sparse(int device, const smvs_point_view *views, int n_views,
         stats->seed_bricks = (int64_t)(sums >> 32);
         stats->allocated_bricks = (int64_t)n_alloc;
         stats->state_bytes = (int64_t)n_alloc * STATE_BYTES_PER_BRICK;
+        stats->tested_bricks = (int64_t)n_tested;
     }
     if (brick_state != nullptr && (rc = ws.download(brick_state, d_state, n_bricks)))
         return rc;

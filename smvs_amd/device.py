@@ -1400,7 +1400,8 @@ def tsdf_bounds(cams, depths, normals, cut=True, device=0):
 
 
 def fuse_tsdf(cams, depths, normals, images, origin, voxel_size, dims, trunc=0, min_weight=0,
-              cut=True, volume=False, device=0, sparse=False, max_bricks=0, brick_state=False):
+              cut=True, volume=False, device=0, sparse=False, max_bricks=0, brick_state=False,
+              cull=None, brick_candidate=False):
     """smvs_tsdf_fuse: the depth maps fused into one surface mesh through a
     truncated signed distance field on the voxel grid (origin, voxel_size,
     dims = (nx, ny, nz)); the definition is in include/smvs_hip.h.  Inputs as
@@ -1415,12 +1416,24 @@ def fuse_tsdf(cams, depths, normals, images, origin, voxel_size, dims, trunc=0, 
     cell's linear index in the grid), stats (bricks, seed_bricks,
     allocated_bricks, state_bytes) and, with brick_state, brick_state
     (bz, by, bx) uint8: 0 none, 1 allocated, 2 seed.  An SmvsError of status -4
-    (more than max_bricks needed) carries the stats as its `stats`."""
+    (more than max_bricks needed) carries the stats as its `stats`.
+
+    cull (with sparse; None: the entry above, the dict as above):
+    smvs_tsdf_fuse_sparse_opts.  True puts the brick cull against the views'
+    depth min/max pyramids in front of the seed pass:
+    every array is the same to the bit, only stats' tested_bricks, the bricks
+    the exact seed test ran on, falls below bricks.  With brick_candidate the
+    dict gains brick_candidate (bz, by, bx) uint8, 1 where it ran.  An SmvsError
+    of status -4 then carries `brick_candidate` as well."""
     if sparse:
+        if brick_candidate and cull is None:
+            raise ValueError("brick_candidate belongs to cull=True or cull=False")
         return _fuse_tsdf_sparse(cams, depths, normals, images, origin, voxel_size, dims, trunc,
-                                 min_weight, cut, volume, device, max_bricks, brick_state)
-    if max_bricks or brick_state:
-        raise ValueError("max_bricks and brick_state belong to sparse=True")
+                                 min_weight, cut, volume, device, max_bricks, brick_state, cull,
+                                 brick_candidate)
+    if max_bricks or brick_state or cull or brick_candidate:
+        raise ValueError("max_bricks, brick_state, cull and brick_candidate belong to "
+                         "sparse=True")
     lib = _capi.load()
     n = len(cams)
     arr, _keep = _tsdf_views(cams, depths, normals, images)
@@ -1459,7 +1472,8 @@ def fuse_tsdf(cams, depths, normals, images, origin, voxel_size, dims, trunc=0, 
 
 
 def _fuse_tsdf_sparse(cams, depths, normals, images, origin, voxel_size, dims, trunc, min_weight,
-                      cut, volume, device, max_bricks, brick_state):
+                      cut, volume, device, max_bricks, brick_state, cull=None,
+                      brick_candidate=False):
     """fuse_tsdf(sparse=True)"""
     lib = _capi.load()
     n = len(cams)
@@ -1472,26 +1486,42 @@ def _fuse_tsdf_sparse(cams, depths, normals, images, origin, voxel_size, dims, t
     opt.voxel_size = float(voxel_size)
     opt.trunc = float(trunc)
     opt.min_weight = int(min_weight)
-    sopt = _capi.TsdfSparseOptions()
-    sopt.max_bricks = int(max_bricks)
-    stats = _capi.TsdfSparseStats()
     shape = tuple(max(int(d), 0) for d in dims)[::-1]
-    tsdf = weight = state = None
+    bricks = (-(-shape[0] // 4), -(-shape[1] // 8), -(-shape[2] // 8))
+    tsdf = weight = state = candidate = None
     if volume:
         tsdf = np.zeros(shape, np.float32)
         weight = np.zeros(shape, np.uint32)
     if brick_state:
-        state = np.zeros((-(-shape[0] // 4), -(-shape[1] // 8), -(-shape[2] // 8)), np.uint8)
+        state = np.zeros(bricks, np.uint8)
+    if brick_candidate:
+        candidate = np.zeros(bricks, np.uint8)
     handle = C.c_void_p()
     n_vertices, n_faces = C.c_int64(), C.c_int64()
-    rc = lib.smvs_tsdf_fuse_sparse(device, arr if n else None, n, C.byref(opt), C.byref(sopt),
-                                   _p(state, _u8p), _p(tsdf, _fp), _p(weight, _u32p),
-                                   C.byref(stats), C.byref(handle), C.byref(n_vertices),
-                                   C.byref(n_faces))
+    if cull is None:
+        sopt = _capi.TsdfSparseOptions()
+        sopt.max_bricks = int(max_bricks)
+        stats = _capi.TsdfSparseStats()
+        rc = lib.smvs_tsdf_fuse_sparse(device, arr if n else None, n, C.byref(opt),
+                                       C.byref(sopt), _p(state, _u8p), _p(tsdf, _fp),
+                                       _p(weight, _u32p), C.byref(stats), C.byref(handle),
+                                       C.byref(n_vertices), C.byref(n_faces))
+    else:
+        sopt = _capi.TsdfSparseOpts()
+        sopt.max_bricks = int(max_bricks)
+        sopt.cull = int(bool(cull))
+        stats = _capi.TsdfSparseOptsStats()
+        rc = lib.smvs_tsdf_fuse_sparse_opts(device, arr if n else None, n, C.byref(opt),
+                                            C.byref(sopt), _p(state, _u8p),
+                                            _p(candidate, _u8p), _p(tsdf, _fp),
+                                            _p(weight, _u32p), C.byref(stats), C.byref(handle),
+                                            C.byref(n_vertices), C.byref(n_faces))
     if rc != 0:
         err = _capi.SmvsError(rc, lib.smvs_last_error().decode())
         if rc == -4:
             err.stats = stats.as_dict()
+            if brick_candidate:
+                err.brick_candidate = candidate
         raise err
     try:
         k = n_vertices.value
@@ -1512,7 +1542,75 @@ def _fuse_tsdf_sparse(cams, depths, normals, images, origin, voxel_size, dims, t
         out["weight"] = weight
     if brick_state:
         out["brick_state"] = state
+    if brick_candidate:
+        out["brick_candidate"] = candidate
     return out
+
+
+def _tsdf_options(origin, voxel_size, dims, trunc, cut):
+    opt = _capi.TsdfOptions()
+    opt.cut_surfaces = int(bool(cut))
+    for k in range(3):
+        opt.origin[k] = float(origin[k])
+        opt.dims[k] = int(dims[k])
+    opt.voxel_size = float(voxel_size)
+    opt.trunc = float(trunc)
+    return opt
+
+
+def tsdf_brick_cull(cams, depths, normals, origin, voxel_size, dims, trunc=0, cut=True,
+                    device=0):
+    """smvs_tsdf_brick_cull: the preparation, the depth min/max pyramids and the
+    brick cull of fuse_tsdf(sparse=True, cull=True) alone.  Inputs as
+    tsdf_bounds, the grid as fuse_tsdf.  Returns brick_candidate (bz, by, bx)
+    uint8: 1 where a view may put a voxel of the brick within its truncation
+    band (every seed brick is one), 0 where provably none does."""
+    lib = _capi.load()
+    n = len(cams)
+    arr, _keep = _tsdf_views(cams, depths, normals, None)
+    opt = _tsdf_options(origin, voxel_size, dims, trunc, cut)
+    shape = tuple(max(int(d), 0) for d in dims)[::-1]
+    out = np.zeros((-(-shape[0] // 4), -(-shape[1] // 8), -(-shape[2] // 8)), np.uint8)
+    check(lib.smvs_tsdf_brick_cull(device, arr if n else None, n, C.byref(opt), _p(out, _u8p),
+                                   None))
+    return out
+
+
+def pyramid_bytes(w, h):
+    """the device bytes of one w x h view's pyramid: 8 per texel of the levels >= 1"""
+    texels = 0
+    while w > 1 or h > 1:
+        w, h = (w + 1) // 2, (h + 1) // 2
+        texels += w * h
+    return 8 * texels
+
+
+def tsdf_depth_pyramid(cams, depths, normals, view, cut=True, device=0):
+    """smvs_tsdf_depth_pyramid: the min/max pyramid of view `view`'s prepared
+    (and cut) z-depth as the brick cull reads it.  Inputs as tsdf_bounds.
+    Returns a list over the levels 1 .. (1 x 1) of (lo, hi), float32
+    (h_l, w_l) each with (+inf, -inf) where no pixel is valid; level 0 is the
+    map itself, and a 1 x 1 view gives an empty list."""
+    n = len(cams)
+    if not 0 <= int(view) < n:
+        raise ValueError("tsdf_depth_pyramid: no view %r" % (view,))
+    lib = _capi.load()
+    arr, _keep = _tsdf_views(cams, depths, normals, None)
+    count, n_levels = C.c_int64(), C.c_int()
+    check(lib.smvs_tsdf_depth_pyramid(device, arr, n, int(bool(cut)), int(view), None, None,
+                                      C.byref(count), C.byref(n_levels)))
+    lo = np.zeros(count.value, np.float32)
+    hi = np.zeros(count.value, np.float32)
+    check(lib.smvs_tsdf_depth_pyramid(device, arr, n, int(bool(cut)), int(view), _p(lo, _fp),
+                                      _p(hi, _fp), None, None))
+    h, w = np.shape(depths[view])[:2]
+    levels, at = [], 0
+    while w > 1 or h > 1:
+        w, h = (w + 1) // 2, (h + 1) // 2
+        levels.append((lo[at:at + w * h].reshape(h, w), hi[at:at + w * h].reshape(h, w)))
+        at += w * h
+    assert at == count.value and len(levels) == n_levels.value
+    return levels
 
 
 class SimplifyOptions(C.Structure):

@@ -1011,9 +1011,14 @@ class FusedSparseSettings(C.Structure):
                 ("min_weight", C.c_int), ("max_bricks", C.c_int64)]
 
 
+class FusedSparseCullSettings(C.Structure):
+    _fields_ = FusedSparseSettings._fields_ + [("cull", C.c_int)]
+
+
 def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=0, min_weight=0,
                    view_ids=None, image_embedding="undistorted", input_scale=0,
-                   use_shading=False, cut=True, device=0, sparse=False, max_bricks=0):
+                   use_shading=False, cut=True, device=0, sparse=False, max_bricks=0,
+                   cull=False):
     """Not in the reference: the views' smvs-{B,S}<input_scale> depth maps fused
     into ONE surface mesh through a truncated signed distance field
     (smvs_tsdf_fuse), written as
@@ -1026,11 +1031,20 @@ def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=
     sparse: the volume is allocated in 8 x 8 x 4 bricks near the surface
     (smvs_tsdf_fuse_sparse, section 9.9): the same mesh with vertices and faces
     in the brick order, under the same file name; resolution may go up to 4096;
-    max_bricks 0: 1 << 20 bricks."""
+    max_bricks 0: 1 << 20 bricks.  cull (with sparse): the brick cull against
+    the views' depth min/max pyramids in front of the seed pass (section 9.10);
+    the file is the same byte for byte."""
+    if cull and not sparse:
+        raise ValueError("cull belongs to sparse=True")
     lib = load()
     st = _point_cloud_settings(image_embedding, input_scale, use_shading, cut, aabb, True,
                                False, device)
-    if sparse:
+    if sparse and cull:
+        fs = FusedSparseCullSettings(0.0 if voxel_size is None else float(voxel_size),
+                                     int(resolution), float(trunc), int(min_weight),
+                                     int(max_bricks), 1)
+        entry = lib.smvs_host_generate_fused_sparse_cull
+    elif sparse:
         fs = FusedSparseSettings(0.0 if voxel_size is None else float(voxel_size),
                                  int(resolution), float(trunc), int(min_weight), int(max_bricks))
         entry = lib.smvs_host_generate_fused_sparse

@@ -12,14 +12,17 @@ tools/points_bench.py's (the 16 views repeat the nine synthetic ones).
 
     python tools/tsdf_bench.py [--dims N] [--views N] [--size W H] [--reps N]
                                [--no-kernels] [--no-peaks]
-                               [--sparse [--resolution N] [--max-bricks N]]
+                               [--sparse [--resolution N] [--max-bricks N] [--cull]]
 
 --sparse times smvs_tsdf_fuse_sparse (the brick-sparse volume, DESIGN.md section
 9.9) on the same case instead: --resolution N is --dims N and may go up to
 4096.  The entry's line carries the stats (bricks, seed and allocated bricks,
 state bytes, the dense volume's would-be bytes); the seed kernel's line its
 time per 1000 (voxel, view) pairs of the whole box, the integration kernel's
-its time per 1000 pairs of the allocated bricks.
+its time per 1000 pairs of the allocated bricks.  --cull puts the brick cull
+(section 9.10) in front of the seed pass: the entry's line gains tested_bricks,
+their share and the pyramids' bytes, and the pyramid, cull, list and listed-seed
+kernels take the seed kernel's place.
 """
 import argparse
 import csv
@@ -44,6 +47,10 @@ SPARSE_KERNELS = ["mesh_prepare_kernel", "mesh_cut_kernel", "tsdf_depth_kernel",
                   "tsdf_sparse_table_kernel", "tsdf_sparse_integrate_kernel",
                   "tsdf_sparse_classify_kernel", "scan_tile_sums_kernel", "scan_tiles_kernel",
                   "scan_apply_kernel", "tsdf_sparse_vertex_kernel", "tsdf_sparse_face_kernel"]
+# with --cull: the pyramids, the cull and the seed pass over the candidate list
+# in the place of tsdf_sparse_seed_kernel (the scan runs twice more)
+CULL_KERNELS = ["tsdf_pyramid_tile_kernel", "tsdf_pyramid_top_kernel", "tsdf_cull_kernel",
+                "tsdf_cull_list_kernel", "tsdf_sparse_seed_list_kernel"]
 CHILD_REPS = 3
 BOX_LO, BOX_SIDE = (-1.3, -1.3, 2.7), 2.6
 
@@ -55,7 +62,19 @@ def case(args):
 
 
 def sparse_args(args):
-    return {"sparse": True, "max_bricks": args.max_bricks} if args.sparse else {}
+    if not args.sparse:
+        return {}
+    out = {"sparse": True, "max_bricks": args.max_bricks}
+    if args.cull:
+        out["cull"] = True
+    return out
+
+
+def sparse_kernels(args):
+    if not args.cull:
+        return SPARSE_KERNELS
+    at = SPARSE_KERNELS.index("tsdf_sparse_seed_kernel")
+    return SPARSE_KERNELS[:at] + CULL_KERNELS + SPARSE_KERNELS[at + 1:]
 
 
 def child(args):
@@ -74,13 +93,15 @@ def kernel_times(args):
                str(args.size[1])]
         if args.sparse:
             cmd += ["--sparse", "--max-bricks", str(args.max_bricks)]
+        if args.cull:
+            cmd += ["--cull"]
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         if res.returncode != 0:
             raise RuntimeError("rocprofv3 failed: " + res.stderr[-2000:])
         files = glob.glob(os.path.join(tmp, "**", "*kernel_trace.csv"), recursive=True)
         if not files:
             raise RuntimeError("rocprofv3 left no kernel trace")
-        names = SPARSE_KERNELS if args.sparse else KERNELS
+        names = sparse_kernels(args) if args.sparse else KERNELS
         rows = {k: [] for k in names}
         for fn in files:
             with open(fn) as f:
@@ -101,13 +122,21 @@ def kernel_times(args):
 
 
 def sparse_kernel_lines(args, kt, stats, n_vox):
-    for k in SPARSE_KERNELS:
+    for k in sparse_kernels(args):
         per, t = kt[k]
         rec = {"case": "sparse_kernel", "kernel": k, "launches_per_call": per,
                "ms_per_call_best": round(1e3 * t, 4)}
         if k == "tsdf_sparse_seed_kernel":
             rec.update({"voxel_views": n_vox * args.views,
                         "ns_per_1000_voxel_views": round(1e12 * t / (n_vox * args.views), 4)})
+        if k == "tsdf_sparse_seed_list_kernel" and stats["tested_bricks"]:
+            pairs = 256 * stats["tested_bricks"] * args.views
+            rec.update({"voxel_views": pairs,
+                        "ns_per_1000_voxel_views": round(1e12 * t / pairs, 4)})
+        if k == "tsdf_cull_kernel":
+            pairs = stats["bricks"] * args.views
+            rec.update({"brick_views": pairs,
+                        "ns_per_1000_brick_views": round(1e12 * t / pairs, 3)})
         if k == "tsdf_sparse_integrate_kernel" and stats["allocated_bricks"]:
             pairs = 256 * stats["allocated_bricks"] * args.views
             rec.update({"voxel_views": pairs,
@@ -130,7 +159,11 @@ def main():
     ap.add_argument("--sparse", action="store_true", help="smvs_tsdf_fuse_sparse")
     ap.add_argument("--resolution", type=int, help="with --sparse: --dims, up to 4096")
     ap.add_argument("--max-bricks", type=int, default=0)
+    ap.add_argument("--cull", action="store_true",
+                    help="with --sparse: the brick cull in front of the seed pass")
     args = ap.parse_args()
+    if args.cull and not args.sparse:
+        ap.error("--cull belongs to --sparse")
     if args.resolution is not None:
         if not args.sparse:
             ap.error("--resolution belongs to --sparse")
@@ -157,6 +190,11 @@ def main():
     if args.sparse:
         st = out["stats"]
         entry.update(st)
+        if args.cull:
+            from smvs_amd.device import pyramid_bytes
+            entry.update({"cull": True,
+                          "tested_share": round(st["tested_bricks"] / st["bricks"], 5),
+                          "pyramid_bytes": args.views * pyramid_bytes(*args.size)})
         entry.update({"max_bricks": args.max_bricks or 1 << 20,
                       "allocated_share": round(st["allocated_bricks"] / st["bricks"], 5),
                       "dense_state_bytes": 28 * n_vox})
