@@ -36,7 +36,10 @@ HOST_LIB = os.path.join(HOST_DIR, "libsmvs_host.so")
 HOST_SOURCES = ["camera.cc", "stereo_view.cc", "surface.cc", "sgm_stereo.cc",
                 "depth_optimizer.cc", "view_selection.cc", "view_queue.cc", "conjugate_gradient.cc",
                 "gauss_newton_step.cc", "scene_io.cc", "mesh_generator.cc", "png_io.cc", "jpeg_io.cc", "pinned_images.cc",
-                "colmap_io.cc", "colmap_import.cc", "host_capi.cc"]
+                "colmap_io.cc", "colmap_import.cc",
+                # the C ABI of host_capi.h, by concern (capi_internal.h is what they share)
+                "capi_optimize.cc", "capi_surface.cc", "capi_sgm.cc", "capi_scene.cc",
+                "capi_export.cc", "capi_colmap.cc"]
 
 
 def _host_stale():

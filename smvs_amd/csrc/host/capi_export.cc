@@ -1,0 +1,211 @@
+// C ABI of the host mirror (host_capi.h): what a reconstructed scene is
+// exported as -- point cloud, mesh, simplified triangulation, fused mesh -- and
+// the two PLY writers.
+#include "capi_internal.h"
+
+#include "mesh_generator.h"
+
+using namespace smvs_amd;
+using namespace smvs_amd::capi;
+
+namespace {
+
+// what every smvs_host_generate_* takes and gives (n_faces: none for the cloud)
+struct ExportCall
+{
+    const char *scene_dir;
+    const smvs_host_point_cloud_settings *o;
+    const int *view_ids;
+    int n_view_ids;
+    char *ply_path;
+    int ply_path_capacity;
+    int64_t *n_vertices;
+    int64_t *n_faces = nullptr;
+};
+
+// The entry's argument check and its settings; `more` stands for what an entry
+// requires beyond the common arguments.
+PointCloudSettings
+export_settings(ExportCall const& c, std::string const& entry, bool more = true)
+{
+    require(c.scene_dir != nullptr && c.o != nullptr && more
+        && (c.view_ids != nullptr || c.n_view_ids <= 0), entry + ": bad argument");
+    PointCloudSettings conf;
+    if (c.o->image_embedding != nullptr)
+        conf.image_embedding = c.o->image_embedding;
+    conf.input_scale = c.o->input_scale;
+    conf.use_shading = c.o->use_shading != 0;
+    conf.cut_surface = c.o->cut_surface != 0;
+    conf.create_triangle_mesh = c.o->create_triangle_mesh != 0;
+    conf.simplify = c.o->simplify != 0;
+    conf.use_aabb = c.o->use_aabb != 0;
+    std::copy(c.o->aabb_min, c.o->aabb_min + 3, conf.aabb_min);
+    std::copy(c.o->aabb_max, c.o->aabb_max + 3, conf.aabb_max);
+    conf.device = c.o->device;
+    if (c.view_ids != nullptr)
+        conf.view_ids.assign(c.view_ids, c.view_ids + c.n_view_ids);
+    return conf;
+}
+
+// the file's name (truncated to the room there is) and the two counts
+void
+export_results(ExportCall const& c, std::string const& path, std::size_t nv, std::size_t nf)
+{
+    if (c.ply_path != nullptr && c.ply_path_capacity > 0) {
+        std::size_t const k = std::min<std::size_t>(path.size(),
+            (std::size_t)c.ply_path_capacity - 1);
+        std::memcpy(c.ply_path, path.data(), k);
+        c.ply_path[k] = 0;
+    }
+    if (c.n_vertices != nullptr)
+        *c.n_vertices = (int64_t)nv;
+    if (c.n_faces != nullptr)
+        *c.n_faces = (int64_t)nf;
+}
+
+// The three fused entries: the settings records share their first four members;
+// `rest` sets what a record has beyond them.
+template <class Settings, class Rest> int
+generate_fused(ExportCall const& c, char const* entry, const Settings *f, Rest rest)
+{
+    return guarded([&] {
+        PointCloudSettings const conf = export_settings(c, entry, f != nullptr);
+        MeshGenerator::FusedOptions fo;
+        fo.voxel_size = f->voxel_size;
+        fo.resolution = f->resolution;
+        fo.trunc = f->trunc;
+        fo.min_weight = f->min_weight;
+        rest(fo);
+        std::size_t nv = 0, nf = 0;
+        std::string const path = generate_scene_fused(c.scene_dir, conf, fo, &nv, &nf);
+        export_results(c, path, nv, nf);
+    });
+}
+
+} // namespace
+
+extern "C" int
+smvs_host_generate_point_cloud(const char *scene_dir,
+    const smvs_host_point_cloud_settings *o, const int *view_ids, int n_view_ids,
+    char *ply_path, int ply_path_capacity, int64_t *n_points)
+{
+    ExportCall const c = { scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
+        n_points };
+    return guarded([&] {
+        PointCloudSettings const conf = export_settings(c, "smvs_host_generate_point_cloud");
+        std::size_t n = 0;
+        std::string const path = generate_scene_point_cloud(scene_dir, conf, &n);
+        export_results(c, path, n, 0);
+    });
+}
+
+extern "C" int
+smvs_host_generate_mesh(const char *scene_dir,
+    const smvs_host_point_cloud_settings *o, const int *view_ids, int n_view_ids,
+    char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces)
+{
+    ExportCall const c = { scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
+        n_vertices, n_faces };
+    return guarded([&] {
+        PointCloudSettings conf = export_settings(c, "smvs_host_generate_mesh");
+        conf.create_triangle_mesh = true;
+        std::size_t nv = 0, nf = 0;
+        std::string const path = generate_scene_mesh(scene_dir, conf, &nv, &nf);
+        export_results(c, path, nv, nf);
+    });
+}
+
+extern "C" int
+smvs_host_generate_simplified(const char *scene_dir,
+    const smvs_host_point_cloud_settings *o, const int *view_ids, int n_view_ids,
+    char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces)
+{
+    ExportCall const c = { scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
+        n_vertices, n_faces };
+    return guarded([&] {
+        PointCloudSettings conf = export_settings(c, "smvs_host_generate_simplified");
+        conf.simplify = true;
+        std::size_t nv = 0, nf = 0;
+        std::string const path = generate_scene_simplified(scene_dir, conf, &nv, &nf);
+        export_results(c, path, nv, nf);
+    });
+}
+
+extern "C" int
+smvs_host_generate_fused(const char *scene_dir,
+    const smvs_host_point_cloud_settings *o, const smvs_host_fused_settings *f,
+    const int *view_ids, int n_view_ids, char *ply_path, int ply_path_capacity,
+    int64_t *n_vertices, int64_t *n_faces)
+{
+    return generate_fused({ scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
+        n_vertices, n_faces }, "smvs_host_generate_fused", f,
+        [](MeshGenerator::FusedOptions&) {});
+}
+
+extern "C" int
+smvs_host_generate_fused_sparse(const char *scene_dir,
+    const smvs_host_point_cloud_settings *o, const smvs_host_fused_sparse_settings *f,
+    const int *view_ids, int n_view_ids, char *ply_path, int ply_path_capacity,
+    int64_t *n_vertices, int64_t *n_faces)
+{
+    return generate_fused({ scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
+        n_vertices, n_faces }, "smvs_host_generate_fused_sparse", f,
+        [f](MeshGenerator::FusedOptions& fo) {
+            fo.sparse = true;
+            fo.max_bricks = f->max_bricks;
+        });
+}
+
+extern "C" int
+smvs_host_generate_fused_sparse_cull(const char *scene_dir,
+    const smvs_host_point_cloud_settings *o, const smvs_host_fused_sparse_cull_settings *f,
+    const int *view_ids, int n_view_ids, char *ply_path, int ply_path_capacity,
+    int64_t *n_vertices, int64_t *n_faces)
+{
+    return generate_fused({ scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
+        n_vertices, n_faces }, "smvs_host_generate_fused_sparse_cull", f,
+        [f](MeshGenerator::FusedOptions& fo) {
+            fo.sparse = true;
+            fo.max_bricks = f->max_bricks;
+            fo.cull = f->cull != 0;
+        });
+}
+
+extern "C" int
+smvs_host_save_ply_points(const char *path, const float *xyz, const float *normals,
+    const uint8_t *rgb, const float *confidence, const float *value, int64_t n)
+{
+    return guarded([&] {
+        require(path != nullptr && n >= 0 && (n <= 0 || (xyz != nullptr && normals != nullptr
+            && rgb != nullptr && confidence != nullptr && value != nullptr)),
+            "smvs_host_save_ply_points: bad argument");
+        PointCloud pc;
+        std::size_t const k = (std::size_t)n;
+        pc.xyz.assign(xyz, xyz + 3 * k);
+        pc.normals.assign(normals, normals + 3 * k);
+        pc.colors.assign(rgb, rgb + 3 * k);
+        pc.confidences.assign(confidence, confidence + k);
+        pc.values.assign(value, value + k);
+        save_ply_points(path, pc);
+    });
+}
+
+extern "C" int
+smvs_host_save_ply_mesh(const char *path, const float *xyz, const float *normals,
+    const uint8_t *rgb, const float *confidence, int64_t n, const uint32_t *faces,
+    int64_t m)
+{
+    return guarded([&] {
+        require(path != nullptr && n >= 0 && m >= 0 && (n <= 0 || (xyz != nullptr
+            && normals != nullptr && rgb != nullptr && confidence != nullptr))
+            && (m <= 0 || faces != nullptr), "smvs_host_save_ply_mesh: bad argument");
+        TriangleMesh mesh;
+        std::size_t const k = (std::size_t)n;
+        mesh.xyz.assign(xyz, xyz + 3 * k);
+        mesh.normals.assign(normals, normals + 3 * k);
+        mesh.colors.assign(rgb, rgb + 3 * k);
+        mesh.confidences.assign(confidence, confidence + k);
+        mesh.faces.assign(faces, faces + 3 * (std::size_t)m);
+        save_ply_mesh(path, mesh);
+    });
+}

@@ -176,8 +176,8 @@ int smvs_host_sgm_depth_merge(const smvs_host_view *main_view,
 /* The merge options as a default-constructed SGMStereo::Options and
  * ReconSettings hold them (no device involved): ints4 = { Options::
  * num_neighbors, consensus, min_agree, 0 }, then the same of ReconSettings::
- * sgm_neighbors, sgm_consensus, sgm_min_agree in ints4[4 .. 7]; ratios2 =
- * { Options::agree_ratio, ReconSettings::sgm_agree_ratio }. */
+ * sgm (an SGMStereo::Options) in ints4[4 .. 7]; ratios2 =
+ * { Options::agree_ratio, ReconSettings::sgm.agree_ratio }. */
 int smvs_host_sgm_merge_defaults(int *ints8, float *ratios2);
 /* SGMStereo::Options::sweep / sweep_min_views / sweep_best_k /
  * sweep_support_cost / sweep_min_support (the multi-neighbour plane sweep of
@@ -283,7 +283,7 @@ int smvs_host_sgm_filter_defaults(int *ints6, float *ratios2);
 /* The switches of the SGM front end that the reference does not have, as a
  * default-constructed SGMStereo::Options and ReconSettings hold them (no
  * device involved): out4 = { Options::adaptive_penalty2, Options::subplane,
- * ReconSettings::sgm_adaptive_penalty2, ReconSettings::sgm_subplane }. */
+ * ReconSettings::sgm.adaptive_penalty2, ReconSettings::sgm.subplane }. */
 int smvs_host_sgm_default_switches(int *out4);
 
 /* smvs::Surface on its own (lib/surface.cc): Surface::create (from the bundle
@@ -380,7 +380,7 @@ int smvs_host_reconstruct_scene(const char *scene_dir,
     const smvs_host_recon_settings *settings, const int *view_ids, int n_view_ids,
     int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
     int *n_skipped, double *seconds, int *input_scale_used);
-/* The same with ReconSettings::sgm_adaptive_penalty2 (the settings struct keeps
+/* The same with ReconSettings::sgm.adaptive_penalty2 (the settings struct keeps
  * its layout for existing callers, so the switch is an argument: != 0 runs the
  * SGM front end of every view as the reference's build without SSE does,
  * lib/sgm_stereo.cc:310-346; 0 is smvs_host_reconstruct_scene). */
@@ -390,7 +390,7 @@ int smvs_host_reconstruct_scene_mode(const char *scene_dir,
     int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used);
 
 /* The same with a word of switches the settings struct does not hold (it keeps
- * its layout for existing callers).  Bit 0: ReconSettings::sgm_adaptive_penalty2
+ * its layout for existing callers).  Bit 0: ReconSettings::sgm.adaptive_penalty2
  * (smvs_host_reconstruct_scene_mode's argument); bit 1: ReconSettings::
  * device_input_scaling -- the input scaling of app/smvsrecon.cc:621-650 runs on
  * the device (smvs_rescale_half_gaussian), one ViewQueue task per view; the
@@ -414,7 +414,7 @@ int smvs_host_reconstruct_scene_flags(const char *scene_dir,
     const smvs_host_recon_settings *settings, unsigned flags, const int *view_ids,
     int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
     int *n_skipped, double *seconds, int *input_scale_used);
-/* The same with ReconSettings::sgm_num_steps, the inverse-depth planes of every
+/* The same with ReconSettings::sgm.num_steps, the inverse-depth planes of every
  * view's SGM front end (the settings struct keeps its layout): 2 .. 128, or a
  * multiple of 8 from 136 to 256; any other count is an argument error before
  * the scene is read.  smvs_host_reconstruct_scene_flags forwards to this with
@@ -423,7 +423,7 @@ int smvs_host_reconstruct_scene_steps(const char *scene_dir,
     const smvs_host_recon_settings *settings, unsigned flags, int sgm_num_steps,
     const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
     int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used);
-/* The same with ReconSettings::sgm_subplane (an argument: the settings struct
+/* The same with ReconSettings::sgm.subplane (an argument: the settings struct
  * keeps its layout and the flags word its known bits): != 0 runs every view's
  * SGM front end with SGMStereo::Options::subplane.  An smvs-sgm embedding of
  * the right size is reused as before (app/smvsrecon.cc:702-708), so a scene
@@ -434,8 +434,8 @@ int smvs_host_reconstruct_scene_subplane(const char *scene_dir,
     int sgm_subplane, const int *view_ids, int n_view_ids, int *reconstructed_out,
     int max_reconstructed, int *n_reconstructed, int *n_skipped, double *seconds,
     int *input_scale_used);
-/* The same with ReconSettings::sgm_neighbors / sgm_consensus / sgm_agree_ratio /
- * sgm_min_agree (arguments: the settings struct keeps its layout): every view's
+/* The same with ReconSettings::sgm.num_neighbors / consensus / agree_ratio /
+ * min_agree (arguments: the settings struct keeps its layout): every view's
  * smvs-sgm map from its first sgm_neighbors neighbours (capped by the
  * neighbours the view has), merged by consensus when sgm_consensus != 0;
  * sgm_neighbors > 2 without it is an argument error.  The reuse rule is that of
@@ -447,7 +447,7 @@ int smvs_host_reconstruct_scene_merge(const char *scene_dir,
     int sgm_min_agree, const int *view_ids, int n_view_ids, int *reconstructed_out,
     int max_reconstructed, int *n_reconstructed, int *n_skipped, double *seconds,
     int *input_scale_used);
-/* The same with ReconSettings::sgm_sweep and its four values: every view's
+/* The same with ReconSettings::sgm.sweep and its four values: every view's
  * smvs-sgm map by the plane sweep over its first sgm_neighbors neighbours.
  * sweep together with sgm_consensus is an argument error; sweep == NULL: off
  * (smvs_host_reconstruct_scene_merge forwards to this with NULL).  The reuse
@@ -459,8 +459,8 @@ int smvs_host_reconstruct_scene_sweep(const char *scene_dir,
     int n_view_ids, int *reconstructed_out, int max_reconstructed, int *n_reconstructed,
     int *n_skipped, double *seconds, int *input_scale_used);
 
-/* The same with ReconSettings::sgm_uniqueness / sgm_uniqueness_window /
- * sgm_speckle_size / sgm_speckle_ratio: the two filters in every view's SGM
+/* The same with ReconSettings::sgm.uniqueness / uniqueness_window /
+ * speckle_size / speckle_ratio: the two filters in every view's SGM
  * front end (arguments: the settings struct keeps its layout).  A value outside
  * the accepted set is an argument error before the scene is read; filter ==
  * NULL: off (smvs_host_reconstruct_scene_sweep forwards to this with NULL).  The
@@ -472,8 +472,8 @@ int smvs_host_reconstruct_scene_filtered(const char *scene_dir,
     const int *view_ids, int n_view_ids, int *reconstructed_out, int max_reconstructed,
     int *n_reconstructed, int *n_skipped, double *seconds, int *input_scale_used);
 
-/* The same with ReconSettings::sgm_photo_radius / sgm_photo_best_k /
- * sgm_photo_min_views / sgm_photo_min_score / sgm_photo_witnesses: the
+/* The same with ReconSettings::sgm.photo_radius / photo_best_k /
+ * photo_min_views / photo_min_score / photo_witnesses: the
  * photo-consistency test behind every view's SGM front end, the confidence saved
  * as smvs-sgm-confidence.  A value outside the accepted set is an argument error
  * before the scene is read; photo == NULL: off
@@ -487,9 +487,9 @@ int smvs_host_reconstruct_scene_photo(const char *scene_dir,
     int *reconstructed_out, int max_reconstructed, int *n_reconstructed, int *n_skipped,
     double *seconds, int *input_scale_used);
 
-/* The same with ReconSettings::sgm_refine_sweeps / sgm_refine_samples /
- * sgm_refine_depth_step / sgm_refine_slant_step / sgm_refine_seed /
- * sgm_refine_fill: the plane refinement sweeps in the photo test's place, the
+/* The same with ReconSettings::sgm.refine_sweeps / refine_samples /
+ * refine_depth_step / refine_slant_step / refine_seed /
+ * refine_fill: the plane refinement sweeps in the photo test's place, the
  * slants saved as smvs-sgm-slant (two channels) next to smvs-sgm-confidence.  A
  * value outside the accepted set is an argument error before the scene is read;
  * refine == NULL: off (smvs_host_reconstruct_scene_photo forwards to this with

@@ -399,10 +399,10 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
     typedef std::chrono::steady_clock Clock;
     ReconSettings conf = conf_in;
     // (before the scene is read and any task starts)
-    if (!SGMStereo::Options::valid_num_steps(conf.sgm_num_steps))
+    if (!SGMStereo::Options::valid_num_steps(conf.sgm.num_steps))
         throw std::invalid_argument("sgm_num_steps must be in [2, 128] or a multiple "
             "of 8 in [136, 256]");
-    if (conf.init_slants && conf.sgm_refine_sweeps == 0)
+    if (conf.init_slants && conf.sgm.refine_sweeps == 0)
         throw std::invalid_argument("init_slants needs sgm_refine_sweeps > 0: without the "
             "refinement sweeps the SGM front end produces no slants");
     Scene::Ptr scene = Scene::create(scene_path);
@@ -415,7 +415,7 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
     } catch (std::exception const&) {
         bundle = nullptr;
         conf.use_sgm = true;
-        if (conf.sgm_max == 0.0f)
+        if (conf.sgm.max_depth == 0.0f)
             throw std::invalid_argument("no bundle file and no SGM depth range "
                 "(sgm_min / sgm_max)");
     }
@@ -571,7 +571,7 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                 if (conf.use_sgm) {
                     // :693-709: reuse an smvs-sgm embedding of the right size
                     int sgm_w = main_view->get_width(), sgm_h = main_view->get_height();
-                    for (int s = 0; s < conf.sgm_scale; ++s) {
+                    for (int s = 0; s < conf.sgm.scale; ++s) {
                         sgm_w = (sgm_w + 1) / 2;
                         sgm_h = (sgm_h + 1) / 2;
                     }
@@ -579,38 +579,8 @@ reconstruct_scene(std::string const& scene_path, ReconSettings const& conf_in)
                     bool const have = mvei_header(view.image_path("smvs-sgm"), whct)
                         && whct[0] == sgm_w && whct[1] == sgm_h;
                     if (conf.force_sgm || !have) {
-                        SGMStereo::Options sgm_opts;
-                        sgm_opts.scale = conf.sgm_scale;
-                        sgm_opts.num_steps = conf.sgm_num_steps;
-                        sgm_opts.min_depth = conf.sgm_min;
-                        sgm_opts.max_depth = conf.sgm_max;
+                        SGMStereo::Options sgm_opts = conf.sgm;
                         sgm_opts.device = device;
-                        sgm_opts.adaptive_penalty2 = conf.sgm_adaptive_penalty2;
-                        sgm_opts.subplane = conf.sgm_subplane;
-                        sgm_opts.num_neighbors = conf.sgm_neighbors;
-                        sgm_opts.consensus = conf.sgm_consensus;
-                        sgm_opts.agree_ratio = conf.sgm_agree_ratio;
-                        sgm_opts.min_agree = conf.sgm_min_agree;
-                        sgm_opts.sweep = conf.sgm_sweep;
-                        sgm_opts.sweep_min_views = conf.sgm_sweep_min_views;
-                        sgm_opts.sweep_best_k = conf.sgm_sweep_best_k;
-                        sgm_opts.sweep_support_cost = conf.sgm_sweep_support_cost;
-                        sgm_opts.sweep_min_support = conf.sgm_sweep_min_support;
-                        sgm_opts.uniqueness = conf.sgm_uniqueness;
-                        sgm_opts.uniqueness_window = conf.sgm_uniqueness_window;
-                        sgm_opts.speckle_size = conf.sgm_speckle_size;
-                        sgm_opts.speckle_ratio = conf.sgm_speckle_ratio;
-                        sgm_opts.photo_radius = conf.sgm_photo_radius;
-                        sgm_opts.photo_best_k = conf.sgm_photo_best_k;
-                        sgm_opts.photo_min_views = conf.sgm_photo_min_views;
-                        sgm_opts.photo_min_score = conf.sgm_photo_min_score;
-                        sgm_opts.photo_witnesses = conf.sgm_photo_witnesses;
-                        sgm_opts.refine_sweeps = conf.sgm_refine_sweeps;
-                        sgm_opts.refine_samples = conf.sgm_refine_samples;
-                        sgm_opts.refine_depth_step = conf.sgm_refine_depth_step;
-                        sgm_opts.refine_slant_step = conf.sgm_refine_slant_step;
-                        sgm_opts.refine_seed = conf.sgm_refine_seed;
-                        sgm_opts.refine_fill = conf.sgm_refine_fill;
                         (void)reconstruct_sgm_depth_for_view(sgm_opts, main_view,
                             stereo_views, bundle);
                         save_mvei(view.image_path("smvs-sgm"),

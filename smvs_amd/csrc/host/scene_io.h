@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "image.h"
+#include "sgm_stereo.h"
 #include "view_selection.h"
 
 namespace smvs_amd {
@@ -92,76 +93,14 @@ struct ReconSettings
     bool gamma_correction = false;
     bool use_sgm = true;
     bool force_recon = false, force_sgm = false, full_optimization = false;
-    float sgm_min = 0.0f, sgm_max = 0.0f;
-    int sgm_scale = 1;
-    // not in the reference's AppSettings: SGMStereo::Options::adaptive_penalty2
-    // (the reference's build without SSE, lib/sgm_stereo.cc:310-346)
-    bool sgm_adaptive_penalty2 = false;
-    // not in the reference's AppSettings (app/smvsrecon.cc:693-709 leaves
-    // SGMStereo::Options::num_steps at its default): the inverse-depth planes of
-    // the SGM front end, 2 .. 128 or a multiple of 8 from 136 to 256
-    int sgm_num_steps = 128;
-    // not in the reference's AppSettings: SGMStereo::Options::subplane (the
-    // smvs-sgm map refined between the planes).  An smvs-sgm embedding of the
-    // right size is reused as before (app/smvsrecon.cc:702-708): switching this
-    // on for a scene that has one needs force_sgm
-    bool sgm_subplane = false;
-    // not in the reference's AppSettings: SGMStereo::Options::num_neighbors /
-    // consensus / agree_ratio / min_agree -- the smvs-sgm map of a view from its
-    // first sgm_neighbors neighbours (capped by the neighbours the view has),
-    // merged by consensus; more than two need sgm_consensus.  0.95 and 2 are
-    // defaults of a user option, not tuned values, and their effect on real
-    // scenes has not been measured.  As for sgm_subplane, an smvs-sgm embedding
-    // of the right size is reused: switching this on for a scene that has one
-    // needs force_sgm
-    int sgm_neighbors = 2;
-    bool sgm_consensus = false;
-    float sgm_agree_ratio = 0.95f;
-    int sgm_min_agree = 2;
-    // SGMStereo::Options::sweep / sweep_min_views / sweep_best_k /
-    // sweep_support_cost / sweep_min_support -- the smvs-sgm map of a view by the
-    // plane sweep over its first sgm_neighbors neighbours (not together with
-    // sgm_consensus); -1: the default at n neighbours.  Untuned defaults of a
-    // user option; the reuse rule is that of sgm_subplane (force_sgm).
-    bool sgm_sweep = false;
-    int sgm_sweep_min_views = -1;
-    int sgm_sweep_best_k = -1;
-    int sgm_sweep_support_cost = 20;
-    int sgm_sweep_min_support = -1;
-    // SGMStereo::Options::uniqueness / uniqueness_window / speckle_size /
-    // speckle_ratio -- the two filters of include/smvs_hip.h ("Two single-run
-    // rejections") in every view's SGM front end, whichever of the three it is.
-    // Off by default; untuned defaults of a user option; the reuse rule is that
-    // of sgm_subplane (force_sgm).
-    int sgm_uniqueness = 0;
-    int sgm_uniqueness_window = 1;
-    int sgm_speckle_size = 0;
-    float sgm_speckle_ratio = 0.95f;
-    // SGMStereo::Options::photo_radius / photo_best_k / photo_min_views /
-    // photo_min_score / photo_witnesses -- the multi-view photo-consistency test
-    // of include/smvs_hip.h behind every view's SGM front end, whichever of the
-    // three it is, with the view's neighbours as witnesses (-1: all num_neighbors
-    // of them); the confidence is saved as smvs-sgm-confidence next to smvs-sgm.
-    // Off by default (radius 0); untuned defaults of a user option; the reuse
-    // rule is that of sgm_subplane (force_sgm).
-    int sgm_photo_radius = 0;
-    int sgm_photo_best_k = 2;
-    int sgm_photo_min_views = 2;
-    float sgm_photo_min_score = 0.49f;
-    int sgm_photo_witnesses = -1;
-    // SGMStereo::Options::refine_sweeps / refine_samples / refine_depth_step /
-    // refine_slant_step / refine_seed / refine_fill -- the multi-view plane
-    // refinement sweeps of include/smvs_hip.h in the photo test's place (they
-    // need sgm_photo_radius > 0); the slants are saved as smvs-sgm-slant (two
-    // channels) next to smvs-sgm-confidence; the optimizer reads them with
-    // init_slants only.  Off by default (sweeps 0); untuned defaults of a user option; the
-    // reuse rule is that of sgm_subplane (force_sgm).
-    int sgm_refine_sweeps = 0;
-    int sgm_refine_samples = 2;
-    float sgm_refine_depth_step = 0.02f;
-    float sgm_refine_slant_step = 0.01f;
-    uint32_t sgm_refine_seed = 1;
-    int sgm_refine_fill = 1;
+    // Every option of the SGM front end, under SGMStereo::Options' own names and
+    // defaults (sgm_stereo.h documents them); smvsrecon's --sgm-range and
+    // --sgm-scale are min_depth / max_depth and scale.  `device` is filled per
+    // task.  An smvs-sgm embedding of the right size is reused as in
+    // app/smvsrecon.cc:702-708, so changing an option for a scene that has one
+    // needs force_sgm; the photo test's confidence and the refinement sweeps'
+    // slants are saved as smvs-sgm-confidence and smvs-sgm-slant next to it.
+    SGMStereo::Options sgm;
     // not in the reference's AppSettings: the input scaling of :621-650 on the
     // device (rescale_half_size_gaussian_device), one ViewQueue task per view
     bool device_input_scaling = false;
@@ -170,7 +109,7 @@ struct ReconSettings
     bool device_shading_prep = false;
     // not in the reference's AppSettings: DepthOptimizer::Options::init_slants --
     // the initial surface's node slopes from every view's smvs-sgm-slant
-    // embedding.  Needs sgm_refine_sweeps > 0 (an error otherwise, before the
+    // embedding.  Needs sgm.refine_sweeps > 0 (an error otherwise, before the
     // scene is read); a view whose smvs-sgm map is reused from disk needs its
     // smvs-sgm-slant next to it.  Off by default.
     bool init_slants = false;

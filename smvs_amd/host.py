@@ -258,7 +258,7 @@ class SgmSweep(C.Structure):
 
 class SgmFilter(C.Structure):
     """smvs_host_sgm_filter of csrc/host/host_capi.h: ReconSettings::
-    sgm_uniqueness / sgm_uniqueness_window / sgm_speckle_size / sgm_speckle_ratio
+    sgm.uniqueness / uniqueness_window / speckle_size / speckle_ratio
     (SGMStereo::Options::uniqueness / ...), passed next to the settings struct,
     which keeps its layout."""
     _fields_ = [("uniqueness", C.c_int), ("uniqueness_window", C.c_int),
@@ -267,8 +267,8 @@ class SgmFilter(C.Structure):
 
 class SgmPhoto(C.Structure):
     """smvs_host_sgm_photo of csrc/host/host_capi.h: ReconSettings::
-    sgm_photo_radius / sgm_photo_best_k / sgm_photo_min_views / sgm_photo_min_score /
-    sgm_photo_witnesses (SGMStereo::Options::photo_radius / ...), passed next to
+    sgm.photo_radius / photo_best_k / photo_min_views / photo_min_score /
+    photo_witnesses (SGMStereo::Options::photo_radius / ...), passed next to
     the settings struct, which keeps its layout."""
     _fields_ = [("radius", C.c_int), ("best_k", C.c_int), ("min_views", C.c_int),
                 ("min_score", C.c_float), ("witnesses", C.c_int)]
@@ -276,8 +276,8 @@ class SgmPhoto(C.Structure):
 
 class SgmRefine(C.Structure):
     """smvs_host_sgm_refine of csrc/host/host_capi.h: ReconSettings::
-    sgm_refine_sweeps / sgm_refine_samples / sgm_refine_depth_step /
-    sgm_refine_slant_step / sgm_refine_seed / sgm_refine_fill (SGMStereo::Options::
+    sgm.refine_sweeps / refine_samples / refine_depth_step /
+    refine_slant_step / refine_seed / refine_fill (SGMStereo::Options::
     refine_sweeps / ...), passed next to the settings struct, which keeps its
     layout."""
     _fields_ = [("sweeps", C.c_int), ("samples", C.c_int), ("depth_step", C.c_float),
@@ -320,20 +320,20 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     sgm_num_steps: the inverse-depth planes of the SGM front end
     (SGMStereo::Options::num_steps): 2 .. 128, or a multiple of 8 from 136 to
     256; smvsrecon runs 128.
-    sgm_subplane: ReconSettings::sgm_subplane -- the smvs-sgm map of every view
+    sgm_subplane: ReconSettings::sgm.subplane -- the smvs-sgm map of every view
     refined between the planes (SGMStereo::Options::subplane); off by default.
     An smvs-sgm embedding of the right size is reused as before
     (app/smvsrecon.cc:702-708): switching the mode on for a scene that has been
     reconstructed already needs force_sgm as well.
     sgm_neighbors, sgm_consensus, sgm_agree_ratio, sgm_min_agree:
-    ReconSettings::sgm_neighbors / ... -- the smvs-sgm map of every view from its
+    ReconSettings::sgm.num_neighbors / ... -- the smvs-sgm map of every view from its
     first sgm_neighbors neighbours (capped by the neighbours the view has, which
     num_neighbors bounds), merged by consensus (SGMStereo::Options::consensus,
     SMVS_SGM_MERGE_CONSENSUS of include/smvs_hip.h); more than two neighbours
     without sgm_consensus is an error.  Off by default; 0.95 and 2 are defaults of
     a user option, not tuned values, and nobody has measured their effect on real
     scenes.  The reuse rule is that of sgm_subplane (force_sgm).
-    sgm_sweep and its four values: ReconSettings::sgm_sweep / ... -- the smvs-sgm
+    sgm_sweep and its four values: ReconSettings::sgm.sweep / ... -- the smvs-sgm
     map of every view by the multi-neighbour plane sweep of include/smvs_hip.h
     over its first sgm_neighbors neighbours (one cost volume from all of them,
     one aggregation, one winner, a support test; no left/right check) instead of
@@ -343,7 +343,7 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     untuned, and nobody has measured them on real scenes.  The reuse rule is that
     of sgm_subplane (force_sgm).
     sgm_uniqueness, sgm_uniqueness_window, sgm_speckle_size, sgm_speckle_ratio:
-    ReconSettings::sgm_uniqueness / ... -- the two filters of include/smvs_hip.h
+    ReconSettings::sgm.uniqueness / ... -- the two filters of include/smvs_hip.h
     in every view's SGM front end, whichever of the three it is: the uniqueness
     test (0 .. 99, a percentage; 0 is off) over planes more than the window
     (1 .. 256) from the winner in every run, and the removal of connected
@@ -352,7 +352,7 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     untuned, and nobody has measured them on real scenes.  The reuse rule is that
     of sgm_subplane (force_sgm).
     sgm_photo_radius, sgm_photo_best_k, sgm_photo_min_views, sgm_photo_min_score,
-    sgm_photo_witnesses: ReconSettings::sgm_photo_radius / ... -- the multi-view
+    sgm_photo_witnesses: ReconSettings::sgm.photo_radius / ... -- the multi-view
     photo-consistency test of include/smvs_hip.h behind every view's SGM front
     end, whichever of the three it is, before the speckle removal: radius 1 .. 3
     (0 is off), the view's first sgm_photo_witnesses neighbours as witnesses (-1:
@@ -363,7 +363,7 @@ def reconstruct_scene(scene_dir, view_ids=None, image_embedding="undistorted",
     scenes.  The reuse rule is that of sgm_subplane (force_sgm).
     sgm_refine_sweeps, sgm_refine_samples, sgm_refine_depth_step,
     sgm_refine_slant_step, sgm_refine_seed, sgm_refine_fill: ReconSettings::
-    sgm_refine_sweeps / ... -- the multi-view plane refinement sweeps of
+    sgm.refine_sweeps / ... -- the multi-view plane refinement sweeps of
     include/smvs_hip.h in the photo test's place (they need sgm_photo_radius > 0):
     1 .. 8 red-black sweeps (0 is off) in which a pixel adopts a neighbour's plane
     or one of `samples` perturbations of its own whenever that raises its
