@@ -1,297 +1,8 @@
-// Cross-view consistency cut of the depth maps on gfx950.
+// Point and triangle-mesh export on gfx950 (smvs_points_generate,
+// smvs_mesh_generate).  The views come out of the shared view stage
+// (mesh_cut.hip); the scan, the AABB vertex clip and the result fill are
+// export_common.hip's (export_shared.h).
 //
-// Replaces MeshGenerator::cut_depth_maps (reference: lib/mesh_generator.cc:24-158)
-// together with the normal preparation of generate_mesh (:189-208) and
-// MeshGenerator::ViewProjection (:300-342).  Every pixel of every view is an
-// independent unit: its 3-D point is reprojected into all other views and
-// kept when enough of them see a compatible surface there.  One thread per
-// pixel walks the other views in the reference's order (the consistency sum
-// and its early exit are order dependent); all maps stay resident on the
-// device, so N views cost one upload and one download of N maps.
-//
-// Arithmetic: float, in the reference's operation order, FMA contraction off
-// (hipcc's float division and square root are correctly rounded), so the cut
-// maps are bit-identical to the CPU path.  MVE pieces (pixel_3dpos,
-// fill_cam_to_world, fill_camera_pos, depthmap_convert_conventions) follow the
-// assumptions listed in tests/golden/README.md [MVE-unverified].
-#include "common.h"
-#include "mesh_shared.h"
-
-#include <algorithm>
-#include <cmath>
-#include <vector>
-
-namespace smvs_hip {
-
-// ViewProjection::get_surface_power, mesh_generator.cc:321-342
-__device__ __forceinline__ float
-surface_power(MeshViewDev const &V, const float *pos, const float *normal)
-{
-#pragma clang fp contract(off)
-    const float *KR = V.KR;
-    float const u = dot3(KR + 0, pos) - V.t[0];
-    float const v = dot3(KR + 3, pos) - V.t[1];
-    float const w = dot3(KR + 6, pos) - V.t[2];
-    float const denom = w * w;
-    float u_dx[3], v_dx[3];
-    for (int k = 0; k < 3; ++k) {
-        u_dx[k] = (KR[k] * w - KR[6 + k] * u) / denom;
-        v_dx[k] = (KR[3 + k] * w - KR[6 + k] * v) / denom;
-    }
-    float cr[3];
-    cr[0] = u_dx[1] * v_dx[2] - u_dx[2] * v_dx[1];
-    cr[1] = u_dx[2] * v_dx[0] - u_dx[0] * v_dx[2];
-    cr[2] = u_dx[0] * v_dx[1] - u_dx[1] * v_dx[0];
-    return -dot3(normal, cr);
-}
-
-// generate_mesh :197-208 (normals to world space) and cut_depth_maps :31-47
-// (ray-length copies, z-depth conversion) for one view
-__global__ void __launch_bounds__(256)
-mesh_prepare_kernel(const MeshViewDev *views, int i)
-{
-#pragma clang fp contract(off)
-    MeshViewDev const V = views[i];
-    int const x = blockIdx.x * blockDim.x + threadIdx.x;
-    int const y = blockIdx.y;
-    if (x >= V.w)
-        return;
-    size_t const p = (size_t)y * V.w + x;
-    float const n[3] = { V.normals[3 * p], -V.normals[3 * p + 1],
-        -V.normals[3 * p + 2] };
-    for (int r = 0; r < 3; ++r) {
-        float s = 0.0f;
-        s += V.rot[r] * n[0];
-        s += V.rot[3 + r] * n[1];
-        s += V.rot[6 + r] * n[2];
-        V.normals[3 * p + r] = s;
-    }
-    float const d = V.depth_ray[p];
-    V.cut[p] = d;
-    float const px = (float)x + 0.5f, py = (float)y + 0.5f;
-    float v[3];
-    for (int r = 0; r < 3; ++r)
-        v[r] = V.invproj[3 * r] * px + V.invproj[3 * r + 1] * py
-            + V.invproj[3 * r + 2];
-    float const len = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    // (depthmap_convert_conventions: `double len = px.norm(); dm *= 1.0 / len`,
-    // tests/golden/README.md M10)
-    V.depth_z[p] = (float)((double)d * (1.0 / (double)len));
-}
-
-// cut_depth_maps :61-150 for view i
-__global__ void __launch_bounds__(256)
-mesh_cut_kernel(const MeshViewDev *__restrict__ views, int n_views, int i)
-{
-#pragma clang fp contract(off)
-    MeshViewDev const V = views[i];
-    int const x = blockIdx.x * blockDim.x + threadIdx.x;
-    int const y = blockIdx.y;
-    if (x >= V.w)
-        return;
-    size_t const p = (size_t)y * V.w + x;
-    float const d = V.depth_ray[p];
-    if (d == 0.0f)
-        return;
-    float pos[3];
-    world_point(V, x, y, d, pos);
-    float const normal[3] = { V.normals[3 * p], V.normals[3 * p + 1],
-        V.normals[3 * p + 2] };
-    float const power = surface_power(V, pos, normal);
-    bool cut = power < 0;
-    float consistency = 0;
-    for (int j = 0; j < n_views; ++j) {
-        if (j == i)
-            continue;
-        MeshViewDev const &N = views[j];
-        float proj[3];
-        proj[0] = dot3(N.KR + 0, pos) - N.t[0];
-        proj[1] = dot3(N.KR + 3, pos) - N.t[1];
-        proj[2] = dot3(N.KR + 6, pos) - N.t[2];
-        if (proj[2] < 0)
-            continue;
-        // A point in view j's principal plane (proj[2] == 0, or NaN): the
-        // reference's quotient is infinite or NaN, its static_cast<int> gives
-        // INT_MIN on x86 and the pair is skipped.  A saturating conversion
-        // would turn NaN into column 0.
-        if (!(proj[2] > 0))
-            continue;
-        // (int) truncates toward zero, so a quotient in (-1, 0) is column or
-        // row 0; the range is tested on the float, and only a finite quotient
-        // inside it is converted
-        float const qx = proj[0] / proj[2], qy = proj[1] / proj[2];
-        if (!(qx > -1.0f && qx < (float)N.w && qy > -1.0f && qy < (float)N.h))
-            continue;
-        int const xj = (int)qx, yj = (int)qy;
-        size_t const pj = (size_t)yj * N.w + xj;
-        float const dm_j = N.depth_z[pj];
-        if (dm_j == 0.0f)
-            continue;
-        float const power_j = surface_power(N, pos, normal);
-        float pos_j[3];
-        world_point(N, xj, yj, N.depth_ray[pj], pos_j);
-        float const normal_j[3] = { N.normals[3 * pj], N.normals[3 * pj + 1],
-            N.normals[3 * pj + 2] };
-        float const power_j_j = surface_power(N, pos_j, normal_j);
-        if ((double)dm_j * 1.01 < (double)proj[2])
-            continue;
-        if ((double)dm_j * 0.997 > (double)proj[2]) {
-            if ((double)power_j_j > 0.5 * (double)power)
-                consistency -= power_j_j;
-            continue;
-        }
-        if ((double)power_j_j > 2.0 * (double)power
-            || (double)power_j > 2.0 * (double)power) {
-            cut = true;
-            break;
-        }
-        consistency += power_j_j;
-    }
-    if (consistency <= 0)
-        cut = true;
-    if (cut)
-        V.cut[p] = 0.0f;
-}
-
-static void
-mat3_mul_f(const float *A, const float *B, float *C)
-{
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-            float s = 0.0f;
-            for (int k = 0; k < 3; ++k)
-                s += A[3 * r + k] * B[3 * k + c];
-            C[3 * r + c] = s;
-        }
-}
-
-// CameraInfo::fill_calibration / fill_inverse_calibration (ppoint = 0.5,
-// paspect = 1) at the depth map's size, ViewProjection's KR and t, and the
-// cam-to-world transform of one view
-void
-fill_view_camera(int width, int height, float flen, const float *rot,
-    const float *trans, MeshViewDev &V)
-{
-    V.w = width;
-    V.h = height;
-    float const fw = (float)width, fh = (float)height;
-    float const dim = fw > fh ? fw : fh;
-    float const ax = flen * dim, ay = flen * dim;
-    float const K[9] = { ax, 0, fw * 0.5f, 0, ay, fh * 0.5f, 0, 0, 1 };
-    float const Ki[9] = { 1.0f / ax, 0, -fw * 0.5f / ax, 0, 1.0f / ay,
-        -fh * 0.5f / ay, 0, 0, 1 };
-    memcpy(V.invproj, Ki, sizeof(Ki));
-    memcpy(V.rot, rot, sizeof(V.rot));
-    mat3_mul_f(K, rot, V.KR);
-    // fill_camera_pos = fill_cam_to_world's translation = -R^T t
-    float pos[3];
-    for (int r = 0; r < 3; ++r) {
-        float s = 0.0f;
-        for (int k = 0; k < 3; ++k)
-            s += -rot[3 * k + r] * trans[k];
-        pos[r] = s;
-        V.c2w_t[r] = s;
-    }
-    for (int r = 0; r < 3; ++r) {
-        float s = 0.0f;
-        for (int k = 0; k < 3; ++k)
-            s += V.KR[3 * r + k] * pos[k];
-        V.t[r] = s;
-    }
-}
-
-// generate_mesh :197-215 for all views: normals to world space, then the cut
-// when asked for and there is more than one view (:211)
-int
-launch_prepare_and_cut(hipStream_t stream, const MeshViewDev *d_table,
-    std::vector<MeshViewDev> const &table, bool cut)
-{
-    int const n_views = (int)table.size();
-    for (int i = 0; i < n_views; ++i)
-        hipLaunchKernelGGL(mesh_prepare_kernel,
-            dim3((table[i].w + 255) / 256, table[i].h), dim3(256), 0, stream,
-            d_table, i);
-    SMVS_HIP_CHECK(hipGetLastError());
-    if (cut && n_views > 1)
-        for (int i = 0; i < n_views; ++i)
-            hipLaunchKernelGGL(mesh_cut_kernel,
-                dim3((table[i].w + 255) / 256, table[i].h), dim3(256), 0, stream,
-                d_table, n_views, i);
-    SMVS_HIP_CHECK(hipGetLastError());
-    return SMVS_OK;
-}
-
-} // namespace smvs_hip
-
-using namespace smvs_hip;
-
-extern "C" int
-smvs_cut_depth_maps(int device, smvs_mesh_view *views, int n_views)
-{
-    SMVS_REQUIRE(views != nullptr && n_views >= 1, "no views");
-    SMVS_REQUIRE(n_views <= 4096, "too many views");
-    for (int i = 0; i < n_views; ++i)
-        SMVS_REQUIRE(views[i].width > 0 && views[i].height > 0
-            && views[i].depth != nullptr && views[i].normals != nullptr
-            && views[i].flen > 0.0f, "bad view");
-    // one slab of a pooled workspace (pool.hip) holds every view's maps and
-    // the view table: no allocation per call
-    WorkspaceLease lease(device);
-    if (lease.w == nullptr)
-        return SMVS_ERR_HIP;
-    Workspace &ws = *lease.w;
-    size_t total = 0;
-    auto carve = [&](size_t bytes) {
-        size_t const at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    std::vector<size_t> offsets((size_t)n_views * 4);
-    for (int i = 0; i < n_views; ++i) {
-        size_t const npix = (size_t)views[i].width * views[i].height;
-        offsets[4 * i + 0] = carve(sizeof(float) * npix);       // depth_z
-        offsets[4 * i + 1] = carve(sizeof(float) * npix);       // depth_ray
-        offsets[4 * i + 2] = carve(sizeof(float) * npix);       // cut
-        offsets[4 * i + 3] = carve(sizeof(float) * 3 * npix);   // normals
-    }
-    size_t const table_at = carve(sizeof(MeshViewDev) * n_views);
-    char *slab = nullptr;
-    int rc;
-    if ((rc = ws.ensure(0, total, &slab)) != SMVS_OK)
-        return rc;
-    hipStream_t const stream = ws.stream;
-
-    std::vector<MeshViewDev> table(n_views);
-    for (int i = 0; i < n_views; ++i) {
-        smvs_mesh_view const &in = views[i];
-        MeshViewDev &V = table[i];
-        fill_view_camera(in.width, in.height, in.flen, in.rot, in.trans, V);
-        size_t const npix = (size_t)in.width * in.height;
-        V.depth_z = reinterpret_cast<float *>(slab + offsets[4 * i + 0]);
-        V.depth_ray = reinterpret_cast<float *>(slab + offsets[4 * i + 1]);
-        V.cut = reinterpret_cast<float *>(slab + offsets[4 * i + 2]);
-        V.normals = reinterpret_cast<float *>(slab + offsets[4 * i + 3]);
-        if ((rc = ws.upload(V.depth_ray, in.depth, sizeof(float) * npix))
-            || (rc = ws.upload(V.normals, in.normals, sizeof(float) * 3 * npix)))
-            return rc;
-    }
-    MeshViewDev *d_table = reinterpret_cast<MeshViewDev *>(slab + table_at);
-    if ((rc = ws.upload(d_table, table.data(), sizeof(MeshViewDev) * n_views)))
-        return rc;
-    // a single depth map is returned unchanged (mesh_generator.cc:211)
-    if ((rc = launch_prepare_and_cut(stream, d_table, table, true)))
-        return rc;
-    for (int i = 0; i < n_views; ++i) {
-        size_t const npix = (size_t)table[i].w * table[i].h;
-        if ((rc = ws.download(views[i].depth, table[i].cut, sizeof(float) * npix))
-            || (rc = ws.download(views[i].normals, table[i].normals,
-                    sizeof(float) * 3 * npix)))
-            return rc;
-    }
-    return SMVS_OK;
-}
-
-// ===========================================================================
 // Point export: generate_mesh :217-297 for every view on the device, merged
 // in view-list order, and smvsrecon's AABB clip (app/smvsrecon.cc:306-319).
 // The MVE pieces (depthmap_triangulate, MeshInfo, depthmap_mesh_confidences,
@@ -314,7 +25,15 @@ smvs_cut_depth_maps(int device, smvs_mesh_view *views, int n_views)
 //   normals  recalc_normals as a per-vertex gather over the incident faces
 //   clip     as above, plus kept faces per block, their scan and a scatter
 //            that renumbers the faces' vertices (AABB only)
-// ===========================================================================
+// Arithmetic: float, in the reference's operation order, FMA contraction off.
+#include "common.h"
+#include "export_shared.h"
+#include "mesh_shared.h"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
 namespace smvs_hip {
 
 struct PointViewDev {
@@ -765,135 +484,6 @@ points_emit_kernel(const MeshViewDev *__restrict__ views,
     B.val[id] = s;
 }
 
-// ------------------------------------------------------------ exclusive scan
-// of n 64-bit values in place: 4096 per tile (256 threads x 16), a tile pass,
-// one workgroup over the tile sums, a second tile pass; order fixed, no atomics
-
-__device__ __forceinline__ unsigned long long
-block_exclusive_scan(unsigned long long v, unsigned long long *total)
-{
-    __shared__ unsigned long long wsum[4];
-    int const lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        unsigned long long const t = __shfl_up(inc, o, 64);
-        if (lane >= o)
-            inc += t;
-    }
-    if (lane == 63)
-        wsum[wave] = inc;
-    __syncthreads();
-    unsigned long long pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        pre += k < wave ? wsum[k] : 0ull;
-        tot += wsum[k];
-    }
-    __syncthreads();
-    *total = tot;
-    return pre + inc - v;
-}
-
-__global__ void __launch_bounds__(256)
-scan_tile_sums_kernel(const unsigned long long *__restrict__ a, size_t n,
-    unsigned long long *__restrict__ tiles)
-{
-    size_t const at = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
-    unsigned long long s = 0;
-    for (int k = 0; k < SCAN_ITEMS; ++k)
-        if (at + k < n)
-            s += a[at + k];
-    unsigned long long tot;
-    (void)block_exclusive_scan(s, &tot);
-    if (threadIdx.x == 0)
-        tiles[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(256)
-scan_tiles_kernel(unsigned long long *tiles, size_t n_tiles)
-{
-    unsigned long long carry = 0;
-    for (size_t at = 0; at < n_tiles; at += 256) {
-        size_t const i = at + threadIdx.x;
-        unsigned long long const v = i < n_tiles ? tiles[i] : 0ull;
-        unsigned long long tot;
-        unsigned long long const ex = block_exclusive_scan(v, &tot);
-        if (i < n_tiles)
-            tiles[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0)
-        tiles[n_tiles] = carry;
-}
-
-__global__ void __launch_bounds__(256)
-scan_apply_kernel(unsigned long long *a, size_t n,
-    const unsigned long long *__restrict__ tiles)
-{
-    size_t const at = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
-    unsigned long long vals[SCAN_ITEMS];
-    unsigned long long s = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        vals[k] = at + k < n ? a[at + k] : 0ull;
-        s += vals[k];
-    }
-    unsigned long long tot;
-    unsigned long long run = block_exclusive_scan(s, &tot) + tiles[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        if (at + k < n)
-            a[at + k] = run;
-        run += vals[k];
-    }
-}
-
-int
-exclusive_scan(hipStream_t stream, unsigned long long *a, size_t n,
-    unsigned long long *tiles)
-{
-    size_t const n_tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3((unsigned)n_tiles), dim3(256), 0,
-        stream, a, n, tiles);
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(256), 0, stream, tiles, n_tiles);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)n_tiles), dim3(256), 0,
-        stream, a, n, tiles);
-    SMVS_HIP_CHECK(hipGetLastError());
-    return SMVS_OK;
-}
-
-// ------------------------------------------------------------------ AABB clip
-__global__ void __launch_bounds__(256)
-points_keep_kernel(const float *__restrict__ xyz, size_t n, float3 lo, float3 hi,
-    unsigned long long *__restrict__ keep)
-{
-    size_t const i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    keep[i] = outside_aabb(xyz + 3 * i, lo, hi) ? 0ull : 1ull;
-}
-
-__global__ void __launch_bounds__(256)
-points_compact_kernel(size_t n, float3 lo, float3 hi,
-    const unsigned long long *__restrict__ at, PointBufs src, PointBufs dst)
-{
-    size_t const i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    if (outside_aabb(src.xyz + 3 * i, lo, hi))
-        return;
-    size_t const j = at[i];
-    for (int r = 0; r < 3; ++r) {
-        dst.xyz[3 * j + r] = src.xyz[3 * i + r];
-        dst.nrm[3 * j + r] = src.nrm[3 * i + r];
-        dst.rgb[3 * j + r] = src.rgb[3 * i + r];
-    }
-    dst.conf[j] = src.conf[i];
-    if (dst.val != nullptr)   // (the triangle mesh has no values)
-        dst.val[j] = src.val[i];
-}
-
 // ------------------------------------------------------------- triangle mesh
 // smvsrecon --mesh: the faces survive the AABB clip
 // (delete_vertices_fix_faces, M2) and every vertex gets recalc_normals' angle
@@ -1027,6 +617,8 @@ mesh_face_scatter_kernel(const PointViewDev *__restrict__ pv, PointBufs B, MeshC
 
 } // namespace smvs_hip
 
+using namespace smvs_hip;
+
 namespace {
 
 // what smvs_points_generate and smvs_mesh_generate ask of export_views
@@ -1046,15 +638,13 @@ export_views(int device, const smvs_point_view *views, int n_views,
     SMVS_REQUIRE(n_views <= 4096, "too many views");
     SMVS_REQUIRE(opt.dd_factor >= 0.0f && std::isfinite(opt.dd_factor),
         "dd_factor must be finite and >= 0");
-    size_t total_pix = 0, max_pix = 0;
+    size_t total_pix = 0;
     for (int i = 0; i < n_views; ++i) {
         smvs_point_view const &in = views[i];
         SMVS_REQUIRE(in.width > 0 && in.height > 0 && in.depth != nullptr
             && in.normals != nullptr && in.image != nullptr
             && in.channels >= 1 && in.channels <= 4 && in.flen > 0.0f, "bad view");
-        size_t const npix = (size_t)in.width * in.height;
-        total_pix += npix;
-        max_pix = npix > max_pix ? npix : max_pix;
+        total_pix += (size_t)in.width * in.height;
     }
     // vertex ids are 32-bit and the faces (<= 2 per pixel) as well
     SMVS_REQUIRE(total_pix < ((size_t)1 << 31), "too many pixels");
@@ -1064,22 +654,9 @@ export_views(int device, const smvs_point_view *views, int n_views,
     if (lease.w == nullptr)
         return SMVS_ERR_HIP;
     Workspace &ws = *lease.w;
-    size_t total = 0;
-    auto carve = [&](size_t bytes) {
-        size_t const at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    std::vector<size_t> offsets((size_t)n_views * 5);
-    for (int i = 0; i < n_views; ++i) {
-        size_t const npix = (size_t)views[i].width * views[i].height;
-        offsets[5 * i + 0] = carve(sizeof(float) * npix);       // depth_z
-        offsets[5 * i + 1] = carve(sizeof(float) * npix);       // depth_ray
-        offsets[5 * i + 2] = carve(sizeof(float) * npix);       // cut
-        offsets[5 * i + 3] = carve(sizeof(float) * 3 * npix);   // normals
-        offsets[5 * i + 4] = carve(npix * views[i].channels);   // image
-    }
-    size_t const table_at = carve(sizeof(MeshViewDev) * n_views);
+    Carver carve;
+    ViewSlab s;
+    carve_views(views, n_views, true, carve, s);
     size_t const ptable_at = carve(sizeof(PointViewDev) * n_views);
     size_t const N = total_pix;
     size_t const n_tiles = (N + SCAN_TILE - 1) / SCAN_TILE;
@@ -1103,43 +680,29 @@ export_views(int device, const smvs_point_view *views, int n_views,
     size_t const ftiles_at = clip_faces ? carve(8 * (n_tiles + 1)) : 0;
     char *slab = nullptr;
     int rc;
-    if ((rc = ws.ensure(0, total, &slab)) != SMVS_OK)
+    if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
         return rc;
     hipStream_t const stream = ws.stream;
+    if ((rc = upload_and_prepare(ws, slab, views, n_views, opt.cut, true, s)))
+        return rc;
+    MeshViewDev *const d_table = s.d_table;
 
-    std::vector<MeshViewDev> table(n_views);
     std::vector<PointViewDev> ptable(n_views);
     size_t off = 0;
     for (int i = 0; i < n_views; ++i) {
-        smvs_point_view const &in = views[i];
-        MeshViewDev &V = table[i];
-        fill_view_camera(in.width, in.height, in.flen, in.rot, in.trans, V);
-        size_t const npix = (size_t)in.width * in.height;
-        V.depth_z = reinterpret_cast<float *>(slab + offsets[5 * i + 0]);
-        V.depth_ray = reinterpret_cast<float *>(slab + offsets[5 * i + 1]);
-        V.cut = reinterpret_cast<float *>(slab + offsets[5 * i + 2]);
-        V.normals = reinterpret_cast<float *>(slab + offsets[5 * i + 3]);
+        MeshViewDev const &V = s.table[i];
         PointViewDev &P = ptable[i];
-        P.w = in.width;
-        P.h = in.height;
-        P.channels = in.channels;
+        P.w = V.w;
+        P.h = V.h;
+        P.channels = views[i].channels;
         P.off = off;
         // generate_mesh triangulates the cut maps, or the depth maps (:211-213)
         P.dm = opt.cut ? V.cut : V.depth_ray;
-        P.image = reinterpret_cast<uint8_t *>(slab + offsets[5 * i + 4]);
-        off += npix;
-        if ((rc = ws.upload(V.depth_ray, in.depth, sizeof(float) * npix))
-            || (rc = ws.upload(V.normals, in.normals, sizeof(float) * 3 * npix))
-            || (rc = ws.upload(const_cast<uint8_t *>(P.image), in.image,
-                    npix * in.channels)))
-            return rc;
+        P.image = s.images[i];
+        off += (size_t)V.w * V.h;
     }
-    MeshViewDev *d_table = reinterpret_cast<MeshViewDev *>(slab + table_at);
     PointViewDev *d_ptable = reinterpret_cast<PointViewDev *>(slab + ptable_at);
-    if ((rc = ws.upload(d_table, table.data(), sizeof(MeshViewDev) * n_views))
-        || (rc = ws.upload(d_ptable, ptable.data(), sizeof(PointViewDev) * n_views)))
-        return rc;
-    if ((rc = launch_prepare_and_cut(stream, d_table, table, opt.cut)))
+    if ((rc = ws.upload(d_ptable, ptable.data(), sizeof(PointViewDev) * n_views)))
         return rc;
 
     PointBufs B;
@@ -1168,7 +731,7 @@ export_views(int device, const smvs_point_view *views, int n_views,
     clip.lo = make_float3(opt.aabb_min[0], opt.aabb_min[1], opt.aabb_min[2]);
     clip.hi = make_float3(opt.aabb_max[0], opt.aabb_max[1], opt.aabb_max[2]);
 
-    dim3 const grid((unsigned)((max_pix + 255) / 256), (unsigned)n_views);
+    dim3 const grid((unsigned)((s.max_pix + 255) / 256), (unsigned)n_views);
     hipLaunchKernelGGL(points_code_kernel, grid, dim3(256), 0, stream, d_table, d_ptable, B);
     hipLaunchKernelGGL(points_count_kernel, grid, dim3(256), 0, stream, d_ptable, B);
     SMVS_HIP_CHECK(hipGetLastError());
@@ -1188,22 +751,16 @@ export_views(int device, const smvs_point_view *views, int n_views,
             d_ptable, B, 1);
     SMVS_HIP_CHECK(hipGetLastError());
     unsigned long long sums = 0;
-    if ((rc = ws.download(&sums, B.tiles + n_tiles, sizeof(sums))))
+    if ((rc = ws.download(&sums, scan_total(B.tiles, N), sizeof(sums))))
         return rc;
     size_t n_vert = (size_t)(sums & 0xffffffffull);
     size_t n_face = (size_t)(sums >> 32);
     PointBufs O = B;
     if (opt.use_aabb && n_vert > 0) {
-        unsigned const blocks = (unsigned)((n_vert + 255) / 256);
-        hipLaunchKernelGGL(points_keep_kernel, dim3(blocks), dim3(256), 0, stream,
-            B.xyz, n_vert, clip.lo, clip.hi, B.scan);
-        SMVS_HIP_CHECK(hipGetLastError());
-        if ((rc = exclusive_scan(stream, B.scan, n_vert, B.tiles)))
-            return rc;
         outputs(O, 1);
-        hipLaunchKernelGGL(points_compact_kernel, dim3(blocks), dim3(256), 0, stream,
-            n_vert, clip.lo, clip.hi, B.scan, B, O);
-        SMVS_HIP_CHECK(hipGetLastError());
+        if ((rc = launch_aabb_clip(stream, n_vert, clip.lo, clip.hi, vertex_attrs(B),
+                vertex_attrs(O), B.scan, B.tiles)))
+            return rc;
         if (clip_faces) {
             unsigned long long *const fscan =
                 reinterpret_cast<unsigned long long *>(slab + fscan_at);
@@ -1217,42 +774,24 @@ export_views(int device, const smvs_point_view *views, int n_views,
             hipLaunchKernelGGL(mesh_face_scatter_kernel, grid, dim3(256), 0, stream,
                 d_ptable, B, clip, fscan, B.scan, faces);
             SMVS_HIP_CHECK(hipGetLastError());
-            if ((rc = ws.download(&sums, ftiles + n_tiles, sizeof(sums))))
+            if ((rc = ws.download(&sums, scan_total(ftiles, N), sizeof(sums))))
                 return rc;
             n_face = (size_t)sums;
         }
-        if ((rc = ws.download(&sums, B.tiles + (n_vert + SCAN_TILE - 1) / SCAN_TILE,
-                sizeof(sums))))
+        if ((rc = ws.download(&sums, scan_total(B.tiles, n_vert), sizeof(sums))))
             return rc;
         n_vert = (size_t)sums;
     }
     for (int i = 0; i < n_views; ++i)
         if (views[i].cut_depth != nullptr
             && (rc = ws.download(views[i].cut_depth, ptable[i].dm,
-                    sizeof(float) * table[i].w * table[i].h)))
+                    sizeof(float) * s.table[i].w * s.table[i].h)))
             return rc;
-    smvs_points *h = new smvs_points;
-    h->mesh = opt.mesh;
-    h->n_points = (int64_t)n_vert;
-    h->n_faces = faces_out ? (int64_t)n_face : 0;
-    h->xyz.resize(3 * n_vert);
-    h->nrm.resize(3 * n_vert);
-    h->rgb.resize(3 * n_vert);
-    h->conf.resize(n_vert);
-    h->val.resize(opt.mesh ? 0 : n_vert);
-    h->faces.resize(3 * (size_t)h->n_faces);
-    if ((rc = ws.download(h->xyz.data(), O.xyz, 12 * n_vert))
-        || (rc = ws.download(h->nrm.data(), O.nrm, 12 * n_vert))
-        || (rc = ws.download(h->rgb.data(), O.rgb, 3 * n_vert))
-        || (rc = ws.download(h->conf.data(), O.conf, 4 * n_vert))
-        || (rc = ws.download(h->val.data(), O.val, 4 * h->val.size()))
-        || (rc = ws.download(h->faces.data(), faces, 12 * (size_t)h->n_faces))) {
-        delete h;
+    if ((rc = fill_points(ws, opt.mesh, false, n_vert, n_face, vertex_attrs(O), faces, nullptr,
+            handle)))
         return rc;
-    }
-    *handle = h;
     if (n_points != nullptr)
-        *n_points = h->n_points;
+        *n_points = (*handle)->n_points;
     return SMVS_OK;
 }
 
@@ -1302,40 +841,3 @@ smvs_mesh_generate(int device, const smvs_point_view *views, int n_views,
     return rc;
 }
 
-extern "C" int
-smvs_points_info(const smvs_points *handle, int64_t *n_points, int64_t *n_faces)
-{
-    SMVS_REQUIRE(handle != nullptr, "no handle");
-    if (n_points != nullptr)
-        *n_points = handle->n_points;
-    if (n_faces != nullptr)
-        *n_faces = handle->n_faces;
-    return SMVS_OK;
-}
-
-extern "C" int
-smvs_points_download(const smvs_points *handle, float *xyz, float *normals,
-    uint8_t *rgb, float *confidence, float *value, uint32_t *faces)
-{
-    SMVS_REQUIRE(handle != nullptr, "no handle");
-    SMVS_REQUIRE(!(handle->mesh && value != nullptr),
-        "a triangle mesh has no values");
-    auto copy = [](void *dst, auto const &src) {
-        if (dst != nullptr && !src.empty())
-            memcpy(dst, src.data(), src.size() * sizeof(src[0]));
-    };
-    copy(xyz, handle->xyz);
-    copy(normals, handle->nrm);
-    copy(rgb, handle->rgb);
-    copy(confidence, handle->conf);
-    copy(value, handle->val);
-    copy(faces, handle->faces);
-    return SMVS_OK;
-}
-
-extern "C" int
-smvs_points_release(smvs_points *handle)
-{
-    delete handle;
-    return SMVS_OK;
-}

@@ -1,11 +1,10 @@
-// Pieces of mesh.hip that simplify.hip and tsdf.hip use as well: the per-view camera record
-// with the cut's prepare / cut launches, the 64-bit exclusive scan, the AABB
-// test, recalc_normals' face term and the result handle.
+// Device side of what the export paths share (mesh_cut.hip, mesh.hip,
+// simplify.hip, the tsdf sources, export_common.hip): the per-view camera
+// record, world_point, the AABB test and recalc_normals' face term.  The host
+// side (view stage, scan, clip, result fill) is export_shared.h.
 #pragma once
 
 #include "common.h"
-
-#include <vector>
 
 namespace smvs_hip {
 
@@ -107,26 +106,4 @@ face_term(const float (*q)[3], int k, float *fn, float *weight)
     return true;
 }
 
-// mesh.hip
-void fill_view_camera(int width, int height, float flen, const float *rot,
-    const float *trans, MeshViewDev &V);
-int launch_prepare_and_cut(hipStream_t stream, const MeshViewDev *d_table,
-    std::vector<MeshViewDev> const &table, bool cut);
-// exclusive scan of n 64-bit values in place; tiles: (n + SCAN_TILE - 1) /
-// SCAN_TILE + 1 words, the grand total behind the last tile
-constexpr int SCAN_ITEMS = 16, SCAN_TILE = 256 * SCAN_ITEMS;
-int exclusive_scan(hipStream_t stream, unsigned long long *a, size_t n,
-    unsigned long long *tiles);
-
 } // namespace smvs_hip
-
-struct smvs_points {
-    bool mesh = false;   // smvs_mesh_generate: no values, faces always
-    int64_t n_points = 0, n_faces = 0;
-    std::vector<float> xyz, nrm, conf, val;
-    std::vector<uint8_t> rgb;
-    std::vector<uint32_t> faces;
-    bool sparse = false;          // smvs_tsdf_fuse_sparse: cells per vertex
-    std::vector<int64_t> cells;
-};
-

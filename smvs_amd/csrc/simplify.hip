@@ -1,7 +1,8 @@
 // smvsrecon --simplify on gfx950:
 // DepthTriangulator::approximate_triangulation (lib/depth_triangulator.cc:27-305)
 // over Delaunay2D (lib/delaunay_2d.cc, lib/quad_edge.h) for every view, then the
-// export of mesh.hip's entries on the irregular meshes.
+// export of mesh.hip's entries on the irregular meshes.  The view stage, the
+// vertex clip and the result fill are the shared ones of export_shared.h.
 //
 //   greedy   one persistent workgroup per view runs the whole insertion loop:
 //            selection (all lanes: max key, earliest scan stamp), the Delaunay
@@ -20,6 +21,7 @@
 // subdivision has an iteration cap; hitting one ends the view with a status the
 // entry returns.
 #include "common.h"
+#include "export_shared.h"
 #include "mesh_shared.h"
 
 #include <algorithm>
@@ -1125,34 +1127,8 @@ simplify_attrs_kernel(const MeshViewDev *__restrict__ cams, const SimpView *__re
     }
 }
 
-// ------------------------------------------------------------------ AABB clip
-__global__ void __launch_bounds__(256)
-simplify_keep_kernel(const float *__restrict__ xyz, size_t n, float3 lo, float3 hi,
-    unsigned long long *__restrict__ keep)
-{
-    size_t const i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        keep[i] = outside_aabb(xyz + 3 * i, lo, hi) ? 0ull : 1ull;
-}
-
-__global__ void __launch_bounds__(256)
-simplify_compact_kernel(size_t n, float3 lo, float3 hi,
-    const unsigned long long *__restrict__ at, SimpOut src, SimpOut dst)
-{
-    size_t const i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || outside_aabb(src.xyz + 3 * i, lo, hi))
-        return;
-    size_t const j = at[i];
-    for (int r = 0; r < 3; ++r) {
-        dst.xyz[3 * j + r] = src.xyz[3 * i + r];
-        dst.nrm[3 * j + r] = src.nrm[3 * i + r];
-        dst.rgb[3 * j + r] = src.rgb[3 * i + r];
-    }
-    dst.conf[j] = src.conf[i];
-    if (dst.val != nullptr)
-        dst.val[j] = src.val[i];
-}
-
+// ----------------------------------------------- AABB clip: the face passes
+// (the vertex passes are export_common.hip's launch_aabb_clip)
 __global__ void __launch_bounds__(256)
 simplify_face_keep_kernel(const uint32_t *__restrict__ faces, size_t m,
     const float *__restrict__ xyz, float3 lo, float3 hi, unsigned long long *__restrict__ keep)
@@ -1187,16 +1163,6 @@ simplify_face_scatter_kernel(const uint32_t *__restrict__ faces, size_t m,
 using namespace smvs_hip;
 
 namespace {
-
-struct Carver {
-    size_t total = 0;
-    size_t operator()(size_t bytes)
-    {
-        size_t const at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    }
-};
 
 // the arena of one view, carved from the slab
 struct ArenaPlan {
@@ -1402,48 +1368,28 @@ smvs_simplified_generate(int device, const smvs_point_view *views, int n_views,
         return SMVS_ERR_HIP;
     Workspace &ws = *lease.w;
     Carver carve;
-    std::vector<size_t> offsets((size_t)n_views * 5);
+    ViewSlab s;
+    carve_views(views, n_views, true, carve, s);
     std::vector<ArenaPlan> plans(n_views);
-    for (int i = 0; i < n_views; ++i) {
-        size_t const npix = (size_t)views[i].width * views[i].height;
-        offsets[5 * i + 0] = carve(4 * npix);       // depth_z
-        offsets[5 * i + 1] = carve(4 * npix);       // depth_ray
-        offsets[5 * i + 2] = carve(4 * npix);       // cut
-        offsets[5 * i + 3] = carve(12 * npix);      // normals
-        offsets[5 * i + 4] = carve(npix * views[i].channels);
+    for (int i = 0; i < n_views; ++i)
         plan_arena(carve, stable[i], plans[i]);
-    }
-    size_t const cams_at = carve(sizeof(MeshViewDev) * n_views);
     size_t const table_at = carve(sizeof(SimpView) * n_views);
     char *slab = nullptr;
     if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
         return rc;
     hipStream_t const stream = ws.stream;
-    std::vector<MeshViewDev> cams(n_views);
+    if ((rc = upload_and_prepare(ws, slab, views, n_views, cut, true, s)))
+        return rc;
+    MeshViewDev *const d_cams = s.d_table;
     for (int i = 0; i < n_views; ++i) {
-        smvs_point_view const &in = views[i];
-        MeshViewDev &C = cams[i];
-        fill_view_camera(in.width, in.height, in.flen, in.rot, in.trans, C);
-        size_t const npix = (size_t)in.width * in.height;
-        C.depth_z = reinterpret_cast<float *>(slab + offsets[5 * i + 0]);
-        C.depth_ray = reinterpret_cast<float *>(slab + offsets[5 * i + 1]);
-        C.cut = reinterpret_cast<float *>(slab + offsets[5 * i + 2]);
-        C.normals = reinterpret_cast<float *>(slab + offsets[5 * i + 3]);
         SimpView &V = stable[i];
         bind_arena(slab, plans[i], V);
         // generate_mesh triangulates the cut maps, or the depth maps (:211-213)
-        V.dm = cut ? C.cut : C.depth_ray;
-        V.image = reinterpret_cast<uint8_t *>(slab + offsets[5 * i + 4]);
-        if ((rc = ws.upload(C.depth_ray, in.depth, 4 * npix))
-            || (rc = ws.upload(C.normals, in.normals, 12 * npix))
-            || (rc = ws.upload(const_cast<uint8_t *>(V.image), in.image, npix * in.channels)))
-            return rc;
+        V.dm = cut ? s.table[i].cut : s.table[i].depth_ray;
+        V.image = s.images[i];
     }
-    MeshViewDev *d_cams = reinterpret_cast<MeshViewDev *>(slab + cams_at);
     SimpView *d_table = reinterpret_cast<SimpView *>(slab + table_at);
-    if ((rc = ws.upload(d_cams, cams.data(), sizeof(MeshViewDev) * n_views))
-        || (rc = ws.upload(d_table, stable.data(), sizeof(SimpView) * n_views))
-        || (rc = launch_prepare_and_cut(stream, d_cams, cams, cut)))
+    if ((rc = ws.upload(d_table, stable.data(), sizeof(SimpView) * n_views)))
         return rc;
     hipLaunchKernelGGL(simplify_greedy_kernel<false>, dim3(n_views), dim3(SIMP_THREADS), 0,
         stream, d_table);
@@ -1507,16 +1453,10 @@ smvs_simplified_generate(int device, const smvs_point_view *views, int n_views,
         unsigned long long *const fscan = reinterpret_cast<unsigned long long *>(outs + fscan_at);
         unsigned long long *const tiles = reinterpret_cast<unsigned long long *>(outs + tiles_at);
         unsigned long long *const ftiles = reinterpret_cast<unsigned long long *>(outs + ftiles_at);
-        unsigned const blocks = (unsigned)((n_vert + 255) / 256);
-        hipLaunchKernelGGL(simplify_keep_kernel, dim3(blocks), dim3(256), 0, stream, A.xyz,
-            n_vert, A.lo, A.hi, vscan);
-        SMVS_HIP_CHECK(hipGetLastError());
-        if ((rc = exclusive_scan(stream, vscan, n_vert, tiles)))
-            return rc;
         outputs(O, 1);
-        hipLaunchKernelGGL(simplify_compact_kernel, dim3(blocks), dim3(256), 0, stream, n_vert,
-            A.lo, A.hi, vscan, A, O);
-        SMVS_HIP_CHECK(hipGetLastError());
+        if ((rc = launch_aabb_clip(stream, n_vert, A.lo, A.hi, vertex_attrs(A), vertex_attrs(O),
+                vscan, tiles)))
+            return rc;
         unsigned long long sum = 0;
         if (mesh && n_face > 0) {
             unsigned const fblocks = (unsigned)((n_face + 255) / 256);
@@ -1528,12 +1468,11 @@ smvs_simplified_generate(int device, const smvs_point_view *views, int n_views,
             hipLaunchKernelGGL(simplify_face_scatter_kernel, dim3(fblocks), dim3(256), 0, stream,
                 A.faces, n_face, A.xyz, A.lo, A.hi, fscan, vscan, O.faces);
             SMVS_HIP_CHECK(hipGetLastError());
-            if ((rc = ws.download(&sum, ftiles + (n_face + SCAN_TILE - 1) / SCAN_TILE,
-                    sizeof(sum))))
+            if ((rc = ws.download(&sum, scan_total(ftiles, n_face), sizeof(sum))))
                 return rc;
             n_face = (size_t)sum;
         }
-        if ((rc = ws.download(&sum, tiles + (n_vert + SCAN_TILE - 1) / SCAN_TILE, sizeof(sum))))
+        if ((rc = ws.download(&sum, scan_total(tiles, n_vert), sizeof(sum))))
             return rc;
         n_vert = (size_t)sum;
     }
@@ -1542,29 +1481,12 @@ smvs_simplified_generate(int device, const smvs_point_view *views, int n_views,
             && (rc = ws.download(views[i].cut_depth, stable[i].dm,
                     4 * (size_t)views[i].width * views[i].height)))
             return rc;
-    smvs_points *h = new smvs_points;
-    h->mesh = mesh;
-    h->n_points = (int64_t)n_vert;
-    h->n_faces = faces_out ? (int64_t)n_face : 0;
-    h->xyz.resize(3 * n_vert);
-    h->nrm.resize(3 * n_vert);
-    h->rgb.resize(3 * n_vert);
-    h->conf.resize(n_vert);
-    h->val.resize(mesh ? 0 : n_vert);
-    h->faces.resize(3 * (size_t)h->n_faces);
-    if ((rc = ws.download(h->xyz.data(), O.xyz, 12 * n_vert))
-        || (rc = ws.download(h->nrm.data(), O.nrm, 12 * n_vert))
-        || (rc = ws.download(h->rgb.data(), O.rgb, 3 * n_vert))
-        || (rc = ws.download(h->conf.data(), O.conf, 4 * n_vert))
-        || (rc = ws.download(h->val.data(), O.val, 4 * h->val.size()))
-        || (rc = ws.download(h->faces.data(), O.faces, 12 * (size_t)h->n_faces))) {
-        delete h;
+    if ((rc = fill_points(ws, mesh, false, n_vert, n_face, vertex_attrs(O),
+            faces_out ? O.faces : nullptr, nullptr, handle)))
         return rc;
-    }
-    *handle = h;
     if (n_vertices != nullptr)
-        *n_vertices = h->n_points;
+        *n_vertices = (*handle)->n_points;
     if (n_faces != nullptr)
-        *n_faces = h->n_faces;
+        *n_faces = (*handle)->n_faces;
     return SMVS_OK;
 }

@@ -52,7 +52,7 @@ surface_maps_kernel(MapArgs A)
             // mve::image::depthmap_convert_conventions, z-depth -> ray length
             // (`double len = px.norm(); dm *= len`, tests/golden/README.md M10;
             // the float operations of host/stereo_view.cc, the inverse of
-            // mesh.hip's mesh_prepare_kernel)
+            // mesh_cut.hip's mesh_prepare_kernel)
             float const fx = (float)px + 0.5f, fy = (float)py + 0.5f;
             float v[3];
 #pragma unroll

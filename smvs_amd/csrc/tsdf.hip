@@ -4,16 +4,17 @@
 // in numpy by tests/tsdf_ref.py; every step below names the paragraph it
 // implements.
 //
-// The views are prepared exactly as the mesh export prepares them
-// (mesh_prepare_kernel, mesh_cut_kernel through launch_prepare_and_cut), then
+// The views are prepared exactly as the mesh export prepares them (the view
+// stage of mesh_cut.hip: carve_views / upload_and_prepare), then
 //   depth      per pixel: D = depth_z where the cut map is non-zero, else 0
 //   integrate  one lane per voxel walks the views in list order with the
 //              voxel's sums in registers; the volume is written once
 //   classify   per block of 256 grid points: active cells | quads << 32
-//   scan       mesh.hip's exclusive_scan over the blocks
+//   scan       export_common.hip's exclusive_scan over the blocks
 //   vertices   one surface-nets vertex per active cell, with its attributes,
 //              and the cell -> vertex id map
 //   faces      two triangles per quad through that map
+//   fill       export_common.hip's fill_points
 // Arithmetic: float, FMA contraction off, term by term as mesh.hip writes it.
 // No atomics: every order is an index order (vertex ids and face positions
 // come from the scan and a scan inside each block).
@@ -285,65 +286,17 @@ check_views(const smvs_point_view *views, int n_views, int cut, bool want_images
     return SMVS_OK;
 }
 
-void
-carve_views(const smvs_point_view *views, int n_views, bool want_images, Carver &carve,
-    ViewSlab &s)
-{
-    s.offsets.resize((size_t)n_views * 5);
-    for (int i = 0; i < n_views; ++i) {
-        size_t const npix = (size_t)views[i].width * views[i].height;
-        s.max_pix = npix > s.max_pix ? npix : s.max_pix;
-        s.offsets[5 * i + 0] = carve(sizeof(float) * npix);       // depth_z
-        s.offsets[5 * i + 1] = carve(sizeof(float) * npix);       // depth_ray
-        s.offsets[5 * i + 2] = carve(sizeof(float) * npix);       // cut
-        s.offsets[5 * i + 3] = carve(sizeof(float) * 3 * npix);   // normals
-        s.offsets[5 * i + 4] = want_images ? carve(npix * views[i].channels) : 0;
-    }
-    s.table_at = carve(sizeof(MeshViewDev) * n_views);
-    s.images_at = carve(sizeof(TsdfImageDev) * n_views);
-}
-
-// uploads the views and runs the mesh path's preparation (and cut)
 int
-upload_and_prepare(Workspace &ws, char *slab, const smvs_point_view *views, int n_views,
-    bool cut, bool want_images, ViewSlab &s)
+upload_image_table(Workspace &ws, char *slab, size_t at, const smvs_point_view *views,
+    ViewSlab const &s, TsdfImageDev **d_images)
 {
-    int rc;
-    s.table.resize(n_views);
-    s.images.resize(n_views);
-    for (int i = 0; i < n_views; ++i) {
-        smvs_point_view const &in = views[i];
-        MeshViewDev &V = s.table[i];
-        fill_view_camera(in.width, in.height, in.flen, in.rot, in.trans, V);
-        size_t const npix = (size_t)in.width * in.height;
-        V.depth_z = reinterpret_cast<float *>(slab + s.offsets[5 * i + 0]);
-        V.depth_ray = reinterpret_cast<float *>(slab + s.offsets[5 * i + 1]);
-        V.cut = reinterpret_cast<float *>(slab + s.offsets[5 * i + 2]);
-        V.normals = reinterpret_cast<float *>(slab + s.offsets[5 * i + 3]);
-        if ((rc = ws.upload(V.depth_ray, in.depth, sizeof(float) * npix)))
-            return rc;
-        // without normals (cut off only) the preparation turns zeros
-        if (in.normals != nullptr) {
-            if ((rc = ws.upload(V.normals, in.normals, sizeof(float) * 3 * npix)))
-                return rc;
-        } else
-            SMVS_HIP_CHECK(hipMemsetAsync(V.normals, 0, sizeof(float) * 3 * npix,
-                ws.stream));
-        s.images[i].image = nullptr;
-        s.images[i].channels = in.channels;
-        if (want_images) {
-            uint8_t *img = reinterpret_cast<uint8_t *>(slab + s.offsets[5 * i + 4]);
-            s.images[i].image = img;
-            if ((rc = ws.upload(img, in.image, npix * in.channels)))
-                return rc;
-        }
+    std::vector<TsdfImageDev> images(s.images.size());
+    for (size_t i = 0; i < images.size(); ++i) {
+        images[i].image = s.images[i];
+        images[i].channels = views[i].channels;
     }
-    s.d_table = reinterpret_cast<MeshViewDev *>(slab + s.table_at);
-    s.d_images = reinterpret_cast<TsdfImageDev *>(slab + s.images_at);
-    if ((rc = ws.upload(s.d_table, s.table.data(), sizeof(MeshViewDev) * n_views))
-        || (rc = ws.upload(s.d_images, s.images.data(), sizeof(TsdfImageDev) * n_views)))
-        return rc;
-    return launch_prepare_and_cut(ws.stream, s.d_table, s.table, cut);
+    *d_images = reinterpret_cast<TsdfImageDev *>(slab + at);
+    return ws.upload(*d_images, images.data(), sizeof(TsdfImageDev) * images.size());
 }
 
 int
@@ -462,6 +415,7 @@ smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
     Carver carve;
     ViewSlab s;
     carve_views(views, n_views, true, carve, s);
+    size_t const images_at = carve(sizeof(TsdfImageDev) * n_views);
     unsigned const point_blocks = (unsigned)((n_vox + 255) / 256);
     size_t const scan_tiles = ((size_t)point_blocks + SCAN_TILE - 1) / SCAN_TILE;
     size_t const tsdf_at = carve(4 * n_vox), weight_at = carve(4 * n_vox),
@@ -471,7 +425,9 @@ smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
     if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
         return rc;
     hipStream_t const stream = ws.stream;
-    if ((rc = upload_and_prepare(ws, slab, views, n_views, opt.cut_surfaces != 0, true, s)))
+    TsdfImageDev *d_images = nullptr;
+    if ((rc = upload_and_prepare(ws, slab, views, n_views, opt.cut_surfaces != 0, true, s))
+        || (rc = upload_image_table(ws, slab, images_at, views, s, &d_images)))
         return rc;
 
     float *d_tsdf = reinterpret_cast<float *>(slab + tsdf_at);
@@ -486,39 +442,27 @@ smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
         * (unsigned)((G.ny + TSDF_BY - 1) / TSDF_BY)
         * (unsigned)((G.nz + TSDF_BZ - 1) / TSDF_BZ);
     hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(bricks), dim3(256), 0, stream, s.d_table,
-        s.d_images, G, d_tsdf, d_weight, d_colour);
+        d_images, G, d_tsdf, d_weight, d_colour);
     hipLaunchKernelGGL(tsdf_classify_kernel, dim3(point_blocks), dim3(256), 0, stream, d_tsdf,
         G, d_counts);
     SMVS_HIP_CHECK(hipGetLastError());
     if ((rc = exclusive_scan(stream, d_counts, point_blocks, d_tiles)))
         return rc;
     unsigned long long sums = 0;
-    if ((rc = ws.download(&sums, d_tiles + scan_tiles, sizeof(sums))))
+    if ((rc = ws.download(&sums, scan_total(d_tiles, point_blocks), sizeof(sums))))
         return rc;
     size_t const n_vert = (size_t)(sums & 0xffffffffull);
     size_t const n_face = 2 * (size_t)(sums >> 32);
 
-    smvs_points *h = new smvs_points;
-    h->mesh = true;
-    h->n_points = (int64_t)n_vert;
-    h->n_faces = (int64_t)n_face;
-    h->xyz.resize(3 * n_vert);
-    h->nrm.resize(3 * n_vert);
-    h->rgb.resize(3 * n_vert);
-    h->conf.resize(n_vert);
-    h->faces.resize(3 * n_face);
-    auto fail = [&](int code) {
-        delete h;
-        return code;
-    };
+    // (no vertices: no second slab, no launches, an empty handle)
+    TsdfOut O = {};
     if (n_vert > 0) {
         Carver oc;
         size_t const xyz_at = oc(12 * n_vert), nrm_at = oc(12 * n_vert), conf_at = oc(4 * n_vert),
             rgb_at = oc(3 * n_vert), faces_at = oc(12 * n_face);
         char *outs = nullptr;
         if ((rc = ws.ensure(1, oc.total, &outs)) != SMVS_OK)
-            return fail(rc);
-        TsdfOut O;
+            return rc;
         O.xyz = reinterpret_cast<float *>(outs + xyz_at);
         O.nrm = reinterpret_cast<float *>(outs + nrm_at);
         O.conf = reinterpret_cast<float *>(outs + conf_at);
@@ -530,18 +474,18 @@ smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
             G, d_counts, d_vid, O);
         if (hipGetLastError() != hipSuccess) {
             set_error("smvs_tsdf_fuse: extraction launch failed");
-            return fail(SMVS_ERR_HIP);
+            return SMVS_ERR_HIP;
         }
-        if ((rc = ws.download(h->xyz.data(), O.xyz, 12 * n_vert))
-            || (rc = ws.download(h->nrm.data(), O.nrm, 12 * n_vert))
-            || (rc = ws.download(h->rgb.data(), O.rgb, 3 * n_vert))
-            || (rc = ws.download(h->conf.data(), O.conf, 4 * n_vert))
-            || (rc = ws.download(h->faces.data(), O.faces, 12 * n_face)))
-            return fail(rc);
     }
+    smvs_points *h = nullptr;
+    if ((rc = fill_points(ws, true, false, n_vert, n_face,
+            VertexAttrs{ O.xyz, O.nrm, O.rgb, O.conf, nullptr }, O.faces, nullptr, &h)))
+        return rc;
     if ((tsdf != nullptr && (rc = ws.download(tsdf, d_tsdf, 4 * n_vox)))
-        || (weight != nullptr && (rc = ws.download(weight, d_weight, 4 * n_vox))))
-        return fail(rc);
+        || (weight != nullptr && (rc = ws.download(weight, d_weight, 4 * n_vox)))) {
+        delete h;
+        return rc;
+    }
     *handle = h;
     if (n_vertices != nullptr)
         *n_vertices = h->n_points;

@@ -9,7 +9,7 @@
 //   pyramid top   one block per view: levels 6 .. 1 x 1 from level 5
 //   cull          one lane per brick, the views in a loop: a byte per brick and
 //                 the candidates per 256 bricks
-//   scan          mesh.hip's exclusive_scan over those counts
+//   scan          export_common.hip's exclusive_scan over those counts
 //   list          rank -> brick, in brick order
 //   seed (list)   tsdf_sparse_seed_kernel's body, one block per listed brick
 // Arithmetic: the pyramid is float min / max (exact); the test is double, FMA

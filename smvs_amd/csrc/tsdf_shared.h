@@ -3,12 +3,13 @@
 // in front of its seed pass) share: the grid record, the brick grid, the
 // per-element device functions of the definition in include/smvs_hip.h (voxel
 // centre, the projection steps 1-6, the cell / edge / quad rules, the block
-// scan, the vertex attribute arithmetic) and the host side's view upload.
+// scan, the vertex attribute arithmetic) and the host pieces of the entries.
 // The field functions take the field as (pointer, grid): tsdf.hip hands them
 // the volume, tsdf_sparse.hip a brick with its halo staged in LDS.
 #pragma once
 
 #include "common.h"
+#include "export_shared.h"
 #include "mesh_shared.h"
 
 #include <vector>
@@ -348,28 +349,10 @@ tsdf_quad_faces(const uint32_t *v, bool inside, uint32_t *out)
 }
 
 // ----------------------------------------------------------------------- host
-// tsdf.hip: the views' maps and tables in a workspace slab, as the mesh export
-// lays them out, uploaded and prepared (and cut)
+// tsdf.hip: what the entries share on top of the view stage (export_shared.h:
+// carve_views / upload_and_prepare lay the views' maps out, upload, prepare
+// and cut them as every export path does)
 namespace tsdf_host {
-
-struct Carver {
-    size_t total = 0;
-    size_t operator()(size_t bytes)
-    {
-        size_t const at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    }
-};
-
-struct ViewSlab {
-    std::vector<size_t> offsets;   // per view: depth_z, depth_ray, cut, normals, image
-    size_t table_at = 0, images_at = 0, max_pix = 0;
-    std::vector<MeshViewDev> table;
-    std::vector<TsdfImageDev> images;
-    MeshViewDev *d_table = nullptr;
-    TsdfImageDev *d_images = nullptr;
-};
 
 // argument checks shared by the entries (before any device call)
 int check_views(const smvs_point_view *views, int n_views, int cut, bool want_images);
@@ -377,12 +360,10 @@ int check_views(const smvs_point_view *views, int n_views, int cut, bool want_im
 // (`who` heads the error text)
 int check_grid(const char *who, const smvs_tsdf_options &opt, int n_views, int max_dim,
     TsdfGrid &G);
-// images only where the caller fuses
-void carve_views(const smvs_point_view *views, int n_views, bool want_images, Carver &carve,
-    ViewSlab &s);
-// uploads the views and runs the mesh path's preparation (and cut)
-int upload_and_prepare(Workspace &ws, char *slab, const smvs_point_view *views, int n_views,
-    bool cut, bool want_images, ViewSlab &s);
+// the fusing entries' colour table, n_views records at slab + at, from the
+// images the view stage uploaded
+int upload_image_table(Workspace &ws, char *slab, size_t at, const smvs_point_view *views,
+    ViewSlab const &s, TsdfImageDev **d_images);
 // D(p) = depth_z[p] where cut[p] != 0, else 0, in place in depth_z
 void launch_depth(hipStream_t stream, ViewSlab const &s, int n_views);
 

@@ -8,7 +8,7 @@
 //              test of step 8 until the first hit: one byte per brick (with
 //              the cull of tsdf_cull.hip, section 9.10: per candidate brick)
 //   dilate     per brick the OR over its 27 neighbours; counts per 256 bricks
-//   scan       mesh.hip's exclusive_scan over those counts
+//   scan       export_common.hip's exclusive_scan over those counts
 //   table      brick -> slot (or -1) and slot -> brick, in linear brick order
 //   integrate  one block per allocated brick, state slot-major (slot * 256 +
 //              the voxel's index in the brick)
@@ -384,6 +384,7 @@ smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views
     ViewSlab s;
     PyramidSlab pyr;
     carve_views(views, n_views, true, carve, s);
+    size_t const images_at = carve(sizeof(TsdfImageDev) * n_views);
     unsigned const brick_blocks = (unsigned)((n_bricks + 255) / 256);
     size_t const brick_tiles = ((size_t)brick_blocks + SCAN_TILE - 1) / SCAN_TILE;
     size_t const seed_at = carve(n_bricks), state_at = carve(n_bricks),
@@ -398,7 +399,9 @@ smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views
     if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
         return rc;
     hipStream_t const stream = ws.stream;
-    if ((rc = upload_and_prepare(ws, slab, views, n_views, opt.cut_surfaces != 0, true, s)))
+    TsdfImageDev *d_images = nullptr;
+    if ((rc = upload_and_prepare(ws, slab, views, n_views, opt.cut_surfaces != 0, true, s))
+        || (rc = upload_image_table(ws, slab, images_at, views, s, &d_images)))
         return rc;
     uint8_t *d_seed = reinterpret_cast<uint8_t *>(slab + seed_at);
     uint8_t *d_state = reinterpret_cast<uint8_t *>(slab + state_at);
@@ -463,18 +466,15 @@ smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views
         return SMVS_ERR_NOMEM;
     }
 
-    smvs_points *h = new smvs_points;
-    h->mesh = true;
-    h->sparse = true;
-    auto fail = [&](int code) {
-        delete h;
-        return code;
-    };
-    std::vector<uint32_t> host_list;
-    std::vector<float> host_f;
-    std::vector<uint32_t> host_w;
+    // (no allocated brick or no vertex: no further slab, no launches, an empty handle)
+    TsdfOut O = {};
+    long long *d_cells = nullptr;
+    size_t n_vert = 0, n_face = 0;
+    size_t const n_state = n_alloc * 256;
+    uint32_t *d_list = nullptr;
+    float *d_tsdf = nullptr;
+    uint32_t *d_weight = nullptr;
     if (n_alloc > 0) {
-        size_t const n_state = n_alloc * 256;
         size_t const scan_tiles = (n_alloc + SCAN_TILE - 1) / SCAN_TILE;
         Carver vc;
         size_t const list_at = vc(4 * n_alloc), f_at = vc(4 * n_state), w_at = vc(4 * n_state),
@@ -482,10 +482,10 @@ smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views
             tiles_at = vc(8 * (scan_tiles + 1));
         char *vol = nullptr;
         if ((rc = ws.ensure(2, vc.total, &vol)) != SMVS_OK)
-            return fail(rc);
-        uint32_t *d_list = reinterpret_cast<uint32_t *>(vol + list_at);
-        float *d_tsdf = reinterpret_cast<float *>(vol + f_at);
-        uint32_t *d_weight = reinterpret_cast<uint32_t *>(vol + w_at);
+            return rc;
+        d_list = reinterpret_cast<uint32_t *>(vol + list_at);
+        d_tsdf = reinterpret_cast<float *>(vol + f_at);
+        d_weight = reinterpret_cast<uint32_t *>(vol + w_at);
         uint4 *d_colour = reinterpret_cast<uint4 *>(vol + colour_at);
         uint32_t *d_vid = reinterpret_cast<uint32_t *>(vol + vid_at);
         unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(vol + counts_at);
@@ -495,27 +495,19 @@ smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views
         hipLaunchKernelGGL(tsdf_sparse_table_kernel, dim3(brick_blocks), dim3(256), 0, stream,
             d_state, B, d_bcounts, d_table, d_list);
         hipLaunchKernelGGL(tsdf_sparse_integrate_kernel, dim3(slots), dim3(256), 0, stream,
-            s.d_table, s.d_images, G, B, d_list, d_tsdf, d_weight, d_colour);
+            s.d_table, d_images, G, B, d_list, d_tsdf, d_weight, d_colour);
         hipLaunchKernelGGL(tsdf_sparse_classify_kernel, dim3(slots), dim3(256), 0, stream,
             d_tsdf, d_table, d_list, G, B, d_counts);
         if (hipGetLastError() != hipSuccess) {
             set_error("smvs_tsdf_fuse_sparse: integration launch failed");
-            return fail(SMVS_ERR_HIP);
+            return SMVS_ERR_HIP;
         }
         if ((rc = exclusive_scan(stream, d_counts, n_alloc, d_tiles)))
-            return fail(rc);
-        if ((rc = ws.download(&sums, d_tiles + scan_tiles, sizeof(sums))))
-            return fail(rc);
-        size_t const n_vert = (size_t)(sums & 0xffffffffull);
-        size_t const n_face = 2 * (size_t)(sums >> 32);
-        h->n_points = (int64_t)n_vert;
-        h->n_faces = (int64_t)n_face;
-        h->xyz.resize(3 * n_vert);
-        h->nrm.resize(3 * n_vert);
-        h->rgb.resize(3 * n_vert);
-        h->conf.resize(n_vert);
-        h->cells.resize(n_vert);
-        h->faces.resize(3 * n_face);
+            return rc;
+        if ((rc = ws.download(&sums, scan_total(d_tiles, n_alloc), sizeof(sums))))
+            return rc;
+        n_vert = (size_t)(sums & 0xffffffffull);
+        n_face = 2 * (size_t)(sums >> 32);
         if (n_vert > 0) {
             Carver oc;
             size_t const xyz_at = oc(12 * n_vert), nrm_at = oc(12 * n_vert),
@@ -523,44 +515,47 @@ smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views
                 cells_at = oc(8 * n_vert);
             char *outs = nullptr;
             if ((rc = ws.ensure(1, oc.total, &outs)) != SMVS_OK)
-                return fail(rc);
-            TsdfOut O;
+                return rc;
             O.xyz = reinterpret_cast<float *>(outs + xyz_at);
             O.nrm = reinterpret_cast<float *>(outs + nrm_at);
             O.conf = reinterpret_cast<float *>(outs + conf_at);
             O.rgb = reinterpret_cast<uint8_t *>(outs + rgb_at);
             O.faces = reinterpret_cast<uint32_t *>(outs + faces_at);
-            long long *d_cells = reinterpret_cast<long long *>(outs + cells_at);
+            d_cells = reinterpret_cast<long long *>(outs + cells_at);
             hipLaunchKernelGGL(tsdf_sparse_vertex_kernel, dim3(slots), dim3(256), 0, stream,
                 d_tsdf, d_weight, d_colour, d_table, d_list, G, B, d_counts, d_vid, O, d_cells);
             hipLaunchKernelGGL(tsdf_sparse_face_kernel, dim3(slots), dim3(256), 0, stream,
                 d_tsdf, d_table, d_list, G, B, d_counts, d_vid, O);
             if (hipGetLastError() != hipSuccess) {
                 set_error("smvs_tsdf_fuse_sparse: extraction launch failed");
-                return fail(SMVS_ERR_HIP);
+                return SMVS_ERR_HIP;
             }
-            if ((rc = ws.download(h->xyz.data(), O.xyz, 12 * n_vert))
-                || (rc = ws.download(h->nrm.data(), O.nrm, 12 * n_vert))
-                || (rc = ws.download(h->rgb.data(), O.rgb, 3 * n_vert))
-                || (rc = ws.download(h->conf.data(), O.conf, 4 * n_vert))
-                || (rc = ws.download(h->cells.data(), d_cells, 8 * n_vert))
-                || (rc = ws.download(h->faces.data(), O.faces, 12 * n_face)))
+        }
+    }
+    smvs_points *h = nullptr;
+    if ((rc = fill_points(ws, true, true, n_vert, n_face,
+            VertexAttrs{ O.xyz, O.nrm, O.rgb, O.conf, nullptr }, O.faces, d_cells, &h)))
+        return rc;
+    auto fail = [&](int code) {
+        delete h;
+        return code;
+    };
+    std::vector<uint32_t> host_list;
+    std::vector<float> host_f;
+    std::vector<uint32_t> host_w;
+    if (n_alloc > 0 && (tsdf != nullptr || weight != nullptr)) {
+        host_list.resize(n_alloc);
+        if ((rc = ws.download(host_list.data(), d_list, 4 * n_alloc)))
+            return fail(rc);
+        if (tsdf != nullptr) {
+            host_f.resize(n_state);
+            if ((rc = ws.download(host_f.data(), d_tsdf, 4 * n_state)))
                 return fail(rc);
         }
-        if (tsdf != nullptr || weight != nullptr) {
-            host_list.resize(n_alloc);
-            if ((rc = ws.download(host_list.data(), d_list, 4 * n_alloc)))
+        if (weight != nullptr) {
+            host_w.resize(n_state);
+            if ((rc = ws.download(host_w.data(), d_weight, 4 * n_state)))
                 return fail(rc);
-            if (tsdf != nullptr) {
-                host_f.resize(n_state);
-                if ((rc = ws.download(host_f.data(), d_tsdf, 4 * n_state)))
-                    return fail(rc);
-            }
-            if (weight != nullptr) {
-                host_w.resize(n_state);
-                if ((rc = ws.download(host_w.data(), d_weight, 4 * n_state)))
-                    return fail(rc);
-            }
         }
     }
     // the whole grid from the slot-major state: NaN / 0 where not allocated

@@ -1,4 +1,4 @@
-"""View sets on which every branch of the cross-view cut (csrc/mesh.hip:
+"""View sets on which every branch of the cross-view cut (csrc/mesh_cut.hip:
 mesh_prepare_kernel, mesh_cut_kernel) decides -- plain numpy, no GPU; walked
 by test_cut_cases_cpu.py (the restatement tests/cut_ref.py against the oracle,
 and the tallies that make the cases non-vacuous) and by test_gpu_cut_cases.py

@@ -113,6 +113,21 @@ def test_mesh_aabb_cuts_faces_in_every_view(hip, oracle, cut, channels):
     assert np.any(np.all(got["normals"] == 0, axis=1))
 
 
+def test_mesh_box_around_everything_changes_nothing(hip):
+    """The shared AABB clip with a box that holds every vertex (the unclipped
+    min / max, one float step outward): bit for bit the unclipped mesh."""
+    _, cams, depths, normals, images = _inputs(3, 128, 96, 3, seed=8)
+    full = hip.generate_mesh(cams, depths, normals, images, cut=True)
+    assert len(full["xyz"]) > 4096          # more than one scan tile
+    lo = np.nextafter(full["xyz"].min(axis=0), np.float32(-np.inf))
+    hi = np.nextafter(full["xyz"].max(axis=0), np.float32(np.inf))
+    got = hip.generate_mesh(cams, depths, normals, images, cut=True, aabb=(lo, hi))
+    assert sorted(got) == sorted(full)
+    for k in ("xyz", "normals", "rgb", "confidence", "faces"):
+        assert got[k].dtype == full[k].dtype and got[k].shape == full[k].shape, k
+        assert got[k].tobytes() == full[k].tobytes(), k
+
+
 def test_mesh_full_size_nine_views(hip, oracle):
     _, cams, depths, normals, images = _inputs(9, 1920, 1080, 3, seed=11)
     got = hip.generate_mesh(cams, depths, normals, images, cut=True)

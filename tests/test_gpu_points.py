@@ -85,6 +85,40 @@ def test_points_aabb_clip(hip, oracle, cut):
     assert 0 < len(got["xyz"]) < len(full["xyz"])
 
 
+def _same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def test_points_box_around_everything_changes_nothing(hip):
+    """The shared AABB clip with a box that holds every vertex (the unclipped
+    min / max, one float step outward): bit for bit the unclipped cloud."""
+    _, cams, depths, normals, images = _inputs(3, 128, 96, 3, seed=8)
+    full = hip.generate_points(cams, depths, normals, images, cut=True)
+    assert len(full["xyz"]) > 4096          # more than one scan tile
+    lo = np.nextafter(full["xyz"].min(axis=0), np.float32(-np.inf))
+    hi = np.nextafter(full["xyz"].max(axis=0), np.float32(np.inf))
+    got = hip.generate_points(cams, depths, normals, images, cut=True, aabb=(lo, hi))
+    for k in KEYS:
+        assert _same_bits(got[k], full[k]), k
+
+
+def test_points_aabb_clip_keeps_the_merged_order(hip):
+    """The clipped cloud is the unclipped one filtered by the inclusive box
+    test, in the unclipped order, across the scan's 4096-element tiles."""
+    _, cams, depths, normals, images = _inputs(3, 128, 96, 3, seed=8)
+    aabb = ((-0.6, -0.5, 0.0), (0.7, 0.6, 4.5))
+    full = hip.generate_points(cams, depths, normals, images, cut=True)
+    got = hip.generate_points(cams, depths, normals, images, cut=True, aabb=aabb)
+    lo, hi = np.float32(aabb[0]), np.float32(aabb[1])
+    keep = ~((full["xyz"] < lo) | (full["xyz"] > hi)).any(axis=1)
+    assert len(full["xyz"]) > 2 * 4096 and 0 < keep.sum() < len(keep)
+    # kept and dropped vertices in more than one tile each
+    tiles = np.arange(len(keep)) // 4096
+    assert len(np.unique(tiles[keep])) > 1 and len(np.unique(tiles[~keep])) > 1
+    for k in KEYS:
+        assert _same_bits(got[k], full[k][keep]), k
+
+
 def test_points_full_size_nine_views(hip, oracle):
     scene, cams, depths, normals, images = _inputs(9, 1920, 1080, 3, seed=11)
     got = hip.generate_points(cams, depths, normals, images, cut=True, faces=True)

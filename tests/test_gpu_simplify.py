@@ -188,6 +188,24 @@ def test_export_with_aabb_and_bounds(hip, oracle, mesh):
     _assert_same_export(got, want, mesh, "bounds-mesh%d" % mesh)
 
 
+@pytest.mark.parametrize("mesh", [False, True])
+def test_export_box_around_everything_changes_nothing(hip, mesh):
+    """The shared AABB clip with a box that holds every vertex (the unclipped
+    min / max, one float step outward): bit for bit the unclipped export; the
+    point cloud's faces are not returned together with a box."""
+    cams, depths, normals, images = _inputs(3, 128, 96, 3)
+    full = hip.generate_simplified(cams, depths, normals, images, mesh=mesh)
+    lo = np.nextafter(full["xyz"].min(axis=0), np.float32(-np.inf))
+    hi = np.nextafter(full["xyz"].max(axis=0), np.float32(np.inf))
+    got = hip.generate_simplified(cams, depths, normals, images, mesh=mesh, aabb=(lo, hi))
+    keys = ["xyz", "normals", "rgb", "confidence"] + (["faces"] if mesh else ["value"])
+    assert sorted(got) == sorted(keys)
+    assert len(got["xyz"]) > 0
+    for k in keys:
+        assert got[k].dtype == full[k].dtype and got[k].shape == full[k].shape, k
+        assert got[k].tobytes() == full[k].tobytes(), k
+
+
 def test_view_without_valid_depth_contributes_nothing(hip, oracle):
     cams, depths, normals, images = _inputs(3, 97, 63, 3)
     depths[1][:] = 0.0

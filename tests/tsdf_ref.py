@@ -17,7 +17,7 @@ EDGES = [(0, 1, 0), (2, 3, 0), (4, 5, 0), (6, 7, 0),
 
 
 def camera(cam, w, h):
-    """fill_view_camera of csrc/mesh.hip: invproj, KR, t, rot, c2w_t (float32,
+    """fill_view_camera of csrc/mesh_cut.hip: invproj, KR, t, rot, c2w_t (float32,
     its summation order)."""
     flen, fw, fh = f32(cam.flen), f32(w), f32(h)
     ax = flen * max(fw, fh)
