@@ -1508,6 +1508,90 @@ int smvs_tsdf_depth_pyramid(int device, const smvs_point_view *views, int n_view
 int smvs_tsdf_bounds(int device, const smvs_point_view *views, int n_views,
     int cut_surfaces, float *lo, float *hi);
 
+/* Cleaning a triangle mesh (not in the reference, whose documented pipeline
+ * ends with MVE's `meshclean -p10`; opt-in): a cut on
+ * the vertex confidences, then the removal of small connected components and
+ * of vertices no face uses.  MVE is not part of this project: the definition
+ * is this comment, tests/mesh_clean_ref.py restates it in numpy, and the device
+ * agrees with it to the bit.  Everything below is a fact of the input -- a
+ * partition, integer counts, an order statistic -- so nothing is rounded.
+ *
+ * Input.  n vertices with xyz, normals (3 floats each), rgb (3 bytes),
+ * confidence (1 float) and optionally cells (int64, the sparse fusion's cell
+ * per vertex); m faces of three uint32 vertex ids.
+ *
+ * 1. Cut value t.
+ *      percentile == 0   t = threshold; threshold <= 0 means no cut
+ *      0 < percentile <= 100
+ *                        k = (int64)((double)percentile * (double)(n - 1) /
+ *                        100.0); t is the k-th smallest confidence, 0-based,
+ *                        in the order of the key u ^ (u >> 31 ? 0xFFFFFFFF :
+ *                        0x80000000) on the float's bits u (-0.0 sorts below
+ *                        0.0, a NaN by its sign beyond the infinities).
+ *                        n == 0 means no cut
+ *    Both non-zero is SMVS_ERR_INVALID.  Vertex v is cut when confidence[v] <
+ *    t, a float comparison: a NaN confidence is never cut, a NaN t cuts
+ *    nothing.  "No cut" is t = -inf.
+ * 2. Faces, first pass.  A face survives when none of its corners is cut and
+ *    its three ids are pairwise different.
+ * 3. Components.  Two uncut vertices are linked when a surviving face holds
+ *    both; components are the transitive closure.  A component's size is its
+ *    number of vertices; an uncut vertex in no surviving face is a component
+ *    of size 1.  A vertex is small when its component has fewer than
+ *    component_size vertices; component_size <= 1 makes nothing small.
+ * 4. Unreferenced.  Unless keep_unreferenced != 0, an uncut vertex in no
+ *    surviving face is dropped whatever component_size is.
+ * 5. Result.  The vertices that are not cut, not small and not dropped, in
+ *    input order; new id = rank.  Every attribute (and cells) is copied bit for
+ *    bit; normals are not recomputed.  The surviving faces whose corners all
+ *    remain, in input order, ids renumbered.  An empty result is not an error.
+ *
+ * Optional outputs per INPUT vertex (each may be NULL):
+ *   component       uint32: the smallest vertex id of the vertex's component,
+ *                   0xFFFFFFFF for a cut vertex
+ *   component_size  uint32: the component's size, 0 for a cut vertex
+ *   new_id          int64: the vertex's id in the result, -1 when it is removed
+ * stats (may be NULL): cut_value = t; n_cut the cut vertices; n_components the
+ * components of step 3 (those of size 1 included); n_small_components and
+ * n_small_vertices the components below component_size and their vertices;
+ * n_unreferenced the uncut vertices in no surviving face (kept or not);
+ * largest_component the largest size, 0 without a component.
+ *
+ * Refused with SMVS_ERR_INVALID before any device call: n or m negative or
+ * above 2^31 - 1; a face id >= n (one host pass over the faces); a percentile
+ * outside [0, 100] or not finite; a threshold that is not finite; threshold and
+ * percentile both non-zero; a missing array with n > 0 (faces with m > 0).
+ *
+ * The handle is a mesh handle (smvs_points_info / _download / _release; no
+ * values).  It answers smvs_tsdf_vertex_cells exactly when cells was given.
+ * smvs_mesh_clean_handle cleans the mesh a handle holds (cells when it is a
+ * sparse fusion's) and is SMVS_ERR_INVALID on a handle without faces: a point
+ * cloud's that kept none.  (A mesh handle with 0 faces has faces.)  A point
+ * cloud's values are not carried over. */
+typedef struct {
+    float threshold;        /* meshclean -t; 0: off */
+    float percentile;       /* meshclean -p; 0: off */
+    int component_size;     /* meshclean -c */
+    int keep_unreferenced;
+} smvs_mesh_clean_options;
+
+typedef struct {
+    float cut_value;
+    int64_t n_cut, n_components, n_small_components, n_small_vertices, n_unreferenced,
+        largest_component;
+} smvs_mesh_clean_stats;
+
+int smvs_mesh_clean(int device, int64_t n, int64_t m, const float *xyz, const float *normals,
+    const uint8_t *rgb, const float *confidence, const int64_t *cells, const uint32_t *faces,
+    const smvs_mesh_clean_options *options, uint32_t *component, uint32_t *component_size,
+    int64_t *new_id, smvs_mesh_clean_stats *stats, smvs_points **handle, int64_t *n_vertices,
+    int64_t *n_faces);
+
+int smvs_mesh_clean_handle(int device, const smvs_points *in,
+    const smvs_mesh_clean_options *options, uint32_t *component, uint32_t *component_size,
+    int64_t *new_id, smvs_mesh_clean_stats *stats, smvs_points **handle, int64_t *n_vertices,
+    int64_t *n_faces);
+
 /* smvsrecon --simplify (MeshGenerator::Options::simplify, mesh_generator.cc:
  * 238-243): per view DepthTriangulator::approximate_triangulation
  * (depth_triangulator.cc:27-172) -- Garland and Heckbert's greedy insertion

@@ -77,6 +77,24 @@ class TsdfSparseOptsStats(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class MeshCleanOptions(C.Structure):
+    """smvs_mesh_clean_options of include/smvs_hip.h."""
+    _fields_ = [("threshold", C.c_float), ("percentile", C.c_float),
+                ("component_size", C.c_int), ("keep_unreferenced", C.c_int)]
+
+
+class MeshCleanStats(C.Structure):
+    """smvs_mesh_clean_stats of include/smvs_hip.h."""
+    _fields_ = [("cut_value", C.c_float), ("n_cut", C.c_int64), ("n_components", C.c_int64),
+                ("n_small_components", C.c_int64), ("n_small_vertices", C.c_int64),
+                ("n_unreferenced", C.c_int64), ("largest_component", C.c_int64)]
+
+    def as_dict(self):
+        out = {name: int(getattr(self, name)) for name, _ in self._fields_[1:]}
+        out["cut_value"] = float(self.cut_value)
+        return out
+
+
 K_NAMES = ["patch", "assemble", "cg_spmv", "cg_update", "cg_init",
            "reactivate", "misc", "cg_resident"]
 

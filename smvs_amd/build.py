@@ -11,7 +11,8 @@ SOURCES = ["ctx.hip", "gn_construct.hip", "cg.hip", "cg_resident.hip", "reactiva
            "sgm_paths.hip", "sgm_wta.hip", "sgm_view.hip", "sgm_sweep.hip", "sgm_speckle.hip", "sgm_photo.hip", "sgm_refine.hip", "image_prep.hip", "bilateral.hip",
            "scale.hip", "topology.hip", "topo_zbuffer.hip", "topo_visibility.hip", "topo_mse.hip",
            "topo_cut.hip", "mesh_cut.hip", "export_common.hip", "mesh.hip", "simplify.hip", "pool.hip", "surface.hip",
-           "surface_planes.hip", "undistort.hip", "tsdf.hip", "tsdf_sparse.hip", "tsdf_cull.hip"]
+           "surface_planes.hip", "undistort.hip", "tsdf.hip", "tsdf_sparse.hip", "tsdf_cull.hip",
+           "mesh_clean.hip"]
 # HIP-free units of the library: the host compiler builds them
 HOST_CC_SOURCES = ["tile_budget.cc"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",

@@ -129,14 +129,7 @@ aabb_compact_kernel(size_t n, float3 lo, float3 hi,
     if (outside_aabb(src.xyz + 3 * i, lo, hi))
         return;
     size_t const j = at[i];
-    for (int r = 0; r < 3; ++r) {
-        dst.xyz[3 * j + r] = src.xyz[3 * i + r];
-        dst.nrm[3 * j + r] = src.nrm[3 * i + r];
-        dst.rgb[3 * j + r] = src.rgb[3 * i + r];
-    }
-    dst.conf[j] = src.conf[i];
-    if (dst.val != nullptr)   // (a triangle mesh has no values)
-        dst.val[j] = src.val[i];
+    SMVS_COPY_VERTEX(src, i, dst, j);
 }
 
 int

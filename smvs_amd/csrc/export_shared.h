@@ -82,6 +82,22 @@ vertex_attrs(Bufs const &b)
 {
     return VertexAttrs{ b.xyz, b.nrm, b.rgb, b.conf, b.val };
 }
+// Vertex i of src becomes vertex j of dst, bit for bit: what an
+// order-preserving compaction does once its keep flag has spoken (the AABB
+// clip and the mesh clean differ in the flag alone).  A macro and not a
+// function: expanded in the clip's kernel it leaves that kernel the instruction
+// stream it had (an inlined function reorders its address arithmetic).
+#define SMVS_COPY_VERTEX(src, i, dst, j)                                      \
+    do {                                                                      \
+        for (int r = 0; r < 3; ++r) {                                         \
+            (dst).xyz[3 * (j) + r] = (src).xyz[3 * (i) + r];                  \
+            (dst).nrm[3 * (j) + r] = (src).nrm[3 * (i) + r];                  \
+            (dst).rgb[3 * (j) + r] = (src).rgb[3 * (i) + r];                  \
+        }                                                                     \
+        (dst).conf[j] = (src).conf[i];                                        \
+        if ((dst).val != nullptr) /* (a triangle mesh has no values) */       \
+            (dst).val[j] = (src).val[i];                                      \
+    } while (0)
 // smvsrecon.cc:306-319 on n vertices: keep flags into `scan`, their exclusive
 // scan (the new ids; the kept count ends up in *scan_total(tiles, n)) and the
 // order-preserving compaction src -> dst.  Only enqueues.
@@ -95,5 +111,39 @@ int launch_aabb_clip(hipStream_t stream, size_t n, float3 lo, float3 hi, VertexA
 // returned); on failure nothing is left behind
 int fill_points(Workspace &ws, bool mesh, bool sparse, size_t n_vert, size_t n_face,
     VertexAttrs const &v, const uint32_t *faces, const long long *cells, smvs_points **handle);
+
+// ------------------------------------------------------ mesh clean (mesh_clean.hip)
+// smvs_mesh_clean's definition (include/smvs_hip.h) from device arrays to device
+// arrays.  Only enqueues: a fusion entry can call it on its vertices and faces
+// before fill_points, with no host round trip in between.
+struct MeshCleanCounts {   // on the device; what the stats and the handle's sizes are read from
+    float cut_value;
+    uint32_t pad;
+    unsigned long long n_cut, n_components, n_small_components, n_small_vertices,
+        n_unreferenced, largest_component, n_vertices, n_faces;
+};
+struct MeshCleanWork {     // pieces of a workspace slab, see carve_mesh_clean
+    MeshCleanCounts *counts;
+    uint32_t *select;                  // the radix select's state and histogram
+    uint32_t *label, *count, *size;    // per vertex; size == nullptr: not wanted
+    uint8_t *cut, *referenced, *survive;   // per vertex, per vertex, per face
+    unsigned long long *vscan, *vtiles, *fscan, *ftiles;
+};
+// lays the work arrays of n vertices and m faces out in a slab; resolve with
+// mesh_clean_work once the slab exists
+struct MeshCleanPieces {
+    size_t counts, select, label, count, size, cut, referenced, survive, vscan, vtiles, fscan,
+        ftiles;
+    bool want_size;
+};
+MeshCleanPieces carve_mesh_clean(Carver &carve, size_t n, size_t m, bool want_size);
+MeshCleanWork mesh_clean_work(char *slab, MeshCleanPieces const &at);
+// src (n vertices, cells may be null, m faces) -> dst, arrays with room for n
+// vertices and m faces.  Afterwards, on the stream: work.counts filled;
+// work.label = `component`, work.size = `component_size` (when wanted) and
+// work.vscan = `new_id` (as int64) of the definition.
+int launch_mesh_clean(hipStream_t stream, size_t n, size_t m, VertexAttrs src,
+    const long long *src_cells, const uint32_t *src_faces, smvs_mesh_clean_options const &opt,
+    MeshCleanWork const &work, VertexAttrs dst, long long *dst_cells, uint32_t *dst_faces);
 
 } // namespace smvs_hip

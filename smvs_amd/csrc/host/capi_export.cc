@@ -63,10 +63,12 @@ export_results(ExportCall const& c, std::string const& path, std::size_t nv, std
         *c.n_faces = (int64_t)nf;
 }
 
-// The three fused entries: the settings records share their first four members;
-// `rest` sets what a record has beyond them.
+// The fused entries: the settings records share their first four members;
+// `rest` sets what a record has beyond them.  clean_stats: the entry with the
+// clean alone.
 template <class Settings, class Rest> int
-generate_fused(ExportCall const& c, char const* entry, const Settings *f, Rest rest)
+generate_fused(ExportCall const& c, char const* entry, const Settings *f, Rest rest,
+    smvs_mesh_clean_stats *clean_stats = nullptr)
 {
     return guarded([&] {
         PointCloudSettings const conf = export_settings(c, entry, f != nullptr);
@@ -77,7 +79,8 @@ generate_fused(ExportCall const& c, char const* entry, const Settings *f, Rest r
         fo.min_weight = f->min_weight;
         rest(fo);
         std::size_t nv = 0, nf = 0;
-        std::string const path = generate_scene_fused(c.scene_dir, conf, fo, &nv, &nf);
+        std::string const path = generate_scene_fused(c.scene_dir, conf, fo, &nv, &nf,
+            clean_stats);
         export_results(c, path, nv, nf);
     });
 }
@@ -169,6 +172,26 @@ smvs_host_generate_fused_sparse_cull(const char *scene_dir,
             fo.max_bricks = f->max_bricks;
             fo.cull = f->cull != 0;
         });
+}
+
+extern "C" int
+smvs_host_generate_fused_clean(const char *scene_dir,
+    const smvs_host_point_cloud_settings *o, const smvs_host_fused_clean_settings *f,
+    const int *view_ids, int n_view_ids, char *ply_path, int ply_path_capacity,
+    int64_t *n_vertices, int64_t *n_faces, smvs_mesh_clean_stats *stats)
+{
+    return generate_fused({ scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
+        n_vertices, n_faces }, "smvs_host_generate_fused_clean", f,
+        [f](MeshGenerator::FusedOptions& fo) {
+            fo.sparse = f->sparse != 0;
+            fo.max_bricks = f->max_bricks;
+            fo.cull = f->cull != 0;
+            fo.clean = true;
+            fo.clean_threshold = f->threshold;
+            fo.clean_percentile = f->percentile;
+            fo.clean_component_size = f->component_size;
+            fo.clean_keep_unreferenced = f->keep_unreferenced != 0;
+        }, stats);
 }
 
 extern "C" int

@@ -608,6 +608,32 @@ int smvs_host_generate_fused_sparse_cull(const char *scene_dir,
     const smvs_host_point_cloud_settings *settings,
     const smvs_host_fused_sparse_cull_settings *fused, const int *view_ids, int n_view_ids,
     char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces);
+/* The fused mesh of one of the three entries above -- dense (sparse == 0;
+ * max_bricks and cull must then be 0), sparse, or sparse with cull != 0 --
+ * cleaned by smvs_mesh_clean_handle (threshold,
+ * percentile, component_size, keep_unreferenced are smvs_mesh_clean_options')
+ * and written through save_ply_mesh as <scene>/smvs-clean-{B,S}<input_scale>
+ * .ply; the fused file is not written.  The record's first six members are the
+ * cull entry's.  n_vertices and n_faces are the cleaned mesh's; stats (may be
+ * NULL) what the clean counted. */
+typedef struct {
+    float voxel_size;
+    int resolution;
+    float trunc;
+    int min_weight;
+    int64_t max_bricks;
+    int cull;
+    int sparse;
+    float threshold;
+    float percentile;
+    int component_size;
+    int keep_unreferenced;
+} smvs_host_fused_clean_settings;
+int smvs_host_generate_fused_clean(const char *scene_dir,
+    const smvs_host_point_cloud_settings *settings,
+    const smvs_host_fused_clean_settings *fused, const int *view_ids, int n_view_ids,
+    char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces,
+    smvs_mesh_clean_stats *stats);
 /* save_ply_mesh: the PLY writer of the triangle mesh from SoA
  * buffers (xyz, normals n*3 floats; rgb n*3 bytes; confidence n floats;
  * faces m*3 vertex ids < n). */

@@ -209,7 +209,8 @@ MeshGenerator::generate_simplified(std::vector<SceneView> const& inputviews,
 
 TriangleMesh::Ptr
 MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
-    std::string const& image_name, std::string const& dm_name, FusedOptions const& fused)
+    std::string const& image_name, std::string const& dm_name, FusedOptions const& fused,
+    smvs_mesh_clean_stats* clean_stats)
 {
     Inputs in;
     load_views(inputviews, image_name, dm_name, in);
@@ -285,6 +286,22 @@ MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
     } else
         check_status(smvs_tsdf_fuse(opts.device, in.pv.data(), n, &to, nullptr, nullptr,
             &handle, &nv, &nf), "smvs_tsdf_fuse");
+    if (fused.clean) {
+        smvs_mesh_clean_options co;
+        co.threshold = fused.clean_threshold;
+        co.percentile = fused.clean_percentile;
+        co.component_size = fused.clean_component_size;
+        co.keep_unreferenced = fused.clean_keep_unreferenced ? 1 : 0;
+        smvs_mesh_clean_stats st = {};
+        smvs_points* cleaned = nullptr;
+        int const rc = smvs_mesh_clean_handle(opts.device, handle, &co, nullptr, nullptr,
+            nullptr, &st, &cleaned, &nv, &nf);
+        smvs_points_release(handle);
+        check_status(rc, "smvs_mesh_clean_handle");
+        handle = cleaned;
+        if (clean_stats != nullptr)
+            *clean_stats = st;
+    }
     mesh->xyz.resize(3 * (std::size_t)nv);
     mesh->normals.resize(3 * (std::size_t)nv);
     mesh->colors.resize(3 * (std::size_t)nv);
@@ -521,12 +538,15 @@ generate_scene_simplified(std::string const& scene_path, PointCloudSettings cons
 
 std::string
 generate_scene_fused(std::string const& scene_path, PointCloudSettings const& conf,
-    MeshGenerator::FusedOptions const& fused, std::size_t* n_vertices, std::size_t* n_faces)
+    MeshGenerator::FusedOptions const& fused, std::size_t* n_vertices, std::size_t* n_faces,
+    smvs_mesh_clean_stats* clean_stats)
 {
     SceneInputs const in = scene_inputs(scene_path, conf);
     MeshGenerator meshgen(generator_options(conf));
-    TriangleMesh::Ptr mesh = meshgen.generate_fused(in.views, in.input_name, in.dm_name, fused);
-    std::string const meshname = in.scene->get_path() + "/smvs-fused-"
+    TriangleMesh::Ptr mesh = meshgen.generate_fused(in.views, in.input_name, in.dm_name, fused,
+        clean_stats);
+    std::string const meshname = in.scene->get_path()
+        + (fused.clean ? "/smvs-clean-" : "/smvs-fused-")
         + (conf.use_shading ? "S" : "B") + std::to_string(conf.input_scale) + ".ply";
     save_ply_mesh(meshname, *mesh);
     if (n_vertices != nullptr)

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "../../../include/smvs_hip.h"   // smvs_mesh_clean_stats
 #include "scene_io.h"
 
 namespace smvs_amd {
@@ -93,10 +94,19 @@ public:
         int64_t max_bricks = 0;     // sparse only; <= 0: 1 << 20
         bool cull = false;          // sparse only: the brick cull in front of the
                                     // seed pass (section 9.10), the same mesh
+        // the fused mesh (dense, sparse or sparse + cull) goes through
+        // smvs_mesh_clean_handle (section 9.12) before it comes back; off:
+        // the calls made are the ones above
+        bool clean = false;
+        float clean_threshold = 0.0f;       // meshclean -t; 0: off
+        float clean_percentile = 0.0f;      // meshclean -p; 0: off
+        int clean_component_size = 1000;    // meshclean -c
+        bool clean_keep_unreferenced = false;
     };
     TriangleMesh::Ptr generate_fused(std::vector<SceneView> const& views,
         std::string const& image_name, std::string const& dm_name,
-        FusedOptions const& fused);
+        FusedOptions const& fused, smvs_mesh_clean_stats* clean_stats = nullptr);
+    // (clean_stats: what the clean counted, with fused.clean)
 
 private:
     struct Inputs;
@@ -156,9 +166,12 @@ std::string generate_scene_simplified(std::string const& scene_path,
 
 // not in the reference: MeshGenerator::generate_fused over the scene's views,
 // <scene>/smvs-fused-{B,S}<input_scale>.ply through save_ply_mesh; the box is
-// the settings' AABB when use_aabb is set; -> the file written
+// the settings' AABB when use_aabb is set; -> the file written.  With
+// fused.clean the cleaned mesh is written instead, as
+// <scene>/smvs-clean-{B,S}<input_scale>.ply, and the fused file is not.
 std::string generate_scene_fused(std::string const& scene_path,
     PointCloudSettings const& settings, MeshGenerator::FusedOptions const& fused,
-    std::size_t* n_vertices = nullptr, std::size_t* n_faces = nullptr);
+    std::size_t* n_vertices = nullptr, std::size_t* n_faces = nullptr,
+    smvs_mesh_clean_stats* clean_stats = nullptr);
 
 } // namespace smvs_amd

@@ -19,6 +19,7 @@
 // a fact of the input and the counts are integer sums: the result is defined
 // to the bit.
 #include "sgm_internal.h"
+#include "union_find.h"
 
 namespace smvs_hip {
 
@@ -35,44 +36,8 @@ speckle_linked(float a, float b, float ratio)
     return a > 0.0f && b > 0.0f && fminf(a, b) / fmaxf(a, b) >= ratio;
 }
 
-// SCOPE: __HIP_MEMORY_SCOPE_WORKGROUP for the labels of a tile in LDS,
-// __HIP_MEMORY_SCOPE_AGENT for the global labels (the L2 caches of the XCDs are
-// not coherent with each other for plain loads)
-template <int SCOPE>
-__device__ __forceinline__ uint32_t
-uf_find(uint32_t *label, uint32_t a)
-{
-    uint32_t p = __hip_atomic_load(label + a, __ATOMIC_RELAXED, SCOPE);
-    while (p != a) {   // p < a
-        a = p;
-        p = __hip_atomic_load(label + a, __ATOMIC_RELAXED, SCOPE);
-    }
-    return a;
-}
-
-// The larger root gets the smaller one as its parent.  Where another thread
-// lowered label[a] first, `old` is below a and the loop goes on from there:
-// max(a, b) falls with every pass.
-template <int SCOPE>
-__device__ __forceinline__ void
-uf_union(uint32_t *label, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = uf_find<SCOPE>(label, a);
-        b = uf_find<SCOPE>(label, b);
-        if (a == b)
-            return;
-        if (a < b) {
-            uint32_t const t = a;
-            a = b;
-            b = t;
-        }
-        uint32_t const old = __hip_atomic_fetch_min(label + a, b, __ATOMIC_RELAXED, SCOPE);
-        if (old == a)
-            return;
-        a = old;
-    }
-}
+// (uf_find and uf_union: union_find.h; workgroup scope for the labels of a tile
+// in LDS, agent scope for the global labels)
 
 // label[p], p = y * w + x: the root of p inside its tile as a global pixel
 // index (a pixel that is not valid is its own root); count[p] = 0.

@@ -1613,6 +1613,71 @@ def tsdf_depth_pyramid(cams, depths, normals, view, cut=True, device=0):
     return levels
 
 
+def clean_mesh(mesh, threshold=0.0, percentile=0.0, component_size=1000, keep_unreferenced=False,
+               labels=False, device=0):
+    """smvs_mesh_clean (what MVE's meshclean does to a fused surface; the
+    definition is in include/smvs_hip.h): the vertices
+    whose confidence is below the cut value are removed -- threshold, or the
+    percentile-th percentile of the confidences (the reference README's
+    `meshclean -p10` is percentile=10) -- then the connected components of
+    fewer than component_size vertices and, unless keep_unreferenced, the
+    vertices no face uses.  The defaults (no cut, components below 1000) are
+    defaults of a user option, untuned.
+
+    mesh: the dict fuse_tsdf / generate_mesh return (xyz, normals, rgb,
+    confidence, faces; cells is carried when present).  Returns the same kind of
+    dict, order kept and attributes bit for bit, plus stats (cut_value, n_cut,
+    n_components, n_small_components, n_small_vertices, n_unreferenced,
+    largest_component) and, with labels, per input vertex component (uint32,
+    the smallest vertex id of its component, 0xFFFFFFFF when cut),
+    component_size (uint32) and new_id (int64, -1 when removed)."""
+    lib = _capi.load()
+    xyz, nrm = _f32(mesh["xyz"]), _f32(mesh["normals"])
+    rgb = np.ascontiguousarray(mesh["rgb"], np.uint8)
+    conf = _f32(mesh["confidence"])
+    faces = np.ascontiguousarray(mesh["faces"], np.uint32)
+    n, m = conf.size, faces.size // 3
+    if xyz.size != 3 * n or nrm.size != 3 * n or rgb.size != 3 * n or faces.size != 3 * m:
+        raise ValueError("clean_mesh: attribute shapes differ")
+    cells = None
+    if mesh.get("cells") is not None:
+        cells = np.ascontiguousarray(mesh["cells"], np.int64)
+        if cells.size != n:
+            raise ValueError("clean_mesh: attribute shapes differ")
+    opt = _capi.MeshCleanOptions(float(threshold), float(percentile), int(component_size),
+                                 int(bool(keep_unreferenced)))
+    stats = _capi.MeshCleanStats()
+    comp = size = new_id = None
+    if labels:
+        comp, size = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        new_id = np.zeros(n, np.int64)
+    i64p = C.POINTER(C.c_int64)
+    handle = C.c_void_p()
+    n_vertices, n_faces = C.c_int64(), C.c_int64()
+    check(lib.smvs_mesh_clean(device, C.c_int64(n), C.c_int64(m), _p(xyz, _fp), _p(nrm, _fp),
+                              _p(rgb, _u8p), _p(conf, _fp), _p(cells, i64p), _p(faces, _u32p),
+                              C.byref(opt), _p(comp, _u32p), _p(size, _u32p), _p(new_id, i64p),
+                              C.byref(stats), C.byref(handle), C.byref(n_vertices),
+                              C.byref(n_faces)))
+    try:
+        k = n_vertices.value
+        out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
+               "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
+               "faces": np.zeros((n_faces.value, 3), np.uint32)}
+        check(lib.smvs_points_download(handle, _p(out["xyz"], _fp), _p(out["normals"], _fp),
+                                       _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
+                                       None, _p(out["faces"], _u32p)))
+        if cells is not None:
+            out["cells"] = np.zeros(k, np.int64)
+            check(lib.smvs_tsdf_vertex_cells(handle, _p(out["cells"], i64p)))
+    finally:
+        lib.smvs_points_release(handle)
+    out["stats"] = stats.as_dict()
+    if labels:
+        out["component"], out["component_size"], out["new_id"] = comp, size, new_id
+    return out
+
+
 class SimplifyOptions(C.Structure):
     """smvs_simplify_options of include/smvs_hip.h."""
     _fields_ = [("cut_surfaces", C.c_int), ("use_aabb", C.c_int),

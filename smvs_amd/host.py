@@ -1015,10 +1015,17 @@ class FusedSparseCullSettings(C.Structure):
     _fields_ = FusedSparseSettings._fields_ + [("cull", C.c_int)]
 
 
+class FusedCleanSettings(C.Structure):
+    """smvs_host_fused_clean_settings"""
+    _fields_ = FusedSparseCullSettings._fields_ + [
+        ("sparse", C.c_int), ("threshold", C.c_float), ("percentile", C.c_float),
+        ("component_size", C.c_int), ("keep_unreferenced", C.c_int)]
+
+
 def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=0, min_weight=0,
                    view_ids=None, image_embedding="undistorted", input_scale=0,
                    use_shading=False, cut=True, device=0, sparse=False, max_bricks=0,
-                   cull=False):
+                   cull=False, clean=None):
     """Not in the reference: the views' smvs-{B,S}<input_scale> depth maps fused
     into ONE surface mesh through a truncated signed distance field
     (smvs_tsdf_fuse), written as
@@ -1033,13 +1040,40 @@ def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=
     in the brick order, under the same file name; resolution may go up to 4096;
     max_bricks 0: 1 << 20 bricks.  cull (with sparse): the brick cull against
     the views' depth min/max pyramids in front of the seed pass (section 9.10);
-    the file is the same byte for byte."""
+    the file is the same byte for byte.
+
+    clean: None, or dict(threshold=, percentile=, component_size=,
+    keep_unreferenced=) -- smvs_amd.clean_mesh's options, the same defaults --
+    and the fused mesh goes through smvs_mesh_clean_handle (section 9.12, what
+    `meshclean -p10` does after fssrecon: percentile=10).  The cleaned mesh is
+    written as <scene>/smvs-clean-{B,S}<input_scale>.ply, the fused file is
+    not, and the call returns (ply path, number of vertices, number of faces,
+    the clean's counts as clean_mesh's stats)."""
     if cull and not sparse:
         raise ValueError("cull belongs to sparse=True")
     lib = load()
     st = _point_cloud_settings(image_embedding, input_scale, use_shading, cut, aabb, True,
                                False, device)
-    if sparse and cull:
+    stats = None
+    if clean is not None:
+        unknown = set(clean) - {"threshold", "percentile", "component_size", "keep_unreferenced"}
+        if unknown:
+            raise ValueError("clean: unknown option %s" % sorted(unknown))
+        if max_bricks and not sparse:
+            raise ValueError("max_bricks belongs to sparse=True")
+        fs = FusedCleanSettings(0.0 if voxel_size is None else float(voxel_size),
+                                int(resolution), float(trunc), int(min_weight), int(max_bricks),
+                                int(bool(cull)), int(bool(sparse)),
+                                float(clean.get("threshold", 0.0)),
+                                float(clean.get("percentile", 0.0)),
+                                int(clean.get("component_size", 1000)),
+                                int(bool(clean.get("keep_unreferenced", False))))
+        stats = _capi.MeshCleanStats()
+        fn = lib.smvs_host_generate_fused_clean
+
+        def entry(*args):
+            return fn(*args, C.byref(stats))
+    elif sparse and cull:
         fs = FusedSparseCullSettings(0.0 if voxel_size is None else float(voxel_size),
                                      int(resolution), float(trunc), int(min_weight),
                                      int(max_bricks), 1)
@@ -1064,6 +1098,8 @@ def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=
         C.byref(nf))
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
+    if stats is not None:
+        return path.value.decode(), nv.value, nf.value, stats.as_dict()
     return path.value.decode(), nv.value, nf.value
 
 
