@@ -1272,11 +1272,11 @@ int smvs_mesh_generate(int device, const smvs_point_view *views, int n_views,
  * world_point and the projection are those of the mesh export.
  *
  * Inputs.  views as smvs_mesh_generate takes them (ray-length depth, camera
- * space normals, 1- or 3-channel colour image, a size per view; cut_depth is
- * not written).  The preparation is the mesh export's (z-depth depth_z and,
- * with cut_surfaces and n_views > 1, the cut map cut).  A view's depth at pixel
- * p is D(p) = depth_z[p] where cut[p] != 0, else 0.  normals may be NULL only
- * when cut_surfaces == 0.
+ * space normals, a colour image of 1 to 4 channels read as step 8 says, a size
+ * per view; cut_depth is not written).  The preparation is the mesh export's
+ * (z-depth depth_z and, with cut_surfaces and n_views > 1, the cut map cut).  A
+ * view's depth at pixel p is D(p) = depth_z[p] where cut[p] != 0, else 0.
+ * normals may be NULL only when cut_surfaces == 0.
  *   trunc <= 0      means 3.0f * voxel_size
  *   min_weight <= 0 means 1
  *
@@ -1290,8 +1290,9 @@ int smvs_mesh_generate(int device, const smvs_point_view *views, int n_views,
  *   5. skip if D(xj, yj) == 0
  *   6. sdf = D - proj[2]; skip if sdf < -trunc
  *   7. S += fminf(1.0f, sdf / trunc); W += 1 (uint32)
- *   8. if sdf <= trunc: R, G, B (uint32) += the pixel's bytes (grey: all
- *      three the one byte; 3 or 4 channels: bytes 0..2), C += 1
+ *   8. if sdf <= trunc: R, G, B (uint32) += the pixel's bytes (1 or 2
+ *      channels, grey: all three its byte 0; 3 or 4 channels: bytes 0..2;
+ *      the pixel's other bytes are not read), C += 1
  * F = S / (float)W where W >= min_weight, else NaN ("unknown").
  *
  * Vertices (surface nets).  Cell (i, j, k), 0 <= idx[a] <= dims[a] - 2, has
