@@ -1509,6 +1509,75 @@ int smvs_tsdf_depth_pyramid(int device, const smvs_point_view *views, int n_view
 int smvs_tsdf_bounds(int device, const smvs_point_view *views, int n_views,
     int cut_surfaces, float *lo, float *hi);
 
+/* A persistent volume of smvs_tsdf_fuse (opt-in): the
+ * sums of its field kept on the device between calls, so that the views are
+ * fused batch by batch, a fusion is resumed from a checkpoint, and the surface
+ * is extracted any number of times.  This comment is the definition on top of
+ * smvs_tsdf_fuse's paragraphs (Inputs, Field, Vertices, Faces), which it does
+ * not repeat; tests/tsdf_volume_ref.py restates it on top of tests/tsdf_ref.py.
+ *
+ * State.  Per voxel S (float), W (uint32) and (R, G, B, C) (4 x uint32), x
+ * fastest: 24 bytes per voxel of device memory the volume owns, and the number
+ * of views integrated so far.  create: all zero.  trunc <= 0 means 3.0f *
+ * voxel_size, fixed at create.
+ *
+ * Integrate.  The list is prepared as smvs_tsdf_fuse prepares its list (the
+ * cut, with cut_surfaces and n_views > 1, acts among the views of THIS list),
+ * and steps 1-8 of Field run for its views in list order, starting from the
+ * stored S, W, R, G, B, C instead of from zero: S is continued term by term
+ * (S = ((S + a) + b) + ..., never S + (a + b + ...)).  The stored count grows
+ * by n_views.  After calls with the lists L1, L2, ... the volume therefore
+ * holds the sums of smvs_tsdf_fuse's Field over the concatenated list, with
+ * each view's D prepared within its own call.  With cut_surfaces == 0, or with
+ * one call, that is smvs_tsdf_fuse itself, to the bit, for every split of the
+ * list into consecutive batches.  A voxel no view of the list contributes to
+ * is neither read nor written.
+ *
+ * Extract.  F = S / (float)W where W >= min_weight (<= 0 means 1), else NaN;
+ * then Vertices and Faces of smvs_tsdf_fuse, n_views in the confidence being
+ * the stored count.  tsdf / weight (either may be NULL) and the handle as
+ * smvs_tsdf_fuse gives them.  No state changes.  With no view integrated the
+ * handle is empty and tsdf all NaN.
+ *
+ * download / upload are the checkpoint (S and W: one value per voxel, rgbc: 4
+ * per voxel; download's pointers may each be NULL, upload needs all three): a
+ * state downloaded and uploaded into a volume of the same options continues to
+ * the same bits.  reset zeroes the sums and the count.  info gives back the
+ * options (trunc as given to create), the count and the device; each pointer
+ * may be NULL.
+ *
+ * Refused with SMVS_ERR_INVALID before any device call: a NULL volume; at
+ * create a voxel_size that is not a positive finite number, a dim < 2 or
+ * > 1024, more than 2^27 voxels, a non-finite origin or trunc; per integrate
+ * what smvs_tsdf_fuse refuses for its views, and a stored count that would
+ * pass 2^24 (255 * count must fit uint32, 8 * count an int); upload with
+ * n_views < 0 or > 2^24.  A refused or failed call leaves the state as it was
+ * (a failed upload: undefined sums, reset or upload again).  A failed
+ * allocation at create is SMVS_ERR_NOMEM and leaves no handle.  Calls on one
+ * volume are not to overlap; different volumes are independent. */
+typedef struct {
+    float origin[3];      /* the low corner of voxel (0, 0, 0) */
+    float voxel_size;
+    int dims[3];
+    float trunc;
+} smvs_tsdf_volume_options;
+typedef struct smvs_tsdf_volume smvs_tsdf_volume;
+
+int smvs_tsdf_volume_create(int device, const smvs_tsdf_volume_options *options,
+    smvs_tsdf_volume **volume);
+int smvs_tsdf_volume_integrate(smvs_tsdf_volume *volume, const smvs_point_view *views,
+    int n_views, int cut_surfaces);
+int smvs_tsdf_volume_extract(const smvs_tsdf_volume *volume, int min_weight, float *tsdf,
+    uint32_t *weight, smvs_points **handle, int64_t *n_vertices, int64_t *n_faces);
+int smvs_tsdf_volume_info(const smvs_tsdf_volume *volume, smvs_tsdf_volume_options *options,
+    int64_t *n_views, int *device);
+int smvs_tsdf_volume_download(const smvs_tsdf_volume *volume, float *S, uint32_t *W,
+    uint32_t *rgbc);
+int smvs_tsdf_volume_upload(smvs_tsdf_volume *volume, const float *S, const uint32_t *W,
+    const uint32_t *rgbc, int64_t n_views);
+int smvs_tsdf_volume_reset(smvs_tsdf_volume *volume);
+void smvs_tsdf_volume_release(smvs_tsdf_volume *volume);
+
 /* Cleaning a triangle mesh (not in the reference, whose documented pipeline
  * ends with MVE's `meshclean -p10`; opt-in): a cut on
  * the vertex confidences, then the removal of small connected components and

@@ -77,6 +77,12 @@ class TsdfSparseOptsStats(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class TsdfVolumeOptions(C.Structure):
+    """smvs_tsdf_volume_options of include/smvs_hip.h."""
+    _fields_ = [("origin", C.c_float * 3), ("voxel_size", C.c_float), ("dims", C.c_int * 3),
+                ("trunc", C.c_float)]
+
+
 class MeshCleanOptions(C.Structure):
     """smvs_mesh_clean_options of include/smvs_hip.h."""
     _fields_ = [("threshold", C.c_float), ("percentile", C.c_float),

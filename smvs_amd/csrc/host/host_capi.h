@@ -634,6 +634,36 @@ int smvs_host_generate_fused_clean(const char *scene_dir,
     const smvs_host_fused_clean_settings *fused, const int *view_ids, int n_view_ids,
     char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces,
     smvs_mesh_clean_stats *stats);
+/* The dense fused mesh with only batch_views consecutive scene views loaded at
+ * a time: the bounds are folded batch by batch, the
+ * batches are integrated into a persistent volume (smvs_tsdf_volume) and the
+ * surface is extracted once.  Without the cut (cut_surface == 0) the file is
+ * smvs_host_generate_fused's byte for byte; the cut, when on, acts within a
+ * batch.  The record's first eleven members are the clean entry's; clean != 0
+ * cleans the mesh as that entry does (file name, counts, stats), clean == 0
+ * writes the fused file and leaves stats alone.  batch_views == 0 is the
+ * unbatched entry (dense or sparse as the record says); batch_views > 0 with
+ * sparse != 0 is refused, and so is batch_views < 0. */
+typedef struct {
+    float voxel_size;
+    int resolution;
+    float trunc;
+    int min_weight;
+    int64_t max_bricks;
+    int cull;
+    int sparse;
+    float threshold;
+    float percentile;
+    int component_size;
+    int keep_unreferenced;
+    int clean;
+    int batch_views;
+} smvs_host_fused_batched_settings;
+int smvs_host_generate_fused_batched(const char *scene_dir,
+    const smvs_host_point_cloud_settings *settings,
+    const smvs_host_fused_batched_settings *fused, const int *view_ids, int n_view_ids,
+    char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces,
+    smvs_mesh_clean_stats *stats);
 /* save_ply_mesh: the PLY writer of the triangle mesh from SoA
  * buffers (xyz, normals n*3 floats; rgb n*3 bytes; confidence n floats;
  * faces m*3 vertex ids < n). */

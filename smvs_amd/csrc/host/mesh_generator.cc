@@ -207,33 +207,14 @@ MeshGenerator::generate_simplified(std::vector<SceneView> const& inputviews,
     save_cut_maps(in);
 }
 
-TriangleMesh::Ptr
-MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
-    std::string const& image_name, std::string const& dm_name, FusedOptions const& fused,
-    smvs_mesh_clean_stats* clean_stats)
+namespace {
+
+// the grid of generate_fused from its box: [lo, hi] is the settings' AABB, or
+// the bounds of the depth maps' points, which are padded here
+smvs_tsdf_options
+fused_grid(MeshGenerator::Options const& opts, MeshGenerator::FusedOptions const& fused,
+    float* lo, float* hi)
 {
-    Inputs in;
-    load_views(inputviews, image_name, dm_name, in);
-    TriangleMesh::Ptr mesh(new TriangleMesh);
-    if (in.views.empty())
-        return mesh;
-    if (fused.voxel_size <= 0.0f && fused.resolution < 8)
-        throw std::invalid_argument("generate_fused: resolution must be at least 8");
-    if (fused.sparse && fused.voxel_size <= 0.0f && fused.resolution > 4096)
-        throw std::invalid_argument("generate_fused: resolution must be at most 4096");
-    if (!fused.sparse && fused.max_bricks > 0)
-        throw std::invalid_argument("generate_fused: max_bricks belongs to sparse");
-    if (!fused.sparse && fused.cull)
-        throw std::invalid_argument("generate_fused: cull belongs to sparse");
-    int const n = (int)in.pv.size();
-    float lo[3], hi[3];
-    if (opts.use_aabb) {
-        std::copy(opts.aabb_min, opts.aabb_min + 3, lo);
-        std::copy(opts.aabb_max, opts.aabb_max + 3, hi);
-    } else {
-        check_status(smvs_tsdf_bounds(opts.device, in.pv.data(), n,
-            opts.cut_surfaces ? 1 : 0, lo, hi), "smvs_tsdf_bounds");
-    }
     for (int a = 0; a < 3; ++a)
         if (!(lo[a] <= hi[a]))
             throw std::invalid_argument(opts.use_aabb
@@ -269,6 +250,82 @@ MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
         to.origin[a] = lo[a];
         to.dims[a] = std::max(2, (int)std::ceil((hi[a] - lo[a]) / voxel));
     }
+    return to;
+}
+
+// the fused mesh behind `handle` (released here), cleaned when asked for
+TriangleMesh::Ptr
+fused_result(MeshGenerator::Options const& opts, MeshGenerator::FusedOptions const& fused,
+    smvs_points* handle, int64_t nv, int64_t nf, smvs_mesh_clean_stats* clean_stats)
+{
+    if (fused.clean) {
+        smvs_mesh_clean_options co;
+        co.threshold = fused.clean_threshold;
+        co.percentile = fused.clean_percentile;
+        co.component_size = fused.clean_component_size;
+        co.keep_unreferenced = fused.clean_keep_unreferenced ? 1 : 0;
+        smvs_mesh_clean_stats st = {};
+        smvs_points* cleaned = nullptr;
+        int const rc = smvs_mesh_clean_handle(opts.device, handle, &co, nullptr, nullptr,
+            nullptr, &st, &cleaned, &nv, &nf);
+        smvs_points_release(handle);
+        check_status(rc, "smvs_mesh_clean_handle");
+        handle = cleaned;
+        if (clean_stats != nullptr)
+            *clean_stats = st;
+    }
+    TriangleMesh::Ptr mesh(new TriangleMesh);
+    mesh->xyz.resize(3 * (std::size_t)nv);
+    mesh->normals.resize(3 * (std::size_t)nv);
+    mesh->colors.resize(3 * (std::size_t)nv);
+    mesh->confidences.resize((std::size_t)nv);
+    mesh->faces.resize(3 * (std::size_t)nf);
+    int const rc = smvs_points_download(handle, mesh->xyz.data(), mesh->normals.data(),
+        mesh->colors.data(), mesh->confidences.data(), nullptr, mesh->faces.data());
+    smvs_points_release(handle);
+    check_status(rc, "smvs_points_download");
+    return mesh;
+}
+
+struct VolumeHolder
+{
+    smvs_tsdf_volume* v = nullptr;
+    ~VolumeHolder() { smvs_tsdf_volume_release(v); }
+};
+
+} // namespace
+
+TriangleMesh::Ptr
+MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
+    std::string const& image_name, std::string const& dm_name, FusedOptions const& fused,
+    smvs_mesh_clean_stats* clean_stats)
+{
+    if (fused.batch_views < 0)
+        throw std::invalid_argument("generate_fused: batch_views must not be negative");
+    if (fused.batch_views > 0)
+        return generate_fused_batched(inputviews, image_name, dm_name, fused, clean_stats);
+    Inputs in;
+    load_views(inputviews, image_name, dm_name, in);
+    if (in.views.empty())
+        return TriangleMesh::Ptr(new TriangleMesh);
+    if (fused.voxel_size <= 0.0f && fused.resolution < 8)
+        throw std::invalid_argument("generate_fused: resolution must be at least 8");
+    if (fused.sparse && fused.voxel_size <= 0.0f && fused.resolution > 4096)
+        throw std::invalid_argument("generate_fused: resolution must be at most 4096");
+    if (!fused.sparse && fused.max_bricks > 0)
+        throw std::invalid_argument("generate_fused: max_bricks belongs to sparse");
+    if (!fused.sparse && fused.cull)
+        throw std::invalid_argument("generate_fused: cull belongs to sparse");
+    int const n = (int)in.pv.size();
+    float lo[3], hi[3];
+    if (opts.use_aabb) {
+        std::copy(opts.aabb_min, opts.aabb_min + 3, lo);
+        std::copy(opts.aabb_max, opts.aabb_max + 3, hi);
+    } else {
+        check_status(smvs_tsdf_bounds(opts.device, in.pv.data(), n,
+            opts.cut_surfaces ? 1 : 0, lo, hi), "smvs_tsdf_bounds");
+    }
+    smvs_tsdf_options const to = fused_grid(opts, fused, lo, hi);
     smvs_points* handle = nullptr;
     int64_t nv = 0, nf = 0;
     if (fused.sparse && fused.cull) {
@@ -286,32 +343,85 @@ MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
     } else
         check_status(smvs_tsdf_fuse(opts.device, in.pv.data(), n, &to, nullptr, nullptr,
             &handle, &nv, &nf), "smvs_tsdf_fuse");
-    if (fused.clean) {
-        smvs_mesh_clean_options co;
-        co.threshold = fused.clean_threshold;
-        co.percentile = fused.clean_percentile;
-        co.component_size = fused.clean_component_size;
-        co.keep_unreferenced = fused.clean_keep_unreferenced ? 1 : 0;
-        smvs_mesh_clean_stats st = {};
-        smvs_points* cleaned = nullptr;
-        int const rc = smvs_mesh_clean_handle(opts.device, handle, &co, nullptr, nullptr,
-            nullptr, &st, &cleaned, &nv, &nf);
-        smvs_points_release(handle);
-        check_status(rc, "smvs_mesh_clean_handle");
-        handle = cleaned;
-        if (clean_stats != nullptr)
-            *clean_stats = st;
+    return fused_result(opts, fused, handle, nv, nf, clean_stats);
+}
+
+// generate_fused with FusedOptions::batch_views: one batch of consecutive
+// scene views is loaded at a time, for the bounds and again for the
+// integration into a persistent volume (smvs_tsdf_volume, DESIGN.md section
+// 9.13).  The usable views of the batches, one after the other, are the list
+// generate_fused loads at once; the cut, when on, acts within a batch.
+TriangleMesh::Ptr
+MeshGenerator::generate_fused_batched(std::vector<SceneView> const& inputviews,
+    std::string const& image_name, std::string const& dm_name, FusedOptions const& fused,
+    smvs_mesh_clean_stats* clean_stats)
+{
+    if (fused.sparse)
+        throw std::invalid_argument("generate_fused: batch_views belongs to the dense volume");
+    if (fused.voxel_size <= 0.0f && fused.resolution < 8)
+        throw std::invalid_argument("generate_fused: resolution must be at least 8");
+    if (fused.max_bricks > 0)
+        throw std::invalid_argument("generate_fused: max_bricks belongs to sparse");
+    if (fused.cull)
+        throw std::invalid_argument("generate_fused: cull belongs to sparse");
+    std::size_t const step = (std::size_t)fused.batch_views;
+    int const cut = opts.cut_surfaces ? 1 : 0;
+    // calls `use` with the loaded views of every batch that has one
+    auto for_batches = [&](auto use) {
+        for (std::size_t at = 0; at < inputviews.size(); at += step) {
+            std::vector<SceneView> const batch(inputviews.begin() + at,
+                inputviews.begin() + std::min(inputviews.size(), at + step));
+            Inputs in;
+            load_views(batch, image_name, dm_name, in);
+            if (!in.views.empty())
+                use(in);
+        }
+    };
+    float lo[3], hi[3];
+    std::size_t usable = 0;
+    if (opts.use_aabb) {
+        std::copy(opts.aabb_min, opts.aabb_min + 3, lo);
+        std::copy(opts.aabb_max, opts.aabb_max + 3, hi);
+    } else {
+        // the union's box: min and max are exact, so the order does not matter
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = INFINITY;
+            hi[a] = -INFINITY;
+        }
+        for_batches([&](Inputs& in) {
+            float blo[3], bhi[3];
+            check_status(smvs_tsdf_bounds(opts.device, in.pv.data(), (int)in.pv.size(), cut,
+                blo, bhi), "smvs_tsdf_bounds");
+            usable += in.pv.size();
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = std::fmin(lo[a], blo[a]);
+                hi[a] = std::fmax(hi[a], bhi[a]);
+            }
+        });
+        if (usable == 0)
+            return TriangleMesh::Ptr(new TriangleMesh);
     }
-    mesh->xyz.resize(3 * (std::size_t)nv);
-    mesh->normals.resize(3 * (std::size_t)nv);
-    mesh->colors.resize(3 * (std::size_t)nv);
-    mesh->confidences.resize((std::size_t)nv);
-    mesh->faces.resize(3 * (std::size_t)nf);
-    int const rc = smvs_points_download(handle, mesh->xyz.data(), mesh->normals.data(),
-        mesh->colors.data(), mesh->confidences.data(), nullptr, mesh->faces.data());
-    smvs_points_release(handle);
-    check_status(rc, "smvs_points_download");
-    return mesh;
+    smvs_tsdf_options const to = fused_grid(opts, fused, lo, hi);
+    smvs_tsdf_volume_options vo;
+    std::copy(to.origin, to.origin + 3, vo.origin);
+    std::copy(to.dims, to.dims + 3, vo.dims);
+    vo.voxel_size = to.voxel_size;
+    vo.trunc = to.trunc;
+    VolumeHolder volume;
+    check_status(smvs_tsdf_volume_create(opts.device, &vo, &volume.v), "smvs_tsdf_volume_create");
+    usable = 0;
+    for_batches([&](Inputs& in) {
+        check_status(smvs_tsdf_volume_integrate(volume.v, in.pv.data(), (int)in.pv.size(), cut),
+            "smvs_tsdf_volume_integrate");
+        usable += in.pv.size();
+    });
+    if (usable == 0)
+        return TriangleMesh::Ptr(new TriangleMesh);
+    smvs_points* handle = nullptr;
+    int64_t nv = 0, nf = 0;
+    check_status(smvs_tsdf_volume_extract(volume.v, to.min_weight, nullptr, nullptr, &handle,
+        &nv, &nf), "smvs_tsdf_volume_extract");
+    return fused_result(opts, fused, handle, nv, nf, clean_stats);
 }
 
 void

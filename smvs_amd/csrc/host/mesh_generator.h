@@ -102,6 +102,12 @@ public:
         float clean_percentile = 0.0f;      // meshclean -p; 0: off
         int clean_component_size = 1000;    // meshclean -c
         bool clean_keep_unreferenced = false;
+        // > 0 (dense only): only batch_views consecutive scene views are
+        // loaded at a time, for the bounds and for the integration into a
+        // persistent volume (smvs_tsdf_volume, section 9.13).  Without the cut
+        // the mesh is the one-shot's to the bit; the cut, when on, acts
+        // within a batch.  0: off, the calls made are the ones above
+        int batch_views = 0;
     };
     TriangleMesh::Ptr generate_fused(std::vector<SceneView> const& views,
         std::string const& image_name, std::string const& dm_name,
@@ -114,6 +120,9 @@ private:
     void load_views(std::vector<SceneView> const& inputviews,
         std::string const& image_name, std::string const& dm_name, Inputs& in) const;
     void save_cut_maps(Inputs const& in) const;
+    TriangleMesh::Ptr generate_fused_batched(std::vector<SceneView> const& views,
+        std::string const& image_name, std::string const& dm_name,
+        FusedOptions const& fused, smvs_mesh_clean_stats* clean_stats);
 
     Options opts;
 };

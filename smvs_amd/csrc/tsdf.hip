@@ -19,7 +19,9 @@
 // No atomics: every order is an index order (vertex ids and face positions
 // come from the scan and a scan inside each block).
 // The per-element device functions live in tsdf_shared.h, which
-// tsdf_sparse.hip (the brick-sparse volume, section 9.9) uses as well.
+// tsdf_sparse.hip (the brick-sparse volume, section 9.9) uses as well; the
+// extraction half of the entry is tsdf_host::extract_surface, which
+// tsdf_volume.hip (the persistent volume, section 9.13) runs on its own sums.
 #include "common.h"
 #include "mesh_shared.h"
 #include "tsdf_shared.h"
@@ -336,18 +338,71 @@ launch_depth(hipStream_t stream, ViewSlab const &s, int n_views)
         (unsigned)n_views), dim3(256), 0, stream, s.d_table);
 }
 
+void
+carve_extract(size_t n_vox, Carver &carve, ExtractPieces &at)
+{
+    at.point_blocks = (unsigned)((n_vox + 255) / 256);
+    size_t const scan_tiles = ((size_t)at.point_blocks + SCAN_TILE - 1) / SCAN_TILE;
+    at.vid = carve(4 * n_vox);
+    at.counts = carve(8 * (size_t)at.point_blocks);
+    at.tiles = carve(8 * (scan_tiles + 1));
+}
+
+int
+extract_surface(Workspace &ws, const char *who, TsdfGrid const &G, char *slab,
+    ExtractPieces const &at, const float *d_tsdf, const uint32_t *d_weight,
+    const uint4 *d_colour, smvs_points **handle)
+{
+    hipStream_t const stream = ws.stream;
+    unsigned const point_blocks = at.point_blocks;
+    uint32_t *d_vid = reinterpret_cast<uint32_t *>(slab + at.vid);
+    unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(slab + at.counts);
+    unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(slab + at.tiles);
+    int rc;
+    hipLaunchKernelGGL(tsdf_classify_kernel, dim3(point_blocks), dim3(256), 0, stream, d_tsdf,
+        G, d_counts);
+    SMVS_HIP_CHECK(hipGetLastError());
+    if ((rc = exclusive_scan(stream, d_counts, point_blocks, d_tiles)))
+        return rc;
+    unsigned long long sums = 0;
+    if ((rc = ws.download(&sums, scan_total(d_tiles, point_blocks), sizeof(sums))))
+        return rc;
+    size_t const n_vert = (size_t)(sums & 0xffffffffull);
+    size_t const n_face = 2 * (size_t)(sums >> 32);
+
+    // (no vertices: no second slab, no launches, an empty handle)
+    TsdfOut O = {};
+    if (n_vert > 0) {
+        Carver oc;
+        size_t const xyz_at = oc(12 * n_vert), nrm_at = oc(12 * n_vert), conf_at = oc(4 * n_vert),
+            rgb_at = oc(3 * n_vert), faces_at = oc(12 * n_face);
+        char *outs = nullptr;
+        if ((rc = ws.ensure(1, oc.total, &outs)) != SMVS_OK)
+            return rc;
+        O.xyz = reinterpret_cast<float *>(outs + xyz_at);
+        O.nrm = reinterpret_cast<float *>(outs + nrm_at);
+        O.conf = reinterpret_cast<float *>(outs + conf_at);
+        O.rgb = reinterpret_cast<uint8_t *>(outs + rgb_at);
+        O.faces = reinterpret_cast<uint32_t *>(outs + faces_at);
+        hipLaunchKernelGGL(tsdf_vertex_kernel, dim3(point_blocks), dim3(256), 0, stream,
+            d_tsdf, d_weight, d_colour, G, d_counts, d_vid, O);
+        hipLaunchKernelGGL(tsdf_face_kernel, dim3(point_blocks), dim3(256), 0, stream, d_tsdf,
+            G, d_counts, d_vid, O);
+        if (hipGetLastError() != hipSuccess) {
+            set_error("%s: extraction launch failed", who);
+            return SMVS_ERR_HIP;
+        }
+    }
+    return fill_points(ws, true, false, n_vert, n_face,
+        VertexAttrs{ O.xyz, O.nrm, O.rgb, O.conf, nullptr }, O.faces, nullptr, handle);
+}
+
 } // namespace tsdf_host
 
 } // namespace smvs_hip
 
 using namespace smvs_hip;
 using namespace smvs_hip::tsdf_host;
-
-namespace {
-
-constexpr size_t TSDF_MAX_VOXELS = (size_t)1 << 27;
-
-} // namespace
 
 extern "C" int
 smvs_tsdf_bounds(int device, const smvs_point_view *views, int n_views, int cut_surfaces,
@@ -416,11 +471,10 @@ smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
     ViewSlab s;
     carve_views(views, n_views, true, carve, s);
     size_t const images_at = carve(sizeof(TsdfImageDev) * n_views);
-    unsigned const point_blocks = (unsigned)((n_vox + 255) / 256);
-    size_t const scan_tiles = ((size_t)point_blocks + SCAN_TILE - 1) / SCAN_TILE;
     size_t const tsdf_at = carve(4 * n_vox), weight_at = carve(4 * n_vox),
-        colour_at = carve(16 * n_vox), vid_at = carve(4 * n_vox),
-        counts_at = carve(8 * (size_t)point_blocks), tiles_at = carve(8 * (scan_tiles + 1));
+        colour_at = carve(16 * n_vox);
+    ExtractPieces extract_at;
+    carve_extract(n_vox, carve, extract_at);
     char *slab = nullptr;
     if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
         return rc;
@@ -433,9 +487,6 @@ smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
     float *d_tsdf = reinterpret_cast<float *>(slab + tsdf_at);
     uint32_t *d_weight = reinterpret_cast<uint32_t *>(slab + weight_at);
     uint4 *d_colour = reinterpret_cast<uint4 *>(slab + colour_at);
-    uint32_t *d_vid = reinterpret_cast<uint32_t *>(slab + vid_at);
-    unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(slab + counts_at);
-    unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(slab + tiles_at);
 
     launch_depth(stream, s, n_views);
     unsigned const bricks = (unsigned)((G.nx + TSDF_BX - 1) / TSDF_BX)
@@ -443,43 +494,9 @@ smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
         * (unsigned)((G.nz + TSDF_BZ - 1) / TSDF_BZ);
     hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(bricks), dim3(256), 0, stream, s.d_table,
         d_images, G, d_tsdf, d_weight, d_colour);
-    hipLaunchKernelGGL(tsdf_classify_kernel, dim3(point_blocks), dim3(256), 0, stream, d_tsdf,
-        G, d_counts);
-    SMVS_HIP_CHECK(hipGetLastError());
-    if ((rc = exclusive_scan(stream, d_counts, point_blocks, d_tiles)))
-        return rc;
-    unsigned long long sums = 0;
-    if ((rc = ws.download(&sums, scan_total(d_tiles, point_blocks), sizeof(sums))))
-        return rc;
-    size_t const n_vert = (size_t)(sums & 0xffffffffull);
-    size_t const n_face = 2 * (size_t)(sums >> 32);
-
-    // (no vertices: no second slab, no launches, an empty handle)
-    TsdfOut O = {};
-    if (n_vert > 0) {
-        Carver oc;
-        size_t const xyz_at = oc(12 * n_vert), nrm_at = oc(12 * n_vert), conf_at = oc(4 * n_vert),
-            rgb_at = oc(3 * n_vert), faces_at = oc(12 * n_face);
-        char *outs = nullptr;
-        if ((rc = ws.ensure(1, oc.total, &outs)) != SMVS_OK)
-            return rc;
-        O.xyz = reinterpret_cast<float *>(outs + xyz_at);
-        O.nrm = reinterpret_cast<float *>(outs + nrm_at);
-        O.conf = reinterpret_cast<float *>(outs + conf_at);
-        O.rgb = reinterpret_cast<uint8_t *>(outs + rgb_at);
-        O.faces = reinterpret_cast<uint32_t *>(outs + faces_at);
-        hipLaunchKernelGGL(tsdf_vertex_kernel, dim3(point_blocks), dim3(256), 0, stream,
-            d_tsdf, d_weight, d_colour, G, d_counts, d_vid, O);
-        hipLaunchKernelGGL(tsdf_face_kernel, dim3(point_blocks), dim3(256), 0, stream, d_tsdf,
-            G, d_counts, d_vid, O);
-        if (hipGetLastError() != hipSuccess) {
-            set_error("smvs_tsdf_fuse: extraction launch failed");
-            return SMVS_ERR_HIP;
-        }
-    }
     smvs_points *h = nullptr;
-    if ((rc = fill_points(ws, true, false, n_vert, n_face,
-            VertexAttrs{ O.xyz, O.nrm, O.rgb, O.conf, nullptr }, O.faces, nullptr, &h)))
+    if ((rc = extract_surface(ws, "smvs_tsdf_fuse", G, slab, extract_at, d_tsdf, d_weight,
+            d_colour, &h)))
         return rc;
     if ((tsdf != nullptr && (rc = ws.download(tsdf, d_tsdf, 4 * n_vox)))
         || (weight != nullptr && (rc = ws.download(weight, d_weight, 4 * n_vox)))) {

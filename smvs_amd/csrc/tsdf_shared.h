@@ -1,6 +1,7 @@
 // Pieces of the volumetric fusion that tsdf.hip (the dense volume),
-// tsdf_sparse.hip (the brick-sparse volume) and tsdf_cull.hip (the brick cull
-// in front of its seed pass) share: the grid record, the brick grid, the
+// tsdf_sparse.hip (the brick-sparse volume), tsdf_cull.hip (the brick cull
+// in front of its seed pass) and tsdf_volume.hip (the persistent dense
+// volume) share: the grid record, the brick grid, the
 // per-element device functions of the definition in include/smvs_hip.h (voxel
 // centre, the projection steps 1-6, the cell / edge / quad rules, the block
 // scan, the vertex attribute arithmetic) and the host pieces of the entries.
@@ -354,6 +355,9 @@ tsdf_quad_faces(const uint32_t *v, bool inside, uint32_t *out)
 // and cut them as every export path does)
 namespace tsdf_host {
 
+// the dense volume's size limit (smvs_tsdf_fuse, smvs_tsdf_volume_create)
+constexpr size_t TSDF_MAX_VOXELS = (size_t)1 << 27;
+
 // argument checks shared by the entries (before any device call)
 int check_views(const smvs_point_view *views, int n_views, int cut, bool want_images);
 // smvs_tsdf_options with each dim 2 .. max_dim (1024 or 4096); fills the grid record
@@ -366,6 +370,21 @@ int upload_image_table(Workspace &ws, char *slab, size_t at, const smvs_point_vi
     ViewSlab const &s, TsdfImageDev **d_images);
 // D(p) = depth_z[p] where cut[p] != 0, else 0, in place in depth_z
 void launch_depth(hipStream_t stream, ViewSlab const &s, int n_views);
+// The extraction half of smvs_tsdf_fuse, which smvs_tsdf_volume_extract
+// (tsdf_volume.hip) runs as well: classify, scan, vertices, faces, fill on a
+// field, weights and colour sums that are on the device (x fastest).
+// carve_extract lays its work arrays (cell -> vertex id, block counts, scan
+// tiles) out in the slab of slot 0; the vertices and faces go to slot 1.
+struct ExtractPieces {
+    size_t vid, counts, tiles;   // offsets in the slab
+    unsigned point_blocks;
+};
+void carve_extract(size_t n_vox, Carver &carve, ExtractPieces &at);
+// G.n_views is the confidence's view count; `who` heads the error text.  On
+// failure no handle is left behind.
+int extract_surface(Workspace &ws, const char *who, TsdfGrid const &G, char *slab,
+    ExtractPieces const &at, const float *d_tsdf, const uint32_t *d_weight,
+    const uint4 *d_colour, smvs_points **handle);
 
 // tsdf_cull.hip: the views' pyramids in the same slab and the passes over them
 struct PyramidSlab {

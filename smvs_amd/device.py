@@ -1547,6 +1547,122 @@ def _fuse_tsdf_sparse(cams, depths, normals, images, origin, voxel_size, dims, t
     return out
 
 
+class TsdfVolume:
+    """smvs_tsdf_volume: the sums of fuse_tsdf's field kept on the device, so
+    that the views are fused batch by batch (the
+    definition is in include/smvs_hip.h).  The grid is fuse_tsdf's (origin,
+    voxel_size, dims = (nx, ny, nz), trunc <= 0: 3 voxels).  With the cut off,
+    every split of a view list into consecutive integrate() calls gives
+    fuse_tsdf's arrays to the bit; the cut, when on, acts within a batch.  A
+    context manager; after close() every method raises ValueError."""
+
+    def __init__(self, origin, voxel_size, dims, trunc=0, device=0):
+        self._handle = None
+        self._lib = _capi.load()
+        opt = _capi.TsdfVolumeOptions()
+        for k in range(3):
+            opt.origin[k] = float(origin[k])
+            opt.dims[k] = int(dims[k])
+        opt.voxel_size = float(voxel_size)
+        opt.trunc = float(trunc)
+        handle = C.c_void_p()
+        check(self._lib.smvs_tsdf_volume_create(int(device), C.byref(opt), C.byref(handle)))
+        self._handle = handle
+        self._shape = tuple(int(d) for d in dims)[::-1]
+
+    def _open(self):
+        if self._handle is None:
+            raise ValueError("TsdfVolume: the volume is closed")
+        return self._handle
+
+    def integrate(self, cams, depths, normals, images, cut=True):
+        """smvs_tsdf_volume_integrate: one batch, inputs as fuse_tsdf's (normals
+        may be None when cut is off)."""
+        handle = self._open()
+        n = len(cams)
+        arr, _keep = _tsdf_views(cams, depths, normals, images)
+        check(self._lib.smvs_tsdf_volume_integrate(handle, arr if n else None, n,
+                                                   int(bool(cut))))
+
+    def extract(self, min_weight=0, volume=False):
+        """smvs_tsdf_volume_extract: the dict fuse_tsdf returns; changes no
+        state."""
+        handle = self._open()
+        lib = self._lib
+        tsdf = weight = None
+        if volume:
+            tsdf = np.zeros(self._shape, np.float32)
+            weight = np.zeros(self._shape, np.uint32)
+        mesh = C.c_void_p()
+        n_vertices, n_faces = C.c_int64(), C.c_int64()
+        check(lib.smvs_tsdf_volume_extract(handle, int(min_weight), _p(tsdf, _fp),
+                                           _p(weight, _u32p), C.byref(mesh),
+                                           C.byref(n_vertices), C.byref(n_faces)))
+        try:
+            k = n_vertices.value
+            out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
+                   "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
+                   "faces": np.zeros((n_faces.value, 3), np.uint32)}
+            check(lib.smvs_points_download(mesh, _p(out["xyz"], _fp), _p(out["normals"], _fp),
+                                           _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
+                                           None, _p(out["faces"], _u32p)))
+        finally:
+            lib.smvs_points_release(mesh)
+        if volume:
+            out["tsdf"] = tsdf
+            out["weight"] = weight
+        return out
+
+    @property
+    def n_views(self):
+        handle = self._open()
+        n = C.c_int64()
+        check(self._lib.smvs_tsdf_volume_info(handle, None, C.byref(n), None))
+        return n.value
+
+    def state(self):
+        """smvs_tsdf_volume_download: (S (nz, ny, nx) float32, W uint32, rgbc
+        (nz, ny, nx, 4) uint32: the sums R, G, B, C)."""
+        handle = self._open()
+        S = np.zeros(self._shape, np.float32)
+        W = np.zeros(self._shape, np.uint32)
+        rgbc = np.zeros(self._shape + (4,), np.uint32)
+        check(self._lib.smvs_tsdf_volume_download(handle, _p(S, _fp), _p(W, _u32p),
+                                                  _p(rgbc, _u32p)))
+        return S, W, rgbc
+
+    def load_state(self, S, W, rgbc, n_views):
+        """smvs_tsdf_volume_upload: what state() and n_views gave."""
+        handle = self._open()
+        S = np.ascontiguousarray(S, np.float32)
+        W = np.ascontiguousarray(W, np.uint32)
+        rgbc = np.ascontiguousarray(rgbc, np.uint32)
+        if S.shape != self._shape or W.shape != self._shape or rgbc.shape != self._shape + (4,):
+            raise ValueError("TsdfVolume.load_state: the arrays do not have the volume's shape")
+        check(self._lib.smvs_tsdf_volume_upload(handle, _p(S, _fp), _p(W, _u32p),
+                                                _p(rgbc, _u32p), C.c_int64(int(n_views))))
+
+    def reset(self):
+        handle = self._open()
+        check(self._lib.smvs_tsdf_volume_reset(handle))
+
+    def close(self):
+        if self._handle is not None:
+            self._lib.smvs_tsdf_volume_release(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        self._open()
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        self.close()
+
+
 def _tsdf_options(origin, voxel_size, dims, trunc, cut):
     opt = _capi.TsdfOptions()
     opt.cut_surfaces = int(bool(cut))

@@ -1022,10 +1022,15 @@ class FusedCleanSettings(C.Structure):
         ("component_size", C.c_int), ("keep_unreferenced", C.c_int)]
 
 
+class FusedBatchedSettings(C.Structure):
+    """smvs_host_fused_batched_settings"""
+    _fields_ = FusedCleanSettings._fields_ + [("clean", C.c_int), ("batch_views", C.c_int)]
+
+
 def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=0, min_weight=0,
                    view_ids=None, image_embedding="undistorted", input_scale=0,
                    use_shading=False, cut=True, device=0, sparse=False, max_bricks=0,
-                   cull=False, clean=None):
+                   cull=False, clean=None, batch_views=0):
     """Not in the reference: the views' smvs-{B,S}<input_scale> depth maps fused
     into ONE surface mesh through a truncated signed distance field
     (smvs_tsdf_fuse), written as
@@ -1048,7 +1053,14 @@ def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=
     `meshclean -p10` does after fssrecon: percentile=10).  The cleaned mesh is
     written as <scene>/smvs-clean-{B,S}<input_scale>.ply, the fused file is
     not, and the call returns (ply path, number of vertices, number of faces,
-    the clean's counts as clean_mesh's stats)."""
+    the clean's counts as clean_mesh's stats).
+
+    batch_views: N > 0 keeps only N consecutive scene views loaded at a time
+    (smvs_host_generate_fused_batched, section 9.13): the bounds are folded
+    batch by batch, the batches are integrated into a persistent dense volume
+    (smvs_amd.TsdfVolume) and the surface is extracted once.  With cut=False
+    the file is the same byte for byte; the cut, when on, acts within a batch.
+    It belongs to the dense volume: with sparse it is refused.  0: off."""
     if cull and not sparse:
         raise ValueError("cull belongs to sparse=True")
     lib = load()
@@ -1059,6 +1071,24 @@ def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=
         unknown = set(clean) - {"threshold", "percentile", "component_size", "keep_unreferenced"}
         if unknown:
             raise ValueError("clean: unknown option %s" % sorted(unknown))
+    if batch_views:
+        if max_bricks and not sparse:
+            raise ValueError("max_bricks belongs to sparse=True")
+        c = clean or {}
+        fs = FusedBatchedSettings(0.0 if voxel_size is None else float(voxel_size),
+                                  int(resolution), float(trunc), int(min_weight),
+                                  int(max_bricks), int(bool(cull)), int(bool(sparse)),
+                                  float(c.get("threshold", 0.0)), float(c.get("percentile", 0.0)),
+                                  int(c.get("component_size", 1000)),
+                                  int(bool(c.get("keep_unreferenced", False))),
+                                  int(clean is not None), int(batch_views))
+        if clean is not None:
+            stats = _capi.MeshCleanStats()
+        batched = lib.smvs_host_generate_fused_batched
+
+        def entry(*args):
+            return batched(*args, C.byref(stats) if stats is not None else None)
+    elif clean is not None:
         if max_bricks and not sparse:
             raise ValueError("max_bricks belongs to sparse=True")
         fs = FusedCleanSettings(0.0 if voxel_size is None else float(voxel_size),

@@ -13,6 +13,7 @@ tools/points_bench.py's (the 16 views repeat the nine synthetic ones).
     python tools/tsdf_bench.py [--dims N] [--views N] [--size W H] [--reps N]
                                [--no-kernels] [--no-peaks]
                                [--sparse [--resolution N] [--max-bricks N] [--cull]]
+                               [--batch N [--no-cut]]
 
 --sparse times smvs_tsdf_fuse_sparse (the brick-sparse volume, DESIGN.md section
 9.9) on the same case instead: --resolution N is --dims N and may go up to
@@ -23,6 +24,14 @@ its time per 1000 pairs of the allocated bricks.  --cull puts the brick cull
 (section 9.10) in front of the seed pass: the entry's line gains tested_bricks,
 their share and the pyramids' bytes, and the pyramid, cull, list and listed-seed
 kernels take the seed kernel's place.
+
+--batch N times the persistent volume (smvs_tsdf_volume, section 9.13) on the
+same case against the one-shot entry in the same process: create, integrate
+per batch of N views, extract, release -- box to box, the two entries
+alternating -- and the kernels of both from one trace each.  With the cut on a
+batch is cut within itself, which is less work than the one-shot's cut and
+another mesh; --no-cut compares like with like (the meshes are then equal, and
+the tool checks that they are).
 """
 import argparse
 import csv
@@ -51,6 +60,11 @@ SPARSE_KERNELS = ["mesh_prepare_kernel", "mesh_cut_kernel", "tsdf_depth_kernel",
 # in the place of tsdf_sparse_seed_kernel (the scan runs twice more)
 CULL_KERNELS = ["tsdf_pyramid_tile_kernel", "tsdf_pyramid_top_kernel", "tsdf_cull_kernel",
                 "tsdf_cull_list_kernel", "tsdf_sparse_seed_list_kernel"]
+# with --batch: the preparation runs per batch, the integration on the stored sums
+VOLUME_KERNELS = ["mesh_prepare_kernel", "mesh_cut_kernel", "tsdf_depth_kernel",
+                  "tsdf_volume_integrate_kernel", "tsdf_volume_field_kernel",
+                  "tsdf_classify_kernel", "scan_tile_sums_kernel", "scan_tiles_kernel",
+                  "scan_apply_kernel", "tsdf_vertex_kernel", "tsdf_face_kernel"]
 CHILD_REPS = 3
 BOX_LO, BOX_SIDE = (-1.3, -1.3, 2.7), 2.6
 
@@ -77,11 +91,25 @@ def sparse_kernels(args):
     return SPARSE_KERNELS[:at] + CULL_KERNELS + SPARSE_KERNELS[at + 1:]
 
 
+def fuse_batched(c, batch, cut):
+    """create, integrate per batch of `batch` views, extract, release"""
+    from smvs_amd import device
+    cams, depths, normals, images, origin, voxel, dims = c
+    with device.TsdfVolume(origin, voxel, dims) as vol:
+        for at in range(0, len(cams), batch):
+            vol.integrate(cams[at:at + batch], depths[at:at + batch], normals[at:at + batch],
+                          images[at:at + batch], cut=cut)
+        return vol.extract()
+
+
 def child(args):
     from smvs_amd import device
     c = case(args)
     for _ in range(CHILD_REPS):
-        device.fuse_tsdf(*c, cut=True, **sparse_args(args))
+        if args.batch:
+            fuse_batched(c, args.batch, not args.no_cut)
+        else:
+            device.fuse_tsdf(*c, cut=not args.no_cut, **sparse_args(args))
 
 
 def kernel_times(args):
@@ -95,6 +123,10 @@ def kernel_times(args):
             cmd += ["--sparse", "--max-bricks", str(args.max_bricks)]
         if args.cull:
             cmd += ["--cull"]
+        if args.batch:
+            cmd += ["--batch", str(args.batch)]
+        if args.no_cut:
+            cmd += ["--no-cut"]
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         if res.returncode != 0:
             raise RuntimeError("rocprofv3 failed: " + res.stderr[-2000:])
@@ -102,6 +134,10 @@ def kernel_times(args):
         if not files:
             raise RuntimeError("rocprofv3 left no kernel trace")
         names = sparse_kernels(args) if args.sparse else KERNELS
+        if args.batch:
+            names = VOLUME_KERNELS
+        if args.no_cut or (args.batch == 1):
+            names = [k for k in names if k != "mesh_cut_kernel"]
         rows = {k: [] for k in names}
         for fn in files:
             with open(fn) as f:
@@ -147,6 +183,44 @@ def sparse_kernel_lines(args, kt, stats, n_vox):
           flush=True)
 
 
+def batched_lines(args, c):
+    """--batch: the one-shot entry and the batched volume, alternating"""
+    import copy
+    from smvs_amd import device
+    cut = not args.no_cut
+    n_vox = args.dims ** 3
+    one, bat = [], []
+    for _ in range(args.reps + 1):
+        t0 = time.perf_counter()
+        a = device.fuse_tsdf(*c, cut=cut)
+        one.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        b = fuse_batched(c, args.batch, cut)
+        bat.append(time.perf_counter() - t0)
+    same = all(np.array_equal(a[k], b[k]) for k in a)
+    if not cut and not same:
+        raise SystemExit("tsdf_bench: without the cut the batched mesh must be the one-shot's")
+    batches = -(-args.views // args.batch)
+    print(json.dumps({"case": "batched_entry", "dims": [args.dims] * 3, "views": args.views,
+                      "size": args.size, "cut": cut, "batch": args.batch, "batches": batches,
+                      "same_mesh": bool(same), "vertices": len(b["xyz"]), "faces": len(b["faces"]),
+                      "one_shot_ms_best": round(1e3 * min(one[1:]), 2),
+                      "batched_ms_best": round(1e3 * min(bat[1:]), 2),
+                      "state_bytes": 24 * n_vox}), flush=True)
+    if args.no_kernels:
+        return
+    one_args = copy.copy(args)
+    one_args.batch = 0
+    for label, a in (("one_shot", one_args), ("batched", args)):
+        kt = kernel_times(a)
+        for k, (per, t) in kt.items():
+            print(json.dumps({"case": label + "_kernel", "kernel": k, "launches_per_call": per,
+                              "ms_per_call_best": round(1e3 * t, 4)}), flush=True)
+        print(json.dumps({"case": label + "_kernels_total",
+                          "ms_per_call_best": round(1e3 * sum(t for _, t in kt.values()), 3)}),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
@@ -161,7 +235,14 @@ def main():
     ap.add_argument("--max-bricks", type=int, default=0)
     ap.add_argument("--cull", action="store_true",
                     help="with --sparse: the brick cull in front of the seed pass")
+    ap.add_argument("--batch", type=int, default=0,
+                    help="the persistent volume, N views per integrate, against the one-shot")
+    ap.add_argument("--no-cut", action="store_true", help="with --batch: the cut off")
     args = ap.parse_args()
+    if args.batch < 0 or (args.batch and args.sparse):
+        ap.error("--batch N > 0 belongs to the dense volume")
+    if args.no_cut and not args.batch and not args.child:
+        ap.error("--no-cut belongs to --batch")
     if args.cull and not args.sparse:
         ap.error("--cull belongs to --sparse")
     if args.resolution is not None:
@@ -176,6 +257,9 @@ def main():
     if smvs_amd.device_count() < 1:
         raise SystemExit("tsdf_bench needs a GPU")
     c = case(args)
+    if args.batch:
+        batched_lines(args, c)
+        return
     n_vox = args.dims ** 3
     times = []
     for _ in range(args.reps + 1):
