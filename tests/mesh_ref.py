@@ -71,10 +71,11 @@ def face_terms(xyz, faces):
     return fn, w, ok.astype(bool)
 
 
-def mesh(cams, dms, wnormals, images, aabb=None, dd_factor=5.0):
+def mesh(cams, dms, wnormals, images, aabb=None, dd_factor=5.0, variant=None):
     """smvsrecon --mesh: the views triangulated and merged by points_ref (M1:
     no values, no looked-up normals), then M2-M5."""
-    merged = points_ref.points(cams, dms, wnormals, images, aabb=None, dd_factor=dd_factor)
+    merged = points_ref.points(cams, dms, wnormals, images, aabb=None, dd_factor=dd_factor,
+                               variant=variant)
     return finish(merged["xyz"], merged["rgb"], merged["confidence"], merged["faces"], aabb)
 
 

@@ -107,15 +107,58 @@ float pixel_footprint(int x, int y, float depth, const float *invproj)
     return invproj[0] * depth / std::sqrt(square_norm(v));
 }
 
+// The rules a subtly wrong kernel would get wrong, one per value (0 = the
+// pinned behaviour); tests/test_export_cases_cpu.py counts what each changes.
+enum Variant {
+    V_PINNED = 0,
+    V_P2_TIE_LE = 1,          // P2: `<=` for `<`
+    V_P3_GE = 2,              // P3: `>=` for `>`
+    V_P3_FOOTPRINT_MAX = 3,   // P3: the footprint of i_max
+    V_P3_NO_SQRT2 = 4,        // P3: no MATH_SQRT2 on the diagonals
+    V_P8_PREPEND_FIRST = 5,   // P8: prepend tested before append
+    V_P9_UNSORTED = 6,        // P9: complex list in face order, not sorted
+    V_P10_COMPLEX_SEEDS = 7,  // P10: complex vertices start the rings too
+    V_S6_LATEST = 8,          // S6: the latest stamp among equal keys
+    V_S7_GE = 9,              // S7: `>=` for `>`
+    V_S8_MULTIPLY = 10,       // S8: x = xa + r * dx for the repeated addition
+    V_S10_GE4 = 11,           // S10: `>= 4` for `> 4`
+    V_S10_OWN_TRIANGLE = 12,  // S10: the face's own triangle, not the k-th
+    V_S3_NO_FALLBACK = 13,    // S3: a zero corner depth stays zero
+};
+
+// What the triangulation met (optional, += so that views add up):
+// [0..15] blocks per corner mask, [16] P2 ties, [17] P3 edges tested,
+// [18] of them discontinuities, [19..21] axis edges whose larger depth is the
+// last float below / the float exactly at / the first float above the
+// threshold, [22..24] the same for diagonals, [25] edges of two equal depths
+enum { STAT_MASK = 0, STAT_TIES = 16, STAT_EDGES = 17, STAT_DISC = 18, STAT_AXIS = 19,
+    STAT_DIAG = 22, STAT_EQUAL = 25, STAT_COUNT = 26 };
+
 bool dm_is_depthdisc(const float *widths, const float *depths, float dd_factor,
-    int i1, int i2)
+    int i1, int i2, int variant = V_PINNED, int64_t *stats = nullptr)
 {
     int i_min = i1, i_max = i2;
     if (depths[i2] < depths[i1])
         std::swap(i_min, i_max);
-    if (i1 + i2 == 3)
+    bool const diagonal = i1 + i2 == 3;
+    if (diagonal && variant != V_P3_NO_SQRT2)
         dd_factor *= 1.41421356237309504880;   // MATH_SQRT2
-    return depths[i_max] - depths[i_min] > widths[i_min] * dd_factor;
+    float const diff = depths[i_max] - depths[i_min];
+    float const limit = widths[variant == V_P3_FOOTPRINT_MAX ? i_max : i_min] * dd_factor;
+    bool const disc = variant == V_P3_GE ? diff >= limit : diff > limit;
+    if (stats != nullptr) {
+        stats[STAT_EDGES] += 1;
+        stats[STAT_DISC] += disc;
+        stats[STAT_EQUAL] += depths[i1] == depths[i2];
+        int64_t *side = stats + (diagonal ? STAT_DIAG : STAT_AXIS);
+        // one float step of the larger depth reaches or crosses the threshold
+        float const up = std::nextafter(depths[i_max], INFINITY) - depths[i_min];
+        float const down = std::nextafter(depths[i_max], 0.0f) - depths[i_min];
+        side[0] += diff < limit && up >= limit;
+        side[1] += diff == limit;
+        side[2] += diff > limit && down <= limit;
+    }
+    return disc;
 }
 
 void dm_make_triangle(std::vector<Vec3> &verts, std::vector<uint32_t> &faces,
@@ -135,7 +178,8 @@ void dm_make_triangle(std::vector<Vec3> &verts, std::vector<uint32_t> &faces,
 
 void depthmap_triangulate(const float *dm, int width, int height,
     const float *invproj, float dd_factor, std::vector<Vec3> &verts,
-    std::vector<uint32_t> &faces, std::vector<uint32_t> &vidx)
+    std::vector<uint32_t> &faces, std::vector<uint32_t> &vidx, int variant = V_PINNED,
+    int64_t *stats = nullptr)
 {
     vidx.assign((size_t)width * height, 0xffffffffu);
     int i = 0;
@@ -149,6 +193,8 @@ void depthmap_triangulate(const float *dm, int width, int height,
                     mask |= 1 << j;
                     pixels += 1;
                 }
+            if (stats != nullptr)
+                stats[STAT_MASK + mask] += 1;
             if (pixels < 3)
                 continue;
             int tris[4][3] = { { 0, 2, 1 }, { 0, 3, 1 }, { 0, 2, 3 }, { 1, 2, 3 } };
@@ -161,7 +207,9 @@ void depthmap_triangulate(const float *dm, int width, int height,
             case 15: {
                 float const ddiff1 = std::abs(depths[0] - depths[3]);
                 float const ddiff2 = std::abs(depths[1] - depths[2]);
-                if (ddiff1 < ddiff2) {
+                if (stats != nullptr)
+                    stats[STAT_TIES] += ddiff1 == ddiff2;
+                if (variant == V_P2_TIE_LE ? ddiff1 <= ddiff2 : ddiff1 < ddiff2) {
                     tri[0] = 2;
                     tri[1] = 3;
                 } else {
@@ -181,9 +229,12 @@ void depthmap_triangulate(const float *dm, int width, int height,
                 }
                 for (int j = 0; j < 2 && tri[j] != 0; ++j) {
                     int *tv = tris[tri[j] - 1];
-                    if (dm_is_depthdisc(widths, depths, dd_factor, tv[0], tv[1])) tri[j] = 0;
-                    if (dm_is_depthdisc(widths, depths, dd_factor, tv[1], tv[2])) tri[j] = 0;
-                    if (dm_is_depthdisc(widths, depths, dd_factor, tv[2], tv[0])) tri[j] = 0;
+                    if (dm_is_depthdisc(widths, depths, dd_factor, tv[0], tv[1], variant, stats))
+                        tri[j] = 0;
+                    if (dm_is_depthdisc(widths, depths, dd_factor, tv[1], tv[2], variant, stats))
+                        tri[j] = 0;
+                    if (dm_is_depthdisc(widths, depths, dd_factor, tv[2], tv[0], variant, stats))
+                        tri[j] = 0;
                 }
             }
             for (int j = 0; j < 2; ++j) {
@@ -206,7 +257,8 @@ struct Edge {
 };
 
 // mve::MeshInfo::initialize / update_vertex
-std::vector<VertexInfo> mesh_info(size_t n_verts, std::vector<uint32_t> const &faces)
+std::vector<VertexInfo> mesh_info(size_t n_verts, std::vector<uint32_t> const &faces,
+    int variant = V_PINNED)
 {
     std::vector<VertexInfo> info(n_verts);
     for (size_t i = 0, i3 = 0; i < faces.size() / 3; ++i)
@@ -236,6 +288,12 @@ std::vector<VertexInfo> mesh_info(size_t n_verts, std::vector<uint32_t> const &f
             uint32_t const back_id = adj_sorted.back().v2;
             bool appended = false;
             for (auto it = adj_temp.begin(); it != adj_temp.end(); ++it) {
+                if (variant == V_P8_PREPEND_FIRST && it->v2 == front_id) {
+                    adj_sorted.push_front(*it);
+                    adj_temp.erase(it);
+                    appended = true;
+                    break;
+                }
                 if (it->v1 == back_id) {
                     adj_sorted.push_back(*it);
                     adj_temp.erase(it);
@@ -259,6 +317,15 @@ std::vector<VertexInfo> mesh_info(size_t n_verts, std::vector<uint32_t> const &f
                 for (int j = 0; j < 3; ++j)
                     if (faces[3 * f + j] != v)
                         vi.verts.push_back(faces[3 * f + j]);
+            if (variant == V_P9_UNSORTED) {
+                // first occurrences in face order
+                std::vector<uint32_t> seen;
+                for (uint32_t a : vi.verts)
+                    if (std::find(seen.begin(), seen.end(), a) == seen.end())
+                        seen.push_back(a);
+                vi.verts = seen;
+                continue;
+            }
             std::sort(vi.verts.begin(), vi.verts.end());
             vi.verts.erase(std::unique(vi.verts.begin(), vi.verts.end()), vi.verts.end());
             continue;
@@ -278,12 +345,13 @@ std::vector<VertexInfo> mesh_info(size_t n_verts, std::vector<uint32_t> const &f
 
 // mve::geom::depthmap_mesh_confidences
 void mesh_confidences(std::vector<VertexInfo> const &info, int iterations,
-    std::vector<float> &confs)
+    std::vector<float> &confs, int variant = V_PINNED)
 {
     confs.assign(info.size(), 1.0f);
     std::vector<size_t> vidx;
     for (size_t i = 0; i < info.size(); ++i)
-        if (info[i].vclass == BORDER) {
+        if (info[i].vclass == BORDER
+            || (variant == V_P10_COMPLEX_SEEDS && info[i].vclass == COMPLEX)) {
             vidx.push_back(i);
             confs[i] = 0.0f;
         }
@@ -305,18 +373,20 @@ void mesh_confidences(std::vector<VertexInfo> const &info, int iterations,
 
 // One view: dm (ray-length depth to triangulate), wnormals (world space),
 // image (channels bytes per pixel).  Outputs hold up to w*h vertices and
-// 2*(w-1)*(h-1) faces; vclass (optional) gets MeshInfo's class per vertex.
-// -> number of vertices.
+// 2*(w-1)*(h-1) faces; vclass (optional) gets MeshInfo's class per vertex,
+// stats (optional, STAT_COUNT entries) what the triangulation met; variant:
+// 0, or the one rule of `Variant` to get wrong.  -> number of vertices.
 extern "C" int64_t
 points_ref_view(int w, int h, float flen, const float *rot, const float *trans,
     const float *dm, const float *wnormals, const uint8_t *image, int channels,
     float dd_factor, float *xyz, float *nrm, uint8_t *rgb, float *conf,
-    float *val, uint32_t *faces_out, int64_t *n_faces, int32_t *vclass)
+    float *val, uint32_t *faces_out, int64_t *n_faces, int32_t *vclass, int variant,
+    int64_t *stats)
 {
     Camera const cam = make_camera(w, h, flen, rot, trans);
     std::vector<Vec3> verts;
     std::vector<uint32_t> faces, vidx;
-    depthmap_triangulate(dm, w, h, cam.invproj, dd_factor, verts, faces, vidx);
+    depthmap_triangulate(dm, w, h, cam.invproj, dd_factor, verts, faces, vidx, variant, stats);
     // mesh_transform with fill_cam_to_world: Matrix4f::mult(v, 1)
     for (Vec3 &v : verts) {
         Vec3 r;
@@ -330,9 +400,9 @@ points_ref_view(int w, int h, float flen, const float *rot, const float *trans,
         v = r;
     }
     size_t const nv = verts.size();
-    std::vector<VertexInfo> const info = mesh_info(nv, faces);
+    std::vector<VertexInfo> const info = mesh_info(nv, faces, variant);
     std::vector<float> confs;
-    mesh_confidences(info, 4, confs);
+    mesh_confidences(info, 4, confs, variant);
     for (size_t i = 0; i < (size_t)w * h; ++i) {
         if (vidx[i] == 0xffffffffu)
             continue;
@@ -381,4 +451,13 @@ points_ref_view(int w, int h, float flen, const float *rot, const float *trans,
     if (n_faces != nullptr)
         *n_faces = (int64_t)(faces.size() / 3);
     return (int64_t)nv;
+}
+
+// P4 alone: the footprint of pixel (x, y) at depth d in a w x h view
+extern "C" float
+points_ref_footprint(int w, int h, float flen, int x, int y, float d)
+{
+    float const rot[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, trans[3] = { 0, 0, 0 };
+    Camera const cam = make_camera(w, h, flen, rot, trans);
+    return pixel_footprint(x, y, d, cam.invproj);
 }

@@ -10,6 +10,7 @@ import tempfile
 import numpy as np
 
 import mesh_ref  # tests/mesh_ref.py
+from points_ref import VARIANTS  # tests/points_ref.py
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
@@ -29,6 +30,11 @@ def lib():
     return _lib
 
 
+# the counters of simplify_ref_view's and simplify_ref_triangulate's stats
+(SSTAT_ZERO, SSTAT_RATIO, SSTAT_FOUR, SSTAT_FIVE, SSTAT_OTHER, SSTAT_NEAR, SSTAT_TIED_TOPS,
+ SSTAT_TIED_SCANS, SSTAT_NOOP, SSTAT_ROWS, SSTAT_ITERATIONS, SSTAT_VALID, SSTAT_COUNT) = range(13)
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
@@ -38,9 +44,10 @@ def budget(w, h, max_vertices=-1):
     return (w * h) // 40 if max_vertices < 0 else int(max_vertices)
 
 
-def triangulate(dm, max_vertices=-1, max_error=-1.0):
+def triangulate(dm, max_vertices=-1, max_error=-1.0, variant=None):
     """S1-S8 on one depth map -> dict iterations, vertices (n, 3) float64,
-    triangles (t, 3) uint32, num_zero_depths (t,) int32."""
+    triangles (t, 3) uint32, num_zero_depths (t,) int32, stats (the counters
+    SSTAT_* of what the loop met)."""
     dm = np.ascontiguousarray(dm, np.float32)
     h, w = dm.shape
     b = budget(w, h, max_vertices)
@@ -48,16 +55,18 @@ def triangulate(dm, max_vertices=-1, max_error=-1.0):
     tris = np.zeros((2 * b + 2, 3), np.uint32)
     nzero = np.zeros(2 * b + 2, np.int32)
     nv, nt = C.c_int64(0), C.c_int64(0)
+    stats = np.zeros(SSTAT_COUNT, np.int64)
     with np.errstate(all="ignore"):
         it = lib().simplify_ref_triangulate(w, h, _ptr(dm, C.c_float), int(max_vertices),
                                             C.c_double(max_error), _ptr(verts, C.c_double),
                                             C.byref(nv), _ptr(tris, C.c_uint32),
-                                            _ptr(nzero, C.c_int32), C.byref(nt))
+                                            _ptr(nzero, C.c_int32), C.byref(nt),
+                                            VARIANTS[variant], _ptr(stats, C.c_int64))
     return {"iterations": int(it), "vertices": verts[:nv.value], "triangles": tris[:nt.value],
-            "num_zero_depths": nzero[:nt.value]}
+            "num_zero_depths": nzero[:nt.value], "stats": stats}
 
 
-def view(cam, dm, wnormals, image, max_vertices=-1, max_error=-1.0):
+def view(cam, dm, wnormals, image, max_vertices=-1, max_error=-1.0, variant=None):
     """One view of generate_mesh with Options::simplify -> dict of arrays."""
     dm = np.ascontiguousarray(dm, np.float32)
     h, w = dm.shape
@@ -74,25 +83,30 @@ def view(cam, dm, wnormals, image, max_vertices=-1, max_error=-1.0):
     val = np.zeros(n, np.float32)
     faces = np.zeros((2 * n, 3), np.uint32)
     nf = C.c_int64(0)
+    stats = np.zeros(SSTAT_COUNT, np.int64)
+    vclass = np.zeros(n, np.int32)
     k = lib().simplify_ref_view(w, h, C.c_float(cam.flen), _ptr(rot, C.c_float),
                                 _ptr(trans, C.c_float), _ptr(dm, C.c_float),
                                 _ptr(wn, C.c_float), _ptr(im, C.c_uint8), ch,
                                 int(max_vertices), C.c_double(max_error),
                                 _ptr(xyz, C.c_float), _ptr(nrm, C.c_float),
                                 _ptr(rgb, C.c_uint8), _ptr(conf, C.c_float),
-                                _ptr(val, C.c_float), _ptr(faces, C.c_uint32), C.byref(nf))
+                                _ptr(val, C.c_float), _ptr(faces, C.c_uint32), C.byref(nf),
+                                VARIANTS[variant], _ptr(stats, C.c_int64),
+                                _ptr(vclass, C.c_int32))
     return {"xyz": xyz[:k], "normals": nrm[:k], "rgb": rgb[:k], "confidence": conf[:k],
-            "value": val[:k], "faces": faces[:nf.value]}
+            "value": val[:k], "faces": faces[:nf.value], "stats": stats, "vclass": vclass[:k]}
 
 
 def simplified(cams, dms, wnormals, images, mesh=False, aabb=None, max_vertices=-1,
-               max_error=-1.0):
+               max_error=-1.0, variant=None):
     """All views merged in view-list order (S13).  mesh=False: the point cloud
     (values, looked-up normals; the faces unless clipped); mesh=True: M2-M5."""
-    parts = [view(c, d, n, i, max_vertices, max_error)
+    parts = [view(c, d, n, i, max_vertices, max_error, variant)
              for c, d, n, i in zip(cams, dms, wnormals, images)]
-    out = {}
-    for key in ("xyz", "normals", "rgb", "confidence", "value"):
+    out = {"stats": sum(p["stats"] for p in parts)}
+    out["stats"][SSTAT_ROWS] = max(p["stats"][SSTAT_ROWS] for p in parts)
+    for key in ("xyz", "normals", "rgb", "confidence", "value", "vclass"):
         out[key] = np.concatenate([p[key] for p in parts])
     base = np.cumsum([0] + [len(p["xyz"]) for p in parts[:-1]])
     out["faces"] = np.concatenate([p["faces"] + np.uint32(b) for p, b in zip(parts, base)])
@@ -102,7 +116,7 @@ def simplified(cams, dms, wnormals, images, mesh=False, aabb=None, max_vertices=
         lo = np.asarray(aabb[0], np.float32)
         hi = np.asarray(aabb[1], np.float32)
         keep = ~((out["xyz"] < lo) | (out["xyz"] > hi)).any(axis=1)
-        out = {k: v[keep] for k, v in out.items() if k != "faces"}
+        out = {k: v[keep] for k, v in out.items() if k not in ("faces", "stats")}
     return out
 
 

@@ -274,43 +274,55 @@ struct Subdivision {
 // ----------------------------------------------------------- S8: rasteriser
 typedef std::vector<std::pair<int, int>> PixelList;
 
-void pixels_bottom_flat(P2 a, P2 b, P2 c, PixelList &out)
+void pixels_bottom_flat(P2 a, P2 b, P2 c, PixelList &out, int variant)
 {
     double const d1 = (c.x - a.x) / (c.y - a.y), d2 = (c.x - b.x) / (c.y - b.y);
     double x1 = c.x, x2 = c.x;
+    int r = 0;
     for (int y = (int)c.y; y > b.y; y--) {
         for (int x = (int)std::ceil(std::min(x1, x2)); x <= (int)std::floor(std::max(x1, x2)); ++x)
             out.emplace_back(x, y);
         x1 -= d1;
         x2 -= d2;
+        if (variant == V_S8_MULTIPLY) {
+            ++r;
+            x1 = c.x - r * d1;
+            x2 = c.x - r * d2;
+        }
     }
 }
 
-void pixels_top_flat(P2 a, P2 b, P2 c, PixelList &out)
+void pixels_top_flat(P2 a, P2 b, P2 c, PixelList &out, int variant)
 {
     double const d1 = (a.x - c.x) / (a.y - c.y), d2 = (a.x - b.x) / (a.y - b.y);
     double x1 = a.x, x2 = a.x;
+    int r = 0;
     for (int y = (int)a.y; y <= b.y; y++) {
         for (int x = (int)std::ceil(std::min(x1, x2)); x <= (int)std::floor(std::max(x1, x2)); ++x)
             out.emplace_back(x, y);
         x1 += d1;
         x2 += d2;
+        if (variant == V_S8_MULTIPLY) {
+            ++r;
+            x1 = a.x + r * d1;
+            x2 = a.x + r * d2;
+        }
     }
 }
 
-void pixels_for_triangle(P2 a, P2 b, P2 c, PixelList &out)
+void pixels_for_triangle(P2 a, P2 b, P2 c, PixelList &out, int variant = V_PINNED)
 {
     P2 v[3] = { a, b, c };
     std::stable_sort(v, v + 3, [](P2 const &l, P2 const &r) { return l.y < r.y; });
     if (v[1].y == v[2].y)
-        pixels_top_flat(v[0], v[1], v[2], out);
+        pixels_top_flat(v[0], v[1], v[2], out, variant);
     else if (v[0].y == v[1].y)
-        pixels_bottom_flat(v[0], v[1], v[2], out);
+        pixels_bottom_flat(v[0], v[1], v[2], out, variant);
     else {
         P2 m{ v[0].x + ((v[1].y - v[0].y) / (v[2].y - v[0].y)) * (v[2].x - v[0].x), v[1].y };
         m.x = v[0].x < v[1].x ? std::ceil(m.x) : std::floor(m.x);
-        pixels_top_flat(v[0], v[1], m, out);
-        pixels_bottom_flat(v[1], m, v[2], out);
+        pixels_top_flat(v[0], v[1], m, out, variant);
+        pixels_bottom_flat(v[1], m, v[2], out, variant);
     }
 }
 
@@ -331,6 +343,19 @@ struct Greedy {
     std::vector<ScanTriangle> tris;
     Heap heap;
     long long iterations = 0;
+    int variant = V_PINNED;
+    // what the loop met: iterations whose top key another triangle shares
+    // (S6), scans in which a later pixel equals the best distance (S7), no-op
+    // insertions (S5), the most rows a scanned triangle spans
+    long long tied_tops = 0, tied_scans = 0, noop_insertions = 0, max_rows = 0;
+
+    // S6: begin(), the earliest emplaced of the largest key
+    Heap::iterator top()
+    {
+        if (variant == V_S6_LATEST)
+            return std::prev(heap.upper_bound(heap.begin()->first));
+        return heap.begin();
+    }
 
     void load(std::size_t id)
     {
@@ -345,7 +370,14 @@ struct Greedy {
         ScanTriangle &t = tris[id];
         PixelList px;
         pixels_for_triangle(P2{ t.v[0].x, t.v[0].y }, P2{ t.v[1].x, t.v[1].y },
-            P2{ t.v[2].x, t.v[2].y }, px);
+            P2{ t.v[2].x, t.v[2].y }, px, variant);
+        if (!px.empty()) {
+            auto const rows = std::minmax_element(px.begin(), px.end(),
+                [](std::pair<int, int> const &l, std::pair<int, int> const &r) {
+                    return l.second < r.second;
+                });
+            max_rows = std::max(max_rows, (long long)(rows.second->second - rows.first->second + 1));
+        }
         // S7: the plane through the three vertices, unit normal
         double const ux = t.v[1].x - t.v[0].x, uy = t.v[1].y - t.v[0].y, uz = t.v[1].z - t.v[0].z;
         double const vx = t.v[2].x - t.v[0].x, vy = t.v[2].y - t.v[0].y, vz = t.v[2].z - t.v[0].z;
@@ -364,6 +396,7 @@ struct Greedy {
         double best = 0;
         P3 cand{ 0.0, 0.0, 0.0 };
         t.num_zero = 0;
+        bool tied = false;
         for (auto const &p : px) {
             if (p.first < 0 || p.first > w - 1 || p.second < 0 || p.second > h - 1)
                 continue;
@@ -373,12 +406,14 @@ struct Greedy {
                 continue;
             }
             double const dist = std::fabs(n[0] * p.first + n[1] * p.second + n[2] * depth + d);
-            if (dist > best) {
+            tied = tied || (dist == best && best > 0);
+            if (variant == V_S7_GE ? dist >= best : dist > best) {
                 best = dist;
                 cand = P3{ (double)p.first, (double)p.second, (double)depth };
             }
         }
         t.candidate = cand;
+        tied_scans += tied;
         heap.erase(t.at);
         t.at = heap.emplace(best, id);
     }
@@ -404,6 +439,8 @@ struct Greedy {
         // S3
         auto corner = [&](int x, int y, int px, int py) {
             float const d = dm[(std::size_t)py * w + px];
+            if (variant == V_S3_NO_FALLBACK)
+                return P3{ (double)x, (double)y, (double)d };
             return P3{ (double)x, (double)y, d > 0 ? (double)d : (double)dm_max };
         };
         sub.initialize(corner(-1, -1, 0, 0), corner(w, -1, w - 1, 0), corner(-1, h, 0, h - 1),
@@ -418,9 +455,12 @@ struct Greedy {
             if (heap.begin()->first < max_error)
                 break;
             ++iterations;
-            ScanTriangle const top = tris[heap.begin()->second];
-            sub.insert(top.candidate, heap.begin()->second);
+            Heap::iterator const first = top();
+            tied_tops += heap.count(first->first) > 1 && first->first > 0;
+            ScanTriangle const chosen = tris[first->second];
+            sub.insert(chosen.candidate, first->second);
             std::vector<std::size_t> const changed(sub.changed.begin(), sub.changed.end());
+            noop_insertions += changed.empty();
             for (std::size_t id : changed) {
                 if (id > tris.size() - 1) {
                     tris.emplace_back();
@@ -452,9 +492,36 @@ void delete_invalid_faces(std::vector<uint32_t> &f)
     f.resize(vi);
 }
 
+// What a view's run met (optional, += so that views add up): [0] faces S10's
+// zero-depth clause removes, [1] faces its edge-ratio clause removes, [2] / [3]
+// faces whose k-th triangle has exactly 4 / 5 zero depths, [4] faces whose
+// k-th triangle is not their own, [5] faces with an edge ratio in [0.1, 0.2),
+// [6] iterations that chose among equal keys, [7] scans with equal best
+// distances, [8] no-op insertions, [9] the most rows of a scanned triangle
+// (a maximum), [10] iterations, [11] maps with a valid depth
+enum { SSTAT_ZERO = 0, SSTAT_RATIO = 1, SSTAT_FOUR = 2, SSTAT_FIVE = 3, SSTAT_OTHER = 4,
+    SSTAT_NEAR = 5, SSTAT_TIED_TOPS = 6, SSTAT_TIED_SCANS = 7, SSTAT_NOOP = 8, SSTAT_ROWS = 9,
+    SSTAT_ITERATIONS = 10, SSTAT_VALID = 11, SSTAT_COUNT = 12 };
+
+void loop_stats(Greedy const &g, int64_t *stats)
+{
+    if (stats == nullptr)
+        return;
+    stats[SSTAT_TIED_TOPS] += g.tied_tops;
+    stats[SSTAT_TIED_SCANS] += g.tied_scans;
+    stats[SSTAT_NOOP] += g.noop_insertions;
+    stats[SSTAT_ROWS] = std::max<int64_t>(stats[SSTAT_ROWS], g.max_rows);
+    stats[SSTAT_ITERATIONS] += g.iterations;
+    bool valid = false;
+    for (std::size_t i = 0; i < (std::size_t)g.w * g.h; ++i)
+        valid = valid || g.dm[i] > 0;
+    stats[SSTAT_VALID] += valid;
+}
+
 // S9-S12 for one view -> world positions, colours (bytes), faces
 void clean_up(Greedy const &g, Camera const &cam, const uint8_t *image, int channels,
-    std::vector<Vec3> &pos, std::vector<uint8_t> &rgb, std::vector<uint32_t> &faces)
+    std::vector<Vec3> &pos, std::vector<uint8_t> &rgb, std::vector<uint32_t> &faces,
+    int variant = V_PINNED, int64_t *stats = nullptr)
 {
     Subdivision &sub = const_cast<Subdivision &>(g.sub);
     // S9: float vertices, corners deleted (faces that use one go, ids shift by 4)
@@ -462,6 +529,7 @@ void clean_up(Greedy const &g, Camera const &cam, const uint8_t *image, int chan
     for (std::size_t i = 4; i < sub.verts.size(); ++i)
         v.push_back(Vec3{ { (float)sub.verts[i].x, (float)sub.verts[i].y, (float)sub.verts[i].z } });
     faces.clear();
+    std::vector<std::size_t> own;   // the triangle a face came from
     for (std::size_t t = 0; t < sub.tri_start.size(); ++t) {
         uint32_t ids[3];
         sub.triangle(t, ids);
@@ -469,6 +537,7 @@ void clean_up(Greedy const &g, Camera const &cam, const uint8_t *image, int chan
             continue;
         for (int k = 0; k < 3; ++k)
             faces.push_back(ids[k] - 4);
+        own.push_back(t);
     }
     rgb.assign(3 * v.size(), 0);
     for (std::size_t i = 0; i < v.size(); ++i) {
@@ -503,7 +572,17 @@ void clean_up(Greedy const &g, Camera const &cam, const uint8_t *image, int chan
         float const e1 = edge(faces[f], faces[f + 1]), e2 = edge(faces[f], faces[f + 2]),
             e3 = edge(faces[f + 1], faces[f + 2]);
         float const lo = std::min(e1, std::min(e2, e3)), hi = std::max(e1, std::max(e2, e3));
-        if (g.tris[f / 3].num_zero > 4 || lo / hi < 0.1)
+        int const zeros = g.tris[variant == V_S10_OWN_TRIANGLE ? own[f / 3] : f / 3].num_zero;
+        bool const holes = variant == V_S10_GE4 ? zeros >= 4 : zeros > 4;
+        if (stats != nullptr) {
+            stats[SSTAT_ZERO] += holes;
+            stats[SSTAT_RATIO] += lo / hi < 0.1;
+            stats[SSTAT_FOUR] += zeros == 4;
+            stats[SSTAT_FIVE] += zeros == 5;
+            stats[SSTAT_OTHER] += own[f / 3] != f / 3;
+            stats[SSTAT_NEAR] += lo / hi >= 0.1 && lo / hi < 0.2;
+        }
+        if (holes || lo / hi < 0.1)
             faces[f] = faces[f + 1] = faces[f + 2] = 0;
     }
     delete_invalid_faces(faces);   // S11
@@ -531,16 +610,20 @@ void clean_up(Greedy const &g, Camera const &cam, const uint8_t *image, int chan
 } // namespace
 
 // S1-S8 on one depth map.  verts: (budget + 4) * 3 doubles, tris: (2 budget + 2)
-// * 3 ids, nzero: 2 budget + 2.  -> loop iterations run.
+// * 3 ids, nzero: 2 budget + 2; variant: 0, or the one rule of `Variant` to
+// get wrong; stats: optional, SSTAT_COUNT entries.  -> loop iterations run.
 extern "C" int64_t
 simplify_ref_triangulate(int w, int h, const float *dm, int max_vertices, double max_error,
-    double *verts, int64_t *n_verts, uint32_t *tris, int32_t *nzero, int64_t *n_tris)
+    double *verts, int64_t *n_verts, uint32_t *tris, int32_t *nzero, int64_t *n_tris,
+    int variant, int64_t *stats)
 {
     Greedy g;
     g.w = w;
     g.h = h;
     g.dm = dm;
+    g.variant = variant;
     g.run(max_vertices, max_error);
+    loop_stats(g, stats);
     for (std::size_t i = 0; i < g.sub.verts.size(); ++i) {
         verts[3 * i] = g.sub.verts[i].x;
         verts[3 * i + 1] = g.sub.verts[i].y;
@@ -557,27 +640,31 @@ simplify_ref_triangulate(int w, int h, const float *dm, int max_vertices, double
 
 // One view of generate_mesh with Options::simplify (S1-S13 up to the merge).
 // Outputs hold up to w * h / 40 + 4 (or max_vertices + 4) vertices and twice as
-// many faces.  -> number of vertices.
+// many faces; variant and stats as simplify_ref_triangulate; vclass (optional)
+// gets MeshInfo's class per vertex.  -> number of vertices.
 extern "C" int64_t
 simplify_ref_view(int w, int h, float flen, const float *rot, const float *trans,
     const float *dm, const float *wnormals, const uint8_t *image, int channels,
     int max_vertices, double max_error, float *xyz, float *nrm, uint8_t *rgb_out,
-    float *conf, float *val, uint32_t *faces_out, int64_t *n_faces)
+    float *conf, float *val, uint32_t *faces_out, int64_t *n_faces, int variant,
+    int64_t *stats, int32_t *vclass)
 {
     Camera const cam = make_camera(w, h, flen, rot, trans);
     Greedy g;
     g.w = w;
     g.h = h;
     g.dm = dm;
+    g.variant = variant;
     g.run(max_vertices, max_error);
+    loop_stats(g, stats);
     std::vector<Vec3> verts;
     std::vector<uint8_t> rgb;
     std::vector<uint32_t> faces;
-    clean_up(g, cam, image, channels, verts, rgb, faces);
+    clean_up(g, cam, image, channels, verts, rgb, faces, variant, stats);
     std::size_t const nv = verts.size();
-    std::vector<VertexInfo> const info = mesh_info(nv, faces);
+    std::vector<VertexInfo> const info = mesh_info(nv, faces, variant);
     std::vector<float> confs;
-    mesh_confidences(info, 4, confs);
+    mesh_confidences(info, 4, confs, variant);
     for (std::size_t j = 0; j < nv; ++j) {
         float s = 0.0f;
         for (uint32_t k : info[j].verts) {
@@ -590,6 +677,8 @@ simplify_ref_view(int w, int h, float flen, const float *rot, const float *trans
         s *= 2.0f;
         val[j] = s;
         conf[j] = confs[j];
+        if (vclass != nullptr)
+            vclass[j] = info[j].vclass;
         for (int i = 0; i < 3; ++i) {
             xyz[3 * j + i] = verts[j][i];
             rgb_out[3 * j + i] = rgb[3 * j + i];
