@@ -1578,6 +1578,134 @@ int smvs_tsdf_volume_upload(smvs_tsdf_volume *volume, const float *S, const uint
 int smvs_tsdf_volume_reset(smvs_tsdf_volume *volume);
 void smvs_tsdf_volume_release(smvs_tsdf_volume *volume);
 
+/* A persistent volume of smvs_tsdf_fuse_sparse (opt-in; DESIGN.md section
+ * 9.14): the brick-sparse sums kept on the device between calls, so that a
+ * grid of up to 4096 voxels per side is fused batch by batch, checkpointed and
+ * extracted any number of times.  This comment is the definition on top of the
+ * comments of smvs_tsdf_fuse (Inputs, Field, Vertices, Faces),
+ * smvs_tsdf_fuse_sparse (brick, seed, the dilation called "allocated" there,
+ * the order) and smvs_tsdf_volume_create (continuing the sums), which it does
+ * not repeat; tests/tsdf_sparse_volume_ref.py restates it on top of their
+ * restatements.
+ *
+ * Which bricks exist depends on all views, and a brick that gets its storage
+ * after some views have passed has missed their free-space terms.  So the
+ * table is a state of its own, fixed by mark, and growth reports what it cost.
+ *
+ * State, owned on the device.  One seed byte per brick of the grid; the table
+ * brick -> slot and the list slot -> brick, the slots always in linear brick
+ * order over the bricks that have storage; per slot birth, the stored view
+ * count at the start of the integrate that gave the brick its slot; per voxel
+ * of a slot, slot-major (slot * 256 + the voxel's index in the brick), S
+ * (float), W (uint32) and (R, G, B, C) (4 x uint32): 24 bytes per voxel, 6144
+ * per slot; and the number of views integrated so far.  F and the vertex ids
+ * are not state.  create: no seed, no slot, count 0.  trunc <= 0 means 3.0f *
+ * voxel_size, fixed at create.  max_bricks <= 0 means 1 << 20.
+ *
+ * mark(list, cut_surfaces, cull).  The list is prepared as
+ * smvs_tsdf_fuse_sparse prepares its list, and the seed bytes are OR-ed with
+ * that entry's seed rule on this list: a brick is a seed when it holds a voxel
+ * where some view of the list passes steps 1-6 with sdf <= trunc.  With cull
+ * the cull of smvs_tsdf_fuse_sparse_opts runs in front and decides nothing.
+ * No sum is touched and no slot is given; images are not read and may be NULL.
+ * The dilation (every seed brick and its up to 26 neighbours) of the would-be
+ * seed set is counted before the OR is committed: more than max_bricks is
+ * SMVS_ERR_NOMEM, the error text names the count needed, nothing changes.
+ *
+ * integrate(list, cut_surfaces, grow, cull).  The list is prepared once.  With
+ * grow != 0 the list is marked first, under the same budget rule, checked
+ * before anything is committed.  Then every brick of the dilation of the seeds
+ * that has no slot gets one: the table is rebuilt in linear brick order, the
+ * sums move to their new slots, new bricks start at zero with birth = the
+ * stored count.  Then steps 1-8 of Field run for the list's views in list
+ * order on every brick that has a slot, continuing the stored sums term by
+ * term as smvs_tsdf_volume_integrate does: a voxel no view of the list
+ * contributes to is neither read nor written.  The count grows by n_views.
+ *
+ * So a brick holds Field's sums over the views of index >= its birth, in list
+ * order from zero.  If every mark precedes the first integrate (all birth = 0)
+ * the state on the bricks with slots is the dense persistent volume's state
+ * there, and with cut_surfaces == 0, or with one batch, the extracted mesh,
+ * cells, brick_state, tsdf and weight are smvs_tsdf_fuse_sparse's over the
+ * concatenated list, to the bit, for every split into consecutive batches.
+ * With the cut on, the cut acts within a batch, as for smvs_tsdf_volume.  A
+ * brick with birth > 0 is LATE: stats.late_bricks == 0 is how a caller learns
+ * that the identity holds.
+ *
+ * Slots that the one-shot would not have (marks of views that are never
+ * integrated) do not change the mesh: an inside corner (F < 0) needs a view
+ * with -trunc <= sdf < 0 there, which makes its brick a seed of the integrated
+ * views; and every cell that holds a seed voxel lies within the seed brick and
+ * its 26 neighbours.  Outside the one-shot's bricks F is >= 0 or NaN, and the
+ * cells, vertices and faces are the one-shot's.
+ *
+ * extract(min_weight).  F = S / (float)W where W >= min_weight (<= 0 means 1),
+ * else NaN, on the bricks with slots, NaN elsewhere; then Vertices and Faces
+ * of smvs_tsdf_fuse_sparse in (slot, index in brick) order, n_views in the
+ * confidence being the stored count.  The handle (smvs_tsdf_vertex_cells
+ * answers it), tsdf and weight (either may be NULL; only for grids of at most
+ * 2^27 voxels) as smvs_tsdf_fuse_sparse gives them; brick_state (may be NULL):
+ * 0 / 1 / 2 from the seeds as marked.  Extract changes no state, and marks not
+ * yet followed by an integrate do not affect the mesh, tsdf or weight.
+ *
+ * info.  stats: bricks of the grid, seed bricks, allocated_bricks (with
+ * slots), pending_bricks (in the dilation, without a slot), late_bricks,
+ * state_bytes (6144 per slot) and the view count.  Each pointer may be NULL.
+ *
+ * download / upload are the checkpoint: brick_state (bricks bytes), list and
+ * birth (allocated_bricks values each), S and W (256 per slot), rgbc (1024 per
+ * slot) and the count.  download's pointers may each be NULL.  upload checks
+ * before any device call: brick_state holds 0, 1, 2 (only 2 is read: the
+ * seeds); n_slots is 0 .. max_bricks, n_views 0 .. 2^24, the seeds' dilation
+ * has at most max_bricks bricks; the list is strictly ascending, inside the
+ * grid and inside the dilation of the uploaded seeds; no birth is above
+ * n_views.  A state uploaded into a fresh volume of the same options continues
+ * to the same bits.  reset: no seed, no slot, count 0.
+ *
+ * Refused with SMVS_ERR_INVALID before any device call: a NULL volume; at
+ * create what smvs_tsdf_fuse_sparse refuses for its grid (a dim < 2 or > 4096,
+ * more than 2^28 bricks, max_bricks > 2^23, voxel_size, origin, trunc); per
+ * mark and integrate what smvs_tsdf_fuse refuses for its views (mark needs no
+ * image), and a stored count that would pass 2^24; at extract tsdf or weight
+ * on a grid of more than 2^27 voxels.  A refused or failed call leaves the
+ * state as it was (a failed upload: undefined, reset or upload again).  During
+ * a re-slot the old and the new sums exist side by side: 6144 bytes times (old
+ * + new slots) at the peak.  Calls on one volume are not to overlap; different
+ * volumes are independent. */
+typedef struct {
+    float origin[3];      /* the low corner of voxel (0, 0, 0) */
+    float voxel_size;
+    int dims[3];
+    float trunc;
+    int64_t max_bricks;
+} smvs_tsdf_sparse_volume_options;
+
+typedef struct {
+    int64_t bricks, seed_bricks, allocated_bricks, pending_bricks, late_bricks, state_bytes,
+        n_views;
+} smvs_tsdf_sparse_volume_stats;
+
+typedef struct smvs_tsdf_sparse_volume smvs_tsdf_sparse_volume;
+
+int smvs_tsdf_sparse_volume_create(int device, const smvs_tsdf_sparse_volume_options *options,
+    smvs_tsdf_sparse_volume **volume);
+int smvs_tsdf_sparse_volume_mark(smvs_tsdf_sparse_volume *volume, const smvs_point_view *views,
+    int n_views, int cut_surfaces, int cull);
+int smvs_tsdf_sparse_volume_integrate(smvs_tsdf_sparse_volume *volume,
+    const smvs_point_view *views, int n_views, int cut_surfaces, int grow, int cull);
+int smvs_tsdf_sparse_volume_extract(const smvs_tsdf_sparse_volume *volume, int min_weight,
+    uint8_t *brick_state, float *tsdf, uint32_t *weight, smvs_points **handle,
+    int64_t *n_vertices, int64_t *n_faces);
+int smvs_tsdf_sparse_volume_info(const smvs_tsdf_sparse_volume *volume,
+    smvs_tsdf_sparse_volume_options *options, smvs_tsdf_sparse_volume_stats *stats, int *device);
+int smvs_tsdf_sparse_volume_download(const smvs_tsdf_sparse_volume *volume, uint8_t *brick_state,
+    uint32_t *list, uint32_t *birth, float *S, uint32_t *W, uint32_t *rgbc);
+int smvs_tsdf_sparse_volume_upload(smvs_tsdf_sparse_volume *volume, const uint8_t *brick_state,
+    const uint32_t *list, const uint32_t *birth, int64_t n_slots, const float *S,
+    const uint32_t *W, const uint32_t *rgbc, int64_t n_views);
+int smvs_tsdf_sparse_volume_reset(smvs_tsdf_sparse_volume *volume);
+void smvs_tsdf_sparse_volume_release(smvs_tsdf_sparse_volume *volume);
+
 /* Cleaning a triangle mesh (not in the reference, whose documented pipeline
  * ends with MVE's `meshclean -p10`; opt-in): a cut on
  * the vertex confidences, then the removal of small connected components and

@@ -9,10 +9,12 @@ from .device import (ViewContext, device_count, sgm_run, bilateral_upsample,  # 
                      sgm_fold_costs, sgm_filter_speckles, sgm_photo_check, sgm_plane_refine, cut_depth_maps, generate_points,
                      generate_mesh,
                      generate_simplified, simplify_triangulate, fuse_tsdf, tsdf_bounds,
-                     tsdf_brick_cull, tsdf_depth_pyramid, clean_mesh, TsdfVolume)
+                     tsdf_brick_cull, tsdf_depth_pyramid, clean_mesh, TsdfVolume,
+                     SparseTsdfVolume)
 
 __all__ = ["ViewContext", "device_count", "sgm_run", "bilateral_upsample",
            "sgm_depth_for_view", "sgm_check_merge", "sgm_sweep_for_view", "sgm_fold_costs", "sgm_filter_speckles", "sgm_photo_check", "sgm_plane_refine",
            "cut_depth_maps", "generate_points", "generate_mesh",
            "generate_simplified", "simplify_triangulate", "fuse_tsdf", "tsdf_bounds",
-           "tsdf_brick_cull", "tsdf_depth_pyramid", "clean_mesh", "TsdfVolume"]
+           "tsdf_brick_cull", "tsdf_depth_pyramid", "clean_mesh", "TsdfVolume",
+           "SparseTsdfVolume"]

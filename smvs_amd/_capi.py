@@ -83,6 +83,21 @@ class TsdfVolumeOptions(C.Structure):
                 ("trunc", C.c_float)]
 
 
+class TsdfSparseVolumeOptions(C.Structure):
+    """smvs_tsdf_sparse_volume_options of include/smvs_hip.h."""
+    _fields_ = TsdfVolumeOptions._fields_ + [("max_bricks", C.c_int64)]
+
+
+class TsdfSparseVolumeStats(C.Structure):
+    """smvs_tsdf_sparse_volume_stats of include/smvs_hip.h."""
+    _fields_ = [("bricks", C.c_int64), ("seed_bricks", C.c_int64),
+                ("allocated_bricks", C.c_int64), ("pending_bricks", C.c_int64),
+                ("late_bricks", C.c_int64), ("state_bytes", C.c_int64), ("n_views", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class MeshCleanOptions(C.Structure):
     """smvs_mesh_clean_options of include/smvs_hip.h."""
     _fields_ = [("threshold", C.c_float), ("percentile", C.c_float),

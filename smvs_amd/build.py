@@ -12,7 +12,7 @@ SOURCES = ["ctx.hip", "gn_construct.hip", "cg.hip", "cg_resident.hip", "reactiva
            "scale.hip", "topology.hip", "topo_zbuffer.hip", "topo_visibility.hip", "topo_mse.hip",
            "topo_cut.hip", "mesh_cut.hip", "export_common.hip", "mesh.hip", "simplify.hip", "pool.hip", "surface.hip",
            "surface_planes.hip", "undistort.hip", "tsdf.hip", "tsdf_sparse.hip", "tsdf_cull.hip",
-           "tsdf_volume.hip",
+           "tsdf_volume.hip", "tsdf_volume_sparse.hip",
            "mesh_clean.hip"]
 # HIP-free units of the library: the host compiler builds them
 HOST_CC_SOURCES = ["tile_budget.cc"]

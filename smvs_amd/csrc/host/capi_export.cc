@@ -216,6 +216,28 @@ smvs_host_generate_fused_batched(const char *scene_dir,
 }
 
 extern "C" int
+smvs_host_generate_fused_sparse_batched(const char *scene_dir,
+    const smvs_host_point_cloud_settings *o, const smvs_host_fused_sparse_batched_settings *f,
+    const int *view_ids, int n_view_ids, char *ply_path, int ply_path_capacity,
+    int64_t *n_vertices, int64_t *n_faces, smvs_mesh_clean_stats *stats)
+{
+    return generate_fused({ scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
+        n_vertices, n_faces }, "smvs_host_generate_fused_sparse_batched", f,
+        [f](MeshGenerator::FusedOptions& fo) {
+            fo.sparse = f->sparse != 0;
+            fo.max_bricks = f->max_bricks;
+            fo.cull = f->cull != 0;
+            fo.clean = f->clean != 0;
+            fo.clean_threshold = f->threshold;
+            fo.clean_percentile = f->percentile;
+            fo.clean_component_size = f->component_size;
+            fo.clean_keep_unreferenced = f->keep_unreferenced != 0;
+            fo.batch_views = f->batch_views;
+            fo.sparse_batch_views = f->sparse_batch_views;
+        }, stats);
+}
+
+extern "C" int
 smvs_host_save_ply_points(const char *path, const float *xyz, const float *normals,
     const uint8_t *rgb, const float *confidence, const float *value, int64_t n)
 {

@@ -664,6 +664,38 @@ int smvs_host_generate_fused_batched(const char *scene_dir,
     const smvs_host_fused_batched_settings *fused, const int *view_ids, int n_view_ids,
     char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces,
     smvs_mesh_clean_stats *stats);
+/* The brick-sparse fused mesh with only sparse_batch_views consecutive scene
+ * views loaded at a time: three passes over the scene
+ * -- the bounds folded batch by batch (skipped with use_aabb), every batch
+ * marked (with cull != 0 the brick cull in front), every batch integrated
+ * without growth -- into a persistent brick-sparse volume
+ * (smvs_tsdf_sparse_volume), and the surface extracted once.  Without the cut
+ * (cut_surface == 0) the file is smvs_host_generate_fused_sparse's byte for
+ * byte; the cut, when on, acts within a batch.  The record's first thirteen
+ * members are the batched entry's, and mean what they mean there (batch_views
+ * > 0 with sparse != 0 stays refused); sparse_batch_views == 0 is that entry,
+ * sparse_batch_views > 0 needs sparse != 0, and < 0 is refused. */
+typedef struct {
+    float voxel_size;
+    int resolution;
+    float trunc;
+    int min_weight;
+    int64_t max_bricks;
+    int cull;
+    int sparse;
+    float threshold;
+    float percentile;
+    int component_size;
+    int keep_unreferenced;
+    int clean;
+    int batch_views;
+    int sparse_batch_views;
+} smvs_host_fused_sparse_batched_settings;
+int smvs_host_generate_fused_sparse_batched(const char *scene_dir,
+    const smvs_host_point_cloud_settings *settings,
+    const smvs_host_fused_sparse_batched_settings *fused, const int *view_ids, int n_view_ids,
+    char *ply_path, int ply_path_capacity, int64_t *n_vertices, int64_t *n_faces,
+    smvs_mesh_clean_stats *stats);
 /* save_ply_mesh: the PLY writer of the triangle mesh from SoA
  * buffers (xyz, normals n*3 floats; rgb n*3 bytes; confidence n floats;
  * faces m*3 vertex ids < n). */

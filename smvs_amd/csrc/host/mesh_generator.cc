@@ -293,6 +293,12 @@ struct VolumeHolder
     ~VolumeHolder() { smvs_tsdf_volume_release(v); }
 };
 
+struct SparseVolumeHolder
+{
+    smvs_tsdf_sparse_volume* v = nullptr;
+    ~SparseVolumeHolder() { smvs_tsdf_sparse_volume_release(v); }
+};
+
 } // namespace
 
 TriangleMesh::Ptr
@@ -304,6 +310,11 @@ MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
         throw std::invalid_argument("generate_fused: batch_views must not be negative");
     if (fused.batch_views > 0)
         return generate_fused_batched(inputviews, image_name, dm_name, fused, clean_stats);
+    if (fused.sparse_batch_views < 0)
+        throw std::invalid_argument("generate_fused: sparse_batch_views must not be negative");
+    if (fused.sparse_batch_views > 0)
+        return generate_fused_sparse_batched(inputviews, image_name, dm_name, fused,
+            clean_stats);
     Inputs in;
     load_views(inputviews, image_name, dm_name, in);
     if (in.views.empty())
@@ -421,6 +432,89 @@ MeshGenerator::generate_fused_batched(std::vector<SceneView> const& inputviews,
     int64_t nv = 0, nf = 0;
     check_status(smvs_tsdf_volume_extract(volume.v, to.min_weight, nullptr, nullptr, &handle,
         &nv, &nf), "smvs_tsdf_volume_extract");
+    return fused_result(opts, fused, handle, nv, nf, clean_stats);
+}
+
+// generate_fused with FusedOptions::sparse_batch_views: one batch of
+// consecutive scene views is loaded at a time, three times over -- for the
+// bounds, for the marks and for the integration into a persistent brick-sparse
+// volume (smvs_tsdf_sparse_volume).  Every mark
+// precedes the first integrate and nothing grows, so no brick is late; the
+// cut, when on, acts within a batch.
+TriangleMesh::Ptr
+MeshGenerator::generate_fused_sparse_batched(std::vector<SceneView> const& inputviews,
+    std::string const& image_name, std::string const& dm_name, FusedOptions const& fused,
+    smvs_mesh_clean_stats* clean_stats)
+{
+    if (!fused.sparse)
+        throw std::invalid_argument("generate_fused: sparse_batch_views belongs to sparse");
+    if (fused.voxel_size <= 0.0f && fused.resolution < 8)
+        throw std::invalid_argument("generate_fused: resolution must be at least 8");
+    if (fused.voxel_size <= 0.0f && fused.resolution > 4096)
+        throw std::invalid_argument("generate_fused: resolution must be at most 4096");
+    std::size_t const step = (std::size_t)fused.sparse_batch_views;
+    int const cut = opts.cut_surfaces ? 1 : 0;
+    // calls `use` with the loaded views of every batch that has one
+    auto for_batches = [&](auto use) {
+        for (std::size_t at = 0; at < inputviews.size(); at += step) {
+            std::vector<SceneView> const batch(inputviews.begin() + at,
+                inputviews.begin() + std::min(inputviews.size(), at + step));
+            Inputs in;
+            load_views(batch, image_name, dm_name, in);
+            if (!in.views.empty())
+                use(in);
+        }
+    };
+    float lo[3], hi[3];
+    std::size_t usable = 0;
+    if (opts.use_aabb) {
+        std::copy(opts.aabb_min, opts.aabb_min + 3, lo);
+        std::copy(opts.aabb_max, opts.aabb_max + 3, hi);
+    } else {
+        // the union's box: min and max are exact, so the order does not matter
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = INFINITY;
+            hi[a] = -INFINITY;
+        }
+        for_batches([&](Inputs& in) {
+            float blo[3], bhi[3];
+            check_status(smvs_tsdf_bounds(opts.device, in.pv.data(), (int)in.pv.size(), cut,
+                blo, bhi), "smvs_tsdf_bounds");
+            usable += in.pv.size();
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = std::fmin(lo[a], blo[a]);
+                hi[a] = std::fmax(hi[a], bhi[a]);
+            }
+        });
+        if (usable == 0)
+            return TriangleMesh::Ptr(new TriangleMesh);
+    }
+    smvs_tsdf_options const to = fused_grid(opts, fused, lo, hi);
+    smvs_tsdf_sparse_volume_options vo;
+    std::copy(to.origin, to.origin + 3, vo.origin);
+    std::copy(to.dims, to.dims + 3, vo.dims);
+    vo.voxel_size = to.voxel_size;
+    vo.trunc = to.trunc;
+    vo.max_bricks = fused.max_bricks;
+    SparseVolumeHolder volume;
+    check_status(smvs_tsdf_sparse_volume_create(opts.device, &vo, &volume.v),
+        "smvs_tsdf_sparse_volume_create");
+    usable = 0;
+    for_batches([&](Inputs& in) {
+        check_status(smvs_tsdf_sparse_volume_mark(volume.v, in.pv.data(), (int)in.pv.size(), cut,
+            fused.cull ? 1 : 0), "smvs_tsdf_sparse_volume_mark");
+        usable += in.pv.size();
+    });
+    if (usable == 0)
+        return TriangleMesh::Ptr(new TriangleMesh);
+    for_batches([&](Inputs& in) {
+        check_status(smvs_tsdf_sparse_volume_integrate(volume.v, in.pv.data(),
+            (int)in.pv.size(), cut, 0, 0), "smvs_tsdf_sparse_volume_integrate");
+    });
+    smvs_points* handle = nullptr;
+    int64_t nv = 0, nf = 0;
+    check_status(smvs_tsdf_sparse_volume_extract(volume.v, to.min_weight, nullptr, nullptr,
+        nullptr, &handle, &nv, &nf), "smvs_tsdf_sparse_volume_extract");
     return fused_result(opts, fused, handle, nv, nf, clean_stats);
 }
 

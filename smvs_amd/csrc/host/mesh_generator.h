@@ -108,6 +108,14 @@ public:
         // the mesh is the one-shot's to the bit; the cut, when on, acts
         // within a batch.  0: off, the calls made are the ones above
         int batch_views = 0;
+        // > 0 (sparse only): batch_views for the brick-sparse volume.  Three
+        // passes with one batch loaded at a time -- the bounds (skipped with
+        // use_aabb), the marks, the integration without growth -- into a
+        // persistent brick-sparse volume (smvs_tsdf_sparse_volume, section
+        // 9.14); cull puts the brick cull in front of the marks.  Without the
+        // cut the mesh is the one-shot sparse one to the bit.  0: off, the
+        // calls made are the ones above
+        int sparse_batch_views = 0;
     };
     TriangleMesh::Ptr generate_fused(std::vector<SceneView> const& views,
         std::string const& image_name, std::string const& dm_name,
@@ -121,6 +129,9 @@ private:
         std::string const& image_name, std::string const& dm_name, Inputs& in) const;
     void save_cut_maps(Inputs const& in) const;
     TriangleMesh::Ptr generate_fused_batched(std::vector<SceneView> const& views,
+        std::string const& image_name, std::string const& dm_name,
+        FusedOptions const& fused, smvs_mesh_clean_stats* clean_stats);
+    TriangleMesh::Ptr generate_fused_sparse_batched(std::vector<SceneView> const& views,
         std::string const& image_name, std::string const& dm_name,
         FusedOptions const& fused, smvs_mesh_clean_stats* clean_stats);
 

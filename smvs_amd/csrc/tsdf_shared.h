@@ -1,7 +1,8 @@
 // Pieces of the volumetric fusion that tsdf.hip (the dense volume),
 // tsdf_sparse.hip (the brick-sparse volume), tsdf_cull.hip (the brick cull
-// in front of its seed pass) and tsdf_volume.hip (the persistent dense
-// volume) share: the grid record, the brick grid, the
+// in front of its seed pass), tsdf_volume.hip (the persistent dense volume)
+// and tsdf_volume_sparse.hip (the persistent brick-sparse volume) share: the
+// grid record, the brick grid, the
 // per-element device functions of the definition in include/smvs_hip.h (voxel
 // centre, the projection steps 1-6, the cell / edge / quad rules, the block
 // scan, the vertex attribute arithmetic) and the host pieces of the entries.
@@ -411,6 +412,37 @@ void launch_seed_list(hipStream_t stream, ViewSlab const &s, TsdfGrid const &G,
     TsdfBricks const &B, const uint32_t *list, size_t n, uint8_t *seed);
 // the entry behind smvs_tsdf_fuse_sparse and smvs_tsdf_fuse_sparse_opts (tsdf_sparse.hip)
 TsdfBricks brick_grid(TsdfGrid const &G, size_t *n_bricks);
+
+// tsdf_sparse.hip: the passes of smvs_tsdf_fuse_sparse_opts that the persistent
+// brick-sparse volume (tsdf_volume_sparse.hip) runs as well.
+// After launch_depth: the list's seed bytes (2 / 0 per brick).  pyr == nullptr:
+// the exact test on every brick.  Else the cull in front (launch_pyramids,
+// launch_cull, the candidates' list into cand_list, the exact test on the list);
+// cand, cand_list (room for B.n entries), counts (one per 256 bricks) and tiles
+// (their scan's) are work arrays.  brick_candidate (host, may be null) and
+// *n_tested as smvs_tsdf_fuse_sparse_opts gives them.
+int launch_seeds(Workspace &ws, char *slab, ViewSlab const &s, int n_views, PyramidSlab *pyr,
+    TsdfGrid const &G, TsdfBricks const &B, uint8_t *cand, uint32_t *cand_list,
+    unsigned long long *counts, unsigned long long *tiles, uint8_t *seed,
+    uint8_t *brick_candidate, size_t *n_tested);
+// state[brick] = 2 seed, 1 a neighbour of a seed, 0 neither; counts[block of 256
+// bricks] = allocated | seeds << 32
+void launch_dilate(hipStream_t stream, const uint8_t *seed, TsdfBricks const &B, uint8_t *state,
+    unsigned long long *counts);
+// counts scanned: brick -> slot (or -1) and slot -> brick, in linear brick order
+void launch_table(hipStream_t stream, const uint8_t *state, TsdfBricks const &B,
+    const unsigned long long *counts, int32_t *table, uint32_t *list);
+// The extraction half of smvs_tsdf_fuse_sparse_opts, which
+// smvs_tsdf_sparse_volume_extract runs as well: classify, scan, vertices, faces
+// and fill on a slot-major field, weights and colour sums, a table and a list
+// (slots in linear brick order) that are on the device, then tsdf / weight
+// (host, either may be null) as the whole grid.  Work arrays go to slot 3 of
+// the workspace, vertices and faces to slot 1.  G.n_views is the confidence's
+// view count; `who` heads the error text.  On failure no handle is left behind.
+int extract_sparse_surface(Workspace &ws, const char *who, TsdfGrid const &G,
+    TsdfBricks const &B, size_t n_alloc, const float *d_tsdf, const uint32_t *d_weight,
+    const uint4 *d_colour, const int32_t *d_table, const uint32_t *d_list, float *tsdf,
+    uint32_t *weight, smvs_points **handle);
 
 } // namespace tsdf_host
 

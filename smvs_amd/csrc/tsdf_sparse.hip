@@ -325,6 +325,179 @@ smvs_hip::tsdf_host::brick_grid(TsdfGrid const &G, size_t *n_bricks)
     return B;
 }
 
+int
+smvs_hip::tsdf_host::launch_seeds(Workspace &ws, char *slab, ViewSlab const &s, int n_views,
+    PyramidSlab *pyr, TsdfGrid const &G, TsdfBricks const &B, uint8_t *d_cand,
+    uint32_t *d_cand_list, unsigned long long *d_counts, unsigned long long *d_tiles,
+    uint8_t *d_seed, uint8_t *brick_candidate, size_t *n_tested)
+{
+    hipStream_t const stream = ws.stream;
+    size_t const n_bricks = B.n;
+    int rc;
+    *n_tested = n_bricks;
+    if (pyr != nullptr) {
+        // the candidates (section 9.10), their list in the table's place, and
+        // the exact test on the list alone; the counts are the dilation's, not
+        // yet in use
+        unsigned const brick_blocks = (unsigned)((n_bricks + 255) / 256);
+        size_t const brick_tiles = ((size_t)brick_blocks + SCAN_TILE - 1) / SCAN_TILE;
+        if ((rc = launch_pyramids(ws, slab, s, n_views, *pyr)))
+            return rc;
+        launch_cull(stream, s, *pyr, G, B, d_cand, d_counts);
+        SMVS_HIP_CHECK(hipGetLastError());
+        if ((rc = exclusive_scan(stream, d_counts, brick_blocks, d_tiles)))
+            return rc;
+        unsigned long long total = 0;
+        if ((rc = ws.download(&total, d_tiles + brick_tiles, sizeof(total))))
+            return rc;
+        *n_tested = (size_t)total;
+        if (brick_candidate != nullptr && (rc = ws.download(brick_candidate, d_cand, n_bricks)))
+            return rc;
+        SMVS_HIP_CHECK(hipMemsetAsync(d_seed, 0, n_bricks, stream));
+        launch_candidate_list(stream, d_cand, B, d_counts, d_cand_list);
+        launch_seed_list(stream, s, G, B, d_cand_list, *n_tested, d_seed);
+    } else {
+        if (brick_candidate != nullptr)
+            std::memset(brick_candidate, 1, n_bricks);
+        // (a launch's x extent in threads is 32 bits: the bricks go over x and y)
+        unsigned const seed_x = n_bricks < SEED_GRID_X ? (unsigned)n_bricks : SEED_GRID_X;
+        unsigned const seed_y = (unsigned)((n_bricks + SEED_GRID_X - 1) / SEED_GRID_X);
+        hipLaunchKernelGGL(tsdf_sparse_seed_kernel, dim3(seed_x, seed_y), dim3(256), 0, stream,
+            s.d_table, G, B, d_seed);
+    }
+    return SMVS_OK;
+}
+
+void
+smvs_hip::tsdf_host::launch_dilate(hipStream_t stream, const uint8_t *seed, TsdfBricks const &B,
+    uint8_t *state, unsigned long long *counts)
+{
+    hipLaunchKernelGGL(tsdf_sparse_dilate_kernel, dim3((B.n + 255u) / 256u), dim3(256), 0, stream,
+        seed, B, state, counts);
+}
+
+void
+smvs_hip::tsdf_host::launch_table(hipStream_t stream, const uint8_t *state, TsdfBricks const &B,
+    const unsigned long long *counts, int32_t *table, uint32_t *list)
+{
+    hipLaunchKernelGGL(tsdf_sparse_table_kernel, dim3((B.n + 255u) / 256u), dim3(256), 0, stream,
+        state, B, counts, table, list);
+}
+
+int
+smvs_hip::tsdf_host::extract_sparse_surface(Workspace &ws, const char *who, TsdfGrid const &G,
+    TsdfBricks const &B, size_t n_alloc, const float *d_tsdf, const uint32_t *d_weight,
+    const uint4 *d_colour, const int32_t *d_table, const uint32_t *d_list, float *tsdf,
+    uint32_t *weight, smvs_points **handle)
+{
+    hipStream_t const stream = ws.stream;
+    int rc;
+    // (no allocated brick or no vertex: no further slab, no launches, an empty handle)
+    TsdfOut O = {};
+    long long *d_cells = nullptr;
+    size_t n_vert = 0, n_face = 0;
+    size_t const n_state = n_alloc * 256;
+    size_t const n_vox = (size_t)G.nx * G.ny * G.nz;
+    if (n_alloc > 0) {
+        size_t const scan_tiles = (n_alloc + SCAN_TILE - 1) / SCAN_TILE;
+        Carver wc;
+        size_t const vid_at = wc(4 * n_state), counts_at = wc(8 * n_alloc),
+            tiles_at = wc(8 * (scan_tiles + 1));
+        char *work = nullptr;
+        if ((rc = ws.ensure(3, wc.total, &work)) != SMVS_OK)
+            return rc;
+        uint32_t *d_vid = reinterpret_cast<uint32_t *>(work + vid_at);
+        unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(work + counts_at);
+        unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(work + tiles_at);
+        unsigned const slots = (unsigned)n_alloc;
+        hipLaunchKernelGGL(tsdf_sparse_classify_kernel, dim3(slots), dim3(256), 0, stream,
+            d_tsdf, d_table, d_list, G, B, d_counts);
+        if (hipGetLastError() != hipSuccess) {
+            set_error("%s: integration launch failed", who);
+            return SMVS_ERR_HIP;
+        }
+        if ((rc = exclusive_scan(stream, d_counts, n_alloc, d_tiles)))
+            return rc;
+        unsigned long long sums = 0;
+        if ((rc = ws.download(&sums, scan_total(d_tiles, n_alloc), sizeof(sums))))
+            return rc;
+        n_vert = (size_t)(sums & 0xffffffffull);
+        n_face = 2 * (size_t)(sums >> 32);
+        if (n_vert > 0) {
+            Carver oc;
+            size_t const xyz_at = oc(12 * n_vert), nrm_at = oc(12 * n_vert),
+                conf_at = oc(4 * n_vert), rgb_at = oc(3 * n_vert), faces_at = oc(12 * n_face),
+                cells_at = oc(8 * n_vert);
+            char *outs = nullptr;
+            if ((rc = ws.ensure(1, oc.total, &outs)) != SMVS_OK)
+                return rc;
+            O.xyz = reinterpret_cast<float *>(outs + xyz_at);
+            O.nrm = reinterpret_cast<float *>(outs + nrm_at);
+            O.conf = reinterpret_cast<float *>(outs + conf_at);
+            O.rgb = reinterpret_cast<uint8_t *>(outs + rgb_at);
+            O.faces = reinterpret_cast<uint32_t *>(outs + faces_at);
+            d_cells = reinterpret_cast<long long *>(outs + cells_at);
+            hipLaunchKernelGGL(tsdf_sparse_vertex_kernel, dim3(slots), dim3(256), 0, stream,
+                d_tsdf, d_weight, d_colour, d_table, d_list, G, B, d_counts, d_vid, O, d_cells);
+            hipLaunchKernelGGL(tsdf_sparse_face_kernel, dim3(slots), dim3(256), 0, stream,
+                d_tsdf, d_table, d_list, G, B, d_counts, d_vid, O);
+            if (hipGetLastError() != hipSuccess) {
+                set_error("%s: extraction launch failed", who);
+                return SMVS_ERR_HIP;
+            }
+        }
+    }
+    smvs_points *h = nullptr;
+    if ((rc = fill_points(ws, true, true, n_vert, n_face,
+            VertexAttrs{ O.xyz, O.nrm, O.rgb, O.conf, nullptr }, O.faces, d_cells, &h)))
+        return rc;
+    auto fail = [&](int code) {
+        delete h;
+        return code;
+    };
+    std::vector<uint32_t> host_list;
+    std::vector<float> host_f;
+    std::vector<uint32_t> host_w;
+    if (n_alloc > 0 && (tsdf != nullptr || weight != nullptr)) {
+        host_list.resize(n_alloc);
+        if ((rc = ws.download(host_list.data(), d_list, 4 * n_alloc)))
+            return fail(rc);
+        if (tsdf != nullptr) {
+            host_f.resize(n_state);
+            if ((rc = ws.download(host_f.data(), d_tsdf, 4 * n_state)))
+                return fail(rc);
+        }
+        if (weight != nullptr) {
+            host_w.resize(n_state);
+            if ((rc = ws.download(host_w.data(), d_weight, 4 * n_state)))
+                return fail(rc);
+        }
+    }
+    // the whole grid from the slot-major state: NaN / 0 where not allocated
+    if (tsdf != nullptr)
+        for (size_t p = 0; p < n_vox; ++p)
+            tsdf[p] = std::nanf("");
+    if (weight != nullptr)
+        std::memset(weight, 0, 4 * n_vox);
+    for (size_t slot = 0; slot < host_list.size(); ++slot) {
+        unsigned const brick = host_list[slot];
+        int const i0 = (int)(brick % B.bx) * TSDF_BX, j0 = (int)(brick / B.bx % B.by) * TSDF_BY,
+            k0 = (int)(brick / B.bx / B.by) * TSDF_BZ;
+        for (int l = 0; l < 256; ++l) {
+            int const i = i0 + (l & 7), j = j0 + (l >> 3 & 7), k = k0 + (l >> 6);
+            if (i >= G.nx || j >= G.ny || k >= G.nz)
+                continue;
+            size_t const at = ((size_t)k * G.ny + j) * G.nx + i;
+            if (tsdf != nullptr)
+                tsdf[at] = host_f[slot * 256 + l];
+            if (weight != nullptr)
+                weight[at] = host_w[slot * 256 + l];
+        }
+    }
+    *handle = h;
+    return SMVS_OK;
+}
+
 extern "C" int
 smvs_tsdf_fuse_sparse(int device, const smvs_point_view *views, int n_views,
     const smvs_tsdf_options *options, const smvs_tsdf_sparse_options *sparse,
@@ -411,36 +584,11 @@ smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views
 
     launch_depth(stream, s, n_views);
     size_t n_tested = n_bricks;
-    if (cull) {
-        // the candidates (section 9.10), their list in the table's place, and
-        // the exact test on the list alone; the counts are the dilation's, not
-        // yet in use
-        uint8_t *d_cand = reinterpret_cast<uint8_t *>(slab + cand_at);
-        uint32_t *d_cand_list = reinterpret_cast<uint32_t *>(d_table);
-        if ((rc = launch_pyramids(ws, slab, s, n_views, pyr)))
-            return rc;
-        launch_cull(stream, s, pyr, G, B, d_cand, d_bcounts);
-        SMVS_HIP_CHECK(hipGetLastError());
-        if ((rc = exclusive_scan(stream, d_bcounts, brick_blocks, d_btiles)))
-            return rc;
-        unsigned long long total = 0;
-        if ((rc = ws.download(&total, d_btiles + brick_tiles, sizeof(total))))
-            return rc;
-        n_tested = (size_t)total;
-        if (brick_candidate != nullptr && (rc = ws.download(brick_candidate, d_cand, n_bricks)))
-            return rc;
-        SMVS_HIP_CHECK(hipMemsetAsync(d_seed, 0, n_bricks, stream));
-        launch_candidate_list(stream, d_cand, B, d_bcounts, d_cand_list);
-        launch_seed_list(stream, s, G, B, d_cand_list, n_tested, d_seed);
-    } else {
-        if (brick_candidate != nullptr)
-            std::memset(brick_candidate, 1, n_bricks);
-        // (a launch's x extent in threads is 32 bits: the bricks go over x and y)
-        unsigned const seed_x = n_bricks < SEED_GRID_X ? (unsigned)n_bricks : SEED_GRID_X;
-        unsigned const seed_y = (unsigned)((n_bricks + SEED_GRID_X - 1) / SEED_GRID_X);
-        hipLaunchKernelGGL(tsdf_sparse_seed_kernel, dim3(seed_x, seed_y), dim3(256), 0, stream,
-            s.d_table, G, B, d_seed);
-    }
+    if ((rc = launch_seeds(ws, slab, s, n_views, cull ? &pyr : nullptr, G, B,
+            cull ? reinterpret_cast<uint8_t *>(slab + cand_at) : nullptr,
+            reinterpret_cast<uint32_t *>(d_table), d_bcounts, d_btiles, d_seed, brick_candidate,
+            &n_tested)))
+        return rc;
     hipLaunchKernelGGL(tsdf_sparse_dilate_kernel, dim3(brick_blocks), dim3(256), 0, stream,
         d_seed, B, d_state, d_bcounts);
     SMVS_HIP_CHECK(hipGetLastError());
@@ -466,119 +614,33 @@ smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views
         return SMVS_ERR_NOMEM;
     }
 
-    // (no allocated brick or no vertex: no further slab, no launches, an empty handle)
-    TsdfOut O = {};
-    long long *d_cells = nullptr;
-    size_t n_vert = 0, n_face = 0;
+    // (no allocated brick: no further slab, no launches, an empty handle)
     size_t const n_state = n_alloc * 256;
     uint32_t *d_list = nullptr;
     float *d_tsdf = nullptr;
     uint32_t *d_weight = nullptr;
+    uint4 *d_colour = nullptr;
     if (n_alloc > 0) {
-        size_t const scan_tiles = (n_alloc + SCAN_TILE - 1) / SCAN_TILE;
         Carver vc;
         size_t const list_at = vc(4 * n_alloc), f_at = vc(4 * n_state), w_at = vc(4 * n_state),
-            colour_at = vc(16 * n_state), vid_at = vc(4 * n_state), counts_at = vc(8 * n_alloc),
-            tiles_at = vc(8 * (scan_tiles + 1));
+            colour_at = vc(16 * n_state);
         char *vol = nullptr;
         if ((rc = ws.ensure(2, vc.total, &vol)) != SMVS_OK)
             return rc;
         d_list = reinterpret_cast<uint32_t *>(vol + list_at);
         d_tsdf = reinterpret_cast<float *>(vol + f_at);
         d_weight = reinterpret_cast<uint32_t *>(vol + w_at);
-        uint4 *d_colour = reinterpret_cast<uint4 *>(vol + colour_at);
-        uint32_t *d_vid = reinterpret_cast<uint32_t *>(vol + vid_at);
-        unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(vol + counts_at);
-        unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(vol + tiles_at);
-        unsigned const slots = (unsigned)n_alloc;
-
+        d_colour = reinterpret_cast<uint4 *>(vol + colour_at);
         hipLaunchKernelGGL(tsdf_sparse_table_kernel, dim3(brick_blocks), dim3(256), 0, stream,
             d_state, B, d_bcounts, d_table, d_list);
-        hipLaunchKernelGGL(tsdf_sparse_integrate_kernel, dim3(slots), dim3(256), 0, stream,
-            s.d_table, d_images, G, B, d_list, d_tsdf, d_weight, d_colour);
-        hipLaunchKernelGGL(tsdf_sparse_classify_kernel, dim3(slots), dim3(256), 0, stream,
-            d_tsdf, d_table, d_list, G, B, d_counts);
-        if (hipGetLastError() != hipSuccess) {
-            set_error("smvs_tsdf_fuse_sparse: integration launch failed");
-            return SMVS_ERR_HIP;
-        }
-        if ((rc = exclusive_scan(stream, d_counts, n_alloc, d_tiles)))
-            return rc;
-        if ((rc = ws.download(&sums, scan_total(d_tiles, n_alloc), sizeof(sums))))
-            return rc;
-        n_vert = (size_t)(sums & 0xffffffffull);
-        n_face = 2 * (size_t)(sums >> 32);
-        if (n_vert > 0) {
-            Carver oc;
-            size_t const xyz_at = oc(12 * n_vert), nrm_at = oc(12 * n_vert),
-                conf_at = oc(4 * n_vert), rgb_at = oc(3 * n_vert), faces_at = oc(12 * n_face),
-                cells_at = oc(8 * n_vert);
-            char *outs = nullptr;
-            if ((rc = ws.ensure(1, oc.total, &outs)) != SMVS_OK)
-                return rc;
-            O.xyz = reinterpret_cast<float *>(outs + xyz_at);
-            O.nrm = reinterpret_cast<float *>(outs + nrm_at);
-            O.conf = reinterpret_cast<float *>(outs + conf_at);
-            O.rgb = reinterpret_cast<uint8_t *>(outs + rgb_at);
-            O.faces = reinterpret_cast<uint32_t *>(outs + faces_at);
-            d_cells = reinterpret_cast<long long *>(outs + cells_at);
-            hipLaunchKernelGGL(tsdf_sparse_vertex_kernel, dim3(slots), dim3(256), 0, stream,
-                d_tsdf, d_weight, d_colour, d_table, d_list, G, B, d_counts, d_vid, O, d_cells);
-            hipLaunchKernelGGL(tsdf_sparse_face_kernel, dim3(slots), dim3(256), 0, stream,
-                d_tsdf, d_table, d_list, G, B, d_counts, d_vid, O);
-            if (hipGetLastError() != hipSuccess) {
-                set_error("smvs_tsdf_fuse_sparse: extraction launch failed");
-                return SMVS_ERR_HIP;
-            }
-        }
+        hipLaunchKernelGGL(tsdf_sparse_integrate_kernel, dim3((unsigned)n_alloc), dim3(256), 0,
+            stream, s.d_table, d_images, G, B, d_list, d_tsdf, d_weight, d_colour);
     }
+    // classify, scan, vertices, faces, fill: the half smvs_tsdf_sparse_volume_extract shares
     smvs_points *h = nullptr;
-    if ((rc = fill_points(ws, true, true, n_vert, n_face,
-            VertexAttrs{ O.xyz, O.nrm, O.rgb, O.conf, nullptr }, O.faces, d_cells, &h)))
+    if ((rc = extract_sparse_surface(ws, "smvs_tsdf_fuse_sparse", G, B, n_alloc, d_tsdf, d_weight,
+            d_colour, d_table, d_list, tsdf, weight, &h)))
         return rc;
-    auto fail = [&](int code) {
-        delete h;
-        return code;
-    };
-    std::vector<uint32_t> host_list;
-    std::vector<float> host_f;
-    std::vector<uint32_t> host_w;
-    if (n_alloc > 0 && (tsdf != nullptr || weight != nullptr)) {
-        host_list.resize(n_alloc);
-        if ((rc = ws.download(host_list.data(), d_list, 4 * n_alloc)))
-            return fail(rc);
-        if (tsdf != nullptr) {
-            host_f.resize(n_state);
-            if ((rc = ws.download(host_f.data(), d_tsdf, 4 * n_state)))
-                return fail(rc);
-        }
-        if (weight != nullptr) {
-            host_w.resize(n_state);
-            if ((rc = ws.download(host_w.data(), d_weight, 4 * n_state)))
-                return fail(rc);
-        }
-    }
-    // the whole grid from the slot-major state: NaN / 0 where not allocated
-    if (tsdf != nullptr)
-        for (size_t p = 0; p < n_vox; ++p)
-            tsdf[p] = std::nanf("");
-    if (weight != nullptr)
-        std::memset(weight, 0, 4 * n_vox);
-    for (size_t slot = 0; slot < host_list.size(); ++slot) {
-        unsigned const brick = host_list[slot];
-        int const i0 = (int)(brick % B.bx) * TSDF_BX, j0 = (int)(brick / B.bx % B.by) * TSDF_BY,
-            k0 = (int)(brick / B.bx / B.by) * TSDF_BZ;
-        for (int l = 0; l < 256; ++l) {
-            int const i = i0 + (l & 7), j = j0 + (l >> 3 & 7), k = k0 + (l >> 6);
-            if (i >= G.nx || j >= G.ny || k >= G.nz)
-                continue;
-            size_t const at = ((size_t)k * G.ny + j) * G.nx + i;
-            if (tsdf != nullptr)
-                tsdf[at] = host_f[slot * 256 + l];
-            if (weight != nullptr)
-                weight[at] = host_w[slot * 256 + l];
-        }
-    }
     *handle = h;
     if (n_vertices != nullptr)
         *n_vertices = h->n_points;

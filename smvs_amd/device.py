@@ -1663,6 +1663,169 @@ class TsdfVolume:
         self.close()
 
 
+class SparseTsdfVolume:
+    """smvs_tsdf_sparse_volume: the sums of fuse_tsdf(sparse=True) kept on the
+    device in 8 x 8 x 4 bricks, so that a grid of up to 4096 voxels per side is
+    fused batch by batch (the definition is in
+    include/smvs_hip.h).  mark() every batch first, then integrate() every batch
+    with grow=False: with the cut off that is fuse_tsdf(sparse=True) over all
+    views, to the bit.  integrate(grow=True) marks its own batch first; bricks
+    that get their storage after the first integrate have missed the earlier
+    views and are counted in stats()["late_bricks"].  max_bricks <= 0: 1 << 20;
+    an SmvsError of status -4 names the bricks needed and changes nothing.  A
+    context manager; after close() every method raises ValueError."""
+
+    def __init__(self, origin, voxel_size, dims, trunc=0, max_bricks=0, device=0):
+        self._handle = None
+        self._lib = _capi.load()
+        opt = _capi.TsdfSparseVolumeOptions()
+        for k in range(3):
+            opt.origin[k] = float(origin[k])
+            opt.dims[k] = int(dims[k])
+        opt.voxel_size = float(voxel_size)
+        opt.trunc = float(trunc)
+        opt.max_bricks = int(max_bricks)
+        handle = C.c_void_p()
+        check(self._lib.smvs_tsdf_sparse_volume_create(int(device), C.byref(opt),
+                                                       C.byref(handle)))
+        self._handle = handle
+        self._shape = tuple(int(d) for d in dims)[::-1]
+        self._bricks = (-(-self._shape[0] // 4), -(-self._shape[1] // 8),
+                        -(-self._shape[2] // 8))
+
+    def _open(self):
+        if self._handle is None:
+            raise ValueError("SparseTsdfVolume: the volume is closed")
+        return self._handle
+
+    def mark(self, cams, depths, normals, cut=True, cull=False):
+        """smvs_tsdf_sparse_volume_mark: the batch's seed bricks join the
+        stored ones; no image is needed (normals may be None when cut is off)."""
+        handle = self._open()
+        n = len(cams)
+        arr, _keep = _tsdf_views(cams, depths, normals, None)
+        check(self._lib.smvs_tsdf_sparse_volume_mark(handle, arr if n else None, n,
+                                                     int(bool(cut)), int(bool(cull))))
+
+    def integrate(self, cams, depths, normals, images, cut=True, grow=True, cull=False):
+        """smvs_tsdf_sparse_volume_integrate: one batch, inputs as fuse_tsdf's;
+        grow marks the batch first (cull: with the brick cull in front)."""
+        handle = self._open()
+        n = len(cams)
+        arr, _keep = _tsdf_views(cams, depths, normals, images)
+        check(self._lib.smvs_tsdf_sparse_volume_integrate(handle, arr if n else None, n,
+                                                          int(bool(cut)), int(bool(grow)),
+                                                          int(bool(cull))))
+
+    def extract(self, min_weight=0, volume=False, brick_state=False):
+        """smvs_tsdf_sparse_volume_extract: the dict fuse_tsdf(sparse=True)
+        returns (stats: this volume's, see stats()); changes no state."""
+        handle = self._open()
+        lib = self._lib
+        tsdf = weight = state = None
+        if volume:
+            tsdf = np.zeros(self._shape, np.float32)
+            weight = np.zeros(self._shape, np.uint32)
+        if brick_state:
+            state = np.zeros(self._bricks, np.uint8)
+        mesh = C.c_void_p()
+        n_vertices, n_faces = C.c_int64(), C.c_int64()
+        check(lib.smvs_tsdf_sparse_volume_extract(handle, int(min_weight), _p(state, _u8p),
+                                                  _p(tsdf, _fp), _p(weight, _u32p),
+                                                  C.byref(mesh), C.byref(n_vertices),
+                                                  C.byref(n_faces)))
+        try:
+            k = n_vertices.value
+            out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
+                   "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
+                   "faces": np.zeros((n_faces.value, 3), np.uint32),
+                   "cells": np.zeros(k, np.int64)}
+            check(lib.smvs_points_download(mesh, _p(out["xyz"], _fp), _p(out["normals"], _fp),
+                                           _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
+                                           None, _p(out["faces"], _u32p)))
+            check(lib.smvs_tsdf_vertex_cells(mesh, out["cells"].ctypes.data_as(
+                C.POINTER(C.c_int64))))
+        finally:
+            lib.smvs_points_release(mesh)
+        out["stats"] = self.stats()
+        if volume:
+            out["tsdf"] = tsdf
+            out["weight"] = weight
+        if brick_state:
+            out["brick_state"] = state
+        return out
+
+    def stats(self):
+        """smvs_tsdf_sparse_volume_info: bricks, seed_bricks, allocated_bricks
+        (with storage), pending_bricks (marked, storage at the next integrate),
+        late_bricks, state_bytes, n_views."""
+        handle = self._open()
+        st = _capi.TsdfSparseVolumeStats()
+        check(self._lib.smvs_tsdf_sparse_volume_info(handle, None, C.byref(st), None))
+        return st.as_dict()
+
+    @property
+    def n_views(self):
+        return self.stats()["n_views"]
+
+    def state(self):
+        """smvs_tsdf_sparse_volume_download, the checkpoint as a dict:
+        brick_state (bz, by, bx) uint8, list and birth (n,) uint32, S (n, 256)
+        float32, W (n, 256) uint32, rgbc (n, 256, 4) uint32 (the sums R, G, B,
+        C) and n_views; n the bricks with storage, in linear brick order."""
+        handle = self._open()
+        st = self.stats()
+        n = st["allocated_bricks"]
+        out = {"brick_state": np.zeros(self._bricks, np.uint8),
+               "list": np.zeros(n, np.uint32), "birth": np.zeros(n, np.uint32),
+               "S": np.zeros((n, 256), np.float32), "W": np.zeros((n, 256), np.uint32),
+               "rgbc": np.zeros((n, 256, 4), np.uint32)}
+        check(self._lib.smvs_tsdf_sparse_volume_download(
+            handle, _p(out["brick_state"], _u8p), _p(out["list"], _u32p),
+            _p(out["birth"], _u32p), _p(out["S"], _fp), _p(out["W"], _u32p),
+            _p(out["rgbc"], _u32p)))
+        out["n_views"] = st["n_views"]
+        return out
+
+    def load_state(self, brick_state, list, birth, S, W, rgbc, n_views):
+        """smvs_tsdf_sparse_volume_upload: load_state(**state())."""
+        handle = self._open()
+        brick_state = np.ascontiguousarray(brick_state, np.uint8)
+        slots = np.ascontiguousarray(list, np.uint32)
+        birth = np.ascontiguousarray(birth, np.uint32)
+        S = np.ascontiguousarray(S, np.float32)
+        W = np.ascontiguousarray(W, np.uint32)
+        rgbc = np.ascontiguousarray(rgbc, np.uint32)
+        n = len(slots)
+        if brick_state.shape != self._bricks or slots.shape != (n,) or birth.shape != (n,) \
+                or S.shape != (n, 256) or W.shape != (n, 256) or rgbc.shape != (n, 256, 4):
+            raise ValueError("SparseTsdfVolume.load_state: the arrays do not have the volume's "
+                             "shape")
+        check(self._lib.smvs_tsdf_sparse_volume_upload(
+            handle, _p(brick_state, _u8p), _p(slots, _u32p), _p(birth, _u32p), C.c_int64(n),
+            _p(S, _fp), _p(W, _u32p), _p(rgbc, _u32p), C.c_int64(int(n_views))))
+
+    def reset(self):
+        handle = self._open()
+        check(self._lib.smvs_tsdf_sparse_volume_reset(handle))
+
+    def close(self):
+        if self._handle is not None:
+            self._lib.smvs_tsdf_sparse_volume_release(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        self._open()
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        self.close()
+
+
 def _tsdf_options(origin, voxel_size, dims, trunc, cut):
     opt = _capi.TsdfOptions()
     opt.cut_surfaces = int(bool(cut))

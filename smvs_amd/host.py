@@ -1027,10 +1027,15 @@ class FusedBatchedSettings(C.Structure):
     _fields_ = FusedCleanSettings._fields_ + [("clean", C.c_int), ("batch_views", C.c_int)]
 
 
+class FusedSparseBatchedSettings(C.Structure):
+    """smvs_host_fused_sparse_batched_settings"""
+    _fields_ = FusedBatchedSettings._fields_ + [("sparse_batch_views", C.c_int)]
+
+
 def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=0, min_weight=0,
                    view_ids=None, image_embedding="undistorted", input_scale=0,
                    use_shading=False, cut=True, device=0, sparse=False, max_bricks=0,
-                   cull=False, clean=None, batch_views=0):
+                   cull=False, clean=None, batch_views=0, sparse_batch_views=0):
     """Not in the reference: the views' smvs-{B,S}<input_scale> depth maps fused
     into ONE surface mesh through a truncated signed distance field
     (smvs_tsdf_fuse), written as
@@ -1060,7 +1065,18 @@ def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=
     batch by batch, the batches are integrated into a persistent dense volume
     (smvs_amd.TsdfVolume) and the surface is extracted once.  With cut=False
     the file is the same byte for byte; the cut, when on, acts within a batch.
-    It belongs to the dense volume: with sparse it is refused.  0: off."""
+    It belongs to the dense volume: with sparse it is refused.  0: off.
+
+    sparse_batch_views (with sparse): N > 0 keeps only N consecutive scene views
+    loaded at a time on the brick-sparse volume
+    (smvs_host_generate_fused_sparse_batched, section 9.14).  Three passes over
+    the scene: the bounds (skipped with aabb), the marks (cull: with the brick
+    cull in front) and the integration without growth into a persistent
+    brick-sparse volume (smvs_amd.SparseTsdfVolume); then the surface is
+    extracted once.  With cut=False the file is the same byte for byte; the
+    cut, when on, acts within a batch.  0: off."""
+    if sparse_batch_views and not sparse:
+        raise ValueError("sparse_batch_views belongs to sparse=True")
     if cull and not sparse:
         raise ValueError("cull belongs to sparse=True")
     lib = load()
@@ -1071,7 +1087,21 @@ def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=
         unknown = set(clean) - {"threshold", "percentile", "component_size", "keep_unreferenced"}
         if unknown:
             raise ValueError("clean: unknown option %s" % sorted(unknown))
-    if batch_views:
+    if sparse_batch_views:
+        c = clean or {}
+        fs = FusedSparseBatchedSettings(
+            0.0 if voxel_size is None else float(voxel_size), int(resolution), float(trunc),
+            int(min_weight), int(max_bricks), int(bool(cull)), int(bool(sparse)),
+            float(c.get("threshold", 0.0)), float(c.get("percentile", 0.0)),
+            int(c.get("component_size", 1000)), int(bool(c.get("keep_unreferenced", False))),
+            int(clean is not None), int(batch_views), int(sparse_batch_views))
+        if clean is not None:
+            stats = _capi.MeshCleanStats()
+        sparse_batched = lib.smvs_host_generate_fused_sparse_batched
+
+        def entry(*args):
+            return sparse_batched(*args, C.byref(stats) if stats is not None else None)
+    elif batch_views:
         if max_bricks and not sparse:
             raise ValueError("max_bricks belongs to sparse=True")
         c = clean or {}

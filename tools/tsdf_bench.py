@@ -14,6 +14,7 @@ tools/points_bench.py's (the 16 views repeat the nine synthetic ones).
                                [--no-kernels] [--no-peaks]
                                [--sparse [--resolution N] [--max-bricks N] [--cull]]
                                [--batch N [--no-cut]]
+                               [--sparse --batch N [--no-cut] [--cull]]
 
 --sparse times smvs_tsdf_fuse_sparse (the brick-sparse volume, DESIGN.md section
 9.9) on the same case instead: --resolution N is --dims N and may go up to
@@ -32,6 +33,13 @@ alternating -- and the kernels of both from one trace each.  With the cut on a
 batch is cut within itself, which is less work than the one-shot's cut and
 another mesh; --no-cut compares like with like (the meshes are then equal, and
 the tool checks that they are).
+
+--sparse --batch N times the persistent brick-sparse volume
+(smvs_tsdf_sparse_volume, section 9.14) against the one-shot sparse entry in
+the same way: create, mark per batch of N views (--cull: with the brick cull in
+front), integrate per batch without growth, extract, release.  The entry's line
+carries the time of the mark pass, of the integrate pass (the first integrate
+gives every brick its slot) and of the extraction, and the volume's stats.
 """
 import argparse
 import csv
@@ -65,6 +73,16 @@ VOLUME_KERNELS = ["mesh_prepare_kernel", "mesh_cut_kernel", "tsdf_depth_kernel",
                   "tsdf_volume_integrate_kernel", "tsdf_volume_field_kernel",
                   "tsdf_classify_kernel", "scan_tile_sums_kernel", "scan_tiles_kernel",
                   "scan_apply_kernel", "tsdf_vertex_kernel", "tsdf_face_kernel"]
+# with --sparse --batch: per batch the preparation twice (mark, integrate), the
+# seed pass and its merge; the slots once; the integration on the stored sums
+SPARSE_VOLUME_KERNELS = ["mesh_prepare_kernel", "mesh_cut_kernel", "tsdf_depth_kernel",
+                         "tsdf_sparse_seed_kernel", "tsdf_sparse_volume_merge_kernel",
+                         "tsdf_sparse_dilate_kernel", "tsdf_sparse_table_kernel",
+                         "tsdf_sparse_volume_reslot_kernel",
+                         "tsdf_sparse_volume_integrate_kernel",
+                         "tsdf_sparse_volume_field_kernel", "tsdf_sparse_classify_kernel",
+                         "scan_tile_sums_kernel", "scan_tiles_kernel", "scan_apply_kernel",
+                         "tsdf_sparse_vertex_kernel", "tsdf_sparse_face_kernel"]
 CHILD_REPS = 3
 BOX_LO, BOX_SIDE = (-1.3, -1.3, 2.7), 2.6
 
@@ -102,11 +120,37 @@ def fuse_batched(c, batch, cut):
         return vol.extract()
 
 
+def fuse_sparse_batched(c, args, times=None):
+    """create, mark per batch, integrate per batch without growth, extract,
+    release; times (a dict): the seconds of the three passes are added to it"""
+    from smvs_amd import device
+    cams, depths, normals, images, origin, voxel, dims = c
+    cut, n = not args.no_cut, args.batch
+    with device.SparseTsdfVolume(origin, voxel, dims, max_bricks=args.max_bricks) as vol:
+        t0 = time.perf_counter()
+        for at in range(0, len(cams), n):
+            vol.mark(cams[at:at + n], depths[at:at + n], normals[at:at + n], cut=cut,
+                     cull=args.cull)
+        t1 = time.perf_counter()
+        for at in range(0, len(cams), n):
+            vol.integrate(cams[at:at + n], depths[at:at + n], normals[at:at + n],
+                          images[at:at + n], cut=cut, grow=False)
+        t2 = time.perf_counter()
+        out = vol.extract()
+        t3 = time.perf_counter()
+    if times is not None:
+        for k, v in (("mark", t1 - t0), ("integrate", t2 - t1), ("extract", t3 - t2)):
+            times.setdefault(k, []).append(v)
+    return out
+
+
 def child(args):
     from smvs_amd import device
     c = case(args)
     for _ in range(CHILD_REPS):
-        if args.batch:
+        if args.batch and args.sparse:
+            fuse_sparse_batched(c, args)
+        elif args.batch:
             fuse_batched(c, args.batch, not args.no_cut)
         else:
             device.fuse_tsdf(*c, cut=not args.no_cut, **sparse_args(args))
@@ -136,6 +180,11 @@ def kernel_times(args):
         names = sparse_kernels(args) if args.sparse else KERNELS
         if args.batch:
             names = VOLUME_KERNELS
+        if args.batch and args.sparse:
+            names = SPARSE_VOLUME_KERNELS
+            if args.cull:
+                at = names.index("tsdf_sparse_seed_kernel")
+                names = names[:at] + CULL_KERNELS + names[at + 1:]
         if args.no_cut or (args.batch == 1):
             names = [k for k in names if k != "mesh_cut_kernel"]
         rows = {k: [] for k in names}
@@ -221,6 +270,48 @@ def batched_lines(args, c):
               flush=True)
 
 
+def sparse_batched_lines(args, c):
+    """--sparse --batch: the one-shot sparse entry and the persistent brick-sparse
+    volume, alternating"""
+    import copy
+    from smvs_amd import device
+    cut = not args.no_cut
+    one, bat, phases = [], [], {}
+    for _ in range(args.reps + 1):
+        t0 = time.perf_counter()
+        a = device.fuse_tsdf(*c, cut=cut, **sparse_args(args))
+        one.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        b = fuse_sparse_batched(c, args, phases)
+        bat.append(time.perf_counter() - t0)
+    keys = ("xyz", "normals", "rgb", "confidence", "faces", "cells")
+    same = all(np.array_equal(a[k], b[k]) for k in keys)
+    if not cut and not same:
+        raise SystemExit("tsdf_bench: without the cut the batched mesh must be the one-shot's")
+    rec = {"case": "sparse_batched_entry", "dims": [args.dims] * 3, "views": args.views,
+           "size": args.size, "cut": cut, "cull": bool(args.cull), "batch": args.batch,
+           "batches": -(-args.views // args.batch), "same_mesh": bool(same),
+           "vertices": len(b["xyz"]), "faces": len(b["faces"]),
+           "one_shot_ms_best": round(1e3 * min(one[1:]), 2),
+           "batched_ms_best": round(1e3 * min(bat[1:]), 2)}
+    for k, v in phases.items():
+        rec[k + "_ms_best"] = round(1e3 * min(v[1:]), 2)
+    rec.update(b["stats"])
+    print(json.dumps(rec), flush=True)
+    if args.no_kernels:
+        return
+    one_args = copy.copy(args)
+    one_args.batch = 0
+    for label, a in (("one_shot", one_args), ("batched", args)):
+        kt = kernel_times(a)
+        for k, (per, t) in kt.items():
+            print(json.dumps({"case": label + "_kernel", "kernel": k, "launches_per_call": per,
+                              "ms_per_call_best": round(1e3 * t, 4)}), flush=True)
+        print(json.dumps({"case": label + "_kernels_total",
+                          "ms_per_call_best": round(1e3 * sum(t for _, t in kt.values()), 3)}),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
@@ -236,11 +327,12 @@ def main():
     ap.add_argument("--cull", action="store_true",
                     help="with --sparse: the brick cull in front of the seed pass")
     ap.add_argument("--batch", type=int, default=0,
-                    help="the persistent volume, N views per integrate, against the one-shot")
+                    help="the persistent volume (with --sparse: the brick-sparse one), N views per "
+                         "batch, against the one-shot")
     ap.add_argument("--no-cut", action="store_true", help="with --batch: the cut off")
     args = ap.parse_args()
-    if args.batch < 0 or (args.batch and args.sparse):
-        ap.error("--batch N > 0 belongs to the dense volume")
+    if args.batch < 0:
+        ap.error("--batch must not be negative")
     if args.no_cut and not args.batch and not args.child:
         ap.error("--no-cut belongs to --batch")
     if args.cull and not args.sparse:
@@ -257,6 +349,9 @@ def main():
     if smvs_amd.device_count() < 1:
         raise SystemExit("tsdf_bench needs a GPU")
     c = case(args)
+    if args.batch and args.sparse:
+        sparse_batched_lines(args, c)
+        return
     if args.batch:
         batched_lines(args, c)
         return
