@@ -3,6 +3,8 @@
 // the two PLY writers.
 #include "capi_internal.h"
 
+#include <cstddef>
+
 #include "mesh_generator.h"
 
 using namespace smvs_amd;
@@ -63,21 +65,55 @@ export_results(ExportCall const& c, std::string const& path, std::size_t nv, std
         *c.n_faces = (int64_t)nf;
 }
 
-// The fused entries: the settings records share their first four members;
-// `rest` sets what a record has beyond them.  clean_stats: the entry with the
-// clean alone.
-template <class Settings, class Rest> int
-generate_fused(ExportCall const& c, char const* entry, const Settings *f, Rest rest,
-    smvs_mesh_clean_stats *clean_stats = nullptr)
+// The fused entries.  Every settings record is a prefix of the widest one,
+// smvs_host_fused_sparse_batched_settings: an entry widens its record (the rest
+// zero), forces what it forces through `force`, and the options are filled from
+// the widest record in one place.  clean_stats: the entries with a clean.
+typedef smvs_host_fused_sparse_batched_settings WidestFused;
+
+// (a later edit to host_capi.h cannot silently break the prefix: the record's
+// last member sits where the widest record has it, and the record ends before
+// the member the widest one goes on with)
+#define FUSED_PREFIX(Narrow, last, next)                                              \
+    static_assert(offsetof(Narrow, last) == offsetof(WidestFused, last)               \
+        && sizeof(Narrow) <= offsetof(WidestFused, next), #Narrow " is no prefix")
+FUSED_PREFIX(smvs_host_fused_settings, min_weight, max_bricks);
+FUSED_PREFIX(smvs_host_fused_sparse_settings, max_bricks, cull);
+// (its tail padding lies over `sparse`, which its entry sets)
+FUSED_PREFIX(smvs_host_fused_sparse_cull_settings, cull, threshold);
+FUSED_PREFIX(smvs_host_fused_clean_settings, keep_unreferenced, clean);
+FUSED_PREFIX(smvs_host_fused_batched_settings, batch_views, sparse_batch_views);
+#undef FUSED_PREFIX
+
+// what an entry forces on its widened record
+void as_stated(WidestFused&) {}
+void forced_sparse(WidestFused& w) { w.sparse = 1; }
+void forced_clean(WidestFused& w) { w.clean = 1; }
+
+template <class Settings> int
+generate_fused(ExportCall const& c, char const* entry, const Settings *f,
+    void (*force)(WidestFused&), smvs_mesh_clean_stats *clean_stats = nullptr)
 {
     return guarded([&] {
         PointCloudSettings const conf = export_settings(c, entry, f != nullptr);
+        WidestFused w = {};
+        std::memcpy(&w, f, sizeof(Settings));
+        force(w);
         MeshGenerator::FusedOptions fo;
-        fo.voxel_size = f->voxel_size;
-        fo.resolution = f->resolution;
-        fo.trunc = f->trunc;
-        fo.min_weight = f->min_weight;
-        rest(fo);
+        fo.voxel_size = w.voxel_size;
+        fo.resolution = w.resolution;
+        fo.trunc = w.trunc;
+        fo.min_weight = w.min_weight;
+        fo.sparse = w.sparse != 0;
+        fo.max_bricks = w.max_bricks;
+        fo.cull = w.cull != 0;
+        fo.clean = w.clean != 0;
+        fo.clean_threshold = w.threshold;
+        fo.clean_percentile = w.percentile;
+        fo.clean_component_size = w.component_size;
+        fo.clean_keep_unreferenced = w.keep_unreferenced != 0;
+        fo.batch_views = w.batch_views;
+        fo.sparse_batch_views = w.sparse_batch_views;
         std::size_t nv = 0, nf = 0;
         std::string const path = generate_scene_fused(c.scene_dir, conf, fo, &nv, &nf,
             clean_stats);
@@ -141,8 +177,7 @@ smvs_host_generate_fused(const char *scene_dir,
     int64_t *n_vertices, int64_t *n_faces)
 {
     return generate_fused({ scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
-        n_vertices, n_faces }, "smvs_host_generate_fused", f,
-        [](MeshGenerator::FusedOptions&) {});
+        n_vertices, n_faces }, "smvs_host_generate_fused", f, as_stated);
 }
 
 extern "C" int
@@ -152,11 +187,7 @@ smvs_host_generate_fused_sparse(const char *scene_dir,
     int64_t *n_vertices, int64_t *n_faces)
 {
     return generate_fused({ scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
-        n_vertices, n_faces }, "smvs_host_generate_fused_sparse", f,
-        [f](MeshGenerator::FusedOptions& fo) {
-            fo.sparse = true;
-            fo.max_bricks = f->max_bricks;
-        });
+        n_vertices, n_faces }, "smvs_host_generate_fused_sparse", f, forced_sparse);
 }
 
 extern "C" int
@@ -166,12 +197,7 @@ smvs_host_generate_fused_sparse_cull(const char *scene_dir,
     int64_t *n_vertices, int64_t *n_faces)
 {
     return generate_fused({ scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
-        n_vertices, n_faces }, "smvs_host_generate_fused_sparse_cull", f,
-        [f](MeshGenerator::FusedOptions& fo) {
-            fo.sparse = true;
-            fo.max_bricks = f->max_bricks;
-            fo.cull = f->cull != 0;
-        });
+        n_vertices, n_faces }, "smvs_host_generate_fused_sparse_cull", f, forced_sparse);
 }
 
 extern "C" int
@@ -181,17 +207,7 @@ smvs_host_generate_fused_clean(const char *scene_dir,
     int64_t *n_vertices, int64_t *n_faces, smvs_mesh_clean_stats *stats)
 {
     return generate_fused({ scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
-        n_vertices, n_faces }, "smvs_host_generate_fused_clean", f,
-        [f](MeshGenerator::FusedOptions& fo) {
-            fo.sparse = f->sparse != 0;
-            fo.max_bricks = f->max_bricks;
-            fo.cull = f->cull != 0;
-            fo.clean = true;
-            fo.clean_threshold = f->threshold;
-            fo.clean_percentile = f->percentile;
-            fo.clean_component_size = f->component_size;
-            fo.clean_keep_unreferenced = f->keep_unreferenced != 0;
-        }, stats);
+        n_vertices, n_faces }, "smvs_host_generate_fused_clean", f, forced_clean, stats);
 }
 
 extern "C" int
@@ -201,18 +217,7 @@ smvs_host_generate_fused_batched(const char *scene_dir,
     int64_t *n_vertices, int64_t *n_faces, smvs_mesh_clean_stats *stats)
 {
     return generate_fused({ scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
-        n_vertices, n_faces }, "smvs_host_generate_fused_batched", f,
-        [f](MeshGenerator::FusedOptions& fo) {
-            fo.sparse = f->sparse != 0;
-            fo.max_bricks = f->max_bricks;
-            fo.cull = f->cull != 0;
-            fo.clean = f->clean != 0;
-            fo.clean_threshold = f->threshold;
-            fo.clean_percentile = f->percentile;
-            fo.clean_component_size = f->component_size;
-            fo.clean_keep_unreferenced = f->keep_unreferenced != 0;
-            fo.batch_views = f->batch_views;
-        }, stats);
+        n_vertices, n_faces }, "smvs_host_generate_fused_batched", f, as_stated, stats);
 }
 
 extern "C" int
@@ -222,19 +227,7 @@ smvs_host_generate_fused_sparse_batched(const char *scene_dir,
     int64_t *n_vertices, int64_t *n_faces, smvs_mesh_clean_stats *stats)
 {
     return generate_fused({ scene_dir, o, view_ids, n_view_ids, ply_path, ply_path_capacity,
-        n_vertices, n_faces }, "smvs_host_generate_fused_sparse_batched", f,
-        [f](MeshGenerator::FusedOptions& fo) {
-            fo.sparse = f->sparse != 0;
-            fo.max_bricks = f->max_bricks;
-            fo.cull = f->cull != 0;
-            fo.clean = f->clean != 0;
-            fo.clean_threshold = f->threshold;
-            fo.clean_percentile = f->percentile;
-            fo.clean_component_size = f->component_size;
-            fo.clean_keep_unreferenced = f->keep_unreferenced != 0;
-            fo.batch_views = f->batch_views;
-            fo.sparse_batch_views = f->sparse_batch_views;
-        }, stats);
+        n_vertices, n_faces }, "smvs_host_generate_fused_sparse_batched", f, as_stated, stats);
 }
 
 extern "C" int

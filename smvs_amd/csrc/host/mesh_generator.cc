@@ -20,6 +20,21 @@ void check_status(int rc, char const* what)
         throw std::runtime_error(std::string(what) + ": " + smvs_last_error());
 }
 
+// `mesh` sized for nv vertices and nf faces and filled from `handle`, which is
+// released here
+void download_mesh(smvs_points* handle, int64_t nv, int64_t nf, TriangleMesh& mesh)
+{
+    mesh.xyz.resize(3 * (std::size_t)nv);
+    mesh.normals.resize(3 * (std::size_t)nv);
+    mesh.colors.resize(3 * (std::size_t)nv);
+    mesh.confidences.resize((std::size_t)nv);
+    mesh.faces.resize(3 * (std::size_t)nf);
+    int const rc = smvs_points_download(handle, mesh.xyz.data(), mesh.normals.data(),
+        mesh.colors.data(), mesh.confidences.data(), nullptr, mesh.faces.data());
+    smvs_points_release(handle);
+    check_status(rc, "smvs_points_download");
+}
+
 } // namespace
 
 MeshGenerator::MeshGenerator(Options const& o) : opts(o)
@@ -147,15 +162,7 @@ MeshGenerator::generate_triangle_mesh(std::vector<SceneView> const& inputviews,
     int64_t nv = 0, nf = 0;
     check_status(smvs_mesh_generate(opts.device, in.pv.data(), (int)in.pv.size(), &mo,
         &handle, &nv, &nf), "smvs_mesh_generate");
-    mesh->xyz.resize(3 * (std::size_t)nv);
-    mesh->normals.resize(3 * (std::size_t)nv);
-    mesh->colors.resize(3 * (std::size_t)nv);
-    mesh->confidences.resize((std::size_t)nv);
-    mesh->faces.resize(3 * (std::size_t)nf);
-    int const rc = smvs_points_download(handle, mesh->xyz.data(), mesh->normals.data(),
-        mesh->colors.data(), mesh->confidences.data(), nullptr, mesh->faces.data());
-    smvs_points_release(handle);
-    check_status(rc, "smvs_points_download");
+    download_mesh(handle, nv, nf, *mesh);
     save_cut_maps(in);
     return mesh;
 }
@@ -183,27 +190,20 @@ MeshGenerator::generate_simplified(std::vector<SceneView> const& inputviews,
     int64_t nv = 0, nf = 0;
     check_status(smvs_simplified_generate(opts.device, in.pv.data(), (int)in.pv.size(), &so,
         &handle, &nv, &nf), "smvs_simplified_generate");
-    std::size_t const n = (std::size_t)nv;
-    int rc;
     if (create_triangle_mesh) {
-        mesh->xyz.resize(3 * n);
-        mesh->normals.resize(3 * n);
-        mesh->colors.resize(3 * n);
-        mesh->confidences.resize(n);
-        mesh->faces.resize(3 * (std::size_t)nf);
-        rc = smvs_points_download(handle, mesh->xyz.data(), mesh->normals.data(),
-            mesh->colors.data(), mesh->confidences.data(), nullptr, mesh->faces.data());
+        download_mesh(handle, nv, nf, *mesh);
     } else {
+        std::size_t const n = (std::size_t)nv;
         points->xyz.resize(3 * n);
         points->normals.resize(3 * n);
         points->colors.resize(3 * n);
         points->confidences.resize(n);
         points->values.resize(n);
-        rc = smvs_points_download(handle, points->xyz.data(), points->normals.data(),
+        int const rc = smvs_points_download(handle, points->xyz.data(), points->normals.data(),
             points->colors.data(), points->confidences.data(), points->values.data(), nullptr);
+        smvs_points_release(handle);
+        check_status(rc, "smvs_points_download");
     }
-    smvs_points_release(handle);
-    check_status(rc, "smvs_points_download");
     save_cut_maps(in);
 }
 
@@ -275,28 +275,104 @@ fused_result(MeshGenerator::Options const& opts, MeshGenerator::FusedOptions con
             *clean_stats = st;
     }
     TriangleMesh::Ptr mesh(new TriangleMesh);
-    mesh->xyz.resize(3 * (std::size_t)nv);
-    mesh->normals.resize(3 * (std::size_t)nv);
-    mesh->colors.resize(3 * (std::size_t)nv);
-    mesh->confidences.resize((std::size_t)nv);
-    mesh->faces.resize(3 * (std::size_t)nf);
-    int const rc = smvs_points_download(handle, mesh->xyz.data(), mesh->normals.data(),
-        mesh->colors.data(), mesh->confidences.data(), nullptr, mesh->faces.data());
-    smvs_points_release(handle);
-    check_status(rc, "smvs_points_download");
+    download_mesh(handle, nv, nf, *mesh);
     return mesh;
 }
 
-struct VolumeHolder
+// What generate_fused refuses in its options, stated once.  Each path asks at
+// the point where it has always asked: the unbatched
+// one after it has found a usable view, the batched ones before they load any.
+void
+check_fused_options(MeshGenerator::FusedOptions const& fused)
 {
-    smvs_tsdf_volume* v = nullptr;
-    ~VolumeHolder() { smvs_tsdf_volume_release(v); }
+    if (fused.voxel_size <= 0.0f && fused.resolution < 8)
+        throw std::invalid_argument("generate_fused: resolution must be at least 8");
+    if (fused.sparse && fused.voxel_size <= 0.0f && fused.resolution > 4096)
+        throw std::invalid_argument("generate_fused: resolution must be at most 4096");
+    if (!fused.sparse && fused.max_bricks > 0)
+        throw std::invalid_argument("generate_fused: max_bricks belongs to sparse");
+    if (!fused.sparse && fused.cull)
+        throw std::invalid_argument("generate_fused: cull belongs to sparse");
+}
+
+} // namespace
+
+// The persistent volume behind a batched generate_fused, released on scope
+// exit.  With marks_first every batch is marked before the first is integrated.
+struct FusedBatchVolume
+{
+    bool marks_first = false;
+    virtual ~FusedBatchVolume() {}
+    virtual void create(int device, smvs_tsdf_options const& to) = 0;
+    virtual void mark(std::vector<smvs_point_view> const&, int /*cut*/) {}
+    virtual void integrate(std::vector<smvs_point_view> const& pv, int cut) = 0;
+    virtual void extract(int min_weight, smvs_points** handle, int64_t* nv, int64_t* nf) = 0;
 };
 
-struct SparseVolumeHolder
+namespace {
+
+// smvs_tsdf_volume
+struct DenseBatchVolume : FusedBatchVolume
+{
+    smvs_tsdf_volume* v = nullptr;
+    ~DenseBatchVolume() { smvs_tsdf_volume_release(v); }
+    void create(int device, smvs_tsdf_options const& to) override
+    {
+        smvs_tsdf_volume_options vo;
+        std::copy(to.origin, to.origin + 3, vo.origin);
+        std::copy(to.dims, to.dims + 3, vo.dims);
+        vo.voxel_size = to.voxel_size;
+        vo.trunc = to.trunc;
+        check_status(smvs_tsdf_volume_create(device, &vo, &v), "smvs_tsdf_volume_create");
+    }
+    void integrate(std::vector<smvs_point_view> const& pv, int cut) override
+    {
+        check_status(smvs_tsdf_volume_integrate(v, pv.data(), (int)pv.size(), cut),
+            "smvs_tsdf_volume_integrate");
+    }
+    void extract(int min_weight, smvs_points** handle, int64_t* nv, int64_t* nf) override
+    {
+        check_status(smvs_tsdf_volume_extract(v, min_weight, nullptr, nullptr, handle, nv, nf),
+            "smvs_tsdf_volume_extract");
+    }
+};
+
+// smvs_tsdf_sparse_volume: every mark precedes the
+// first integrate and nothing grows, so no brick is late
+struct SparseBatchVolume : FusedBatchVolume
 {
     smvs_tsdf_sparse_volume* v = nullptr;
-    ~SparseVolumeHolder() { smvs_tsdf_sparse_volume_release(v); }
+    int64_t max_bricks;
+    int cull;
+    explicit SparseBatchVolume(MeshGenerator::FusedOptions const& fused)
+        : max_bricks(fused.max_bricks), cull(fused.cull ? 1 : 0) { marks_first = true; }
+    ~SparseBatchVolume() { smvs_tsdf_sparse_volume_release(v); }
+    void create(int device, smvs_tsdf_options const& to) override
+    {
+        smvs_tsdf_sparse_volume_options vo;
+        std::copy(to.origin, to.origin + 3, vo.origin);
+        std::copy(to.dims, to.dims + 3, vo.dims);
+        vo.voxel_size = to.voxel_size;
+        vo.trunc = to.trunc;
+        vo.max_bricks = max_bricks;
+        check_status(smvs_tsdf_sparse_volume_create(device, &vo, &v),
+            "smvs_tsdf_sparse_volume_create");
+    }
+    void mark(std::vector<smvs_point_view> const& pv, int cut) override
+    {
+        check_status(smvs_tsdf_sparse_volume_mark(v, pv.data(), (int)pv.size(), cut, cull),
+            "smvs_tsdf_sparse_volume_mark");
+    }
+    void integrate(std::vector<smvs_point_view> const& pv, int cut) override
+    {
+        check_status(smvs_tsdf_sparse_volume_integrate(v, pv.data(), (int)pv.size(), cut, 0, 0),
+            "smvs_tsdf_sparse_volume_integrate");
+    }
+    void extract(int min_weight, smvs_points** handle, int64_t* nv, int64_t* nf) override
+    {
+        check_status(smvs_tsdf_sparse_volume_extract(v, min_weight, nullptr, nullptr, nullptr,
+            handle, nv, nf), "smvs_tsdf_sparse_volume_extract");
+    }
 };
 
 } // namespace
@@ -308,25 +384,27 @@ MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
 {
     if (fused.batch_views < 0)
         throw std::invalid_argument("generate_fused: batch_views must not be negative");
-    if (fused.batch_views > 0)
-        return generate_fused_batched(inputviews, image_name, dm_name, fused, clean_stats);
+    if (fused.batch_views > 0) {
+        if (fused.sparse)
+            throw std::invalid_argument("generate_fused: batch_views belongs to the dense volume");
+        DenseBatchVolume volume;
+        return generate_fused_batched(inputviews, image_name, dm_name, fused,
+            (std::size_t)fused.batch_views, volume, clean_stats);
+    }
     if (fused.sparse_batch_views < 0)
         throw std::invalid_argument("generate_fused: sparse_batch_views must not be negative");
-    if (fused.sparse_batch_views > 0)
-        return generate_fused_sparse_batched(inputviews, image_name, dm_name, fused,
-            clean_stats);
+    if (fused.sparse_batch_views > 0) {
+        if (!fused.sparse)
+            throw std::invalid_argument("generate_fused: sparse_batch_views belongs to sparse");
+        SparseBatchVolume volume(fused);
+        return generate_fused_batched(inputviews, image_name, dm_name, fused,
+            (std::size_t)fused.sparse_batch_views, volume, clean_stats);
+    }
     Inputs in;
     load_views(inputviews, image_name, dm_name, in);
     if (in.views.empty())
         return TriangleMesh::Ptr(new TriangleMesh);
-    if (fused.voxel_size <= 0.0f && fused.resolution < 8)
-        throw std::invalid_argument("generate_fused: resolution must be at least 8");
-    if (fused.sparse && fused.voxel_size <= 0.0f && fused.resolution > 4096)
-        throw std::invalid_argument("generate_fused: resolution must be at most 4096");
-    if (!fused.sparse && fused.max_bricks > 0)
-        throw std::invalid_argument("generate_fused: max_bricks belongs to sparse");
-    if (!fused.sparse && fused.cull)
-        throw std::invalid_argument("generate_fused: cull belongs to sparse");
+    check_fused_options(fused);
     int const n = (int)in.pv.size();
     float lo[3], hi[3];
     if (opts.use_aabb) {
@@ -357,27 +435,20 @@ MeshGenerator::generate_fused(std::vector<SceneView> const& inputviews,
     return fused_result(opts, fused, handle, nv, nf, clean_stats);
 }
 
-// generate_fused with FusedOptions::batch_views: one batch of consecutive
-// scene views is loaded at a time, for the bounds and again for the
-// integration into a persistent volume (smvs_tsdf_volume, DESIGN.md section
-// 9.13).  The usable views of the batches, one after the other, are the list
-// generate_fused loads at once; the cut, when on, acts within a batch.
+// generate_fused with FusedOptions::batch_views or ::sparse_batch_views: `step`
+// consecutive scene views are loaded at a time, once per pass -- for the bounds
+// (skipped with use_aabb), for the marks where the volume has them, and for the
+// integration into the persistent volume.  The usable views of the batches, one
+// after the other, are the list generate_fused loads at once; the cut, when on,
+// acts within a batch.
 TriangleMesh::Ptr
 MeshGenerator::generate_fused_batched(std::vector<SceneView> const& inputviews,
     std::string const& image_name, std::string const& dm_name, FusedOptions const& fused,
-    smvs_mesh_clean_stats* clean_stats)
+    std::size_t step, FusedBatchVolume& volume, smvs_mesh_clean_stats* clean_stats)
 {
-    if (fused.sparse)
-        throw std::invalid_argument("generate_fused: batch_views belongs to the dense volume");
-    if (fused.voxel_size <= 0.0f && fused.resolution < 8)
-        throw std::invalid_argument("generate_fused: resolution must be at least 8");
-    if (fused.max_bricks > 0)
-        throw std::invalid_argument("generate_fused: max_bricks belongs to sparse");
-    if (fused.cull)
-        throw std::invalid_argument("generate_fused: cull belongs to sparse");
-    std::size_t const step = (std::size_t)fused.batch_views;
+    check_fused_options(fused);
     int const cut = opts.cut_surfaces ? 1 : 0;
-    // calls `use` with the loaded views of every batch that has one
+    // calls `use` with the view records of every batch that has a usable view
     auto for_batches = [&](auto use) {
         for (std::size_t at = 0; at < inputviews.size(); at += step) {
             std::vector<SceneView> const batch(inputviews.begin() + at,
@@ -385,7 +456,7 @@ MeshGenerator::generate_fused_batched(std::vector<SceneView> const& inputviews,
             Inputs in;
             load_views(batch, image_name, dm_name, in);
             if (!in.views.empty())
-                use(in);
+                use(in.pv);
         }
     };
     float lo[3], hi[3];
@@ -399,11 +470,11 @@ MeshGenerator::generate_fused_batched(std::vector<SceneView> const& inputviews,
             lo[a] = INFINITY;
             hi[a] = -INFINITY;
         }
-        for_batches([&](Inputs& in) {
+        for_batches([&](std::vector<smvs_point_view> const& pv) {
             float blo[3], bhi[3];
-            check_status(smvs_tsdf_bounds(opts.device, in.pv.data(), (int)in.pv.size(), cut,
-                blo, bhi), "smvs_tsdf_bounds");
-            usable += in.pv.size();
+            check_status(smvs_tsdf_bounds(opts.device, pv.data(), (int)pv.size(), cut, blo, bhi),
+                "smvs_tsdf_bounds");
+            usable += pv.size();
             for (int a = 0; a < 3; ++a) {
                 lo[a] = std::fmin(lo[a], blo[a]);
                 hi[a] = std::fmax(hi[a], bhi[a]);
@@ -413,108 +484,23 @@ MeshGenerator::generate_fused_batched(std::vector<SceneView> const& inputviews,
             return TriangleMesh::Ptr(new TriangleMesh);
     }
     smvs_tsdf_options const to = fused_grid(opts, fused, lo, hi);
-    smvs_tsdf_volume_options vo;
-    std::copy(to.origin, to.origin + 3, vo.origin);
-    std::copy(to.dims, to.dims + 3, vo.dims);
-    vo.voxel_size = to.voxel_size;
-    vo.trunc = to.trunc;
-    VolumeHolder volume;
-    check_status(smvs_tsdf_volume_create(opts.device, &vo, &volume.v), "smvs_tsdf_volume_create");
+    volume.create(opts.device, to);
+    // (with use_aabb this pass is the first to learn whether a view is usable)
     usable = 0;
-    for_batches([&](Inputs& in) {
-        check_status(smvs_tsdf_volume_integrate(volume.v, in.pv.data(), (int)in.pv.size(), cut),
-            "smvs_tsdf_volume_integrate");
-        usable += in.pv.size();
+    for_batches([&](std::vector<smvs_point_view> const& pv) {
+        if (volume.marks_first)
+            volume.mark(pv, cut);
+        else
+            volume.integrate(pv, cut);
+        usable += pv.size();
     });
     if (usable == 0)
         return TriangleMesh::Ptr(new TriangleMesh);
+    if (volume.marks_first)
+        for_batches([&](std::vector<smvs_point_view> const& pv) { volume.integrate(pv, cut); });
     smvs_points* handle = nullptr;
     int64_t nv = 0, nf = 0;
-    check_status(smvs_tsdf_volume_extract(volume.v, to.min_weight, nullptr, nullptr, &handle,
-        &nv, &nf), "smvs_tsdf_volume_extract");
-    return fused_result(opts, fused, handle, nv, nf, clean_stats);
-}
-
-// generate_fused with FusedOptions::sparse_batch_views: one batch of
-// consecutive scene views is loaded at a time, three times over -- for the
-// bounds, for the marks and for the integration into a persistent brick-sparse
-// volume (smvs_tsdf_sparse_volume).  Every mark
-// precedes the first integrate and nothing grows, so no brick is late; the
-// cut, when on, acts within a batch.
-TriangleMesh::Ptr
-MeshGenerator::generate_fused_sparse_batched(std::vector<SceneView> const& inputviews,
-    std::string const& image_name, std::string const& dm_name, FusedOptions const& fused,
-    smvs_mesh_clean_stats* clean_stats)
-{
-    if (!fused.sparse)
-        throw std::invalid_argument("generate_fused: sparse_batch_views belongs to sparse");
-    if (fused.voxel_size <= 0.0f && fused.resolution < 8)
-        throw std::invalid_argument("generate_fused: resolution must be at least 8");
-    if (fused.voxel_size <= 0.0f && fused.resolution > 4096)
-        throw std::invalid_argument("generate_fused: resolution must be at most 4096");
-    std::size_t const step = (std::size_t)fused.sparse_batch_views;
-    int const cut = opts.cut_surfaces ? 1 : 0;
-    // calls `use` with the loaded views of every batch that has one
-    auto for_batches = [&](auto use) {
-        for (std::size_t at = 0; at < inputviews.size(); at += step) {
-            std::vector<SceneView> const batch(inputviews.begin() + at,
-                inputviews.begin() + std::min(inputviews.size(), at + step));
-            Inputs in;
-            load_views(batch, image_name, dm_name, in);
-            if (!in.views.empty())
-                use(in);
-        }
-    };
-    float lo[3], hi[3];
-    std::size_t usable = 0;
-    if (opts.use_aabb) {
-        std::copy(opts.aabb_min, opts.aabb_min + 3, lo);
-        std::copy(opts.aabb_max, opts.aabb_max + 3, hi);
-    } else {
-        // the union's box: min and max are exact, so the order does not matter
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = INFINITY;
-            hi[a] = -INFINITY;
-        }
-        for_batches([&](Inputs& in) {
-            float blo[3], bhi[3];
-            check_status(smvs_tsdf_bounds(opts.device, in.pv.data(), (int)in.pv.size(), cut,
-                blo, bhi), "smvs_tsdf_bounds");
-            usable += in.pv.size();
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = std::fmin(lo[a], blo[a]);
-                hi[a] = std::fmax(hi[a], bhi[a]);
-            }
-        });
-        if (usable == 0)
-            return TriangleMesh::Ptr(new TriangleMesh);
-    }
-    smvs_tsdf_options const to = fused_grid(opts, fused, lo, hi);
-    smvs_tsdf_sparse_volume_options vo;
-    std::copy(to.origin, to.origin + 3, vo.origin);
-    std::copy(to.dims, to.dims + 3, vo.dims);
-    vo.voxel_size = to.voxel_size;
-    vo.trunc = to.trunc;
-    vo.max_bricks = fused.max_bricks;
-    SparseVolumeHolder volume;
-    check_status(smvs_tsdf_sparse_volume_create(opts.device, &vo, &volume.v),
-        "smvs_tsdf_sparse_volume_create");
-    usable = 0;
-    for_batches([&](Inputs& in) {
-        check_status(smvs_tsdf_sparse_volume_mark(volume.v, in.pv.data(), (int)in.pv.size(), cut,
-            fused.cull ? 1 : 0), "smvs_tsdf_sparse_volume_mark");
-        usable += in.pv.size();
-    });
-    if (usable == 0)
-        return TriangleMesh::Ptr(new TriangleMesh);
-    for_batches([&](Inputs& in) {
-        check_status(smvs_tsdf_sparse_volume_integrate(volume.v, in.pv.data(),
-            (int)in.pv.size(), cut, 0, 0), "smvs_tsdf_sparse_volume_integrate");
-    });
-    smvs_points* handle = nullptr;
-    int64_t nv = 0, nf = 0;
-    check_status(smvs_tsdf_sparse_volume_extract(volume.v, to.min_weight, nullptr, nullptr,
-        nullptr, &handle, &nv, &nf), "smvs_tsdf_sparse_volume_extract");
+    volume.extract(to.min_weight, &handle, &nv, &nf);
     return fused_result(opts, fused, handle, nv, nf, clean_stats);
 }
 

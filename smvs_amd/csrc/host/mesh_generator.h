@@ -40,6 +40,9 @@ struct TriangleMesh
     std::size_t num_faces(void) const { return faces.size() / 3; }
 };
 
+// the persistent volume behind a batched generate_fused (mesh_generator.cc)
+struct FusedBatchVolume;
+
 class MeshGenerator
 {
 public:
@@ -130,10 +133,8 @@ private:
     void save_cut_maps(Inputs const& in) const;
     TriangleMesh::Ptr generate_fused_batched(std::vector<SceneView> const& views,
         std::string const& image_name, std::string const& dm_name,
-        FusedOptions const& fused, smvs_mesh_clean_stats* clean_stats);
-    TriangleMesh::Ptr generate_fused_sparse_batched(std::vector<SceneView> const& views,
-        std::string const& image_name, std::string const& dm_name,
-        FusedOptions const& fused, smvs_mesh_clean_stats* clean_stats);
+        FusedOptions const& fused, std::size_t step, FusedBatchVolume& volume,
+        smvs_mesh_clean_stats* clean_stats);
 
     Options opts;
 };

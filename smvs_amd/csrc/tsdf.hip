@@ -467,33 +467,25 @@ smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
     if (lease.w == nullptr)
         return SMVS_ERR_HIP;
     Workspace &ws = *lease.w;
-    Carver carve;
-    ViewSlab s;
-    carve_views(views, n_views, true, carve, s);
-    size_t const images_at = carve(sizeof(TsdfImageDev) * n_views);
-    size_t const tsdf_at = carve(4 * n_vox), weight_at = carve(4 * n_vox),
-        colour_at = carve(16 * n_vox);
+    ViewStage stage;
+    size_t tsdf_at = 0, weight_at = 0, colour_at = 0;
     ExtractPieces extract_at;
-    carve_extract(n_vox, carve, extract_at);
-    char *slab = nullptr;
-    if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
+    if ((rc = stage(ws, views, n_views, opt.cut_surfaces != 0, true, [&](Carver &carve) {
+            tsdf_at = carve(4 * n_vox);
+            weight_at = carve(4 * n_vox);
+            colour_at = carve(16 * n_vox);
+            carve_extract(n_vox, carve, extract_at);
+        })))
         return rc;
-    hipStream_t const stream = ws.stream;
-    TsdfImageDev *d_images = nullptr;
-    if ((rc = upload_and_prepare(ws, slab, views, n_views, opt.cut_surfaces != 0, true, s))
-        || (rc = upload_image_table(ws, slab, images_at, views, s, &d_images)))
-        return rc;
-
+    char *const slab = stage.slab;
     float *d_tsdf = reinterpret_cast<float *>(slab + tsdf_at);
     uint32_t *d_weight = reinterpret_cast<uint32_t *>(slab + weight_at);
     uint4 *d_colour = reinterpret_cast<uint4 *>(slab + colour_at);
 
-    launch_depth(stream, s, n_views);
-    unsigned const bricks = (unsigned)((G.nx + TSDF_BX - 1) / TSDF_BX)
-        * (unsigned)((G.ny + TSDF_BY - 1) / TSDF_BY)
-        * (unsigned)((G.nz + TSDF_BZ - 1) / TSDF_BZ);
-    hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(bricks), dim3(256), 0, stream, s.d_table,
-        d_images, G, d_tsdf, d_weight, d_colour);
+    size_t n_bricks;
+    unsigned const bricks = brick_grid(G, &n_bricks).n;
+    hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(bricks), dim3(256), 0, ws.stream,
+        stage.s.d_table, stage.d_images, G, d_tsdf, d_weight, d_colour);
     smvs_points *h = nullptr;
     if ((rc = extract_surface(ws, "smvs_tsdf_fuse", G, slab, extract_at, d_tsdf, d_weight,
             d_colour, &h)))
@@ -503,10 +495,5 @@ smvs_tsdf_fuse(int device, const smvs_point_view *views, int n_views,
         delete h;
         return rc;
     }
-    *handle = h;
-    if (n_vertices != nullptr)
-        *n_vertices = h->n_points;
-    if (n_faces != nullptr)
-        *n_faces = h->n_faces;
-    return SMVS_OK;
+    return publish(h, handle, n_vertices, n_faces);
 }

@@ -356,8 +356,21 @@ tsdf_quad_faces(const uint32_t *v, bool inside, uint32_t *out)
 // and cut them as every export path does)
 namespace tsdf_host {
 
-// the dense volume's size limit (smvs_tsdf_fuse, smvs_tsdf_volume_create)
+// The limits of the entries.  TSDF_MAX_VOXELS: the dense volume's size
+// (smvs_tsdf_fuse, smvs_tsdf_volume_create), and the grid up to which the
+// brick-sparse entries hand tsdf / weight out
 constexpr size_t TSDF_MAX_VOXELS = (size_t)1 << 27;
+constexpr size_t MAX_BRICKS_GRID = (size_t)1 << 28;
+constexpr int64_t DEFAULT_MAX_BRICKS = (int64_t)1 << 20;
+constexpr int64_t MAX_MAX_BRICKS = (int64_t)1 << 23;       // vertex ids are 32 bits
+// what the stats and the budget's text count per allocated brick: the
+// one-shot entry's 24 bytes of sums and 4 of vertex id per voxel, the volume's
+// sums alone (its vertex ids live in a workspace for the length of an extract)
+constexpr int64_t ONE_SHOT_STATE_BYTES_PER_BRICK = 256 * 28;
+constexpr int64_t VOLUME_STATE_BYTES_PER_BRICK = 256 * 24;
+// a persistent volume: 255 * n_views must fit uint32 (the colour sums),
+// 8 * n_views an int (the confidence's divisor)
+constexpr int64_t VOLUME_MAX_VIEWS = (int64_t)1 << 24;
 
 // argument checks shared by the entries (before any device call)
 int check_views(const smvs_point_view *views, int n_views, int cut, bool want_images);
@@ -365,12 +378,64 @@ int check_views(const smvs_point_view *views, int n_views, int cut, bool want_im
 // (`who` heads the error text)
 int check_grid(const char *who, const smvs_tsdf_options &opt, int n_views, int max_dim,
     TsdfGrid &G);
+// check_grid on a volume's options record (smvs_tsdf_volume_options,
+// smvs_tsdf_sparse_volume_options): a grid without a view list
+template <class VolumeOptions> int
+check_volume_grid(const char *who, VolumeOptions const &options, int max_dim, TsdfGrid &G)
+{
+    smvs_tsdf_options opt = {};
+    for (int r = 0; r < 3; ++r) {
+        opt.origin[r] = options.origin[r];
+        opt.dims[r] = options.dims[r];
+    }
+    opt.voxel_size = options.voxel_size;
+    opt.trunc = options.trunc;
+    return check_grid(who, opt, 0, max_dim, G);
+}
 // the fusing entries' colour table, n_views records at slab + at, from the
 // images the view stage uploaded
 int upload_image_table(Workspace &ws, char *slab, size_t at, const smvs_point_view *views,
     ViewSlab const &s, TsdfImageDev **d_images);
 // D(p) = depth_z[p] where cut[p] != 0, else 0, in place in depth_z
 void launch_depth(hipStream_t stream, ViewSlab const &s, int n_views);
+// The staging of a view list, as every entry that walks one does it: the view
+// stage's pieces are carved first (and the colour table's with want_images),
+// then the caller's own (`more(carve)`), all in the slab of slot 0; the views
+// are uploaded, prepared and cut, the colour table uploaded, and D launched.
+struct ViewStage {
+    Carver carve;
+    ViewSlab s;
+    char *slab = nullptr;
+    TsdfImageDev *d_images = nullptr;    // with want_images
+
+    template <class More> int
+    operator()(Workspace &ws, const smvs_point_view *views, int n_views, bool cut,
+        bool want_images, More more)
+    {
+        carve_views(views, n_views, want_images, carve, s);
+        size_t const images_at = want_images ? carve(sizeof(TsdfImageDev) * n_views) : 0;
+        more(carve);
+        int rc;
+        if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
+            return rc;
+        if ((rc = upload_and_prepare(ws, slab, views, n_views, cut, want_images, s))
+            || (want_images && (rc = upload_image_table(ws, slab, images_at, views, s, &d_images))))
+            return rc;
+        launch_depth(ws.stream, s, n_views);
+        return SMVS_OK;
+    }
+};
+// a finished mesh goes out: the entries' last step
+inline int
+publish(smvs_points *h, smvs_points **handle, int64_t *n_vertices, int64_t *n_faces)
+{
+    *handle = h;
+    if (n_vertices != nullptr)
+        *n_vertices = h->n_points;
+    if (n_faces != nullptr)
+        *n_faces = h->n_faces;
+    return SMVS_OK;
+}
 // The extraction half of smvs_tsdf_fuse, which smvs_tsdf_volume_extract
 // (tsdf_volume.hip) runs as well: classify, scan, vertices, faces, fill on a
 // field, weights and colour sums that are on the device (x fastest).
@@ -415,16 +480,31 @@ TsdfBricks brick_grid(TsdfGrid const &G, size_t *n_bricks);
 
 // tsdf_sparse.hip: the passes of smvs_tsdf_fuse_sparse_opts that the persistent
 // brick-sparse volume (tsdf_volume_sparse.hip) runs as well.
-// After launch_depth: the list's seed bytes (2 / 0 per brick).  pyr == nullptr:
-// the exact test on every brick.  Else the cull in front (launch_pyramids,
-// launch_cull, the candidates' list into cand_list, the exact test on the list);
-// cand, cand_list (room for B.n entries), counts (one per 256 bricks) and tiles
-// (their scan's) are work arrays.  brick_candidate (host, may be null) and
-// *n_tested as smvs_tsdf_fuse_sparse_opts gives them.
-int launch_seeds(Workspace &ws, char *slab, ViewSlab const &s, int n_views, PyramidSlab *pyr,
-    TsdfGrid const &G, TsdfBricks const &B, uint8_t *cand, uint32_t *cand_list,
-    unsigned long long *counts, unsigned long long *tiles, uint8_t *seed,
-    uint8_t *brick_candidate, size_t *n_tested);
+// Their work arrays over the bricks of the grid, in a ViewStage's slab: the
+// seed and state bytes, the table (whose place holds the cull's candidate list
+// first), the counts per 256 bricks and their scan's tiles; with the cull the
+// views' pyramids and the candidate bytes behind them.
+struct BrickWork {
+    bool cull = false;
+    unsigned blocks = 0;        // of 256 bricks
+    PyramidSlab pyr;
+    uint8_t *seed = nullptr, *state = nullptr, *cand = nullptr;
+    int32_t *table = nullptr;
+    unsigned long long *counts = nullptr, *tiles = nullptr;
+
+    void carve(const smvs_point_view *views, int n_views, size_t n_bricks, bool with_cull,
+        Carver &carve);
+    void place(char *slab);     // the pointers, once the slab is there
+private:
+    size_t seed_at = 0, state_at = 0, table_at = 0, counts_at = 0, tiles_at = 0, cand_at = 0;
+};
+// After launch_depth: the list's seed bytes (2 / 0 per brick) in w.seed.
+// Without w.cull the exact test on every brick.  Else the cull in front
+// (launch_pyramids, launch_cull, the candidates' list, the exact test on the
+// list).  brick_candidate (host, may be null) and *n_tested as
+// smvs_tsdf_fuse_sparse_opts gives them.
+int launch_seeds(Workspace &ws, char *slab, ViewSlab const &s, int n_views, TsdfGrid const &G,
+    TsdfBricks const &B, BrickWork &w, uint8_t *brick_candidate, size_t *n_tested);
 // state[brick] = 2 seed, 1 a neighbour of a seed, 0 neither; counts[block of 256
 // bricks] = allocated | seeds << 32
 void launch_dilate(hipStream_t stream, const uint8_t *seed, TsdfBricks const &B, uint8_t *state,

@@ -303,16 +303,6 @@ tsdf_sparse_face_kernel(const float *__restrict__ tsdf, const int32_t *__restric
 using namespace smvs_hip;
 using namespace smvs_hip::tsdf_host;
 
-namespace {
-
-constexpr size_t DENSE_MAX_VOXELS = (size_t)1 << 27;       // smvs_tsdf_fuse's limit
-constexpr size_t MAX_BRICKS_GRID = (size_t)1 << 28;
-constexpr int64_t DEFAULT_MAX_BRICKS = (int64_t)1 << 20;
-constexpr int64_t MAX_MAX_BRICKS = (int64_t)1 << 23;       // vertex ids are 32 bits
-constexpr int64_t STATE_BYTES_PER_BRICK = 256 * 28;
-
-} // namespace
-
 TsdfBricks
 smvs_hip::tsdf_host::brick_grid(TsdfGrid const &G, size_t *n_bricks)
 {
@@ -325,37 +315,64 @@ smvs_hip::tsdf_host::brick_grid(TsdfGrid const &G, size_t *n_bricks)
     return B;
 }
 
+void
+smvs_hip::tsdf_host::BrickWork::carve(const smvs_point_view *views, int n_views, size_t n_bricks,
+    bool with_cull, Carver &carve)
+{
+    cull = with_cull;
+    blocks = (unsigned)((n_bricks + 255) / 256);
+    size_t const scan_tiles = ((size_t)blocks + SCAN_TILE - 1) / SCAN_TILE;
+    seed_at = carve(n_bricks);
+    state_at = carve(n_bricks);
+    table_at = carve(4 * n_bricks);
+    counts_at = carve(8 * (size_t)blocks);
+    tiles_at = carve(8 * (scan_tiles + 1));
+    if (cull) {
+        carve_pyramids(views, n_views, carve, pyr);
+        cand_at = carve(n_bricks);
+    }
+}
+
+void
+smvs_hip::tsdf_host::BrickWork::place(char *slab)
+{
+    seed = reinterpret_cast<uint8_t *>(slab + seed_at);
+    state = reinterpret_cast<uint8_t *>(slab + state_at);
+    table = reinterpret_cast<int32_t *>(slab + table_at);
+    counts = reinterpret_cast<unsigned long long *>(slab + counts_at);
+    tiles = reinterpret_cast<unsigned long long *>(slab + tiles_at);
+    cand = cull ? reinterpret_cast<uint8_t *>(slab + cand_at) : nullptr;
+}
+
 int
 smvs_hip::tsdf_host::launch_seeds(Workspace &ws, char *slab, ViewSlab const &s, int n_views,
-    PyramidSlab *pyr, TsdfGrid const &G, TsdfBricks const &B, uint8_t *d_cand,
-    uint32_t *d_cand_list, unsigned long long *d_counts, unsigned long long *d_tiles,
-    uint8_t *d_seed, uint8_t *brick_candidate, size_t *n_tested)
+    TsdfGrid const &G, TsdfBricks const &B, BrickWork &w, uint8_t *brick_candidate,
+    size_t *n_tested)
 {
     hipStream_t const stream = ws.stream;
     size_t const n_bricks = B.n;
     int rc;
     *n_tested = n_bricks;
-    if (pyr != nullptr) {
+    if (w.cull) {
         // the candidates (section 9.10), their list in the table's place, and
         // the exact test on the list alone; the counts are the dilation's, not
         // yet in use
-        unsigned const brick_blocks = (unsigned)((n_bricks + 255) / 256);
-        size_t const brick_tiles = ((size_t)brick_blocks + SCAN_TILE - 1) / SCAN_TILE;
-        if ((rc = launch_pyramids(ws, slab, s, n_views, *pyr)))
+        if ((rc = launch_pyramids(ws, slab, s, n_views, w.pyr)))
             return rc;
-        launch_cull(stream, s, *pyr, G, B, d_cand, d_counts);
+        launch_cull(stream, s, w.pyr, G, B, w.cand, w.counts);
         SMVS_HIP_CHECK(hipGetLastError());
-        if ((rc = exclusive_scan(stream, d_counts, brick_blocks, d_tiles)))
+        if ((rc = exclusive_scan(stream, w.counts, w.blocks, w.tiles)))
             return rc;
         unsigned long long total = 0;
-        if ((rc = ws.download(&total, d_tiles + brick_tiles, sizeof(total))))
+        if ((rc = ws.download(&total, scan_total(w.tiles, w.blocks), sizeof(total))))
             return rc;
         *n_tested = (size_t)total;
-        if (brick_candidate != nullptr && (rc = ws.download(brick_candidate, d_cand, n_bricks)))
+        if (brick_candidate != nullptr && (rc = ws.download(brick_candidate, w.cand, n_bricks)))
             return rc;
-        SMVS_HIP_CHECK(hipMemsetAsync(d_seed, 0, n_bricks, stream));
-        launch_candidate_list(stream, d_cand, B, d_counts, d_cand_list);
-        launch_seed_list(stream, s, G, B, d_cand_list, *n_tested, d_seed);
+        SMVS_HIP_CHECK(hipMemsetAsync(w.seed, 0, n_bricks, stream));
+        uint32_t *const cand_list = reinterpret_cast<uint32_t *>(w.table);
+        launch_candidate_list(stream, w.cand, B, w.counts, cand_list);
+        launch_seed_list(stream, s, G, B, cand_list, *n_tested, w.seed);
     } else {
         if (brick_candidate != nullptr)
             std::memset(brick_candidate, 1, n_bricks);
@@ -363,7 +380,7 @@ smvs_hip::tsdf_host::launch_seeds(Workspace &ws, char *slab, ViewSlab const &s, 
         unsigned const seed_x = n_bricks < SEED_GRID_X ? (unsigned)n_bricks : SEED_GRID_X;
         unsigned const seed_y = (unsigned)((n_bricks + SEED_GRID_X - 1) / SEED_GRID_X);
         hipLaunchKernelGGL(tsdf_sparse_seed_kernel, dim3(seed_x, seed_y), dim3(256), 0, stream,
-            s.d_table, G, B, d_seed);
+            s.d_table, G, B, w.seed);
     }
     return SMVS_OK;
 }
@@ -541,7 +558,7 @@ smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views
     TsdfBricks const B = brick_grid(G, &n_bricks);
     SMVS_REQUIRE(n_bricks <= MAX_BRICKS_GRID, "the brick grid has more than 2^28 bricks");
     size_t const n_vox = (size_t)G.nx * G.ny * G.nz;
-    SMVS_REQUIRE((tsdf == nullptr && weight == nullptr) || n_vox <= DENSE_MAX_VOXELS,
+    SMVS_REQUIRE((tsdf == nullptr && weight == nullptr) || n_vox <= TSDF_MAX_VOXELS,
         "tsdf / weight are given only for grids of at most 2^27 voxels");
     int64_t max_bricks = sparse != nullptr ? sparse->max_bricks : 0;
     if (max_bricks <= 0)
@@ -553,64 +570,41 @@ smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views
     if (lease.w == nullptr)
         return SMVS_ERR_HIP;
     Workspace &ws = *lease.w;
-    Carver carve;
-    ViewSlab s;
-    PyramidSlab pyr;
-    carve_views(views, n_views, true, carve, s);
-    size_t const images_at = carve(sizeof(TsdfImageDev) * n_views);
-    unsigned const brick_blocks = (unsigned)((n_bricks + 255) / 256);
-    size_t const brick_tiles = ((size_t)brick_blocks + SCAN_TILE - 1) / SCAN_TILE;
-    size_t const seed_at = carve(n_bricks), state_at = carve(n_bricks),
-        table_at = carve(4 * n_bricks), bcounts_at = carve(8 * (size_t)brick_blocks),
-        btiles_at = carve(8 * (brick_tiles + 1));
-    size_t cand_at = 0;
-    if (cull) {
-        carve_pyramids(views, n_views, carve, pyr);
-        cand_at = carve(n_bricks);
-    }
-    char *slab = nullptr;
-    if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
+    ViewStage stage;
+    BrickWork w;
+    if ((rc = stage(ws, views, n_views, opt.cut_surfaces != 0, true,
+            [&](Carver &carve) { w.carve(views, n_views, n_bricks, cull, carve); })))
         return rc;
     hipStream_t const stream = ws.stream;
-    TsdfImageDev *d_images = nullptr;
-    if ((rc = upload_and_prepare(ws, slab, views, n_views, opt.cut_surfaces != 0, true, s))
-        || (rc = upload_image_table(ws, slab, images_at, views, s, &d_images)))
-        return rc;
-    uint8_t *d_seed = reinterpret_cast<uint8_t *>(slab + seed_at);
-    uint8_t *d_state = reinterpret_cast<uint8_t *>(slab + state_at);
-    int32_t *d_table = reinterpret_cast<int32_t *>(slab + table_at);
-    unsigned long long *d_bcounts = reinterpret_cast<unsigned long long *>(slab + bcounts_at);
-    unsigned long long *d_btiles = reinterpret_cast<unsigned long long *>(slab + btiles_at);
+    ViewSlab const &s = stage.s;
+    w.place(stage.slab);
 
-    launch_depth(stream, s, n_views);
     size_t n_tested = n_bricks;
-    if ((rc = launch_seeds(ws, slab, s, n_views, cull ? &pyr : nullptr, G, B,
-            cull ? reinterpret_cast<uint8_t *>(slab + cand_at) : nullptr,
-            reinterpret_cast<uint32_t *>(d_table), d_bcounts, d_btiles, d_seed, brick_candidate,
-            &n_tested)))
+    if ((rc = launch_seeds(ws, stage.slab, s, n_views, G, B, w, brick_candidate, &n_tested)))
         return rc;
-    hipLaunchKernelGGL(tsdf_sparse_dilate_kernel, dim3(brick_blocks), dim3(256), 0, stream,
-        d_seed, B, d_state, d_bcounts);
+    hipLaunchKernelGGL(tsdf_sparse_dilate_kernel, dim3(w.blocks), dim3(256), 0, stream, w.seed, B,
+        w.state, w.counts);
     SMVS_HIP_CHECK(hipGetLastError());
-    if ((rc = exclusive_scan(stream, d_bcounts, brick_blocks, d_btiles)))
+    if ((rc = exclusive_scan(stream, w.counts, w.blocks, w.tiles)))
         return rc;
     unsigned long long sums = 0;
-    if ((rc = ws.download(&sums, d_btiles + brick_tiles, sizeof(sums))))
+    if ((rc = ws.download(&sums, scan_total(w.tiles, w.blocks), sizeof(sums))))
         return rc;
     size_t const n_alloc = (size_t)(sums & 0xffffffffull);
     if (stats != nullptr) {
         stats->bricks = (int64_t)n_bricks;
         stats->seed_bricks = (int64_t)(sums >> 32);
         stats->allocated_bricks = (int64_t)n_alloc;
-        stats->state_bytes = (int64_t)n_alloc * STATE_BYTES_PER_BRICK;
+        stats->state_bytes = (int64_t)n_alloc * ONE_SHOT_STATE_BYTES_PER_BRICK;
         stats->tested_bricks = (int64_t)n_tested;
     }
-    if (brick_state != nullptr && (rc = ws.download(brick_state, d_state, n_bricks)))
+    if (brick_state != nullptr && (rc = ws.download(brick_state, w.state, n_bricks)))
         return rc;
     if ((int64_t)n_alloc > max_bricks) {
         set_error("smvs_tsdf_fuse_sparse: the surface needs %lld bricks (%lld bytes of state), "
             "max_bricks is %lld", (long long)n_alloc,
-            (long long)n_alloc * (long long)STATE_BYTES_PER_BRICK, (long long)max_bricks);
+            (long long)n_alloc * (long long)ONE_SHOT_STATE_BYTES_PER_BRICK,
+            (long long)max_bricks);
         return SMVS_ERR_NOMEM;
     }
 
@@ -631,22 +625,17 @@ smvs_tsdf_fuse_sparse_opts(int device, const smvs_point_view *views, int n_views
         d_tsdf = reinterpret_cast<float *>(vol + f_at);
         d_weight = reinterpret_cast<uint32_t *>(vol + w_at);
         d_colour = reinterpret_cast<uint4 *>(vol + colour_at);
-        hipLaunchKernelGGL(tsdf_sparse_table_kernel, dim3(brick_blocks), dim3(256), 0, stream,
-            d_state, B, d_bcounts, d_table, d_list);
+        hipLaunchKernelGGL(tsdf_sparse_table_kernel, dim3(w.blocks), dim3(256), 0, stream,
+            w.state, B, w.counts, w.table, d_list);
         hipLaunchKernelGGL(tsdf_sparse_integrate_kernel, dim3((unsigned)n_alloc), dim3(256), 0,
-            stream, s.d_table, d_images, G, B, d_list, d_tsdf, d_weight, d_colour);
+            stream, s.d_table, stage.d_images, G, B, d_list, d_tsdf, d_weight, d_colour);
     }
     // classify, scan, vertices, faces, fill: the half smvs_tsdf_sparse_volume_extract shares
     smvs_points *h = nullptr;
     if ((rc = extract_sparse_surface(ws, "smvs_tsdf_fuse_sparse", G, B, n_alloc, d_tsdf, d_weight,
-            d_colour, d_table, d_list, tsdf, weight, &h)))
+            d_colour, w.table, d_list, tsdf, weight, &h)))
         return rc;
-    *handle = h;
-    if (n_vertices != nullptr)
-        *n_vertices = h->n_points;
-    if (n_faces != nullptr)
-        *n_faces = h->n_faces;
-    return SMVS_OK;
+    return publish(h, handle, n_vertices, n_faces);
 }
 
 extern "C" int

@@ -113,10 +113,6 @@ using namespace smvs_hip::tsdf_host;
 
 namespace {
 
-// 255 * n_views must fit uint32 (the colour sums), 8 * n_views an int (the
-// confidence's divisor)
-constexpr int64_t VOLUME_MAX_VIEWS = (int64_t)1 << 24;
-
 int
 zero_state(Workspace &ws, smvs_tsdf_volume const &vol)
 {
@@ -146,16 +142,9 @@ smvs_tsdf_volume_create(int device, const smvs_tsdf_volume_options *options,
     SMVS_REQUIRE(volume != nullptr, "no volume pointer");
     *volume = nullptr;
     SMVS_REQUIRE(options != nullptr, "no options");
-    smvs_tsdf_options opt = {};
-    for (int r = 0; r < 3; ++r) {
-        opt.origin[r] = options->origin[r];
-        opt.dims[r] = options->dims[r];
-    }
-    opt.voxel_size = options->voxel_size;
-    opt.trunc = options->trunc;
     TsdfGrid G;
     int rc;
-    if ((rc = check_grid("smvs_tsdf_volume_create", opt, 0, 1024, G)))
+    if ((rc = check_volume_grid("smvs_tsdf_volume_create", *options, 1024, G)))
         return rc;
     size_t const n_vox = (size_t)G.nx * G.ny * G.nz;
     SMVS_REQUIRE(n_vox <= TSDF_MAX_VOXELS, "the volume has more than 2^27 voxels");
@@ -200,23 +189,13 @@ smvs_tsdf_volume_integrate(smvs_tsdf_volume *volume, const smvs_point_view *view
     if (lease.w == nullptr)
         return SMVS_ERR_HIP;
     Workspace &ws = *lease.w;
-    Carver carve;
-    ViewSlab s;
-    carve_views(views, n_views, true, carve, s);
-    size_t const images_at = carve(sizeof(TsdfImageDev) * n_views);
-    char *slab = nullptr;
-    if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
+    ViewStage stage;
+    if ((rc = stage(ws, views, n_views, cut_surfaces != 0, true, [](Carver &) {})))
         return rc;
-    TsdfImageDev *d_images = nullptr;
-    if ((rc = upload_and_prepare(ws, slab, views, n_views, cut_surfaces != 0, true, s))
-        || (rc = upload_image_table(ws, slab, images_at, views, s, &d_images)))
-        return rc;
-    launch_depth(ws.stream, s, n_views);
-    unsigned const bricks = (unsigned)((G.nx + TSDF_BX - 1) / TSDF_BX)
-        * (unsigned)((G.ny + TSDF_BY - 1) / TSDF_BY)
-        * (unsigned)((G.nz + TSDF_BZ - 1) / TSDF_BZ);
+    size_t n_bricks;
+    unsigned const bricks = brick_grid(G, &n_bricks).n;
     hipLaunchKernelGGL(tsdf_volume_integrate_kernel, dim3(bricks), dim3(256), 0, ws.stream,
-        s.d_table, d_images, G, volume->S, volume->W, volume->colour);
+        stage.s.d_table, stage.d_images, G, volume->S, volume->W, volume->colour);
     SMVS_HIP_CHECK(hipGetLastError());
     SMVS_HIP_CHECK(hipStreamSynchronize(ws.stream));
     volume->n_views += n_views;
@@ -260,12 +239,7 @@ smvs_tsdf_volume_extract(const smvs_tsdf_volume *volume, int min_weight, float *
         return rc;
     }
     // (fill_points has drained the stream)
-    *handle = h;
-    if (n_vertices != nullptr)
-        *n_vertices = h->n_points;
-    if (n_faces != nullptr)
-        *n_faces = h->n_faces;
-    return SMVS_OK;
+    return publish(h, handle, n_vertices, n_faces);
 }
 
 extern "C" int

@@ -175,15 +175,6 @@ using namespace smvs_hip::tsdf_host;
 
 namespace {
 
-constexpr size_t DENSE_MAX_VOXELS = (size_t)1 << 27;       // smvs_tsdf_fuse's limit
-constexpr size_t MAX_BRICKS_GRID = (size_t)1 << 28;
-constexpr int64_t DEFAULT_MAX_BRICKS = (int64_t)1 << 20;
-constexpr int64_t MAX_MAX_BRICKS = (int64_t)1 << 23;       // vertex ids are 32 bits
-constexpr int64_t STATE_BYTES_PER_BRICK = 256 * 24;
-// 255 * n_views must fit uint32 (the colour sums), 8 * n_views an int (the
-// confidence's divisor)
-constexpr int64_t VOLUME_MAX_VIEWS = (int64_t)1 << 24;
-
 // the planes of n slots
 struct Planes {
     uint32_t *list = nullptr, *birth = nullptr;
@@ -278,7 +269,7 @@ int
 over_budget(const char *who, size_t need, int64_t max_bricks)
 {
     set_error("%s: the surface needs %lld bricks (%lld bytes of state), max_bricks is %lld", who,
-        (long long)need, (long long)need * (long long)STATE_BYTES_PER_BRICK,
+        (long long)need, (long long)need * (long long)VOLUME_STATE_BYTES_PER_BRICK,
         (long long)max_bricks);
     return SMVS_ERR_NOMEM;
 }
@@ -301,61 +292,36 @@ run(const char *who, smvs_tsdf_sparse_volume &vol, const smvs_point_view *views,
         return SMVS_ERR_HIP;
     Workspace &ws = *lease.w;
     hipStream_t const stream = ws.stream;
-    Carver carve;
-    ViewSlab s;
-    PyramidSlab pyr;
-    carve_views(views, n_views, integrate, carve, s);
-    size_t const images_at = integrate ? carve(sizeof(TsdfImageDev) * n_views) : 0;
-    unsigned const brick_blocks = (unsigned)((n_bricks + 255) / 256);
-    size_t const brick_tiles = ((size_t)brick_blocks + SCAN_TILE - 1) / SCAN_TILE;
     // (the table's place holds the cull's candidate list first, as in the one-shot entry)
-    size_t const seed_at = carve(n_bricks), state_at = carve(n_bricks),
-        table_at = carve(4 * n_bricks), bcounts_at = carve(8 * (size_t)brick_blocks),
-        btiles_at = carve(8 * (brick_tiles + 1));
-    size_t cand_at = 0;
-    bool const culled = mark && cull;
-    if (culled) {
-        carve_pyramids(views, n_views, carve, pyr);
-        cand_at = carve(n_bricks);
-    }
-    char *slab = nullptr;
-    if ((rc = ws.ensure(0, carve.total, &slab)) != SMVS_OK)
+    ViewStage stage;
+    BrickWork w;
+    if ((rc = stage(ws, views, n_views, cut, integrate,
+            [&](Carver &carve) { w.carve(views, n_views, n_bricks, mark && cull, carve); })))
         return rc;
-    TsdfImageDev *d_images = nullptr;
-    if ((rc = upload_and_prepare(ws, slab, views, n_views, cut, integrate, s))
-        || (integrate && (rc = upload_image_table(ws, slab, images_at, views, s, &d_images))))
-        return rc;
-    uint8_t *d_seed = reinterpret_cast<uint8_t *>(slab + seed_at);
-    uint8_t *d_state = reinterpret_cast<uint8_t *>(slab + state_at);
-    int32_t *d_table = reinterpret_cast<int32_t *>(slab + table_at);
-    unsigned long long *d_bcounts = reinterpret_cast<unsigned long long *>(slab + bcounts_at);
-    unsigned long long *d_btiles = reinterpret_cast<unsigned long long *>(slab + btiles_at);
-    launch_depth(stream, s, n_views);
+    ViewSlab const &s = stage.s;
+    w.place(stage.slab);
 
     // the would-be seeds, their dilation and its count
     const uint8_t *d_seeds_now = vol.seed;
     size_t n_seeds = vol.n_seeds, n_dilated = vol.n_dilated;
     if (mark) {
         size_t n_tested;
-        if ((rc = launch_seeds(ws, slab, s, n_views, culled ? &pyr : nullptr, G, B,
-                culled ? reinterpret_cast<uint8_t *>(slab + cand_at) : nullptr,
-                reinterpret_cast<uint32_t *>(d_table), d_bcounts, d_btiles, d_seed, nullptr,
-                &n_tested)))
+        if ((rc = launch_seeds(ws, stage.slab, s, n_views, G, B, w, nullptr, &n_tested)))
             return rc;
         size_t const n_words = (n_bricks + 3) / 4;
         hipLaunchKernelGGL(tsdf_sparse_volume_merge_kernel, dim3((unsigned)((n_words + 255) / 256)),
             dim3(256), 0, stream, reinterpret_cast<const uint32_t *>(vol.seed), n_words,
-            reinterpret_cast<uint32_t *>(d_seed));
-        d_seeds_now = d_seed;
+            reinterpret_cast<uint32_t *>(w.seed));
+        d_seeds_now = w.seed;
     }
     bool const reslot_may_be_needed = integrate && (mark || vol.n_dilated > vol.n_slots);
     if (mark || reslot_may_be_needed) {
-        launch_dilate(stream, d_seeds_now, B, d_state, d_bcounts);
+        launch_dilate(stream, d_seeds_now, B, w.state, w.counts);
         SMVS_HIP_CHECK(hipGetLastError());
-        if ((rc = exclusive_scan(stream, d_bcounts, brick_blocks, d_btiles)))
+        if ((rc = exclusive_scan(stream, w.counts, w.blocks, w.tiles)))
             return rc;
         unsigned long long sums = 0;
-        if ((rc = ws.download(&sums, d_btiles + brick_tiles, sizeof(sums))))
+        if ((rc = ws.download(&sums, scan_total(w.tiles, w.blocks), sizeof(sums))))
             return rc;
         n_dilated = (size_t)(sums & 0xffffffffull);
         n_seeds = (size_t)(sums >> 32);
@@ -368,7 +334,7 @@ run(const char *who, smvs_tsdf_sparse_volume &vol, const smvs_point_view *views,
         Planes fresh;
         if ((rc = alloc_planes(n_dilated, fresh)))
             return rc;
-        launch_table(stream, d_state, B, d_bcounts, d_table, fresh.list);
+        launch_table(stream, w.state, B, w.counts, w.table, fresh.list);
         hipLaunchKernelGGL(tsdf_sparse_volume_reslot_kernel, dim3((unsigned)n_dilated), dim3(256),
             0, stream, fresh.list, vol.table, vol.S, vol.W, vol.colour, vol.birth,
             (uint32_t)vol.n_views, fresh.S, fresh.W, fresh.colour, fresh.birth);
@@ -377,7 +343,7 @@ run(const char *who, smvs_tsdf_sparse_volume &vol, const smvs_point_view *views,
             err = hipStreamSynchronize(stream);
         // (the old table was read to the end: the new one takes its place)
         if (err == hipSuccess)
-            err = hipMemcpyAsync(vol.table, d_table, 4 * n_bricks, hipMemcpyDeviceToDevice, stream);
+            err = hipMemcpyAsync(vol.table, w.table, 4 * n_bricks, hipMemcpyDeviceToDevice, stream);
         if (err == hipSuccess)
             err = hipStreamSynchronize(stream);
         if (err != hipSuccess) {
@@ -390,13 +356,14 @@ run(const char *who, smvs_tsdf_sparse_volume &vol, const smvs_point_view *views,
         adopt_planes(vol, fresh, n_dilated);      // frees the old planes
     }
     if (mark) {
-        SMVS_HIP_CHECK(hipMemcpyAsync(vol.seed, d_seed, n_bricks, hipMemcpyDeviceToDevice, stream));
+        SMVS_HIP_CHECK(hipMemcpyAsync(vol.seed, w.seed, n_bricks, hipMemcpyDeviceToDevice, stream));
         vol.n_seeds = n_seeds;
         vol.n_dilated = n_dilated;
     }
     if (integrate && vol.n_slots > 0) {
         hipLaunchKernelGGL(tsdf_sparse_volume_integrate_kernel, dim3((unsigned)vol.n_slots),
-            dim3(256), 0, stream, s.d_table, d_images, G, B, vol.list, vol.S, vol.W, vol.colour);
+            dim3(256), 0, stream, s.d_table, stage.d_images, G, B, vol.list, vol.S, vol.W,
+            vol.colour);
         SMVS_HIP_CHECK(hipGetLastError());
     }
     SMVS_HIP_CHECK(hipStreamSynchronize(stream));
@@ -414,16 +381,9 @@ smvs_tsdf_sparse_volume_create(int device, const smvs_tsdf_sparse_volume_options
     SMVS_REQUIRE(volume != nullptr, "no volume pointer");
     *volume = nullptr;
     SMVS_REQUIRE(options != nullptr, "no options");
-    smvs_tsdf_options opt = {};
-    for (int r = 0; r < 3; ++r) {
-        opt.origin[r] = options->origin[r];
-        opt.dims[r] = options->dims[r];
-    }
-    opt.voxel_size = options->voxel_size;
-    opt.trunc = options->trunc;
     TsdfGrid G;
     int rc;
-    if ((rc = check_grid("smvs_tsdf_sparse_volume_create", opt, 0, 4096, G)))
+    if ((rc = check_volume_grid("smvs_tsdf_sparse_volume_create", *options, 4096, G)))
         return rc;
     size_t n_bricks;
     TsdfBricks const B = brick_grid(G, &n_bricks);
@@ -495,7 +455,7 @@ smvs_tsdf_sparse_volume_extract(const smvs_tsdf_sparse_volume *volume, int min_w
     G.min_weight = min_weight > 0 ? (uint32_t)min_weight : 1u;
     G.n_views = (int)volume->n_views;
     size_t const n_vox = (size_t)G.nx * G.ny * G.nz;
-    SMVS_REQUIRE((tsdf == nullptr && weight == nullptr) || n_vox <= DENSE_MAX_VOXELS,
+    SMVS_REQUIRE((tsdf == nullptr && weight == nullptr) || n_vox <= TSDF_MAX_VOXELS,
         "tsdf / weight are given only for grids of at most 2^27 voxels");
     size_t const n_bricks = volume->n_bricks, n_slots = volume->n_slots;
 
@@ -528,12 +488,7 @@ smvs_tsdf_sparse_volume_extract(const smvs_tsdf_sparse_volume *volume, int min_w
             d_tsdf, volume->W, volume->colour, volume->table, volume->list, tsdf, weight, &h)))
         return rc;
     // (fill_points has drained the stream)
-    *handle = h;
-    if (n_vertices != nullptr)
-        *n_vertices = h->n_points;
-    if (n_faces != nullptr)
-        *n_faces = h->n_faces;
-    return SMVS_OK;
+    return publish(h, handle, n_vertices, n_faces);
 }
 
 extern "C" int
@@ -549,7 +504,7 @@ smvs_tsdf_sparse_volume_info(const smvs_tsdf_sparse_volume *volume,
         stats->allocated_bricks = (int64_t)volume->n_slots;
         stats->pending_bricks = (int64_t)(volume->n_dilated - volume->n_slots);
         stats->late_bricks = (int64_t)volume->n_late;
-        stats->state_bytes = (int64_t)volume->n_slots * STATE_BYTES_PER_BRICK;
+        stats->state_bytes = (int64_t)volume->n_slots * VOLUME_STATE_BYTES_PER_BRICK;
         stats->n_views = volume->n_views;
     }
     if (device != nullptr)

@@ -1322,6 +1322,25 @@ def generate_points(cams, depths, normals, images, cut=True, aabb=None, faces=Fa
     return out
 
 
+def _download_mesh(lib, handle, n_vertices, n_faces, cells=False):
+    """The mesh behind `handle` as the dict generate_mesh returns (cells: with
+    smvs_tsdf_vertex_cells' per-vertex cells); the handle is released."""
+    try:
+        k = n_vertices
+        out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
+               "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
+               "faces": np.zeros((n_faces, 3), np.uint32)}
+        check(lib.smvs_points_download(handle, _p(out["xyz"], _fp), _p(out["normals"], _fp),
+                                       _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
+                                       None, _p(out["faces"], _u32p)))
+        if cells:
+            out["cells"] = np.zeros(k, np.int64)
+            check(lib.smvs_tsdf_vertex_cells(handle, _p(out["cells"], C.POINTER(C.c_int64))))
+    finally:
+        lib.smvs_points_release(handle)
+    return out
+
+
 class MeshOptions(C.Structure):
     """smvs_mesh_options of include/smvs_hip.h."""
     _fields_ = [("cut_surfaces", C.c_int), ("use_aabb", C.c_int),
@@ -1353,16 +1372,7 @@ def generate_mesh(cams, depths, normals, images, cut=True, aabb=None, dd_factor=
     n_vertices, n_faces = C.c_int64(), C.c_int64()
     check(lib.smvs_mesh_generate(device, arr if n else None, n, C.byref(opt),
                                  C.byref(handle), C.byref(n_vertices), C.byref(n_faces)))
-    try:
-        k = n_vertices.value
-        out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
-               "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
-               "faces": np.zeros((n_faces.value, 3), np.uint32)}
-        check(lib.smvs_points_download(handle, _p(out["xyz"], _fp), _p(out["normals"], _fp),
-                                       _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
-                                       None, _p(out["faces"], _u32p)))
-    finally:
-        lib.smvs_points_release(handle)
+    out = _download_mesh(lib, handle, n_vertices.value, n_faces.value)
     if cut_maps:
         out["cut_depth"] = cuts
     return out
@@ -1384,6 +1394,29 @@ def _tsdf_views(cams, depths, normals, images):
         for i in range(n):
             arr[i].normals = None
     return arr, keep
+
+
+def _fill_grid(opt, origin, voxel_size, dims, trunc):
+    """the grid members every options record of the fusion has"""
+    for k in range(3):
+        opt.origin[k] = float(origin[k])
+        opt.dims[k] = int(dims[k])
+    opt.voxel_size = float(voxel_size)
+    opt.trunc = float(trunc)
+    return opt
+
+
+def _tsdf_options(origin, voxel_size, dims, trunc, cut, min_weight=0):
+    opt = _fill_grid(_capi.TsdfOptions(), origin, voxel_size, dims, trunc)
+    opt.cut_surfaces = int(bool(cut))
+    opt.min_weight = int(min_weight)
+    return opt
+
+
+def _brick_shape(dims):
+    """(bz, by, bx): the 8 x 8 x 4 bricks of a grid of dims = (nx, ny, nz)"""
+    nx, ny, nz = (max(int(d), 0) for d in dims[:3])
+    return (-(-nz // 4), -(-ny // 8), -(-nx // 8))
 
 
 def tsdf_bounds(cams, depths, normals, cut=True, device=0):
@@ -1437,14 +1470,7 @@ def fuse_tsdf(cams, depths, normals, images, origin, voxel_size, dims, trunc=0, 
     lib = _capi.load()
     n = len(cams)
     arr, _keep = _tsdf_views(cams, depths, normals, images)
-    opt = _capi.TsdfOptions()
-    opt.cut_surfaces = int(bool(cut))
-    for k in range(3):
-        opt.origin[k] = float(origin[k])
-        opt.dims[k] = int(dims[k])
-    opt.voxel_size = float(voxel_size)
-    opt.trunc = float(trunc)
-    opt.min_weight = int(min_weight)
+    opt = _tsdf_options(origin, voxel_size, dims, trunc, cut, min_weight)
     tsdf = weight = None
     if volume:
         shape = tuple(max(int(d), 0) for d in dims)[::-1]
@@ -1455,16 +1481,7 @@ def fuse_tsdf(cams, depths, normals, images, origin, voxel_size, dims, trunc=0, 
     check(lib.smvs_tsdf_fuse(device, arr if n else None, n, C.byref(opt), _p(tsdf, _fp),
                              _p(weight, _u32p), C.byref(handle), C.byref(n_vertices),
                              C.byref(n_faces)))
-    try:
-        k = n_vertices.value
-        out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
-               "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
-               "faces": np.zeros((n_faces.value, 3), np.uint32)}
-        check(lib.smvs_points_download(handle, _p(out["xyz"], _fp), _p(out["normals"], _fp),
-                                       _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
-                                       None, _p(out["faces"], _u32p)))
-    finally:
-        lib.smvs_points_release(handle)
+    out = _download_mesh(lib, handle, n_vertices.value, n_faces.value)
     if volume:
         out["tsdf"] = tsdf
         out["weight"] = weight
@@ -1478,16 +1495,9 @@ def _fuse_tsdf_sparse(cams, depths, normals, images, origin, voxel_size, dims, t
     lib = _capi.load()
     n = len(cams)
     arr, _keep = _tsdf_views(cams, depths, normals, images)
-    opt = _capi.TsdfOptions()
-    opt.cut_surfaces = int(bool(cut))
-    for k in range(3):
-        opt.origin[k] = float(origin[k])
-        opt.dims[k] = int(dims[k])
-    opt.voxel_size = float(voxel_size)
-    opt.trunc = float(trunc)
-    opt.min_weight = int(min_weight)
+    opt = _tsdf_options(origin, voxel_size, dims, trunc, cut, min_weight)
     shape = tuple(max(int(d), 0) for d in dims)[::-1]
-    bricks = (-(-shape[0] // 4), -(-shape[1] // 8), -(-shape[2] // 8))
+    bricks = _brick_shape(dims)
     tsdf = weight = state = candidate = None
     if volume:
         tsdf = np.zeros(shape, np.float32)
@@ -1523,19 +1533,7 @@ def _fuse_tsdf_sparse(cams, depths, normals, images, origin, voxel_size, dims, t
             if brick_candidate:
                 err.brick_candidate = candidate
         raise err
-    try:
-        k = n_vertices.value
-        out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
-               "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
-               "faces": np.zeros((n_faces.value, 3), np.uint32),
-               "cells": np.zeros(k, np.int64)}
-        check(lib.smvs_points_download(handle, _p(out["xyz"], _fp), _p(out["normals"], _fp),
-                                       _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
-                                       None, _p(out["faces"], _u32p)))
-        check(lib.smvs_tsdf_vertex_cells(handle, out["cells"].ctypes.data_as(
-            C.POINTER(C.c_int64))))
-    finally:
-        lib.smvs_points_release(handle)
+    out = _download_mesh(lib, handle, n_vertices.value, n_faces.value, cells=True)
     out["stats"] = stats.as_dict()
     if volume:
         out["tsdf"] = tsdf
@@ -1547,7 +1545,36 @@ def _fuse_tsdf_sparse(cams, depths, normals, images, origin, voxel_size, dims, t
     return out
 
 
-class TsdfVolume:
+class _VolumeHandle:
+    """What TsdfVolume and SparseTsdfVolume share: the handle of a persistent
+    volume (set by the class's __init__, released through the entry `_release`
+    names) as a context manager."""
+    _release = None
+    _handle = None
+
+    def _open(self):
+        if self._handle is None:
+            raise ValueError("%s: the volume is closed" % type(self).__name__)
+        return self._handle
+
+    def close(self):
+        if self._handle is not None:
+            getattr(self._lib, self._release)(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        self._open()
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        self.close()
+
+
+class TsdfVolume(_VolumeHandle):
     """smvs_tsdf_volume: the sums of fuse_tsdf's field kept on the device, so
     that the views are fused batch by batch (the
     definition is in include/smvs_hip.h).  The grid is fuse_tsdf's (origin,
@@ -1556,24 +1583,16 @@ class TsdfVolume:
     fuse_tsdf's arrays to the bit; the cut, when on, acts within a batch.  A
     context manager; after close() every method raises ValueError."""
 
+    _release = "smvs_tsdf_volume_release"
+
     def __init__(self, origin, voxel_size, dims, trunc=0, device=0):
         self._handle = None
         self._lib = _capi.load()
-        opt = _capi.TsdfVolumeOptions()
-        for k in range(3):
-            opt.origin[k] = float(origin[k])
-            opt.dims[k] = int(dims[k])
-        opt.voxel_size = float(voxel_size)
-        opt.trunc = float(trunc)
+        opt = _fill_grid(_capi.TsdfVolumeOptions(), origin, voxel_size, dims, trunc)
         handle = C.c_void_p()
         check(self._lib.smvs_tsdf_volume_create(int(device), C.byref(opt), C.byref(handle)))
         self._handle = handle
         self._shape = tuple(int(d) for d in dims)[::-1]
-
-    def _open(self):
-        if self._handle is None:
-            raise ValueError("TsdfVolume: the volume is closed")
-        return self._handle
 
     def integrate(self, cams, depths, normals, images, cut=True):
         """smvs_tsdf_volume_integrate: one batch, inputs as fuse_tsdf's (normals
@@ -1598,16 +1617,7 @@ class TsdfVolume:
         check(lib.smvs_tsdf_volume_extract(handle, int(min_weight), _p(tsdf, _fp),
                                            _p(weight, _u32p), C.byref(mesh),
                                            C.byref(n_vertices), C.byref(n_faces)))
-        try:
-            k = n_vertices.value
-            out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
-                   "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
-                   "faces": np.zeros((n_faces.value, 3), np.uint32)}
-            check(lib.smvs_points_download(mesh, _p(out["xyz"], _fp), _p(out["normals"], _fp),
-                                           _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
-                                           None, _p(out["faces"], _u32p)))
-        finally:
-            lib.smvs_points_release(mesh)
+        out = _download_mesh(lib, mesh, n_vertices.value, n_faces.value)
         if volume:
             out["tsdf"] = tsdf
             out["weight"] = weight
@@ -1646,24 +1656,8 @@ class TsdfVolume:
         handle = self._open()
         check(self._lib.smvs_tsdf_volume_reset(handle))
 
-    def close(self):
-        if self._handle is not None:
-            self._lib.smvs_tsdf_volume_release(self._handle)
-            self._handle = None
 
-    def __enter__(self):
-        self._open()
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        self.close()
-
-
-class SparseTsdfVolume:
+class SparseTsdfVolume(_VolumeHandle):
     """smvs_tsdf_sparse_volume: the sums of fuse_tsdf(sparse=True) kept on the
     device in 8 x 8 x 4 bricks, so that a grid of up to 4096 voxels per side is
     fused batch by batch (the definition is in
@@ -1675,28 +1669,19 @@ class SparseTsdfVolume:
     an SmvsError of status -4 names the bricks needed and changes nothing.  A
     context manager; after close() every method raises ValueError."""
 
+    _release = "smvs_tsdf_sparse_volume_release"
+
     def __init__(self, origin, voxel_size, dims, trunc=0, max_bricks=0, device=0):
         self._handle = None
         self._lib = _capi.load()
-        opt = _capi.TsdfSparseVolumeOptions()
-        for k in range(3):
-            opt.origin[k] = float(origin[k])
-            opt.dims[k] = int(dims[k])
-        opt.voxel_size = float(voxel_size)
-        opt.trunc = float(trunc)
+        opt = _fill_grid(_capi.TsdfSparseVolumeOptions(), origin, voxel_size, dims, trunc)
         opt.max_bricks = int(max_bricks)
         handle = C.c_void_p()
         check(self._lib.smvs_tsdf_sparse_volume_create(int(device), C.byref(opt),
                                                        C.byref(handle)))
         self._handle = handle
         self._shape = tuple(int(d) for d in dims)[::-1]
-        self._bricks = (-(-self._shape[0] // 4), -(-self._shape[1] // 8),
-                        -(-self._shape[2] // 8))
-
-    def _open(self):
-        if self._handle is None:
-            raise ValueError("SparseTsdfVolume: the volume is closed")
-        return self._handle
+        self._bricks = _brick_shape(dims)
 
     def mark(self, cams, depths, normals, cut=True, cull=False):
         """smvs_tsdf_sparse_volume_mark: the batch's seed bricks join the
@@ -1734,19 +1719,7 @@ class SparseTsdfVolume:
                                                   _p(tsdf, _fp), _p(weight, _u32p),
                                                   C.byref(mesh), C.byref(n_vertices),
                                                   C.byref(n_faces)))
-        try:
-            k = n_vertices.value
-            out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
-                   "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
-                   "faces": np.zeros((n_faces.value, 3), np.uint32),
-                   "cells": np.zeros(k, np.int64)}
-            check(lib.smvs_points_download(mesh, _p(out["xyz"], _fp), _p(out["normals"], _fp),
-                                           _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
-                                           None, _p(out["faces"], _u32p)))
-            check(lib.smvs_tsdf_vertex_cells(mesh, out["cells"].ctypes.data_as(
-                C.POINTER(C.c_int64))))
-        finally:
-            lib.smvs_points_release(mesh)
+        out = _download_mesh(lib, mesh, n_vertices.value, n_faces.value, cells=True)
         out["stats"] = self.stats()
         if volume:
             out["tsdf"] = tsdf
@@ -1809,33 +1782,6 @@ class SparseTsdfVolume:
         handle = self._open()
         check(self._lib.smvs_tsdf_sparse_volume_reset(handle))
 
-    def close(self):
-        if self._handle is not None:
-            self._lib.smvs_tsdf_sparse_volume_release(self._handle)
-            self._handle = None
-
-    def __enter__(self):
-        self._open()
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        self.close()
-
-
-def _tsdf_options(origin, voxel_size, dims, trunc, cut):
-    opt = _capi.TsdfOptions()
-    opt.cut_surfaces = int(bool(cut))
-    for k in range(3):
-        opt.origin[k] = float(origin[k])
-        opt.dims[k] = int(dims[k])
-    opt.voxel_size = float(voxel_size)
-    opt.trunc = float(trunc)
-    return opt
-
 
 def tsdf_brick_cull(cams, depths, normals, origin, voxel_size, dims, trunc=0, cut=True,
                     device=0):
@@ -1848,8 +1794,7 @@ def tsdf_brick_cull(cams, depths, normals, origin, voxel_size, dims, trunc=0, cu
     n = len(cams)
     arr, _keep = _tsdf_views(cams, depths, normals, None)
     opt = _tsdf_options(origin, voxel_size, dims, trunc, cut)
-    shape = tuple(max(int(d), 0) for d in dims)[::-1]
-    out = np.zeros((-(-shape[0] // 4), -(-shape[1] // 8), -(-shape[2] // 8)), np.uint8)
+    out = np.zeros(_brick_shape(dims), np.uint8)
     check(lib.smvs_tsdf_brick_cull(device, arr if n else None, n, C.byref(opt), _p(out, _u8p),
                                    None))
     return out
@@ -1938,19 +1883,7 @@ def clean_mesh(mesh, threshold=0.0, percentile=0.0, component_size=1000, keep_un
                               C.byref(opt), _p(comp, _u32p), _p(size, _u32p), _p(new_id, i64p),
                               C.byref(stats), C.byref(handle), C.byref(n_vertices),
                               C.byref(n_faces)))
-    try:
-        k = n_vertices.value
-        out = {"xyz": np.zeros((k, 3), np.float32), "normals": np.zeros((k, 3), np.float32),
-               "rgb": np.zeros((k, 3), np.uint8), "confidence": np.zeros(k, np.float32),
-               "faces": np.zeros((n_faces.value, 3), np.uint32)}
-        check(lib.smvs_points_download(handle, _p(out["xyz"], _fp), _p(out["normals"], _fp),
-                                       _p(out["rgb"], _u8p), _p(out["confidence"], _fp),
-                                       None, _p(out["faces"], _u32p)))
-        if cells is not None:
-            out["cells"] = np.zeros(k, np.int64)
-            check(lib.smvs_tsdf_vertex_cells(handle, _p(out["cells"], i64p)))
-    finally:
-        lib.smvs_points_release(handle)
+    out = _download_mesh(lib, handle, n_vertices.value, n_faces.value, cells=cells is not None)
     out["stats"] = stats.as_dict()
     if labels:
         out["component"], out["component_size"], out["new_id"] = comp, size, new_id

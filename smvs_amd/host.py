@@ -1032,6 +1032,22 @@ class FusedSparseBatchedSettings(C.Structure):
     _fields_ = FusedBatchedSettings._fields_ + [("sparse_batch_views", C.c_int)]
 
 
+# generate_fused: the record, the entry and whether it takes the clean's stats;
+# every record is the widest one cut to its field count
+_FUSED_ENTRIES = {
+    "dense": (FusedSettings, "smvs_host_generate_fused", False),
+    "sparse": (FusedSparseSettings, "smvs_host_generate_fused_sparse", False),
+    "sparse_cull": (FusedSparseCullSettings, "smvs_host_generate_fused_sparse_cull", False),
+    "clean": (FusedCleanSettings, "smvs_host_generate_fused_clean", True),
+    "batched": (FusedBatchedSettings, "smvs_host_generate_fused_batched", True),
+    "sparse_batched": (FusedSparseBatchedSettings, "smvs_host_generate_fused_sparse_batched",
+                       True),
+}
+# smvs_amd.clean_mesh's defaults
+_CLEAN_DEFAULTS = dict(threshold=0.0, percentile=0.0, component_size=1000,
+                       keep_unreferenced=False)
+
+
 def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=0, min_weight=0,
                    view_ids=None, image_embedding="undistorted", input_scale=0,
                    use_shading=False, cut=True, device=0, sparse=False, max_bricks=0,
@@ -1082,80 +1098,34 @@ def generate_fused(scene_dir, voxel_size=None, resolution=256, aabb=None, trunc=
     lib = load()
     st = _point_cloud_settings(image_embedding, input_scale, use_shading, cut, aabb, True,
                                False, device)
-    stats = None
     if clean is not None:
-        unknown = set(clean) - {"threshold", "percentile", "component_size", "keep_unreferenced"}
+        unknown = set(clean) - set(_CLEAN_DEFAULTS)
         if unknown:
             raise ValueError("clean: unknown option %s" % sorted(unknown))
-    if sparse_batch_views:
-        c = clean or {}
-        fs = FusedSparseBatchedSettings(
-            0.0 if voxel_size is None else float(voxel_size), int(resolution), float(trunc),
-            int(min_weight), int(max_bricks), int(bool(cull)), int(bool(sparse)),
-            float(c.get("threshold", 0.0)), float(c.get("percentile", 0.0)),
-            int(c.get("component_size", 1000)), int(bool(c.get("keep_unreferenced", False))),
-            int(clean is not None), int(batch_views), int(sparse_batch_views))
-        if clean is not None:
-            stats = _capi.MeshCleanStats()
-        sparse_batched = lib.smvs_host_generate_fused_sparse_batched
-
-        def entry(*args):
-            return sparse_batched(*args, C.byref(stats) if stats is not None else None)
-    elif batch_views:
-        if max_bricks and not sparse:
-            raise ValueError("max_bricks belongs to sparse=True")
-        c = clean or {}
-        fs = FusedBatchedSettings(0.0 if voxel_size is None else float(voxel_size),
-                                  int(resolution), float(trunc), int(min_weight),
-                                  int(max_bricks), int(bool(cull)), int(bool(sparse)),
-                                  float(c.get("threshold", 0.0)), float(c.get("percentile", 0.0)),
-                                  int(c.get("component_size", 1000)),
-                                  int(bool(c.get("keep_unreferenced", False))),
-                                  int(clean is not None), int(batch_views))
-        if clean is not None:
-            stats = _capi.MeshCleanStats()
-        batched = lib.smvs_host_generate_fused_batched
-
-        def entry(*args):
-            return batched(*args, C.byref(stats) if stats is not None else None)
-    elif clean is not None:
-        if max_bricks and not sparse:
-            raise ValueError("max_bricks belongs to sparse=True")
-        fs = FusedCleanSettings(0.0 if voxel_size is None else float(voxel_size),
-                                int(resolution), float(trunc), int(min_weight), int(max_bricks),
-                                int(bool(cull)), int(bool(sparse)),
-                                float(clean.get("threshold", 0.0)),
-                                float(clean.get("percentile", 0.0)),
-                                int(clean.get("component_size", 1000)),
-                                int(bool(clean.get("keep_unreferenced", False))))
-        stats = _capi.MeshCleanStats()
-        fn = lib.smvs_host_generate_fused_clean
-
-        def entry(*args):
-            return fn(*args, C.byref(stats))
-    elif sparse and cull:
-        fs = FusedSparseCullSettings(0.0 if voxel_size is None else float(voxel_size),
-                                     int(resolution), float(trunc), int(min_weight),
-                                     int(max_bricks), 1)
-        entry = lib.smvs_host_generate_fused_sparse_cull
-    elif sparse:
-        fs = FusedSparseSettings(0.0 if voxel_size is None else float(voxel_size),
-                                 int(resolution), float(trunc), int(min_weight), int(max_bricks))
-        entry = lib.smvs_host_generate_fused_sparse
-    else:
-        if max_bricks:
-            raise ValueError("max_bricks belongs to sparse=True")
-        fs = FusedSettings(0.0 if voxel_size is None else float(voxel_size), int(resolution),
-                           float(trunc), int(min_weight))
-        entry = lib.smvs_host_generate_fused
+    if max_bricks and not sparse:
+        raise ValueError("max_bricks belongs to sparse=True")
+    # the narrowest entry that states the request: it decides the error text
+    key = ("sparse_batched" if sparse_batch_views else "batched" if batch_views
+           else "clean" if clean is not None else "sparse_cull" if sparse and cull
+           else "sparse" if sparse else "dense")
+    record, name, takes_stats = _FUSED_ENTRIES[key]
+    c = dict(_CLEAN_DEFAULTS, **(clean or {}))
+    widest = (0.0 if voxel_size is None else float(voxel_size), int(resolution), float(trunc),
+              int(min_weight), int(max_bricks), int(bool(cull)), int(bool(sparse)),
+              float(c["threshold"]), float(c["percentile"]), int(c["component_size"]),
+              int(bool(c["keep_unreferenced"])), int(clean is not None), int(batch_views),
+              int(sparse_batch_views))
+    fs = record(*widest[:len(record._fields_)])
+    stats = _capi.MeshCleanStats() if clean is not None else None
+    tail = (C.byref(stats) if stats is not None else None,) if takes_stats else ()
     ids = None if view_ids is None else np.asarray(view_ids, dtype=np.int32)
     path = C.create_string_buffer(4096)
     nv, nf = C.c_int64(0), C.c_int64(0)
-    rc = entry(
+    rc = getattr(lib, name)(
         scene_dir.encode(), C.byref(st), C.byref(fs),
         ids.ctypes.data_as(_i32p) if ids is not None else None,
         C.c_int(0 if ids is None else ids.size), path, C.c_int(len(path)), C.byref(nv),
-        C.byref(nf))
+        C.byref(nf), *tail)
     if rc != 0:
         raise _capi.SmvsError(rc, lib.smvs_host_last_error().decode())
     if stats is not None:

@@ -541,3 +541,61 @@ def test_scene_sparse_batches_belong_to_the_sparse_volume(hip, scene):
     b = host.generate_fused(scene, resolution=64, input_scale=0, cut=True, sparse=True)
     with open(b[0], "rb") as f:
         assert f.read() == batched and a == b
+
+
+# ------------------------------- 18. the six C entries state the same request
+def test_a_wider_entry_with_the_narrower_options_unset_is_the_narrower_entry(hip, scene):
+    """The six smvs_host_generate_fused* entries through ctypes, with records
+    that state the same request: file name, counts, the clean's stats and the
+    file's bytes are equal within the dense group, the sparse group (the cull
+    changes no byte) and the clean group, dense and sparse."""
+    import ctypes as C
+    import os
+    from smvs_amd import _capi, host
+    lib = host.load()
+    records = dict(_fused=host.FusedSettings, _fused_sparse=host.FusedSparseSettings,
+                   _fused_sparse_cull=host.FusedSparseCullSettings,
+                   _fused_clean=host.FusedCleanSettings, _fused_batched=host.FusedBatchedSettings,
+                   _fused_sparse_batched=host.FusedSparseBatchedSettings)
+
+    def call(entry, cull=0, sparse=0, clean=0):
+        # (voxel_size, resolution, trunc, min_weight, max_bricks, cull, sparse, threshold,
+        # percentile, component_size, keep_unreferenced, clean, batch_views, sparse_batch_views)
+        widest = (0.05, 0, 0.0, 0, 0, cull, sparse, 0.0, 10.0 if clean else 0.0,
+                  50 if clean else 1000, 0, clean, 0, 0)
+        fs = records[entry](*widest[:len(records[entry]._fields_)])
+        st = host._point_cloud_settings("undistorted", 0, False, False, AABB, True, False, 0)
+        path = C.create_string_buffer(4096)
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        args = [scene.encode(), C.byref(st), C.byref(fs), None, C.c_int(0), path,
+                C.c_int(len(path)), C.byref(nv), C.byref(nf)]
+        stats = _capi.MeshCleanStats()
+        if entry in ("_fused_clean", "_fused_batched", "_fused_sparse_batched"):
+            args.append(C.byref(stats))
+        rc = getattr(lib, "smvs_host_generate" + entry)(*args)
+        assert rc == 0, (entry, lib.smvs_host_last_error().decode())
+        with open(path.value.decode(), "rb") as f:
+            data = f.read()
+        os.remove(path.value.decode())
+        return (os.path.basename(path.value.decode()), nv.value, nf.value, stats.as_dict(), data)
+
+    def all_equal(results, name):
+        assert results[0][0] == name and results[0][2] > 100 and len(results[0][4]) > 1000
+        for r in results[1:]:
+            assert r == results[0]
+        return results[0]
+
+    dense = all_equal([call("_fused"), call("_fused_batched"), call("_fused_sparse_batched")],
+                      "smvs-fused-B0.ply")
+    sparse = all_equal([call("_fused_sparse"), call("_fused_sparse_cull", cull=0),
+                        call("_fused_sparse_cull", cull=1), call("_fused_batched", sparse=1),
+                        call("_fused_sparse_batched", sparse=1)], "smvs-fused-B0.ply")
+    # the same mesh in another order (section 9.9), and no clean has counted
+    assert sparse[1:3] == dense[1:3] and sparse[4] != dense[4]
+    assert dense[3] == sparse[3] == _capi.MeshCleanStats().as_dict()
+    for s in (0, 1):
+        cleaned = all_equal([call("_fused_clean", sparse=s, clean=1),
+                             call("_fused_batched", sparse=s, clean=1),
+                             call("_fused_sparse_batched", sparse=s, clean=1)],
+                            "smvs-clean-B0.ply")
+        assert cleaned[3]["n_components"] >= 1 and 0 < cleaned[1] <= dense[1]
